@@ -3,8 +3,14 @@
 ray loop on the synthetic 100k-triangle scene at 1024x1024 (configs[2]; 256 spp = the
 default 8 steps x 32 frames).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`, ray counts,
+`primary_beams`, `distributed`).  --dump-outputs DIR writes the film the timed steps left (rank 0, after the reduce)
+to DIR/film_hdr.npy; the inputs are seeded, so two builds given the same arguments can be compared film for film.
+--full adds what follows the timed region below: build times, the film sampled against the CPU oracle,
+value_cold_256spp, the lists-off steps, `roofline`, `cpu_baseline` and `configs`.
 
 A "step" = one pass of the hot path over one batch of pixel-samples: `--frames-per-step`
 (default 32) consecutive frames of the full 1024^2 film, i.e. 33.5 M paths (one wavefront batch).  With N > 1 the
@@ -18,10 +24,10 @@ Timing: W untimed warm-up steps, then exactly K steps bracketed by barrier +
 torch.cuda.synchronize() + tirt_sync on both sides; MAX over ranks; rank 0 prints one JSON
 line.  Inputs (scene, BVH) are resident in HBM before the timed region; what belongs to the
 RENDER -- the camera rays' per-pixel candidate lists -- is forgotten when the clock starts and
-made again by the first timed batch (primary_beams.prepare_ms_in_timed_region).  N = 1 also
-prints value_cold_256spp: BASELINE config 3 as written (one camera set, 8 x 32 frames, sync).
+made again by the first timed batch (primary_beams.prepare_ms_in_timed_region).  With --full, N = 1
+also prints value_cold_256spp: BASELINE config 3 as written (one camera set, 8 x 32 frames, sync).
 
-Extra objects:
+Extra objects (--full):
   roofline      dominant kernel = the traversal kernel k_trace (closest hits of bounce b + NEE shadow
                 rays of bounce b-1 in one launch).  Three ceilings from MI355X_MICROARCH.md, each with the
                 kernel's measured use of it (four rocprofv3 --pmc passes this script runs itself on a child
@@ -91,6 +97,9 @@ def parse():
     ap.add_argument("--opt", action="append", default=[], help="name=value passed to tirt_set_option (tuning)")
     ap.add_argument("--keep-lists", action="store_true", help="internal (profiler children): do not rebuild the camera rays' candidate lists at the start of the timed region -- "
                                                               "their counters are those of a steady-state step, not of one step plus a list build")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure as well: build times, the film against the CPU oracle, value_cold_256spp, "
+                                                        "the lists-off steps, the roofline, cpu_baseline and the other configs (the --no-* options switch parts of it off)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the film the timed steps left to DIR/film_hdr.npy (float32; beyond 64 MB a fixed sample of its pixels)")
     return ap.parse_args()
 
 
@@ -544,6 +553,26 @@ def cpu_baseline(args, ex, W, H, build_ms):
     }
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, hdr, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the hdr film the timed steps left (what a caller of render_frames reads back) as out_dir/film_hdr.npy.  A film larger
+    than `limit` is cut to a fixed, seeded sample of its pixels: film_hdr_sample.npy [k, 3] float32 and film_hdr_sample_pixels.npy [k] float64
+    (their linear pixel indices), k as large as the limit allows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    hdr = np.ascontiguousarray(hdr, dtype=np.float32)
+    if hdr.nbytes <= limit:
+        np.save(os.path.join(out_dir, "film_hdr.npy"), hdr)
+        return
+    flat = hdr.reshape(-1, 3)
+    k = (limit - 4096) // (3 * 4 + 8)                   # (4096: the two .npy headers)
+    pix = np.sort(np.random.RandomState(0).choice(flat.shape[0], k, replace=False))
+    np.save(os.path.join(out_dir, "film_hdr_sample.npy"), flat[pix])
+    np.save(os.path.join(out_dir, "film_hdr_sample_pixels.npy"), pix.astype(np.float64))
+
+
 def _with_timeout(what, fn, seconds):
     """Runs fn() on a helper thread; if it has not returned after `seconds` the process reports why and exits (a stalled RCCL /
     process-group set-up would otherwise hang until the driver's own limit)."""
@@ -591,6 +620,8 @@ def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.configs_only:
         self_launch(args)
+    if not args.full:               # a plain run: set-up, warm-up, the timed steps, the result line
+        args.no_roofline = args.no_cpu_baseline = args.no_configs = True
     if args.no_roofline:            # the quick form every tool and test uses: headline number only
         args.no_configs = True
     if args.configs_only:                       # child of bdpt_roofline's profiler passes: one config, optional context options
@@ -656,15 +687,18 @@ def main():
     build_wall = time.time() - t0
     # build times (HIP events around the build on the context's stream), second build of each kind: the reference's LBVH alone
     # (Morton, sort, Karras, refit, flatten + the 4-wide collapse of it) and with the binned-SAH traversal tree in between
+    # (--full only: the scene's own build above is the one the timed steps use either way -- the loop's last build is of the same kind)
     tree_opt = int(float(opts.get("traversal_tree", "1")))
     build_detail = {}
-    for tree in (1 - tree_opt, tree_opt):
-        ctx.set_option("traversal_tree", tree)
-        ms = []
-        for _ in range(4):
-            ctx.lbvh_build(); ms.append(ctx.stats()["ms_build"])
-        build_ms = min(ms[1:])                         # (the first one allocates; an idle GPU clocks down between Python calls)
-        build_detail["with_sah_traversal_tree_ms" if tree else "lbvh_only_ms"] = round(build_ms, 3)
+    build_ms = None
+    if args.full:
+        for tree in (1 - tree_opt, tree_opt):
+            ctx.set_option("traversal_tree", tree)
+            ms = []
+            for _ in range(4):
+                ctx.lbvh_build(); ms.append(ctx.stats()["ms_build"])
+            build_ms = min(ms[1:])                         # (the first one allocates; an idle GPU clocks down between Python calls)
+            build_detail["with_sah_traversal_tree_ms" if tree else "lbvh_only_ms"] = round(build_ms, 3)
     fps = args.frames_per_step
 
     # what the example classes tell the library at set-up (Example.build_scene: their sample count): the frames of the job ahead -- it
@@ -760,10 +794,11 @@ def main():
         },
         "rays": {"closest": int(rays_closest), "shadow": int(rays_shadow), "paths": int(paths),
                  "rays_per_path": round((rays_closest + rays_shadow) / max(paths, 1.0), 3)},
-        "lbvh_build_ms": round(build_ms, 3),
-        "build_detail": build_detail,
         "scene_setup_wall_s": round(build_wall, 3),
     }
+    if args.full:
+        result["lbvh_build_ms"] = round(build_ms, 3)
+        result["build_detail"] = build_detail
     try:
         pb = ctx.primary_beam_stats()
         if pb["rays"]:
@@ -789,6 +824,10 @@ def main():
         ctx.film_import_device(film.data_ptr()) if world > 1 else None
         ctx.tone_map(0.5)
         write_png(ctx.film_download(W, H, want_hdr=False, want_rgb=True)[1], args.save_png)
+
+    # ---- what the timed steps computed (rank 0 holds the reduced film when N > 1), before the --full legs render more frames on this context
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx.film_download(W, H)[0])
 
     # ---- the headline film itself against the CPU oracle: 2048 pixels x every frame rendered so far (warm-up + timed), bit for bit; after the
     #      timed region, on rank 0 (whose context holds the reduced film when N > 1), before the roofline probes add frames -------------------

@@ -57,3 +57,23 @@ def test_gpus_n_without_a_launcher_starts_one_process_per_gpu(monkeypatch):
     assert os.path.samefile(cmd[cmd.index("--master-port") + 2], os.path.join(ROOT, "bench.py"))
     assert cmd[-6:] == ["--gpus", "4", "--steps", "2", "--warmup", "1"]
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_dump_outputs_whole_film_or_a_fixed_sample(tmp_path):
+    """--dump-outputs: a film within the limit is written whole; a larger one as the same seeded sample of its pixels every time, within the limit."""
+    import numpy as np
+    import bench
+    film = np.random.RandomState(5).rand(64, 48, 3).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), film)
+    got = np.load(str(tmp_path / "whole" / "film_hdr.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, film)
+    limit = 4096 + 1000 * 20
+    for tag in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / tag), film, limit=limit)
+    s1 = np.load(str(tmp_path / "s1" / "film_hdr_sample.npy"))
+    pix = np.load(str(tmp_path / "s1" / "film_hdr_sample_pixels.npy"))
+    assert s1.dtype == np.float32 and pix.dtype == np.float64 and s1.shape == (1000, 3) and pix.shape == (1000,)
+    assert np.array_equal(s1, film.reshape(-1, 3)[pix.astype(np.int64)])
+    assert np.array_equal(s1, np.load(str(tmp_path / "s2" / "film_hdr_sample.npy")))
+    assert sum(os.path.getsize(str(tmp_path / "s1" / f)) for f in os.listdir(str(tmp_path / "s1"))) <= limit
+    assert not os.path.exists(str(tmp_path / "s1" / "film_hdr.npy"))

@@ -64,9 +64,9 @@ def test_force_dist_one_rank_rccl(gpu_ctx_ok, tmp_path):
 
 def test_bench_line_carries_the_contract_fields(gpu_ctx_ok, tmp_path):
     """One JSON line, last on stdout, with the driver's fields, a `roofline` object measured in this run (HIP-event launch duration, rocprofv3 --pmc child
-    passes for the traffic) and a `cpu_baseline` object (the CPU oracle on a bounded sample); small sizes, same code path as the default run."""
+    passes for the traffic) and a `cpu_baseline` object (the CPU oracle on a bounded sample); small sizes, same code path as the --full run."""
     r = run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--frames-per-step", "16", "--size", "512", "--ntri", "20000",
-             "--no-configs", "--cpu-target-s", "1.5"], {}, tmp_path, "contract")
+             "--full", "--no-configs", "--cpu-target-s", "1.5"], {}, tmp_path, "contract")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
         assert k in r, k
     assert r["unit"] == "Mrays/s" and r["n_gpus"] == 1 and r["steps"] == 2 and r["dtype"] == "f32" and r["vs_baseline"] is None and "workload" in r["config"]
@@ -84,3 +84,22 @@ def test_bench_line_carries_the_contract_fields(gpu_ctx_ok, tmp_path):
     assert abs(roof["frac"] - roof["achieved"] / roof["peak"]) < 1e-3
     cb = r["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "sample" in cb
+
+
+def test_plain_run_is_the_headline_only_and_dumps_a_reproducible_film(gpu_ctx_ok, tmp_path):
+    """Without --full the line carries the headline and nothing measured beside it; --dump-outputs writes the film the timed steps left,
+    the same bits from run to run (seeded inputs), and --steps sets the number of timed steps."""
+    import numpy as np
+    common = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--frames-per-step", "4", "--size", "256", "--ntri", "20000"]
+    films = []
+    for tag in ("a", "b"):
+        r = run([sys.executable, "bench.py"] + common + ["--dump-outputs", str(tmp_path / tag)], {}, tmp_path, tag)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in r, k
+        assert r["steps"] == 3 and r["value"] > 0 and r["ms_per_step"] > 0 and r["unit"] == "Mrays/s"
+        assert r["rays"]["paths"] == 3 * 4 * 256 * 256
+        for k in ("roofline", "cpu_baseline", "configs", "value_cold_256spp", "oracle_sample_identical", "build_detail"):
+            assert k not in r, k
+        films.append(np.load(str(tmp_path / tag / "film_hdr.npy")))
+    assert films[0].dtype == np.float32 and films[0].shape == (256, 256, 3) and np.isfinite(films[0]).any() and films[0].any()
+    assert np.array_equal(films[0], films[1], equal_nan=True)

@@ -1,8 +1,9 @@
 # round-5 measurement set on the GPU box: bash tools/r05_final.sh <tag>  -> gpurun_out/<tag>_*
 R=$GRAFT_REPO_ROOT; T=${1:-r05z}; cd $R
+L=${LOG_DIR:-logs}; mkdir -p "$L"          # the logs of the bench.py --full runs
 timeout 1500 python -m pytest tests -q -m gpu > gpurun_out/${T}_pytest_gpu.log 2>&1; tail -1 gpurun_out/${T}_pytest_gpu.log
-timeout 900 python bench.py > gpurun_out/${T}_bench_default.json.log 2> gpurun_out/${T}_bench_default.err; tail -c 400 gpurun_out/${T}_bench_default.json.log; echo
-TIRT_FORCE_DIST=1 timeout 600 python bench.py --no-cpu-baseline --no-configs --no-traffic > gpurun_out/${T}_bench_force_dist_one_rank_rccl.json.log 2>&1
+timeout 900 python bench.py --full > "$L/${T}_bench_default.json.log" 2> "$L/${T}_bench_default.err"; tail -c 400 "$L/${T}_bench_default.json.log"; echo
+TIRT_FORCE_DIST=1 timeout 600 python bench.py --full --no-cpu-baseline --no-configs --no-traffic > "$L/${T}_bench_force_dist_one_rank_rccl.json.log" 2>&1
 for n in 1 2 4 8; do timeout 300 python bench.py --no-cpu-baseline --no-roofline --emulate-world $n 2>/dev/null | tail -1; done > gpurun_out/${T}_emulated_rank_scaling.log
 for s in 4 8 16 32; do timeout 300 python bench.py --no-cpu-baseline --no-roofline --emulate-world 8 --steps $s 2>/dev/null | tail -1; done > gpurun_out/${T}_emulated_8_ranks_steps_4_8_16_32.log
 for n in 1 2 4 8; do timeout 300 python bench.py --no-cpu-baseline --no-roofline --no-configs --steps 20 --warmup 5 --emulate-world $n 2>/dev/null | tail -1; done > gpurun_out/${T}_emulated_rank_scaling_driver_command_steps20.log
