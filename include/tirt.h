@@ -205,6 +205,21 @@ int tirt_spec_table_build(tirt_ctx *ctx, int res, const float *cie_xyz, const fl
 int tirt_spectral_upload(tirt_ctx *ctx, const tirt_spectral_t *tables);
 int tirt_pt_spec_render(tirt_ctx *ctx, uint32_t frame_begin, int frame_count, uint32_t seed, int max_depth, int stack_size, int flags);
 
+/* Debug.render (integrator/Debug.py:44-67): for every pixel of this context's tiles, the camera ray of `frame` (jittered iff
+ * frame != 0, the same ray as tirt_pt_rgb_render's at that frame and seed), its closest hit, and hdr[i, j] OVERWRITTEN with one
+ * view of that hit -- (0, 0, 0) on a miss, no running mean:
+ *   TIRT_DEBUG_ALBEDO   the material colour, words 2..4 (:65)
+ *   TIRT_DEBUG_FNORMAL  (faceforward(normal, -direction, gnormal) + 1) * 0.5 (:62)
+ *   TIRT_DEBUG_NORMAL   (normal + 1) * 0.5 (:63)
+ *   TIRT_DEBUG_GNORMAL  (gnormal + 1) * 0.5 (:64)
+ * Pixels of other ranks' tiles are left as they are.  flags: TIRT_TRAVERSE_EXHAUSTIVE, TIRT_COUNT_NODES; stack_size 1..4096.
+ * Asynchronous; the rays count in rays_closest, a traversal stack overflow is reported by tirt_stats (TIRT_ERR_STACK). */
+#define TIRT_DEBUG_ALBEDO 0
+#define TIRT_DEBUG_FNORMAL 1
+#define TIRT_DEBUG_NORMAL 2
+#define TIRT_DEBUG_GNORMAL 3
+int tirt_debug_render(tirt_ctx *ctx, uint32_t frame, uint32_t seed, int mode, int stack_size, int flags);
+
 /* UtilsFunc.tone_map(exposure, hdr, rgb_film) (UtilsFunc.py:583-586) */
 int tirt_tone_map(tirt_ctx *ctx, float exposure);
 /* field.to_numpy(): either pointer may be NULL */

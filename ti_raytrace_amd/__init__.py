@@ -1,7 +1,7 @@
 """ti_raytrace_amd -- MI355X-native path-tracing core behind the ti-raytrace Python API.
 
 Modules keep the reference's names: ``SceneData``, ``Scene``, ``Camera``, ``LBvh``,
-``PT_RGB``, ``UtilsFunc``, ``Texture``, ``Example`` (+ ``scenes`` with the example set-ups).
+``PT_RGB``, ``Debug``, ``UtilsFunc``, ``Texture``, ``Example`` (+ ``scenes`` with the example set-ups).
 The compute path is ``csrc/libtirt.so`` (hand-written HIP for gfx950) behind the C-ABI of
 ``include/tirt.h``; see DESIGN.md / INTEGRATION.md.
 """
@@ -15,6 +15,6 @@ import os as _os
 if _os.environ.get("TIRT_NO_ENV_TUNING", "0") in ("", "0"):
     _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
-from . import SceneData, UtilsFunc, Texture, Camera, LBvh, Scene, PT_RGB, BDPT_RGB, Example  # noqa: F401
+from . import SceneData, UtilsFunc, Texture, Camera, LBvh, Scene, PT_RGB, BDPT_RGB, Debug, Example  # noqa: F401
 
-__all__ = ["SceneData", "UtilsFunc", "Texture", "Camera", "LBvh", "Scene", "PT_RGB", "BDPT_RGB", "Example"]
+__all__ = ["SceneData", "UtilsFunc", "Texture", "Camera", "LBvh", "Scene", "PT_RGB", "BDPT_RGB", "Debug", "Example"]

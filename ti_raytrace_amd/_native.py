@@ -50,6 +50,12 @@ TRAVERSE_ORDERED = 0
 TRAVERSE_EXHAUSTIVE = 1
 COUNT_NODES = 2
 
+# tirt_debug_render modes (include/tirt.h): the views of integrator/Debug.py:62-65
+DEBUG_ALBEDO = 0
+DEBUG_FNORMAL = 1
+DEBUG_NORMAL = 2
+DEBUG_GNORMAL = 3
+
 # name -> (restype, argtypes).  tests/test_abi.py checks every name against include/tirt.h.
 _vp = C.c_void_p
 SIGNATURES = {
@@ -77,6 +83,7 @@ SIGNATURES = {
     "tirt_pt_rgb_render": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int]),
     "tirt_bdpt_rgb_render": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_uint32]),
     "tirt_bdpt_spec_render": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_uint32]),
+    "tirt_debug_render": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int]),
     "tirt_tone_map": (C.c_int, [_vp, C.c_float]),
     "tirt_film_download": (C.c_int, [_vp, _vp, _vp]),
     "tirt_film_export_device": (C.c_int, [_vp, _vp]),
@@ -323,6 +330,9 @@ class Context:
         for k in range(3):
             st.sun_dir[k] = t["sun_dir"][k]
         check(lib().tirt_spectral_upload(self.handle, C.byref(st)))
+
+    def debug_render(self, frame, seed, mode, stack_size=64, flags=0):
+        check(lib().tirt_debug_render(self.handle, int(frame), int(seed), int(mode), int(stack_size), int(flags)))
 
     def tone_map(self, exposure):
         check(lib().tirt_tone_map(self.handle, float(exposure)))

@@ -371,6 +371,7 @@ struct tirt_ctx {
 
     // batch trace scratch
     tirt::DevBuf tr_rays, tr_out, tr_prim, tr_counts;
+    tirt::DevBuf debug_mem;                       // Debug integrator (tirt_debug.hip): hit records + camera directions of the local pixels
 
     // RCCL communicator of tirt_comm_init (single-process multi-GPU film reduce; opaque ncclComm_t)
     void *comm = nullptr; int comm_rank = 0, comm_size = 0;
@@ -432,6 +433,8 @@ int bdpt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t see
 int trace_arrays(tirt_ctx *c, const float *ox, const float *oy, const float *oz, const float *dx, const float *dy, const float *dz,
                  int count, const int *count_ptr, float4 *hit, const int *expect, const float *bound, bool count_rays, int lane = -1,
                  const float4 *ray4 = nullptr, bool query = false, const int *ray_index = nullptr);      // (ray_index: TraceArgs) ray4: the rays as 32-byte records (TraceArgs::ray4); query: bounded queries whose expect / bound ride in the records
+int trace_camera(tirt_ctx *c, const float *dx, const float *dy, const float *dz, int count, float4 *hit, int stack_size, int flags);      // rays from the eye (Debug)
+int debug_render(tirt_ctx *c, uint32_t frame, uint32_t seed, int mode, int stack_size, int flags);      // tirt_debug.hip
 int pvb_prepare(tirt_ctx *c);                          // tirt_pvb.hip
 void pvb_launch_cand(tirt_ctx *c, hipStream_t st, const BvhView &bv, const float *dx, const float *dy, const float *dz, const TileMap &tm, int P, int S,
                      float4 *hit, int *fb_count, int *fb_slot, float *fb_dx, float *fb_dy, float *fb_dz, DevCounters *ctr);

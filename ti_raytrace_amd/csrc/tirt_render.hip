@@ -904,6 +904,32 @@ int trace_arrays(tirt_ctx *c, const float *ox, const float *oy, const float *oz,
     return (expect || query) ? launch_trace<KIND_QUERY>(c, st, a, 0, grid) : launch_trace<KIND_CLOSEST>(c, st, a, 0, grid);
 }
 
+// Closest hits of `count` camera rays that start at the eye (TraceArgs::eye, ox == nullptr), directions in device arrays, hit
+// records to `hit` -- the traversal of the Debug integrator (tirt_debug.hip).  On the main stream, with the caller's stack size and
+// traversal flags (ordered / exhaustive, node counts); the rays count as closest-hit rays.
+int trace_camera(tirt_ctx *c, const float *dx, const float *dy, const float *dz, int count, float4 *hit, int stack_size, int flags)
+{
+    if (count <= 0) return TIRT_OK;
+    hipStream_t st = c->stream;
+    int spill_depth;
+    if (ensure_spill(c, c->spill, stack_size, spill_depth)) return TIRT_ERR_HIP;
+    if (c->counters_mem.ensure(sizeof(int) * TR_FETCH_STRIDE * TR_FETCH_LINES)) return TIRT_ERR_HIP;
+    TIRT_HIP(hipMemsetAsync(c->counters_mem.p, 0, sizeof(int) * TR_FETCH_STRIDE * TR_FETCH_LINES, st));
+    TraceArgs a = {};
+    a.bvh = bvh_view(c);
+    a.ox = a.oy = a.oz = nullptr; for (int k = 0; k < 3; k++) a.eye[k] = c->cam.eye[k];
+    a.dx = dx; a.dy = dy; a.dz = dz;
+    a.count_ptr = nullptr; a.count_fixed = count; a.hit = hit;
+    a.spill = c->spill.as<int>(); a.spill_depth = spill_depth;
+    a.ctr = c->dev_counters.as<DevCounters>(); a.per_ray_counts = nullptr;
+    a.fetch = c->counters_mem.as<int>();
+    fill_tunables(c, a);
+    int grid = (count + TR_BLOCK - 1) / TR_BLOCK; if (grid > c->tr_grid_alone) grid = c->tr_grid_alone;
+    a.timeline = timeline_for(c, flags, grid);
+    c->launches_trace_closest++;
+    return launch_trace<KIND_CLOSEST>(c, st, a, flags, grid);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Wavefront PT_RGB
 // ---------------------------------------------------------------------------------------------

@@ -189,44 +189,15 @@ def kat_functions(out):
                camera_dir_frame0=rd0, camera_dir_jittered=rd1)
 
 
-# ---- the reference's whole integrator, executed from its source text ----------------------------------------------------------------
-# integrator/PT_RGB.py:49-136 (`render`) with everything it calls -- Camera.get_ray_direction, Scene.closet_hit / closet_hit_shadow /
-# intersect_prim / intersect_tri / sample_li / get_prim_random_point_normal / get_prim_area, Disney.*, Glass.*, UF.*, Texture.texture2D --
-# run as plain Python over a small film.  Two things are supplied from this repo, because the reference has no reproducible
-# equivalent: (1) ti.random() returns the counter-based tm_rand(seed, pixel, frame, dim) with the dimension decided by the CALL SITE
-# (which reference function drew it, the how-many-th draw of that activation, and the `depth` of the render loop: SURVEY A.6 / tirt_math.h
-# TM_DIM_* -- so the mapping "which random number feeds which decision" is pinned too); (2) sin / cos / exp / pow / atan2 / acos / sqrt
-# are the shared polynomial kernels (through the oracle library's orc_kat_math), so that a film that differs does so because of the
-# reference's formulas, not because of a different math library.  The scene arrays (vertex / primitive / material / shape / light rows,
-# the compact LBVH nodes -- pinned by nodelist.txt --, camera matrices) are put straight into the reference classes' fields.
-def render_reference_text(out, W, H, frames, seed, scene_name):
-    import ctypes as C
+# The example `scene_name` at W x H packed on the host, its OracleScene (LBVH built; smooth normals for "sphere"), and the reference's own
+# Camera / Scene objects (through the stand-in) with their fields filled from the same arrays -- the compact LBVH nodes from the oracle.
+def reference_scene(W, H, scene_name):
     sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
     import oracle_api as oa
     from common import host_only
     from ti_raytrace_amd import scenes
-    import Scene as RScene, PT_RGB as RPT, SceneData as RSCD       # the reference's modules (through the stand-in)
-    for _m in (RScene, RPT):
-        _m.pow = ti.pow_
-
-    L = oa.load()
-
-    def m1(fn):
-        def f(x):
-            xi = np.array([x], np.float32); o = np.zeros(1, np.float32)
-            L.orc_kat_math(fn, xi, np.zeros(1, np.float32), o, 1)
-            return o[0]
-        return f
-
-    def m2(fn):
-        def f(x, y):
-            o = np.zeros(1, np.float32)
-            L.orc_kat_math(fn, np.array([x], np.float32), np.array([y], np.float32), o, 1)
-            return o[0]
-        return f
-    ti.set_math({"sin": m1(0), "cos": m1(1), "exp": m1(2), "log": m1(3), "pow": m2(4), "atan2": m2(5), "acos": m1(6),
-                 "tan": lambda x: np.float32(m1(0)(x) / m1(1)(x))})                  # tirt_math.h: tm_tan = tm_sin / tm_cos
-
+    import Scene as RScene, SceneData as RSCD
+    RScene.pow = ti.pow_
     from common import cornell_glass_wall
     if scene_name == "cornell":
         ex = scenes.cornell_box(W, H, 4, device_id=None)
@@ -260,6 +231,45 @@ def render_reference_text(out, W, H, frames, seed, scene_name):
     class _B:
         pass
     rs.bvh = _B(); rs.bvh.compact_node = ti.Vector.field(RSCD.CPNOD_VEC_SIZE, dtype=ti.f32); rs.bvh.compact_node.from_numpy(compact)
+    return ex, sc, orc, rcam, rs
+
+
+# ---- the reference's whole integrator, executed from its source text ----------------------------------------------------------------
+# integrator/PT_RGB.py:49-136 (`render`) with everything it calls -- Camera.get_ray_direction, Scene.closet_hit / closet_hit_shadow /
+# intersect_prim / intersect_tri / sample_li / get_prim_random_point_normal / get_prim_area, Disney.*, Glass.*, UF.*, Texture.texture2D --
+# run as plain Python over a small film.  Two things are supplied from this repo, because the reference has no reproducible
+# equivalent: (1) ti.random() returns the counter-based tm_rand(seed, pixel, frame, dim) with the dimension decided by the CALL SITE
+# (which reference function drew it, the how-many-th draw of that activation, and the `depth` of the render loop: SURVEY A.6 / tirt_math.h
+# TM_DIM_* -- so the mapping "which random number feeds which decision" is pinned too); (2) sin / cos / exp / pow / atan2 / acos / sqrt
+# are the shared polynomial kernels (through the oracle library's orc_kat_math), so that a film that differs does so because of the
+# reference's formulas, not because of a different math library.  The scene arrays (vertex / primitive / material / shape / light rows,
+# the compact LBVH nodes -- pinned by nodelist.txt --, camera matrices) are put straight into the reference classes' fields.
+def render_reference_text(out, W, H, frames, seed, scene_name):
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+    import oracle_api as oa
+    import Scene as RScene, PT_RGB as RPT                           # the reference's modules (through the stand-in)
+    for _m in (RScene, RPT):
+        _m.pow = ti.pow_
+
+    L = oa.load()
+
+    def m1(fn):
+        def f(x):
+            xi = np.array([x], np.float32); o = np.zeros(1, np.float32)
+            L.orc_kat_math(fn, xi, np.zeros(1, np.float32), o, 1)
+            return o[0]
+        return f
+
+    def m2(fn):
+        def f(x, y):
+            o = np.zeros(1, np.float32)
+            L.orc_kat_math(fn, np.array([x], np.float32), np.array([y], np.float32), o, 1)
+            return o[0]
+        return f
+    ti.set_math({"sin": m1(0), "cos": m1(1), "exp": m1(2), "log": m1(3), "pow": m2(4), "atan2": m2(5), "acos": m1(6),
+                 "tan": lambda x: np.float32(m1(0)(x) / m1(1)(x))})                  # tirt_math.h: tm_tan = tm_sin / tm_cos
+
+    ex, sc, orc, rcam, rs = reference_scene(W, H, scene_name)
     pt = RPT.PathTrace(W, H, rcam, rs, 64)
     pt.setup_data_cpu()
 
