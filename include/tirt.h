@@ -82,6 +82,7 @@ int tirt_sync(tirt_ctx *ctx);
  *          "overlap_lanes" (1..8, default 4) -- wavefront batches in flight on separate streams
  *          "trace_lds_depth" / "trace_refill_min" / "trace_node_min" / "trace_grid" / "trace_grid_alone" / "trace_slices" /
  *          "shade_grid" -- kernel tuning
+ *          "query_chunk_rays" (256 .. 2^27, default 2^21) -- rays per chunk of tirt_query_closest / tirt_query_occluded (48 B of scratch each)
  *          "bdpt_bounded" (0/1, default 1) -- BDPT connection rays are cut off at their target distance (same
  *            visibility answers as the full closest-hit query; 0 = reference-style full query, for cross-checks)
  *          "merge_paths" -- consecutive tirt_pt_rgb_render calls over contiguous frames are merged
@@ -239,6 +240,29 @@ int tirt_trace_closest(tirt_ctx *ctx, const float *rays, int nr, int stack_size,
                        float *out_hit, int32_t *out_prim, int32_t *counts);
 int tirt_trace_shadow(tirt_ctx *ctx, const float *rays, int nr, int stack_size, int flags,
                       float *out_t, int32_t *out_prim, int32_t *counts);
+
+/* Ray queries on DEVICE memory (no reference entry point: the same traversal as tirt_trace_closest / tirt_trace_shadow, for rays that
+ * already live on the GPU, e.g. in torch tensors).  Every pointer is device memory of ctx's device, allocated through the same HIP runtime
+ * as libtirt.so (a process with two libamdhip64 runtimes cannot share pointers); `stream` is the caller's hipStream_t (NULL: the null
+ * stream).  Row i of the rays starts at rays + i * ray_stride floats and holds origin, direction in its first six floats.
+ * Asynchronous: the work runs on the context's own stream, after everything queued on `stream` before the call, and `stream` waits for
+ * it; the call returns once the work is queued, with no host sync.  Rays go through in chunks of option "query_chunk_rays" (default 2^21,
+ * 256 .. 2^27), whose scratch the context keeps.
+ * tirt_query_closest: the closest hit, bit for bit tirt_trace_closest's.  Each output may be NULL: out_t[nr] = t (1e6 on a miss),
+ *   out_prim[nr] = primitive (-1 on a miss), out_hit + i * hit_stride = the 13 floats of tirt_trace_closest (t, pos3, gnormal3, normal3,
+ *   tex3), counts[nr*2] = N_box, N_leaf per ray (8-byte aligned; only with TIRT_COUNT_NODES).  The rays count in rays_closest.
+ * tirt_query_occluded: out_occluded[nr] = 1 where tirt_trace_shadow's t satisfies t < 1e6 && t < tmax, else 0 -- exact, with the walk
+ *   stopping early at a hit well inside tmax.  tmax[i * tmax_stride] per ray, or tmax_all for every ray when tmax is NULL; +inf asks for
+ *   any hit, tmax <= 0 or NaN answers 0.  The rays count in rays_shadow.
+ * flags: TIRT_TRAVERSE_EXHAUSTIVE, TIRT_COUNT_NODES; stack_size 1..4096; a stack overflow is reported by tirt_stats (TIRT_ERR_STACK).
+ * Refused with TIRT_ERR_ARG before anything is queued: a pointer that is not device memory of ctx's device, ray_stride < 6, hit_stride < 13
+ * with out_hit, tmax_stride < 1 with tmax, an LBVH that is not built, other flags, and a `stream` that is capturing a graph.  nr == 0 queues
+ * nothing. */
+int tirt_query_closest(tirt_ctx *ctx, const float *rays, int64_t nr, int64_t ray_stride, int stack_size, int flags,
+                       float *out_t, int32_t *out_prim, float *out_hit, int64_t hit_stride, int32_t *counts, void *stream);
+int tirt_query_occluded(tirt_ctx *ctx, const float *rays, int64_t nr, int64_t ray_stride,
+                        const float *tmax, int64_t tmax_stride, float tmax_all,
+                        int stack_size, int flags, uint8_t *out_occluded, void *stream);
 
 /* Multi-GPU without a Python framework in the loop (the reference has nothing here): ONE host thread drives
  * ndev contexts, one per device of the node, each created with tirt_film_create(..., tile_rank = i, tile_count = ndev, ...).

@@ -1,7 +1,8 @@
 """ti_raytrace_amd -- MI355X-native path-tracing core behind the ti-raytrace Python API.
 
 Modules keep the reference's names: ``SceneData``, ``Scene``, ``Camera``, ``LBvh``,
-``PT_RGB``, ``Debug``, ``UtilsFunc``, ``Texture``, ``Example`` (+ ``scenes`` with the example set-ups).
+``PT_RGB``, ``Debug``, ``UtilsFunc``, ``Texture``, ``Example`` (+ ``scenes`` with the example set-ups, and ``RayQuery``: closest-hit / occlusion
+queries on rays in PyTorch device tensors).
 The compute path is ``csrc/libtirt.so`` (hand-written HIP for gfx950) behind the C-ABI of
 ``include/tirt.h``; see DESIGN.md / INTEGRATION.md.
 """
@@ -16,5 +17,6 @@ if _os.environ.get("TIRT_NO_ENV_TUNING", "0") in ("", "0"):
     _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 from . import SceneData, UtilsFunc, Texture, Camera, LBvh, Scene, PT_RGB, BDPT_RGB, Debug, Example  # noqa: F401
+from .RayQuery import RayQuery, RayHits  # noqa: F401  (torch is imported when a RayQuery is made)
 
-__all__ = ["SceneData", "UtilsFunc", "Texture", "Camera", "LBvh", "Scene", "PT_RGB", "BDPT_RGB", "Debug", "Example"]
+__all__ = ["SceneData", "UtilsFunc", "Texture", "Camera", "LBvh", "Scene", "PT_RGB", "BDPT_RGB", "Debug", "Example", "RayQuery", "RayHits"]

@@ -90,6 +90,8 @@ SIGNATURES = {
     "tirt_film_import_device": (C.c_int, [_vp, _vp]),
     "tirt_trace_closest": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _vp]),
     "tirt_trace_shadow": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _vp]),
+    "tirt_query_closest": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
+    "tirt_query_occluded": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int, _vp, _vp]),
     "tirt_comm_init": (C.c_int, [C.POINTER(_vp), C.c_int]),
     "tirt_film_reduce": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int]),
     "tirt_comm_destroy": (C.c_int, [C.POINTER(_vp), C.c_int]),
@@ -368,6 +370,18 @@ class Context:
         check(lib().tirt_trace_shadow(self.handle, rays.reshape(-1), nr, int(stack_size), int(flags),
                                       out, prim, _ptr(counts)))
         return out, prim, counts
+
+    def query_closest(self, rays, nr, ray_stride, stack_size=64, flags=0, out_t=0, out_prim=0, out_hit=0, hit_stride=13, counts=0, stream=0):
+        """tirt_query_closest on device memory: every buffer is an integer device address (0 = none), `stream` a hipStream_t handle
+        (0 = the null stream).  Asynchronous (include/tirt.h); ti_raytrace_amd.RayQuery is the torch front end."""
+        check(lib().tirt_query_closest(self.handle, _vp(int(rays) or None), int(nr), int(ray_stride), int(stack_size), int(flags),
+                                       _vp(int(out_t) or None), _vp(int(out_prim) or None), _vp(int(out_hit) or None), int(hit_stride),
+                                       _vp(int(counts) or None), _vp(int(stream) or None)))
+
+    def query_occluded(self, rays, nr, ray_stride, out_occluded, tmax=0, tmax_stride=1, tmax_all=float("inf"), stack_size=64, flags=0, stream=0):
+        """tirt_query_occluded on device memory: integer device addresses, tmax = 0 means tmax_all for every ray."""
+        check(lib().tirt_query_occluded(self.handle, _vp(int(rays) or None), int(nr), int(ray_stride), _vp(int(tmax) or None), int(tmax_stride),
+                                        float(tmax_all), int(stack_size), int(flags), _vp(int(out_occluded) or None), _vp(int(stream) or None)))
 
     def bvh_info(self):
         out = (C.c_uint64 * 4)()

@@ -289,7 +289,7 @@ using namespace tirt;
 extern "C" {
 
 const char *tirt_last_error(void) { return g_error.c_str(); }
-int tirt_version(void) { return 100; }
+int tirt_version(void) { return 101; }
 
 int tirt_device_count(int *out)
 {
@@ -339,7 +339,7 @@ void tirt_destroy(tirt_ctx *c)
                       &c->keys_b, &c->vals_a, &c->vals_b, &c->hist, &c->morton_sorted, &c->bvh_node, &c->compact, &c->parent,
                       &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb,
                       &c->counters_mem, &c->spill, &c->tr_rays,
-                      &c->tr_out, &c->tr_prim, &c->tr_counts, &c->debug_mem, &c->dev_counters, &c->bdpt_px, &c->timeline, &c->pvb_set[0].count, &c->pvb_set[0].cand, &c->pvb_set[0].bound, &c->pvb_set[1].count, &c->pvb_set[1].cand, &c->pvb_set[1].bound, &c->pvb_stat, &c->pvb_tmp};
+                      &c->tr_out, &c->tr_prim, &c->tr_counts, &c->debug_mem, &c->query_mem, &c->dev_counters, &c->bdpt_px, &c->timeline, &c->pvb_set[0].count, &c->pvb_set[0].cand, &c->pvb_set[0].bound, &c->pvb_set[1].count, &c->pvb_set[1].cand, &c->pvb_set[1].bound, &c->pvb_stat, &c->pvb_tmp};
     for (DevBuf *b : bufs) b->release();
     for (auto &bl : c->bd) {
         DevBuf *bb[] = {&bl.items, &bl.state, &bl.rays, &bl.hits, &bl.qidx, &bl.ctr, &bl.rad};
@@ -356,6 +356,8 @@ void tirt_destroy(tirt_ctx *c)
     c->spec_mem.release(); c->spec_dev.release();
     if (c->spec_view) { delete (SpecView *)c->spec_view; c->spec_view = nullptr; }
     if (c->ev_main) (void)hipEventDestroy(c->ev_main);
+    if (c->query_ev_in) (void)hipEventDestroy(c->query_ev_in);
+    if (c->query_ev_out) (void)hipEventDestroy(c->query_ev_out);
     (void)hipEventDestroy(c->ev0); (void)hipEventDestroy(c->ev1);
     (void)hipStreamDestroy(c->stream);
     delete c;
@@ -436,6 +438,10 @@ int tirt_set_option(tirt_ctx *c, const char *name, double value)
     if (!strcmp(name, "path_order_blocks")) { c->path_order_blocks = value != 0.0; return TIRT_OK; }
     if (!strcmp(name, "slices_contiguous")) { c->slices_contiguous = value != 0.0; return TIRT_OK; }
     if (!strcmp(name, "trace_grid_alone")) { TIRT_REQUIRE(value >= 1 && value <= 16384, "trace_grid_alone: 1..16384"); c->tr_grid_alone = (int)value; return TIRT_OK; }
+    if (!strcmp(name, "query_chunk_rays")) {       // rays per chunk of tirt_query_closest / tirt_query_occluded (the scratch is sized to one chunk, 48 bytes per ray)
+        TIRT_REQUIRE(value >= 256.0 && value <= (double)(1 << 27), "query_chunk_rays: 256 .. 2^27");
+        c->query_chunk = (size_t)value; return TIRT_OK;
+    }
     if (!strcmp(name, "trace_grid")) { TIRT_REQUIRE(value >= 1 && value <= 16384, "trace_grid: 1..16384"); c->tr_grid = (int)value; c->grid_user = true; return TIRT_OK; }
     set_error(std::string("tirt_set_option: unknown option ") + name);
     return TIRT_ERR_ARG;
@@ -759,6 +765,20 @@ int tirt_trace_shadow(tirt_ctx *c, const float *rays, int nr, int stack_size, in
     CTX(c);
     TIRT_REQUIRE(rays && out_t && out_prim, "tirt_trace_shadow: null");
     return launch_trace_batch(c, rays, nr, stack_size, flags, true, out_t, out_prim, counts);
+}
+
+int tirt_query_closest(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, int stack_size, int flags,
+                       float *out_t, int32_t *out_prim, float *out_hit, int64_t hit_stride, int32_t *counts, void *stream)
+{
+    CTX(c);
+    return query_closest(c, rays, nr, ray_stride, stack_size, flags, out_t, out_prim, out_hit, hit_stride, counts, stream);
+}
+
+int tirt_query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, const float *tmax, int64_t tmax_stride, float tmax_all,
+                        int stack_size, int flags, uint8_t *out_occluded, void *stream)
+{
+    CTX(c);
+    return query_occluded(c, rays, nr, ray_stride, tmax, tmax_stride, tmax_all, stack_size, flags, out_occluded, stream);
 }
 
 int tirt_bvh_info(tirt_ctx *c, uint64_t out[4])

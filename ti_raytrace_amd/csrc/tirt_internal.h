@@ -372,6 +372,10 @@ struct tirt_ctx {
     // batch trace scratch
     tirt::DevBuf tr_rays, tr_out, tr_prim, tr_counts;
     tirt::DevBuf debug_mem;                       // Debug integrator (tirt_debug.hip): hit records + camera directions of the local pixels
+    // ray queries on device memory (tirt_query.hip): one chunk's ray + hit records, option "query_chunk_rays", the two events that order the
+    // context's stream after and before the caller's (made on first use)
+    tirt::DevBuf query_mem; size_t query_chunk = (size_t)1 << 21;
+    hipEvent_t query_ev_in = nullptr, query_ev_out = nullptr;
 
     // RCCL communicator of tirt_comm_init (single-process multi-GPU film reduce; opaque ncclComm_t)
     void *comm = nullptr; int comm_rank = 0, comm_size = 0;
@@ -434,7 +438,12 @@ int trace_arrays(tirt_ctx *c, const float *ox, const float *oy, const float *oz,
                  int count, const int *count_ptr, float4 *hit, const int *expect, const float *bound, bool count_rays, int lane = -1,
                  const float4 *ray4 = nullptr, bool query = false, const int *ray_index = nullptr);      // (ray_index: TraceArgs) ray4: the rays as 32-byte records (TraceArgs::ray4); query: bounded queries whose expect / bound ride in the records
 int trace_camera(tirt_ctx *c, const float *dx, const float *dy, const float *dz, int count, float4 *hit, int stack_size, int flags);      // rays from the eye (Debug)
+int trace_records(tirt_ctx *c, const float4 *ray4, int count, float4 *hit, int stack_size, int flags, bool query, int2 *per_ray_counts);      // rays as 32-byte records (queries)
 int debug_render(tirt_ctx *c, uint32_t frame, uint32_t seed, int mode, int stack_size, int flags);      // tirt_debug.hip
+int query_closest(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, int stack_size, int flags, float *out_t, int32_t *out_prim,
+                  float *out_hit, int64_t hit_stride, int32_t *counts, void *stream);      // tirt_query.hip
+int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, const float *tmax, int64_t tmax_stride, float tmax_all,
+                   int stack_size, int flags, uint8_t *out_occluded, void *stream);
 int pvb_prepare(tirt_ctx *c);                          // tirt_pvb.hip
 void pvb_launch_cand(tirt_ctx *c, hipStream_t st, const BvhView &bv, const float *dx, const float *dy, const float *dz, const TileMap &tm, int P, int S,
                      float4 *hit, int *fb_count, int *fb_slot, float *fb_dx, float *fb_dy, float *fb_dz, DevCounters *ctr);

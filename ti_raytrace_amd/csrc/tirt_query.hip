@@ -1,0 +1,190 @@
+// tirt_query.hip -- closest-hit and occlusion queries on rays that live in device memory (tirt_query_closest / tirt_query_occluded).
+//
+// No reference counterpart as an entry point: the traversal is Scene.closet_hit / closet_hit_shadow (Scene.py:702-744, 671-699), run by
+// the existing k_trace instantiations.  What is new is the plumbing around it, in chunks of option "query_chunk_rays" rays, all on the
+// context's main stream, ordered after and before the caller's stream by two events (no host sync):
+//
+//   k_query_pack               caller rays (f32, any row stride >= 6) -> 32-byte records TraceArgs::ray4: (o.xyz, d.x), (d.y, d.z, bits expect, bound)
+//   k_trace<closest | query>   closest hit, or the bounded query with bound = tmax                 (trace_records, tirt_render.hip)
+//   k_query_resolve_closest    t, prim and optionally the 13-float record of tirt_trace_closest (the same hit_attributes call as k_hit_attr)
+//   k_query_resolve_occluded   one byte per ray: t < INF_VALUE && t < tmax
+//
+// Why the occlusion answer is exact: with bound = tmax > 0 an ordered walk stops early ("settled") only on an accepted hit with
+// hit_t < 0.99 tmax, which is a hit the reference finds too, so its closest is closer still and below tmax; a walk that does not settle
+// culls nothing nearer than 1.01 tmax and so ends with the reference's closest hit whenever that is below tmax, and with a hit at or beyond
+// tmax (or a miss) otherwise.  Rays from far away (no culling), the exhaustive walk and tmax <= 0 / NaN (no bound) end with the full closest
+// hit.  A miss leaves t = INF_VALUE (1e6, the reference's value), which is why the test is not a bare t < tmax.
+#include "tirt_internal.h"
+
+namespace tirt {
+
+constexpr int QUERY_EXPECT = -2;          // the `expect` of an occlusion query: equals no primitive id, and k_trace gives it no meaning of its own
+
+__global__ void k_query_pack(const float *rays, int64_t base, int n, int64_t ray_stride, int occluded, const float *tmax, int64_t tmax_stride,
+                             float tmax_all, float4 *rec)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t g = base + i;
+    const float *r = rays + g * ray_stride;
+    const float ox = r[0], oy = r[1], oz = r[2], dx = r[3], dy = r[4], dz = r[5];
+    int expect = -3; float bound = -1.0f;                 // closest: the "no query" encoding of the BDPT ray lists
+    if (occluded) { expect = QUERY_EXPECT; bound = tmax ? tmax[g * tmax_stride] : tmax_all; }
+    rec[2 * (size_t)i] = make_float4(ox, oy, oz, dx);
+    rec[2 * (size_t)i + 1] = make_float4(dy, dz, __int_as_float(expect), bound);
+}
+
+// k_hit_attr (tirt_render.hip) on the records: the same floats in, the same hit_attributes call, the same miss handling
+__global__ void k_query_resolve_closest(SceneView s, const float4 *rec, const float4 *hit, int64_t base, int n, float *out_t, int32_t *out_prim,
+                                        float *out_hit, int64_t hit_stride)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t g = base + i;
+    const float4 hr = hit[i];
+    if (out_t) out_t[g] = hr.x;
+    if (out_prim) out_prim[g] = __float_as_int(hr.w);
+    if (!out_hit) return;
+    const float4 r0 = rec[2 * (size_t)i], r1 = rec[2 * (size_t)i + 1];
+    HitAttr h; h.pos = h.gnor = h.nor = h.tex = V(0.0f, 0.0f, 0.0f);
+    if (hr.x < INF_VALUE) h = hit_attributes(s, V(r0.x, r0.y, r0.z), V(r0.w, r1.x, r1.y), __float_as_int(hr.w), hr.x, hr.y, hr.z);
+    else { h.gnor = normalized(h.gnor); h.nor = normalized(h.nor); }     // reference normalises (0,0,0) on a miss
+    float *o = out_hit + g * hit_stride;
+    o[0] = hr.x;
+    o[1] = h.pos.x; o[2] = h.pos.y; o[3] = h.pos.z;
+    o[4] = h.gnor.x; o[5] = h.gnor.y; o[6] = h.gnor.z;
+    o[7] = h.nor.x; o[8] = h.nor.y; o[9] = h.nor.z;
+    o[10] = h.tex.x; o[11] = h.tex.y; o[12] = h.tex.z;
+}
+
+// the bound the record carries is the caller's tmax, bit for bit (NaN and -1 compare false: 0)
+__global__ void k_query_resolve_occluded(const float4 *rec, const float4 *hit, int64_t base, int n, uint8_t *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float t = hit[i].x, tmax = rec[2 * (size_t)i + 1].w;
+    out[base + i] = (t < INF_VALUE && t < tmax) ? 1 : 0;
+}
+
+// Device memory of this context's device, as the HIP runtime libtirt.so runs on sees it.  A pointer of another runtime (a second
+// libamdhip64 in the process, _native._check_one_hip_runtime) or of the host is refused here, before anything is queued.
+static int require_device_ptr(tirt_ctx *c, const void *p, const char *what)
+{
+    hipPointerAttribute_t at = {};
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    (void)hipGetLastError();                               // an unknown pointer leaves a sticky error behind
+    if (e == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged) && at.device == c->device) return TIRT_OK;
+    set_error(std::string(what) + ": not device memory of this context's device " + std::to_string(c->device) +
+              " (a host pointer, another device's memory, or memory of a second HIP runtime in the process -- libtirt.so and the "
+              "caller's framework must share one libamdhip64)");
+    return TIRT_ERR_ARG;
+}
+
+static int query_common_checks(tirt_ctx *c, const char *fn, int64_t nr, int64_t ray_stride, int stack_size, int flags, void *stream)
+{
+    TIRT_REQUIRE(c->built, std::string(fn) + ": LBVH not built");
+    TIRT_REQUIRE(nr >= 0, std::string(fn) + ": nr < 0");
+    TIRT_REQUIRE(ray_stride >= 6, std::string(fn) + ": ray_stride < 6 (floats per ray: origin, direction)");
+    TIRT_REQUIRE(stack_size >= 1 && stack_size <= 4096, std::string(fn) + ": stack_size 1..4096");
+    TIRT_REQUIRE((flags & ~(TIRT_TRAVERSE_EXHAUSTIVE | TIRT_COUNT_NODES)) == 0, std::string(fn) + ": unknown flags");
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error(std::string(fn) + ": the caller's stream is not a stream of this process's HIP runtime");
+        return TIRT_ERR_ARG;
+    }
+    TIRT_REQUIRE(cs == hipStreamCaptureStatusNone, std::string(fn) + ": the caller's stream is capturing a graph (queries cannot be captured)");
+    return TIRT_OK;
+}
+
+// Scratch of one chunk (ray records, then hit records) and the two ordering events, made once.  Growing the buffer waits for the work
+// queued on the context's stream, which may still read the old one.
+static int query_prepare(tirt_ctx *c, int64_t nr, int &chunk, float4 *&rec, float4 *&hit)
+{
+    const int64_t want = nr < (int64_t)c->query_chunk ? nr : (int64_t)c->query_chunk;
+    chunk = (int)want;
+    const size_t bytes = (size_t)want * 48;
+    if (bytes > c->query_mem.bytes) {
+        TIRT_HIP(hipStreamSynchronize(c->stream));
+        if (c->query_mem.ensure(bytes)) return TIRT_ERR_HIP;
+    }
+    rec = c->query_mem.as<float4>();
+    hit = rec + 2 * (size_t)want;
+    if (!c->query_ev_in) TIRT_HIP(hipEventCreateWithFlags(&c->query_ev_in, hipEventDisableTiming));
+    if (!c->query_ev_out) TIRT_HIP(hipEventCreateWithFlags(&c->query_ev_out, hipEventDisableTiming));
+    if (ensure_counters(c)) return TIRT_ERR_HIP;
+    return TIRT_OK;
+}
+
+static int query_begin(tirt_ctx *c, void *stream)
+{
+    TIRT_HIP(hipEventRecord(c->query_ev_in, (hipStream_t)stream));
+    TIRT_HIP(hipStreamWaitEvent(c->stream, c->query_ev_in, 0));
+    return TIRT_OK;
+}
+
+static int query_end(tirt_ctx *c, void *stream)
+{
+    TIRT_HIP(hipGetLastError());
+    TIRT_HIP(hipEventRecord(c->query_ev_out, c->stream));
+    TIRT_HIP(hipStreamWaitEvent((hipStream_t)stream, c->query_ev_out, 0));
+    return TIRT_OK;
+}
+
+int query_closest(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, int stack_size, int flags, float *out_t, int32_t *out_prim,
+                  float *out_hit, int64_t hit_stride, int32_t *counts, void *stream)
+{
+    const char *fn = "tirt_query_closest";
+    if (int rc = query_common_checks(c, fn, nr, ray_stride, stack_size, flags, stream)) return rc;
+    TIRT_REQUIRE(!out_hit || hit_stride >= 13, "tirt_query_closest: hit_stride < 13 (floats per hit record)");
+    TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, "tirt_query_closest: counts must be 8-byte aligned");
+    if (nr == 0) return TIRT_OK;
+    TIRT_REQUIRE(rays, "tirt_query_closest: null rays");
+    if (int rc = require_device_ptr(c, rays, "tirt_query_closest: rays")) return rc;
+    if (out_t) if (int rc = require_device_ptr(c, out_t, "tirt_query_closest: out_t")) return rc;
+    if (out_prim) if (int rc = require_device_ptr(c, out_prim, "tirt_query_closest: out_prim")) return rc;
+    if (out_hit) if (int rc = require_device_ptr(c, out_hit, "tirt_query_closest: out_hit")) return rc;
+    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
+    if (want_counts) if (int rc = require_device_ptr(c, counts, "tirt_query_closest: counts")) return rc;
+    int chunk; float4 *rec, *hit;
+    if (int rc = query_prepare(c, nr, chunk, rec, hit)) return rc;
+    if (int rc = query_begin(c, stream)) return rc;
+    const SceneView sv = scene_view(c);
+    const int B = 256;
+    for (int64_t base = 0; base < nr; base += chunk) {
+        const int n = (int)(nr - base < chunk ? nr - base : chunk);
+        const dim3 g((unsigned)((n + B - 1) / B));
+        hipLaunchKernelGGL(k_query_pack, g, dim3(B), 0, c->stream, rays, base, n, ray_stride, 0, (const float *)nullptr, (int64_t)0, 0.0f, rec);
+        if (int rc = trace_records(c, rec, n, hit, stack_size, flags, false, want_counts ? (int2 *)counts + base : nullptr)) return rc;
+        hipLaunchKernelGGL(k_query_resolve_closest, g, dim3(B), 0, c->stream, sv, (const float4 *)rec, (const float4 *)hit, base, n, out_t, out_prim,
+                           out_hit, hit_stride);
+    }
+    return query_end(c, stream);
+}
+
+int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, const float *tmax, int64_t tmax_stride, float tmax_all,
+                   int stack_size, int flags, uint8_t *out_occluded, void *stream)
+{
+    const char *fn = "tirt_query_occluded";
+    if (int rc = query_common_checks(c, fn, nr, ray_stride, stack_size, flags, stream)) return rc;
+    TIRT_REQUIRE(!tmax || tmax_stride >= 1, "tirt_query_occluded: tmax_stride < 1");
+    if (nr == 0) return TIRT_OK;
+    TIRT_REQUIRE(rays && out_occluded, "tirt_query_occluded: null rays / out_occluded");
+    if (int rc = require_device_ptr(c, rays, "tirt_query_occluded: rays")) return rc;
+    if (tmax) if (int rc = require_device_ptr(c, tmax, "tirt_query_occluded: tmax")) return rc;
+    if (int rc = require_device_ptr(c, out_occluded, "tirt_query_occluded: out_occluded")) return rc;
+    int chunk; float4 *rec, *hit;
+    if (int rc = query_prepare(c, nr, chunk, rec, hit)) return rc;
+    if (int rc = query_begin(c, stream)) return rc;
+    const int B = 256;
+    for (int64_t base = 0; base < nr; base += chunk) {
+        const int n = (int)(nr - base < chunk ? nr - base : chunk);
+        const dim3 g((unsigned)((n + B - 1) / B));
+        hipLaunchKernelGGL(k_query_pack, g, dim3(B), 0, c->stream, rays, base, n, ray_stride, 1, tmax, tmax_stride, tmax_all, rec);
+        if (int rc = trace_records(c, rec, n, hit, stack_size, flags, true, nullptr)) return rc;
+        hipLaunchKernelGGL(k_query_resolve_occluded, g, dim3(B), 0, c->stream, (const float4 *)rec, (const float4 *)hit, base, n, out_occluded);
+    }
+    return query_end(c, stream);
+}
+
+}  // namespace tirt

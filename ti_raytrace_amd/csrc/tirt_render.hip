@@ -930,6 +930,34 @@ int trace_camera(tirt_ctx *c, const float *dx, const float *dy, const float *dz,
     return launch_trace<KIND_CLOSEST>(c, st, a, flags, grid);
 }
 
+// `count` rays held as 32-byte records (TraceArgs::ray4), hit records to `hit` -- the traversal of the ray queries on device memory
+// (tirt_query.hip).  On the main stream, with the caller's stack size and traversal flags.  query == false: closest hits, the rays count
+// as closest-hit rays; query == true: bounded queries whose expect / bound ride in the records (KIND_QUERY), counted as shadow rays.
+// per_ray_counts: N_box / N_leaf per ray under TIRT_COUNT_NODES (or nullptr).
+int trace_records(tirt_ctx *c, const float4 *ray4, int count, float4 *hit, int stack_size, int flags, bool query, int2 *per_ray_counts)
+{
+    if (count <= 0) return TIRT_OK;
+    hipStream_t st = c->stream;
+    int spill_depth;
+    if (ensure_spill(c, c->spill, stack_size, spill_depth)) return TIRT_ERR_HIP;
+    if (c->counters_mem.ensure(sizeof(int) * TR_FETCH_STRIDE * TR_FETCH_LINES)) return TIRT_ERR_HIP;
+    TIRT_HIP(hipMemsetAsync(c->counters_mem.p, 0, sizeof(int) * TR_FETCH_STRIDE * TR_FETCH_LINES, st));
+    TraceArgs a = {};
+    a.bvh = bvh_view(c);
+    a.ray4 = ray4; a.ray_index = nullptr;
+    a.count_ptr = nullptr; a.count_fixed = count; a.hit = hit;
+    a.spill = c->spill.as<int>(); a.spill_depth = spill_depth;
+    a.ctr = c->dev_counters.as<DevCounters>();
+    a.per_ray_counts = (flags & TIRT_COUNT_NODES) ? per_ray_counts : nullptr;
+    a.fetch = c->counters_mem.as<int>();
+    fill_tunables(c, a);
+    int grid = (count + TR_BLOCK - 1) / TR_BLOCK; if (grid > c->tr_grid_alone) grid = c->tr_grid_alone;
+    a.timeline = timeline_for(c, flags, grid);
+    if (query) { c->launches_trace_shadow++; return launch_trace<KIND_QUERY>(c, st, a, flags, grid); }
+    c->launches_trace_closest++;
+    return launch_trace<KIND_CLOSEST>(c, st, a, flags, grid);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Wavefront PT_RGB
 // ---------------------------------------------------------------------------------------------
