@@ -304,6 +304,43 @@ def test_ray_counts(gpu_ctx_ok):
     assert st["rays_closest"] == n and st["rays_shadow"] == n + 1000 and st["stack_overflow"] == 0
 
 
+def test_host_route_call_shape(gpu_ctx_ok):
+    """Context.trace_closest / trace_shadow share the closest-query path (csrc/tirt_query.hip) but keep the host route's shape: one k_trace
+    launch per call whatever query_chunk_rays is, on the grid of option trace_grid (not trace_grid_alone), no launches_trace_* counts, every
+    ray counted as a closest-hit ray, and the per-ray node counts of RayQuery.closest_counts."""
+    ex = scenes.cornell_box(64, 64, 4, device_id=0)       # a context of its own: the options below stay with it
+    ex.build_scene()
+    if not ex.cam.view_inv_np.any():
+        ex.frame_camera(0.8)
+    ctx = ex.scene.ctx
+    rays = ray_set(ex, 64, 20000, seed=29)
+    n = rays.shape[0]
+    assert (n + 255) // 256 > 16
+    ctx.set_option("trace_grid", 8)
+    ctx.set_option("trace_grid_alone", 16)
+    ctx.set_option("query_chunk_rays", 1000)
+    ctx.stats_reset()
+    ctx.set_option("trace_timeline", 1)                   # the second counting launch from now: trace_shadow's if trace_closest made one
+    _, prim, _ = ctx.trace_closest(rays, 64, _native.COUNT_NODES)
+    t, sprim, _ = ctx.trace_shadow(rays, 64, _native.COUNT_NODES)
+    waves = len(ctx.trace_timeline())
+    ctx.set_option("trace_timeline", -1)
+    st = ctx.stats()
+    assert waves == 8 * 4                                  # trace_grid blocks of four waves
+    assert st["launches_trace_closest"] == 0 and st["launches_trace_shadow"] == 0
+    assert st["rays_closest"] == 2 * n and st["rays_shadow"] == 0
+    assert np.array_equal(sprim, prim)
+    # per-ray node counts: only with a lane for every ray are they free of the refill order of idle lanes (8 blocks refill all the time),
+    # so they are compared on a context with the default grids, as in test_closest_equals_host_route
+    ex, _ = scene("cornell")
+    ctx = ex.scene.ctx
+    _, prim, cnt = ctx.trace_closest(rays, 64, _native.COUNT_NODES)
+    t, _, scnt = ctx.trace_shadow(rays, 64, _native.COUNT_NODES)
+    h, qcnt = RayQuery(ex.scene, 64, _native.COUNT_NODES).closest_counts(on_dev(rays))
+    assert np.array_equal(cpu(qcnt), cnt) and np.array_equal(scnt, cnt)
+    assert np.array_equal(cpu(h.prim), prim) and np.array_equal(bits(cpu(h.t)), bits(t))
+
+
 def test_stack_overflow_is_reported(gpu_ctx_ok):
     """The 600-deep duplicate-Morton chain of test_gpu_trace.py::test_very_long_duplicate_chain in the reference's own LBVH (option
     "traversal_tree" 0, where the reference's 64-entry stack overflows), traced with a 64-entry stack: the ordered walk keeps the far

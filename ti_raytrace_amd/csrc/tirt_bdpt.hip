@@ -1064,7 +1064,7 @@ int bdpt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t see
     }
     // the traversal's own buffers first (stack spill: ~2 GB per lane at bdpt_stack_size 1024), so that the measurement below sees them and a
     // failed allocation leaves the film untouched (they used to be allocated inside the batch loop, after the guard)
-    for (int l = 0; l < NL; l++) if (int rc = trace_arrays_prepare(c, NL > 1 ? l : -1)) return rc;
+    for (int l = 0; l < NL; l++) if (int rc = trace_rays_prepare(c, NL > 1 ? l : -1)) return rc;
     {
         // not more than the device has free right now (plus what this context's BDPT buffers hold already: growing them frees them first), less
         // 2 GB: a batch half the size is a few per cent slower, a failed hipMalloc ends the render (bench.py's profiler child, next to the
@@ -1142,10 +1142,14 @@ int bdpt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t see
         int *alive_cnt = scount + 4;
         if (spectral) hipLaunchKernelGGL(k_bd_init<true>, dim3((N + B - 1) / B), dim3(B), 0, st, bc, items, state, rset[1], oset[1], alive_cnt, tm, P, N, frame0, &ctr->paths);
         else hipLaunchKernelGGL(k_bd_init<false>, dim3((N + B - 1) / B), dim3(B), 0, st, bc, items, state, rset[1], oset[1], alive_cnt, tm, P, N, frame0, &ctr->paths);
+        // the traversal of this batch's rays, which count themselves; the grid of an idle GPU also with two batches in flight: the other batch
+        // mostly runs its vertex / connection kernels (config 5: 384 blocks 2 047, 512 blocks 2 145 Mrays/s)
+        TraceJob tj; tj.lane = lane; tj.stack_size = c->bdpt_stack; tj.count_rays = false; tj.grid_cap = c->tr_grid_alone;
         // rays of the two sub-paths share the launches
         for (int d = 1; d < BD_EYE_MAX; d++) {
             const BdRays &ri = rset[d & 1], &ro = rset[(d + 1) & 1];
-            if (int rc = trace_arrays(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 2 * N, alive_cnt + d, ehits, nullptr, nullptr, false, lane, ri.r, false)) return rc;
+            tj.ray4 = ri.r; tj.count = 2 * N; tj.count_ptr = alive_cnt + d; tj.hit = ehits;
+            if (int rc = trace_rays(c, tj)) return rc;
             if (spectral) hipLaunchKernelGGL(k_bd_step<true>, dim3((2 * N + BD_STEP_BLOCK - 1) / BD_STEP_BLOCK), dim3(BD_STEP_BLOCK), 0, st, bc, items, state, ri, oset[d & 1], ro,
                                oset[(d + 1) & 1], alive_cnt, ehits, tm, P, N, frame0, d, &ctr->rays_closest);
             else hipLaunchKernelGGL(k_bd_step<false>, dim3((2 * N + BD_STEP_BLOCK - 1) / BD_STEP_BLOCK), dim3(BD_STEP_BLOCK), 0, st, bc, items, state, ri, oset[d & 1], ro,
@@ -1159,7 +1163,8 @@ int bdpt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t see
         else hipLaunchKernelGGL(k_bd_connect<false>, dim3((N + BD_CONNECT_BLOCK - 1) / BD_CONNECT_BLOCK), dim3(BD_CONNECT_BLOCK), 0, st, bc, items, state, tm, P, N, frame0,
                            stage, qmask, ibase, icount, scount);
         hipLaunchKernelGGL(k_bd_compact, dim3((N + B - 1) / B), dim3(B), 0, st, N, ibase, icount, qlist, scount, &ctr->rays_shadow);
-        if (int rc = trace_arrays(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (int)(SCAP < (size_t)N * BD_RAY_PAIRS ? SCAP : (size_t)N * BD_RAY_PAIRS), scount, shits, nullptr, nullptr, false, lane, stage, true, qlist)) return rc;
+        tj.query = true; tj.ray4 = stage; tj.ray_index = qlist; tj.count = (int)(SCAP < (size_t)N * BD_RAY_PAIRS ? SCAP : (size_t)N * BD_RAY_PAIRS); tj.count_ptr = scount; tj.hit = shits;
+        if (int rc = trace_rays(c, tj)) return rc;
         if (spectral) hipLaunchKernelGGL(k_bd_emitted<true>, dim3((N + B - 1) / B), dim3(B), 0, st, bc, items, state, tm, P, N, frame0, bl.rad.as<float>(), 3 * NP);
         else hipLaunchKernelGGL(k_bd_emitted<false>, dim3((N + B - 1) / B), dim3(B), 0, st, bc, items, state, tm, P, N, frame0, bl.rad.as<float>(), 3 * NP);
         {

@@ -5,7 +5,7 @@
 // out there).  No bounce loop, no shading, no running mean.  Here it is three launches on the context's main stream:
 //
 //   k_debug_generate   camera direction of every local pixel            Camera.py:131-142
-//   k_trace<closest>   closest hit, origin = the eye (TraceArgs::eye)    Scene.py:702-744 (trace_camera, tirt_render.hip)
+//   k_trace<closest>   closest hit, origin = the eye (TraceArgs::eye)    Scene.py:702-744 (trace_rays, tirt_render.hip)
 //   k_debug_resolve    the view of the chosen mode, written to hdr       integrator/Debug.py:55-67
 //
 // Queue index k is local pixel k of this context's tile (local_to_pixel): a wave holds an 8 x 8 pixel bundle, as in k_generate.
@@ -78,7 +78,9 @@ int debug_render(tirt_ctx *c, uint32_t frame, uint32_t seed, int mode, int stack
     const TileMap tm = {c->tile_rank, c->tile_count, c->tile_size, c->H, c->tile_blocked, 0};
     const int B = 256, G = (P + B - 1) / B;
     hipLaunchKernelGGL(k_debug_generate, dim3(G), dim3(B), 0, c->stream, c->cam, tm, P, frame, seed, dx, dy, dz);
-    if (int rc = trace_camera(c, dx, dy, dz, P, hit, stack_size, flags)) return rc;
+    TraceJob job; job.stack_size = stack_size; job.flags = flags; job.dx = dx; job.dy = dy; job.dz = dz; job.count = P; job.hit = hit; job.grid_cap = c->tr_grid_alone;
+    c->launches_trace_closest++;
+    if (int rc = trace_rays(c, job)) return rc;
     v3 eye; eye.x = c->cam.eye[0]; eye.y = c->cam.eye[1]; eye.z = c->cam.eye[2];
     hipLaunchKernelGGL(k_debug_resolve, dim3(G), dim3(B), 0, c->stream, scene_view(c), eye, tm, P, mode, dx, dy, dz, hit, c->hdr.as<float>());
     TIRT_HIP(hipGetLastError());

@@ -369,8 +369,7 @@ struct tirt_ctx {
     tirt::DevBuf spec_dev;                      // the SpecView again, in device memory (BDPT_SPEC)
     tirt::DevBuf spec_mem; bool spec_set = false; void *spec_view = nullptr;      // spec_view: a heap tirt::SpecView (tirt_spectral.h) with device pointers
 
-    // batch trace scratch
-    tirt::DevBuf tr_rays, tr_out, tr_prim, tr_counts;
+    tirt::DevBuf trace_stage;                     // tirt_trace_closest / tirt_trace_shadow (tirt_query.hip): the host rays and the results on their way back
     tirt::DevBuf debug_mem;                       // Debug integrator (tirt_debug.hip): hit records + camera directions of the local pixels
     // ray queries on device memory (tirt_query.hip): one chunk's ray + hit records, option "query_chunk_rays", the two events that order the
     // context's stream after and before the caller's (made on first use)
@@ -429,26 +428,37 @@ TD float sphere_pad(float r, float pad_abs) { return 1.0e-3f * r + pad_abs / (r 
 #ifdef TIRT_EXPERIMENTS
 int exp_wide_from_tree(tirt_ctx *c, const float *compact_host, const int *csize_host);     // tools/exp/sah_tree.py
 #endif
-int launch_trace_batch(tirt_ctx *c, const float *rays, int nr, int stack_size, int flags, bool shadow,
-                       float *out_f, int32_t *out_prim, int32_t *counts);
 struct SpecView;
 int pt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed, int max_depth, int stack_size, int flags, const SpecView *spec = nullptr);   // spec != nullptr: PT_Spec
 int bdpt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed, bool spectral = false);      // spectral: BDPT_SPEC
-int trace_arrays(tirt_ctx *c, const float *ox, const float *oy, const float *oz, const float *dx, const float *dy, const float *dz,
-                 int count, const int *count_ptr, float4 *hit, const int *expect, const float *bound, bool count_rays, int lane = -1,
-                 const float4 *ray4 = nullptr, bool query = false, const int *ray_index = nullptr);      // (ray_index: TraceArgs) ray4: the rays as 32-byte records (TraceArgs::ray4); query: bounded queries whose expect / bound ride in the records
-int trace_camera(tirt_ctx *c, const float *dx, const float *dy, const float *dz, int count, float4 *hit, int stack_size, int flags);      // rays from the eye (Debug)
-int trace_records(tirt_ctx *c, const float4 *ray4, int count, float4 *hit, int stack_size, int flags, bool query, int2 *per_ray_counts);      // rays as 32-byte records (queries)
+// One k_trace launch outside the path tracer (trace_rays, tirt_render.hip): the traversal service of BDPT, the primary beams, Debug and the
+// ray queries.  The rays are 32-byte records (TraceArgs::ray4) or, without them, camera rays from the eye with their directions in dx / dy / dz.
+struct TraceJob {
+    int lane = -1;                               // < 0: the main stream, c->spill and c->counters_mem; else that render lane's stream and buffers
+    int stack_size = 64;                         // sizes the spill (the integrator's stack_size)
+    int flags = 0;                               // TIRT_TRAVERSE_EXHAUSTIVE | TIRT_COUNT_NODES: the instantiation, timeline arming
+    bool query = false;                          // KIND_QUERY (bounded queries whose expect / bound ride in the records) instead of KIND_CLOSEST
+    const float4 *ray4 = nullptr;
+    const int *ray_index = nullptr;              // KIND_QUERY: ray q is record ray_index[q]
+    const float *dx = nullptr, *dy = nullptr, *dz = nullptr;
+    int count = 0; const int *count_ptr = nullptr;      // the rays: *count_ptr if given, `count` then being its capacity (sizes the grid)
+    float4 *hit = nullptr;
+    int2 *per_ray_counts = nullptr;              // N_box / N_leaf per ray, under TIRT_COUNT_NODES only
+    bool count_rays = true;                      // false: the caller counts its rays itself (TraceArgs::no_ray_count)
+    int grid_cap = 0;                            // persistent blocks at most: c->tr_grid_alone or c->tr_grid
+};
+int trace_rays(tirt_ctx *c, const TraceJob &j);
+int trace_rays_prepare(tirt_ctx *c, int lane);      // allocates what trace_rays needs on that lane at bdpt_stack_size (stack spill, fetch cursors)
 int debug_render(tirt_ctx *c, uint32_t frame, uint32_t seed, int mode, int stack_size, int flags);      // tirt_debug.hip
 int query_closest(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, int stack_size, int flags, float *out_t, int32_t *out_prim,
                   float *out_hit, int64_t hit_stride, int32_t *counts, void *stream);      // tirt_query.hip
 int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, const float *tmax, int64_t tmax_stride, float tmax_all,
                    int stack_size, int flags, uint8_t *out_occluded, void *stream);
+int trace_host(tirt_ctx *c, const float *rays, int nr, int stack_size, int flags, bool shadow, float *out_f, int32_t *out_prim, int32_t *counts);      // tirt_trace_closest / tirt_trace_shadow
 int pvb_prepare(tirt_ctx *c);                          // tirt_pvb.hip
 void pvb_launch_cand(tirt_ctx *c, hipStream_t st, const BvhView &bv, const float *dx, const float *dy, const float *dz, const TileMap &tm, int P, int S,
                      float4 *hit, int *fb_count, int *fb_slot, float *fb_dx, float *fb_dy, float *fb_dz, DevCounters *ctr);
 void pvb_launch_scatter(hipStream_t st, const int *fb_count, const int *fb_slot, const float4 *fb_hit, float4 *hit);
-int trace_arrays_prepare(tirt_ctx *c, int lane);      // allocates what trace_arrays needs on that lane (stack spill, fetch cursors)
 int ensure_counters(tirt_ctx *c);
 int ensure_shade_records(tirt_ctx *c);
 int sync_all(tirt_ctx *c);

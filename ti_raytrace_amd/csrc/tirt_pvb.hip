@@ -323,7 +323,7 @@ int pvb_prepare(tirt_ctx *c)
         if (c->pvb_tmp.ensure(tmp_bytes)) return without("probe scratch");
         tmp = c->pvb_tmp.p;
     }
-    if (trace_arrays_prepare(c, -1)) return without("traversal buffers");
+    if (trace_rays_prepare(c, -1)) return without("traversal buffers");
     // batches still in flight read the OTHER set (a camera move submits what is pending and does not wait); this one was last read by the batches of the camera
     // before last: the film updates are chained in submission order, so the event of the last of them covers them all
     if (ps.busy && hipStreamWaitEvent(st, ps.busy, 0) != hipSuccess) return without("event");
@@ -336,7 +336,8 @@ int pvb_prepare(tirt_ctx *c)
     if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) (void)hipEventRecord(e0, st);
     else { if (e0) (void)hipEventDestroy(e0); e0 = e1 = nullptr; (void)hipGetLastError(); }
     hipLaunchKernelGGL(k_pvb_probes, dim3((P + B - 1) / B), dim3(B), 0, st, c->cam, tm, P, rays);
-    if (int rc = trace_arrays(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 5 * P, nullptr, hits, nullptr, nullptr, false, -1, rays)) { if (tmp_async) (void)hipFreeAsync(tmp, st); if (e0) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); } return rc; }
+    TraceJob job; job.stack_size = c->bdpt_stack; job.ray4 = rays; job.count = 5 * P; job.hit = hits; job.count_rays = false; job.grid_cap = c->tr_grid_alone;
+    if (int rc = trace_rays(c, job)) { if (tmp_async) (void)hipFreeAsync(tmp, st); if (e0) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); } return rc; }
     hipLaunchKernelGGL(k_pvb_beam, dim3((P + 63) / 64), dim3(64), 0, st, bvh_view(c), c->cam, tm, P, hits, ps.count.as<int>(), ps.cand.as<int2>(),
                        ps.bound.as<float>(), c->pvb_stat.as<unsigned long long>());
     if (e0) { (void)hipEventRecord(e1, st); c->pvb_ev.push_back({e0, e1}); }

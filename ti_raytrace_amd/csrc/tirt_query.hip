@@ -1,12 +1,13 @@
-// tirt_query.hip -- closest-hit and occlusion queries on rays that live in device memory (tirt_query_closest / tirt_query_occluded).
+// tirt_query.hip -- closest-hit and occlusion queries on rays that live in device memory (tirt_query_closest / tirt_query_occluded), and
+// the host route (tirt_trace_closest / tirt_trace_shadow) through the same closest-hit path.
 //
 // No reference counterpart as an entry point: the traversal is Scene.closet_hit / closet_hit_shadow (Scene.py:702-744, 671-699), run by
 // the existing k_trace instantiations.  What is new is the plumbing around it, in chunks of option "query_chunk_rays" rays, all on the
 // context's main stream, ordered after and before the caller's stream by two events (no host sync):
 //
 //   k_query_pack               caller rays (f32, any row stride >= 6) -> 32-byte records TraceArgs::ray4: (o.xyz, d.x), (d.y, d.z, bits expect, bound)
-//   k_trace<closest | query>   closest hit, or the bounded query with bound = tmax                 (trace_records, tirt_render.hip)
-//   k_query_resolve_closest    t, prim and optionally the 13-float record of tirt_trace_closest (the same hit_attributes call as k_hit_attr)
+//   k_trace<closest | query>   closest hit, or the bounded query with bound = tmax                 (trace_rays, tirt_render.hip)
+//   k_query_resolve_closest    t, prim and optionally the 13-float record of tirt_trace_closest
 //   k_query_resolve_occluded   one byte per ray: t < INF_VALUE && t < tmax
 //
 // Why the occlusion answer is exact: with bound = tmax > 0 an ordered walk stops early ("settled") only on an accepted hit with
@@ -34,7 +35,7 @@ __global__ void k_query_pack(const float *rays, int64_t base, int n, int64_t ray
     rec[2 * (size_t)i + 1] = make_float4(dy, dz, __int_as_float(expect), bound);
 }
 
-// k_hit_attr (tirt_render.hip) on the records: the same floats in, the same hit_attributes call, the same miss handling
+// the record of tirt_trace_closest: t, then hit_attributes (pos, gnormal, normal, tex); a miss normalises (0, 0, 0) as the reference does
 __global__ void k_query_resolve_closest(SceneView s, const float4 *rec, const float4 *hit, int64_t base, int n, float *out_t, int32_t *out_prim,
                                         float *out_hit, int64_t hit_stride)
 {
@@ -97,27 +98,27 @@ static int query_common_checks(tirt_ctx *c, const char *fn, int64_t nr, int64_t 
     return TIRT_OK;
 }
 
-// Scratch of one chunk (ray records, then hit records) and the two ordering events, made once.  Growing the buffer waits for the work
-// queued on the context's stream, which may still read the old one.
-static int query_prepare(tirt_ctx *c, int64_t nr, int &chunk, float4 *&rec, float4 *&hit)
+// Scratch of one chunk of `chunk` rays (ray records, then hit records).  Growing the buffer waits for the work queued on the context's
+// stream, which may still read the old one.
+static int query_prepare(tirt_ctx *c, int chunk, float4 *&rec, float4 *&hit)
 {
-    const int64_t want = nr < (int64_t)c->query_chunk ? nr : (int64_t)c->query_chunk;
-    chunk = (int)want;
-    const size_t bytes = (size_t)want * 48;
+    const size_t bytes = (size_t)chunk * 48;
     if (bytes > c->query_mem.bytes) {
         TIRT_HIP(hipStreamSynchronize(c->stream));
         if (c->query_mem.ensure(bytes)) return TIRT_ERR_HIP;
     }
     rec = c->query_mem.as<float4>();
-    hit = rec + 2 * (size_t)want;
-    if (!c->query_ev_in) TIRT_HIP(hipEventCreateWithFlags(&c->query_ev_in, hipEventDisableTiming));
-    if (!c->query_ev_out) TIRT_HIP(hipEventCreateWithFlags(&c->query_ev_out, hipEventDisableTiming));
+    hit = rec + 2 * (size_t)chunk;
     if (ensure_counters(c)) return TIRT_ERR_HIP;
     return TIRT_OK;
 }
+static int query_chunk_of(const tirt_ctx *c, int64_t nr) { return (int)(nr < (int64_t)c->query_chunk ? nr : (int64_t)c->query_chunk); }
 
+// the two ordering events are made on first use
 static int query_begin(tirt_ctx *c, void *stream)
 {
+    if (!c->query_ev_in) TIRT_HIP(hipEventCreateWithFlags(&c->query_ev_in, hipEventDisableTiming));
+    if (!c->query_ev_out) TIRT_HIP(hipEventCreateWithFlags(&c->query_ev_out, hipEventDisableTiming));
     TIRT_HIP(hipEventRecord(c->query_ev_in, (hipStream_t)stream));
     TIRT_HIP(hipStreamWaitEvent(c->stream, c->query_ev_in, 0));
     return TIRT_OK;
@@ -128,6 +129,27 @@ static int query_end(tirt_ctx *c, void *stream)
     TIRT_HIP(hipGetLastError());
     TIRT_HIP(hipEventRecord(c->query_ev_out, c->stream));
     TIRT_HIP(hipStreamWaitEvent((hipStream_t)stream, c->query_ev_out, 0));
+    return TIRT_OK;
+}
+
+// pack, trace, resolve: `nr` rays in chunks of `chunk` through the records at `rec` / `hit` (query_prepare) on the context's stream.
+// `job` holds the traversal settings; counts: N_box / N_leaf per ray under TIRT_COUNT_NODES (or nullptr).
+static int closest_chunks(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, int chunk, float4 *rec, float4 *hit, TraceJob job,
+                          bool count_launches, float *out_t, int32_t *out_prim, float *out_hit, int64_t hit_stride, int2 *counts)
+{
+    const SceneView sv = scene_view(c);
+    const int B = 256;
+    job.ray4 = rec; job.hit = hit;
+    for (int64_t base = 0; base < nr; base += chunk) {
+        const int n = (int)(nr - base < chunk ? nr - base : chunk);
+        const dim3 g((unsigned)((n + B - 1) / B));
+        hipLaunchKernelGGL(k_query_pack, g, dim3(B), 0, c->stream, rays, base, n, ray_stride, 0, (const float *)nullptr, (int64_t)0, 0.0f, rec);
+        job.count = n; job.per_ray_counts = counts ? counts + base : nullptr;
+        if (count_launches) c->launches_trace_closest++;
+        if (int rc = trace_rays(c, job)) return rc;
+        hipLaunchKernelGGL(k_query_resolve_closest, g, dim3(B), 0, c->stream, sv, (const float4 *)rec, (const float4 *)hit, base, n, out_t, out_prim,
+                           out_hit, hit_stride);
+    }
     return TIRT_OK;
 }
 
@@ -146,20 +168,43 @@ int query_closest(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride
     if (out_hit) if (int rc = require_device_ptr(c, out_hit, "tirt_query_closest: out_hit")) return rc;
     const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
     if (want_counts) if (int rc = require_device_ptr(c, counts, "tirt_query_closest: counts")) return rc;
-    int chunk; float4 *rec, *hit;
-    if (int rc = query_prepare(c, nr, chunk, rec, hit)) return rc;
+    const int chunk = query_chunk_of(c, nr);
+    float4 *rec, *hit;
+    if (int rc = query_prepare(c, chunk, rec, hit)) return rc;
     if (int rc = query_begin(c, stream)) return rc;
-    const SceneView sv = scene_view(c);
-    const int B = 256;
-    for (int64_t base = 0; base < nr; base += chunk) {
-        const int n = (int)(nr - base < chunk ? nr - base : chunk);
-        const dim3 g((unsigned)((n + B - 1) / B));
-        hipLaunchKernelGGL(k_query_pack, g, dim3(B), 0, c->stream, rays, base, n, ray_stride, 0, (const float *)nullptr, (int64_t)0, 0.0f, rec);
-        if (int rc = trace_records(c, rec, n, hit, stack_size, flags, false, want_counts ? (int2 *)counts + base : nullptr)) return rc;
-        hipLaunchKernelGGL(k_query_resolve_closest, g, dim3(B), 0, c->stream, sv, (const float4 *)rec, (const float4 *)hit, base, n, out_t, out_prim,
-                           out_hit, hit_stride);
-    }
+    TraceJob job; job.stack_size = stack_size; job.flags = flags; job.grid_cap = c->tr_grid_alone;
+    if (int rc = closest_chunks(c, rays, nr, ray_stride, chunk, rec, hit, job, true, out_t, out_prim, out_hit, hit_stride,
+                                want_counts ? (int2 *)counts : nullptr)) return rc;
     return query_end(c, stream);
+}
+
+// tirt_trace_closest / tirt_trace_shadow: host rays (6 floats each) staged in device memory, one chunk of all of them through the
+// closest-hit path above with the grid of a busy GPU (trace_grid), shadow: t, else the 13-float record, back to the host with a sync.
+// (The staging buffer is used here alone, and each call ends with a sync of the stream that used it.)
+int trace_host(tirt_ctx *c, const float *rays, int nr, int stack_size, int flags, bool shadow, float *out_f, int32_t *out_prim, int32_t *counts)
+{
+    TIRT_REQUIRE(c->built, "trace: LBVH not built");
+    TIRT_REQUIRE(nr >= 0, "trace: nr < 0");
+    if (nr == 0) return TIRT_OK;
+    float4 *rec, *hit;
+    if (int rc = query_prepare(c, nr, rec, hit)) return rc;
+    // staging: rays [nr][6], t or records [nr][13], prim [nr], counts [nr][2]
+    if (c->trace_stage.ensure(sizeof(float) * 22 * (size_t)nr)) return TIRT_ERR_HIP;
+    float *d_rays = c->trace_stage.as<float>(), *d_out = d_rays + 6 * (size_t)nr;
+    int32_t *d_prim = (int32_t *)(d_out + 13 * (size_t)nr);
+    int2 *d_counts = (int2 *)(d_prim + nr);
+    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
+    hipStream_t st = c->stream;
+    TIRT_HIP(hipMemcpyAsync(d_rays, rays, sizeof(float) * 6 * (size_t)nr, hipMemcpyHostToDevice, st));
+    TraceJob job; job.stack_size = stack_size; job.flags = flags; job.grid_cap = c->tr_grid;
+    if (int rc = closest_chunks(c, d_rays, nr, 6, nr, rec, hit, job, false, shadow ? d_out : nullptr, d_prim, shadow ? nullptr : d_out, 13,
+                                want_counts ? d_counts : nullptr)) return rc;
+    TIRT_HIP(hipMemcpyAsync(out_f, d_out, sizeof(float) * (shadow ? 1 : 13) * (size_t)nr, hipMemcpyDeviceToHost, st));
+    TIRT_HIP(hipMemcpyAsync(out_prim, d_prim, sizeof(int32_t) * (size_t)nr, hipMemcpyDeviceToHost, st));
+    if (want_counts) TIRT_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int2) * (size_t)nr, hipMemcpyDeviceToHost, st));
+    TIRT_HIP(hipStreamSynchronize(st));
+    TIRT_HIP(hipGetLastError());
+    return TIRT_OK;
 }
 
 int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, const float *tmax, int64_t tmax_stride, float tmax_all,
@@ -173,15 +218,19 @@ int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_strid
     if (int rc = require_device_ptr(c, rays, "tirt_query_occluded: rays")) return rc;
     if (tmax) if (int rc = require_device_ptr(c, tmax, "tirt_query_occluded: tmax")) return rc;
     if (int rc = require_device_ptr(c, out_occluded, "tirt_query_occluded: out_occluded")) return rc;
-    int chunk; float4 *rec, *hit;
-    if (int rc = query_prepare(c, nr, chunk, rec, hit)) return rc;
+    const int chunk = query_chunk_of(c, nr);
+    float4 *rec, *hit;
+    if (int rc = query_prepare(c, chunk, rec, hit)) return rc;
     if (int rc = query_begin(c, stream)) return rc;
+    TraceJob job; job.stack_size = stack_size; job.flags = flags; job.query = true; job.ray4 = rec; job.hit = hit; job.grid_cap = c->tr_grid_alone;
     const int B = 256;
     for (int64_t base = 0; base < nr; base += chunk) {
         const int n = (int)(nr - base < chunk ? nr - base : chunk);
         const dim3 g((unsigned)((n + B - 1) / B));
         hipLaunchKernelGGL(k_query_pack, g, dim3(B), 0, c->stream, rays, base, n, ray_stride, 1, tmax, tmax_stride, tmax_all, rec);
-        if (int rc = trace_records(c, rec, n, hit, stack_size, flags, true, nullptr)) return rc;
+        job.count = n;
+        c->launches_trace_shadow++;
+        if (int rc = trace_rays(c, job)) return rc;
         hipLaunchKernelGGL(k_query_resolve_occluded, g, dim3(B), 0, c->stream, (const float4 *)rec, (const float4 *)hit, base, n, out_occluded);
     }
     return query_end(c, stream);

@@ -786,176 +786,45 @@ static int ensure_spill(tirt_ctx *c, DevBuf &spill, int stack_size, int &spill_d
 static void fill_tunables(const tirt_ctx *c, TraceArgs &a)
 { a.lds_depth = c->tr_lds_depth; a.refill_min = c->tr_refill_min; a.node_min = c->tr_node_min; a.slice_log2 = c->tr_slice_log2; a.slices_contig = c->slices_contiguous; }
 
-// ---------------------------------------------------------------------------------------------
-// Batch entry points (Debug-integrator style closest hit on caller-supplied rays)
-// ---------------------------------------------------------------------------------------------
-__global__ void k_split_rays(const float *rays, int nr, float *ox, float *oy, float *oz, float *dx, float *dy, float *dz)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nr) return;
-    const float *r = rays + (size_t)i * 6;
-    ox[i] = r[0]; oy[i] = r[1]; oz[i] = r[2]; dx[i] = r[3]; dy[i] = r[4]; dz[i] = r[5];
-}
-__global__ void k_hit_attr(SceneView s, int nr, const float *ox, const float *oy, const float *oz, const float *dx, const float *dy,
-                           const float *dz, const float4 *hit, float *out, float *out_t, int *out_prim)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nr) return;
-    float *o = out + (size_t)i * 13;
-    const float4 hr = hit[i];
-    o[0] = hr.x; out_t[i] = hr.x; out_prim[i] = __float_as_int(hr.w);
-    HitAttr h; h.pos = h.gnor = h.nor = h.tex = V(0.0f, 0.0f, 0.0f);
-    if (hr.x < INF_VALUE) h = hit_attributes(s, V(ox[i], oy[i], oz[i]), V(dx[i], dy[i], dz[i]), __float_as_int(hr.w), hr.x, hr.y, hr.z);
-    else { h.gnor = normalized(h.gnor); h.nor = normalized(h.nor); }     // reference normalises (0,0,0) on a miss
-    o[1] = h.pos.x; o[2] = h.pos.y; o[3] = h.pos.z;
-    o[4] = h.gnor.x; o[5] = h.gnor.y; o[6] = h.gnor.z;
-    o[7] = h.nor.x; o[8] = h.nor.y; o[9] = h.nor.z;
-    o[10] = h.tex.x; o[11] = h.tex.y; o[12] = h.tex.z;
-}
-
-int launch_trace_batch(tirt_ctx *c, const float *rays, int nr, int stack_size, int flags, bool shadow,
-                       float *out_f, int32_t *out_prim, int32_t *counts)
-{
-    TIRT_REQUIRE(c->built, "trace: LBVH not built");
-    TIRT_REQUIRE(nr >= 0, "trace: nr < 0");
-    if (nr == 0) return TIRT_OK;
-    if (ensure_counters(c)) return TIRT_ERR_HIP;
-    hipStream_t st = c->stream;
-    if (c->tr_rays.ensure(sizeof(float) * 6 * (size_t)nr)) return TIRT_ERR_HIP;
-    if (c->tr_out.ensure(sizeof(float) * (6 + 4 + 1 + 13) * (size_t)nr + 64)) return TIRT_ERR_HIP;
-    if (c->tr_prim.ensure(sizeof(int) * (size_t)nr)) return TIRT_ERR_HIP;
-    if (c->tr_counts.ensure(sizeof(int2) * (size_t)nr)) return TIRT_ERR_HIP;
-    int spill_depth;
-    if (ensure_spill(c, c->spill, stack_size, spill_depth)) return TIRT_ERR_HIP;
-    float *base = c->tr_out.as<float>();
-    float *ox = base, *oy = ox + nr, *oz = oy + nr, *dx = oz + nr, *dy = dx + nr, *dz = dy + nr;
-    float4 *hit = (float4 *)(((uintptr_t)(dz + nr) + 15) & ~(uintptr_t)15);
-    float *ht = (float *)(hit + nr), *attr = ht + nr;
-    TIRT_HIP(hipMemcpyAsync(c->tr_rays.p, rays, sizeof(float) * 6 * (size_t)nr, hipMemcpyHostToDevice, st));
-    const int B = 256;
-    hipLaunchKernelGGL(k_split_rays, dim3((nr + B - 1) / B), dim3(B), 0, st, c->tr_rays.as<float>(), nr, ox, oy, oz, dx, dy, dz);
-    TraceArgs a = {};
-    a.bvh = bvh_view(c);
-    a.ox = ox; a.oy = oy; a.oz = oz; a.dx = dx; a.dy = dy; a.dz = dz;
-    a.count_ptr = nullptr; a.count_fixed = nr;
-    a.hit = hit;
-    a.spill = c->spill.as<int>(); a.spill_depth = spill_depth;
-    a.ctr = c->dev_counters.as<DevCounters>();
-    a.per_ray_counts = (flags & TIRT_COUNT_NODES) ? c->tr_counts.as<int2>() : nullptr;
-    if (c->counters_mem.ensure(sizeof(int) * TR_FETCH_STRIDE * TR_FETCH_LINES)) return TIRT_ERR_HIP;
-    TIRT_HIP(hipMemsetAsync(c->counters_mem.p, 0, sizeof(int) * TR_FETCH_STRIDE * TR_FETCH_LINES, st));
-    a.fetch = c->counters_mem.as<int>();
-    fill_tunables(c, a);
-    int grid = (nr + TR_BLOCK - 1) / TR_BLOCK; if (grid > c->tr_grid) grid = c->tr_grid;
-    a.timeline = timeline_for(c, flags, grid);
-    if (int rc = launch_trace<KIND_CLOSEST>(c, st, a, flags, grid)) return rc;
-    hipLaunchKernelGGL(k_hit_attr, dim3((nr + B - 1) / B), dim3(B), 0, st, scene_view(c), nr, ox, oy, oz, dx, dy, dz, hit, attr, ht,
-                       c->tr_prim.as<int>());
-    if (!shadow) TIRT_HIP(hipMemcpyAsync(out_f, attr, sizeof(float) * 13 * (size_t)nr, hipMemcpyDeviceToHost, st));
-    else TIRT_HIP(hipMemcpyAsync(out_f, ht, sizeof(float) * (size_t)nr, hipMemcpyDeviceToHost, st));
-    TIRT_HIP(hipMemcpyAsync(out_prim, c->tr_prim.p, sizeof(int) * (size_t)nr, hipMemcpyDeviceToHost, st));
-    if (counts && (flags & TIRT_COUNT_NODES))
-        TIRT_HIP(hipMemcpyAsync(counts, c->tr_counts.p, sizeof(int2) * (size_t)nr, hipMemcpyDeviceToHost, st));
-    TIRT_HIP(hipStreamSynchronize(st));
-    TIRT_HIP(hipGetLastError());
-    return TIRT_OK;
-}
-
-// The buffers trace_arrays needs on a lane (lane < 0: the main stream) -- the paged tail of the traversal stacks, sized by the integrator's
-// stack size (2 GB per lane at bdpt_stack_size 1024), and the ray-fetch cursors -- allocated up front: a caller that sizes its batches to the free
-// memory (bdpt_render) calls this BEFORE it measures, and a failed allocation ends the call before anything has been blended into the film.
-int trace_arrays_prepare(tirt_ctx *c, int lane)
+// The paged tail of the traversal stacks (sized by the integrator's stack size: 2 GB per lane at bdpt_stack_size 1024) and the ray-fetch cursors
+// of a lane (lane < 0: the main stream), into `a`.  (The lanes' counter buffers hold the per-bounce cursors of the path tracer as well: ensure()
+// keeps a larger one.)
+static int trace_buffers(tirt_ctx *c, int lane, int stack_size, TraceArgs &a)
 {
     DevBuf &spill = lane < 0 ? c->spill : c->lanes[lane].spill;
     DevBuf &fetch = lane < 0 ? c->counters_mem : c->lanes[lane].counters_mem;
-    int spill_depth;
-    if (ensure_spill(c, spill, c->bdpt_stack, spill_depth)) return TIRT_ERR_HIP;
+    if (ensure_spill(c, spill, stack_size, a.spill_depth)) return TIRT_ERR_HIP;
     if (fetch.ensure(sizeof(int) * TR_FETCH_STRIDE * TR_FETCH_LINES)) return TIRT_ERR_HIP;
+    a.spill = spill.as<int>(); a.fetch = fetch.as<int>();
     return TIRT_OK;
 }
 
-// Closest hits (expect == nullptr) or bounded connection queries of `count` rays held in device arrays, hit records to
-// `hit` -- the traversal service of the BDPT wavefront (tirt_bdpt.hip).  Ordered traversal, on the main stream (lane < 0) or on
-// the stream of a render lane with that lane's ray-fetch cursors and spill buffer (two BDPT batches in flight).
-int trace_arrays(tirt_ctx *c, const float *ox, const float *oy, const float *oz, const float *dx, const float *dy, const float *dz,
-                 int count, const int *count_ptr, float4 *hit, const int *expect, const float *bound, bool count_rays, int lane,
-                 const float4 *ray4, bool query, const int *ray_index)
+// The buffers of BDPT's rays allocated up front: a caller that sizes its batches to the free memory (bdpt_render) calls this BEFORE it
+// measures, and a failed allocation ends the call before anything has been blended into the film.
+int trace_rays_prepare(tirt_ctx *c, int lane)
 {
-    if (count <= 0) return TIRT_OK;
-    hipStream_t st = lane < 0 ? c->stream : c->lanes[lane].stream;
-    DevBuf &spill = lane < 0 ? c->spill : c->lanes[lane].spill;
-    // (the lanes' counter buffers hold the per-bounce cursors of the path tracer as well: ensure() keeps a larger one)
-    DevBuf &fetch = lane < 0 ? c->counters_mem : c->lanes[lane].counters_mem;
-    int spill_depth;
-    if (ensure_spill(c, spill, c->bdpt_stack, spill_depth)) return TIRT_ERR_HIP;      // (the integrator's stack_size: option "bdpt_stack_size")
-    if (fetch.ensure(sizeof(int) * TR_FETCH_STRIDE * TR_FETCH_LINES)) return TIRT_ERR_HIP;
-    TIRT_HIP(hipMemsetAsync(fetch.p, 0, sizeof(int) * TR_FETCH_STRIDE * TR_FETCH_LINES, st));
     TraceArgs a = {};
-    a.bvh = bvh_view(c);
-    a.ox = ox; a.oy = oy; a.oz = oz; a.dx = dx; a.dy = dy; a.dz = dz; a.ray4 = ray4; a.ray_index = ray_index;
-    a.count_ptr = count_ptr; a.count_fixed = count; a.hit = hit;      // count: the capacity when count_ptr is given (sizes the grid)
-    a.sprim = expect; a.sdist = bound;
-    a.spill = spill.as<int>(); a.spill_depth = spill_depth;
-    a.ctr = c->dev_counters.as<DevCounters>(); a.per_ray_counts = nullptr; a.no_ray_count = count_rays ? 0 : 1;
-    a.fetch = fetch.as<int>();
-    fill_tunables(c, a);
-    const int grid_cap = c->tr_grid_alone;          // also with two BDPT batches in flight: the other batch mostly runs its vertex / connection kernels (config 5: 384 blocks 2 047, 512 blocks 2 145 Mrays/s)
-    int grid = (count + TR_BLOCK - 1) / TR_BLOCK; if (grid > grid_cap) grid = grid_cap;
-    return (expect || query) ? launch_trace<KIND_QUERY>(c, st, a, 0, grid) : launch_trace<KIND_CLOSEST>(c, st, a, 0, grid);
+    return trace_buffers(c, lane, c->bdpt_stack, a);
 }
 
-// Closest hits of `count` camera rays that start at the eye (TraceArgs::eye, ox == nullptr), directions in device arrays, hit
-// records to `hit` -- the traversal of the Debug integrator (tirt_debug.hip).  On the main stream, with the caller's stack size and
-// traversal flags (ordered / exhaustive, node counts); the rays count as closest-hit rays.
-int trace_camera(tirt_ctx *c, const float *dx, const float *dy, const float *dz, int count, float4 *hit, int stack_size, int flags)
+int trace_rays(tirt_ctx *c, const TraceJob &j)
 {
-    if (count <= 0) return TIRT_OK;
-    hipStream_t st = c->stream;
-    int spill_depth;
-    if (ensure_spill(c, c->spill, stack_size, spill_depth)) return TIRT_ERR_HIP;
-    if (c->counters_mem.ensure(sizeof(int) * TR_FETCH_STRIDE * TR_FETCH_LINES)) return TIRT_ERR_HIP;
-    TIRT_HIP(hipMemsetAsync(c->counters_mem.p, 0, sizeof(int) * TR_FETCH_STRIDE * TR_FETCH_LINES, st));
+    if (j.count <= 0) return TIRT_OK;
+    hipStream_t st = j.lane < 0 ? c->stream : c->lanes[j.lane].stream;
     TraceArgs a = {};
+    if (int rc = trace_buffers(c, j.lane, j.stack_size, a)) return rc;
+    TIRT_HIP(hipMemsetAsync(a.fetch, 0, sizeof(int) * TR_FETCH_STRIDE * TR_FETCH_LINES, st));
     a.bvh = bvh_view(c);
-    a.ox = a.oy = a.oz = nullptr; for (int k = 0; k < 3; k++) a.eye[k] = c->cam.eye[k];
-    a.dx = dx; a.dy = dy; a.dz = dz;
-    a.count_ptr = nullptr; a.count_fixed = count; a.hit = hit;
-    a.spill = c->spill.as<int>(); a.spill_depth = spill_depth;
-    a.ctr = c->dev_counters.as<DevCounters>(); a.per_ray_counts = nullptr;
-    a.fetch = c->counters_mem.as<int>();
+    a.ray4 = j.ray4; a.ray_index = j.ray_index;
+    if (!j.ray4) { a.dx = j.dx; a.dy = j.dy; a.dz = j.dz; for (int k = 0; k < 3; k++) a.eye[k] = c->cam.eye[k]; }      // camera rays (ox == nullptr): from the eye
+    a.count_ptr = j.count_ptr; a.count_fixed = j.count; a.hit = j.hit;
+    a.ctr = c->dev_counters.as<DevCounters>(); a.no_ray_count = j.count_rays ? 0 : 1;
+    a.per_ray_counts = (j.flags & TIRT_COUNT_NODES) ? j.per_ray_counts : nullptr;
     fill_tunables(c, a);
-    int grid = (count + TR_BLOCK - 1) / TR_BLOCK; if (grid > c->tr_grid_alone) grid = c->tr_grid_alone;
-    a.timeline = timeline_for(c, flags, grid);
-    c->launches_trace_closest++;
-    return launch_trace<KIND_CLOSEST>(c, st, a, flags, grid);
-}
-
-// `count` rays held as 32-byte records (TraceArgs::ray4), hit records to `hit` -- the traversal of the ray queries on device memory
-// (tirt_query.hip).  On the main stream, with the caller's stack size and traversal flags.  query == false: closest hits, the rays count
-// as closest-hit rays; query == true: bounded queries whose expect / bound ride in the records (KIND_QUERY), counted as shadow rays.
-// per_ray_counts: N_box / N_leaf per ray under TIRT_COUNT_NODES (or nullptr).
-int trace_records(tirt_ctx *c, const float4 *ray4, int count, float4 *hit, int stack_size, int flags, bool query, int2 *per_ray_counts)
-{
-    if (count <= 0) return TIRT_OK;
-    hipStream_t st = c->stream;
-    int spill_depth;
-    if (ensure_spill(c, c->spill, stack_size, spill_depth)) return TIRT_ERR_HIP;
-    if (c->counters_mem.ensure(sizeof(int) * TR_FETCH_STRIDE * TR_FETCH_LINES)) return TIRT_ERR_HIP;
-    TIRT_HIP(hipMemsetAsync(c->counters_mem.p, 0, sizeof(int) * TR_FETCH_STRIDE * TR_FETCH_LINES, st));
-    TraceArgs a = {};
-    a.bvh = bvh_view(c);
-    a.ray4 = ray4; a.ray_index = nullptr;
-    a.count_ptr = nullptr; a.count_fixed = count; a.hit = hit;
-    a.spill = c->spill.as<int>(); a.spill_depth = spill_depth;
-    a.ctr = c->dev_counters.as<DevCounters>();
-    a.per_ray_counts = (flags & TIRT_COUNT_NODES) ? per_ray_counts : nullptr;
-    a.fetch = c->counters_mem.as<int>();
-    fill_tunables(c, a);
-    int grid = (count + TR_BLOCK - 1) / TR_BLOCK; if (grid > c->tr_grid_alone) grid = c->tr_grid_alone;
-    a.timeline = timeline_for(c, flags, grid);
-    if (query) { c->launches_trace_shadow++; return launch_trace<KIND_QUERY>(c, st, a, flags, grid); }
-    c->launches_trace_closest++;
-    return launch_trace<KIND_CLOSEST>(c, st, a, flags, grid);
+    int grid = (j.count + TR_BLOCK - 1) / TR_BLOCK; if (grid > j.grid_cap) grid = j.grid_cap;
+    a.timeline = timeline_for(c, j.flags, grid);
+    if (!j.query) return launch_trace<KIND_CLOSEST>(c, st, a, j.flags, grid);
+    return launch_trace<KIND_QUERY>(c, st, a, j.flags, grid);
 }
 
 // ---------------------------------------------------------------------------------------------
