@@ -98,6 +98,18 @@ def refkat_lbvh_scene(which, device_id=None):
     return ex
 
 
+def same_bits(a, b, nan_payload=False):
+    """bit-for-bit equality of two float32 arrays of one shape; a NaN equals any NaN (the oracle's NaN payloads need not be the device's)
+    unless nan_payload asks for the payloads too (device against device)"""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    if a.shape != b.shape:
+        return False
+    eq = a.view(np.uint32) == b.view(np.uint32)
+    if not nan_payload:
+        eq = eq | (np.isnan(a) & np.isnan(b))
+    return bool(eq.all())
+
+
 def rel_l2(a, b):
     return float(np.sqrt(((a.astype(np.float64) - b) ** 2).sum() / max((b.astype(np.float64) ** 2).sum(), 1e-30)))
 

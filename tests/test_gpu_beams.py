@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import oracle_api as oa
-from common import rel_l2, tiny_scene
+from common import rel_l2, same_bits, tiny_scene
 from ti_raytrace_amd import scenes
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +26,7 @@ def film_and_counts(ex, W, H, frames, beams, render=None, opts=None, build=True)
 
 
 def same(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    return same_bits(a, b, nan_payload=True)          # device against device: the NaNs' payloads too
 
 
 def one_primitive(W, H, n, kind):

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import oracle_api as oa
+from common import same_bits as same
 from ti_raytrace_amd import RayQuery, scenes, _native
 
 pytestmark = pytest.mark.gpu
@@ -17,11 +18,6 @@ _SCENES = {}
 
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.int32)
-
-
-def same(a, b):
-    """bit for bit, a NaN equal to any NaN (the oracle's NaN payloads need not be the device's)"""
-    return ((bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))).all()
 
 
 def cpu(x):

@@ -1,6 +1,7 @@
 """Golden vectors computed by the REFERENCE'S OWN SOURCE TEXT -- build container only (needs /root/reference).
 
     python tools/refkat/make_refkat.py            # writes tests/golden/refkat.npz (+ refkat_render.npz with --render)
+    python tools/refkat/make_refkat.py --nonsquare-only     # tests/golden/refkat_nonsquare.npz: PT_RGB / BDPT_RGB at 60 x 44, 9 minutes
 
 The reference cannot run here: it is Python + Taichi DSL and Taichi is not installable.  But its `@ti.func`s are
 plain Python once `taichi` / `taichi_glsl` resolve to the stand-in under tools/refkat/standin (identity decorators, an fp32 vector
@@ -527,6 +528,30 @@ def normals_reference_text(out):
     ti._math_impl.clear()
 
 
+# ---- a film that is not square ----------------------------------------------------------------------------------------------------------
+# Every fixture above is 16 x 16, where W and H can be exchanged anywhere (film index i * H + j, cx / cy, the bounds of
+# Camera.get_image_point) without a number moving.  This one runs PT_RGB.render and BDPT_RGB.render on the Cornell box at one W != H film whose
+# pixel count is not a multiple of 64 (nor H of 8), frames 0 (no jitter) and 1.  Shape and generator time: 60 x 44 (2 640 pixels) is about the largest the
+# stand-in finishes in ten minutes in the build container on one core -- PT_RGB 149 s, BDPT_RGB 375 s, 8 min 44 s in all (0.2 s per pixel: 12 x 9 takes 22 s);
+# both times go into the npz's `cfg`.  Both films came out bit for bit the oracle's.
+NONSQUARE = (60, 44, 2, 7)                                      # W, H, frames, seed
+
+
+def nonsquare_reference_text(path, W, H, frames, seed):
+    import time
+    assert W != H and (W * H) % 64 != 0 and W >= 12 and H >= 8
+    out, secs = {}, {}
+    for key, fn in (("render", render_reference_text), ("bdpt", render_bdpt_reference_text)):
+        t0 = time.time()
+        fn(out, W, H, frames, seed, "cornell")
+        secs[key] = time.time() - t0
+        print("%s: %.0f s" % (key, secs[key]))
+    np.savez_compressed(path, pt_film=out["render_cornell_film"], bdpt_film=out["bdpt_cornell_film"],
+                        cfg=np.array([W, H, frames, seed, round(secs["render"]), round(secs["bdpt"])], np.int64),
+                        cfg_names=np.array(["W", "H", "frames", "seed", "pt_generator_seconds", "bdpt_generator_seconds"]))
+    print("wrote", path, "(%.1f KB)" % (os.path.getsize(path) / 1024))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "refkat.npz"))
@@ -534,7 +559,14 @@ def main():
     ap.add_argument("--render-only", action="store_true")
     ap.add_argument("--lbvh-only", action="store_true", help="accel/LBvh.py's build from its source text")
     ap.add_argument("--bdpt-only", action="store_true", help="integrator/BDPT_RGB.py's render from its source text (minutes)")
+    ap.add_argument("--nonsquare-only", action="store_true", help="PT_RGB.render and BDPT_RGB.render on one W != H film (about ten minutes)")
+    ap.add_argument("--nonsquare-shape", default="%dx%d" % NONSQUARE[:2], help="WxH of --nonsquare-only (W != H, W*H not a multiple of 64)")
     a = ap.parse_args()
+    if a.nonsquare_only:
+        W, H = (int(v) for v in a.nonsquare_shape.split("x"))
+        path = a.out.replace("refkat.npz", "refkat_nonsquare.npz")
+        nonsquare_reference_text(path, W, H, NONSQUARE[2], NONSQUARE[3])
+        return
     if not (a.render_only or a.bdpt_only or a.lbvh_only):
         out = {}
         kat_functions(out)
