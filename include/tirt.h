@@ -332,6 +332,19 @@ int tirt_kat_brdf(tirt_ctx *ctx, int which, const float *in, int in_stride, floa
  *  11 HeroSample.get_rnd_hero (:31-35) in: ti.random(), Lambda0 out: index, Lambda */
 int tirt_kat_spec(tirt_ctx *ctx, int which, const float *in, int in_stride, float *out, int out_stride, int n);
 
+/* The tables k_shade reads instead of recomputing what depends on a primitive or a light alone (tests/test_gpu_shade_tables.py).  They are built on
+ * the device after a scene upload, a material upload or tirt_process_normal, by the first call that needs them.
+ * tirt_shade_table_download: which 0 the shading records, 32 floats (128 bytes) per primitive -- triangles (v1, bits mat) (v2, bits 1) (v3, -) (n1, -) (n2, -)
+ *   (n3, -) (gnor, area) -; shapes (centre, bits mat) (radius, type, area, bits 2) --, which 1 the light records, 32 floats per entry of the light list --
+ *   triangles (v1, area) (v3 - v1, choice pdf) (v2 - v1, bits -1) (n1, emission.r) (n2, .g) (n3, .b); shapes (centre, area) (shape[4], shape[5], -, choice pdf)
+ *   (-, -, -, bits type) (shape[7..9], emission.r) (-, .g) (-, .b).  floats: the size of out, which must be the table's.
+ * tirt_kat_shade_tables: the un-hoisted device functions.  which 0, n = primitives: out 4 per primitive, gnor3 (zero for shapes), Scene.get_prim_area;
+ *   which 1, n = light_count: out 5 per light, area, light_choice_pdf of Scene.sample_li, emission3;  which 2: in 6 per sample (random number of the light
+ *   choice, a, b, shaded point3), out 2 x 12: (light_pos3, light_normal3, emission3 x visible, area, choice pdf, light_dist) by the un-hoisted functions,
+ *   then from the light records. */
+int tirt_shade_table_download(tirt_ctx *ctx, int which, float *out, uint64_t floats);
+int tirt_kat_shade_tables(tirt_ctx *ctx, int which, const float *in, float *out, int n);
+
 /* ---- native Wavefront OBJ/MTL ingest (host only; no device, no context) -----------------------------
  * Replaces the reference's use of the third-party PyWavefront 1.3.3 package in Scene.add_obj
  * (Scene.py:66-127: `pywavefront.Wavefront(filename)`, `scene.materials[name].vertices / vertex_format /

@@ -104,6 +104,8 @@ SIGNATURES = {
     "tirt_kat_math": (C.c_int, [_vp, C.c_int, _f32p, _f32p, _f32p, C.c_int]),
     "tirt_kat_brdf": (C.c_int, [_vp, C.c_int, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
     "tirt_kat_spec": (C.c_int, [_vp, C.c_int, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
+    "tirt_shade_table_download": (C.c_int, [_vp, C.c_int, _f32p, C.c_uint64]),
+    "tirt_kat_shade_tables": (C.c_int, [_vp, C.c_int, _vp, _f32p, C.c_int]),
     "tirt_obj_load": (C.c_int, [C.c_char_p, C.POINTER(_vp)]),
     "tirt_obj_free": (None, [_vp]),
     "tirt_obj_material_count": (C.c_int, [_vp]),
@@ -432,6 +434,21 @@ class Context:
         n, stride = inp.shape
         out = np.zeros((n, out_stride), np.float32)
         check(lib().tirt_kat_brdf(self.handle, int(which), inp.reshape(-1), stride, out.reshape(-1), out_stride, n))
+        return out
+
+    def shade_table_download(self, which, count):
+        """The shading records (which 0, count = primitives) or the light records (which 1, count = light_count): (count, 8, 4) float32."""
+        out = np.zeros((int(count), 8, 4), np.float32)
+        check(lib().tirt_shade_table_download(self.handle, int(which), out.reshape(-1), out.size))
+        return out
+
+    def kat_shade_tables(self, which, n, inp=None):
+        """include/tirt.h, tirt_kat_shade_tables: (n, 4), (n, 5) or -- which 2, inp (n, 6) -- (n, 2, 12) float32."""
+        if inp is not None:
+            inp = np.ascontiguousarray(inp, np.float32)
+            n = inp.shape[0]
+        out = np.zeros((int(n), 4) if which == 0 else (int(n), 5) if which == 1 else (int(n), 2, 12), np.float32)
+        check(lib().tirt_kat_shade_tables(self.handle, int(which), _ptr(inp), out.reshape(-1), int(n)))
         return out
 
     def kat_spec(self, which, inp, out_stride):

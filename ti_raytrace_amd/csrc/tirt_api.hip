@@ -16,7 +16,7 @@ SceneView scene_view(const tirt_ctx *c)
     SceneView s;
     s.vertex = c->vertex.as<float>(); s.primitive = c->primitive.as<int>(); s.material = c->material.as<float>();
     s.shape = c->shape.as<float>(); s.light = c->light.as<int>(); s.env = c->env.as<int>();
-    s.mat_lrgb = c->mat_lrgb.as<float>(); s.shade_rec = c->shade_rec.as<float4>();
+    s.mat_lrgb = c->mat_lrgb.as<float>(); s.shade_rec = c->shade_rec.as<float4>(); s.light_rec = c->light_rec.as<float4>();
     s.n = c->n; s.light_count = c->light_count; s.env_w = c->env_w; s.env_h = c->env_h; s.env_power = c->env_power;
     return s;
 }
@@ -73,6 +73,7 @@ static int refresh_material_table(tirt_ctx *c)
 }
 
 // ---- 128-byte shading record per primitive (tirt_device.h, hit_attributes_rec) -----------------------
+// gnor and area: the expressions of hit_attributes (Scene.py:537-561) and get_prim_area (Scene.py:324-350), evaluated here once per primitive
 __global__ void k_shade_records(SceneView s, float4 *rec)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -80,25 +81,67 @@ __global__ void k_shade_records(SceneView s, float4 *rec)
     const int *pr = s.primitive + (size_t)i * PRI_VEC;
     float4 *r = rec + (size_t)i * 8;
     const float mat = __int_as_float(pr[2]);
+    const float area = get_prim_area(s, i);
+    r[6] = r[7] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (pr[0] == PRIMITIVE_TRI) {
         const v3 v1 = vtx_pos(s, pr[1]), v2 = vtx_pos(s, pr[1] + 1), v3_ = vtx_pos(s, pr[1] + 2);
         const v3 n1 = vtx_nor(s, pr[1]), n2 = vtx_nor(s, pr[1] + 1), n3 = vtx_nor(s, pr[1] + 2);
+        const v3 v13 = v3_ - v1, v12 = v2 - v1;
+        const v3 gnor = normalized(cross(v12, v13));
         r[0] = make_float4(v1.x, v1.y, v1.z, mat); r[1] = make_float4(v2.x, v2.y, v2.z, __int_as_float(PRIMITIVE_TRI));
         r[2] = make_float4(v3_.x, v3_.y, v3_.z, 0.0f);
         r[3] = make_float4(n1.x, n1.y, n1.z, 0.0f); r[4] = make_float4(n2.x, n2.y, n2.z, 0.0f); r[5] = make_float4(n3.x, n3.y, n3.z, 0.0f);
+        r[6] = make_float4(gnor.x, gnor.y, gnor.z, area);
     } else {
         const float *sh = s.shape + (size_t)pr[1] * SHA_VEC;
-        r[0] = make_float4(sh[1], sh[2], sh[3], mat); r[1] = make_float4(sh[4], sh[0], 0.0f, __int_as_float(2));
+        r[0] = make_float4(sh[1], sh[2], sh[3], mat); r[1] = make_float4(sh[4], sh[0], area, __int_as_float(2));
         r[2] = r[3] = r[4] = r[5] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+}
+// ---- 128-byte record per entry of the light list (tirt_device.h, light_sample_rec): Scene.sample_li's reads of the emitter (Scene.py:477-518) ----
+__global__ void k_light_records(SceneView s, float4 *rec)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= s.light_count) return;
+    const int light_prim = s.light[i];
+    const int *pr = s.primitive + (size_t)light_prim * PRI_VEC;
+    float4 *r = rec + (size_t)i * LIGHT_REC_QUADS;
+    const float *lm = s.material + (size_t)pr[2] * MAT_VEC;
+    const v3 em = V(lm[2], lm[3], lm[4]);
+    const float light_area = get_prim_area(s, light_prim);
+    float light_choice_pdf = 1.0f / ((float)s.light_count * light_area);
+    if (pr[0] == PRIMITIVE_TRI) {
+        const v3 v1 = vtx_pos(s, pr[1]), v2 = vtx_pos(s, pr[1] + 1), v3_ = vtx_pos(s, pr[1] + 2);
+        const v3 n1 = vtx_nor(s, pr[1]), n2 = vtx_nor(s, pr[1] + 1), n3 = vtx_nor(s, pr[1] + 2);
+        const v3 e31 = v3_ - v1, e21 = v2 - v1;
+        r[0] = make_float4(v1.x, v1.y, v1.z, light_area); r[1] = make_float4(e31.x, e31.y, e31.z, light_choice_pdf);
+        r[2] = make_float4(e21.x, e21.y, e21.z, __int_as_float(-1));
+        r[3] = make_float4(n1.x, n1.y, n1.z, em.x); r[4] = make_float4(n2.x, n2.y, n2.z, em.y); r[5] = make_float4(n3.x, n3.y, n3.z, em.z);
+    } else {
+        const float *sh = s.shape + (size_t)pr[1] * SHA_VEC;
+        int st = (int)sh[0];
+        if (st == SHAPE_LASER) light_choice_pdf = 1.0f / (float)s.light_count;       // Scene.py:509 (light_shape_visible)
+        if (st == -1) st = -2;                                                       // (-1 marks a triangle; no shape type is negative)
+        r[0] = make_float4(sh[1], sh[2], sh[3], light_area); r[1] = make_float4(sh[4], sh[5], 0.0f, light_choice_pdf);
+        r[2] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(st));
+        r[3] = make_float4(sh[7], sh[8], sh[9], em.x); r[4] = make_float4(0.0f, 0.0f, 0.0f, em.y); r[5] = make_float4(0.0f, 0.0f, 0.0f, em.z);
     }
     r[6] = r[7] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 int ensure_shade_records(tirt_ctx *c)
 {
-    if (c->shade_rec_valid && c->shade_rec.p) return 0;
-    if (c->shade_rec.ensure(sizeof(float4) * 8 * (size_t)c->n)) return TIRT_ERR_HIP;
-    hipLaunchKernelGGL(k_shade_records, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, scene_view(c), c->shade_rec.as<float4>());
-    c->shade_rec_valid = true;
+    if (!(c->shade_rec_valid && c->shade_rec.p)) {
+        if (c->shade_rec.ensure(sizeof(float4) * 8 * (size_t)c->n)) return TIRT_ERR_HIP;
+        hipLaunchKernelGGL(k_shade_records, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, scene_view(c), c->shade_rec.as<float4>());
+        c->shade_rec_valid = true;
+    }
+    if (!(c->light_rec_valid && c->light_rec.p)) {
+        const int nl = c->light_count > 0 ? c->light_count : 1;          // (never an empty allocation; no record is read when light_count is 0)
+        if (c->light_rec.ensure(sizeof(float4) * LIGHT_REC_QUADS * (size_t)nl)) return TIRT_ERR_HIP;
+        if (c->light_count > 0)
+            hipLaunchKernelGGL(k_light_records, dim3((c->light_count + 63) / 64), dim3(64), 0, c->stream, scene_view(c), c->light_rec.as<float4>());
+        c->light_rec_valid = true;
+    }
     return 0;
 }
 
@@ -249,6 +292,68 @@ __global__ void k_kat_brdf(int which, const float *in, int in_stride, float *out
     }
 }
 
+// ---- known-answer kernels of the shading tables (tests/test_gpu_shade_tables.py): the un-hoisted device functions, per primitive / light / sample ----
+// which 0, per primitive i: hit_attributes' gnor (zero for a shape: a sphere's normal depends on the hit), get_prim_area   -> gnor3, area
+// which 1, per light list entry i: get_prim_area, the choice pdf of sample_li (after light_shape_visible), the material colour  -> area, pdf, rgb
+__global__ void k_kat_shade_tables(SceneView s, int which, float *out, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (which == 0) {
+        float *o = out + (size_t)i * 4;
+        v3 g = V(0.0f, 0.0f, 0.0f);
+        if (s.primitive[(size_t)i * PRI_VEC] == PRIMITIVE_TRI) g = hit_attributes(s, g, V(0.0f, 0.0f, 1.0f), i, 1.0f, 0.25f, 0.25f).gnor;
+        o[0] = g.x; o[1] = g.y; o[2] = g.z; o[3] = get_prim_area(s, i);
+    } else {
+        float *o = out + (size_t)i * 5;
+        const int light_prim = s.light[i];
+        const float *lm = s.material + (size_t)s.primitive[(size_t)light_prim * PRI_VEC + 2] * MAT_VEC;
+        const float light_area = get_prim_area(s, light_prim);
+        float light_choice_pdf = 1.0f / ((float)s.light_count * light_area);
+        (void)light_shape_visible(s, light_prim, V(0.0f, 0.0f, 1.0f), V(0.0f, 0.0f, 1.0f), 1.0f, light_choice_pdf);
+        o[0] = light_area; o[1] = light_choice_pdf; o[2] = lm[2]; o[3] = lm[3]; o[4] = lm[4];
+    }
+}
+// One NEE set-up of Scene.sample_li for (random number of the light choice, a, b, shaded point): first by the un-hoisted functions, then from the
+// light records.  in: u, a, b, p3 -> out: 2 x (pos3, normal3 after its three normalisations, emission3 x visible, area, choice pdf, light_dist)
+TD void kat_nee_store(float *o, v3 pos, v3 nor, v3 em, float area, float pdf, float dist)
+{ o[0] = pos.x; o[1] = pos.y; o[2] = pos.z; o[3] = nor.x; o[4] = nor.y; o[5] = nor.z; o[6] = em.x; o[7] = em.y; o[8] = em.z; o[9] = area; o[10] = pdf; o[11] = dist; }
+__global__ void k_kat_light_sample(SceneView s, const float *in, float *out, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *a = in + (size_t)i * 6;
+    float *o = out + (size_t)i * 24;
+    int lidx = (int)(a[0] * (float)s.light_count);
+    if (lidx >= s.light_count) lidx = s.light_count - 1;
+    if (lidx < 0) lidx = 0;                                  // (a test input outside [0, 1]: stay inside the tables)
+    const v3 p = V(a[3], a[4], a[5]);
+    {
+        const int light_prim = s.light[lidx];
+        v3 light_pos, light_normal;
+        get_prim_random_point_normal(s, light_prim, a[1], a[2], light_pos, light_normal);
+        const float *lm = s.material + (size_t)s.primitive[(size_t)light_prim * PRI_VEC + 2] * MAT_VEC;
+        const float light_area = get_prim_area(s, light_prim);
+        float light_choice_pdf = 1.0f / ((float)s.light_count * light_area);
+        light_normal = normalized(light_normal);
+        v3 light_dir = p - light_pos;
+        const float light_dist = norm(light_dir);
+        light_dir = light_dir / light_dist;
+        const v3 em = V(lm[2], lm[3], lm[4]) * light_shape_visible(s, light_prim, light_dir, light_normal, light_dist, light_choice_pdf);
+        kat_nee_store(o, light_pos, light_normal, em, light_area, light_choice_pdf, light_dist);
+    }
+    {
+        v3 light_pos, light_normal;
+        const LightRec lr = light_sample_rec(s.light_rec, lidx, a[1], a[2], light_pos, light_normal);
+        light_normal = normalized(light_normal);
+        v3 light_dir = p - light_pos;
+        const float light_dist = norm(light_dir);
+        light_dir = light_dir / light_dist;
+        const v3 em = lr.emission * light_shape_visible_rec(lr, light_dir, light_normal, light_dist);
+        kat_nee_store(o + 12, light_pos, light_normal, em, lr.area, lr.choice_pdf, light_dist);
+    }
+}
+
 // ---- bench helper: ceiling of scattered 64-byte record gathers (the node-fetch pattern of k_trace) ----
 TD uint32_t mg_mix(uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
 __global__ __launch_bounds__(256) void k_micro_gather(const float4 *rec, uint32_t nrec, int iters, float *out)
@@ -335,7 +440,7 @@ void tirt_destroy(tirt_ctx *c)
     (void)hipSetDevice(c->device);
     (void)sync_all(c);
     drain_render_events(c);
-    DevBuf *bufs[] = {&c->vertex, &c->primitive, &c->material, &c->shape, &c->light, &c->env, &c->mat_lrgb, &c->shade_rec, &c->morton_unsorted, &c->keys_a,
+    DevBuf *bufs[] = {&c->vertex, &c->primitive, &c->material, &c->shape, &c->light, &c->env, &c->mat_lrgb, &c->shade_rec, &c->light_rec, &c->morton_unsorted, &c->keys_a,
                       &c->keys_b, &c->vals_a, &c->vals_b, &c->hist, &c->morton_sorted, &c->bvh_node, &c->compact, &c->parent,
                       &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb,
                       &c->counters_mem, &c->spill, &c->trace_stage, &c->debug_mem, &c->query_mem, &c->dev_counters, &c->bdpt_px, &c->timeline, &c->pvb_set[0].count, &c->pvb_set[0].cand, &c->pvb_set[0].bound, &c->pvb_set[1].count, &c->pvb_set[1].cand, &c->pvb_set[1].bound, &c->pvb_stat, &c->pvb_tmp};
@@ -475,7 +580,7 @@ int tirt_scene_upload(tirt_ctx *c, const float *vertex, int nv, const int32_t *p
     if (upload(c->material, material, sizeof(float) * 10 * (size_t)nm, st)) return TIRT_ERR_HIP;
     if (upload(c->shape, shape, sizeof(float) * 10 * (size_t)ns, st)) return TIRT_ERR_HIP;
     if (upload(c->light, light, sizeof(int) * (size_t)nl, st)) return TIRT_ERR_HIP;
-    c->nv = nv; c->n = n; c->nm = nm; c->ns = ns; c->nl = nl; c->light_count = light_count; c->shade_rec_valid = false;
+    c->nv = nv; c->n = n; c->nm = nm; c->ns = ns; c->nl = nl; c->light_count = light_count; c->shade_rec_valid = false; c->light_rec_valid = false;
     for (int k = 0; k < 3; k++) { c->bmin[k] = bmin[k]; c->bmax[k] = bmax[k]; }
     if (refresh_material_table(c)) return TIRT_ERR_HIP;
     if (!c->env.p) {        // default: 1x1 black (Scene.py:295-296 loads image/black.png)
@@ -494,6 +599,7 @@ int tirt_material_upload(tirt_ctx *c, const float *material, int nm)
     TIRT_REQUIRE(material && nm == c->nm, "tirt_material_upload: material count differs from the uploaded scene");
     if (upload(c->material, material, sizeof(float) * 10 * (size_t)nm, c->stream)) return TIRT_ERR_HIP;
     if (refresh_material_table(c)) return TIRT_ERR_HIP;
+    c->light_rec_valid = false;                // the light records carry the emitters' colours
     TIRT_HIP(hipStreamSynchronize(c->stream));
     return TIRT_OK;
 }
@@ -580,7 +686,7 @@ int tirt_process_normal(tirt_ctx *c, const int32_t *vertex_index)
     const int B = 128, G = (c->nv + B - 1) / B;
     hipLaunchKernelGGL(k_smooth_normal, dim3(G), dim3(B), 0, c->stream, scene_view(c), c->nv, c->compact.as<float>(), vi.as<int>(), smooth.as<float>());
     hipLaunchKernelGGL(k_write_normal, dim3(G), dim3(B), 0, c->stream, c->vertex.as<float>(), c->nv, smooth.as<float>());
-    c->shade_rec_valid = false;
+    c->shade_rec_valid = false; c->light_rec_valid = false;
     hipError_t e = hipStreamSynchronize(c->stream);
     vi.release(); smooth.release();
     TIRT_HIP(e);
@@ -932,6 +1038,44 @@ int tirt_kat_brdf(tirt_ctx *c, int which, const float *in, int in_stride, float 
         hipError_t e = hipMemcpyAsync(out, dout.p, sizeof(float) * (size_t)n * out_stride, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) { set_error(std::string("tirt_kat_brdf: ") + hipGetErrorString(e)); rc = TIRT_ERR_HIP; }
+    }
+    din.release(); dout.release();
+    return rc;
+}
+
+int tirt_shade_table_download(tirt_ctx *c, int which, float *out, uint64_t floats)
+{
+    CTX(c);
+    TIRT_REQUIRE(out && (which == 0 || which == 1), "tirt_shade_table_download: bad args");
+    TIRT_REQUIRE(c->n >= 1, "tirt_shade_table_download: no scene");
+    if (sync_all(c)) return TIRT_ERR_HIP;
+    if (ensure_shade_records(c)) return TIRT_ERR_HIP;
+    const uint64_t have = which == 0 ? (uint64_t)32 * c->n : (uint64_t)4 * LIGHT_REC_QUADS * c->light_count;
+    TIRT_REQUIRE(floats == have, "tirt_shade_table_download: 32 floats per primitive (which 0) or per light (which 1)");
+    if (floats) TIRT_HIP(hipMemcpyAsync(out, which == 0 ? c->shade_rec.p : c->light_rec.p, sizeof(float) * floats, hipMemcpyDeviceToHost, c->stream));
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    return TIRT_OK;
+}
+
+int tirt_kat_shade_tables(tirt_ctx *c, int which, const float *in, float *out, int n)
+{
+    CTX(c);
+    TIRT_REQUIRE(out && n >= 0 && which >= 0 && which <= 2, "tirt_kat_shade_tables: bad args");
+    TIRT_REQUIRE(c->n >= 1, "tirt_kat_shade_tables: no scene");
+    TIRT_REQUIRE(which == 2 ? (in && c->light_count > 0) : n == (which == 0 ? c->n : c->light_count), "tirt_kat_shade_tables: n is the primitive / light count; which 2 needs input and a light");
+    if (n == 0) return TIRT_OK;
+    if (sync_all(c)) return TIRT_ERR_HIP;
+    if (ensure_shade_records(c)) return TIRT_ERR_HIP;
+    const size_t out_floats = (size_t)n * (which == 0 ? 4 : which == 1 ? 5 : 24);
+    DevBuf din, dout;
+    int rc = TIRT_OK;
+    if ((which == 2 && upload(din, in, sizeof(float) * 6 * (size_t)n, c->stream)) || dout.ensure(sizeof(float) * out_floats)) rc = TIRT_ERR_HIP;
+    if (rc == TIRT_OK) {
+        if (which == 2) hipLaunchKernelGGL(k_kat_light_sample, dim3((n + 255) / 256), dim3(256), 0, c->stream, scene_view(c), din.as<float>(), dout.as<float>(), n);
+        else hipLaunchKernelGGL(k_kat_shade_tables, dim3((n + 255) / 256), dim3(256), 0, c->stream, scene_view(c), which, dout.as<float>(), n);
+        hipError_t e = hipMemcpyAsync(out, dout.p, sizeof(float) * out_floats, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { set_error(std::string("tirt_kat_shade_tables: ") + hipGetErrorString(e)); rc = TIRT_ERR_HIP; }
     }
     din.release(); dout.release();
     return rc;

@@ -53,6 +53,7 @@ struct SceneView {
     const int *env;          // [w*h]
     const float *mat_lrgb;   // [nm*3] srgb_to_lrgb(material colour), filled on device at upload
     const float4 *shade_rec; // [n*8] one 128-byte line per primitive: what k_shade needs to shade a hit on it (k_shade_records)
+    const float4 *light_rec; // [light_count*8] one 128-byte line per entry of `light`: what sample_li needs of that emitter (k_light_records)
     int n, light_count, env_w, env_h;
     float env_power;
 };
@@ -157,10 +158,10 @@ TD float intersect_sphere(v3 origin, v3 direction, v3 centre, float r, float &c_
 }
 
 // ---- hit attributes of the winning candidate (Scene.py:537-561, 565-596) -----------------------
-struct HitAttr { v3 pos, gnor, nor, tex; };
+struct HitAttr { v3 pos, gnor, nor, tex; float area; };      // area: get_prim_area of the primitive (hit_attributes_rec only)
 TD HitAttr hit_attributes(const SceneView &s, v3 origin, v3 direction, int prim, float t, float u, float v)
 {
-    HitAttr h; h.pos = h.gnor = h.nor = h.tex = V(0.0f, 0.0f, 0.0f);
+    HitAttr h; h.pos = h.gnor = h.nor = h.tex = V(0.0f, 0.0f, 0.0f); h.area = 0.0f;
     const int *pr = s.primitive + (size_t)prim * PRI_VEC;
     v3 gn = V(0.0f, 0.0f, 0.0f), nn = gn;
     if (pr[0] == PRIMITIVE_TRI) {
@@ -190,8 +191,12 @@ TD HitAttr hit_attributes(const SceneView &s, v3 origin, v3 direction, int prim,
 
 // The same from the 128-byte shading record of the primitive (one cache line instead of a 12-byte primitive row plus three
 // 36-byte vertex rows in three more lines; exact copies of the same floats, so the same results):
-//   triangles: (v1.xyz, bits mat) (v2.xyz, bits PRIMITIVE_TRI) (v3.xyz, -) (n1.xyz, -) (n2.xyz, -) (n3.xyz, -) - -
-//   shapes   : (centre.xyz, bits mat) (radius, shape type, -, bits 2)
+//   triangles: (v1.xyz, bits mat) (v2.xyz, bits PRIMITIVE_TRI) (v3.xyz, -) (n1.xyz, -) (n2.xyz, -) (n3.xyz, -) (gnor.xyz, area) -
+//   shapes   : (centre.xyz, bits mat) (radius, shape type, area, bits 2)
+// gnor = normalized(cross(v2 - v1, v3 - v1)) and area = get_prim_area depend on the primitive alone: k_shade_records evaluates them
+// once, with the very expressions of hit_attributes / get_prim_area (a cross product, five correctly rounded square roots and three
+// divisions less per shaded path).  A sphere's normal depends on the hit point and stays here; its gn IS its nn, so the one
+// normalisation serves both.
 // uv is not carried: the path tracer does not use it (the reference's albedo textures are unused, PT_RGB.py:86).
 TD HitAttr hit_attributes_rec(const float4 *rec, v3 origin, v3 direction, int prim, float t, float u, float v, int &mat_id)
 {
@@ -199,14 +204,15 @@ TD HitAttr hit_attributes_rec(const float4 *rec, v3 origin, v3 direction, int pr
     const float4 *r = rec + (size_t)prim * 8;
     const float4 r0 = r[0], r1 = r[1];
     mat_id = __float_as_int(r0.w);
-    v3 gn = V(0.0f, 0.0f, 0.0f), nn = gn;
-    if (__float_as_int(r1.w) == PRIMITIVE_TRI) {
-        const float4 r2 = r[2], r3 = r[3], r4 = r[4], r5 = r[5];
+    h.area = r1.z;
+    v3 nn = V(0.0f, 0.0f, 0.0f);
+    const bool tri = __float_as_int(r1.w) == PRIMITIVE_TRI;
+    if (tri) {
+        const float4 r2 = r[2], r3 = r[3], r4 = r[4], r5 = r[5], r6 = r[6];
         float a = 1.0f - u - v, b = u, c = v;
         v3 v1 = V(r0.x, r0.y, r0.z), v2 = V(r1.x, r1.y, r1.z), v3_ = V(r2.x, r2.y, r2.z);
         v3 n1 = V(r3.x, r3.y, r3.z), n2 = V(r4.x, r4.y, r4.z), n3 = V(r5.x, r5.y, r5.z);
-        v3 v13 = v3_ - v1, v12 = v2 - v1;
-        gn = cross(v12, v13);
+        h.gnor = V(r6.x, r6.y, r6.z); h.area = r6.w;
         h.pos = (v1 * a + v2 * b) + v3_ * c;
         nn = (n1 * a + n2 * b) + n3 * c;
     } else if ((int)r1.y == SHAPE_SPHERE) {
@@ -214,9 +220,9 @@ TD HitAttr hit_attributes_rec(const float4 *rec, v3 origin, v3 direction, int pr
         (void)intersect_sphere(origin, direction, V(r0.x, r0.y, r0.z), r1.x, c);
         h.pos = origin + direction * t;
         nn = V(h.pos.x - c, h.pos.y - c, h.pos.z - c);          // quirk B3
-        gn = nn;
     }
-    h.gnor = normalized(gn); h.nor = normalized(nn);
+    h.nor = normalized(nn);
+    if (!tri) h.gnor = h.nor;                                   // gn = nn: the same expression on the same floats
     return h;
 }
 
@@ -449,6 +455,55 @@ TD float light_shape_visible(const SceneView &s, int light_prim, v3 light_dir, v
             const float r = tm_sqrt(light_dist * light_dist - proj * proj);
             if (r > sh[4]) visable = 0.0f;
         }
+    }
+    return visable;
+}
+// ---- the per-light record (k_light_records): what Scene.sample_li (Scene.py:477-518) reads of emitter light[lidx] that does not depend on
+// the path, one 128-byte line per entry of `light` instead of a primitive row, three vertex rows (or a shape row) and a material row --
+//   triangles: (v1.xyz, area) (v3 - v1, choice_pdf) (v2 - v1, bits -1) (n1.xyz, emission.r) (n2.xyz, emission.g) (n3.xyz, emission.b) - -
+//   shapes   : (centre.xyz, area) (sh[4], sh[5], -, choice_pdf) (-, -, -, bits shape type) (sh[7..9], emission.r) (-, -, -, .g) (-, -, -, .b)
+// area = get_prim_area (Heron: four correctly rounded square roots), choice_pdf = 1 / (light_count * area), or 1 / light_count for a laser
+// (light_shape_visible overwrites it, Scene.py:509), the two edges of get_prim_random_point_normal's point and the emitter's material
+// colour: each evaluated once by the expression of the function it replaces.  What depends on the sample (a, b) stays per path, in
+// get_prim_random_point_normal's order, and so do the three normalisations of the light's normal. ----
+constexpr int LIGHT_REC_QUADS = 8;
+struct LightRec { v3 emission; float area, choice_pdf, p0, p1; int kind; };      // kind: -1 triangle, else the shape type; p0, p1 = sh[4], sh[5]
+TD LightRec light_sample_rec(const float4 *lrec, int lidx, float a, float b, v3 &pos, v3 &nor)
+{
+    const float4 *r = lrec + (size_t)lidx * LIGHT_REC_QUADS;
+    const float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3], r4 = r[4], r5 = r[5];
+    LightRec L; L.emission = V(r3.w, r4.w, r5.w); L.area = r0.w; L.choice_pdf = r1.w; L.p0 = r1.x; L.p1 = r1.y; L.kind = __float_as_int(r2.w);
+    pos = V(0.0f, 0.0f, 0.0f); v3 normal = pos;
+    if (L.kind == -1) {
+        const v3 v1 = V(r0.x, r0.y, r0.z), e31 = V(r1.x, r1.y, r1.z), e21 = V(r2.x, r2.y, r2.z);
+        const v3 n1 = V(r3.x, r3.y, r3.z), n2 = V(r4.x, r4.y, r4.z), n3 = V(r5.x, r5.y, r5.z);
+        if (a + b > 1.0f) { a = 1.0f - a; b = 1.0f - b; }
+        pos = (v1 + e31 * a) + e21 * b;
+        normal = normalized((n1 * (1.0f - a - b) + n2 * a) + n3 * b);
+    } else if (L.kind == SHAPE_SPHERE) {
+        normal = uniform_sample_sphere(a, b);
+        pos = V(r0.x, r0.y, r0.z) + normal * L.p0;
+    } else if (L.kind == SHAPE_SPOT || L.kind == SHAPE_LASER) {
+        normal = V(r3.x, r3.y, r3.z);
+        pos = V(r0.x, r0.y, r0.z);
+    }
+    nor = normalized(normal);
+    return L;
+}
+// light_shape_visible on the record (the laser's choice pdf is already in it)
+TD float light_shape_visible_rec(const LightRec &L, v3 light_dir, v3 light_normal, float light_dist)
+{
+    float visable = 1.0f;
+    if (L.kind == SHAPE_SPOT) {
+        const float NdotL = absf(dot(light_dir, light_normal));
+        const float x1 = L.p0, x2 = L.p1;
+        const float x = tm_acos(NdotL);
+        if (x > x2) visable = 0.0f;
+        else if (x > x1) visable *= 1.0f - (x - x1) / (x2 - x1);
+    } else if (L.kind == SHAPE_LASER) {
+        const float proj = dot(light_dir, light_normal) * light_dist;
+        const float r = tm_sqrt(light_dist * light_dist - proj * proj);
+        if (r > L.p0) visable = 0.0f;
     }
     return visable;
 }

@@ -278,8 +278,9 @@ struct tirt_ctx {
     // scene (Scene.py fields)
     int nv = 0, n = 0, nm = 0, ns = 0, nl = 0, light_count = 0;
     float bmin[3] = {0, 0, 0}, bmax[3] = {0, 0, 0};
-    tirt::DevBuf vertex, primitive, material, shape, light, env, mat_lrgb, shade_rec;
+    tirt::DevBuf vertex, primitive, material, shape, light, env, mat_lrgb, shade_rec, light_rec;
     bool shade_rec_valid = false;                  // shading records follow vertex / primitive / shape uploads and process_normal
+    bool light_rec_valid = false;                  // light records follow those and material uploads (they carry the emitter's colour)
     int env_w = 0, env_h = 0; float env_power = 0.0f;
 
     // LBVH (accel/LBvh.py fields)

@@ -110,7 +110,7 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
             if (perfect_spec == 1) {
                 radiance = radiance + throughout * mat_color;
             } else {
-                const float area = get_prim_area(sc, prim_id) * (float)sc.light_count;
+                const float area = h.area * (float)sc.light_count;              // get_prim_area of the emitter, from its shading record
                 const float light_pdf = (t * t) / (area * fCosTheta);
                 radiance = radiance + (throughout * power_heuristic(brdf_pdf, light_pdf)) * mat_color;
             }
@@ -130,21 +130,17 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
                 if (sc.light_count > 0) {
                 int lidx = (int)(tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LIGHT) * (float)sc.light_count);
                 if (lidx >= sc.light_count) lidx = sc.light_count - 1;
-                const int light_prim = sc.light[lidx];
                 const float ra = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LA);
                 const float rb = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LB);
                 v3 light_pos, light_normal;
-                get_prim_random_point_normal(sc, light_prim, ra, rb, light_pos, light_normal);
-                const int lmat = sc.primitive[(size_t)light_prim * PRI_VEC + 2];
-                const float *lm = sc.material + (size_t)lmat * MAT_VEC;
-                const v3 light_emission0 = V(lm[2], lm[3], lm[4]);
-                const float light_area = get_prim_area(sc, light_prim);
-                float light_choice_pdf = 1.0f / ((float)sc.light_count * light_area);
+                // the emitter's area, choice pdf, emission and the edges of its sampled point: per-light record (tirt_device.h, k_light_records)
+                const LightRec lr = light_sample_rec(sc.light_rec, lidx, ra, rb, light_pos, light_normal);
+                const float light_choice_pdf = lr.choice_pdf;
                 light_normal = normalized(light_normal);
                 v3 light_dir = h.pos - light_pos;
                 const float light_dist = norm(light_dir);
                 light_dir = light_dir / light_dist;
-                const v3 light_emission = light_emission0 * light_shape_visible(sc, light_prim, light_dir, light_normal, light_dist, light_choice_pdf);   // spot / laser (Scene.py:491-516)
+                const v3 light_emission = lr.emission * light_shape_visible_rec(lr, light_dir, light_normal, light_dist);   // spot / laser (Scene.py:491-516)
                 const float NdotL_surface = dot(fnormal, light_dir);            // PT_RGB.py:101-109
                 const float NdotL_light = dot(light_normal, light_dir);
                 if ((NdotL_surface < 0.0f) & (NdotL_light > 0.0f)) {
@@ -1078,18 +1074,15 @@ __global__ __launch_bounds__(SH_BLOCK, 4) void k_shade_spec(ShadeArgs paths_in_k
                         if (sc.light_count > 0) {                                                   // :240-249, Scene.sample_li
                             int lidx = (int)(tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LIGHT) * (float)sc.light_count);
                             if (lidx >= sc.light_count) lidx = sc.light_count - 1;
-                            const int light_prim = sc.light[lidx];
                             const float ra = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LA);
                             const float rb = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LB);
                             v3 light_pos, light_normal;
-                            get_prim_random_point_normal(sc, light_prim, ra, rb, light_pos, light_normal);
-                            const float light_area = get_prim_area(sc, light_prim);
-                            float light_choice_pdf = 1.0f / ((float)sc.light_count * light_area);
+                            const LightRec lr = light_sample_rec(sc.light_rec, lidx, ra, rb, light_pos, light_normal);
+                            const float light_choice_pdf = lr.choice_pdf;          // (of light_shape_visible only the laser's pdf is used by :245: it is in the record)
                             light_normal = normalized(light_normal);
                             v3 light_dir = h.pos - light_pos;
                             const float light_dist = norm(light_dir);
                             light_dir = light_dir / light_dist;
-                            (void)light_shape_visible(sc, light_prim, light_dir, light_normal, light_dist, light_choice_pdf);      // only its pdf is used by :245
                             const float NdotL_surface = dot(fnormal, light_dir);
                             const float NdotL_light = dot(light_normal, light_dir);
                             if ((NdotL_surface < 0.0f) & (NdotL_light > 0.0f)) {
