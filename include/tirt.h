@@ -155,6 +155,18 @@ int tirt_morton_download(tirt_ctx *ctx, int32_t *morton_unsorted);
 /* Scene.process_normal (Scene.py:754-798); vertex_index[nv] = owning primitive (Scene.py:128) */
 int tirt_process_normal(tirt_ctx *ctx, const int32_t *vertex_index);
 int tirt_vertex_download(tirt_ctx *ctx, float *vertex);
+/* Move whole triangles of the uploaded scene in place (csrc/tirt_dynamic.hip): vertices first ..
+ * first + count - 1 (multiples of 3) get position and normal, row i at pos + i * pos_stride floats; nrm == NULL: Scene.cal_normal's face
+ * normals.  Host pointers, or (_device) memory of ctx's device, ordered after `stream`; the rows must not change during the call.  Waits for
+ * all batches first and for its own work; tirt_lbvh_build must follow.  The scene box becomes the fminf / fmaxf box of ALL vertex rows
+ * (rows left non-finite by tirt_scene_upload are ignored; which zero a +-0 corner gets is not defined).  TIRT_ERR_ARG before anything is
+ * queued (range, stride, pointer kind, capturing stream, no scene) or written (a NaN / infinite position): the old build stays usable. */
+int tirt_vertex_update(tirt_ctx *ctx, int64_t first, int64_t count, const float *pos, int64_t pos_stride,
+                       const float *nrm, int64_t nrm_stride);
+int tirt_vertex_update_device(tirt_ctx *ctx, int64_t first, int64_t count, const float *pos, int64_t pos_stride,
+                              const float *nrm, int64_t nrm_stride, void *stream);
+/* the scene box as the context holds it: tirt_scene_upload's, or the one the last vertex update computed */
+int tirt_scene_box(tirt_ctx *ctx, float bmin[3], float bmax[3]);
 /* Scene.total_area (Scene.py:747-750) */
 int tirt_total_area(tirt_ctx *ctx, float *out);
 

@@ -3,6 +3,7 @@
 Host: OBJ/MTL ingest (``add_obj`` :59-141), analytic shapes (``add_shape`` :188-205), env
 (``add_env`` :183-185), struct packing (``setup_data_cpu`` :223-296), uploads + LBVH build
 (``setup_data_gpu`` :299-310), ``total_area`` (:747-750), ``process_normal`` (:754-798).
+``update_vertices`` (extension): moves triangles of a scene that is already on the device and rebuilds.
 Device: everything the reference declares as ``@ti.func`` on this class (``closet_hit``,
 ``closet_hit_shadow``, ``intersect_*``, ``sample_li`` ...) is HIP code in ``csrc/`` reached
 through the C-ABI (``include/tirt.h``); there is no CPU fallback.
@@ -12,6 +13,7 @@ numbers it produces (primitive order, f32 rounding points, face normals, AABB) f
 reference; ``tests/test_oracle_golden.py`` pins that against the reference's nodelist.txt.
 """
 import os
+import sys
 
 import numpy as np
 
@@ -67,6 +69,8 @@ class Scene:
         self._device_id = device_id
         self._ctx = None
         self._light_area = np.zeros(1, np.float32)
+        self._area_called = False
+        self._vertex_np_stale = False       # update_vertices moved the device's rows: vertex_np is read back when it is next asked for
 
         self.vertex = DeviceField("vertex", self, lambda: self.ctx.vertex_download(self.vertex_count))
         self.primitive = DeviceField("primitive", self, lambda: self.primitive_np.copy())
@@ -84,6 +88,19 @@ class Scene:
                 dev = int(os.environ.get("LOCAL_RANK", "0"))
             self._ctx = _native.Context(dev)
         return self._ctx
+
+    @property
+    def vertex_np(self):
+        """the packed vertex rows as setup_data_cpu made them (before process_normal), following update_vertices"""
+        if self._vertex_np_stale:
+            self._vertex_np = self.ctx.vertex_download(self.vertex_count)
+            self._vertex_np_stale = False
+        return self._vertex_np
+
+    @vertex_np.setter
+    def vertex_np(self, value):
+        self._vertex_np = value
+        self._vertex_np_stale = False
 
     # -- ingest -------------------------------------------------------------------------------
     def add_obj(self, filename):
@@ -246,8 +263,101 @@ class Scene:
     def total_area(self):
         """Scene.py:747-750 (accumulates, like the reference's ``+=``)."""
         self._light_area[0] += np.float32(self.ctx.total_area())
+        self._area_called = True
 
     def process_normal(self):
         """Scene.py:754-798: angle x area weighted smooth normals via a BVH point query."""
+        self.vertex_np                                   # (a stale mirror is read back while the device still holds the un-smoothed normals)
         self.ctx.process_normal(self.vertex_index_np)
         self.normals_processed = True
+
+    # -- moving geometry (extension, no reference equivalent) ------------------------------------------
+    def _check_rows(self, rows, name, torch):
+        """rows of update_vertices -> (address, vertices, floats per row step, the object that keeps the memory alive)"""
+        fn = "Scene.update_vertices"
+        is_tensor = torch is not None and isinstance(rows, torch.Tensor)
+        if not is_tensor and not isinstance(rows, np.ndarray):
+            raise TypeError("%s: %s must be a numpy array or a torch.Tensor, got %s" % (fn, name, type(rows).__name__))
+        if rows.dtype != (torch.float32 if is_tensor else np.float32):
+            raise TypeError("%s: %s must be float32, got %s" % (fn, name, rows.dtype))
+        shape = tuple(rows.shape)
+        if not ((len(shape) == 2 and shape[1] == 3) or (len(shape) == 3 and shape[1:] == (3, 3))):
+            raise ValueError("%s: %s must be [k, 3] or [k/3, 3, 3], got shape %s" % (fn, name, shape))
+        k = shape[0] * (3 if len(shape) == 3 else 1)
+        if k % 3:
+            raise ValueError("%s: %s must hold whole triangles, got %d vertices" % (fn, name, k))
+        if not is_tensor:
+            rows = np.ascontiguousarray(rows).reshape(-1, 3)
+            return rows.ctypes.data, k, 3, rows
+        if rows.device.type != "cuda":
+            raise TypeError("%s: %s must be a numpy array or a tensor on the GPU, got a %s tensor" % (fn, name, rows.device.type))
+        dev = torch.device("cuda", self._ctx.device_id)
+        if rows.device != dev:
+            raise ValueError("%s: %s is on %s, the scene's context on %s" % (fn, name, rows.device, dev))
+        if k == 0:
+            return 0, 0, 3, rows
+        if rows.stride(-1) != 1:
+            raise ValueError("%s: the last dimension of %s must have stride 1, got %d" % (fn, name, rows.stride(-1)))
+        step = rows.stride(-2)
+        if rows.dim() == 3 and shape[0] > 1 and rows.stride(0) != 3 * step:
+            raise ValueError("%s: the vertices of %s must be evenly spaced (stride(0) == 3 * stride(1)), got strides %s" % (fn, name, tuple(rows.stride())))
+        if k > 1 and step < 3:
+            raise ValueError("%s: rows of %s overlap (stride = %d < 3)" % (fn, name, step))
+        return rows.data_ptr(), k, step, rows
+
+    def update_vertices(self, positions, normals=None, first_vertex=0):
+        """Move triangles of a scene that is on the device (after setup_data_gpu) and rebuild the LBVH: vertices ``first_vertex ..
+        first_vertex + k - 1`` (whole triangles, in the order of ``vertex_np``) get ``positions`` -- float32 ``[k, 3]`` or ``[k/3, 3, 3]``, a
+        numpy array or a torch tensor on the context's device (any row stride with ``stride(-1) == 1``, e.g. ``buf[:, :3]``; the update runs
+        after the work queued on ``torch.cuda.current_stream``, nothing has to be synchronised first).  ``normals`` of the same kind and shape
+        are stored as they are; without them the triangles get their face normals, as ``cal_normal`` gives a mesh without normals.
+        Afterwards the device state -- vertex rows, scene box, Morton codes, trees, shading tables, smooth normals if ``process_normal`` had
+        been applied (the rows that are not moved are first given their un-smoothed normals back from ``vertex_np``, so a partial update does
+        not smooth them twice) -- is bit for bit that of a fresh scene built from the moved positions, and ``vertex_np``, ``minboundarynp`` /
+        ``maxboundarynp`` (the ``bvh``'s too) and ``light_area`` follow.  The call waits for the device (include/tirt.h, tirt_vertex_update).
+        The film is not touched: clear it (``ctx.film_clear()``) or keep accumulating, and re-frame the camera if the box matters to it."""
+        fn = "Scene.update_vertices"
+        torch = sys.modules.get("torch")                  # a tensor cannot be passed without it: never imported here
+        if torch is not None and not hasattr(torch, "Tensor"):
+            torch = None
+        if self.bvh is None or self._ctx is None:
+            raise RuntimeError("%s: the scene is not on the device yet (setup_data_cpu / setup_data_gpu first)" % fn)
+        pos_ptr, k, pos_step, keep_pos = self._check_rows(positions, "positions", torch)
+        nrm_ptr, nrm_step, keep_nrm = 0, 3, None
+        on_device = not isinstance(keep_pos, np.ndarray)
+        if normals is not None:
+            nrm_ptr, nk, nrm_step, keep_nrm = self._check_rows(normals, "normals", torch)
+            if isinstance(keep_nrm, np.ndarray) == on_device:
+                raise TypeError("%s: positions and normals must both be numpy arrays or both be tensors on the GPU" % fn)
+            if nk != k:
+                raise ValueError("%s: normals hold %d vertices, positions %d" % (fn, nk, k))
+        if int(first_vertex) != first_vertex or first_vertex < 0 or first_vertex % 3:
+            raise ValueError("%s: first_vertex must be a non-negative multiple of 3 (whole triangles), got %r" % (fn, first_vertex))
+        if first_vertex + k > self.vertex_count:
+            raise ValueError("%s: vertices %d .. %d are past the scene's %d" % (fn, first_vertex, first_vertex + k - 1, self.vertex_count))
+        if k == 0:
+            return
+        ctx = self._ctx
+        smoothed = getattr(self, "normals_processed", False)
+        raw = self.vertex_np if smoothed else None        # the rows before process_normal (never stale while the scene is smoothed: see below)
+        stream = torch.cuda.current_stream(keep_pos.device).cuda_stream if on_device else 0
+        ctx.vertex_update(int(first_vertex), k, pos_ptr, pos_step, nrm_ptr, nrm_step, device=on_device, stream=stream)
+        del keep_pos, keep_nrm                           # (the call has waited for the device)
+        self._vertex_np_stale = True                     # from here on the device holds other rows and another box than the mirrors
+        try:
+            if smoothed:
+                # the rows that are not moved hold SMOOTHED normals, and process_normal smooths what it finds: they get the normals a fresh
+                # scene starts from again, so that the pass below repeats a fresh scene's and not a second round on top of the first
+                for lo_v, hi_v in ((0, int(first_vertex)), (int(first_vertex) + k, self.vertex_count)):
+                    if hi_v > lo_v:
+                        rows = np.ascontiguousarray(raw[lo_v:hi_v, 0:6])
+                        ctx.vertex_update(lo_v, hi_v - lo_v, rows.ctypes.data, 6, rows.ctypes.data + 12, 6)
+            ctx.lbvh_build()
+        finally:
+            lo, hi = ctx.scene_box()
+            self.minboundarynp[0, :] = lo                # in place: the Bvh holds the same arrays
+            self.maxboundarynp[0, :] = hi
+        if smoothed:
+            self.process_normal()                        # (reads vertex_np back first: the mirror keeps the un-smoothed rows)
+        if self._area_called:
+            self._light_area[0] = np.float32(0.0) + np.float32(ctx.total_area())

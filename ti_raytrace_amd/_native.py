@@ -76,6 +76,9 @@ SIGNATURES = {
     "tirt_morton_download": (C.c_int, [_vp, _i32p]),
     "tirt_process_normal": (C.c_int, [_vp, _i32p]),
     "tirt_vertex_download": (C.c_int, [_vp, _f32p]),
+    "tirt_vertex_update": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64]),
+    "tirt_vertex_update_device": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "tirt_scene_box": (C.c_int, [_vp, _f32p, _f32p]),
     "tirt_total_area": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "tirt_camera_set": (C.c_int, [_vp, _f32p, _f32p, _f32p, C.c_float, C.c_float, C.c_float, C.c_float]),
     "tirt_film_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -282,6 +285,23 @@ class Context:
         out = np.zeros((nv, 9), np.float32)
         check(lib().tirt_vertex_download(self.handle, out.reshape(-1)))
         return out
+
+    def vertex_update(self, first, count, pos, pos_stride=3, nrm=0, nrm_stride=3, device=False, stream=0):
+        """tirt_vertex_update (device=False: `pos` / `nrm` are integer HOST addresses) or tirt_vertex_update_device (integer device
+        addresses, `stream` a hipStream_t handle, 0 = the null stream).  nrm = 0: face normals.  Strides in floats.  The LBVH counts as
+        not built afterwards: lbvh_build() next (include/tirt.h)."""
+        if device:
+            check(lib().tirt_vertex_update_device(self.handle, int(first), int(count), _vp(int(pos) or None), int(pos_stride),
+                                                  _vp(int(nrm) or None), int(nrm_stride), _vp(int(stream) or None)))
+        else:
+            check(lib().tirt_vertex_update(self.handle, int(first), int(count), _vp(int(pos) or None), int(pos_stride),
+                                           _vp(int(nrm) or None), int(nrm_stride)))
+
+    def scene_box(self):
+        """(bmin[3], bmax[3]) float32: the scene box as the context holds it"""
+        lo, hi = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        check(lib().tirt_scene_box(self.handle, lo, hi))
+        return lo, hi
 
     def total_area(self):
         v = C.c_float(0.0)

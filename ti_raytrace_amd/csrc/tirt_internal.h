@@ -376,6 +376,7 @@ struct tirt_ctx {
     // context's stream after and before the caller's (made on first use)
     tirt::DevBuf query_mem; size_t query_chunk = (size_t)1 << 21;
     hipEvent_t query_ev_in = nullptr, query_ev_out = nullptr;
+    tirt::DevBuf dyn_mem;                         // geometry updates (tirt_dynamic.hip): validation flag, scene box and its block partials, the staged rows of a host update
 
     // RCCL communicator of tirt_comm_init (single-process multi-GPU film reduce; opaque ncclComm_t)
     void *comm = nullptr; int comm_rank = 0, comm_size = 0;
