@@ -242,6 +242,27 @@ int tirt_film_download(tirt_ctx *ctx, float *hdr, float *rgb);
 int tirt_film_export_device(tirt_ctx *ctx, void *dev_dst);
 int tirt_film_import_device(tirt_ctx *ctx, const void *dev_src);
 
+/* Feature buffers of the path tracer (csrc/tirt_aov.hip; no reference counterpart).  While enabled, every frame of tirt_pt_rgb_render /
+ * tirt_pt_spec_render also folds, per pixel of this context's tiles, the closest hit of that frame's camera ray into TIRT_AOV_WORDS f32 with the
+ * film's running mean (integrator/PT_RGB.py:134-136), frames in ascending order:
+ *   TIRT_AOV_ALBEDO  3 words: the material colour as TIRT_DEBUG_ALBEDO reads it (no sRGB conversion)
+ *   TIRT_AOV_NORMAL  3 words: the shading normal as TIRT_DEBUG_NORMAL reads it, NOT mapped to [0, 1] and not face-forwarded (a NaN stays a NaN)
+ *   TIRT_AOV_DEPTH   1 word : the hit distance t
+ *   TIRT_AOV_ALPHA   1 word : 1
+ * and zeros on a miss.  hdr is not touched; pixels of other ranks' tiles are never written (zero: the ranks' records sum to the whole).
+ * tirt_bdpt_rgb_render, tirt_bdpt_spec_render and tirt_debug_render leave the records alone.  tirt_film_clear zeroes them.
+ * tirt_aov_enable: needs a film.  on != 0 allocates and zeroes the records, on == 0 frees them; tirt_film_create disables.  Waits for pending work.
+ * tirt_aov_download: out[W*H*TIRT_AOV_WORDS], pixel p = i*H + j as hdr.  tirt_aov_export_device: the same into device memory, as
+ * tirt_film_export_device.  TIRT_ERR_ARG when not enabled, without a film, or for a null pointer. */
+#define TIRT_AOV_WORDS 8
+#define TIRT_AOV_ALBEDO 0
+#define TIRT_AOV_NORMAL 3
+#define TIRT_AOV_DEPTH 6
+#define TIRT_AOV_ALPHA 7
+int tirt_aov_enable(tirt_ctx *ctx, int on);
+int tirt_aov_download(tirt_ctx *ctx, float *out);
+int tirt_aov_export_device(tirt_ctx *ctx, void *dev_dst);
+
 /* Scene.closet_hit / closet_hit_shadow on a batch of rays (Scene.py:702-744, 671-699).  The default (ordered) traversal returns the
  * reference's hit bit for bit for every ray but the in-plane rays named under "traversal_tree" above; rays that start more than 8
  * scene extents away are traced without distance culling (from there the reference's own distances are rounding noise), so they

@@ -20,13 +20,14 @@ def write_png(rgb_film_np, path):
 
 
 class example:
-    def __init__(self, imgSizeX, imgSizeY, sample_count, device_id=None):
+    def __init__(self, imgSizeX, imgSizeY, sample_count, device_id=None, aov=None):
         self.imgSizeX = imgSizeX
         self.imgSizeY = imgSizeY
         self.sample_count = sample_count
         self.cam = Camera.Camera(imgSizeX, imgSizeY, sample_count)
         self.scene = Scene.Scene(device_id)
         self.integrator = None
+        self.aov = aov                       # extension: True / False sets the path tracer's `aov` (feature buffers) when the scene is built; None leaves it
         self.out_path = "out.png"
         self.exposure = 0.5                  # example/Example.py:43
         # progressive preview (example/Example.py:41-46 tone-maps and blits to a ti.GUI window every frame): headless here --
@@ -37,6 +38,8 @@ class example:
     def build_scene(self):
         self.scene.setup_data_cpu()
         self.integrator.setup_data_cpu()
+        if self.aov is not None:
+            self.integrator.aov = bool(self.aov)
         self.integrator.setup_data_gpu()
         self.scene.setup_data_gpu()
         # hint for the device library: this job renders sample_count frames (bounds its batch buffers)

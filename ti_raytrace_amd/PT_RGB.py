@@ -21,7 +21,7 @@ def default_tile_size(H):
 
 class PathTrace:
     def __init__(self, imgSizeX, imgSizeY, cam, scene, stack_size,
-                 seed=1, tile_rank=0, tile_count=1, tile_size=None, flags=0):
+                 seed=1, tile_rank=0, tile_count=1, tile_size=None, flags=0, aov=False):
         self.imgSizeX = imgSizeX
         self.imgSizeY = imgSizeY
         self.cam = cam
@@ -34,6 +34,34 @@ class PathTrace:
         self.flags = flags
         self.hdr = DeviceField("hdr", scene, lambda: self._download(True))
         self.rgb_film = DeviceField("rgb_film", scene, lambda: self._download(False))
+        # extension: feature buffers of the film's own camera rays, for a denoiser or a compositor
+        self.aov = aov
+        self._aov_fields()
+
+    def _aov_fields(self):
+        """the feature buffers as fields (aov=True): first-hit albedo and shading normal [W, H, 3], depth and coverage [W, H], means over the
+        film's own camera rays (include/tirt.h, tirt_aov_enable).  Each to_numpy() is one download of the whole record."""
+        from . import _native
+        words = {"albedo": slice(_native.AOV_ALBEDO, _native.AOV_ALBEDO + 3), "normal": slice(_native.AOV_NORMAL, _native.AOV_NORMAL + 3),
+                 "depth": _native.AOV_DEPTH, "alpha": _native.AOV_ALPHA}
+        for name, w in words.items():
+            setattr(self, name, DeviceField(name, self.scene, lambda w=w: np.ascontiguousarray(self.aov_to_numpy()[:, :, w])))
+
+    def aov_to_numpy(self):
+        """[W, H, 8] float32: albedo3, normal3, depth, alpha"""
+        return self.scene.ctx.aov_download(self.imgSizeX, self.imgSizeY)
+
+    def aov_to_torch(self):
+        """The same as a float32 tensor on the context's device, filled device to device (tirt_aov_export_device)."""
+        try:
+            import torch
+        except ImportError as exc:
+            raise ImportError("aov_to_torch needs PyTorch (ROCm build); aov_to_numpy and the C-ABI tirt_aov_download work without it") from exc
+        from . import _native
+        ctx = self.scene.ctx
+        out = torch.empty((self.imgSizeX, self.imgSizeY, _native.AOV_WORDS), dtype=torch.float32, device=torch.device("cuda", ctx.device_id))
+        ctx.aov_export_device(out.data_ptr())
+        return out
 
     def _download(self, hdr):
         h, r = self.scene.ctx.film_download(self.imgSizeX, self.imgSizeY, want_hdr=hdr, want_rgb=not hdr)
@@ -45,6 +73,8 @@ class PathTrace:
     def setup_data_gpu(self):
         self.scene.ctx.film_create(self.imgSizeX, self.imgSizeY, self.tile_rank, self.tile_count, self.tile_size)
         self.cam.attach(self.scene.ctx)
+        if self.aov:
+            self.scene.ctx.aov_enable(True)
 
     def render(self):
         """One frame at ``cam.frame`` (the caller advances it with ``cam.update_frame()``)."""

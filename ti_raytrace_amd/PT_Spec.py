@@ -14,6 +14,7 @@ from . import HeroSample as Hero
 from . import Rgb2Spec as RGB2SPEC
 from . import Sky
 from . import Spectrum as Spec
+from . import PT_RGB
 from .PT_RGB import default_tile_size
 from .Scene import DeviceField
 
@@ -25,7 +26,7 @@ _TABLE_CACHE = {}        # (res, who built it) -> (scale, data): the optimiser's
 
 class PathTrace:
     def __init__(self, imgSizeX, imgSizeY, cam, scene, stack_size, seed=1, tile_rank=0, tile_count=1, tile_size=None, flags=0,
-                 spec_table_path=None):
+                 spec_table_path=None, aov=False):
         self.imgSizeX = imgSizeX
         self.imgSizeY = imgSizeY
         self.lambda_min = 10000
@@ -47,6 +48,10 @@ class PathTrace:
         self.spec_table_path = spec_table_path
         self.hdr = DeviceField("hdr", scene, lambda: self._download(True))
         self.rgb_film = DeviceField("rgb_film", scene, lambda: self._download(False))
+        self.aov = aov                               # the feature buffers of PT_RGB.PathTrace: the camera rays and the launch are the same
+        self._aov_fields()
+
+    _aov_fields, aov_to_numpy, aov_to_torch = PT_RGB.PathTrace._aov_fields, PT_RGB.PathTrace.aov_to_numpy, PT_RGB.PathTrace.aov_to_torch
 
     def _download(self, hdr):
         h, r = self.scene.ctx.film_download(self.imgSizeX, self.imgSizeY, want_hdr=hdr, want_rgb=not hdr)
@@ -124,6 +129,8 @@ class PathTrace:
         ctx = self.scene.ctx
         ctx.film_create(self.imgSizeX, self.imgSizeY, self.tile_rank, self.tile_count, self.tile_size)
         self.cam.attach(ctx)
+        if self.aov:
+            ctx.aov_enable(True)
         self.setup_tables(ctx.spec_table_build)
         ctx.spectral_upload(self.tables())
 

@@ -56,6 +56,13 @@ DEBUG_FNORMAL = 1
 DEBUG_NORMAL = 2
 DEBUG_GNORMAL = 3
 
+# the words of a pixel's feature-buffer record (include/tirt.h, TIRT_AOV_*)
+AOV_WORDS = 8
+AOV_ALBEDO = 0
+AOV_NORMAL = 3
+AOV_DEPTH = 6
+AOV_ALPHA = 7
+
 # name -> (restype, argtypes).  tests/test_abi.py checks every name against include/tirt.h.
 _vp = C.c_void_p
 SIGNATURES = {
@@ -91,6 +98,9 @@ SIGNATURES = {
     "tirt_film_download": (C.c_int, [_vp, _vp, _vp]),
     "tirt_film_export_device": (C.c_int, [_vp, _vp]),
     "tirt_film_import_device": (C.c_int, [_vp, _vp]),
+    "tirt_aov_enable": (C.c_int, [_vp, C.c_int]),
+    "tirt_aov_download": (C.c_int, [_vp, _vp]),
+    "tirt_aov_export_device": (C.c_int, [_vp, _vp]),
     "tirt_trace_closest": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _vp]),
     "tirt_trace_shadow": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _vp]),
     "tirt_query_closest": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
@@ -372,6 +382,19 @@ class Context:
 
     def film_import_device(self, dev_ptr):
         check(lib().tirt_film_import_device(self.handle, C.c_void_p(int(dev_ptr))))
+
+    def aov_enable(self, on=True):
+        """tirt_aov_enable: the feature buffers of the film (include/tirt.h), zeroed; on=False frees them"""
+        check(lib().tirt_aov_enable(self.handle, 1 if on else 0))
+
+    def aov_download(self, W, H):
+        """[W, H, AOV_WORDS] float32: albedo3, normal3, depth, alpha per pixel"""
+        out = np.zeros((W, H, AOV_WORDS), np.float32)
+        check(lib().tirt_aov_download(self.handle, _ptr(out)))
+        return out
+
+    def aov_export_device(self, dev_ptr):
+        check(lib().tirt_aov_export_device(self.handle, C.c_void_p(int(dev_ptr))))
 
     def trace_closest(self, rays, stack_size=64, flags=0):
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)

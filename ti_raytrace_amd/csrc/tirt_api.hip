@@ -419,6 +419,7 @@ int tirt_create(int device_id, tirt_ctx **out)
     for (Lane &L : c->lanes) {
         TIRT_HIP(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
         TIRT_HIP(hipEventCreateWithFlags(&L.film_done, hipEventDisableTiming));
+        TIRT_HIP(hipEventCreateWithFlags(&L.aov_done, hipEventDisableTiming));
     }
     memset(&c->cam, 0, sizeof(c->cam));
     int optin = 0;
@@ -442,7 +443,7 @@ void tirt_destroy(tirt_ctx *c)
     drain_render_events(c);
     DevBuf *bufs[] = {&c->vertex, &c->primitive, &c->material, &c->shape, &c->light, &c->env, &c->mat_lrgb, &c->shade_rec, &c->light_rec, &c->morton_unsorted, &c->keys_a,
                       &c->keys_b, &c->vals_a, &c->vals_b, &c->hist, &c->morton_sorted, &c->bvh_node, &c->compact, &c->parent,
-                      &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb,
+                      &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb, &c->aov,
                       &c->counters_mem, &c->spill, &c->trace_stage, &c->debug_mem, &c->query_mem, &c->dyn_mem, &c->dev_counters, &c->bdpt_px, &c->timeline, &c->pvb_set[0].count, &c->pvb_set[0].cand, &c->pvb_set[0].bound, &c->pvb_set[1].count, &c->pvb_set[1].cand, &c->pvb_set[1].bound, &c->pvb_stat, &c->pvb_tmp};
     for (DevBuf *b : bufs) b->release();
     for (auto &bl : c->bd) {
@@ -455,6 +456,7 @@ void tirt_destroy(tirt_ctx *c)
         DevBuf *lb[] = {&L.path_mem, &L.counters_mem, &L.spill};
         for (DevBuf *b : lb) b->release();
         if (L.film_done) (void)hipEventDestroy(L.film_done);
+        if (L.aov_done) (void)hipEventDestroy(L.aov_done);
         if (L.stream) (void)hipStreamDestroy(L.stream);
     }
     c->spec_mem.release(); c->spec_dev.release();
@@ -470,6 +472,10 @@ void tirt_destroy(tirt_ctx *c)
 // film readers/writers on the main stream run after the last film update of the render lanes
 #define AFTER_RENDER(c)                                                            \
     do { if ((c)->last_film) TIRT_HIP(hipStreamWaitEvent((c)->stream, (c)->last_film, 0)); } while (0)
+
+// the same for the feature buffers (tirt_aov.hip): after the last k_aov
+#define AFTER_AOV(c)                                                               \
+    do { if ((c)->last_aov) TIRT_HIP(hipStreamWaitEvent((c)->stream, (c)->last_aov, 0)); } while (0)
 
 #define CTX_NOFLUSH(c)                                                             \
     TIRT_REQUIRE(c, "null context");                                               \
@@ -737,6 +743,10 @@ int tirt_film_create(tirt_ctx *c, int W, int H, int tile_rank, int tile_count, i
     TIRT_REQUIRE(W >= 1 && H >= 1 && (long long)W * H < (1ll << 30), "tirt_film_create: bad size");
     TIRT_REQUIRE(tile_count >= 1 && tile_rank >= 0 && tile_rank < tile_count && tile_size >= 1, "tirt_film_create: bad tiling");
     const long NP = (long)W * H;
+    if (c->aov.p) {                              // the feature buffers belong to the film: a new film starts without them
+        if (sync_all(c)) return TIRT_ERR_HIP;
+        c->aov.release(); c->last_aov = nullptr;
+    }
     if (c->hdr.ensure(sizeof(float) * 3 * (size_t)NP) || c->rgb.ensure(sizeof(float) * 3 * (size_t)NP)) return TIRT_ERR_HIP;
     c->W = W; c->H = H; c->tile_rank = tile_rank; c->tile_count = tile_count; c->tile_size = tile_size;
     c->tile_blocked = (H % 8 == 0 && tile_size % (8 * H) == 0 && ((long)W * H) % tile_size == 0) ? 1 : 0;       // local_to_pixel
@@ -761,6 +771,48 @@ int tirt_film_clear(tirt_ctx *c)
     if (c->bdpt_px.p) TIRT_HIP(hipMemsetAsync(c->bdpt_px.p, 0, c->bdpt_px.bytes, c->stream));
     TIRT_HIP(hipMemsetAsync(c->hdr.p, 0, sizeof(float) * 3 * (size_t)c->W * c->H, c->stream));
     TIRT_HIP(hipMemsetAsync(c->rgb.p, 0, sizeof(float) * 3 * (size_t)c->W * c->H, c->stream));
+    if (c->aov.p) {
+        AFTER_AOV(c);
+        TIRT_HIP(hipMemsetAsync(c->aov.p, 0, sizeof(float) * TIRT_AOV_WORDS * (size_t)c->W * c->H, c->stream));
+    }
+    return TIRT_OK;
+}
+
+int tirt_aov_enable(tirt_ctx *c, int on)
+{
+    CTX(c);
+    TIRT_REQUIRE(c->hdr.p, "tirt_aov_enable: film not created");
+    if (sync_all(c)) return TIRT_ERR_HIP;      // no k_aov in flight while the records come or go
+    c->last_aov = nullptr;
+    if (!on) { c->aov.release(); return TIRT_OK; }
+    const size_t bytes = sizeof(float) * TIRT_AOV_WORDS * (size_t)c->W * c->H;
+    if (c->aov.ensure(bytes)) return TIRT_ERR_HIP;
+    TIRT_HIP(hipMemsetAsync(c->aov.p, 0, bytes, c->stream));
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    return TIRT_OK;
+}
+
+int tirt_aov_download(tirt_ctx *c, float *out)
+{
+    CTX(c);
+    AFTER_AOV(c);
+    TIRT_REQUIRE(c->hdr.p, "tirt_aov_download: film not created");
+    TIRT_REQUIRE(c->aov.p, "tirt_aov_download: feature buffers not enabled (tirt_aov_enable)");
+    TIRT_REQUIRE(out, "tirt_aov_download: null pointer");
+    TIRT_HIP(hipMemcpyAsync(out, c->aov.p, sizeof(float) * TIRT_AOV_WORDS * (size_t)c->W * c->H, hipMemcpyDeviceToHost, c->stream));
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    return TIRT_OK;
+}
+
+int tirt_aov_export_device(tirt_ctx *c, void *dev_dst)
+{
+    CTX(c);
+    AFTER_AOV(c);
+    TIRT_REQUIRE(c->hdr.p, "tirt_aov_export_device: film not created");
+    TIRT_REQUIRE(c->aov.p, "tirt_aov_export_device: feature buffers not enabled (tirt_aov_enable)");
+    TIRT_REQUIRE(dev_dst, "tirt_aov_export_device: null pointer");
+    TIRT_HIP(hipMemcpyAsync(dev_dst, c->aov.p, sizeof(float) * TIRT_AOV_WORDS * (size_t)c->W * c->H, hipMemcpyDeviceToDevice, c->stream));
+    TIRT_HIP(hipStreamSynchronize(c->stream));
     return TIRT_OK;
 }
 

@@ -263,6 +263,7 @@ struct DevCounters {          // lives in device memory; accumulated by the kern
 struct Lane {
     hipStream_t stream = nullptr;
     hipEvent_t film_done = nullptr; bool film_recorded = false;
+    hipEvent_t aov_done = nullptr;               // after this lane's last k_aov (tirt_aov.hip)
     size_t path_capacity = 0;
     DevBuf path_mem, counters_mem, spill;
     PathState ps;
@@ -311,6 +312,8 @@ struct tirt_ctx {
     int W = 0, H = 0, tile_rank = 0, tile_count = 1, tile_size = 4096, tile_blocked = 0;
     long npix_local = 0;
     tirt::DevBuf hdr, rgb;
+    tirt::DevBuf aov;                             // tirt_aov_enable: TIRT_AOV_WORDS f32 per pixel of the film (p == nullptr: disabled)
+    hipEvent_t last_aov = nullptr;                // aov_done of the most recent batch (any lane): the next k_aov and the records' main-stream consumers wait for it
 
     // wavefront state
     tirt::Lane lanes[TIRT_MAX_LANES];
@@ -452,6 +455,7 @@ struct TraceJob {
 int trace_rays(tirt_ctx *c, const TraceJob &j);
 int trace_rays_prepare(tirt_ctx *c, int lane);      // allocates what trace_rays needs on that lane at bdpt_stack_size (stack spill, fetch cursors)
 int debug_render(tirt_ctx *c, uint32_t frame, uint32_t seed, int mode, int stack_size, int flags);      // tirt_debug.hip
+int aov_launch(tirt_ctx *c, Lane &L, const TileMap &tm, int P, int F, uint32_t frame_begin);      // tirt_aov.hip: k_aov over a batch's bounce-0 hits
 int query_closest(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, int stack_size, int flags, float *out_t, int32_t *out_prim,
                   float *out_hit, int64_t hit_stride, int32_t *counts, void *stream);      // tirt_query.hip
 int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, const float *tmax, int64_t tmax_stride, float tmax_all,

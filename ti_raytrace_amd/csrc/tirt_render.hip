@@ -1377,6 +1377,7 @@ int pt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed,
             if (int rc = (b == 0) ? launch_trace<KIND_CLOSEST>(c, st, a, flags, grid_full) : launch_trace<KIND_MIXED>(c, st, a, flags, grid_full)) return rc;
             if (!(b == 0 && use_beams)) stamp(evc, false);
             c->launches_trace_closest++;
+            if (b == 0 && c->aov.p) { if (int rc = aov_launch(c, L, tm, P, F, f0)) return rc; }      // the camera rays' hits are complete: the feature buffers read them
 
             stamp(evh, true);
             if (spec)
