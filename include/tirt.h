@@ -82,6 +82,8 @@ int tirt_sync(tirt_ctx *ctx);
  *          "overlap_lanes" (1..8, default 4) -- wavefront batches in flight on separate streams
  *          "trace_lds_depth" / "trace_refill_min" / "trace_node_min" / "trace_grid" / "trace_grid_alone" / "trace_slices" /
  *          "shade_grid" -- kernel tuning
+ *          "shade_specialize" (0/1, default 1) -- k_shade / k_shade_spec are compiled for a few scene feature sets (tirt_shade_features); 1 launches the
+ *            narrowest instantiation that covers the scene, 0 the generic kernel for every scene.  Same films bit for bit either way
  *          "query_chunk_rays" (256 .. 2^27, default 2^21) -- rays per chunk of tirt_query_closest / tirt_query_occluded (48 B of scratch each)
  *          "bdpt_bounded" (0/1, default 1) -- BDPT connection rays are cut off at their target distance (same
  *            visibility answers as the full closest-hit query; 0 = reference-style full query, for cross-checks)
@@ -135,6 +137,17 @@ int tirt_material_upload(tirt_ctx *ctx, const float *material, int nm);
 
 /* Texture.setup_data_gpu (texture/Texture.py:38-39): rgb_packed[w*h] 0xRRGGBB, index x*h + y */
 int tirt_env_upload(tirt_ctx *ctx, const int32_t *rgb_packed, int w, int h, float power);
+
+/* The scene feature word: which shading code the uploaded tables can reach, and so which instantiation of the shading kernels a render
+ * launches (option "shade_specialize").  Bits: 1 a MAT_GLASS material row, 2 environment lit (power != 0 or a texel that is not black),
+ * 4 / 32 / 8 / 64 a triangle / a sphere / a spot or laser / an emitter of unknown kind on the light list, 16 light_count == 0.
+ * tirt_shade_features: out[0] = the word the context holds (refreshed by every scene, material, environment and vertex upload),
+ * out[1] = the "shade_specialize" option.  tirt_shade_features_host: the same rule on host tables, without a context or a device
+ * (env may be NULL: lit if env_power != 0). */
+int tirt_shade_features(tirt_ctx *ctx, uint32_t *out);
+int tirt_shade_features_host(const float *material, int nm, const int32_t *primitive, int n, const float *shape, int ns,
+                             const int32_t *light, int light_count, const int32_t *env, int env_w, int env_h, float env_power,
+                             uint32_t *out);
 
 /* LBvh.Bvh.setup_data_gpu (accel/LBvh.py:192-226): Morton codes, stable radix sort, Karras
  * topology, leaf boxes, bottom-up refit, DFS flatten -- all on device. */

@@ -63,6 +63,14 @@ AOV_NORMAL = 3
 AOV_DEPTH = 6
 AOV_ALPHA = 7
 
+# bits of the scene feature word (include/tirt.h, tirt_shade_features)
+SF_GLASS, SF_ENV, SF_LIGHT_TRI, SF_LIGHT_SPOT_LASER, SF_NO_LIGHT, SF_LIGHT_SPHERE, SF_LIGHT_OTHER = 1, 2, 4, 8, 16, 32, 64
+
+# context options that select code rather than tune it: name -> (default, meaning).  (The tuning options are listed in include/tirt.h.)
+OPTIONS = {
+    "shade_specialize": (1, "1: the narrowest instantiation of k_shade / k_shade_spec that covers the scene's feature word; 0: the generic kernel"),
+}
+
 # name -> (restype, argtypes).  tests/test_abi.py checks every name against include/tirt.h.
 _vp = C.c_void_p
 SIGNATURES = {
@@ -77,6 +85,9 @@ SIGNATURES = {
                                     _f32p, C.c_int, _i32p, C.c_int, C.c_int, _f32p, _f32p]),
     "tirt_material_upload": (C.c_int, [_vp, _f32p, C.c_int]),
     "tirt_env_upload": (C.c_int, [_vp, _i32p, C.c_int, C.c_int, C.c_float]),
+    "tirt_shade_features": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
+    "tirt_shade_features_host": (C.c_int, [_f32p, C.c_int, _i32p, C.c_int, _f32p, C.c_int, _i32p, C.c_int, _vp, C.c_int, C.c_int, C.c_float,
+                                           C.POINTER(C.c_uint32)]),
     "tirt_lbvh_build": (C.c_int, [_vp]),
     "tirt_lbvh_download": (C.c_int, [_vp, _vp, _vp, _vp]),
     "tirt_traversal_tree_download": (C.c_int, [_vp, _vp]),
@@ -265,6 +276,12 @@ class Context:
     def env_upload(self, packed, power):
         packed = np.ascontiguousarray(packed, np.int32)
         check(lib().tirt_env_upload(self.handle, packed.reshape(-1), packed.shape[0], packed.shape[1], float(power)))
+
+    def shade_features(self):
+        """(feature word, shade_specialize option) of the context: include/tirt.h, tirt_shade_features"""
+        out = (C.c_uint32 * 2)()
+        check(lib().tirt_shade_features(self.handle, out))
+        return int(out[0]), int(out[1])
 
     def lbvh_build(self):
         check(lib().tirt_lbvh_build(self.handle))
@@ -500,6 +517,18 @@ class Context:
         out = np.zeros((n, out_stride), np.float32)
         check(lib().tirt_kat_spec(self.handle, int(which), inp.reshape(-1), stride, out.reshape(-1), out_stride, n))
         return out
+
+
+def shade_features_host(material, primitive, shape, light, light_count, env=None, env_power=0.0):
+    """The scene feature word of host tables (Scene.material_np, primitive_np, shape_np, light_np, light_count, Texture.np_img): needs no device."""
+    material = np.ascontiguousarray(material, np.float32); primitive = np.ascontiguousarray(primitive, np.int32)
+    shape = np.ascontiguousarray(shape, np.float32); light = np.ascontiguousarray(light, np.int32)
+    env = None if env is None else np.ascontiguousarray(env, np.int32)
+    out = C.c_uint32(0)
+    check(lib().tirt_shade_features_host(material.reshape(-1), material.shape[0], primitive.reshape(-1), primitive.shape[0], shape.reshape(-1), shape.shape[0],
+                                         light.reshape(-1), int(light_count), _ptr(env), 0 if env is None else env.shape[0], 0 if env is None else env.shape[1],
+                                         float(env_power), C.byref(out)))
+    return int(out.value)
 
 
 def device_count():

@@ -128,6 +128,42 @@ __global__ void k_light_records(SceneView s, float4 *rec)
     }
     r[6] = r[7] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
+// ---- scene feature word (tirt_device.h, SF_*) ------------------------------------------------------------
+// the kind of every emitter on the light list as k_light_records writes it into the light record: -1 a triangle, else the shape type
+static void light_kinds(const int32_t *primitive, const float *shape, const int32_t *light, int light_count, std::vector<int> &kind)
+{
+    kind.resize((size_t)(light_count > 0 ? light_count : 0));
+    for (int i = 0; i < light_count; i++) {
+        const int32_t *pr = primitive + (size_t)light[i] * PRI_VEC;
+        int st = -1;
+        if (pr[0] != PRIMITIVE_TRI) { st = (int)shape[(size_t)pr[1] * SHA_VEC]; if (st == -1) st = -2; }
+        kind[(size_t)i] = st;
+    }
+}
+static bool env_is_lit(const int32_t *texel, size_t count, float power)
+{
+    if (power != 0.0f) return true;
+    for (size_t k = 0; k < count; k++) if (texel[k] & 0x00FFFFFF) return true;      // (tex_sample reads the low 24 bits)
+    return false;
+}
+static unsigned shade_features_core(const float *material, int nm, const int *light_kind, int light_count, bool env_lit)
+{
+    unsigned f = 0u;
+    for (int i = 0; i < nm; i++) if ((int)material[(size_t)i * MAT_VEC] == MAT_GLASS) f |= SF_GLASS;
+    if (env_lit) f |= SF_ENV;
+    if (light_count <= 0) f |= SF_NO_LIGHT;
+    for (int i = 0; i < light_count; i++) {
+        const int k = light_kind[i];
+        f |= k == -1 ? SF_LIGHT_TRI : k == SHAPE_SPHERE ? SF_LIGHT_SPHERE : (k == SHAPE_SPOT || k == SHAPE_LASER) ? SF_LIGHT_SPOT_LASER : SF_LIGHT_OTHER;
+    }
+    return f;
+}
+void refresh_shade_features(tirt_ctx *c)
+{
+    c->shade_features = c->h_material.empty() ? SF_ALL
+        : shade_features_core(c->h_material.data(), c->nm, c->h_light_kind.data(), c->light_count, c->env_lit);
+}
+
 int ensure_shade_records(tirt_ctx *c)
 {
     if (!(c->shade_rec_valid && c->shade_rec.p)) {
@@ -544,6 +580,7 @@ int tirt_set_option(tirt_ctx *c, const char *name, double value)
         int l = 0; while ((1 << l) < iv) l++;
         c->tr_slice_log2 = l; return TIRT_OK;
     }
+    if (!strcmp(name, "shade_specialize")) { TIRT_REQUIRE(value == 0.0 || value == 1.0, "shade_specialize: 0 (generic kernel) or 1"); if (flush_pending(c)) return TIRT_ERR_HIP; c->shade_specialize = (int)value; return TIRT_OK; }
     if (!strcmp(name, "shade_grid")) { TIRT_REQUIRE(value >= 1 && value <= 65536, "shade_grid: 1..65536"); c->sh_grid = (int)value; c->grid_user = true; return TIRT_OK; }
     if (!strcmp(name, "path_order_blocks")) { c->path_order_blocks = value != 0.0; return TIRT_OK; }
     if (!strcmp(name, "slices_contiguous")) { c->slices_contiguous = value != 0.0; return TIRT_OK; }
@@ -592,8 +629,11 @@ int tirt_scene_upload(tirt_ctx *c, const float *vertex, int nv, const int32_t *p
     if (!c->env.p) {        // default: 1x1 black (Scene.py:295-296 loads image/black.png)
         int32_t z = 0;
         if (upload(c->env, &z, sizeof(int32_t), st)) return TIRT_ERR_HIP;
-        c->env_w = 1; c->env_h = 1; c->env_power = 0.0f;
+        c->env_w = 1; c->env_h = 1; c->env_power = 0.0f; c->env_lit = false;
     }
+    c->h_material.assign(material, material + (size_t)MAT_VEC * nm);
+    light_kinds(primitive, shape, light, light_count, c->h_light_kind);
+    refresh_shade_features(c);
     TIRT_HIP(hipStreamSynchronize(st));
     return TIRT_OK;
 }
@@ -606,6 +646,8 @@ int tirt_material_upload(tirt_ctx *c, const float *material, int nm)
     if (upload(c->material, material, sizeof(float) * 10 * (size_t)nm, c->stream)) return TIRT_ERR_HIP;
     if (refresh_material_table(c)) return TIRT_ERR_HIP;
     c->light_rec_valid = false;                // the light records carry the emitters' colours
+    c->h_material.assign(material, material + (size_t)MAT_VEC * nm);
+    refresh_shade_features(c);                 // (a material may have become glass, or stopped being it)
     TIRT_HIP(hipStreamSynchronize(c->stream));
     return TIRT_OK;
 }
@@ -617,7 +659,35 @@ int tirt_env_upload(tirt_ctx *c, const int32_t *rgb_packed, int w, int h, float 
     TIRT_REQUIRE(rgb_packed && w >= 1 && h >= 1, "tirt_env_upload: bad image");
     if (upload(c->env, rgb_packed, sizeof(int32_t) * (size_t)w * h, c->stream)) return TIRT_ERR_HIP;
     c->env_w = w; c->env_h = h; c->env_power = power;
+    c->env_lit = env_is_lit(rgb_packed, (size_t)w * h, power);
+    refresh_shade_features(c);
     TIRT_HIP(hipStreamSynchronize(c->stream));
+    return TIRT_OK;
+}
+
+int tirt_shade_features(tirt_ctx *c, uint32_t *out)
+{
+    TIRT_REQUIRE(c, "null context");
+    TIRT_REQUIRE(out, "tirt_shade_features: null pointer");
+    out[0] = c->shade_features;
+    out[1] = c->shade_specialize ? 1u : 0u;
+    return TIRT_OK;
+}
+
+int tirt_shade_features_host(const float *material, int nm, const int32_t *primitive, int n, const float *shape, int ns,
+                             const int32_t *light, int light_count, const int32_t *env, int env_w, int env_h, float env_power, uint32_t *out)
+{
+    TIRT_REQUIRE(material && primitive && shape && out && nm >= 1 && n >= 1 && ns >= 1, "tirt_shade_features_host: null pointer or empty table");
+    TIRT_REQUIRE(light_count >= 0 && (light_count == 0 || light), "tirt_shade_features_host: bad light list");
+    for (int i = 0; i < light_count; i++) {
+        TIRT_REQUIRE(light[i] >= 0 && light[i] < n, "tirt_shade_features_host: light index out of range");
+        const int32_t *pr = primitive + (size_t)light[i] * 3;
+        TIRT_REQUIRE(pr[0] == PRIMITIVE_TRI || (pr[1] >= 0 && pr[1] < ns), "tirt_shade_features_host: shape index out of range");
+    }
+    std::vector<int> kind;
+    light_kinds(primitive, shape, light, light_count, kind);
+    const bool lit = env ? env_is_lit(env, (size_t)(env_w > 0 ? env_w : 0) * (size_t)(env_h > 0 ? env_h : 0), env_power) : env_power != 0.0f;
+    *out = shade_features_core(material, nm, kind.data(), light_count, lit);
     return TIRT_OK;
 }
 

@@ -59,6 +59,21 @@ struct SceneView {
 };
 struct CameraView { float view_inv[12]; float eye[3]; float fx, fy, cx, cy; };
 
+// ---- scene feature word (tirt_api.hip, shade_features_core): what of the shading code a scene can reach at all, from the material rows, the
+// kinds of the emitters on the light list and the environment.  k_shade / k_shade_spec are compiled per feature set (tirt_render.hip): a
+// branch whose bit is clear in the instantiation's mask is not compiled, one whose bit is the only emitter kind left is taken without a test ----
+enum : unsigned {
+    SF_GLASS = 1u,            // a material row of type MAT_GLASS
+    SF_ENV = 2u,              // env_power != 0 or a texel of the environment image that is not black
+    SF_LIGHT_TRI = 4u,        // a triangle on the light list
+    SF_LIGHT_SPOT_LASER = 8u, // a spot or a laser on the light list
+    SF_NO_LIGHT = 16u,        // light_count == 0
+    SF_LIGHT_SPHERE = 32u,    // a sphere on the light list
+    SF_LIGHT_OTHER = 64u,     // an emitter of no kind sample_li knows (it samples the origin): generic kernel only
+    SF_ALL = 127u,
+    SF_LIGHT_KINDS = SF_LIGHT_TRI | SF_LIGHT_SPOT_LASER | SF_LIGHT_SPHERE | SF_LIGHT_OTHER
+};
+
 TD v3 vtx_pos(const SceneView &s, int i) { const float *p = s.vertex + (size_t)i * VER_VEC; return V(p[0], p[1], p[2]); }
 TD v3 vtx_nor(const SceneView &s, int i) { const float *p = s.vertex + (size_t)i * VER_VEC; return V(p[3], p[4], p[5]); }
 TD v3 vtx_uv(const SceneView &s, int i)  { const float *p = s.vertex + (size_t)i * VER_VEC; return V(p[6], p[7], p[8]); }
@@ -299,14 +314,66 @@ TD float offset_ray1(float p, float n)
 }
 TD v3 offset_ray(v3 p, v3 n) { return V(offset_ray1(p.x, n.x), offset_ray1(p.y, n.y), offset_ray1(p.z, n.z)); }
 
-// ---- brdf/Disney.py:17-40 -----------------------------------------------------------------------------
-TD v3 disney_sample(const float *m, v3 dir, v3 N, float probability, float r1, float r2)
+// ---- brdf/Disney.py:17-40, 65-108.  What evaluate_pdf and sample compute from the material row alone, and what evaluate_pdf computes from
+// (N, V) alone, in one place: a path evaluates the BSDF twice at one hit (NEE sample, continuation) with the same N and V, and samples
+// it once.  Every value is the expression of the reference on the same operands; only how often it is evaluated differs. ----
+struct DisneySetup {
+    float metal1, rough, Cspec0, specularAlpha, a2, roughg, diffuseRatio, specularRatio;      // material only (metal1 = 1 - metal)
+    float NDotV, FV, GV;                                                                       // view: dot(N, V), schlick_fresnel, smithg_ggx
+};
+TD float gtr2_a2(float NDotH, float a2) { float t = 1.0f + (a2 - 1.0f) * NDotH * NDotH; return a2 / (PI_UF * t * t); }      // gtr2 with a * a given
+TD void disney_setup_material(const float *m, DisneySetup &d)
+{
+    const float metal = m[5], rough = m[6];
+    d.rough = rough;
+    d.metal1 = 1.0f - metal;
+    d.Cspec0 = mixf(0.04f, 1.0f, metal);
+    d.specularAlpha = maxf(0.001f, rough);
+    d.a2 = d.specularAlpha * d.specularAlpha;
+    const float rg = rough * 0.5f + 0.5f; d.roughg = rg * rg;
+    d.diffuseRatio = 0.5f * d.metal1;
+    d.specularRatio = 1.0f - d.diffuseRatio;
+}
+TD DisneySetup disney_setup(const float *m, v3 N, v3 Vv)
+{
+    DisneySetup d;
+    disney_setup_material(m, d);
+    d.NDotV = dot(N, Vv);
+    d.FV = schlick_fresnel(d.NDotV);
+    d.GV = smithg_ggx(d.NDotV, d.roughg);
+    return d;
+}
+TD v3 disney_sample_set(const DisneySetup &ds, v3 dir, v3 N, float probability, float r1, float r2)
 {
     // Both lobes of the reference (diffuse: cosine_sample_hemisphere + inverse_transform, specular: GTR2
     // half vector + inverse_transform + reflect) take one sin/cos pair of a lobe-specific angle and one change
     // of basis around N.  Written so that a wave with lanes in both lobes evaluates the expensive shared
     // pieces (sincos, the three normalisations of the basis) once; every lane still performs exactly the
     // reference's operations for its lobe.
+    const bool diffuse = probability < ds.diffuseRatio;
+    const float two_pi = (float)(2.0 * 3.1415956);
+    const float phi = diffuse ? two_pi * r2 : r1 * 2.0f * PI_UF;       // UtilsFunc.py:352-361 / Disney.py:28
+    float sinPhi, cosPhi; tm_sincos(phi, &sinPhi, &cosPhi);
+    v3 local;
+    if (diffuse) {
+        float r = tm_sqrt(r1);
+        v3 p;
+        p.x = r * cosPhi;
+        p.y = r * sinPhi;
+        p.z = tm_sqrt(maxf(0.0f, 1.0f - p.x * p.x - p.y * p.y));
+        local = normalized(p);
+    } else {
+        float cosTheta = tm_sqrt((1.0f - r2) / (1.0f + (ds.a2 - 1.0f) * r2));
+        float sinTheta = tm_sqrt(1.0f - (cosTheta * cosTheta));
+        local = V(sinTheta * cosPhi, sinTheta * sinPhi, cosTheta);
+    }
+    const v3 world = inverse_transform(local, N);
+    return diffuse ? world : reflect_(dir, world);
+}
+// the reference's signature (BDPT, PT_Spec, the known-answer tests, the instantiations of k_shade that do not share a set-up): the same function
+// with its own material terms.  (Not a wrapper around disney_sample_set: through one the generic k_shade needs 8 bytes of scratch.)
+TD v3 disney_sample(const float *m, v3 dir, v3 N, float probability, float r1, float r2)
+{
     float metal = m[5], rough = m[6];
     float diffuseRatio = 0.5f * (1.0f - metal);
     float specularAlpha = maxf(0.001f, rough);
@@ -330,7 +397,33 @@ TD v3 disney_sample(const float *m, v3 dir, v3 N, float probability, float r1, f
     const v3 world = inverse_transform(local, N);
     return diffuse ? world : reflect_(dir, world);
 }
-// ---- brdf/Disney.py:65-108 -----------------------------------------------------------------------------
+// ---- brdf/Disney.py:65-108: the part that depends on L ------------------------------------------------------
+TD float disney_evaluate_pdf_set(const DisneySetup &ds, v3 N, v3 Vv, v3 L, float &pdf)
+{
+    float outputC = 0.0f; pdf = -1.0f;
+    float NDotL = dot(N, L);
+    if ((NDotL > 0.0f) & (ds.NDotV > 0.0f)) {
+        const float inv_pi = (float)(1.0 / 3.1415956);
+        v3 H = normalized(L + Vv);
+        float NDotH = dot(H, N), LDotH = dot(H, L);
+        float Csheen = 0.5f;
+        float FL = schlick_fresnel(NDotL);
+        float Fd90 = 0.5f + 2.0f * LDotH * LDotH * ds.rough;
+        float Fd = mixf(1.0f, Fd90, FL) * mixf(1.0f, Fd90, ds.FV);
+        float Ds = gtr2_a2(NDotH, ds.a2);
+        float FH = schlick_fresnel(LDotH);
+        float Fs = mixf(ds.Cspec0, 1.0f, FH);
+        float Gs = smithg_ggx(NDotL, ds.roughg) * ds.GV;
+        float Fsheen = FH * Csheen;
+        outputC = (Fsheen + inv_pi) * Fd * ds.metal1 + Gs * Fs * Ds;
+        float pdfGTR2 = Ds * NDotH;
+        float pdfSpec = pdfGTR2 / (4.0f * absf(LDotH));
+        float pdfDiff = inv_pi;                               // quirk B4
+        pdf = ds.diffuseRatio * pdfDiff + ds.specularRatio * pdfSpec;
+    }
+    return outputC;
+}
+// the reference's signature: set-up and evaluation in one function, every term inside the early-out (see disney_sample)
 TD float disney_evaluate_pdf(const float *m, v3 N, v3 Vv, v3 L, float &pdf)
 {
     float outputC = 0.0f; pdf = -1.0f;
@@ -468,22 +561,25 @@ TD float light_shape_visible(const SceneView &s, int light_prim, v3 light_dir, v
 // get_prim_random_point_normal's order, and so do the three normalisations of the light's normal. ----
 constexpr int LIGHT_REC_QUADS = 8;
 struct LightRec { v3 emission; float area, choice_pdf, p0, p1; int kind; };      // kind: -1 triangle, else the shape type; p0, p1 = sh[4], sh[5]
+// FEAT (a scene feature word): emitter kinds the mask rules out are not compiled, and where it leaves one kind no test is made for it
+template <unsigned FEAT = SF_ALL>
 TD LightRec light_sample_rec(const float4 *lrec, int lidx, float a, float b, v3 &pos, v3 &nor)
 {
+    constexpr unsigned LK = FEAT & SF_LIGHT_KINDS;
     const float4 *r = lrec + (size_t)lidx * LIGHT_REC_QUADS;
     const float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3], r4 = r[4], r5 = r[5];
     LightRec L; L.emission = V(r3.w, r4.w, r5.w); L.area = r0.w; L.choice_pdf = r1.w; L.p0 = r1.x; L.p1 = r1.y; L.kind = __float_as_int(r2.w);
     pos = V(0.0f, 0.0f, 0.0f); v3 normal = pos;
-    if (L.kind == -1) {
+    if ((LK & SF_LIGHT_TRI) && (LK == SF_LIGHT_TRI || L.kind == -1)) {
         const v3 v1 = V(r0.x, r0.y, r0.z), e31 = V(r1.x, r1.y, r1.z), e21 = V(r2.x, r2.y, r2.z);
         const v3 n1 = V(r3.x, r3.y, r3.z), n2 = V(r4.x, r4.y, r4.z), n3 = V(r5.x, r5.y, r5.z);
         if (a + b > 1.0f) { a = 1.0f - a; b = 1.0f - b; }
         pos = (v1 + e31 * a) + e21 * b;
         normal = normalized((n1 * (1.0f - a - b) + n2 * a) + n3 * b);
-    } else if (L.kind == SHAPE_SPHERE) {
+    } else if ((LK & SF_LIGHT_SPHERE) && (LK == SF_LIGHT_SPHERE || L.kind == SHAPE_SPHERE)) {
         normal = uniform_sample_sphere(a, b);
         pos = V(r0.x, r0.y, r0.z) + normal * L.p0;
-    } else if (L.kind == SHAPE_SPOT || L.kind == SHAPE_LASER) {
+    } else if ((LK & SF_LIGHT_SPOT_LASER) && (L.kind == SHAPE_SPOT || L.kind == SHAPE_LASER)) {
         normal = V(r3.x, r3.y, r3.z);
         pos = V(r0.x, r0.y, r0.z);
     }
@@ -491,9 +587,11 @@ TD LightRec light_sample_rec(const float4 *lrec, int lidx, float a, float b, v3 
     return L;
 }
 // light_shape_visible on the record (the laser's choice pdf is already in it)
+template <unsigned FEAT = SF_ALL>
 TD float light_shape_visible_rec(const LightRec &L, v3 light_dir, v3 light_normal, float light_dist)
 {
     float visable = 1.0f;
+    if (!(FEAT & SF_LIGHT_SPOT_LASER)) return visable;
     if (L.kind == SHAPE_SPOT) {
         const float NdotL = absf(dot(light_dir, light_normal));
         const float x1 = L.p0, x2 = L.p1;

@@ -283,6 +283,12 @@ struct tirt_ctx {
     bool shade_rec_valid = false;                  // shading records follow vertex / primitive / shape uploads and process_normal
     bool light_rec_valid = false;                  // light records follow those and material uploads (they carry the emitter's colour)
     int env_w = 0, env_h = 0; float env_power = 0.0f;
+    // scene feature word (tirt_device.h, SF_*): which instantiation of k_shade / k_shade_spec the scene gets.  Derived from host copies of the rows the
+    // kernels read -- the material table, the kind of every emitter on the light list (from the primitive and shape rows), the environment --
+    // by refresh_shade_features, wherever one of them is uploaded again
+    std::vector<float> h_material; std::vector<int> h_light_kind; bool env_lit = false;
+    unsigned shade_features = 127u;                // (SF_ALL until a scene is uploaded)
+    int shade_specialize = 1;                      // option "shade_specialize": 0 = the generic kernel for every scene (A/B and parity switch)
 
     // LBVH (accel/LBvh.py fields)
     bool built = false;
@@ -467,6 +473,7 @@ void pvb_launch_cand(tirt_ctx *c, hipStream_t st, const BvhView &bv, const float
 void pvb_launch_scatter(hipStream_t st, const int *fb_count, const int *fb_slot, const float4 *fb_hit, float4 *hit);
 int ensure_counters(tirt_ctx *c);
 int ensure_shade_records(tirt_ctx *c);
+void refresh_shade_features(tirt_ctx *c);      // tirt_api.hip
 int sync_all(tirt_ctx *c);
 int flush_pending(tirt_ctx *c);
 }  // namespace tirt

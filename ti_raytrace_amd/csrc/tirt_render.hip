@@ -88,6 +88,9 @@ struct ShadeStep {
     v3 next_o = V(0.0f, 0.0f, 0.0f), next_d = next_o, next_thr = next_o, sh_o = next_o, sh_d = next_o, sh_c = next_o;
     float next_pdf = 0.0f, sh_dist = 0.0f; int next_spec = 0, sh_expect = -2;
 };
+// FEAT: the feature word (tirt_device.h, SF_*) this copy is compiled for -- a superset of the scene's.  A scene without glass, without a lit environment, with one
+// kind of emitter compiles none of the code of the others; what is left performs the same operations on the same operands in the same order.
+template <unsigned FEAT>
 TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame_begin, uint32_t seed, int bounce, int last_bounce, int slot,
                    const v3 origin, const v3 direction, const float4 hrec, v3 throughout, v3 &radiance, float brdf_pdf, int perfect_spec, ShadeStep &s)
 {
@@ -119,7 +122,7 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
             // UF.srgb_to_lrgb(material colour) (PT_RGB.py:86): per-material table filled by the same device function
             const v3 reflect_color = V(sc.mat_lrgb[mat_id * 3], sc.mat_lrgb[mat_id * 3 + 1], sc.mat_lrgb[mat_id * 3 + 2]);
             v3 next_dir; float f_or_b = 1.0f, brdf = 1.0f;
-            if (mat_type == MAT_GLASS) {                                       // PT_RGB.py:89-92
+            if ((FEAT & SF_GLASS) && mat_type == MAT_GLASS) {                  // PT_RGB.py:89-92
                 perfect_spec = 1;
                 next_dir = glass_sample(m, direction, normal, tm_rand(seed, pixel, frame, dim0 + TM_SLOT_GLASS), f_or_b);
                 brdf = 1.0f; brdf_pdf = 1.0f;
@@ -127,26 +130,33 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
                 perfect_spec = 0;
                 // Scene.py:477-518 sample_li.  No emitters (env-lit scene): the reference would index light[-1]
                 // (Scene.py:423-428, undefined) -- defined here, as in the oracle, as "no NEE sample"
-                if (sc.light_count > 0) {
+                // the view-only and material-only terms of the BSDF, once for the NEE sample, the lobe choice and the continuation (tirt_device.h)
+                // (only where the glass branch is not compiled: with it the body sits on the 96-VGPR limit of SH_MIN_WAVES and the set-up's live values go
+                // to scratch -- there every evaluation makes its own, as before)
+                constexpr bool SHARE_SETUP = !(FEAT & SF_GLASS);
+                DisneySetup ds;
+                if (SHARE_SETUP) ds = disney_setup(m, fnormal, -direction);
+                if (!(FEAT & SF_NO_LIGHT) || sc.light_count > 0) {
                 int lidx = (int)(tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LIGHT) * (float)sc.light_count);
                 if (lidx >= sc.light_count) lidx = sc.light_count - 1;
                 const float ra = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LA);
                 const float rb = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LB);
                 v3 light_pos, light_normal;
                 // the emitter's area, choice pdf, emission and the edges of its sampled point: per-light record (tirt_device.h, k_light_records)
-                const LightRec lr = light_sample_rec(sc.light_rec, lidx, ra, rb, light_pos, light_normal);
+                const LightRec lr = light_sample_rec<FEAT>(sc.light_rec, lidx, ra, rb, light_pos, light_normal);
                 const float light_choice_pdf = lr.choice_pdf;
                 light_normal = normalized(light_normal);
                 v3 light_dir = h.pos - light_pos;
                 const float light_dist = norm(light_dir);
                 light_dir = light_dir / light_dist;
-                const v3 light_emission = lr.emission * light_shape_visible_rec(lr, light_dir, light_normal, light_dist);   // spot / laser (Scene.py:491-516)
+                const v3 light_emission = lr.emission * light_shape_visible_rec<FEAT>(lr, light_dir, light_normal, light_dist);   // spot / laser (Scene.py:491-516)
                 const float NdotL_surface = dot(fnormal, light_dir);            // PT_RGB.py:101-109
                 const float NdotL_light = dot(light_normal, light_dir);
                 if ((NdotL_surface < 0.0f) & (NdotL_light > 0.0f)) {
                     s.want_shadow = true;
                     float e_pdf;
-                    const float e_brdf = disney_evaluate_pdf(m, fnormal, -direction, -light_dir, e_pdf);
+                    const float e_brdf = SHARE_SETUP ? disney_evaluate_pdf_set(ds, fnormal, -direction, -light_dir, e_pdf)
+                                                     : disney_evaluate_pdf(m, fnormal, -direction, -light_dir, e_pdf);
                     const float light_pdf = light_dist * light_dist * light_choice_pdf / NdotL_light;
                     v3 c = V(0.0f, 0.0f, 0.0f);
                     int expect = -2;                       // never equals a primitive id
@@ -162,17 +172,18 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
                     s.sh_o = light_pos; s.sh_d = light_dir; s.sh_c = c; s.sh_expect = expect; s.sh_dist = light_dist;
                 }
                 }   // light_count > 0
-                next_dir = disney_sample(m, direction, fnormal, tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LOBE),
-                                         tm_rand(seed, pixel, frame, dim0 + TM_SLOT_R1),
-                                         tm_rand(seed, pixel, frame, dim0 + TM_SLOT_R2));
+                const float r_lobe = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LOBE), r_1 = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_R1),
+                            r_2 = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_R2);
+                next_dir = SHARE_SETUP ? disney_sample_set(ds, direction, fnormal, r_lobe, r_1, r_2) : disney_sample(m, direction, fnormal, r_lobe, r_1, r_2);
                 f_or_b = 1.0f;
-                brdf = disney_evaluate_pdf(m, fnormal, -direction, next_dir, brdf_pdf);
+                brdf = SHARE_SETUP ? disney_evaluate_pdf_set(ds, fnormal, -direction, next_dir, brdf_pdf)
+                                   : disney_evaluate_pdf(m, fnormal, -direction, next_dir, brdf_pdf);
                 brdf *= absf(dot(normal, next_dir));
             }
             const v3 next_origin = offset_ray(h.pos, fnormal * signf(f_or_b));   // PT_RGB.py:115
             if (brdf_pdf > 0.0f) {
                 bool alive = true;
-                if (f_or_b < 0.0f) {                                             // PT_RGB.py:118-122
+                if ((FEAT & SF_GLASS) && f_or_b < 0.0f) {                        // PT_RGB.py:118-122
                     const float extinction = m[6];
                     const float R = tm_exp(-t / extinction);
                     if (tm_rand(seed, pixel, frame, dim0 + TM_SLOT_EXT) >= R) alive = false;
@@ -185,12 +196,23 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
                 }
             }
         }
-    } else if (sc.env_power == 0.0f && (direction.x - direction.x == 0.0f) && (direction.y - direction.y == 0.0f) &&
+    } else if ((!(FEAT & SF_ENV) || sc.env_power == 0.0f) && (direction.x - direction.x == 0.0f) && (direction.y - direction.y == 0.0f) &&
                (direction.z - direction.z == 0.0f)) {
         // black environment (PT_RGB.py:127-132 with env_power == 0): for a finite direction the lookup returns a
         // finite e >= 0, so (e * throughput) * 0 is +-0 with throughput's sign, or NaN where throughput is not
         // finite -- exactly throughput * env_power, without the two atan2, four texel fetches and three pow
         radiance = radiance + throughout * sc.env_power;
+    } else if (!(FEAT & SF_ENV)) {
+        // a direction that is not finite under a black environment (env_power == 0 and every texel 0: the SF_ENV bit is clear).  The lookup below then
+        // fetches zeros whatever the texel indices are, and mixes them with the weights x - floor(x) of the clamped coordinates: 0 where tx and ty are
+        // numbers (a clamped coordinate is finite), NaN where one of them is NaN -- and srgb_to_lrgb keeps both.  tm_atan2 returns NaN for a NaN
+        // argument and for two infinite ones (its quotient), a number otherwise; `dis` is the lookup's own expression.  So e is all NaN or all zero:
+        const float dis = tm_sqrt(direction.x * direction.x + direction.z * direction.z);
+        const float big = 3.4028234e38f;
+        const bool e_nan = direction.x != direction.x || direction.y != direction.y || direction.z != direction.z ||
+                           (absf(direction.x) > big && absf(direction.z) > big) || (absf(direction.y) > big && dis > big);
+        const float e1 = e_nan ? tm_nan() : 0.0f;
+        radiance = radiance + (V(e1, e1, e1) * throughout) * sc.env_power;
     } else {                                                                     // PT_RGB.py:127-132
         const float dis = tm_sqrt(direction.x * direction.x + direction.z * direction.z);
         const float tx = (tm_atan2(direction.z, direction.x) + PI_SCENE) / PI_SCENE / 2.0f;
@@ -860,6 +882,9 @@ __global__ void k_generate(PathSoA ps, CameraView cam, TileMap tm, int P, int S,
 #ifndef SH_MIN_WAVES
 #define SH_MIN_WAVES 5
 #endif
+#ifndef SH_MIN_WAVES_NARROW      // the instantiations without glass and environment (82 VGPRs at 5 waves, 80 and still no scratch at 6)
+#define SH_MIN_WAVES_NARROW 5
+#endif
 // The 78 array pointers of the path state are the first kernel argument and are never read from it directly: each of the three places
 // that needs some of them (a path's state in, the survivor's state out, the shadow ray out) reads those from the kernel-argument segment in
 // one batch of scalar loads -- as k_trace does (TR_COLD), and for the same reason: kept in SGPRs across the loop they overflow the scalar
@@ -869,7 +894,8 @@ typedef const __attribute__((address_space(4))) ShadeArgs *cold_shade_t;
 #define SH_COLD(ca) cold_shade_t ca = (cold_shade_t)__builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(ca))
 #define SH_LD(x) __builtin_nontemporal_load(&(x))
 #define SH_ST(x, v) __builtin_nontemporal_store((v), &(x))
-__global__ __launch_bounds__(SH_BLOCK, SH_MIN_WAVES) void k_shade(ShadeArgs paths_in_kernarg_segment, SceneView sc, TileMap tm, int P,
+template <unsigned FEAT, int MIN_WAVES>
+__global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_shade(ShadeArgs paths_in_kernarg_segment, SceneView sc, TileMap tm, int P,
                                                    uint32_t frame_begin, uint32_t seed, int bounce, int last_bounce,
                                                    const int *count_ptr, int count_fixed, unsigned long long *append_ctr,
                                                    DevCounters *ctr, v3 eye)
@@ -909,7 +935,7 @@ __global__ __launch_bounds__(SH_BLOCK, SH_MIN_WAVES) void k_shade(ShadeArgs path
             float brdf_pdf = first ? 1.0f : SH_LD(c_pdf[q]);
             int perfect_spec = first ? 1 : (int)(SH_LD(c_flags[q]) & 1u);
             ShadeStep ss;
-            shade_path(sc, tm, P, frame_begin, seed, bounce, last_bounce, slot, origin, direction, hrec, throughout, radiance, brdf_pdf, perfect_spec, ss);
+            shade_path<FEAT>(sc, tm, P, frame_begin, seed, bounce, last_bounce, slot, origin, direction, hrec, throughout, radiance, brdf_pdf, perfect_spec, ss);
             want_next = ss.want_next; want_shadow = ss.want_shadow; if (ss.shaded) n_shaded++;
             next_o = ss.next_o; next_d = ss.next_d; next_thr = ss.next_thr; next_pdf = ss.next_pdf; next_spec = ss.next_spec;
             sh_o = ss.sh_o; sh_d = ss.sh_d; sh_c = ss.sh_c; sh_expect = ss.sh_expect; sh_dist = ss.sh_dist;
@@ -1002,6 +1028,7 @@ __global__ void k_film(PathState ps, TileMap tm, int P, int F, uint32_t frame_be
 // the hero wavelength is not stored: Lambda = 360 + 100 * rand(pixel, frame, TM_DIM_SPEC_LAMBDA) is recomputed where it is needed.
 // Reference behaviours kept: the NEE sample is tinted with the colour of the surface that was HIT (`light_tint` of :213), not with
 // the light's emission; Disney.evaluate_pdf for the continuation is called with (N, V = next_dir, L = -direction) (:251).
+template <unsigned FEAT>
 __global__ __launch_bounds__(SH_BLOCK, 4) void k_shade_spec(ShadeArgs paths_in_kernarg_segment, SceneView sc, SpecView sp, TileMap tm, int P,
                                                    uint32_t frame_begin, uint32_t seed, int bounce, int last_bounce,
                                                    const int *count_ptr, int count_fixed, unsigned long long *append_ctr,
@@ -1066,18 +1093,18 @@ __global__ __launch_bounds__(SH_BLOCK, 4) void k_shade_spec(ShadeArgs paths_in_k
                     n_shaded++;
                     const f4s reflect_spec = get_spec_power(sp, m, Lambda);
                     v3 next_dir; float f_or_b = 1.0f, brdf = 1.0f, brdf_pdf = 1.0f;
-                    if (mat_type == MAT_GLASS) {                                                    // :234-238
+                    if ((FEAT & SF_GLASS) && mat_type == MAT_GLASS) {                               // :234-238
                         const int index = (int)(tm_rand(seed, pixel, frame, dim0 + TM_SLOT_HERO) * (float)HERO_N);
                         const float rnd_lambda = Lambda + (float)index * HERO_LAMBDA_STEP;
                         next_dir = glass_sample_lambda(direction, normal, rnd_lambda, tm_rand(seed, pixel, frame, dim0 + TM_SLOT_GLASS), f_or_b);
                     } else {
-                        if (sc.light_count > 0) {                                                   // :240-249, Scene.sample_li
+                        if (!(FEAT & SF_NO_LIGHT) || sc.light_count > 0) {                          // :240-249, Scene.sample_li
                             int lidx = (int)(tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LIGHT) * (float)sc.light_count);
                             if (lidx >= sc.light_count) lidx = sc.light_count - 1;
                             const float ra = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LA);
                             const float rb = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LB);
                             v3 light_pos, light_normal;
-                            const LightRec lr = light_sample_rec(sc.light_rec, lidx, ra, rb, light_pos, light_normal);
+                            const LightRec lr = light_sample_rec<FEAT>(sc.light_rec, lidx, ra, rb, light_pos, light_normal);
                             const float light_choice_pdf = lr.choice_pdf;          // (of light_shape_visible only the laser's pdf is used by :245: it is in the record)
                             light_normal = normalized(light_normal);
                             v3 light_dir = h.pos - light_pos;
@@ -1183,6 +1210,30 @@ __global__ __launch_bounds__(SH_BLOCK, 4) void k_shade_spec(ShadeArgs paths_in_k
     if ((threadIdx.x & 63) == 0 && n_shaded) atomicAdd(&s_shaded, n_shaded);
     __syncthreads();
     if (threadIdx.x == 0 && s_shaded) atomicAdd(&ctr->shaded, s_shaded);
+}
+
+// ---- the instantiations of the two shading kernels, narrowest first.  pt_render launches the first one whose mask covers the scene's feature word
+// (tirt_ctx::shade_features, refreshed with the tables it is derived from); the last one carries every feature and serves every other scene, and every
+// scene when the option "shade_specialize" is 0. ----
+typedef void (*shade_fn_t)(ShadeArgs, SceneView, TileMap, int, uint32_t, uint32_t, int, int, const int *, int, unsigned long long *, DevCounters *, v3);
+typedef void (*shade_spec_fn_t)(ShadeArgs, SceneView, SpecView, TileMap, int, uint32_t, uint32_t, int, int, const int *, int, unsigned long long *, DevCounters *, v3);
+struct ShadeInst { unsigned feat; shade_fn_t fn; };
+struct ShadeSpecInst { unsigned feat; shade_spec_fn_t fn; };
+constexpr unsigned SF_I_SPHERE = SF_LIGHT_SPHERE;                                   // Disney, sphere lights, black environment: the synthetic headline scene
+constexpr unsigned SF_I_MESH = SF_LIGHT_TRI;                                        // Disney, mesh lights, black environment: Cornell box, Veach
+// (Built and left out: SF_GLASS | SF_ENV | SF_LIGHT_SPHERE for Teapot and the gallery spheres -- 3 509 VALU against the generic 3 872, but 12 bytes of scratch at
+// the 96-VGPR limit where the generic kernel has none; those scenes stay on the generic kernel.)
+static const ShadeInst SHADE_INST[] = {
+    {SF_I_SPHERE, k_shade<SF_I_SPHERE, SH_MIN_WAVES_NARROW>}, {SF_I_MESH, k_shade<SF_I_MESH, SH_MIN_WAVES_NARROW>},
+    {SF_ALL, k_shade<SF_ALL, SH_MIN_WAVES>}};
+static const ShadeSpecInst SHADE_SPEC_INST[] = {
+    {SF_I_SPHERE, k_shade_spec<SF_I_SPHERE>}, {SF_I_MESH, k_shade_spec<SF_I_MESH>}, {SF_ALL, k_shade_spec<SF_ALL>}};
+template <class T, size_t N>
+static const T &pick_shade_inst(const T (&tab)[N], const tirt_ctx *c)
+{
+    if (c->shade_specialize)
+        for (size_t k = 0; k + 1 < N; k++) if ((c->shade_features & ~tab[k].feat) == 0u) return tab[k];
+    return tab[N - 1];
 }
 
 // integrator/PT_Spec.py:141-158 (AddSplat) + :273-274, frames applied in order
@@ -1341,6 +1392,8 @@ int pt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed,
         const int sh_cap = two_big ? 2 * c->sh_grid : c->sh_grid;
         int grid_shade = (S + SH_BLOCK - 1) / SH_BLOCK; if (grid_shade > sh_cap) grid_shade = sh_cap;
         v3 eye_v; eye_v.x = c->cam.eye[0]; eye_v.y = c->cam.eye[1]; eye_v.z = c->cam.eye[2];
+        const shade_fn_t shade_fn = pick_shade_inst(SHADE_INST, c).fn;
+        const shade_spec_fn_t shade_spec_fn = pick_shade_inst(SHADE_SPEC_INST, c).fn;
         for (int b = 0; b < max_depth; b++) {
             const PathSoA &in = L.ps.st[b & 1], &out = L.ps.st[(b + 1) & 1];
             // closest hits of bounce b, together with the NEE shadow rays of bounce b-1 (they add into
@@ -1381,11 +1434,11 @@ int pt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed,
 
             stamp(evh, true);
             if (spec)
-                hipLaunchKernelGGL(k_shade_spec, dim3(grid_shade), dim3(SH_BLOCK), 0, st, ShadeArgs{L.ps, in, out}, sv, *spec, tm, P, f0, seed, b,
+                hipLaunchKernelGGL(shade_spec_fn, dim3(grid_shade), dim3(SH_BLOCK), 0, st, ShadeArgs{L.ps, in, out}, sv, *spec, tm, P, f0, seed, b,
                                    (b == max_depth - 1) ? 1 : 0, (b == 0) ? (const int *)nullptr : cnt_path(b), S,
                                    append_ctr(b), ctr, eye_v);
             else
-            hipLaunchKernelGGL(k_shade, dim3(grid_shade), dim3(SH_BLOCK), 0, st, ShadeArgs{L.ps, in, out}, sv, tm, P, f0, seed, b,
+            hipLaunchKernelGGL(shade_fn, dim3(grid_shade), dim3(SH_BLOCK), 0, st, ShadeArgs{L.ps, in, out}, sv, tm, P, f0, seed, b,
                                (b == max_depth - 1) ? 1 : 0, (b == 0) ? (const int *)nullptr : cnt_path(b), S,
                                append_ctr(b), ctr, eye_v);
             stamp(evh, false);
