@@ -391,6 +391,18 @@ int tirt_kat_spec(tirt_ctx *ctx, int which, const float *in, int in_stride, floa
 int tirt_shade_table_download(tirt_ctx *ctx, int which, float *out, uint64_t floats);
 int tirt_kat_shade_tables(tirt_ctx *ctx, int which, const float *in, float *out, int n);
 
+/* One shading step of PT_RGB (integrator/PT_RGB.py:66-132 between a closest hit and the next: emission with MIS, glass / Disney, the NEE set-up, the next ray, the
+ * miss) by the body of one instantiation of k_shade, on the context's own tables (shading and light records, material colours, environment) -- for
+ * tests/test_gpu_shade_step.py against the CPU oracle's orc_kat_shade_step.  One launch, row i on thread i.
+ * feat: the feature word of the instantiation -- 32 (sphere lights), 4 (mesh lights) or 127 (generic), the ones a render picks from (tirt_shade_features).
+ * in, 23 words per row (integers as their bit patterns): seed, pixel, frame, bounce, last_bounce; origin3, direction3; t, u, v, prim (t >= 1e6: a miss, prim unused);
+ *   throughout3, radiance3, brdf_pdf, perfect_spec.  NaN and infinity in the ray, the barycentrics and the state are data.
+ * out, 28 words per row: radiance3, shaded, want_next, next_o3, next_d3, next_thr3, next_pdf, next_spec, want_shadow, sh_o3, sh_d3, sh_c3, sh_expect, sh_dist -- what
+ *   k_shade writes to the path state and the shadow-ray queue; a field the step does not set is 0, sh_expect -2.  sh_c counts if the shadow ray finds sh_expect first.
+ * TIRT_ERR_ARG before anything is launched: in_stride < 23, out_stride < 28, a feat that is not one of the three (both also with a NULL ctx), a feat that does not
+ * cover the context's feature word, a hit row (t < 1e6) whose prim is outside [0, n_prims), a pixel outside [0, 2^31 - 1). */
+int tirt_kat_shade_step(tirt_ctx *ctx, uint32_t feat, const float *in, int in_stride, float *out, int out_stride, int n);
+
 /* ---- native Wavefront OBJ/MTL ingest (host only; no device, no context) -----------------------------
  * Replaces the reference's use of the third-party PyWavefront 1.3.3 package in Scene.add_obj
  * (Scene.py:66-127: `pywavefront.Wavefront(filename)`, `scene.materials[name].vertices / vertex_format /

@@ -525,30 +525,55 @@ static float intersect_tri(const orc_scene *s, v3 origin, v3 direction, int prim
     return t;
 }
 
-typedef struct { float t; v3 pos, gnor, nor, tex; int prim; } hit_t;
+typedef struct { float t; v3 pos, gnor, nor, tex; int prim; float u, v; } hit_t;      /* (u, v): the barycentrics of a triangle hit, 0 for a shape */
 
-/* Scene.py:529-600 */
-static float intersect_prim(const orc_scene *s, v3 origin, v3 direction, int prim,
+/* Scene.py:537-561, 565-596: position, normals and texture coordinate of the hit (t, u, v) of `prim` -- what intersect_prim hands back with a
+ * hit, as a function of the hit record (the device keeps (t, u, v, prim) per ray and evaluates the same expressions when it shades) */
+static void prim_attributes(const orc_scene *s, v3 origin, v3 direction, int prim, float t, float u, float v,
                             v3 *hit_pos, v3 *hit_gnor, v3 *hit_nor, v3 *hit_tex)
 {
     const int32_t *pr = s->primitive + (size_t)prim * PRI_VEC;
-    float hit_tv = INF_VALUE;
     v3 pos = V(0, 0, 0), nor = V(0, 0, 0), tex = V(0, 0, 0), gnor = V(0, 0, 0);
     if (pr[0] == PRIMITIVE_TRI) {
-        float u, v;
-        hit_tv = intersect_tri(s, origin, direction, prim, &u, &v);
-        if (hit_tv < INF_VALUE) {
-            int vi = pr[1];
-            float a = 1.0f - u - v, b = u, c = v;
-            v3 v1 = vtx_pos(s, vi), v2 = vtx_pos(s, vi + 1), v3_ = vtx_pos(s, vi + 2);
-            v3 n1 = vtx_nor(s, vi), n2 = vtx_nor(s, vi + 1), n3 = vtx_nor(s, vi + 2);
-            v3 t1 = vtx_uv(s, vi), t2 = vtx_uv(s, vi + 1), t3 = vtx_uv(s, vi + 2);
-            v3 v13 = vsub(v3_, v1), v12 = vsub(v2, v1);
-            gnor = vcross(v12, v13);
-            pos = vadd(vadd(vscale(v1, a), vscale(v2, b)), vscale(v3_, c));
-            tex = vadd(vadd(vscale(t1, a), vscale(t2, b)), vscale(t3, c));
-            nor = vadd(vadd(vscale(n1, a), vscale(n2, b)), vscale(n3, c));
+        int vi = pr[1];
+        float a = 1.0f - u - v, b = u, c = v;
+        v3 v1 = vtx_pos(s, vi), v2 = vtx_pos(s, vi + 1), v3_ = vtx_pos(s, vi + 2);
+        v3 n1 = vtx_nor(s, vi), n2 = vtx_nor(s, vi + 1), n3 = vtx_nor(s, vi + 2);
+        v3 t1 = vtx_uv(s, vi), t2 = vtx_uv(s, vi + 1), t3 = vtx_uv(s, vi + 2);
+        v3 v13 = vsub(v3_, v1), v12 = vsub(v2, v1);
+        gnor = vcross(v12, v13);
+        pos = vadd(vadd(vscale(v1, a), vscale(v2, b)), vscale(v3_, c));
+        tex = vadd(vadd(vscale(t1, a), vscale(t2, b)), vscale(t3, c));
+        nor = vadd(vadd(vscale(n1, a), vscale(n2, b)), vscale(n3, c));
+    } else {
+        const float *sh = s->shape + (size_t)pr[1] * SHA_VEC;
+        if ((int)sh[0] == SHAPE_SPHERE) {
+            float r = sh[4];
+            v3 centre = V(sh[1], sh[2], sh[3]);
+            v3 oc = vsub(centre, origin);
+            float dis_oc_square = vdot(oc, oc);
+            float dis_op = vdot(direction, oc);
+            float dis_cp = m_sqrt(dis_oc_square - dis_op * dis_op);
+            float c = 0.0f;                                      /* (a hit record the ray could not have produced: the scalar stays 0) */
+            if (dis_cp < r) c = dis_oc_square - r * r;
+            pos = vadd(origin, vscale(direction, t));
+            nor = V(pos.x - c, pos.y - c, pos.z - c);            /* quirk B3: scalar c, not centre */
+            gnor = nor;
         }
+    }
+    *hit_pos = pos; *hit_gnor = vnormalized(gnor); *hit_nor = vnormalized(nor); *hit_tex = tex;
+}
+
+/* Scene.py:529-600 */
+static float intersect_prim(const orc_scene *s, v3 origin, v3 direction, int prim,
+                            v3 *hit_pos, v3 *hit_gnor, v3 *hit_nor, v3 *hit_tex, float *uo, float *vo)
+{
+    const int32_t *pr = s->primitive + (size_t)prim * PRI_VEC;
+    float hit_tv = INF_VALUE, u = 0.0f, v = 0.0f;
+    int have = 0;
+    if (pr[0] == PRIMITIVE_TRI) {
+        hit_tv = intersect_tri(s, origin, direction, prim, &u, &v);
+        have = hit_tv < INF_VALUE;
     } else {
         const float *sh = s->shape + (size_t)pr[1] * SHA_VEC;
         if ((int)sh[0] == SHAPE_SPHERE) {
@@ -563,13 +588,13 @@ static float intersect_prim(const orc_scene *s, v3 origin, v3 direction, int pri
                 float b = -2.0f * dis_op;
                 float c = dis_oc_square - r * r;
                 hit_tv = (-b - m_sqrt(b * b - 4.0f * a * c)) / 2.0f / a;
-                pos = vadd(origin, vscale(direction, hit_tv));
-                nor = V(pos.x - c, pos.y - c, pos.z - c);      /* quirk B3: scalar c, not centre */
-                gnor = nor;
+                have = 1;
             }
         } else hit_tv = INF_VALUE;
     }
-    *hit_pos = pos; *hit_gnor = vnormalized(gnor); *hit_nor = vnormalized(nor); *hit_tex = tex;
+    if (have) prim_attributes(s, origin, direction, prim, hit_tv, u, v, hit_pos, hit_gnor, hit_nor, hit_tex);
+    else { *hit_pos = *hit_tex = V(0, 0, 0); *hit_gnor = *hit_nor = vnormalized(V(0, 0, 0)); }
+    *uo = u; *vo = v;
     return hit_tv;
 }
 
@@ -607,7 +632,7 @@ static inline int cn_is_leaf(const float *cn) { return ((int)cn[0]) & 1; }
 static hit_t closet_hit(const orc_scene *s, v3 origin, v3 direction, int32_t *stack, int max_size,
                         orc_stats *st)
 {
-    hit_t h; h.t = INF_VALUE; h.pos = h.nor = h.gnor = h.tex = V(0, 0, 0); h.prim = -1;
+    hit_t h; h.t = INF_VALUE; h.pos = h.nor = h.gnor = h.tex = V(0, 0, 0); h.prim = -1; h.u = h.v = 0.0f;
     stack[0] = 0;
     int stack_pos = 0;
     uint64_t nbox = 0, nleaf = 0, maxs = 0;
@@ -619,9 +644,9 @@ static hit_t closet_hit(const orc_scene *s, v3 origin, v3 direction, int32_t *st
         if (cn_is_leaf(cn) == IS_LEAF) {
             nleaf++;
             int prim = (int)cn[1];
-            v3 pos, gn, nn, tx;
-            float t = intersect_prim(s, origin, direction, prim, &pos, &gn, &nn, &tx);
-            if ((t < h.t) & (t > 0.0f)) { h.t = t; h.pos = pos; h.nor = nn; h.gnor = gn; h.tex = tx; h.prim = prim; }
+            v3 pos, gn, nn, tx; float u, v;
+            float t = intersect_prim(s, origin, direction, prim, &pos, &gn, &nn, &tx, &u, &v);
+            if ((t < h.t) & (t > 0.0f)) { h.t = t; h.pos = pos; h.nor = nn; h.gnor = gn; h.tex = tx; h.prim = prim; h.u = u; h.v = v; }
         } else {
             if (slabs(origin, direction, V(cn[2], cn[3], cn[4]), V(cn[5], cn[6], cn[7])) == 1) {
                 stack_pos += 1; stack[stack_pos] = node + 1;
@@ -676,8 +701,8 @@ static float closet_hit_shadow(const orc_scene *s, v3 origin, v3 direction, int3
 /* Batch entry points for kernel-level parity tests.
  * rays: [nr*6] (origin, direction); out_f: [nr*13] = t, pos3, gnormal3, normal3, tex3;
  * out_prim: [nr]; counts: [nr*2] = (N_box, N_leaf) per ray (nullable). */
-void orc_closest_hit_batch(const orc_scene *s, const float *rays, int nr, int max_size,
-                           float *out_f, int32_t *out_prim, int32_t *counts)
+static void closest_hit_batch(const orc_scene *s, const float *rays, int nr, int max_size,
+                              float *out_f, int32_t *out_prim, int32_t *counts, float *out_uv)
 {
     int32_t *stack = (int32_t *)malloc(sizeof(int32_t) * (size_t)(max_size + 2));
     for (int r = 0; r < nr; r++) {
@@ -691,9 +716,17 @@ void orc_closest_hit_batch(const orc_scene *s, const float *rays, int nr, int ma
         o[10] = h.tex.x; o[11] = h.tex.y; o[12] = h.tex.z;
         out_prim[r] = h.prim;
         if (counts) { counts[2 * r] = (int32_t)st.box_closest; counts[2 * r + 1] = (int32_t)st.leaf_closest; }
+        if (out_uv) { out_uv[2 * r] = h.u; out_uv[2 * r + 1] = h.v; }
     }
     free(stack);
 }
+void orc_closest_hit_batch(const orc_scene *s, const float *rays, int nr, int max_size,
+                           float *out_f, int32_t *out_prim, int32_t *counts)
+{ closest_hit_batch(s, rays, nr, max_size, out_f, out_prim, counts, NULL); }
+/* the same with the barycentrics of the hit, out_uv: [nr*2] -- (t, u, v, prim) is the hit record the device keeps per ray */
+void orc_closest_hit_uv_batch(const orc_scene *s, const float *rays, int nr, int max_size,
+                              float *out_f, int32_t *out_prim, int32_t *counts, float *out_uv)
+{ closest_hit_batch(s, rays, nr, max_size, out_f, out_prim, counts, out_uv); }
 void orc_shadow_hit_batch(const orc_scene *s, const float *rays, int nr, int max_size,
                           float *out_t, int32_t *out_prim, int32_t *counts)
 {
@@ -813,7 +846,8 @@ static v3 offset_ray(v3 p, v3 n)
 }
 
 /* brdf/Disney.py:17-40; rnd[3] = (probability, r1, r2) */
-static v3 disney_sample(const orc_scene *s, v3 dir, v3 N, int mat_id, const float *rnd)
+/* (lobe_out, nullable: 1 if the diffuse lobe was taken, 0 for the specular one) */
+static v3 disney_sample_lobe(const orc_scene *s, v3 dir, v3 N, int mat_id, const float *rnd, int *lobe_out)
 {
     const float *m = s->material + (size_t)mat_id * MAT_VEC;
     float metal = m[5], rough = m[6];
@@ -821,6 +855,7 @@ static v3 disney_sample(const orc_scene *s, v3 dir, v3 N, int mat_id, const floa
     float specularAlpha = fmax_(0.001f, rough);
     float probability = rnd[0], r1 = rnd[1], r2 = rnd[2];
     v3 next_dir;
+    if (lobe_out) *lobe_out = probability < diffuseRatio;
     if (probability < diffuseRatio) {
         next_dir = cosine_sample_hemisphere(r1, r2);
         next_dir = inverse_transform(next_dir, N);
@@ -835,6 +870,7 @@ static v3 disney_sample(const orc_scene *s, v3 dir, v3 N, int mat_id, const floa
     }
     return next_dir;
 }
+static v3 disney_sample(const orc_scene *s, v3 dir, v3 N, int mat_id, const float *rnd) { return disney_sample_lobe(s, dir, N, mat_id, rnd, NULL); }
 
 /* brdf/Disney.py:65-108 */
 static float disney_evaluate_pdf(const orc_scene *s, v3 N, v3 Vv, v3 L, int mat_id, float *pdf_out)
@@ -1016,6 +1052,149 @@ static v3 texture2d(const orc_scene *s, float u, float v)
 
 #define PATH_MAX_DEPTH_DEFAULT 15   /* integrator/PT_RGB.py:21 */
 
+/* One path at one bounce: integrator/PT_RGB.py:66-132 between the closest hit and the next one, as a function of the hit record (t, u, v, prim;
+ * t >= INF_VALUE: a miss) and the path's state.  The fields are those of the device's ShadeStep (tirt_render.hip) plus the updated radiance; a field
+ * the taken branch does not write keeps its default (0, sh_expect -2).  The NEE contribution sh_c is NOT added here: it counts if the shadow ray
+ * (sh_o, sh_d) finds primitive sh_expect first (-2: no primitive) -- pt_rgb_pixel makes that test, the device hands it to its shadow-ray launch.
+ * `branch`: which way the step went, one SB_* bit each (diagnostic; the device has no such word). */
+enum {
+    SB_EMIT_MIS = 1 << 0, SB_EMIT_SPEC = 1 << 1, SB_GLASS_REFLECT = 1 << 2, SB_GLASS_REFRACT = 1 << 3, SB_EXTINCT = 1 << 4,
+    SB_NEE = 1 << 5, SB_NEE_NOPDF = 1 << 6, SB_NEE_REJECT = 1 << 7, SB_LOBE_DIFFUSE = 1 << 8, SB_LOBE_SPECULAR = 1 << 9, SB_END_PDF = 1 << 10,
+    SB_MISS_FINITE = 1 << 11, SB_MISS_NONFINITE = 1 << 12, SB_LIGHT_TRI = 1 << 13, SB_LIGHT_SPHERE = 1 << 14, SB_LIGHT_SPOT = 1 << 15, SB_LIGHT_LASER = 1 << 16
+};
+typedef struct {
+    v3 radiance; int shaded;
+    int want_next; v3 next_o, next_d, next_thr; float next_pdf; int next_spec;
+    int want_shadow; v3 sh_o, sh_d, sh_c; int sh_expect; float sh_dist;
+    uint32_t branch;
+} shade_step;
+
+static shade_step pt_rgb_step(const orc_scene *s, uint32_t seed, uint32_t pixel, uint32_t frame, int bounce, int last_bounce,
+                              v3 origin, v3 direction, float t, float u, float v, int prim,
+                              v3 throughout, v3 radiance, float brdf_pdf, int perfect_spec)
+{
+    shade_step r;
+    r.shaded = r.want_next = r.want_shadow = r.next_spec = 0; r.next_pdf = r.sh_dist = 0.0f; r.sh_expect = -2; r.branch = 0u;
+    r.next_o = r.next_d = r.next_thr = r.sh_o = r.sh_d = r.sh_c = V(0, 0, 0);
+    const uint32_t dim0 = TM_DIM_BOUNCE0 + TM_DIMS_PER_BOUNCE * (uint32_t)bounce;
+    float light_pdf = 1.0f, f_or_b = 1.0f, brdf = 1.0f;
+    if (t < INF_VALUE) {
+        hit_t h; h.t = t; h.prim = prim; h.u = u; h.v = v;
+        prim_attributes(s, origin, direction, prim, t, u, v, &h.pos, &h.gnor, &h.nor, &h.tex);
+        v3 fnormal = vscale(h.nor, signf(vdot(vneg(direction), h.gnor)));      /* UtilsFunc.py:465-467 */
+        int mat_id = s->primitive[(size_t)h.prim * PRI_VEC + 2];
+        const float *m = s->material + (size_t)mat_id * MAT_VEC;
+        v3 mat_color = V(m[2], m[3], m[4]);
+        int mat_type = (int)m[0];
+        if (mat_type == MAT_LIGHT) {
+            float fCosTheta = fabs_(vdot(direction, h.gnor));
+            if (perfect_spec == 1) {
+                radiance = vadd(radiance, vmul(throughout, mat_color));
+                r.branch |= SB_EMIT_SPEC;
+            } else {
+                float area = get_prim_area(s, h.prim) * (float)s->light_count;
+                light_pdf = (h.t * h.t) / (area * fCosTheta);
+                radiance = vadd(radiance, vmul(vscale(throughout, power_heuristic(brdf_pdf, light_pdf)), mat_color));
+                r.branch |= SB_EMIT_MIS;
+            }
+        } else {
+            v3 reflect_color = srgb_to_lrgb(mat_color);
+            v3 normal = h.nor;
+            v3 next_dir;
+            r.shaded = 1;
+            if (mat_type == MAT_GLASS) {
+                perfect_spec = 1;
+                next_dir = glass_sample(s, direction, normal, mat_id,
+                                        tm_rand(seed, pixel, frame, dim0 + TM_SLOT_GLASS), &f_or_b);
+                brdf = 1.0f; brdf_pdf = 1.0f;                                   /* brdf/Glass.py:72-74 */
+                r.branch |= f_or_b < 0.0f ? SB_GLASS_REFRACT : SB_GLASS_REFLECT;
+            } else {
+                perfect_spec = 0;
+                /* Scene.py:477-518 sample_li.  A scene without emitters (light_count == 0, env-lit): the reference
+                 * would index light[-1] (Scene.py:423-428, undefined); defined here as "no NEE sample". */
+                if (s->light_count > 0) {
+                int lidx = (int)(tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LIGHT) * (float)s->light_count);
+                if (lidx >= s->light_count) lidx = s->light_count - 1;
+                int light_prim = s->light[lidx];
+                float ra = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LA);
+                float rb = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LB);
+                v3 light_pos, light_normal;
+                get_prim_random_point_normal(s, light_prim, ra, rb, &light_pos, &light_normal);
+                {
+                    const int32_t *lp = s->primitive + (size_t)light_prim * PRI_VEC;
+                    const int lst = lp[0] == PRIMITIVE_TRI ? -1 : (int)s->shape[(size_t)lp[1] * SHA_VEC];
+                    r.branch |= lst == -1 ? SB_LIGHT_TRI : lst == SHAPE_SPHERE ? SB_LIGHT_SPHERE : lst == SHAPE_SPOT ? SB_LIGHT_SPOT : lst == SHAPE_LASER ? SB_LIGHT_LASER : 0u;
+                }
+                int lmat = s->primitive[(size_t)light_prim * PRI_VEC + 2];
+                const float *lm = s->material + (size_t)lmat * MAT_VEC;
+                v3 light_emission = V(lm[2], lm[3], lm[4]);
+                float light_area = get_prim_area(s, light_prim);
+                float light_choice_pdf = 1.0f / ((float)s->light_count * light_area);
+                light_normal = vnormalized(light_normal);
+                v3 light_dir = vsub(h.pos, light_pos);
+                float light_dist = vnorm(light_dir);
+                light_dir = vdivs(light_dir, light_dist);
+                light_emission = vscale(light_emission, light_shape_visible(s, light_prim, light_dir, light_normal, light_dist, &light_choice_pdf));
+                /* PT_RGB.py:101-109: the contribution, if the shadow ray from the light's point finds this primitive first */
+                float NdotL_surface = vdot(fnormal, light_dir);
+                float NdotL_light = vdot(light_normal, light_dir);
+                if ((NdotL_surface < 0.0f) & (NdotL_light > 0.0f)) {
+                    float e_pdf;
+                    float e_brdf = disney_evaluate_pdf(s, fnormal, vneg(direction), vneg(light_dir), mat_id, &e_pdf);
+                    light_pdf = light_dist * light_dist * light_choice_pdf / NdotL_light;
+                    v3 c = V(0, 0, 0);
+                    int expect = -2;                        /* never equals a primitive id */
+                    if (e_pdf > 0.0f) {
+                        float w = power_heuristic(light_pdf, e_pdf) / fmax_(0.0001f, light_pdf);
+                        c = vscale(light_emission, w);
+                        c = vmul(c, throughout);
+                        c = vmul(c, reflect_color);
+                        c = vscale(c, e_brdf);
+                        c = vscale(c, fabs_(NdotL_surface));
+                        expect = h.prim;
+                        r.branch |= SB_NEE;
+                    } else r.branch |= SB_NEE_NOPDF;
+                    r.want_shadow = 1; r.sh_o = light_pos; r.sh_d = light_dir; r.sh_c = c; r.sh_expect = expect; r.sh_dist = light_dist;
+                } else r.branch |= SB_NEE_REJECT;
+                }   /* light_count > 0 */
+                float rnd[3] = { tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LOBE),
+                                 tm_rand(seed, pixel, frame, dim0 + TM_SLOT_R1),
+                                 tm_rand(seed, pixel, frame, dim0 + TM_SLOT_R2) };
+                int diffuse_lobe;
+                next_dir = disney_sample_lobe(s, direction, fnormal, mat_id, rnd, &diffuse_lobe);
+                r.branch |= diffuse_lobe ? SB_LOBE_DIFFUSE : SB_LOBE_SPECULAR;
+                f_or_b = 1.0f;
+                brdf = disney_evaluate_pdf(s, fnormal, vneg(direction), next_dir, mat_id, &brdf_pdf);
+                brdf *= fabs_(vdot(normal, next_dir));
+            }
+            v3 next_origin = offset_ray(h.pos, vscale(fnormal, signf(f_or_b)));
+            if (brdf_pdf > 0.0f) {
+                int alive = 1;
+                if (f_or_b < 0.0f) {
+                    float extinction = m[6];
+                    float R = m_exp(-h.t / extinction);
+                    if (tm_rand(seed, pixel, frame, dim0 + TM_SLOT_EXT) >= R) { alive = 0; r.branch |= SB_EXTINCT; }
+                }
+                if (alive) {
+                    throughout = vmul(throughout, vscale(reflect_color, brdf / brdf_pdf));
+                    r.want_next = !last_bounce;          /* depth reaches max_depth after the last bounce: the loop ends */
+                    r.next_o = next_origin; r.next_d = next_dir; r.next_thr = throughout; r.next_pdf = brdf_pdf; r.next_spec = perfect_spec;
+                }
+            } else r.branch |= SB_END_PDF;
+        }
+    } else {
+        /* PT_RGB.py:127-132 */
+        float dis = m_sqrt(direction.x * direction.x + direction.z * direction.z);
+        float tx = (m_atan2(direction.z, direction.x) + PI_SCENE) / PI_SCENE / 2.0f;
+        float ty = m_atan2(direction.y, dis) / PI_SCENE + 0.5f;
+        v3 e = srgb_to_lrgb(texture2d(s, tx, ty));
+        radiance = vadd(radiance, vscale(vmul(e, throughout), s->env_power));
+        r.branch |= ((direction.x - direction.x == 0.0f) & (direction.y - direction.y == 0.0f) & (direction.z - direction.z == 0.0f)) ? SB_MISS_FINITE : SB_MISS_NONFINITE;
+    }
+    r.radiance = radiance;
+    return r;
+}
+
 /* integrator/PT_RGB.py:49-132 for one pixel (i, j) at one frame; returns radiance */
 static v3 pt_rgb_pixel(const orc_scene *s, int i, int j, int H, uint32_t frame, uint32_t seed,
                        int max_depth, int32_t *stack, int stack_size, orc_stats *st)
@@ -1040,110 +1219,25 @@ static v3 pt_rgb_pixel(const orc_scene *s, int i, int j, int H, uint32_t frame, 
         next_dir = vnormalized(V(wx, wy, wz));
     }
     int depth = 0;
-    float light_pdf = 1.0f, brdf_pdf = 1.0f, f_or_b = 1.0f, brdf = 1.0f;
+    float brdf_pdf = 1.0f;
     int perfect_spec = 1;
     v3 throughout = V(1, 1, 1), radiance = V(0, 0, 0);
     if (st) st->paths++;
     while (depth < max_depth) {
         v3 origin = next_origin, direction = next_dir;
-        uint32_t dim0 = TM_DIM_BOUNCE0 + TM_DIMS_PER_BOUNCE * (uint32_t)depth;
         hit_t h = closet_hit(s, origin, direction, stack, stack_size, st);
-        if (h.t < INF_VALUE) {
-            v3 fnormal = vscale(h.nor, signf(vdot(vneg(direction), h.gnor)));      /* UtilsFunc.py:465-467 */
-            int mat_id = s->primitive[(size_t)h.prim * PRI_VEC + 2];
-            const float *m = s->material + (size_t)mat_id * MAT_VEC;
-            v3 mat_color = V(m[2], m[3], m[4]);
-            int mat_type = (int)m[0];
-            if (mat_type == MAT_LIGHT) {
-                float fCosTheta = fabs_(vdot(direction, h.gnor));
-                if (perfect_spec == 1) {
-                    radiance = vadd(radiance, vmul(throughout, mat_color));
-                } else {
-                    float area = get_prim_area(s, h.prim) * (float)s->light_count;
-                    light_pdf = (h.t * h.t) / (area * fCosTheta);
-                    radiance = vadd(radiance, vmul(vscale(throughout, power_heuristic(brdf_pdf, light_pdf)), mat_color));
-                }
-                break;
-            } else {
-                v3 reflect_color = srgb_to_lrgb(mat_color);
-                v3 normal = h.nor;
-                if (st) st->shaded++;
-                if (mat_type == MAT_GLASS) {
-                    perfect_spec = 1;
-                    next_dir = glass_sample(s, direction, normal, mat_id,
-                                            tm_rand(seed, pixel, frame, dim0 + TM_SLOT_GLASS), &f_or_b);
-                    brdf = 1.0f; brdf_pdf = 1.0f;                                   /* brdf/Glass.py:72-74 */
-                } else {
-                    perfect_spec = 0;
-                    /* Scene.py:477-518 sample_li.  A scene without emitters (light_count == 0, env-lit): the reference
-                     * would index light[-1] (Scene.py:423-428, undefined); defined here as "no NEE sample". */
-                    if (s->light_count > 0) {
-                    int lidx = (int)(tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LIGHT) * (float)s->light_count);
-                    if (lidx >= s->light_count) lidx = s->light_count - 1;
-                    int light_prim = s->light[lidx];
-                    float ra = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LA);
-                    float rb = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LB);
-                    v3 light_pos, light_normal;
-                    get_prim_random_point_normal(s, light_prim, ra, rb, &light_pos, &light_normal);
-                    int lmat = s->primitive[(size_t)light_prim * PRI_VEC + 2];
-                    const float *lm = s->material + (size_t)lmat * MAT_VEC;
-                    v3 light_emission = V(lm[2], lm[3], lm[4]);
-                    float light_area = get_prim_area(s, light_prim);
-                    float light_choice_pdf = 1.0f / ((float)s->light_count * light_area);
-                    light_normal = vnormalized(light_normal);
-                    v3 light_dir = vsub(h.pos, light_pos);
-                    float light_dist = vnorm(light_dir);
-                    light_dir = vdivs(light_dir, light_dist);
-                    light_emission = vscale(light_emission, light_shape_visible(s, light_prim, light_dir, light_normal, light_dist, &light_choice_pdf));
-                    /* PT_RGB.py:101-109 */
-                    float NdotL_surface = vdot(fnormal, light_dir);
-                    float NdotL_light = vdot(light_normal, light_dir);
-                    if ((NdotL_surface < 0.0f) & (NdotL_light > 0.0f)) {
-                        int shadow_prim;
-                        (void)closet_hit_shadow(s, light_pos, light_dir, stack, stack_size, &shadow_prim, st);
-                        if (shadow_prim == h.prim) {
-                            brdf = disney_evaluate_pdf(s, fnormal, vneg(direction), vneg(light_dir), mat_id, &brdf_pdf);
-                            light_pdf = light_dist * light_dist * light_choice_pdf / NdotL_light;
-                            if (brdf_pdf > 0.0f) {
-                                float w = power_heuristic(light_pdf, brdf_pdf) / fmax_(0.0001f, light_pdf);
-                                v3 c = vscale(light_emission, w);
-                                c = vmul(c, throughout);
-                                c = vmul(c, reflect_color);
-                                c = vscale(c, brdf);
-                                c = vscale(c, fabs_(NdotL_surface));
-                                radiance = vadd(radiance, c);
-                            }
-                        }
-                    }
-                    }   /* light_count > 0 */
-                    float rnd[3] = { tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LOBE),
-                                     tm_rand(seed, pixel, frame, dim0 + TM_SLOT_R1),
-                                     tm_rand(seed, pixel, frame, dim0 + TM_SLOT_R2) };
-                    next_dir = disney_sample(s, direction, fnormal, mat_id, rnd);
-                    f_or_b = 1.0f;
-                    brdf = disney_evaluate_pdf(s, fnormal, vneg(direction), next_dir, mat_id, &brdf_pdf);
-                    brdf *= fabs_(vdot(normal, next_dir));
-                }
-                next_origin = offset_ray(h.pos, vscale(fnormal, signf(f_or_b)));
-                if (brdf_pdf > 0.0f) {
-                    if (f_or_b < 0.0f) {
-                        float extinction = m[6];
-                        float R = m_exp(-h.t / extinction);
-                        if (tm_rand(seed, pixel, frame, dim0 + TM_SLOT_EXT) >= R) break;
-                    }
-                    throughout = vmul(throughout, vscale(reflect_color, brdf / brdf_pdf));
-                    depth += 1;
-                } else break;
-            }
-        } else {
-            /* PT_RGB.py:127-132 */
-            float dis = m_sqrt(direction.x * direction.x + direction.z * direction.z);
-            float tx = (m_atan2(direction.z, direction.x) + PI_SCENE) / PI_SCENE / 2.0f;
-            float ty = m_atan2(direction.y, dis) / PI_SCENE + 0.5f;
-            v3 e = srgb_to_lrgb(texture2d(s, tx, ty));
-            radiance = vadd(radiance, vscale(vmul(e, throughout), s->env_power));
-            break;
+        const shade_step r = pt_rgb_step(s, seed, pixel, frame, depth, depth == max_depth - 1, origin, direction, h.t, h.u, h.v, h.prim,
+                                         throughout, radiance, brdf_pdf, perfect_spec);
+        radiance = r.radiance;
+        if (st && r.shaded) st->shaded++;
+        if (r.want_shadow) {                                                        /* PT_RGB.py:104-109 */
+            int shadow_prim;
+            (void)closet_hit_shadow(s, r.sh_o, r.sh_d, stack, stack_size, &shadow_prim, st);
+            if (shadow_prim == r.sh_expect) radiance = vadd(radiance, r.sh_c);
         }
+        if (!r.want_next) break;
+        next_origin = r.next_o; next_dir = r.next_d; throughout = r.next_thr; brdf_pdf = r.next_pdf; perfect_spec = r.next_spec;
+        depth += 1;
     }
     return radiance;
 }
@@ -2564,6 +2658,30 @@ void orc_kat_glass_sample(const float *mat10, const float *dir, const float *N, 
     orc_scene s; memset(&s, 0, sizeof(s)); s.material = (float *)mat10;
     float fb; v3 r = glass_sample(&s, V(dir[0], dir[1], dir[2]), V(N[0], N[1], N[2]), 0, prob, &fb);
     out4[0] = r.x; out4[1] = r.y; out4[2] = r.z; out4[3] = fb;
+}
+/* pt_rgb_step row by row.  in: [n*in_stride] 32-bit words -- seed, pixel, frame, bounce, last_bounce (integers), origin3, direction3, t, u, v,
+ * prim (integer), throughout3, radiance3, brdf_pdf, perfect_spec (integer): 23 words; out: [n*out_stride] -- radiance3, shaded, want_next, next_o3,
+ * next_d3, next_thr3, next_pdf, next_spec, want_shadow, sh_o3, sh_d3, sh_c3, sh_expect, sh_dist (the 28 words of the device's tirt_kat_shade_step),
+ * then the branch word: 29 words.  A row with t < INF_VALUE must name a primitive of the scene. */
+int orc_kat_shade_step(const orc_scene *s, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    if (!s || !in || !out || in_stride < 23 || out_stride < 29 || n < 0) return -1;
+    for (int i = 0; i < n; i++) {
+        const float *a = in + (size_t)i * in_stride; const uint32_t *w = (const uint32_t *)a;
+        if (a[11] < INF_VALUE && ((int32_t)w[14] < 0 || (int32_t)w[14] >= s->n)) return -2;
+    }
+    for (int i = 0; i < n; i++) {
+        const float *a = in + (size_t)i * in_stride; const uint32_t *w = (const uint32_t *)a;
+        float *o = out + (size_t)i * out_stride; int32_t *oi = (int32_t *)o;
+        const shade_step r = pt_rgb_step(s, w[0], w[1], w[2], (int)w[3], (int)w[4] != 0, V(a[5], a[6], a[7]), V(a[8], a[9], a[10]), a[11], a[12], a[13], (int)w[14],
+                                         V(a[15], a[16], a[17]), V(a[18], a[19], a[20]), a[21], (int)w[22]);
+        o[0] = r.radiance.x; o[1] = r.radiance.y; o[2] = r.radiance.z; oi[3] = r.shaded; oi[4] = r.want_next;
+        o[5] = r.next_o.x; o[6] = r.next_o.y; o[7] = r.next_o.z; o[8] = r.next_d.x; o[9] = r.next_d.y; o[10] = r.next_d.z;
+        o[11] = r.next_thr.x; o[12] = r.next_thr.y; o[13] = r.next_thr.z; o[14] = r.next_pdf; oi[15] = r.next_spec; oi[16] = r.want_shadow;
+        o[17] = r.sh_o.x; o[18] = r.sh_o.y; o[19] = r.sh_o.z; o[20] = r.sh_d.x; o[21] = r.sh_d.y; o[22] = r.sh_d.z;
+        o[23] = r.sh_c.x; o[24] = r.sh_c.y; o[25] = r.sh_c.z; oi[26] = r.sh_expect; o[27] = r.sh_dist; oi[28] = (int32_t)r.branch;
+    }
+    return 0;
 }
 void orc_kat_offset_ray(const float *p, const float *n, float *out3)
 {

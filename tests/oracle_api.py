@@ -28,6 +28,12 @@ class OrcStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+# orc_kat_shade_step: words per output row (the device's 28 + the branch word) and the bits of the branch word (oracle.c, SB_*)
+SHADE_STEP_OUT = 29
+SB = {name: 1 << k for k, name in enumerate((
+    "emit_mis", "emit_spec", "glass_reflect", "glass_refract", "extinct", "nee", "nee_nopdf", "nee_reject", "lobe_diffuse", "lobe_specular", "end_pdf",
+    "miss_finite", "miss_nonfinite", "light_tri", "light_sphere", "light_spot", "light_laser"))}
+
 _libs = {}
 
 
@@ -71,7 +77,10 @@ def load(libm=False, native=False):
         L.orc_gen_aabb_rounds.argtypes = [_vp]
         L.orc_vertex_get.argtypes = [_vp, _f32p]
         L.orc_closest_hit_batch.argtypes = [_vp, _f32p, C.c_int, C.c_int, _f32p, _i32p, _vp]
+        L.orc_closest_hit_uv_batch.argtypes = [_vp, _f32p, C.c_int, C.c_int, _f32p, _i32p, _vp, _f32p]
         L.orc_shadow_hit_batch.argtypes = [_vp, _f32p, C.c_int, C.c_int, _f32p, _i32p, _vp]
+        L.orc_kat_shade_step.restype = C.c_int
+        L.orc_kat_shade_step.argtypes = [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]
         L.orc_pt_rgb_render.restype = C.c_int
         L.orc_pt_rgb_render.argtypes = [_vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int,
                                         _f32p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -171,15 +180,31 @@ class OracleScene:
         self.L.orc_vertex_get(self.h, out.reshape(-1))
         return out
 
-    def closest_hit(self, rays, stack_size=64, counts=False):
+    def closest_hit(self, rays, stack_size=64, counts=False, uv=False):
+        """(out[n,13], prim[n], counts); with uv=True also the barycentrics [n,2]: (t, u, v, prim) is the device's hit record"""
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         nr = rays.shape[0]
         out = np.zeros((nr, 13), np.float32)
         prim = np.zeros(nr, np.int32)
         cnt = np.zeros((nr, 2), np.int32) if counts else None
+        if uv:
+            bary = np.zeros((nr, 2), np.float32)
+            self.L.orc_closest_hit_uv_batch(self.h, rays.reshape(-1), nr, stack_size, out.reshape(-1), prim,
+                                            cnt.ctypes.data_as(_vp) if counts else None, bary.reshape(-1))
+            return out, prim, cnt, bary
         self.L.orc_closest_hit_batch(self.h, rays.reshape(-1), nr, stack_size, out.reshape(-1), prim,
                                      cnt.ctypes.data_as(_vp) if counts else None)
         return out, prim, cnt
+
+    def kat_shade_step(self, rows):
+        """orc_kat_shade_step: rows (n, 23) of 32-bit words (layout in oracle.c / include/tirt.h) -> (n, 29) float32 view, word 28 = the branch word"""
+        rows = np.ascontiguousarray(rows).view(np.float32)
+        n, stride = rows.shape
+        out = np.zeros((n, SHADE_STEP_OUT), np.float32)
+        rc = self.L.orc_kat_shade_step(self.h, rows.reshape(-1), stride, out.reshape(-1), SHADE_STEP_OUT, n)
+        if rc != 0:
+            raise ValueError("orc_kat_shade_step: %s" % {-1: "bad arguments", -2: "a hit row names no primitive of the scene"}.get(rc, rc))
+        return out
 
     def shadow_hit(self, rays, stack_size=64, counts=False):
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)

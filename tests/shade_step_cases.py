@@ -1,0 +1,351 @@
+"""Input rows for the known-answer tests of one shading step (tests/test_shade_step_host.py, tests/test_gpu_shade_step.py): four scenes and, per scene, about
+1e5 rows of (seed, pixel, frame, bounce, ray, hit record, path state) built deterministically from a seed.  Hits come from the CPU oracle
+(OracleScene.closest_hit), so the CPU test and the GPU test see the same rows and branch coverage is a property of the rows that needs no GPU.
+
+Row layout (include/tirt.h, tirt_kat_shade_step; 32-bit words, integers as themselves):
+   0 seed  1 pixel  2 frame  3 bounce  4 last_bounce  5..7 origin  8..10 direction  11 t  12 u  13 v  14 prim  15..17 throughout  18..20 radiance  21 brdf_pdf  22 perfect_spec
+"""
+import numpy as np
+
+import common
+import oracle_api
+from ti_raytrace_amd import _native, scenes, Example, PT_RGB
+from ti_raytrace_amd import SceneData as SCD
+
+IN_WORDS = _native.KAT_STEP_IN
+INF_VALUE = np.float32(1000000.0)
+MAX_DEPTH = 15
+FILM_W, FILM_H = 24, 16
+
+# output fields: name -> (first word, words, is float)
+OUT_FIELDS = [("radiance", 0, 3, True), ("shaded", 3, 1, False), ("want_next", 4, 1, False), ("next_o", 5, 3, True), ("next_d", 8, 3, True),
+              ("next_thr", 11, 3, True), ("next_pdf", 14, 1, True), ("next_spec", 15, 1, False), ("want_shadow", 16, 1, False), ("sh_o", 17, 3, True),
+              ("sh_d", 20, 3, True), ("sh_c", 23, 3, True), ("sh_expect", 26, 1, False), ("sh_dist", 27, 1, True)]
+
+METALLIC = (0.0, 0.3, 1.0)
+ROUGHNESS = (0.0, 0.0005, 0.001, 0.2, 1.0)
+COLOURS = ((0.0, 0.5, 1.0), (1.0, 0.0, 0.25), (0.8, 0.8, 0.8))          # a 0 and a 1 channel in two of them
+
+
+def disney(metal, rough, colour):
+    m = SCD.Material(); m.type = SCD.MAT_DISNEY; m.setMetal(metal); m.setRough(rough); m.setColor([colour[0], colour[1], colour[2], 1.0]); m.alebdoTex = -1
+    return m
+
+
+def glass(ior, extinction, colour=(0.9, 0.95, 1.0)):
+    m = SCD.Material(); m.type = SCD.MAT_GLASS; m.setIor(ior); m.setExtinciton(extinction); m.setColor([colour[0], colour[1], colour[2], 1.0]); m.alebdoTex = -1
+    return m
+
+
+def emitter(colour):
+    m = SCD.Material(); m.type = SCD.MAT_LIGHT; m.setColor([colour[0], colour[1], colour[2]]); m.alebdoTex = -1
+    return m
+
+
+def material_grid():
+    """45 Disney materials: metallic x roughness x colour"""
+    return [disney(me, ro, co) for co in COLOURS for me in METALLIC for ro in ROUGHNESS]
+
+
+def tilted_normals(pos, rng):
+    """vertex normals up to 83 degrees away from the face normal of triangles pos[k,3,3], each vertex by its own angle"""
+    e1, e2 = pos[:, 1] - pos[:, 0], pos[:, 2] - pos[:, 0]
+    fn = np.cross(e1, e2); fn /= np.linalg.norm(fn, axis=1, keepdims=True)
+    tang = e1 / np.linalg.norm(e1, axis=1, keepdims=True)
+    tilt = rng.uniform(0.3, 1.45, size=(pos.shape[0], 3, 1))
+    return np.cos(tilt) * fn[:, None, :] + np.sin(tilt) * tang[:, None, :]
+
+
+def add_material_grid(ex, scale=1.0, centre=(0.0, 0.0, 0.0), tris_per_material=3, seed=21):
+    """a triangle soup split into the materials of material_grid(); every third material gets vertex normals tilted away from the face normal (a shading
+    normal on the other side of the surface than the geometric one is what makes a BSDF pdf of -1 at an accepted NEE sample)"""
+    mats = material_grid()
+    tri = scenes.synthetic_triangles(tris_per_material * len(mats), seed, 0.25) * scale + np.asarray(centre)[None, None, :]
+    rng = np.random.RandomState(seed)
+    for k, m in enumerate(mats):
+        pos = tri[k * tris_per_material:(k + 1) * tris_per_material]
+        ex.scene.add_mesh(pos, m, tilted_normals(pos, rng) if k % 3 == 1 else None)
+    return len(mats)
+
+
+def sphere_shape(pos, radius):
+    sh = SCD.Shape(); sh.type = SCD.SHPAE_SPHERE; sh.pos = [float(x) for x in pos]; sh.setRadius(radius)
+    return sh
+
+
+def grid_sphere():
+    ex = Example.example(FILM_W, FILM_H, 4, 0)
+    add_material_grid(ex)
+    ex.scene.add_shape(sphere_shape((0.2, -0.1, 0.3), 0.35), disney(0.3, 0.2, (0.9, 0.4, 0.1)))
+    ex.add_sphere_light(pos=(0.0, 3.0, 0.0), radius=0.75, emission=50.0)
+    ex.add_sphere_light(pos=(-1.5, 0.5, 2.0), radius=0.2, emission=120.0)
+    ex.integrator = PT_RGB.PathTrace(FILM_W, FILM_H, ex.cam, ex.scene, 64)
+    return ex
+
+
+def grid_mesh():
+    ex = Example.example(FILM_W, FILM_H, 4, 0)
+    add_material_grid(ex)
+    # three emitter triangles of different areas, and a fourth with smooth (non-face) vertex normals
+    ex.scene.add_mesh(np.array([[[-0.5, 1.6, -0.5], [0.5, 1.6, -0.5], [0.0, 1.6, 0.6]]]), emitter((30.0, 28.0, 20.0)))
+    ex.scene.add_mesh(np.array([[[1.5, -0.2, -0.1], [1.5, 0.1, 0.0], [1.5, -0.1, 0.15]],
+                                [[-1.6, -1.0, -1.0], [-1.6, 1.0, -0.8], [-1.6, 0.0, 1.0]]]), emitter((8.0, 12.0, 40.0)))
+    nrm = np.array([[[0.3, -1.0, 0.0], [-0.3, -1.0, 0.2], [0.0, -1.0, -0.4]]])
+    nrm = nrm / np.linalg.norm(nrm, axis=2, keepdims=True)
+    ex.scene.add_mesh(np.array([[[0.6, 1.3, 0.6], [1.2, 1.3, 0.7], [0.8, 1.4, 1.3]]]), emitter((60.0, 60.0, 60.0)), nrm)
+    ex.integrator = PT_RGB.PathTrace(FILM_W, FILM_H, ex.cam, ex.scene, 64)
+    return ex
+
+
+def generic():
+    """Cornell box (Disney walls, quad light) + glass of three indices and two extinctions + sphere light + spot + laser under env.png"""
+    ex = common.spot_laser_scene(FILM_W, FILM_H, device_id=0)
+    tri = scenes.synthetic_triangles(20, 5, 0.3) * 200.0 + np.array([278.0, 270.0, -280.0])[None, None, :]
+    for k, (ior, ext) in enumerate(((1.0, 5.0), (1.3, 0.01), (1.3, 1.0e4), (2.4, 300.0), (2.4, 0.5))):
+        ex.scene.add_mesh(tri[4 * k:4 * k + 4], glass(ior, ext))
+    soup = scenes.synthetic_triangles(12, 9, 0.3) * 200.0 + np.array([278.0, 270.0, -280.0])[None, None, :]
+    ex.scene.add_mesh(soup[:6], disney(0.3, 0.001, COLOURS[0]), tilted_normals(soup[:6], np.random.RandomState(5)))
+    ex.scene.add_mesh(soup[6:], disney(1.0, 0.0, COLOURS[1]))
+    ex.add_sphere_light(pos=(400.0, 300.0, -150.0), radius=30.0, emission=80.0)
+    ex.scene.add_env(scenes.asset("image", "env.png"), 2.0)
+    return ex
+
+
+def env_only():
+    ex = Example.example(FILM_W, FILM_H, 4, 0)
+    add_material_grid(ex, tris_per_material=2)
+    ex.scene.add_env(scenes.asset("image", "env.png"), 2.0)
+    ex.integrator = PT_RGB.PathTrace(FILM_W, FILM_H, ex.cam, ex.scene, 64)
+    return ex
+
+
+SF = _native
+# name: (constructor, feature word of the scene, instantiations it runs on)
+SCENES = {
+    "grid_sphere": (grid_sphere, SF.SF_LIGHT_SPHERE, (SF.SF_LIGHT_SPHERE, SF.SF_ALL)),
+    "grid_mesh": (grid_mesh, SF.SF_LIGHT_TRI, (SF.SF_LIGHT_TRI, SF.SF_ALL)),
+    "generic": (generic, SF.SF_GLASS | SF.SF_ENV | SF.SF_LIGHT_TRI | SF.SF_LIGHT_SPHERE | SF.SF_LIGHT_SPOT_LASER, (SF.SF_ALL,)),
+    "env_only": (env_only, SF.SF_ENV | SF.SF_NO_LIGHT, (SF.SF_ALL,)),
+}
+
+
+def host_scene(name):
+    """the scene packed on the host with its camera (no device), and its oracle with the tree built"""
+    ex = SCENES[name][0]()
+    common.host_only(ex)
+    orc = oracle_api.OracleScene(ex.scene, ex.cam)
+    assert orc.lbvh_build() == ex.scene.primitive_count - 1
+    return ex, orc
+
+
+# ---- rows ---------------------------------------------------------------------------------------------------------------------
+SPECIAL = np.array([0.0, -0.0, 1.0e-42, 1.0e30, 3.0e38, np.inf, -np.inf, np.nan], np.float32)        # zero, denormal, huge, infinite, NaN
+
+
+def path_state(n, rng):
+    """(head[n,5] uint32, tail[n,8] float32): seed, pixel, frame, bounce, last_bounce / throughout3, radiance3, brdf_pdf, perfect_spec (as float bits later)"""
+    head = np.zeros((n, 5), np.uint32)
+    head[:, 0] = rng.choice(np.array([1, 7, 0xdeadbeef, 0], np.uint32), n)
+    pix = rng.randint(0, 1 << 20, n).astype(np.uint32)
+    pix[rng.rand(n) < 0.05] = 0
+    pix[rng.rand(n) < 0.02] = (1 << 31) - 2
+    head[:, 1] = pix
+    head[:, 2] = rng.choice(np.array([0, 0, 1, 2, 17, 4095, (1 << 31) + 5, 0xffffffff], np.uint32), n)
+    head[:, 3] = np.arange(n) % MAX_DEPTH
+    head[:, 4] = head[:, 3] == MAX_DEPTH - 1
+    tail = np.zeros((n, 7), np.float32)
+    tail[:, 0:3] = rng.uniform(0.0, 1.5, (n, 3))
+    tail[:, 3:6] = rng.uniform(0.0, 3.0, (n, 3)) * (rng.rand(n, 1) < 0.7)
+    for cols, frac in ((slice(0, 3), 0.15), (slice(3, 6), 0.03)):
+        sel = np.where(rng.rand(n) < frac)[0]
+        block = tail[:, cols]
+        block[sel, rng.randint(0, 3, sel.size)] = SPECIAL[rng.randint(0, SPECIAL.size, sel.size)]
+        tail[:, cols] = block
+    pdf = rng.uniform(0.01, 5.0, n)
+    wide = rng.rand(n) < 0.3
+    pdf[wide] = 10.0 ** rng.uniform(-30.0, 30.0, int(wide.sum()))
+    tail[:, 6] = pdf
+    spec = (rng.rand(n) < 0.4).astype(np.uint32)
+    return head, tail, spec
+
+
+def pack(head, o, d, t, u, v, prim, tail, spec):
+    n = head.shape[0]
+    rows = np.zeros((n, IN_WORDS), np.uint32)
+    f = rows.view(np.float32)
+    rows[:, 0:5] = head
+    f[:, 5:8] = o; f[:, 8:11] = d; f[:, 11] = t; f[:, 12] = u; f[:, 13] = v
+    rows[:, 14] = np.asarray(prim, np.int32).view(np.uint32)
+    f[:, 15:22] = tail
+    rows[:, 22] = spec
+    return rows
+
+
+def rows_from_rays(orc, rays, rng):
+    out, prim, _, bary = orc.closest_hit(rays, uv=True)
+    head, tail, spec = path_state(rays.shape[0], rng)
+    return pack(head, rays[:, 0:3], rays[:, 3:6], out[:, 0], bary[:, 0], bary[:, 1], prim, tail, spec)
+
+
+def unit(v):
+    return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+
+def real_hit_rows(ex, orc, rng, n_random=16000, n_bundle=8000, n_second=12000):
+    sc = ex.scene
+    lo, hi = sc.minboundarynp[0].astype(np.float64), sc.maxboundarynp[0].astype(np.float64)
+    mid, ext = 0.5 * (lo + hi), 0.5 * (hi - lo)
+    f32 = np.float32
+    # random rays from inside and outside the scene box
+    o = mid + ext * rng.uniform(-1.0, 1.0, (n_random, 3)) * np.where(rng.rand(n_random, 1) < 0.5, 0.9, 2.5)
+    tgt = mid + ext * rng.uniform(-1.0, 1.0, (n_random, 3))
+    d = np.where(rng.rand(n_random, 1) < 0.5, unit(tgt - o), unit(rng.normal(size=(n_random, 3))))
+    rays = [np.concatenate([o, d], axis=1).astype(f32)]
+    # camera-like coherent bundles: a pinhole outside the box, a regular grid of directions in a narrow cone
+    per = 400
+    for _ in range(n_bundle // per):
+        eye = mid + unit(rng.normal(size=3)) * np.linalg.norm(ext) * rng.uniform(1.5, 3.0)
+        fwd = unit(mid + ext * rng.uniform(-0.3, 0.3, 3) - eye)
+        side = unit(np.cross(fwd, [0.0, 1.0, 0.1])); up = np.cross(side, fwd)
+        g = (np.arange(20) - 9.5) / 20.0 * rng.uniform(0.2, 0.8)
+        dd = unit(fwd[None, None, :] + g[:, None, None] * side[None, None, :] + g[None, :, None] * up[None, None, :]).reshape(-1, 3)
+        rays.append(np.concatenate([np.broadcast_to(eye, dd.shape), dd], axis=1).astype(f32))
+    first = rows_from_rays(orc, np.concatenate(rays, axis=0), rng)
+    # second-bounce rays: the continuation the oracle's step gives the first hits with an ordinary state (they start at offset_ray points)
+    plain = first.copy()
+    pf = plain.view(np.float32)
+    pf[:, 15:18] = 1.0; pf[:, 18:21] = 0.0; pf[:, 21] = 1.0; plain[:, 3] = 0; plain[:, 4] = 0
+    step = orc.kat_shade_step(plain)
+    go = np.where(step.view(np.int32)[:, 4] == 1)[0][:n_second]
+    second = rows_from_rays(orc, np.ascontiguousarray(step[go, 5:11]), rng)
+    return np.concatenate([first, second], axis=0)
+
+
+def geometric_normals(ex, orc):
+    """per primitive: (gnor as the oracle computes it, a point on it) for triangles -- from a closest hit of a short ray aimed at the centroid;
+    (nan, centre) for shapes"""
+    sc = ex.scene
+    n = sc.primitive_count
+    gn = np.full((n, 3), np.nan, np.float32)
+    tri = np.where(sc.primitive_np[:, 0] == SCD.PRIMITIVE_TRI)[0]
+    v = sc.vertex_np[:, 0:3].astype(np.float64)
+    first = sc.primitive_np[tri, 1]
+    a, b, c = v[first], v[first + 1], v[first + 2]
+    fn = unit(np.cross(b - a, c - a))
+    cen = (a + b + c) / 3.0
+    reach = np.linalg.norm(b - a, axis=1, keepdims=True) * 0.01
+    rays = np.concatenate([cen + fn * reach, -fn], axis=1).astype(np.float32)
+    out, prim, _ = orc.closest_hit(rays)
+    ok = prim == tri
+    gn[tri[ok]] = out[ok, 4:7]
+    gn[tri[~ok]] = fn[~ok].astype(np.float32)          # (a triangle hidden behind another within 1 % of its edge: the normal to float precision)
+    return gn
+
+
+COS_SWEEP = (1.0, 0.9, 0.5, 0.1, 1.0e-2, 1.0e-4, 1.0e-6)      # from normal incidence to within 1e-6 of grazing
+BARY = ((0.0, 0.0), (1.0, 0.0), (0.0, 1.0), (0.5, 0.5), (0.25, 0.75), (1.0 / 3.0, 1.0 / 3.0))
+
+
+def synthetic_hit_rows(ex, orc, rng, repeats=3):
+    """hit records that no ray produced, on every primitive: barycentrics at the corners, on the edge u + v = 1 and at the centre; directions swept from
+    normal incidence to grazing on both sides of gnor, exactly perpendicular to gnor, and +-gnor; emitters also with t tiny and huge"""
+    sc = ex.scene
+    gn = geometric_normals(ex, orc)
+    f32 = np.float32
+    o_l, d_l, t_l, u_l, v_l, p_l = [], [], [], [], [], []
+    light_mat = sc.material_np[sc.primitive_np[:, 2], 0] == SCD.MAT_LIGHT
+    for p in range(sc.primitive_count):
+        is_tri = sc.primitive_np[p, 0] == SCD.PRIMITIVE_TRI
+        if is_tri:
+            g = gn[p].astype(np.float64)
+            vi = sc.primitive_np[p, 1]
+            v1, v2, v3 = sc.vertex_np[vi:vi + 3, 0:3].astype(np.float64)
+        else:
+            sh = sc.shape_np[sc.primitive_np[p, 1]]
+            g = unit(rng.normal(size=3))
+            v1 = v2 = v3 = sh[1:4].astype(np.float64) + g * float(sh[4])          # a point of the sphere (spot, laser: of a sphere of "radius" param[0])
+        tang = unit(np.cross(g, [0.3, -0.5, 0.8]))
+        dirs = []
+        for c in COS_SWEEP:
+            s = np.sqrt(max(0.0, 1.0 - c * c))
+            for side in (1.0, -1.0):
+                phi = rng.uniform(0.0, 2.0 * np.pi)
+                tg = np.cos(phi) * tang + np.sin(phi) * np.cross(g, tang)
+                dirs.append((-side * c * g + s * tg).astype(f32))
+        gf = gn[p] if is_tri else g.astype(f32)
+        dirs.append(np.array([gf[1], -gf[0], 0.0], f32))        # (gx * gy + gy * -gx) + gz * 0 is exactly 0 in float32: perpendicular, not normalised
+        dirs.append(gf.copy()); dirs.append(-gf)
+        ts = (1.0,) if not light_mat[p] else (1.0, 1.0e-30, 1.0e-3, 9.9e5)
+        for (u, v) in BARY:
+            pos = v1 * (1.0 - u - v) + v2 * u + v3 * v
+            for d in dirs:
+                for t in ts:
+                    o_l.append((pos - d.astype(np.float64) * min(t, 10.0)).astype(f32)); d_l.append(d); t_l.append(t); u_l.append(u); v_l.append(v); p_l.append(p)
+    o, d = np.tile(np.asarray(o_l, f32), (repeats, 1)), np.tile(np.asarray(d_l, f32), (repeats, 1))
+    t, u, v, p = (np.tile(np.asarray(x), repeats) for x in (t_l, u_l, v_l, p_l))
+    head, tail, spec = path_state(o.shape[0], rng)
+    rows = pack(head, o, d, t.astype(f32), u.astype(f32), v.astype(f32), p, tail, spec)
+    return rows
+
+
+def miss_rows(rng, per_direction=150):
+    nan, inf = np.nan, np.inf
+    finite = [(1, 0, 0), (-1, 0, 0), (0, 0, 1), (0, 0, -1), (0, 1, 0), (0, -1, 0), (0.6, 0.0, 0.8), (0.0, 0.6, -0.8), (1.0e-20, 1.0, 0.0), (0, 0, 0)]
+    finite += [tuple(x) for x in unit(np.random.RandomState(4).normal(size=(14, 3)))]
+    nonfinite = [(nan, 0, 1), (0, nan, 1), (1, 0, nan), (nan, nan, 0.5), (nan, 0.5, nan), (0.5, nan, nan), (nan, nan, nan),
+                 (inf, 0.2, 0.3), (-inf, 0.2, 0.3), (0.2, 0.3, inf), (0.2, 0.3, -inf), (inf, 0.1, inf), (-inf, 0.1, inf), (inf, 0.1, -inf),
+                 (0.3, inf, 0.4), (0.3, -inf, 0.4), (inf, inf, 0.4), (0.3, -inf, -inf), (inf, inf, inf), (inf, nan, 0.0), (0.0, inf, 0.0), (nan, inf, inf)]
+    d = np.repeat(np.asarray(finite + nonfinite, np.float32), per_direction, axis=0)
+    n = d.shape[0]
+    head, tail, spec = path_state(n, rng)
+    t = rng.choice(np.array([1.0e6, 2.0e6, np.inf, np.nan, 3.0e38], np.float32), n)
+    o = rng.uniform(-2.0, 2.0, (n, 3)).astype(np.float32)
+    return pack(head, o, d, t, np.zeros(n, np.float32), np.zeros(n, np.float32), np.full(n, -1), tail, spec)
+
+
+_cache = {}
+
+
+def build(name, seed=2024):
+    """(ex, orc, rows[n, 23] uint32) for one scene; cached per process"""
+    key = (name, seed)
+    if key not in _cache:
+        ex, orc = host_scene(name)
+        rng = np.random.RandomState(seed)
+        nprim = ex.scene.primitive_count
+        rows = np.concatenate([real_hit_rows(ex, orc, rng), synthetic_hit_rows(ex, orc, rng, repeats=max(1, 60000 // (nprim * 120))), miss_rows(rng)], axis=0)
+        _cache[key] = (ex, orc, np.ascontiguousarray(rows))
+    return _cache[key]
+
+
+def describe(rows, out_want, k, ex):
+    """one line about row k for a failure report: branch word, material row, hit record"""
+    f = rows.view(np.float32)
+    br = int(out_want.view(np.uint32)[k, 28]) if out_want.shape[1] > 28 else 0
+    names = "+".join(n for n, b in oracle_api.SB.items() if br & b) or "-"
+    prim = int(rows.view(np.int32)[k, 14])
+    mat = ex.scene.material_np[ex.scene.primitive_np[prim, 2]].tolist() if (f[k, 11] < INF_VALUE and 0 <= prim < ex.scene.primitive_count) else None
+    return "row %d branch %s prim %d t %r uv (%r, %r) dir %s state %s material %s" % (
+        k, names, prim, float(f[k, 11]), float(f[k, 12]), float(f[k, 13]), f[k, 8:11].tolist(), f[k, 15:22].tolist() + [int(rows[k, 22])], mat)
+
+
+def first_differences(got, want, rows, ex, limit=8):
+    """[] if the 28 words agree on every row (integers equal, floats bit-identical, NaN exactly where `want` has NaN); else a report of the first rows"""
+    gi, wi = got.view(np.uint32)[:, :28], want.view(np.uint32)[:, :28]
+    eq = gi == wi
+    fcols = np.zeros(28, bool)
+    for _, first, words, is_float in OUT_FIELDS:
+        if is_float:
+            fcols[first:first + words] = True
+    both_nan = np.isnan(got[:, :28]) & np.isnan(want[:, :28]) & fcols[None, :]
+    bad = ~(eq | both_nan)
+    report = []
+    for k in np.where(bad.any(axis=1))[0][:limit]:
+        fields = [name for name, first, words, _ in OUT_FIELDS if bad[k, first:first + words].any()]
+        detail = "; ".join("%s got %s want %s" % (name, got[k, first:first + words].tolist() if fl else gi[k, first:first + words].view(np.int32).tolist(),
+                                                   want[k, first:first + words].tolist() if fl else wi[k, first:first + words].view(np.int32).tolist())
+                           for name, first, words, fl in OUT_FIELDS if name in fields)
+        report.append(describe(rows, want, int(k), ex) + " :: " + detail)
+    if report:
+        report.insert(0, "%d of %d rows differ" % (int(bad.any(axis=1).sum()), got.shape[0]))
+    return report

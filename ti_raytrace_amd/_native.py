@@ -65,6 +65,9 @@ AOV_ALPHA = 7
 
 # bits of the scene feature word (include/tirt.h, tirt_shade_features)
 SF_GLASS, SF_ENV, SF_LIGHT_TRI, SF_LIGHT_SPOT_LASER, SF_NO_LIGHT, SF_LIGHT_SPHERE, SF_LIGHT_OTHER = 1, 2, 4, 8, 16, 32, 64
+SF_ALL = 127
+SHADE_INSTANTIATIONS = (SF_LIGHT_SPHERE, SF_LIGHT_TRI, SF_ALL)      # the feature words k_shade / k_shade_spec are compiled for, narrowest first
+KAT_STEP_IN, KAT_STEP_OUT = 23, 28                                  # words per row of tirt_kat_shade_step
 
 # context options that select code rather than tune it: name -> (default, meaning).  (The tuning options are listed in include/tirt.h.)
 OPTIONS = {
@@ -130,6 +133,7 @@ SIGNATURES = {
     "tirt_kat_spec": (C.c_int, [_vp, C.c_int, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
     "tirt_shade_table_download": (C.c_int, [_vp, C.c_int, _f32p, C.c_uint64]),
     "tirt_kat_shade_tables": (C.c_int, [_vp, C.c_int, _vp, _f32p, C.c_int]),
+    "tirt_kat_shade_step": (C.c_int, [_vp, C.c_uint32, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
     "tirt_obj_load": (C.c_int, [C.c_char_p, C.POINTER(_vp)]),
     "tirt_obj_free": (None, [_vp]),
     "tirt_obj_material_count": (C.c_int, [_vp]),
@@ -511,12 +515,25 @@ class Context:
         check(lib().tirt_kat_shade_tables(self.handle, int(which), _ptr(inp), out.reshape(-1), int(n)))
         return out
 
+    def kat_shade_step(self, feat, rows, out_stride=KAT_STEP_OUT):
+        """include/tirt.h, tirt_kat_shade_step: rows (n, >= 23) of 32-bit words (float32 view; integers as bit patterns) -> (n, out_stride) float32."""
+        return kat_shade_step(self.handle, feat, rows, out_stride)
+
     def kat_spec(self, which, inp, out_stride):
         inp = np.ascontiguousarray(inp, np.float32)
         n, stride = inp.shape
         out = np.zeros((n, out_stride), np.float32)
         check(lib().tirt_kat_spec(self.handle, int(which), inp.reshape(-1), stride, out.reshape(-1), out_stride, n))
         return out
+
+
+def kat_shade_step(handle, feat, rows, out_stride=KAT_STEP_OUT, in_stride=None):
+    """tirt_kat_shade_step on a raw context handle (None: only the refusals that need no context can be reached)."""
+    rows = np.ascontiguousarray(rows).view(np.float32)
+    n, stride = rows.shape
+    out = np.zeros((n, max(int(out_stride), 1)), np.float32)
+    check(lib().tirt_kat_shade_step(handle, int(feat), rows.reshape(-1), int(stride if in_stride is None else in_stride), out.reshape(-1), int(out_stride), n))
+    return out
 
 
 def shade_features_host(material, primitive, shape, light, light_count, env=None, env_power=0.0):

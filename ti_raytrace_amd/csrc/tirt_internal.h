@@ -476,4 +476,6 @@ int ensure_shade_records(tirt_ctx *c);
 void refresh_shade_features(tirt_ctx *c);      // tirt_api.hip
 int sync_all(tirt_ctx *c);
 int flush_pending(tirt_ctx *c);
+bool kat_shade_step_has_inst(unsigned feat);      // tirt_render.hip: is `feat` the word of an instantiation of k_shade
+int kat_shade_step(tirt_ctx *c, unsigned feat, const float *in, int in_stride, float *out, int out_stride, int n);
 }  // namespace tirt

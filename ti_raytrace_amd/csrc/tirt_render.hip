@@ -1236,6 +1236,77 @@ static const T &pick_shade_inst(const T (&tab)[N], const tirt_ctx *c)
     return tab[N - 1];
 }
 
+// ---- known-answer evaluation of one shading step (tirt_kat_shade_step, include/tirt.h): shade_path<FEAT> -- the body of k_shade<FEAT> -- on row i of a table of
+// hit records and path states, on the context's own tables.  (pixel, frame) reach it the way they reach k_shade, through a TileMap: one tile that holds every
+// pixel (local pixel = pixel), frame-major paths with P = INT_MAX (slot = pixel gives frame 0 of the batch) and frame_begin = the row's frame.  Rows: the 23
+// words in / 28 words out of include/tirt.h; integers travel as their bit patterns. ----
+constexpr int KAT_STEP_IN = 23, KAT_STEP_OUT = 28;
+template <unsigned FEAT, int MIN_WAVES>
+__global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_kat_shade_step(SceneView sc, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *a = in + (size_t)i * in_stride;
+    float *o = out + (size_t)i * out_stride;
+    const TileMap tm = {0, 1, 0x7fffffff, 1, 0, 0};
+    v3 radiance = V(a[18], a[19], a[20]);
+    ShadeStep ss;
+    shade_path<FEAT>(sc, tm, 0x7fffffff, (uint32_t)__float_as_int(a[2]), (uint32_t)__float_as_int(a[0]), __float_as_int(a[3]), __float_as_int(a[4]) != 0, __float_as_int(a[1]),
+                     V(a[5], a[6], a[7]), V(a[8], a[9], a[10]), make_float4(a[11], a[12], a[13], a[14]), V(a[15], a[16], a[17]), radiance, a[21], __float_as_int(a[22]), ss);
+    o[0] = radiance.x; o[1] = radiance.y; o[2] = radiance.z; o[3] = __int_as_float(ss.shaded ? 1 : 0); o[4] = __int_as_float(ss.want_next ? 1 : 0);
+    o[5] = ss.next_o.x; o[6] = ss.next_o.y; o[7] = ss.next_o.z; o[8] = ss.next_d.x; o[9] = ss.next_d.y; o[10] = ss.next_d.z;
+    o[11] = ss.next_thr.x; o[12] = ss.next_thr.y; o[13] = ss.next_thr.z; o[14] = ss.next_pdf; o[15] = __int_as_float(ss.next_spec); o[16] = __int_as_float(ss.want_shadow ? 1 : 0);
+    o[17] = ss.sh_o.x; o[18] = ss.sh_o.y; o[19] = ss.sh_o.z; o[20] = ss.sh_d.x; o[21] = ss.sh_d.y; o[22] = ss.sh_d.z;
+    o[23] = ss.sh_c.x; o[24] = ss.sh_c.y; o[25] = ss.sh_c.z; o[26] = __int_as_float(ss.sh_expect); o[27] = ss.sh_dist;
+}
+typedef void (*kat_step_fn_t)(SceneView, const float *, int, float *, int, int);
+struct KatStepInst { unsigned feat; kat_step_fn_t fn; };
+static const KatStepInst KAT_STEP_INST[] = {       // one per entry of SHADE_INST, same word, same launch bounds
+    {SF_I_SPHERE, k_kat_shade_step<SF_I_SPHERE, SH_MIN_WAVES_NARROW>}, {SF_I_MESH, k_kat_shade_step<SF_I_MESH, SH_MIN_WAVES_NARROW>},
+    {SF_ALL, k_kat_shade_step<SF_ALL, SH_MIN_WAVES>}};
+static_assert(sizeof(KAT_STEP_INST) / sizeof(KAT_STEP_INST[0]) == sizeof(SHADE_INST) / sizeof(SHADE_INST[0]), "one known-answer kernel per instantiation of k_shade");
+
+static kat_step_fn_t kat_step_inst(unsigned feat)
+{
+    for (const KatStepInst &k : KAT_STEP_INST) if (k.feat == feat) return k.fn;
+    return nullptr;
+}
+bool kat_shade_step_has_inst(unsigned feat) { return kat_step_inst(feat) != nullptr; }
+// the arguments that need no context were checked by the caller (tirt_api.hip); here: what depends on the scene, then the launch
+int kat_shade_step(tirt_ctx *c, unsigned feat, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    TIRT_REQUIRE(c->n >= 1, "tirt_kat_shade_step: no scene");
+    TIRT_REQUIRE((c->shade_features & ~feat) == 0u, "tirt_kat_shade_step: feat does not cover the scene's feature word (tirt_shade_features)");
+    const kat_step_fn_t fn = kat_step_inst(feat);
+    TIRT_REQUIRE(fn, "tirt_kat_shade_step: feat is not an instantiation of k_shade");
+    for (int i = 0; i < n; i++) {
+        const float *a = in + (size_t)i * in_stride;
+        const int32_t *w = (const int32_t *)a; const int32_t prim = w[14], pixel = w[1];
+        TIRT_REQUIRE(!(a[11] < INF_VALUE) || (prim >= 0 && prim < c->n), "tirt_kat_shade_step: row " + std::to_string(i) + ": prim outside [0, n_prims) of a hit (t < INF)");
+        TIRT_REQUIRE(pixel >= 0 && pixel < 0x7fffffff, "tirt_kat_shade_step: row " + std::to_string(i) + ": pixel outside [0, 2^31 - 1)");
+    }
+    if (n == 0) return TIRT_OK;
+    if (sync_all(c)) return TIRT_ERR_HIP;
+    if (ensure_shade_records(c)) return TIRT_ERR_HIP;
+    DevBuf din, dout;
+    int rc = TIRT_OK;
+    const size_t in_bytes = sizeof(float) * (size_t)n * in_stride, out_bytes = sizeof(float) * (size_t)n * out_stride;
+    if (din.ensure(in_bytes) || dout.ensure(out_bytes)) rc = TIRT_ERR_HIP;
+    if (rc == TIRT_OK) {
+        hipError_t e = hipMemcpyAsync(din.p, in, in_bytes, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(dout.p, 0, out_bytes, c->stream);          // (the words of a row beyond the 28: zero)
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(fn, dim3((n + SH_BLOCK - 1) / SH_BLOCK), dim3(SH_BLOCK), 0, c->stream, scene_view(c), din.as<float>(), in_stride, dout.as<float>(), out_stride, n);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, out_bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { set_error(std::string("tirt_kat_shade_step: ") + hipGetErrorString(e)); rc = TIRT_ERR_HIP; }
+    }
+    din.release(); dout.release();
+    return rc;
+}
+
 // integrator/PT_Spec.py:141-158 (AddSplat) + :273-274, frames applied in order
 __global__ void k_film_spec(PathState ps, const float *fw, SpecView sp, TileMap tm, int P, int F, uint32_t frame_begin, uint32_t seed, float *hdr)
 {
