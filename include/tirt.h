@@ -276,6 +276,33 @@ int tirt_aov_enable(tirt_ctx *ctx, int on);
 int tirt_aov_download(tirt_ctx *ctx, float *out);
 int tirt_aov_export_device(tirt_ctx *ctx, void *dev_dst);
 
+/* Edge-avoiding a-trous denoiser over the film and its feature buffers (csrc/tirt_denoise.hip; no reference counterpart): the joint-bilateral wavelet filter of
+ * Dammertz et al. 2010 on albedo-demodulated radiance, guided by the records' first-hit normal and depth.  It writes a buffer of its own; hdr, rgb_film and
+ * the records are only read.  All f32, one rounding per operation in the order written (tests/denoise_expected.py restates it; the device gives its bits):
+ *   prepare, per pixel p = i*H + j with record words alb[3], n[3], z, al:  d = fmaxf(alb + (1 - al), 1e-3) per channel (the missed share of a pixel counts as
+ *     albedo 1),  e = hdr / d,  rz = 1 / fmaxf(z*z, 1e-12)
+ *   level l = 0 .. levels-1, step = 1 << l, on the host ic = 1 / (s*s) with s = sigma_c * 2^-l, in = 1 / (sigma_n*sigma_n), iz = 1 / (sigma_z*sigma_z): the taps
+ *     q = (i + di*step, j + dj*step), di = -2..2 outer, dj = -2..2 inner, those outside the film skipped, the centre included:
+ *       k = h[|di|] * h[|dj|], h = {0.375, 0.25, 0.0625};  dc = ((e_p.r-e_q.r)^2 + (e_p.g-e_q.g)^2) + (e_p.b-e_q.b)^2;  dn the same over n;
+ *       dz = ((z_p-z_q) * (z_p-z_q)) * rz_p;  x = (dc*ic + dn*in) + dz*iz;  w = k * exp(-x), exp as tirt_kat_math fn 2;
+ *       a tap counts only if w and all of e_q are finite: sum_c += e_q * w per channel, sum_w += w
+ *     e'_p = sum_c / sum_w; a pixel whose own e_p is not finite keeps it (the film's NaN pixels stay and poison no neighbour).  A NaN normal makes every w of its
+ *     pixel NaN, its own centre tap included: such a pixel drops out of its neighbours' sums and comes out NaN itself (0 / 0)
+ *   remodulate: out = e * d
+ * tirt_denoise_t: levels 1..8, sigmas finite and > 0, else TIRT_ERR_ARG; a NULL pointer means the defaults {5, 1.0, 0.3, 0.1}.
+ * tirt_denoise: the context's hdr with its records into a context-owned buffer, on the main stream after the last film and record update; asynchronous.
+ *   TIRT_ERR_ARG without a film, without enabled feature buffers, or with tile_count > 1 (a rank's film is partial: reduce, then tirt_denoise_device).
+ * tirt_denoise_download / tirt_denoise_export_device: out[W*H*3], as tirt_film_download / tirt_film_export_device; TIRT_ERR_ARG before the first tirt_denoise
+ *   of this film.  tirt_film_create drops the buffer and the filter's scratch (60 B per pixel); tirt_film_clear leaves both alone.
+ * tirt_denoise_device: the same filter on caller-owned device arrays hdr [W,H,3], aov [W,H,TIRT_AOV_WORDS] (16-byte aligned), out [W,H,3] (e.g. torch tensors);
+ *   needs no film.  Ordering on `stream`, the pointer checks and the refusal of a capturing stream are tirt_query_closest's; out may not overlap the inputs.
+ * First-hit guides know nothing of what is seen through glass or in a mirror: there the filter can blur detail the guides do not show. */
+typedef struct { int levels; float sigma_c, sigma_n, sigma_z; } tirt_denoise_t;
+int tirt_denoise(tirt_ctx *ctx, const tirt_denoise_t *params);
+int tirt_denoise_download(tirt_ctx *ctx, float *out);
+int tirt_denoise_export_device(tirt_ctx *ctx, void *dev_dst);
+int tirt_denoise_device(tirt_ctx *ctx, const float *hdr, const float *aov, float *out, int W, int H, const tirt_denoise_t *params, void *stream);
+
 /* Scene.closet_hit / closet_hit_shadow on a batch of rays (Scene.py:702-744, 671-699).  The default (ordered) traversal returns the
  * reference's hit bit for bit for every ray but the in-plane rays named under "traversal_tree" above; rays that start more than 8
  * scene extents away are traced without distance culling (from there the reference's own distances are rounding noise), so they

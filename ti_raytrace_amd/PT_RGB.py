@@ -37,6 +37,8 @@ class PathTrace:
         # extension: feature buffers of the film's own camera rays, for a denoiser or a compositor
         self.aov = aov
         self._aov_fields()
+        # extension: the film after denoise(), a buffer of its own beside hdr
+        self.denoised = DeviceField("denoised", scene, self._denoised_download)
 
     def _aov_fields(self):
         """the feature buffers as fields (aov=True): first-hit albedo and shading normal [W, H, 3], depth and coverage [W, H], means over the
@@ -61,6 +63,25 @@ class PathTrace:
         ctx = self.scene.ctx
         out = torch.empty((self.imgSizeX, self.imgSizeY, _native.AOV_WORDS), dtype=torch.float32, device=torch.device("cuda", ctx.device_id))
         ctx.aov_export_device(out.data_ptr())
+        return out
+
+    def denoise(self, levels=5, sigma_c=1.0, sigma_n=0.3, sigma_z=0.1):
+        """Filter hdr with the edge-avoiding a-trous wavelet, guided by the feature buffers (aov=True; include/tirt.h, tirt_denoise), into
+        `denoised`.  hdr, rgb_film and the feature buffers are only read.  Asynchronous."""
+        self.scene.ctx.denoise(levels, sigma_c, sigma_n, sigma_z)
+
+    def _denoised_download(self):
+        return self.scene.ctx.denoise_download(self.imgSizeX, self.imgSizeY)
+
+    def denoised_to_torch(self):
+        """`denoised` as a float32 tensor [W, H, 3] on the context's device, filled device to device (tirt_denoise_export_device)."""
+        try:
+            import torch
+        except ImportError as exc:
+            raise ImportError("denoised_to_torch needs PyTorch (ROCm build); denoised.to_numpy() and the C-ABI tirt_denoise_download work without it") from exc
+        ctx = self.scene.ctx
+        out = torch.empty((self.imgSizeX, self.imgSizeY, 3), dtype=torch.float32, device=torch.device("cuda", ctx.device_id))
+        ctx.denoise_export_device(out.data_ptr())
         return out
 
     def _download(self, hdr):

@@ -50,8 +50,10 @@ class PathTrace:
         self.rgb_film = DeviceField("rgb_film", scene, lambda: self._download(False))
         self.aov = aov                               # the feature buffers of PT_RGB.PathTrace: the camera rays and the launch are the same
         self._aov_fields()
+        self.denoised = DeviceField("denoised", scene, self._denoised_download)      # the film after denoise(), as PT_RGB.PathTrace's
 
     _aov_fields, aov_to_numpy, aov_to_torch = PT_RGB.PathTrace._aov_fields, PT_RGB.PathTrace.aov_to_numpy, PT_RGB.PathTrace.aov_to_torch
+    denoise, _denoised_download, denoised_to_torch = PT_RGB.PathTrace.denoise, PT_RGB.PathTrace._denoised_download, PT_RGB.PathTrace.denoised_to_torch
 
     def _download(self, hdr):
         h, r = self.scene.ctx.film_download(self.imgSizeX, self.imgSizeY, want_hdr=hdr, want_rgb=not hdr)

@@ -156,6 +156,20 @@ SIGNATURES.update({
     "tirt_pt_spec_render": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int]),
 })
 
+class DenoiseParams(C.Structure):
+    """tirt_denoise_t (include/tirt.h)"""
+    _fields_ = [("levels", C.c_int), ("sigma_c", C.c_float), ("sigma_n", C.c_float), ("sigma_z", C.c_float)]
+
+
+DENOISE_DEFAULTS = {"levels": 5, "sigma_c": 1.0, "sigma_n": 0.3, "sigma_z": 0.1}      # what a NULL tirt_denoise_t means
+
+SIGNATURES.update({
+    "tirt_denoise": (C.c_int, [_vp, C.POINTER(DenoiseParams)]),
+    "tirt_denoise_download": (C.c_int, [_vp, _vp]),
+    "tirt_denoise_export_device": (C.c_int, [_vp, _vp]),
+    "tirt_denoise_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(DenoiseParams), _vp]),
+})
+
 _lib = None
 
 
@@ -416,6 +430,27 @@ class Context:
 
     def aov_export_device(self, dev_ptr):
         check(lib().tirt_aov_export_device(self.handle, C.c_void_p(int(dev_ptr))))
+
+    def denoise(self, levels=5, sigma_c=1.0, sigma_n=0.3, sigma_z=0.1):
+        """tirt_denoise: the a-trous filter over the context's film and feature buffers into a buffer of its own (include/tirt.h); asynchronous"""
+        prm = DenoiseParams(int(levels), float(sigma_c), float(sigma_n), float(sigma_z))
+        check(lib().tirt_denoise(self.handle, C.byref(prm)))
+
+    def denoise_download(self, W, H):
+        """[W, H, 3] float32: the filtered film of the last denoise()"""
+        out = np.zeros((W, H, 3), np.float32)
+        check(lib().tirt_denoise_download(self.handle, _ptr(out)))
+        return out
+
+    def denoise_export_device(self, dev_ptr):
+        check(lib().tirt_denoise_export_device(self.handle, C.c_void_p(int(dev_ptr))))
+
+    def denoise_device(self, hdr, aov, out, W, H, levels=5, sigma_c=1.0, sigma_n=0.3, sigma_z=0.1, stream=0):
+        """tirt_denoise_device on device memory: hdr [W, H, 3], aov [W, H, 8], out [W, H, 3] are integer device addresses, `stream` a hipStream_t
+        handle (0 = the null stream).  Asynchronous; ti_raytrace_amd.denoise is the torch front end."""
+        prm = DenoiseParams(int(levels), float(sigma_c), float(sigma_n), float(sigma_z))
+        check(lib().tirt_denoise_device(self.handle, _vp(int(hdr) or None), _vp(int(aov) or None), _vp(int(out) or None), int(W), int(H),
+                                        C.byref(prm), _vp(int(stream) or None)))
 
     def trace_closest(self, rays, stack_size=64, flags=0):
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)

@@ -479,7 +479,7 @@ void tirt_destroy(tirt_ctx *c)
     drain_render_events(c);
     DevBuf *bufs[] = {&c->vertex, &c->primitive, &c->material, &c->shape, &c->light, &c->env, &c->mat_lrgb, &c->shade_rec, &c->light_rec, &c->morton_unsorted, &c->keys_a,
                       &c->keys_b, &c->vals_a, &c->vals_b, &c->hist, &c->morton_sorted, &c->bvh_node, &c->compact, &c->parent,
-                      &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb, &c->aov,
+                      &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb, &c->aov, &c->dn_mem, &c->dn_out,
                       &c->counters_mem, &c->spill, &c->trace_stage, &c->debug_mem, &c->query_mem, &c->dyn_mem, &c->dev_counters, &c->bdpt_px, &c->timeline, &c->pvb_set[0].count, &c->pvb_set[0].cand, &c->pvb_set[0].bound, &c->pvb_set[1].count, &c->pvb_set[1].cand, &c->pvb_set[1].bound, &c->pvb_stat, &c->pvb_tmp};
     for (DevBuf *b : bufs) b->release();
     for (auto &bl : c->bd) {
@@ -817,6 +817,10 @@ int tirt_film_create(tirt_ctx *c, int W, int H, int tile_rank, int tile_count, i
         if (sync_all(c)) return TIRT_ERR_HIP;
         c->aov.release(); c->last_aov = nullptr;
     }
+    if (c->dn_mem.p || c->dn_out.p) {            // so does the denoiser's buffer and its scratch; a filter may still be queued on the main stream
+        TIRT_HIP(hipStreamSynchronize(c->stream));
+        c->dn_mem.release(); c->dn_out.release();
+    }
     if (c->hdr.ensure(sizeof(float) * 3 * (size_t)NP) || c->rgb.ensure(sizeof(float) * 3 * (size_t)NP)) return TIRT_ERR_HIP;
     c->W = W; c->H = H; c->tile_rank = tile_rank; c->tile_count = tile_count; c->tile_size = tile_size;
     c->tile_blocked = (H % 8 == 0 && tile_size % (8 * H) == 0 && ((long)W * H) % tile_size == 0) ? 1 : 0;       // local_to_pixel
@@ -884,6 +888,43 @@ int tirt_aov_export_device(tirt_ctx *c, void *dev_dst)
     TIRT_HIP(hipMemcpyAsync(dev_dst, c->aov.p, sizeof(float) * TIRT_AOV_WORDS * (size_t)c->W * c->H, hipMemcpyDeviceToDevice, c->stream));
     TIRT_HIP(hipStreamSynchronize(c->stream));
     return TIRT_OK;
+}
+
+int tirt_denoise(tirt_ctx *c, const tirt_denoise_t *params)
+{
+    CTX(c);
+    AFTER_RENDER(c);
+    AFTER_AOV(c);
+    return denoise_film(c, params);
+}
+
+int tirt_denoise_download(tirt_ctx *c, float *out)
+{
+    CTX(c);
+    TIRT_REQUIRE(c->hdr.p, "tirt_denoise_download: film not created");
+    TIRT_REQUIRE(c->dn_out.p, "tirt_denoise_download: nothing filtered yet (tirt_denoise)");
+    TIRT_REQUIRE(out, "tirt_denoise_download: null pointer");
+    TIRT_HIP(hipMemcpyAsync(out, c->dn_out.p, sizeof(float) * 3 * (size_t)c->W * c->H, hipMemcpyDeviceToHost, c->stream));
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    TIRT_HIP(hipGetLastError());
+    return TIRT_OK;
+}
+
+int tirt_denoise_export_device(tirt_ctx *c, void *dev_dst)
+{
+    CTX(c);
+    TIRT_REQUIRE(c->hdr.p, "tirt_denoise_export_device: film not created");
+    TIRT_REQUIRE(c->dn_out.p, "tirt_denoise_export_device: nothing filtered yet (tirt_denoise)");
+    TIRT_REQUIRE(dev_dst, "tirt_denoise_export_device: null pointer");
+    TIRT_HIP(hipMemcpyAsync(dev_dst, c->dn_out.p, sizeof(float) * 3 * (size_t)c->W * c->H, hipMemcpyDeviceToDevice, c->stream));
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    return TIRT_OK;
+}
+
+int tirt_denoise_device(tirt_ctx *c, const float *hdr, const float *aov, float *out, int W, int H, const tirt_denoise_t *params, void *stream)
+{
+    CTX(c);
+    return denoise_device(c, hdr, aov, out, W, H, params, stream);
 }
 
 static int submit_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed, int max_depth, int stack_size, int flags, bool spectral)

@@ -320,6 +320,7 @@ struct tirt_ctx {
     tirt::DevBuf hdr, rgb;
     tirt::DevBuf aov;                             // tirt_aov_enable: TIRT_AOV_WORDS f32 per pixel of the film (p == nullptr: disabled)
     hipEvent_t last_aov = nullptr;                // aov_done of the most recent batch (any lane): the next k_aov and the records' main-stream consumers wait for it
+    tirt::DevBuf dn_mem, dn_out;                  // denoiser (tirt_denoise.hip): 60 B of scratch per pixel; the filtered film W*H*3 f32 (p == nullptr: no tirt_denoise yet).  Both go with the film
 
     // wavefront state
     tirt::Lane lanes[TIRT_MAX_LANES];
@@ -466,6 +467,12 @@ int query_closest(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride
                   float *out_hit, int64_t hit_stride, int32_t *counts, void *stream);      // tirt_query.hip
 int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, const float *tmax, int64_t tmax_stride, float tmax_all,
                    int stack_size, int flags, uint8_t *out_occluded, void *stream);
+// what the entry points that take caller-owned device memory share (tirt_query.hip): the pointer check, and the two events that order the context's stream after and before the caller's
+int require_device_ptr(tirt_ctx *c, const void *p, const char *what);
+int query_begin(tirt_ctx *c, void *stream);
+int query_end(tirt_ctx *c, void *stream);
+int denoise_film(tirt_ctx *c, const tirt_denoise_t *prm);      // tirt_denoise.hip
+int denoise_device(tirt_ctx *c, const float *hdr, const float *aov, float *out, int W, int H, const tirt_denoise_t *prm, void *stream);
 int trace_host(tirt_ctx *c, const float *rays, int nr, int stack_size, int flags, bool shadow, float *out_f, int32_t *out_prim, int32_t *counts);      // tirt_trace_closest / tirt_trace_shadow
 int pvb_prepare(tirt_ctx *c);                          // tirt_pvb.hip
 void pvb_launch_cand(tirt_ctx *c, hipStream_t st, const BvhView &bv, const float *dx, const float *dy, const float *dz, const TileMap &tm, int P, int S,

@@ -69,7 +69,7 @@ __global__ void k_query_resolve_occluded(const float4 *rec, const float4 *hit, i
 
 // Device memory of this context's device, as the HIP runtime libtirt.so runs on sees it.  A pointer of another runtime (a second
 // libamdhip64 in the process, _native._check_one_hip_runtime) or of the host is refused here, before anything is queued.
-static int require_device_ptr(tirt_ctx *c, const void *p, const char *what)
+int require_device_ptr(tirt_ctx *c, const void *p, const char *what)
 {
     hipPointerAttribute_t at = {};
     const hipError_t e = hipPointerGetAttributes(&at, p);
@@ -115,7 +115,7 @@ static int query_prepare(tirt_ctx *c, int chunk, float4 *&rec, float4 *&hit)
 static int query_chunk_of(const tirt_ctx *c, int64_t nr) { return (int)(nr < (int64_t)c->query_chunk ? nr : (int64_t)c->query_chunk); }
 
 // the two ordering events are made on first use
-static int query_begin(tirt_ctx *c, void *stream)
+int query_begin(tirt_ctx *c, void *stream)
 {
     if (!c->query_ev_in) TIRT_HIP(hipEventCreateWithFlags(&c->query_ev_in, hipEventDisableTiming));
     if (!c->query_ev_out) TIRT_HIP(hipEventCreateWithFlags(&c->query_ev_out, hipEventDisableTiming));
@@ -124,7 +124,7 @@ static int query_begin(tirt_ctx *c, void *stream)
     return TIRT_OK;
 }
 
-static int query_end(tirt_ctx *c, void *stream)
+int query_end(tirt_ctx *c, void *stream)
 {
     TIRT_HIP(hipGetLastError());
     TIRT_HIP(hipEventRecord(c->query_ev_out, c->stream));
