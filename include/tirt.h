@@ -162,6 +162,18 @@ int tirt_lbvh_download(tirt_ctx *ctx, int32_t *morton_sorted, float *bvh_node, f
  * reference's traversal would have visited that leaf (Scene.py:702-744) -- this tree only finds the candidates with fewer
  * node visits.  With traversal_tree = 0 the rows are those of compact_node. */
 int tirt_traversal_tree_download(tirt_ctx *ctx, float *rows);
+/* Diagnostic, read-only: the arrays k_trace<ordered>, the beam kernels and the ray queries actually walk, as tirt_lbvh_build left them.
+ * Any of the four arrays may be NULL (call once with all four NULL to learn the node counts):
+ *   cnode[(wide_nodes + n_far_nodes) * 16]  64-byte 4-wide nodes in breadth-first order, the chain nodes of far-origin rays behind them:
+ *                                           dword 3 * slot + axis = half(min plane) | half(max plane) << 16 in grid cells, dwords 12..15 the
+ *                                           child codes (>= 0: node index; < 0: ~(record index | shape << 30); 0x80000001: empty slot)
+ *   tri[n * 12]        48-byte primitive records in the leaf order of the traversal tree
+ *   wnode[(2n-1) * 16] two-child nodes of the exhaustive traversal, one per compact_node row (rows of leaves are not written)
+ *   prim_slot[n]       index of primitive i's record in tri
+ * grid[19] = grid_min[3] (the centre of the padded root box), cell[3], inv_cell[3], inv_extent[3], root_min[3], root_max[3], and the
+ * padding of leaf boxes.  info[6] = wide_nodes, n_far_nodes, root_code, far_qcode, built_sah (1: the rows of
+ * tirt_traversal_tree_download are the binned-SAH tree's), shapes_boxed (1: sphere slots carry their own padded boxes, 0: the whole grid). */
+int tirt_wide_tree_download(tirt_ctx *ctx, uint32_t *cnode, float *tri, float *wnode, int32_t *prim_slot, float grid[19], int32_t info[6]);
 /* unsorted Morton pairs [n*2] as produced by build_morton_3d (accel/LBvh.py:318-336) */
 int tirt_morton_download(tirt_ctx *ctx, int32_t *morton_unsorted);
 
@@ -349,7 +361,8 @@ int tirt_comm_destroy(tirt_ctx **ctxs, int ndev);
 
 /* Measurement helpers for bench.py's roofline object (no counterpart in the reference).
  * tirt_bvh_info: bytes of the traversal data the ordered traversal walks (out[0] = quantised 4-wide nodes,
- *   out[1] = primitive records, out[2] = node count, out[3] = of those kept in LDS by every block).
+ *   out[1] = primitive records, out[2] = node count, out[3] = of those kept in LDS by every block; the chain nodes of far-origin
+ *   rays, tirt_wide_tree_download, are counted: they are walked and kept in LDS like the others).
  * tirt_micro_gather_rate: the ceiling of the access pattern k_trace is bound by, measured on this device now --
  *   every lane of 1536 x 256 threads gathers `iters` random 64-byte records (4 x 16-byte loads) from an array of
  *   `working_set_bytes`; returns the rate in GB/s (best of 3 launches). */

@@ -39,6 +39,54 @@ def duplicate_code_scene(W=32, H=32, device_id=None):
     return ex
 
 
+def long_chain_scene(W=32, H=32, device_id=0):
+    """600 triangles with one Morton code (a 600-deep chain in the reference tree, ~200 levels of the 4-wide tree collapsed from it), 30
+    more around them and a sphere light; not built yet."""
+    ex = Example.example(W, H, 4, device_id)
+    mat = SCD.Material(); mat.type = SCD.MAT_DISNEY; mat.setRough(0.5); mat.setColor([0.8, 0.8, 0.8, 1.0]); mat.alebdoTex = -1
+    r = np.random.RandomState(3)
+    tris = []
+    for k in range(600):
+        a = r.uniform(0.2, 1.0); th = r.uniform(0, 2 * np.pi)
+        p = np.array([[np.cos(th + 2 * np.pi * j / 3) * a, np.sin(th + 2 * np.pi * j / 3) * a, r.uniform(-0.3, 0.3)] for j in range(3)])
+        p -= p.mean(axis=0, keepdims=True)
+        tris.append(p)
+    for k in range(30):
+        c = r.uniform(-1.5, 1.5, size=3); tris.append(c[None, :] + r.uniform(-0.2, 0.2, size=(3, 3)))
+    ex.scene.add_mesh(np.asarray(tris), mat)
+    ex.add_sphere_light(pos=(0.0, 3.0, 0.0), radius=0.5, emission=30.0)
+    ex.integrator = PT_RGB.PathTrace(W, H, ex.cam, ex.scene, 2048)
+    return ex
+
+
+def custom_scene(tris, W=24, H=24, device_id=0, spheres=((0.0, 3.0, 0.0, 0.75),)):
+    """a grey mesh of the given triangles [k, 3, 3] and sphere lights (x, y, z, radius); not built yet"""
+    ex = Example.example(W, H, 4, device_id)
+    mat = SCD.Material()
+    mat.type = SCD.MAT_DISNEY
+    mat.setMetal(0.0); mat.setRough(0.5); mat.setColor([0.8, 0.8, 0.8, 1.0]); mat.alebdoTex = -1
+    ex.scene.add_mesh(np.asarray(tris, np.float64), mat)
+    for x, y, z, radius in spheres:
+        ex.add_sphere_light(pos=(x, y, z), radius=radius, emission=50.0)
+    ex.integrator = PT_RGB.PathTrace(W, H, ex.cam, ex.scene, 64)
+    return ex
+
+
+def hostile_triangles(kind, r):
+    """Inputs a binned SAH build handles badly, drawn from the RandomState r: centroids spaced exponentially, 3000 identical triangles,
+    two far-apart clusters of very different size."""
+    if kind == "exponential":
+        n = 300
+        c = np.zeros((n, 3)); c[:, 0] = 1.05 ** np.arange(n) * 1e-3; c[:, 1] = r.uniform(-1, 1, n) * c[:, 0]
+        return c[:, None, :] + r.uniform(-0.2, 0.2, (n, 3, 3)) * c[:, 0][:, None, None]
+    if kind == "identical":
+        one = r.uniform(-1, 1, (3, 3))
+        return np.repeat(one[None], 3000, axis=0)
+    a = r.uniform(-1, 1, (5000, 1, 3)) * 0.01 + r.uniform(-0.001, 0.001, (5000, 3, 3))
+    b = r.uniform(-1, 1, (40, 1, 3)) * 50.0 + 1000.0 + r.uniform(-5, 5, (40, 3, 3))
+    return np.concatenate([a, b], axis=0)
+
+
 def spot_laser_scene(W, H, kinds=("spot", "laser"), device_id=None, integrator="pt", with_quad_light=True):
     """Cornell box plus the two shape emitters that have no surface (SceneData.SHPAE_SPOT / SHPAE_LASER; the reference uses them in
     example/prism_rainbow.py:39-50 and samples them in Scene.sample_li / sample_light, Scene.py:449-472, 491-516): a spot light under

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import oracle_api as oa
-from common import same_bits as same
+from common import long_chain_scene, same_bits as same
 from ti_raytrace_amd import RayQuery, scenes, _native
 
 pytestmark = pytest.mark.gpu
@@ -342,23 +342,8 @@ def test_stack_overflow_is_reported(gpu_ctx_ok):
     "traversal_tree" 0, where the reference's 64-entry stack overflows), traced with a 64-entry stack: the ordered walk keeps the far
     children of the chain on its stack and overflows on some camera rays (the exhaustive walk, popping the chain side first, does not).
     The host route and the query drop the same rays, and stats() reports it (a counted condition, not a fault)."""
-    from ti_raytrace_amd import Example, PT_RGB
-    from ti_raytrace_amd import SceneData as SCD
     W = H = 32
-    ex = Example.example(W, H, 4, 0)
-    mat = SCD.Material(); mat.type = SCD.MAT_DISNEY; mat.setRough(0.5); mat.setColor([0.8, 0.8, 0.8, 1.0]); mat.alebdoTex = -1
-    r = np.random.RandomState(3)
-    tris = []
-    for k in range(600):
-        a = r.uniform(0.2, 1.0); th = r.uniform(0, 2 * np.pi)
-        p = np.array([[np.cos(th + 2 * np.pi * j / 3) * a, np.sin(th + 2 * np.pi * j / 3) * a, r.uniform(-0.3, 0.3)] for j in range(3)])
-        p -= p.mean(axis=0, keepdims=True)
-        tris.append(p)
-    for k in range(30):
-        c = r.uniform(-1.5, 1.5, size=3); tris.append(c[None, :] + r.uniform(-0.2, 0.2, size=(3, 3)))
-    ex.scene.add_mesh(np.asarray(tris), mat)
-    ex.add_sphere_light(pos=(0.0, 3.0, 0.0), radius=0.5, emission=30.0)
-    ex.integrator = PT_RGB.PathTrace(W, H, ex.cam, ex.scene, 2048)
+    ex = long_chain_scene(W, H)
     ex.scene.ctx.set_option("traversal_tree", 0)
     ex.build_scene(); ex.frame_camera(0.8)
     rs = np.random.RandomState(9)

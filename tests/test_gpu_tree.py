@@ -7,7 +7,7 @@ import pytest
 
 import oracle_api as oa
 from ti_raytrace_amd import scenes, _native
-from common import duplicate_code_scene, tiny_scene
+from common import custom_scene, duplicate_code_scene, hostile_triangles, tiny_scene
 from test_gpu_trace import random_rays
 
 pytestmark = pytest.mark.gpu
@@ -137,37 +137,14 @@ def test_cost_optimal_collapse_changes_no_bit(gpu_ctx_ok, experiments_lib):
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
-def _custom_scene(tris, W=24, H=24):
-    from ti_raytrace_amd import Example, PT_RGB
-    from ti_raytrace_amd import SceneData as SCD
-    ex = Example.example(W, H, 4, 0)
-    mat = SCD.Material()
-    mat.type = SCD.MAT_DISNEY
-    mat.setMetal(0.0); mat.setRough(0.5); mat.setColor([0.8, 0.8, 0.8, 1.0]); mat.alebdoTex = -1
-    ex.scene.add_mesh(np.asarray(tris, np.float64), mat)
-    ex.add_sphere_light(pos=(0.0, 3.0, 0.0), radius=0.75, emission=50.0)
-    ex.integrator = PT_RGB.PathTrace(W, H, ex.cam, ex.scene, 64)
-    return ex
-
-
 @pytest.mark.parametrize("kind", ["exponential", "identical", "two_clusters"])
 def test_traversal_tree_on_hostile_distributions(gpu_ctx_ok, kind):
     """Inputs a binned SAH build handles badly: centroids spaced exponentially (every split peels off a few primitives: the tree
     is as deep as the 64 levels after which ranges are halved), 3000 identical triangles (no plane separates anything: halving
     from the root), two far-apart clusters of very different size.  The tree must still be a tree and the hits the oracle's."""
     r = np.random.RandomState(7)
-    if kind == "exponential":
-        n = 300
-        c = np.zeros((n, 3)); c[:, 0] = 1.05 ** np.arange(n) * 1e-3; c[:, 1] = r.uniform(-1, 1, n) * c[:, 0]
-        tris = c[:, None, :] + r.uniform(-0.2, 0.2, (n, 3, 3)) * c[:, 0][:, None, None]
-    elif kind == "identical":
-        one = r.uniform(-1, 1, (3, 3))
-        tris = np.repeat(one[None], 3000, axis=0)
-    else:
-        a = r.uniform(-1, 1, (5000, 1, 3)) * 0.01 + r.uniform(-0.001, 0.001, (5000, 3, 3))
-        b = r.uniform(-1, 1, (40, 1, 3)) * 50.0 + 1000.0 + r.uniform(-5, 5, (40, 3, 3))
-        tris = np.concatenate([a, b], axis=0)
-    ex = _custom_scene(tris); ex.build_scene()
+    tris = hostile_triangles(kind, r)
+    ex = custom_scene(tris); ex.build_scene()
     sc = ex.scene
     check_tree(sc.ctx.traversal_tree_download(sc.primitive_count), prim_boxes(sc), np.flatnonzero(sc.primitive_np[:, 0] != 1))
     o = oa.OracleScene(sc, ex.cam); o.lbvh_build()

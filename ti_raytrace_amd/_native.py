@@ -94,6 +94,7 @@ SIGNATURES = {
     "tirt_lbvh_build": (C.c_int, [_vp]),
     "tirt_lbvh_download": (C.c_int, [_vp, _vp, _vp, _vp]),
     "tirt_traversal_tree_download": (C.c_int, [_vp, _vp]),
+    "tirt_wide_tree_download": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tirt_morton_download": (C.c_int, [_vp, _i32p]),
     "tirt_process_normal": (C.c_int, [_vp, _i32p]),
     "tirt_vertex_download": (C.c_int, [_vp, _f32p]),
@@ -317,6 +318,24 @@ class Context:
         rows = np.zeros((2 * n - 1, 9), np.float32)
         check(lib().tirt_traversal_tree_download(self.handle, _ptr(rows)))
         return rows
+
+    def wide_tree_download(self, n):
+        """What the ordered and the exhaustive traversal walk, as lbvh_build left it (tirt.h, tirt_wide_tree_download): a dict with cnode
+        uint32 [wide_nodes + n_far_nodes, 16], tri float32 [n, 12], wnode float32 [2n-1, 16] (rows of leaves are not written), prim_slot
+        int32 [n], the grid (grid_min, grid_cell, grid_inv_cell, grid_inv_extent, root_min, root_max: float32 [3]), pad (np.float32)
+        and the integers wide_nodes, n_far_nodes, root_code, far_qcode, built_sah, shapes_boxed."""
+        grid = np.zeros(19, np.float32); info = np.zeros(6, np.int32)
+        check(lib().tirt_wide_tree_download(self.handle, None, None, None, None, _ptr(grid), _ptr(info)))
+        out = {"cnode": np.zeros((int(info[0]) + int(info[1]), 16), np.uint32), "tri": np.zeros((n, 12), np.float32),
+               "wnode": np.zeros((2 * n - 1, 16), np.float32), "prim_slot": np.zeros(n, np.int32)}
+        check(lib().tirt_wide_tree_download(self.handle, _ptr(out["cnode"]), _ptr(out["tri"]), _ptr(out["wnode"]), _ptr(out["prim_slot"]),
+                                            _ptr(grid), _ptr(info)))
+        for k, name in enumerate(("grid_min", "grid_cell", "grid_inv_cell", "grid_inv_extent", "root_min", "root_max")):
+            out[name] = grid[3 * k:3 * k + 3].copy()
+        out["pad"] = np.float32(grid[18])
+        for k, name in enumerate(("wide_nodes", "n_far_nodes", "root_code", "far_qcode", "built_sah", "shapes_boxed")):
+            out[name] = int(info[k])
+        return out
 
     def morton_download(self, n):
         out = np.zeros((n, 2), np.int32)

@@ -611,10 +611,13 @@ int tirt_scene_upload(tirt_ctx *c, const float *vertex, int nv, const int32_t *p
         TIRT_REQUIRE(pr[2] >= 0 && pr[2] < nm, "tirt_scene_upload: material index out of range");
     }
     for (int i = 0; i < nl; i++) TIRT_REQUIRE(light[i] >= 0 && light[i] < n, "tirt_scene_upload: light index out of range");
-    c->sphere_prims.clear();
+    c->sphere_prims.clear(); c->sphere_geom.clear();
     for (int i = 0; i < n; i++) {
         const int32_t *pr = primitive + (size_t)i * 3;
-        if (pr[0] != PRIMITIVE_TRI && (int)shape[(size_t)pr[1] * 10] == SHAPE_SPHERE) c->sphere_prims.push_back(i);
+        if (pr[0] != PRIMITIVE_TRI && (int)shape[(size_t)pr[1] * 10] == SHAPE_SPHERE) {
+            c->sphere_prims.push_back(i);
+            for (int k = 1; k <= 4; k++) c->sphere_geom.push_back(shape[(size_t)pr[1] * 10 + k]);
+        }
     }
     hipStream_t st = c->stream;
     c->built = false;
@@ -737,6 +740,26 @@ int tirt_traversal_tree_download(tirt_ctx *c, float *rows)
     const bool sah = c->built_sah != 0;
     TIRT_HIP(hipMemcpyAsync(rows, sah ? c->sah_compact.p : c->compact.p, sizeof(float) * N * CPN_VEC, hipMemcpyDeviceToHost, c->stream));
     TIRT_HIP(hipStreamSynchronize(c->stream));
+    return TIRT_OK;
+}
+
+int tirt_wide_tree_download(tirt_ctx *c, uint32_t *cnode, float *tri, float *wnode, int32_t *prim_slot, float grid[19], int32_t info[6])
+{
+    CTX(c);
+    TIRT_REQUIRE(c->built && grid && info, "tirt_wide_tree_download: LBVH not built / null pointer");
+    const size_t n = c->n, N = 2 * n - 1, nodes = (size_t)c->wide_nodes + (size_t)c->n_far_nodes;
+    if (cnode && nodes) TIRT_HIP(hipMemcpyAsync(cnode, c->cnode.p, 64 * nodes, hipMemcpyDeviceToHost, c->stream));
+    if (tri) TIRT_HIP(hipMemcpyAsync(tri, c->tri.p, sizeof(float4) * TRI_STRIDE * n, hipMemcpyDeviceToHost, c->stream));
+    if (wnode) TIRT_HIP(hipMemcpyAsync(wnode, c->wnode.p, sizeof(float4) * 4 * N, hipMemcpyDeviceToHost, c->stream));
+    if (prim_slot) TIRT_HIP(hipMemcpyAsync(prim_slot, c->prim_slot.p, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    const BvhView b = bvh_view(c);
+    for (int k = 0; k < 3; k++) {
+        grid[k] = b.grid_min[k]; grid[3 + k] = b.cell[k]; grid[6 + k] = b.inv_cell[k]; grid[9 + k] = b.inv_extent[k];
+        grid[12 + k] = b.root_min[k]; grid[15 + k] = b.root_max[k];
+    }
+    grid[18] = c->wide_pad;
+    info[0] = c->wide_nodes; info[1] = c->n_far_nodes; info[2] = b.root_code; info[3] = b.far_qcode; info[4] = c->built_sah; info[5] = c->shapes_boxed;
     return TIRT_OK;
 }
 
@@ -1053,7 +1076,7 @@ int tirt_bvh_info(tirt_ctx *c, uint64_t out[4])
 {
     CTX(c);
     TIRT_REQUIRE(out && c->built, "tirt_bvh_info: LBVH not built");
-    const int nq = c->wide_nodes;
+    const int nq = c->wide_nodes + c->n_far_nodes;      // the chain nodes of far-origin rays are walked, and kept in LDS, like any other (bvh_view: top_count)
     out[0] = (uint64_t)nq * 64u; out[1] = (uint64_t)c->n * sizeof(float4) * TRI_STRIDE; out[2] = (uint64_t)nq;
     const int top = TR_TOP_SLOTS;
     out[3] = (uint64_t)(nq < top ? nq : top);

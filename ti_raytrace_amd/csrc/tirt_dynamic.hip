@@ -27,7 +27,7 @@ __global__ __launch_bounds__(DYN_BLOCK) void k_dyn_validate(const float *pos, in
     if (i >= count) return;
     const float *p = pos + i * stride;
     const float x = p[0], y = p[1], z = p[2];
-    const bool finite = (absf(x) <= 3.402823466e+38f) & (absf(y) <= 3.402823466e+38f) & (absf(z) <= 3.402823466e+38f);      // false for NaN and +-inf
+    const bool finite = ((int)(absf(x) <= 3.402823466e+38f) & (int)(absf(y) <= 3.402823466e+38f) & (int)(absf(z) <= 3.402823466e+38f)) != 0;      // false for NaN and +-inf
     if (!finite) flag[0] = 1;
 }
 

@@ -304,12 +304,14 @@ struct tirt_ctx {
     tirt::DevBuf sah_compact, sah_csize, sah_parent, wide_dp, sah_box, sah_idx, sah_tasks, sah_counts;   // traversal tree (tirt_sah.hip): `compact`-layout rows + subtree sizes, build scratch
     int use_sah = 1, sah_levels = 0, built_sah = 0;
     std::vector<int> sphere_prims;                  // primitive ids of the analytic spheres (tirt_scene_upload)
+    std::vector<float> sphere_geom;                 // their (centre.xyz, radius), four floats each
     tirt::DevBuf timeline; int timeline_arm = -1, timeline_waves = 0;      // diagnostics: option "trace_timeline", tirt_trace_timeline
     int n_far_nodes = 0;                      // chain nodes behind the wide tree (cnode[wide_nodes ...]): the entry of far-origin rays when the spheres' slots carry padded boxes (lbvh_build)
     int wide_dp_on = 0;                            // option "wide_collapse": 0 = greedy by surface area (default), 1 = cost-optimal grouping of the binary tree into 4-wide nodes (dynamic programme; 1-9 % fewer visits, same rays/s)               // option "traversal_tree": 1 = binned-SAH tree (default), 0 = the reference's LBVH
     float grid_min[3] = {0, 0, 0}, grid_cell[3] = {1, 1, 1}, grid_inv_cell[3] = {1, 1, 1}, grid_inv_extent[3] = {1, 1, 1};
     size_t lds_optin = 65536;                      // hipDeviceAttributeMaxSharedMemoryPerBlock (opt-in) of this device
     float root_min[3], root_max[3]; int root_code = 0;
+    float wide_pad = 0.0f; int shapes_boxed = 0;   // what lbvh_build padded the leaf slots of cnode / wnode by; whether the spheres' slots carry their own padded boxes (tirt_wide_tree_download)
 
     // camera
     tirt::CameraView cam; float view[16]; bool cam_set = false;

@@ -438,18 +438,20 @@ __global__ void k_tris(SceneView s, const int *leaf_compact, const int *prim_slo
 // condition has been re-established (k_trace).  Nodes are numbered in breadth-first order (a level's nodes take the next
 // free indices), so the first TR_TOP_SLOTS records ARE the top of the tree that k_trace keeps in LDS.
 // Planes: fp16 cells around the centre of the root box, min planes rounded down and max planes up, one more cell outward
-// against the rounding of the mapping itself; leaf slots are padded by `pad` before the mapping (the reference never
+// against the rounding of the mapping itself; leaf slots are padded by `pad` in the mapping (grid_lo / grid_hi; the reference never
 // box-tests a leaf: the padding keeps "box missed but Moller-Trumbore hit" impossible).
 // Analytic shapes (the sphere light) keep the whole grid as their slot box: the reference's sphere test (Scene.py:565-596:
 // a square root of a difference of squares of the distance to the centre) answers "hit" for rays that pass the sphere at
 // a distance that grows with the distance of the origin -- no fixed padding of the sphere's box covers that.
 // ---------------------------------------------------------------------------------------------
 struct GridMap { float g0[3], inv_cell[3]; };
-// fp16 bit pattern of the largest half <= x - 1 / the smallest half >= x + 1 (x in grid cells, |x| <= TR_GRID_HALF + a few)
-TD unsigned grid_lo(float x, float g0, float inv_cell)
-{ const float v = (x - g0) * inv_cell - 1.0f; return (unsigned)__half_as_ushort(__float2half_rd(v < -60000.0f ? -60000.0f : (v > 60000.0f ? 60000.0f : v))); }
-TD unsigned grid_hi(float x, float g0, float inv_cell)
-{ const float v = (x - g0) * inv_cell + 1.0f; return (unsigned)__half_as_ushort(__float2half_ru(v < -60000.0f ? -60000.0f : (v > 60000.0f ? 60000.0f : v))); }
+// fp16 bit pattern of the largest half <= x - 1 / the smallest half >= x + 1 (x in grid cells, |x| <= TR_GRID_HALF + a few).  The padding p of a leaf slot is
+// taken off AFTER the subtraction of the grid centre: `x - p` itself is x again wherever p is below the spacing of float32 at x (a small scene far from the
+// origin: tests/test_gpu_wide_tree.py, the offset scene, lost all of its padding of ten cells that way)
+TD unsigned grid_lo(float x, float p, float g0, float inv_cell)
+{ const float v = ((x - g0) - p) * inv_cell - 1.0f; return (unsigned)__half_as_ushort(__float2half_rd(v < -60000.0f ? -60000.0f : (v > 60000.0f ? 60000.0f : v))); }
+TD unsigned grid_hi(float x, float p, float g0, float inv_cell)
+{ const float v = ((x - g0) + p) * inv_cell + 1.0f; return (unsigned)__half_as_ushort(__float2half_ru(v < -60000.0f ? -60000.0f : (v > 60000.0f ? 60000.0f : v))); }
 TD bool cn_leaf(const float *compact, int i) { return (((int)compact[(size_t)i * CPN_VEC]) & 1) == 1; }
 TD float cn_area(const float *compact, int i)
 {
@@ -574,7 +576,7 @@ __global__ void k_wide_level(SceneView s, const int *prim_slot, const float *com
             const float p = leaf ? pad : 0.0f;
             for (int a = 0; a < 3; a++)
                 wd[3 * c + a] = shape ? (TR_H_NEG | (TR_H_POS << 16))
-                                      : (grid_lo(cn[2 + a] - p, gm.g0[a], gm.inv_cell[a]) | (grid_hi(cn[5 + a] + p, gm.g0[a], gm.inv_cell[a]) << 16));
+                                      : (grid_lo(cn[2 + a], p, gm.g0[a], gm.inv_cell[a]) | (grid_hi(cn[5 + a], p, gm.g0[a], gm.inv_cell[a]) << 16));
         } else {
             for (int a = 0; a < 3; a++) wd[3 * c + a] = TR_H_POS | (TR_H_NEG << 16);       // inverted box: never hit
         }
@@ -723,8 +725,19 @@ int lbvh_build(tirt_ctx *c)
     const float *tree = c->compact.as<float>(); const int *tree_size = c->csize.as<int>(), *tree_parent = c->cparent.as<int>();
     // analytic spheres get their own padded box in the traversal tree when there are few of them (far-origin rays enter through chain nodes that
     // hold them with whole-grid boxes: BvhView::far_qcode); otherwise, and on the reference's LBVH, their 4-wide slots span the whole grid as before
-    const int shapes_boxed = (n >= 2 && c->use_sah && c->sphere_prims.size() <= 8) ? 1 : 0;
+    int shapes_boxed = (n >= 2 && c->use_sah && c->sphere_prims.size() <= 8) ? 1 : 0;
+    // ... and when every padded box can be written down: the fp16 planes end at +-60000 cells (grid_lo / grid_hi clamp there), so a sphere whose padding reaches
+    // further (a small sphere in a large scene: the padding grows with diagonal^2 / r) would get a box that is cut short -- such a scene keeps the whole-grid slots
+    for (size_t k = 0; shapes_boxed && k < c->sphere_prims.size(); k++) {
+        const float *g = &c->sphere_geom[4 * k];
+        const float rr = g[3] + (1.0e-3f * g[3] + sphere_pad_abs(diag) / (g[3] > 1.0e-20f ? g[3] : 1.0e-20f)) + pad;      // (sphere_pad, tirt_internal.h)
+        for (int a = 0; a < 3; a++) {
+            const float lo = (g[a] - rr - gm.g0[a]) * gm.inv_cell[a] - 1.0f, hi = (g[a] + rr - gm.g0[a]) * gm.inv_cell[a] + 1.0f;
+            if (!(lo > -59000.0f && hi < 59000.0f)) shapes_boxed = 0;
+        }
+    }
     c->n_far_nodes = 0;
+    c->wide_pad = pad; c->shapes_boxed = shapes_boxed;
     if (n >= 2 && c->use_sah) {          // walk a better tree than the reference's (tirt_sah.hip); the hits stay the reference's (k_trace)
         if (int rc = sah_build(c, va, shapes_boxed ? sphere_pad_abs(diag) : -1.0f)) return rc;                                  // also fills prim_slot
         tree = c->sah_compact.as<float>(); tree_size = c->sah_csize.as<int>(); tree_parent = c->sah_parent.as<int>();

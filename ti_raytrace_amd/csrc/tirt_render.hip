@@ -1240,7 +1240,7 @@ static const T &pick_shade_inst(const T (&tab)[N], const tirt_ctx *c)
 // hit records and path states, on the context's own tables.  (pixel, frame) reach it the way they reach k_shade, through a TileMap: one tile that holds every
 // pixel (local pixel = pixel), frame-major paths with P = INT_MAX (slot = pixel gives frame 0 of the batch) and frame_begin = the row's frame.  Rows: the 23
 // words in / 28 words out of include/tirt.h; integers travel as their bit patterns. ----
-constexpr int KAT_STEP_IN = 23, KAT_STEP_OUT = 28;
+[[maybe_unused]] constexpr int KAT_STEP_IN = 23, KAT_STEP_OUT = 28;
 template <unsigned FEAT, int MIN_WAVES>
 __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_kat_shade_step(SceneView sc, const float *in, int in_stride, float *out, int out_stride, int n)
 {
