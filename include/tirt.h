@@ -315,6 +315,62 @@ int tirt_denoise_download(tirt_ctx *ctx, float *out);
 int tirt_denoise_export_device(tirt_ctx *ctx, void *dev_dst);
 int tirt_denoise_device(tirt_ctx *ctx, const float *hdr, const float *aov, float *out, int W, int H, const tirt_denoise_t *params, void *stream);
 
+/* Sample moments of the path tracer (csrc/tirt_moments.hip; no reference counterpart).  While enabled, every frame of tirt_pt_rgb_render also folds, per pixel of
+ * this context's tiles, that frame's pixel-sample x = the final radiance (r, g, b) that the film's running mean takes in, into TIRT_MOM_WORDS f32:
+ *   TIRT_MOM_N     1 word : n, the samples folded so far
+ *   TIRT_MOM_MEAN  3 words: their mean
+ *   TIRT_MOM_M2    3 words: their sum of squared deviations from the mean (sample variance = M2 / (n - 1), variance of the mean = M2 / (n * (n - 1)))
+ *   TIRT_MOM_BAD   1 word : samples skipped because a channel was NaN or +-infinite
+ * by Welford's update, frames in ascending order, all f32 with one rounding per operation in this order (tests/moments_expected.py restates it; the device
+ * gives its bits):  a sample with a channel that is not finite: bad = bad + 1, nothing else;  otherwise n = n + 1 and per channel
+ *   delta = x - mean;  mean = mean + delta / n;  M2 = M2 + delta * (x - mean)      (the new mean; the division is tirt_kat_math fn 8's; no FMA)
+ * n is the record's own count, not a frame index: frames may start anywhere, come in any order or repeat with other seeds, and the record is the moments
+ * of whatever was rendered since the last clear.  As an f32 it is exact up to 2^24 samples per pixel.  The result does not depend on how the same frames
+ * are cut into calls, merges ("merge_paths"), batches, lanes and tiles, nor on the route of the camera rays.
+ * hdr is not touched; pixels of other ranks' tiles are never written (zero: the ranks' records sum to the whole).  tirt_pt_spec_render, tirt_bdpt_rgb_render,
+ * tirt_bdpt_spec_render and tirt_debug_render leave the records alone: their per-frame samples are not RGB radiance per pixel-sample (PT_RGB only).
+ * tirt_moments_enable: needs a film.  on != 0 allocates and zeroes the records, on == 0 frees them; tirt_film_create disables, tirt_film_clear zeroes.  Waits
+ *   for pending work.
+ * tirt_moments_download: out[W*H*TIRT_MOM_WORDS], pixel p = i*H + j as hdr.  tirt_moments_export_device: the same into device memory, as
+ *   tirt_film_export_device.  TIRT_ERR_ARG when not enabled, without a film, or for a null pointer.
+ * tirt_moments_converged: over this context's own pixels, out[0] = the measured ones (n >= 2), out[1] = the measured ones that are still noisy:
+ *     v > t2 * (Y * Y)  with  nn = n * (n - 1),  v = (M2.r / nn + M2.g / nn) + M2.b / nn,  Y = ((mean.r + mean.g) + mean.b) / 3,  t2 = threshold * threshold (host)
+ *   -- the standard error exceeds `threshold` x the mean level; a measured black pixel without variance is converged --, out[2] = pixels with bad > 0.
+ *   One pass on the device; waits for pending work and for the answer.  TIRT_ERR_ARG as the downloads, and for a threshold that is NaN or <= 0. */
+#define TIRT_MOM_WORDS 8
+#define TIRT_MOM_N 0
+#define TIRT_MOM_MEAN 1
+#define TIRT_MOM_M2 4
+#define TIRT_MOM_BAD 7
+int tirt_moments_enable(tirt_ctx *ctx, int on);
+int tirt_moments_download(tirt_ctx *ctx, float *out);
+int tirt_moments_export_device(tirt_ctx *ctx, void *dev_dst);
+int tirt_moments_converged(tirt_ctx *ctx, float threshold, uint64_t out[3]);
+
+/* Variance-guided mode of the denoiser (csrc/tirt_denoise.hip): the a-trous of SVGF (Schied et al. 2017) without its temporal part.  The colour edge-stopping
+ * term of tirt_denoise is scaled by the pixel's own variance of the mean, from the sample moments, instead of one film-wide sigma_c, and that variance is
+ * filtered along.  tirt_denoise and its structure are unchanged.  All f32, one rounding per operation in the order written (tests/denoise_var_expected.py):
+ *   prepare, per pixel: d, e = hdr / d and z as tirt_denoise; from the moment record  s = -1  unless n >= 2 and, with nn = n * (n - 1), v = M2 / nn per channel,
+ *     t = (v.r / (d.r*d.r) + v.g / (d.g*d.g)) + v.b / (d.b*d.b)  satisfies 0 <= t < inf: then s = t (the variance of the mean of e, summed over channels).
+ *     A value s is KNOWN when 0 <= s < inf; -1, NaN and inf are not.  A pixel whose s is not known has its colour term switched off (it is filtered by the
+ *     guides alone), keeps that s through every step, and is skipped wherever variances are summed: no weight is NaN because of it.
+ *   prefilter, once: a pixel with a known s gets  s = sum(k * s_q) / sum(k)  over the taps q = (i + di, j + dj), di = -1..1 outer, dj = -1..1 inner, that are
+ *     inside the film and have a known s_q;  k = g[|di|] * g[|dj|], g = {0.5, 0.25} (so 1/4, 1/8, 1/16); sums in tap order
+ *   level l = 0 .. levels-1, step = 1 << l, on the host sc2 = sigma_c * sigma_c (the same at every level), in and iz as tirt_denoise; per pixel
+ *     rz = 1 / fmaxf(z*z, 1e-12),  cden = sc2 * s_p + 1e-12;  taps, k, dc, dn, dz as tirt_denoise;
+ *       xc = dc / cden if s_p is known, else 0;  x = (xc + dn*in) + dz*iz;  w = k * exp(-x);
+ *       a tap counts only if w and all of e_q are finite: sum_c += e_q * w, sum_w += w, and if s_q is known also  sum_v += (w * w) * s_q, sum_wv += w
+ *     e'_p as tirt_denoise (a pixel whose own e is not finite keeps it);  s'_p = sum_v / (sum_wv * sum_wv) if s_p is known and sum_wv > 0, else s_p
+ *   remodulate: out = e * d
+ * tirt_denoise_var_t: levels 1..8, sigmas finite and > 0, else TIRT_ERR_ARG; NULL means {5, TIRT_DENOISE_VAR_SIGMA_C, 0.3, 0.1}.
+ * tirt_denoise_var: the context's hdr, feature records and moment records into the buffer tirt_denoise_download / tirt_denoise_export_device read.  Refusals:
+ *   tirt_denoise's, and TIRT_ERR_ARG when the moment buffers are not enabled.
+ * tirt_denoise_var_device: on caller-owned device arrays, mom [W,H,TIRT_MOM_WORDS] 16-byte aligned as aov; otherwise as tirt_denoise_device. */
+#define TIRT_DENOISE_VAR_SIGMA_C 3.0f
+typedef struct { int levels; float sigma_c, sigma_n, sigma_z; } tirt_denoise_var_t;
+int tirt_denoise_var(tirt_ctx *ctx, const tirt_denoise_var_t *params);
+int tirt_denoise_var_device(tirt_ctx *ctx, const float *hdr, const float *aov, const float *mom, float *out, int W, int H, const tirt_denoise_var_t *params, void *stream);
+
 /* Scene.closet_hit / closet_hit_shadow on a batch of rays (Scene.py:702-744, 671-699).  The default (ordered) traversal returns the
  * reference's hit bit for bit for every ray but the in-plane rays named under "traversal_tree" above; rays that start more than 8
  * scene extents away are traced without distance culling (from there the reference's own distances are rounding noise), so they

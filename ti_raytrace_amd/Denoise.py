@@ -8,6 +8,11 @@ csrc/tirt_denoise.hip).
 that device -- ``scene.ctx`` when there is a scene; without one a context per device is made on first use and kept: the filter needs no
 scene and no film.  The work is queued on ``torch.cuda.current_stream(device)``: nothing waits for it on the host.  The same filter, bit
 for bit, as ``PathTrace.denoise()``.
+
+    out = denoise_var(hdr, aov, moments, levels=5, sigma_c=3.0, sigma_n=0.3, sigma_z=0.1, ctx=None)
+
+is the variance-guided mode (``tirt_denoise_var_device``, the filter of ``PathTrace.denoise_var()``): ``moments`` is a ``[W, H, 8]`` tensor of
+sample moments (n, mean3, M2 3, bad: ``PathTrace.moments_to_torch()``, or the ranks' records merged).
 """
 from . import _native
 
@@ -23,30 +28,50 @@ def _torch():
     return torch
 
 
-def denoise(hdr, aov, levels=5, sigma_c=1.0, sigma_n=0.3, sigma_z=0.1, ctx=None):
+def _check(fn, tensors):
+    """the tensors' types, shapes and device; returns (torch, device, W, H)"""
     torch = _torch()
-    for name, t, words in (("hdr", hdr, 3), ("aov", aov, _native.AOV_WORDS)):
+    for name, t, words in tensors:
         if not isinstance(t, torch.Tensor):
-            raise TypeError("denoise: %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+            raise TypeError("%s: %s must be a torch.Tensor, got %s" % (fn, name, type(t).__name__))
         if t.dtype != torch.float32:
-            raise TypeError("denoise: %s must be float32, got %s" % (name, t.dtype))
+            raise TypeError("%s: %s must be float32, got %s" % (fn, name, t.dtype))
         if t.device.type != "cuda":
-            raise TypeError("denoise: %s must be on the GPU, got a %s tensor" % (name, t.device.type))
+            raise TypeError("%s: %s must be on the GPU, got a %s tensor" % (fn, name, t.device.type))
         if t.dim() != 3 or t.shape[2] != words or t.shape[0] < 1 or t.shape[1] < 1:
-            raise ValueError("denoise: %s must be [W, H, %d], got shape %s" % (name, words, tuple(t.shape)))
+            raise ValueError("%s: %s must be [W, H, %d], got shape %s" % (fn, name, words, tuple(t.shape)))
         if not t.is_contiguous():
-            raise ValueError("denoise: %s must be contiguous" % name)
-    if aov.device != hdr.device or aov.shape[:2] != hdr.shape[:2]:
-        raise ValueError("denoise: hdr is %s on %s, aov %s on %s" % (tuple(hdr.shape), hdr.device, tuple(aov.shape), aov.device))
-    dev = hdr.device
+            raise ValueError("%s: %s must be contiguous" % (fn, name))
+    hdr = tensors[0][1]
+    for name, t, _ in tensors[1:]:
+        if t.device != hdr.device or t.shape[:2] != hdr.shape[:2]:
+            raise ValueError("%s: hdr is %s on %s, %s %s on %s" % (fn, tuple(hdr.shape), hdr.device, name, tuple(t.shape), t.device))
+    return torch, hdr.device, int(hdr.shape[0]), int(hdr.shape[1])
+
+
+def _context(fn, ctx, dev):
     if ctx is None:
         ctx = _CONTEXTS.get(dev.index)
         if ctx is None:
             ctx = _CONTEXTS[dev.index] = _native.Context(dev.index)
     elif ctx.device_id != dev.index:
-        raise ValueError("denoise: the tensors are on %s, the context on device %d" % (dev, ctx.device_id))
-    W, H = int(hdr.shape[0]), int(hdr.shape[1])
+        raise ValueError("%s: the tensors are on %s, the context on device %d" % (fn, dev, ctx.device_id))
+    return ctx
+
+
+def denoise(hdr, aov, levels=5, sigma_c=1.0, sigma_n=0.3, sigma_z=0.1, ctx=None):
+    torch, dev, W, H = _check("denoise", (("hdr", hdr, 3), ("aov", aov, _native.AOV_WORDS)))
+    ctx = _context("denoise", ctx, dev)
     out = torch.empty((W, H, 3), dtype=torch.float32, device=dev)
     ctx.denoise_device(hdr.data_ptr(), aov.data_ptr(), out.data_ptr(), W, H, levels, sigma_c, sigma_n, sigma_z,
                        stream=torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+def denoise_var(hdr, aov, moments, levels=5, sigma_c=3.0, sigma_n=0.3, sigma_z=0.1, ctx=None):
+    torch, dev, W, H = _check("denoise_var", (("hdr", hdr, 3), ("aov", aov, _native.AOV_WORDS), ("moments", moments, _native.MOM_WORDS)))
+    ctx = _context("denoise_var", ctx, dev)
+    out = torch.empty((W, H, 3), dtype=torch.float32, device=dev)
+    ctx.denoise_var_device(hdr.data_ptr(), aov.data_ptr(), moments.data_ptr(), out.data_ptr(), W, H, levels, sigma_c, sigma_n, sigma_z,
+                           stream=torch.cuda.current_stream(dev).cuda_stream)
     return out

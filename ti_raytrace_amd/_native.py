@@ -63,6 +63,13 @@ AOV_NORMAL = 3
 AOV_DEPTH = 6
 AOV_ALPHA = 7
 
+# the words of a pixel's sample-moment record (include/tirt.h, TIRT_MOM_*)
+MOM_WORDS = 8
+MOM_N = 0
+MOM_MEAN = 1
+MOM_M2 = 4
+MOM_BAD = 7
+
 # bits of the scene feature word (include/tirt.h, tirt_shade_features)
 SF_GLASS, SF_ENV, SF_LIGHT_TRI, SF_LIGHT_SPOT_LASER, SF_NO_LIGHT, SF_LIGHT_SPHERE, SF_LIGHT_OTHER = 1, 2, 4, 8, 16, 32, 64
 SF_ALL = 127
@@ -169,6 +176,17 @@ SIGNATURES.update({
     "tirt_denoise_download": (C.c_int, [_vp, _vp]),
     "tirt_denoise_export_device": (C.c_int, [_vp, _vp]),
     "tirt_denoise_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(DenoiseParams), _vp]),
+})
+
+DENOISE_VAR_DEFAULTS = {"levels": 5, "sigma_c": 3.0, "sigma_n": 0.3, "sigma_z": 0.1}      # what a NULL tirt_denoise_var_t means (TIRT_DENOISE_VAR_SIGMA_C)
+
+SIGNATURES.update({
+    "tirt_moments_enable": (C.c_int, [_vp, C.c_int]),
+    "tirt_moments_download": (C.c_int, [_vp, _vp]),
+    "tirt_moments_export_device": (C.c_int, [_vp, _vp]),
+    "tirt_moments_converged": (C.c_int, [_vp, C.c_float, C.POINTER(C.c_uint64)]),
+    "tirt_denoise_var": (C.c_int, [_vp, C.POINTER(DenoiseParams)]),      # tirt_denoise_var_t has tirt_denoise_t's fields
+    "tirt_denoise_var_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(DenoiseParams), _vp]),
 })
 
 _lib = None
@@ -449,6 +467,37 @@ class Context:
 
     def aov_export_device(self, dev_ptr):
         check(lib().tirt_aov_export_device(self.handle, C.c_void_p(int(dev_ptr))))
+
+    def moments_enable(self, on=True):
+        """tirt_moments_enable: the sample moments of the film (include/tirt.h), zeroed; on=False frees them"""
+        check(lib().tirt_moments_enable(self.handle, 1 if on else 0))
+
+    def moments_download(self, W, H):
+        """[W, H, MOM_WORDS] float32: n, mean3, M2 3, bad per pixel"""
+        out = np.zeros((W, H, MOM_WORDS), np.float32)
+        check(lib().tirt_moments_download(self.handle, _ptr(out)))
+        return out
+
+    def moments_export_device(self, dev_ptr):
+        check(lib().tirt_moments_export_device(self.handle, C.c_void_p(int(dev_ptr))))
+
+    def moments_converged(self, threshold):
+        """tirt_moments_converged: (measured pixels, measured pixels whose standard error exceeds threshold x their mean level, pixels with skipped samples)"""
+        out = (C.c_uint64 * 3)()
+        check(lib().tirt_moments_converged(self.handle, float(threshold), out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def denoise_var(self, levels=5, sigma_c=DENOISE_VAR_DEFAULTS["sigma_c"], sigma_n=0.3, sigma_z=0.1):
+        """tirt_denoise_var: the variance-guided a-trous filter over the context's film, feature buffers and sample moments, into the buffer
+        denoise_download reads (include/tirt.h); asynchronous"""
+        prm = DenoiseParams(int(levels), float(sigma_c), float(sigma_n), float(sigma_z))
+        check(lib().tirt_denoise_var(self.handle, C.byref(prm)))
+
+    def denoise_var_device(self, hdr, aov, mom, out, W, H, levels=5, sigma_c=DENOISE_VAR_DEFAULTS["sigma_c"], sigma_n=0.3, sigma_z=0.1, stream=0):
+        """tirt_denoise_var_device on device memory: as denoise_device, with mom [W, H, 8] the sample moments"""
+        prm = DenoiseParams(int(levels), float(sigma_c), float(sigma_n), float(sigma_z))
+        check(lib().tirt_denoise_var_device(self.handle, _vp(int(hdr) or None), _vp(int(aov) or None), _vp(int(mom) or None), _vp(int(out) or None),
+                                            int(W), int(H), C.byref(prm), _vp(int(stream) or None)))
 
     def denoise(self, levels=5, sigma_c=1.0, sigma_n=0.3, sigma_z=0.1):
         """tirt_denoise: the a-trous filter over the context's film and feature buffers into a buffer of its own (include/tirt.h); asynchronous"""

@@ -479,7 +479,7 @@ void tirt_destroy(tirt_ctx *c)
     drain_render_events(c);
     DevBuf *bufs[] = {&c->vertex, &c->primitive, &c->material, &c->shape, &c->light, &c->env, &c->mat_lrgb, &c->shade_rec, &c->light_rec, &c->morton_unsorted, &c->keys_a,
                       &c->keys_b, &c->vals_a, &c->vals_b, &c->hist, &c->morton_sorted, &c->bvh_node, &c->compact, &c->parent,
-                      &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb, &c->aov, &c->dn_mem, &c->dn_out,
+                      &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb, &c->aov, &c->mom, &c->mom_cnt, &c->dn_mem, &c->dn_out,
                       &c->counters_mem, &c->spill, &c->trace_stage, &c->debug_mem, &c->query_mem, &c->dyn_mem, &c->dev_counters, &c->bdpt_px, &c->timeline, &c->pvb_set[0].count, &c->pvb_set[0].cand, &c->pvb_set[0].bound, &c->pvb_set[1].count, &c->pvb_set[1].cand, &c->pvb_set[1].bound, &c->pvb_stat, &c->pvb_tmp};
     for (DevBuf *b : bufs) b->release();
     for (auto &bl : c->bd) {
@@ -840,6 +840,10 @@ int tirt_film_create(tirt_ctx *c, int W, int H, int tile_rank, int tile_count, i
         if (sync_all(c)) return TIRT_ERR_HIP;
         c->aov.release(); c->last_aov = nullptr;
     }
+    if (c->mom.p) {                              // and so do the sample moments
+        if (sync_all(c)) return TIRT_ERR_HIP;
+        c->mom.release();
+    }
     if (c->dn_mem.p || c->dn_out.p) {            // so does the denoiser's buffer and its scratch; a filter may still be queued on the main stream
         TIRT_HIP(hipStreamSynchronize(c->stream));
         c->dn_mem.release(); c->dn_out.release();
@@ -872,6 +876,7 @@ int tirt_film_clear(tirt_ctx *c)
         AFTER_AOV(c);
         TIRT_HIP(hipMemsetAsync(c->aov.p, 0, sizeof(float) * TIRT_AOV_WORDS * (size_t)c->W * c->H, c->stream));
     }
+    if (c->mom.p) TIRT_HIP(hipMemsetAsync(c->mom.p, 0, sizeof(float) * TIRT_MOM_WORDS * (size_t)c->W * c->H, c->stream));      // (k_moments lies before last_film)
     return TIRT_OK;
 }
 
@@ -911,6 +916,69 @@ int tirt_aov_export_device(tirt_ctx *c, void *dev_dst)
     TIRT_HIP(hipMemcpyAsync(dev_dst, c->aov.p, sizeof(float) * TIRT_AOV_WORDS * (size_t)c->W * c->H, hipMemcpyDeviceToDevice, c->stream));
     TIRT_HIP(hipStreamSynchronize(c->stream));
     return TIRT_OK;
+}
+
+// ---- sample moments (tirt_moments.hip).  Their last update lies before last_film: AFTER_RENDER orders the main stream after it ----
+int tirt_moments_enable(tirt_ctx *c, int on)
+{
+    CTX(c);
+    TIRT_REQUIRE(c->hdr.p, "tirt_moments_enable: film not created");
+    if (sync_all(c)) return TIRT_ERR_HIP;      // no k_moments in flight while the records come or go
+    if (!on) { c->mom.release(); return TIRT_OK; }
+    const size_t bytes = sizeof(float) * TIRT_MOM_WORDS * (size_t)c->W * c->H;
+    if (c->mom.ensure(bytes)) return TIRT_ERR_HIP;
+    TIRT_HIP(hipMemsetAsync(c->mom.p, 0, bytes, c->stream));
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    return TIRT_OK;
+}
+
+int tirt_moments_download(tirt_ctx *c, float *out)
+{
+    CTX(c);
+    AFTER_RENDER(c);
+    TIRT_REQUIRE(c->hdr.p, "tirt_moments_download: film not created");
+    TIRT_REQUIRE(c->mom.p, "tirt_moments_download: moment buffers not enabled (tirt_moments_enable)");
+    TIRT_REQUIRE(out, "tirt_moments_download: null pointer");
+    TIRT_HIP(hipMemcpyAsync(out, c->mom.p, sizeof(float) * TIRT_MOM_WORDS * (size_t)c->W * c->H, hipMemcpyDeviceToHost, c->stream));
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    return TIRT_OK;
+}
+
+int tirt_moments_export_device(tirt_ctx *c, void *dev_dst)
+{
+    CTX(c);
+    AFTER_RENDER(c);
+    TIRT_REQUIRE(c->hdr.p, "tirt_moments_export_device: film not created");
+    TIRT_REQUIRE(c->mom.p, "tirt_moments_export_device: moment buffers not enabled (tirt_moments_enable)");
+    TIRT_REQUIRE(dev_dst, "tirt_moments_export_device: null pointer");
+    TIRT_HIP(hipMemcpyAsync(dev_dst, c->mom.p, sizeof(float) * TIRT_MOM_WORDS * (size_t)c->W * c->H, hipMemcpyDeviceToDevice, c->stream));
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    return TIRT_OK;
+}
+
+int tirt_moments_converged(tirt_ctx *c, float threshold, uint64_t out[3])
+{
+    CTX(c);
+    AFTER_RENDER(c);
+    TIRT_REQUIRE(c->hdr.p, "tirt_moments_converged: film not created");
+    TIRT_REQUIRE(c->mom.p, "tirt_moments_converged: moment buffers not enabled (tirt_moments_enable)");
+    TIRT_REQUIRE(out, "tirt_moments_converged: null pointer");
+    TIRT_REQUIRE(threshold > 0.0f, "tirt_moments_converged: threshold must be > 0 (and not NaN)");
+    return moments_converged(c, threshold * threshold, out);
+}
+
+int tirt_denoise_var(tirt_ctx *c, const tirt_denoise_var_t *params)
+{
+    CTX(c);
+    AFTER_RENDER(c);
+    AFTER_AOV(c);
+    return denoise_var_film(c, params);
+}
+
+int tirt_denoise_var_device(tirt_ctx *c, const float *hdr, const float *aov, const float *mom, float *out, int W, int H, const tirt_denoise_var_t *params, void *stream)
+{
+    CTX(c);
+    return denoise_var_device(c, hdr, aov, mom, out, W, H, params, stream);
 }
 
 int tirt_denoise(tirt_ctx *c, const tirt_denoise_t *params)

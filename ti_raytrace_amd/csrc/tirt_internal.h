@@ -322,6 +322,7 @@ struct tirt_ctx {
     tirt::DevBuf hdr, rgb;
     tirt::DevBuf aov;                             // tirt_aov_enable: TIRT_AOV_WORDS f32 per pixel of the film (p == nullptr: disabled)
     hipEvent_t last_aov = nullptr;                // aov_done of the most recent batch (any lane): the next k_aov and the records' main-stream consumers wait for it
+    tirt::DevBuf mom, mom_cnt;                    // tirt_moments_enable: TIRT_MOM_WORDS f32 per pixel of the film (p == nullptr: disabled), updated behind k_film and covered by last_film; the three counters of tirt_moments_converged
     tirt::DevBuf dn_mem, dn_out;                  // denoiser (tirt_denoise.hip): 60 B of scratch per pixel; the filtered film W*H*3 f32 (p == nullptr: no tirt_denoise yet).  Both go with the film
 
     // wavefront state
@@ -465,6 +466,8 @@ int trace_rays(tirt_ctx *c, const TraceJob &j);
 int trace_rays_prepare(tirt_ctx *c, int lane);      // allocates what trace_rays needs on that lane at bdpt_stack_size (stack spill, fetch cursors)
 int debug_render(tirt_ctx *c, uint32_t frame, uint32_t seed, int mode, int stack_size, int flags);      // tirt_debug.hip
 int aov_launch(tirt_ctx *c, Lane &L, const TileMap &tm, int P, int F, uint32_t frame_begin);      // tirt_aov.hip: k_aov over a batch's bounce-0 hits
+int moments_launch(tirt_ctx *c, Lane &L, const TileMap &tm, int P, int F);      // tirt_moments.hip: k_moments over a batch's final radiances
+int moments_converged(tirt_ctx *c, float t2, uint64_t out[3]);
 int query_closest(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, int stack_size, int flags, float *out_t, int32_t *out_prim,
                   float *out_hit, int64_t hit_stride, int32_t *counts, void *stream);      // tirt_query.hip
 int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, const float *tmax, int64_t tmax_stride, float tmax_all,
@@ -475,6 +478,8 @@ int query_begin(tirt_ctx *c, void *stream);
 int query_end(tirt_ctx *c, void *stream);
 int denoise_film(tirt_ctx *c, const tirt_denoise_t *prm);      // tirt_denoise.hip
 int denoise_device(tirt_ctx *c, const float *hdr, const float *aov, float *out, int W, int H, const tirt_denoise_t *prm, void *stream);
+int denoise_var_film(tirt_ctx *c, const tirt_denoise_var_t *prm);
+int denoise_var_device(tirt_ctx *c, const float *hdr, const float *aov, const float *mom, float *out, int W, int H, const tirt_denoise_var_t *prm, void *stream);
 int trace_host(tirt_ctx *c, const float *rays, int nr, int stack_size, int flags, bool shadow, float *out_f, int32_t *out_prim, int32_t *counts);      // tirt_trace_closest / tirt_trace_shadow
 int pvb_prepare(tirt_ctx *c);                          // tirt_pvb.hip
 void pvb_launch_cand(tirt_ctx *c, hipStream_t st, const BvhView &bv, const float *dx, const float *dy, const float *dz, const TileMap &tm, int P, int S,

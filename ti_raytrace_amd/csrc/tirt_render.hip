@@ -1536,6 +1536,7 @@ int pt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed,
         if (c->last_film) TIRT_HIP(hipStreamWaitEvent(st, c->last_film, 0));
         if (spec) hipLaunchKernelGGL(k_film_spec, dim3((P + B - 1) / B), dim3(B), 0, st, L.ps, L.ps.fw, *spec, tm, P, F, f0, seed, c->hdr.as<float>());
         else hipLaunchKernelGGL(k_film, dim3((P + B - 1) / B), dim3(B), 0, st, L.ps, tm, P, F, f0, c->hdr.as<float>());
+        if (c->mom.p && !spec) { if (int rc = moments_launch(c, L, tm, P, F)) return rc; }      // the sample moments read fr / fg / fb too: behind the same wait, before film_done (tirt_moments.hip)
         TIRT_HIP(hipEventRecord(L.film_done, st));
         L.film_recorded = true;
         c->last_film = L.film_done;
