@@ -367,7 +367,7 @@ int tirt_moments_converged(tirt_ctx *ctx, float threshold, uint64_t out[3]);
  *   tirt_denoise's, and TIRT_ERR_ARG when the moment buffers are not enabled.
  * tirt_denoise_var_device: on caller-owned device arrays, mom [W,H,TIRT_MOM_WORDS] 16-byte aligned as aov; otherwise as tirt_denoise_device. */
 #define TIRT_DENOISE_VAR_SIGMA_C 3.0f
-typedef struct { int levels; float sigma_c, sigma_n, sigma_z; } tirt_denoise_var_t;
+typedef tirt_denoise_t tirt_denoise_var_t;
 int tirt_denoise_var(tirt_ctx *ctx, const tirt_denoise_var_t *params);
 int tirt_denoise_var_device(tirt_ctx *ctx, const float *hdr, const float *aov, const float *mom, float *out, int W, int H, const tirt_denoise_var_t *params, void *stream);
 

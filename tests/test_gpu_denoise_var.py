@@ -151,3 +151,41 @@ def test_refusals(gpu_ctx_ok):
             fresh.denoise_var()
     finally:
         fresh.close()
+
+
+@pytest.mark.parametrize("W,H", [(5, 3), (33, 17)], ids=["5x3", "33x17"])
+def test_the_two_modes_in_turn_on_one_context_leave_nothing_behind_for_each_other(gpu_ctx_ok, W, H):
+    """Both modes are one set of kernels over one scratch and one launch path; they pack the fourth words of its records differently, and the
+    variance-guided mode starts its ping-pong from the other half of A: on one context tirt_denoise, tirt_denoise_var, tirt_denoise again, at levels 1 and 3.  The first and the third
+    give the same bits, those of denoise_expected; the second those of denoise_var_expected.  5 x 3 is the smallest film where a level-1 tap leaves
+    the film on every side; 33 x 17 crosses a wave boundary along j and every step of level 3 lands inside and outside.
+    The device-memory entry points take a made-up film (`made_up`: NaN pixels, unknown variances).  The context's own route has no way to take made-up
+    records -- there is no import of feature or moment records -- so it runs the same sequence on a rendered Cornell box of the same size."""
+    import torch
+    dev = torch.device("cuda", 0)
+    hdr, aov, mom = made_up(W, H, 100 * W + H)
+    hdr_t, aov_t, mom_t = (torch.from_numpy(a).to(dev) for a in (hdr, aov, mom))
+    ctx = _native.Context(0)
+    try:
+        for levels in (1, 3):
+            first = ti_raytrace_amd.denoise(hdr_t, aov_t, levels=levels, ctx=ctx).cpu().numpy()
+            second = ti_raytrace_amd.denoise_var(hdr_t, aov_t, mom_t, levels=levels, ctx=ctx).cpu().numpy()
+            third = ti_raytrace_amd.denoise(hdr_t, aov_t, levels=levels, ctx=ctx).cpu().numpy()
+            check(first, de.denoise_expected(hdr, aov, levels=levels), ("tirt_denoise_device first", W, H, levels))
+            check(second, dv.denoise_var_expected(hdr, aov, mom, levels=levels), ("tirt_denoise_var_device between", W, H, levels))
+            check(third, first, ("tirt_denoise_device again", W, H, levels), True)
+    finally:
+        ctx.close()
+    N = 2
+    ex = build("cornell", W, H, N, aov=True, moments=True)
+    it = ex.integrator
+    it.render_frames(N)
+    hdr, aov, mom = it.hdr.to_numpy(), it.aov_to_numpy(), it.moments_to_numpy()
+    assert (mom[:, :, 0] == N).all()
+    for levels in (1, 3):
+        it.denoise(levels=levels); first = it.denoised.to_numpy()
+        it.denoise_var(levels=levels); second = it.denoised.to_numpy()
+        it.denoise(levels=levels); third = it.denoised.to_numpy()
+        check(first, de.denoise_expected(hdr, aov, levels=levels), ("tirt_denoise first", W, H, levels))
+        check(second, dv.denoise_var_expected(hdr, aov, mom, levels=levels), ("tirt_denoise_var between", W, H, levels))
+        check(third, first, ("tirt_denoise again", W, H, levels), True)

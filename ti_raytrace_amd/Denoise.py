@@ -59,19 +59,20 @@ def _context(fn, ctx, dev):
     return ctx
 
 
-def denoise(hdr, aov, levels=5, sigma_c=1.0, sigma_n=0.3, sigma_z=0.1, ctx=None):
-    torch, dev, W, H = _check("denoise", (("hdr", hdr, 3), ("aov", aov, _native.AOV_WORDS)))
-    ctx = _context("denoise", ctx, dev)
+def _run(fn, tensors, params, ctx):
+    """tensors: hdr and aov for tirt_denoise_device; hdr, aov and moments for tirt_denoise_var_device"""
+    torch, dev, W, H = _check(fn, tensors)
+    ctx = _context(fn, ctx, dev)
     out = torch.empty((W, H, 3), dtype=torch.float32, device=dev)
-    ctx.denoise_device(hdr.data_ptr(), aov.data_ptr(), out.data_ptr(), W, H, levels, sigma_c, sigma_n, sigma_z,
-                       stream=torch.cuda.current_stream(dev).cuda_stream)
+    run = ctx.denoise_var_device if len(tensors) == 3 else ctx.denoise_device
+    run(*[t.data_ptr() for _, t, _ in tensors], out.data_ptr(), W, H, *params, stream=torch.cuda.current_stream(dev).cuda_stream)
     return out
+
+
+def denoise(hdr, aov, levels=5, sigma_c=1.0, sigma_n=0.3, sigma_z=0.1, ctx=None):
+    return _run("denoise", (("hdr", hdr, 3), ("aov", aov, _native.AOV_WORDS)), (levels, sigma_c, sigma_n, sigma_z), ctx)
 
 
 def denoise_var(hdr, aov, moments, levels=5, sigma_c=3.0, sigma_n=0.3, sigma_z=0.1, ctx=None):
-    torch, dev, W, H = _check("denoise_var", (("hdr", hdr, 3), ("aov", aov, _native.AOV_WORDS), ("moments", moments, _native.MOM_WORDS)))
-    ctx = _context("denoise_var", ctx, dev)
-    out = torch.empty((W, H, 3), dtype=torch.float32, device=dev)
-    ctx.denoise_var_device(hdr.data_ptr(), aov.data_ptr(), moments.data_ptr(), out.data_ptr(), W, H, levels, sigma_c, sigma_n, sigma_z,
-                           stream=torch.cuda.current_stream(dev).cuda_stream)
-    return out
+    return _run("denoise_var", (("hdr", hdr, 3), ("aov", aov, _native.AOV_WORDS), ("moments", moments, _native.MOM_WORDS)),
+                (levels, sigma_c, sigma_n, sigma_z), ctx)

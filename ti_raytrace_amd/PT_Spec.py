@@ -14,7 +14,7 @@ from . import HeroSample as Hero
 from . import Rgb2Spec as RGB2SPEC
 from . import Sky
 from . import Spectrum as Spec
-from . import PT_RGB
+from .FilmRecords import FilmRecords
 from .PT_RGB import default_tile_size
 from .Scene import DeviceField
 
@@ -24,7 +24,7 @@ _TABLE_CACHE = {}        # (res, who built it) -> (scale, data): the optimiser's
                          # tests made with the oracle's generator must not stand in for the device-built one (or the reverse) in one process
 
 
-class PathTrace:
+class PathTrace(FilmRecords):
     def __init__(self, imgSizeX, imgSizeY, cam, scene, stack_size, seed=1, tile_rank=0, tile_count=1, tile_size=None, flags=0,
                  spec_table_path=None, aov=False):
         self.imgSizeX = imgSizeX
@@ -51,13 +51,6 @@ class PathTrace:
         self.aov = aov                               # the feature buffers of PT_RGB.PathTrace: the camera rays and the launch are the same
         self._aov_fields()
         self.denoised = DeviceField("denoised", scene, self._denoised_download)      # the film after denoise(), as PT_RGB.PathTrace's
-
-    _aov_fields, aov_to_numpy, aov_to_torch = PT_RGB.PathTrace._aov_fields, PT_RGB.PathTrace.aov_to_numpy, PT_RGB.PathTrace.aov_to_torch
-    denoise, _denoised_download, denoised_to_torch = PT_RGB.PathTrace.denoise, PT_RGB.PathTrace._denoised_download, PT_RGB.PathTrace.denoised_to_torch
-
-    def _download(self, hdr):
-        h, r = self.scene.ctx.film_download(self.imgSizeX, self.imgSizeY, want_hdr=hdr, want_rgb=not hdr)
-        return h if hdr else r
 
     # -- integrator/PT_Spec.py:56-91 -----------------------------------------------------------------------------
     def setup_data_cpu(self):

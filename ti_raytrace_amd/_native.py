@@ -449,11 +449,29 @@ class Context:
         check(lib().tirt_film_download(self.handle, _ptr(hdr), _ptr(rgb)))
         return hdr, rgb
 
+    def _record_download(self, symbol, W, H, words):
+        """[W, H, words] float32 from one of the tirt_*_download entry points"""
+        out = np.zeros((W, H, words), np.float32)
+        check(getattr(lib(), symbol)(self.handle, _ptr(out)))
+        return out
+
+    def _export(self, symbol, dev_ptr):
+        """the tirt_*_export_device / tirt_film_import_device entry points: one device address"""
+        check(getattr(lib(), symbol)(self.handle, C.c_void_p(int(dev_ptr))))
+
+    @staticmethod
+    def _denoise_params(levels, sigma_c, sigma_n, sigma_z):
+        return DenoiseParams(int(levels), float(sigma_c), float(sigma_n), float(sigma_z))
+
+    def _denoise_device(self, symbol, arrays, W, H, levels, sigma_c, sigma_n, sigma_z, stream):
+        check(getattr(lib(), symbol)(self.handle, *[_vp(int(a) or None) for a in arrays], int(W), int(H),
+                                     C.byref(self._denoise_params(levels, sigma_c, sigma_n, sigma_z)), _vp(int(stream) or None)))
+
     def film_export_device(self, dev_ptr):
-        check(lib().tirt_film_export_device(self.handle, C.c_void_p(int(dev_ptr))))
+        self._export("tirt_film_export_device", dev_ptr)
 
     def film_import_device(self, dev_ptr):
-        check(lib().tirt_film_import_device(self.handle, C.c_void_p(int(dev_ptr))))
+        self._export("tirt_film_import_device", dev_ptr)
 
     def aov_enable(self, on=True):
         """tirt_aov_enable: the feature buffers of the film (include/tirt.h), zeroed; on=False frees them"""
@@ -461,12 +479,10 @@ class Context:
 
     def aov_download(self, W, H):
         """[W, H, AOV_WORDS] float32: albedo3, normal3, depth, alpha per pixel"""
-        out = np.zeros((W, H, AOV_WORDS), np.float32)
-        check(lib().tirt_aov_download(self.handle, _ptr(out)))
-        return out
+        return self._record_download("tirt_aov_download", W, H, AOV_WORDS)
 
     def aov_export_device(self, dev_ptr):
-        check(lib().tirt_aov_export_device(self.handle, C.c_void_p(int(dev_ptr))))
+        self._export("tirt_aov_export_device", dev_ptr)
 
     def moments_enable(self, on=True):
         """tirt_moments_enable: the sample moments of the film (include/tirt.h), zeroed; on=False frees them"""
@@ -474,12 +490,10 @@ class Context:
 
     def moments_download(self, W, H):
         """[W, H, MOM_WORDS] float32: n, mean3, M2 3, bad per pixel"""
-        out = np.zeros((W, H, MOM_WORDS), np.float32)
-        check(lib().tirt_moments_download(self.handle, _ptr(out)))
-        return out
+        return self._record_download("tirt_moments_download", W, H, MOM_WORDS)
 
     def moments_export_device(self, dev_ptr):
-        check(lib().tirt_moments_export_device(self.handle, C.c_void_p(int(dev_ptr))))
+        self._export("tirt_moments_export_device", dev_ptr)
 
     def moments_converged(self, threshold):
         """tirt_moments_converged: (measured pixels, measured pixels whose standard error exceeds threshold x their mean level, pixels with skipped samples)"""
@@ -490,35 +504,27 @@ class Context:
     def denoise_var(self, levels=5, sigma_c=DENOISE_VAR_DEFAULTS["sigma_c"], sigma_n=0.3, sigma_z=0.1):
         """tirt_denoise_var: the variance-guided a-trous filter over the context's film, feature buffers and sample moments, into the buffer
         denoise_download reads (include/tirt.h); asynchronous"""
-        prm = DenoiseParams(int(levels), float(sigma_c), float(sigma_n), float(sigma_z))
-        check(lib().tirt_denoise_var(self.handle, C.byref(prm)))
+        check(lib().tirt_denoise_var(self.handle, C.byref(self._denoise_params(levels, sigma_c, sigma_n, sigma_z))))
 
     def denoise_var_device(self, hdr, aov, mom, out, W, H, levels=5, sigma_c=DENOISE_VAR_DEFAULTS["sigma_c"], sigma_n=0.3, sigma_z=0.1, stream=0):
         """tirt_denoise_var_device on device memory: as denoise_device, with mom [W, H, 8] the sample moments"""
-        prm = DenoiseParams(int(levels), float(sigma_c), float(sigma_n), float(sigma_z))
-        check(lib().tirt_denoise_var_device(self.handle, _vp(int(hdr) or None), _vp(int(aov) or None), _vp(int(mom) or None), _vp(int(out) or None),
-                                            int(W), int(H), C.byref(prm), _vp(int(stream) or None)))
+        self._denoise_device("tirt_denoise_var_device", (hdr, aov, mom, out), W, H, levels, sigma_c, sigma_n, sigma_z, stream)
 
     def denoise(self, levels=5, sigma_c=1.0, sigma_n=0.3, sigma_z=0.1):
         """tirt_denoise: the a-trous filter over the context's film and feature buffers into a buffer of its own (include/tirt.h); asynchronous"""
-        prm = DenoiseParams(int(levels), float(sigma_c), float(sigma_n), float(sigma_z))
-        check(lib().tirt_denoise(self.handle, C.byref(prm)))
+        check(lib().tirt_denoise(self.handle, C.byref(self._denoise_params(levels, sigma_c, sigma_n, sigma_z))))
 
     def denoise_download(self, W, H):
         """[W, H, 3] float32: the filtered film of the last denoise()"""
-        out = np.zeros((W, H, 3), np.float32)
-        check(lib().tirt_denoise_download(self.handle, _ptr(out)))
-        return out
+        return self._record_download("tirt_denoise_download", W, H, 3)
 
     def denoise_export_device(self, dev_ptr):
-        check(lib().tirt_denoise_export_device(self.handle, C.c_void_p(int(dev_ptr))))
+        self._export("tirt_denoise_export_device", dev_ptr)
 
     def denoise_device(self, hdr, aov, out, W, H, levels=5, sigma_c=1.0, sigma_n=0.3, sigma_z=0.1, stream=0):
         """tirt_denoise_device on device memory: hdr [W, H, 3], aov [W, H, 8], out [W, H, 3] are integer device addresses, `stream` a hipStream_t
         handle (0 = the null stream).  Asynchronous; ti_raytrace_amd.denoise is the torch front end."""
-        prm = DenoiseParams(int(levels), float(sigma_c), float(sigma_n), float(sigma_z))
-        check(lib().tirt_denoise_device(self.handle, _vp(int(hdr) or None), _vp(int(aov) or None), _vp(int(out) or None), int(W), int(H),
-                                        C.byref(prm), _vp(int(stream) or None)))
+        self._denoise_device("tirt_denoise_device", (hdr, aov, out), W, H, levels, sigma_c, sigma_n, sigma_z, stream)
 
     def trace_closest(self, rays, stack_size=64, flags=0):
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)

@@ -829,6 +829,44 @@ int tirt_camera_set(tirt_ctx *c, const float view[16], const float view_inv[16],
     return TIRT_OK;
 }
 
+// ---- the per-pixel buffers beside the film: `words` f32 per pixel, pixel p = i * H + j as hdr ----
+enum RecordOrder { ORDER_NONE, ORDER_RENDER, ORDER_AOV };      // what a main-stream reader waits for: nothing, last_film, last_aov
+struct FilmRecord { tirt::DevBuf tirt_ctx::*buf; int words; const char *missing; RecordOrder order; };
+enum { REC_AOV, REC_MOM, REC_DENOISED };
+static const FilmRecord RECORDS[3] = {
+    {&tirt_ctx::aov, TIRT_AOV_WORDS, "feature buffers not enabled (tirt_aov_enable)", ORDER_AOV},
+    {&tirt_ctx::mom, TIRT_MOM_WORDS, "moment buffers not enabled (tirt_moments_enable)", ORDER_RENDER},
+    {&tirt_ctx::dn_out, 3, "nothing filtered yet (tirt_denoise)", ORDER_NONE},      // written by the filter on the main stream itself
+};
+
+static size_t record_bytes(const tirt_ctx *c, const FilmRecord &r) { return sizeof(float) * r.words * (size_t)c->W * c->H; }
+
+// tirt_*_enable: on != 0 allocates and zeroes the record, on == 0 frees it
+static int record_enable(tirt_ctx *c, const FilmRecord &r, int on, const char *fn)
+{
+    TIRT_REQUIRE(c->hdr.p, std::string(fn) + ": film not created");
+    if (sync_all(c)) return TIRT_ERR_HIP;      // no kernel of the render in flight while the records come or go
+    if (r.order == ORDER_AOV) c->last_aov = nullptr;
+    if (!on) { (c->*r.buf).release(); return TIRT_OK; }
+    if ((c->*r.buf).ensure(record_bytes(c, r))) return TIRT_ERR_HIP;
+    TIRT_HIP(hipMemsetAsync((c->*r.buf).p, 0, record_bytes(c, r), c->stream));
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    return TIRT_OK;
+}
+
+// tirt_*_download (kind = hipMemcpyDeviceToHost) and tirt_*_export_device (hipMemcpyDeviceToDevice): the whole record, and wait for it
+static int record_copy_out(tirt_ctx *c, const FilmRecord &r, void *dst, hipMemcpyKind kind, const char *fn)
+{
+    if (r.order == ORDER_RENDER) AFTER_RENDER(c);
+    if (r.order == ORDER_AOV) AFTER_AOV(c);
+    TIRT_REQUIRE(c->hdr.p, std::string(fn) + ": film not created");
+    TIRT_REQUIRE((c->*r.buf).p, std::string(fn) + ": " + r.missing);
+    TIRT_REQUIRE(dst, std::string(fn) + ": null pointer");
+    TIRT_HIP(hipMemcpyAsync(dst, (c->*r.buf).p, record_bytes(c, r), kind, c->stream));
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    return TIRT_OK;
+}
+
 int tirt_film_create(tirt_ctx *c, int W, int H, int tile_rank, int tile_count, int tile_size)
 {
     CTX(c);
@@ -836,14 +874,12 @@ int tirt_film_create(tirt_ctx *c, int W, int H, int tile_rank, int tile_count, i
     TIRT_REQUIRE(W >= 1 && H >= 1 && (long long)W * H < (1ll << 30), "tirt_film_create: bad size");
     TIRT_REQUIRE(tile_count >= 1 && tile_rank >= 0 && tile_rank < tile_count && tile_size >= 1, "tirt_film_create: bad tiling");
     const long NP = (long)W * H;
-    if (c->aov.p) {                              // the feature buffers belong to the film: a new film starts without them
-        if (sync_all(c)) return TIRT_ERR_HIP;
-        c->aov.release(); c->last_aov = nullptr;
-    }
-    if (c->mom.p) {                              // and so do the sample moments
-        if (sync_all(c)) return TIRT_ERR_HIP;
-        c->mom.release();
-    }
+    for (const FilmRecord &r : RECORDS)          // the records the render writes belong to the film: a new film starts without them
+        if (r.order != ORDER_NONE && (c->*r.buf).p) {
+            if (sync_all(c)) return TIRT_ERR_HIP;
+            (c->*r.buf).release();
+            if (r.order == ORDER_AOV) c->last_aov = nullptr;
+        }
     if (c->dn_mem.p || c->dn_out.p) {            // so does the denoiser's buffer and its scratch; a filter may still be queued on the main stream
         TIRT_HIP(hipStreamSynchronize(c->stream));
         c->dn_mem.release(); c->dn_out.release();
@@ -872,89 +908,22 @@ int tirt_film_clear(tirt_ctx *c)
     if (c->bdpt_px.p) TIRT_HIP(hipMemsetAsync(c->bdpt_px.p, 0, c->bdpt_px.bytes, c->stream));
     TIRT_HIP(hipMemsetAsync(c->hdr.p, 0, sizeof(float) * 3 * (size_t)c->W * c->H, c->stream));
     TIRT_HIP(hipMemsetAsync(c->rgb.p, 0, sizeof(float) * 3 * (size_t)c->W * c->H, c->stream));
-    if (c->aov.p) {
-        AFTER_AOV(c);
-        TIRT_HIP(hipMemsetAsync(c->aov.p, 0, sizeof(float) * TIRT_AOV_WORDS * (size_t)c->W * c->H, c->stream));
-    }
-    if (c->mom.p) TIRT_HIP(hipMemsetAsync(c->mom.p, 0, sizeof(float) * TIRT_MOM_WORDS * (size_t)c->W * c->H, c->stream));      // (k_moments lies before last_film)
+    for (const FilmRecord &r : RECORDS)          // (the denoiser's buffer stays; k_moments lies before last_film)
+        if (r.order != ORDER_NONE && (c->*r.buf).p) {
+            if (r.order == ORDER_AOV) AFTER_AOV(c);
+            TIRT_HIP(hipMemsetAsync((c->*r.buf).p, 0, record_bytes(c, r), c->stream));
+        }
     return TIRT_OK;
 }
 
-int tirt_aov_enable(tirt_ctx *c, int on)
-{
-    CTX(c);
-    TIRT_REQUIRE(c->hdr.p, "tirt_aov_enable: film not created");
-    if (sync_all(c)) return TIRT_ERR_HIP;      // no k_aov in flight while the records come or go
-    c->last_aov = nullptr;
-    if (!on) { c->aov.release(); return TIRT_OK; }
-    const size_t bytes = sizeof(float) * TIRT_AOV_WORDS * (size_t)c->W * c->H;
-    if (c->aov.ensure(bytes)) return TIRT_ERR_HIP;
-    TIRT_HIP(hipMemsetAsync(c->aov.p, 0, bytes, c->stream));
-    TIRT_HIP(hipStreamSynchronize(c->stream));
-    return TIRT_OK;
-}
+int tirt_aov_enable(tirt_ctx *c, int on) { CTX(c); return record_enable(c, RECORDS[REC_AOV], on, "tirt_aov_enable"); }
+int tirt_aov_download(tirt_ctx *c, float *out) { CTX(c); return record_copy_out(c, RECORDS[REC_AOV], out, hipMemcpyDeviceToHost, "tirt_aov_download"); }
+int tirt_aov_export_device(tirt_ctx *c, void *dev_dst) { CTX(c); return record_copy_out(c, RECORDS[REC_AOV], dev_dst, hipMemcpyDeviceToDevice, "tirt_aov_export_device"); }
 
-int tirt_aov_download(tirt_ctx *c, float *out)
-{
-    CTX(c);
-    AFTER_AOV(c);
-    TIRT_REQUIRE(c->hdr.p, "tirt_aov_download: film not created");
-    TIRT_REQUIRE(c->aov.p, "tirt_aov_download: feature buffers not enabled (tirt_aov_enable)");
-    TIRT_REQUIRE(out, "tirt_aov_download: null pointer");
-    TIRT_HIP(hipMemcpyAsync(out, c->aov.p, sizeof(float) * TIRT_AOV_WORDS * (size_t)c->W * c->H, hipMemcpyDeviceToHost, c->stream));
-    TIRT_HIP(hipStreamSynchronize(c->stream));
-    return TIRT_OK;
-}
-
-int tirt_aov_export_device(tirt_ctx *c, void *dev_dst)
-{
-    CTX(c);
-    AFTER_AOV(c);
-    TIRT_REQUIRE(c->hdr.p, "tirt_aov_export_device: film not created");
-    TIRT_REQUIRE(c->aov.p, "tirt_aov_export_device: feature buffers not enabled (tirt_aov_enable)");
-    TIRT_REQUIRE(dev_dst, "tirt_aov_export_device: null pointer");
-    TIRT_HIP(hipMemcpyAsync(dev_dst, c->aov.p, sizeof(float) * TIRT_AOV_WORDS * (size_t)c->W * c->H, hipMemcpyDeviceToDevice, c->stream));
-    TIRT_HIP(hipStreamSynchronize(c->stream));
-    return TIRT_OK;
-}
-
-// ---- sample moments (tirt_moments.hip).  Their last update lies before last_film: AFTER_RENDER orders the main stream after it ----
-int tirt_moments_enable(tirt_ctx *c, int on)
-{
-    CTX(c);
-    TIRT_REQUIRE(c->hdr.p, "tirt_moments_enable: film not created");
-    if (sync_all(c)) return TIRT_ERR_HIP;      // no k_moments in flight while the records come or go
-    if (!on) { c->mom.release(); return TIRT_OK; }
-    const size_t bytes = sizeof(float) * TIRT_MOM_WORDS * (size_t)c->W * c->H;
-    if (c->mom.ensure(bytes)) return TIRT_ERR_HIP;
-    TIRT_HIP(hipMemsetAsync(c->mom.p, 0, bytes, c->stream));
-    TIRT_HIP(hipStreamSynchronize(c->stream));
-    return TIRT_OK;
-}
-
-int tirt_moments_download(tirt_ctx *c, float *out)
-{
-    CTX(c);
-    AFTER_RENDER(c);
-    TIRT_REQUIRE(c->hdr.p, "tirt_moments_download: film not created");
-    TIRT_REQUIRE(c->mom.p, "tirt_moments_download: moment buffers not enabled (tirt_moments_enable)");
-    TIRT_REQUIRE(out, "tirt_moments_download: null pointer");
-    TIRT_HIP(hipMemcpyAsync(out, c->mom.p, sizeof(float) * TIRT_MOM_WORDS * (size_t)c->W * c->H, hipMemcpyDeviceToHost, c->stream));
-    TIRT_HIP(hipStreamSynchronize(c->stream));
-    return TIRT_OK;
-}
-
-int tirt_moments_export_device(tirt_ctx *c, void *dev_dst)
-{
-    CTX(c);
-    AFTER_RENDER(c);
-    TIRT_REQUIRE(c->hdr.p, "tirt_moments_export_device: film not created");
-    TIRT_REQUIRE(c->mom.p, "tirt_moments_export_device: moment buffers not enabled (tirt_moments_enable)");
-    TIRT_REQUIRE(dev_dst, "tirt_moments_export_device: null pointer");
-    TIRT_HIP(hipMemcpyAsync(dev_dst, c->mom.p, sizeof(float) * TIRT_MOM_WORDS * (size_t)c->W * c->H, hipMemcpyDeviceToDevice, c->stream));
-    TIRT_HIP(hipStreamSynchronize(c->stream));
-    return TIRT_OK;
-}
+// ---- sample moments (tirt_moments.hip).  Their last update lies before last_film: ORDER_RENDER orders the main stream after it ----
+int tirt_moments_enable(tirt_ctx *c, int on) { CTX(c); return record_enable(c, RECORDS[REC_MOM], on, "tirt_moments_enable"); }
+int tirt_moments_download(tirt_ctx *c, float *out) { CTX(c); return record_copy_out(c, RECORDS[REC_MOM], out, hipMemcpyDeviceToHost, "tirt_moments_download"); }
+int tirt_moments_export_device(tirt_ctx *c, void *dev_dst) { CTX(c); return record_copy_out(c, RECORDS[REC_MOM], dev_dst, hipMemcpyDeviceToDevice, "tirt_moments_export_device"); }
 
 int tirt_moments_converged(tirt_ctx *c, float threshold, uint64_t out[3])
 {
@@ -967,56 +936,37 @@ int tirt_moments_converged(tirt_ctx *c, float threshold, uint64_t out[3])
     return moments_converged(c, threshold * threshold, out);
 }
 
-int tirt_denoise_var(tirt_ctx *c, const tirt_denoise_var_t *params)
+// ---- denoiser (tirt_denoise.hip): the film routes wait for the last film update (which covers the moments) and the last k_aov ----
+static int denoise_entry(tirt_ctx *c, const tirt_denoise_t *params, bool var)
 {
     CTX(c);
     AFTER_RENDER(c);
     AFTER_AOV(c);
-    return denoise_var_film(c, params);
+    return denoise_film(c, params, var);
+}
+int tirt_denoise(tirt_ctx *c, const tirt_denoise_t *params) { return denoise_entry(c, params, false); }
+int tirt_denoise_var(tirt_ctx *c, const tirt_denoise_var_t *params) { return denoise_entry(c, params, true); }
+
+int tirt_denoise_device(tirt_ctx *c, const float *hdr, const float *aov, float *out, int W, int H, const tirt_denoise_t *params, void *stream)
+{
+    CTX(c);
+    return denoise_device(c, false, hdr, aov, nullptr, out, W, H, params, stream);
 }
 
 int tirt_denoise_var_device(tirt_ctx *c, const float *hdr, const float *aov, const float *mom, float *out, int W, int H, const tirt_denoise_var_t *params, void *stream)
 {
     CTX(c);
-    return denoise_var_device(c, hdr, aov, mom, out, W, H, params, stream);
-}
-
-int tirt_denoise(tirt_ctx *c, const tirt_denoise_t *params)
-{
-    CTX(c);
-    AFTER_RENDER(c);
-    AFTER_AOV(c);
-    return denoise_film(c, params);
+    return denoise_device(c, true, hdr, aov, mom, out, W, H, params, stream);
 }
 
 int tirt_denoise_download(tirt_ctx *c, float *out)
 {
     CTX(c);
-    TIRT_REQUIRE(c->hdr.p, "tirt_denoise_download: film not created");
-    TIRT_REQUIRE(c->dn_out.p, "tirt_denoise_download: nothing filtered yet (tirt_denoise)");
-    TIRT_REQUIRE(out, "tirt_denoise_download: null pointer");
-    TIRT_HIP(hipMemcpyAsync(out, c->dn_out.p, sizeof(float) * 3 * (size_t)c->W * c->H, hipMemcpyDeviceToHost, c->stream));
-    TIRT_HIP(hipStreamSynchronize(c->stream));
+    if (int rc = record_copy_out(c, RECORDS[REC_DENOISED], out, hipMemcpyDeviceToHost, "tirt_denoise_download")) return rc;
     TIRT_HIP(hipGetLastError());
     return TIRT_OK;
 }
-
-int tirt_denoise_export_device(tirt_ctx *c, void *dev_dst)
-{
-    CTX(c);
-    TIRT_REQUIRE(c->hdr.p, "tirt_denoise_export_device: film not created");
-    TIRT_REQUIRE(c->dn_out.p, "tirt_denoise_export_device: nothing filtered yet (tirt_denoise)");
-    TIRT_REQUIRE(dev_dst, "tirt_denoise_export_device: null pointer");
-    TIRT_HIP(hipMemcpyAsync(dev_dst, c->dn_out.p, sizeof(float) * 3 * (size_t)c->W * c->H, hipMemcpyDeviceToDevice, c->stream));
-    TIRT_HIP(hipStreamSynchronize(c->stream));
-    return TIRT_OK;
-}
-
-int tirt_denoise_device(tirt_ctx *c, const float *hdr, const float *aov, float *out, int W, int H, const tirt_denoise_t *params, void *stream)
-{
-    CTX(c);
-    return denoise_device(c, hdr, aov, out, W, H, params, stream);
-}
+int tirt_denoise_export_device(tirt_ctx *c, void *dev_dst) { CTX(c); return record_copy_out(c, RECORDS[REC_DENOISED], dev_dst, hipMemcpyDeviceToDevice, "tirt_denoise_export_device"); }
 
 static int submit_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed, int max_depth, int stack_size, int flags, bool spectral)
 {

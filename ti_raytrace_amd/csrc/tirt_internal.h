@@ -476,10 +476,8 @@ int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_strid
 int require_device_ptr(tirt_ctx *c, const void *p, const char *what);
 int query_begin(tirt_ctx *c, void *stream);
 int query_end(tirt_ctx *c, void *stream);
-int denoise_film(tirt_ctx *c, const tirt_denoise_t *prm);      // tirt_denoise.hip
-int denoise_device(tirt_ctx *c, const float *hdr, const float *aov, float *out, int W, int H, const tirt_denoise_t *prm, void *stream);
-int denoise_var_film(tirt_ctx *c, const tirt_denoise_var_t *prm);
-int denoise_var_device(tirt_ctx *c, const float *hdr, const float *aov, const float *mom, float *out, int W, int H, const tirt_denoise_var_t *prm, void *stream);
+int denoise_film(tirt_ctx *c, const tirt_denoise_t *prm, bool var);      // tirt_denoise.hip; var: the variance-guided mode
+int denoise_device(tirt_ctx *c, bool var, const float *hdr, const float *aov, const float *mom, float *out, int W, int H, const tirt_denoise_t *prm, void *stream);
 int trace_host(tirt_ctx *c, const float *rays, int nr, int stack_size, int flags, bool shadow, float *out_f, int32_t *out_prim, int32_t *counts);      // tirt_trace_closest / tirt_trace_shadow
 int pvb_prepare(tirt_ctx *c);                          // tirt_pvb.hip
 void pvb_launch_cand(tirt_ctx *c, hipStream_t st, const BvhView &bv, const float *dx, const float *dy, const float *dz, const TileMap &tm, int P, int S,
