@@ -205,7 +205,7 @@ int tirt_camera_set(tirt_ctx *ctx, const float view[16], const float view_inv[16
  * columns (8 * H pixels; H a multiple of 8, W * H a multiple of tile_size) lets the device walk a tile in 8 x 8 pixel blocks
  * -- the camera rays of a wave are then a compact bundle; any other tile_size works too. */
 int tirt_film_create(tirt_ctx *ctx, int W, int H, int tile_rank, int tile_count, int tile_size);
-int tirt_film_clear(tirt_ctx *ctx);
+int tirt_film_clear(tirt_ctx *ctx);       /* zeroes hdr, rgb_film and the enabled records; an installed pixel set (tirt_pixel_set_*) stays installed */
 
 /* PathTrace.render x frame_count (integrator/PT_RGB.py:44-136), frames frame_begin ..
  * frame_begin+frame_count-1 accumulated into hdr as the running mean of :134-136.
@@ -370,6 +370,49 @@ int tirt_moments_converged(tirt_ctx *ctx, float threshold, uint64_t out[3]);
 typedef tirt_denoise_t tirt_denoise_var_t;
 int tirt_denoise_var(tirt_ctx *ctx, const tirt_denoise_var_t *params);
 int tirt_denoise_var_device(tirt_ctx *ctx, const float *hdr, const float *aov, const float *mom, float *out, int W, int H, const tirt_denoise_var_t *params, void *stream);
+
+/* Pixel set and adaptive sampling of the path tracer (csrc/tirt_adaptive.hip; no reference counterpart; PT_RGB only).  A pixel set is a list of linear pixel
+ * indices p = i*H + j of this context's own tiles, strictly ascending in the context's LOCAL order (the order in which the device walks its tiles: tile by
+ * tile, and inside a tile of whole 8-column groups in 8 x 8 pixel blocks -- tirt_film_create; for every other tiling ascending p).  While one is installed,
+ * tirt_pt_rgb_render renders the n listed pixels instead of all of this context's: path s of a batch is (frame, list entry), and the camera jitter, the random
+ * numbers, the film, the feature buffers and the sample moments all see the listed pixel.  The random numbers are counter-based on (seed, pixel, frame,
+ * dimension) and the film's weight is 1 / (frame + 1), so a pixel rendered at frames 0 .. m-1 and left alone since holds, bit for bit, the film, feature and
+ * moment records of a dense render of m frames at that pixel.  Pixels outside the set are neither read nor written.  An empty set (n == 0) makes
+ * tirt_pt_rgb_render a no-op that returns TIRT_OK.  The camera rays of such batches all go through the ordinary traversal (option "primary_beams" does not apply).
+ * tirt_pt_spec_render, tirt_bdpt_rgb_render, tirt_bdpt_spec_render and tirt_debug_render return TIRT_ERR_ARG while a set is installed (tirt_pixel_set_clear first).
+ * Every call below waits for pending work (as tirt_moments_enable does): a list is never rewritten under a batch that reads it.
+ * tirt_pixel_set_upload: installs the caller's list pixels[0 .. n).  Refused with TIRT_ERR_ARG, before anything is written and with an installed set left as it
+ *   was: no film; n < 0; n > 0 with a null list; n == 0 with a non-null list; an entry outside [0, W*H), in another rank's tile, equal to its predecessor or
+ *   before it in local order.  n == 0 with a null list installs the empty set.
+ * tirt_pixel_set_from_moments: makes the list on the device from the moment records (needs tirt_moments_enable) and installs it; *count (may be NULL) = its
+ *   length.  Pixel k of the local order, record (n, mean, M2, bad), all f32 in this order, t2 = threshold * threshold (host), a comparison with a NaN false:
+ *     total = n + bad;  nn = n * (n - 1);  v = (M2.r / nn + M2.g / nn) + M2.b / nn;  Y = ((mean.r + mean.g) + mean.b) / 3      (tirt_moments_converged's v and Y)
+ *     listed  <=>  total < max_samples  and  ( total < min_samples  or  n < 2  or  v > t2 * (Y * Y) )
+ *   in ascending local order (an order-preserving compaction: the result does not depend on the scheduling).  TIRT_ERR_ARG, nothing changed: no film, no moment
+ *   records, min_samples < 1, max_samples < min_samples, threshold negative or not finite.  One host wait, for the count.
+ * tirt_pixel_set_clear: removes the set (no set installed: nothing to do).  tirt_film_create removes it too; tirt_film_clear leaves it alone.
+ * tirt_pixel_set_download: *n = the length of the installed list, or -1 when no set is installed; the list into out[0 .. *n) when out is not NULL.
+ *   TIRT_ERR_ARG, nothing written: n NULL, cap < 0, or out not NULL and cap < the length.
+ * tirt_pt_rgb_render_adaptive: frames from frame_begin on, each pass on the pixels still listed by tirt_pixel_set_from_moments' rule:
+ *     start = the total every pixel of this context has (see below);  done = 0
+ *     repeat:  select(threshold, min_samples, max_samples);  stop if nothing is listed;  F = min(pass_frames, max_samples - start - done);
+ *              render frames frame_begin + done .. + F - 1 on the list;  done += F;  stop if start + done == max_samples
+ *   It needs the moment records and NO set installed; it owns the set meanwhile and leaves none installed, on errors too.  The film must be a dense prefix
+ *   the caller rendered itself: every pixel of this context with total == frame_begin (start = frame_begin), or all its moment records zero (start = 0);
+ *   checked on the device in the first pass, TIRT_ERR_ARG and nothing rendered otherwise.  TIRT_ERR_ARG also for select's refusals and pass_frames < 1.
+ *   out (may be NULL): passes rendered, pixel-samples rendered, pixels that reached max_samples in this call, frames of the longest-running pixel (done).
+ *   With tile_count > 1 every rank runs its own loop on its own pixels; the ranks' films and records still sum to the single context's.
+ *   Waits for every pass's count; a pixel's per-pixel sample count is n + bad of its moment record.
+ * The limit: a pixel is stopped on its OWN variance estimate, which is biased towards stopping early where a few samples happen to agree (a pixel whose first
+ * min_samples paths all miss a small light is "converged" and black).  min_samples is the only guard; no neighbour-aware or hierarchical criterion is offered. */
+typedef struct { float threshold; int32_t min_samples, max_samples, pass_frames; } tirt_adaptive_t;
+typedef struct { int64_t passes, pixel_samples, pixels_at_max, frames; } tirt_adaptive_result_t;
+int tirt_pixel_set_upload(tirt_ctx *ctx, const int32_t *pixels, int64_t n);
+int tirt_pixel_set_from_moments(tirt_ctx *ctx, float threshold, int min_samples, int max_samples, int64_t *count);
+int tirt_pixel_set_clear(tirt_ctx *ctx);
+int tirt_pixel_set_download(tirt_ctx *ctx, int32_t *out, int64_t cap, int64_t *n);
+int tirt_pt_rgb_render_adaptive(tirt_ctx *ctx, uint32_t frame_begin, uint32_t seed, int max_depth, int stack_size, int flags,
+                                const tirt_adaptive_t *a, tirt_adaptive_result_t *out);
 
 /* Scene.closet_hit / closet_hit_shadow on a batch of rays (Scene.py:702-744, 671-699).  The default (ordered) traversal returns the
  * reference's hit bit for bit for every ray but the in-plane rays named under "traversal_tree" above; rays that start more than 8

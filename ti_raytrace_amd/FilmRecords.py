@@ -58,7 +58,7 @@ class SampleMoments:
 
     def _moment_fields(self):
         """the sample moments as fields (moments=True; include/tirt.h, tirt_moments_enable): samples [W, H] (n), mean [W, H, 3], variance [W, H, 3]
-        (the sample variance M2 / (n - 1), 0 where n < 2) and bad [W, H] (samples skipped because they were not finite).  Each to_numpy() is one
+        (the sample variance M2 / (n - 1), 0 where n < 2), bad [W, H] (samples skipped because they were not finite) and sample_count [W, H] (samples + bad).  Each to_numpy() is one
         download of the whole record."""
         def variance():
             m = self.moments_to_numpy()
@@ -69,6 +69,11 @@ class SampleMoments:
         self.mean = DeviceField("mean", self.scene, lambda: np.ascontiguousarray(self.moments_to_numpy()[:, :, _native.MOM_MEAN:_native.MOM_MEAN + 3]))
         self.variance = DeviceField("variance", self.scene, variance)
         self.bad = DeviceField("bad", self.scene, lambda: np.ascontiguousarray(self.moments_to_numpy()[:, :, _native.MOM_BAD]))
+        # how many frames a pixel was rendered at: samples + bad (after render_adaptive it differs from pixel to pixel)
+        def sample_count():
+            m = self.moments_to_numpy()
+            return np.ascontiguousarray(m[:, :, _native.MOM_N] + m[:, :, _native.MOM_BAD])
+        self.sample_count = DeviceField("sample_count", self.scene, sample_count)
 
     def moments_to_numpy(self):
         """[W, H, 8] float32: n, mean3, M2 3, bad"""

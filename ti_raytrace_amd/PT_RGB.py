@@ -61,3 +61,24 @@ class PathTrace(FilmRecords, SampleMoments):
         """Extension: ``count`` consecutive frames starting at ``cam.frame`` in one call
         (identical film to calling render()/update_frame() ``count`` times)."""
         self.scene.ctx.pt_rgb_render(self.cam.frame, count, self.seed, MAX_DEPTH, self.stack_size, self.flags)
+
+    def pixel_set(self, pixels):
+        """Extension: restrict render() / render_frames() to the pixels of `pixels` -- linear indices i * imgSizeY + j of this context's tiles, strictly
+        ascending in the context's local order (include/tirt.h, tirt_pixel_set_upload; a single tile of any size that is not whole 8-column groups walks
+        them in ascending index) -- or, with None, render every pixel again.  Pixels outside the set are neither read nor written."""
+        if pixels is None:
+            self.scene.ctx.pixel_set_clear()
+        else:
+            self.scene.ctx.pixel_set_upload(pixels)
+
+    def render_adaptive(self, threshold, max_samples, min_samples=4, pass_frames=4):
+        """Extension (moments=True): passes of `pass_frames` frames starting at ``cam.frame`` -- the caller has rendered exactly the frames before it, or
+        none --, each pass only on the pixels whose standard error still exceeds `threshold` x their mean level (converged()'s rule) or that have fewer
+        than `min_samples` samples, until no pixel is left or all have `max_samples` (include/tirt.h, tirt_pt_rgb_render_adaptive).  Every pixel holds,
+        bit for bit, the film of a dense render of its own sample_count frames.  Returns {"passes", "pixel_samples", "pixels_at_max", "frames"};
+        ``cam.frame`` is not advanced.  A pixel is stopped on its own variance estimate, which is biased towards stopping early where few samples
+        happen to agree: min_samples is the only guard."""
+        if not self.moments:
+            raise ValueError("render_adaptive needs the sample moments: PT_RGB.PathTrace(..., moments=True)")
+        return self.scene.ctx.pt_rgb_render_adaptive(self.cam.frame, self.seed, threshold, max_samples, min_samples, pass_frames,
+                                                     MAX_DEPTH, self.stack_size, self.flags)

@@ -189,6 +189,26 @@ SIGNATURES.update({
     "tirt_denoise_var_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(DenoiseParams), _vp]),
 })
 
+
+
+class AdaptiveParams(C.Structure):
+    """tirt_adaptive_t (include/tirt.h)"""
+    _fields_ = [("threshold", C.c_float), ("min_samples", C.c_int32), ("max_samples", C.c_int32), ("pass_frames", C.c_int32)]
+
+
+class AdaptiveResult(C.Structure):
+    """tirt_adaptive_result_t (include/tirt.h)"""
+    _fields_ = [("passes", C.c_int64), ("pixel_samples", C.c_int64), ("pixels_at_max", C.c_int64), ("frames", C.c_int64)]
+
+
+SIGNATURES.update({
+    "tirt_pixel_set_upload": (C.c_int, [_vp, _vp, C.c_int64]),
+    "tirt_pixel_set_from_moments": (C.c_int, [_vp, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "tirt_pixel_set_clear": (C.c_int, [_vp]),
+    "tirt_pixel_set_download": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    "tirt_pt_rgb_render_adaptive": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveResult)]),
+})
+
 _lib = None
 
 
@@ -500,6 +520,39 @@ class Context:
         out = (C.c_uint64 * 3)()
         check(lib().tirt_moments_converged(self.handle, float(threshold), out))
         return int(out[0]), int(out[1]), int(out[2])
+
+    def pixel_set_upload(self, pixels):
+        """tirt_pixel_set_upload: restrict the next pt_rgb_render calls to these linear pixel indices (p = i*H + j) of this context's tiles, strictly
+        ascending in the context's local order (include/tirt.h); an empty list installs the empty set"""
+        px = np.ascontiguousarray(pixels, np.int32).reshape(-1)
+        check(lib().tirt_pixel_set_upload(self.handle, _ptr(px) if px.size else None, px.size))
+
+    def pixel_set_from_moments(self, threshold, min_samples, max_samples):
+        """tirt_pixel_set_from_moments: the set of the pixels still noisy by the moment records, made on the device; returns its length"""
+        count = C.c_int64(0)
+        check(lib().tirt_pixel_set_from_moments(self.handle, float(threshold), int(min_samples), int(max_samples), C.byref(count)))
+        return int(count.value)
+
+    def pixel_set_clear(self):
+        check(lib().tirt_pixel_set_clear(self.handle))
+
+    def pixel_set_download(self):
+        """tirt_pixel_set_download: the installed list as int32 [n], or None when no set is installed"""
+        n = C.c_int64(0)
+        check(lib().tirt_pixel_set_download(self.handle, None, 0, C.byref(n)))
+        if n.value < 0:
+            return None
+        out = np.zeros(max(int(n.value), 1), np.int32)
+        check(lib().tirt_pixel_set_download(self.handle, _ptr(out), out.size, C.byref(n)))
+        return out[:int(n.value)].copy()
+
+    def pt_rgb_render_adaptive(self, frame_begin, seed, threshold, max_samples, min_samples=4, pass_frames=4, max_depth=15, stack_size=64, flags=0):
+        """tirt_pt_rgb_render_adaptive: pass after pass of pass_frames frames from frame_begin on, each on the pixels the moment records still call
+        noisy, until none is left or every pixel has max_samples; returns {passes, pixel_samples, pixels_at_max, frames}"""
+        prm = AdaptiveParams(float(threshold), int(min_samples), int(max_samples), int(pass_frames))
+        res = AdaptiveResult()
+        check(lib().tirt_pt_rgb_render_adaptive(self.handle, int(frame_begin), int(seed), int(max_depth), int(stack_size), int(flags), C.byref(prm), C.byref(res)))
+        return {"passes": int(res.passes), "pixel_samples": int(res.pixel_samples), "pixels_at_max": int(res.pixels_at_max), "frames": int(res.frames)}
 
     def denoise_var(self, levels=5, sigma_c=DENOISE_VAR_DEFAULTS["sigma_c"], sigma_n=0.3, sigma_z=0.1):
         """tirt_denoise_var: the variance-guided a-trous filter over the context's film, feature buffers and sample moments, into the buffer

@@ -16,12 +16,14 @@ typedef float f4s__ __attribute__((ext_vector_type(4)));
 
 // One thread per local pixel k.  The slot's hit record (one 16-byte load) and direction words are streams, read once: non-temporal.  The loads of
 // frame f + 1 are issued before the dependent gathers of frame f (primitive row -> vertex rows / material row) are waited for.
+// LIST: the batch's local pixels are a pixel set's list (mapped_pixel, tirt_internal.h).
+template <bool LIST>
 __global__ __launch_bounds__(256) void k_aov(SceneView sc, v3 eye, TileMap tm, int P, int F, uint32_t frame_begin, const float4 *hit,
                                              const float *dx, const float *dy, const float *dz, float *aov)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= P) return;
-    const int p = local_to_pixel(tm, k);
+    const int p = mapped_pixel<LIST>(tm, k);
     float4 *const px = (float4 *)(aov + (size_t)p * TIRT_AOV_WORDS);
     const float4 lo = px[0], hi = px[1];
     float a0 = lo.x, a1 = lo.y, a2 = lo.z, a3 = lo.w, a4 = hi.x, a5 = hi.y, a6 = hi.z, a7 = hi.w;
@@ -67,7 +69,7 @@ int aov_launch(tirt_ctx *c, Lane &L, const TileMap &tm, int P, int F, uint32_t f
     if (c->last_aov) TIRT_HIP(hipStreamWaitEvent(L.stream, c->last_aov, 0));
     v3 eye; eye.x = c->cam.eye[0]; eye.y = c->cam.eye[1]; eye.z = c->cam.eye[2];
     const int B = 256;
-    hipLaunchKernelGGL(k_aov, dim3((P + B - 1) / B), dim3(B), 0, L.stream, scene_view(c), eye, tm, P, F, frame_begin, L.ps.hit,
+    hipLaunchKernelGGL(tm.pixels ? k_aov<true> : k_aov<false>, dim3((P + B - 1) / B), dim3(B), 0, L.stream, scene_view(c), eye, tm, P, F, frame_begin, L.ps.hit,
                        L.ps.st[0].dx, L.ps.st[0].dy, L.ps.st[0].dz, c->aov.as<float>());
     TIRT_HIP(hipEventRecord(L.aov_done, L.stream));
     c->last_aov = L.aov_done;

@@ -479,7 +479,7 @@ void tirt_destroy(tirt_ctx *c)
     drain_render_events(c);
     DevBuf *bufs[] = {&c->vertex, &c->primitive, &c->material, &c->shape, &c->light, &c->env, &c->mat_lrgb, &c->shade_rec, &c->light_rec, &c->morton_unsorted, &c->keys_a,
                       &c->keys_b, &c->vals_a, &c->vals_b, &c->hist, &c->morton_sorted, &c->bvh_node, &c->compact, &c->parent,
-                      &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb, &c->aov, &c->mom, &c->mom_cnt, &c->dn_mem, &c->dn_out,
+                      &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb, &c->aov, &c->mom, &c->mom_cnt, &c->pixset, &c->pixset_tmp, &c->dn_mem, &c->dn_out,
                       &c->counters_mem, &c->spill, &c->trace_stage, &c->debug_mem, &c->query_mem, &c->dyn_mem, &c->dev_counters, &c->bdpt_px, &c->timeline, &c->pvb_set[0].count, &c->pvb_set[0].cand, &c->pvb_set[0].bound, &c->pvb_set[1].count, &c->pvb_set[1].cand, &c->pvb_set[1].bound, &c->pvb_stat, &c->pvb_tmp};
     for (DevBuf *b : bufs) b->release();
     for (auto &bl : c->bd) {
@@ -874,6 +874,10 @@ int tirt_film_create(tirt_ctx *c, int W, int H, int tile_rank, int tile_count, i
     TIRT_REQUIRE(W >= 1 && H >= 1 && (long long)W * H < (1ll << 30), "tirt_film_create: bad size");
     TIRT_REQUIRE(tile_count >= 1 && tile_rank >= 0 && tile_rank < tile_count && tile_size >= 1, "tirt_film_create: bad tiling");
     const long NP = (long)W * H;
+    if (c->pixset_n >= 0) {                      // a pixel set is a list of THIS film's pixels: it goes with the film
+        if (sync_all(c)) return TIRT_ERR_HIP;
+        c->pixset_n = -1;
+    }
     for (const FilmRecord &r : RECORDS)          // the records the render writes belong to the film: a new film starts without them
         if (r.order != ORDER_NONE && (c->*r.buf).p) {
             if (sync_all(c)) return TIRT_ERR_HIP;
@@ -936,6 +940,57 @@ int tirt_moments_converged(tirt_ctx *c, float threshold, uint64_t out[3])
     return moments_converged(c, threshold * threshold, out);
 }
 
+// ---- pixel set and adaptive sampling (tirt_adaptive.hip).  Every entry point waits for pending work before it touches the list ----
+#define NO_PIXEL_SET(c, fn)                                                        \
+    TIRT_REQUIRE((c)->pixset_n < 0, std::string(fn) + ": a pixel set is installed (it restricts tirt_pt_rgb_render alone): tirt_pixel_set_clear first")
+
+static int select_args(tirt_ctx *c, const char *fn, float threshold, int min_samples, int max_samples)
+{
+    TIRT_REQUIRE(c->hdr.p, std::string(fn) + ": film not created");
+    TIRT_REQUIRE(c->mom.p, std::string(fn) + ": moment buffers not enabled (tirt_moments_enable)");
+    TIRT_REQUIRE(threshold >= 0.0f && threshold < __builtin_inff(), std::string(fn) + ": threshold must be finite and >= 0");
+    TIRT_REQUIRE(min_samples >= 1, std::string(fn) + ": min_samples must be >= 1");
+    TIRT_REQUIRE(max_samples >= min_samples && max_samples <= (1 << 24), std::string(fn) + ": max_samples must be >= min_samples (and <= 2^24, where the f32 count stops being exact)");
+    return TIRT_OK;
+}
+
+int tirt_pixel_set_upload(tirt_ctx *c, const int32_t *pixels, int64_t n) { CTX(c); return pixel_set_upload(c, pixels, n); }
+int tirt_pixel_set_clear(tirt_ctx *c) { CTX(c); return pixel_set_clear(c); }
+
+int tirt_pixel_set_from_moments(tirt_ctx *c, float threshold, int min_samples, int max_samples, int64_t *count)
+{
+    CTX(c);
+    if (int rc = select_args(c, "tirt_pixel_set_from_moments", threshold, min_samples, max_samples)) return rc;
+    return pixel_set_select(c, threshold * threshold, min_samples, max_samples, -1, count, nullptr);
+}
+
+int tirt_pixel_set_download(tirt_ctx *c, int32_t *out, int64_t cap, int64_t *n)
+{
+    CTX(c);
+    TIRT_REQUIRE(n && cap >= 0, "tirt_pixel_set_download: null count or negative capacity");
+    TIRT_REQUIRE(!out || cap >= c->pixset_n, "tirt_pixel_set_download: the list has " + std::to_string(c->pixset_n) + " entries, more than the capacity");
+    *n = c->pixset_n < 0 ? -1 : (int64_t)c->pixset_n;
+    if (out && c->pixset_n > 0) {
+        if (sync_all(c)) return TIRT_ERR_HIP;
+        TIRT_HIP(hipMemcpy(out, c->pixset.p, sizeof(int32_t) * (size_t)c->pixset_n, hipMemcpyDeviceToHost));
+    }
+    return TIRT_OK;
+}
+
+int tirt_pt_rgb_render_adaptive(tirt_ctx *c, uint32_t frame_begin, uint32_t seed, int max_depth, int stack_size, int flags, const tirt_adaptive_t *a,
+                                tirt_adaptive_result_t *out)
+{
+    CTX(c);
+    TIRT_REQUIRE(a, "tirt_pt_rgb_render_adaptive: null parameters");
+    NO_PIXEL_SET(c, "tirt_pt_rgb_render_adaptive");
+    if (int rc = select_args(c, "tirt_pt_rgb_render_adaptive", a->threshold, a->min_samples, a->max_samples)) return rc;
+    TIRT_REQUIRE(a->pass_frames >= 1, "tirt_pt_rgb_render_adaptive: pass_frames must be >= 1");
+    TIRT_REQUIRE(c->built && c->cam_set, "tirt_pt_rgb_render_adaptive: LBVH not built or camera not set");
+    TIRT_REQUIRE(max_depth >= 1 && max_depth <= 4096, "tirt_pt_rgb_render_adaptive: bad max_depth");
+    TIRT_REQUIRE((uint64_t)frame_begin + (uint64_t)a->max_samples < ((uint64_t)1 << 31), "tirt_pt_rgb_render_adaptive: frame_begin + max_samples must stay below 2^31");
+    return render_adaptive(c, frame_begin, seed, max_depth, stack_size, flags, a, out);
+}
+
 // ---- denoiser (tirt_denoise.hip): the film routes wait for the last film update (which covers the moments) and the last k_aov ----
 static int denoise_entry(tirt_ctx *c, const tirt_denoise_t *params, bool var)
 {
@@ -974,7 +1029,8 @@ static int submit_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uin
     TIRT_REQUIRE(c->cam_set, "render: camera not set");
     TIRT_REQUIRE(c->hdr.p && c->npix_local >= 0, "render: film not created");
     TIRT_REQUIRE(frame_count >= 0 && max_depth >= 1 && max_depth <= 4096, "render: bad frame_count/max_depth");
-    if (frame_count == 0) return TIRT_OK;
+    if (spectral) NO_PIXEL_SET(c, "tirt_pt_spec_render");
+    if (frame_count == 0 || c->pixset_n == 0) return TIRT_OK;      // (an empty pixel set: nothing to render)
     auto &p = c->pend;
     if (p.valid && p.begin + (uint32_t)p.count == frame_begin && p.seed == seed && p.max_depth == max_depth &&
         p.stack_size == stack_size && p.flags == flags && p.spectral == spectral) {
@@ -984,7 +1040,8 @@ static int submit_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uin
         p.valid = true; p.begin = frame_begin; p.count = frame_count; p.seed = seed;
         p.max_depth = max_depth; p.stack_size = stack_size; p.flags = flags; p.spectral = spectral;
     }
-    if ((size_t)p.count * (size_t)(c->npix_local > 0 ? c->npix_local : 1) >= effective_merge_paths(c)) return flush_pending(c);
+    const int P = render_pixels(c);
+    if ((size_t)p.count * (size_t)(P > 0 ? P : 1) >= effective_merge_paths(c)) return flush_pending(c);
     return TIRT_OK;
 }
 int tirt_pt_rgb_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed, int max_depth, int stack_size, int flags)
@@ -1002,11 +1059,13 @@ int tirt_pt_spec_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint
 int tirt_bdpt_rgb_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed)
 {
     CTX(c);
+    NO_PIXEL_SET(c, "tirt_bdpt_rgb_render");
     return bdpt_render(c, frame_begin, frame_count, seed);
 }
 int tirt_bdpt_spec_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed)
 {
     CTX(c);
+    NO_PIXEL_SET(c, "tirt_bdpt_spec_render");
     TIRT_REQUIRE(c->spec_set && c->spec_dev.p, "tirt_bdpt_spec_render: spectral tables not uploaded (tirt_spectral_upload)");
     return bdpt_render(c, frame_begin, frame_count, seed, true);
 }
@@ -1014,6 +1073,7 @@ int tirt_bdpt_spec_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, ui
 int tirt_debug_render(tirt_ctx *c, uint32_t frame, uint32_t seed, int mode, int stack_size, int flags)
 {
     CTX(c);
+    NO_PIXEL_SET(c, "tirt_debug_render");
     AFTER_RENDER(c);                 // the view overwrites pixels the lanes' last film update may still be writing
     return debug_render(c, frame, seed, mode, stack_size, flags);
 }

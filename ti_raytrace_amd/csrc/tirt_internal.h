@@ -224,7 +224,9 @@ struct PathState {
 // `F` > 0: the paths of a wavefront batch of F frames are numbered pixel-block major -- 64-path chunk c = (block of 64 local pixels c / F, frame c % F)
 // -- instead of frame major (F == 0: path s = frame * P + pixel): every contiguous stretch of the ray queue then belongs to ONE region of the film in
 // all its frames, which is what lets k_trace hand each XCD (its own L2) the rays of one part of the scene (slices_contiguous).  Needs P % 64 == 0.
-struct TileMap { int tile_rank, tile_count, tile_size, H, blocked, F; };
+// `pixels` (a pixel set, tirt_adaptive.hip; nullptr otherwise): the local pixels of the batch are the P entries of this list instead of the tiles' -- read by the
+// LIST instantiations of the kernels alone (mapped_pixel<true>), which never look at the tile fields; the others never look at it.
+struct TileMap { int tile_rank, tile_count, tile_size, H, blocked, F; const int *pixels; };
 TD void slot_to_frame_pixel(const TileMap &m, int P, int slot, int &f, int &k)
 {
     if (m.F > 0) { const int c = slot >> 6, kb = c / m.F; f = c - kb * m.F; k = (kb << 6) | (slot & 63); }
@@ -245,6 +247,10 @@ TD int local_to_pixel(const TileMap &m, int k)
     }
     return (lt * m.tile_count + m.tile_rank) * m.tile_size + within;
 }
+
+// Local pixel k of a batch -> linear pixel index: through the pixel set's list (LIST) or the tiles.  A template parameter and not a test of m.pixels, so
+// that the kernels of a dense render hold no trace of the list (k_shade above all: DESIGN.md section 6 has its register counts before and after).
+template <bool LIST> TD int mapped_pixel(const TileMap &m, int k) { if constexpr (LIST) return m.pixels[k]; else return local_to_pixel(m, k); }
 
 struct DevCounters {          // lives in device memory; accumulated by the kernels
     unsigned long long rays_closest, rays_shadow, box_closest, leaf_closest, box_shadow, leaf_shadow;
@@ -323,6 +329,9 @@ struct tirt_ctx {
     tirt::DevBuf aov;                             // tirt_aov_enable: TIRT_AOV_WORDS f32 per pixel of the film (p == nullptr: disabled)
     hipEvent_t last_aov = nullptr;                // aov_done of the most recent batch (any lane): the next k_aov and the records' main-stream consumers wait for it
     tirt::DevBuf mom, mom_cnt;                    // tirt_moments_enable: TIRT_MOM_WORDS f32 per pixel of the film (p == nullptr: disabled), updated behind k_film and covered by last_film; the three counters of tirt_moments_converged
+    // pixel set (tirt_adaptive.hip): the list tirt_pt_rgb_render is restricted to, 4 * npix_local bytes, linear pixel indices in ascending local order
+    // (pixset_n < 0: no set installed); the block counts of k_pixel_select and its three result words
+    tirt::DevBuf pixset, pixset_tmp; long pixset_n = -1;
     tirt::DevBuf dn_mem, dn_out;                  // denoiser (tirt_denoise.hip): 60 B of scratch per pixel; the filtered film W*H*3 f32 (p == nullptr: no tirt_denoise yet).  Both go with the film
 
     // wavefront state
@@ -465,6 +474,15 @@ struct TraceJob {
 int trace_rays(tirt_ctx *c, const TraceJob &j);
 int trace_rays_prepare(tirt_ctx *c, int lane);      // allocates what trace_rays needs on that lane at bdpt_stack_size (stack spill, fetch cursors)
 int debug_render(tirt_ctx *c, uint32_t frame, uint32_t seed, int mode, int stack_size, int flags);      // tirt_debug.hip
+// the local pixels a PT_RGB batch renders and the map to them: the installed pixel set's, else the tiles' (F is set per batch)
+inline int render_pixels(const tirt_ctx *c) { return (int)(c->pixset_n >= 0 ? c->pixset_n : c->npix_local); }
+inline TileMap render_tile_map(const tirt_ctx *c)
+{ return TileMap{c->tile_rank, c->tile_count, c->tile_size, c->H, c->tile_blocked, 0, c->pixset_n >= 0 ? c->pixset.as<int>() : nullptr}; }
+// tirt_adaptive.hip: the pixel set and the adaptive driver (the entry points of tirt_api.hip have flushed and checked what needs no device)
+int pixel_set_upload(tirt_ctx *c, const int32_t *pixels, int64_t n);
+int pixel_set_select(tirt_ctx *c, float t2, int min_samples, int max_samples, long expect_total, int64_t *count, int64_t check[2]);
+int pixel_set_clear(tirt_ctx *c);
+int render_adaptive(tirt_ctx *c, uint32_t frame_begin, uint32_t seed, int max_depth, int stack_size, int flags, const tirt_adaptive_t *a, tirt_adaptive_result_t *out);
 int aov_launch(tirt_ctx *c, Lane &L, const TileMap &tm, int P, int F, uint32_t frame_begin);      // tirt_aov.hip: k_aov over a batch's bounce-0 hits
 int moments_launch(tirt_ctx *c, Lane &L, const TileMap &tm, int P, int F);      // tirt_moments.hip: k_moments over a batch's final radiances
 int moments_converged(tirt_ctx *c, float t2, uint64_t out[3]);

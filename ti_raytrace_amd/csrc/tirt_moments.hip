@@ -26,11 +26,13 @@ TD bool mom_finite(float x) { return __builtin_fabsf(x) < __builtin_inff(); }   
 
 // One thread per local pixel k.  The three sample words of a slot are streams, read once: non-temporal.  The loads of frame f + 1 are issued
 // before frame f's dependent arithmetic (three divisions on one chain per channel).
+// LIST: the batch's local pixels are a pixel set's list (mapped_pixel, tirt_internal.h).
+template <bool LIST>
 __global__ __launch_bounds__(256) void k_moments(const float *fr, const float *fg, const float *fb, TileMap tm, int P, int F, float *mom)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= P) return;
-    const int p = local_to_pixel(tm, k);
+    const int p = mapped_pixel<LIST>(tm, k);
     float4 *const px = (float4 *)(mom + (size_t)p * TIRT_MOM_WORDS);
     const float4 lo = px[0], hi = px[1];
     float n = lo.x, m0 = lo.y, m1 = lo.z, m2 = lo.w, q0 = hi.x, q1 = hi.y, q2 = hi.z, bad = hi.w;
@@ -60,7 +62,7 @@ __global__ __launch_bounds__(256) void k_moments(const float *fr, const float *f
 int moments_launch(tirt_ctx *c, Lane &L, const TileMap &tm, int P, int F)
 {
     const int B = 256;
-    hipLaunchKernelGGL(k_moments, dim3((P + B - 1) / B), dim3(B), 0, L.stream, (const float *)L.ps.fr, (const float *)L.ps.fg, (const float *)L.ps.fb,
+    hipLaunchKernelGGL(tm.pixels ? k_moments<true> : k_moments<false>, dim3((P + B - 1) / B), dim3(B), 0, L.stream, (const float *)L.ps.fr, (const float *)L.ps.fg, (const float *)L.ps.fb,
                        tm, P, F, c->mom.as<float>());
     return TIRT_OK;
 }

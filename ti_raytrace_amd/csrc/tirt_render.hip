@@ -90,12 +90,13 @@ struct ShadeStep {
 };
 // FEAT: the feature word (tirt_device.h, SF_*) this copy is compiled for -- a superset of the scene's.  A scene without glass, without a lit environment, with one
 // kind of emitter compiles none of the code of the others; what is left performs the same operations on the same operands in the same order.
-template <unsigned FEAT>
+// LIST: the batch's local pixels are a pixel set's list (mapped_pixel, tirt_internal.h) -- the pixel is the random numbers' and nothing else here.
+template <unsigned FEAT, bool LIST = false>
 TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame_begin, uint32_t seed, int bounce, int last_bounce, int slot,
                    const v3 origin, const v3 direction, const float4 hrec, v3 throughout, v3 &radiance, float brdf_pdf, int perfect_spec, ShadeStep &s)
 {
     int f, k; slot_to_frame_pixel(tm, P, slot, f, k);
-    const uint32_t pixel = (uint32_t)local_to_pixel(tm, k);
+    const uint32_t pixel = (uint32_t)mapped_pixel<LIST>(tm, k);
     const uint32_t frame = frame_begin + (uint32_t)f;
     const uint32_t dim0 = TM_DIM_BOUNCE0 + TM_DIMS_PER_BOUNCE * (uint32_t)bounce;
     const float t = hrec.x;
@@ -848,6 +849,7 @@ int trace_rays(tirt_ctx *c, const TraceJob &j)
 // ---------------------------------------------------------------------------------------------
 // Wavefront PT_RGB
 // ---------------------------------------------------------------------------------------------
+template <bool LIST>
 __global__ void k_generate(PathSoA ps, CameraView cam, TileMap tm, int P, int S, uint32_t frame_begin, uint32_t seed,
                            DevCounters *ctr)
 {
@@ -857,7 +859,7 @@ __global__ void k_generate(PathSoA ps, CameraView cam, TileMap tm, int P, int S,
     int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= S) return;
     int f, k; slot_to_frame_pixel(tm, P, s, f, k);
-    int p = local_to_pixel(tm, k);
+    int p = mapped_pixel<LIST>(tm, k);
     int i = p / tm.H, j = p - i * tm.H;
     uint32_t frame = frame_begin + (uint32_t)f;
     float jx = 0.0f, jy = 0.0f;
@@ -894,7 +896,7 @@ typedef const __attribute__((address_space(4))) ShadeArgs *cold_shade_t;
 #define SH_COLD(ca) cold_shade_t ca = (cold_shade_t)__builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(ca))
 #define SH_LD(x) __builtin_nontemporal_load(&(x))
 #define SH_ST(x, v) __builtin_nontemporal_store((v), &(x))
-template <unsigned FEAT, int MIN_WAVES>
+template <unsigned FEAT, int MIN_WAVES, bool LIST = false>
 __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_shade(ShadeArgs paths_in_kernarg_segment, SceneView sc, TileMap tm, int P,
                                                    uint32_t frame_begin, uint32_t seed, int bounce, int last_bounce,
                                                    const int *count_ptr, int count_fixed, unsigned long long *append_ctr,
@@ -935,7 +937,7 @@ __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_shade(ShadeArgs paths_i
             float brdf_pdf = first ? 1.0f : SH_LD(c_pdf[q]);
             int perfect_spec = first ? 1 : (int)(SH_LD(c_flags[q]) & 1u);
             ShadeStep ss;
-            shade_path<FEAT>(sc, tm, P, frame_begin, seed, bounce, last_bounce, slot, origin, direction, hrec, throughout, radiance, brdf_pdf, perfect_spec, ss);
+            shade_path<FEAT, LIST>(sc, tm, P, frame_begin, seed, bounce, last_bounce, slot, origin, direction, hrec, throughout, radiance, brdf_pdf, perfect_spec, ss);
             want_next = ss.want_next; want_shadow = ss.want_shadow; if (ss.shaded) n_shaded++;
             next_o = ss.next_o; next_d = ss.next_d; next_thr = ss.next_thr; next_pdf = ss.next_pdf; next_spec = ss.next_spec;
             sh_o = ss.sh_o; sh_d = ss.sh_d; sh_c = ss.sh_c; sh_expect = ss.sh_expect; sh_dist = ss.sh_dist;
@@ -1002,11 +1004,12 @@ __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_shade(ShadeArgs paths_i
 }
 
 // integrator/PT_RGB.py:134-136, frames applied in order
+template <bool LIST>
 __global__ void k_film(PathState ps, TileMap tm, int P, int F, uint32_t frame_begin, float *hdr)
 {
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= P) return;
-    int p = local_to_pixel(tm, k);
+    int p = mapped_pixel<LIST>(tm, k);
     float *px = hdr + (size_t)p * 3;
     float r = px[0], g = px[1], b = px[2];
     for (int f = 0; f < F; f++) {
@@ -1217,15 +1220,16 @@ __global__ __launch_bounds__(SH_BLOCK, 4) void k_shade_spec(ShadeArgs paths_in_k
 // scene when the option "shade_specialize" is 0. ----
 typedef void (*shade_fn_t)(ShadeArgs, SceneView, TileMap, int, uint32_t, uint32_t, int, int, const int *, int, unsigned long long *, DevCounters *, v3);
 typedef void (*shade_spec_fn_t)(ShadeArgs, SceneView, SpecView, TileMap, int, uint32_t, uint32_t, int, int, const int *, int, unsigned long long *, DevCounters *, v3);
-struct ShadeInst { unsigned feat; shade_fn_t fn; };
+struct ShadeInst { unsigned feat; shade_fn_t fn, fn_list; };      // fn_list: the same kernel for the batches of a pixel set (LIST)
 struct ShadeSpecInst { unsigned feat; shade_spec_fn_t fn; };
 constexpr unsigned SF_I_SPHERE = SF_LIGHT_SPHERE;                                   // Disney, sphere lights, black environment: the synthetic headline scene
 constexpr unsigned SF_I_MESH = SF_LIGHT_TRI;                                        // Disney, mesh lights, black environment: Cornell box, Veach
 // (Built and left out: SF_GLASS | SF_ENV | SF_LIGHT_SPHERE for Teapot and the gallery spheres -- 3 509 VALU against the generic 3 872, but 12 bytes of scratch at
 // the 96-VGPR limit where the generic kernel has none; those scenes stay on the generic kernel.)
 static const ShadeInst SHADE_INST[] = {
-    {SF_I_SPHERE, k_shade<SF_I_SPHERE, SH_MIN_WAVES_NARROW>}, {SF_I_MESH, k_shade<SF_I_MESH, SH_MIN_WAVES_NARROW>},
-    {SF_ALL, k_shade<SF_ALL, SH_MIN_WAVES>}};
+    {SF_I_SPHERE, k_shade<SF_I_SPHERE, SH_MIN_WAVES_NARROW>, k_shade<SF_I_SPHERE, SH_MIN_WAVES_NARROW, true>},
+    {SF_I_MESH, k_shade<SF_I_MESH, SH_MIN_WAVES_NARROW>, k_shade<SF_I_MESH, SH_MIN_WAVES_NARROW, true>},
+    {SF_ALL, k_shade<SF_ALL, SH_MIN_WAVES>, k_shade<SF_ALL, SH_MIN_WAVES, true>}};
 static const ShadeSpecInst SHADE_SPEC_INST[] = {
     {SF_I_SPHERE, k_shade_spec<SF_I_SPHERE>}, {SF_I_MESH, k_shade_spec<SF_I_MESH>}, {SF_ALL, k_shade_spec<SF_ALL>}};
 template <class T, size_t N>
@@ -1367,10 +1371,13 @@ int pt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed,
     TIRT_REQUIRE(c->cam_set, "tirt_pt_rgb_render: camera not set");
     TIRT_REQUIRE(c->hdr.p && c->npix_local >= 0, "tirt_pt_rgb_render: film not created");
     TIRT_REQUIRE(frame_count >= 0 && max_depth >= 1 && max_depth <= 4096, "tirt_pt_rgb_render: bad frame_count/max_depth");
-    if (frame_count == 0 || c->npix_local == 0) return TIRT_OK;
+    // a pixel set (tirt_adaptive.hip): the batches' local pixels are its list -- P of them, planned and numbered as any P, through the LIST kernels
+    const bool list = c->pixset_n >= 0;
+    TIRT_REQUIRE(!(list && spec), "tirt_pt_spec_render: a pixel set is installed (PT_RGB only): tirt_pixel_set_clear first");
+    if (frame_count == 0 || c->npix_local == 0 || c->pixset_n == 0) return TIRT_OK;
     if (ensure_counters(c)) return TIRT_ERR_HIP;
     if (ensure_shade_records(c)) return TIRT_ERR_HIP;          // on the main stream: the lanes wait for ev_main below
-    const int P = (int)c->npix_local;
+    const int P = render_pixels(c);
     // frames per batch: up to batch_paths pixel-samples in flight (the per-bounce launches of a
     // batch end in a latency-bound tail of a few long rays, so bigger batches amortise it)
     const size_t batch_paths = effective_batch_paths(c), merge_paths = effective_merge_paths(c);
@@ -1386,12 +1393,13 @@ int pt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed,
         { int parts = c->split_lone < c->n_lanes ? c->split_lone : c->n_lanes; if (parts > frame_count) parts = frame_count; FB = (frame_count + parts - 1) / parts; }
     const SceneView sv = scene_view(c);
     const BvhView bv = bvh_view(c);
-    TileMap tm = {c->tile_rank, c->tile_count, c->tile_size, c->H, c->tile_blocked, 0};
+    TileMap tm = render_tile_map(c);
     DevCounters *ctr = c->dev_counters.as<DevCounters>();
     const int B = 256;
     // the pixels' candidate lists for the camera rays (tirt_pvb.hip), made on the main stream when the scene, the camera or the film changed since
+    // (indexed by the tiles' local pixel: the camera rays of a pixel set's batches all go through k_trace)
     bool beams_ready = false;
-    if (c->primary_beams && FB >= c->primary_beams_min_frames && !(flags & TIRT_TRAVERSE_EXHAUSTIVE)) {
+    if (!list && c->primary_beams && FB >= c->primary_beams_min_frames && !(flags & TIRT_TRAVERSE_EXHAUSTIVE)) {
         if (int rc = pvb_prepare(c)) return rc;
         beams_ready = c->pvb_valid;
     }
@@ -1449,7 +1457,7 @@ int pt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed,
         };
 
         TIRT_HIP(hipMemsetAsync(L.counters_mem.p, 0, lane_counter_bytes(max_depth), st));
-        hipLaunchKernelGGL(k_generate, dim3((S + B - 1) / B), dim3(B), 0, st, L.ps.st[0], c->cam, tm, P, S, f0, seed, ctr);
+        hipLaunchKernelGGL(list ? k_generate<true> : k_generate<false>, dim3((S + B - 1) / B), dim3(B), 0, st, L.ps.st[0], c->cam, tm, P, S, f0, seed, ctr);
         // a batch that will run next to the previous one (still in flight on another lane) uses fewer persistent
         // blocks, so that both traversal kernels find LDS on the CUs; a batch submitted to an idle GPU takes them all
         bool busy = false;
@@ -1463,7 +1471,7 @@ int pt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed,
         const int sh_cap = two_big ? 2 * c->sh_grid : c->sh_grid;
         int grid_shade = (S + SH_BLOCK - 1) / SH_BLOCK; if (grid_shade > sh_cap) grid_shade = sh_cap;
         v3 eye_v; eye_v.x = c->cam.eye[0]; eye_v.y = c->cam.eye[1]; eye_v.z = c->cam.eye[2];
-        const shade_fn_t shade_fn = pick_shade_inst(SHADE_INST, c).fn;
+        const shade_fn_t shade_fn = list ? pick_shade_inst(SHADE_INST, c).fn_list : pick_shade_inst(SHADE_INST, c).fn;
         const shade_spec_fn_t shade_spec_fn = pick_shade_inst(SHADE_SPEC_INST, c).fn;
         for (int b = 0; b < max_depth; b++) {
             const PathSoA &in = L.ps.st[b & 1], &out = L.ps.st[(b + 1) & 1];
@@ -1535,7 +1543,7 @@ int pt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed,
         // the running mean is order dependent: this batch's film update follows the previous batch's
         if (c->last_film) TIRT_HIP(hipStreamWaitEvent(st, c->last_film, 0));
         if (spec) hipLaunchKernelGGL(k_film_spec, dim3((P + B - 1) / B), dim3(B), 0, st, L.ps, L.ps.fw, *spec, tm, P, F, f0, seed, c->hdr.as<float>());
-        else hipLaunchKernelGGL(k_film, dim3((P + B - 1) / B), dim3(B), 0, st, L.ps, tm, P, F, f0, c->hdr.as<float>());
+        else hipLaunchKernelGGL(list ? k_film<true> : k_film<false>, dim3((P + B - 1) / B), dim3(B), 0, st, L.ps, tm, P, F, f0, c->hdr.as<float>());
         if (c->mom.p && !spec) { if (int rc = moments_launch(c, L, tm, P, F)) return rc; }      // the sample moments read fr / fg / fb too: behind the same wait, before film_done (tirt_moments.hip)
         TIRT_HIP(hipEventRecord(L.film_done, st));
         L.film_recorded = true;
