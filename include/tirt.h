@@ -371,6 +371,71 @@ typedef tirt_denoise_t tirt_denoise_var_t;
 int tirt_denoise_var(tirt_ctx *ctx, const tirt_denoise_var_t *params);
 int tirt_denoise_var_device(tirt_ctx *ctx, const float *hdr, const float *aov, const float *mom, float *out, int W, int H, const tirt_denoise_var_t *params, void *stream);
 
+/* Temporal accumulation (csrc/tirt_temporal.hip; no reference counterpart; PT_RGB only): the temporal part of SVGF (Schied et al. 2017) beside
+ * tirt_denoise_var.  The film and the moment records of the PREVIOUS view are reprojected through the current view's first-hit surface point, rejected
+ * where the surfaces disagree, and merged with the current film as sample statistics; the result has the layout of hdr and of the moment records, so
+ * tirt_denoise_var consumes it unchanged, with the current feature records as its guides.  The world must have stood still between the views (no motion
+ * vectors), and first-hit guides know nothing of what is seen through glass or in a mirror.
+ * The random numbers are counter-based on (seed, pixel, frame, dimension) and a cleared film restarts at frame 0: two views rendered with the same seed
+ * draw the same numbers per pixel, so a caller who accumulates views must change the seed per view (seed + view, say).
+ * One thread per current pixel p = i*H + j; all f32, one rounding per operation in the order written (tests/temporal_expected.py restates it; the device
+ * gives its bits).  "c" = current, "h" = history; a comparison with a NaN is false:
+ *   1. surface point: record words n_c[3], z, al of aov_c.  al > 0 fails (every camera ray missed): NO HISTORY.  zc = z / al;
+ *      D = camera_ray_direction(cur, i, j, 0, 0) (the pixel centre: x = ((float)i + 0 - cx) / fx, ..., the view_inv rows summed left to right, normalised
+ *      by 1 / sqrt);  X = eye_cur + D * zc per component
+ *   2. into the previous view: q.r = ((V[r][0] * X.x + V[r][1] * X.y) + V[r][2] * X.z) + V[r][3], r = 0..2, V = prev.view.  q.z < 0 fails: NO HISTORY.
+ *      nz = -q.z;  fi = (q.x / nz) * fx_prev + cx_prev;  fj = (q.y / nz) * fy_prev + cy_prev  (an integer fi is a pixel centre).
+ *      -1 < fi < W and -1 < fj < H fails (no tap would lie inside the film): NO HISTORY.  i0 = floor(fi), j0 = floor(fj), wi = fi - i0, wj = fj - j0;
+ *      e = X - eye_prev;  d_exp = sqrt((e.x*e.x + e.y*e.y) + e.z*e.z), correctly rounded
+ *   3. taps t = (i0 + a, j0 + b), a = 0..1 outer, b = 0..1 inner, weight k = (a ? wi : 1 - wi) * (b ? wj : 1 - wj).  A tap counts only if it lies inside
+ *      the film, al_h > 0, dn = ((n_c.x-n_h.x)^2 + (n_c.y-n_h.y)^2) + (n_c.z-n_h.z)^2 <= sigma_n * sigma_n (host product),
+ *      |d_exp - z_h / al_h| <= sigma_z * d_exp, its count n_h > 0, and its hdr_h[3] and its mean and M2 words are all finite.  Counted taps, in tap order:
+ *      sw += k;  s_hdr[3] += hdr_h * k;  s_mom[8] += mom_h * k (all eight words: n, mean, M2 and bad interpolate linearly, which keeps M2 / n where the
+ *      neighbourhood is uniform).  sw >= 1e-3 fails: NO HISTORY.  Otherwise hdr_h = s_hdr / sw and (n_h, mean_h, M2_h, bad_h) = s_mom / sw
+ *   4. cap: if n_h > max_history:  f = max_history / n_h;  n_h = max_history;  M2_h = M2_h * f;  bad_h = bad_h * f  (mean_h and hdr_h stay: old samples
+ *      fade once the history is full -- an exponential window written as a sample count)
+ *   5. merge (the pairwise update of Chan et al.), with the current record (n_c, mean_c, M2_c, bad_c):  N = n_h + n_c.
+ *      n_c == 0: mom_o = the history's eight words, hdr_o = hdr_h.  Else N == 0: NO HISTORY.  Else  w = n_c / N  and per channel
+ *        delta = mean_c - mean_h;  mean_o = mean_h + delta * w;  M2_o = (M2_h + M2_c) + (delta * delta) * (n_h * w);  hdr_o = hdr_h + (hdr_c - hdr_h) * w
+ *      and n_o = N, bad_o = bad_h + bad_c.  In both cases a pixel whose own hdr_c has a channel that is not finite keeps hdr_c in all three channels
+ *      (the film's NaN pixels stay, as in tirt_denoise); its moment words still merge: they only ever held the finite samples
+ *   6. NO HISTORY: hdr_o = hdr_c and mom_o = mom_c, bit for bit.
+ * tirt_temporal_t: max_history, sigma_n, sigma_z finite and > 0, else TIRT_ERR_ARG; NULL means {TIRT_TEMPORAL_MAX_HISTORY, 0.3, 0.1}
+ *   (profiles/temporal_quality.txt has the sweep behind them).
+ * tirt_temporal_camera_t: what tirt_camera_set takes.  Of `cur` the kernel reads view_inv, eye and the intrinsics, of `prev` view, eye and the intrinsics.
+ * tirt_temporal_device: on caller-owned device arrays (e.g. torch tensors) in the layouts of tirt_film_export_device, tirt_aov_export_device and
+ *   tirt_moments_export_device: current hdr_c, aov_c, mom_c, history hdr_h, aov_h, mom_h (the output of an earlier call with the aov_c of that call, or a
+ *   plain film with its records), out hdr_o [W,H,3], mom_o [W,H,TIRT_MOM_WORDS]; the guide record of the output is aov_c itself.  The feature and moment
+ *   arrays must be 16-byte aligned; no output may overlap an input or the other output.  Needs no film and no scene.  Ordering on `stream`, the pointer
+ *   checks and the refusal of a capturing stream are tirt_denoise_device's.
+ * The context's own history (tile_count == 1; a rank's film is partial: reduce the films and the records, then tirt_temporal_device):
+ * tirt_temporal_enable: needs a film with enabled feature buffers and moment records; on != 0 allocates two history sets of (3 + 8 + 8) f32 per pixel
+ *   and marks the history empty, on == 0 frees them.  tirt_film_create disables; tirt_aov_enable(0) and tirt_moments_enable(0) return TIRT_ERR_ARG while
+ *   it is on.  Waits for pending work.
+ * tirt_temporal_accumulate: on the main stream after the last film and record update; asynchronous.  Current = the context's hdr, feature and moment
+ *   records and the camera set now; history = the result of the previous call with the feature records and the camera of that call.  With an empty
+ *   history the result is the current film and records copied.  The result, a copy of the feature records and the camera become the new history.
+ *   hdr, rgb_film, the records, the denoised film and an installed pixel set are only read; an adaptively sampled film merges pixel by pixel with its
+ *   own n.  Nothing is added to the render path.  TIRT_ERR_ARG when not enabled or without a camera.
+ * tirt_temporal_reset: empties the history.  tirt_scene_upload, tirt_vertex_update and tirt_vertex_update_device empty it too (the reprojection assumes
+ *   the world stood still); tirt_film_clear leaves it alone -- carrying samples across a cleared film is what this is for.
+ * tirt_temporal_download / tirt_temporal_export_device: the accumulated hdr [W*H*3] and moment records [W*H*TIRT_MOM_WORDS]; either pointer may be NULL.
+ *   TIRT_ERR_ARG while the history is empty.  They wait for the copy.
+ * tirt_temporal_denoise_var: tirt_denoise_var's filter over the accumulated hdr and moments with the history's feature records (those of the last
+ *   accumulated view), into the buffer tirt_denoise_download / tirt_denoise_export_device read.  tirt_denoise and tirt_denoise_var are unchanged. */
+#define TIRT_TEMPORAL_MAX_HISTORY 32.0f
+typedef struct { float max_history, sigma_n, sigma_z; } tirt_temporal_t;
+typedef struct { float view[16], view_inv[16], eye[3], fx, fy, cx, cy; } tirt_temporal_camera_t;
+int tirt_temporal_device(tirt_ctx *ctx, const float *hdr_c, const float *aov_c, const float *mom_c, const float *hdr_h, const float *aov_h, const float *mom_h,
+                         const tirt_temporal_camera_t *cur, const tirt_temporal_camera_t *prev, float *hdr_o, float *mom_o, int W, int H,
+                         const tirt_temporal_t *params, void *stream);
+int tirt_temporal_enable(tirt_ctx *ctx, int on);
+int tirt_temporal_accumulate(tirt_ctx *ctx, const tirt_temporal_t *params);
+int tirt_temporal_reset(tirt_ctx *ctx);
+int tirt_temporal_download(tirt_ctx *ctx, float *hdr_out, float *mom_out);
+int tirt_temporal_export_device(tirt_ctx *ctx, void *hdr_dst, void *mom_dst);
+int tirt_temporal_denoise_var(tirt_ctx *ctx, const tirt_denoise_var_t *params);
+
 /* Pixel set and adaptive sampling of the path tracer (csrc/tirt_adaptive.hip; no reference counterpart; PT_RGB only).  A pixel set is a list of linear pixel
  * indices p = i*H + j of this context's own tiles, strictly ascending in the context's LOCAL order (the order in which the device walks its tiles: tile by
  * tile, and inside a tile of whole 8-column groups in 8 x 8 pixel blocks -- tirt_film_create; for every other tiling ascending p).  While one is installed,

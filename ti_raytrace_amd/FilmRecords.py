@@ -1,6 +1,6 @@
 """What the path tracers share beside the film (no reference counterpart): the feature buffers, the denoised film and, for PT_RGB alone, the
-sample moments -- as fields, numpy arrays and torch tensors.  ``PT_RGB.PathTrace`` and ``PT_Spec.PathTrace`` inherit ``FilmRecords``;
-``PT_RGB.PathTrace`` also ``SampleMoments``.  A class that inherits them has ``scene``, ``imgSizeX``, ``imgSizeY`` and the flags ``aov`` / ``moments``.
+sample moments and the temporal accumulation -- as fields, numpy arrays and torch tensors.  ``PT_RGB.PathTrace`` and ``PT_Spec.PathTrace`` inherit
+``FilmRecords``; ``PT_RGB.PathTrace`` also ``SampleMoments`` and ``TemporalAccumulation``.  A class that inherits them has ``scene``, ``imgSizeX``, ``imgSizeY`` and the flags ``aov`` / ``moments``.
 """
 import numpy as np
 
@@ -96,3 +96,59 @@ class SampleMoments:
         if not (self.aov and self.moments):
             raise ValueError("denoise_var needs the feature buffers and the sample moments: PT_RGB.PathTrace(..., aov=True, moments=True)")
         self.scene.ctx.denoise_var(levels, sigma_c, sigma_n, sigma_z)
+
+
+class TemporalAccumulation:
+    """PT_RGB only (temporal=True, which needs aov=True and moments=True): the film and the moments of the views rendered so far, carried across camera
+    moves (include/tirt.h, tirt_temporal_enable).  The loop of an interactive viewer:
+
+        move the camera;  scene.ctx.film_clear(), cam.frame = 0;  integrator.seed = s + view;  render_frames(k)
+        temporal_accumulate();  denoise_temporal();  denoised_to_torch()
+
+    The seed must change per view: a cleared film restarts at frame 0, and the random numbers depend on (seed, pixel, frame) alone."""
+
+    def _temporal_fields(self):
+        """accumulated [W, H, 3]: the accumulated film; accumulated_samples [W, H]: the samples behind each of its pixels (n of its moment record)"""
+        ctx = lambda: self.scene.ctx
+        self.accumulated = DeviceField("accumulated", self.scene, lambda: ctx().temporal_download(self.imgSizeX, self.imgSizeY, want_mom=False)[0])
+        self.accumulated_samples = DeviceField("accumulated_samples", self.scene, lambda: np.ascontiguousarray(
+            ctx().temporal_download(self.imgSizeX, self.imgSizeY, want_hdr=False)[1][:, :, _native.MOM_N]))
+
+    def _need_temporal(self, what):
+        if not self.temporal:
+            raise ValueError("%s needs the temporal history: PT_RGB.PathTrace(..., aov=True, moments=True, temporal=True)" % what)
+
+    def temporal_accumulate(self, max_history=32.0, sigma_n=0.3, sigma_z=0.1):
+        """Reproject the history into the camera as it stands and merge it with hdr and the sample moments (tirt_temporal_accumulate); the result
+        is the new history.  hdr, rgb_film and the records are only read.  Asynchronous."""
+        self._need_temporal("temporal_accumulate")
+        self.scene.ctx.temporal_accumulate(max_history, sigma_n, sigma_z)
+
+    def temporal_reset(self):
+        """Empty the history (a geometry update or a scene upload does so too; film_clear does not)."""
+        self._need_temporal("temporal_reset")
+        self.scene.ctx.temporal_reset()
+
+    def denoise_temporal(self, levels=5, sigma_c=3.0, sigma_n=0.3, sigma_z=0.1):
+        """denoise_var()'s filter over the accumulated film and moments, guided by the last accumulated view's feature buffers, into `denoised`
+        (tirt_temporal_denoise_var).  Asynchronous."""
+        self._need_temporal("denoise_temporal")
+        self.scene.ctx.temporal_denoise_var(levels, sigma_c, sigma_n, sigma_z)
+
+    def temporal_to_numpy(self):
+        """(hdr [W, H, 3], moments [W, H, 8]) float32 of the accumulated film"""
+        self._need_temporal("temporal_to_numpy")
+        return self.scene.ctx.temporal_download(self.imgSizeX, self.imgSizeY)
+
+    def temporal_to_torch(self):
+        """The same as float32 tensors on the context's device, filled device to device (tirt_temporal_export_device)."""
+        self._need_temporal("temporal_to_torch")
+        try:
+            import torch
+        except ImportError as exc:
+            raise ImportError("temporal_to_torch needs PyTorch (ROCm build); temporal_to_numpy and the C-ABI tirt_temporal_download work without it") from exc
+        dev = torch.device("cuda", self.scene.ctx.device_id)
+        hdr = torch.empty((self.imgSizeX, self.imgSizeY, 3), dtype=torch.float32, device=dev)
+        mom = torch.empty((self.imgSizeX, self.imgSizeY, _native.MOM_WORDS), dtype=torch.float32, device=dev)
+        self.scene.ctx.temporal_export_device(hdr.data_ptr(), mom.data_ptr())
+        return hdr, mom

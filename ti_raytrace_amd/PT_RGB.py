@@ -5,7 +5,7 @@ pixel at frame ``cam.frame``, running-mean film, :44-136).  On the device it is 
 per-pixel megakernel but a wavefront pipeline (generate -> trace -> shade -> shadow-trace ->
 film) over struct-of-arrays path queues in HBM -- see DESIGN.md.
 """
-from .FilmRecords import FilmRecords, SampleMoments
+from .FilmRecords import FilmRecords, SampleMoments, TemporalAccumulation
 from .Scene import DeviceField
 
 MAX_DEPTH = 15           # integrator/PT_RGB.py:21
@@ -18,9 +18,9 @@ def default_tile_size(H):
     return 8 * H if (H % 8 == 0 and 4096 <= 8 * H <= 16384) else 4096
 
 
-class PathTrace(FilmRecords, SampleMoments):
+class PathTrace(FilmRecords, SampleMoments, TemporalAccumulation):
     def __init__(self, imgSizeX, imgSizeY, cam, scene, stack_size,
-                 seed=1, tile_rank=0, tile_count=1, tile_size=None, flags=0, moments=False, aov=False):
+                 seed=1, tile_rank=0, tile_count=1, tile_size=None, flags=0, temporal=False, moments=False, aov=False):
         self.imgSizeX = imgSizeX
         self.imgSizeY = imgSizeY
         self.cam = cam
@@ -39,6 +39,11 @@ class PathTrace(FilmRecords, SampleMoments):
         # extension: per-pixel sample moments (count, mean, sum of squared deviations) of the pixel-samples the film averages
         self.moments = moments
         self._moment_fields()
+        # extension: the film and the moments accumulated across camera moves
+        if temporal and not (aov and moments):
+            raise ValueError("temporal=True needs the feature buffers and the sample moments: PT_RGB.PathTrace(..., aov=True, moments=True, temporal=True)")
+        self.temporal = temporal
+        self._temporal_fields()
         # extension: the film after denoise(), a buffer of its own beside hdr
         self.denoised = DeviceField("denoised", scene, self._denoised_download)
 
@@ -52,6 +57,8 @@ class PathTrace(FilmRecords, SampleMoments):
             self.scene.ctx.aov_enable(True)
         if self.moments:
             self.scene.ctx.moments_enable(True)
+        if self.temporal:
+            self.scene.ctx.temporal_enable(True)
 
     def render(self):
         """One frame at ``cam.frame`` (the caller advances it with ``cam.update_frame()``)."""

@@ -18,6 +18,6 @@ if _os.environ.get("TIRT_NO_ENV_TUNING", "0") in ("", "0"):
 
 from . import SceneData, UtilsFunc, Texture, Camera, LBvh, Scene, PT_RGB, BDPT_RGB, Debug, Example  # noqa: F401
 from .RayQuery import RayQuery, RayHits  # noqa: F401  (torch is imported when a RayQuery is made)
-from .Denoise import denoise, denoise_var  # noqa: F401  (torch is imported when they are called)
+from .Denoise import denoise, denoise_var, temporal_accumulate  # noqa: F401  (torch is imported when they are called)
 
-__all__ = ["SceneData", "UtilsFunc", "Texture", "Camera", "LBvh", "Scene", "PT_RGB", "BDPT_RGB", "Debug", "Example", "RayQuery", "RayHits", "denoise", "denoise_var"]
+__all__ = ["SceneData", "UtilsFunc", "Texture", "Camera", "LBvh", "Scene", "PT_RGB", "BDPT_RGB", "Debug", "Example", "RayQuery", "RayHits", "denoise", "denoise_var", "temporal_accumulate"]

@@ -209,6 +209,48 @@ SIGNATURES.update({
     "tirt_pt_rgb_render_adaptive": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveResult)]),
 })
 
+class TemporalParams(C.Structure):
+    """tirt_temporal_t (include/tirt.h)"""
+    _fields_ = [("max_history", C.c_float), ("sigma_n", C.c_float), ("sigma_z", C.c_float)]
+
+
+class TemporalCamera(C.Structure):
+    """tirt_temporal_camera_t (include/tirt.h): what tirt_camera_set takes"""
+    _fields_ = [("view", C.c_float * 16), ("view_inv", C.c_float * 16), ("eye", C.c_float * 3),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float)]
+
+
+TEMPORAL_DEFAULTS = {"max_history": 32.0, "sigma_n": 0.3, "sigma_z": 0.1}      # what a NULL tirt_temporal_t means (TIRT_TEMPORAL_MAX_HISTORY)
+
+SIGNATURES.update({
+    "tirt_temporal_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(TemporalCamera), C.POINTER(TemporalCamera), _vp, _vp, C.c_int, C.c_int,
+                                       C.POINTER(TemporalParams), _vp]),
+    "tirt_temporal_enable": (C.c_int, [_vp, C.c_int]),
+    "tirt_temporal_accumulate": (C.c_int, [_vp, C.POINTER(TemporalParams)]),
+    "tirt_temporal_reset": (C.c_int, [_vp]),
+    "tirt_temporal_download": (C.c_int, [_vp, _vp, _vp]),
+    "tirt_temporal_export_device": (C.c_int, [_vp, _vp, _vp]),
+    "tirt_temporal_denoise_var": (C.c_int, [_vp, C.POINTER(DenoiseParams)]),
+})
+
+
+def temporal_camera(cam):
+    """a TemporalCamera from a Camera (or anything with view_np, view_inv_np, eye_np, fx, fy, cx, cy) or from the tuple Camera pushes to tirt_camera_set:
+    (view, view_inv, eye, fx, fy, cx, cy)"""
+    if isinstance(cam, TemporalCamera):
+        return cam
+    if hasattr(cam, "view_np"):
+        cam = (cam.view_np[0], cam.view_inv_np[0], cam.eye_np[0], cam.fx, cam.fy, cam.cx, cam.cy)
+    view, view_inv, eye, fx, fy, cx, cy = cam
+    view, view_inv, eye = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (view, view_inv, eye))
+    if view.size != 16 or view_inv.size != 16 or eye.size != 3:
+        raise ValueError("a camera is (view[4, 4], view_inv[4, 4], eye[3], fx, fy, cx, cy)")
+    out = TemporalCamera()
+    out.view[:] = view.tolist(); out.view_inv[:] = view_inv.tolist(); out.eye[:] = eye.tolist()
+    out.fx, out.fy, out.cx, out.cy = float(fx), float(fy), float(cx), float(cy)
+    return out
+
+
 _lib = None
 
 
@@ -562,6 +604,40 @@ class Context:
     def denoise_var_device(self, hdr, aov, mom, out, W, H, levels=5, sigma_c=DENOISE_VAR_DEFAULTS["sigma_c"], sigma_n=0.3, sigma_z=0.1, stream=0):
         """tirt_denoise_var_device on device memory: as denoise_device, with mom [W, H, 8] the sample moments"""
         self._denoise_device("tirt_denoise_var_device", (hdr, aov, mom, out), W, H, levels, sigma_c, sigma_n, sigma_z, stream)
+
+    def temporal_enable(self, on=True):
+        """tirt_temporal_enable: the context's history of accumulated views (include/tirt.h), empty; needs the feature buffers and the sample moments"""
+        check(lib().tirt_temporal_enable(self.handle, 1 if on else 0))
+
+    def temporal_accumulate(self, max_history=TEMPORAL_DEFAULTS["max_history"], sigma_n=0.3, sigma_z=0.1):
+        """tirt_temporal_accumulate: the history reprojected into the camera set now and merged with the film and its moment records; asynchronous"""
+        check(lib().tirt_temporal_accumulate(self.handle, C.byref(TemporalParams(float(max_history), float(sigma_n), float(sigma_z)))))
+
+    def temporal_reset(self):
+        check(lib().tirt_temporal_reset(self.handle))
+
+    def temporal_download(self, W, H, want_hdr=True, want_mom=True):
+        """(hdr [W, H, 3], moments [W, H, MOM_WORDS]) float32 of the accumulated film; None for what is not wanted"""
+        hdr = np.zeros((W, H, 3), np.float32) if want_hdr else None
+        mom = np.zeros((W, H, MOM_WORDS), np.float32) if want_mom else None
+        check(lib().tirt_temporal_download(self.handle, _ptr(hdr), _ptr(mom)))
+        return hdr, mom
+
+    def temporal_export_device(self, hdr_ptr, mom_ptr):
+        """tirt_temporal_export_device: integer device addresses, 0 for what is not wanted"""
+        check(lib().tirt_temporal_export_device(self.handle, _vp(int(hdr_ptr) or None), _vp(int(mom_ptr) or None)))
+
+    def temporal_denoise_var(self, levels=5, sigma_c=DENOISE_VAR_DEFAULTS["sigma_c"], sigma_n=0.3, sigma_z=0.1):
+        """tirt_temporal_denoise_var: tirt_denoise_var's filter over the accumulated film, into the buffer denoise_download reads; asynchronous"""
+        check(lib().tirt_temporal_denoise_var(self.handle, C.byref(self._denoise_params(levels, sigma_c, sigma_n, sigma_z))))
+
+    def temporal_device(self, hdr_c, aov_c, mom_c, hdr_h, aov_h, mom_h, cam, cam_prev, hdr_o, mom_o, W, H,
+                        max_history=TEMPORAL_DEFAULTS["max_history"], sigma_n=0.3, sigma_z=0.1, stream=0):
+        """tirt_temporal_device on device memory: the arrays are integer device addresses, the cameras what temporal_camera takes, `stream` a
+        hipStream_t handle (0 = the null stream).  Asynchronous; ti_raytrace_amd.temporal_accumulate is the torch front end."""
+        check(lib().tirt_temporal_device(self.handle, *[_vp(int(a) or None) for a in (hdr_c, aov_c, mom_c, hdr_h, aov_h, mom_h)],
+                                         C.byref(temporal_camera(cam)), C.byref(temporal_camera(cam_prev)), _vp(int(hdr_o) or None), _vp(int(mom_o) or None),
+                                         int(W), int(H), C.byref(TemporalParams(float(max_history), float(sigma_n), float(sigma_z))), _vp(int(stream) or None)))
 
     def denoise(self, levels=5, sigma_c=1.0, sigma_n=0.3, sigma_z=0.1):
         """tirt_denoise: the a-trous filter over the context's film and feature buffers into a buffer of its own (include/tirt.h); asynchronous"""

@@ -211,11 +211,18 @@ int denoise_film(tirt_ctx *c, const tirt_denoise_t *prm, bool var)
     TIRT_REQUIRE(c->aov.p, fn + ": feature buffers not enabled (tirt_aov_enable)");
     if (var) TIRT_REQUIRE(c->mom.p, fn + ": moment buffers not enabled (tirt_moments_enable)");
     TIRT_REQUIRE(c->tile_count == 1, fn + ": tile_count > 1 -- this context's film is partial: reduce the films and the records, then " + fn + "_device");
-    if (int rc = denoise_check_params(fn, prm, var ? DNV_DEFAULTS : DN_DEFAULTS)) return rc;
+    return denoise_into_film_buffer(c, fn, c->hdr.as<float>(), c->aov.as<float>(), var ? c->mom.as<float>() : nullptr, prm);
+}
+
+// Context-owned arrays of the film's size (the film and its records, or the temporal history of tirt_temporal.hip) into the context's own buffer;
+// mom != nullptr selects the variance-guided mode.
+int denoise_into_film_buffer(tirt_ctx *c, const std::string &fn, const float *hdr, const float *aov, const float *mom, const tirt_denoise_t *prm)
+{
+    if (int rc = denoise_check_params(fn, prm, mom ? DNV_DEFAULTS : DN_DEFAULTS)) return rc;
     const size_t NP = (size_t)c->W * c->H;
     if (int rc = denoise_prepare(c, NP)) return rc;
     if (c->dn_out.ensure(sizeof(float) * 3 * NP)) return TIRT_ERR_HIP;      // (allocates once per film: tirt_film_create drops it)
-    return denoise_launch(c, c->hdr.as<float>(), c->aov.as<float>(), var ? c->mom.as<float>() : nullptr, c->dn_out.as<float>(), c->W, c->H, *prm);
+    return denoise_launch(c, hdr, aov, mom, c->dn_out.as<float>(), c->W, c->H, *prm);
 }
 
 // tirt_denoise_device / tirt_denoise_var_device.  `var` and not `mom` says which: a null mom in the variance-guided mode is refused like any other.

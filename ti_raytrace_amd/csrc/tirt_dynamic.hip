@@ -184,6 +184,7 @@ static int dyn_apply(tirt_ctx *c, const char *fn, int64_t first, int64_t count, 
     TIRT_HIP(hipMemcpyAsync(hb, box, sizeof(hb), hipMemcpyDeviceToHost, st));
     // from here on the old build describes geometry that is gone, whatever the copy and the sync below return
     c->built = false; c->built_sah = 0; c->shade_rec_valid = false; c->light_rec_valid = false; c->pvb_valid = false;
+    c->tp_valid = false;                       // the temporal history (tirt_temporal.hip) has no motion vectors: it assumes the world stood still
     refresh_shade_features(c);                 // (with the tables it selects kernels for; moving vertices changes no bit of it)
     TIRT_HIP(hipStreamSynchronize(st));
     TIRT_HIP(hipGetLastError());

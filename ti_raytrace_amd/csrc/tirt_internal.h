@@ -332,6 +332,9 @@ struct tirt_ctx {
     // pixel set (tirt_adaptive.hip): the list tirt_pt_rgb_render is restricted to, 4 * npix_local bytes, linear pixel indices in ascending local order
     // (pixset_n < 0: no set installed); the block counts of k_pixel_select and its three result words
     tirt::DevBuf pixset, pixset_tmp; long pixset_n = -1;
+    // temporal accumulation (tirt_temporal.hip): two history sets of {aov 8, mom 8, hdr 3} f32 per pixel (p == nullptr: disabled); tp_cur = the set that holds
+    // the last result, with the camera it was rendered from; tp_valid = false: the history is empty.  Goes with the film
+    tirt::DevBuf tp_mem; int tp_cur = 0; bool tp_valid = false; tirt_temporal_camera_t tp_cam = {};
     tirt::DevBuf dn_mem, dn_out;                  // denoiser (tirt_denoise.hip): 60 B of scratch per pixel; the filtered film W*H*3 f32 (p == nullptr: no tirt_denoise yet).  Both go with the film
 
     // wavefront state
@@ -496,6 +499,15 @@ int query_begin(tirt_ctx *c, void *stream);
 int query_end(tirt_ctx *c, void *stream);
 int denoise_film(tirt_ctx *c, const tirt_denoise_t *prm, bool var);      // tirt_denoise.hip; var: the variance-guided mode
 int denoise_device(tirt_ctx *c, bool var, const float *hdr, const float *aov, const float *mom, float *out, int W, int H, const tirt_denoise_t *prm, void *stream);
+int denoise_into_film_buffer(tirt_ctx *c, const std::string &fn, const float *hdr, const float *aov, const float *mom, const tirt_denoise_t *prm);
+// tirt_temporal.hip
+int temporal_device(tirt_ctx *c, const float *hdr_c, const float *aov_c, const float *mom_c, const float *hdr_h, const float *aov_h, const float *mom_h,
+                    const tirt_temporal_camera_t *cur, const tirt_temporal_camera_t *prev, float *hdr_o, float *mom_o, int W, int H,
+                    const tirt_temporal_t *prm, void *stream);
+int temporal_enable(tirt_ctx *c, int on);
+int temporal_accumulate(tirt_ctx *c, const tirt_temporal_t *prm);
+int temporal_copy_out(tirt_ctx *c, const char *fn, void *hdr_dst, void *mom_dst, hipMemcpyKind kind);
+int temporal_denoise_var(tirt_ctx *c, const tirt_denoise_var_t *prm);
 int trace_host(tirt_ctx *c, const float *rays, int nr, int stack_size, int flags, bool shadow, float *out_f, int32_t *out_prim, int32_t *counts);      // tirt_trace_closest / tirt_trace_shadow
 int pvb_prepare(tirt_ctx *c);                          // tirt_pvb.hip
 void pvb_launch_cand(tirt_ctx *c, hipStream_t st, const BvhView &bv, const float *dx, const float *dy, const float *dz, const TileMap &tm, int P, int S,
