@@ -374,8 +374,8 @@ int tirt_denoise_var_device(tirt_ctx *ctx, const float *hdr, const float *aov, c
 /* Temporal accumulation (csrc/tirt_temporal.hip; no reference counterpart; PT_RGB only): the temporal part of SVGF (Schied et al. 2017) beside
  * tirt_denoise_var.  The film and the moment records of the PREVIOUS view are reprojected through the current view's first-hit surface point, rejected
  * where the surfaces disagree, and merged with the current film as sample statistics; the result has the layout of hdr and of the moment records, so
- * tirt_denoise_var consumes it unchanged, with the current feature records as its guides.  The world must have stood still between the views (no motion
- * vectors), and first-hit guides know nothing of what is seen through glass or in a mirror.
+ * tirt_denoise_var consumes it unchanged, with the current feature records as its guides.  The world must have stood still between the views (unless
+ * the motion records of the next section are on), and first-hit guides know nothing of what is seen through glass or in a mirror.
  * The random numbers are counter-based on (seed, pixel, frame, dimension) and a cleared film restarts at frame 0: two views rendered with the same seed
  * draw the same numbers per pixel, so a caller who accumulates views must change the seed per view (seed + view, say).
  * One thread per current pixel p = i*H + j; all f32, one rounding per operation in the order written (tests/temporal_expected.py restates it; the device
@@ -418,7 +418,7 @@ int tirt_denoise_var_device(tirt_ctx *ctx, const float *hdr, const float *aov, c
  *   hdr, rgb_film, the records, the denoised film and an installed pixel set are only read; an adaptively sampled film merges pixel by pixel with its
  *   own n.  Nothing is added to the render path.  TIRT_ERR_ARG when not enabled or without a camera.
  * tirt_temporal_reset: empties the history.  tirt_scene_upload, tirt_vertex_update and tirt_vertex_update_device empty it too (the reprojection assumes
- *   the world stood still); tirt_film_clear leaves it alone -- carrying samples across a cleared film is what this is for.
+ *   the world stood still; with tirt_motion_enable the two updates keep it); tirt_film_clear leaves it alone -- carrying samples across a cleared film is what this is for.
  * tirt_temporal_download / tirt_temporal_export_device: the accumulated hdr [W*H*3] and moment records [W*H*TIRT_MOM_WORDS]; either pointer may be NULL.
  *   TIRT_ERR_ARG while the history is empty.  They wait for the copy.
  * tirt_temporal_denoise_var: tirt_denoise_var's filter over the accumulated hdr and moments with the history's feature records (those of the last
@@ -435,6 +435,43 @@ int tirt_temporal_reset(tirt_ctx *ctx);
 int tirt_temporal_download(tirt_ctx *ctx, float *hdr_out, float *mom_out);
 int tirt_temporal_export_device(tirt_ctx *ctx, void *hdr_dst, void *mom_dst);
 int tirt_temporal_denoise_var(tirt_ctx *ctx, const tirt_denoise_var_t *params);
+
+/* Temporal accumulation across MOVING geometry: per-pixel motion records (csrc/tirt_temporal.hip, csrc/tirt_dynamic.hip; no reference counterpart; opt-in).
+ * The part of SVGF the section above leaves out: backprojection through the surface's own motion.  While tirt_motion_enable is off everything above holds as
+ * stated, a geometry update emptying the history included.  While it is on and the history is not empty, tirt_vertex_update and tirt_vertex_update_device
+ * -- after all their refusals, a refused call changes nothing -- copy the whole vertex buffer to a SNAPSHOT before they write, unless an earlier update
+ * since the last accumulate has done so already, mark the geometry as moved, and leave the history in place: however many updates lie between two
+ * accumulates, the snapshot holds the vertex rows of the last accumulated view.  tirt_scene_upload, tirt_temporal_reset, tirt_film_create and every
+ * successful tirt_temporal_accumulate clear the mark; tirt_scene_upload and tirt_temporal_reset still empty the history.  Normals rewritten by
+ * tirt_process_normal are not tracked: the snapshot is taken by the vertex updates alone, so a scene whose normals are smoothed again after an update is
+ * compared with whatever normals the rows held when the update began.
+ * Motion record, TIRT_MOTION_WORDS f32 per pixel p = i*H + j, 16-byte aligned, made by tirt_temporal_accumulate when the geometry is marked as moved:
+ * the camera ray through the pixel centre (tirt_debug_render's ray at frame 0: no jitter) is traced to its closest hit (t, u, v, prim), stack size 64.
+ * For a triangle with first vertex vi, a = 1.0f - u - v, on vertex rows R:
+ *     P(R) = (v1*a + v2*u) + v3*v        N(R) = normalized((n1*a + n2*u) + n3*v)       (per component; normalized: x * (1 / sqrt((x.x*x.x + x.y*x.y) + x.z*x.z)))
+ *   words 0..2  D  = P(snapshot) - P(current)      word 3  1.0
+ *   words 4..6  dN = N(snapshot) - N(current)      word 7  0
+ * A miss, and a hit on an analytic shape (shapes do not move): eight zeros.  All f32, one rounding per operation in the order written
+ * (tests/motion_expected.py restates it; the device gives its bits).
+ * With motion records the accumulation above changes in step 1 alone: after X = eye_cur + D * zc,  X = X + D_motion per component, and
+ * n_c = n_c + dN per component before the taps' normal test.  A record of zeros is added like any other.  Steps 2 to 6 are as stated: d_exp and the
+ * projection use the point where the surface WAS, and the depth and normal tests reject what the moved object uncovered.
+ * tirt_motion_enable: needs tirt_temporal_enable; on != 0 allocates the records, on == 0 frees them and the snapshot (and empties a history whose
+ *   geometry is marked as moved).  tirt_temporal_enable(0) returns TIRT_ERR_ARG while it is on; tirt_film_create disables it.  Waits for pending work.
+ * tirt_temporal_accumulate while it is on: an empty history, or geometry not marked as moved: exactly as without it, and the records are zeroed.  Marked
+ *   as moved: TIRT_ERR_ARG when the LBVH is not built (tirt_lbvh_build must follow the vertex update); otherwise the rays, the records and the
+ *   accumulation with them on the main stream.  The rays count in rays_closest; a traversal stack overflow is reported by tirt_stats, as tirt_debug_render's.
+ * tirt_motion_download / tirt_motion_export_device: out[W*H*TIRT_MOTION_WORDS], the records of the last accumulate; TIRT_ERR_ARG when not enabled, while
+ *   the history is empty or before the first accumulate since tirt_motion_enable, or for a null pointer.  They wait for the copy.
+ * tirt_motion_temporal_device: tirt_temporal_device with `motion` [W,H,TIRT_MOTION_WORDS] (device memory, 16-byte aligned, no output may overlap it)
+ *   between `params` and `stream`: the same checks through the same code, and the accumulation with the records.  tirt_temporal_device is unchanged. */
+#define TIRT_MOTION_WORDS 8
+int tirt_motion_enable(tirt_ctx *ctx, int on);
+int tirt_motion_download(tirt_ctx *ctx, float *out);
+int tirt_motion_export_device(tirt_ctx *ctx, void *dev_dst);
+int tirt_motion_temporal_device(tirt_ctx *ctx, const float *hdr_c, const float *aov_c, const float *mom_c, const float *hdr_h, const float *aov_h, const float *mom_h,
+                                const tirt_temporal_camera_t *cur, const tirt_temporal_camera_t *prev, float *hdr_o, float *mom_o, int W, int H,
+                                const tirt_temporal_t *params, const float *motion, void *stream);
 
 /* Pixel set and adaptive sampling of the path tracer (csrc/tirt_adaptive.hip; no reference counterpart; PT_RGB only).  A pixel set is a list of linear pixel
  * indices p = i*H + j of this context's own tiles, strictly ascending in the context's LOCAL order (the order in which the device walks its tiles: tile by

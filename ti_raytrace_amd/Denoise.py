@@ -20,7 +20,8 @@ sample moments (n, mean3, M2 3, bad: ``PathTrace.moments_to_torch()``, or the ra
 is the temporal accumulation of ``PathTrace.temporal_accumulate()`` (``tirt_temporal_device``): the history -- an earlier result with the ``aov`` of
 that call, or a plain film with its records -- seen from ``cam_prev`` is reprojected into the view of ``cam`` and merged with the current film and
 its moments.  ``cam`` / ``cam_prev`` are ``Camera`` objects as they stood at the two views, or the tuples ``(view, view_inv, eye, fx, fy, cx, cy)``
-a ``Camera`` pushes.  The guide record of the result is ``aov``: ``denoise_var(hdr_o, aov, mom_o)`` filters it.
+a ``Camera`` pushes.  The guide record of the result is ``aov``: ``denoise_var(hdr_o, aov, mom_o)`` filters it.  ``motion=`` takes a ``[W, H, 8]``
+tensor of motion records (``PathTrace.motion_to_torch()``) for geometry that moved between the two views (``tirt_motion_temporal_device``).
 """
 from . import _native
 
@@ -86,14 +87,20 @@ def denoise_var(hdr, aov, moments, levels=5, sigma_c=3.0, sigma_n=0.3, sigma_z=0
                 (levels, sigma_c, sigma_n, sigma_z), ctx)
 
 
-def temporal_accumulate(hdr, aov, moments, hist_hdr, hist_aov, hist_moments, cam, cam_prev, max_history=32.0, sigma_n=0.3, sigma_z=0.1, ctx=None):
+def temporal_accumulate(hdr, aov, moments, hist_hdr, hist_aov, hist_moments, cam, cam_prev, max_history=32.0, sigma_n=0.3, sigma_z=0.1, ctx=None,
+                        motion=None):
     fn = "temporal_accumulate"
     tensors = (("hdr", hdr, 3), ("aov", aov, _native.AOV_WORDS), ("moments", moments, _native.MOM_WORDS),
                ("hist_hdr", hist_hdr, 3), ("hist_aov", hist_aov, _native.AOV_WORDS), ("hist_moments", hist_moments, _native.MOM_WORDS))
-    torch, dev, W, H = _check(fn, tensors)
+    torch, dev, W, H = _check(fn, tensors + ((("motion", motion, _native.MOTION_WORDS),) if motion is not None else ()))
     ctx = _context(fn, ctx, dev)
     hdr_o = torch.empty((W, H, 3), dtype=torch.float32, device=dev)
     mom_o = torch.empty((W, H, _native.MOM_WORDS), dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if motion is not None:
+        ctx.motion_temporal_device(*[t.data_ptr() for _, t, _ in tensors], cam, cam_prev, hdr_o.data_ptr(), mom_o.data_ptr(), W, H, motion.data_ptr(),
+                               max_history, sigma_n, sigma_z, stream=stream)
+        return hdr_o, mom_o
     ctx.temporal_device(*[t.data_ptr() for _, t, _ in tensors], cam, cam_prev, hdr_o.data_ptr(), mom_o.data_ptr(), W, H,
-                        max_history, sigma_n, sigma_z, stream=torch.cuda.current_stream(dev).cuda_stream)
+                        max_history, sigma_n, sigma_z, stream=stream)
     return hdr_o, mom_o

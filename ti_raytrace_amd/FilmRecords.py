@@ -125,7 +125,7 @@ class TemporalAccumulation:
         self.scene.ctx.temporal_accumulate(max_history, sigma_n, sigma_z)
 
     def temporal_reset(self):
-        """Empty the history (a geometry update or a scene upload does so too; film_clear does not)."""
+        """Empty the history (a scene upload does so too, and a geometry update unless motion=True; film_clear does not)."""
         self._need_temporal("temporal_reset")
         self.scene.ctx.temporal_reset()
 
@@ -152,3 +152,24 @@ class TemporalAccumulation:
         mom = torch.empty((self.imgSizeX, self.imgSizeY, _native.MOM_WORDS), dtype=torch.float32, device=dev)
         self.scene.ctx.temporal_export_device(hdr.data_ptr(), mom.data_ptr())
         return hdr, mom
+
+    # ---- motion records (motion=True): the accumulation across Scene.update_vertices (include/tirt.h, tirt_motion_enable).  The viewer's loop with an
+    # animated mesh:  scene.update_vertices(...) (it rebuilds);  scene.ctx.film_clear(), cam.frame = 0;  integrator.seed = s + step;  render_frames(k);
+    # temporal_accumulate();  denoise_temporal() ----
+    def _motion_fields(self):
+        """motion [W, H, 8]: per pixel where its surface point and shading normal were at the last accumulated view, relative to now (D3, 1, dN3, 0)"""
+        self.motion = DeviceField("motion", self.scene, self.motion_to_numpy)
+
+    def _need_motion(self, what):
+        if not self.motion_records:
+            raise ValueError("%s needs the motion records: PT_RGB.PathTrace(..., aov=True, moments=True, temporal=True, motion=True)" % what)
+
+    def motion_to_numpy(self):
+        """[W, H, 8] float32: the motion records of the last temporal_accumulate()"""
+        self._need_motion("motion_to_numpy")
+        return self.scene.ctx.motion_download(self.imgSizeX, self.imgSizeY)
+
+    def motion_to_torch(self):
+        """The same as a float32 tensor on the context's device, filled device to device (tirt_motion_export_device)."""
+        self._need_motion("motion_to_torch")
+        return self._to_torch(_native.MOTION_WORDS, "motion_export_device", ("motion_to_torch", "motion_to_numpy and the C-ABI tirt_motion_download"))

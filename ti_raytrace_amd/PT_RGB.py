@@ -20,7 +20,7 @@ def default_tile_size(H):
 
 class PathTrace(FilmRecords, SampleMoments, TemporalAccumulation):
     def __init__(self, imgSizeX, imgSizeY, cam, scene, stack_size,
-                 seed=1, tile_rank=0, tile_count=1, tile_size=None, flags=0, temporal=False, moments=False, aov=False):
+                 seed=1, tile_rank=0, tile_count=1, tile_size=None, flags=0, motion=False, temporal=False, moments=False, aov=False):
         self.imgSizeX = imgSizeX
         self.imgSizeY = imgSizeY
         self.cam = cam
@@ -44,6 +44,11 @@ class PathTrace(FilmRecords, SampleMoments, TemporalAccumulation):
             raise ValueError("temporal=True needs the feature buffers and the sample moments: PT_RGB.PathTrace(..., aov=True, moments=True, temporal=True)")
         self.temporal = temporal
         self._temporal_fields()
+        # extension: motion records, so that the accumulation survives Scene.update_vertices
+        if motion and not temporal:
+            raise ValueError("motion=True needs the temporal history: PT_RGB.PathTrace(..., aov=True, moments=True, temporal=True, motion=True)")
+        self.motion_records = motion
+        self._motion_fields()
         # extension: the film after denoise(), a buffer of its own beside hdr
         self.denoised = DeviceField("denoised", scene, self._denoised_download)
 
@@ -59,6 +64,8 @@ class PathTrace(FilmRecords, SampleMoments, TemporalAccumulation):
             self.scene.ctx.moments_enable(True)
         if self.temporal:
             self.scene.ctx.temporal_enable(True)
+        if self.motion_records:
+            self.scene.ctx.motion_enable(True)
 
     def render(self):
         """One frame at ``cam.frame`` (the caller advances it with ``cam.update_frame()``)."""

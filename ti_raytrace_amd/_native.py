@@ -70,6 +70,9 @@ MOM_MEAN = 1
 MOM_M2 = 4
 MOM_BAD = 7
 
+# the words of a pixel's motion record (include/tirt.h, TIRT_MOTION_WORDS): D3, 1, dN3, 0
+MOTION_WORDS = 8
+
 # bits of the scene feature word (include/tirt.h, tirt_shade_features)
 SF_GLASS, SF_ENV, SF_LIGHT_TRI, SF_LIGHT_SPOT_LASER, SF_NO_LIGHT, SF_LIGHT_SPHERE, SF_LIGHT_OTHER = 1, 2, 4, 8, 16, 32, 64
 SF_ALL = 127
@@ -231,6 +234,15 @@ SIGNATURES.update({
     "tirt_temporal_download": (C.c_int, [_vp, _vp, _vp]),
     "tirt_temporal_export_device": (C.c_int, [_vp, _vp, _vp]),
     "tirt_temporal_denoise_var": (C.c_int, [_vp, C.POINTER(DenoiseParams)]),
+})
+
+
+SIGNATURES.update({
+    "tirt_motion_enable": (C.c_int, [_vp, C.c_int]),
+    "tirt_motion_download": (C.c_int, [_vp, _vp]),
+    "tirt_motion_export_device": (C.c_int, [_vp, _vp]),
+    "tirt_motion_temporal_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(TemporalCamera), C.POINTER(TemporalCamera), _vp, _vp, C.c_int,
+                                              C.c_int, C.POINTER(TemporalParams), _vp, _vp]),
 })
 
 
@@ -638,6 +650,25 @@ class Context:
         check(lib().tirt_temporal_device(self.handle, *[_vp(int(a) or None) for a in (hdr_c, aov_c, mom_c, hdr_h, aov_h, mom_h)],
                                          C.byref(temporal_camera(cam)), C.byref(temporal_camera(cam_prev)), _vp(int(hdr_o) or None), _vp(int(mom_o) or None),
                                          int(W), int(H), C.byref(TemporalParams(float(max_history), float(sigma_n), float(sigma_z))), _vp(int(stream) or None)))
+
+    def motion_enable(self, on=True):
+        """tirt_motion_enable: motion records for the temporal accumulation (include/tirt.h): geometry updates then keep the history; needs temporal_enable"""
+        check(lib().tirt_motion_enable(self.handle, 1 if on else 0))
+
+    def motion_download(self, W, H):
+        """[W, H, MOTION_WORDS] float32: the motion records of the last temporal_accumulate (D3, 1, dN3, 0 per pixel; zeros where nothing moved)"""
+        return self._record_download("tirt_motion_download", W, H, MOTION_WORDS)
+
+    def motion_export_device(self, dev_ptr):
+        self._export("tirt_motion_export_device", dev_ptr)
+
+    def motion_temporal_device(self, hdr_c, aov_c, mom_c, hdr_h, aov_h, mom_h, cam, cam_prev, hdr_o, mom_o, W, H, motion,
+                           max_history=TEMPORAL_DEFAULTS["max_history"], sigma_n=0.3, sigma_z=0.1, stream=0):
+        """tirt_motion_temporal_device: temporal_device with `motion`, the device address of [W, H, MOTION_WORDS] motion records"""
+        check(lib().tirt_motion_temporal_device(self.handle, *[_vp(int(a) or None) for a in (hdr_c, aov_c, mom_c, hdr_h, aov_h, mom_h)],
+                                                C.byref(temporal_camera(cam)), C.byref(temporal_camera(cam_prev)), _vp(int(hdr_o) or None), _vp(int(mom_o) or None),
+                                                int(W), int(H), C.byref(TemporalParams(float(max_history), float(sigma_n), float(sigma_z))),
+                                                _vp(int(motion) or None), _vp(int(stream) or None)))
 
     def denoise(self, levels=5, sigma_c=1.0, sigma_n=0.3, sigma_z=0.1):
         """tirt_denoise: the a-trous filter over the context's film and feature buffers into a buffer of its own (include/tirt.h); asynchronous"""

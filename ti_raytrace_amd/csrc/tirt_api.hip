@@ -479,7 +479,7 @@ void tirt_destroy(tirt_ctx *c)
     drain_render_events(c);
     DevBuf *bufs[] = {&c->vertex, &c->primitive, &c->material, &c->shape, &c->light, &c->env, &c->mat_lrgb, &c->shade_rec, &c->light_rec, &c->morton_unsorted, &c->keys_a,
                       &c->keys_b, &c->vals_a, &c->vals_b, &c->hist, &c->morton_sorted, &c->bvh_node, &c->compact, &c->parent,
-                      &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb, &c->aov, &c->mom, &c->mom_cnt, &c->pixset, &c->pixset_tmp, &c->tp_mem, &c->dn_mem, &c->dn_out,
+                      &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb, &c->aov, &c->mom, &c->mom_cnt, &c->pixset, &c->pixset_tmp, &c->tp_mem, &c->mv_rec, &c->mv_snap, &c->dn_mem, &c->dn_out,
                       &c->counters_mem, &c->spill, &c->trace_stage, &c->debug_mem, &c->query_mem, &c->dyn_mem, &c->dev_counters, &c->bdpt_px, &c->timeline, &c->pvb_set[0].count, &c->pvb_set[0].cand, &c->pvb_set[0].bound, &c->pvb_set[1].count, &c->pvb_set[1].cand, &c->pvb_set[1].bound, &c->pvb_stat, &c->pvb_tmp};
     for (DevBuf *b : bufs) b->release();
     for (auto &bl : c->bd) {
@@ -621,7 +621,7 @@ int tirt_scene_upload(tirt_ctx *c, const float *vertex, int nv, const int32_t *p
     }
     hipStream_t st = c->stream;
     c->built = false;
-    c->tp_valid = false;                       // another world: the temporal history (tirt_temporal.hip) describes the old one
+    c->tp_valid = false; c->mv_moved = false;  // another world: the temporal history (tirt_temporal.hip) and its snapshot of the vertex rows describe the old one
     if (upload(c->vertex, vertex, sizeof(float) * 9 * (size_t)nv, st)) return TIRT_ERR_HIP;
     if (upload(c->primitive, primitive, sizeof(int) * 3 * (size_t)n, st)) return TIRT_ERR_HIP;
     if (upload(c->material, material, sizeof(float) * 10 * (size_t)nm, st)) return TIRT_ERR_HIP;
@@ -890,6 +890,7 @@ int tirt_film_create(tirt_ctx *c, int W, int H, int tile_rank, int tile_count, i
         TIRT_HIP(hipStreamSynchronize(c->stream));
         c->dn_mem.release(); c->dn_out.release();
         c->tp_mem.release(); c->tp_valid = false;
+        c->mv_rec.release(); c->mv_snap.release(); c->mv_moved = false; c->mv_rec_valid = false;
     }
     if (c->hdr.ensure(sizeof(float) * 3 * (size_t)NP) || c->rgb.ensure(sizeof(float) * 3 * (size_t)NP)) return TIRT_ERR_HIP;
     c->W = W; c->H = H; c->tile_rank = tile_rank; c->tile_count = tile_count; c->tile_size = tile_size;
@@ -1032,7 +1033,15 @@ int tirt_temporal_device(tirt_ctx *c, const float *hdr_c, const float *aov_c, co
                          const tirt_temporal_t *params, void *stream)
 {
     CTX(c);
-    return temporal_device(c, hdr_c, aov_c, mom_c, hdr_h, aov_h, mom_h, cur, prev, hdr_o, mom_o, W, H, params, stream);
+    return temporal_device(c, hdr_c, aov_c, mom_c, hdr_h, aov_h, mom_h, cur, prev, hdr_o, mom_o, W, H, params, nullptr, stream);
+}
+int tirt_motion_temporal_device(tirt_ctx *c, const float *hdr_c, const float *aov_c, const float *mom_c, const float *hdr_h, const float *aov_h, const float *mom_h,
+                            const tirt_temporal_camera_t *cur, const tirt_temporal_camera_t *prev, float *hdr_o, float *mom_o, int W, int H,
+                            const tirt_temporal_t *params, const float *motion, void *stream)
+{
+    CTX(c);
+    TIRT_REQUIRE(motion, "tirt_motion_temporal_device: null pointer");
+    return temporal_device(c, hdr_c, aov_c, mom_c, hdr_h, aov_h, mom_h, cur, prev, hdr_o, mom_o, W, H, params, motion, stream);
 }
 int tirt_temporal_enable(tirt_ctx *c, int on) { CTX(c); return temporal_enable(c, on); }
 int tirt_temporal_accumulate(tirt_ctx *c, const tirt_temporal_t *params)
@@ -1046,9 +1055,12 @@ int tirt_temporal_reset(tirt_ctx *c)
 {
     CTX(c);
     TIRT_REQUIRE(c->tp_mem.p, "tirt_temporal_reset: temporal accumulation not enabled (tirt_temporal_enable)");
-    c->tp_valid = false;
+    c->tp_valid = false; c->mv_moved = false;
     return TIRT_OK;
 }
+int tirt_motion_enable(tirt_ctx *c, int on) { CTX(c); return motion_enable(c, on); }
+int tirt_motion_download(tirt_ctx *c, float *out) { CTX(c); return motion_copy_out(c, "tirt_motion_download", out, hipMemcpyDeviceToHost); }
+int tirt_motion_export_device(tirt_ctx *c, void *dev_dst) { CTX(c); return motion_copy_out(c, "tirt_motion_export_device", dev_dst, hipMemcpyDeviceToDevice); }
 int tirt_temporal_download(tirt_ctx *c, float *hdr_out, float *mom_out) { CTX(c); return temporal_copy_out(c, "tirt_temporal_download", hdr_out, mom_out, hipMemcpyDeviceToHost); }
 int tirt_temporal_export_device(tirt_ctx *c, void *hdr_dst, void *mom_dst) { CTX(c); return temporal_copy_out(c, "tirt_temporal_export_device", hdr_dst, mom_dst, hipMemcpyDeviceToDevice); }
 int tirt_temporal_denoise_var(tirt_ctx *c, const tirt_denoise_var_t *params) { CTX(c); return temporal_denoise_var(c, params); }

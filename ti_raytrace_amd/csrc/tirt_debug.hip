@@ -59,6 +59,25 @@ __global__ void k_debug_resolve(SceneView sc, v3 eye, TileMap tm, int P, int mod
     o[0] = rad.x; o[1] = rad.y; o[2] = rad.z;
 }
 
+// The first two launches: the camera rays of this context's local pixels at `frame` (0: through the pixel centres, no jitter) and their closest
+// hits, both in c->debug_mem, indexed by local pixel.  The callers have checked the build, the camera and the film.
+int debug_trace(tirt_ctx *c, uint32_t frame, uint32_t seed, int stack_size, int flags, DebugRays &r)
+{
+    if (ensure_counters(c)) return TIRT_ERR_HIP;
+    const int P = (int)c->npix_local;
+    // scratch: one hit record (16 B) and three direction words per local pixel
+    const size_t hit_bytes = sizeof(float4) * (size_t)P, dir_bytes = sizeof(float) * (((size_t)P + 3) & ~(size_t)3);
+    if (c->debug_mem.ensure(hit_bytes + 3 * dir_bytes)) return TIRT_ERR_HIP;
+    r.hit = c->debug_mem.as<float4>();
+    r.dx = (float *)((char *)c->debug_mem.p + hit_bytes); r.dy = (float *)((char *)r.dx + dir_bytes); r.dz = (float *)((char *)r.dy + dir_bytes);
+    r.tm = TileMap{c->tile_rank, c->tile_count, c->tile_size, c->H, c->tile_blocked, 0};
+    const int B = 256, G = (P + B - 1) / B;
+    hipLaunchKernelGGL(k_debug_generate, dim3(G), dim3(B), 0, c->stream, c->cam, r.tm, P, frame, seed, r.dx, r.dy, r.dz);
+    TraceJob job; job.stack_size = stack_size; job.flags = flags; job.dx = r.dx; job.dy = r.dy; job.dz = r.dz; job.count = P; job.hit = r.hit; job.grid_cap = c->tr_grid_alone;
+    c->launches_trace_closest++;
+    return trace_rays(c, job);
+}
+
 int debug_render(tirt_ctx *c, uint32_t frame, uint32_t seed, int mode, int stack_size, int flags)
 {
     TIRT_REQUIRE(c->built, "tirt_debug_render: LBVH not built");
@@ -68,21 +87,11 @@ int debug_render(tirt_ctx *c, uint32_t frame, uint32_t seed, int mode, int stack
     TIRT_REQUIRE(stack_size >= 1 && stack_size <= 4096, "tirt_debug_render: stack_size 1..4096");
     TIRT_REQUIRE((flags & ~(TIRT_TRAVERSE_EXHAUSTIVE | TIRT_COUNT_NODES)) == 0, "tirt_debug_render: unknown flags");
     if (c->npix_local == 0) return TIRT_OK;
-    if (ensure_counters(c)) return TIRT_ERR_HIP;
-    const int P = (int)c->npix_local;
-    // scratch: one hit record (16 B) and three direction words per local pixel
-    const size_t hit_bytes = sizeof(float4) * (size_t)P, dir_bytes = sizeof(float) * (((size_t)P + 3) & ~(size_t)3);
-    if (c->debug_mem.ensure(hit_bytes + 3 * dir_bytes)) return TIRT_ERR_HIP;
-    float4 *hit = c->debug_mem.as<float4>();
-    float *dx = (float *)((char *)c->debug_mem.p + hit_bytes), *dy = (float *)((char *)dx + dir_bytes), *dz = (float *)((char *)dy + dir_bytes);
-    const TileMap tm = {c->tile_rank, c->tile_count, c->tile_size, c->H, c->tile_blocked, 0};
-    const int B = 256, G = (P + B - 1) / B;
-    hipLaunchKernelGGL(k_debug_generate, dim3(G), dim3(B), 0, c->stream, c->cam, tm, P, frame, seed, dx, dy, dz);
-    TraceJob job; job.stack_size = stack_size; job.flags = flags; job.dx = dx; job.dy = dy; job.dz = dz; job.count = P; job.hit = hit; job.grid_cap = c->tr_grid_alone;
-    c->launches_trace_closest++;
-    if (int rc = trace_rays(c, job)) return rc;
+    DebugRays r;
+    if (int rc = debug_trace(c, frame, seed, stack_size, flags, r)) return rc;
+    const int P = (int)c->npix_local, B = 256, G = (P + B - 1) / B;
     v3 eye; eye.x = c->cam.eye[0]; eye.y = c->cam.eye[1]; eye.z = c->cam.eye[2];
-    hipLaunchKernelGGL(k_debug_resolve, dim3(G), dim3(B), 0, c->stream, scene_view(c), eye, tm, P, mode, dx, dy, dz, hit, c->hdr.as<float>());
+    hipLaunchKernelGGL(k_debug_resolve, dim3(G), dim3(B), 0, c->stream, scene_view(c), eye, r.tm, P, mode, r.dx, r.dy, r.dz, r.hit, c->hdr.as<float>());
     TIRT_HIP(hipGetLastError());
     return TIRT_OK;
 }

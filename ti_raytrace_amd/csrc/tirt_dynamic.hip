@@ -173,6 +173,15 @@ static int dyn_apply(tirt_ctx *c, const char *fn, int64_t first, int64_t count, 
     TIRT_HIP(hipGetLastError());
     TIRT_REQUIRE(!bad, std::string(fn) + ": a position is NaN or infinite (nothing was changed)");
 
+    // With motion records on and a history to carry (tirt_temporal.hip) the first update since the last accumulate keeps the rows that view saw.
+    // The history stays, marked as moved, only once everything below has succeeded: a call that fails half way leaves it empty
+    const bool keep_history = c->mv_rec.p && c->tp_valid;
+    if (keep_history && !c->mv_moved) {
+        const size_t bytes = sizeof(float) * VER_VEC * (size_t)c->nv;
+        if (c->mv_snap.ensure(bytes)) return TIRT_ERR_HIP;
+        TIRT_HIP(hipMemcpyAsync(c->mv_snap.p, c->vertex.p, bytes, hipMemcpyDeviceToDevice, st));
+    }
+    c->tp_valid = false;                       // the rows change from here on: without motion records the history assumes the world stood still
     const int64_t ntri = count / 3;
     hipLaunchKernelGGL(k_dyn_scatter, dim3((unsigned)((ntri + DYN_BLOCK - 1) / DYN_BLOCK)), dim3(DYN_BLOCK), 0, st, c->vertex.as<float>(), first, ntri,
                        pos, pos_stride, nrm, nrm_stride);
@@ -184,11 +193,11 @@ static int dyn_apply(tirt_ctx *c, const char *fn, int64_t first, int64_t count, 
     TIRT_HIP(hipMemcpyAsync(hb, box, sizeof(hb), hipMemcpyDeviceToHost, st));
     // from here on the old build describes geometry that is gone, whatever the copy and the sync below return
     c->built = false; c->built_sah = 0; c->shade_rec_valid = false; c->light_rec_valid = false; c->pvb_valid = false;
-    c->tp_valid = false;                       // the temporal history (tirt_temporal.hip) has no motion vectors: it assumes the world stood still
     refresh_shade_features(c);                 // (with the tables it selects kernels for; moving vertices changes no bit of it)
     TIRT_HIP(hipStreamSynchronize(st));
     TIRT_HIP(hipGetLastError());
     for (int k = 0; k < 3; k++) { c->bmin[k] = hb[k]; c->bmax[k] = hb[3 + k]; }
+    if (keep_history) { c->tp_valid = true; c->mv_moved = true; }      // the snapshot holds the rows of the last accumulated view
     return TIRT_OK;
 }
 

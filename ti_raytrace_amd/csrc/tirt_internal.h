@@ -335,6 +335,9 @@ struct tirt_ctx {
     // temporal accumulation (tirt_temporal.hip): two history sets of {aov 8, mom 8, hdr 3} f32 per pixel (p == nullptr: disabled); tp_cur = the set that holds
     // the last result, with the camera it was rendered from; tp_valid = false: the history is empty.  Goes with the film
     tirt::DevBuf tp_mem; int tp_cur = 0; bool tp_valid = false; tirt_temporal_camera_t tp_cam = {};
+    // motion records (tirt_motion_enable): TIRT_MOTION_WORDS f32 per pixel of the last accumulate (p == nullptr: disabled; mv_rec_valid: one has run since);
+    // mv_snap = the vertex rows as the last accumulated view saw them, copied by the first geometry update after it (tirt_dynamic.hip), which sets mv_moved
+    tirt::DevBuf mv_rec, mv_snap; bool mv_moved = false, mv_rec_valid = false;
     tirt::DevBuf dn_mem, dn_out;                  // denoiser (tirt_denoise.hip): 60 B of scratch per pixel; the filtered film W*H*3 f32 (p == nullptr: no tirt_denoise yet).  Both go with the film
 
     // wavefront state
@@ -477,6 +480,9 @@ struct TraceJob {
 int trace_rays(tirt_ctx *c, const TraceJob &j);
 int trace_rays_prepare(tirt_ctx *c, int lane);      // allocates what trace_rays needs on that lane at bdpt_stack_size (stack spill, fetch cursors)
 int debug_render(tirt_ctx *c, uint32_t frame, uint32_t seed, int mode, int stack_size, int flags);      // tirt_debug.hip
+// Debug's camera rays and their closest hits per local pixel, in c->debug_mem on the main stream (tirt_debug.hip; frame 0: the pixel centres)
+struct DebugRays { float4 *hit; float *dx, *dy, *dz; TileMap tm; };
+int debug_trace(tirt_ctx *c, uint32_t frame, uint32_t seed, int stack_size, int flags, DebugRays &r);
 // the local pixels a PT_RGB batch renders and the map to them: the installed pixel set's, else the tiles' (F is set per batch)
 inline int render_pixels(const tirt_ctx *c) { return (int)(c->pixset_n >= 0 ? c->pixset_n : c->npix_local); }
 inline TileMap render_tile_map(const tirt_ctx *c)
@@ -503,8 +509,10 @@ int denoise_into_film_buffer(tirt_ctx *c, const std::string &fn, const float *hd
 // tirt_temporal.hip
 int temporal_device(tirt_ctx *c, const float *hdr_c, const float *aov_c, const float *mom_c, const float *hdr_h, const float *aov_h, const float *mom_h,
                     const tirt_temporal_camera_t *cur, const tirt_temporal_camera_t *prev, float *hdr_o, float *mom_o, int W, int H,
-                    const tirt_temporal_t *prm, void *stream);
+                    const tirt_temporal_t *prm, const float *motion, void *stream);      // motion != nullptr: tirt_motion_temporal_device
 int temporal_enable(tirt_ctx *c, int on);
+int motion_enable(tirt_ctx *c, int on);
+int motion_copy_out(tirt_ctx *c, const char *fn, void *dst, hipMemcpyKind kind);
 int temporal_accumulate(tirt_ctx *c, const tirt_temporal_t *prm);
 int temporal_copy_out(tirt_ctx *c, const char *fn, void *hdr_dst, void *mom_dst, hipMemcpyKind kind);
 int temporal_denoise_var(tirt_ctx *c, const tirt_denoise_var_t *prm);

@@ -1,5 +1,6 @@
 // tirt_temporal.hip -- temporal accumulation: the previous view's film and moment records reprojected into the current view and merged with it
-// (tirt_temporal_device, and the context's own history behind tirt_temporal_enable / _accumulate / _reset / _download / _export_device / _denoise_var).
+// (tirt_temporal_device, tirt_motion_temporal_device, and the context's own history behind tirt_temporal_enable / _accumulate / _reset / _download / _export_device /
+// _denoise_var, with the motion records of tirt_motion_enable / _download / _export_device).
 //
 // No reference counterpart.  This is the temporal part of SVGF (Schied et al., "Spatiotemporal Variance-Guided Filtering", HPG 2017) for a world that
 // stands still: the backprojection goes through the first-hit surface point of the feature records (tirt_aov.hip) instead of motion vectors, the
@@ -13,6 +14,11 @@
 // and its hdr are fetched, so a rejected tap costs 32 B instead of 76; neighbouring lanes' taps are neighbouring pixels of the history (the
 // reprojection of a small camera move is close to a translation), so their loads share cache lines.  No LDS, no atomics; the registers and the scratch
 // the compiler reports are in DESIGN.md section 6.  Stores are plain (not non-temporal): the output is the next call's history and the filter's input.
+//
+// Moving geometry (tirt_motion_enable): SVGF's backprojection through the surface's own motion.  k_motion_resolve, one thread per pixel behind Debug's
+// pixel-centre rays and their closest hits (debug_trace), evaluates the hit's barycentric point and shading normal on the vertex rows as they are and on
+// the snapshot tirt_dynamic.hip took before the first update since the last accumulate: the record is (snapshot - current).  k_temporal<true> adds it to
+// the surface point and to the current normal of step 1 (two more 16-byte loads per pixel); k_temporal<false> is the kernel as it was.
 #include <string.h>
 #include "tirt_internal.h"
 
@@ -24,10 +30,46 @@ TD bool tp_finite(float x) { return __builtin_fabsf(x) < __builtin_inff(); }    
 struct TemporalPrev { float view[12]; float eye[3]; float fx, fy, cx, cy; };
 struct TemporalParams { float max_history, sn2, sigma_z; };
 
+// the barycentric point and the shading normal of a triangle hit on vertex rows, with hit_attributes' own expressions
+TD void motion_point(const float *__restrict__ rows, int vi, float a, float u, float v, v3 &P, v3 &N)
+{
+    const float *r1 = rows + (size_t)vi * VER_VEC, *r2 = r1 + VER_VEC, *r3 = r2 + VER_VEC;
+    const v3 v1 = V(r1[0], r1[1], r1[2]), v2 = V(r2[0], r2[1], r2[2]), v3_ = V(r3[0], r3[1], r3[2]);
+    const v3 n1 = V(r1[3], r1[4], r1[5]), n2 = V(r2[3], r2[4], r2[5]), n3 = V(r3[3], r3[4], r3[5]);
+    P = (v1 * a + v2 * u) + v3_ * v;
+    N = normalized((n1 * a + n2 * u) + n3 * v);
+}
+
+// One thread per local pixel k (tile_count == 1: every pixel of the film), behind debug_trace at frame 0.  A miss and a hit on a shape: eight zeros.
+// Both row sets hold nv rows and a triangle's vi + 2 < nv (tirt_scene_upload checks it); rec holds W * H records.
+__global__ __launch_bounds__(256) void k_motion_resolve(const float *__restrict__ vertex, const float *__restrict__ snapshot, const int *__restrict__ primitive,
+                                                        TileMap tm, int P, const float4 *__restrict__ hit, float4 *__restrict__ rec)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= P) return;
+    const int p = local_to_pixel(tm, k);
+    const float4 h = hit[k];
+    float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0;
+    if (h.x < INF_VALUE) {
+        const int *pr = primitive + (size_t)__float_as_int(h.w) * PRI_VEC;
+        if (pr[0] == PRIMITIVE_TRI) {
+            const int vi = pr[1];
+            const float a = 1.0f - h.y - h.z;
+            v3 Pc, Nc, Ps, Ns;
+            motion_point(vertex, vi, a, h.y, h.z, Pc, Nc);
+            motion_point(snapshot, vi, a, h.y, h.z, Ps, Ns);
+            r0 = make_float4(Ps.x - Pc.x, Ps.y - Pc.y, Ps.z - Pc.z, 1.0f);
+            r1 = make_float4(Ns.x - Nc.x, Ns.y - Nc.y, Ns.z - Nc.z, 0.0f);
+        }
+    }
+    rec[2 * (size_t)p] = r0; rec[2 * (size_t)p + 1] = r1;
+}
+
+template <bool MOTION>
 __global__ __launch_bounds__(256) void k_temporal(const float *__restrict__ hdr_c, const float4 *__restrict__ aov_c, const float4 *__restrict__ mom_c,
                                                   const float *__restrict__ hdr_h, const float4 *__restrict__ aov_h, const float4 *__restrict__ mom_h,
                                                   float *__restrict__ hdr_o, float4 *__restrict__ mom_o, int W, int H, int NP,
-                                                  CameraView cur, TemporalPrev prev, TemporalParams prm)
+                                                  CameraView cur, TemporalPrev prev, TemporalParams prm, const float4 *__restrict__ mv)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= NP) return;
@@ -39,12 +81,18 @@ __global__ __launch_bounds__(256) void k_temporal(const float *__restrict__ hdr_
     float o0 = h0, o1 = h1, o2 = h2;                       // 6. no history: the current pixel, bit for bit
     float4 r0 = c0, r1 = c1;
 
-    const float ncx = lo.w, ncy = hi.x, ncz = hi.y, z = hi.z, al = hi.w;
+    float ncx = lo.w, ncy = hi.x, ncz = hi.y;
+    const float z = hi.z, al = hi.w;
     if (al > 0.0f) {
         // 1. the surface point the pixel's camera rays met, on the ray through the pixel centre
         const float zc = z / al;
         const v3 D = camera_ray_direction(cur, i, j, 0.0f, 0.0f);
-        const float Xx = cur.eye[0] + D.x * zc, Xy = cur.eye[1] + D.y * zc, Xz = cur.eye[2] + D.z * zc;
+        float Xx = cur.eye[0] + D.x * zc, Xy = cur.eye[1] + D.y * zc, Xz = cur.eye[2] + D.z * zc;
+        if constexpr (MOTION) {                            // to where the surface was, with the normal it had
+            const float4 d0 = mv[2 * (size_t)p], d1 = mv[2 * (size_t)p + 1];
+            Xx = Xx + d0.x; Xy = Xy + d0.y; Xz = Xz + d0.z;
+            ncx = ncx + d1.x; ncy = ncy + d1.y; ncz = ncz + d1.z;
+        }
         // 2. where the previous camera saw it
         const float *V = prev.view;
         const float qx = ((V[0] * Xx + V[1] * Xy) + V[2] * Xz) + V[3];
@@ -141,7 +189,7 @@ static int temporal_check_params(const std::string &fn, const tirt_temporal_t *&
 // the kernel on the context's stream; the parameters have passed temporal_check_params
 static int temporal_launch(tirt_ctx *c, const float *hdr_c, const float *aov_c, const float *mom_c, const float *hdr_h, const float *aov_h, const float *mom_h,
                            const tirt_temporal_camera_t &cur, const tirt_temporal_camera_t &prev, float *hdr_o, float *mom_o, int W, int H,
-                           const tirt_temporal_t &prm)
+                           const tirt_temporal_t &prm, const float *motion = nullptr)
 {
     CameraView cv;
     memcpy(cv.view_inv, cur.view_inv, sizeof(float) * 12);
@@ -153,17 +201,22 @@ static int temporal_launch(tirt_ctx *c, const float *hdr_c, const float *aov_c, 
     pv.fx = prev.fx; pv.fy = prev.fy; pv.cx = prev.cx; pv.cy = prev.cy;
     const TemporalParams kp = {prm.max_history, prm.sigma_n * prm.sigma_n, prm.sigma_z};
     const int NP = W * H, B = 256;
-    hipLaunchKernelGGL(k_temporal, dim3((unsigned)((NP + B - 1) / B)), dim3(B), 0, c->stream, hdr_c, (const float4 *)aov_c, (const float4 *)mom_c,
-                       hdr_h, (const float4 *)aov_h, (const float4 *)mom_h, hdr_o, (float4 *)mom_o, W, H, NP, cv, pv, kp);
+    const dim3 G((unsigned)((NP + B - 1) / B));
+    if (motion)
+        hipLaunchKernelGGL(k_temporal<true>, G, dim3(B), 0, c->stream, hdr_c, (const float4 *)aov_c, (const float4 *)mom_c, hdr_h, (const float4 *)aov_h,
+                           (const float4 *)mom_h, hdr_o, (float4 *)mom_o, W, H, NP, cv, pv, kp, (const float4 *)motion);
+    else
+        hipLaunchKernelGGL(k_temporal<false>, G, dim3(B), 0, c->stream, hdr_c, (const float4 *)aov_c, (const float4 *)mom_c, hdr_h, (const float4 *)aov_h,
+                           (const float4 *)mom_h, hdr_o, (float4 *)mom_o, W, H, NP, cv, pv, kp, (const float4 *)nullptr);
     TIRT_HIP(hipGetLastError());
     return TIRT_OK;
 }
 
 int temporal_device(tirt_ctx *c, const float *hdr_c, const float *aov_c, const float *mom_c, const float *hdr_h, const float *aov_h, const float *mom_h,
                     const tirt_temporal_camera_t *cur, const tirt_temporal_camera_t *prev, float *hdr_o, float *mom_o, int W, int H,
-                    const tirt_temporal_t *prm, void *stream)
+                    const tirt_temporal_t *prm, const float *motion, void *stream)
 {
-    const std::string fn = "tirt_temporal_device";
+    const std::string fn = motion ? "tirt_motion_temporal_device" : "tirt_temporal_device";      // (a null motion array: tirt_motion_temporal_device has refused it)
     TIRT_REQUIRE(W >= 1 && H >= 1 && (long long)W * H < (1ll << 30), fn + ": bad size");
     if (int rc = temporal_check_params(fn, prm)) return rc;
     TIRT_REQUIRE(cur && prev, fn + ": null camera");
@@ -175,28 +228,29 @@ int temporal_device(tirt_ctx *c, const float *hdr_c, const float *aov_c, const f
     }
     TIRT_REQUIRE(cs == hipStreamCaptureStatusNone, fn + ": the caller's stream is capturing a graph (the accumulation cannot be captured)");
     const size_t NP = (size_t)W * H;
-    const struct { const char *name; const void *p; size_t words; bool out; } a[8] = {
+    const int NA = motion ? 9 : 8;                         // the outputs are a[6] and a[7]
+    const struct { const char *name; const void *p; size_t words; bool out; } a[9] = {
         {"hdr_c", hdr_c, 3, false}, {"aov_c", aov_c, TIRT_AOV_WORDS, false}, {"mom_c", mom_c, TIRT_MOM_WORDS, false},
         {"hdr_h", hdr_h, 3, false}, {"aov_h", aov_h, TIRT_AOV_WORDS, false}, {"mom_h", mom_h, TIRT_MOM_WORDS, false},
-        {"hdr_o", hdr_o, 3, true}, {"mom_o", mom_o, TIRT_MOM_WORDS, true}};
+        {"hdr_o", hdr_o, 3, true}, {"mom_o", mom_o, TIRT_MOM_WORDS, true}, {"motion", motion, TIRT_MOTION_WORDS, false}};
     bool null = false, overlap = false, aligned = true;
-    for (int k = 0; k < 8; k++) {
+    for (int k = 0; k < NA; k++) {
         null = null || !a[k].p;
         aligned = aligned && (a[k].words == 3 || ((uintptr_t)a[k].p & 15) == 0);      // the records go as float4, hdr word by word
     }
     for (int o = 6; o < 8; o++)
-        for (int k = 0; k < 8; k++) {
+        for (int k = 0; k < NA; k++) {
             if (k == o) continue;
             const uintptr_t o0 = (uintptr_t)a[o].p, o1 = o0 + sizeof(float) * a[o].words * NP, b0 = (uintptr_t)a[k].p, b1 = b0 + sizeof(float) * a[k].words * NP;
             overlap = overlap || !(o1 <= b0 || b1 <= o0);
         }
     TIRT_REQUIRE(!null, fn + ": null pointer");
-    for (int k = 0; k < 8; k++)
+    for (int k = 0; k < NA; k++)
         if (int rc = require_device_ptr(c, a[k].p, (fn + ": " + a[k].name).c_str())) return rc;
     TIRT_REQUIRE(!overlap, fn + ": an output overlaps an input or the other output");
-    TIRT_REQUIRE(aligned, fn + ": the feature and moment arrays must be 16-byte aligned");
+    TIRT_REQUIRE(aligned, fn + ": the feature and moment arrays" + (motion ? " and the motion records" : "") + " must be 16-byte aligned");
     if (int rc = query_begin(c, stream)) return rc;
-    if (int rc = temporal_launch(c, hdr_c, aov_c, mom_c, hdr_h, aov_h, mom_h, *cur, *prev, hdr_o, mom_o, W, H, *prm)) return rc;
+    if (int rc = temporal_launch(c, hdr_c, aov_c, mom_c, hdr_h, aov_h, mom_h, *cur, *prev, hdr_o, mom_o, W, H, *prm, motion)) return rc;
     return query_end(c, stream);
 }
 
@@ -217,8 +271,9 @@ int temporal_enable(tirt_ctx *c, int on)
 {
     const std::string fn = "tirt_temporal_enable";
     TIRT_REQUIRE(c->hdr.p, fn + ": film not created");
+    TIRT_REQUIRE(on || !c->mv_rec.p, fn + ": motion records are on and need the history (tirt_motion_enable(0) first)");
     if (sync_all(c)) return TIRT_ERR_HIP;
-    c->tp_valid = false;
+    c->tp_valid = false; c->mv_moved = false;
     if (!on) { c->tp_mem.release(); return TIRT_OK; }
     TIRT_REQUIRE(c->aov.p, fn + ": feature buffers not enabled (tirt_aov_enable)");
     TIRT_REQUIRE(c->mom.p, fn + ": moment buffers not enabled (tirt_moments_enable)");
@@ -228,12 +283,57 @@ int temporal_enable(tirt_ctx *c, int on)
     return TIRT_OK;
 }
 
+static size_t motion_bytes(const tirt_ctx *c) { return sizeof(float) * TIRT_MOTION_WORDS * (size_t)c->W * c->H; }
+
+int motion_enable(tirt_ctx *c, int on)
+{
+    const std::string fn = "tirt_motion_enable";
+    TIRT_REQUIRE(c->hdr.p, fn + ": film not created");
+    TIRT_REQUIRE(!on || c->tp_mem.p, fn + ": temporal accumulation not enabled (tirt_temporal_enable)");
+    if (sync_all(c)) return TIRT_ERR_HIP;
+    if (!on) {
+        if (c->mv_moved) c->tp_valid = false;              // the history is of geometry that has moved since, and nothing says how any more
+        c->mv_rec.release(); c->mv_snap.release();
+        c->mv_moved = false; c->mv_rec_valid = false;
+        return TIRT_OK;
+    }
+    if (c->mv_rec.p) return TIRT_OK;                       // already on: the snapshot and its flag stay
+    if (c->mv_rec.ensure(motion_bytes(c))) return TIRT_ERR_HIP;
+    c->mv_moved = false; c->mv_rec_valid = false;
+    return TIRT_OK;
+}
+
+// generate, trace, resolve: the record of every pixel into c->mv_rec, on the main stream (the caller has checked the build and the camera)
+static int motion_resolve(tirt_ctx *c)
+{
+    DebugRays r;
+    if (int rc = debug_trace(c, 0, 0, 64, 0, r)) return rc;
+    const int P = (int)c->npix_local, B = 256;
+    hipLaunchKernelGGL(k_motion_resolve, dim3((unsigned)((P + B - 1) / B)), dim3(B), 0, c->stream, (const float *)c->vertex.as<float>(),
+                       (const float *)c->mv_snap.as<float>(), (const int *)c->primitive.as<int>(), r.tm, P, (const float4 *)r.hit, c->mv_rec.as<float4>());
+    TIRT_HIP(hipGetLastError());
+    return TIRT_OK;
+}
+
+int motion_copy_out(tirt_ctx *c, const char *fn, void *dst, hipMemcpyKind kind)
+{
+    TIRT_REQUIRE(c->mv_rec.p, std::string(fn) + ": motion records not enabled (tirt_motion_enable)");
+    TIRT_REQUIRE(c->tp_valid && c->mv_rec_valid, std::string(fn) + ": nothing accumulated yet (tirt_temporal_accumulate)");
+    TIRT_REQUIRE(dst, std::string(fn) + ": null pointer");
+    TIRT_HIP(hipMemcpyAsync(dst, c->mv_rec.p, motion_bytes(c), kind, c->stream));
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    TIRT_HIP(hipGetLastError());
+    return TIRT_OK;
+}
+
 int temporal_accumulate(tirt_ctx *c, const tirt_temporal_t *prm)
 {
     const std::string fn = "tirt_temporal_accumulate";
     TIRT_REQUIRE(c->tp_mem.p, fn + ": temporal accumulation not enabled (tirt_temporal_enable)");
     TIRT_REQUIRE(c->cam_set, fn + ": camera not set");
     if (int rc = temporal_check_params(fn, prm)) return rc;
+    const bool moved = c->mv_rec.p && c->tp_valid && c->mv_moved;      // geometry updates since the last accumulate: through the motion records
+    TIRT_REQUIRE(!moved || c->built, fn + ": LBVH not built (tirt_lbvh_build must follow the vertex update)");
     tirt_temporal_camera_t cur;
     memcpy(cur.view, c->view, sizeof(float) * 16);
     memset(cur.view_inv, 0, sizeof(cur.view_inv));
@@ -243,9 +343,11 @@ int temporal_accumulate(tirt_ctx *c, const tirt_temporal_t *prm)
     cur.fx = c->cam.fx; cur.fy = c->cam.fy; cur.cx = c->cam.cx; cur.cy = c->cam.cy;
     const size_t NP = (size_t)c->W * c->H;
     const TemporalSet h = temporal_set(c, c->tp_cur), o = temporal_set(c, c->tp_cur ^ 1);
+    if (moved) { if (int rc = motion_resolve(c)) return rc; }
+    else if (c->mv_rec.p) TIRT_HIP(hipMemsetAsync(c->mv_rec.p, 0, motion_bytes(c), c->stream));      // nothing moved: the records say so
     if (c->tp_valid) {
         if (int rc = temporal_launch(c, c->hdr.as<float>(), c->aov.as<float>(), c->mom.as<float>(), h.hdr, h.aov, h.mom, cur, c->tp_cam, o.hdr, o.mom,
-                                     c->W, c->H, *prm)) return rc;
+                                     c->W, c->H, *prm, moved ? c->mv_rec.as<float>() : nullptr)) return rc;
     } else {                                                // an empty history: the current film and records as they are
         TIRT_HIP(hipMemcpyAsync(o.hdr, c->hdr.p, sizeof(float) * 3 * NP, hipMemcpyDeviceToDevice, c->stream));
         TIRT_HIP(hipMemcpyAsync(o.mom, c->mom.p, sizeof(float) * TIRT_MOM_WORDS * NP, hipMemcpyDeviceToDevice, c->stream));
@@ -254,6 +356,7 @@ int temporal_accumulate(tirt_ctx *c, const tirt_temporal_t *prm)
     c->tp_cam = cur;
     c->tp_cur ^= 1;
     c->tp_valid = true;
+    c->mv_moved = false; c->mv_rec_valid = c->mv_rec.p != nullptr;
     return TIRT_OK;
 }
 

@@ -11,7 +11,17 @@ reprojection.  The first call of every run is the yaw step itself; `--calls 1` t
 the same repeats, ONE level of tirt_denoise -- the other gather pass over the film -- as the yardstick.  Medians, minima and maxima, megapixels per
 second of the median, and the bytes a call moves per pixel by construction: 76 B of current records in, up to 4 taps x 76 B of history (32 B for a tap
 the guides reject), 44 B out, and the 32 B + 32 B copy of the feature records beside the result.  The share of a peak is not claimed.  Every line goes
-to stdout as JSON and, as text, to the end of --out."""
+to stdout as JSON and, as text, to the end of --out.
+
+    python tools/temporal_rate.py --motion [--sizes 512 1024] [--calls 10] [--repeats 5]
+
+times the accumulate with motion records (tirt_motion_enable) on the headline scene (scenes.synthetic, 100k triangles): before every timed call one
+object -- the first `--object-tris` triangles -- is moved back or forth by Scene.update_vertices (untimed: it rebuilds and waits), then the host clock
+runs around ONE tirt_temporal_accumulate and the device sync behind it: the pixel-centre rays, k_motion_resolve and k_temporal<true>.  Beside it, timed
+the same way (one call and its sync, launch latency included, so the three are comparable with each other and not with the batched figures above) and
+alternating in the same repeats: the static accumulate on a TWIN context of the same scene and film without motion records (the call as it was
+before them: with the records on, a static accumulate also zeroes the 32 B per pixel of the record buffer, which is not part of the yardstick) and
+one Debug frame on that twin (tirt_debug_render at frame 0: the same rays and one resolve kernel).  ms per call = a run's timed calls over their number; medians of the repeats."""
 import argparse
 import json
 import os
@@ -30,6 +40,60 @@ def say(a, text, **rec):
             fh.write(text + "\n")
 
 
+def motion_mode(a, scenes):
+    import numpy as np
+    from ti_raytrace_amd import _native
+    calls = min(a.calls, 10)
+    for size in a.sizes:
+        ex = scenes.synthetic(size, size, a.frames, device_id=0, seed=5, aov=True, moments=True, temporal=True, motion=True)
+        ex.build_scene()
+        it, ctx = ex.integrator, ex.scene.ctx
+        it.render_frames(a.frames)
+        it.temporal_accumulate()
+        twin = scenes.synthetic(size, size, a.frames, device_id=0, seed=5, aov=True, moments=True, temporal=True)
+        twin.build_scene()
+        twin.integrator.render_frames(a.frames)
+        twin.integrator.temporal_accumulate()
+        k = 3 * a.object_tris
+        home = np.ascontiguousarray(ex.scene.vertex_np[:k, 0:3], np.float32)
+        away = (home + np.float32([0.01, 0.0, 0.0])).astype(np.float32)
+        state = {"away": False}
+
+        def timed(fn):
+            ctx.sync(); twin.scene.ctx.sync()
+            t0 = time.perf_counter()
+            fn()
+            ctx.sync(); twin.scene.ctx.sync()
+            return (time.perf_counter() - t0) * 1e3
+
+        def with_motion():
+            state["away"] = not state["away"]
+            ex.scene.update_vertices(away if state["away"] else home)      # untimed; marks the geometry as moved
+            return timed(it.temporal_accumulate)
+
+        def static():
+            return timed(twin.integrator.temporal_accumulate)
+
+        def debug_frame():
+            return timed(lambda: twin.scene.ctx.debug_render(0, 5, _native.DEBUG_NORMAL))
+
+        runs = (("tirt_temporal_accumulate, motion records", with_motion), ("tirt_temporal_accumulate, no motion records", static), ("tirt_debug_render, one frame", debug_frame))
+        for _, fn in runs:                                     # untimed: code objects, the scratch, the snapshot
+            fn()
+        moved_px = int((it.motion_to_numpy()[:, :, 0:3] != 0).any(axis=2).sum()) if with_motion() else 0
+        ms = {name: [] for name, _ in runs}
+        for _ in range(a.repeats):
+            for name, fn in runs:
+                ms[name].append(sum(fn() for _ in range(calls)) / calls)
+        say(a, "headline scene (%d triangles) %d x %d, %d frames per view, %d triangles moved before every call (%d pixels with a record that is not zero); "
+            "%d repeats of %d single timed calls, alternating" % (ex.scene.primitive_count, size, size, a.frames, a.object_tris, moved_px, a.repeats, calls))
+        for name, _ in runs:
+            med = statistics.median(ms[name])
+            say(a, "%4d^2 %-42s ms per call median %.4f  min %.4f  max %.4f  (n = %d)"
+                % (size, name + ":", med, min(ms[name]), max(ms[name]), len(ms[name])), size=size, what=name, ms=ms[name])
+        ctx.close(); twin.scene.ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[512, 1024])
@@ -39,9 +103,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--loop-ms", type=float, default=3.56, help="ms per call of the one-frame loop (tools/moments_rate.py) the cost is set against")
     ap.add_argument("--out", default=os.path.join(HERE, "profiles", "temporal_rate.txt"))
+    ap.add_argument("--motion", action="store_true", help="the accumulate with motion records after a one-object update, on the headline scene")
+    ap.add_argument("--object-tris", type=int, default=1000)
     a = ap.parse_args()
     sys.path.insert(0, HERE)
     from ti_raytrace_amd import scenes
+    if a.motion:
+        return motion_mode(a, scenes)
 
     for size in a.sizes:
         ex = scenes.cornell_box(size, size, a.frames, device_id=0, seed=5, aov=True, moments=True, temporal=True)
