@@ -138,10 +138,50 @@ int tirt_material_upload(tirt_ctx *ctx, const float *material, int nm);
 /* Texture.setup_data_gpu (texture/Texture.py:38-39): rgb_packed[w*h] 0xRRGGBB, index x*h + y */
 int tirt_env_upload(tirt_ctx *ctx, const int32_t *rgb_packed, int w, int h, float power);
 
+/* Albedo textures on materials (csrc/tirt_device.h, tex_albedo; no reference counterpart: integrator/PT_RGB.py:86 takes the material colour, and the
+ * reference's Scene.add_obj fails on a map_Kd line).  PT_RGB, its feature buffers and the Debug albedo view honour them; nothing else does.
+ * Which materials are textured: with T >= 1 uploaded textures, a material row whose type is not MAT_LIGHT and whose slot 1 (SceneData.Material.alebdoTex)
+ *   satisfies 1 <= (int)row[1] <= T is textured with texture number (int)row[1] - 1.  0 (the default) and -1 (what Scene.add_obj writes for "none") mean
+ *   untextured; an emitter's row ignores its slot (emission is never textured).  With T == 0 nothing is textured, whatever the rows hold.  A row that is
+ *   not an emitter's and names a texture beyond T is refused (TIRT_ERR_ARG) by tirt_scene_upload, tirt_material_upload and tirt_texture_upload alike, so
+ *   that the device never needs the count.
+ * Texel format: a texture is w x h packed texels exactly as the environment image: i32 (R<<16)|(G<<8)|B, index x*h + y, y = 0 the bottom image row
+ *   (Texture.load_image), and a wrap flag: 0 clamp, 1 repeat.
+ * tex_albedo(tex, u, v), all f32, one rounding per operation, no contraction (tests/texture_expected.py restates it; the device gives its bits):
+ *   1. finite(x) := |x| <= 3.4028234e38 (false for a NaN).  u = finite(u) ? u : 0; the same for v
+ *   2. wrap == 1:  u = u - floor(u);  v = v - floor(v)      (floor: t = (float)(int)x, t > x ? t - 1 : t; |x| < 2^31)
+ *   3. the reference's texture2D (texture/Texture.py:41-69) with this texture's w, h -- the function the environment lookup runs, on (buffer, w, h):
+ *        x = min(w - 1, max(0, u * w));  y = min(h - 1, max(0, v * h))   (w - 1 computed in f32);  lx = floor(x), ly = floor(y);  wlr = x - floor(x), wbt = y - floor(y)
+ *        sample(fx, fy): xi = clamp((int)fx, 0, w - 1), yi = clamp((int)fy, 0, h - 1), texel = buffer[xi*h + yi], (R, G, B) = ((texel >> 16) & 255, (texel >> 8) & 255, texel & 255) / 255.0f
+ *        lt = sample(lx, ly), rt = sample(lx + 1, ly), lb = sample(lx, ly + 1), rb = sample(lx + 1, ly + 1);  mix(a, b, t) = a * (1 - t) + b * t per channel
+ *        c = mix(mix(lt, rt, wlr), mix(lb, rb, wlr), wbt)
+ *   c is an encoded (sRGB-valued) colour, in the space of a material row's colour.  uv = (0, 0) reads texel (0, 0) with weight exactly 1.
+ * Where c goes, at a hit on a textured material: k_shade's reflect_color = srgb_to_lrgb(c) instead of srgb_to_lrgb(material colour) (PT_RGB.py:86), in the
+ *   NEE contribution and the continuation's throughput; TIRT_AOV_ALBEDO and TIRT_DEBUG_ALBEDO = c instead of the row's words 2..4.
+ *   The hit's uv is (t1*a + t2*b) + t3*c per component over the vertex rows' columns 6, 7 (a = 1 - u - v, b = u, c = v of the hit record), as
+ *   Scene.hit_attributes (Scene.py:537-561) interpolates it; column 8 is not used.  Analytic shapes have uv 0.
+ * Kernels: a textured scene sets bit 128 of the feature word (tirt_shade_features) and is shaded by an instantiation of k_shade of its own, the generic
+ *   kernel plus the lookup behind a test of the material row; the shading records then carry the three vertex uvs in words that are otherwise zero
+ *   (tirt_shade_table_download).  A scene without a textured material runs the kernels and produces the bits it did before textures existed.
+ *   tirt_vertex_update and tirt_vertex_update_device write columns 0..5 of the vertex rows: uvs survive them.
+ * tirt_bdpt_rgb_render, tirt_pt_spec_render and tirt_bdpt_spec_render return TIRT_ERR_ARG while the feature word has bit 128 (textures there are out of
+ *   scope); tirt_texture_upload with count 0 clears it.
+ * tirt_texture_upload: replaces all textures by `count` new ones; texture i is the w[i]*h[i] texels from texels + offset[i], `total` = the ints at `texels`.
+ *   count == 0 removes all textures (the pointers may be NULL).  TIRT_ERR_ARG before anything is written, the old textures staying: w or h < 1, a wrap
+ *   flag other than 0 / 1, texels that run past `total` or overlap another texture's, total >= 2^31 - 4 * count, a material row that names a texture
+ *   beyond count (see above).  The first three need no context.  Waits for work in flight and for the copy, as tirt_env_upload.  Textures outlive
+ *   tirt_scene_upload exactly as the environment image does; the feature word follows every texture and material upload.
+ * tirt_kat_texture: known-answer entry (tests/test_gpu_texture.py).  in, 3 words per row: texture number (its bits), u, v; out, 6 words: c3,
+ *   srgb_to_lrgb(c)3.  One launch, row i on thread i.  TIRT_ERR_ARG: in_stride < 3, out_stride < 6, no textures, a number outside [0, count). */
+int tirt_texture_upload(tirt_ctx *ctx, int count, const int32_t *texels, int64_t total, const int64_t *offset, const int32_t *w, const int32_t *h,
+                        const int32_t *wrap);
+int tirt_kat_texture(tirt_ctx *ctx, const float *in, int in_stride, float *out, int out_stride, int n);
+
 /* The scene feature word: which shading code the uploaded tables can reach, and so which instantiation of the shading kernels a render
  * launches (option "shade_specialize").  Bits: 1 a MAT_GLASS material row, 2 environment lit (power != 0 or a texel that is not black),
- * 4 / 32 / 8 / 64 a triangle / a sphere / a spot or laser / an emitter of unknown kind on the light list, 16 light_count == 0.
- * tirt_shade_features: out[0] = the word the context holds (refreshed by every scene, material, environment and vertex upload),
+ * 4 / 32 / 8 / 64 a triangle / a sphere / a spot or laser / an emitter of unknown kind on the light list, 16 light_count == 0,
+ * 128 a material row that is not an emitter's names an uploaded albedo texture (never set by tirt_shade_features_host, which sees no textures).
+ * tirt_shade_features: out[0] = the word the context holds (refreshed by every scene, material, environment, texture and vertex upload),
  * out[1] = the "shade_specialize" option.  tirt_shade_features_host: the same rule on host tables, without a context or a device
  * (env may be NULL: lit if env_power != 0). */
 int tirt_shade_features(tirt_ctx *ctx, uint32_t *out);
@@ -183,7 +223,7 @@ int tirt_vertex_download(tirt_ctx *ctx, float *vertex);
 /* Move whole triangles of the uploaded scene in place (csrc/tirt_dynamic.hip): vertices first ..
  * first + count - 1 (multiples of 3) get position and normal, row i at pos + i * pos_stride floats; nrm == NULL: Scene.cal_normal's face
  * normals.  Host pointers, or (_device) memory of ctx's device, ordered after `stream`; the rows must not change during the call.  Waits for
- * all batches first and for its own work; tirt_lbvh_build must follow.  The scene box becomes the fminf / fmaxf box of ALL vertex rows
+ * all batches first and for its own work; tirt_lbvh_build must follow.  Columns 6..8 of the rows (the uvs of albedo textures) are not written: they survive.  The scene box becomes the fminf / fmaxf box of ALL vertex rows
  * (rows left non-finite by tirt_scene_upload are ignored; which zero a +-0 corner gets is not defined).  TIRT_ERR_ARG before anything is
  * queued (range, stride, pointer kind, capturing stream, no scene) or written (a NaN / infinite position): the old build stays usable. */
 int tirt_vertex_update(tirt_ctx *ctx, int64_t first, int64_t count, const float *pos, int64_t pos_stride,
@@ -246,7 +286,7 @@ int tirt_pt_spec_render(tirt_ctx *ctx, uint32_t frame_begin, int frame_count, ui
 /* Debug.render (integrator/Debug.py:44-67): for every pixel of this context's tiles, the camera ray of `frame` (jittered iff
  * frame != 0, the same ray as tirt_pt_rgb_render's at that frame and seed), its closest hit, and hdr[i, j] OVERWRITTEN with one
  * view of that hit -- (0, 0, 0) on a miss, no running mean:
- *   TIRT_DEBUG_ALBEDO   the material colour, words 2..4 (:65)
+ *   TIRT_DEBUG_ALBEDO   the material colour, words 2..4 (:65); on a textured material tex_albedo at the hit's uv (tirt_texture_upload)
  *   TIRT_DEBUG_FNORMAL  (faceforward(normal, -direction, gnormal) + 1) * 0.5 (:62)
  *   TIRT_DEBUG_NORMAL   (normal + 1) * 0.5 (:63)
  *   TIRT_DEBUG_GNORMAL  (gnormal + 1) * 0.5 (:64)
@@ -270,7 +310,7 @@ int tirt_film_import_device(tirt_ctx *ctx, const void *dev_src);
 /* Feature buffers of the path tracer (csrc/tirt_aov.hip; no reference counterpart).  While enabled, every frame of tirt_pt_rgb_render /
  * tirt_pt_spec_render also folds, per pixel of this context's tiles, the closest hit of that frame's camera ray into TIRT_AOV_WORDS f32 with the
  * film's running mean (integrator/PT_RGB.py:134-136), frames in ascending order:
- *   TIRT_AOV_ALBEDO  3 words: the material colour as TIRT_DEBUG_ALBEDO reads it (no sRGB conversion)
+ *   TIRT_AOV_ALBEDO  3 words: the material colour, or the albedo texture's, as TIRT_DEBUG_ALBEDO reads it (no sRGB conversion)
  *   TIRT_AOV_NORMAL  3 words: the shading normal as TIRT_DEBUG_NORMAL reads it, NOT mapped to [0, 1] and not face-forwarded (a NaN stays a NaN)
  *   TIRT_AOV_DEPTH   1 word : the hit distance t
  *   TIRT_AOV_ALPHA   1 word : 1
@@ -622,7 +662,8 @@ int tirt_kat_spec(tirt_ctx *ctx, int which, const float *in, int in_stride, floa
 /* The tables k_shade reads instead of recomputing what depends on a primitive or a light alone (tests/test_gpu_shade_tables.py).  They are built on
  * the device after a scene upload, a material upload or tirt_process_normal, by the first call that needs them.
  * tirt_shade_table_download: which 0 the shading records, 32 floats (128 bytes) per primitive -- triangles (v1, bits mat) (v2, bits 1) (v3, -) (n1, -) (n2, -)
- *   (n3, -) (gnor, area) -; shapes (centre, bits mat) (radius, type, area, bits 2) --, which 1 the light records, 32 floats per entry of the light list --
+ *   (n3, -) (gnor, area) -, and while the feature word has bit 128 (a textured scene) the vertex uvs in three of the free places: (v3, t3.u) (n1, t3.v) and the
+ *   last quad (t1.u, t1.v, t2.u, t2.v); shapes (centre, bits mat) (radius, type, area, bits 2) --, which 1 the light records, 32 floats per entry of the light list --
  *   triangles (v1, area) (v3 - v1, choice pdf) (v2 - v1, bits -1) (n1, emission.r) (n2, .g) (n3, .b); shapes (centre, area) (shape[4], shape[5], -, choice pdf)
  *   (-, -, -, bits type) (shape[7..9], emission.r) (-, .g) (-, .b).  floats: the size of out, which must be the table's.
  * tirt_kat_shade_tables: the un-hoisted device functions.  which 0, n = primitives: out 4 per primitive, gnor3 (zero for shapes), Scene.get_prim_area;
@@ -635,13 +676,13 @@ int tirt_kat_shade_tables(tirt_ctx *ctx, int which, const float *in, float *out,
 /* One shading step of PT_RGB (integrator/PT_RGB.py:66-132 between a closest hit and the next: emission with MIS, glass / Disney, the NEE set-up, the next ray, the
  * miss) by the body of one instantiation of k_shade, on the context's own tables (shading and light records, material colours, environment) -- for
  * tests/test_gpu_shade_step.py against the CPU oracle's orc_kat_shade_step.  One launch, row i on thread i.
- * feat: the feature word of the instantiation -- 32 (sphere lights), 4 (mesh lights) or 127 (generic), the ones a render picks from (tirt_shade_features).
+ * feat: the feature word of the instantiation -- 32 (sphere lights), 4 (mesh lights), 127 (generic) or 255 (generic + albedo textures), the ones a render picks from (tirt_shade_features).
  * in, 23 words per row (integers as their bit patterns): seed, pixel, frame, bounce, last_bounce; origin3, direction3; t, u, v, prim (t >= 1e6: a miss, prim unused);
  *   throughout3, radiance3, brdf_pdf, perfect_spec.  NaN and infinity in the ray, the barycentrics and the state are data.
  * out, 28 words per row: radiance3, shaded, want_next, next_o3, next_d3, next_thr3, next_pdf, next_spec, want_shadow, sh_o3, sh_d3, sh_c3, sh_expect, sh_dist -- what
  *   k_shade writes to the path state and the shadow-ray queue; a field the step does not set is 0, sh_expect -2.  sh_c counts if the shadow ray finds sh_expect first.
- * TIRT_ERR_ARG before anything is launched: in_stride < 23, out_stride < 28, a feat that is not one of the three (both also with a NULL ctx), a feat that does not
- * cover the context's feature word, a hit row (t < 1e6) whose prim is outside [0, n_prims), a pixel outside [0, 2^31 - 1). */
+ * TIRT_ERR_ARG before anything is launched: in_stride < 23, out_stride < 28, a feat that is not one of the four (both also with a NULL ctx), a feat that does not
+ * cover the context's feature word, feat 255 on a context without uploaded textures, a hit row (t < 1e6) whose prim is outside [0, n_prims), a pixel outside [0, 2^31 - 1). */
 int tirt_kat_shade_step(tirt_ctx *ctx, uint32_t feat, const float *in, int in_stride, float *out, int out_stride, int n);
 
 /* ---- native Wavefront OBJ/MTL ingest (host only; no device, no context) -----------------------------
@@ -659,6 +700,9 @@ int tirt_obj_material_count(const tirt_obj *obj);
 int tirt_obj_material_info(const tirt_obj *obj, int index, char *name, int name_cap, double *params, int *vertex_format,
                            int *is_default, long long *n_floats);
 int tirt_obj_material_vertices(const tirt_obj *obj, int index, double *out, long long n_floats);
+/* the image of the material's map_Kd statement (options before the file name skipped), resolved against the directory of the MTL file, NUL-terminated
+ * into path[cap]; the empty string when the material has none.  TIRT_ERR_ARG when cap is too small. */
+int tirt_obj_material_texture(const tirt_obj *obj, int index, char *path, int cap);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,11 @@ The reference ingests meshes through the third-party ``pywavefront`` package
   ``T2F_V3F``, ``N3F_V3F`` or ``V3F``;
 * polygons are fan-triangulated as (v0, v[k-1], v[k]);
 * material defaults: diffuse .8, emissive 0, transparency (``d``) 1.0, optical_density
-  (``Ni``) 1.0, shininess (``Ns``) 0.0, texture None.
+  (``Ni``) 1.0, shininess (``Ns``) 0.0, texture None;
+* ``map_Kd [options] file`` sets ``texture`` to the image's path, resolved against the directory
+  of the MTL file (an extension: PyWavefront makes a Texture object there, on which the
+  reference's ``Scene.add_obj`` fails).  Options before the file name are skipped: ``-o`` / ``-s`` /
+  ``-t`` with their one to three numbers, ``-mm`` with two arguments, every other ``-option`` with one.
 
 The reference's committed ``nodelist.txt`` pins the material order + grouping for
 ``cornell_box.obj`` (tests/test_oracle_golden.py); the fan order is unpinned.
@@ -55,6 +59,48 @@ class ObjMaterial:
         return {"T2F_N3F_V3F": 8, "T2F_V3F": 5, "N3F_V3F": 6, "V3F": 3}.get(self.vertex_format, 0)
 
 
+def _is_number(tok):
+    """a plain decimal number, [+-] digits [. digits] [e [+-] digits] (csrc/tirt_obj.hip, is_number: the two parsers must agree)"""
+    i, n, digits = 0, len(tok), 0
+    if i < n and tok[i] in "+-":
+        i += 1
+    while i < n and tok[i] in "0123456789":
+        i += 1; digits += 1
+    if i < n and tok[i] == ".":
+        i += 1
+        while i < n and tok[i] in "0123456789":
+            i += 1; digits += 1
+    if not digits:
+        return False
+    if i < n and tok[i] in "eE":
+        i += 1
+        if i < n and tok[i] in "+-":
+            i += 1
+        ed = 0
+        while i < n and tok[i] in "0123456789":
+            i += 1; ed += 1
+        if not ed:
+            return False
+    return i == n
+
+
+def _map_file(tok):
+    """the file name of a ``map_Kd`` statement: the tokens behind its options (the last token is never an option's argument)"""
+    k = 1
+    while k + 1 < len(tok) and len(tok[k]) > 1 and tok[k][0] == "-":
+        opt = tok[k]
+        k += 1
+        if opt in ("-o", "-s", "-t"):
+            a = 0
+            while a < 3 and k + 1 < len(tok) and _is_number(tok[k]):
+                k += 1; a += 1
+        else:
+            a = 0
+            while a < (2 if opt == "-mm" else 1) and k + 1 < len(tok):
+                k += 1; a += 1
+    return " ".join(tok[k:])
+
+
 def _parse_mtl(path, materials):
     cur = None
     with open(path, "r", errors="replace") as fh:
@@ -84,8 +130,12 @@ def _parse_mtl(path, materials):
                 cur.optical_density = float(tok[1])
             elif key == "Ns":
                 cur.shininess = float(tok[1])
-            # map_Kd etc.: the reference would call float() on a Texture object and fail
-            # (Scene.py:86-87); textures on materials are out of scope.
+            elif key == "map_Kd":
+                # (the reference would call float() on PyWavefront's Texture object and fail, Scene.py:86-87)
+                name = _map_file(tok)
+                if not name:
+                    raise ValueError("map_Kd without a file name (%s)" % path)
+                cur.texture = name if (name.startswith("/") or "/" not in path) else path[:path.rindex("/")] + "/" + name
 
 
 class Wavefront:
@@ -121,6 +171,9 @@ class Wavefront:
                 flat = np.zeros(nfl.value, dtype=np.float64)
                 _native.check(L.tirt_obj_material_vertices(h, i, flat, nfl.value))
                 m._flat = flat
+                tex = C.create_string_buffer(4096)
+                _native.check(L.tirt_obj_material_texture(h, i, tex, 4096))
+                m.texture = os.fsdecode(tex.value) if tex.value else None
                 self.materials[m.name] = m
         finally:
             L.tirt_obj_free(h)

@@ -64,6 +64,8 @@ class Scene:
 
         self.env = TX.Texture()
         self.env_power = 0.0
+        self.textures = []              # albedo textures (add_texture): (Texture, wrap flag), id = index + 1
+        self._texture_ids = {}          # (absolute path, wrap flag) -> id
         self.bvh = None
 
         self._device_id = device_id
@@ -124,6 +126,8 @@ class Scene:
                 material.setExtinciton(src.shininess)
                 material.setColor(src.diffuse)
             material.alebdoTex = -1
+            if src.texture is not None and material.type != SCD.MAT_LIGHT:
+                material.alebdoTex = self.add_texture(src.texture)          # map_Kd
             self.material_cpu.append(material)
 
             flat = src.vertices
@@ -175,6 +179,32 @@ class Scene:
         # quirk B16); here the argument is honoured.
         self.env.load_image(filename)
         self.env_power = env_power
+
+    def add_texture(self, image, wrap="repeat"):
+        """Extension (the reference never samples a texture for a surface): an albedo texture for materials.  ``image`` is a path, decoded as
+        ``add_env`` decodes its image, or an ``(h, w, 3)`` uint8 array with row 0 the top of the image; ``wrap`` is "repeat" or "clamp".
+        Returns the texture's 1-based id: the value to put into ``Material.alebdoTex`` (0 and -1 mean no texture).  The same path with
+        the same wrap mode gives the same id.  Textures go to the device with the scene (``setup_data_gpu``); PT_RGB, its feature
+        buffers and the Debug albedo view use them, the BDPT and spectral integrators refuse a textured scene (include/tirt.h)."""
+        if wrap not in ("repeat", "clamp"):
+            raise ValueError("Scene.add_texture: wrap must be 'repeat' or 'clamp', got %r" % (wrap,))
+        flag = 1 if wrap == "repeat" else 0
+        tex = TX.Texture()
+        if isinstance(image, (str, bytes, os.PathLike)):
+            path = os.path.abspath(os.fsdecode(image))
+            if (path, flag) in self._texture_ids:
+                return self._texture_ids[(path, flag)]
+            if not os.path.isfile(path):
+                raise FileNotFoundError("Scene.add_texture: no such image file: %s" % path)
+            tex.load_image(path)
+            self._texture_ids[(path, flag)] = len(self.textures) + 1
+        else:
+            arr = np.asarray(image)
+            if arr.ndim != 3 or arr.shape[2] != 3 or arr.dtype != np.uint8 or arr.shape[0] < 1 or arr.shape[1] < 1:
+                raise ValueError("Scene.add_texture: an image array must be (h, w, 3) uint8, got %s %s" % (arr.dtype, arr.shape))
+            tex.load_array(arr)
+        self.textures.append((tex, flag))
+        return len(self.textures)
 
     def add_shape(self, shape, mat):
         """Scene.py:188-205.  Does not extend the scene AABB (quirk B8)."""
@@ -254,9 +284,13 @@ class Scene:
     def setup_data_gpu(self):
         """Scene.py:299-310: uploads, then the device LBVH build."""
         ctx = self.ctx
+        # textures outlive a scene upload on the device, and a material row may only name an uploaded one: the old ones go first, the new ones follow the rows
+        ctx.texture_upload([])
         ctx.scene_upload(self.vertex_np, self.primitive_np, self.material_np, self.shape_np,
                          self.light_np, self.light_count, self.minboundarynp, self.maxboundarynp)
         self.env.setup_data_gpu(ctx, self.env_power)
+        if self.textures:
+            ctx.texture_upload([(tex.np_img, flag) for tex, flag in self.textures])
         self.bvh.setup_data_gpu(self.vertex, self.shape, self.primitive)
 
     # -- kernels ------------------------------------------------------------------------------------

@@ -76,7 +76,8 @@ MOTION_WORDS = 8
 # bits of the scene feature word (include/tirt.h, tirt_shade_features)
 SF_GLASS, SF_ENV, SF_LIGHT_TRI, SF_LIGHT_SPOT_LASER, SF_NO_LIGHT, SF_LIGHT_SPHERE, SF_LIGHT_OTHER = 1, 2, 4, 8, 16, 32, 64
 SF_ALL = 127
-SHADE_INSTANTIATIONS = (SF_LIGHT_SPHERE, SF_LIGHT_TRI, SF_ALL)      # the feature words k_shade / k_shade_spec are compiled for, narrowest first
+SF_TEXTURE = 128                                                    # a textured material (tirt_texture_upload); not part of SF_ALL
+SHADE_INSTANTIATIONS = (SF_LIGHT_SPHERE, SF_LIGHT_TRI, SF_ALL, SF_ALL | SF_TEXTURE)      # the feature words k_shade / k_shade_spec are compiled for, narrowest first
 KAT_STEP_IN, KAT_STEP_OUT = 23, 28                                  # words per row of tirt_kat_shade_step
 
 # context options that select code rather than tune it: name -> (default, meaning).  (The tuning options are listed in include/tirt.h.)
@@ -98,6 +99,8 @@ SIGNATURES = {
                                     _f32p, C.c_int, _i32p, C.c_int, C.c_int, _f32p, _f32p]),
     "tirt_material_upload": (C.c_int, [_vp, _f32p, C.c_int]),
     "tirt_env_upload": (C.c_int, [_vp, _i32p, C.c_int, C.c_int, C.c_float]),
+    "tirt_texture_upload": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
+    "tirt_kat_texture": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
     "tirt_shade_features": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "tirt_shade_features_host": (C.c_int, [_f32p, C.c_int, _i32p, C.c_int, _f32p, C.c_int, _i32p, C.c_int, _vp, C.c_int, C.c_int, C.c_float,
                                            C.POINTER(C.c_uint32)]),
@@ -150,6 +153,7 @@ SIGNATURES = {
     "tirt_obj_material_count": (C.c_int, [_vp]),
     "tirt_obj_material_info": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int),
                                          C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
+    "tirt_obj_material_texture": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_int]),
     "tirt_obj_material_vertices": (C.c_int, [_vp, C.c_int, np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS"), C.c_longlong]),
 }
 
@@ -387,6 +391,18 @@ class Context:
     def env_upload(self, packed, power):
         packed = np.ascontiguousarray(packed, np.int32)
         check(lib().tirt_env_upload(self.handle, packed.reshape(-1), packed.shape[0], packed.shape[1], float(power)))
+
+    def texture_upload(self, textures):
+        """include/tirt.h, tirt_texture_upload: `textures` is a sequence of (packed [w, h] int32 as Texture.np_img, wrap 0 clamp / 1 repeat); empty: remove all"""
+        texture_upload(self.handle, textures)
+
+    def kat_texture(self, rows, out_stride=6):
+        """include/tirt.h, tirt_kat_texture: rows (n, >= 3) of 32-bit words (texture number as its bits, u, v) -> (n, out_stride) float32: c3, srgb_to_lrgb(c)3"""
+        rows = np.ascontiguousarray(rows).view(np.float32)
+        n, stride = rows.shape
+        out = np.zeros((n, max(int(out_stride), 1)), np.float32)
+        check(lib().tirt_kat_texture(self.handle, rows.reshape(-1), int(stride), out.reshape(-1), int(out_stride), n))
+        return out
 
     def shade_features(self):
         """(feature word, shade_specialize option) of the context: include/tirt.h, tirt_shade_features"""
@@ -803,6 +819,23 @@ def kat_shade_step(handle, feat, rows, out_stride=KAT_STEP_OUT, in_stride=None):
     out = np.zeros((n, max(int(out_stride), 1)), np.float32)
     check(lib().tirt_kat_shade_step(handle, int(feat), rows.reshape(-1), int(stride if in_stride is None else in_stride), out.reshape(-1), int(out_stride), n))
     return out
+
+
+def texture_upload(handle, textures):
+    """tirt_texture_upload on a raw context handle (None: only the refusals that need no context can be reached): the textures packed back to back"""
+    imgs = [np.ascontiguousarray(img, np.int32) for img, _ in textures]
+    for img in imgs:
+        if img.ndim != 2:
+            raise ValueError("texture_upload: a texture is a [w, h] array of packed texels (Texture.np_img), got shape %s" % (img.shape,))
+    n = len(imgs)
+    w = np.asarray([img.shape[0] for img in imgs], np.int32)
+    h = np.asarray([img.shape[1] for img in imgs], np.int32)
+    wrap = np.asarray([int(wr) for _, wr in textures], np.int32)
+    sizes = np.asarray([img.size for img in imgs], np.int64)
+    offset = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64) if n else np.zeros(0, np.int64)
+    texels = np.concatenate([img.reshape(-1) for img in imgs]) if n else np.zeros(0, np.int32)
+    check(lib().tirt_texture_upload(handle, n, _ptr(texels) if n else None, int(texels.size), _ptr(offset) if n else None,
+                                    _ptr(w) if n else None, _ptr(h) if n else None, _ptr(wrap) if n else None))
 
 
 def shade_features_host(material, primitive, shape, light, light_count, env=None, env_power=0.0):

@@ -4,7 +4,7 @@
 // PathState::hit[0 .. S) holds the closest hit of every camera ray and PathSoA st[0].dx / dy / dz its direction, on both routes (k_trace alone,
 // or the candidate lists + leftover k_trace + scatter); both stay as they are until bounce 1.  k_aov is one more reader of them: per local pixel
 // it folds the F samples of the batch, in frame order, into the pixel's TIRT_AOV_WORDS running means with k_film's recurrence
-// (integrator/PT_RGB.py:134-136).  The values are k_debug_resolve's (tirt_debug.hip): the same material row, the same hit_attributes call.
+// (integrator/PT_RGB.py:134-136).  The values are k_debug_resolve's (tirt_debug.hip): the same material row (or albedo texture), the same hit_attributes call.
 //
 // Batches run on different lanes and the recurrence is order dependent, so the k_aov launches are chained through events of their own
 // (Lane::aov_done, tirt_ctx::last_aov) -- not through last_film, which is recorded at the END of a batch and would serialise the lanes.
@@ -43,7 +43,10 @@ __global__ __launch_bounds__(256) void k_aov(SceneView sc, v3 eye, TileMap tm, i
             const int prim = __float_as_int(h.w);
             const float *m = sc.material + (size_t)sc.primitive[(size_t)prim * PRI_VEC + 2] * MAT_VEC;
             alb = V(m[2], m[3], m[4]);
-            nor = hit_attributes(sc, eye, d, prim, h.x, h.y, h.z).nor;
+            const HitAttr a = hit_attributes(sc, eye, d, prim, h.x, h.y, h.z);
+            nor = a.nor;
+            // a textured material: the texture's colour at the hit's uv (tirt_device.h, tex_albedo), as k_shade's reflectance before srgb_to_lrgb
+            if (sc.tex) { const int ti = material_texture(m); if (ti >= 0) alb = tex_albedo(sc.tex, ti, a.tex.x, a.tex.y); }
             depth = h.x; alpha = 1.0f;
         }
         const float frame = (float)(int)(frame_begin + (uint32_t)f);

@@ -3,6 +3,7 @@
 #include "tirt_internal.h"
 #include "tirt_spectral.h"
 #include <stddef.h>
+#include <algorithm>
 #include <mutex>
 #include <string.h>
 
@@ -17,6 +18,7 @@ SceneView scene_view(const tirt_ctx *c)
     s.vertex = c->vertex.as<float>(); s.primitive = c->primitive.as<int>(); s.material = c->material.as<float>();
     s.shape = c->shape.as<float>(); s.light = c->light.as<int>(); s.env = c->env.as<int>();
     s.mat_lrgb = c->mat_lrgb.as<float>(); s.shade_rec = c->shade_rec.as<float4>(); s.light_rec = c->light_rec.as<float4>();
+    s.tex = c->tex_count > 0 ? c->tex.as<int>() : nullptr;
     s.n = c->n; s.light_count = c->light_count; s.env_w = c->env_w; s.env_h = c->env_h; s.env_power = c->env_power;
     return s;
 }
@@ -74,7 +76,8 @@ static int refresh_material_table(tirt_ctx *c)
 
 // ---- 128-byte shading record per primitive (tirt_device.h, hit_attributes_rec) -----------------------
 // gnor and area: the expressions of hit_attributes (Scene.py:537-561) and get_prim_area (Scene.py:324-350), evaluated here once per primitive
-__global__ void k_shade_records(SceneView s, float4 *rec)
+// textured (the scene's feature word has SF_TEXTURE): the uvs of the three vertices go into the free words; otherwise those stay zero
+__global__ void k_shade_records(SceneView s, float4 *rec, int textured)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= s.n) return;
@@ -92,6 +95,11 @@ __global__ void k_shade_records(SceneView s, float4 *rec)
         r[2] = make_float4(v3_.x, v3_.y, v3_.z, 0.0f);
         r[3] = make_float4(n1.x, n1.y, n1.z, 0.0f); r[4] = make_float4(n2.x, n2.y, n2.z, 0.0f); r[5] = make_float4(n3.x, n3.y, n3.z, 0.0f);
         r[6] = make_float4(gnor.x, gnor.y, gnor.z, area);
+        if (textured) {
+            const v3 t1 = vtx_uv(s, pr[1]), t2 = vtx_uv(s, pr[1] + 1), t3 = vtx_uv(s, pr[1] + 2);
+            r[2].w = t3.x; r[3].w = t3.y;
+            r[7] = make_float4(t1.x, t1.y, t2.x, t2.y);
+        }
     } else {
         const float *sh = s.shape + (size_t)pr[1] * SHA_VEC;
         r[0] = make_float4(sh[1], sh[2], sh[3], mat); r[1] = make_float4(sh[4], sh[0], area, __int_as_float(2));
@@ -146,10 +154,33 @@ static bool env_is_lit(const int32_t *texel, size_t count, float power)
     for (size_t k = 0; k < count; k++) if (texel[k] & 0x00FFFFFF) return true;      // (tex_sample reads the low 24 bits)
     return false;
 }
-static unsigned shade_features_core(const float *material, int nm, const int *light_kind, int light_count, bool env_lit)
+// the slot a material row names (row[1] as the device's (int) conversion reads it: saturating, NaN -> 0): >= 1 names texture slot - 1
+static int material_texture_slot(const float *row)
+{
+    const float s = row[1];
+    return s >= 2147483648.0f ? 0x7fffffff : s >= 1.0f ? (int)s : 0;
+}
+// every material row that is not an emitter's names no texture, or one of the tex_count uploaded ones (tex_count == 0: nothing is textured, nothing to check)
+static int check_material_textures(const char *fn, const float *material, int nm, int tex_count)
+{
+    if (tex_count <= 0) return TIRT_OK;
+    for (int i = 0; i < nm; i++) {
+        const float *row = material + (size_t)i * MAT_VEC;
+        TIRT_REQUIRE((int)row[0] == MAT_LIGHT || material_texture_slot(row) <= tex_count,
+                     std::string(fn) + ": material " + std::to_string(i) + " names texture " + std::to_string(material_texture_slot(row)) + " of " + std::to_string(tex_count) +
+                     " uploaded (slot 1 of the row: 0 or -1 = none; tirt_texture_upload with count 0 removes all textures)");
+    }
+    return TIRT_OK;
+}
+static unsigned shade_features_core(const float *material, int nm, const int *light_kind, int light_count, bool env_lit, int tex_count = 0)
 {
     unsigned f = 0u;
     for (int i = 0; i < nm; i++) if ((int)material[(size_t)i * MAT_VEC] == MAT_GLASS) f |= SF_GLASS;
+    for (int i = 0; i < nm && tex_count > 0; i++) {
+        const float *row = material + (size_t)i * MAT_VEC;
+        const int slot = material_texture_slot(row);
+        if ((int)row[0] != MAT_LIGHT && slot >= 1 && slot <= tex_count) f |= SF_TEXTURE;
+    }
     if (env_lit) f |= SF_ENV;
     if (light_count <= 0) f |= SF_NO_LIGHT;
     for (int i = 0; i < light_count; i++) {
@@ -161,14 +192,14 @@ static unsigned shade_features_core(const float *material, int nm, const int *li
 void refresh_shade_features(tirt_ctx *c)
 {
     c->shade_features = c->h_material.empty() ? SF_ALL
-        : shade_features_core(c->h_material.data(), c->nm, c->h_light_kind.data(), c->light_count, c->env_lit);
+        : shade_features_core(c->h_material.data(), c->nm, c->h_light_kind.data(), c->light_count, c->env_lit, c->tex_count);
 }
 
 int ensure_shade_records(tirt_ctx *c)
 {
     if (!(c->shade_rec_valid && c->shade_rec.p)) {
         if (c->shade_rec.ensure(sizeof(float4) * 8 * (size_t)c->n)) return TIRT_ERR_HIP;
-        hipLaunchKernelGGL(k_shade_records, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, scene_view(c), c->shade_rec.as<float4>());
+        hipLaunchKernelGGL(k_shade_records, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, scene_view(c), c->shade_rec.as<float4>(), (c->shade_features & SF_TEXTURE) ? 1 : 0);
         c->shade_rec_valid = true;
     }
     if (!(c->light_rec_valid && c->light_rec.p)) {
@@ -423,6 +454,18 @@ static void drain_render_events(tirt_ctx *c)
     c->ev_pool.clear();
 }
 
+// ---- known-answer evaluation of tex_albedo (tirt_kat_texture): row i on thread i ----
+__global__ void k_kat_texture(const int *tex, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *a = in + (size_t)i * in_stride;
+    float *o = out + (size_t)i * out_stride;
+    const v3 c = tex_albedo(tex, __float_as_int(a[0]), a[1], a[2]);
+    const v3 l = srgb_to_lrgb(c);
+    o[0] = c.x; o[1] = c.y; o[2] = c.z; o[3] = l.x; o[4] = l.y; o[5] = l.z;
+}
+
 }  // namespace tirt
 
 using namespace tirt;
@@ -477,7 +520,7 @@ void tirt_destroy(tirt_ctx *c)
     (void)hipSetDevice(c->device);
     (void)sync_all(c);
     drain_render_events(c);
-    DevBuf *bufs[] = {&c->vertex, &c->primitive, &c->material, &c->shape, &c->light, &c->env, &c->mat_lrgb, &c->shade_rec, &c->light_rec, &c->morton_unsorted, &c->keys_a,
+    DevBuf *bufs[] = {&c->vertex, &c->primitive, &c->material, &c->shape, &c->light, &c->env, &c->tex, &c->mat_lrgb, &c->shade_rec, &c->light_rec, &c->morton_unsorted, &c->keys_a,
                       &c->keys_b, &c->vals_a, &c->vals_b, &c->hist, &c->morton_sorted, &c->bvh_node, &c->compact, &c->parent,
                       &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb, &c->aov, &c->mom, &c->mom_cnt, &c->pixset, &c->pixset_tmp, &c->tp_mem, &c->mv_rec, &c->mv_snap, &c->dn_mem, &c->dn_out,
                       &c->counters_mem, &c->spill, &c->trace_stage, &c->debug_mem, &c->query_mem, &c->dyn_mem, &c->dev_counters, &c->bdpt_px, &c->timeline, &c->pvb_set[0].count, &c->pvb_set[0].cand, &c->pvb_set[0].bound, &c->pvb_set[1].count, &c->pvb_set[1].cand, &c->pvb_set[1].bound, &c->pvb_stat, &c->pvb_tmp};
@@ -611,6 +654,7 @@ int tirt_scene_upload(tirt_ctx *c, const float *vertex, int nv, const int32_t *p
         TIRT_REQUIRE(pr[2] >= 0 && pr[2] < nm, "tirt_scene_upload: material index out of range");
     }
     for (int i = 0; i < nl; i++) TIRT_REQUIRE(light[i] >= 0 && light[i] < n, "tirt_scene_upload: light index out of range");
+    if (int rc = check_material_textures("tirt_scene_upload", material, nm, c->tex_count)) return rc;
     c->sphere_prims.clear(); c->sphere_geom.clear();
     for (int i = 0; i < n; i++) {
         const int32_t *pr = primitive + (size_t)i * 3;
@@ -647,9 +691,11 @@ int tirt_material_upload(tirt_ctx *c, const float *material, int nm)
     CTX(c);
     if (sync_all(c)) return TIRT_ERR_HIP;      // scene data must not change under batches still in flight
     TIRT_REQUIRE(material && nm == c->nm, "tirt_material_upload: material count differs from the uploaded scene");
+    if (int rc = check_material_textures("tirt_material_upload", material, nm, c->tex_count)) return rc;
     if (upload(c->material, material, sizeof(float) * 10 * (size_t)nm, c->stream)) return TIRT_ERR_HIP;
     if (refresh_material_table(c)) return TIRT_ERR_HIP;
     c->light_rec_valid = false;                // the light records carry the emitters' colours
+    c->shade_rec_valid = false;                // the shading records carry uvs iff a material is textured
     c->h_material.assign(material, material + (size_t)MAT_VEC * nm);
     refresh_shade_features(c);                 // (a material may have become glass, or stopped being it)
     TIRT_HIP(hipStreamSynchronize(c->stream));
@@ -667,6 +713,73 @@ int tirt_env_upload(tirt_ctx *c, const int32_t *rgb_packed, int w, int h, float 
     refresh_shade_features(c);
     TIRT_HIP(hipStreamSynchronize(c->stream));
     return TIRT_OK;
+}
+
+// One buffer for all textures: `count` quads (offset in ints from the buffer's start, w, h, wrap), then the caller's texels.
+int tirt_texture_upload(tirt_ctx *c, int count, const int32_t *texels, int64_t total, const int64_t *offset, const int32_t *w, const int32_t *h, const int32_t *wrap)
+{
+    // what needs no context first (and no device: these refusals hold for a null context too)
+    TIRT_REQUIRE(count >= 0 && count <= (1 << 20), "tirt_texture_upload: count outside 0 .. 2^20");
+    TIRT_REQUIRE(count == 0 || (texels && offset && w && h && wrap), "tirt_texture_upload: null pointer");
+    TIRT_REQUIRE(total >= 0 && total < ((int64_t)1 << 31) - 4 * (int64_t)count, "tirt_texture_upload: total outside 0 .. 2^31 - 4 * count (texels are indexed by int)");
+    std::vector<std::pair<int64_t, int64_t>> span((size_t)count);
+    for (int i = 0; i < count; i++) {
+        const std::string t = "tirt_texture_upload: texture " + std::to_string(i);
+        TIRT_REQUIRE(w[i] >= 1 && h[i] >= 1, t + ": w and h must be >= 1");
+        TIRT_REQUIRE(wrap[i] == 0 || wrap[i] == 1, t + ": wrap is 0 (clamp) or 1 (repeat)");
+        const int64_t sz = (int64_t)w[i] * h[i];
+        TIRT_REQUIRE(offset[i] >= 0 && offset[i] <= total && sz <= total - offset[i], t + ": its texels run past `total`");
+        span[(size_t)i] = {offset[i], offset[i] + sz};
+    }
+    std::sort(span.begin(), span.end());
+    for (int i = 1; i < count; i++) TIRT_REQUIRE(span[(size_t)i].first >= span[(size_t)i - 1].second, "tirt_texture_upload: two textures overlap");
+    CTX(c);
+    if (sync_all(c)) return TIRT_ERR_HIP;      // scene data must not change under batches still in flight
+    if (!c->h_material.empty())
+        if (int rc = check_material_textures("tirt_texture_upload", c->h_material.data(), c->nm, count)) return rc;
+    if (count > 0) {
+        std::vector<int32_t> table(4 * (size_t)count);
+        for (int i = 0; i < count; i++) {
+            table[4 * (size_t)i] = (int32_t)(4 * (int64_t)count + offset[i]); table[4 * (size_t)i + 1] = w[i];
+            table[4 * (size_t)i + 2] = h[i]; table[4 * (size_t)i + 3] = wrap[i];
+        }
+        const size_t tb = sizeof(int32_t) * table.size(), xb = sizeof(int32_t) * (size_t)total;
+        if (c->tex.ensure(tb + xb)) return TIRT_ERR_HIP;
+        TIRT_HIP(hipMemcpyAsync(c->tex.p, table.data(), tb, hipMemcpyHostToDevice, c->stream));
+        if (xb) TIRT_HIP(hipMemcpyAsync((char *)c->tex.p + tb, texels, xb, hipMemcpyHostToDevice, c->stream));
+        TIRT_HIP(hipStreamSynchronize(c->stream));      // (table is a local)
+    } else c->tex.release();
+    c->tex_count = count;
+    c->shade_rec_valid = false;                // the shading records carry uvs iff a material is textured
+    refresh_shade_features(c);
+    return TIRT_OK;
+}
+
+int tirt_kat_texture(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_texture: null pointer or negative n");
+    TIRT_REQUIRE(in_stride >= 3 && out_stride >= 6, "tirt_kat_texture: stride too small (3 words in, 6 out)");
+    CTX(c);
+    TIRT_REQUIRE(c->tex_count > 0, "tirt_kat_texture: no textures uploaded (tirt_texture_upload)");
+    for (int i = 0; i < n; i++) {
+        const int32_t id = ((const int32_t *)in)[(size_t)i * in_stride];
+        TIRT_REQUIRE(id >= 0 && id < c->tex_count, "tirt_kat_texture: row " + std::to_string(i) + ": texture number outside [0, count)");
+    }
+    if (n == 0) return TIRT_OK;
+    DevBuf din, dout;
+    int rc = TIRT_OK;
+    if (upload(din, in, sizeof(float) * (size_t)n * in_stride, c->stream) || dout.ensure(sizeof(float) * (size_t)n * out_stride)) rc = TIRT_ERR_HIP;
+    if (rc == TIRT_OK) {
+        hipError_t e = hipMemsetAsync(dout.p, 0, sizeof(float) * (size_t)n * out_stride, c->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_kat_texture, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->tex.as<int>(), din.as<float>(), in_stride, dout.as<float>(), out_stride, n);
+            e = hipMemcpyAsync(out, dout.p, sizeof(float) * (size_t)n * out_stride, hipMemcpyDeviceToHost, c->stream);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { set_error(std::string("tirt_kat_texture: ") + hipGetErrorString(e)); rc = TIRT_ERR_HIP; }
+    }
+    din.release(); dout.release();
+    return rc;
 }
 
 int tirt_shade_features(tirt_ctx *c, uint32_t *out)
@@ -1086,6 +1199,9 @@ static int submit_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uin
     if ((size_t)p.count * (size_t)(P > 0 ? P : 1) >= effective_merge_paths(c)) return flush_pending(c);
     return TIRT_OK;
 }
+// albedo textures are PT_RGB's (and the feature buffers', Debug's): the other integrators refuse a textured scene instead of rendering it flat
+#define NO_TEXTURES(c, fn)                                                         \
+    TIRT_REQUIRE(!((c)->shade_features & SF_TEXTURE), std::string(fn) + ": a material of the scene has an albedo texture (PT_RGB only): tirt_texture_upload with count 0 removes all textures")
 int tirt_pt_rgb_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed, int max_depth, int stack_size, int flags)
 {
     CTX_NOFLUSH(c);
@@ -1095,6 +1211,7 @@ int tirt_pt_spec_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint
 {
     CTX_NOFLUSH(c);
     TIRT_REQUIRE(c->spec_set && c->spec_view, "tirt_pt_spec_render: spectral tables not uploaded (tirt_spectral_upload)");
+    NO_TEXTURES(c, "tirt_pt_spec_render");
     return submit_render(c, frame_begin, frame_count, seed, max_depth, stack_size, flags, true);
 }
 
@@ -1102,12 +1219,14 @@ int tirt_bdpt_rgb_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uin
 {
     CTX(c);
     NO_PIXEL_SET(c, "tirt_bdpt_rgb_render");
+    NO_TEXTURES(c, "tirt_bdpt_rgb_render");
     return bdpt_render(c, frame_begin, frame_count, seed);
 }
 int tirt_bdpt_spec_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed)
 {
     CTX(c);
     NO_PIXEL_SET(c, "tirt_bdpt_spec_render");
+    NO_TEXTURES(c, "tirt_bdpt_spec_render");
     TIRT_REQUIRE(c->spec_set && c->spec_dev.p, "tirt_bdpt_spec_render: spectral tables not uploaded (tirt_spectral_upload)");
     return bdpt_render(c, frame_begin, frame_count, seed, true);
 }
@@ -1354,7 +1473,7 @@ int tirt_kat_shade_step(tirt_ctx *c, uint32_t feat, const float *in, int in_stri
     // what needs no context first (and no device: these refusals hold for a null context too)
     TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_shade_step: null pointer or negative n");
     TIRT_REQUIRE(in_stride >= 23 && out_stride >= 28, "tirt_kat_shade_step: stride too small (23 words in, 28 out)");
-    TIRT_REQUIRE(kat_shade_step_has_inst(feat), "tirt_kat_shade_step: feat is not an instantiation of k_shade (SF_LIGHT_SPHERE, SF_LIGHT_TRI, SF_ALL)");
+    TIRT_REQUIRE(kat_shade_step_has_inst(feat), "tirt_kat_shade_step: feat is not an instantiation of k_shade (SF_LIGHT_SPHERE, SF_LIGHT_TRI, SF_ALL, SF_ALL | SF_TEXTURE)");
     CTX(c);
     return kat_shade_step(c, feat, in, in_stride, out, out_stride, n);
 }

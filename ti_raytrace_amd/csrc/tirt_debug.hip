@@ -30,7 +30,7 @@ __global__ void k_debug_generate(CameraView cam, TileMap tm, int P, uint32_t fra
 }
 
 // integrator/Debug.py:55-67.  A miss writes (0, 0, 0).  On a hit:
-//   albedo   get_material_color(material, get_prim_mindex(primitive, prim_id))      (:65, UtilsFunc.py:132-133)
+//   albedo   get_material_color(material, get_prim_mindex(primitive, prim_id))      (:65, UtilsFunc.py:132-133); a textured material: tex_albedo at the hit's uv
 //   fnormal  (faceforward(normal, -direction, gnormal) + 1) * 0.5                   (:62; UtilsFunc.py:466-467: sign(dot(i, nref)) * n)
 //   normal   (normal + 1) * 0.5                                                     (:63)
 //   gnormal  (gnormal + 1) * 0.5                                                    (:64)
@@ -47,6 +47,10 @@ __global__ void k_debug_resolve(SceneView sc, v3 eye, TileMap tm, int P, int mod
         if (mode == TIRT_DEBUG_ALBEDO) {
             const float *m = sc.material + (size_t)sc.primitive[(size_t)prim * PRI_VEC + 2] * MAT_VEC;
             rad = V(m[2], m[3], m[4]);
+            if (sc.tex) {                                // a textured material: the texture's colour at the hit's uv (tirt_device.h, tex_albedo)
+                const int ti = material_texture(m);
+                if (ti >= 0) { const HitAttr a = hit_attributes(sc, eye, V(dx[k], dy[k], dz[k]), prim, h.x, h.y, h.z); rad = tex_albedo(sc.tex, ti, a.tex.x, a.tex.y); }
+            }
         } else {
             const v3 d = V(dx[k], dy[k], dz[k]);
             const HitAttr a = hit_attributes(sc, eye, d, prim, h.x, h.y, h.z);

@@ -54,6 +54,7 @@ struct SceneView {
     const float *mat_lrgb;   // [nm*3] srgb_to_lrgb(material colour), filled on device at upload
     const float4 *shade_rec; // [n*8] one 128-byte line per primitive: what k_shade needs to shade a hit on it (k_shade_records)
     const float4 *light_rec; // [light_count*8] one 128-byte line per entry of `light`: what sample_li needs of that emitter (k_light_records)
+    const int *tex;          // albedo textures (tirt_texture_upload): T quads (offset, w, h, wrap), then the packed texels; offset counts ints from `tex`.  nullptr: none
     int n, light_count, env_w, env_h;
     float env_power;
 };
@@ -71,6 +72,7 @@ enum : unsigned {
     SF_LIGHT_SPHERE = 32u,    // a sphere on the light list
     SF_LIGHT_OTHER = 64u,     // an emitter of no kind sample_li knows (it samples the origin): generic kernel only
     SF_ALL = 127u,
+    SF_TEXTURE = 128u,        // a material row that is not an emitter's names an uploaded albedo texture (not part of SF_ALL: untextured scenes keep their kernels)
     SF_LIGHT_KINDS = SF_LIGHT_TRI | SF_LIGHT_SPOT_LASER | SF_LIGHT_SPHERE | SF_LIGHT_OTHER
 };
 
@@ -206,13 +208,16 @@ TD HitAttr hit_attributes(const SceneView &s, v3 origin, v3 direction, int prim,
 
 // The same from the 128-byte shading record of the primitive (one cache line instead of a 12-byte primitive row plus three
 // 36-byte vertex rows in three more lines; exact copies of the same floats, so the same results):
-//   triangles: (v1.xyz, bits mat) (v2.xyz, bits PRIMITIVE_TRI) (v3.xyz, -) (n1.xyz, -) (n2.xyz, -) (n3.xyz, -) (gnor.xyz, area) -
+//   triangles: (v1.xyz, bits mat) (v2.xyz, bits PRIMITIVE_TRI) (v3.xyz, t3.u) (n1.xyz, t3.v) (n2.xyz, -) (n3.xyz, -) (gnor.xyz, area) (t1.u, t1.v, t2.u, t2.v)
 //   shapes   : (centre.xyz, bits mat) (radius, shape type, area, bits 2)
 // gnor = normalized(cross(v2 - v1, v3 - v1)) and area = get_prim_area depend on the primitive alone: k_shade_records evaluates them
 // once, with the very expressions of hit_attributes / get_prim_area (a cross product, five correctly rounded square roots and three
 // divisions less per shaded path).  A sphere's normal depends on the hit point and stays here; its gn IS its nn, so the one
 // normalisation serves both.
-// uv is not carried: the path tracer does not use it (the reference's albedo textures are unused, PT_RGB.py:86).
+// The uvs t1, t2, t3 of the three vertices (columns 6, 7 of their rows; column 8 is not carried) are in the record only while the scene is textured
+// (SF_TEXTURE); otherwise those words are zero, as they always were.  TEX -- the textured instantiation of k_shade alone -- reads them and returns
+// tex = (t1 * a + t2 * b) + t3 * c as hit_attributes does, .z = 0; every other caller gets tex = 0 and loads nothing more than before.  Shapes have uv 0.
+template <bool TEX = false>
 TD HitAttr hit_attributes_rec(const float4 *rec, v3 origin, v3 direction, int prim, float t, float u, float v, int &mat_id)
 {
     HitAttr h; h.pos = h.gnor = h.nor = h.tex = V(0.0f, 0.0f, 0.0f);
@@ -230,6 +235,10 @@ TD HitAttr hit_attributes_rec(const float4 *rec, v3 origin, v3 direction, int pr
         h.gnor = V(r6.x, r6.y, r6.z); h.area = r6.w;
         h.pos = (v1 * a + v2 * b) + v3_ * c;
         nn = (n1 * a + n2 * b) + n3 * c;
+        if constexpr (TEX) {
+            const float4 r7 = r[7];
+            h.tex = V((r7.x * a + r7.z * b) + r2.w * c, (r7.y * a + r7.w * b) + r3.w * c, 0.0f);
+        }
     } else if ((int)r1.y == SHAPE_SPHERE) {
         float c;
         (void)intersect_sphere(origin, direction, V(r0.x, r0.y, r0.z), r1.x, c);
@@ -632,27 +641,45 @@ TD float get_prim_angle(const SceneView &s, int index, v3 v)
     return tm_acos(ret);
 }
 
-// ---- texture/Texture.py:41-69 -------------------------------------------------------------------------------
-TD v3 tex_sample(const SceneView &s, float fx, float fy)
+// ---- texture/Texture.py:41-69: `sample` and `texture2D` on an image of w x h packed texels (the environment's, or one albedo texture's) ----
+TD v3 tex_sample(const int *img, int w, int h, float fx, float fy)
 {
     int x = (int)fx, y = (int)fy;
-    x = x < 0 ? 0 : (x > s.env_w - 1 ? s.env_w - 1 : x);
-    y = y < 0 ? 0 : (y > s.env_h - 1 ? s.env_h - 1 : y);
-    int RGBA = s.env[(size_t)x * s.env_h + y];
+    x = x < 0 ? 0 : (x > w - 1 ? w - 1 : x);
+    y = y < 0 ? 0 : (y > h - 1 ? h - 1 : y);
+    int RGBA = img[(size_t)x * h + y];
     float R = (float)((RGBA & 0x00FF0000) >> 16) / 255.0f;
     float G = (float)((RGBA & 0x0000FF00) >> 8) / 255.0f;
     float B = (float)(RGBA & 0x000000FF) / 255.0f;
     return V(R, G, B);
 }
-TD v3 texture2d(const SceneView &s, float u, float v)
+TD v3 texture2d(const int *img, int w, int h, float u, float v)
 {
-    float x = clampf(u * (float)s.env_w, 0.0f, (float)s.env_w - 1.0f);
-    float y = clampf(v * (float)s.env_h, 0.0f, (float)s.env_h - 1.0f);
+    float x = clampf(u * (float)w, 0.0f, (float)w - 1.0f);
+    float y = clampf(v * (float)h, 0.0f, (float)h - 1.0f);
     float lx = tm_floor(x), ly = tm_floor(y);
     float wbt = y - tm_floor(y), wlr = x - tm_floor(x);
-    v3 lt = tex_sample(s, lx, ly), rt = tex_sample(s, lx + 1.0f, ly);
-    v3 lb = tex_sample(s, lx, ly + 1.0f), rb = tex_sample(s, lx + 1.0f, ly + 1.0f);
+    v3 lt = tex_sample(img, w, h, lx, ly), rt = tex_sample(img, w, h, lx + 1.0f, ly);
+    v3 lb = tex_sample(img, w, h, lx, ly + 1.0f), rb = tex_sample(img, w, h, lx + 1.0f, ly + 1.0f);
     return mix3(mix3(lt, rt, wlr), mix3(lb, rb, wlr), wbt);
+}
+
+// ---- albedo textures (include/tirt.h, tirt_texture_upload; no reference counterpart: PT_RGB.py:86 takes the material colour) ----
+// The texture a material row names: (int)row[1] - 1 where 1 <= (int)row[1], else -1.  The host has refused every row of a material that is not an emitter
+// whose slot exceeds the number of uploaded textures, so a slot >= 1 found on the device names a table entry (no count is passed to any kernel).
+// Only meaningful while textures are uploaded (SceneView::tex != nullptr, or the SF_TEXTURE instantiation).
+// (the test before the subtraction: a slot below -2^31 converts to INT_MIN, and INT_MIN - 1 would come out as a texture number)
+TD int material_texture(const float *m) { const int slot = (int)m[1]; return ((int)m[0] == MAT_LIGHT || slot < 1) ? -1 : slot - 1; }
+// tex_albedo of include/tirt.h: a u or v that is not finite counts as 0; repeat takes the fractional part; then the environment's bilinear lookup.
+// An encoded (sRGB-valued) colour, in the space of a material row's colour.
+TD v3 tex_albedo(const int *tex, int id, float u, float v)
+{
+    const int4 e = ((const int4 *)tex)[id];                    // offset, w, h, wrap
+    const float big = 3.4028234e38f;
+    if (!(absf(u) <= big)) u = 0.0f;
+    if (!(absf(v) <= big)) v = 0.0f;
+    if (e.w == 1) { u = u - tm_floor(u); v = v - tm_floor(v); }
+    return texture2d(tex + e.x, e.y, e.z, u, v);
 }
 
 // ---- Camera.py:122-142 ----------------------------------------------------------------------------------------

@@ -286,9 +286,10 @@ struct tirt_ctx {
     int nv = 0, n = 0, nm = 0, ns = 0, nl = 0, light_count = 0;
     float bmin[3] = {0, 0, 0}, bmax[3] = {0, 0, 0};
     tirt::DevBuf vertex, primitive, material, shape, light, env, mat_lrgb, shade_rec, light_rec;
-    bool shade_rec_valid = false;                  // shading records follow vertex / primitive / shape uploads and process_normal
+    bool shade_rec_valid = false;                  // shading records follow vertex / primitive / shape uploads and process_normal; material and texture uploads too (they carry uvs iff the scene is textured)
     bool light_rec_valid = false;                  // light records follow those and material uploads (they carry the emitter's colour)
     int env_w = 0, env_h = 0; float env_power = 0.0f;
+    tirt::DevBuf tex; int tex_count = 0;           // albedo textures (tirt_texture_upload): tex_count table quads + the texels, SceneView::tex; they outlive a scene upload as env does
     // scene feature word (tirt_device.h, SF_*): which instantiation of k_shade / k_shade_spec the scene gets.  Derived from host copies of the rows the
     // kernels read -- the material table, the kind of every emitter on the light list (from the primitive and shape rows), the environment --
     // by refresh_shade_features, wherever one of them is uploaded again

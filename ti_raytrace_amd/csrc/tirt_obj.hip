@@ -23,6 +23,7 @@ struct ObjMat {
     double diffuse[4] = {0.8, 0.8, 0.8, 1.0}, ambient[4] = {0.2, 0.2, 0.2, 1.0}, specular[4] = {0.0, 0.0, 0.0, 1.0},
            emissive[4] = {0.0, 0.0, 0.0, 1.0};
     double transparency = 1.0, optical_density = 1.0, shininess = 0.0;
+    std::string texture;            // map_Kd: the image's path, resolved against the MTL file's directory (empty: none)
     int format = 0;                 // 0 unset, else bit0: T2F, bit1: N3F  (+4 once decided): 4 V3F, 5 T2F_V3F, 6 N3F_V3F, 7 T2F_N3F_V3F
     std::vector<double> flat;
 };
@@ -77,6 +78,36 @@ bool to_double(const std::string &s, double &v)
     errno = 0;
     v = strtod(s.c_str(), &end);
     return end == s.c_str() + s.size();
+}
+// a plain decimal number ([+-] digits [. digits] [e [+-] digits]): what tells an option's optional arguments from the file name (ObjLoader.py, _is_number)
+bool is_number(const std::string &s)
+{
+    size_t i = 0, n = s.size(), digits = 0;
+    if (i < n && (s[i] == '+' || s[i] == '-')) i++;
+    while (i < n && s[i] >= '0' && s[i] <= '9') { i++; digits++; }
+    if (i < n && s[i] == '.') { i++; while (i < n && s[i] >= '0' && s[i] <= '9') { i++; digits++; } }
+    if (!digits) return false;
+    if (i < n && (s[i] == 'e' || s[i] == 'E')) {
+        i++;
+        if (i < n && (s[i] == '+' || s[i] == '-')) i++;
+        size_t ed = 0;
+        while (i < n && s[i] >= '0' && s[i] <= '9') { i++; ed++; }
+        if (!ed) return false;
+    }
+    return i == n;
+}
+// the file name of a map_Kd statement: the tokens behind the options (ObjLoader.py, _map_file: -o / -s / -t take one to three numbers, -mm two arguments,
+// every other option one; the last token is never an argument)
+std::string map_file(const std::vector<std::string> &tok)
+{
+    size_t k = 1;
+    while (k + 1 < tok.size() && tok[k].size() > 1 && tok[k][0] == '-') {
+        const std::string &opt = tok[k];
+        k++;
+        if (opt == "-o" || opt == "-s" || opt == "-t") { for (int a = 0; a < 3 && k + 1 < tok.size() && is_number(tok[k]); a++) k++; }
+        else { const int na = opt == "-mm" ? 2 : 1; for (int a = 0; a < na && k + 1 < tok.size(); a++) k++; }
+    }
+    return join_from(tok, k);
 }
 bool to_long(const char *b, const char *e, long &v)
 {
@@ -138,6 +169,12 @@ int parse_mtl(const std::string &path, tirt_obj *o)
         else if (key == "Tr") { double t; if (!scalar(t)) OBJ_FAIL("bad Tr"); m.transparency = 1.0 - t; }
         else if (key == "Ni") { if (!scalar(m.optical_density)) OBJ_FAIL("bad Ni"); }
         else if (key == "Ns") { if (!scalar(m.shininess)) OBJ_FAIL("bad Ns"); }
+        else if (key == "map_Kd") {
+            const std::string name = map_file(tok);
+            if (name.empty()) OBJ_FAIL("map_Kd without a file name");
+            const size_t sl = path.find_last_of('/');
+            m.texture = (name[0] == '/' || sl == std::string::npos) ? name : path.substr(0, sl) + "/" + name;
+        }
         return 0;
     });
 }
@@ -257,6 +294,16 @@ int tirt_obj_material_info(const tirt_obj *o, int i, char *name, int name_cap, d
     if (vertex_format) *vertex_format = m.format;
     if (is_default) *is_default = m.is_default;
     if (n_floats) *n_floats = (long long)m.flat.size();
+    return TIRT_OK;
+}
+
+/* the material's map_Kd image, resolved against the MTL file's directory; the empty string when it has none */
+int tirt_obj_material_texture(const tirt_obj *o, int i, char *path, int cap)
+{
+    if (!o || i < 0 || i >= (int)o->mats.size() || !path) { tirt::set_error("tirt_obj_material_texture: bad index or null pointer"); return TIRT_ERR_ARG; }
+    const std::string &t = o->mats[i].texture;
+    if (cap < 1 || t.size() + 1 > (size_t)cap) { tirt::set_error("tirt_obj_material_texture: the path needs " + std::to_string(t.size() + 1) + " bytes"); return TIRT_ERR_ARG; }
+    memcpy(path, t.c_str(), t.size() + 1);
     return TIRT_OK;
 }
 

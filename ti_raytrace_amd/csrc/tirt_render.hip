@@ -103,7 +103,7 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
     if (t < INF_VALUE) {
         const int prim_id = __float_as_int(hrec.w);
         int mat_id;
-        const HitAttr h = hit_attributes_rec(sc.shade_rec, origin, direction, prim_id, t, hrec.y, hrec.z, mat_id);
+        const HitAttr h = hit_attributes_rec<(FEAT & SF_TEXTURE) != 0u>(sc.shade_rec, origin, direction, prim_id, t, hrec.y, hrec.z, mat_id);
         const v3 normal = h.nor;
         const v3 fnormal = normal * signf(dot(-direction, h.gnor));            // UtilsFunc.py:465-467
         const float *m = sc.material + (size_t)mat_id * MAT_VEC;
@@ -121,7 +121,11 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
         } else {
             s.shaded = true;
             // UF.srgb_to_lrgb(material colour) (PT_RGB.py:86): per-material table filled by the same device function
-            const v3 reflect_color = V(sc.mat_lrgb[mat_id * 3], sc.mat_lrgb[mat_id * 3 + 1], sc.mat_lrgb[mat_id * 3 + 2]);
+            v3 reflect_color;
+            // a textured material (SF_TEXTURE instantiation only): srgb_to_lrgb of the texture's colour at the hit's uv takes the place of the table's entry
+            const int tex_id = (FEAT & SF_TEXTURE) ? material_texture(m) : -1;
+            if ((FEAT & SF_TEXTURE) && tex_id >= 0) reflect_color = srgb_to_lrgb(tex_albedo(sc.tex, tex_id, h.tex.x, h.tex.y));
+            else reflect_color = V(sc.mat_lrgb[mat_id * 3], sc.mat_lrgb[mat_id * 3 + 1], sc.mat_lrgb[mat_id * 3 + 2]);
             v3 next_dir; float f_or_b = 1.0f, brdf = 1.0f;
             if ((FEAT & SF_GLASS) && mat_type == MAT_GLASS) {                  // PT_RGB.py:89-92
                 perfect_spec = 1;
@@ -218,7 +222,7 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
         const float dis = tm_sqrt(direction.x * direction.x + direction.z * direction.z);
         const float tx = (tm_atan2(direction.z, direction.x) + PI_SCENE) / PI_SCENE / 2.0f;
         const float ty = tm_atan2(direction.y, dis) / PI_SCENE + 0.5f;
-        const v3 e = srgb_to_lrgb(texture2d(sc, tx, ty));
+        const v3 e = srgb_to_lrgb(texture2d(sc.env, sc.env_w, sc.env_h, tx, ty));
         radiance = radiance + (e * throughout) * sc.env_power;
     }
 }
@@ -1216,8 +1220,8 @@ __global__ __launch_bounds__(SH_BLOCK, 4) void k_shade_spec(ShadeArgs paths_in_k
 }
 
 // ---- the instantiations of the two shading kernels, narrowest first.  pt_render launches the first one whose mask covers the scene's feature word
-// (tirt_ctx::shade_features, refreshed with the tables it is derived from); the last one carries every feature and serves every other scene, and every
-// scene when the option "shade_specialize" is 0. ----
+// (tirt_ctx::shade_features, refreshed with the tables it is derived from); SF_ALL carries every feature of an untextured scene and serves every other one of
+// those, and all of them when the option "shade_specialize" is 0; the last entry is SF_ALL with the albedo lookup, for the scenes that have a textured material. ----
 typedef void (*shade_fn_t)(ShadeArgs, SceneView, TileMap, int, uint32_t, uint32_t, int, int, const int *, int, unsigned long long *, DevCounters *, v3);
 typedef void (*shade_spec_fn_t)(ShadeArgs, SceneView, SpecView, TileMap, int, uint32_t, uint32_t, int, int, const int *, int, unsigned long long *, DevCounters *, v3);
 struct ShadeInst { unsigned feat; shade_fn_t fn, fn_list; };      // fn_list: the same kernel for the batches of a pixel set (LIST)
@@ -1229,14 +1233,16 @@ constexpr unsigned SF_I_MESH = SF_LIGHT_TRI;                                    
 static const ShadeInst SHADE_INST[] = {
     {SF_I_SPHERE, k_shade<SF_I_SPHERE, SH_MIN_WAVES_NARROW>, k_shade<SF_I_SPHERE, SH_MIN_WAVES_NARROW, true>},
     {SF_I_MESH, k_shade<SF_I_MESH, SH_MIN_WAVES_NARROW>, k_shade<SF_I_MESH, SH_MIN_WAVES_NARROW, true>},
-    {SF_ALL, k_shade<SF_ALL, SH_MIN_WAVES>, k_shade<SF_ALL, SH_MIN_WAVES, true>}};
+    {SF_ALL, k_shade<SF_ALL, SH_MIN_WAVES>, k_shade<SF_ALL, SH_MIN_WAVES, true>},
+    {SF_ALL | SF_TEXTURE, k_shade<SF_ALL | SF_TEXTURE, SH_MIN_WAVES>, k_shade<SF_ALL | SF_TEXTURE, SH_MIN_WAVES, true>}};      // textured scenes: the generic kernel + the albedo lookup
 static const ShadeSpecInst SHADE_SPEC_INST[] = {
     {SF_I_SPHERE, k_shade_spec<SF_I_SPHERE>}, {SF_I_MESH, k_shade_spec<SF_I_MESH>}, {SF_ALL, k_shade_spec<SF_ALL>}};
 template <class T, size_t N>
 static const T &pick_shade_inst(const T (&tab)[N], const tirt_ctx *c)
 {
-    if (c->shade_specialize)
-        for (size_t k = 0; k + 1 < N; k++) if ((c->shade_features & ~tab[k].feat) == 0u) return tab[k];
+    size_t k = 0;
+    if (!c->shade_specialize) while (k + 1 < N && tab[k].feat != SF_ALL) k++;      // from the generic kernel on: behind it only what SF_ALL does not cover
+    for (; k + 1 < N; k++) if ((c->shade_features & ~tab[k].feat) == 0u) return tab[k];
     return tab[N - 1];
 }
 
@@ -1267,7 +1273,7 @@ typedef void (*kat_step_fn_t)(SceneView, const float *, int, float *, int, int);
 struct KatStepInst { unsigned feat; kat_step_fn_t fn; };
 static const KatStepInst KAT_STEP_INST[] = {       // one per entry of SHADE_INST, same word, same launch bounds
     {SF_I_SPHERE, k_kat_shade_step<SF_I_SPHERE, SH_MIN_WAVES_NARROW>}, {SF_I_MESH, k_kat_shade_step<SF_I_MESH, SH_MIN_WAVES_NARROW>},
-    {SF_ALL, k_kat_shade_step<SF_ALL, SH_MIN_WAVES>}};
+    {SF_ALL, k_kat_shade_step<SF_ALL, SH_MIN_WAVES>}, {SF_ALL | SF_TEXTURE, k_kat_shade_step<SF_ALL | SF_TEXTURE, SH_MIN_WAVES>}};
 static_assert(sizeof(KAT_STEP_INST) / sizeof(KAT_STEP_INST[0]) == sizeof(SHADE_INST) / sizeof(SHADE_INST[0]), "one known-answer kernel per instantiation of k_shade");
 
 static kat_step_fn_t kat_step_inst(unsigned feat)
@@ -1283,6 +1289,7 @@ int kat_shade_step(tirt_ctx *c, unsigned feat, const float *in, int in_stride, f
     TIRT_REQUIRE((c->shade_features & ~feat) == 0u, "tirt_kat_shade_step: feat does not cover the scene's feature word (tirt_shade_features)");
     const kat_step_fn_t fn = kat_step_inst(feat);
     TIRT_REQUIRE(fn, "tirt_kat_shade_step: feat is not an instantiation of k_shade");
+    TIRT_REQUIRE(!(feat & SF_TEXTURE) || c->tex_count > 0, "tirt_kat_shade_step: the textured instantiation needs uploaded textures (tirt_texture_upload): without them no material row's slot is checked");
     for (int i = 0; i < n; i++) {
         const float *a = in + (size_t)i * in_stride;
         const int32_t *w = (const int32_t *)a; const int32_t prim = w[14], pixel = w[1];
