@@ -177,10 +177,45 @@ int tirt_texture_upload(tirt_ctx *ctx, int count, const int32_t *texels, int64_t
                         const int32_t *wrap);
 int tirt_kat_texture(tirt_ctx *ctx, const float *in, int in_stride, float *out, int out_stride, int n);
 
+/* Roughness, metallic and normal-map textures on materials (csrc/tirt_device.h, tex_roughness / tex_metallic / tex_normal; no reference counterpart).  PT_RGB, its
+ * feature buffers' normal and the Debug normal / fnormal views honour them; nothing else does.  Storage, upload and lookup are the albedo textures' own.
+ * Slots: words 7, 8, 9 of a material row (SceneData.Material.roughTex, metalTex, normalTex; no reader before this) by word 1's convention: with T uploaded
+ *   textures 1 <= (int)word <= T names texture word - 1, 0 and anything below mean none.  An emitter's row ignores all of them; a glass row ignores words 7 and
+ *   8 (its words 5 and 6 are ior and extinction) and honours word 9.  A word that is not ignored and names a texture beyond T is refused (TIRT_ERR_ARG, before
+ *   anything is written) by tirt_scene_upload, tirt_material_upload and tirt_texture_upload, as word 1 is.  With T == 0 nothing is textured, whatever the rows hold.
+ * Values, all f32, one rounding per operation, no contraction, in the order written (tests/material_maps_expected.py restates them; the device gives its bits);
+ *   (tu, tv) is the hit's uv as the albedo lookup takes it, c = tex_albedo(tex, id, tu, tv) the unchanged lookup:
+ *   rough = c.y of the roughness texture, metal = c.z of the metallic texture (glTF's channels, so one occlusion-roughness-metallic image serves both slots);
+ *     linear, no sRGB decode.  They take the place of row[6] / row[5] wherever the Disney functions read them (disney_setup, disney_evaluate_pdf, disney_sample, through
+ *     a local copy of the two words): maxf(0.001, rough) and every other expression of those functions applies to them unchanged.
+ *   normal map: n = c * 2 - 1 per channel (the product, then the difference).  With the triangle's vertex positions p0, p1, p2 and uvs t0, t1, t2 and N the
+ *     interpolated, normalised shading normal (hit_attributes' nor):
+ *       d1 = t1 - t0, d2 = t2 - t0;  det = d1.x * d2.y - d2.x * d1.y (two products, one difference)
+ *       det == 0, or not |det| <= 3.4028234e38 (infinite, NaN), or the primitive is an analytic shape:  N' = N
+ *       e1 = p1 - p0, e2 = p2 - p0;  T = (e1 * d2.y - e2 * d1.y) / det per component (two products, one difference, one quotient)
+ *       T = T - N * dot(N, T), dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z;  T = normalized(T), normalized(a) = a * (1 / sqrt(dot(a, a)))
+ *       a component of T not |.| <= 3.4028234e38:  N' = N
+ *       B = cross(N, T) = (N.y * T.z - N.z * T.y, N.z * T.x - N.x * T.z, N.x * T.y - N.y * T.x)
+ *       Nraw = (T * n.x + B * n.y) + N * n.z;  N' = normalized(Nraw)      (a texel of 0.5, 0.5, 1 does not give N back exactly: 2 * (128 / 255) - 1 != 0)
+ *     N' takes the place of the shading normal before k_shade forms fnormal = N' * sign(dot(-direction, gnor)); the geometric normal is untouched.
+ *     TIRT_AOV_NORMAL, TIRT_DEBUG_NORMAL and TIRT_DEBUG_FNORMAL show N'.  The motion records (tirt_motion_enable) keep using the vertex normals: a mapped
+ *     normal's own motion is not tracked.
+ * Kernels: a row that is not an emitter's and names an uploaded texture in a word it honours sets bit 256 of the feature word (SF_TEXTURE_PARAM); the scene is
+ *   then shaded by k_shade<SF_ALL | SF_TEXTURE | SF_TEXTURE_PARAM> (511), the albedo instantiation plus these lookups behind tests of the material row, and the
+ *   shading records carry the vertex uvs exactly as under bit 128.  Every other scene runs the kernels and produces the bits it did before.
+ * tirt_bdpt_rgb_render, tirt_pt_spec_render and tirt_bdpt_spec_render return TIRT_ERR_ARG while bit 256 is set; tirt_texture_upload with count 0 clears it;
+ *   tirt_shade_features_host never sets it.
+ * tirt_kat_material_maps: known-answer entry (tests/test_gpu_material_maps.py).  in, 3 words per row: primitive (its bits), hit u, hit v (the barycentrics of
+ *   the hit record); out, 8 words: the hit's uv (2), rough, metal -- looked up, or the row's words 6 and 5 as they are --, N' (3), 0.  A triangle's N is
+ *   normalized((n0 * a + n1 * u) + n2 * v), a = 1 - u - v; an analytic shape has uv 0 and, there being no ray, N = N' = (0, 0, 0).  One launch, row i on
+ *   thread i.  TIRT_ERR_ARG: in_stride < 3, out_stride < 8, no scene, no textures, a primitive outside [0, n_prims). */
+int tirt_kat_material_maps(tirt_ctx *ctx, const float *in, int in_stride, float *out, int out_stride, int n);
+
 /* The scene feature word: which shading code the uploaded tables can reach, and so which instantiation of the shading kernels a render
  * launches (option "shade_specialize").  Bits: 1 a MAT_GLASS material row, 2 environment lit (power != 0 or a texel that is not black),
  * 4 / 32 / 8 / 64 a triangle / a sphere / a spot or laser / an emitter of unknown kind on the light list, 16 light_count == 0,
- * 128 a material row that is not an emitter's names an uploaded albedo texture (never set by tirt_shade_features_host, which sees no textures).
+ * 128 a material row that is not an emitter's names an uploaded albedo texture (never set by tirt_shade_features_host, which sees no textures),
+ * 256 such a row names an uploaded roughness, metallic or normal-map texture in a word it honours (likewise never set by tirt_shade_features_host).
  * tirt_shade_features: out[0] = the word the context holds (refreshed by every scene, material, environment, texture and vertex upload),
  * out[1] = the "shade_specialize" option.  tirt_shade_features_host: the same rule on host tables, without a context or a device
  * (env may be NULL: lit if env_power != 0). */
@@ -287,8 +322,8 @@ int tirt_pt_spec_render(tirt_ctx *ctx, uint32_t frame_begin, int frame_count, ui
  * frame != 0, the same ray as tirt_pt_rgb_render's at that frame and seed), its closest hit, and hdr[i, j] OVERWRITTEN with one
  * view of that hit -- (0, 0, 0) on a miss, no running mean:
  *   TIRT_DEBUG_ALBEDO   the material colour, words 2..4 (:65); on a textured material tex_albedo at the hit's uv (tirt_texture_upload)
- *   TIRT_DEBUG_FNORMAL  (faceforward(normal, -direction, gnormal) + 1) * 0.5 (:62)
- *   TIRT_DEBUG_NORMAL   (normal + 1) * 0.5 (:63)
+ *   TIRT_DEBUG_FNORMAL  (faceforward(normal, -direction, gnormal) + 1) * 0.5 (:62); normal as below
+ *   TIRT_DEBUG_NORMAL   (normal + 1) * 0.5 (:63); on a normal-mapped material the mapped normal N' (tirt_kat_material_maps)
  *   TIRT_DEBUG_GNORMAL  (gnormal + 1) * 0.5 (:64)
  * Pixels of other ranks' tiles are left as they are.  flags: TIRT_TRAVERSE_EXHAUSTIVE, TIRT_COUNT_NODES; stack_size 1..4096.
  * Asynchronous; the rays count in rays_closest, a traversal stack overflow is reported by tirt_stats (TIRT_ERR_STACK). */
@@ -311,7 +346,7 @@ int tirt_film_import_device(tirt_ctx *ctx, const void *dev_src);
  * tirt_pt_spec_render also folds, per pixel of this context's tiles, the closest hit of that frame's camera ray into TIRT_AOV_WORDS f32 with the
  * film's running mean (integrator/PT_RGB.py:134-136), frames in ascending order:
  *   TIRT_AOV_ALBEDO  3 words: the material colour, or the albedo texture's, as TIRT_DEBUG_ALBEDO reads it (no sRGB conversion)
- *   TIRT_AOV_NORMAL  3 words: the shading normal as TIRT_DEBUG_NORMAL reads it, NOT mapped to [0, 1] and not face-forwarded (a NaN stays a NaN)
+ *   TIRT_AOV_NORMAL  3 words: the shading normal (a normal-mapped material's mapped normal) as TIRT_DEBUG_NORMAL reads it, NOT mapped to [0, 1] and not face-forwarded (a NaN stays a NaN)
  *   TIRT_AOV_DEPTH   1 word : the hit distance t
  *   TIRT_AOV_ALPHA   1 word : 1
  * and zeros on a miss.  hdr is not touched; pixels of other ranks' tiles are never written (zero: the ranks' records sum to the whole).
@@ -676,13 +711,13 @@ int tirt_kat_shade_tables(tirt_ctx *ctx, int which, const float *in, float *out,
 /* One shading step of PT_RGB (integrator/PT_RGB.py:66-132 between a closest hit and the next: emission with MIS, glass / Disney, the NEE set-up, the next ray, the
  * miss) by the body of one instantiation of k_shade, on the context's own tables (shading and light records, material colours, environment) -- for
  * tests/test_gpu_shade_step.py against the CPU oracle's orc_kat_shade_step.  One launch, row i on thread i.
- * feat: the feature word of the instantiation -- 32 (sphere lights), 4 (mesh lights), 127 (generic) or 255 (generic + albedo textures), the ones a render picks from (tirt_shade_features).
+ * feat: the feature word of the instantiation -- 32 (sphere lights), 4 (mesh lights), 127 (generic), 255 (generic + albedo textures) or 511 (+ roughness, metallic and normal maps), the ones a render picks from (tirt_shade_features).
  * in, 23 words per row (integers as their bit patterns): seed, pixel, frame, bounce, last_bounce; origin3, direction3; t, u, v, prim (t >= 1e6: a miss, prim unused);
  *   throughout3, radiance3, brdf_pdf, perfect_spec.  NaN and infinity in the ray, the barycentrics and the state are data.
  * out, 28 words per row: radiance3, shaded, want_next, next_o3, next_d3, next_thr3, next_pdf, next_spec, want_shadow, sh_o3, sh_d3, sh_c3, sh_expect, sh_dist -- what
  *   k_shade writes to the path state and the shadow-ray queue; a field the step does not set is 0, sh_expect -2.  sh_c counts if the shadow ray finds sh_expect first.
- * TIRT_ERR_ARG before anything is launched: in_stride < 23, out_stride < 28, a feat that is not one of the four (both also with a NULL ctx), a feat that does not
- * cover the context's feature word, feat 255 on a context without uploaded textures, a hit row (t < 1e6) whose prim is outside [0, n_prims), a pixel outside [0, 2^31 - 1). */
+ * TIRT_ERR_ARG before anything is launched: in_stride < 23, out_stride < 28, a feat that is not one of the five (both also with a NULL ctx), a feat that does not
+ * cover the context's feature word, feat 255 or 511 on a context without uploaded textures, a hit row (t < 1e6) whose prim is outside [0, n_prims), a pixel outside [0, 2^31 - 1). */
 int tirt_kat_shade_step(tirt_ctx *ctx, uint32_t feat, const float *in, int in_stride, float *out, int out_stride, int n);
 
 /* ---- native Wavefront OBJ/MTL ingest (host only; no device, no context) -----------------------------
@@ -703,6 +738,9 @@ int tirt_obj_material_vertices(const tirt_obj *obj, int index, double *out, long
 /* the image of the material's map_Kd statement (options before the file name skipped), resolved against the directory of the MTL file, NUL-terminated
  * into path[cap]; the empty string when the material has none.  TIRT_ERR_ARG when cap is too small. */
 int tirt_obj_material_texture(const tirt_obj *obj, int index, char *path, int cap);
+/* the same for the material's map_Pr (kind 0: roughness), map_Pm (kind 1: metallic) and norm / map_Bump / bump statement (kind 2: a tangent-space normal map,
+ * not a height field; -bm and the other options are skipped as map_Kd's are).  TIRT_ERR_ARG: a kind outside 0..2, cap too small. */
+int tirt_obj_material_map(const tirt_obj *obj, int index, int kind, char *path, int cap);
 
 #ifdef __cplusplus
 }

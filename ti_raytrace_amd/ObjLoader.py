@@ -16,7 +16,9 @@ The reference ingests meshes through the third-party ``pywavefront`` package
 * ``map_Kd [options] file`` sets ``texture`` to the image's path, resolved against the directory
   of the MTL file (an extension: PyWavefront makes a Texture object there, on which the
   reference's ``Scene.add_obj`` fails).  Options before the file name are skipped: ``-o`` / ``-s`` /
-  ``-t`` with their one to three numbers, ``-mm`` with two arguments, every other ``-option`` with one.
+  ``-t`` with their one to three numbers, ``-mm`` with two arguments, every other ``-option`` with one;
+* ``map_Pr`` / ``map_Pm`` / ``norm`` (or ``map_Bump``, ``bump``) set ``maps[0..2]`` the same way: roughness,
+  metallic and tangent-space normal-map images.
 
 The reference's committed ``nodelist.txt`` pins the material order + grouping for
 ``cornell_box.obj`` (tests/test_oracle_golden.py); the fan order is unpinned.
@@ -43,6 +45,7 @@ class ObjMaterial:
         self.optical_density = 1.0
         self.shininess = 0.0
         self.texture = None
+        self.maps = [None, None, None]          # map_Pr, map_Pm, norm / map_Bump / bump: image paths as `texture`
         self.vertex_format = ""
         self.chunks = []          # list of per-face float arrays, concatenated lazily
         self._flat = None
@@ -101,6 +104,9 @@ def _map_file(tok):
     return " ".join(tok[k:])
 
 
+_MAP_KIND = {"map_Pr": 0, "map_Pm": 1, "norm": 2, "map_Bump": 2, "bump": 2}      # tirt_obj_material_map's kinds
+
+
 def _parse_mtl(path, materials):
     cur = None
     with open(path, "r", errors="replace") as fh:
@@ -136,6 +142,12 @@ def _parse_mtl(path, materials):
                 if not name:
                     raise ValueError("map_Kd without a file name (%s)" % path)
                 cur.texture = name if (name.startswith("/") or "/" not in path) else path[:path.rindex("/")] + "/" + name
+            elif key in _MAP_KIND:
+                # roughness, metallic and tangent-space normal maps (map_Bump / bump are read as normal maps, not height fields; -bm is skipped as any option)
+                name = _map_file(tok)
+                if not name:
+                    raise ValueError("%s without a file name (%s)" % (key, path))
+                cur.maps[_MAP_KIND[key]] = name if (name.startswith("/") or "/" not in path) else path[:path.rindex("/")] + "/" + name
 
 
 class Wavefront:
@@ -174,6 +186,9 @@ class Wavefront:
                 tex = C.create_string_buffer(4096)
                 _native.check(L.tirt_obj_material_texture(h, i, tex, 4096))
                 m.texture = os.fsdecode(tex.value) if tex.value else None
+                for kind in range(3):
+                    _native.check(L.tirt_obj_material_map(h, i, kind, tex, 4096))
+                    m.maps[kind] = os.fsdecode(tex.value) if tex.value else None
                 self.materials[m.name] = m
         finally:
             L.tirt_obj_free(h)

@@ -128,6 +128,10 @@ class Scene:
             material.alebdoTex = -1
             if src.texture is not None and material.type != SCD.MAT_LIGHT:
                 material.alebdoTex = self.add_texture(src.texture)          # map_Kd
+            if material.type != SCD.MAT_LIGHT:                              # map_Pr, map_Pm, norm / map_Bump / bump (one file named twice: one texture)
+                for slot, path in zip(("roughTex", "metalTex", "normalTex"), getattr(src, "maps", (None, None, None))):
+                    if path is not None and not (material.type == SCD.MAT_GLASS and slot != "normalTex"):
+                        setattr(material, slot, self.add_texture(path))
             self.material_cpu.append(material)
 
             flat = src.vertices
@@ -181,7 +185,8 @@ class Scene:
         self.env_power = env_power
 
     def add_texture(self, image, wrap="repeat"):
-        """Extension (the reference never samples a texture for a surface): an albedo texture for materials.  ``image`` is a path, decoded as
+        """Extension (the reference never samples a texture for a surface): a texture for materials -- albedo, or a roughness (.g), metallic (.b) or
+        tangent-space normal map for ``Material.roughTex`` / ``metalTex`` / ``normalTex``, all in the same storage.  ``image`` is a path, decoded as
         ``add_env`` decodes its image, or an ``(h, w, 3)`` uint8 array with row 0 the top of the image; ``wrap`` is "repeat" or "clamp".
         Returns the texture's 1-based id: the value to put into ``Material.alebdoTex`` (0 and -1 mean no texture).  The same path with
         the same wrap mode gives the same id.  Textures go to the device with the scene (``setup_data_gpu``); PT_RGB, its feature

@@ -7,7 +7,9 @@ directly (``scene.material_cpu[0].setIor(1.3)``, ``shape.setRadius(5.0)``).
 
 Row layouts (f32 unless noted), reference SceneData.py:7-30:
   material  [10]: type, albedoTex, r, g, b, param0..4   (disney: metallic, roughness;
-                                                         glass: ior, extinction)
+                                                         glass: ior, extinction;
+                                                         param2..4 = words 7..9: roughTex, metalTex, normalTex,
+                                                         an extension -- the reference reads none of them)
   shape     [10]: type, px, py, pz, param0..5           (sphere: radius)
   vertex    [ 9]: pos3, normal3, uv3
   primitive [ 3] i32: type (1 tri / 2 shape), first-vertex | shape index, material index
@@ -40,6 +42,10 @@ class Material:
     def __init__(self):
         self.type = 0
         self.alebdoTex = 0
+        # extension (include/tirt.h, "Roughness, metallic and normal-map textures"): 1-based texture ids as alebdoTex's, 0 = none; row words 7, 8, 9
+        self.roughTex = 0
+        self.metalTex = 0
+        self.normalTex = 0
         self.color = [0.0, 0.0, 0.0]
         self.param = [0.0] * 5
 
@@ -63,7 +69,8 @@ class Material:
         row[0] = float(self.type)
         row[1] = float(self.alebdoTex)
         row[2:5] = [self.color[0], self.color[1], self.color[2]]
-        row[5:MAT_VEC_SIZE] = self.param[:MAT_VEC_SIZE - 5]
+        row[5:7] = self.param[:2]
+        row[7:MAT_VEC_SIZE] = [float(self.roughTex), float(self.metalTex), float(self.normalTex)]      # (param[2:5] was read by nothing)
 
 
 class Shape:

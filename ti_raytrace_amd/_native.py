@@ -77,7 +77,12 @@ MOTION_WORDS = 8
 SF_GLASS, SF_ENV, SF_LIGHT_TRI, SF_LIGHT_SPOT_LASER, SF_NO_LIGHT, SF_LIGHT_SPHERE, SF_LIGHT_OTHER = 1, 2, 4, 8, 16, 32, 64
 SF_ALL = 127
 SF_TEXTURE = 128                                                    # a textured material (tirt_texture_upload); not part of SF_ALL
-SHADE_INSTANTIATIONS = (SF_LIGHT_SPHERE, SF_LIGHT_TRI, SF_ALL, SF_ALL | SF_TEXTURE)      # the feature words k_shade / k_shade_spec are compiled for, narrowest first
+# the feature words k_shade is compiled for, narrowest first, up to the albedo instantiation (k_shade_spec: the first three); k_shade's fifth and last,
+# behind these, is SHADE_INSTANTIATION_MAPS below -- kept out of this tuple, whose last entry the albedo tests hold to 255
+SHADE_INSTANTIATIONS = (SF_LIGHT_SPHERE, SF_LIGHT_TRI, SF_ALL, SF_ALL | SF_TEXTURE)
+SF_TEXTURE_PARAM = 256                                              # a roughness, metallic or normal-map texture on a material (row words 7..9); not part of SF_ALL
+SHADE_INSTANTIATION_MAPS = SF_ALL | SF_TEXTURE | SF_TEXTURE_PARAM   # k_shade's fifth instantiation, behind the four above (that tuple ends at 255: tests/test_texture_abi.py)
+KAT_MAPS_IN, KAT_MAPS_OUT = 3, 8                                    # words per row of tirt_kat_material_maps
 KAT_STEP_IN, KAT_STEP_OUT = 23, 28                                  # words per row of tirt_kat_shade_step
 
 # context options that select code rather than tune it: name -> (default, meaning).  (The tuning options are listed in include/tirt.h.)
@@ -101,6 +106,7 @@ SIGNATURES = {
     "tirt_env_upload": (C.c_int, [_vp, _i32p, C.c_int, C.c_int, C.c_float]),
     "tirt_texture_upload": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
     "tirt_kat_texture": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
+    "tirt_kat_material_maps": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
     "tirt_shade_features": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "tirt_shade_features_host": (C.c_int, [_f32p, C.c_int, _i32p, C.c_int, _f32p, C.c_int, _i32p, C.c_int, _vp, C.c_int, C.c_int, C.c_float,
                                            C.POINTER(C.c_uint32)]),
@@ -154,6 +160,7 @@ SIGNATURES = {
     "tirt_obj_material_info": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int),
                                          C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "tirt_obj_material_texture": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_int]),
+    "tirt_obj_material_map": (C.c_int, [_vp, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "tirt_obj_material_vertices": (C.c_int, [_vp, C.c_int, np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS"), C.c_longlong]),
 }
 
@@ -402,6 +409,14 @@ class Context:
         n, stride = rows.shape
         out = np.zeros((n, max(int(out_stride), 1)), np.float32)
         check(lib().tirt_kat_texture(self.handle, rows.reshape(-1), int(stride), out.reshape(-1), int(out_stride), n))
+        return out
+
+    def kat_material_maps(self, rows, out_stride=KAT_MAPS_OUT):
+        """include/tirt.h, tirt_kat_material_maps: rows (n, >= 3) of 32-bit words (primitive as its bits, hit u, hit v) -> (n, out_stride) float32: uv2, rough, metal, N'3, 0"""
+        rows = np.ascontiguousarray(rows).view(np.float32)
+        n, stride = rows.shape
+        out = np.zeros((n, max(int(out_stride), 1)), np.float32)
+        check(lib().tirt_kat_material_maps(self.handle, rows.reshape(-1), int(stride), out.reshape(-1), int(out_stride), n))
         return out
 
     def shade_features(self):

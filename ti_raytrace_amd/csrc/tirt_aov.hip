@@ -46,7 +46,10 @@ __global__ __launch_bounds__(256) void k_aov(SceneView sc, v3 eye, TileMap tm, i
             const HitAttr a = hit_attributes(sc, eye, d, prim, h.x, h.y, h.z);
             nor = a.nor;
             // a textured material: the texture's colour at the hit's uv (tirt_device.h, tex_albedo), as k_shade's reflectance before srgb_to_lrgb
-            if (sc.tex) { const int ti = material_texture(m); if (ti >= 0) alb = tex_albedo(sc.tex, ti, a.tex.x, a.tex.y); }
+            if (sc.tex) {
+                const int ti = material_texture(m); if (ti >= 0) alb = tex_albedo(sc.tex, ti, a.tex.x, a.tex.y);
+                nor = shading_normal_rows(sc, m, prim, a.tex, nor);      // a normal-mapped material: the mapped normal, as k_shade's `normal`
+            }
             depth = h.x; alpha = 1.0f;
         }
         const float frame = (float)(int)(frame_begin + (uint32_t)f);

@@ -154,11 +154,19 @@ static bool env_is_lit(const int32_t *texel, size_t count, float power)
     for (size_t k = 0; k < count; k++) if (texel[k] & 0x00FFFFFF) return true;      // (tex_sample reads the low 24 bits)
     return false;
 }
-// the slot a material row names (row[1] as the device's (int) conversion reads it: saturating, NaN -> 0): >= 1 names texture slot - 1
-static int material_texture_slot(const float *row)
+// the slot a material row names in `word` (1 albedo, 7 roughness, 8 metallic, 9 normal map; as the device's (int) conversion reads it: saturating,
+// NaN -> 0): >= 1 names texture slot - 1
+static int material_texture_slot(const float *row, int word = 1)
 {
-    const float s = row[1];
+    const float s = row[word];
     return s >= 2147483648.0f ? 0x7fffffff : s >= 1.0f ? (int)s : 0;
+}
+// the words of a row that name textures, and whether the row's type honours that word: an emitter none, glass not 7 and 8 (its words 5, 6 are ior and extinction)
+static const int MAT_TEX_WORDS[4] = {1, 7, 8, 9};
+static bool material_honours(const float *row, int word)
+{
+    const int type = (int)row[0];
+    return type != MAT_LIGHT && !(type == MAT_GLASS && (word == 7 || word == 8));
 }
 // every material row that is not an emitter's names no texture, or one of the tex_count uploaded ones (tex_count == 0: nothing is textured, nothing to check)
 static int check_material_textures(const char *fn, const float *material, int nm, int tex_count)
@@ -169,6 +177,12 @@ static int check_material_textures(const char *fn, const float *material, int nm
         TIRT_REQUIRE((int)row[0] == MAT_LIGHT || material_texture_slot(row) <= tex_count,
                      std::string(fn) + ": material " + std::to_string(i) + " names texture " + std::to_string(material_texture_slot(row)) + " of " + std::to_string(tex_count) +
                      " uploaded (slot 1 of the row: 0 or -1 = none; tirt_texture_upload with count 0 removes all textures)");
+        for (int k = 1; k < 4; k++) {
+            const int word = MAT_TEX_WORDS[k];
+            TIRT_REQUIRE(!material_honours(row, word) || material_texture_slot(row, word) <= tex_count,
+                         std::string(fn) + ": material " + std::to_string(i) + " names texture " + std::to_string(material_texture_slot(row, word)) + " of " + std::to_string(tex_count) +
+                         " uploaded in word " + std::to_string(word) + " (7 roughness, 8 metallic, 9 normal map: 0 = none; tirt_texture_upload with count 0 removes all textures)");
+        }
     }
     return TIRT_OK;
 }
@@ -180,6 +194,10 @@ static unsigned shade_features_core(const float *material, int nm, const int *li
         const float *row = material + (size_t)i * MAT_VEC;
         const int slot = material_texture_slot(row);
         if ((int)row[0] != MAT_LIGHT && slot >= 1 && slot <= tex_count) f |= SF_TEXTURE;
+        for (int k = 1; k < 4; k++) {
+            const int ps = material_texture_slot(row, MAT_TEX_WORDS[k]);
+            if (material_honours(row, MAT_TEX_WORDS[k]) && ps >= 1 && ps <= tex_count) f |= SF_TEXTURE_PARAM;
+        }
     }
     if (env_lit) f |= SF_ENV;
     if (light_count <= 0) f |= SF_NO_LIGHT;
@@ -199,7 +217,7 @@ int ensure_shade_records(tirt_ctx *c)
 {
     if (!(c->shade_rec_valid && c->shade_rec.p)) {
         if (c->shade_rec.ensure(sizeof(float4) * 8 * (size_t)c->n)) return TIRT_ERR_HIP;
-        hipLaunchKernelGGL(k_shade_records, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, scene_view(c), c->shade_rec.as<float4>(), (c->shade_features & SF_TEXTURE) ? 1 : 0);
+        hipLaunchKernelGGL(k_shade_records, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, scene_view(c), c->shade_rec.as<float4>(), (c->shade_features & (SF_TEXTURE | SF_TEXTURE_PARAM)) ? 1 : 0);
         c->shade_rec_valid = true;
     }
     if (!(c->light_rec_valid && c->light_rec.p)) {
@@ -464,6 +482,34 @@ __global__ void k_kat_texture(const int *tex, const float *in, int in_stride, fl
     const v3 c = tex_albedo(tex, __float_as_int(a[0]), a[1], a[2]);
     const v3 l = srgb_to_lrgb(c);
     o[0] = c.x; o[1] = c.y; o[2] = c.z; o[3] = l.x; o[4] = l.y; o[5] = l.z;
+}
+
+// ---- known-answer evaluation of the material maps (tirt_kat_material_maps): row i on thread i, from the vertex rows as k_aov and Debug read them ----
+__global__ void k_kat_material_maps(SceneView sc, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *a = in + (size_t)i * in_stride;
+    float *o = out + (size_t)i * out_stride;
+    const int prim = __float_as_int(a[0]);
+    const int *pr = sc.primitive + (size_t)prim * PRI_VEC;
+    const float *m = sc.material + (size_t)pr[2] * MAT_VEC;
+    v3 uv = V(0.0f, 0.0f, 0.0f), N = uv;
+    // hit_attributes' expressions for uv and normal, restated here because that function needs a ray (for shapes) and these rows have none: a change to its
+    // interpolation must be made here too -- tests/test_gpu_material_maps.py holds k_aov and Debug, which call hit_attributes, and this entry to one restatement.
+    // A shape has uv 0 and, without a ray, no normal here: (0, 0, 0)
+    if (pr[0] == PRIMITIVE_TRI) {
+        const int vi = pr[1];
+        const float u = a[1], v = a[2], ba = 1.0f - u - v;
+        uv = (vtx_uv(sc, vi) * ba + vtx_uv(sc, vi + 1) * u) + vtx_uv(sc, vi + 2) * v;
+        N = normalized((vtx_nor(sc, vi) * ba + vtx_nor(sc, vi + 1) * u) + vtx_nor(sc, vi + 2) * v);
+    }
+    float rough = m[6], metal = m[5];
+    const int ri = material_map(m, 7), mi = material_map(m, 8);
+    if (ri >= 0) rough = tex_roughness(sc.tex, ri, uv.x, uv.y);
+    if (mi >= 0) metal = tex_metallic(sc.tex, mi, uv.x, uv.y);
+    const v3 Np = shading_normal_rows(sc, m, prim, uv, N);
+    o[0] = uv.x; o[1] = uv.y; o[2] = rough; o[3] = metal; o[4] = Np.x; o[5] = Np.y; o[6] = Np.z; o[7] = 0.0f;
 }
 
 }  // namespace tirt
@@ -777,6 +823,35 @@ int tirt_kat_texture(tirt_ctx *c, const float *in, int in_stride, float *out, in
         }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) { set_error(std::string("tirt_kat_texture: ") + hipGetErrorString(e)); rc = TIRT_ERR_HIP; }
+    }
+    din.release(); dout.release();
+    return rc;
+}
+
+int tirt_kat_material_maps(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_material_maps: null pointer or negative n");
+    TIRT_REQUIRE(in_stride >= 3 && out_stride >= 8, "tirt_kat_material_maps: stride too small (3 words in, 8 out)");
+    CTX(c);
+    TIRT_REQUIRE(c->n >= 1, "tirt_kat_material_maps: no scene");
+    TIRT_REQUIRE(c->tex_count > 0, "tirt_kat_material_maps: no textures uploaded (tirt_texture_upload)");
+    for (int i = 0; i < n; i++) {
+        const int32_t prim = ((const int32_t *)in)[(size_t)i * in_stride];
+        TIRT_REQUIRE(prim >= 0 && prim < c->n, "tirt_kat_material_maps: row " + std::to_string(i) + ": prim outside [0, n_prims)");
+    }
+    if (n == 0) return TIRT_OK;
+    if (sync_all(c)) return TIRT_ERR_HIP;
+    DevBuf din, dout;
+    int rc = TIRT_OK;
+    if (upload(din, in, sizeof(float) * (size_t)n * in_stride, c->stream) || dout.ensure(sizeof(float) * (size_t)n * out_stride)) rc = TIRT_ERR_HIP;
+    if (rc == TIRT_OK) {
+        hipError_t e = hipMemsetAsync(dout.p, 0, sizeof(float) * (size_t)n * out_stride, c->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_kat_material_maps, dim3((n + 255) / 256), dim3(256), 0, c->stream, scene_view(c), din.as<float>(), in_stride, dout.as<float>(), out_stride, n);
+            e = hipMemcpyAsync(out, dout.p, sizeof(float) * (size_t)n * out_stride, hipMemcpyDeviceToHost, c->stream);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { set_error(std::string("tirt_kat_material_maps: ") + hipGetErrorString(e)); rc = TIRT_ERR_HIP; }
     }
     din.release(); dout.release();
     return rc;
@@ -1201,7 +1276,8 @@ static int submit_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uin
 }
 // albedo textures are PT_RGB's (and the feature buffers', Debug's): the other integrators refuse a textured scene instead of rendering it flat
 #define NO_TEXTURES(c, fn)                                                         \
-    TIRT_REQUIRE(!((c)->shade_features & SF_TEXTURE), std::string(fn) + ": a material of the scene has an albedo texture (PT_RGB only): tirt_texture_upload with count 0 removes all textures")
+    TIRT_REQUIRE(!((c)->shade_features & SF_TEXTURE), std::string(fn) + ": a material of the scene has an albedo texture (PT_RGB only): tirt_texture_upload with count 0 removes all textures"); \
+    TIRT_REQUIRE(!((c)->shade_features & SF_TEXTURE_PARAM), std::string(fn) + ": a material of the scene has a roughness, metallic or normal-map texture (PT_RGB only): tirt_texture_upload with count 0 removes all textures")
 int tirt_pt_rgb_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed, int max_depth, int stack_size, int flags)
 {
     CTX_NOFLUSH(c);
@@ -1473,7 +1549,7 @@ int tirt_kat_shade_step(tirt_ctx *c, uint32_t feat, const float *in, int in_stri
     // what needs no context first (and no device: these refusals hold for a null context too)
     TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_shade_step: null pointer or negative n");
     TIRT_REQUIRE(in_stride >= 23 && out_stride >= 28, "tirt_kat_shade_step: stride too small (23 words in, 28 out)");
-    TIRT_REQUIRE(kat_shade_step_has_inst(feat), "tirt_kat_shade_step: feat is not an instantiation of k_shade (SF_LIGHT_SPHERE, SF_LIGHT_TRI, SF_ALL, SF_ALL | SF_TEXTURE)");
+    TIRT_REQUIRE(kat_shade_step_has_inst(feat), "tirt_kat_shade_step: feat is not an instantiation of k_shade (SF_LIGHT_SPHERE, SF_LIGHT_TRI, SF_ALL, SF_ALL | SF_TEXTURE, SF_ALL | SF_TEXTURE | SF_TEXTURE_PARAM)");
     CTX(c);
     return kat_shade_step(c, feat, in, in_stride, out, out_stride, n);
 }

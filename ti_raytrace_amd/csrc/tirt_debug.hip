@@ -32,7 +32,7 @@ __global__ void k_debug_generate(CameraView cam, TileMap tm, int P, uint32_t fra
 // integrator/Debug.py:55-67.  A miss writes (0, 0, 0).  On a hit:
 //   albedo   get_material_color(material, get_prim_mindex(primitive, prim_id))      (:65, UtilsFunc.py:132-133); a textured material: tex_albedo at the hit's uv
 //   fnormal  (faceforward(normal, -direction, gnormal) + 1) * 0.5                   (:62; UtilsFunc.py:466-467: sign(dot(i, nref)) * n)
-//   normal   (normal + 1) * 0.5                                                     (:63)
+//   normal   (normal + 1) * 0.5                                                     (:63); a normal-mapped material: the mapped normal, here and in fnormal
 //   gnormal  (gnormal + 1) * 0.5                                                    (:64)
 __global__ void k_debug_resolve(SceneView sc, v3 eye, TileMap tm, int P, int mode, const float *dx, const float *dy, const float *dz,
                                 const float4 *hit, float *hdr)
@@ -54,7 +54,9 @@ __global__ void k_debug_resolve(SceneView sc, v3 eye, TileMap tm, int P, int mod
         } else {
             const v3 d = V(dx[k], dy[k], dz[k]);
             const HitAttr a = hit_attributes(sc, eye, d, prim, h.x, h.y, h.z);
-            v3 n = (mode == TIRT_DEBUG_GNORMAL) ? a.gnor : a.nor;
+            v3 nor = a.nor;                              // a normal-mapped material: the mapped normal (tirt_device.h, tex_normal), in the normal and fnormal views
+            if (sc.tex && mode != TIRT_DEBUG_GNORMAL) nor = shading_normal_rows(sc, sc.material + (size_t)sc.primitive[(size_t)prim * PRI_VEC + 2] * MAT_VEC, prim, a.tex, nor);
+            v3 n = (mode == TIRT_DEBUG_GNORMAL) ? a.gnor : nor;
             if (mode == TIRT_DEBUG_FNORMAL) { const float s = signf(dot(-d, a.gnor)); n = V(s * n.x, s * n.y, s * n.z); }
             rad = V((n.x + 1.0f) * 0.5f, (n.y + 1.0f) * 0.5f, (n.z + 1.0f) * 0.5f);
         }

@@ -73,6 +73,7 @@ enum : unsigned {
     SF_LIGHT_OTHER = 64u,     // an emitter of no kind sample_li knows (it samples the origin): generic kernel only
     SF_ALL = 127u,
     SF_TEXTURE = 128u,        // a material row that is not an emitter's names an uploaded albedo texture (not part of SF_ALL: untextured scenes keep their kernels)
+    SF_TEXTURE_PARAM = 256u,  // a material row that is not an emitter's names an uploaded roughness, metallic or normal texture (words 7..9; implies uvs in the shading records as 128 does)
     SF_LIGHT_KINDS = SF_LIGHT_TRI | SF_LIGHT_SPOT_LASER | SF_LIGHT_SPHERE | SF_LIGHT_OTHER
 };
 
@@ -215,7 +216,7 @@ TD HitAttr hit_attributes(const SceneView &s, v3 origin, v3 direction, int prim,
 // divisions less per shaded path).  A sphere's normal depends on the hit point and stays here; its gn IS its nn, so the one
 // normalisation serves both.
 // The uvs t1, t2, t3 of the three vertices (columns 6, 7 of their rows; column 8 is not carried) are in the record only while the scene is textured
-// (SF_TEXTURE); otherwise those words are zero, as they always were.  TEX -- the textured instantiation of k_shade alone -- reads them and returns
+// (SF_TEXTURE or SF_TEXTURE_PARAM); otherwise those words are zero, as they always were.  TEX -- the textured instantiation of k_shade alone -- reads them and returns
 // tex = (t1 * a + t2 * b) + t3 * c as hit_attributes does, .z = 0; every other caller gets tex = 0 and loads nothing more than before.  Shapes have uv 0.
 template <bool TEX = false>
 TD HitAttr hit_attributes_rec(const float4 *rec, v3 origin, v3 direction, int prim, float t, float u, float v, int &mat_id)
@@ -680,6 +681,75 @@ TD v3 tex_albedo(const int *tex, int id, float u, float v)
     if (!(absf(v) <= big)) v = 0.0f;
     if (e.w == 1) { u = u - tm_floor(u); v = v - tm_floor(v); }
     return texture2d(tex + e.x, e.y, e.z, u, v);
+}
+
+// ---- roughness, metallic and normal-map textures (include/tirt.h, "Roughness, metallic and normal-map textures"; no reference counterpart) ----
+// The texture word `word` (7 roughness, 8 metallic, 9 normal map) of a material row names: (int)row[word] - 1 where 1 <= (int)row[word], else -1, by
+// material_texture's rule.  An emitter's row names none; a glass row none in words 7 and 8 (its words 5 and 6 are ior and extinction).
+TD int material_map(const float *m, int word)
+{
+    const int type = (int)m[0], slot = (int)m[word];
+    return (type == MAT_LIGHT || (type == MAT_GLASS && word != 9) || slot < 1) ? -1 : slot - 1;
+}
+// roughness = .y of the roughness texture, metallic = .z of the metallic texture (glTF's channels; linear values, no sRGB decode): what takes the place of
+// m[6] / m[5] of a Disney row.  The lookup is tex_albedo itself.
+TD float tex_roughness(const int *tex, int id, float u, float v) { return tex_albedo(tex, id, u, v).y; }
+TD float tex_metallic(const int *tex, int id, float u, float v) { return tex_albedo(tex, id, u, v).z; }
+// The mapped shading normal N' of a hit at (u, v) on a triangle with vertex positions p0..p2 and vertex uvs (t0x, t0y) .. (t2x, t2y), N the interpolated,
+// normalised shading normal.  Every operation in the order written, f32, one rounding each:
+//   c = tex_albedo(tex, id, u, v);  n = c * 2 - 1 per channel
+//   e1 = p1 - p0, e2 = p2 - p0;  d1 = t1 - t0, d2 = t2 - t0;  det = d1.x * d2.y - d2.x * d1.y
+//   det == 0 or not finite (|det| <= 3.4028234e38 fails): N
+//   T = (e1 * d2.y - e2 * d1.y) / det;  T = T - N * dot(N, T);  T = normalized(T);  a component of T not finite: N
+//   B = cross(N, T);  Nraw = (T * n.x + B * n.y) + N * n.z;  N' = normalized(Nraw)
+// k_shade, k_aov, the Debug normal views and tirt_kat_material_maps all come through here.
+TD v3 tex_normal_raw(const int *tex, int id, float u, float v, v3 N, v3 p0, v3 p1, v3 p2, float t0x, float t0y, float t1x, float t1y, float t2x, float t2y, bool &mapped)
+{
+    mapped = false;
+    const float big = 3.4028234e38f;
+    const float d1x = t1x - t0x, d1y = t1y - t0y, d2x = t2x - t0x, d2y = t2y - t0y;
+    const float det = d1x * d2y - d2x * d1y;
+    if (det == 0.0f || !(absf(det) <= big)) return N;
+    const v3 e1 = p1 - p0, e2 = p2 - p0;
+    v3 T = (e1 * d2y - e2 * d1y) / det;
+    T = T - N * dot(N, T);
+    T = normalized(T);
+    if (!(absf(T.x) <= big) || !(absf(T.y) <= big) || !(absf(T.z) <= big)) return N;
+    const v3 c = tex_albedo(tex, id, u, v);
+    const v3 n = V(c.x * 2.0f - 1.0f, c.y * 2.0f - 1.0f, c.z * 2.0f - 1.0f);
+    const v3 B = cross(N, T);
+    mapped = true;
+    return (T * n.x + B * n.y) + N * n.z;
+}
+TD v3 tex_normal(const int *tex, int id, float u, float v, v3 N, v3 p0, v3 p1, v3 p2, float t0x, float t0y, float t1x, float t1y, float t2x, float t2y)
+{
+    bool mapped;
+    const v3 raw = tex_normal_raw(tex, id, u, v, N, p0, p1, p2, t0x, t0y, t1x, t1y, t2x, t2y, mapped);
+    return mapped ? normalized(raw) : N;
+}
+// the same for a hit on primitive `prim` from the vertex rows (k_aov, Debug, tirt_kat_material_maps) and from the shading record (k_shade): exact copies
+// of the same floats.  uv is the hit's interpolated uv (HitAttr::tex).  An analytic shape keeps its normal.
+TD v3 tex_normal_rows(const SceneView &s, int id, int prim, v3 uv, v3 N)
+{
+    const int *pr = s.primitive + (size_t)prim * PRI_VEC;
+    if (pr[0] != PRIMITIVE_TRI) return N;
+    const int vi = pr[1];
+    const v3 t0 = vtx_uv(s, vi), t1 = vtx_uv(s, vi + 1), t2 = vtx_uv(s, vi + 2);
+    return tex_normal(s.tex, id, uv.x, uv.y, N, vtx_pos(s, vi), vtx_pos(s, vi + 1), vtx_pos(s, vi + 2), t0.x, t0.y, t1.x, t1.y, t2.x, t2.y);
+}
+TD v3 tex_normal_rec(const int *tex, const float4 *rec, int id, int prim, v3 uv, v3 N)
+{
+    const float4 *r = rec + (size_t)prim * 8;
+    const float4 r1 = r[1];
+    if (__float_as_int(r1.w) != PRIMITIVE_TRI) return N;
+    const float4 r0 = r[0], r2 = r[2], r7 = r[7]; const float t2y = r[3].w;
+    return tex_normal(tex, id, uv.x, uv.y, N, V(r0.x, r0.y, r0.z), V(r1.x, r1.y, r1.z), V(r2.x, r2.y, r2.z), r7.x, r7.y, r7.z, r7.w, r2.w, t2y);
+}
+// what k_aov and the Debug normal views show: the mapped normal where the hit's material names a normal map (textures uploaded: s.tex != nullptr), else N
+TD v3 shading_normal_rows(const SceneView &s, const float *m, int prim, v3 uv, v3 N)
+{
+    const int ni = material_map(m, 9);
+    return ni >= 0 ? tex_normal_rows(s, ni, prim, uv, N) : N;
 }
 
 // ---- Camera.py:122-142 ----------------------------------------------------------------------------------------

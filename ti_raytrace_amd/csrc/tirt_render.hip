@@ -103,8 +103,13 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
     if (t < INF_VALUE) {
         const int prim_id = __float_as_int(hrec.w);
         int mat_id;
-        const HitAttr h = hit_attributes_rec<(FEAT & SF_TEXTURE) != 0u>(sc.shade_rec, origin, direction, prim_id, t, hrec.y, hrec.z, mat_id);
-        const v3 normal = h.nor;
+        const HitAttr h = hit_attributes_rec<(FEAT & (SF_TEXTURE | SF_TEXTURE_PARAM)) != 0u>(sc.shade_rec, origin, direction, prim_id, t, hrec.y, hrec.z, mat_id);
+        v3 normal = h.nor;
+        // a normal-mapped material (SF_TEXTURE_PARAM instantiation only): the mapped normal takes h.nor's place before fnormal is formed; h.gnor stays
+        if constexpr ((FEAT & SF_TEXTURE_PARAM) != 0u) {
+            const int nor_id = material_map(sc.material + (size_t)mat_id * MAT_VEC, 9);
+            if (nor_id >= 0) normal = tex_normal_rec(sc.tex, sc.shade_rec, nor_id, prim_id, h.tex, normal);
+        }
         const v3 fnormal = normal * signf(dot(-direction, h.gnor));            // UtilsFunc.py:465-467
         const float *m = sc.material + (size_t)mat_id * MAT_VEC;
         const v3 mat_color = V(m[2], m[3], m[4]);
@@ -133,6 +138,18 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
                 brdf = 1.0f; brdf_pdf = 1.0f;
             } else {
                 perfect_spec = 0;
+                // roughness / metallic textures (SF_TEXTURE_PARAM instantiation only): a local copy of the whole row with the looked-up values in words 5
+                // and 6, which the Disney functions read through the pointer they always took (they read those two words; the rest is copied so that a
+                // function that comes to read another word through `md` finds it)
+                float mp[MAT_VEC];
+                const float *md = m;
+                if constexpr ((FEAT & SF_TEXTURE_PARAM) != 0u) {
+                    for (int w = 0; w < MAT_VEC; w++) mp[w] = m[w];
+                    const int metal_id = material_map(m, 8), rough_id = material_map(m, 7);
+                    if (metal_id >= 0) mp[5] = tex_metallic(sc.tex, metal_id, h.tex.x, h.tex.y);
+                    if (rough_id >= 0) mp[6] = tex_roughness(sc.tex, rough_id, h.tex.x, h.tex.y);
+                    md = mp;
+                }
                 // Scene.py:477-518 sample_li.  No emitters (env-lit scene): the reference would index light[-1]
                 // (Scene.py:423-428, undefined) -- defined here, as in the oracle, as "no NEE sample"
                 // the view-only and material-only terms of the BSDF, once for the NEE sample, the lobe choice and the continuation (tirt_device.h)
@@ -140,7 +157,7 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
                 // to scratch -- there every evaluation makes its own, as before)
                 constexpr bool SHARE_SETUP = !(FEAT & SF_GLASS);
                 DisneySetup ds;
-                if (SHARE_SETUP) ds = disney_setup(m, fnormal, -direction);
+                if (SHARE_SETUP) ds = disney_setup(md, fnormal, -direction);
                 if (!(FEAT & SF_NO_LIGHT) || sc.light_count > 0) {
                 int lidx = (int)(tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LIGHT) * (float)sc.light_count);
                 if (lidx >= sc.light_count) lidx = sc.light_count - 1;
@@ -161,7 +178,7 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
                     s.want_shadow = true;
                     float e_pdf;
                     const float e_brdf = SHARE_SETUP ? disney_evaluate_pdf_set(ds, fnormal, -direction, -light_dir, e_pdf)
-                                                     : disney_evaluate_pdf(m, fnormal, -direction, -light_dir, e_pdf);
+                                                     : disney_evaluate_pdf(md, fnormal, -direction, -light_dir, e_pdf);
                     const float light_pdf = light_dist * light_dist * light_choice_pdf / NdotL_light;
                     v3 c = V(0.0f, 0.0f, 0.0f);
                     int expect = -2;                       // never equals a primitive id
@@ -179,10 +196,10 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
                 }   // light_count > 0
                 const float r_lobe = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LOBE), r_1 = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_R1),
                             r_2 = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_R2);
-                next_dir = SHARE_SETUP ? disney_sample_set(ds, direction, fnormal, r_lobe, r_1, r_2) : disney_sample(m, direction, fnormal, r_lobe, r_1, r_2);
+                next_dir = SHARE_SETUP ? disney_sample_set(ds, direction, fnormal, r_lobe, r_1, r_2) : disney_sample(md, direction, fnormal, r_lobe, r_1, r_2);
                 f_or_b = 1.0f;
                 brdf = SHARE_SETUP ? disney_evaluate_pdf_set(ds, fnormal, -direction, next_dir, brdf_pdf)
-                                   : disney_evaluate_pdf(m, fnormal, -direction, next_dir, brdf_pdf);
+                                   : disney_evaluate_pdf(md, fnormal, -direction, next_dir, brdf_pdf);
                 brdf *= absf(dot(normal, next_dir));
             }
             const v3 next_origin = offset_ray(h.pos, fnormal * signf(f_or_b));   // PT_RGB.py:115
@@ -891,6 +908,9 @@ __global__ void k_generate(PathSoA ps, CameraView cam, TileMap tm, int P, int S,
 #ifndef SH_MIN_WAVES_NARROW      // the instantiations without glass and environment (82 VGPRs at 5 waves, 80 and still no scratch at 6)
 #define SH_MIN_WAVES_NARROW 5
 #endif
+#ifndef SH_MIN_WAVES_MAPS        // the instantiation with every texture slot (SF_TEXTURE_PARAM): see DESIGN.md, "Roughness, metallic and normal-map textures"
+#define SH_MIN_WAVES_MAPS 4      // at 5 (96 VGPRs) it has 28 bytes of scratch, at 4 112 VGPRs (108 LIST) and none
+#endif
 // The 78 array pointers of the path state are the first kernel argument and are never read from it directly: each of the three places
 // that needs some of them (a path's state in, the survivor's state out, the shadow ray out) reads those from the kernel-argument segment in
 // one batch of scalar loads -- as k_trace does (TR_COLD), and for the same reason: kept in SGPRs across the loop they overflow the scalar
@@ -1221,7 +1241,8 @@ __global__ __launch_bounds__(SH_BLOCK, 4) void k_shade_spec(ShadeArgs paths_in_k
 
 // ---- the instantiations of the two shading kernels, narrowest first.  pt_render launches the first one whose mask covers the scene's feature word
 // (tirt_ctx::shade_features, refreshed with the tables it is derived from); SF_ALL carries every feature of an untextured scene and serves every other one of
-// those, and all of them when the option "shade_specialize" is 0; the last entry is SF_ALL with the albedo lookup, for the scenes that have a textured material. ----
+// those, and all of them when the option "shade_specialize" is 0; behind it SF_ALL with the albedo lookup, for the scenes that have a textured material, and last
+// that kernel with the roughness / metallic / normal-map lookups (SF_TEXTURE_PARAM), for the scenes in which a material names one of those. ----
 typedef void (*shade_fn_t)(ShadeArgs, SceneView, TileMap, int, uint32_t, uint32_t, int, int, const int *, int, unsigned long long *, DevCounters *, v3);
 typedef void (*shade_spec_fn_t)(ShadeArgs, SceneView, SpecView, TileMap, int, uint32_t, uint32_t, int, int, const int *, int, unsigned long long *, DevCounters *, v3);
 struct ShadeInst { unsigned feat; shade_fn_t fn, fn_list; };      // fn_list: the same kernel for the batches of a pixel set (LIST)
@@ -1230,11 +1251,13 @@ constexpr unsigned SF_I_SPHERE = SF_LIGHT_SPHERE;                               
 constexpr unsigned SF_I_MESH = SF_LIGHT_TRI;                                        // Disney, mesh lights, black environment: Cornell box, Veach
 // (Built and left out: SF_GLASS | SF_ENV | SF_LIGHT_SPHERE for Teapot and the gallery spheres -- 3 509 VALU against the generic 3 872, but 12 bytes of scratch at
 // the 96-VGPR limit where the generic kernel has none; those scenes stay on the generic kernel.)
+constexpr unsigned SF_I_MAPS = SF_ALL | SF_TEXTURE | SF_TEXTURE_PARAM;               // every texture slot of a material row
 static const ShadeInst SHADE_INST[] = {
     {SF_I_SPHERE, k_shade<SF_I_SPHERE, SH_MIN_WAVES_NARROW>, k_shade<SF_I_SPHERE, SH_MIN_WAVES_NARROW, true>},
     {SF_I_MESH, k_shade<SF_I_MESH, SH_MIN_WAVES_NARROW>, k_shade<SF_I_MESH, SH_MIN_WAVES_NARROW, true>},
     {SF_ALL, k_shade<SF_ALL, SH_MIN_WAVES>, k_shade<SF_ALL, SH_MIN_WAVES, true>},
-    {SF_ALL | SF_TEXTURE, k_shade<SF_ALL | SF_TEXTURE, SH_MIN_WAVES>, k_shade<SF_ALL | SF_TEXTURE, SH_MIN_WAVES, true>}};      // textured scenes: the generic kernel + the albedo lookup
+    {SF_ALL | SF_TEXTURE, k_shade<SF_ALL | SF_TEXTURE, SH_MIN_WAVES>, k_shade<SF_ALL | SF_TEXTURE, SH_MIN_WAVES, true>},      // textured scenes: the generic kernel + the albedo lookup
+    {SF_I_MAPS, k_shade<SF_I_MAPS, SH_MIN_WAVES_MAPS>, k_shade<SF_I_MAPS, SH_MIN_WAVES_MAPS, true>}};                              // + roughness, metallic and normal maps
 static const ShadeSpecInst SHADE_SPEC_INST[] = {
     {SF_I_SPHERE, k_shade_spec<SF_I_SPHERE>}, {SF_I_MESH, k_shade_spec<SF_I_MESH>}, {SF_ALL, k_shade_spec<SF_ALL>}};
 template <class T, size_t N>
@@ -1273,7 +1296,8 @@ typedef void (*kat_step_fn_t)(SceneView, const float *, int, float *, int, int);
 struct KatStepInst { unsigned feat; kat_step_fn_t fn; };
 static const KatStepInst KAT_STEP_INST[] = {       // one per entry of SHADE_INST, same word, same launch bounds
     {SF_I_SPHERE, k_kat_shade_step<SF_I_SPHERE, SH_MIN_WAVES_NARROW>}, {SF_I_MESH, k_kat_shade_step<SF_I_MESH, SH_MIN_WAVES_NARROW>},
-    {SF_ALL, k_kat_shade_step<SF_ALL, SH_MIN_WAVES>}, {SF_ALL | SF_TEXTURE, k_kat_shade_step<SF_ALL | SF_TEXTURE, SH_MIN_WAVES>}};
+    {SF_ALL, k_kat_shade_step<SF_ALL, SH_MIN_WAVES>}, {SF_ALL | SF_TEXTURE, k_kat_shade_step<SF_ALL | SF_TEXTURE, SH_MIN_WAVES>},
+    {SF_I_MAPS, k_kat_shade_step<SF_I_MAPS, SH_MIN_WAVES_MAPS>}};
 static_assert(sizeof(KAT_STEP_INST) / sizeof(KAT_STEP_INST[0]) == sizeof(SHADE_INST) / sizeof(SHADE_INST[0]), "one known-answer kernel per instantiation of k_shade");
 
 static kat_step_fn_t kat_step_inst(unsigned feat)
@@ -1289,7 +1313,7 @@ int kat_shade_step(tirt_ctx *c, unsigned feat, const float *in, int in_stride, f
     TIRT_REQUIRE((c->shade_features & ~feat) == 0u, "tirt_kat_shade_step: feat does not cover the scene's feature word (tirt_shade_features)");
     const kat_step_fn_t fn = kat_step_inst(feat);
     TIRT_REQUIRE(fn, "tirt_kat_shade_step: feat is not an instantiation of k_shade");
-    TIRT_REQUIRE(!(feat & SF_TEXTURE) || c->tex_count > 0, "tirt_kat_shade_step: the textured instantiation needs uploaded textures (tirt_texture_upload): without them no material row's slot is checked");
+    TIRT_REQUIRE(!(feat & (SF_TEXTURE | SF_TEXTURE_PARAM)) || c->tex_count > 0, "tirt_kat_shade_step: the textured instantiation needs uploaded textures (tirt_texture_upload): without them no material row's slot is checked");
     for (int i = 0; i < n; i++) {
         const float *a = in + (size_t)i * in_stride;
         const int32_t *w = (const int32_t *)a; const int32_t prim = w[14], pixel = w[1];
