@@ -177,6 +177,36 @@ int tirt_texture_upload(tirt_ctx *ctx, int count, const int32_t *texels, int64_t
                         const int32_t *wrap);
 int tirt_kat_texture(tirt_ctx *ctx, const float *in, int in_stride, float *out, int out_stride, int n);
 
+/* Alpha cut-outs (csrc/tirt_device.h, tex_alpha; csrc/tirt_internal.h, trace_leaf_step; no reference counterpart).  A hit on a transparent texel of a cut-out
+ * triangle is no hit, for every ray the library traces: camera, bounce and NEE shadow rays of PT_RGB, Debug, tirt_trace_closest / _shadow, tirt_query_*, the
+ * feature buffers and the motion records.
+ * Texel: bits 24..31 of a packed texel hold 255 - A (transparency), so a texture packed without them (every texture before this) is fully opaque; tex_albedo
+ *   and everything built on it mask them off and do not change by a bit.
+ * Which textures are masks: none, until tirt_texture_cutout(ctx, flags, count) says so: flags[i] = 1 makes the top byte of texture i a cut-out mask, 0 leaves it
+ *   ignored.  count must equal the number of uploaded textures, every flag must be 0 or 1: TIRT_ERR_ARG otherwise, before anything is written (the flag values
+ *   are checked first and need no context).  Every tirt_texture_upload clears all flags (its own behaviour and refusals are unchanged).  Waits for work in flight.
+ * Which primitives: a triangle whose material row is not an emitter's and whose word 1 names an uploaded texture with its flag set is a cut-out triangle.  Analytic
+ *   shapes and emitters are never cut out (an emitter's row ignores its slot, as for the albedo).
+ * tex_alpha(tex, id, tu, tv): the fourth channel of the unchanged tex_albedo lookup -- steps 1 and 2, then texture2D's x, y, lx, ly, wlr, wbt and the four samples
+ *   lt, rt, lb, rb with   alpha(texel) = (float)(255 - ((texel >> 24) & 255)) / 255.0f   in place of (R, G, B), and mix(mix(lt, rt, wlr), mix(lb, rb, wlr), wbt).
+ *   All f32, one rounding per operation, no contraction (tests/cutout_expected.py restates it; the device gives its bits).
+ * Hit uv: (tu, tv) = (t1*a + t2*b) + t3*c over columns 6, 7 of the vertex rows, a = 1 - u - v, b = u, c = v of the candidate -- exactly the albedo lookup's uv.
+ * Rule: a candidate of the traversal's leaf step on a cut-out triangle replaces the current hit only if, besides everything it must satisfy anyway (0 < t < best,
+ *   the equal-distance rule, the ordered walk's proof that the reference reaches the leaf), tex_alpha >= 0.5f.  The cutoff is fixed (glTF's MASK default).  A
+ *   rejected candidate changes nothing: not the hit, not the equal-distance state, not the culling distance, not a bounded query's settled answer.
+ * Feature word: bit 512 (SF_CUTOUT) = a cut-out triangle exists; reported by tirt_shade_features, refreshed by scene, material, texture, flag and vertex uploads,
+ *   never set by tirt_shade_features_host.  No instantiation of k_shade depends on it (an albedo-only cut-out scene is shaded by 255, one with maps by 511): the
+ *   hits k_shade, the feature buffers and the denoisers see are on opaque texels.  Bit 128 is set with it, so tirt_bdpt_rgb_render, tirt_pt_spec_render and
+ *   tirt_bdpt_spec_render refuse such a scene.
+ * Kernels: while bit 512 is set every k_trace launch is the CUTOUT twin of the instantiation it would have been; the triangle records of the traversal layout carry
+ *   a tag (0, or texture number + 1) in the last word of their second quad (tirt_wide_tree_download), written lazily before the next trace; the camera-ray candidate
+ *   lists (option "primary_beams") are not used.  A scene without a cut-out triangle launches the kernels, and downloads the records, it did before.
+ * tirt_kat_texture_alpha: known-answer entry (tests/test_gpu_cutout.py).  in, 3 words per row: texture number (its bits), u, v; out, 2 words: tex_alpha and the
+ *   decision (1.0f where alpha >= 0.5f, else 0.0f).  One launch, row i on thread i.  TIRT_ERR_ARG: in_stride < 3, out_stride < 2, no textures, a number outside
+ *   [0, count).  Needs no flags: every texture has a top byte. */
+int tirt_texture_cutout(tirt_ctx *ctx, const int32_t *flags, int count);
+int tirt_kat_texture_alpha(tirt_ctx *ctx, const float *in, int in_stride, float *out, int out_stride, int n);
+
 /* Roughness, metallic and normal-map textures on materials (csrc/tirt_device.h, tex_roughness / tex_metallic / tex_normal; no reference counterpart).  PT_RGB, its
  * feature buffers' normal and the Debug normal / fnormal views honour them; nothing else does.  Storage, upload and lookup are the albedo textures' own.
  * Slots: words 7, 8, 9 of a material row (SceneData.Material.roughTex, metalTex, normalTex; no reader before this) by word 1's convention: with T uploaded
@@ -741,6 +771,9 @@ int tirt_obj_material_texture(const tirt_obj *obj, int index, char *path, int ca
 /* the same for the material's map_Pr (kind 0: roughness), map_Pm (kind 1: metallic) and norm / map_Bump / bump statement (kind 2: a tangent-space normal map,
  * not a height field; -bm and the other options are skipped as map_Kd's are).  TIRT_ERR_ARG: a kind outside 0..2, cap too small. */
 int tirt_obj_material_map(const tirt_obj *obj, int index, int kind, char *path, int cap);
+/* the same for the material's map_d statement (an opacity mask: Scene.add_obj makes an alpha cut-out texture of it, see "Alpha cut-outs").  An entry of its
+ * own: tirt_obj_material_map's kinds stay 0..2. */
+int tirt_obj_material_opacity(const tirt_obj *obj, int index, char *path, int cap);
 
 #ifdef __cplusplus
 }

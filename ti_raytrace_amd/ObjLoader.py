@@ -18,7 +18,8 @@ The reference ingests meshes through the third-party ``pywavefront`` package
   reference's ``Scene.add_obj`` fails).  Options before the file name are skipped: ``-o`` / ``-s`` /
   ``-t`` with their one to three numbers, ``-mm`` with two arguments, every other ``-option`` with one;
 * ``map_Pr`` / ``map_Pm`` / ``norm`` (or ``map_Bump``, ``bump``) set ``maps[0..2]`` the same way: roughness,
-  metallic and tangent-space normal-map images.
+  metallic and tangent-space normal-map images;
+* ``map_d [options] file`` sets ``opacity`` the same way: an opacity mask, of which ``Scene.add_obj`` makes an alpha cut-out texture.
 
 The reference's committed ``nodelist.txt`` pins the material order + grouping for
 ``cornell_box.obj`` (tests/test_oracle_golden.py); the fan order is unpinned.
@@ -45,6 +46,7 @@ class ObjMaterial:
         self.optical_density = 1.0
         self.shininess = 0.0
         self.texture = None
+        self.opacity = None                     # map_d: an opacity (alpha cut-out) mask's path as `texture`
         self.maps = [None, None, None]          # map_Pr, map_Pm, norm / map_Bump / bump: image paths as `texture`
         self.vertex_format = ""
         self.chunks = []          # list of per-face float arrays, concatenated lazily
@@ -142,6 +144,11 @@ def _parse_mtl(path, materials):
                 if not name:
                     raise ValueError("map_Kd without a file name (%s)" % path)
                 cur.texture = name if (name.startswith("/") or "/" not in path) else path[:path.rindex("/")] + "/" + name
+            elif key == "map_d":
+                name = _map_file(tok)
+                if not name:
+                    raise ValueError("map_d without a file name (%s)" % path)
+                cur.opacity = name if (name.startswith("/") or "/" not in path) else path[:path.rindex("/")] + "/" + name
             elif key in _MAP_KIND:
                 # roughness, metallic and tangent-space normal maps (map_Bump / bump are read as normal maps, not height fields; -bm is skipped as any option)
                 name = _map_file(tok)
@@ -189,6 +196,8 @@ class Wavefront:
                 for kind in range(3):
                     _native.check(L.tirt_obj_material_map(h, i, kind, tex, 4096))
                     m.maps[kind] = os.fsdecode(tex.value) if tex.value else None
+                _native.check(L.tirt_obj_material_opacity(h, i, tex, 4096))
+                m.opacity = os.fsdecode(tex.value) if tex.value else None
                 self.materials[m.name] = m
         finally:
             L.tirt_obj_free(h)

@@ -65,7 +65,8 @@ class Scene:
         self.env = TX.Texture()
         self.env_power = 0.0
         self.textures = []              # albedo textures (add_texture): (Texture, wrap flag), id = index + 1
-        self._texture_ids = {}          # (absolute path, wrap flag) -> id
+        self._texture_ids = {}          # (absolute path, wrap flag, cut-out flag) -> id
+        self.texture_cutout = []        # per texture: is its alpha channel a cut-out mask (add_texture(cutout=True)); beside `textures`, whose entries stay pairs
         self.bvh = None
 
         self._device_id = device_id
@@ -107,7 +108,10 @@ class Scene:
     # -- ingest -------------------------------------------------------------------------------
     def add_obj(self, filename):
         """Scene.py:59-141.  One material per MTL entry in file order; its faces become
-        consecutive triangles (9-float vertex rows: pos, normal, uv+0)."""
+        consecutive triangles (9-float vertex rows: pos, normal, uv+0).
+        Extension: ``map_Kd`` becomes the material's albedo texture, ``map_d`` an alpha cut-out texture (``_add_opacity_texture``: the ``map_Kd`` file
+        itself, or another file of the same size whose alpha or grey value joins the ``map_Kd`` image's RGB; ``map_d`` alone takes ``Kd`` ROUNDED TO 8 BITS
+        as its RGB, which quantises the colour; different sizes raise ValueError)."""
         scene = ObjLoader.Wavefront(filename)
         for name in scene.materials:
             src = scene.materials[name]
@@ -126,7 +130,9 @@ class Scene:
                 material.setExtinciton(src.shininess)
                 material.setColor(src.diffuse)
             material.alebdoTex = -1
-            if src.texture is not None and material.type != SCD.MAT_LIGHT:
+            if src.opacity is not None and material.type != SCD.MAT_LIGHT:
+                material.alebdoTex = self._add_opacity_texture(src.texture, src.opacity, src.diffuse)      # map_d (with or without map_Kd)
+            elif src.texture is not None and material.type != SCD.MAT_LIGHT:
                 material.alebdoTex = self.add_texture(src.texture)          # map_Kd
             if material.type != SCD.MAT_LIGHT:                              # map_Pr, map_Pm, norm / map_Bump / bump (one file named twice: one texture)
                 for slot, path in zip(("roughTex", "metalTex", "normalTex"), getattr(src, "maps", (None, None, None))):
@@ -184,31 +190,76 @@ class Scene:
         self.env.load_image(filename)
         self.env_power = env_power
 
-    def add_texture(self, image, wrap="repeat"):
+    def _add_opacity_texture(self, kd_path, d_path, diffuse):
+        """The alpha cut-out texture of an MTL material with a ``map_d`` statement (include/tirt.h, "Alpha cut-outs").
+        ``map_d`` names the ``map_Kd`` file: that image with its own alpha channel.  Another file of the same size: its alpha channel -- its grey
+        value if it has none -- joins the ``map_Kd`` image's RGB.  ``map_d`` alone: RGB is the material's ``Kd`` ROUNDED TO 8 BITS
+        (round(255 * clip(Kd, 0, 1)): the texture takes the place of the row's colour, so the colour is quantised).  Different sizes: ValueError."""
+        from PIL import Image
+        d_abs = os.path.abspath(os.fsdecode(d_path))
+        kd_abs = None if kd_path is None else os.path.abspath(os.fsdecode(kd_path))
+        if kd_abs == d_abs:
+            return self.add_texture(d_abs, cutout=True)
+        key = ("map_d", kd_abs, d_abs, tuple(float(x) for x in diffuse[:3]) if kd_abs is None else None)
+        if key in self._texture_ids:
+            return self._texture_ids[key]
+        if not os.path.isfile(d_abs):
+            raise FileNotFoundError("Scene.add_obj: no such map_d image file: %s" % d_abs)
+        dimg = Image.open(d_abs)
+        has_alpha = "A" in dimg.getbands() or (dimg.mode == "P" and "transparency" in dimg.info)
+        alpha = np.asarray(dimg.convert("RGBA"), np.uint8)[:, :, 3] if has_alpha else np.asarray(dimg.convert("L"), np.uint8)
+        if kd_abs is None:
+            kd8 = np.round(255.0 * np.clip(np.asarray(diffuse[:3], np.float64), 0.0, 1.0)).astype(np.uint8)
+            rgb = np.broadcast_to(kd8, alpha.shape + (3,))
+        else:
+            if not os.path.isfile(kd_abs):
+                raise FileNotFoundError("Scene.add_obj: no such map_Kd image file: %s" % kd_abs)
+            rgb = np.asarray(Image.open(kd_abs).convert("RGB"), np.uint8)
+            if rgb.shape[:2] != alpha.shape:
+                raise ValueError("Scene.add_obj: map_d image %s is %d x %d, map_Kd image %s is %d x %d (they must have one size)"
+                                 % (d_abs, alpha.shape[1], alpha.shape[0], kd_abs, rgb.shape[1], rgb.shape[0]))
+        tid = self.add_texture(np.ascontiguousarray(np.concatenate([rgb, alpha[:, :, None]], axis=2), np.uint8), cutout=True)
+        self._texture_ids[key] = tid
+        return tid
+
+    def add_texture(self, image, wrap="repeat", cutout=False):
         """Extension (the reference never samples a texture for a surface): a texture for materials -- albedo, or a roughness (.g), metallic (.b) or
         tangent-space normal map for ``Material.roughTex`` / ``metalTex`` / ``normalTex``, all in the same storage.  ``image`` is a path, decoded as
         ``add_env`` decodes its image, or an ``(h, w, 3)`` uint8 array with row 0 the top of the image; ``wrap`` is "repeat" or "clamp".
         Returns the texture's 1-based id: the value to put into ``Material.alebdoTex`` (0 and -1 mean no texture).  The same path with
         the same wrap mode gives the same id.  Textures go to the device with the scene (``setup_data_gpu``); PT_RGB, its feature
-        buffers and the Debug albedo view use them, the BDPT and spectral integrators refuse a textured scene (include/tirt.h)."""
+        buffers and the Debug albedo view use them, the BDPT and spectral integrators refuse a textured scene (include/tirt.h).
+        ``cutout=True``: an alpha cut-out texture for ``Material.alebdoTex`` -- an image file with an alpha channel (one without is opaque) or an
+        ``(h, w, 4)`` uint8 array; a hit where the bilinearly looked-up alpha is below 0.5 is no hit, for every ray (include/tirt.h, "Alpha cut-outs").
+        The same path gives another id with another ``cutout``."""
+        cutout = bool(cutout)
         if wrap not in ("repeat", "clamp"):
             raise ValueError("Scene.add_texture: wrap must be 'repeat' or 'clamp', got %r" % (wrap,))
         flag = 1 if wrap == "repeat" else 0
         tex = TX.Texture()
         if isinstance(image, (str, bytes, os.PathLike)):
             path = os.path.abspath(os.fsdecode(image))
-            if (path, flag) in self._texture_ids:
-                return self._texture_ids[(path, flag)]
+            if (path, flag, cutout) in self._texture_ids:
+                return self._texture_ids[(path, flag, cutout)]
             if not os.path.isfile(path):
                 raise FileNotFoundError("Scene.add_texture: no such image file: %s" % path)
-            tex.load_image(path)
-            self._texture_ids[(path, flag)] = len(self.textures) + 1
+            if cutout:
+                tex.load_image_rgba(path)
+            else:
+                tex.load_image(path)
+            self._texture_ids[(path, flag, cutout)] = len(self.textures) + 1
+        elif cutout:
+            arr = np.asarray(image)
+            if arr.ndim != 3 or arr.shape[2] != 4 or arr.dtype != np.uint8 or arr.shape[0] < 1 or arr.shape[1] < 1:
+                raise ValueError("Scene.add_texture: a cut-out image array must be (h, w, 4) uint8, got %s %s" % (arr.dtype, arr.shape))
+            tex.load_array_rgba(arr)
         else:
             arr = np.asarray(image)
             if arr.ndim != 3 or arr.shape[2] != 3 or arr.dtype != np.uint8 or arr.shape[0] < 1 or arr.shape[1] < 1:
                 raise ValueError("Scene.add_texture: an image array must be (h, w, 3) uint8, got %s %s" % (arr.dtype, arr.shape))
             tex.load_array(arr)
         self.textures.append((tex, flag))
+        self.texture_cutout.append(1 if cutout else 0)
         return len(self.textures)
 
     def add_shape(self, shape, mat):
@@ -296,6 +347,8 @@ class Scene:
         self.env.setup_data_gpu(ctx, self.env_power)
         if self.textures:
             ctx.texture_upload([(tex.np_img, flag) for tex, flag in self.textures])
+            if any(self.texture_cutout):
+                ctx.texture_cutout(self.texture_cutout)
         self.bvh.setup_data_gpu(self.vertex, self.shape, self.primitive)
 
     # -- kernels ------------------------------------------------------------------------------------

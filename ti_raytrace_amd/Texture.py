@@ -31,6 +31,20 @@ class Texture:
         # np_img[j, hgt-1-i] = packed[i, j]   (texture/Texture.py:29-34)
         self.np_img = np.ascontiguousarray(packed[::-1, :].T, dtype=np.int32)       # [wid, hgt]
 
+    def load_image_rgba(self, imagePath):
+        """An image with its alpha channel (one without is opaque): the cut-out packing of load_array_rgba."""
+        from PIL import Image
+        self.load_array_rgba(np.asarray(Image.open(imagePath).convert("RGBA"), dtype=np.int32))
+
+    def load_array_rgba(self, rgba_u8):
+        """rgba_u8: [hgt, wid, 4] integer array, row 0 = top of the image.  Bits 24..31 of a texel hold 255 - A, the transparency (include/tirt.h,
+        "Alpha cut-outs"): an opaque texel is the 0xRRGGBB of load_array, bit for bit."""
+        img = np.asarray(rgba_u8).astype(np.int64)
+        self.hgt, self.wid, self.channel = img.shape[0], img.shape[1], 4
+        self.size = self.wid * self.hgt * self.channel
+        packed = ((255 - img[:, :, 3]) << 24) | (img[:, :, 0] << 16) | (img[:, :, 1] << 8) | img[:, :, 2]
+        self.np_img = np.ascontiguousarray(packed[::-1, :].T.astype(np.uint32).view(np.int32))       # [wid, hgt]
+
     def load_black(self, wid=512, hgt=512):
         """Equivalent of the reference's default ``image/black.png`` (Scene.py:295-296)."""
         self.load_array(np.zeros((hgt, wid, 3), np.int32))

@@ -82,6 +82,8 @@ SF_TEXTURE = 128                                                    # a textured
 SHADE_INSTANTIATIONS = (SF_LIGHT_SPHERE, SF_LIGHT_TRI, SF_ALL, SF_ALL | SF_TEXTURE)
 SF_TEXTURE_PARAM = 256                                              # a roughness, metallic or normal-map texture on a material (row words 7..9); not part of SF_ALL
 SHADE_INSTANTIATION_MAPS = SF_ALL | SF_TEXTURE | SF_TEXTURE_PARAM   # k_shade's fifth instantiation, behind the four above (that tuple ends at 255: tests/test_texture_abi.py)
+SF_CUTOUT = 512                                                     # a cut-out triangle exists (tirt_texture_cutout); reported only: no instantiation of k_shade depends on it
+KAT_ALPHA_IN, KAT_ALPHA_OUT = 3, 2                                  # words per row of tirt_kat_texture_alpha
 KAT_MAPS_IN, KAT_MAPS_OUT = 3, 8                                    # words per row of tirt_kat_material_maps
 KAT_STEP_IN, KAT_STEP_OUT = 23, 28                                  # words per row of tirt_kat_shade_step
 
@@ -107,6 +109,8 @@ SIGNATURES = {
     "tirt_texture_upload": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
     "tirt_kat_texture": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
     "tirt_kat_material_maps": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
+    "tirt_texture_cutout": (C.c_int, [_vp, _vp, C.c_int]),
+    "tirt_kat_texture_alpha": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
     "tirt_shade_features": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "tirt_shade_features_host": (C.c_int, [_f32p, C.c_int, _i32p, C.c_int, _f32p, C.c_int, _i32p, C.c_int, _vp, C.c_int, C.c_int, C.c_float,
                                            C.POINTER(C.c_uint32)]),
@@ -161,6 +165,7 @@ SIGNATURES = {
                                          C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "tirt_obj_material_texture": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_int]),
     "tirt_obj_material_map": (C.c_int, [_vp, C.c_int, C.c_int, C.c_char_p, C.c_int]),
+    "tirt_obj_material_opacity": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_int]),
     "tirt_obj_material_vertices": (C.c_int, [_vp, C.c_int, np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS"), C.c_longlong]),
 }
 
@@ -409,6 +414,18 @@ class Context:
         n, stride = rows.shape
         out = np.zeros((n, max(int(out_stride), 1)), np.float32)
         check(lib().tirt_kat_texture(self.handle, rows.reshape(-1), int(stride), out.reshape(-1), int(out_stride), n))
+        return out
+
+    def texture_cutout(self, flags):
+        """include/tirt.h, tirt_texture_cutout: one 0 / 1 per uploaded texture -- is its top byte (255 - alpha) a cut-out mask"""
+        texture_cutout(self.handle, flags)
+
+    def kat_texture_alpha(self, rows, out_stride=KAT_ALPHA_OUT):
+        """include/tirt.h, tirt_kat_texture_alpha: rows (n, >= 3) of 32-bit words (texture number as its bits, u, v) -> (n, out_stride) float32: alpha, decision"""
+        rows = np.ascontiguousarray(rows).view(np.float32)
+        n, stride = rows.shape
+        out = np.zeros((n, max(int(out_stride), 1)), np.float32)
+        check(lib().tirt_kat_texture_alpha(self.handle, rows.reshape(-1), int(stride), out.reshape(-1), int(out_stride), n))
         return out
 
     def kat_material_maps(self, rows, out_stride=KAT_MAPS_OUT):
@@ -851,6 +868,12 @@ def texture_upload(handle, textures):
     texels = np.concatenate([img.reshape(-1) for img in imgs]) if n else np.zeros(0, np.int32)
     check(lib().tirt_texture_upload(handle, n, _ptr(texels) if n else None, int(texels.size), _ptr(offset) if n else None,
                                     _ptr(w) if n else None, _ptr(h) if n else None, _ptr(wrap) if n else None))
+
+
+def texture_cutout(handle, flags, count=None):
+    """tirt_texture_cutout on a raw context handle (None: only the refusals that need no context can be reached)"""
+    flags = np.ascontiguousarray(flags, np.int32).reshape(-1)
+    check(lib().tirt_texture_cutout(handle, _ptr(flags) if flags.size else None, int(flags.size if count is None else count)))
 
 
 def shade_features_host(material, primitive, shape, light, light_count, env=None, env_power=0.0):

@@ -211,6 +211,55 @@ void refresh_shade_features(tirt_ctx *c)
 {
     c->shade_features = c->h_material.empty() ? SF_ALL
         : shade_features_core(c->h_material.data(), c->nm, c->h_light_kind.data(), c->light_count, c->env_lit, c->tex_count);
+    // SF_CUTOUT, kept beside the word (tirt_shade_features puts it in): a material row some triangle uses, not an emitter's, whose word 1 names a flagged texture
+    c->has_cutout = false;
+    for (int i = 0; i < c->nm && !c->h_material.empty() && !c->tex_cutout.empty(); i++) {
+        const float *row = c->h_material.data() + (size_t)i * MAT_VEC;
+        const int slot = material_texture_slot(row);
+        if ((size_t)i < c->h_mat_on_tri.size() && c->h_mat_on_tri[(size_t)i] && (int)row[0] != MAT_LIGHT && slot >= 1 && slot <= c->tex_count &&
+            (size_t)slot <= c->tex_cutout.size() && c->tex_cutout[(size_t)slot - 1]) c->has_cutout = true;
+    }
+    c->cut_rec_valid = false;      // every caller has changed one of the tables the tags are derived from
+}
+
+// ---- alpha cut-outs: the tag in every record of `tri` and the side array of vertex uvs (tirt_internal.h, trace_leaf_step) ----
+// flags == nullptr: every tag back to 0 (a scene that has lost its last cut-out triangle; cut_uv is not touched)
+__global__ void k_cutout_records(SceneView s, const int *prim_slot, const int *flags, int tex_count, float4 *tri, float4 *cut_uv)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= s.n) return;
+    const int *pr = s.primitive + (size_t)i * PRI_VEC;
+    const size_t slot = (size_t)prim_slot[i];
+    int tag = 0;
+    float4 ua = make_float4(0.0f, 0.0f, 0.0f, 0.0f), ub = ua;
+    if (flags && pr[0] == PRIMITIVE_TRI) {
+        const int id = material_texture(s.material + (size_t)pr[2] * MAT_VEC);
+        if (id >= 0 && id < tex_count && flags[id]) {
+            tag = id + 1;
+            const v3 t1 = vtx_uv(s, pr[1]), t2 = vtx_uv(s, pr[1] + 1), t3 = vtx_uv(s, pr[1] + 2);
+            ua = make_float4(t1.x, t1.y, t2.x, t2.y); ub = make_float4(t3.x, t3.y, __int_as_float(id), 0.0f);
+        }
+    }
+    tri[slot * TRI_STRIDE + 1].w = __int_as_float(tag);
+    if (flags) { cut_uv[slot * 2] = ua; cut_uv[slot * 2 + 1] = ub; }
+}
+int ensure_cutout_records(tirt_ctx *c)
+{
+    if (c->cut_rec_valid || !c->built) return TIRT_OK;
+    if (c->has_cutout || c->cut_tagged) {
+        const int *flags = nullptr;
+        if (c->has_cutout) {
+            if (c->cut_uv.ensure(sizeof(float4) * 2 * (size_t)c->n) || c->cut_flags.ensure(sizeof(int) * (size_t)c->tex_count)) return TIRT_ERR_HIP;
+            TIRT_HIP(hipMemcpyAsync(c->cut_flags.p, c->tex_cutout.data(), sizeof(int) * (size_t)c->tex_count, hipMemcpyHostToDevice, c->stream));
+            flags = c->cut_flags.as<int>();
+        }
+        hipLaunchKernelGGL(k_cutout_records, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, scene_view(c), c->prim_slot.as<int>(), flags, c->tex_count,
+                           c->tri.as<float4>(), c->cut_uv.as<float4>());
+        TIRT_HIP(hipStreamSynchronize(c->stream));      // (rare: after an upload; the launch that follows may be on a lane's stream, and tex_cutout may change)
+        c->cut_tagged = c->has_cutout;
+    }
+    c->cut_rec_valid = true;
+    return TIRT_OK;
 }
 
 int ensure_shade_records(tirt_ctx *c)
@@ -472,6 +521,16 @@ static void drain_render_events(tirt_ctx *c)
     c->ev_pool.clear();
 }
 
+// ---- known-answer evaluation of tex_alpha and the cut-out decision (tirt_kat_texture_alpha): row i on thread i ----
+__global__ void k_kat_texture_alpha(const int *tex, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *a = in + (size_t)i * in_stride;
+    const float al = tex_alpha(tex, __float_as_int(a[0]), a[1], a[2]);
+    float *o = out + (size_t)i * out_stride;
+    o[0] = al; o[1] = al >= 0.5f ? 1.0f : 0.0f;
+}
 // ---- known-answer evaluation of tex_albedo (tirt_kat_texture): row i on thread i ----
 __global__ void k_kat_texture(const int *tex, const float *in, int in_stride, float *out, int out_stride, int n)
 {
@@ -566,7 +625,7 @@ void tirt_destroy(tirt_ctx *c)
     (void)hipSetDevice(c->device);
     (void)sync_all(c);
     drain_render_events(c);
-    DevBuf *bufs[] = {&c->vertex, &c->primitive, &c->material, &c->shape, &c->light, &c->env, &c->tex, &c->mat_lrgb, &c->shade_rec, &c->light_rec, &c->morton_unsorted, &c->keys_a,
+    DevBuf *bufs[] = {&c->vertex, &c->primitive, &c->material, &c->shape, &c->light, &c->env, &c->tex, &c->cut_uv, &c->cut_flags, &c->mat_lrgb, &c->shade_rec, &c->light_rec, &c->morton_unsorted, &c->keys_a,
                       &c->keys_b, &c->vals_a, &c->vals_b, &c->hist, &c->morton_sorted, &c->bvh_node, &c->compact, &c->parent,
                       &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb, &c->aov, &c->mom, &c->mom_cnt, &c->pixset, &c->pixset_tmp, &c->tp_mem, &c->mv_rec, &c->mv_snap, &c->dn_mem, &c->dn_out,
                       &c->counters_mem, &c->spill, &c->trace_stage, &c->debug_mem, &c->query_mem, &c->dyn_mem, &c->dev_counters, &c->bdpt_px, &c->timeline, &c->pvb_set[0].count, &c->pvb_set[0].cand, &c->pvb_set[0].bound, &c->pvb_set[1].count, &c->pvb_set[1].cand, &c->pvb_set[1].bound, &c->pvb_stat, &c->pvb_tmp};
@@ -702,8 +761,10 @@ int tirt_scene_upload(tirt_ctx *c, const float *vertex, int nv, const int32_t *p
     for (int i = 0; i < nl; i++) TIRT_REQUIRE(light[i] >= 0 && light[i] < n, "tirt_scene_upload: light index out of range");
     if (int rc = check_material_textures("tirt_scene_upload", material, nm, c->tex_count)) return rc;
     c->sphere_prims.clear(); c->sphere_geom.clear();
+    c->h_mat_on_tri.assign((size_t)nm, 0);
     for (int i = 0; i < n; i++) {
         const int32_t *pr = primitive + (size_t)i * 3;
+        if (pr[0] == PRIMITIVE_TRI) c->h_mat_on_tri[(size_t)pr[2]] = 1;
         if (pr[0] != PRIMITIVE_TRI && (int)shape[(size_t)pr[1] * 10] == SHAPE_SPHERE) {
             c->sphere_prims.push_back(i);
             for (int k = 1; k <= 4; k++) c->sphere_geom.push_back(shape[(size_t)pr[1] * 10 + k]);
@@ -796,9 +857,51 @@ int tirt_texture_upload(tirt_ctx *c, int count, const int32_t *texels, int64_t t
         TIRT_HIP(hipStreamSynchronize(c->stream));      // (table is a local)
     } else c->tex.release();
     c->tex_count = count;
+    c->tex_cutout.clear();                     // no texture is a cut-out mask until tirt_texture_cutout says so
     c->shade_rec_valid = false;                // the shading records carry uvs iff a material is textured
     refresh_shade_features(c);
     return TIRT_OK;
+}
+
+int tirt_texture_cutout(tirt_ctx *c, const int32_t *flags, int count)
+{
+    // what needs no context first (and no device: these refusals hold for a null context too)
+    TIRT_REQUIRE(count >= 0 && (count == 0 || flags), "tirt_texture_cutout: null pointer or negative count");
+    for (int i = 0; i < count; i++) TIRT_REQUIRE(flags[i] == 0 || flags[i] == 1, "tirt_texture_cutout: flag " + std::to_string(i) + " is neither 0 nor 1");
+    CTX(c);
+    TIRT_REQUIRE(count == c->tex_count, "tirt_texture_cutout: count " + std::to_string(count) + " differs from the " + std::to_string(c->tex_count) + " uploaded textures");
+    if (sync_all(c)) return TIRT_ERR_HIP;      // the tags must not change under batches still in flight
+    c->tex_cutout.assign(flags, flags + count);
+    c->pvb_valid = false;                      // the candidate lists of an opaque scene are not those of one with holes, and the other way round
+    refresh_shade_features(c);
+    return TIRT_OK;
+}
+
+int tirt_kat_texture_alpha(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_texture_alpha: null pointer or negative n");
+    TIRT_REQUIRE(in_stride >= 3 && out_stride >= 2, "tirt_kat_texture_alpha: stride too small (3 words in, 2 out)");
+    CTX(c);
+    TIRT_REQUIRE(c->tex_count > 0, "tirt_kat_texture_alpha: no textures uploaded (tirt_texture_upload)");
+    for (int i = 0; i < n; i++) {
+        const int32_t id = ((const int32_t *)in)[(size_t)i * in_stride];
+        TIRT_REQUIRE(id >= 0 && id < c->tex_count, "tirt_kat_texture_alpha: row " + std::to_string(i) + ": texture number outside [0, count)");
+    }
+    if (n == 0) return TIRT_OK;
+    DevBuf din, dout;
+    int rc = TIRT_OK;
+    if (upload(din, in, sizeof(float) * (size_t)n * in_stride, c->stream) || dout.ensure(sizeof(float) * (size_t)n * out_stride)) rc = TIRT_ERR_HIP;
+    if (rc == TIRT_OK) {
+        hipError_t e = hipMemsetAsync(dout.p, 0, sizeof(float) * (size_t)n * out_stride, c->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_kat_texture_alpha, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->tex.as<int>(), din.as<float>(), in_stride, dout.as<float>(), out_stride, n);
+            e = hipMemcpyAsync(out, dout.p, sizeof(float) * (size_t)n * out_stride, hipMemcpyDeviceToHost, c->stream);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { set_error(std::string("tirt_kat_texture_alpha: ") + hipGetErrorString(e)); rc = TIRT_ERR_HIP; }
+    }
+    din.release(); dout.release();
+    return rc;
 }
 
 int tirt_kat_texture(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n)
@@ -861,7 +964,7 @@ int tirt_shade_features(tirt_ctx *c, uint32_t *out)
 {
     TIRT_REQUIRE(c, "null context");
     TIRT_REQUIRE(out, "tirt_shade_features: null pointer");
-    out[0] = c->shade_features;
+    out[0] = c->shade_features | (c->has_cutout ? (unsigned)SF_CUTOUT : 0u);
     out[1] = c->shade_specialize ? 1u : 0u;
     return TIRT_OK;
 }
@@ -936,6 +1039,7 @@ int tirt_wide_tree_download(tirt_ctx *c, uint32_t *cnode, float *tri, float *wno
 {
     CTX(c);
     TIRT_REQUIRE(c->built && grid && info, "tirt_wide_tree_download: LBVH not built / null pointer");
+    if (int rc = ensure_cutout_records(c)) return rc;      // (the records' tag words as the next trace would see them)
     const size_t n = c->n, N = 2 * n - 1, nodes = (size_t)c->wide_nodes + (size_t)c->n_far_nodes;
     if (cnode && nodes) TIRT_HIP(hipMemcpyAsync(cnode, c->cnode.p, 64 * nodes, hipMemcpyDeviceToHost, c->stream));
     if (tri) TIRT_HIP(hipMemcpyAsync(tri, c->tri.p, sizeof(float4) * TRI_STRIDE * n, hipMemcpyDeviceToHost, c->stream));

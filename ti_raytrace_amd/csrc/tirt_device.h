@@ -73,6 +73,8 @@ enum : unsigned {
     SF_LIGHT_OTHER = 64u,     // an emitter of no kind sample_li knows (it samples the origin): generic kernel only
     SF_ALL = 127u,
     SF_TEXTURE = 128u,        // a material row that is not an emitter's names an uploaded albedo texture (not part of SF_ALL: untextured scenes keep their kernels)
+    SF_CUTOUT = 512u,         // a triangle's material row that is not an emitter's names, in word 1, an uploaded texture flagged as a cut-out mask (tirt_texture_cutout): k_trace's
+                              // CUTOUT twins.  Reported by tirt_shade_features; no instantiation of k_shade depends on it (pick_shade_inst never sees it)
     SF_TEXTURE_PARAM = 256u,  // a material row that is not an emitter's names an uploaded roughness, metallic or normal texture (words 7..9; implies uvs in the shading records as 128 does)
     SF_LIGHT_KINDS = SF_LIGHT_TRI | SF_LIGHT_SPOT_LASER | SF_LIGHT_SPHERE | SF_LIGHT_OTHER
 };
@@ -681,6 +683,33 @@ TD v3 tex_albedo(const int *tex, int id, float u, float v)
     if (!(absf(v) <= big)) v = 0.0f;
     if (e.w == 1) { u = u - tm_floor(u); v = v - tm_floor(v); }
     return texture2d(tex + e.x, e.y, e.z, u, v);
+}
+
+// tex_alpha of include/tirt.h: the fourth channel of the same lookup -- the same non-finite rule, wrap, clamp, lx / ly / wlr / wbt, the four texels lt / rt / lb / rb
+// and mix order as tex_albedo / texture2d; a texel's alpha is (255 - top byte) / 255 (the top byte holds the transparency: 0 in every texture packed without one)
+TD float tex_sample_alpha(const int *img, int w, int h, float fx, float fy)
+{
+    int x = (int)fx, y = (int)fy;
+    x = x < 0 ? 0 : (x > w - 1 ? w - 1 : x);
+    y = y < 0 ? 0 : (y > h - 1 ? h - 1 : y);
+    const int RGBA = img[(size_t)x * h + y];
+    return (float)(255 - ((RGBA >> 24) & 255)) / 255.0f;
+}
+TD float tex_alpha(const int *tex, int id, float u, float v)
+{
+    const int4 e = ((const int4 *)tex)[id];                    // offset, w, h, wrap
+    const float big = 3.4028234e38f;
+    if (!(absf(u) <= big)) u = 0.0f;
+    if (!(absf(v) <= big)) v = 0.0f;
+    if (e.w == 1) { u = u - tm_floor(u); v = v - tm_floor(v); }
+    const int *img = tex + e.x; const int w = e.y, h = e.z;
+    const float x = clampf(u * (float)w, 0.0f, (float)w - 1.0f);
+    const float y = clampf(v * (float)h, 0.0f, (float)h - 1.0f);
+    const float lx = tm_floor(x), ly = tm_floor(y);
+    const float wbt = y - tm_floor(y), wlr = x - tm_floor(x);
+    const float lt = tex_sample_alpha(img, w, h, lx, ly), rt = tex_sample_alpha(img, w, h, lx + 1.0f, ly);
+    const float lb = tex_sample_alpha(img, w, h, lx, ly + 1.0f), rb = tex_sample_alpha(img, w, h, lx + 1.0f, ly + 1.0f);
+    return mixf(mixf(lt, rt, wlr), mixf(lb, rb, wlr), wbt);
 }
 
 // ---- roughness, metallic and normal-map textures (include/tirt.h, "Roughness, metallic and normal-map textures"; no reference counterpart) ----

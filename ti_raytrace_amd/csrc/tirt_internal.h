@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/tirt.h"
 #include "tirt_device.h"
@@ -56,6 +57,7 @@ struct DevBuf {
 //              E1 = v1 - v0, E2 = v2 - v0 are formed per test as the reference does (Scene.py:608-609), and the exact
 //              leaf box (min / max of the three) is at hand for the hit verification of the ordered traversal
 //   spheres  : (centre.xyz, bits leaf_compact_index) (radius, 0, 0, 0) (0,0,0,0)
+//   (the last word of the second quad is 0 in every record of a scene without cut-out triangles; else k_cutout_records keeps a tag there, see trace_leaf_step)
 #ifndef TRI_STRIDE_N
 #define TRI_STRIDE_N 3
 #endif
@@ -120,6 +122,8 @@ struct BvhView {
     // a ray that starts too far away for that box to be safe (cull_far < 0, k_trace) gets these leaves pushed at its start.
     int far_qcode;                // where a far-origin ray starts: root_qcode, or the first of the chain nodes that hold the padded analytic spheres beside the root (lbvh_build)
 };
+// what the CUTOUT twins of k_trace read beside BvhView (TraceArgsCut, tirt_render.hip)
+struct CutView { const float4 *uv; const int *tex; };
 
 // ---- what k_trace (ordered and exhaustive), k_pvb_beam and k_pvb_cand must agree on to the last bit: ONE definition each ----
 constexpr float TR_FAR_RHO = 8.0f;            // ordered traversal: rays starting further than this many root-box extents from the grid do not cull by distance (and a camera out there gets no candidate lists)
@@ -137,9 +141,18 @@ TD float trace_margin_cells(float rho) { return TR_MARGIN_CELLS + TR_MARGIN_PER_
 // leaf's exact box (it implies every ancestor's: `slabs` is monotone in the plane positions), else `slabs` on every proper ancestor (compact_node rows along cparent).
 // `code` = ~(child code of the leaf) = record slot | shape << 30.  Returns whether the hit (hit_t .. hit_leaf) was replaced.  Used by k_trace and k_pvb_cand: one
 // leaf step, so the two cannot drift apart (they did not in round 5, but only the on / off tests said so).
-template <bool VERIFY>
+// CUTOUT (alpha cut-out textures, include/tirt.h "Alpha cut-outs"): word .w of the record's second quad is a tag -- 0 opaque, else 1 + the number of the cut-out
+// texture the triangle's material names (k_cutout_records, tirt_api.hip; analytic shapes and emitters are never tagged) -- and a candidate on a tagged triangle
+// replaces the hit only if tex_alpha at the hit's uv is >= 0.5.  The uv is formed as hit_attributes forms it, from the three vertex uvs of the side array `cut_uv`
+// (two quads per record, in the records' order: (t1.u, t1.v, t2.u, t2.v) (t3.u, t3.v, bits texture, 0)).  A rejected candidate changes nothing.  The test is the
+// LAST term of the AND: the exact-box `slabs` of VERIFY is ~25 VALU instructions on values already in registers, the alpha lookup three dependent rounds of gathers
+// (uv record, table entry, four texels), so only candidates that passed everything else pay for it -- and only waves that hold one (the ballot, as for the sphere).
+// `CS::load` hands out the two pointers where they are needed (k_trace reads them from the kernel-argument segment there: nothing is held across the walk).
+struct NoCutSource { static TD void load(const float4 *&, const int *&) {} };
+template <bool VERIFY, bool CUTOUT = false, class CS = NoCutSource>
 TD bool trace_leaf_step(const BvhView &b, const RayCtx &r, const bool par, const int code, float &hit_t, float &hit_u, float &hit_v, int &hit_prim, int &hit_leaf)
 {
+    static_assert(!CUTOUT || !std::is_same<CS, NoCutSource>::value, "trace_leaf_step<VERIFY, true> needs a source of the cut-out pointers (NoCutSource hands out none)");
     const float4 *tp = b.tri + (size_t)(code & 0x3fffffff) * TRI_STRIDE;          // records in the traversal tree's leaf order
     // (the records themselves must NOT be loaded non-temporally: -25 %, profiles/r05m -- their residency in L2 is what the kernel lives on)
     const float4 ta = tp[0], tb = tp[1], tc = tp[2];
@@ -188,6 +201,20 @@ TD bool trace_leaf_step(const BvhView &b, const RayCtx &r, const bool par, const
             // needed below (tools/dbg/prim_clobber.sh shows the ISA; 156 of 15 000 box-grazing rays on the Cornell box then kept the PREVIOUS
             // hit's primitive id, tests/test_gpu_trace.py::test_quantised_nodes_on_grazing_rays).  Round 3 pinned the value with an empty asm.
             prim = (int)b.compact[(size_t)leaf * CPN_VEC + 1];
+        }
+    }
+    if constexpr (CUTOUT) {
+        const bool need = cand & (__float_as_int(tb.w) != 0);
+        if (__builtin_amdgcn_ballot_w64(need) != 0ull) {
+            if (need) {
+                const float4 *cut_uv = nullptr; const int *cut_tex = nullptr;
+                CS::load(cut_uv, cut_tex);
+                const float4 *up = cut_uv + (size_t)(code & 0x3fffffff) * 2;
+                const float4 ua = up[0], ub = up[1];
+                const float a_ = 1.0f - u - v;
+                const float tu = (ua.x * a_ + ua.z * u) + ub.x * v, tv = (ua.y * a_ + ua.w * u) + ub.y * v;
+                cand = tex_alpha(cut_tex, __float_as_int(ub.z), tu, tv) >= 0.5f;
+            }
         }
     }
     if (cand) { hit_t = t; hit_u = u; hit_v = v; hit_prim = prim; hit_leaf = leaf; }
@@ -289,6 +316,11 @@ struct tirt_ctx {
     bool shade_rec_valid = false;                  // shading records follow vertex / primitive / shape uploads and process_normal; material and texture uploads too (they carry uvs iff the scene is textured)
     bool light_rec_valid = false;                  // light records follow those and material uploads (they carry the emitter's colour)
     int env_w = 0, env_h = 0; float env_power = 0.0f;
+    // alpha cut-outs (tirt_texture_cutout): the flag per uploaded texture (empty = all 0); which materials a triangle uses (tirt_scene_upload); has_cutout = bit SF_CUTOUT of the
+    // feature word, kept OUT of shade_features (k_shade does not change with it); cut_uv = the side array of trace_leaf_step, allocated for scenes with cut-outs only;
+    // cut_rec_valid: tags and side array follow textures, flags, materials, vertices and the build (ensure_cutout_records); cut_tagged: a record of `tri` carries a tag
+    std::vector<int> tex_cutout; std::vector<unsigned char> h_mat_on_tri; bool has_cutout = false;
+    tirt::DevBuf cut_uv, cut_flags; bool cut_rec_valid = false, cut_tagged = false;
     tirt::DevBuf tex; int tex_count = 0;           // albedo textures (tirt_texture_upload): tex_count table quads + the texels, SceneView::tex; they outlive a scene upload as env does
     // scene feature word (tirt_device.h, SF_*): which instantiation of k_shade / k_shade_spec the scene gets.  Derived from host copies of the rows the
     // kernels read -- the material table, the kind of every emitter on the light list (from the primitive and shape rows), the environment --
@@ -524,6 +556,7 @@ void pvb_launch_cand(tirt_ctx *c, hipStream_t st, const BvhView &bv, const float
 void pvb_launch_scatter(hipStream_t st, const int *fb_count, const int *fb_slot, const float4 *fb_hit, float4 *hit);
 int ensure_counters(tirt_ctx *c);
 int ensure_shade_records(tirt_ctx *c);
+int ensure_cutout_records(tirt_ctx *c);      // tirt_api.hip: before every k_trace launch (pt_render, trace_rays), on the main stream
 void refresh_shade_features(tirt_ctx *c);      // tirt_api.hip
 int sync_all(tirt_ctx *c);
 int flush_pending(tirt_ctx *c);

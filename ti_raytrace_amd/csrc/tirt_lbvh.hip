@@ -643,6 +643,7 @@ int exp_wide_from_tree(tirt_ctx *c, const float *compact_host, const int *csize_
     GridMap gm;
     for (int k = 0; k < 3; k++) { gm.g0[k] = c->grid_min[k]; gm.inv_cell[k] = c->grid_inv_cell[k]; }
     c->build_serial++;                       // (another traversal tree: the camera rays' candidate lists belong to the old one, tirt_pvb.hip)
+    c->cut_rec_valid = false;                // (the records keep their slots; the cut-out tags and side array are written again before the next trace all the same)
     return build_wide(c, alt_compact.as<float>(), alt_csize.as<int>(), nullptr, pad, gm);
 }
 #endif
@@ -788,6 +789,7 @@ int lbvh_build(tirt_ctx *c)
     TIRT_HIP(hipGetLastError());
     c->build_serial++;
     c->built = true;
+    c->cut_rec_valid = false; c->cut_tagged = false;      // k_tris wrote every record's tag word as 0: ensure_cutout_records tags them again before the next trace
     return TIRT_OK;
 }
 

@@ -24,6 +24,7 @@ struct ObjMat {
            emissive[4] = {0.0, 0.0, 0.0, 1.0};
     double transparency = 1.0, optical_density = 1.0, shininess = 0.0;
     std::string texture;            // map_Kd: the image's path, resolved against the MTL file's directory (empty: none)
+    std::string opacity;            // map_d (tirt_obj_material_opacity): likewise
     std::string maps[3];            // map_Pr, map_Pm, norm / map_Bump / bump (tirt_obj_material_map kinds 0, 1, 2): likewise
     int format = 0;                 // 0 unset, else bit0: T2F, bit1: N3F  (+4 once decided): 4 V3F, 5 T2F_V3F, 6 N3F_V3F, 7 T2F_N3F_V3F
     std::vector<double> flat;
@@ -176,6 +177,12 @@ int parse_mtl(const std::string &path, tirt_obj *o)
             const size_t sl = path.find_last_of('/');
             m.texture = (name[0] == '/' || sl == std::string::npos) ? name : path.substr(0, sl) + "/" + name;
         }
+        else if (key == "map_d") {
+            const std::string name = map_file(tok);
+            if (name.empty()) OBJ_FAIL("map_d without a file name");
+            const size_t sl = path.find_last_of('/');
+            m.opacity = (name[0] == '/' || sl == std::string::npos) ? name : path.substr(0, sl) + "/" + name;
+        }
         else if (key == "map_Pr" || key == "map_Pm" || key == "norm" || key == "map_Bump" || key == "bump") {
             const std::string name = map_file(tok);
             if (name.empty()) OBJ_FAIL(key + " without a file name");
@@ -320,6 +327,16 @@ int tirt_obj_material_map(const tirt_obj *o, int i, int kind, char *path, int ca
     if (!o || i < 0 || i >= (int)o->mats.size() || !path || kind < 0 || kind > 2) { tirt::set_error("tirt_obj_material_map: bad index, kind or null pointer"); return TIRT_ERR_ARG; }
     const std::string &t = o->mats[i].maps[kind];
     if (cap < 1 || t.size() + 1 > (size_t)cap) { tirt::set_error("tirt_obj_material_map: the path needs " + std::to_string(t.size() + 1) + " bytes"); return TIRT_ERR_ARG; }
+    memcpy(path, t.c_str(), t.size() + 1);
+    return TIRT_OK;
+}
+
+/* the image of the material's map_d statement (an opacity / alpha cut-out mask), as tirt_obj_material_texture gives map_Kd's */
+int tirt_obj_material_opacity(const tirt_obj *o, int i, char *path, int cap)
+{
+    if (!o || i < 0 || i >= (int)o->mats.size() || !path) { tirt::set_error("tirt_obj_material_opacity: bad index or null pointer"); return TIRT_ERR_ARG; }
+    const std::string &t = o->mats[i].opacity;
+    if (cap < 1 || t.size() + 1 > (size_t)cap) { tirt::set_error("tirt_obj_material_opacity: the path needs " + std::to_string(t.size() + 1) + " bytes"); return TIRT_ERR_ARG; }
     memcpy(path, t.c_str(), t.size() + 1);
     return TIRT_OK;
 }

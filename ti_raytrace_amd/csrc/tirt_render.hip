@@ -79,6 +79,12 @@ struct TraceArgs {
     const float4 *ray4;
     const int *ray_index;                        // KIND_QUERY: ray q is record ray_index[q] of ray4 (BDPT: the connection rays stay where they were staged; the queue is a list of places)
 };
+// the argument of the CUTOUT twins (scenes with a cut-out triangle): TraceArgs, and behind it the vertex uvs in the records' order and the texture buffer
+// (trace_leaf_step), read from the kernel-argument segment where a tagged candidate needs them (CutSource).  The opaque instantiations keep TraceArgs itself:
+// not an offset of their argument block moves, the hidden arguments behind it included.
+struct TraceArgsCut : TraceArgs { CutView cut; };
+template <bool CUTOUT> struct trace_args_of { typedef TraceArgs type; };
+template <> struct trace_args_of<true> { typedef TraceArgsCut type; };
 
 // One path at one bounce: what integrator/PT_RGB.py:66-132 does between the closest hit and the next one -- emission (with MIS), the glass / disney
 // branch, the NEE sample (its shadow ray and the contribution it adds IF the ray arrives), the next ray and the throughput, the environment
@@ -324,8 +330,19 @@ typedef const __attribute__((address_space(4))) TraceArgs *cold_args_t;
 #define TR_LADDER_PADS(where) do { } while (0)
 #endif
 
-template <int MODE, bool COUNT, int KIND>
-__global__ __launch_bounds__(TR_BLOCK, TR_MIN_WAVES) void k_trace(TraceArgs a)
+// (CutSource reads the kernel-argument segment as a TraceArgsCut: the struct must stay k_trace's first and only explicit argument, TraceArgs its base at offset 0)
+static_assert(std::is_base_of<TraceArgs, TraceArgsCut>::value && sizeof(TraceArgsCut) >= sizeof(TraceArgs) + sizeof(CutView) && sizeof(TraceArgsCut) <= sizeof(TraceArgs) + 2 * sizeof(CutView),
+              "TraceArgsCut is TraceArgs with the CutView behind it");
+struct CutSource {
+    static TD void load(const float4 *&uv, const int *&tex)
+    {
+        const __attribute__((address_space(4))) TraceArgsCut *ca = (const __attribute__((address_space(4))) TraceArgsCut *)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ca));
+        uv = ca->cut.uv; tex = ca->cut.tex;
+    }
+};
+template <int MODE, bool COUNT, int KIND, bool CUTOUT = false>
+__global__ __launch_bounds__(TR_BLOCK, TR_MIN_WAVES) void k_trace(typename trace_args_of<CUTOUT>::type a)
 {
     extern __shared__ __attribute__((aligned(16))) int lds_stack[];      // [lds_depth][TR_BLOCK]
     const int TR_LDS_DEPTH = a.lds_depth;
@@ -705,7 +722,9 @@ __global__ __launch_bounds__(TR_BLOCK, TR_MIN_WAVES) void k_trace(TraceArgs a)
             // that the reference would have visited this leaf (`slabs` on its exact box, else on every ancestor); shared with k_pvb_cand
             const int code = ~(from_pend ? pend : cur);
             if (COUNT) nleaf += 1;
-            const bool accepted = trace_leaf_step<MODE != TIRT_TRAVERSE_EXHAUSTIVE>(b, r, par, code, hit_t, hit_u, hit_v, hit_prim, hit_leaf);
+            bool accepted;
+            if constexpr (CUTOUT) accepted = trace_leaf_step<MODE != TIRT_TRAVERSE_EXHAUSTIVE, true, CutSource>(b, r, par, code, hit_t, hit_u, hit_v, hit_prim, hit_leaf);
+            else accepted = trace_leaf_step<MODE != TIRT_TRAVERSE_EXHAUSTIVE>(b, r, par, code, hit_t, hit_u, hit_v, hit_prim, hit_leaf);
             if (from_pend) pend = 0; else TR_POP(cur);
             if (accepted) {
                 lim = __builtin_fminf(__builtin_fminf(cull_far < 0.0f ? INF_VALUE : hit_t * 1.0001f, __builtin_fabsf(cull_far)), INF_VALUE);      // (v_min: a canonical value, so the node loop does not re-canonicalise it every step)
@@ -789,18 +808,18 @@ static unsigned long long *timeline_for(tirt_ctx *c, int flags, int grid)
     return c->timeline.as<unsigned long long>();
 }
 
-template <int MODE, bool COUNT, int KIND>
-static int launch_trace_as(tirt_ctx *c, hipStream_t stream, const TraceArgs &a, dim3 g, dim3 b, size_t lds)
+template <int MODE, bool COUNT, int KIND, bool CUTOUT = false>
+static int launch_trace_as(tirt_ctx *c, hipStream_t stream, const typename trace_args_of<CUTOUT>::type &a, dim3 g, dim3 b, size_t lds)
 {
     // more than 64 KB of dynamic LDS per block (stacks + tree top): the opt-in is per kernel AND per device
     static size_t allowed[TIRT_MAX_DEVICES] = {};
     TIRT_REQUIRE(lds <= c->lds_optin, "k_trace: trace_lds_depth needs more LDS than the device has per block");
     const int dev = (c->device >= 0 && c->device < TIRT_MAX_DEVICES) ? c->device : 0;
     if (lds > allowed[dev] || c->device >= TIRT_MAX_DEVICES) {
-        TIRT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace<MODE, COUNT, KIND>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        TIRT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace<MODE, COUNT, KIND, CUTOUT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         allowed[dev] = lds;
     }
-    hipLaunchKernelGGL((k_trace<MODE, COUNT, KIND>), g, b, lds, stream, a);
+    hipLaunchKernelGGL((k_trace<MODE, COUNT, KIND, CUTOUT>), g, b, lds, stream, a);
     return TIRT_OK;
 }
 template <int KIND>
@@ -809,6 +828,16 @@ static int launch_trace(tirt_ctx *c, hipStream_t stream, const TraceArgs &a, int
     const bool exh = (flags & TIRT_TRAVERSE_EXHAUSTIVE) != 0, cnt = (flags & TIRT_COUNT_NODES) != 0;
     dim3 g(grid), b(TR_BLOCK);
     const size_t lds = trace_lds_bytes(a.lds_depth);
+    // a scene with a cut-out triangle (tirt_ctx::has_cutout, the feature word's SF_CUTOUT) gets the CUTOUT twin of whatever it would launch; every other scene what it always got
+    if (c->has_cutout) {
+        TraceArgsCut ac; static_cast<TraceArgs &>(ac) = a;
+        ac.cut.uv = c->cut_uv.as<float4>(); ac.cut.tex = c->tex.as<int>();
+        TIRT_REQUIRE(c->cut_rec_valid && ac.cut.uv && ac.cut.tex, "k_trace: the cut-out records are stale (internal: ensure_cutout_records was not run)");
+        if (exh && cnt) return launch_trace_as<TIRT_TRAVERSE_EXHAUSTIVE, true, KIND, true>(c, stream, ac, g, b, lds);
+        if (exh) return launch_trace_as<TIRT_TRAVERSE_EXHAUSTIVE, false, KIND, true>(c, stream, ac, g, b, lds);
+        if (cnt) return launch_trace_as<TIRT_TRAVERSE_ORDERED, true, KIND, true>(c, stream, ac, g, b, lds);
+        return launch_trace_as<TIRT_TRAVERSE_ORDERED, false, KIND, true>(c, stream, ac, g, b, lds);
+    }
     if (exh && cnt) return launch_trace_as<TIRT_TRAVERSE_EXHAUSTIVE, true, KIND>(c, stream, a, g, b, lds);
     if (exh) return launch_trace_as<TIRT_TRAVERSE_EXHAUSTIVE, false, KIND>(c, stream, a, g, b, lds);
     if (cnt) return launch_trace_as<TIRT_TRAVERSE_ORDERED, true, KIND>(c, stream, a, g, b, lds);
@@ -850,6 +879,7 @@ int trace_rays_prepare(tirt_ctx *c, int lane)
 int trace_rays(tirt_ctx *c, const TraceJob &j)
 {
     if (j.count <= 0) return TIRT_OK;
+    if (int rc = ensure_cutout_records(c)) return rc;
     hipStream_t st = j.lane < 0 ? c->stream : c->lanes[j.lane].stream;
     TraceArgs a = {};
     if (int rc = trace_buffers(c, j.lane, j.stack_size, a)) return rc;
@@ -1408,6 +1438,7 @@ int pt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed,
     if (frame_count == 0 || c->npix_local == 0 || c->pixset_n == 0) return TIRT_OK;
     if (ensure_counters(c)) return TIRT_ERR_HIP;
     if (ensure_shade_records(c)) return TIRT_ERR_HIP;          // on the main stream: the lanes wait for ev_main below
+    if (int rc = ensure_cutout_records(c)) return rc;
     const int P = render_pixels(c);
     // frames per batch: up to batch_paths pixel-samples in flight (the per-bounce launches of a
     // batch end in a latency-bound tail of a few long rays, so bigger batches amortise it)
@@ -1430,7 +1461,8 @@ int pt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed,
     // the pixels' candidate lists for the camera rays (tirt_pvb.hip), made on the main stream when the scene, the camera or the film changed since
     // (indexed by the tiles' local pixel: the camera rays of a pixel set's batches all go through k_trace)
     bool beams_ready = false;
-    if (!list && c->primary_beams && FB >= c->primary_beams_min_frames && !(flags & TIRT_TRAVERSE_EXHAUSTIVE)) {
+    // (and they assume opaque leaves: a scene with cut-outs traces its camera rays the ordinary way, as a pixel set's batches do)
+    if (!list && !c->has_cutout && c->primary_beams && FB >= c->primary_beams_min_frames && !(flags & TIRT_TRAVERSE_EXHAUSTIVE)) {
         if (int rc = pvb_prepare(c)) return rc;
         beams_ready = c->pvb_valid;
     }

@@ -24,7 +24,7 @@ for l in txt:
     if not body or not t or t[0] in ";." or t.endswith(":"): continue
     op = t.split()[0]
     s = stats[cur]; s["total"] += 1
-    s["hash"] = (s["hash"] * 1000003 + int(hashlib.md5(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s+", " ", t.split(";")[0])).encode()).hexdigest()[:12], 16) ) & 0xffffffffffff      # (order-sensitive digest of the instruction text)
+    s["hash"] = (s["hash"] * 1000003 + int(hashlib.md5(re.sub(r"(\.Ltr_[a-z_]+?)\d+\b", r"\1", re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s+", " ", t.split(";")[0]))).encode()).hexdigest()[:12], 16) ) & 0xffffffffffff      # (order-sensitive digest of the instruction text; the number an inline asm's %= puts into its .Ltr_* labels counts the asm blocks of the whole translation unit, not this kernel's: left out)
     if op.startswith(("v_writelane", "v_readlane")): s["lane"] += 1
     if op.startswith("v_sqrt_"): s["sqrt"] += 1
     if op.startswith("v_div_fixup_"): s["div"] += 1
