@@ -254,6 +254,56 @@ int tirt_shade_features_host(const float *material, int nm, const int32_t *primi
                              const int32_t *light, int light_count, const int32_t *env, int env_w, int env_h, float env_power,
                              uint32_t *out);
 
+/* Importance sampling of the environment (csrc/tirt_envsample.hip, the table; csrc/tirt_device.h, env_sample / env_pdf; csrc/tirt_render.hip, shade_path under
+ * SF_ENV_SAMPLE; no reference counterpart: integrator/PT_RGB.py:127-132 reads the environment only where a BSDF-sampled ray misses).  Opt-in, PT_RGB only: with the
+ * switch off every kernel keeps its code and its bits; tirt_pt_spec_render, both BDPT integrators, the feature buffers, moments, denoisers and the temporal
+ * history never read the switch.  Limit: the environment stays 8 bits per channel times env_power; a float / RGBE environment is out of scope.
+ * All f32 below: one rounding per operation, no contraction, in the order written (tests/env_sampling_expected.py restates it; the device gives its bits).
+ * 1. Cells and weights.  One cell per texel index (i, j), i < w, j < h: the lookup coordinates with floor(min(w - 1, max(0, tx * w))) = i and the same for
+ *      (ty, h, j) -- the cell texture2D's lx, ly name; cell w - 1 / h - 1 takes what the clamp folds into it.
+ *      lum(x, y) = ((l.r + l.g) + l.b) / 3.0f of l = srgb_to_lrgb(texel(min(x, w - 1), min(y, h - 1)) / 255.0f)   (the level of tirt_moments_converged, not Rec.709)
+ *      m = ((lum(i, j) + lum(i + 1, j)) + (lum(i, j + 1) + lum(i + 1, j + 1))) * 0.25f          -- the four texels texture2D mixes in the cell
+ *      el = ((j + 0.5f) / h - 0.5f) * PI_SCENE;   weight = m * cos(el);   q(i, j) = (uint32) rintf(weight * 16777216.0f)   (round half to even; 0 <= q <= 2^24)
+ * 2. Sums, 64-bit integers: R_j[i] = q(0, j) + .. + q(i, j);  M[j] = R_0[w - 1] + .. + R_j[w - 1];  total = M[h - 1].  total == 0, env_power == 0,
+ *      max(w, h) > 16384 or w * h > 2^25: no table, the feature is inactive.  Any summation order gives these values.
+ * 3. Sample from two randoms ra, rb in [0, 1) (24 bits: k = (uint32)(r * 16777216.0f)).  pick(C, n, k, tot), C an inclusive sum with C[n - 1] = tot:
+ *        t = floor(k * tot / 2^24), fb = (k * tot) mod 2^24 (exact: the high and low halves of (k << 40) * tot);  e = the first index with C[e] > t;
+ *        below = e ? C[e - 1] : 0;  off = (float)(((t - below) * 2^24 + fb) / (C[e] - below)) * 2^-24    (integer quotient < 2^24: off is exact and < 1)
+ *      (j, offy) = pick(M, h, ka, total);  (i, offx) = pick(R_j, w, kb, R_j[w - 1]);   tx = ((float)i + offx) / (float)w;  ty = ((float)j + offy) / (float)h
+ *      az = (tx * 2.0f) * PI_SCENE - PI_SCENE;  el = (ty - 0.5f) * PI_SCENE;  d = (cos(el) * cos(az), sin(el), cos(el) * sin(az))   -- the inverse of the miss branch's
+ *      tx = (atan2(d.z, d.x) + PI_SCENE) / PI_SCENE / 2.0f,  ty = atan2(d.y, dis) / PI_SCENE + 0.5f,  dis = sqrt(d.x * d.x + d.z * d.z)     (PI_SCENE = 3.1415926f)
+ * 4. pdf over solid angle of a direction d: dis, tx, ty as the miss branch forms them; x = min(w - 1, max(0, tx * w)), i = clamp((int)floor(x), 0, w - 1), j likewise;
+ *        pdf = (((float)q(i, j) / (float)total) * ((float)w * (float)h)) / (((2.0f * PI_SCENE) * PI_SCENE) * dis);   dis < 1e-6f: pdf = 0
+ *      The pdf of a sample is the pdf of ITS direction by this lookup (a tx that rounds onto a cell's edge may land in the neighbour: both sides then agree).
+ * 5. One bounce of k_shade with the table (bit 1024).  p_env = light_count == 0 ? 1 : share.  r = tm_rand(.., TM_SLOT_LIGHT):
+ *      r < p_env: the environment sample d of (ra, rb) = (TM_SLOT_LA, TM_SLOT_LB), Disney branch only.  Taken iff dot(fnormal, d) > 0 and pdf(d) > 0:
+ *        pdf_l = p_env * pdf(d);  e_brdf, e_pdf = the Disney evaluation towards d;  e_pdf > 0:  w = power_heuristic(pdf_l, e_pdf) / max(1e-4f, pdf_l),
+ *        c = (srgb_to_lrgb(texture2D(env, tx, ty)) * env_power) * w, then * throughput, * reflect_color, * e_brdf, * |dot(fnormal, d)|, * (drawn / e_pdf) in that order, with (tx, ty)
+ *        of step 4 for d and drawn = max(0, e_pdf + (dr * (float)(1.0 / 3.1415956)) * (dot(fnormal, d) - 1)), dr = 0.5f * (1 - metallic): the density Disney.sample
+ *        draws d with (its diffuse lobe by cos / pi) where evaluate_pdf states 1 / pi for that lobe.  The switch-off estimator weights its draws by 1 / e_pdf and so
+ *        converges to the integral of (drawn / e_pdf) * f * cos * L; with the ratio the light sample estimates that integrand too, the MIS weights sum to 1 over one
+ *        integrand, and switch on and off have one expectation.  A metal has dr = 0 and the ratio exactly 1;
+ *        LIMIT: the emitter sample keeps the reference's form (no ratio), and the share rescales its pdf, so on dielectrics in a scene WITH emitters the expectation
+ *        depends on `share` to the extent that an emitter's MIS weights move with it (nothing where light_pdf dwarfs e_pdf, as for small lamps);  shadow ray from offset_ray(pos, fnormal) along d with expect = -1 (-2 and c = 0 where e_pdf <= 0) and distance 2e6: it contributes iff it
+ *        hits nothing (k_trace is unchanged: -1 is the hit primitive of a ray without a hit; a bound beyond INF_VALUE lets any accepted hit end the walk)
+ *      otherwise: the emitter sample as before with r' = (r - p_env) / (1 - p_env) in r's place and light_pdf * (1 - p_env)
+ *      emitter hit: light_pdf * (1 - p_env).  Miss: the environment term times 1 where perfect_spec == 1, else power_heuristic(brdf_pdf, p_env * pdf(direction)).
+ * tirt_env_sampling(ctx, on, share): the switch and the share (0 < share < 1, on 0 / 1: TIRT_ERR_ARG otherwise, before a context is needed).  Submits pending renders,
+ *   waits for work in flight, builds or drops the table.  tirt_env_upload rebuilds or drops it; a scene upload keeps it (the feature bit follows the word's bit 2).
+ * Feature word: bit 1024 (SF_ENV_SAMPLE) = switch on, bit 2 set, table exists; reported by tirt_shade_features, kept out of every other integrator's kernel choice.
+ *   tirt_pt_rgb_render then launches k_shade<127 | 1024>, or k_shade<511 | 1024> where the word has bit 128 or 256.  tirt_shade_features_host_env is
+ *   tirt_shade_features_host with the switch as an input (env == NULL never sets the bit: a table needs the image).
+ * tirt_env_table_download: info = (w, h, table exists, bit 1024); with a table q[h * w] (row j at j * w), row_sums[h * w] (R_j) and marginal[h] (M); each may be NULL.
+ * tirt_kat_env_sample: in 2 words (ra, rb in [0, 1)), out 10: i, j (bits), tx, ty, d3, pdf(d), and the cell (i, j bits) the lookup of d lands in.
+ * tirt_kat_env_pdf: in 3 words (d), out 5: i, j (bits), tx, ty, pdf.  Both: one launch, row r on thread r; TIRT_ERR_ARG without a table or with strides too small. */
+int tirt_env_sampling(tirt_ctx *ctx, int on, float share);
+int tirt_env_table_download(tirt_ctx *ctx, uint32_t *q, uint64_t *row_sums, uint64_t *marginal, int32_t info[4]);
+int tirt_kat_env_sample(tirt_ctx *ctx, const float *in, int in_stride, float *out, int out_stride, int n);
+int tirt_kat_env_pdf(tirt_ctx *ctx, const float *in, int in_stride, float *out, int out_stride, int n);
+int tirt_shade_features_host_env(const float *material, int nm, const int32_t *primitive, int n, const float *shape, int ns,
+                                 const int32_t *light, int light_count, const int32_t *env, int env_w, int env_h, float env_power,
+                                 int env_sampling, uint32_t *out);
+
 /* LBvh.Bvh.setup_data_gpu (accel/LBvh.py:192-226): Morton codes, stable radix sort, Karras
  * topology, leaf boxes, bottom-up refit, DFS flatten -- all on device. */
 int tirt_lbvh_build(tirt_ctx *ctx);
@@ -742,6 +792,7 @@ int tirt_kat_shade_tables(tirt_ctx *ctx, int which, const float *in, float *out,
  * miss) by the body of one instantiation of k_shade, on the context's own tables (shading and light records, material colours, environment) -- for
  * tests/test_gpu_shade_step.py against the CPU oracle's orc_kat_shade_step.  One launch, row i on thread i.
  * feat: the feature word of the instantiation -- 32 (sphere lights), 4 (mesh lights), 127 (generic), 255 (generic + albedo textures) or 511 (+ roughness, metallic and normal maps), the ones a render picks from (tirt_shade_features).
+ *   With environment importance sampling: 127 | 1024 and 511 | 1024 (they need the context's table: bit 1024 of tirt_shade_features).
  * in, 23 words per row (integers as their bit patterns): seed, pixel, frame, bounce, last_bounce; origin3, direction3; t, u, v, prim (t >= 1e6: a miss, prim unused);
  *   throughout3, radiance3, brdf_pdf, perfect_spec.  NaN and infinity in the ray, the barycentrics and the state are data.
  * out, 28 words per row: radiance3, shaded, want_next, next_o3, next_d3, next_thr3, next_pdf, next_spec, want_shadow, sh_o3, sh_d3, sh_c3, sh_expect, sh_dist -- what

@@ -20,7 +20,8 @@ def default_tile_size(H):
 
 class PathTrace(FilmRecords, SampleMoments, TemporalAccumulation):
     def __init__(self, imgSizeX, imgSizeY, cam, scene, stack_size,
-                 seed=1, tile_rank=0, tile_count=1, tile_size=None, flags=0, motion=False, temporal=False, moments=False, aov=False):
+                 seed=1, tile_rank=0, tile_count=1, tile_size=None, flags=0, env_sampling=False, env_share=0.5,
+                 motion=False, temporal=False, moments=False, aov=False):
         self.imgSizeX = imgSizeX
         self.imgSizeY = imgSizeY
         self.cam = cam
@@ -49,6 +50,11 @@ class PathTrace(FilmRecords, SampleMoments, TemporalAccumulation):
             raise ValueError("motion=True needs the temporal history: PT_RGB.PathTrace(..., aov=True, moments=True, temporal=True, motion=True)")
         self.motion_records = motion
         self._motion_fields()
+        # extension: light samples aimed at the environment by its brightness, weighted against BSDF sampling (include/tirt.h, "Importance sampling of the
+        # environment"); env_share = the part of the light samples the environment gets in a scene that has emitters too
+        if not 0.0 < float(env_share) < 1.0:
+            raise ValueError("PT_RGB.PathTrace: env_share must lie in (0, 1), got %r" % (env_share,))
+        self._env_sampling, self._env_share = bool(env_sampling), float(env_share)
         # extension: the film after denoise(), a buffer of its own beside hdr
         self.denoised = DeviceField("denoised", scene, self._denoised_download)
 
@@ -58,6 +64,7 @@ class PathTrace(FilmRecords, SampleMoments, TemporalAccumulation):
     def setup_data_gpu(self):
         self.scene.ctx.film_create(self.imgSizeX, self.imgSizeY, self.tile_rank, self.tile_count, self.tile_size)
         self.cam.attach(self.scene.ctx)
+        self.scene.ctx.env_sampling(self._env_sampling, self._env_share)
         if self.aov:
             self.scene.ctx.aov_enable(True)
         if self.moments:
@@ -66,6 +73,23 @@ class PathTrace(FilmRecords, SampleMoments, TemporalAccumulation):
             self.scene.ctx.temporal_enable(True)
         if self.motion_records:
             self.scene.ctx.motion_enable(True)
+
+    @property
+    def env_sampling(self):
+        """(switch, share) as given; ``env_sampling_active`` says whether the device samples (a lit environment with a table: bit 1024 of the feature word)."""
+        return self._env_sampling, self._env_share
+
+    @property
+    def env_sampling_active(self):
+        return bool(self.scene.ctx.shade_features()[0] & 1024)
+
+    def set_env_sampling(self, on, share=None):
+        """Switch the environment's light sample on or off between renders (the film is not cleared)."""
+        share = self._env_share if share is None else float(share)
+        if not 0.0 < share < 1.0:
+            raise ValueError("PT_RGB.PathTrace: env_share must lie in (0, 1), got %r" % (share,))
+        self._env_sampling, self._env_share = bool(on), share
+        self.scene.ctx.env_sampling(self._env_sampling, self._env_share)
 
     def render(self):
         """One frame at ``cam.frame`` (the caller advances it with ``cam.update_frame()``)."""

@@ -187,7 +187,14 @@ class Scene:
     def add_env(self, filename, env_power):
         # The reference ignores `filename` and always loads image/env.png (Scene.py:183-185,
         # quirk B16); here the argument is honoured.
-        self.env.load_image(filename)
+        # Extension: an ``(h, w, 3)`` uint8 array with row 0 the top of the image, as ``add_texture`` takes one.
+        if isinstance(filename, (str, bytes, os.PathLike)):
+            self.env.load_image(filename)
+        else:
+            arr = np.asarray(filename)
+            if arr.ndim != 3 or arr.shape[2] != 3 or arr.dtype != np.uint8 or arr.shape[0] < 1 or arr.shape[1] < 1:
+                raise ValueError("Scene.add_env: an image array must be (h, w, 3) uint8, got %s %s" % (arr.dtype, arr.shape))
+            self.env.load_array(arr)
         self.env_power = env_power
 
     def _add_opacity_texture(self, kd_path, d_path, diffuse):

@@ -83,6 +83,10 @@ SHADE_INSTANTIATIONS = (SF_LIGHT_SPHERE, SF_LIGHT_TRI, SF_ALL, SF_ALL | SF_TEXTU
 SF_TEXTURE_PARAM = 256                                              # a roughness, metallic or normal-map texture on a material (row words 7..9); not part of SF_ALL
 SHADE_INSTANTIATION_MAPS = SF_ALL | SF_TEXTURE | SF_TEXTURE_PARAM   # k_shade's fifth instantiation, behind the four above (that tuple ends at 255: tests/test_texture_abi.py)
 SF_CUTOUT = 512                                                     # a cut-out triangle exists (tirt_texture_cutout); reported only: no instantiation of k_shade depends on it
+SF_ENV_SAMPLE = 1024                                                # environment importance sampling on, environment lit, table built (tirt_env_sampling); not part of SF_ALL
+SHADE_INSTANTIATIONS_ENV = (SF_ALL | SF_ENV_SAMPLE, SHADE_INSTANTIATION_MAPS | SF_ENV_SAMPLE)       # k_shade's twins with the environment's light sample
+KAT_ENV_SAMPLE_IN, KAT_ENV_SAMPLE_OUT = 2, 10                       # words per row of tirt_kat_env_sample
+KAT_ENV_PDF_IN, KAT_ENV_PDF_OUT = 3, 5                              # words per row of tirt_kat_env_pdf
 KAT_ALPHA_IN, KAT_ALPHA_OUT = 3, 2                                  # words per row of tirt_kat_texture_alpha
 KAT_MAPS_IN, KAT_MAPS_OUT = 3, 8                                    # words per row of tirt_kat_material_maps
 KAT_STEP_IN, KAT_STEP_OUT = 23, 28                                  # words per row of tirt_kat_shade_step
@@ -114,6 +118,12 @@ SIGNATURES = {
     "tirt_shade_features": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "tirt_shade_features_host": (C.c_int, [_f32p, C.c_int, _i32p, C.c_int, _f32p, C.c_int, _i32p, C.c_int, _vp, C.c_int, C.c_int, C.c_float,
                                            C.POINTER(C.c_uint32)]),
+    "tirt_shade_features_host_env": (C.c_int, [_f32p, C.c_int, _i32p, C.c_int, _f32p, C.c_int, _i32p, C.c_int, _vp, C.c_int, C.c_int, C.c_float,
+                                               C.c_int, C.POINTER(C.c_uint32)]),
+    "tirt_env_sampling": (C.c_int, [_vp, C.c_int, C.c_float]),
+    "tirt_env_table_download": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
+    "tirt_kat_env_sample": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
+    "tirt_kat_env_pdf": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
     "tirt_lbvh_build": (C.c_int, [_vp]),
     "tirt_lbvh_download": (C.c_int, [_vp, _vp, _vp, _vp]),
     "tirt_traversal_tree_download": (C.c_int, [_vp, _vp]),
@@ -434,6 +444,35 @@ class Context:
         n, stride = rows.shape
         out = np.zeros((n, max(int(out_stride), 1)), np.float32)
         check(lib().tirt_kat_material_maps(self.handle, rows.reshape(-1), int(stride), out.reshape(-1), int(out_stride), n))
+        return out
+
+    def env_sampling(self, on, share=0.5):
+        """include/tirt.h, tirt_env_sampling: importance-sample the environment in PT_RGB (NEE + MIS); share of the light samples it gets beside emitters"""
+        env_sampling(self.handle, on, share)
+
+    def env_table_download(self):
+        """include/tirt.h, tirt_env_table_download: None without a table, else {"w", "h", "active", "q" [h, w] uint32, "row_sums" [h, w] uint64, "marginal" [h] uint64}"""
+        info = (C.c_int32 * 4)()
+        check(lib().tirt_env_table_download(self.handle, None, None, None, info))
+        if not info[2]:
+            return None
+        w, h = int(info[0]), int(info[1])
+        q, rows, marg = np.zeros((h, w), np.uint32), np.zeros((h, w), np.uint64), np.zeros(h, np.uint64)
+        check(lib().tirt_env_table_download(self.handle, _ptr(q), _ptr(rows), _ptr(marg), info))
+        return {"w": w, "h": h, "active": bool(info[3]), "q": q, "row_sums": rows, "marginal": marg}
+
+    def kat_env_sample(self, rows, out_stride=KAT_ENV_SAMPLE_OUT):
+        """include/tirt.h, tirt_kat_env_sample: rows (n, >= 2) float32 (ra, rb) -> (n, out_stride) float32: i, j (bits), tx, ty, d3, pdf, lookup cell i, j (bits)"""
+        rows = np.ascontiguousarray(rows, np.float32)
+        out = np.zeros((rows.shape[0], max(int(out_stride), 1)), np.float32)
+        check(lib().tirt_kat_env_sample(self.handle, rows.reshape(-1), int(rows.shape[1]), out.reshape(-1), int(out_stride), rows.shape[0]))
+        return out
+
+    def kat_env_pdf(self, rows, out_stride=KAT_ENV_PDF_OUT):
+        """include/tirt.h, tirt_kat_env_pdf: rows (n, >= 3) float32 directions -> (n, out_stride) float32: i, j (bits), tx, ty, pdf"""
+        rows = np.ascontiguousarray(rows, np.float32)
+        out = np.zeros((rows.shape[0], max(int(out_stride), 1)), np.float32)
+        check(lib().tirt_kat_env_pdf(self.handle, rows.reshape(-1), int(rows.shape[1]), out.reshape(-1), int(out_stride), rows.shape[0]))
         return out
 
     def shade_features(self):
@@ -886,6 +925,23 @@ def shade_features_host(material, primitive, shape, light, light_count, env=None
                                          light.reshape(-1), int(light_count), _ptr(env), 0 if env is None else env.shape[0], 0 if env is None else env.shape[1],
                                          float(env_power), C.byref(out)))
     return int(out.value)
+
+
+def shade_features_host_env(material, primitive, shape, light, light_count, env=None, env_power=0.0, env_sampling=False):
+    """shade_features_host with the switch of tirt_env_sampling as an input: bit 1024 where a context would report it."""
+    material = np.ascontiguousarray(material, np.float32); primitive = np.ascontiguousarray(primitive, np.int32)
+    shape = np.ascontiguousarray(shape, np.float32); light = np.ascontiguousarray(light, np.int32)
+    env = None if env is None else np.ascontiguousarray(env, np.int32)
+    out = C.c_uint32(0)
+    check(lib().tirt_shade_features_host_env(material.reshape(-1), material.shape[0], primitive.reshape(-1), primitive.shape[0], shape.reshape(-1), shape.shape[0],
+                                             light.reshape(-1), int(light_count), _ptr(env), 0 if env is None else env.shape[0], 0 if env is None else env.shape[1],
+                                             float(env_power), 1 if env_sampling else 0, C.byref(out)))
+    return int(out.value)
+
+
+def env_sampling(handle, on, share=0.5):
+    """tirt_env_sampling on a raw context handle (None: only the refusals that need no context can be reached)"""
+    check(lib().tirt_env_sampling(handle, 1 if on else 0, float(share)))
 
 
 def device_count():

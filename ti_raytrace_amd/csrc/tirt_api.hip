@@ -819,7 +819,42 @@ int tirt_env_upload(tirt_ctx *c, const int32_t *rgb_packed, int w, int h, float 
     c->env_lit = env_is_lit(rgb_packed, (size_t)w * h, power);
     refresh_shade_features(c);
     TIRT_HIP(hipStreamSynchronize(c->stream));
-    return TIRT_OK;
+    return env_table_refresh(c);               // (tirt_env_sampling on: the table of the new image, or none)
+}
+
+int tirt_env_sampling(tirt_ctx *c, int on, float share)
+{
+    // what needs no context first
+    TIRT_REQUIRE(on == 0 || on == 1, "tirt_env_sampling: on is 0 or 1");
+    TIRT_REQUIRE(share > 0.0f && share < 1.0f, "tirt_env_sampling: share outside (0, 1)");
+    CTX(c);
+    if (sync_all(c)) return TIRT_ERR_HIP;      // the kernels in flight read the share, and the texels the table may move
+    const bool share_only = on == 1 && c->env_sample_on == 1 && c->env_tab_valid;
+    c->env_sample_on = on; c->env_share = share;
+    return share_only ? env_table_set_share(c) : env_table_refresh(c);
+}
+
+int tirt_env_table_download(tirt_ctx *c, uint32_t *q, uint64_t *row_sums, uint64_t *marginal, int32_t info[4])
+{
+    CTX(c);
+    if (sync_all(c)) return TIRT_ERR_HIP;
+    return env_table_download(c, q, row_sums, marginal, info);
+}
+
+int tirt_kat_env_sample(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_env_sample: null pointer or negative n");
+    TIRT_REQUIRE(in_stride >= 2 && out_stride >= 10, "tirt_kat_env_sample: stride too small (2 words in, 10 out)");
+    CTX(c);
+    return kat_env(c, 0, in, in_stride, out, out_stride, n);
+}
+
+int tirt_kat_env_pdf(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_env_pdf: null pointer or negative n");
+    TIRT_REQUIRE(in_stride >= 3 && out_stride >= 5, "tirt_kat_env_pdf: stride too small (3 words in, 5 out)");
+    CTX(c);
+    return kat_env(c, 1, in, in_stride, out, out_stride, n);
 }
 
 // One buffer for all textures: `count` quads (offset in ints from the buffer's start, w, h, wrap), then the caller's texels.
@@ -964,7 +999,7 @@ int tirt_shade_features(tirt_ctx *c, uint32_t *out)
 {
     TIRT_REQUIRE(c, "null context");
     TIRT_REQUIRE(out, "tirt_shade_features: null pointer");
-    out[0] = c->shade_features | (c->has_cutout ? (unsigned)SF_CUTOUT : 0u);
+    out[0] = c->shade_features | (c->has_cutout ? (unsigned)SF_CUTOUT : 0u) | (env_sample_active(c) ? (unsigned)SF_ENV_SAMPLE : 0u);
     out[1] = c->shade_specialize ? 1u : 0u;
     return TIRT_OK;
 }
@@ -983,6 +1018,14 @@ int tirt_shade_features_host(const float *material, int nm, const int32_t *primi
     light_kinds(primitive, shape, light, light_count, kind);
     const bool lit = env ? env_is_lit(env, (size_t)(env_w > 0 ? env_w : 0) * (size_t)(env_h > 0 ? env_h : 0), env_power) : env_power != 0.0f;
     *out = shade_features_core(material, nm, kind.data(), light_count, lit);
+    return TIRT_OK;
+}
+// the same with the switch of tirt_env_sampling as an input: bit 1024 where the context would report it (a table needs the image: env == NULL never sets it)
+int tirt_shade_features_host_env(const float *material, int nm, const int32_t *primitive, int n, const float *shape, int ns,
+                                 const int32_t *light, int light_count, const int32_t *env, int env_w, int env_h, float env_power, int env_sampling, uint32_t *out)
+{
+    if (int rc = tirt_shade_features_host(material, nm, primitive, n, shape, ns, light, light_count, env, env_w, env_h, env_power, out)) return rc;
+    if (env_sampling && (*out & SF_ENV) && env_table_exists_host(env, env_w, env_h, env_power)) *out |= SF_ENV_SAMPLE;
     return TIRT_OK;
 }
 
@@ -1653,7 +1696,7 @@ int tirt_kat_shade_step(tirt_ctx *c, uint32_t feat, const float *in, int in_stri
     // what needs no context first (and no device: these refusals hold for a null context too)
     TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_shade_step: null pointer or negative n");
     TIRT_REQUIRE(in_stride >= 23 && out_stride >= 28, "tirt_kat_shade_step: stride too small (23 words in, 28 out)");
-    TIRT_REQUIRE(kat_shade_step_has_inst(feat), "tirt_kat_shade_step: feat is not an instantiation of k_shade (SF_LIGHT_SPHERE, SF_LIGHT_TRI, SF_ALL, SF_ALL | SF_TEXTURE, SF_ALL | SF_TEXTURE | SF_TEXTURE_PARAM)");
+    TIRT_REQUIRE(kat_shade_step_has_inst(feat), "tirt_kat_shade_step: feat is not an instantiation of k_shade (SF_LIGHT_SPHERE, SF_LIGHT_TRI, SF_ALL, SF_ALL | SF_TEXTURE, SF_ALL | SF_TEXTURE | SF_TEXTURE_PARAM; SF_ALL and the last also with SF_ENV_SAMPLE)");
     CTX(c);
     return kat_shade_step(c, feat, in, in_stride, out, out_stride, n);
 }

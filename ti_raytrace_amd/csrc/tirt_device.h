@@ -76,6 +76,8 @@ enum : unsigned {
     SF_CUTOUT = 512u,         // a triangle's material row that is not an emitter's names, in word 1, an uploaded texture flagged as a cut-out mask (tirt_texture_cutout): k_trace's
                               // CUTOUT twins.  Reported by tirt_shade_features; no instantiation of k_shade depends on it (pick_shade_inst never sees it)
     SF_TEXTURE_PARAM = 256u,  // a material row that is not an emitter's names an uploaded roughness, metallic or normal texture (words 7..9; implies uvs in the shading records as 128 does)
+    SF_ENV_SAMPLE = 1024u,    // environment importance sampling is switched on (tirt_env_sampling), the environment is lit and its sampling table exists: k_shade's ENV twins.
+                              // Kept beside tirt_ctx::shade_features as 512 is (k_shade_spec and BDPT never see it); reported by tirt_shade_features
     SF_LIGHT_KINDS = SF_LIGHT_TRI | SF_LIGHT_SPOT_LASER | SF_LIGHT_SPHERE | SF_LIGHT_OTHER
 };
 
@@ -779,6 +781,91 @@ TD v3 shading_normal_rows(const SceneView &s, const float *m, int prim, v3 uv, v
 {
     const int ni = material_map(m, 9);
     return ni >= 0 ? tex_normal_rows(s, ni, prim, uv, N) : N;
+}
+
+// ---- environment importance sampling (include/tirt.h, "Importance sampling of the environment"; tirt_envsample.hip builds the table; no reference counterpart) ----
+// The table lives BEHIND the environment's texels in the same allocation, 16-byte aligned: (total u64, share f32, 0) (marginal u64[h]) (row sums u64[h * w], row j at j * w).
+// SceneView does not change for it: the kernels compiled without SF_ENV_SAMPLE keep their argument block, and their code, to the bit.
+typedef unsigned long long env_u64;
+constexpr int ENV_SAMPLE_MAX_DIM = 16384;           // w, h of an environment that gets a table (row totals times 2^24 stay below 2^64)
+constexpr long long ENV_SAMPLE_MAX_CELLS = 1ll << 25;     // and w * h: the table takes 8 bytes a cell (256 MiB at the cap; 16384 x 2048 fits)
+TM_HD bool env_sample_dims_ok(int w, int h) { return w >= 1 && h >= 1 && w <= ENV_SAMPLE_MAX_DIM && h <= ENV_SAMPLE_MAX_DIM && (long long)w * h <= ENV_SAMPLE_MAX_CELLS; }
+constexpr float ENV_SHADOW_DIST = 2000000.0f;       // the "unbounded" sh_dist of an environment shadow ray: beyond INF_VALUE, so any accepted hit settles a bounded walk
+constexpr float ENV_TWO_PI_SQ = (2.0f * PI_SCENE) * PI_SCENE;
+TM_HD size_t env_table_offset(int w, int h) { return (((size_t)w * (size_t)h) * 4u + 15u) & ~(size_t)15u; }
+TM_HD size_t env_table_bytes(int w, int h) { return 16u + 8u * ((size_t)h + (size_t)w * (size_t)h); }
+// q(i, j): step 1 of include/tirt.h.  Host and device (tm_* only): tirt_shade_features_host_env asks "is any q > 0" without a device.
+TM_HD float env_texel_lum(const int *img, int w, int h, int x, int y)
+{
+    x = x > w - 1 ? w - 1 : x; y = y > h - 1 ? h - 1 : y;
+    const int RGBA = img[(size_t)x * h + y];
+    const float c[3] = {(float)((RGBA & 0x00FF0000) >> 16) / 255.0f, (float)((RGBA & 0x0000FF00) >> 8) / 255.0f, (float)(RGBA & 0x000000FF) / 255.0f};
+    float l[3];
+    for (int k = 0; k < 3; k++) l[k] = (c[k] < 0.04045f) ? c[k] / 12.92f : tm_pow((c[k] + 0.055f) / 1.055f, 2.4f);      // srgb_to_lrgb1
+    return ((l[0] + l[1]) + l[2]) / 3.0f;                                                                                // the level of tirt_moments_converged
+}
+TM_HD unsigned env_cell_q(const int *img, int w, int h, int i, int j)
+{
+    const float m = ((env_texel_lum(img, w, h, i, j) + env_texel_lum(img, w, h, i + 1, j)) + (env_texel_lum(img, w, h, i, j + 1) + env_texel_lum(img, w, h, i + 1, j + 1))) * 0.25f;
+    const float el = (((float)j + 0.5f) / (float)h - 0.5f) * PI_SCENE;
+    const float wgt = m * tm_cos(el);
+    const float s = __builtin_rintf(wgt * 16777216.0f);
+    return s > 0.0f ? (unsigned)s : 0u;
+}
+struct EnvTable { const env_u64 *marg, *rows; env_u64 total; float share; };
+TD EnvTable env_table(const SceneView &sc)
+{
+    const char *b = (const char *)sc.env + env_table_offset(sc.env_w, sc.env_h);
+    EnvTable t; t.total = *(const env_u64 *)b; t.share = *(const float *)(b + 8);
+    t.marg = (const env_u64 *)(b + 16); t.rows = t.marg + sc.env_h;
+    return t;
+}
+// step 3: entry of an inclusive sum `cum[n]` (last entry `tot` > 0) picked by the 24-bit random k, and the offset inside it: all integers, then one exact conversion
+TD int env_pick(const env_u64 *cum, int n, unsigned k, env_u64 tot, float &off)
+{
+    const env_u64 a = (env_u64)k << 40;
+    const env_u64 t = __umul64hi(a, tot);                    // floor(k * tot / 2^24)
+    const env_u64 fb = (a * tot) >> 40;                      // (k * tot) mod 2^24
+    int lo = 0, hi = n - 1;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (cum[mid] > t) hi = mid; else lo = mid + 1; }
+    const env_u64 below = lo > 0 ? cum[lo - 1] : 0ull;
+    env_u64 q = cum[lo] - below;
+    if (q == 0ull) q = 1ull;                                 // (never with tot > 0; keeps the division defined on a table that is not one)
+    off = (float)((((t - below) << 24) | fb) / q) * 5.9604644775390625e-08f;
+    return lo;
+}
+struct EnvSample { int i, j; float tx, ty; v3 d; };
+TD EnvSample env_sample(const EnvTable &t, int w, int h, float ra, float rb)
+{
+    EnvSample s; float offx, offy;
+    const unsigned ka = (unsigned)(ra * 16777216.0f) & 0xffffffu, kb = (unsigned)(rb * 16777216.0f) & 0xffffffu;
+    s.j = env_pick(t.marg, h, ka, t.total, offy);
+    const env_u64 rowtot = t.marg[s.j] - (s.j > 0 ? t.marg[s.j - 1] : 0ull);
+    s.i = env_pick(t.rows + (size_t)s.j * w, w, kb, rowtot, offx);
+    s.tx = ((float)s.i + offx) / (float)w; s.ty = ((float)s.j + offy) / (float)h;
+    const float az = (s.tx * 2.0f) * PI_SCENE - PI_SCENE, el = (s.ty - 0.5f) * PI_SCENE;
+    float sa, ca, se, ce; tm_sincos(az, &sa, &ca); tm_sincos(el, &se, &ce);
+    s.d = V(ce * ca, se, ce * sa);
+    return s;
+}
+// step 4: the lookup coordinates of the miss branch (tirt_render.hip, shade_path) and the pdf over solid angle of the cell they land in
+struct EnvPdf { int i, j; float tx, ty, pdf; };
+TD EnvPdf env_pdf(const EnvTable &t, int w, int h, v3 d)
+{
+    EnvPdf p;
+    const float dis = tm_sqrt(d.x * d.x + d.z * d.z);
+    p.tx = (tm_atan2(d.z, d.x) + PI_SCENE) / PI_SCENE / 2.0f;
+    p.ty = tm_atan2(d.y, dis) / PI_SCENE + 0.5f;
+    const float x = clampf(p.tx * (float)w, 0.0f, (float)w - 1.0f), y = clampf(p.ty * (float)h, 0.0f, (float)h - 1.0f);
+    int i = (int)tm_floor(x), j = (int)tm_floor(y);
+    i = i < 0 ? 0 : (i > w - 1 ? w - 1 : i); j = j < 0 ? 0 : (j > h - 1 ? h - 1 : j);
+    p.i = i; p.j = j; p.pdf = 0.0f;
+    if (dis >= 0.000001f) {
+        const env_u64 *row = t.rows + (size_t)j * w;
+        const env_u64 q = row[i] - (i > 0 ? row[i - 1] : 0ull);
+        p.pdf = (((float)q / (float)t.total) * ((float)w * (float)h)) / (ENV_TWO_PI_SQ * dis);
+    }
+    return p;
 }
 
 // ---- Camera.py:122-142 ----------------------------------------------------------------------------------------

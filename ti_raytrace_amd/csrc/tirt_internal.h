@@ -327,6 +327,9 @@ struct tirt_ctx {
     // by refresh_shade_features, wherever one of them is uploaded again
     std::vector<float> h_material; std::vector<int> h_light_kind; bool env_lit = false;
     unsigned shade_features = 127u;                // (SF_ALL until a scene is uploaded)
+    // environment importance sampling (tirt_envsample.hip): the switch and share of tirt_env_sampling; env_tab_valid = the table stands behind the texels of `env`
+    // (switch on, env_power != 0, w and h within ENV_SAMPLE_MAX_DIM, total > 0).  Bit SF_ENV_SAMPLE is derived (env_sample_active), never stored in shade_features
+    int env_sample_on = 0; float env_share = 0.5f; bool env_tab_valid = false;
     int shade_specialize = 1;                      // option "shade_specialize": 0 = the generic kernel for every scene (A/B and parity switch)
 
     // LBVH (accel/LBvh.py fields)
@@ -558,6 +561,13 @@ int ensure_counters(tirt_ctx *c);
 int ensure_shade_records(tirt_ctx *c);
 int ensure_cutout_records(tirt_ctx *c);      // tirt_api.hip: before every k_trace launch (pt_render, trace_rays), on the main stream
 void refresh_shade_features(tirt_ctx *c);      // tirt_api.hip
+// tirt_envsample.hip
+inline bool env_sample_active(const tirt_ctx *c) { return c->env_sample_on && c->env_tab_valid && (c->shade_features & SF_ENV) != 0u; }
+int env_table_refresh(tirt_ctx *c);            // after the environment or the switch has changed, work in flight drained: builds the table behind the texels, or drops it
+int env_table_download(tirt_ctx *c, uint32_t *q, uint64_t *row_sums, uint64_t *marginal, int32_t info[4]);
+int kat_env(tirt_ctx *c, int which, const float *in, int in_stride, float *out, int out_stride, int n);      // which: 0 sample, 1 pdf
+int env_table_set_share(tirt_ctx *c);          // only the share has changed: rewrites the table's head
+bool env_table_exists_host(const int32_t *env, int w, int h, float power);      // the rule of env_table_refresh on a host image
 int sync_all(tirt_ctx *c);
 int flush_pending(tirt_ctx *c);
 bool kat_shade_step_has_inst(unsigned feat);      // tirt_render.hip: is `feat` the word of an instantiation of k_shade

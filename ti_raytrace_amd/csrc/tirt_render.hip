@@ -106,6 +106,10 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
     const uint32_t frame = frame_begin + (uint32_t)f;
     const uint32_t dim0 = TM_DIM_BOUNCE0 + TM_DIMS_PER_BOUNCE * (uint32_t)bounce;
     const float t = hrec.x;
+    // environment importance sampling (SF_ENV_SAMPLE instantiations only; include/tirt.h): the share of the light samples that go to the environment
+    constexpr bool ENV_NEE = (FEAT & SF_ENV_SAMPLE) != 0u;
+    [[maybe_unused]] float p_env = 0.0f;
+    if constexpr (ENV_NEE) p_env = sc.light_count == 0 ? 1.0f : env_table(sc).share;
     if (t < INF_VALUE) {
         const int prim_id = __float_as_int(hrec.w);
         int mat_id;
@@ -126,7 +130,8 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
                 radiance = radiance + throughout * mat_color;
             } else {
                 const float area = h.area * (float)sc.light_count;              // get_prim_area of the emitter, from its shading record
-                const float light_pdf = (t * t) / (area * fCosTheta);
+                float light_pdf = (t * t) / (area * fCosTheta);
+                if constexpr (ENV_NEE) light_pdf = light_pdf * (1.0f - p_env);
                 radiance = radiance + (throughout * power_heuristic(brdf_pdf, light_pdf)) * mat_color;
             }
         } else {
@@ -164,8 +169,48 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
                 constexpr bool SHARE_SETUP = !(FEAT & SF_GLASS);
                 DisneySetup ds;
                 if (SHARE_SETUP) ds = disney_setup(md, fnormal, -direction);
-                if (!(FEAT & SF_NO_LIGHT) || sc.light_count > 0) {
-                int lidx = (int)(tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LIGHT) * (float)sc.light_count);
+                [[maybe_unused]] bool env_taken = false;
+                if constexpr (ENV_NEE) {
+                    // the environment's turn: r < p_env.  The sample, its pdf and the lookup coordinates of its OWN direction (what a BSDF ray in that direction
+                    // would fetch in the miss branch below) come from the table behind the texels; one shadow ray that arrives iff it hits nothing
+                    if (tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LIGHT) < p_env) {
+                        env_taken = true;
+                        const EnvTable et = env_table(sc);
+                        const EnvSample es = env_sample(et, sc.env_w, sc.env_h, tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LA), tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LB));
+                        const EnvPdf ep = env_pdf(et, sc.env_w, sc.env_h, es.d);
+                        const float NdotL = dot(fnormal, es.d);
+                        if ((NdotL > 0.0f) & (ep.pdf > 0.0f)) {
+                            s.want_shadow = true;
+                            float e_pdf;
+                            const float e_brdf = SHARE_SETUP ? disney_evaluate_pdf_set(ds, fnormal, -direction, es.d, e_pdf)
+                                                             : disney_evaluate_pdf(md, fnormal, -direction, es.d, e_pdf);
+                            const float pdf_l = p_env * ep.pdf;
+                            v3 c = V(0.0f, 0.0f, 0.0f);
+                            int expect = -2;
+                            if (e_pdf > 0.0f) {
+                                const float w = power_heuristic(pdf_l, e_pdf) / maxf(0.0001f, pdf_l);
+                                c = (srgb_to_lrgb(texture2d(sc.env, sc.env_w, sc.env_h, ep.tx, ep.ty)) * sc.env_power) * w;
+                                c = c * throughout;
+                                c = c * reflect_color;
+                                c = c * e_brdf;
+                                c = c * absf(NdotL);
+                                // The reference draws its diffuse lobe with density cos / pi and states 1 / pi (quirk B4, disney_evaluate_pdf), so a BSDF sample
+                                // weighted by 1 / e_pdf -- the switch-off estimator -- converges to the integral of (drawn / e_pdf) * f * cos * L, not of
+                                // f * cos * L.  The light sample carries the same ratio: both strategies then estimate one integrand and their MIS weights,
+                                // which sum to 1, leave its integral where the switch-off render has it.  A metal (diffuseRatio 0) has the ratio exactly 1.
+                                const float dr = SHARE_SETUP ? ds.diffuseRatio : 0.5f * (1.0f - md[5]);
+                                const float drawn = maxf(0.0f, e_pdf + (dr * (float)(1.0 / 3.1415956)) * (NdotL - 1.0f));
+                                c = c * (drawn / e_pdf);
+                                expect = -1;                   // k_trace's hit_prim of a ray that hits nothing
+                            }
+                            s.sh_o = offset_ray(h.pos, fnormal); s.sh_d = es.d; s.sh_c = c; s.sh_expect = expect; s.sh_dist = ENV_SHADOW_DIST;
+                        }
+                    }
+                }
+                if (!env_taken && (!(FEAT & SF_NO_LIGHT) || sc.light_count > 0)) {
+                float r_light = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LIGHT);
+                if constexpr (ENV_NEE) r_light = (r_light - p_env) / (1.0f - p_env);
+                int lidx = (int)(r_light * (float)sc.light_count);
                 if (lidx >= sc.light_count) lidx = sc.light_count - 1;
                 const float ra = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LA);
                 const float rb = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LB);
@@ -185,7 +230,8 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
                     float e_pdf;
                     const float e_brdf = SHARE_SETUP ? disney_evaluate_pdf_set(ds, fnormal, -direction, -light_dir, e_pdf)
                                                      : disney_evaluate_pdf(md, fnormal, -direction, -light_dir, e_pdf);
-                    const float light_pdf = light_dist * light_dist * light_choice_pdf / NdotL_light;
+                    float light_pdf = light_dist * light_dist * light_choice_pdf / NdotL_light;
+                    if constexpr (ENV_NEE) light_pdf = light_pdf * (1.0f - p_env);
                     v3 c = V(0.0f, 0.0f, 0.0f);
                     int expect = -2;                       // never equals a primitive id
                     if (e_pdf > 0.0f) {
@@ -246,6 +292,12 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
         const float tx = (tm_atan2(direction.z, direction.x) + PI_SCENE) / PI_SCENE / 2.0f;
         const float ty = tm_atan2(direction.y, dis) / PI_SCENE + 0.5f;
         const v3 e = srgb_to_lrgb(texture2d(sc.env, sc.env_w, sc.env_h, tx, ty));
+        if constexpr (ENV_NEE) {
+            // MIS against the environment sample the previous vertex could have taken: weight 1 behind a camera or glass vertex (no NEE there)
+            float w = 1.0f;
+            if (perfect_spec != 1) w = power_heuristic(brdf_pdf, p_env * env_pdf(env_table(sc), sc.env_w, sc.env_h, direction).pdf);
+            radiance = radiance + ((e * throughout) * sc.env_power) * w;
+        } else
         radiance = radiance + (e * throughout) * sc.env_power;
     }
 }
@@ -941,6 +993,9 @@ __global__ void k_generate(PathSoA ps, CameraView cam, TileMap tm, int P, int S,
 #ifndef SH_MIN_WAVES_MAPS        // the instantiation with every texture slot (SF_TEXTURE_PARAM): see DESIGN.md, "Roughness, metallic and normal-map textures"
 #define SH_MIN_WAVES_MAPS 4      // at 5 (96 VGPRs) it has 28 bytes of scratch, at 4 112 VGPRs (108 LIST) and none
 #endif
+#ifndef SH_MIN_WAVES_ENV         // the instantiations with environment importance sampling (SF_ENV_SAMPLE): see DESIGN.md, "Importance sampling of the environment"
+#define SH_MIN_WAVES_ENV 4
+#endif
 // The 78 array pointers of the path state are the first kernel argument and are never read from it directly: each of the three places
 // that needs some of them (a path's state in, the survivor's state out, the shadow ray out) reads those from the kernel-argument segment in
 // one batch of scalar loads -- as k_trace does (TR_COLD), and for the same reason: kept in SGPRs across the loop they overflow the scalar
@@ -1288,6 +1343,12 @@ static const ShadeInst SHADE_INST[] = {
     {SF_ALL, k_shade<SF_ALL, SH_MIN_WAVES>, k_shade<SF_ALL, SH_MIN_WAVES, true>},
     {SF_ALL | SF_TEXTURE, k_shade<SF_ALL | SF_TEXTURE, SH_MIN_WAVES>, k_shade<SF_ALL | SF_TEXTURE, SH_MIN_WAVES, true>},      // textured scenes: the generic kernel + the albedo lookup
     {SF_I_MAPS, k_shade<SF_I_MAPS, SH_MIN_WAVES_MAPS>, k_shade<SF_I_MAPS, SH_MIN_WAVES_MAPS, true>}};                              // + roughness, metallic and normal maps
+// environment importance sampling on (tirt_env_sampling), environment lit, table built: the generic kernel or the one with every texture slot, each with the
+// environment's light sample and MIS weights (SF_ENV_SAMPLE).  A table of their own: SHADE_INST, its order and its fall-back are what they were
+constexpr unsigned SF_I_ENV = SF_ALL | SF_ENV_SAMPLE, SF_I_ENV_MAPS = SF_I_MAPS | SF_ENV_SAMPLE;
+static const ShadeInst SHADE_ENV_INST[] = {
+    {SF_I_ENV, k_shade<SF_I_ENV, SH_MIN_WAVES_ENV>, k_shade<SF_I_ENV, SH_MIN_WAVES_ENV, true>},
+    {SF_I_ENV_MAPS, k_shade<SF_I_ENV_MAPS, SH_MIN_WAVES_ENV>, k_shade<SF_I_ENV_MAPS, SH_MIN_WAVES_ENV, true>}};
 static const ShadeSpecInst SHADE_SPEC_INST[] = {
     {SF_I_SPHERE, k_shade_spec<SF_I_SPHERE>}, {SF_I_MESH, k_shade_spec<SF_I_MESH>}, {SF_ALL, k_shade_spec<SF_ALL>}};
 template <class T, size_t N>
@@ -1297,6 +1358,11 @@ static const T &pick_shade_inst(const T (&tab)[N], const tirt_ctx *c)
     if (!c->shade_specialize) while (k + 1 < N && tab[k].feat != SF_ALL) k++;      // from the generic kernel on: behind it only what SF_ALL does not cover
     for (; k + 1 < N; k++) if ((c->shade_features & ~tab[k].feat) == 0u) return tab[k];
     return tab[N - 1];
+}
+static const ShadeInst &pick_shade_rgb(const tirt_ctx *c)
+{
+    if (env_sample_active(c)) return SHADE_ENV_INST[(c->shade_features & ~SF_ALL) ? 1 : 0];
+    return pick_shade_inst(SHADE_INST, c);
 }
 
 // ---- known-answer evaluation of one shading step (tirt_kat_shade_step, include/tirt.h): shade_path<FEAT> -- the body of k_shade<FEAT> -- on row i of a table of
@@ -1329,10 +1395,14 @@ static const KatStepInst KAT_STEP_INST[] = {       // one per entry of SHADE_INS
     {SF_ALL, k_kat_shade_step<SF_ALL, SH_MIN_WAVES>}, {SF_ALL | SF_TEXTURE, k_kat_shade_step<SF_ALL | SF_TEXTURE, SH_MIN_WAVES>},
     {SF_I_MAPS, k_kat_shade_step<SF_I_MAPS, SH_MIN_WAVES_MAPS>}};
 static_assert(sizeof(KAT_STEP_INST) / sizeof(KAT_STEP_INST[0]) == sizeof(SHADE_INST) / sizeof(SHADE_INST[0]), "one known-answer kernel per instantiation of k_shade");
+static const KatStepInst KAT_STEP_ENV_INST[] = {   // one per entry of SHADE_ENV_INST
+    {SF_I_ENV, k_kat_shade_step<SF_I_ENV, SH_MIN_WAVES_ENV>}, {SF_I_ENV_MAPS, k_kat_shade_step<SF_I_ENV_MAPS, SH_MIN_WAVES_ENV>}};
+static_assert(sizeof(KAT_STEP_ENV_INST) / sizeof(KAT_STEP_ENV_INST[0]) == sizeof(SHADE_ENV_INST) / sizeof(SHADE_ENV_INST[0]), "one known-answer kernel per instantiation of k_shade");
 
 static kat_step_fn_t kat_step_inst(unsigned feat)
 {
     for (const KatStepInst &k : KAT_STEP_INST) if (k.feat == feat) return k.fn;
+    for (const KatStepInst &k : KAT_STEP_ENV_INST) if (k.feat == feat) return k.fn;
     return nullptr;
 }
 bool kat_shade_step_has_inst(unsigned feat) { return kat_step_inst(feat) != nullptr; }
@@ -1341,6 +1411,7 @@ int kat_shade_step(tirt_ctx *c, unsigned feat, const float *in, int in_stride, f
 {
     TIRT_REQUIRE(c->n >= 1, "tirt_kat_shade_step: no scene");
     TIRT_REQUIRE((c->shade_features & ~feat) == 0u, "tirt_kat_shade_step: feat does not cover the scene's feature word (tirt_shade_features)");
+    TIRT_REQUIRE(!(feat & SF_ENV_SAMPLE) || env_sample_active(c), "tirt_kat_shade_step: an instantiation with bit 1024 needs the environment's sampling table (tirt_env_sampling on, a lit environment)");
     const kat_step_fn_t fn = kat_step_inst(feat);
     TIRT_REQUIRE(fn, "tirt_kat_shade_step: feat is not an instantiation of k_shade");
     TIRT_REQUIRE(!(feat & (SF_TEXTURE | SF_TEXTURE_PARAM)) || c->tex_count > 0, "tirt_kat_shade_step: the textured instantiation needs uploaded textures (tirt_texture_upload): without them no material row's slot is checked");
@@ -1534,7 +1605,7 @@ int pt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed,
         const int sh_cap = two_big ? 2 * c->sh_grid : c->sh_grid;
         int grid_shade = (S + SH_BLOCK - 1) / SH_BLOCK; if (grid_shade > sh_cap) grid_shade = sh_cap;
         v3 eye_v; eye_v.x = c->cam.eye[0]; eye_v.y = c->cam.eye[1]; eye_v.z = c->cam.eye[2];
-        const shade_fn_t shade_fn = list ? pick_shade_inst(SHADE_INST, c).fn_list : pick_shade_inst(SHADE_INST, c).fn;
+        const shade_fn_t shade_fn = list ? pick_shade_rgb(c).fn_list : pick_shade_rgb(c).fn;
         const shade_spec_fn_t shade_spec_fn = pick_shade_inst(SHADE_SPEC_INST, c).fn;
         for (int b = 0; b < max_depth; b++) {
             const PathSoA &in = L.ps.st[b & 1], &out = L.ps.st[(b + 1) & 1];

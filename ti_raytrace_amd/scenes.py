@@ -148,6 +148,50 @@ class sky_dome(Example.example):
         self.frame_camera(2.0)
 
 
+def sun_sky_image(w=16, h=8, floor=8, at=(11, 1)):
+    """(h, w, 3) uint8, row 0 the top: one texel at 255 -- a "sun" about 480 times the floor in linear light -- on a dim uniform sky."""
+    img = np.full((h, w, 3), floor, np.uint8)
+    img[at[1], at[0]] = 255
+    return img
+
+
+def _box(lo, hi):
+    """the twelve triangles of an axis-aligned box, outward facing"""
+    x0, y0, z0 = lo
+    x1, y1, z1 = hi
+    c = [(x0, y0, z0), (x1, y0, z0), (x1, y1, z0), (x0, y1, z0), (x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)]
+    quads = [(0, 3, 2, 1), (4, 5, 6, 7), (0, 1, 5, 4), (3, 7, 6, 2), (0, 4, 7, 3), (1, 2, 6, 5)]
+    return np.array([[c[q[0]], c[q[a]], c[q[a + 1]]] for q in quads for a in (1, 2)], np.float64)
+
+
+class sun_ground(Example.example):
+    """No reference counterpart: a box on a ground quad under a synthetic sky whose light is nearly all in one texel, no emitters -- the case BSDF
+    sampling alone handles worst.  ``env_sampling=True`` (the default here) aims the light samples at the sky by its brightness (include/tirt.h,
+    "Importance sampling of the environment"); ``env_sampling=False`` renders with the reference's estimator.  Both surfaces are rough metals, or rough
+    dielectrics with ``metallic=0.0``."""
+
+    def __init__(self, imgSizeX, imgSizeY, sample_count, device_id=None, env_power=20.0, sky=None, env_sampling=True, metallic=1.0, **pt_kwargs):
+        Example.example.__init__(self, imgSizeX, imgSizeY, sample_count, device_id)
+
+        def disney(colour, rough):
+            m = SCD.Material(); m.type = SCD.MAT_DISNEY; m.setMetal(metallic); m.setRough(rough); m.setColor([colour[0], colour[1], colour[2], 1.0]); m.alebdoTex = -1
+            return m
+        g = 2.0
+        self.scene.add_mesh(np.array([[(-g, 0, -g), (-g, 0, g), (g, 0, g)], [(-g, 0, -g), (g, 0, g), (g, 0, -g)]], np.float64), disney((0.7, 0.7, 0.7), 0.8))
+        self.scene.add_mesh(_box((-0.5, 0.0, -0.5), (0.5, 1.5, 0.5)), disney((0.8, 0.4, 0.2), 0.5))
+        self.scene.add_env(sun_sky_image() if sky is None else sky, env_power)
+        self.integrator = PT_RGB.PathTrace(imgSizeX, imgSizeY, self.cam, self.scene, 64, env_sampling=env_sampling, **pt_kwargs)
+
+    def frame_camera(self, scale_factor=0.6):
+        Example.example.frame_camera(self, scale_factor)
+        self.cam.set_view_point(1.96, 0.7, 0.0, self.cam.scale)      # across the shadow, from above
+
+    def build_scene(self):
+        Example.example.build_scene(self)
+        self.scene.total_area()
+        self.frame_camera()
+
+
 # ---- synthetic scene -------------------------------------------------------------------------
 _GOLDEN = np.uint64(0x9E3779B97F4A7C15)
 
