@@ -746,7 +746,10 @@ int tirt_primary_beam_stats(tirt_ctx *ctx, uint64_t out[12]);
 int tirt_stats(tirt_ctx *ctx, tirt_stats_t *out);
 int tirt_stats_reset(tirt_ctx *ctx);
 
-/* Device-side evaluation of the shared scalar functions (known-answer tests):
+/* The known-answer entries tirt_kat_* (these and the ones further up; csrc/tirt_kat.hip): row i of `in` is evaluated on thread i of one launch into row i of `out`.
+ * In every one of them the words of an output row beyond those the entry writes (an out_stride larger than it needs) are zero, and n == 0 returns TIRT_OK
+ * without touching the device or `out`.
+ * Device-side evaluation of the shared scalar functions:
  * fn 0 sin 1 cos 2 exp 3 log 4 pow(x,y) 5 atan2(x,y) 6 acos 7 sqrt 8 x/y */
 int tirt_kat_math(tirt_ctx *ctx, int fn, const float *x, const float *y, float *out, int n);
 /* which 0 Disney.evaluate_pdf  in: mat10,N3,V3,L3        out: f, pdf

@@ -362,6 +362,16 @@ def _ptr(arr):
     return None if arr is None else arr.ctypes.data_as(C.c_void_p)
 
 
+def _kat_rows(symbol, handle, head, rows, out_stride, words=False, in_stride=None):
+    """One known-answer entry over a table of rows: symbol(handle, *head, rows, in_stride, out, out_stride, n) -> the zero-initialised (n, out_stride) float32.
+    words: the rows are 32-bit words taken as their bits (integers ride in them); otherwise they are converted to float32."""
+    rows = np.ascontiguousarray(rows).view(np.float32) if words else np.ascontiguousarray(rows, np.float32)
+    n, stride = rows.shape
+    out = np.zeros((n, max(int(out_stride), 1)), np.float32)
+    check(getattr(lib(), symbol)(handle, *head, rows.reshape(-1), int(stride if in_stride is None else in_stride), out.reshape(-1), int(out_stride), n))
+    return out
+
+
 class Context:
     """RAII wrapper around tirt_ctx*."""
 
@@ -420,11 +430,7 @@ class Context:
 
     def kat_texture(self, rows, out_stride=6):
         """include/tirt.h, tirt_kat_texture: rows (n, >= 3) of 32-bit words (texture number as its bits, u, v) -> (n, out_stride) float32: c3, srgb_to_lrgb(c)3"""
-        rows = np.ascontiguousarray(rows).view(np.float32)
-        n, stride = rows.shape
-        out = np.zeros((n, max(int(out_stride), 1)), np.float32)
-        check(lib().tirt_kat_texture(self.handle, rows.reshape(-1), int(stride), out.reshape(-1), int(out_stride), n))
-        return out
+        return _kat_rows("tirt_kat_texture", self.handle, (), rows, out_stride, words=True)
 
     def texture_cutout(self, flags):
         """include/tirt.h, tirt_texture_cutout: one 0 / 1 per uploaded texture -- is its top byte (255 - alpha) a cut-out mask"""
@@ -432,19 +438,11 @@ class Context:
 
     def kat_texture_alpha(self, rows, out_stride=KAT_ALPHA_OUT):
         """include/tirt.h, tirt_kat_texture_alpha: rows (n, >= 3) of 32-bit words (texture number as its bits, u, v) -> (n, out_stride) float32: alpha, decision"""
-        rows = np.ascontiguousarray(rows).view(np.float32)
-        n, stride = rows.shape
-        out = np.zeros((n, max(int(out_stride), 1)), np.float32)
-        check(lib().tirt_kat_texture_alpha(self.handle, rows.reshape(-1), int(stride), out.reshape(-1), int(out_stride), n))
-        return out
+        return _kat_rows("tirt_kat_texture_alpha", self.handle, (), rows, out_stride, words=True)
 
     def kat_material_maps(self, rows, out_stride=KAT_MAPS_OUT):
         """include/tirt.h, tirt_kat_material_maps: rows (n, >= 3) of 32-bit words (primitive as its bits, hit u, hit v) -> (n, out_stride) float32: uv2, rough, metal, N'3, 0"""
-        rows = np.ascontiguousarray(rows).view(np.float32)
-        n, stride = rows.shape
-        out = np.zeros((n, max(int(out_stride), 1)), np.float32)
-        check(lib().tirt_kat_material_maps(self.handle, rows.reshape(-1), int(stride), out.reshape(-1), int(out_stride), n))
-        return out
+        return _kat_rows("tirt_kat_material_maps", self.handle, (), rows, out_stride, words=True)
 
     def env_sampling(self, on, share=0.5):
         """include/tirt.h, tirt_env_sampling: importance-sample the environment in PT_RGB (NEE + MIS); share of the light samples it gets beside emitters"""
@@ -463,17 +461,11 @@ class Context:
 
     def kat_env_sample(self, rows, out_stride=KAT_ENV_SAMPLE_OUT):
         """include/tirt.h, tirt_kat_env_sample: rows (n, >= 2) float32 (ra, rb) -> (n, out_stride) float32: i, j (bits), tx, ty, d3, pdf, lookup cell i, j (bits)"""
-        rows = np.ascontiguousarray(rows, np.float32)
-        out = np.zeros((rows.shape[0], max(int(out_stride), 1)), np.float32)
-        check(lib().tirt_kat_env_sample(self.handle, rows.reshape(-1), int(rows.shape[1]), out.reshape(-1), int(out_stride), rows.shape[0]))
-        return out
+        return _kat_rows("tirt_kat_env_sample", self.handle, (), rows, out_stride)
 
     def kat_env_pdf(self, rows, out_stride=KAT_ENV_PDF_OUT):
         """include/tirt.h, tirt_kat_env_pdf: rows (n, >= 3) float32 directions -> (n, out_stride) float32: i, j (bits), tx, ty, pdf"""
-        rows = np.ascontiguousarray(rows, np.float32)
-        out = np.zeros((rows.shape[0], max(int(out_stride), 1)), np.float32)
-        check(lib().tirt_kat_env_pdf(self.handle, rows.reshape(-1), int(rows.shape[1]), out.reshape(-1), int(out_stride), rows.shape[0]))
-        return out
+        return _kat_rows("tirt_kat_env_pdf", self.handle, (), rows, out_stride)
 
     def shade_features(self):
         """(feature word, shade_specialize option) of the context: include/tirt.h, tirt_shade_features"""
@@ -850,11 +842,7 @@ class Context:
         return out
 
     def kat_brdf(self, which, inp, out_stride):
-        inp = np.ascontiguousarray(inp, np.float32)
-        n, stride = inp.shape
-        out = np.zeros((n, out_stride), np.float32)
-        check(lib().tirt_kat_brdf(self.handle, int(which), inp.reshape(-1), stride, out.reshape(-1), out_stride, n))
-        return out
+        return _kat_rows("tirt_kat_brdf", self.handle, (int(which),), inp, out_stride)
 
     def shade_table_download(self, which, count):
         """The shading records (which 0, count = primitives) or the light records (which 1, count = light_count): (count, 8, 4) float32."""
@@ -876,20 +864,12 @@ class Context:
         return kat_shade_step(self.handle, feat, rows, out_stride)
 
     def kat_spec(self, which, inp, out_stride):
-        inp = np.ascontiguousarray(inp, np.float32)
-        n, stride = inp.shape
-        out = np.zeros((n, out_stride), np.float32)
-        check(lib().tirt_kat_spec(self.handle, int(which), inp.reshape(-1), stride, out.reshape(-1), out_stride, n))
-        return out
+        return _kat_rows("tirt_kat_spec", self.handle, (int(which),), inp, out_stride)
 
 
 def kat_shade_step(handle, feat, rows, out_stride=KAT_STEP_OUT, in_stride=None):
     """tirt_kat_shade_step on a raw context handle (None: only the refusals that need no context can be reached)."""
-    rows = np.ascontiguousarray(rows).view(np.float32)
-    n, stride = rows.shape
-    out = np.zeros((n, max(int(out_stride), 1)), np.float32)
-    check(lib().tirt_kat_shade_step(handle, int(feat), rows.reshape(-1), int(stride if in_stride is None else in_stride), out.reshape(-1), int(out_stride), n))
-    return out
+    return _kat_rows("tirt_kat_shade_step", handle, (int(feat),), rows, out_stride, words=True, in_stride=in_stride)
 
 
 def texture_upload(handle, textures):

@@ -160,23 +160,9 @@ int kat_env(tirt_ctx *c, int which, const float *in, int in_stride, float *out, 
     }
     if (n == 0) return TIRT_OK;
     if (sync_all(c)) return TIRT_ERR_HIP;
-    DevBuf din, dout;
-    int rc = TIRT_OK;
-    const size_t in_bytes = sizeof(float) * (size_t)n * in_stride, out_bytes = sizeof(float) * (size_t)n * out_stride;
-    if (din.ensure(in_bytes) || dout.ensure(out_bytes)) rc = TIRT_ERR_HIP;
-    if (rc == TIRT_OK) {
-        hipError_t e = hipMemcpyAsync(din.p, in, in_bytes, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(dout.p, 0, out_bytes, c->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_kat_env, dim3((n + 63) / 64), dim3(64), 0, c->stream, scene_view(c), which, din.as<float>(), in_stride, dout.as<float>(), out_stride, n);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, out_bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { set_error(std::string(fn) + ": " + hipGetErrorString(e)); rc = TIRT_ERR_HIP; }
-    }
-    din.release(); dout.release();
-    return rc;
+    return kat_round_trip(c, fn, {{in, kat_row_bytes(n, in_stride)}}, out, kat_row_bytes(n, out_stride), [&](const void *const *din, void *dout) {
+        hipLaunchKernelGGL(k_kat_env, dim3((n + 63) / 64), dim3(64), 0, c->stream, scene_view(c), which, (const float *)din[0], in_stride, (float *)dout, out_stride, n);
+    });
 }
 
 }  // namespace tirt

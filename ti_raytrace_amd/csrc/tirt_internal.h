@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <initializer_list>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -572,4 +573,39 @@ int sync_all(tirt_ctx *c);
 int flush_pending(tirt_ctx *c);
 bool kat_shade_step_has_inst(unsigned feat);      // tirt_render.hip: is `feat` the word of an instantiation of k_shade
 int kat_shade_step(tirt_ctx *c, unsigned feat, const float *in, int in_stride, float *out, int out_stride, int n);
+
+// The device round trip of a known-answer entry (tirt_kat_*, tirt_spec_table_build), after the entry's own checks: device copies of the inputs (on c->stream;
+// an input of 0 bytes gets none, its pointer is null), a zeroed output, `launch(device inputs in order, device output)` -- one hipLaunchKernelGGL on c->stream --,
+// the launch's own error, the copy back and the wait for it.  A HIP failure anywhere is "<fn>: <its text>" and TIRT_ERR_HIP; the scratch is freed on every path.
+struct KatIn { const void *src; size_t bytes; };
+inline size_t kat_row_bytes(int n, int stride) { return sizeof(float) * (size_t)n * stride; }      // n rows of `stride` 32-bit words
+template <class Launch>
+int kat_round_trip(tirt_ctx *c, const char *fn, std::initializer_list<KatIn> in, void *out, size_t out_bytes, Launch launch)
+{
+    std::vector<void *> d(in.size() + 1, nullptr);      // the inputs, then the output
+    void *&dout = d.back();
+    hipError_t e = hipMalloc(&dout, out_bytes);
+    size_t k = 0;
+    for (const KatIn &i : in) {
+        if (e == hipSuccess && i.bytes) e = hipMalloc(&d[k], i.bytes);
+        if (e == hipSuccess && i.bytes) e = hipMemcpyAsync(d[k], i.src, i.bytes, hipMemcpyHostToDevice, c->stream);
+        k++;
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(dout, 0, out_bytes, c->stream);
+    if (e == hipSuccess) { launch((const void *const *)d.data(), dout); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    for (void *p : d) if (p) (void)hipFree(p);
+    if (e == hipSuccess) return TIRT_OK;
+    set_error(std::string(fn) + ": " + hipGetErrorString(e));
+    return TIRT_ERR_HIP;
+}
 }  // namespace tirt
+
+// what every entry point starts with: the context, its device and -- all but tirt_pt_rgb_render and the few that say so -- the render calls still pending
+#define CTX_NOFLUSH(c)                                                             \
+    TIRT_REQUIRE(c, "null context");                                               \
+    TIRT_HIP(hipSetDevice((c)->device))
+#define CTX(c)                                                                     \
+    CTX_NOFLUSH(c);                                                                \
+    do { if (int rc__ = flush_pending(c)) return rc__; } while (0)

@@ -1424,23 +1424,9 @@ int kat_shade_step(tirt_ctx *c, unsigned feat, const float *in, int in_stride, f
     if (n == 0) return TIRT_OK;
     if (sync_all(c)) return TIRT_ERR_HIP;
     if (ensure_shade_records(c)) return TIRT_ERR_HIP;
-    DevBuf din, dout;
-    int rc = TIRT_OK;
-    const size_t in_bytes = sizeof(float) * (size_t)n * in_stride, out_bytes = sizeof(float) * (size_t)n * out_stride;
-    if (din.ensure(in_bytes) || dout.ensure(out_bytes)) rc = TIRT_ERR_HIP;
-    if (rc == TIRT_OK) {
-        hipError_t e = hipMemcpyAsync(din.p, in, in_bytes, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(dout.p, 0, out_bytes, c->stream);          // (the words of a row beyond the 28: zero)
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(fn, dim3((n + SH_BLOCK - 1) / SH_BLOCK), dim3(SH_BLOCK), 0, c->stream, scene_view(c), din.as<float>(), in_stride, dout.as<float>(), out_stride, n);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, out_bytes, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { set_error(std::string("tirt_kat_shade_step: ") + hipGetErrorString(e)); rc = TIRT_ERR_HIP; }
-    }
-    din.release(); dout.release();
-    return rc;
+    return kat_round_trip(c, "tirt_kat_shade_step", {{in, kat_row_bytes(n, in_stride)}}, out, kat_row_bytes(n, out_stride), [&](const void *const *din, void *dout) {
+        hipLaunchKernelGGL(fn, dim3((n + SH_BLOCK - 1) / SH_BLOCK), dim3(SH_BLOCK), 0, c->stream, scene_view(c), (const float *)din[0], in_stride, (float *)dout, out_stride, n);
+    });
 }
 
 // integrator/PT_Spec.py:141-158 (AddSplat) + :273-274, frames applied in order

@@ -192,25 +192,12 @@ int tirt_spec_table_build(tirt_ctx *c, int res, const float *cie_xyz, const floa
     SptArgs a;
     a.wp[0] = wp[0] / wp[1]; a.wp[2] = wp[2] / wp[1]; a.wp[1] = wp[1] / wp[1];
     a.res = res;
-    DevBuf d_tbl, d_scale, d_out;
     const size_t nout = sizeof(float) * 9 * (size_t)res * res * res;
-    int rc = TIRT_OK;
-    if (d_tbl.ensure(sizeof(double) * tbl.size()) || d_scale.ensure(sizeof(double) * scale.size()) || d_out.ensure(nout)) rc = TIRT_ERR_HIP;
-    if (rc == TIRT_OK) {
-        hipError_t e = hipMemcpyAsync(d_tbl.p, tbl.data(), sizeof(double) * tbl.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_scale.p, scale.data(), sizeof(double) * scale.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_out.p, 0, nout, c->stream);
-        a.rgb_tbl = d_tbl.as<double>(); a.scale = d_scale.as<double>(); a.out = d_out.as<float>();
-        if (e == hipSuccess) {
-            const int cells = 3 * res * res;
-            hipLaunchKernelGGL(k_spec_table, dim3((cells + 63) / 64), dim3(64), 0, c->stream, a);
-            e = hipMemcpyAsync(coeff_out, d_out.p, nout, hipMemcpyDeviceToHost, c->stream);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { set_error(std::string("tirt_spec_table_build: ") + hipGetErrorString(e)); rc = TIRT_ERR_HIP; }
-    }
-    d_tbl.release(); d_scale.release(); d_out.release();
-    return rc;
+    return kat_round_trip(c, "tirt_spec_table_build", {{tbl.data(), sizeof(double) * tbl.size()}, {scale.data(), sizeof(double) * scale.size()}}, coeff_out, nout, [&](const void *const *din, void *dout) {
+        a.rgb_tbl = (const double *)din[0]; a.scale = (const double *)din[1]; a.out = (float *)dout;
+        const int cells = 3 * res * res;
+        hipLaunchKernelGGL(k_spec_table, dim3((cells + 63) / 64), dim3(64), 0, c->stream, a);
+    });
 }
 
 int tirt_kat_spec(tirt_ctx *c, int which, const float *in, int in_stride, float *out, int out_stride, int n)
@@ -218,22 +205,10 @@ int tirt_kat_spec(tirt_ctx *c, int which, const float *in, int in_stride, float 
     TIRT_REQUIRE(c && in && out && n >= 0 && which >= 0 && which <= 11, "tirt_kat_spec: bad arguments");
     TIRT_REQUIRE(c->spec_set && c->spec_view, "tirt_kat_spec: tirt_spectral_upload first");
     if (n == 0) return TIRT_OK;
-    TIRT_HIP(hipSetDevice(c->device));
-    DevBuf din, dout;
-    int rc = TIRT_OK;
-    if (din.ensure(sizeof(float) * (size_t)n * in_stride) || dout.ensure(sizeof(float) * (size_t)n * out_stride)) rc = TIRT_ERR_HIP;
-    if (rc == TIRT_OK) {
-        hipError_t e = hipMemcpyAsync(din.p, in, sizeof(float) * (size_t)n * in_stride, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(dout.p, 0, sizeof(float) * (size_t)n * out_stride, c->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_kat_spec, dim3((n + 255) / 256), dim3(256), 0, c->stream, *(const SpecView *)c->spec_view, which, din.as<float>(), in_stride, dout.as<float>(), out_stride, n);
-            e = hipMemcpyAsync(out, dout.p, sizeof(float) * (size_t)n * out_stride, hipMemcpyDeviceToHost, c->stream);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { set_error(std::string("tirt_kat_spec: ") + hipGetErrorString(e)); rc = TIRT_ERR_HIP; }
-    }
-    din.release(); dout.release();
-    return rc;
+    CTX_NOFLUSH(c);      // (this entry does not submit the render calls still pending: it reads the spectral tables alone)
+    return kat_round_trip(c, "tirt_kat_spec", {{in, kat_row_bytes(n, in_stride)}}, out, kat_row_bytes(n, out_stride), [&](const void *const *din, void *dout) {
+        hipLaunchKernelGGL(k_kat_spec, dim3((n + 255) / 256), dim3(256), 0, c->stream, *(const SpecView *)c->spec_view, which, (const float *)din[0], in_stride, (float *)dout, out_stride, n);
+    });
 }
 
 int tirt_spectral_upload(tirt_ctx *c, const tirt_spectral_t *t)
