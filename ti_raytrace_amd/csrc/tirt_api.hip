@@ -371,16 +371,6 @@ static int upload(DevBuf &b, const void *src, size_t bytes, hipStream_t st)
     return 0;
 }
 
-static void drain_render_events(tirt_ctx *c)
-{
-    for (auto &pr : c->ev_pool) {
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) c->ms_render += ms;
-        (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second);
-    }
-    c->ev_pool.clear();
-}
-
 }  // namespace tirt
 
 using namespace tirt;
@@ -434,7 +424,7 @@ void tirt_destroy(tirt_ctx *c)
     if (c->comm) { tirt_ctx *one[1] = {c}; (void)tirt_comm_destroy(one, 1); }
     (void)hipSetDevice(c->device);
     (void)sync_all(c);
-    drain_render_events(c);
+    retire_render_events(c, false);
     DevBuf *bufs[] = {&c->vertex, &c->primitive, &c->material, &c->shape, &c->light, &c->env, &c->tex, &c->cut_uv, &c->cut_flags, &c->mat_lrgb, &c->shade_rec, &c->light_rec, &c->morton_unsorted, &c->keys_a,
                       &c->keys_b, &c->vals_a, &c->vals_b, &c->hist, &c->morton_sorted, &c->bvh_node, &c->compact, &c->parent,
                       &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb, &c->aov, &c->mom, &c->mom_cnt, &c->pixset, &c->pixset_tmp, &c->tp_mem, &c->mv_rec, &c->mv_snap, &c->dn_mem, &c->dn_out,
@@ -1283,7 +1273,7 @@ int tirt_stats(tirt_ctx *c, tirt_stats_t *out)
     if (sync_all(c)) return TIRT_ERR_HIP;
     TIRT_HIP(hipMemcpyAsync(&h, c->dev_counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     TIRT_HIP(hipStreamSynchronize(c->stream));
-    drain_render_events(c);
+    retire_render_events(c, false);
     out->rays_closest = h.rays_closest; out->rays_shadow = h.rays_shadow;
     out->box_closest = h.box_closest; out->leaf_closest = h.leaf_closest;
     out->box_shadow = h.box_shadow; out->leaf_shadow = h.leaf_shadow;
@@ -1347,7 +1337,7 @@ int tirt_stats_reset(tirt_ctx *c)
     CTX(c);
     if (ensure_counters(c)) return TIRT_ERR_HIP;
     if (sync_all(c)) return TIRT_ERR_HIP;
-    drain_render_events(c);
+    retire_render_events(c, false);
     TIRT_HIP(hipMemsetAsync(c->dev_counters.p, 0, sizeof(DevCounters), c->stream));
     TIRT_HIP(hipStreamSynchronize(c->stream));
     c->ms_render = c->ms_trace_closest = c->ms_trace_shadow = c->ms_shade = 0.0;

@@ -3,7 +3,7 @@
 //
 // The reference (integrator/BDPT_RGB.py:595-642) is one per-pixel kernel: eye_path, light_path, then every (e, l)
 // connection, each with its traversal inlined.  Here every ray goes through the traversal kernel of PT_RGB
-// (tirt_render.hip, k_trace) in large batches, and the arithmetic around the rays runs in between:
+// (tirt_trace.hip, k_trace) in large batches, and the arithmetic around the rays runs in between:
 //
 //   k_bd_init          lens vertex + camera ray, light vertex + first light ray       BDPT_RGB.py:104-125, 201-228
 //   6 x { trace the live rays ; k_bd_step(d) }   vertex d of the eye and of the light sub-path; the rays of a depth are a
@@ -29,7 +29,7 @@
 // MAT_DISNEY in mis_weight; restores to index -1 skipped.  Light-tracing contributions are added to other pixels with
 // float atomics, so a frame is reproducible only up to the order of those additions (the parity test uses the north
 // star's 1e-3 relative-L2 tolerance; measured 1e-7).
-#include "tirt_internal.h"
+#include "tirt_trace.h"
 #include "tirt_spectral.h"
 
 #if (defined(BDX_NO_ATOMIC) || defined(BDX_NO_MIS) || defined(BDX_NO_PRESUM) || defined(BD_RESOLVE_WAVES)) && !defined(TIRT_EXPERIMENTS)

@@ -5,12 +5,12 @@
 // out there).  No bounce loop, no shading, no running mean.  Here it is three launches on the context's main stream:
 //
 //   k_debug_generate   camera direction of every local pixel            Camera.py:131-142
-//   k_trace<closest>   closest hit, origin = the eye (TraceArgs::eye)    Scene.py:702-744 (trace_rays, tirt_render.hip)
+//   k_trace<closest>   closest hit, origin = the eye (TraceArgs::eye)    Scene.py:702-744 (trace_rays, tirt_trace.hip)
 //   k_debug_resolve    the view of the chosen mode, written to hdr       integrator/Debug.py:55-67
 //
 // Queue index k is local pixel k of this context's tile (local_to_pixel): a wave holds an 8 x 8 pixel bundle, as in k_generate.
 // Pixels of other tiles are not touched.
-#include "tirt_internal.h"
+#include "tirt_trace.h"
 
 namespace tirt {
 

@@ -43,6 +43,16 @@ TD float signf(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
 TD float mixf(float a, float b, float t) { return a * (1.0f - t) + b * t; }
 TD v3 mix3(v3 a, v3 b, float t) { return V(mixf(a.x, b.x, t), mixf(a.y, b.y, t), mixf(a.z, b.z, t)); }
 
+// ---- votes and sums over a wave of 64 (k_trace, k_shade, k_shade_spec) ------------------------
+TD unsigned long long ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+TD bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
+TD unsigned long long wave_sum(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+
 // ---- scene view passed to kernels by value ---------------------------------------------------
 struct SceneView {
     const float *vertex;     // [nv*9]

@@ -103,7 +103,7 @@ constexpr int TR_BLOCK = TR_BLOCK_SIZE;                  // threads per persiste
 constexpr int TIRT_MAX_DEVICES = 64;
 // dynamic LDS of a k_trace block: `depth` stack entries per lane + the LDS copy of the tree top (64-byte records)
 #ifdef TR_PADG
-constexpr size_t TR_LADDER_LDS = 4 * TR_BLOCK;           // bound-ladder builds only (tirt_render.hip, TR_LADDER_PADS): where the dummy gathers land
+constexpr size_t TR_LADDER_LDS = 4 * TR_BLOCK;           // bound-ladder builds only (tirt_trace.hip, TR_LADDER_PADS): where the dummy gathers land
 #else
 constexpr size_t TR_LADDER_LDS = 0;
 #endif
@@ -123,7 +123,7 @@ struct BvhView {
     // a ray that starts too far away for that box to be safe (cull_far < 0, k_trace) gets these leaves pushed at its start.
     int far_qcode;                // where a far-origin ray starts: root_qcode, or the first of the chain nodes that hold the padded analytic spheres beside the root (lbvh_build)
 };
-// what the CUTOUT twins of k_trace read beside BvhView (TraceArgsCut, tirt_render.hip)
+// what the CUTOUT twins of k_trace read beside BvhView (TraceArgsCut, tirt_trace.h)
 struct CutView { const float4 *uv; const int *tex; };
 
 // ---- what k_trace (ordered and exhaustive), k_pvb_beam and k_pvb_cand must agree on to the last bit: ONE definition each ----
@@ -498,24 +498,9 @@ int exp_wide_from_tree(tirt_ctx *c, const float *compact_host, const int *csize_
 struct SpecView;
 int pt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed, int max_depth, int stack_size, int flags, const SpecView *spec = nullptr);   // spec != nullptr: PT_Spec
 int bdpt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t seed, bool spectral = false);      // spectral: BDPT_SPEC
-// One k_trace launch outside the path tracer (trace_rays, tirt_render.hip): the traversal service of BDPT, the primary beams, Debug and the
-// ray queries.  The rays are 32-byte records (TraceArgs::ray4) or, without them, camera rays from the eye with their directions in dx / dy / dz.
-struct TraceJob {
-    int lane = -1;                               // < 0: the main stream, c->spill and c->counters_mem; else that render lane's stream and buffers
-    int stack_size = 64;                         // sizes the spill (the integrator's stack_size)
-    int flags = 0;                               // TIRT_TRAVERSE_EXHAUSTIVE | TIRT_COUNT_NODES: the instantiation, timeline arming
-    bool query = false;                          // KIND_QUERY (bounded queries whose expect / bound ride in the records) instead of KIND_CLOSEST
-    const float4 *ray4 = nullptr;
-    const int *ray_index = nullptr;              // KIND_QUERY: ray q is record ray_index[q]
-    const float *dx = nullptr, *dy = nullptr, *dz = nullptr;
-    int count = 0; const int *count_ptr = nullptr;      // the rays: *count_ptr if given, `count` then being its capacity (sizes the grid)
-    float4 *hit = nullptr;
-    int2 *per_ray_counts = nullptr;              // N_box / N_leaf per ray, under TIRT_COUNT_NODES only
-    bool count_rays = true;                      // false: the caller counts its rays itself (TraceArgs::no_ray_count)
-    int grid_cap = 0;                            // persistent blocks at most: c->tr_grid_alone or c->tr_grid
-};
-int trace_rays(tirt_ctx *c, const TraceJob &j);
-int trace_rays_prepare(tirt_ctx *c, int lane);      // allocates what trace_rays needs on that lane at bdpt_stack_size (stack spill, fetch cursors)
+// tirt_render.hip: the (begin, end) pairs of pt_render's batches (tirt_ctx::ev_pool) into ms_render, then destroyed -- all of them (the caller has
+// synchronised), or with finished_only those whose batch is done (long render loops that never ask for stats)
+void retire_render_events(tirt_ctx *c, bool finished_only);
 int debug_render(tirt_ctx *c, uint32_t frame, uint32_t seed, int mode, int stack_size, int flags);      // tirt_debug.hip
 // Debug's camera rays and their closest hits per local pixel, in c->debug_mem on the main stream (tirt_debug.hip; frame 0: the pixel centres)
 struct DebugRays { float4 *hit; float *dx, *dy, *dz; TileMap tm; };

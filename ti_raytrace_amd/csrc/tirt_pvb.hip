@@ -29,7 +29,7 @@
 // the list lies within bound it is therefore k_trace's; if not, k_trace is asked.  A list made with bound = infinity (some probe
 // left the scene) and not cut short is complete: a miss on it is a miss.  Rays that fail `slabs` on the root's exact box miss, as in
 // k_trace (KIND_CLOSEST).  A camera further than TR_FAR_RHO extents from the scene (k_trace stops culling by distance there) gets no lists.
-#include "tirt_internal.h"
+#include "tirt_trace.h"
 #include <cstring>
 
 namespace tirt {

@@ -6,7 +6,7 @@
 // context's main stream, ordered after and before the caller's stream by two events (no host sync):
 //
 //   k_query_pack               caller rays (f32, any row stride >= 6) -> 32-byte records TraceArgs::ray4: (o.xyz, d.x), (d.y, d.z, bits expect, bound)
-//   k_trace<closest | query>   closest hit, or the bounded query with bound = tmax                 (trace_rays, tirt_render.hip)
+//   k_trace<closest | query>   closest hit, or the bounded query with bound = tmax                 (trace_rays, tirt_trace.hip)
 //   k_query_resolve_closest    t, prim and optionally the 13-float record of tirt_trace_closest
 //   k_query_resolve_occluded   one byte per ray: t < INF_VALUE && t < tmax
 //
@@ -15,7 +15,7 @@
 // culls nothing nearer than 1.01 tmax and so ends with the reference's closest hit whenever that is below tmax, and with a hit at or beyond
 // tmax (or a miss) otherwise.  Rays from far away (no culling), the exhaustive walk and tmax <= 0 / NaN (no bound) end with the full closest
 // hit.  A miss leaves t = INF_VALUE (1e6, the reference's value), which is why the test is not a bare t < tmax.
-#include "tirt_internal.h"
+#include "tirt_trace.h"
 
 namespace tirt {
 

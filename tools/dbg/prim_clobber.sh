@@ -59,8 +59,8 @@ git -C $R show d3df674^:include/tirt.h > $T/old/include/tirt.h
 analyse $T/old.s
 echo "== today's source with the reload line removed =="
 mkdir -p $T/new/ti_raytrace_amd/csrc $T/new/include
-cp $R/ti_raytrace_amd/csrc/*.h $R/ti_raytrace_amd/csrc/tirt_render.hip $T/new/ti_raytrace_amd/csrc/; cp $R/include/tirt.h $T/new/include/
+cp $R/ti_raytrace_amd/csrc/*.h $R/ti_raytrace_amd/csrc/tirt_trace.hip $T/new/ti_raytrace_amd/csrc/; cp $R/include/tirt.h $T/new/include/
 grep -v "prim = (int)b.compact\[(size_t)leaf \* CPN_VEC + 1\];" $R/ti_raytrace_amd/csrc/tirt_internal.h > $T/new/ti_raytrace_amd/csrc/tirt_internal.h
-(cd $T/new/ti_raytrace_amd/csrc && /opt/rocm/bin/hipcc $FLAGS -o $T/new.s tirt_render.hip 2>/dev/null)
+(cd $T/new/ti_raytrace_amd/csrc && /opt/rocm/bin/hipcc $FLAGS -o $T/new.s tirt_trace.hip 2>/dev/null)
 analyse $T/new.s
 rm -rf $T

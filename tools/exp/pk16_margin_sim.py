@@ -1,7 +1,7 @@
 """Round 6, VERDICT item 1 (b): what a WIDER conservative margin costs in node visits (CPU only).
 A packed-fp16 box test (t = h * gA + gB for two children at once in v_pk_fma_f16) has 11 bits of mantissa: gB = (grid_min - o) / d rounded to fp16 is off by
 up to |grid_min - o| * 2^-11 in POSITION (<= 4.9e-4 of the root box's extent for an origin inside it), h * gA by another |h * cell| * 2^-12 (<= 1.2e-4), the rounding
-of the FMA's result by |t * d| * 2^-12 -- together ~8e-4 extents per plane against the 0.25 cells = 4.2e-6 extents of the fp32 test (tirt_render.hip, TR_GRID_AXIS).
+of the FMA's result by |t * d| * 2^-12 -- together ~8e-4 extents per plane against the 0.25 cells = 4.2e-6 extents of the fp32 test (tirt_trace.hip, TR_GRID_AXIS).
 The 4-wide SAH tree of tools/exp/sah_build.c walked as k_trace walks it (wide_sim.c: near to far, distance culled), every child box grown by the margin.
    python tools/exp/pk16_margin_sim.py [synthetic|veach|teapot]"""
 import ctypes as C, os, subprocess, sys

@@ -1,7 +1,8 @@
 """Instruction counts per kernel of a translation unit's gfx950 ISA (hipcc -S --cuda-device-only): VALU / SALU / VMEM / LDS / total, VGPRs, SGPRs, scratch,
 the lane moves of SGPR spills (v_writelane + v_readlane), square roots (v_sqrt_*) and divisions (v_div_fixup_*).  Every instantiation of a kernel
 template is listed under its own demangled name (k_shade<32u, 5>, k_trace<0, false, 2>, ...).
-   python tools/isa_stats.py ti_raytrace_amd/csrc/tirt_render.hip [kernel-name-substring ...]   (prints one line per kernel; used to show that a refactoring left the ISA alone)"""
+   python tools/isa_stats.py ti_raytrace_amd/csrc/tirt_trace.hip [kernel-name-substring ...]    (k_trace; tirt_render.hip for the shading kernels)
+prints one line per kernel; used to show that a refactoring left the ISA alone."""
 import hashlib, re, subprocess, sys, os, tempfile
 src = sys.argv[1]; keys = sys.argv[2:]
 d = os.path.dirname(os.path.abspath(src))

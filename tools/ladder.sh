@@ -1,7 +1,7 @@
 # Bound ladder for k_trace: what limits the traversal kernel is asked of the kernel itself.
 #   bash tools/ladder.sh <tag>
 # Builds variants of libtirt.so HERE (cross-compile) -- TR_PAD=k identity VALU instructions per node visit (behind the loads / behind
-# the sort), TR_PADG=k dummy node-record gathers per visit (tirt_render.hip, TR_LADDER_PADS) -- and times each on the GPU box in ONE
+# the sort), TR_PADG=k dummy node-record gathers per visit (tirt_trace.hip, TR_LADDER_PADS) -- and times each on the GPU box in ONE
 # gpurun call: the headline job (4 overlapped batches) and the same job on one render lane (launches back to back: ms/step = the
 # sum of the kernels' durations).  Output: gpurun_out/<tag>_ladder.log; the table goes to profiles/.
 set -e
