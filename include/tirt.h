@@ -257,7 +257,7 @@ int tirt_shade_features_host(const float *material, int nm, const int32_t *primi
 /* Importance sampling of the environment (csrc/tirt_envsample.hip, the table; csrc/tirt_device.h, env_sample / env_pdf; csrc/tirt_render.hip, shade_path under
  * SF_ENV_SAMPLE; no reference counterpart: integrator/PT_RGB.py:127-132 reads the environment only where a BSDF-sampled ray misses).  Opt-in, PT_RGB only: with the
  * switch off every kernel keeps its code and its bits; tirt_pt_spec_render, both BDPT integrators, the feature buffers, moments, denoisers and the temporal
- * history never read the switch.  Limit: the environment stays 8 bits per channel times env_power; a float / RGBE environment is out of scope.
+ * history never read the switch.  The image is 8 bits per channel (tirt_env_upload) or RGBE8 (tirt_env_upload_hdr, "HDR environment" below).
  * All f32 below: one rounding per operation, no contraction, in the order written (tests/env_sampling_expected.py restates it; the device gives its bits).
  * 1. Cells and weights.  One cell per texel index (i, j), i < w, j < h: the lookup coordinates with floor(min(w - 1, max(0, tx * w))) = i and the same for
  *      (ty, h, j) -- the cell texture2D's lx, ly name; cell w - 1 / h - 1 takes what the clamp folds into it.
@@ -303,6 +303,46 @@ int tirt_kat_env_pdf(tirt_ctx *ctx, const float *in, int in_stride, float *out, 
 int tirt_shade_features_host_env(const float *material, int nm, const int32_t *primitive, int n, const float *shape, int ns,
                                  const int32_t *light, int light_count, const int32_t *env, int env_w, int env_h, float env_power,
                                  int env_sampling, uint32_t *out);
+
+/* HDR environment (csrc/tirt_device.h, hdr_decode / texture2d_hdr / env_lookup / env_cell_q_hdr; no reference counterpart: texture/Texture.py packs 8 bits per channel).
+ * PT_RGB only, as the 8-bit image: tirt_pt_spec_render and both BDPT integrators do not light from the image at all, so they neither read nor refuse it.
+ * A scene with an 8-bit environment launches the kernels it launched before this format existed; they are compiled without bit 2048 and keep their code.
+ * Texel format: RGBE8 in the word the environment already uses, w x h packed i32 at index x*h + y, y = 0 the bottom row: (E << 24) | (R << 16) | (G << 8) | B.
+ *   channel = (float)mantissa * 2^(E - 136)  -- one exact integer-to-float conversion and one exact scaling (ldexp).  Linear radiance: no srgb_to_lrgb is applied.
+ *   f32 denormals are kept as they come (E <= 17 reaches them): the library is built with -fno-fast-math and without denormal flushing (float_denorm_mode_32 = 3).
+ *   E == 0 is allowed only with R = G = B = 0, which is black; tirt_env_upload_hdr refuses every other E == 0 texel (TIRT_ERR_ARG), so the decode above needs no
+ *   special case: the all-zero word gives 0 * 2^-136 = 0.  The largest value is 255 * 2^119 < FLT_MAX: a texel is never Inf or NaN.
+ *   (Not float3 / float4 texels: a tap stays one 4-byte gather, the allocation, env_table_offset and the kernels' SceneView argument stay what they are; and a
+ *   Radiance .hdr file stores exactly these four bytes.)
+ * Lookup L(tx, ty), all f32, one rounding per operation, in the order written (tests/env_hdr_expected.py restates it; the device gives its bits) -- texture2D on decoded texels:
+ *   x = min(w - 1, max(0, tx * w)), y = min(h - 1, max(0, ty * h))   (max(a, b) = a > b ? a : b, min(a, b) = a < b ? a : b: a NaN coordinate stays NaN);
+ *   lx = floor(x), ly = floor(y);  wlr = x - floor(x), wbt = y - floor(y);  texel(fx, fy) = decode(img[clamp((int)fx, 0, w - 1) * h + clamp((int)fy, 0, h - 1)]);
+ *   lt = texel(lx, ly), rt = texel(lx + 1, ly), lb = texel(lx, ly + 1), rb = texel(lx + 1, ly + 1);  mix(a, b, t) = a * (1 - t) + b * t;
+ *   L = mix(mix(lt, rt, wlr), mix(lb, rb, wlr), wbt).
+ *   It takes the place of srgb_to_lrgb(texture2D(env, tx, ty)) in the miss branch -- radiance += (L * throughput) * env_power, times the MIS weight w last under bit 1024 --
+ *   and in the environment sample of "Importance sampling of the environment", step 5: c = (L * env_power) * w, then the factors in the order given there.
+ * Sampling table: steps 2..5 are unchanged; step 1 becomes
+ *   lum(x, y) = ((c.r + c.g) + c.b) / 3.0f of c = decode(texel(min(x, w - 1), min(y, h - 1)));  m and el as there;  weight = m * cos(el);
+ *   E_max = the largest exponent byte among the texels with a mantissa that is not 0 (found by the host at upload, passed to the kernel);
+ *   s = rintf(ldexpf(weight, 152 - E_max));  q(i, j) = s > 0 ? (s < 2^24 ? (uint32) s : 2^24) : 0.   Every channel is below 2^(E_max - 128), so q <= 2^24 and every bound of
+ *   steps 2..4 holds; the clamp only acts where a sum of channels overflowed to +Inf, which needs E_max >= 254.  The scale is applied by ldexp, never as a float factor
+ *   (2^(152 - E_max) is no f32 for E_max < 25).  Adding a constant to the exponent byte of every texel with a mantissa gives the same table to the bit.
+ * Feature word: bit 2048 (SF_ENV_HDR) = the uploaded image is RGBE8 and the environment is lit (bit 2: env_power != 0 or a texel whose low 24 bits are not 0 -- the
+ *   8-bit rule).  Reported by tirt_shade_features.  tirt_pt_rgb_render then launches k_shade<127 | 2048>, or k_shade<511 | 2048> where the word has bit 128 or 256; with
+ *   bit 1024 as well k_shade<127 | 1024 | 2048> or k_shade<511 | 1024 | 2048>.  "shade_specialize" does not matter to them: a lit environment means the generic kernel.
+ * tirt_env_upload_hdr: as tirt_env_upload (waits for work in flight, refreshes the feature word, rebuilds or drops the sampling table) and sets the format; the
+ *   E == 0 rule is checked first, without a context, and the message names the first offending texel's index.  tirt_env_upload sets the format back to 8 bits.
+ * tirt_env_format: out = (format: 0 8-bit, 1 RGBE8;  E_max, 0 for format 0 or an image without a mantissa).
+ * tirt_kat_env_lookup: in 2 words (tx, ty), out 3: the linear colour the miss branch adds before env_power, in the context's current format -- L above, or
+ *   srgb_to_lrgb(texture2D(env, tx, ty)) for an 8-bit image.  One launch, row r on thread r.  TIRT_ERR_ARG: strides too small, no image.
+ * tirt_shade_features_host_env_hdr: tirt_shade_features_host_env with the format as an input.  env_format 0: that function.  env_format 1: the image is required
+ *   (NULL, w < 1, h < 1 and an E == 0 texel with a mantissa are TIRT_ERR_ARG); bit 2048 where bit 2 is set, bit 1024 by the table rule above. */
+int tirt_env_upload_hdr(tirt_ctx *ctx, const int32_t *rgbe_packed, int w, int h, float power);
+int tirt_env_format(tirt_ctx *ctx, int32_t out[2]);
+int tirt_kat_env_lookup(tirt_ctx *ctx, const float *in, int in_stride, float *out, int out_stride, int n);
+int tirt_shade_features_host_env_hdr(const float *material, int nm, const int32_t *primitive, int n, const float *shape, int ns,
+                                     const int32_t *light, int light_count, const int32_t *env, int env_w, int env_h, float env_power,
+                                     int env_sampling, int env_format, uint32_t *out);
 
 /* LBvh.Bvh.setup_data_gpu (accel/LBvh.py:192-226): Morton codes, stable radix sort, Karras
  * topology, leaf boxes, bottom-up refit, DFS flatten -- all on device. */
@@ -796,11 +836,12 @@ int tirt_kat_shade_tables(tirt_ctx *ctx, int which, const float *in, float *out,
  * tests/test_gpu_shade_step.py against the CPU oracle's orc_kat_shade_step.  One launch, row i on thread i.
  * feat: the feature word of the instantiation -- 32 (sphere lights), 4 (mesh lights), 127 (generic), 255 (generic + albedo textures) or 511 (+ roughness, metallic and normal maps), the ones a render picks from (tirt_shade_features).
  *   With environment importance sampling: 127 | 1024 and 511 | 1024 (they need the context's table: bit 1024 of tirt_shade_features).
+ *   With an RGBE8 environment: 127 | 2048, 511 | 2048, 127 | 1024 | 2048 and 511 | 1024 | 2048; feat carries bit 2048 exactly when tirt_shade_features does (TIRT_ERR_ARG otherwise).
  * in, 23 words per row (integers as their bit patterns): seed, pixel, frame, bounce, last_bounce; origin3, direction3; t, u, v, prim (t >= 1e6: a miss, prim unused);
  *   throughout3, radiance3, brdf_pdf, perfect_spec.  NaN and infinity in the ray, the barycentrics and the state are data.
  * out, 28 words per row: radiance3, shaded, want_next, next_o3, next_d3, next_thr3, next_pdf, next_spec, want_shadow, sh_o3, sh_d3, sh_c3, sh_expect, sh_dist -- what
  *   k_shade writes to the path state and the shadow-ray queue; a field the step does not set is 0, sh_expect -2.  sh_c counts if the shadow ray finds sh_expect first.
- * TIRT_ERR_ARG before anything is launched: in_stride < 23, out_stride < 28, a feat that is not one of the five (both also with a NULL ctx), a feat that does not
+ * TIRT_ERR_ARG before anything is launched: in_stride < 23, out_stride < 28, a feat that is not one of those listed (both also with a NULL ctx), a feat that does not
  * cover the context's feature word, feat 255 or 511 on a context without uploaded textures, a hit row (t < 1e6) whose prim is outside [0, n_prims), a pixel outside [0, 2^31 - 1). */
 int tirt_kat_shade_step(tirt_ctx *ctx, uint32_t feat, const float *in, int in_stride, float *out, int out_stride, int n);
 

@@ -197,6 +197,16 @@ class Scene:
             self.env.load_array(arr)
         self.env_power = env_power
 
+    def add_env_hdr(self, source, env_power):
+        """No reference counterpart (include/tirt.h, "HDR environment"): an environment of linear radiance beyond 8 bits per channel, PT_RGB only.  ``source`` is the
+        path of a Radiance ``.hdr`` file (``Texture.load_hdr``) or an ``(h, w, 3)`` float32 / float64 array with row 0 the top of the image
+        (``Texture.load_array_float``, which states how it rounds).  ``add_env`` stays what it is: 8-bit images."""
+        if isinstance(source, (str, bytes, os.PathLike)):
+            self.env.load_hdr(source)
+        else:
+            self.env.load_array_float(source)
+        self.env_power = env_power
+
     def _add_opacity_texture(self, kd_path, d_path, diffuse):
         """The alpha cut-out texture of an MTL material with a ``map_d`` statement (include/tirt.h, "Alpha cut-outs").
         ``map_d`` names the ``map_Kd`` file: that image with its own alpha channel.  Another file of the same size: its alpha channel -- its grey

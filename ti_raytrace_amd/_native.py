@@ -85,6 +85,11 @@ SHADE_INSTANTIATION_MAPS = SF_ALL | SF_TEXTURE | SF_TEXTURE_PARAM   # k_shade's 
 SF_CUTOUT = 512                                                     # a cut-out triangle exists (tirt_texture_cutout); reported only: no instantiation of k_shade depends on it
 SF_ENV_SAMPLE = 1024                                                # environment importance sampling on, environment lit, table built (tirt_env_sampling); not part of SF_ALL
 SHADE_INSTANTIATIONS_ENV = (SF_ALL | SF_ENV_SAMPLE, SHADE_INSTANTIATION_MAPS | SF_ENV_SAMPLE)       # k_shade's twins with the environment's light sample
+SF_ENV_HDR = 2048                                                   # the uploaded environment is RGBE8 (tirt_env_upload_hdr) and lit; not part of SF_ALL
+SHADE_INSTANTIATIONS_HDR = (SF_ALL | SF_ENV_HDR, SHADE_INSTANTIATION_MAPS | SF_ENV_HDR,             # k_shade's twins that decode RGBE8 texels, without and with the light sample
+                            SF_ALL | SF_ENV_SAMPLE | SF_ENV_HDR, SHADE_INSTANTIATION_MAPS | SF_ENV_SAMPLE | SF_ENV_HDR)
+ENV_FORMAT_RGB8, ENV_FORMAT_RGBE8 = 0, 1                            # tirt_env_format, Texture.format
+KAT_ENV_LOOKUP_IN, KAT_ENV_LOOKUP_OUT = 2, 3                        # words per row of tirt_kat_env_lookup
 KAT_ENV_SAMPLE_IN, KAT_ENV_SAMPLE_OUT = 2, 10                       # words per row of tirt_kat_env_sample
 KAT_ENV_PDF_IN, KAT_ENV_PDF_OUT = 3, 5                              # words per row of tirt_kat_env_pdf
 KAT_ALPHA_IN, KAT_ALPHA_OUT = 3, 2                                  # words per row of tirt_kat_texture_alpha
@@ -124,6 +129,11 @@ SIGNATURES = {
     "tirt_env_table_download": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
     "tirt_kat_env_sample": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
     "tirt_kat_env_pdf": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
+    "tirt_env_upload_hdr": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_float]),
+    "tirt_env_format": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
+    "tirt_kat_env_lookup": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
+    "tirt_shade_features_host_env_hdr": (C.c_int, [_f32p, C.c_int, _i32p, C.c_int, _f32p, C.c_int, _i32p, C.c_int, _vp, C.c_int, C.c_int, C.c_float,
+                                                   C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
     "tirt_lbvh_build": (C.c_int, [_vp]),
     "tirt_lbvh_download": (C.c_int, [_vp, _vp, _vp, _vp]),
     "tirt_traversal_tree_download": (C.c_int, [_vp, _vp]),
@@ -423,6 +433,20 @@ class Context:
     def env_upload(self, packed, power):
         packed = np.ascontiguousarray(packed, np.int32)
         check(lib().tirt_env_upload(self.handle, packed.reshape(-1), packed.shape[0], packed.shape[1], float(power)))
+
+    def env_upload_hdr(self, packed, power):
+        """include/tirt.h, tirt_env_upload_hdr: packed [w, h] int32 RGBE8 texels (Texture.np_img of load_hdr / load_array_float)"""
+        env_upload_hdr(self.handle, packed, power)
+
+    def env_format(self):
+        """include/tirt.h, tirt_env_format: (format 0 8-bit / 1 RGBE8, E_max of the sampling table's scale)"""
+        out = (C.c_int32 * 2)()
+        check(lib().tirt_env_format(self.handle, out))
+        return int(out[0]), int(out[1])
+
+    def kat_env_lookup(self, rows, out_stride=KAT_ENV_LOOKUP_OUT):
+        """include/tirt.h, tirt_kat_env_lookup: rows (n, >= 2) float32 (tx, ty) -> (n, out_stride) float32: the environment's linear colour before env_power"""
+        return _kat_rows("tirt_kat_env_lookup", self.handle, (), rows, out_stride)
 
     def texture_upload(self, textures):
         """include/tirt.h, tirt_texture_upload: `textures` is a sequence of (packed [w, h] int32 as Texture.np_img, wrap 0 clamp / 1 repeat); empty: remove all"""
@@ -917,6 +941,27 @@ def shade_features_host_env(material, primitive, shape, light, light_count, env=
                                              light.reshape(-1), int(light_count), _ptr(env), 0 if env is None else env.shape[0], 0 if env is None else env.shape[1],
                                              float(env_power), 1 if env_sampling else 0, C.byref(out)))
     return int(out.value)
+
+
+def shade_features_host_env_hdr(material, primitive, shape, light, light_count, env=None, env_power=0.0, env_sampling=False, env_format=0, dims=None):
+    """shade_features_host_env with the texel format as an input (0 8-bit, 1 RGBE8): bits 2048 and 1024 where a context would report them.
+    dims: (w, h) passed in place of env's shape (the refusals of w, h < 1)."""
+    material = np.ascontiguousarray(material, np.float32); primitive = np.ascontiguousarray(primitive, np.int32)
+    shape = np.ascontiguousarray(shape, np.float32); light = np.ascontiguousarray(light, np.int32)
+    env = None if env is None else np.ascontiguousarray(env, np.int32)
+    w, h = dims if dims is not None else ((0, 0) if env is None else env.shape)
+    out = C.c_uint32(0)
+    check(lib().tirt_shade_features_host_env_hdr(material.reshape(-1), material.shape[0], primitive.reshape(-1), primitive.shape[0], shape.reshape(-1), shape.shape[0],
+                                                 light.reshape(-1), int(light_count), _ptr(env), int(w), int(h),
+                                                 float(env_power), 1 if env_sampling else 0, int(env_format), C.byref(out)))
+    return int(out.value)
+
+
+def env_upload_hdr(handle, packed, power, dims=None):
+    """tirt_env_upload_hdr on a raw context handle (None: only the refusals that need no context can be reached).  dims: (w, h) in place of packed's shape."""
+    packed = None if packed is None else np.ascontiguousarray(packed, np.int32)
+    w, h = dims if dims is not None else ((0, 0) if packed is None else packed.shape)
+    check(lib().tirt_env_upload_hdr(handle, _ptr(packed), int(w), int(h), float(power)))
 
 
 def env_sampling(handle, on, share=0.5):

@@ -576,7 +576,7 @@ int tirt_scene_upload(tirt_ctx *c, const float *vertex, int nv, const int32_t *p
     if (!c->env.p) {        // default: 1x1 black (Scene.py:295-296 loads image/black.png)
         int32_t z = 0;
         if (upload(c->env, &z, sizeof(int32_t), st)) return TIRT_ERR_HIP;
-        c->env_w = 1; c->env_h = 1; c->env_power = 0.0f; c->env_lit = false;
+        c->env_w = 1; c->env_h = 1; c->env_power = 0.0f; c->env_lit = false; c->env_format = 0; c->env_emax = 0;
     }
     c->h_material.assign(material, material + (size_t)MAT_VEC * nm);
     light_kinds(primitive, shape, light, light_count, c->h_light_kind);
@@ -608,10 +608,36 @@ int tirt_env_upload(tirt_ctx *c, const int32_t *rgb_packed, int w, int h, float 
     TIRT_REQUIRE(rgb_packed && w >= 1 && h >= 1, "tirt_env_upload: bad image");
     if (upload(c->env, rgb_packed, sizeof(int32_t) * (size_t)w * h, c->stream)) return TIRT_ERR_HIP;
     c->env_w = w; c->env_h = h; c->env_power = power;
+    c->env_format = 0; c->env_emax = 0;
     c->env_lit = env_is_lit(rgb_packed, (size_t)w * h, power);
     refresh_shade_features(c);
     TIRT_HIP(hipStreamSynchronize(c->stream));
     return env_table_refresh(c);               // (tirt_env_sampling on: the table of the new image, or none)
+}
+
+// the same for RGBE8 texels (include/tirt.h, "HDR environment"): what needs no context first
+int tirt_env_upload_hdr(tirt_ctx *c, const int32_t *rgbe_packed, int w, int h, float power)
+{
+    TIRT_REQUIRE(rgbe_packed && w >= 1 && h >= 1, "tirt_env_upload_hdr: bad image");
+    int e_max = 0;
+    if (int rc = env_hdr_check("tirt_env_upload_hdr", rgbe_packed, w, h, &e_max)) return rc;
+    CTX(c);
+    if (sync_all(c)) return TIRT_ERR_HIP;      // scene data must not change under batches still in flight
+    if (upload(c->env, rgbe_packed, sizeof(int32_t) * (size_t)w * h, c->stream)) return TIRT_ERR_HIP;
+    c->env_w = w; c->env_h = h; c->env_power = power;
+    c->env_format = 1; c->env_emax = e_max;
+    c->env_lit = env_is_lit(rgbe_packed, (size_t)w * h, power);      // the same rule: power != 0 or a mantissa that is not 0
+    refresh_shade_features(c);
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    return env_table_refresh(c);
+}
+
+int tirt_env_format(tirt_ctx *c, int32_t out[2])
+{
+    TIRT_REQUIRE(c, "null context");
+    TIRT_REQUIRE(out, "tirt_env_format: null pointer");
+    out[0] = c->env_format; out[1] = c->env_emax;
+    return TIRT_OK;
 }
 
 int tirt_env_sampling(tirt_ctx *c, int on, float share)
@@ -692,7 +718,7 @@ int tirt_shade_features(tirt_ctx *c, uint32_t *out)
 {
     TIRT_REQUIRE(c, "null context");
     TIRT_REQUIRE(out, "tirt_shade_features: null pointer");
-    out[0] = c->shade_features | (c->has_cutout ? (unsigned)SF_CUTOUT : 0u) | (env_sample_active(c) ? (unsigned)SF_ENV_SAMPLE : 0u);
+    out[0] = c->shade_features | (c->has_cutout ? (unsigned)SF_CUTOUT : 0u) | (env_sample_active(c) ? (unsigned)SF_ENV_SAMPLE : 0u) | (env_hdr_active(c) ? (unsigned)SF_ENV_HDR : 0u);
     out[1] = c->shade_specialize ? 1u : 0u;
     return TIRT_OK;
 }
@@ -719,6 +745,23 @@ int tirt_shade_features_host_env(const float *material, int nm, const int32_t *p
 {
     if (int rc = tirt_shade_features_host(material, nm, primitive, n, shape, ns, light, light_count, env, env_w, env_h, env_power, out)) return rc;
     if (env_sampling && (*out & SF_ENV) && env_table_exists_host(env, env_w, env_h, env_power)) *out |= SF_ENV_SAMPLE;
+    return TIRT_OK;
+}
+
+// the same with the texel format as an input: env_format 0 is tirt_shade_features_host_env; env_format 1 reads RGBE8 texels -- the image is then required and
+// checked as tirt_env_upload_hdr checks it --, sets bit 2048 where the environment is lit and bit 1024 by the RGBE8 table's rule
+int tirt_shade_features_host_env_hdr(const float *material, int nm, const int32_t *primitive, int n, const float *shape, int ns,
+                                     const int32_t *light, int light_count, const int32_t *env, int env_w, int env_h, float env_power, int env_sampling, int env_format, uint32_t *out)
+{
+    TIRT_REQUIRE(env_format == 0 || env_format == 1, "tirt_shade_features_host_env_hdr: env_format is 0 (8 bits per channel) or 1 (RGBE8)");
+    if (env_format == 0)
+        return tirt_shade_features_host_env(material, nm, primitive, n, shape, ns, light, light_count, env, env_w, env_h, env_power, env_sampling, out);
+    TIRT_REQUIRE(env && env_w >= 1 && env_h >= 1, "tirt_shade_features_host_env_hdr: bad image");
+    int e_max = 0;
+    if (int rc = env_hdr_check("tirt_shade_features_host_env_hdr", env, env_w, env_h, &e_max)) return rc;
+    if (int rc = tirt_shade_features_host(material, nm, primitive, n, shape, ns, light, light_count, env, env_w, env_h, env_power, out)) return rc;
+    if (*out & SF_ENV) *out |= SF_ENV_HDR;
+    if (env_sampling && (*out & SF_ENV) && env_table_exists_host_hdr(env, env_w, env_h, env_power, e_max)) *out |= SF_ENV_SAMPLE;
     return TIRT_OK;
 }
 

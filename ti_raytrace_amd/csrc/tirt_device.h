@@ -88,6 +88,8 @@ enum : unsigned {
     SF_TEXTURE_PARAM = 256u,  // a material row that is not an emitter's names an uploaded roughness, metallic or normal texture (words 7..9; implies uvs in the shading records as 128 does)
     SF_ENV_SAMPLE = 1024u,    // environment importance sampling is switched on (tirt_env_sampling), the environment is lit and its sampling table exists: k_shade's ENV twins.
                               // Kept beside tirt_ctx::shade_features as 512 is (k_shade_spec and BDPT never see it); reported by tirt_shade_features
+    SF_ENV_HDR = 2048u,       // the uploaded environment is RGBE8 (tirt_env_upload_hdr) and lit (bit 2): k_shade's HDR twins decode its texels.  Derived (env_hdr_active), never stored in
+                              // the context's word, reported by tirt_shade_features; the 8-bit kernels are compiled without it and keep their code
     SF_LIGHT_KINDS = SF_LIGHT_TRI | SF_LIGHT_SPOT_LASER | SF_LIGHT_SPHERE | SF_LIGHT_OTHER
 };
 
@@ -679,6 +681,43 @@ TD v3 texture2d(const int *img, int w, int h, float u, float v)
     return mix3(mix3(lt, rt, wlr), mix3(lb, rb, wlr), wbt);
 }
 
+// ---- HDR environment (include/tirt.h, "HDR environment"; no reference counterpart): RGBE8 texels (E << 24) | (R << 16) | (G << 8) | B at the index of an 8-bit image.
+// A channel is mantissa * 2^(E - 136), linear radiance: one exact conversion and one exact scaling (v_ldexp_f32; f32 denormals are kept -- the library is
+// compiled with -fno-fast-math and without -fgpu-flush-denormals-to-zero, the kernels' float_denorm_mode_32 is 3).  The upload has refused E == 0 with a mantissa,
+// so an all-zero word is the only texel with E == 0 and decodes to 0 by the same expression: no special case.  Host and device (env_texel_lum_hdr runs on both).
+TM_HD void hdr_decode(int texel, float c[3])
+{
+    const unsigned t = (unsigned)texel;
+    const int e = (int)(t >> 24) - 136;
+    c[0] = __builtin_ldexpf((float)((t >> 16) & 255u), e); c[1] = __builtin_ldexpf((float)((t >> 8) & 255u), e); c[2] = __builtin_ldexpf((float)(t & 255u), e);
+}
+TD v3 tex_sample_hdr(const int *img, int w, int h, float fx, float fy)
+{
+    int x = (int)fx, y = (int)fy;
+    x = x < 0 ? 0 : (x > w - 1 ? w - 1 : x);
+    y = y < 0 ? 0 : (y > h - 1 ? h - 1 : y);
+    float c[3]; hdr_decode(img[(size_t)x * h + y], c);
+    return V(c[0], c[1], c[2]);
+}
+// texture2d on decoded texels: the same clamp, lx / ly / wlr / wbt, four taps and mix order
+TD v3 texture2d_hdr(const int *img, int w, int h, float u, float v)
+{
+    float x = clampf(u * (float)w, 0.0f, (float)w - 1.0f);
+    float y = clampf(v * (float)h, 0.0f, (float)h - 1.0f);
+    float lx = tm_floor(x), ly = tm_floor(y);
+    float wbt = y - tm_floor(y), wlr = x - tm_floor(x);
+    v3 lt = tex_sample_hdr(img, w, h, lx, ly), rt = tex_sample_hdr(img, w, h, lx + 1.0f, ly);
+    v3 lb = tex_sample_hdr(img, w, h, lx, ly + 1.0f), rb = tex_sample_hdr(img, w, h, lx + 1.0f, ly + 1.0f);
+    return mix3(mix3(lt, rt, wlr), mix3(lb, rb, wlr), wbt);
+}
+// the linear colour of the environment at lookup coordinates (tx, ty), before env_power: what shade_path's miss branch and its environment sample read
+template <bool HDR>
+TD v3 env_lookup(const int *img, int w, int h, float tx, float ty)
+{
+    if constexpr (HDR) return texture2d_hdr(img, w, h, tx, ty);
+    else return srgb_to_lrgb(texture2d(img, w, h, tx, ty));
+}
+
 // ---- albedo textures (include/tirt.h, tirt_texture_upload; no reference counterpart: PT_RGB.py:86 takes the material colour) ----
 // The texture a material row names: (int)row[1] - 1 where 1 <= (int)row[1], else -1.  The host has refused every row of a material that is not an emitter
 // whose slot exceeds the number of uploaded textures, so a slot >= 1 found on the device names a table entry (no count is passed to any kernel).
@@ -821,6 +860,23 @@ TM_HD unsigned env_cell_q(const int *img, int w, int h, int i, int j)
     const float wgt = m * tm_cos(el);
     const float s = __builtin_rintf(wgt * 16777216.0f);
     return s > 0.0f ? (unsigned)s : 0u;
+}
+// the same for an RGBE8 image: the level of the decoded texels, the same cell mean and cos(el), and the scale 2^(152 - e_max) in 2^24's place, applied by an exact ldexp
+// (e_max: the largest exponent byte among texels with a mantissa, so every channel is below 2^(e_max - 128) and q <= 2^24; sums that overflow to +Inf -- possible
+// only from e_max = 254 on -- give 2^24 by the clamp).  Adding a constant to every such texel's exponent byte scales m and the inverse scale by exact powers of two: the same q.
+TM_HD float env_texel_lum_hdr(const int *img, int w, int h, int x, int y)
+{
+    x = x > w - 1 ? w - 1 : x; y = y > h - 1 ? h - 1 : y;
+    float l[3]; hdr_decode(img[(size_t)x * h + y], l);
+    return ((l[0] + l[1]) + l[2]) / 3.0f;
+}
+TM_HD unsigned env_cell_q_hdr(const int *img, int w, int h, int i, int j, int e_max)
+{
+    const float m = ((env_texel_lum_hdr(img, w, h, i, j) + env_texel_lum_hdr(img, w, h, i + 1, j)) + (env_texel_lum_hdr(img, w, h, i, j + 1) + env_texel_lum_hdr(img, w, h, i + 1, j + 1))) * 0.25f;
+    const float el = (((float)j + 0.5f) / (float)h - 0.5f) * PI_SCENE;
+    const float wgt = m * tm_cos(el);
+    const float s = __builtin_rintf(__builtin_ldexpf(wgt, 152 - e_max));
+    return s > 0.0f ? (s < 16777216.0f ? (unsigned)s : 16777216u) : 0u;
 }
 struct EnvTable { const env_u64 *marg, *rows; env_u64 total; float share; };
 TD EnvTable env_table(const SceneView &sc)

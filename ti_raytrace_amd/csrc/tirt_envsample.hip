@@ -11,7 +11,7 @@
 // Where it lives: behind the texels, in the allocation SceneView::env points to (env_table_offset, tirt_device.h).  SceneView is an argument of every shading
 // kernel; a new member would move the argument block of the kernels that do not sample, and with it their code.
 //
-//   k_env_cells      q of every cell, as the unsummed row entries                         one thread per cell
+//   k_env_cells      q of every cell, as the unsummed row entries                         one thread per cell   (k_env_cells_hdr: the same of an RGBE8 image)
 //   k_env_row_scan   inclusive sum of a row in place, its total into the marginal          one 256-thread block per row: wave scans + a carry per 256-entry chunk
 //   k_env_marg_scan  inclusive sum of the marginal in place, total and share into the head one block
 #include "tirt_internal.h"
@@ -25,6 +25,16 @@ __global__ __launch_bounds__(256) void k_env_cells(const int *img, int w, int h,
     if (c >= (size_t)w * h) return;
     const int j = (int)(c / (size_t)w), i = (int)(c - (size_t)j * w);
     rows[c] = (env_u64)env_cell_q(img, w, h, i, j);
+}
+
+// an RGBE8 image (include/tirt.h, "HDR environment"): the level of the decoded texels, scaled by 2^(152 - e_max).  A kernel of its own: k_env_cells keeps its
+// argument block and its code
+__global__ __launch_bounds__(256) void k_env_cells_hdr(const int *img, int w, int h, env_u64 *rows, int e_max)
+{
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= (size_t)w * h) return;
+    const int j = (int)(c / (size_t)w), i = (int)(c - (size_t)j * w);
+    rows[c] = (env_u64)env_cell_q_hdr(img, w, h, i, j, e_max);
 }
 
 // inclusive sum over the 256 threads of a block; every thread of the block calls it
@@ -84,7 +94,8 @@ int env_table_refresh(tirt_ctx *c)
     }
     env_u64 *head = (env_u64 *)((char *)c->env.p + off), *marg = head + 2, *rows = marg + h;
     const size_t cells = (size_t)w * h;
-    hipLaunchKernelGGL(k_env_cells, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, c->env.as<int>(), w, h, rows);
+    if (c->env_format == 1) hipLaunchKernelGGL(k_env_cells_hdr, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, c->env.as<int>(), w, h, rows, c->env_emax);
+    else hipLaunchKernelGGL(k_env_cells, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, c->env.as<int>(), w, h, rows);
     hipLaunchKernelGGL(k_env_scan, dim3((unsigned)h), dim3(256), 0, c->stream, rows, w, marg, (size_t)1);
     hipLaunchKernelGGL(k_env_scan, dim3(1), dim3(256), 0, c->stream, marg, h, (env_u64 *)nullptr, (size_t)0);
     hipLaunchKernelGGL(k_env_head, dim3(1), dim3(1), 0, c->stream, head, marg, h, c->env_share);
@@ -111,6 +122,27 @@ bool env_table_exists_host(const int32_t *env, int w, int h, float power)
 {
     if (!env || power == 0.0f || !env_sample_dims_ok(w, h)) return false;
     for (int j = 0; j < h; j++) for (int i = 0; i < w; i++) if (env_cell_q(env, w, h, i, j) > 0u) return true;
+    return false;
+}
+
+int env_hdr_check(const char *fn, const int32_t *rgbe, int w, int h, int *e_max)
+{
+    int top = 0;
+    const size_t count = (size_t)w * h;
+    for (size_t k = 0; k < count; k++) {
+        const unsigned t = (unsigned)rgbe[k];
+        const int e = (int)(t >> 24);
+        TIRT_REQUIRE(e != 0 || (t & 0x00FFFFFFu) == 0u, std::string(fn) + ": texel " + std::to_string(k) + " has exponent byte 0 and a mantissa that is not 0 (E == 0 is black only)");
+        if ((t & 0x00FFFFFFu) != 0u && e > top) top = e;
+    }
+    *e_max = top;
+    return TIRT_OK;
+}
+
+bool env_table_exists_host_hdr(const int32_t *env, int w, int h, float power, int e_max)
+{
+    if (!env || power == 0.0f || !env_sample_dims_ok(w, h)) return false;
+    for (int j = 0; j < h; j++) for (int i = 0; i < w; i++) if (env_cell_q_hdr(env, w, h, i, j, e_max) > 0u) return true;
     return false;
 }
 
@@ -148,6 +180,27 @@ __global__ void k_kat_env(SceneView sc, int which, const float *in, int in_strid
         const EnvPdf ep = env_pdf(et, sc.env_w, sc.env_h, V(a[0], a[1], a[2]));
         o[0] = __int_as_float(ep.i); o[1] = __int_as_float(ep.j); o[2] = ep.tx; o[3] = ep.ty; o[4] = ep.pdf;
     }
+}
+
+// tirt_kat_env_lookup: env_lookup of tirt_device.h, the function shade_path's miss branch and environment sample call, in the format of the uploaded image
+__global__ void k_kat_env_lookup(SceneView sc, int hdr, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const float *a = in + (size_t)r * in_stride;
+    float *o = out + (size_t)r * out_stride;
+    const v3 e = hdr ? env_lookup<true>(sc.env, sc.env_w, sc.env_h, a[0], a[1]) : env_lookup<false>(sc.env, sc.env_w, sc.env_h, a[0], a[1]);
+    o[0] = e.x; o[1] = e.y; o[2] = e.z;
+}
+
+int kat_env_lookup(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    TIRT_REQUIRE(c->env.p && c->env_w >= 1 && c->env_h >= 1, "tirt_kat_env_lookup: no environment image (tirt_env_upload, tirt_env_upload_hdr or a scene upload)");
+    if (n == 0) return TIRT_OK;
+    if (sync_all(c)) return TIRT_ERR_HIP;
+    return kat_round_trip(c, "tirt_kat_env_lookup", {{in, kat_row_bytes(n, in_stride)}}, out, kat_row_bytes(n, out_stride), [&](const void *const *din, void *dout) {
+        hipLaunchKernelGGL(k_kat_env_lookup, dim3((n + 63) / 64), dim3(64), 0, c->stream, scene_view(c), c->env_format == 1 ? 1 : 0, (const float *)din[0], in_stride, (float *)dout, out_stride, n);
+    });
 }
 
 int kat_env(tirt_ctx *c, int which, const float *in, int in_stride, float *out, int out_stride, int n)

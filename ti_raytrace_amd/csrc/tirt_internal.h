@@ -331,6 +331,9 @@ struct tirt_ctx {
     // environment importance sampling (tirt_envsample.hip): the switch and share of tirt_env_sampling; env_tab_valid = the table stands behind the texels of `env`
     // (switch on, env_power != 0, w and h within ENV_SAMPLE_MAX_DIM, total > 0).  Bit SF_ENV_SAMPLE is derived (env_sample_active), never stored in shade_features
     int env_sample_on = 0; float env_share = 0.5f; bool env_tab_valid = false;
+    // the texel format of `env`: 0 = 8 bits per channel (tirt_env_upload), 1 = RGBE8 (tirt_env_upload_hdr); env_emax = the largest exponent byte among the RGBE8
+    // texels with a mantissa (0: none, or format 0), the scale of the sampling table.  Bit SF_ENV_HDR is derived (env_hdr_active), never stored in shade_features
+    int env_format = 0, env_emax = 0;
     int shade_specialize = 1;                      // option "shade_specialize": 0 = the generic kernel for every scene (A/B and parity switch)
 
     // LBVH (accel/LBvh.py fields)
@@ -554,6 +557,11 @@ int env_table_download(tirt_ctx *c, uint32_t *q, uint64_t *row_sums, uint64_t *m
 int kat_env(tirt_ctx *c, int which, const float *in, int in_stride, float *out, int out_stride, int n);      // which: 0 sample, 1 pdf
 int env_table_set_share(tirt_ctx *c);          // only the share has changed: rewrites the table's head
 bool env_table_exists_host(const int32_t *env, int w, int h, float power);      // the rule of env_table_refresh on a host image
+// RGBE8 environments (include/tirt.h, "HDR environment")
+inline bool env_hdr_active(const tirt_ctx *c) { return c->env_format == 1 && (c->shade_features & SF_ENV) != 0u; }
+int env_hdr_check(const char *fn, const int32_t *rgbe, int w, int h, int *e_max);      // TIRT_ERR_ARG for a texel with E == 0 and a mantissa (its index in the text); e_max as tirt_ctx::env_emax
+bool env_table_exists_host_hdr(const int32_t *env, int w, int h, float power, int e_max);
+int kat_env_lookup(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n);
 int sync_all(tirt_ctx *c);
 int flush_pending(tirt_ctx *c);
 bool kat_shade_step_has_inst(unsigned feat);      // tirt_render.hip: is `feat` the word of an instantiation of k_shade

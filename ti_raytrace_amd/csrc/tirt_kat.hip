@@ -218,6 +218,14 @@ int tirt_kat_env_pdf(tirt_ctx *c, const float *in, int in_stride, float *out, in
     return kat_env(c, 1, in, in_stride, out, out_stride, n);
 }
 
+int tirt_kat_env_lookup(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_env_lookup: null pointer or negative n");
+    TIRT_REQUIRE(in_stride >= 2 && out_stride >= 3, "tirt_kat_env_lookup: stride too small (2 words in, 3 out)");
+    CTX(c);
+    return kat_env_lookup(c, in, in_stride, out, out_stride, n);
+}
+
 int tirt_kat_texture_alpha(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n)
 {
     TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_texture_alpha: null pointer or negative n");

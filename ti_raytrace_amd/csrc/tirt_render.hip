@@ -43,6 +43,8 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
     const float t = hrec.x;
     // environment importance sampling (SF_ENV_SAMPLE instantiations only; include/tirt.h): the share of the light samples that go to the environment
     constexpr bool ENV_NEE = (FEAT & SF_ENV_SAMPLE) != 0u;
+    // an RGBE8 environment (SF_ENV_HDR instantiations only; include/tirt.h, "HDR environment"): the two lookups below decode linear texels, no srgb_to_lrgb
+    constexpr bool ENV_HDR = (FEAT & SF_ENV_HDR) != 0u;
     [[maybe_unused]] float p_env = 0.0f;
     if constexpr (ENV_NEE) p_env = sc.light_count == 0 ? 1.0f : env_table(sc).share;
     if (t < INF_VALUE) {
@@ -124,7 +126,7 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
                             int expect = -2;
                             if (e_pdf > 0.0f) {
                                 const float w = power_heuristic(pdf_l, e_pdf) / maxf(0.0001f, pdf_l);
-                                c = (srgb_to_lrgb(texture2d(sc.env, sc.env_w, sc.env_h, ep.tx, ep.ty)) * sc.env_power) * w;
+                                c = (env_lookup<ENV_HDR>(sc.env, sc.env_w, sc.env_h, ep.tx, ep.ty) * sc.env_power) * w;
                                 c = c * throughout;
                                 c = c * reflect_color;
                                 c = c * e_brdf;
@@ -226,7 +228,7 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
         const float dis = tm_sqrt(direction.x * direction.x + direction.z * direction.z);
         const float tx = (tm_atan2(direction.z, direction.x) + PI_SCENE) / PI_SCENE / 2.0f;
         const float ty = tm_atan2(direction.y, dis) / PI_SCENE + 0.5f;
-        const v3 e = srgb_to_lrgb(texture2d(sc.env, sc.env_w, sc.env_h, tx, ty));
+        const v3 e = env_lookup<ENV_HDR>(sc.env, sc.env_w, sc.env_h, tx, ty);
         if constexpr (ENV_NEE) {
             // MIS against the environment sample the previous vertex could have taken: weight 1 behind a camera or glass vertex (no NEE there)
             float w = 1.0f;
@@ -283,6 +285,9 @@ __global__ void k_generate(PathSoA ps, CameraView cam, TileMap tm, int P, int S,
 #endif
 #ifndef SH_MIN_WAVES_ENV         // the instantiations with environment importance sampling (SF_ENV_SAMPLE): see DESIGN.md, "Importance sampling of the environment"
 #define SH_MIN_WAVES_ENV 4
+#endif
+#ifndef SH_MIN_WAVES_HDR         // the generic kernel's twin for an RGBE8 environment (SF_ENV_HDR): see DESIGN.md, "HDR environment"
+#define SH_MIN_WAVES_HDR 4       // at 5 (96 VGPRs) it has 12 bytes of scratch where its 8-bit sibling has none
 #endif
 // The 78 array pointers of the path state are the first kernel argument and are never read from it directly: each of the three places
 // that needs some of them (a path's state in, the survivor's state out, the shadow ray out) reads those from the kernel-argument segment in
@@ -680,6 +685,14 @@ constexpr unsigned SF_I_ENV = SF_ALL | SF_ENV_SAMPLE, SF_I_ENV_MAPS = SF_I_MAPS 
 static const ShadeInst SHADE_ENV_INST[] = {
     {SF_I_ENV, k_shade<SF_I_ENV, SH_MIN_WAVES_ENV>, k_shade<SF_I_ENV, SH_MIN_WAVES_ENV, true>},
     {SF_I_ENV_MAPS, k_shade<SF_I_ENV_MAPS, SH_MIN_WAVES_ENV>, k_shade<SF_I_ENV_MAPS, SH_MIN_WAVES_ENV, true>}};
+// an RGBE8 environment that is lit (SF_ENV_HDR; tirt_env_upload_hdr): twins of the generic kernel and of the one with every texture slot, without and with the
+// environment's light sample, in tables of their own -- entry 0 an untextured scene's, entry 1 a textured one's.  Launch bounds: each twin's 8-bit sibling's, but for
+// the generic twin, which spills at 5 waves and has SH_MIN_WAVES_HDR ("HDR environment": no scratch at any of them)
+constexpr unsigned SF_I_HDR = SF_ALL | SF_ENV_HDR, SF_I_HDR_MAPS = SF_I_MAPS | SF_ENV_HDR, SF_I_ENV_HDR = SF_I_ENV | SF_ENV_HDR, SF_I_ENV_HDR_MAPS = SF_I_ENV_MAPS | SF_ENV_HDR;
+template <unsigned F, int MW>
+constexpr ShadeInst shade_inst() { return {F, k_shade<F, MW>, k_shade<F, MW, true>}; }      // a table entry: the word, the kernel and its LIST variant
+static const ShadeInst SHADE_HDR_INST[] = {shade_inst<SF_I_HDR, SH_MIN_WAVES_HDR>(), shade_inst<SF_I_HDR_MAPS, SH_MIN_WAVES_MAPS>()};
+static const ShadeInst SHADE_ENV_HDR_INST[] = {shade_inst<SF_I_ENV_HDR, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_ENV_HDR_MAPS, SH_MIN_WAVES_ENV>()};
 static const ShadeSpecInst SHADE_SPEC_INST[] = {
     {SF_I_SPHERE, k_shade_spec<SF_I_SPHERE>}, {SF_I_MESH, k_shade_spec<SF_I_MESH>}, {SF_ALL, k_shade_spec<SF_ALL>}};
 template <class T, size_t N>
@@ -692,6 +705,7 @@ static const T &pick_shade_inst(const T (&tab)[N], const tirt_ctx *c)
 }
 static const ShadeInst &pick_shade_rgb(const tirt_ctx *c)
 {
+    if (env_hdr_active(c)) return (env_sample_active(c) ? SHADE_ENV_HDR_INST : SHADE_HDR_INST)[(c->shade_features & ~SF_ALL) ? 1 : 0];
     if (env_sample_active(c)) return SHADE_ENV_INST[(c->shade_features & ~SF_ALL) ? 1 : 0];
     return pick_shade_inst(SHADE_INST, c);
 }
@@ -707,11 +721,19 @@ static_assert(sizeof(KAT_STEP_INST) / sizeof(KAT_STEP_INST[0]) == sizeof(SHADE_I
 static const KatStepInst KAT_STEP_ENV_INST[] = {   // one per entry of SHADE_ENV_INST
     {SF_I_ENV, k_kat_shade_step<SF_I_ENV, SH_MIN_WAVES_ENV>}, {SF_I_ENV_MAPS, k_kat_shade_step<SF_I_ENV_MAPS, SH_MIN_WAVES_ENV>}};
 static_assert(sizeof(KAT_STEP_ENV_INST) / sizeof(KAT_STEP_ENV_INST[0]) == sizeof(SHADE_ENV_INST) / sizeof(SHADE_ENV_INST[0]), "one known-answer kernel per instantiation of k_shade");
+static const KatStepInst KAT_STEP_HDR_INST[] = {   // one per entry of SHADE_HDR_INST
+    {SF_I_HDR, k_kat_shade_step<SF_I_HDR, SH_MIN_WAVES_HDR>}, {SF_I_HDR_MAPS, k_kat_shade_step<SF_I_HDR_MAPS, SH_MIN_WAVES_MAPS>}};
+static_assert(sizeof(KAT_STEP_HDR_INST) / sizeof(KAT_STEP_HDR_INST[0]) == sizeof(SHADE_HDR_INST) / sizeof(SHADE_HDR_INST[0]), "one known-answer kernel per instantiation of k_shade");
+static const KatStepInst KAT_STEP_ENV_HDR_INST[] = {   // one per entry of SHADE_ENV_HDR_INST
+    {SF_I_ENV_HDR, k_kat_shade_step<SF_I_ENV_HDR, SH_MIN_WAVES_ENV>}, {SF_I_ENV_HDR_MAPS, k_kat_shade_step<SF_I_ENV_HDR_MAPS, SH_MIN_WAVES_ENV>}};
+static_assert(sizeof(KAT_STEP_ENV_HDR_INST) / sizeof(KAT_STEP_ENV_HDR_INST[0]) == sizeof(SHADE_ENV_HDR_INST) / sizeof(SHADE_ENV_HDR_INST[0]), "one known-answer kernel per instantiation of k_shade");
 
 static kat_step_fn_t kat_step_inst(unsigned feat)
 {
     for (const KatStepInst &k : KAT_STEP_INST) if (k.feat == feat) return k.fn;
     for (const KatStepInst &k : KAT_STEP_ENV_INST) if (k.feat == feat) return k.fn;
+    for (const KatStepInst &k : KAT_STEP_HDR_INST) if (k.feat == feat) return k.fn;
+    for (const KatStepInst &k : KAT_STEP_ENV_HDR_INST) if (k.feat == feat) return k.fn;
     return nullptr;
 }
 bool kat_shade_step_has_inst(unsigned feat) { return kat_step_inst(feat) != nullptr; }
@@ -720,6 +742,7 @@ int kat_shade_step(tirt_ctx *c, unsigned feat, const float *in, int in_stride, f
 {
     TIRT_REQUIRE(c->n >= 1, "tirt_kat_shade_step: no scene");
     TIRT_REQUIRE((c->shade_features & ~feat) == 0u, "tirt_kat_shade_step: feat does not cover the scene's feature word (tirt_shade_features)");
+    TIRT_REQUIRE(((feat & SF_ENV_HDR) != 0u) == env_hdr_active(c), "tirt_kat_shade_step: an instantiation with bit 2048 reads RGBE8 texels and one without it 8-bit texels: feat must carry the bit exactly when tirt_shade_features does");
     TIRT_REQUIRE(!(feat & SF_ENV_SAMPLE) || env_sample_active(c), "tirt_kat_shade_step: an instantiation with bit 1024 needs the environment's sampling table (tirt_env_sampling on, a lit environment)");
     const kat_step_fn_t fn = kat_step_inst(feat);
     TIRT_REQUIRE(fn, "tirt_kat_shade_step: feat is not an instantiation of k_shade");

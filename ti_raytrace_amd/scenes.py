@@ -155,6 +155,14 @@ def sun_sky_image(w=16, h=8, floor=8, at=(11, 1)):
     return img
 
 
+def hdr_sun_sky(w=16, h=8, floor=0.02, sun=5000.0, at=(11, 1)):
+    """(h, w, 3) float32 linear radiance, row 0 the top: one texel at ``sun`` on a uniform sky of ``floor`` -- 250 000 : 1 by default, the ratio of a real sun
+    to its sky, which 8 bits per channel times one env_power cannot hold (Scene.add_env_hdr)."""
+    img = np.full((h, w, 3), floor, np.float32)
+    img[at[1], at[0]] = sun
+    return img
+
+
 def _box(lo, hi):
     """the twelve triangles of an axis-aligned box, outward facing"""
     x0, y0, z0 = lo
@@ -168,7 +176,8 @@ class sun_ground(Example.example):
     """No reference counterpart: a box on a ground quad under a synthetic sky whose light is nearly all in one texel, no emitters -- the case BSDF
     sampling alone handles worst.  ``env_sampling=True`` (the default here) aims the light samples at the sky by its brightness (include/tirt.h,
     "Importance sampling of the environment"); ``env_sampling=False`` renders with the reference's estimator.  Both surfaces are rough metals, or rough
-    dielectrics with ``metallic=0.0``."""
+    dielectrics with ``metallic=0.0``.  ``sky``: an ``(h, w, 3)`` uint8 image (default ``sun_sky_image()``), or an HDR sky -- a float32 / float64 array of linear
+    radiance such as ``hdr_sun_sky()``, or the path of a ``.hdr`` file -- which goes through ``Scene.add_env_hdr``."""
 
     def __init__(self, imgSizeX, imgSizeY, sample_count, device_id=None, env_power=20.0, sky=None, env_sampling=True, metallic=1.0, **pt_kwargs):
         Example.example.__init__(self, imgSizeX, imgSizeY, sample_count, device_id)
@@ -179,7 +188,11 @@ class sun_ground(Example.example):
         g = 2.0
         self.scene.add_mesh(np.array([[(-g, 0, -g), (-g, 0, g), (g, 0, g)], [(-g, 0, -g), (g, 0, g), (g, 0, -g)]], np.float64), disney((0.7, 0.7, 0.7), 0.8))
         self.scene.add_mesh(_box((-0.5, 0.0, -0.5), (0.5, 1.5, 0.5)), disney((0.8, 0.4, 0.2), 0.5))
-        self.scene.add_env(sun_sky_image() if sky is None else sky, env_power)
+        is_path = isinstance(sky, (str, bytes, os.PathLike))
+        if (is_path and os.fsdecode(sky).lower().endswith(".hdr")) or (sky is not None and not is_path and np.asarray(sky).dtype in (np.float32, np.float64)):
+            self.scene.add_env_hdr(sky, env_power)
+        else:
+            self.scene.add_env(sun_sky_image() if sky is None else sky, env_power)
         self.integrator = PT_RGB.PathTrace(imgSizeX, imgSizeY, self.cam, self.scene, 64, env_sampling=env_sampling, **pt_kwargs)
 
     def frame_camera(self, scale_factor=0.6):
