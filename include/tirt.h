@@ -344,6 +344,55 @@ int tirt_shade_features_host_env_hdr(const float *material, int nm, const int32_
                                      const int32_t *light, int light_count, const int32_t *env, int env_w, int env_h, float env_power,
                                      int env_sampling, int env_format, uint32_t *out);
 
+/* Choosing emitters by power (csrc/tirt_envsample.hip, the table; csrc/tirt_device.h, light_pick; csrc/tirt_render.hip, shade_path under SF_LIGHT_POWER; no reference
+ * counterpart: Scene.sample_li picks light[(int)(r * light_count)], one entry per emissive PRIMITIVE, so an emitter is found as often as it has entries).  Opt-in, PT_RGB
+ * only: with mode 0 every kernel keeps its code and its bits; tirt_pt_spec_render and both BDPT integrators never read the switch.
+ * All f32 below: one rounding per operation, no contraction, in the order written (tests/light_sampling_expected.py restates it; the device gives its bits).
+ * 1. Weight of entry i of the light list: w_i = (((e.r + e.g) + e.b) / 3.0f) * area_i, e = words 2..4 of the emitter's material row as they stand (shade_path does not
+ *      sRGB-decode an emission), area_i = get_prim_area of the primitive (Heron for a triangle, r * r * PI_SCENE for a sphere: what the light record holds).
+ *      An entry takes part iff w_i > 0 and w_i <= FLT_MAX (so not 0, negative, NaN or infinite -- a degenerate triangle's NaN area among them).
+ * 2. e_max = the exponent frexpf gives for the largest w_i that takes part (w = f * 2^e, 0.5 <= f < 1).  q_i = max(1, rintf(ldexpf(w_i, 24 - e_max))) for an entry that
+ *      takes part (round half to even; 1 <= q_i <= 2^24), q_i = 0 otherwise.  The floor of 1 keeps every emitter with a weight reachable: no uniform share is needed for an
+ *      unbiased estimator.  Scaling every emission by a power of two gives the same q to the bit.  The maximum is taken over the bits of positive floats, which order as
+ *      the floats do: exact and free of order.
+ * 3. C[i] = q_0 + .. + q_i, 64-bit integers (any summation order gives them); total = C[N - 1], N = light_count.  The table exists, and the feature is active, iff
+ *      mode == 1, N > 0, total > 0 and every entry of the list is a triangle or a sphere (bits 8 and 64 of the feature word clear).
+ * 4. Choice from the light random r in [0, 1] with the uniform share u in [0, 1) (default 0):
+ *        r < u:      i = min((int)((r / u) * (float)N), N - 1)                                     -- the reference's expression on the rescaled random
+ *        otherwise:  k = min((uint32)(((r - u) / (1.0f - u)) * 16777216.0f), 2^24 - 1);  t = floor(k * total / 2^24) (exact: the high half of (k << 40) * total);
+ *                    i = the first index with C[i] > t                                             -- env_pick's integer inverse; an entry with q = 0 is never its answer
+ *      P_i = u / (float)N + (1.0f - u) * ((float)q_i / (float)total): quotient, quotient, difference, product, sum, in that order.  With u = 0, r' = r to the bit.
+ * 5. One bounce of k_shade with the table (bit 4096).  Under bit 1024 r is the rescaled random r' of "Importance sampling of the environment", step 5, and every
+ *      (1 - p_env) factor applies as there, last.
+ *      light sample: entry i and P_i of step 4 in the place of lidx;  light_choice_pdf = P_i / area_i;  the point (a, b), the directions, visibility,
+ *        light_pdf = light_dist * light_dist * light_choice_pdf / NdotL_light, the power heuristic, the contribution and the shadow ray (expect = the hit primitive, its distance)
+ *        keep their form and operand order.  No drawn / stated factor ("Importance sampling of the environment"): the emitter sample keeps the reference's form.
+ *      emitter hit with perfect_spec != 1: light_pdf = (t * t) * (P_hit / area) / fCosTheta -- a product, a quotient, a product, a quotient -- in the place of
+ *        (t * t) / ((area * light_count) * fCosTheta).
+ *      P_hit rides in a spare word of the hit primitive's 128-byte shading record: the last word of quad 4 of a triangle, the first word of quad 2 of a sphere.  Both are 0
+ *        while the feature is inactive (written with the table, written back to 0 when the feature goes).  The record holds its entry's own P.  Scene (Python) lists a
+ *        primitive at most once.  A list uploaded through this ABI may name one twice: the entries then have equal weights and equal P, the record holds that P, and a
+ *        hit's light_pdf understates the chance of sampling the primitive by the number of its entries -- exactly as 1 / (area * light_count) does with the switch off.
+ *      LIMIT: where metallic < 1 the reference's sampler does not draw from the pdf it states, so its MIS estimate depends on the weights; changing light_pdf moves them.
+ *        On metals switch on and off have one expectation; on dielectrics they can differ where an emitter's solid-angle pdf is comparable to the BSDF's.
+ * tirt_light_sampling(ctx, mode, uniform_share): mode 0 uniform (the default), 1 power; 0 <= uniform_share < 1 (TIRT_ERR_ARG otherwise, before a context is needed).
+ *   Submits pending renders and waits for work in flight.  The switch persists across scene, material and vertex uploads and tirt_film_create; the table is rebuilt
+ *   lazily with the light records (the next render, tirt_shade_features or query), which all three uploads invalidate.
+ * Feature word: bit 4096 (SF_LIGHT_POWER) = active by step 3; reported by tirt_shade_features (which builds the table if it is stale), kept out of every other
+ *   integrator's kernel choice.  tirt_pt_rgb_render then launches the twin with bit 4096 of k_shade<127>, <511> and of their twins with bits 1024 and / or 2048; a scene with
+ *   a spot, a laser or an unknown emitter runs exactly the kernels it runs with mode 0.
+ * tirt_light_table_download: info = (light_count, e_max, bit 4096, table built: mode 1 and a list of triangles and spheres); with a table q[N], prefix[N] (C) and
+ *   P[N] (all 0 where total == 0); each may be NULL.
+ * tirt_kat_light_pick: in 1 word (r in [0, 1]), out 2: i (bits), P_i.  One launch, row r on thread r.  TIRT_ERR_ARG: strides too small, r outside [0, 1], feature inactive.
+ * tirt_shade_features_host_lights: tirt_shade_features_host_env_hdr with the mode as an input, and the vertex rows a triangle's area needs: bit 4096 by step 3.
+ * tirt_kat_shade_step accepts the eight words with bit 4096 while the feature is active. */
+int tirt_light_sampling(tirt_ctx *ctx, int mode, float uniform_share);
+int tirt_light_table_download(tirt_ctx *ctx, uint32_t *q, uint64_t *prefix, float *P, int32_t info[4]);
+int tirt_kat_light_pick(tirt_ctx *ctx, const float *in, int in_stride, float *out, int out_stride, int n);
+int tirt_shade_features_host_lights(const float *material, int nm, const int32_t *primitive, int n, const float *shape, int ns,
+                                    const int32_t *light, int light_count, const int32_t *env, int env_w, int env_h, float env_power,
+                                    int env_sampling, int env_format, const float *vertex, int nv, int light_sampling, uint32_t *out);
+
 /* LBvh.Bvh.setup_data_gpu (accel/LBvh.py:192-226): Morton codes, stable radix sort, Karras
  * topology, leaf boxes, bottom-up refit, DFS flatten -- all on device. */
 int tirt_lbvh_build(tirt_ctx *ctx);

@@ -7,6 +7,7 @@ film) over struct-of-arrays path queues in HBM -- see DESIGN.md.
 """
 from .FilmRecords import FilmRecords, SampleMoments, TemporalAccumulation
 from .Scene import DeviceField
+from ._native import SF_LIGHT_POWER
 
 MAX_DEPTH = 15           # integrator/PT_RGB.py:21
 
@@ -21,7 +22,7 @@ def default_tile_size(H):
 class PathTrace(FilmRecords, SampleMoments, TemporalAccumulation):
     def __init__(self, imgSizeX, imgSizeY, cam, scene, stack_size,
                  seed=1, tile_rank=0, tile_count=1, tile_size=None, flags=0, env_sampling=False, env_share=0.5,
-                 motion=False, temporal=False, moments=False, aov=False):
+                 light_sampling="uniform", light_uniform_share=0.0, motion=False, temporal=False, moments=False, aov=False):
         self.imgSizeX = imgSizeX
         self.imgSizeY = imgSizeY
         self.cam = cam
@@ -55,6 +56,9 @@ class PathTrace(FilmRecords, SampleMoments, TemporalAccumulation):
         if not 0.0 < float(env_share) < 1.0:
             raise ValueError("PT_RGB.PathTrace: env_share must lie in (0, 1), got %r" % (env_share,))
         self._env_sampling, self._env_share = bool(env_sampling), float(env_share)
+        # extension: emitters chosen by power instead of one entry of the light list in light_count (include/tirt.h, "Choosing emitters by power");
+        # light_uniform_share = the part of the emitter samples that still picks uniformly
+        self._light_sampling, self._light_uniform_share = self._check_light_sampling(light_sampling, light_uniform_share)
         # extension: the film after denoise(), a buffer of its own beside hdr
         self.denoised = DeviceField("denoised", scene, self._denoised_download)
 
@@ -65,6 +69,7 @@ class PathTrace(FilmRecords, SampleMoments, TemporalAccumulation):
         self.scene.ctx.film_create(self.imgSizeX, self.imgSizeY, self.tile_rank, self.tile_count, self.tile_size)
         self.cam.attach(self.scene.ctx)
         self.scene.ctx.env_sampling(self._env_sampling, self._env_share)
+        self.scene.ctx.light_sampling(self._light_sampling == "power", self._light_uniform_share)
         if self.aov:
             self.scene.ctx.aov_enable(True)
         if self.moments:
@@ -90,6 +95,29 @@ class PathTrace(FilmRecords, SampleMoments, TemporalAccumulation):
             raise ValueError("PT_RGB.PathTrace: env_share must lie in (0, 1), got %r" % (share,))
         self._env_sampling, self._env_share = bool(on), share
         self.scene.ctx.env_sampling(self._env_sampling, self._env_share)
+
+    @staticmethod
+    def _check_light_sampling(mode, uniform_share):
+        if mode not in ("uniform", "power"):
+            raise ValueError("PT_RGB.PathTrace: light_sampling is \"uniform\" or \"power\", got %r" % (mode,))
+        if not 0.0 <= float(uniform_share) < 1.0:
+            raise ValueError("PT_RGB.PathTrace: light_uniform_share must lie in [0, 1), got %r" % (uniform_share,))
+        return mode, float(uniform_share)
+
+    @property
+    def light_sampling(self):
+        """(mode, uniform share) as given; ``light_sampling_active`` says whether the device chooses by power (bit 4096 of the feature word: mode "power", emitters
+        that are all triangles or spheres, a table with a weight in it)."""
+        return self._light_sampling, self._light_uniform_share
+
+    @property
+    def light_sampling_active(self):
+        return bool(self.scene.ctx.shade_features()[0] & SF_LIGHT_POWER)
+
+    def set_light_sampling(self, mode, uniform_share=None):
+        """Choose emitters uniformly or by power between renders (the film is not cleared)."""
+        self._light_sampling, self._light_uniform_share = self._check_light_sampling(mode, self._light_uniform_share if uniform_share is None else uniform_share)
+        self.scene.ctx.light_sampling(self._light_sampling == "power", self._light_uniform_share)
 
     def render(self):
         """One frame at ``cam.frame`` (the caller advances it with ``cam.update_frame()``)."""

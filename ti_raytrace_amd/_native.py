@@ -90,6 +90,9 @@ SHADE_INSTANTIATIONS_HDR = (SF_ALL | SF_ENV_HDR, SHADE_INSTANTIATION_MAPS | SF_E
                             SF_ALL | SF_ENV_SAMPLE | SF_ENV_HDR, SHADE_INSTANTIATION_MAPS | SF_ENV_SAMPLE | SF_ENV_HDR)
 ENV_FORMAT_RGB8, ENV_FORMAT_RGBE8 = 0, 1                            # tirt_env_format, Texture.format
 KAT_ENV_LOOKUP_IN, KAT_ENV_LOOKUP_OUT = 2, 3                        # words per row of tirt_kat_env_lookup
+SF_LIGHT_POWER = 4096                                               # emitters chosen by power, table built with a weight in it (tirt_light_sampling); not part of SF_ALL
+SHADE_INSTANTIATIONS_POWER = tuple(f | 4096 for f in (127, 511, 127 | 1024, 511 | 1024, 127 | 2048, 511 | 2048, 127 | 1024 | 2048, 511 | 1024 | 2048))      # k_shade's twins that choose by power
+KAT_LIGHT_PICK_IN, KAT_LIGHT_PICK_OUT = 1, 2                        # words per row of tirt_kat_light_pick
 KAT_ENV_SAMPLE_IN, KAT_ENV_SAMPLE_OUT = 2, 10                       # words per row of tirt_kat_env_sample
 KAT_ENV_PDF_IN, KAT_ENV_PDF_OUT = 3, 5                              # words per row of tirt_kat_env_pdf
 KAT_ALPHA_IN, KAT_ALPHA_OUT = 3, 2                                  # words per row of tirt_kat_texture_alpha
@@ -126,6 +129,11 @@ SIGNATURES = {
     "tirt_shade_features_host_env": (C.c_int, [_f32p, C.c_int, _i32p, C.c_int, _f32p, C.c_int, _i32p, C.c_int, _vp, C.c_int, C.c_int, C.c_float,
                                                C.c_int, C.POINTER(C.c_uint32)]),
     "tirt_env_sampling": (C.c_int, [_vp, C.c_int, C.c_float]),
+    "tirt_light_sampling": (C.c_int, [_vp, C.c_int, C.c_float]),
+    "tirt_light_table_download": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
+    "tirt_kat_light_pick": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
+    "tirt_shade_features_host_lights": (C.c_int, [_f32p, C.c_int, _i32p, C.c_int, _f32p, C.c_int, _i32p, C.c_int, _vp, C.c_int, C.c_int, C.c_float,
+                                                  C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
     "tirt_env_table_download": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
     "tirt_kat_env_sample": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
     "tirt_kat_env_pdf": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
@@ -471,6 +479,28 @@ class Context:
     def env_sampling(self, on, share=0.5):
         """include/tirt.h, tirt_env_sampling: importance-sample the environment in PT_RGB (NEE + MIS); share of the light samples it gets beside emitters"""
         env_sampling(self.handle, on, share)
+
+    def light_sampling(self, power, uniform_share=0.0):
+        """include/tirt.h, tirt_light_sampling: choose PT_RGB's emitter samples by power (True) or uniformly over the light list; the share that stays uniform"""
+        light_sampling(self.handle, 1 if power else 0, uniform_share)
+
+    def light_table_download(self):
+        """include/tirt.h, tirt_light_table_download: None without a table, else {"count", "e_max", "active", "q" [N] uint32, "prefix" [N] uint64, "P" [N] float32}"""
+        info = (C.c_int32 * 4)()
+        check(lib().tirt_light_table_download(self.handle, None, None, None, info))
+        if not info[3]:
+            return None
+        n = int(info[0])
+        q, prefix, P = np.zeros(n, np.uint32), np.zeros(n, np.uint64), np.zeros(n, np.float32)
+        check(lib().tirt_light_table_download(self.handle, _ptr(q), _ptr(prefix), _ptr(P), info))
+        return {"count": n, "e_max": int(info[1]), "active": bool(info[2]), "q": q, "prefix": prefix, "P": P}
+
+    def kat_light_pick(self, r):
+        """include/tirt.h, tirt_kat_light_pick: r (n,) float32 in [0, 1] -> (index (n,) int32, P (n,) float32)"""
+        r = np.ascontiguousarray(r, np.float32).reshape(-1)
+        out = np.zeros((r.shape[0], KAT_LIGHT_PICK_OUT), np.float32)
+        check(lib().tirt_kat_light_pick(self.handle, r, 1, out.reshape(-1), KAT_LIGHT_PICK_OUT, r.shape[0]))
+        return out[:, 0].copy().view(np.int32), out[:, 1].copy()
 
     def env_table_download(self):
         """include/tirt.h, tirt_env_table_download: None without a table, else {"w", "h", "active", "q" [h, w] uint32, "row_sums" [h, w] uint64, "marginal" [h] uint64}"""
@@ -962,6 +992,25 @@ def env_upload_hdr(handle, packed, power, dims=None):
     packed = None if packed is None else np.ascontiguousarray(packed, np.int32)
     w, h = dims if dims is not None else ((0, 0) if packed is None else packed.shape)
     check(lib().tirt_env_upload_hdr(handle, _ptr(packed), int(w), int(h), float(power)))
+
+
+def shade_features_host_lights(material, primitive, shape, light, light_count, vertex=None, light_sampling=False, env=None, env_power=0.0, env_sampling=False, env_format=0):
+    """shade_features_host_env_hdr with the mode of tirt_light_sampling as an input, and the vertex rows a triangle emitter's area needs: bit 4096 where a context would report it."""
+    material = np.ascontiguousarray(material, np.float32); primitive = np.ascontiguousarray(primitive, np.int32)
+    shape = np.ascontiguousarray(shape, np.float32); light = np.ascontiguousarray(light, np.int32)
+    env = None if env is None else np.ascontiguousarray(env, np.int32)
+    vertex = None if vertex is None else np.ascontiguousarray(vertex, np.float32)
+    out = C.c_uint32(0)
+    check(lib().tirt_shade_features_host_lights(material.reshape(-1), material.shape[0], primitive.reshape(-1), primitive.shape[0], shape.reshape(-1), shape.shape[0],
+                                                light.reshape(-1), int(light_count), _ptr(env), 0 if env is None else env.shape[0], 0 if env is None else env.shape[1],
+                                                float(env_power), 1 if env_sampling else 0, int(env_format), _ptr(vertex), 0 if vertex is None else vertex.shape[0],
+                                                1 if light_sampling else 0, C.byref(out)))
+    return int(out.value)
+
+
+def light_sampling(handle, mode, uniform_share=0.0):
+    """tirt_light_sampling on a raw context handle (None: only the refusals that need no context can be reached)"""
+    check(lib().tirt_light_sampling(handle, int(mode), float(uniform_share)))
 
 
 def env_sampling(handle, on, share=0.5):

@@ -268,15 +268,17 @@ int ensure_shade_records(tirt_ctx *c)
         if (c->shade_rec.ensure(sizeof(float4) * 8 * (size_t)c->n)) return TIRT_ERR_HIP;
         hipLaunchKernelGGL(k_shade_records, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, scene_view(c), c->shade_rec.as<float4>(), (c->shade_features & (SF_TEXTURE | SF_TEXTURE_PARAM)) ? 1 : 0);
         c->shade_rec_valid = true;
+        c->light_phit_written = false;             // (the spare words are zero again)
     }
     if (!(c->light_rec_valid && c->light_rec.p)) {
-        const int nl = c->light_count > 0 ? c->light_count : 1;          // (never an empty allocation; no record is read when light_count is 0)
-        if (c->light_rec.ensure(sizeof(float4) * LIGHT_REC_QUADS * (size_t)nl)) return TIRT_ERR_HIP;
+        // (never an empty allocation; no record is read when light_count is 0.  Behind the records: room for the table of tirt_light_sampling, 8 bytes an entry)
+        if (c->light_rec.ensure(light_table_offset(c->light_count) + light_table_bytes(c->light_count))) return TIRT_ERR_HIP;
         if (c->light_count > 0)
             hipLaunchKernelGGL(k_light_records, dim3((c->light_count + 63) / 64), dim3(64), 0, c->stream, scene_view(c), c->light_rec.as<float4>());
         c->light_rec_valid = true;
+        c->light_tab_valid = false;
     }
-    return 0;
+    return light_table_sync(c);
 }
 
 // ---- Scene.total_area (Scene.py:747-750): serial so the f32 sum order is defined --------------
@@ -378,7 +380,7 @@ using namespace tirt;
 extern "C" {
 
 const char *tirt_last_error(void) { return g_error.c_str(); }
-int tirt_version(void) { return 101; }
+int tirt_version(void) { return 102; }
 
 int tirt_device_count(int *out)
 {
@@ -659,6 +661,33 @@ int tirt_env_table_download(tirt_ctx *c, uint32_t *q, uint64_t *row_sums, uint64
     return env_table_download(c, q, row_sums, marginal, info);
 }
 
+int tirt_light_sampling(tirt_ctx *c, int mode, float uniform_share)
+{
+    // what needs no context first
+    TIRT_REQUIRE(mode == 0 || mode == 1, "tirt_light_sampling: mode is 0 (uniform) or 1 (power)");
+    TIRT_REQUIRE(uniform_share >= 0.0f && uniform_share < 1.0f, "tirt_light_sampling: uniform_share outside [0, 1)");
+    CTX(c);
+    if (sync_all(c)) return TIRT_ERR_HIP;      // the kernels in flight read the table's head and the emitters' spare words
+    c->light_sample_mode = mode; c->light_uniform_share = uniform_share;
+    c->light_tab_valid = false;                // rebuilt with the next render or query, as the light records are (ensure_shade_records)
+    return TIRT_OK;
+}
+
+int tirt_light_table_download(tirt_ctx *c, uint32_t *q, uint64_t *prefix, float *P, int32_t info[4])
+{
+    CTX(c);
+    if (sync_all(c)) return TIRT_ERR_HIP;
+    return light_table_download(c, q, prefix, P, info);
+}
+
+int tirt_kat_light_pick(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_light_pick: null pointer or negative n");
+    TIRT_REQUIRE(in_stride >= 1 && out_stride >= 2, "tirt_kat_light_pick: stride too small (1 word in, 2 out)");
+    CTX(c);
+    return kat_light_pick(c, in, in_stride, out, out_stride, n);
+}
+
 // One buffer for all textures: `count` quads (offset in ints from the buffer's start, w, h, wrap), then the caller's texels.
 int tirt_texture_upload(tirt_ctx *c, int count, const int32_t *texels, int64_t total, const int64_t *offset, const int32_t *w, const int32_t *h, const int32_t *wrap)
 {
@@ -718,7 +747,12 @@ int tirt_shade_features(tirt_ctx *c, uint32_t *out)
 {
     TIRT_REQUIRE(c, "null context");
     TIRT_REQUIRE(out, "tirt_shade_features: null pointer");
-    out[0] = c->shade_features | (c->has_cutout ? (unsigned)SF_CUTOUT : 0u) | (env_sample_active(c) ? (unsigned)SF_ENV_SAMPLE : 0u) | (env_hdr_active(c) ? (unsigned)SF_ENV_HDR : 0u);
+    if (c->light_sample_mode == 1 && c->n >= 1 && !(c->shade_rec_valid && c->light_rec_valid && c->light_tab_valid)) {
+        // bit 4096 needs the table's total: built here as a render would build it (whatever invalidated it has drained the work in flight)
+        TIRT_HIP(hipSetDevice(c->device));
+        if (sync_all(c) || ensure_shade_records(c)) return TIRT_ERR_HIP;
+    }
+    out[0] = (c->n >= 1 && light_power_active(c) ? (unsigned)SF_LIGHT_POWER : 0u) | c->shade_features | (c->has_cutout ? (unsigned)SF_CUTOUT : 0u) | (env_sample_active(c) ? (unsigned)SF_ENV_SAMPLE : 0u) | (env_hdr_active(c) ? (unsigned)SF_ENV_HDR : 0u);
     out[1] = c->shade_specialize ? 1u : 0u;
     return TIRT_OK;
 }
@@ -762,6 +796,24 @@ int tirt_shade_features_host_env_hdr(const float *material, int nm, const int32_
     if (int rc = tirt_shade_features_host(material, nm, primitive, n, shape, ns, light, light_count, env, env_w, env_h, env_power, out)) return rc;
     if (*out & SF_ENV) *out |= SF_ENV_HDR;
     if (env_sampling && (*out & SF_ENV) && env_table_exists_host_hdr(env, env_w, env_h, env_power, e_max)) *out |= SF_ENV_SAMPLE;
+    return TIRT_OK;
+}
+
+// the same with the mode of tirt_light_sampling as an input: bit 4096 where a context would report it (a triangle's weight needs the vertex rows)
+int tirt_shade_features_host_lights(const float *material, int nm, const int32_t *primitive, int n, const float *shape, int ns,
+                                    const int32_t *light, int light_count, const int32_t *env, int env_w, int env_h, float env_power, int env_sampling, int env_format,
+                                    const float *vertex, int nv, int light_sampling, uint32_t *out)
+{
+    TIRT_REQUIRE(light_sampling == 0 || light_sampling == 1, "tirt_shade_features_host_lights: light_sampling is 0 (uniform) or 1 (power)");
+    if (int rc = tirt_shade_features_host_env_hdr(material, nm, primitive, n, shape, ns, light, light_count, env, env_w, env_h, env_power, env_sampling, env_format, out)) return rc;
+    if (!light_sampling || light_count <= 0 || (*out & (SF_LIGHT_SPOT_LASER | SF_LIGHT_OTHER))) return TIRT_OK;
+    TIRT_REQUIRE(nv >= 0 && (vertex || nv == 0), "tirt_shade_features_host_lights: bad vertex table");
+    for (int i = 0; i < light_count; i++) {
+        const int32_t *pr = primitive + (size_t)light[i] * 3;
+        TIRT_REQUIRE(pr[2] >= 0 && pr[2] < nm, "tirt_shade_features_host_lights: material index out of range");
+        TIRT_REQUIRE(pr[0] != PRIMITIVE_TRI || (pr[1] >= 0 && pr[1] + 2 < nv), "tirt_shade_features_host_lights: vertex index out of range");
+    }
+    if (light_table_exists_host(material, nm, primitive, n, shape, ns, vertex, nv, light, light_count)) *out |= SF_LIGHT_POWER;
     return TIRT_OK;
 }
 

@@ -90,6 +90,8 @@ enum : unsigned {
                               // Kept beside tirt_ctx::shade_features as 512 is (k_shade_spec and BDPT never see it); reported by tirt_shade_features
     SF_ENV_HDR = 2048u,       // the uploaded environment is RGBE8 (tirt_env_upload_hdr) and lit (bit 2): k_shade's HDR twins decode its texels.  Derived (env_hdr_active), never stored in
                               // the context's word, reported by tirt_shade_features; the 8-bit kernels are compiled without it and keep their code
+    SF_LIGHT_POWER = 4096u,   // emitters are chosen by power (tirt_light_sampling mode 1), the list holds triangles and spheres only and its table has total > 0: k_shade's POWER twins.
+                              // Derived (light_power_active), never stored in the context's word (k_shade_spec, BDPT and pick_shade_inst never see it); reported by tirt_shade_features
     SF_LIGHT_KINDS = SF_LIGHT_TRI | SF_LIGHT_SPOT_LASER | SF_LIGHT_SPHERE | SF_LIGHT_OTHER
 };
 
@@ -932,6 +934,67 @@ TD EnvPdf env_pdf(const EnvTable &t, int w, int h, v3 d)
         p.pdf = (((float)q / (float)t.total) * ((float)w * (float)h)) / (ENV_TWO_PI_SQ * dis);
     }
     return p;
+}
+
+// ---- emitter choice by power (include/tirt.h, "Choosing emitters by power"; tirt_envsample.hip builds the table; no reference counterpart: Scene.sample_li picks uniformly) ----
+// The table lives BEHIND the 8 * light_count quads of the light records in the same allocation: a 32-byte head (total u64, uniform share f32, e_max i32, bits of the
+// largest weight u32, -) and the inclusive 64-bit sums C[light_count] of the quantised weights.  SceneView does not change for it, and the light records stay what
+// BDPT and the spectral path read.  The binary search walks the dense 8-byte sums; the chosen 128-byte record is read once afterwards (light_sample_rec).
+constexpr size_t LIGHT_TABLE_HEAD = 32u;
+TM_HD size_t light_table_offset(int light_count) { return sizeof(float) * 4u * 8u * (size_t)(light_count > 0 ? light_count : 1); }
+TM_HD size_t light_table_bytes(int light_count) { return LIGHT_TABLE_HEAD + 8u * (size_t)(light_count > 0 ? light_count : 1); }
+// w_i and q_i of include/tirt.h: level of the emission times the area; the bits of a weight that takes part (finite and > 0), else 0
+TM_HD unsigned light_weight_bits(float er, float eg, float eb, float area)
+{
+    const float w = (((er + eg) + eb) / 3.0f) * area;
+    unsigned u; __builtin_memcpy(&u, &w, 4);
+    return (w > 0.0f && w <= 3.4028234e38f) ? u : 0u;
+}
+TM_HD int light_weight_emax(unsigned max_bits)
+{
+    float m; __builtin_memcpy(&m, &max_bits, 4);
+    int e = 0; (void)__builtin_frexpf(m, &e);
+    return max_bits ? e : 0;
+}
+TM_HD unsigned light_weight_q(unsigned bits, int e_max)
+{
+    if (!bits) return 0u;
+    float w; __builtin_memcpy(&w, &bits, 4);
+    const float s = __builtin_rintf(__builtin_ldexpf(w, 24 - e_max));
+    return s > 1.0f ? (unsigned)s : 1u;
+}
+struct LightTable { const env_u64 *cum; env_u64 total; float u; };
+TD LightTable light_table(const SceneView &sc)
+{
+    const char *b = (const char *)sc.light_rec + light_table_offset(sc.light_count);
+    LightTable t; t.total = *(const env_u64 *)b; t.u = *(const float *)(b + 8); t.cum = (const env_u64 *)(b + LIGHT_TABLE_HEAD);
+    return t;
+}
+// P_i = u / N + (1 - u) * ((float)q_i / (float)total): a quotient, a quotient, a difference, a product, a sum -- in that order
+TM_HD float light_choice_P(env_u64 q, env_u64 total, float u, int n) { return u / (float)n + (1.0f - u) * ((float)q / (float)total); }
+// the entry a light random r in [0, 1] picks, and its P: below u the reference's index on r / u, else the integer inverse of env_pick on the 24 bits of (r - u) / (1 - u)
+TD int light_pick(const LightTable &t, int n, float r, float &P)
+{
+    int i;
+    if (r < t.u) {
+        i = (int)((r / t.u) * (float)n);
+        if (i >= n) i = n - 1;
+    } else {
+        unsigned k = (unsigned)(((r - t.u) / (1.0f - t.u)) * 16777216.0f);
+        if (k > 16777215u) k = 16777215u;                    // (a rescaled random that rounds to 1)
+        const env_u64 tt = __umul64hi((env_u64)k << 40, t.total);      // floor(k * total / 2^24)
+        int lo = 0, hi = n - 1;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (t.cum[mid] > tt) hi = mid; else lo = mid + 1; }
+        i = lo;
+    }
+    P = light_choice_P(t.cum[i] - (i > 0 ? t.cum[i - 1] : 0ull), t.total, t.u, n);
+    return i;
+}
+// P of the entry that names a hit primitive: the spare word of its shading record (k_light_phit writes it while the feature is active, 0 otherwise)
+TD float shade_rec_phit(const float4 *rec, int prim)
+{
+    const float4 *r = rec + (size_t)prim * 8;
+    return __float_as_int(r[1].w) == PRIMITIVE_TRI ? r[4].w : r[2].x;
 }
 
 // ---- Camera.py:122-142 ----------------------------------------------------------------------------------------

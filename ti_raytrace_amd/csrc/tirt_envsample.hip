@@ -218,4 +218,153 @@ int kat_env(tirt_ctx *c, int which, const float *in, int in_stride, float *out, 
     });
 }
 
+// ---- emitters chosen by power (include/tirt.h, "Choosing emitters by power"): the table behind the light records (tirt_device.h, light_table).  Here because it shares
+// the scan.  Weights come from the light records -- the emission and get_prim_area k_light_records put there --, their maximum from an atomic maximum over the bits of
+// positive floats (exact and order-free: such bits order as the floats do), the sums from the integer scan above: every order of threads gives one table.
+//   k_light_weights  bits of w_i (0: takes no part) into the unsummed entries, their maximum into the head      one thread per entry
+//   k_light_quant    e_max from the maximum, q_i in the entries' place                                          one thread per entry
+//   k_env_scan       inclusive sum in place                                                                       one block
+//   k_light_head     total, uniform share and e_max into the head
+//   k_light_phit     P_i into the spare word of the shading record of the primitive entry i names (or 0 there)  one thread per entry
+__global__ __launch_bounds__(256) void k_light_weights(const float4 *lrec, int n, env_u64 *cum, unsigned *max_bits)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 *r = lrec + (size_t)i * LIGHT_REC_QUADS;
+    const unsigned b = light_weight_bits(r[3].w, r[4].w, r[5].w, r[0].w);
+    cum[i] = (env_u64)b;
+    if (b) atomicMax(max_bits, b);
+}
+__global__ __launch_bounds__(256) void k_light_quant(env_u64 *cum, int n, const unsigned *max_bits)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    cum[i] = (env_u64)light_weight_q((unsigned)cum[i], light_weight_emax(*max_bits));
+}
+__global__ void k_light_head(env_u64 *head, const env_u64 *cum, int n, float u)
+{
+    const unsigned max_bits = ((const unsigned *)head)[4];
+    head[0] = cum[n - 1];
+    ((float *)head)[2] = u; ((int *)head)[3] = light_weight_emax(max_bits);
+}
+__global__ __launch_bounds__(256) void k_light_phit(SceneView s, float4 *shade_rec, int on)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= s.light_count) return;
+    const int prim = s.light[i];
+    if (prim < 0 || prim >= s.n) return;
+    float P = 0.0f;
+    if (on) { const LightTable t = light_table(s); P = light_choice_P(t.cum[i] - (i > 0 ? t.cum[i - 1] : 0ull), t.total, t.u, s.light_count); }
+    float4 *r = shade_rec + (size_t)prim * 8;
+    if (s.primitive[(size_t)prim * PRI_VEC] == PRIMITIVE_TRI) r[4].w = P; else r[2].x = P;
+}
+
+int light_table_sync(tirt_ctx *c)
+{
+    bool rebuilt = false;
+    if (!c->light_tab_valid) {
+        c->light_tab_total = 0ull; c->light_tab_emax = 0;
+        if (light_power_wanted(c)) {
+            const int n = c->light_count;
+            env_u64 *head = (env_u64 *)((char *)c->light_rec.p + light_table_offset(n)), *cum = head + LIGHT_TABLE_HEAD / 8;
+            TIRT_HIP(hipMemsetAsync(head, 0, LIGHT_TABLE_HEAD, c->stream));
+            hipLaunchKernelGGL(k_light_weights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->light_rec.as<float4>(), n, cum, (unsigned *)head + 4);
+            hipLaunchKernelGGL(k_light_quant, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, cum, n, (const unsigned *)head + 4);
+            hipLaunchKernelGGL(k_env_scan, dim3(1), dim3(256), 0, c->stream, cum, n, (env_u64 *)nullptr, (size_t)0);
+            hipLaunchKernelGGL(k_light_head, dim3(1), dim3(1), 0, c->stream, head, cum, n, c->light_uniform_share);
+            TIRT_HIP(hipGetLastError());
+            env_u64 h[2] = {0ull, 0ull};
+            TIRT_HIP(hipMemcpyAsync(h, head, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+            TIRT_HIP(hipStreamSynchronize(c->stream));
+            c->light_tab_total = h[0]; c->light_tab_emax = (int)(h[1] >> 32);
+        }
+        c->light_tab_valid = true;
+        rebuilt = true;
+    }
+    const bool want = light_power_active(c);
+    if (c->light_count > 0 && ((want && (rebuilt || !c->light_phit_written)) || (!want && c->light_phit_written))) {
+        hipLaunchKernelGGL(k_light_phit, dim3((unsigned)((c->light_count + 255) / 256)), dim3(256), 0, c->stream, scene_view(c), c->shade_rec.as<float4>(), want ? 1 : 0);
+        TIRT_HIP(hipGetLastError());
+        c->light_phit_written = want;
+    }
+    return TIRT_OK;
+}
+
+// the rule of light_table_sync on host tables: does an entry of the list have a weight that takes part (get_prim_area's expressions, Scene.py:324-350)
+bool light_table_exists_host(const float *material, int nm, const int32_t *primitive, int n, const float *shape, int ns, const float *vertex, int nv, const int32_t *light, int light_count)
+{
+    for (int i = 0; i < light_count; i++) {
+        if (light[i] < 0 || light[i] >= n) continue;
+        const int32_t *pr = primitive + (size_t)light[i] * PRI_VEC;
+        if (pr[2] < 0 || pr[2] >= nm) continue;
+        const float *m = material + (size_t)pr[2] * MAT_VEC;
+        float area = 0.0f;
+        if (pr[0] == PRIMITIVE_TRI) {
+            if (pr[1] < 0 || pr[1] + 2 >= nv) continue;
+            const float *p1 = vertex + (size_t)pr[1] * VER_VEC, *p2 = p1 + VER_VEC, *p3 = p2 + VER_VEC;
+            float len[3];
+            const float *ea[3] = {p1, p1, p3}, *eb[3] = {p2, p3, p2};
+            for (int k = 0; k < 3; k++) {
+                const float x = ea[k][0] - eb[k][0], y = ea[k][1] - eb[k][1], z = ea[k][2] - eb[k][2];
+                len[k] = tm_sqrt((x * x + y * y) + z * z);
+            }
+            const float sum = (len[0] + len[1] + len[2]) * 0.5f;
+            area = tm_sqrt(sum * (sum - len[0]) * (sum - len[1]) * (sum - len[2]));
+        } else {
+            if (pr[1] < 0 || pr[1] >= ns) continue;
+            const float *sh = shape + (size_t)pr[1] * SHA_VEC;
+            const int st = (int)sh[0];
+            if (st == SHAPE_SPHERE || st == SHAPE_SPOT || st == SHAPE_LASER) area = sh[4] * sh[4] * PI_SCENE;
+        }
+        if (light_weight_bits(m[2], m[3], m[4], area)) return true;
+    }
+    return false;
+}
+
+int light_table_download(tirt_ctx *c, uint32_t *q, uint64_t *prefix, float *P, int32_t info[4])
+{
+    TIRT_REQUIRE(info, "tirt_light_table_download: null info");
+    if (c->n >= 1 && ensure_shade_records(c)) return TIRT_ERR_HIP;
+    const bool built = c->n >= 1 && light_power_wanted(c);
+    info[0] = c->light_count; info[1] = c->light_tab_emax; info[2] = c->n >= 1 && light_power_active(c) ? 1 : 0; info[3] = built ? 1 : 0;
+    if (!built || !(q || prefix || P)) return TIRT_OK;
+    const int n = c->light_count;
+    std::vector<uint64_t> cum((size_t)n);
+    TIRT_HIP(hipMemcpyAsync(cum.data(), (const char *)c->light_rec.p + light_table_offset(n) + LIGHT_TABLE_HEAD, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < n; i++) {
+        const uint64_t qi = cum[(size_t)i] - (i ? cum[(size_t)i - 1] : 0ull);
+        if (q) q[i] = (uint32_t)qi;
+        if (prefix) prefix[i] = cum[(size_t)i];
+        if (P) P[i] = c->light_tab_total ? light_choice_P(qi, c->light_tab_total, c->light_uniform_share, n) : 0.0f;
+    }
+    return TIRT_OK;
+}
+
+// ---- known-answer entry (tirt_kat_light_pick): light_pick of tirt_device.h, the function shade_path calls, row i on thread i ----
+__global__ void k_kat_light_pick(SceneView sc, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    float P;
+    const int i = light_pick(light_table(sc), sc.light_count, in[(size_t)r * in_stride], P);
+    float *o = out + (size_t)r * out_stride;
+    o[0] = __int_as_float(i); o[1] = P;
+}
+
+int kat_light_pick(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    TIRT_REQUIRE(c->n >= 1, "tirt_kat_light_pick: no scene");
+    for (int i = 0; i < n; i++) {
+        const float r = in[(size_t)i * in_stride];
+        TIRT_REQUIRE(r >= 0.0f && r <= 1.0f, "tirt_kat_light_pick: row " + std::to_string(i) + ": a random outside [0, 1]");
+    }
+    if (sync_all(c) || ensure_shade_records(c)) return TIRT_ERR_HIP;
+    TIRT_REQUIRE(light_power_active(c), "tirt_kat_light_pick: no table (tirt_light_sampling mode 1, triangle and sphere emitters only, total > 0)");
+    if (n == 0) return TIRT_OK;
+    return kat_round_trip(c, "tirt_kat_light_pick", {{in, kat_row_bytes(n, in_stride)}}, out, kat_row_bytes(n, out_stride), [&](const void *const *din, void *dout) {
+        hipLaunchKernelGGL(k_kat_light_pick, dim3((n + 63) / 64), dim3(64), 0, c->stream, scene_view(c), (const float *)din[0], in_stride, (float *)dout, out_stride, n);
+    });
+}
+
 }  // namespace tirt

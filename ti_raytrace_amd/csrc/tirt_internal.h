@@ -334,6 +334,11 @@ struct tirt_ctx {
     // the texel format of `env`: 0 = 8 bits per channel (tirt_env_upload), 1 = RGBE8 (tirt_env_upload_hdr); env_emax = the largest exponent byte among the RGBE8
     // texels with a mantissa (0: none, or format 0), the scale of the sampling table.  Bit SF_ENV_HDR is derived (env_hdr_active), never stored in shade_features
     int env_format = 0, env_emax = 0;
+    // emitters chosen by power (tirt_envsample.hip, light_table_sync): the mode and uniform share of tirt_light_sampling; light_tab_valid = the table behind the light
+    // records is the one of the present records and switch (rebuilt with them, lazily); light_tab_total / light_tab_emax = its total and exponent (0: no table);
+    // light_phit_written = the spare words of the emitters' shading records hold their P.  Bit SF_LIGHT_POWER is derived (light_power_active), never stored in shade_features
+    int light_sample_mode = 0; float light_uniform_share = 0.0f; bool light_tab_valid = false, light_phit_written = false;
+    unsigned long long light_tab_total = 0ull; int light_tab_emax = 0;
     int shade_specialize = 1;                      // option "shade_specialize": 0 = the generic kernel for every scene (A/B and parity switch)
 
     // LBVH (accel/LBvh.py fields)
@@ -562,6 +567,13 @@ inline bool env_hdr_active(const tirt_ctx *c) { return c->env_format == 1 && (c-
 int env_hdr_check(const char *fn, const int32_t *rgbe, int w, int h, int *e_max);      // TIRT_ERR_ARG for a texel with E == 0 and a mantissa (its index in the text); e_max as tirt_ctx::env_emax
 bool env_table_exists_host_hdr(const int32_t *env, int w, int h, float power, int e_max);
 int kat_env_lookup(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n);
+// emitters chosen by power (include/tirt.h, "Choosing emitters by power"; tirt_envsample.hip)
+inline bool light_power_wanted(const tirt_ctx *c) { return c->light_sample_mode == 1 && c->light_count > 0 && (c->shade_features & (SF_LIGHT_SPOT_LASER | SF_LIGHT_OTHER)) == 0u; }
+inline bool light_power_active(const tirt_ctx *c) { return light_power_wanted(c) && c->light_tab_valid && c->light_tab_total > 0ull; }      // (after ensure_shade_records)
+int light_table_sync(tirt_ctx *c);             // the tail of ensure_shade_records: the table behind fresh light records, P into (or out of) the emitters' shading records
+int light_table_download(tirt_ctx *c, uint32_t *q, uint64_t *prefix, float *P, int32_t info[4]);
+int kat_light_pick(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n);
+bool light_table_exists_host(const float *material, int nm, const int32_t *primitive, int n, const float *shape, int ns, const float *vertex, int nv, const int32_t *light, int light_count);
 int sync_all(tirt_ctx *c);
 int flush_pending(tirt_ctx *c);
 bool kat_shade_step_has_inst(unsigned feat);      // tirt_render.hip: is `feat` the word of an instantiation of k_shade

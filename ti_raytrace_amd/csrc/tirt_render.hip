@@ -45,6 +45,9 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
     constexpr bool ENV_NEE = (FEAT & SF_ENV_SAMPLE) != 0u;
     // an RGBE8 environment (SF_ENV_HDR instantiations only; include/tirt.h, "HDR environment"): the two lookups below decode linear texels, no srgb_to_lrgb
     constexpr bool ENV_HDR = (FEAT & SF_ENV_HDR) != 0u;
+    // emitters chosen by power (SF_LIGHT_POWER instantiations only; include/tirt.h, "Choosing emitters by power"): the entry and its P come from the table behind the light
+    // records, an emitter hit reads the P of its entry from the spare word of its shading record
+    constexpr bool LIGHT_POW = (FEAT & SF_LIGHT_POWER) != 0u;
     [[maybe_unused]] float p_env = 0.0f;
     if constexpr (ENV_NEE) p_env = sc.light_count == 0 ? 1.0f : env_table(sc).share;
     if (t < INF_VALUE) {
@@ -68,6 +71,7 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
             } else {
                 const float area = h.area * (float)sc.light_count;              // get_prim_area of the emitter, from its shading record
                 float light_pdf = (t * t) / (area * fCosTheta);
+                if constexpr (LIGHT_POW) light_pdf = (t * t) * (shade_rec_phit(sc.shade_rec, prim_id) / h.area) / fCosTheta;
                 if constexpr (ENV_NEE) light_pdf = light_pdf * (1.0f - p_env);
                 radiance = radiance + (throughout * power_heuristic(brdf_pdf, light_pdf)) * mat_color;
             }
@@ -149,17 +153,20 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
                 if constexpr (ENV_NEE) r_light = (r_light - p_env) / (1.0f - p_env);
                 int lidx = (int)(r_light * (float)sc.light_count);
                 if (lidx >= sc.light_count) lidx = sc.light_count - 1;
+                [[maybe_unused]] float P_light = 0.0f;
+                if constexpr (LIGHT_POW) lidx = light_pick(light_table(sc), sc.light_count, r_light, P_light);
                 const float ra = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LA);
                 const float rb = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LB);
                 v3 light_pos, light_normal;
                 // the emitter's area, choice pdf, emission and the edges of its sampled point: per-light record (tirt_device.h, k_light_records)
-                const LightRec lr = light_sample_rec<FEAT>(sc.light_rec, lidx, ra, rb, light_pos, light_normal);
-                const float light_choice_pdf = lr.choice_pdf;
+                // (chosen by power: the list holds triangles and spheres only, the other kinds are not compiled)
+                const LightRec lr = light_sample_rec<LIGHT_POW ? (FEAT & ~(SF_LIGHT_SPOT_LASER | SF_LIGHT_OTHER)) : FEAT>(sc.light_rec, lidx, ra, rb, light_pos, light_normal);
+                const float light_choice_pdf = LIGHT_POW ? P_light / lr.area : lr.choice_pdf;
                 light_normal = normalized(light_normal);
                 v3 light_dir = h.pos - light_pos;
                 const float light_dist = norm(light_dir);
                 light_dir = light_dir / light_dist;
-                const v3 light_emission = lr.emission * light_shape_visible_rec<FEAT>(lr, light_dir, light_normal, light_dist);   // spot / laser (Scene.py:491-516)
+                const v3 light_emission = lr.emission * light_shape_visible_rec<LIGHT_POW ? (FEAT & ~SF_LIGHT_SPOT_LASER) : FEAT>(lr, light_dir, light_normal, light_dist);   // spot / laser (Scene.py:491-516)
                 const float NdotL_surface = dot(fnormal, light_dir);            // PT_RGB.py:101-109
                 const float NdotL_light = dot(light_normal, light_dir);
                 if ((NdotL_surface < 0.0f) & (NdotL_light > 0.0f)) {
@@ -285,6 +292,9 @@ __global__ void k_generate(PathSoA ps, CameraView cam, TileMap tm, int P, int S,
 #endif
 #ifndef SH_MIN_WAVES_ENV         // the instantiations with environment importance sampling (SF_ENV_SAMPLE): see DESIGN.md, "Importance sampling of the environment"
 #define SH_MIN_WAVES_ENV 4
+#endif
+#ifndef SH_MIN_WAVES_POWER       // the generic kernel's twin that chooses emitters by power (SF_LIGHT_POWER): see DESIGN.md, "Choosing emitters by power"
+#define SH_MIN_WAVES_POWER 4     // at 5 (96 VGPRs) it has 20 bytes of scratch where its sibling has none
 #endif
 #ifndef SH_MIN_WAVES_HDR         // the generic kernel's twin for an RGBE8 environment (SF_ENV_HDR): see DESIGN.md, "HDR environment"
 #define SH_MIN_WAVES_HDR 4       // at 5 (96 VGPRs) it has 12 bytes of scratch where its 8-bit sibling has none
@@ -693,6 +703,14 @@ template <unsigned F, int MW>
 constexpr ShadeInst shade_inst() { return {F, k_shade<F, MW>, k_shade<F, MW, true>}; }      // a table entry: the word, the kernel and its LIST variant
 static const ShadeInst SHADE_HDR_INST[] = {shade_inst<SF_I_HDR, SH_MIN_WAVES_HDR>(), shade_inst<SF_I_HDR_MAPS, SH_MIN_WAVES_MAPS>()};
 static const ShadeInst SHADE_ENV_HDR_INST[] = {shade_inst<SF_I_ENV_HDR, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_ENV_HDR_MAPS, SH_MIN_WAVES_ENV>()};
+// emitters chosen by power (SF_LIGHT_POWER; tirt_light_sampling): a twin of each of the eight kernels above that serve a generic scene -- without and with every texture slot,
+// the environment's light sample, an RGBE8 environment -- in a table of its own, indexed by those three bits.  Launch bounds: each twin's sibling's
+constexpr unsigned SF_P = SF_LIGHT_POWER;
+static const ShadeInst SHADE_POWER_INST[8] = {
+    shade_inst<SF_ALL | SF_P, SH_MIN_WAVES_POWER>(), shade_inst<SF_I_MAPS | SF_P, SH_MIN_WAVES_MAPS>(),
+    shade_inst<SF_I_ENV | SF_P, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_ENV_MAPS | SF_P, SH_MIN_WAVES_ENV>(),
+    shade_inst<SF_I_HDR | SF_P, SH_MIN_WAVES_HDR>(), shade_inst<SF_I_HDR_MAPS | SF_P, SH_MIN_WAVES_MAPS>(),
+    shade_inst<SF_I_ENV_HDR | SF_P, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_ENV_HDR_MAPS | SF_P, SH_MIN_WAVES_ENV>()};
 static const ShadeSpecInst SHADE_SPEC_INST[] = {
     {SF_I_SPHERE, k_shade_spec<SF_I_SPHERE>}, {SF_I_MESH, k_shade_spec<SF_I_MESH>}, {SF_ALL, k_shade_spec<SF_ALL>}};
 template <class T, size_t N>
@@ -705,6 +723,7 @@ static const T &pick_shade_inst(const T (&tab)[N], const tirt_ctx *c)
 }
 static const ShadeInst &pick_shade_rgb(const tirt_ctx *c)
 {
+    if (light_power_active(c)) return SHADE_POWER_INST[(env_hdr_active(c) ? 4 : 0) + (env_sample_active(c) ? 2 : 0) + ((c->shade_features & ~SF_ALL) ? 1 : 0)];
     if (env_hdr_active(c)) return (env_sample_active(c) ? SHADE_ENV_HDR_INST : SHADE_HDR_INST)[(c->shade_features & ~SF_ALL) ? 1 : 0];
     if (env_sample_active(c)) return SHADE_ENV_INST[(c->shade_features & ~SF_ALL) ? 1 : 0];
     return pick_shade_inst(SHADE_INST, c);
@@ -727,6 +746,13 @@ static_assert(sizeof(KAT_STEP_HDR_INST) / sizeof(KAT_STEP_HDR_INST[0]) == sizeof
 static const KatStepInst KAT_STEP_ENV_HDR_INST[] = {   // one per entry of SHADE_ENV_HDR_INST
     {SF_I_ENV_HDR, k_kat_shade_step<SF_I_ENV_HDR, SH_MIN_WAVES_ENV>}, {SF_I_ENV_HDR_MAPS, k_kat_shade_step<SF_I_ENV_HDR_MAPS, SH_MIN_WAVES_ENV>}};
 static_assert(sizeof(KAT_STEP_ENV_HDR_INST) / sizeof(KAT_STEP_ENV_HDR_INST[0]) == sizeof(SHADE_ENV_HDR_INST) / sizeof(SHADE_ENV_HDR_INST[0]), "one known-answer kernel per instantiation of k_shade");
+template <unsigned F, int MW>
+constexpr KatStepInst kat_inst() { return {F, k_kat_shade_step<F, MW>}; }
+static const KatStepInst KAT_STEP_POWER_INST[8] = {   // one per entry of SHADE_POWER_INST
+    kat_inst<SF_ALL | SF_P, SH_MIN_WAVES_POWER>(), kat_inst<SF_I_MAPS | SF_P, SH_MIN_WAVES_MAPS>(),
+    kat_inst<SF_I_ENV | SF_P, SH_MIN_WAVES_ENV>(), kat_inst<SF_I_ENV_MAPS | SF_P, SH_MIN_WAVES_ENV>(),
+    kat_inst<SF_I_HDR | SF_P, SH_MIN_WAVES_HDR>(), kat_inst<SF_I_HDR_MAPS | SF_P, SH_MIN_WAVES_MAPS>(),
+    kat_inst<SF_I_ENV_HDR | SF_P, SH_MIN_WAVES_ENV>(), kat_inst<SF_I_ENV_HDR_MAPS | SF_P, SH_MIN_WAVES_ENV>()};
 
 static kat_step_fn_t kat_step_inst(unsigned feat)
 {
@@ -734,6 +760,7 @@ static kat_step_fn_t kat_step_inst(unsigned feat)
     for (const KatStepInst &k : KAT_STEP_ENV_INST) if (k.feat == feat) return k.fn;
     for (const KatStepInst &k : KAT_STEP_HDR_INST) if (k.feat == feat) return k.fn;
     for (const KatStepInst &k : KAT_STEP_ENV_HDR_INST) if (k.feat == feat) return k.fn;
+    for (const KatStepInst &k : KAT_STEP_POWER_INST) if (k.feat == feat) return k.fn;
     return nullptr;
 }
 bool kat_shade_step_has_inst(unsigned feat) { return kat_step_inst(feat) != nullptr; }
@@ -744,6 +771,10 @@ int kat_shade_step(tirt_ctx *c, unsigned feat, const float *in, int in_stride, f
     TIRT_REQUIRE((c->shade_features & ~feat) == 0u, "tirt_kat_shade_step: feat does not cover the scene's feature word (tirt_shade_features)");
     TIRT_REQUIRE(((feat & SF_ENV_HDR) != 0u) == env_hdr_active(c), "tirt_kat_shade_step: an instantiation with bit 2048 reads RGBE8 texels and one without it 8-bit texels: feat must carry the bit exactly when tirt_shade_features does");
     TIRT_REQUIRE(!(feat & SF_ENV_SAMPLE) || env_sample_active(c), "tirt_kat_shade_step: an instantiation with bit 1024 needs the environment's sampling table (tirt_env_sampling on, a lit environment)");
+    if (feat & SF_LIGHT_POWER) {                   // the table is built with the light records, lazily
+        if (sync_all(c) || ensure_shade_records(c)) return TIRT_ERR_HIP;
+        TIRT_REQUIRE(light_power_active(c), "tirt_kat_shade_step: an instantiation with bit 4096 needs the emitters' table (tirt_light_sampling mode 1, triangle and sphere emitters only, total > 0)");
+    }
     const kat_step_fn_t fn = kat_step_inst(feat);
     TIRT_REQUIRE(fn, "tirt_kat_shade_step: feat is not an instantiation of k_shade");
     TIRT_REQUIRE(!(feat & (SF_TEXTURE | SF_TEXTURE_PARAM)) || c->tex_count > 0, "tirt_kat_shade_step: the textured instantiation needs uploaded textures (tirt_texture_upload): without them no material row's slot is checked");

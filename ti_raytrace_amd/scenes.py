@@ -205,6 +205,48 @@ class sun_ground(Example.example):
         self.frame_camera()
 
 
+class lamp_and_embers(Example.example):
+    """No reference counterpart: a ground quad under one bright two-triangle lamp and ``n_embers`` small dim emissive triangles scattered above the ground -- the
+    case a uniform choice among the light list's entries handles worst: the lamp holds over 95 % of the emitted power (emission x area) and gets two entries in
+    ``n_embers + 2``.  ``light_sampling="power"`` (the default here) chooses emitters by power (include/tirt.h, "Choosing emitters by power");
+    ``"uniform"`` renders with the reference's estimator.  The ground is a rough metal, or a rough dielectric with ``metallic=0.0``."""
+
+    def __init__(self, imgSizeX, imgSizeY, sample_count, device_id=None, n_embers=254, metallic=1.0, light_sampling="power", lamp_emission=640.0, lamp_size=0.25,
+                 ember_emission=0.5, ember_size=0.04, ember_seed=7, **pt_kwargs):
+        Example.example.__init__(self, imgSizeX, imgSizeY, sample_count, device_id)
+        ground = SCD.Material(); ground.type = SCD.MAT_DISNEY; ground.setMetal(metallic); ground.setRough(0.8); ground.setColor([0.7, 0.7, 0.7, 1.0]); ground.alebdoTex = -1
+        g = 2.0
+        self.scene.add_mesh(np.array([[(-g, 0, -g), (-g, 0, g), (g, 0, g)], [(-g, 0, -g), (g, 0, g), (g, 0, -g)]], np.float64), ground)
+
+        def emitter(e):
+            m = SCD.Material(); m.type = SCD.MAT_LIGHT; m.setColor([e, e, e]); m.alebdoTex = -1
+            return m
+        # the lamp: lamp_size x lamp_size at height 2, facing down -- small and bright, so that BSDF sampling seldom finds it (area 1 / 16, power 40: the embers
+        # below hold n * 0.5 * 0.0008 = 0.1 at the default 254)
+        a = 0.5 * float(lamp_size)
+        self.scene.add_mesh(np.array([[(-a, 2.0, -a), (a, 2.0, a), (-a, 2.0, a)], [(-a, 2.0, -a), (a, 2.0, -a), (a, 2.0, a)]], np.float64), emitter(lamp_emission))
+        # the embers: right triangles of leg ember_size in horizontal planes, facing up and down alike (an emitter radiates from both faces)
+        if n_embers > 0:
+            u = splitmix64_unit(ember_seed, 3 * n_embers).reshape(n_embers, 3)
+            c = np.stack([u[:, 0] * 3.0 - 1.5, 0.1 + u[:, 1] * 0.8, u[:, 2] * 3.0 - 1.5], axis=1)
+            s = float(ember_size)
+            tri = np.stack([c, c + np.array([s, 0.0, 0.0]), c + np.array([0.0, 0.0, s])], axis=1)
+            self.scene.add_mesh(tri, emitter(ember_emission))
+        self.integrator = PT_RGB.PathTrace(imgSizeX, imgSizeY, self.cam, self.scene, 64, light_sampling=light_sampling, **pt_kwargs)
+
+    def frame_camera(self, scale_factor=0.6):
+        # at the ground's centre, from below the lamp's height: the film shows the lit ground and the embers, never the lamp itself (a pixel on the lamp's edge
+        # would carry more variance than all the light samples of the film together)
+        self.cam.scale = 5.0 * scale_factor
+        self.cam.set_target(0.0, 0.0, 0.0)
+        self.cam.set_view_point(1.96, 0.6, 0.0, self.cam.scale)
+
+    def build_scene(self):
+        Example.example.build_scene(self)
+        self.scene.total_area()
+        self.frame_camera()
+
+
 # ---- synthetic scene -------------------------------------------------------------------------
 _GOLDEN = np.uint64(0x9E3779B97F4A7C15)
 
