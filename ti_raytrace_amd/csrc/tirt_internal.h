@@ -229,9 +229,10 @@ TD bool trace_leaf_step(const BvhView &b, const RayCtx &r, const bool par, const
 struct PathSoA {
     float *ox, *oy, *oz, *dx, *dy, *dz;          // current ray
     float *tr, *tg, *tb;                         // throughput
-    float *rr, *rg, *rb;                         // radiance so far
-    float *brdf_pdf; uint32_t *flags;           // bit0 perfect_spec
-    int *slot;                                   // path id = frame_in_batch * P + local pixel
+    float *rr, *rg, *rb;                         // PT_Spec: radiance so far (PT_RGB does not touch them: its radiance so far is PathState::fr / fg / fb[slot])
+    float *brdf_pdf; uint32_t *flags;           // flags: PT_Spec's fourth radiance word (PT_RGB does not touch it: perfect_spec is bit 31 of `slot`)
+    int *slot;                                   // path id = frame_in_batch * P + local pixel: 0 <= id < 2^31, so bit 31 of the stored word is free and PT_RGB
+                                                 // keeps the path's perfect_spec there -- whoever reads a stored slot of a PT_RGB batch masks it (k_shade)
 };
 struct PathState {
     PathSoA st[2];                               // ping-pong: bounce b reads st[b&1], writes st[(b+1)&1]
@@ -239,9 +240,9 @@ struct PathState {
     float *sox, *soy, *soz, *sdx, *sdy, *sdz;    // shadow rays (dense, origin on the light)
     float *scr, *scg, *scb; int *sprim;         // contribution if sprim is the closest hit
     float *sdist;                               // distance light point -> shaded point
-    int *sdst;                                   // where the contribution goes: >= 0 index in the next
-                                                 // PathSoA (path continues), < 0: ~slot in the final radiance
-    float *fr, *fg, *fb;                         // final radiance per path id (read by k_film)
+    int *sdst;                                   // where the contribution goes: >= 0 index in the next PathSoA (PT_Spec, path continues),
+                                                 // < 0: ~slot in fr / fg / fb (PT_RGB always: the clean slot, without the flag bit)
+    float *fr, *fg, *fb;                         // radiance per path id (read by k_film).  PT_RGB: the path's accumulator from bounce 0 on; PT_Spec: stored when the path ends
     float *scw, *fw;                             // PT_Spec: fourth hero-wavelength component of the shadow-ray contribution / of the final radiance
 };
 

@@ -14,6 +14,12 @@
 //   k_trace<shadow>   NEE visibility, adds the stored contribution  Scene.py:671-699, PT_RGB.py:104-109
 //   k_film            running-mean film update                      integrator/PT_RGB.py:134-136
 //
+// PT_RGB keeps a path's radiance in one place from bounce 0 on: PathState::fr / fg / fb[slot], which k_film reads.  k_shade of bounce 0 stores every path's first
+// value there (slot == q: coalesced); at a later bounce only a path with something to add -- an emitter hit, a miss under a lit environment -- reads, adds and
+// writes its three words, and every shadow ray carries ~slot, so k_trace's write-back adds the light sample's contribution there too.  Per path the additions
+// come in the reference's order: a lane's launches are on one stream, and within a launch a path has one writer.  A path that goes on moves 11 words from one
+// PathSoA to the other (ray, throughput, brdf_pdf, and the slot word with perfect_spec in its bit 31); the rr / rg / rb / flags arrays are PT_Spec's.
+//
 // k_trace and its launchers (the walk, its two visiting rules, the tie rule) are in tirt_trace.hip; this file holds the shading kernels, the tables of
 // their instantiations and the scheduler that submits a batch's launches (pt_render), in that order.
 #include "tirt_trace.h"
@@ -23,9 +29,11 @@ namespace tirt {
 
 // One path at one bounce: what integrator/PT_RGB.py:66-132 does between the closest hit and the next one -- emission (with MIS), the glass / disney
 // branch, the NEE sample (its shadow ray and the contribution it adds IF the ray arrives), the next ray and the throughput, the environment
-// for a miss.  The body of k_shade, kept apart from its queue handling.  `radiance`, `throughout`, `brdf_pdf`, `perfect_spec` are the path's state coming in; `radiance` is updated in place.
+// for a miss.  The body of k_shade, kept apart from its queue handling.  `throughout`, `brdf_pdf`, `perfect_spec` are the path's state coming in.  The radiance so far is
+// not: the step reports the term it adds to it (`adds`, `add`: an emitter hit or a miss; a Disney or glass hit adds nothing) and the caller performs `radiance + add`.
 struct ShadeStep {
-    bool want_next = false, want_shadow = false, shaded = false;
+    bool want_next = false, want_shadow = false, shaded = false, adds = false;
+    v3 add = V(0.0f, 0.0f, 0.0f);
     v3 next_o = V(0.0f, 0.0f, 0.0f), next_d = next_o, next_thr = next_o, sh_o = next_o, sh_d = next_o, sh_c = next_o;
     float next_pdf = 0.0f, sh_dist = 0.0f; int next_spec = 0, sh_expect = -2;
 };
@@ -34,7 +42,7 @@ struct ShadeStep {
 // LIST: the batch's local pixels are a pixel set's list (mapped_pixel, tirt_internal.h) -- the pixel is the random numbers' and nothing else here.
 template <unsigned FEAT, bool LIST = false>
 TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame_begin, uint32_t seed, int bounce, int last_bounce, int slot,
-                   const v3 origin, const v3 direction, const float4 hrec, v3 throughout, v3 &radiance, float brdf_pdf, int perfect_spec, ShadeStep &s)
+                   const v3 origin, const v3 direction, const float4 hrec, v3 throughout, float brdf_pdf, int perfect_spec, ShadeStep &s)
 {
     int f, k; slot_to_frame_pixel(tm, P, slot, f, k);
     const uint32_t pixel = (uint32_t)mapped_pixel<LIST>(tm, k);
@@ -66,14 +74,15 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
         const int mat_type = (int)m[0];
         if (mat_type == MAT_LIGHT) {                                           // PT_RGB.py:72-81
             const float fCosTheta = absf(dot(direction, h.gnor));
+            s.adds = true;
             if (perfect_spec == 1) {
-                radiance = radiance + throughout * mat_color;
+                s.add = throughout * mat_color;
             } else {
                 const float area = h.area * (float)sc.light_count;              // get_prim_area of the emitter, from its shading record
                 float light_pdf = (t * t) / (area * fCosTheta);
                 if constexpr (LIGHT_POW) light_pdf = (t * t) * (shade_rec_phit(sc.shade_rec, prim_id) / h.area) / fCosTheta;
                 if constexpr (ENV_NEE) light_pdf = light_pdf * (1.0f - p_env);
-                radiance = radiance + (throughout * power_heuristic(brdf_pdf, light_pdf)) * mat_color;
+                s.add = (throughout * power_heuristic(brdf_pdf, light_pdf)) * mat_color;
             }
         } else {
             s.shaded = true;
@@ -219,7 +228,7 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
         // black environment (PT_RGB.py:127-132 with env_power == 0): for a finite direction the lookup returns a
         // finite e >= 0, so (e * throughput) * 0 is +-0 with throughput's sign, or NaN where throughput is not
         // finite -- exactly throughput * env_power, without the two atan2, four texel fetches and three pow
-        radiance = radiance + throughout * sc.env_power;
+        s.adds = true; s.add = throughout * sc.env_power;
     } else if (!(FEAT & SF_ENV)) {
         // a direction that is not finite under a black environment (env_power == 0 and every texel 0: the SF_ENV bit is clear).  The lookup below then
         // fetches zeros whatever the texel indices are, and mixes them with the weights x - floor(x) of the clamped coordinates: 0 where tx and ty are
@@ -230,19 +239,20 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
         const bool e_nan = direction.x != direction.x || direction.y != direction.y || direction.z != direction.z ||
                            (absf(direction.x) > big && absf(direction.z) > big) || (absf(direction.y) > big && dis > big);
         const float e1 = e_nan ? tm_nan() : 0.0f;
-        radiance = radiance + (V(e1, e1, e1) * throughout) * sc.env_power;
+        s.adds = true; s.add = (V(e1, e1, e1) * throughout) * sc.env_power;
     } else {                                                                     // PT_RGB.py:127-132
         const float dis = tm_sqrt(direction.x * direction.x + direction.z * direction.z);
         const float tx = (tm_atan2(direction.z, direction.x) + PI_SCENE) / PI_SCENE / 2.0f;
         const float ty = tm_atan2(direction.y, dis) / PI_SCENE + 0.5f;
         const v3 e = env_lookup<ENV_HDR>(sc.env, sc.env_w, sc.env_h, tx, ty);
+        s.adds = true;
         if constexpr (ENV_NEE) {
             // MIS against the environment sample the previous vertex could have taken: weight 1 behind a camera or glass vertex (no NEE there)
             float w = 1.0f;
             if (perfect_spec != 1) w = power_heuristic(brdf_pdf, p_env * env_pdf(env_table(sc), sc.env_w, sc.env_h, direction).pdf);
-            radiance = radiance + ((e * throughout) * sc.env_power) * w;
+            s.add = ((e * throughout) * sc.env_power) * w;
         } else
-        radiance = radiance + (e * throughout) * sc.env_power;
+        s.add = (e * throughout) * sc.env_power;
     }
 }
 
@@ -288,16 +298,16 @@ __global__ void k_generate(PathSoA ps, CameraView cam, TileMap tm, int P, int S,
 #define SH_MIN_WAVES_NARROW 5
 #endif
 #ifndef SH_MIN_WAVES_MAPS        // the instantiation with every texture slot (SF_TEXTURE_PARAM): see DESIGN.md, "Roughness, metallic and normal-map textures"
-#define SH_MIN_WAVES_MAPS 4      // at 5 (96 VGPRs) it has 28 bytes of scratch, at 4 112 VGPRs (108 LIST) and none
+#define SH_MIN_WAVES_MAPS 4      // at 5 (96 VGPRs) it has 20 bytes of scratch (12 LIST), at 4 110 VGPRs (107 LIST) and none
 #endif
 #ifndef SH_MIN_WAVES_ENV         // the instantiations with environment importance sampling (SF_ENV_SAMPLE): see DESIGN.md, "Importance sampling of the environment"
 #define SH_MIN_WAVES_ENV 4
 #endif
 #ifndef SH_MIN_WAVES_POWER       // the generic kernel's twin that chooses emitters by power (SF_LIGHT_POWER): see DESIGN.md, "Choosing emitters by power"
-#define SH_MIN_WAVES_POWER 4     // at 5 (96 VGPRs) it has 20 bytes of scratch where its sibling has none
+#define SH_MIN_WAVES_POWER 4     // at 5 (96 VGPRs) it has 12 bytes of scratch where its sibling has none; its RGBE8 twin (SF_ENV_HDR | SF_LIGHT_POWER) likewise
 #endif
 #ifndef SH_MIN_WAVES_HDR         // the generic kernel's twin for an RGBE8 environment (SF_ENV_HDR): see DESIGN.md, "HDR environment"
-#define SH_MIN_WAVES_HDR 4       // at 5 (96 VGPRs) it has 12 bytes of scratch where its 8-bit sibling has none
+#define SH_MIN_WAVES_HDR 5       // as its 8-bit sibling: no scratch at 5 (96 VGPRs) since the radiance is no longer live across shade_path (it had 12 bytes, and sat at 4)
 #endif
 // The 78 array pointers of the path state are the first kernel argument and are never read from it directly: each of the three places
 // that needs some of them (a path's state in, the survivor's state out, the shadow ray out) reads those from the kernel-argument segment in
@@ -324,39 +334,49 @@ __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_shade(ShadeArgs paths_i
     unsigned long long n_shaded = 0;
     for (int it = 0; it < rounds; it++) {
         const int q = it * total + blockIdx.x * blockDim.x + threadIdx.x;
-        bool live = q < count, want_next = false, want_shadow = false;
+        bool live = q < count, want_next = false, want_shadow = false, adds = false;
         int slot = 0;
+        // `radiance`: at bounce 0 the path's radiance after this step (0 + the step's term), at a later bounce the term alone -- the radiance so far is fr / fg / fb[slot]
         v3 radiance = V(0.0f, 0.0f, 0.0f), next_o = radiance, next_d = radiance, next_thr = radiance;
         v3 sh_o = radiance, sh_d = radiance, sh_c = radiance;
         float next_pdf = 0.0f, sh_dist = 0.0f; int next_spec = 0, sh_expect = -2;
+        const bool first = bounce == 0;              // camera rays: constant state, see k_generate
         if (live) {
-            const bool first = bounce == 0;          // camera rays: constant state, see k_generate
             SH_COLD(ca);
-            const int *const c_slot = ca->in.slot; const uint32_t *const c_flags = ca->in.flags; const float4 *const c_hit = ca->ps.hit;
+            const int *const c_slot = ca->in.slot; const float4 *const c_hit = ca->ps.hit;
             const float *const c_ox = ca->in.ox, *const c_oy = ca->in.oy, *const c_oz = ca->in.oz, *const c_dx = ca->in.dx, *const c_dy = ca->in.dy, *const c_dz = ca->in.dz;
-            const float *const c_tr = ca->in.tr, *const c_tg = ca->in.tg, *const c_tb = ca->in.tb, *const c_rr = ca->in.rr, *const c_rg = ca->in.rg, *const c_rb = ca->in.rb;
+            const float *const c_tr = ca->in.tr, *const c_tg = ca->in.tg, *const c_tb = ca->in.tb;
             const float *const c_pdf = ca->in.brdf_pdf;
-            asm volatile("" :: "s"(c_slot), "s"(c_flags), "s"(c_hit), "s"(c_ox), "s"(c_oy), "s"(c_oz), "s"(c_dx), "s"(c_dy), "s"(c_dz), "s"(c_tr), "s"(c_tg), "s"(c_tb),
-                         "s"(c_rr), "s"(c_rg), "s"(c_rb), "s"(c_pdf));
-            slot = first ? q : SH_LD(c_slot[q]);
+            asm volatile("" :: "s"(c_slot), "s"(c_hit), "s"(c_ox), "s"(c_oy), "s"(c_oz), "s"(c_dx), "s"(c_dy), "s"(c_dz), "s"(c_tr), "s"(c_tg), "s"(c_tb), "s"(c_pdf));
+            // the stored slot word: the path id (>= 0) with perfect_spec in bit 31 (PathSoA::slot)
+            const uint32_t slot_word = first ? (uint32_t)q | 0x80000000u : (uint32_t)SH_LD(c_slot[q]);
+            slot = (int)(slot_word & 0x7fffffffu);
             const v3 origin = first ? eye : V(SH_LD(c_ox[q]), SH_LD(c_oy[q]), SH_LD(c_oz[q]));
             const v3 direction = V(SH_LD(c_dx[q]), SH_LD(c_dy[q]), SH_LD(c_dz[q]));
             typedef float f4nt__ __attribute__((ext_vector_type(4)));
             const f4nt__ hnt__ = __builtin_nontemporal_load((const f4nt__ *)&c_hit[q]);
             const float4 hrec = make_float4(hnt__.x, hnt__.y, hnt__.z, hnt__.w);
             v3 throughout = first ? V(1.0f, 1.0f, 1.0f) : V(SH_LD(c_tr[q]), SH_LD(c_tg[q]), SH_LD(c_tb[q]));
-            radiance = first ? V(0.0f, 0.0f, 0.0f) : V(SH_LD(c_rr[q]), SH_LD(c_rg[q]), SH_LD(c_rb[q]));
             float brdf_pdf = first ? 1.0f : SH_LD(c_pdf[q]);
-            int perfect_spec = first ? 1 : (int)(SH_LD(c_flags[q]) & 1u);
+            int perfect_spec = (int)(slot_word >> 31);
             ShadeStep ss;
-            shade_path<FEAT, LIST>(sc, tm, P, frame_begin, seed, bounce, last_bounce, slot, origin, direction, hrec, throughout, radiance, brdf_pdf, perfect_spec, ss);
+            shade_path<FEAT, LIST>(sc, tm, P, frame_begin, seed, bounce, last_bounce, slot, origin, direction, hrec, throughout, brdf_pdf, perfect_spec, ss);
             want_next = ss.want_next; want_shadow = ss.want_shadow; if (ss.shaded) n_shaded++;
             next_o = ss.next_o; next_d = ss.next_d; next_thr = ss.next_thr; next_pdf = ss.next_pdf; next_spec = ss.next_spec;
             sh_o = ss.sh_o; sh_d = ss.sh_d; sh_c = ss.sh_c; sh_expect = ss.sh_expect; sh_dist = ss.sh_dist;
+            if (first) {
+                if (ss.adds) radiance = radiance + ss.add;       // 0 + term: the add stays, 0 + (-0) is +0
+            } else {
+                radiance = ss.add;
+                // A miss whose term is +-0 in every channel (a black environment, a finite throughput: every miss of such a scene) leaves the accumulator as it is,
+                // bit for bit: the accumulator is never -0 (it starts as 0 + x, and a sum is -0 only if both operands are), so acc + (+-0) == acc.  A NaN term
+                // compares unequal and is added.
+                const bool nothing = !(hrec.x < INF_VALUE) && ss.add.x == 0.0f && ss.add.y == 0.0f && ss.add.z == 0.0f;
+                adds = ss.adds && !nothing;
+            }
         }
-        // dense compaction: survivors go to consecutive indices of the other PathSoA, finished
-        // paths deposit their radiance in the per-path final array, shadow rays get their own
-        // dense list with the address their contribution must be added to
+        // dense compaction: survivors go to consecutive indices of the other PathSoA, shadow rays get their
+        // own dense list with the path whose radiance (fr / fg / fb[slot]) their contribution must be added to
         const int par = it & 1;
         const unsigned long long nmask = __ballot(want_next), smask = __ballot(want_shadow);
         if (lane == 0) s_wcnt[par][wid] = (unsigned)__popcll(nmask) | ((unsigned)__popcll(smask) << 16);
@@ -377,20 +397,22 @@ __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_shade(ShadeArgs paths_i
         if (want_next) {
             SH_COLD(ca);
             float *const o_ox = ca->out.ox, *const o_oy = ca->out.oy, *const o_oz = ca->out.oz, *const o_dx = ca->out.dx, *const o_dy = ca->out.dy, *const o_dz = ca->out.dz;
-            float *const o_tr = ca->out.tr, *const o_tg = ca->out.tg, *const o_tb = ca->out.tb, *const o_rr = ca->out.rr, *const o_rg = ca->out.rg, *const o_rb = ca->out.rb;
-            float *const o_pdf = ca->out.brdf_pdf; uint32_t *const o_flags = ca->out.flags; int *const o_slot = ca->out.slot;
-            asm volatile("" :: "s"(o_ox), "s"(o_oy), "s"(o_oz), "s"(o_dx), "s"(o_dy), "s"(o_dz), "s"(o_tr), "s"(o_tg), "s"(o_tb), "s"(o_rr), "s"(o_rg), "s"(o_rb),
-                         "s"(o_pdf), "s"(o_flags), "s"(o_slot));
+            float *const o_tr = ca->out.tr, *const o_tg = ca->out.tg, *const o_tb = ca->out.tb;
+            float *const o_pdf = ca->out.brdf_pdf; int *const o_slot = ca->out.slot;
+            asm volatile("" :: "s"(o_ox), "s"(o_oy), "s"(o_oz), "s"(o_dx), "s"(o_dy), "s"(o_dz), "s"(o_tr), "s"(o_tg), "s"(o_tb), "s"(o_pdf), "s"(o_slot));
             SH_ST(o_ox[qn], next_o.x); SH_ST(o_oy[qn], next_o.y); SH_ST(o_oz[qn], next_o.z);
             SH_ST(o_dx[qn], next_d.x); SH_ST(o_dy[qn], next_d.y); SH_ST(o_dz[qn], next_d.z);
             SH_ST(o_tr[qn], next_thr.x); SH_ST(o_tg[qn], next_thr.y); SH_ST(o_tb[qn], next_thr.z);
-            SH_ST(o_rr[qn], radiance.x); SH_ST(o_rg[qn], radiance.y); SH_ST(o_rb[qn], radiance.z);
-            SH_ST(o_pdf[qn], next_pdf); SH_ST(o_flags[qn], (uint32_t)next_spec); SH_ST(o_slot[qn], slot);
-        } else if (live) {
+            SH_ST(o_pdf[qn], next_pdf); SH_ST(o_slot[qn], (int)((uint32_t)slot | ((uint32_t)next_spec << 31)));
+        }
+        // the path's radiance lives in fr / fg / fb[slot] from bounce 0 on (k_trace's shadow write-back adds into it there: sdst below): every camera path stores
+        // its first value (slot == q: coalesced), a later bounce adds its term, if it has one, where the path's slot is; a path that ends has nothing left to store
+        if (first ? live : adds) {
             SH_COLD(ca);
             float *const f_r = ca->ps.fr, *const f_g = ca->ps.fg, *const f_b = ca->ps.fb;
             asm volatile("" :: "s"(f_r), "s"(f_g), "s"(f_b));
-            SH_ST(f_r[slot], radiance.x); SH_ST(f_g[slot], radiance.y); SH_ST(f_b[slot], radiance.z);
+            if (first) { SH_ST(f_r[slot], radiance.x); SH_ST(f_g[slot], radiance.y); SH_ST(f_b[slot], radiance.z); }
+            else { f_r[slot] = f_r[slot] + radiance.x; f_g[slot] = f_g[slot] + radiance.y; f_b[slot] = f_b[slot] + radiance.z; }
         }
         if (want_shadow) {
             SH_COLD(ca);
@@ -402,7 +424,7 @@ __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_shade(ShadeArgs paths_i
             SH_ST(s_dx[qs], sh_d.x); SH_ST(s_dy[qs], sh_d.y); SH_ST(s_dz[qs], sh_d.z);
             SH_ST(s_cr[qs], sh_c.x); SH_ST(s_cg[qs], sh_c.y); SH_ST(s_cb[qs], sh_c.z);
             SH_ST(s_prim[qs], sh_expect); SH_ST(s_dist[qs], sh_dist);
-            SH_ST(s_dst[qs], want_next ? qn : ~slot);
+            SH_ST(s_dst[qs], ~slot);           // always the per-path accumulator (k_trace's dst < 0 case), whether the path goes on or not
         }
     }
     // statistics: one global atomic per block (through LDS), not per wave -- same-address atomics retire at ~11 ns
@@ -662,7 +684,8 @@ __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_kat_shade_step(SceneVie
     v3 radiance = V(a[18], a[19], a[20]);
     ShadeStep ss;
     shade_path<FEAT>(sc, tm, 0x7fffffff, (uint32_t)__float_as_int(a[2]), (uint32_t)__float_as_int(a[0]), __float_as_int(a[3]), __float_as_int(a[4]) != 0, __float_as_int(a[1]),
-                     V(a[5], a[6], a[7]), V(a[8], a[9], a[10]), make_float4(a[11], a[12], a[13], a[14]), V(a[15], a[16], a[17]), radiance, a[21], __float_as_int(a[22]), ss);
+                     V(a[5], a[6], a[7]), V(a[8], a[9], a[10]), make_float4(a[11], a[12], a[13], a[14]), V(a[15], a[16], a[17]), a[21], __float_as_int(a[22]), ss);
+    if (ss.adds) radiance = radiance + ss.add;      // the plain add, whatever the term: a row's radiance may be -0, which k_shade's accumulator never is
     o[0] = radiance.x; o[1] = radiance.y; o[2] = radiance.z; o[3] = __int_as_float(ss.shaded ? 1 : 0); o[4] = __int_as_float(ss.want_next ? 1 : 0);
     o[5] = ss.next_o.x; o[6] = ss.next_o.y; o[7] = ss.next_o.z; o[8] = ss.next_d.x; o[9] = ss.next_d.y; o[10] = ss.next_d.z;
     o[11] = ss.next_thr.x; o[12] = ss.next_thr.y; o[13] = ss.next_thr.z; o[14] = ss.next_pdf; o[15] = __int_as_float(ss.next_spec); o[16] = __int_as_float(ss.want_shadow ? 1 : 0);
@@ -697,7 +720,7 @@ static const ShadeInst SHADE_ENV_INST[] = {
     {SF_I_ENV_MAPS, k_shade<SF_I_ENV_MAPS, SH_MIN_WAVES_ENV>, k_shade<SF_I_ENV_MAPS, SH_MIN_WAVES_ENV, true>}};
 // an RGBE8 environment that is lit (SF_ENV_HDR; tirt_env_upload_hdr): twins of the generic kernel and of the one with every texture slot, without and with the
 // environment's light sample, in tables of their own -- entry 0 an untextured scene's, entry 1 a textured one's.  Launch bounds: each twin's 8-bit sibling's, but for
-// the generic twin, which spills at 5 waves and has SH_MIN_WAVES_HDR ("HDR environment": no scratch at any of them)
+// the generic twin, which has SH_MIN_WAVES_HDR ("HDR environment": no scratch at any of them)
 constexpr unsigned SF_I_HDR = SF_ALL | SF_ENV_HDR, SF_I_HDR_MAPS = SF_I_MAPS | SF_ENV_HDR, SF_I_ENV_HDR = SF_I_ENV | SF_ENV_HDR, SF_I_ENV_HDR_MAPS = SF_I_ENV_MAPS | SF_ENV_HDR;
 template <unsigned F, int MW>
 constexpr ShadeInst shade_inst() { return {F, k_shade<F, MW>, k_shade<F, MW, true>}; }      // a table entry: the word, the kernel and its LIST variant
@@ -709,7 +732,7 @@ constexpr unsigned SF_P = SF_LIGHT_POWER;
 static const ShadeInst SHADE_POWER_INST[8] = {
     shade_inst<SF_ALL | SF_P, SH_MIN_WAVES_POWER>(), shade_inst<SF_I_MAPS | SF_P, SH_MIN_WAVES_MAPS>(),
     shade_inst<SF_I_ENV | SF_P, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_ENV_MAPS | SF_P, SH_MIN_WAVES_ENV>(),
-    shade_inst<SF_I_HDR | SF_P, SH_MIN_WAVES_HDR>(), shade_inst<SF_I_HDR_MAPS | SF_P, SH_MIN_WAVES_MAPS>(),
+    shade_inst<SF_I_HDR | SF_P, SH_MIN_WAVES_POWER>(), shade_inst<SF_I_HDR_MAPS | SF_P, SH_MIN_WAVES_MAPS>(),
     shade_inst<SF_I_ENV_HDR | SF_P, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_ENV_HDR_MAPS | SF_P, SH_MIN_WAVES_ENV>()};
 static const ShadeSpecInst SHADE_SPEC_INST[] = {
     {SF_I_SPHERE, k_shade_spec<SF_I_SPHERE>}, {SF_I_MESH, k_shade_spec<SF_I_MESH>}, {SF_ALL, k_shade_spec<SF_ALL>}};
@@ -751,7 +774,7 @@ constexpr KatStepInst kat_inst() { return {F, k_kat_shade_step<F, MW>}; }
 static const KatStepInst KAT_STEP_POWER_INST[8] = {   // one per entry of SHADE_POWER_INST
     kat_inst<SF_ALL | SF_P, SH_MIN_WAVES_POWER>(), kat_inst<SF_I_MAPS | SF_P, SH_MIN_WAVES_MAPS>(),
     kat_inst<SF_I_ENV | SF_P, SH_MIN_WAVES_ENV>(), kat_inst<SF_I_ENV_MAPS | SF_P, SH_MIN_WAVES_ENV>(),
-    kat_inst<SF_I_HDR | SF_P, SH_MIN_WAVES_HDR>(), kat_inst<SF_I_HDR_MAPS | SF_P, SH_MIN_WAVES_MAPS>(),
+    kat_inst<SF_I_HDR | SF_P, SH_MIN_WAVES_POWER>(), kat_inst<SF_I_HDR_MAPS | SF_P, SH_MIN_WAVES_MAPS>(),
     kat_inst<SF_I_ENV_HDR | SF_P, SH_MIN_WAVES_ENV>(), kat_inst<SF_I_ENV_HDR_MAPS | SF_P, SH_MIN_WAVES_ENV>()};
 
 static kat_step_fn_t kat_step_inst(unsigned feat)
@@ -973,8 +996,8 @@ static int submit_batch(tirt_ctx *c, const RenderCall &r, Lane &L, uint32_t f0, 
     const TraceArgs base = batch_trace_args(c, r, L);
     for (int b = 0; b < max_depth; b++) {
         const PathSoA &in = L.ps.st[b & 1], &out = L.ps.st[(b + 1) & 1];
-        // closest hits of bounce b, together with the NEE shadow rays of bounce b-1 (they add into
-        // `in`'s radiance, which nothing reads before shade(b)): one launch instead of two
+        // closest hits of bounce b, together with the NEE shadow rays of bounce b-1: one launch instead of two (PT_RGB: they add into fr / fg / fb[slot],
+        // which shade(b) adds to after them; PT_Spec: into `in`'s radiance, which nothing reads before shade(b) -- rr / rg / rb, rw below are PT_Spec's)
         TraceArgs a = base;
         a.dx = in.dx; a.dy = in.dy; a.dz = in.dz;
         if (b == 0) for (int k = 0; k < 3; k++) a.eye[k] = c->cam.eye[k];      // camera rays share their origin (ox stays nullptr)
