@@ -794,6 +794,51 @@ int tirt_query_occluded(tirt_ctx *ctx, const float *rays, int64_t nr, int64_t ra
                         const float *tmax, int64_t tmax_stride, float tmax_all,
                         int stack_size, int flags, uint8_t *out_occluded, void *stream);
 
+/* Closest point (no reference counterpart; csrc/tirt_closest_point.h / .hip): the nearest surface point of the scene to a query point p.
+ * Everything is fp32, every operation in the order written, no contraction; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ * D2(p, i), Q(p, i), u(p, i), v(p, i) of primitive i:
+ *   Triangle with positions a, b, c (Ericson, Real-Time Collision Detection, 5.1.5):
+ *     ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c;
+ *     d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp);
+ *     vc = d1*d4 - d3*d2, vb = d5*d2 - d1*d6, va = d3*d6 - d5*d4.  The first region whose test holds, in this order:
+ *       A   d1 <= 0 and d2 <= 0:                        Q = a (the vertex itself), (u, v) = (0, 0)
+ *       B   d3 >= 0 and d4 <= d3:                       Q = b, (u, v) = (1, 0)
+ *       AB  vc <= 0 and d1 >= 0 and d3 <= 0:            u = d1 / (d1 - d3), v = 0, Q = a + ab * u
+ *       C   d6 >= 0 and d5 <= d6:                       Q = c, (u, v) = (0, 1)
+ *       AC  vb <= 0 and d2 >= 0 and d6 <= 0:            v = d2 / (d2 - d6), u = 0, Q = a + ac * v
+ *       BC  va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0:  w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), Q = b + (c - b) * w, (u, v) = (1 - w, w)
+ *       interior otherwise:                             den = 1 / ((va + vb) + vc), u = vb * den, v = vc * den, Q = (a + ab * u) + ac * v
+ *     D2 = dot(p - Q, p - Q).  (u, v) is the hit record's convention, pos = a + u E1 + v E2: normals and uvs interpolate as for a hit.  A comparison
+ *     with a NaN is false (such a triangle falls through to the interior); a zero-area triangle yields whatever these expressions yield.
+ *   Analytic sphere (SHAPE_SPHERE) with centre c, radius r: pc = p - c, len = sqrt(dot(pc, pc)), d = |len - r| (x < 0 ? -x : x), D2 = d * d,
+ *     Q = c + pc * (r / len), and Q = c + (r, 0, 0) where len == 0; u = v = 0.  Spot and laser shapes have no surface and take no part.
+ * The answer for p with bound dmax: lim2 = dmax * dmax, formed once (dmax < 0 or NaN: nothing is found; +inf: no bound).  Among the primitives with
+ *   D2 <= lim2 the one with the smallest D2; at equal D2 bits the smallest primitive id.  A NaN D2 is never accepted, and neither is D2 = +inf: "nothing"
+ *   is prim = -1, d2 = +inf, point and uv 0 -- so a NaN or infinite coordinate of p finds nothing.  This is the minimum of a total order on (D2, prim):
+ *   it does not depend on the order of the visits, and the culled walk returns the bits of a scan over all primitives (the culling argument is in the
+ *   head of csrc/tirt_closest_point.hip).  Alpha cut-outs are ignored: a transparent texel is still surface.
+ * tirt_query_closest_point: device memory on the caller's stream with the plumbing of tirt_query_closest -- asynchronous, ordered after and before
+ *   `stream` by two events, no host sync, chunks of option "query_chunk_rays" (one launch each; it reads and writes the caller's arrays in place and
+ *   needs 0 bytes of scratch per query).  Row i of the points starts at points + i * point_stride floats; dmax[i * dmax_stride] per query, or dmax_all
+ *   for every query when dmax is NULL.  Each output may be NULL: out_d2[n], out_prim[n], out_point + i * point_out_stride = Q, out_uv + i * uv_stride =
+ *   (u, v), counts[n*2] = N_box (four per node visit), N_leaf (primitive tests) per query (8-byte aligned; only with TIRT_COUNT_NODES).
+ *   flags: TIRT_TRAVERSE_EXHAUSTIVE = the scan over all primitive records (the yardstick: N_box 0, N_leaf = primitives), TIRT_COUNT_NODES.  stack_size
+ *   1..4096 entries of 8 bytes per query (the first 16 in LDS, the rest in the context's spill buffer); an entry that does not fit is dropped and the
+ *   query counted in stack_overflow (tirt_stats: TIRT_ERR_STACK), as a ray's.  The queries are not rays: no ray counter moves.
+ *   Refused with TIRT_ERR_ARG before anything is queued: a pointer that is not device memory of ctx's device, point_stride < 3, point_out_stride < 3
+ *   with out_point, uv_stride < 2 with out_uv, dmax_stride < 1 with dmax, other flags, an LBVH that is not built, a capturing stream.  n == 0 queues nothing.
+ * tirt_closest_point: host arrays (points[n*3], dmax[n] or NULL = +inf, out_point[n*3], out_uv[n*2]), staged in the context's query scratch (52 bytes
+ *   per query) and synchronous, as tirt_trace_closest is to tirt_query_closest.
+ * tirt_kat_closest_point: D2, Q, u, v of explicit operands through the same device function, one row per thread: rows of 12 floats (p3, a3, b3, c3) or,
+ *   with is_sphere, 7 floats (p3, c3, r), to rows of 6 floats (d2, q3, u, v). */
+int tirt_query_closest_point(tirt_ctx *ctx, const float *points, int64_t n, int64_t point_stride,
+                             const float *dmax, int64_t dmax_stride, float dmax_all, int stack_size, int flags,
+                             float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride,
+                             float *out_uv, int64_t uv_stride, int32_t *counts, void *stream);
+int tirt_closest_point(tirt_ctx *ctx, const float *points, int n, const float *dmax, int stack_size, int flags,
+                       float *out_d2, int32_t *out_prim, float *out_point, float *out_uv, int32_t *counts);
+int tirt_kat_closest_point(tirt_ctx *ctx, const float *in, int n, int is_sphere, float *out);
+
 /* Multi-GPU without a Python framework in the loop (the reference has nothing here): ONE host thread drives
  * ndev contexts, one per device of the node, each created with tirt_film_create(..., tile_rank = i, tile_count = ndev, ...).
  * tirt_comm_init builds one RCCL communicator over them (librccl is loaded on first use); tirt_film_reduce sums the films

@@ -1,0 +1,124 @@
+"""The nearest surface point of a scene to query points held in PyTorch device tensors (no reference counterpart; include/tirt.h,
+"Closest point": the definition, bit for bit; csrc/tirt_closest_point.hip: the walk over the scene's 4-wide nodes).
+
+    q = PointQuery(scene, stack_size=64, flags=0)         # scene after setup_data_gpu() (Example.build_scene)
+    h = q.closest(points, max_distance=None, attributes=False)      # PointHits(dist2 [N] f32, prim [N] i32, point [N, 3] or None, uv [N, 2] or None)
+
+``points`` is a float32 tensor ``[N, C >= 3]`` on the scene context's device with ``stride(1) == 1`` and any row stride (an ``[N, 8]``
+tensor's ``[:, :3]`` view works).  ``max_distance``: None (no bound), a float for every query, or an ``[N]`` float32 tensor on the same
+device (any positive stride); a negative or NaN bound finds nothing.  Nothing found: ``prim = -1``, ``dist2 = inf``, point and uv 0.
+``uv`` is the hit record's convention (``point = a + u (b - a) + v (c - a)``).  The outputs come from ``torch.empty`` and the work is
+queued on ``torch.cuda.current_stream(device)``: nothing waits for it on the host.
+"""
+import collections
+import os
+
+from . import _native
+
+PointHits = collections.namedtuple("PointHits", ["dist2", "prim", "point", "uv"])
+
+
+def _torch():
+    try:
+        import torch
+    except ImportError as exc:
+        raise ImportError("ti_raytrace_amd.PointQuery needs PyTorch (ROCm build); the C-ABI tirt_query_closest_point "
+                          "(include/tirt.h) works without it") from exc
+    return torch
+
+
+class PointQuery:
+    def __init__(self, scene, stack_size=64, flags=0):
+        self.torch = _torch()
+        if not 1 <= int(stack_size) <= 4096:
+            raise ValueError("PointQuery: stack_size must be 1..4096, got %r" % (stack_size,))
+        if int(flags) & ~(_native.TRAVERSE_EXHAUSTIVE | _native.COUNT_NODES):
+            raise ValueError("PointQuery: flags are TRAVERSE_EXHAUSTIVE and COUNT_NODES, got %r" % (flags,))
+        self.scene = scene
+        self.stack_size = int(stack_size)
+        self.flags = int(flags)
+
+    def _device(self):
+        """the scene context's device, without creating the context"""
+        ctx = getattr(self.scene, "_ctx", None)
+        if ctx is not None:
+            dev = ctx.device_id
+        else:
+            dev = getattr(self.scene, "_device_id", None)
+            if dev is None:
+                dev = int(os.environ.get("LOCAL_RANK", "0"))           # what Scene.ctx will pick
+        return self.torch.device("cuda", int(dev))
+
+    def _check_points(self, points, what):
+        torch = self.torch
+        if not isinstance(points, torch.Tensor):
+            raise TypeError("PointQuery.%s: points must be a torch.Tensor, got %s" % (what, type(points).__name__))
+        if points.dtype != torch.float32:
+            raise TypeError("PointQuery.%s: points must be float32, got %s" % (what, points.dtype))
+        # (type and layout first: these checks need no device)
+        if points.dim() != 2 or points.shape[1] < 3:
+            raise ValueError("PointQuery.%s: points must be [N, C >= 3], got shape %s" % (what, tuple(points.shape)))
+        n = points.shape[0]
+        if n > 1 and points.stride(0) < 3:
+            raise ValueError("PointQuery.%s: rows of points overlap (stride(0) = %d < 3)" % (what, points.stride(0)))
+        if n > 0 and points.stride(1) != 1:
+            raise ValueError("PointQuery.%s: the last dimension of points must have stride 1, got %d" % (what, points.stride(1)))
+        if points.device.type != "cuda":
+            raise TypeError("PointQuery.%s: points must be on the GPU, got a %s tensor" % (what, points.device.type))
+        dev = self._device()
+        if points.device != dev:
+            raise ValueError("PointQuery.%s: points are on %s, the scene's context on %s" % (what, points.device, dev))
+        return dev, n, (points.stride(0) if n > 1 else max(points.shape[1], 3))
+
+    def _check_bound(self, max_distance, dev, n, what):
+        """(device address or 0, stride, the bound of every query when the address is 0)"""
+        torch = self.torch
+        if max_distance is None:
+            return 0, 1, float("inf")
+        if isinstance(max_distance, torch.Tensor):
+            if max_distance.dtype != torch.float32:
+                raise TypeError("PointQuery.%s: max_distance must be float32, got %s" % (what, max_distance.dtype))
+            if max_distance.device != dev:
+                raise ValueError("PointQuery.%s: max_distance is on %s, the points on %s" % (what, max_distance.device, dev))
+            if max_distance.dim() != 1 or max_distance.shape[0] != n:
+                raise ValueError("PointQuery.%s: max_distance must be [N] = [%d], got shape %s" % (what, n, tuple(max_distance.shape)))
+            if n > 1 and max_distance.stride(0) < 1:
+                raise ValueError("PointQuery.%s: max_distance must have a positive stride, got %d" % (what, max_distance.stride(0)))
+            if n:
+                return max_distance.data_ptr(), (max_distance.stride(0) if n > 1 else 1), float("inf")
+            return 0, 1, float("inf")
+        if isinstance(max_distance, (int, float)):
+            return 0, 1, float(max_distance)
+        raise TypeError("PointQuery.%s: max_distance must be None, a float or a float32 tensor, got %s" % (what, type(max_distance).__name__))
+
+    def closest(self, points, max_distance=None, attributes=False):
+        """The nearest surface point of every query, bit for bit Context.closest_point's: dist2 (inf where nothing is found), prim (-1) and, with
+        attributes=True, the point and its (u, v).  Asynchronous on the current stream."""
+        torch = self.torch
+        dev, n, stride = self._check_points(points, "closest")
+        dptr, dstride, dall = self._check_bound(max_distance, dev, n, "closest")
+        d2 = torch.empty(n, dtype=torch.float32, device=dev)
+        prim = torch.empty(n, dtype=torch.int32, device=dev)
+        point = torch.empty((n, 3), dtype=torch.float32, device=dev) if attributes else None
+        uv = torch.empty((n, 2), dtype=torch.float32, device=dev) if attributes else None
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self.scene.ctx.query_closest_point(points.data_ptr(), n, stride, self.stack_size, self.flags, dmax=dptr, dmax_stride=dstride, dmax_all=dall,
+                                               out_d2=d2.data_ptr(), out_prim=prim.data_ptr(), out_point=point.data_ptr() if attributes else 0,
+                                               out_uv=uv.data_ptr() if attributes else 0, stream=stream)
+        return PointHits(d2, prim, point, uv)
+
+    def closest_counts(self, points, max_distance=None):
+        """closest() with the per-query N_box / N_leaf counts ([N, 2] int32) of a COUNT_NODES walk: (PointHits, counts)"""
+        torch = self.torch
+        dev, n, stride = self._check_points(points, "closest_counts")
+        dptr, dstride, dall = self._check_bound(max_distance, dev, n, "closest_counts")
+        d2 = torch.empty(n, dtype=torch.float32, device=dev)
+        prim = torch.empty(n, dtype=torch.int32, device=dev)
+        counts = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self.scene.ctx.query_closest_point(points.data_ptr(), n, stride, self.stack_size, self.flags | _native.COUNT_NODES, dmax=dptr,
+                                               dmax_stride=dstride, dmax_all=dall, out_d2=d2.data_ptr(), out_prim=prim.data_ptr(),
+                                               counts=counts.data_ptr(), stream=stream)
+        return PointHits(d2, prim, None, None), counts

@@ -171,6 +171,10 @@ SIGNATURES = {
     "tirt_trace_shadow": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _vp]),
     "tirt_query_closest": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
     "tirt_query_occluded": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int, _vp, _vp]),
+    "tirt_query_closest_point": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64,
+                                           _vp, C.c_int64, _vp, _vp]),
+    "tirt_closest_point": (C.c_int, [_vp, _f32p, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "tirt_kat_closest_point": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, _f32p]),
     "tirt_comm_init": (C.c_int, [C.POINTER(_vp), C.c_int]),
     "tirt_film_reduce": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int]),
     "tirt_comm_destroy": (C.c_int, [C.POINTER(_vp), C.c_int]),
@@ -850,6 +854,39 @@ class Context:
         """tirt_query_occluded on device memory: integer device addresses, tmax = 0 means tmax_all for every ray."""
         check(lib().tirt_query_occluded(self.handle, _vp(int(rays) or None), int(nr), int(ray_stride), _vp(int(tmax) or None), int(tmax_stride),
                                         float(tmax_all), int(stack_size), int(flags), _vp(int(out_occluded) or None), _vp(int(stream) or None)))
+
+    def query_closest_point(self, points, n, point_stride, stack_size=64, flags=0, dmax=0, dmax_stride=1, dmax_all=float("inf"), out_d2=0, out_prim=0,
+                            out_point=0, point_out_stride=3, out_uv=0, uv_stride=2, counts=0, stream=0):
+        """tirt_query_closest_point on device memory: every buffer is an integer device address (0 = none), dmax = 0 means dmax_all for every
+        query.  Asynchronous (include/tirt.h, "Closest point"); ti_raytrace_amd.PointQuery is the torch front end."""
+        check(lib().tirt_query_closest_point(self.handle, _vp(int(points) or None), int(n), int(point_stride), _vp(int(dmax) or None), int(dmax_stride),
+                                             float(dmax_all), int(stack_size), int(flags), _vp(int(out_d2) or None), _vp(int(out_prim) or None),
+                                             _vp(int(out_point) or None), int(point_out_stride), _vp(int(out_uv) or None), int(uv_stride),
+                                             _vp(int(counts) or None), _vp(int(stream) or None)))
+
+    def closest_point(self, points, max_distance=None, stack_size=64, flags=0, attributes=True):
+        """tirt_closest_point, the host route: points (n, 3) float32, max_distance None (= inf), a float or (n,) float32 ->
+        (dist2 (n,), prim (n,), point (n, 3) or None, uv (n, 2) or None, counts (n, 2) or None [COUNT_NODES])"""
+        points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = points.shape[0]
+        dmax = None
+        if max_distance is not None:
+            dmax = np.ascontiguousarray(np.broadcast_to(np.asarray(max_distance, np.float32), (n,)))
+        d2 = np.zeros(n, np.float32)
+        prim = np.zeros(n, np.int32)
+        point = np.zeros((n, 3), np.float32) if attributes else None
+        uv = np.zeros((n, 2), np.float32) if attributes else None
+        counts = np.zeros((n, 2), np.int32) if (flags & COUNT_NODES) else None
+        check(lib().tirt_closest_point(self.handle, points.reshape(-1), n, _ptr(dmax), int(stack_size), int(flags), _ptr(d2), _ptr(prim),
+                                       _ptr(point), _ptr(uv), _ptr(counts)))
+        return d2, prim, point, uv, counts
+
+    def kat_closest_point(self, rows, is_sphere=False):
+        """include/tirt.h, tirt_kat_closest_point: rows (n, 12) (p, a, b, c) or, is_sphere, (n, 7) (p, c, r) -> (n, 6): d2, q3, u, v"""
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 7 if is_sphere else 12)
+        out = np.zeros((rows.shape[0], 6), np.float32)
+        check(lib().tirt_kat_closest_point(self.handle, rows.reshape(-1), rows.shape[0], 1 if is_sphere else 0, out.reshape(-1)))
+        return out
 
     def bvh_info(self):
         out = (C.c_uint64 * 4)()

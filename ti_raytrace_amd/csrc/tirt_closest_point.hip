@@ -1,0 +1,399 @@
+// tirt_closest_point.hip -- the nearest surface point to a query point (tirt_query_closest_point / tirt_closest_point / tirt_kat_closest_point,
+// include/tirt.h "Closest point").  No reference counterpart: the reference only answers questions that start from a ray.
+//
+//   k_cp_scan   one query per lane against all n primitive records in primitive-id order (TIRT_TRAVERSE_EXHAUSTIVE): the yardstick on the device
+//   k_cp_walk   one query per lane, best-first over the quantised 4-wide nodes `cnode` (BvhView): the hot path
+//
+// Both call cp_triangle / cp_sphere / cp_accept (tirt_closest_point.h) and nothing else decides an answer, and the answer is the minimum of a total
+// order on (D2, prim): the walk returns the scan's bits if and only if it never skips a primitive that would have been accepted.
+//
+// THE WALK.  A wave is a block (no barrier anywhere); lane l holds query base + l and the blocks stride over the chunk.  A node visit decodes the four
+// children's planes (grid_min + h * cell, h the fp16 halves of the record), forms lb2 = sum over the axes of max(mn - p - m, p - mx - m, 0)^2 with the
+// margin m below, drops empty slots and children with lb2 > cut (cut = min(best D2 so far, lim2)), sorts the rest (five compare-exchanges, as k_trace),
+// descends into the nearest and pushes the others far to near WITH their lb2; a popped entry is tested against the cut of that moment again (the best
+// distance of a nearest-neighbour walk shrinks fast: most entries are dead when they surface).  Leaves gather the three quads of the record; the
+// sphere branch (a square root and a division) sits behind a wave ballot, as in trace_leaf_step.  Node steps and leaf steps alternate, each for the
+// lanes that are at one.  Stack entries are 8 bytes (child code, lb2); the first CP_LDS_DEPTH of a lane live in LDS ([entry][lane]), the rest of its
+// stack_size in the context's spill buffer ([entry][global thread]) -- DESIGN.md "Closest point" has the sizes and why 16.  An entry beyond stack_size
+// is dropped and the query counted in DevCounters::stack_overflow (tirt_stats: TIRT_ERR_STACK), as a ray's.
+// The walk starts at root_qcode (a leaf code in a one-primitive scene).  Every analytic sphere is below it: its slot carries its padded box
+// (shapes_boxed) or the whole grid, and both contain the sphere, as every ancestor's box does -- the chain nodes at far_qcode exist for rays, whose
+// sphere test can answer from outside the padded box; a closest point lies ON the sphere.  Spot and laser leaves are reached and skipped.
+// A query with a NaN or infinite coordinate finds nothing by the definition (every D2 is NaN or +inf): it does not walk.
+//
+// WHY THE CULL IS CONSERVATIVE.  A subtree is skipped on lb2 > cut only, never on equality, so it suffices that lb2 <= D2 holds, as computed fp32
+// numbers, for every primitive t below the node.  Write eps = 2^-24, E = the largest extent of the padded root box, C = E / 60000 = the largest cell,
+// M = the largest coordinate magnitude among p and the scene, d = the distance from p to t.
+//  (1) The computed D2.  cp_triangle's Q is a vertex, or a + ab u with u in [0, 1] (AB, AC, BC: the region tests make numerator and denominator
+//      non-negative with numerator <= denominator, and a correctly rounded quotient keeps that), or (a + ab u) + ac v with u = vb den, v = vc den.
+//      On an edge the exact a + ab u lies on the segment, hence in the leaf's exact box, and the evaluated one differs from it by the roundings of
+//      b - a, the product and the sum: <= 2 eps M per coordinate.  In the interior u, v, 1 - u - v carry the error of va, vb, vc (differences of
+//      products of dot products whose terms reach |ab| |ap|): a relative error of order eps (|p - a| / |ab|) in (u, v), i.e. a shift of Q IN THE
+//      TRIANGLE'S PLANE of order eps (d + |ab|), a few eps M again.  So Q is within k eps M of the box with k "a few"; p - Q adds eps M / 2 per
+//      coordinate and the dot product 3 eps relative.  sqrt(D2) >= (d_box - sqrt(3) (k + 1) eps M) (1 - 2 eps), d_box = the exact distance from p to
+//      the exact box.  The sphere: |len - r| is off by <= 3 eps max(len, r) <= 3 eps (M + d) from a distance to a surface inside its box.
+//      [A needle whose area is so small against its edges that va + vb + vc is rounding noise can put the interior's Q further out than that; such a
+//      triangle has no trustworthy interior answer in the scan either.  The margin below is sized for k <= 100, not for "a few".]
+//  (2) The computed lb2.  A decoded plane is off by eps E / 4 (the product) + eps M / 2 (the sum), the differences mn - p, p - mx by eps M each at
+//      most, the squares and sums by 3 eps relative: sqrt(lb2) <= (|e| + 3 sqrt(3) eps M) (1 + 2 eps), e the exact per-axis distances to the
+//      quantised box moved outward by m.
+//  (3) The slack.  A quantised plane is >= 0.9 of ITS axis' cell outside the exact box (tirt_internal.h: rounded outward by at least one cell); that
+//      cell can be tiny on a flat scene's thin axis, so it is not relied on beyond the rounding of the planes themselves.  The margin m is the SAME
+//      length on all axes, m = mc * C.  With x the exact per-axis distances to the exact box (|x| = d_box) and e_a <= max(x_a - m, 0):
+//      |x|^2 = |e|^2 + 2 e.(x - e) + |x - e|^2 >= (|e| + m)^2 whenever e != 0, because x_a - e_a = m on every axis with e_a > 0.  So |e| <= d_box - m.
+//  Together: lb2 <= D2 if m >= sqrt(3) (k + 4) eps M + 4 eps d.  With rho_p = max_a |p_a - grid_min_a| / E and rho_0 = max_a |grid_min_a| / E,
+//  M <= (rho_0 + max(rho_p, 1/2)) E and d <= sqrt(3) (rho_p + 1/2) E; eps E = 0.00358 C.  mc = 0.5 + 0.5 (rho_p + rho_0) (cp_margin_cells) gives
+//  m >= 0.5 C (rho_p + rho_0 + 1) >= 140 eps M and leaves >= 100 eps M for k after the 4 sqrt(3) eps M and 4 eps d terms (<= 14 + 14 eps M-equivalents).
+//  Unlike trace_margin_cells it grows with the SCENE's distance from the origin too (rho_0): a mesh 10^4 extents from the origin has vertices that are
+//  36 cells apart in fp32.  Half a cell is 8e-6 of the extent: it costs no visit worth counting near the scene; a query many extents away
+//  gets a margin that swallows the boxes and its walk degenerates towards the scan, which is acceptable (no cut-off).
+#include "tirt_internal.h"
+#include "tirt_closest_point.h"
+
+namespace tirt {
+
+constexpr int CP_BLOCK = 64;                 // one wave per block
+#ifndef CP_LDS_DEPTH_N
+#define CP_LDS_DEPTH_N 16
+#endif
+constexpr int CP_LDS_DEPTH = CP_LDS_DEPTH_N;  // stack entries per lane in LDS: 16 x 8 B x 64 lanes = 8 KiB per block (24: the same rate, 32 / 48: 15 % / 36 % slower, profiles/closest_point_rate.txt)
+constexpr int CP_WAVES_PER_CU = 20;          // persistent blocks per CU at most: what 8 KiB of LDS each admits (62 VGPRs would admit 32)
+constexpr size_t CP_SPILL_BYTES_MAX = (size_t)256 << 20;      // the grid shrinks until the stacks' global tails fit this
+constexpr int CP_SENT = (int)0x80000000;     // "nothing to do": never a node index nor a leaf code (k_trace's TR_SENT)
+constexpr float CP_MARGIN_CELLS = 0.5f, CP_MARGIN_PER_RHO = 0.5f;
+TD float cp_margin_cells(float rho_p, float rho_0) { return CP_MARGIN_CELLS + CP_MARGIN_PER_RHO * (rho_p + rho_0); }
+
+struct CpArgs {
+    BvhView bvh;
+    const int *primitive, *prim_slot; int n_prim;      // the scan: kind and record slot of primitive i
+    const float *points; int64_t point_stride;          // this chunk's first row
+    const float *dmax; int64_t dmax_stride; float dmax_all;
+    int n;                                              // queries of this chunk
+    int stack_size;
+    uint2 *spill;                                       // [stack_size - CP_LDS_DEPTH][gridDim.x * CP_BLOCK], or nullptr when stack_size <= CP_LDS_DEPTH
+    float *out_d2; int32_t *out_prim; float *out_point; int64_t point_out_stride; float *out_uv; int64_t uv_stride; int2 *counts;
+    DevCounters *ctr;
+};
+
+TD void cp_load_query(const CpArgs &a, int q, v3 &p, float &lim2)
+{
+    const float *r = a.points + (int64_t)q * a.point_stride;
+    p = V(r[0], r[1], r[2]);
+    lim2 = cp_limit2(a.dmax ? a.dmax[(int64_t)q * a.dmax_stride] : a.dmax_all);
+}
+
+TD void cp_store(const CpArgs &a, int q, float best2, int best_prim, const CpPoint &bp, unsigned nbox, unsigned nleaf, bool count)
+{
+    if (a.out_d2) a.out_d2[q] = best2;
+    if (a.out_prim) a.out_prim[q] = best_prim;
+    if (a.out_point) { float *o = a.out_point + (int64_t)q * a.point_out_stride; o[0] = bp.q.x; o[1] = bp.q.y; o[2] = bp.q.z; }
+    if (a.out_uv) { float *o = a.out_uv + (int64_t)q * a.uv_stride; o[0] = bp.u; o[1] = bp.v; }
+    if (count && a.counts) a.counts[q] = make_int2((int)nbox, (int)nleaf);
+}
+
+// one record against the query: the kind comes from the caller (the leaf code's shape bit, or the primitive table)
+TD void cp_test_record(const BvhView &b, int slot, bool is_tri, const v3 p, float lim2, float &best2, int &best_prim, CpPoint &bp)
+{
+    const float4 *tp = b.tri + (size_t)slot * TRI_STRIDE;
+    const float4 ta = tp[0], tb = tp[1], tc = tp[2];
+    const int prim = __float_as_int(tc.w);
+    const v3 pa = V(ta.x, ta.y, ta.z);
+    CpPoint r; r.d2 = __int_as_float(0x7fc00000); r.q = V(0.0f, 0.0f, 0.0f); r.u = 0.0f; r.v = 0.0f;      // spot / laser: no surface, a NaN D2 is never accepted
+    if (is_tri) r = cp_triangle(p, pa, V(tb.x, tb.y, tb.z), V(tc.x, tc.y, tc.z));
+    const bool sph = !is_tri && (int)tb.y == SHAPE_SPHERE;
+    if (__builtin_amdgcn_ballot_w64(sph) != 0ull) { if (sph) r = cp_sphere(p, pa, tb.x); }
+    if (cp_accept(r.d2, prim, lim2, best2, best_prim)) { best2 = r.d2; best_prim = prim; bp = r; }
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(CP_BLOCK) void k_cp_scan(CpArgs a)
+{
+    const int q = blockIdx.x * CP_BLOCK + threadIdx.x;
+    if (q >= a.n) return;
+    v3 p; float lim2;
+    cp_load_query(a, q, p, lim2);
+    float best2 = __int_as_float(0x7f800000); int best_prim = -1;
+    CpPoint bp; bp.d2 = best2; bp.q = V(0.0f, 0.0f, 0.0f); bp.u = 0.0f; bp.v = 0.0f;
+    for (int i = 0; i < a.n_prim; i++)
+        cp_test_record(a.bvh, a.prim_slot[i], a.primitive[(size_t)i * PRI_VEC] == PRIMITIVE_TRI, p, lim2, best2, best_prim, bp);
+    cp_store(a, q, best2, best_prim, bp, 0u, (unsigned)a.n_prim, COUNT);
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(CP_BLOCK) void k_cp_walk(CpArgs a)
+{
+    __shared__ uint2 stk[CP_LDS_DEPTH * CP_BLOCK];      // [entry][lane]
+    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
+    const BvhView &b = a.bvh;
+    const int lane = threadIdx.x;
+    const size_t gthreads = (size_t)gridDim.x * CP_BLOCK, gtid = (size_t)blockIdx.x * CP_BLOCK + lane;
+    const float cell_max = maxf(maxf(b.cell[0], b.cell[1]), b.cell[2]);
+    const float inv_ext = 1.0f / (cell_max * (2.0f * TR_GRID_HALF));
+    const float rho_0 = maxf(maxf(absf(b.grid_min[0]), absf(b.grid_min[1])), absf(b.grid_min[2])) * inv_ext;
+    unsigned long long n_over = 0;
+
+    for (int base = blockIdx.x * CP_BLOCK; base < a.n; base += gridDim.x * CP_BLOCK) {      // wave-uniform
+        const int q = base + lane;
+        const bool live = q < a.n;
+        v3 p = V(0.0f, 0.0f, 0.0f); float lim2 = -1.0f;
+        if (live) cp_load_query(a, q, p, lim2);
+        float best2 = __int_as_float(0x7f800000); int best_prim = -1;
+        CpPoint bp; bp.d2 = best2; bp.q = V(0.0f, 0.0f, 0.0f); bp.u = 0.0f; bp.v = 0.0f;
+        const bool finite = absf(p.x) < best2 && absf(p.y) < best2 && absf(p.z) < best2;      // false for NaN and +-inf
+        const float rho_p = maxf(maxf(absf(p.x - b.grid_min[0]), absf(p.y - b.grid_min[1])), absf(p.z - b.grid_min[2])) * inv_ext;
+        const float m = cp_margin_cells(rho_p, rho_0) * cell_max;
+        float cut = lim2;                       // min(best2, lim2): best2 starts at +inf
+        int cur = (live && finite && lim2 >= 0.0f) ? b.root_qcode : CP_SENT;
+        int sp = 0;                             // entries on this lane's stack
+        unsigned nbox = 0, nleaf = 0; bool overflow = false;
+
+#define CP_PUSH(code_, lb2_)                                                                        \
+        do {                                                                                        \
+            if (sp < a.stack_size) {                                                                \
+                const uint2 e__ = make_uint2((unsigned)(code_), __float_as_uint(lb2_));             \
+                if (sp < CP_LDS_DEPTH) stk[sp * CP_BLOCK + lane] = e__;                             \
+                else a.spill[(size_t)(sp - CP_LDS_DEPTH) * gthreads + gtid] = e__;                  \
+                sp++;                                                                               \
+            } else overflow = true;               /* out of room: the entry is lost (counted) */    \
+        } while (0)
+        // the next entry that can still win; most are dead by the time they surface
+#define CP_POP()                                                                                    \
+        do {                                                                                        \
+            cur = CP_SENT;                                                                          \
+            while (sp > 0) {                                                                        \
+                sp--;                                                                               \
+                const uint2 e__ = sp < CP_LDS_DEPTH ? stk[sp * CP_BLOCK + lane] : a.spill[(size_t)(sp - CP_LDS_DEPTH) * gthreads + gtid]; \
+                if (!(__uint_as_float(e__.y) > cut)) { cur = (int)e__.x; break; }                   \
+            }                                                                                       \
+        } while (0)
+
+        while (__builtin_amdgcn_ballot_w64(cur != CP_SENT) != 0ull) {
+            // ---- node step: the lanes that are at an inner node
+            if (cur >= 0) {
+                const uint4 *w = b.cnode + (size_t)cur * 4;
+                const uint4 q0 = w[0], q1 = w[1], q2 = w[2], q3 = w[3];
+                int c0 = (int)q3.x, c1 = (int)q3.y, c2 = (int)q3.z, c3 = (int)q3.w;
+                if (COUNT) nbox += 4;
+                constexpr float MISS = 3.0e38f;
+                float l0, l1, l2, l3;
+#define CP_AXIS(W, k, pk)                                                                           \
+                ({  const h2v h__ = __builtin_bit_cast(h2v, (unsigned)(W));                         \
+                    const float mn__ = b.grid_min[k] + (float)h__.x * b.cell[k], mx__ = b.grid_min[k] + (float)h__.y * b.cell[k]; \
+                    maxf(maxf(mn__ - (pk), (pk) - mx__) - m, 0.0f); })
+                // kept: a child that is there and can still win (never culled on equality).  The flag travels with the child through the sort, so
+                // a kept child whose lb2 overflowed to +inf (a query ~1e19 away, cut = +inf) sorts behind the dropped ones and is still pushed
+#define CP_BOX(X, Y, Z, code_, lb_, keep_)                                                          \
+                do {                                                                                \
+                    const float ex__ = CP_AXIS(X, 0, p.x), ey__ = CP_AXIS(Y, 1, p.y), ez__ = CP_AXIS(Z, 2, p.z); \
+                    const float s__ = (ex__ * ex__ + ey__ * ey__) + ez__ * ez__;                    \
+                    keep_ = ((code_) != TR_EMPTY) && !(s__ > cut);                                  \
+                    lb_ = keep_ ? s__ : MISS;                                                       \
+                } while (0)
+                bool k0, k1, k2, k3;
+                CP_BOX(q0.x, q0.y, q0.z, c0, l0, k0);
+                CP_BOX(q0.w, q1.x, q1.y, c1, l1, k1);
+                CP_BOX(q1.z, q1.w, q2.x, c2, l2, k2);
+                CP_BOX(q2.y, q2.z, q2.w, c3, l3, k3);
+#define CP_CE(la, ca, ka, lb, cb, kb)                                                               \
+                do {                                                                                \
+                    const bool s__ = (lb) < (la);                                                   \
+                    const float lo__ = s__ ? (lb) : (la), hi__ = s__ ? (la) : (lb);                 \
+                    const int clo__ = s__ ? (cb) : (ca), chi__ = s__ ? (ca) : (cb);                 \
+                    const bool klo__ = s__ ? (kb) : (ka), khi__ = s__ ? (ka) : (kb);                \
+                    la = lo__; lb = hi__; ca = clo__; cb = chi__; ka = klo__; kb = khi__;           \
+                } while (0)
+                CP_CE(l0, c0, k0, l1, c1, k1); CP_CE(l2, c2, k2, l3, c3, k3); CP_CE(l0, c0, k0, l2, c2, k2); CP_CE(l1, c1, k1, l3, c3, k3); CP_CE(l1, c1, k1, l2, c2, k2);
+                if (k3) CP_PUSH(c3, l3);
+                if (k2) CP_PUSH(c2, l2);
+                if (k1) CP_PUSH(c1, l1);
+                if (k0) cur = c0; else CP_POP();
+            }
+            // ---- leaf step: the lanes that are at a leaf
+            const bool at_leaf = cur < 0 && cur != CP_SENT;
+            if (__builtin_amdgcn_ballot_w64(at_leaf) != 0ull) {
+                if (at_leaf) {
+                    const int code = ~cur;
+                    if (COUNT) nleaf += 1;
+                    cp_test_record(b, code & 0x3fffffff, ((code >> 30) & 1) == 0, p, lim2, best2, best_prim, bp);
+                    cut = __builtin_fminf(best2, lim2);
+                    CP_POP();
+                }
+            }
+        }
+        if (live) cp_store(a, q, best2, best_prim, bp, nbox, nleaf, COUNT);
+        if (overflow) n_over++;
+    }
+    n_over = wave_sum(n_over);
+    if (lane == 0 && n_over && a.ctr) atomicAdd(&a.ctr->stack_overflow, n_over);
+}
+
+// the checks of query_common_checks (tirt_query.hip), worded for points
+static int cp_common_checks(tirt_ctx *c, const char *fn, int64_t n, int stack_size, int flags)
+{
+    TIRT_REQUIRE(c->built, std::string(fn) + ": LBVH not built");
+    TIRT_REQUIRE(n >= 0, std::string(fn) + ": n < 0");
+    TIRT_REQUIRE(stack_size >= 1 && stack_size <= 4096, std::string(fn) + ": stack_size 1..4096");
+    TIRT_REQUIRE((flags & ~(TIRT_TRAVERSE_EXHAUSTIVE | TIRT_COUNT_NODES)) == 0, std::string(fn) + ": unknown flags");
+    return TIRT_OK;
+}
+
+// `n` queries in chunks of `chunk` on the context's stream; every pointer is device memory (or null)
+static int cp_chunks(tirt_ctx *c, const float *points, int64_t n, int64_t point_stride, const float *dmax, int64_t dmax_stride, float dmax_all,
+                     int stack_size, int flags, int chunk, float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride,
+                     float *out_uv, int64_t uv_stride, int2 *counts)
+{
+    if (ensure_counters(c)) return TIRT_ERR_HIP;
+    const bool scan = (flags & TIRT_TRAVERSE_EXHAUSTIVE) != 0, cnt = (flags & TIRT_COUNT_NODES) != 0;
+    CpArgs a = {};
+    a.bvh = bvh_view(c);
+    a.primitive = c->primitive.as<int>(); a.prim_slot = c->prim_slot.as<int>(); a.n_prim = c->n;
+    a.point_stride = point_stride; a.dmax_stride = dmax_stride; a.dmax_all = dmax_all;
+    a.stack_size = stack_size; a.point_out_stride = point_out_stride; a.uv_stride = uv_stride;
+    a.ctr = c->dev_counters.as<DevCounters>();
+    // the walk's grid: a lane for every query of a chunk, at most CP_WAVES_PER_CU blocks per CU, fewer while the stacks' global tails would not fit
+    int grid_cap = c->cu_count * CP_WAVES_PER_CU;
+    const size_t tail = stack_size > CP_LDS_DEPTH ? (size_t)(stack_size - CP_LDS_DEPTH) * sizeof(uint2) : 0;      // bytes per thread
+    if (tail) { const size_t fit = CP_SPILL_BYTES_MAX / (tail * CP_BLOCK); if ((size_t)grid_cap > fit) grid_cap = (int)(fit > 0 ? fit : 1); }
+    int grid_max = (int)(((int64_t)(n < chunk ? n : chunk) + CP_BLOCK - 1) / CP_BLOCK); if (grid_max > grid_cap) grid_max = grid_cap;
+    if (!scan && tail) {
+        const size_t want = tail * CP_BLOCK * (size_t)grid_max;
+        if (want > c->spill.bytes) {            // growing frees the old buffer, which queued work may still use
+            TIRT_HIP(hipStreamSynchronize(c->stream));
+            if (c->spill.ensure(want)) return TIRT_ERR_HIP;
+        }
+        a.spill = c->spill.as<uint2>();
+    }
+    for (int64_t base = 0; base < n; base += chunk) {
+        const int m = (int)(n - base < chunk ? n - base : chunk);
+        a.n = m;
+        a.points = points + base * point_stride; a.dmax = dmax ? dmax + base * dmax_stride : nullptr;
+        a.out_d2 = out_d2 ? out_d2 + base : nullptr; a.out_prim = out_prim ? out_prim + base : nullptr;
+        a.out_point = out_point ? out_point + base * point_out_stride : nullptr; a.out_uv = out_uv ? out_uv + base * uv_stride : nullptr;
+        a.counts = counts ? counts + base : nullptr;
+        const int blocks = (m + CP_BLOCK - 1) / CP_BLOCK;
+        if (scan) {
+            if (cnt) hipLaunchKernelGGL(k_cp_scan<true>, dim3(blocks), dim3(CP_BLOCK), 0, c->stream, a);
+            else hipLaunchKernelGGL(k_cp_scan<false>, dim3(blocks), dim3(CP_BLOCK), 0, c->stream, a);
+        } else {
+            const int g = blocks < grid_max ? blocks : grid_max;
+            if (cnt) hipLaunchKernelGGL(k_cp_walk<true>, dim3(g), dim3(CP_BLOCK), 0, c->stream, a);
+            else hipLaunchKernelGGL(k_cp_walk<false>, dim3(g), dim3(CP_BLOCK), 0, c->stream, a);
+        }
+    }
+    return TIRT_OK;
+}
+
+static int query_closest_point(tirt_ctx *c, const float *points, int64_t n, int64_t point_stride, const float *dmax, int64_t dmax_stride, float dmax_all,
+                               int stack_size, int flags, float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride,
+                               float *out_uv, int64_t uv_stride, int32_t *counts, void *stream)
+{
+    const char *fn = "tirt_query_closest_point";
+    if (int rc = cp_common_checks(c, fn, n, stack_size, flags)) return rc;
+    TIRT_REQUIRE(point_stride >= 3, "tirt_query_closest_point: point_stride < 3 (floats per point)");
+    TIRT_REQUIRE(!out_point || point_out_stride >= 3, "tirt_query_closest_point: point_out_stride < 3 (floats per closest point)");
+    TIRT_REQUIRE(!out_uv || uv_stride >= 2, "tirt_query_closest_point: uv_stride < 2");
+    TIRT_REQUIRE(!dmax || dmax_stride >= 1, "tirt_query_closest_point: dmax_stride < 1");
+    TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, "tirt_query_closest_point: counts must be 8-byte aligned");
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error(std::string(fn) + ": the caller's stream is not a stream of this process's HIP runtime");
+        return TIRT_ERR_ARG;
+    }
+    TIRT_REQUIRE(cs == hipStreamCaptureStatusNone, std::string(fn) + ": the caller's stream is capturing a graph (queries cannot be captured)");
+    if (n == 0) return TIRT_OK;
+    TIRT_REQUIRE(points, "tirt_query_closest_point: null points");
+    if (int rc = require_device_ptr(c, points, "tirt_query_closest_point: points")) return rc;
+    if (dmax) if (int rc = require_device_ptr(c, dmax, "tirt_query_closest_point: dmax")) return rc;
+    if (out_d2) if (int rc = require_device_ptr(c, out_d2, "tirt_query_closest_point: out_d2")) return rc;
+    if (out_prim) if (int rc = require_device_ptr(c, out_prim, "tirt_query_closest_point: out_prim")) return rc;
+    if (out_point) if (int rc = require_device_ptr(c, out_point, "tirt_query_closest_point: out_point")) return rc;
+    if (out_uv) if (int rc = require_device_ptr(c, out_uv, "tirt_query_closest_point: out_uv")) return rc;
+    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
+    if (want_counts) if (int rc = require_device_ptr(c, counts, "tirt_query_closest_point: counts")) return rc;
+    const int chunk = (int)(n < (int64_t)c->query_chunk ? n : (int64_t)c->query_chunk);
+    if (int rc = query_begin(c, stream)) return rc;
+    if (int rc = cp_chunks(c, points, n, point_stride, dmax, dmax_stride, dmax_all, stack_size, flags, chunk, out_d2, out_prim, out_point,
+                           point_out_stride, out_uv, uv_stride, want_counts ? (int2 *)counts : nullptr)) return rc;
+    return query_end(c, stream);
+}
+
+// host arrays staged in the context's query scratch (query_mem: 52 bytes per query), one chunk of all of them, back with a sync
+static int closest_point_host(tirt_ctx *c, const float *points, int n, const float *dmax, int stack_size, int flags, float *out_d2, int32_t *out_prim,
+                              float *out_point, float *out_uv, int32_t *counts)
+{
+    if (int rc = cp_common_checks(c, "tirt_closest_point", n, stack_size, flags)) return rc;
+    if (n == 0) return TIRT_OK;
+    TIRT_REQUIRE(points, "tirt_closest_point: null points");
+    const size_t N = (size_t)n, bytes = N * 52;
+    hipStream_t st = c->stream;
+    if (bytes > c->query_mem.bytes) {
+        TIRT_HIP(hipStreamSynchronize(st));
+        if (c->query_mem.ensure(bytes)) return TIRT_ERR_HIP;
+    }
+    // counts [n][2] first (8-byte aligned), then points [n][3], dmax [n], d2 [n], prim [n], point [n][3], uv [n][2]
+    int2 *d_counts = c->query_mem.as<int2>();
+    float *d_points = (float *)(d_counts + N), *d_dmax = d_points + 3 * N, *d_d2 = d_dmax + N;
+    int32_t *d_prim = (int32_t *)(d_d2 + N);
+    float *d_point = (float *)(d_prim + N), *d_uv = d_point + 3 * N;
+    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
+    TIRT_HIP(hipMemcpyAsync(d_points, points, sizeof(float) * 3 * N, hipMemcpyHostToDevice, st));
+    if (dmax) TIRT_HIP(hipMemcpyAsync(d_dmax, dmax, sizeof(float) * N, hipMemcpyHostToDevice, st));
+    if (int rc = cp_chunks(c, d_points, n, 3, dmax ? d_dmax : nullptr, 1, __builtin_inff(), stack_size, flags, n, d_d2, d_prim, d_point, 3, d_uv, 2,
+                           want_counts ? d_counts : nullptr)) return rc;
+    if (out_d2) TIRT_HIP(hipMemcpyAsync(out_d2, d_d2, sizeof(float) * N, hipMemcpyDeviceToHost, st));
+    if (out_prim) TIRT_HIP(hipMemcpyAsync(out_prim, d_prim, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+    if (out_point) TIRT_HIP(hipMemcpyAsync(out_point, d_point, sizeof(float) * 3 * N, hipMemcpyDeviceToHost, st));
+    if (out_uv) TIRT_HIP(hipMemcpyAsync(out_uv, d_uv, sizeof(float) * 2 * N, hipMemcpyDeviceToHost, st));
+    if (want_counts) TIRT_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int2) * N, hipMemcpyDeviceToHost, st));
+    TIRT_HIP(hipStreamSynchronize(st));
+    TIRT_HIP(hipGetLastError());
+    return TIRT_OK;
+}
+
+// rows of (p3, a3, b3, c3) or (p3, c3, r) -> d2, q3, u, v
+__global__ void k_kat_closest_point(const float *in, int n, int is_sphere, float *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *r = in + (size_t)i * (is_sphere ? 7 : 12);
+    const v3 p = V(r[0], r[1], r[2]);
+    const CpPoint a = is_sphere ? cp_sphere(p, V(r[3], r[4], r[5]), r[6])
+                                : cp_triangle(p, V(r[3], r[4], r[5]), V(r[6], r[7], r[8]), V(r[9], r[10], r[11]));
+    float *o = out + (size_t)i * 6;
+    o[0] = a.d2; o[1] = a.q.x; o[2] = a.q.y; o[3] = a.q.z; o[4] = a.u; o[5] = a.v;
+}
+
+}  // namespace tirt
+
+using namespace tirt;
+
+extern "C" {
+
+int tirt_query_closest_point(tirt_ctx *c, const float *points, int64_t n, int64_t point_stride, const float *dmax, int64_t dmax_stride, float dmax_all,
+                             int stack_size, int flags, float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride,
+                             float *out_uv, int64_t uv_stride, int32_t *counts, void *stream)
+{
+    CTX(c);
+    return query_closest_point(c, points, n, point_stride, dmax, dmax_stride, dmax_all, stack_size, flags, out_d2, out_prim, out_point, point_out_stride,
+                               out_uv, uv_stride, counts, stream);
+}
+
+int tirt_closest_point(tirt_ctx *c, const float *points, int n, const float *dmax, int stack_size, int flags, float *out_d2, int32_t *out_prim,
+                       float *out_point, float *out_uv, int32_t *counts)
+{
+    CTX(c);
+    return closest_point_host(c, points, n, dmax, stack_size, flags, out_d2, out_prim, out_point, out_uv, counts);
+}
+
+int tirt_kat_closest_point(tirt_ctx *c, const float *in, int n, int is_sphere, float *out)
+{
+    TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_closest_point: null pointer or negative n");
+    CTX(c);
+    if (n == 0) return TIRT_OK;
+    return kat_round_trip(c, "tirt_kat_closest_point", {{in, kat_row_bytes(n, is_sphere ? 7 : 12)}}, out, kat_row_bytes(n, 6), [&](const void *const *din, void *dout) {
+        hipLaunchKernelGGL(k_kat_closest_point, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float *)din[0], n, is_sphere, (float *)dout);
+    });
+}
+
+}  // extern "C"
