@@ -248,8 +248,15 @@ int tirt_kat_material_maps(tirt_ctx *ctx, const float *in, int in_stride, float 
  * 256 such a row names an uploaded roughness, metallic or normal-map texture in a word it honours (likewise never set by tirt_shade_features_host).
  * tirt_shade_features: out[0] = the word the context holds (refreshed by every scene, material, environment, texture and vertex upload),
  * out[1] = the "shade_specialize" option.  tirt_shade_features_host: the same rule on host tables, without a context or a device
- * (env may be NULL: lit if env_power != 0). */
+ * (env may be NULL: lit if env_power != 0).
+ * tirt_shade_instantiation: the choice itself.  k_shade is compiled for 19 words, kept in one table in this order: 32, 4, 127, 255, 511, then 127 | d and 511 | d for
+ * d = 1024, 2048, 3072, then the same eight (127, 511 and their six twins) | 4096; k_shade_spec for 32, 4, 127.  With M = 1024 | 2048 | 4096 (the derived bits:
+ * "Environment importance sampling", "HDR environment", "Choosing emitters by power") a render launches the first entry e of the table with (e & M) == (word & M),
+ * (word & ~512 & ~e) == 0 and, where specialize is 0, (e & 127) == 127.  feat[0] = e.  spectral 1: PT_Spec's table; its words lie within 127.
+ * TIRT_ERR_ARG: a NULL feat, specialize or spectral neither 0 nor 1, a word with bits at or above 8192, spectral 1 with bits outside 127. */
 int tirt_shade_features(tirt_ctx *ctx, uint32_t *out);
+/* which instantiation a render launches for a feature word as tirt_shade_features reports it (bit 512 ignored); no context, no device */
+int tirt_shade_instantiation(uint32_t word, int specialize, int spectral, uint32_t *feat);
 int tirt_shade_features_host(const float *material, int nm, const int32_t *primitive, int n, const float *shape, int ns,
                              const int32_t *light, int light_count, const int32_t *env, int env_w, int env_h, float env_power,
                              uint32_t *out);
@@ -928,9 +935,10 @@ int tirt_kat_shade_tables(tirt_ctx *ctx, int which, const float *in, float *out,
 /* One shading step of PT_RGB (integrator/PT_RGB.py:66-132 between a closest hit and the next: emission with MIS, glass / Disney, the NEE set-up, the next ray, the
  * miss) by the body of one instantiation of k_shade, on the context's own tables (shading and light records, material colours, environment) -- for
  * tests/test_gpu_shade_step.py against the CPU oracle's orc_kat_shade_step.  One launch, row i on thread i.
- * feat: the feature word of the instantiation -- 32 (sphere lights), 4 (mesh lights), 127 (generic), 255 (generic + albedo textures) or 511 (+ roughness, metallic and normal maps), the ones a render picks from (tirt_shade_features).
- *   With environment importance sampling: 127 | 1024 and 511 | 1024 (they need the context's table: bit 1024 of tirt_shade_features).
- *   With an RGBE8 environment: 127 | 2048, 511 | 2048, 127 | 1024 | 2048 and 511 | 1024 | 2048; feat carries bit 2048 exactly when tirt_shade_features does (TIRT_ERR_ARG otherwise).
+ * feat: the feature word of the instantiation, one of the 19 that tirt_shade_instantiation can return (its table, above) -- 32 (sphere lights), 4 (mesh lights), 127 (generic),
+ *   255 (generic + albedo textures), 511 (+ roughness, metallic and normal maps), and 127 and 511 with each combination of bits 1024, 2048 and 4096.
+ *   Bit 1024 needs the context's environment table and bit 4096 its emitters' table (those bits of tirt_shade_features); feat carries bit 2048 exactly when
+ *   tirt_shade_features does (TIRT_ERR_ARG otherwise).
  * in, 23 words per row (integers as their bit patterns): seed, pixel, frame, bounce, last_bounce; origin3, direction3; t, u, v, prim (t >= 1e6: a miss, prim unused);
  *   throughout3, radiance3, brdf_pdf, perfect_spec.  NaN and infinity in the ray, the barycentrics and the state are data.
  * out, 28 words per row: radiance3, shaded, want_next, next_o3, next_d3, next_thr3, next_pdf, next_spec, want_shadow, sh_o3, sh_d3, sh_c3, sh_expect, sh_dist -- what

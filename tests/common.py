@@ -1,4 +1,4 @@
-"""Shared scene builders for the tests (host side only; no device work here)."""
+"""Shared scene builders for the tests (host side only; the one step onto a device is on_device)."""
 import numpy as np
 
 from ti_raytrace_amd import scenes, Example, PT_RGB
@@ -9,6 +9,28 @@ def host_only(ex, scale=0.8):
     """Run the host half of build_scene (packing + camera) without touching a device."""
     ex.scene.setup_data_cpu()
     ex.frame_camera(scale)
+    return ex
+
+
+def on_device(ex):
+    """The host tables of a scene built on the host (host_only) uploaded to its context, which is returned (GPU tests only)."""
+    ex.integrator.setup_data_cpu(); ex.integrator.setup_data_gpu(); ex.scene.setup_data_gpu()
+    return ex.scene.ctx
+
+
+def step_scene(env):
+    """tests/shade_step_cases.py's material grid under its four emissive triangles AND two sphere lights (a triangle + sphere list), one unused texture (the
+    instantiations with bit 128 / 256 need an uploaded one), and no / an 8-bit / an RGBE8 environment"""
+    import shade_step_cases as cases      # (it imports this module)
+    ex = cases.grid_mesh()
+    ex.add_sphere_light(pos=(0.0, 3.0, 0.0), radius=0.75, emission=50.0)
+    ex.add_sphere_light(pos=(-1.5, 0.5, 2.0), radius=0.2, emission=120.0)
+    ex.scene.add_texture(np.full((2, 2, 3), 128, np.uint8))
+    if env == "ldr":
+        ex.scene.add_env(scenes.sun_sky_image(), 5.0)
+    elif env == "hdr":
+        ex.scene.add_env_hdr(scenes.hdr_sun_sky(), 1.0)
+    host_only(ex)
     return ex
 
 

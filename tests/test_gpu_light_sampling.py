@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import common
+from common import on_device, step_scene
 import cutout_scenes as cs
 import env_sampling_expected as ee
 import env_sampling_scenes as es
@@ -28,11 +29,6 @@ NAN_TRI = np.array([[(0.0, 0.0, 0.0), (0.1, 0.1, 0.1), (0.25, 0.25, 0.25)]])    
 
 def bits(a):
     return np.ascontiguousarray(a, f).view(np.uint32)
-
-
-def on_device(ex):
-    ex.integrator.setup_data_cpu(); ex.integrator.setup_data_gpu(); ex.scene.setup_data_gpu()
-    return ex.scene.ctx
 
 
 def render(ex, frames, calls=(None,), seed=SEED, clear=True):
@@ -173,21 +169,6 @@ FORCED = 150
 U_STEP, P_ENV = 0.25, 0.5
 BRANCHES = ("light_power", "light_uniform", "light_not_facing", "light_pdf0", "emitter_spec", "emitter_mis")
 _step = {}
-
-
-def step_scene(env):
-    """tests/shade_step_cases.py's material grid under its four emissive triangles AND two sphere lights (a triangle + sphere list), one unused texture (the
-    instantiations with bit 128 / 256 need an uploaded one), and no / an 8-bit / an RGBE8 environment"""
-    ex = cases.grid_mesh()
-    ex.add_sphere_light(pos=(0.0, 3.0, 0.0), radius=0.75, emission=50.0)
-    ex.add_sphere_light(pos=(-1.5, 0.5, 2.0), radius=0.2, emission=120.0)
-    ex.scene.add_texture(np.full((2, 2, 3), 128, np.uint8))
-    if env == "ldr":
-        ex.scene.add_env(scenes.sun_sky_image(), 5.0)
-    elif env == "hdr":
-        ex.scene.add_env_hdr(scenes.hdr_sun_sky(), 1.0)
-    common.host_only(ex)
-    return ex
 
 
 def step_rows():

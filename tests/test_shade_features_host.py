@@ -129,5 +129,11 @@ def test_header_binding_and_kernels_agree_on_the_bits():
     dyn = open(os.path.join(ROOT, "ti_raytrace_amd", "csrc", "tirt_dynamic.hip")).read()
     assert api.count("refresh_shade_features(c);") >= 3 and "refresh_shade_features(c);" in dyn      # scene, material, environment; vertex updates
     render = open(os.path.join(ROOT, "ti_raytrace_amd", "csrc", "tirt_render.hip")).read()
-    n_rgb = len(re.findall(r"\bk_shade<SF_\w+, SH_MIN_WAVES\w*>", render)); n_spec = len(re.findall(r"\bk_shade_spec<SF_\w+>", render))
-    assert 2 <= n_rgb <= 6 and 2 <= n_spec <= 6, (n_rgb, n_spec)
+    n_spec = len(re.findall(r"\bk_shade_spec<SF_\w+>", render))
+    assert 2 <= n_spec <= 6, n_spec
+    # k_shade's instantiations are named once, inside shade_inst<>(): one table holds them, and every word the binding lists is an entry that a render can launch
+    assert len(re.findall(r"\bShadeInst\s+\w+\s*\[", render)) == 1 and "KatStepInst" not in render
+    words = _native.SHADE_INSTANTIATIONS + (_native.SHADE_INSTANTIATION_MAPS,) + _native.SHADE_INSTANTIATIONS_ENV + _native.SHADE_INSTANTIATIONS_HDR + _native.SHADE_INSTANTIATIONS_POWER
+    assert len(set(words)) == 19
+    for feat in words:
+        assert _native.shade_instantiation(feat, 1, 0) == feat, feat

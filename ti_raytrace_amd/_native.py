@@ -124,6 +124,7 @@ SIGNATURES = {
     "tirt_texture_cutout": (C.c_int, [_vp, _vp, C.c_int]),
     "tirt_kat_texture_alpha": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
     "tirt_shade_features": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
+    "tirt_shade_instantiation": (C.c_int, [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
     "tirt_shade_features_host": (C.c_int, [_f32p, C.c_int, _i32p, C.c_int, _f32p, C.c_int, _i32p, C.c_int, _vp, C.c_int, C.c_int, C.c_float,
                                            C.POINTER(C.c_uint32)]),
     "tirt_shade_features_host_env": (C.c_int, [_f32p, C.c_int, _i32p, C.c_int, _f32p, C.c_int, _i32p, C.c_int, _vp, C.c_int, C.c_int, C.c_float,
@@ -984,6 +985,13 @@ def texture_cutout(handle, flags, count=None):
     """tirt_texture_cutout on a raw context handle (None: only the refusals that need no context can be reached)"""
     flags = np.ascontiguousarray(flags, np.int32).reshape(-1)
     check(lib().tirt_texture_cutout(handle, _ptr(flags) if flags.size else None, int(flags.size if count is None else count)))
+
+
+def shade_instantiation(word, specialize=True, spectral=False):
+    """include/tirt.h, tirt_shade_instantiation: the word of the instantiation of k_shade (spectral: k_shade_spec) a render launches for a feature word; needs no device."""
+    out = C.c_uint32(0)
+    check(lib().tirt_shade_instantiation(int(word), int(specialize), int(spectral), C.byref(out)))
+    return int(out.value)
 
 
 def shade_features_host(material, primitive, shape, light, light_count, env=None, env_power=0.0):

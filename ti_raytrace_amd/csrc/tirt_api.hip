@@ -752,8 +752,20 @@ int tirt_shade_features(tirt_ctx *c, uint32_t *out)
         TIRT_HIP(hipSetDevice(c->device));
         if (sync_all(c) || ensure_shade_records(c)) return TIRT_ERR_HIP;
     }
-    out[0] = (c->n >= 1 && light_power_active(c) ? (unsigned)SF_LIGHT_POWER : 0u) | c->shade_features | (c->has_cutout ? (unsigned)SF_CUTOUT : 0u) | (env_sample_active(c) ? (unsigned)SF_ENV_SAMPLE : 0u) | (env_hdr_active(c) ? (unsigned)SF_ENV_HDR : 0u);
+    out[0] = shade_word(c) | (c->has_cutout ? (unsigned)SF_CUTOUT : 0u);
     out[1] = c->shade_specialize ? 1u : 0u;
+    return TIRT_OK;
+}
+
+int tirt_shade_instantiation(uint32_t word, int specialize, int spectral, uint32_t *feat)
+{
+    TIRT_REQUIRE(feat, "tirt_shade_instantiation: null pointer");
+    TIRT_REQUIRE((specialize == 0 || specialize == 1) && (spectral == 0 || spectral == 1), "tirt_shade_instantiation: specialize and spectral are 0 or 1");
+    TIRT_REQUIRE(word < 8192u, "tirt_shade_instantiation: the word has bits at or above 8192");
+    TIRT_REQUIRE(!spectral || (word & ~(unsigned)SF_ALL) == 0u, "tirt_shade_instantiation: PT_Spec renders no textured scene and never sees the derived bits: a spectral word lies within 127");
+    unsigned f = 0;
+    TIRT_REQUIRE(shade_instantiation(word, specialize, spectral != 0, &f), "tirt_shade_instantiation: no instantiation serves the word");
+    *feat = f;
     return TIRT_OK;
 }
 

@@ -84,14 +84,14 @@ enum : unsigned {
     SF_ALL = 127u,
     SF_TEXTURE = 128u,        // a material row that is not an emitter's names an uploaded albedo texture (not part of SF_ALL: untextured scenes keep their kernels)
     SF_CUTOUT = 512u,         // a triangle's material row that is not an emitter's names, in word 1, an uploaded texture flagged as a cut-out mask (tirt_texture_cutout): k_trace's
-                              // CUTOUT twins.  Reported by tirt_shade_features; no instantiation of k_shade depends on it (pick_shade_inst never sees it)
+                              // CUTOUT twins.  Reported by tirt_shade_features; no instantiation of k_shade depends on it (pick_shade masks it out)
     SF_TEXTURE_PARAM = 256u,  // a material row that is not an emitter's names an uploaded roughness, metallic or normal texture (words 7..9; implies uvs in the shading records as 128 does)
     SF_ENV_SAMPLE = 1024u,    // environment importance sampling is switched on (tirt_env_sampling), the environment is lit and its sampling table exists: k_shade's ENV twins.
                               // Kept beside tirt_ctx::shade_features as 512 is (k_shade_spec and BDPT never see it); reported by tirt_shade_features
     SF_ENV_HDR = 2048u,       // the uploaded environment is RGBE8 (tirt_env_upload_hdr) and lit (bit 2): k_shade's HDR twins decode its texels.  Derived (env_hdr_active), never stored in
                               // the context's word, reported by tirt_shade_features; the 8-bit kernels are compiled without it and keep their code
     SF_LIGHT_POWER = 4096u,   // emitters are chosen by power (tirt_light_sampling mode 1), the list holds triangles and spheres only and its table has total > 0: k_shade's POWER twins.
-                              // Derived (light_power_active), never stored in the context's word (k_shade_spec, BDPT and pick_shade_inst never see it); reported by tirt_shade_features
+                              // Derived (light_power_active), never stored in the context's word (k_shade_spec and BDPT never see it); reported by tirt_shade_features
     SF_LIGHT_KINDS = SF_LIGHT_TRI | SF_LIGHT_SPOT_LASER | SF_LIGHT_SPHERE | SF_LIGHT_OTHER
 };
 

@@ -571,13 +571,22 @@ int kat_env_lookup(tirt_ctx *c, const float *in, int in_stride, float *out, int 
 // emitters chosen by power (include/tirt.h, "Choosing emitters by power"; tirt_envsample.hip)
 inline bool light_power_wanted(const tirt_ctx *c) { return c->light_sample_mode == 1 && c->light_count > 0 && (c->shade_features & (SF_LIGHT_SPOT_LASER | SF_LIGHT_OTHER)) == 0u; }
 inline bool light_power_active(const tirt_ctx *c) { return light_power_wanted(c) && c->light_tab_valid && c->light_tab_total > 0ull; }      // (after ensure_shade_records)
-int light_table_sync(tirt_ctx *c);             // the tail of ensure_shade_records: the table behind fresh light records, P into (or out of) the emitters' shading records
+// The feature word as tirt_shade_features reports it, SF_CUTOUT aside: the stored word and the three derived bits.  The one place that forms them: the choice of
+// k_shade's instantiation, the checks of tirt_kat_shade_step and the report all read it.  (Bit SF_LIGHT_POWER: after ensure_shade_records)
+constexpr unsigned SF_DERIVED = SF_ENV_SAMPLE | SF_ENV_HDR | SF_LIGHT_POWER;
+inline unsigned shade_word(const tirt_ctx *c)
+{
+    return c->shade_features | (env_sample_active(c) ? (unsigned)SF_ENV_SAMPLE : 0u) | (env_hdr_active(c) ? (unsigned)SF_ENV_HDR : 0u) |
+           (c->n >= 1 && light_power_active(c) ? (unsigned)SF_LIGHT_POWER : 0u);
+}
+int light_table_sync(tirt_ctx *c);           // the tail of ensure_shade_records: the table behind fresh light records, P into (or out of) the emitters' shading records
 int light_table_download(tirt_ctx *c, uint32_t *q, uint64_t *prefix, float *P, int32_t info[4]);
 int kat_light_pick(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n);
 bool light_table_exists_host(const float *material, int nm, const int32_t *primitive, int n, const float *shape, int ns, const float *vertex, int nv, const int32_t *light, int light_count);
 int sync_all(tirt_ctx *c);
 int flush_pending(tirt_ctx *c);
 bool kat_shade_step_has_inst(unsigned feat);      // tirt_render.hip: is `feat` the word of an instantiation of k_shade
+bool shade_instantiation(unsigned word, int specialize, bool spectral, unsigned *feat);      // tirt_render.hip: the word of the instantiation a render launches; false: none
 int kat_shade_step(tirt_ctx *c, unsigned feat, const float *in, int in_stride, float *out, int out_stride, int n);
 
 // The device round trip of a known-answer entry (tirt_kat_*, tirt_spec_table_build), after the entry's own checks: device copies of the inputs (on c->stream;

@@ -303,7 +303,7 @@ int tirt_kat_shade_step(tirt_ctx *c, uint32_t feat, const float *in, int in_stri
     // what needs no context first (and no device: these refusals hold for a null context too)
     TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_shade_step: null pointer or negative n");
     TIRT_REQUIRE(in_stride >= 23 && out_stride >= 28, "tirt_kat_shade_step: stride too small (23 words in, 28 out)");
-    TIRT_REQUIRE(kat_shade_step_has_inst(feat), "tirt_kat_shade_step: feat is not an instantiation of k_shade (SF_LIGHT_SPHERE, SF_LIGHT_TRI, SF_ALL, SF_ALL | SF_TEXTURE, SF_ALL | SF_TEXTURE | SF_TEXTURE_PARAM; SF_ALL and the last also with SF_ENV_SAMPLE)");
+    TIRT_REQUIRE(kat_shade_step_has_inst(feat), "tirt_kat_shade_step: feat is not an instantiation of k_shade (the words tirt_shade_instantiation returns: include/tirt.h, tirt_kat_shade_step)");
     CTX(c);
     return kat_shade_step(c, feat, in, in_stride, out, out_stride, n);
 }

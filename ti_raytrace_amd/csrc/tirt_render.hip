@@ -693,97 +693,57 @@ __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_kat_shade_step(SceneVie
     o[23] = ss.sh_c.x; o[24] = ss.sh_c.y; o[25] = ss.sh_c.z; o[26] = __int_as_float(ss.sh_expect); o[27] = ss.sh_dist;
 }
 
-// ---- the instantiations of the two shading kernels, narrowest first.  pt_render launches the first one whose mask covers the scene's feature word
-// (tirt_ctx::shade_features, refreshed with the tables it is derived from); SF_ALL carries every feature of an untextured scene and serves every other one of
-// those, and all of them when the option "shade_specialize" is 0; behind it SF_ALL with the albedo lookup, for the scenes that have a textured material, and last
-// that kernel with the roughness / metallic / normal-map lookups (SF_TEXTURE_PARAM), for the scenes in which a material names one of those. ----
+// ---- the instantiations of the shading kernels.  One table for PT_RGB (SHADE_RGB: k_shade, its LIST variant and the known-answer twin k_kat_shade_step of every
+// word), one for PT_Spec (SHADE_SPEC_INST), and one rule that chooses from either (pick_shade).  The stored words, narrowest first: sphere lights, mesh lights, SF_ALL
+// -- every feature of an untextured scene; it serves every other one of those, and all of them when the option "shade_specialize" is 0 --, SF_ALL with the albedo
+// lookup, and that with the roughness / metallic / normal-map lookups (SF_TEXTURE_PARAM).  Behind them the twins of SF_ALL and of the kernel with every texture slot
+// for each combination of the three derived bits (SF_DERIVED, tirt_internal.h: the environment's light sample, RGBE8 texels, emitters chosen by power); launch
+// bounds: DESIGN.md, "HDR environment" and the sections before it. ----
 typedef void (*shade_fn_t)(ShadeArgs, SceneView, TileMap, int, uint32_t, uint32_t, int, int, const int *, int, unsigned long long *, DevCounters *, v3);
 typedef void (*shade_spec_fn_t)(ShadeArgs, SceneView, SpecView, TileMap, int, uint32_t, uint32_t, int, int, const int *, int, unsigned long long *, DevCounters *, v3);
-struct ShadeInst { unsigned feat; shade_fn_t fn, fn_list; };      // fn_list: the same kernel for the batches of a pixel set (LIST)
+typedef void (*kat_step_fn_t)(SceneView, const float *, int, float *, int, int);
+struct ShadeInst { unsigned feat; shade_fn_t fn, fn_list; kat_step_fn_t kat; };      // fn_list: the same kernel for the batches of a pixel set (LIST); kat: tirt_kat_shade_step's
 struct ShadeSpecInst { unsigned feat; shade_spec_fn_t fn; };
-constexpr unsigned SF_I_SPHERE = SF_LIGHT_SPHERE;                                   // Disney, sphere lights, black environment: the synthetic headline scene
-constexpr unsigned SF_I_MESH = SF_LIGHT_TRI;                                        // Disney, mesh lights, black environment: Cornell box, Veach
+template <unsigned F, int MW>
+constexpr ShadeInst shade_inst() { return {F, k_shade<F, MW>, k_shade<F, MW, true>, k_kat_shade_step<F, MW>}; }
 // (Built and left out: SF_GLASS | SF_ENV | SF_LIGHT_SPHERE for Teapot and the gallery spheres -- 3 509 VALU against the generic 3 872, but 12 bytes of scratch at
 // the 96-VGPR limit where the generic kernel has none; those scenes stay on the generic kernel.)
 constexpr unsigned SF_I_MAPS = SF_ALL | SF_TEXTURE | SF_TEXTURE_PARAM;               // every texture slot of a material row
-static const ShadeInst SHADE_INST[] = {
-    {SF_I_SPHERE, k_shade<SF_I_SPHERE, SH_MIN_WAVES_NARROW>, k_shade<SF_I_SPHERE, SH_MIN_WAVES_NARROW, true>},
-    {SF_I_MESH, k_shade<SF_I_MESH, SH_MIN_WAVES_NARROW>, k_shade<SF_I_MESH, SH_MIN_WAVES_NARROW, true>},
-    {SF_ALL, k_shade<SF_ALL, SH_MIN_WAVES>, k_shade<SF_ALL, SH_MIN_WAVES, true>},
-    {SF_ALL | SF_TEXTURE, k_shade<SF_ALL | SF_TEXTURE, SH_MIN_WAVES>, k_shade<SF_ALL | SF_TEXTURE, SH_MIN_WAVES, true>},      // textured scenes: the generic kernel + the albedo lookup
-    {SF_I_MAPS, k_shade<SF_I_MAPS, SH_MIN_WAVES_MAPS>, k_shade<SF_I_MAPS, SH_MIN_WAVES_MAPS, true>}};                              // + roughness, metallic and normal maps
-// environment importance sampling on (tirt_env_sampling), environment lit, table built: the generic kernel or the one with every texture slot, each with the
-// environment's light sample and MIS weights (SF_ENV_SAMPLE).  A table of their own: SHADE_INST, its order and its fall-back are what they were
-constexpr unsigned SF_I_ENV = SF_ALL | SF_ENV_SAMPLE, SF_I_ENV_MAPS = SF_I_MAPS | SF_ENV_SAMPLE;
-static const ShadeInst SHADE_ENV_INST[] = {
-    {SF_I_ENV, k_shade<SF_I_ENV, SH_MIN_WAVES_ENV>, k_shade<SF_I_ENV, SH_MIN_WAVES_ENV, true>},
-    {SF_I_ENV_MAPS, k_shade<SF_I_ENV_MAPS, SH_MIN_WAVES_ENV>, k_shade<SF_I_ENV_MAPS, SH_MIN_WAVES_ENV, true>}};
-// an RGBE8 environment that is lit (SF_ENV_HDR; tirt_env_upload_hdr): twins of the generic kernel and of the one with every texture slot, without and with the
-// environment's light sample, in tables of their own -- entry 0 an untextured scene's, entry 1 a textured one's.  Launch bounds: each twin's 8-bit sibling's, but for
-// the generic twin, which has SH_MIN_WAVES_HDR ("HDR environment": no scratch at any of them)
-constexpr unsigned SF_I_HDR = SF_ALL | SF_ENV_HDR, SF_I_HDR_MAPS = SF_I_MAPS | SF_ENV_HDR, SF_I_ENV_HDR = SF_I_ENV | SF_ENV_HDR, SF_I_ENV_HDR_MAPS = SF_I_ENV_MAPS | SF_ENV_HDR;
-template <unsigned F, int MW>
-constexpr ShadeInst shade_inst() { return {F, k_shade<F, MW>, k_shade<F, MW, true>}; }      // a table entry: the word, the kernel and its LIST variant
-static const ShadeInst SHADE_HDR_INST[] = {shade_inst<SF_I_HDR, SH_MIN_WAVES_HDR>(), shade_inst<SF_I_HDR_MAPS, SH_MIN_WAVES_MAPS>()};
-static const ShadeInst SHADE_ENV_HDR_INST[] = {shade_inst<SF_I_ENV_HDR, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_ENV_HDR_MAPS, SH_MIN_WAVES_ENV>()};
-// emitters chosen by power (SF_LIGHT_POWER; tirt_light_sampling): a twin of each of the eight kernels above that serve a generic scene -- without and with every texture slot,
-// the environment's light sample, an RGBE8 environment -- in a table of its own, indexed by those three bits.  Launch bounds: each twin's sibling's
-constexpr unsigned SF_P = SF_LIGHT_POWER;
-static const ShadeInst SHADE_POWER_INST[8] = {
+constexpr unsigned SF_E = SF_ENV_SAMPLE, SF_H = SF_ENV_HDR, SF_P = SF_LIGHT_POWER;
+static const ShadeInst SHADE_RGB[] = {
+    shade_inst<SF_LIGHT_SPHERE, SH_MIN_WAVES_NARROW>(),      // Disney, sphere lights, black environment: the synthetic headline scene
+    shade_inst<SF_LIGHT_TRI, SH_MIN_WAVES_NARROW>(),         // Disney, mesh lights, black environment: Cornell box, Veach
+    shade_inst<SF_ALL, SH_MIN_WAVES>(),
+    shade_inst<SF_ALL | SF_TEXTURE, SH_MIN_WAVES>(),         // textured scenes: the generic kernel + the albedo lookup
+    shade_inst<SF_I_MAPS, SH_MIN_WAVES_MAPS>(),              // + roughness, metallic and normal maps
+    shade_inst<SF_ALL | SF_E, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_MAPS | SF_E, SH_MIN_WAVES_ENV>(),
+    shade_inst<SF_ALL | SF_H, SH_MIN_WAVES_HDR>(), shade_inst<SF_I_MAPS | SF_H, SH_MIN_WAVES_MAPS>(),
+    shade_inst<SF_ALL | SF_E | SF_H, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_MAPS | SF_E | SF_H, SH_MIN_WAVES_ENV>(),
     shade_inst<SF_ALL | SF_P, SH_MIN_WAVES_POWER>(), shade_inst<SF_I_MAPS | SF_P, SH_MIN_WAVES_MAPS>(),
-    shade_inst<SF_I_ENV | SF_P, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_ENV_MAPS | SF_P, SH_MIN_WAVES_ENV>(),
-    shade_inst<SF_I_HDR | SF_P, SH_MIN_WAVES_POWER>(), shade_inst<SF_I_HDR_MAPS | SF_P, SH_MIN_WAVES_MAPS>(),
-    shade_inst<SF_I_ENV_HDR | SF_P, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_ENV_HDR_MAPS | SF_P, SH_MIN_WAVES_ENV>()};
+    shade_inst<SF_ALL | SF_E | SF_P, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_MAPS | SF_E | SF_P, SH_MIN_WAVES_ENV>(),
+    shade_inst<SF_ALL | SF_H | SF_P, SH_MIN_WAVES_POWER>(), shade_inst<SF_I_MAPS | SF_H | SF_P, SH_MIN_WAVES_MAPS>(),
+    shade_inst<SF_ALL | SF_E | SF_H | SF_P, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_MAPS | SF_E | SF_H | SF_P, SH_MIN_WAVES_ENV>()};
 static const ShadeSpecInst SHADE_SPEC_INST[] = {
-    {SF_I_SPHERE, k_shade_spec<SF_I_SPHERE>}, {SF_I_MESH, k_shade_spec<SF_I_MESH>}, {SF_ALL, k_shade_spec<SF_ALL>}};
+    {SF_LIGHT_SPHERE, k_shade_spec<SF_LIGHT_SPHERE>}, {SF_LIGHT_TRI, k_shade_spec<SF_LIGHT_TRI>}, {SF_ALL, k_shade_spec<SF_ALL>}};
+// The rule: the first entry, in table order, that carries exactly the word's derived bits and covers its other bits (SF_CUTOUT aside: no instantiation depends on it);
+// with specialize == 0 only the entries that carry all of SF_ALL.  Null where the table has none: no word that a context can hold
 template <class T, size_t N>
-static const T &pick_shade_inst(const T (&tab)[N], const tirt_ctx *c)
+static const T *pick_shade(const T (&tab)[N], unsigned word, int specialize)
 {
-    size_t k = 0;
-    if (!c->shade_specialize) while (k + 1 < N && tab[k].feat != SF_ALL) k++;      // from the generic kernel on: behind it only what SF_ALL does not cover
-    for (; k + 1 < N; k++) if ((c->shade_features & ~tab[k].feat) == 0u) return tab[k];
-    return tab[N - 1];
+    for (const T &e : tab)
+        if ((e.feat & SF_DERIVED) == (word & SF_DERIVED) && (word & ~SF_CUTOUT & ~e.feat) == 0u && (specialize || (e.feat & SF_ALL) == SF_ALL)) return &e;
+    return nullptr;
 }
-static const ShadeInst &pick_shade_rgb(const tirt_ctx *c)
+bool shade_instantiation(unsigned word, int specialize, bool spectral, unsigned *feat)      // behind tirt_shade_instantiation: the rule, no context
 {
-    if (light_power_active(c)) return SHADE_POWER_INST[(env_hdr_active(c) ? 4 : 0) + (env_sample_active(c) ? 2 : 0) + ((c->shade_features & ~SF_ALL) ? 1 : 0)];
-    if (env_hdr_active(c)) return (env_sample_active(c) ? SHADE_ENV_HDR_INST : SHADE_HDR_INST)[(c->shade_features & ~SF_ALL) ? 1 : 0];
-    if (env_sample_active(c)) return SHADE_ENV_INST[(c->shade_features & ~SF_ALL) ? 1 : 0];
-    return pick_shade_inst(SHADE_INST, c);
+    if (spectral) { const ShadeSpecInst *e = pick_shade(SHADE_SPEC_INST, word, specialize); if (e) *feat = e->feat; return e != nullptr; }
+    const ShadeInst *e = pick_shade(SHADE_RGB, word, specialize); if (e) *feat = e->feat; return e != nullptr;
 }
 
-// ---- the instantiations of k_kat_shade_step, and the entry behind tirt_kat_shade_step ----
-typedef void (*kat_step_fn_t)(SceneView, const float *, int, float *, int, int);
-struct KatStepInst { unsigned feat; kat_step_fn_t fn; };
-static const KatStepInst KAT_STEP_INST[] = {       // one per entry of SHADE_INST, same word, same launch bounds
-    {SF_I_SPHERE, k_kat_shade_step<SF_I_SPHERE, SH_MIN_WAVES_NARROW>}, {SF_I_MESH, k_kat_shade_step<SF_I_MESH, SH_MIN_WAVES_NARROW>},
-    {SF_ALL, k_kat_shade_step<SF_ALL, SH_MIN_WAVES>}, {SF_ALL | SF_TEXTURE, k_kat_shade_step<SF_ALL | SF_TEXTURE, SH_MIN_WAVES>},
-    {SF_I_MAPS, k_kat_shade_step<SF_I_MAPS, SH_MIN_WAVES_MAPS>}};
-static_assert(sizeof(KAT_STEP_INST) / sizeof(KAT_STEP_INST[0]) == sizeof(SHADE_INST) / sizeof(SHADE_INST[0]), "one known-answer kernel per instantiation of k_shade");
-static const KatStepInst KAT_STEP_ENV_INST[] = {   // one per entry of SHADE_ENV_INST
-    {SF_I_ENV, k_kat_shade_step<SF_I_ENV, SH_MIN_WAVES_ENV>}, {SF_I_ENV_MAPS, k_kat_shade_step<SF_I_ENV_MAPS, SH_MIN_WAVES_ENV>}};
-static_assert(sizeof(KAT_STEP_ENV_INST) / sizeof(KAT_STEP_ENV_INST[0]) == sizeof(SHADE_ENV_INST) / sizeof(SHADE_ENV_INST[0]), "one known-answer kernel per instantiation of k_shade");
-static const KatStepInst KAT_STEP_HDR_INST[] = {   // one per entry of SHADE_HDR_INST
-    {SF_I_HDR, k_kat_shade_step<SF_I_HDR, SH_MIN_WAVES_HDR>}, {SF_I_HDR_MAPS, k_kat_shade_step<SF_I_HDR_MAPS, SH_MIN_WAVES_MAPS>}};
-static_assert(sizeof(KAT_STEP_HDR_INST) / sizeof(KAT_STEP_HDR_INST[0]) == sizeof(SHADE_HDR_INST) / sizeof(SHADE_HDR_INST[0]), "one known-answer kernel per instantiation of k_shade");
-static const KatStepInst KAT_STEP_ENV_HDR_INST[] = {   // one per entry of SHADE_ENV_HDR_INST
-    {SF_I_ENV_HDR, k_kat_shade_step<SF_I_ENV_HDR, SH_MIN_WAVES_ENV>}, {SF_I_ENV_HDR_MAPS, k_kat_shade_step<SF_I_ENV_HDR_MAPS, SH_MIN_WAVES_ENV>}};
-static_assert(sizeof(KAT_STEP_ENV_HDR_INST) / sizeof(KAT_STEP_ENV_HDR_INST[0]) == sizeof(SHADE_ENV_HDR_INST) / sizeof(SHADE_ENV_HDR_INST[0]), "one known-answer kernel per instantiation of k_shade");
-template <unsigned F, int MW>
-constexpr KatStepInst kat_inst() { return {F, k_kat_shade_step<F, MW>}; }
-static const KatStepInst KAT_STEP_POWER_INST[8] = {   // one per entry of SHADE_POWER_INST
-    kat_inst<SF_ALL | SF_P, SH_MIN_WAVES_POWER>(), kat_inst<SF_I_MAPS | SF_P, SH_MIN_WAVES_MAPS>(),
-    kat_inst<SF_I_ENV | SF_P, SH_MIN_WAVES_ENV>(), kat_inst<SF_I_ENV_MAPS | SF_P, SH_MIN_WAVES_ENV>(),
-    kat_inst<SF_I_HDR | SF_P, SH_MIN_WAVES_POWER>(), kat_inst<SF_I_HDR_MAPS | SF_P, SH_MIN_WAVES_MAPS>(),
-    kat_inst<SF_I_ENV_HDR | SF_P, SH_MIN_WAVES_ENV>(), kat_inst<SF_I_ENV_HDR_MAPS | SF_P, SH_MIN_WAVES_ENV>()};
-
+// ---- the entry behind tirt_kat_shade_step: the known-answer twin of the instantiation whose word is exactly `feat` ----
 static kat_step_fn_t kat_step_inst(unsigned feat)
 {
-    for (const KatStepInst &k : KAT_STEP_INST) if (k.feat == feat) return k.fn;
-    for (const KatStepInst &k : KAT_STEP_ENV_INST) if (k.feat == feat) return k.fn;
-    for (const KatStepInst &k : KAT_STEP_HDR_INST) if (k.feat == feat) return k.fn;
-    for (const KatStepInst &k : KAT_STEP_ENV_HDR_INST) if (k.feat == feat) return k.fn;
-    for (const KatStepInst &k : KAT_STEP_POWER_INST) if (k.feat == feat) return k.fn;
+    for (const ShadeInst &e : SHADE_RGB) if (e.feat == feat) return e.kat;
     return nullptr;
 }
 bool kat_shade_step_has_inst(unsigned feat) { return kat_step_inst(feat) != nullptr; }
@@ -791,12 +751,13 @@ bool kat_shade_step_has_inst(unsigned feat) { return kat_step_inst(feat) != null
 int kat_shade_step(tirt_ctx *c, unsigned feat, const float *in, int in_stride, float *out, int out_stride, int n)
 {
     TIRT_REQUIRE(c->n >= 1, "tirt_kat_shade_step: no scene");
-    TIRT_REQUIRE((c->shade_features & ~feat) == 0u, "tirt_kat_shade_step: feat does not cover the scene's feature word (tirt_shade_features)");
-    TIRT_REQUIRE(((feat & SF_ENV_HDR) != 0u) == env_hdr_active(c), "tirt_kat_shade_step: an instantiation with bit 2048 reads RGBE8 texels and one without it 8-bit texels: feat must carry the bit exactly when tirt_shade_features does");
-    TIRT_REQUIRE(!(feat & SF_ENV_SAMPLE) || env_sample_active(c), "tirt_kat_shade_step: an instantiation with bit 1024 needs the environment's sampling table (tirt_env_sampling on, a lit environment)");
+    const unsigned word = shade_word(c);           // (bit 4096 of it counts only after ensure_shade_records: read again below)
+    TIRT_REQUIRE((word & ~SF_DERIVED & ~feat) == 0u, "tirt_kat_shade_step: feat does not cover the scene's feature word (tirt_shade_features)");
+    TIRT_REQUIRE(((feat ^ word) & SF_ENV_HDR) == 0u, "tirt_kat_shade_step: an instantiation with bit 2048 reads RGBE8 texels and one without it 8-bit texels: feat must carry the bit exactly when tirt_shade_features does");
+    TIRT_REQUIRE((feat & SF_ENV_SAMPLE & ~word) == 0u, "tirt_kat_shade_step: an instantiation with bit 1024 needs the environment's sampling table (tirt_env_sampling on, a lit environment)");
     if (feat & SF_LIGHT_POWER) {                   // the table is built with the light records, lazily
         if (sync_all(c) || ensure_shade_records(c)) return TIRT_ERR_HIP;
-        TIRT_REQUIRE(light_power_active(c), "tirt_kat_shade_step: an instantiation with bit 4096 needs the emitters' table (tirt_light_sampling mode 1, triangle and sphere emitters only, total > 0)");
+        TIRT_REQUIRE(shade_word(c) & SF_LIGHT_POWER, "tirt_kat_shade_step: an instantiation with bit 4096 needs the emitters' table (tirt_light_sampling mode 1, triangle and sphere emitters only, total > 0)");
     }
     const kat_step_fn_t fn = kat_step_inst(feat);
     TIRT_REQUIRE(fn, "tirt_kat_shade_step: feat is not an instantiation of k_shade");
@@ -969,6 +930,12 @@ static int submit_batch(tirt_ctx *c, const RenderCall &r, Lane &L, uint32_t f0, 
     auto cnt_path = [&](int b) { return (const int *)append_ctr(b - 1); };           // live paths entering bounce b >= 1
     auto cnt_shadow = [&](int b) { return (const int *)append_ctr(b) + 1; };         // shadow rays made by bounce b
     auto fetch = [&](int launch) { return (int *)(cm + LINE * (size_t)(max_depth + 1)) + (size_t)launch * TR_FETCH_STRIDE * TR_FETCH_LINES; };
+    // the batch's shading kernel (after pt_render's ensure_shade_records: shade_word).  PT_Spec never sees the derived bits, and refuses the textured scenes
+    const ShadeInst *const rgb_inst = spec ? nullptr : pick_shade(SHADE_RGB, shade_word(c), c->shade_specialize);
+    const ShadeSpecInst *const spec_inst = spec ? pick_shade(SHADE_SPEC_INST, c->shade_features, c->shade_specialize) : nullptr;
+    TIRT_REQUIRE(rgb_inst || spec_inst, "render: no instantiation of the shading kernel serves the scene's feature word " + std::to_string(shade_word(c)) + " (tirt_shade_instantiation)");
+    const shade_fn_t shade_fn = !rgb_inst ? nullptr : r.list ? rgb_inst->fn_list : rgb_inst->fn;
+    const shade_spec_fn_t shade_spec_fn = spec_inst ? spec_inst->fn : nullptr;
 
     TIRT_HIP(hipStreamWaitEvent(st, c->ev_main, 0));
     hipEvent_t r0, r1;
@@ -991,8 +958,6 @@ static int submit_batch(tirt_ctx *c, const RenderCall &r, Lane &L, uint32_t f0, 
     const int sh_cap = two_big ? 2 * c->sh_grid : c->sh_grid;
     int grid_shade = (S + SH_BLOCK - 1) / SH_BLOCK; if (grid_shade > sh_cap) grid_shade = sh_cap;
     v3 eye_v; eye_v.x = c->cam.eye[0]; eye_v.y = c->cam.eye[1]; eye_v.z = c->cam.eye[2];
-    const shade_fn_t shade_fn = r.list ? pick_shade_rgb(c).fn_list : pick_shade_rgb(c).fn;
-    const shade_spec_fn_t shade_spec_fn = pick_shade_inst(SHADE_SPEC_INST, c).fn;
     const TraceArgs base = batch_trace_args(c, r, L);
     for (int b = 0; b < max_depth; b++) {
         const PathSoA &in = L.ps.st[b & 1], &out = L.ps.st[(b + 1) & 1];
