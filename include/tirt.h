@@ -846,6 +846,52 @@ int tirt_closest_point(tirt_ctx *ctx, const float *points, int n, const float *d
                        float *out_d2, int32_t *out_prim, float *out_point, float *out_uv, int32_t *counts);
 int tirt_kat_closest_point(tirt_ctx *ctx, const float *in, int n, int is_sphere, float *out);
 
+/* Signed distance (no reference counterpart; csrc/tirt_signed_distance.hip, sd_sign in csrc/tirt_closest_point.h): the distance of "Closest point" with the
+ * sign of the angle-weighted pseudo-normal of the closest FEATURE -- face, edge or vertex (Baerentzen & Aanaes, "Signed distance computation using the
+ * angle weighted pseudonormal", 2005).  The face normal of the winning triangle alone is wrong at sharp and concave vertices and edges, where several
+ * triangles tie.  All fp32, every operation in the order written, no contraction, dot as above, cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z,
+ * a.x*b.y - a.y*b.x); tm_sqrt / tm_atan2 are csrc/tirt_math.h's.
+ * Feature of a closest point, from the (u, v) of "Closest point" alone -- the first line that holds:
+ *     v == 0 and u == 0: A     v == 0 and u == 1: B     v == 0: AB     u == 0 and v == 1: C     u == 0: AC     u == 1.0f - v: BC     else: interior
+ *   (the BC region forms u = 1 - w, v = w, so its test is exact; an interior result that rounding puts on an edge counts as that edge).
+ * Per triangle t with corners a, b, c (the bits of its vertex rows): g = cross(b - a, c - a), l2 = dot(g, g); t is VALID iff 0 < l2 < +inf;
+ *   n^ = g / tm_sqrt(l2) per component; the angle at a corner with leaving edges e1, e2 is alpha = tm_atan2(tm_sqrt(dot(x, x)), dot(e1, e2)), x = cross(e1, e2),
+ *   with (e1, e2) = (b - a, c - a) at a, (c - b, a - b) at b, (a - c, b - c) at c.  I(x) = (int64) rintf(x * 1073741824.0f).
+ * Vertex sum of a corner at position v: over all valid triangles t' of any primitive id (t included) with a corner at a position == v (three fp32 ==: -0
+ *   equals +0, a NaN equals nothing), the 64-bit integer sums of I(alpha' * n^'.x), I(alpha' * n^'.y), I(alpha' * n^'.z), alpha' the angle at that corner.
+ * Edge sum of an edge (v0, v1) of t: over all valid t' that SHARE it -- a corner of t' == v0 and the corner after or before it == v1 --, the sums of
+ *   I(n^'.x), I(n^'.y), I(n^'.z).  Its class counts the sharing t' of another primitive id: 0 closed (one, running v1 -> v0), 1 boundary (none),
+ *   2 non-manifold (two or more), 3 flipped (one, running v0 -> v1).  The edges of t are AB = (a, b), BC = (b, c), CA = (c, a).
+ * The table: float4[7] per primitive id, rows interior, A, B, C, AB, AC, BC.  Row 0 .xyz = n^ (whatever the divisions yield for an invalid t), the others
+ *   (float) of the three sums (round to nearest; not normalised, only the direction matters) with .w = 0.  Row 0 .w as an int: the classes of AB, BC, CA in bits
+ *   0-1, 2-3, 4-5, bit 6 = t is invalid.  Spheres, spots and lasers: all zero.  Integer sums: the table does not depend on the order anything is visited in.
+ * The answer: with D2, prim, Q, u, v of "Closest point", for a triangle s = dot(p - Q, N.xyz) with N the row of the feature, d = tm_sqrt(D2),
+ *   sd = s < 0 ? -d : d (s == 0 and a NaN s: positive); for an analytic sphere sd = len < r ? -d : d with len as "Closest point" forms it; nothing found: +inf.
+ *   Negative is inside for a closed, consistently oriented mesh (and for unions of disjoint ones), "behind the sheet" for an open one; solids that
+ *   intersect are not resolved; alpha cut-outs are ignored as above.
+ * The table is context state, built ON THE DEVICE by the first signed query after tirt_scene_upload, tirt_vertex_update[_device] or tirt_lbvh_build dropped it:
+ *   one lane per triangle corner walks the quantised nodes to every triangle that touches the corner's position, on the context's stream, inside the
+ *   query's own ordering: no host sync (allocating the table, on first use or for a larger scene, waits for the context's stream as growing any of its
+ *   scratch buffers does).  Its stack is the query's stack_size (4-byte entries, the first 16 in LDS).  An entry that does not fit loses
+ *   the table: every sd answered from it is NaN and the corners count in stack_overflow (tirt_stats: TIRT_ERR_STACK); the entries that wait for the
+ *   device anyway -- tirt_signed_distance, _prepare, _table_download -- return TIRT_ERR_STACK themselves.  The next signed call with a larger stack_size
+ *   builds it again.
+ * tirt_query_signed_distance: tirt_query_closest_point with out_sd[n] (required; the other outputs stay optional); the same flags, chunks and refusals.
+ * tirt_signed_distance: host arrays, synchronous, as tirt_closest_point (56 bytes of scratch per query).
+ * tirt_signed_distance_prepare: builds the table now (with the largest stack, 4096, unless one stands), waits, and reports report[0..4] = triangle edges
+ *   that are boundary, non-manifold, flipped; invalid triangles; primitives.  All four zero: every mesh of the scene is closed and consistently oriented.
+ * tirt_signed_distance_table_download: the same, and the table as out[n * 28] floats.
+ * tirt_kat_signed_distance: rows of 33 floats (p3, a3, b3, c3, N[7][3]) through cp_triangle and sd_sign to rows of 2 floats: sd, the feature's row index. */
+int tirt_query_signed_distance(tirt_ctx *ctx, const float *points, int64_t n, int64_t point_stride,
+                               const float *dmax, int64_t dmax_stride, float dmax_all, int stack_size, int flags,
+                               float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride,
+                               float *out_uv, int64_t uv_stride, int32_t *counts, void *stream, float *out_sd);
+int tirt_signed_distance(tirt_ctx *ctx, const float *points, int n, const float *dmax, int stack_size, int flags,
+                         float *out_d2, int32_t *out_prim, float *out_point, float *out_uv, int32_t *counts, float *out_sd);
+int tirt_signed_distance_prepare(tirt_ctx *ctx, int64_t report[5]);
+int tirt_signed_distance_table_download(tirt_ctx *ctx, float *out);
+int tirt_kat_signed_distance(tirt_ctx *ctx, const float *in, int n, float *out);
+
 /* Multi-GPU without a Python framework in the loop (the reference has nothing here): ONE host thread drives
  * ndev contexts, one per device of the node, each created with tirt_film_create(..., tile_rank = i, tile_count = ndev, ...).
  * tirt_comm_init builds one RCCL communicator over them (librccl is loaded on first use); tirt_film_reduce sums the films

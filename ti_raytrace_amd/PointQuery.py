@@ -3,12 +3,20 @@
 
     q = PointQuery(scene, stack_size=64, flags=0)         # scene after setup_data_gpu() (Example.build_scene)
     h = q.closest(points, max_distance=None, attributes=False)      # PointHits(dist2 [N] f32, prim [N] i32, point [N, 3] or None, uv [N, 2] or None)
+    s = q.signed_distance(points, max_distance=None, attributes=False)      # SignedHits(dist [N] f32, prim, point, uv): dist < 0 inside
+    m = q.inside(points)                                  # [N] bool
+    r = q.mesh_report()                                   # {"boundary_edges", "nonmanifold_edges", "flipped_edges", "invalid_triangles", "primitives", "closed"}
 
 ``points`` is a float32 tensor ``[N, C >= 3]`` on the scene context's device with ``stride(1) == 1`` and any row stride (an ``[N, 8]``
 tensor's ``[:, :3]`` view works).  ``max_distance``: None (no bound), a float for every query, or an ``[N]`` float32 tensor on the same
 device (any positive stride); a negative or NaN bound finds nothing.  Nothing found: ``prim = -1``, ``dist2 = inf``, point and uv 0.
 ``uv`` is the hit record's convention (``point = a + u (b - a) + v (c - a)``).  The outputs come from ``torch.empty`` and the work is
 queued on ``torch.cuda.current_stream(device)``: nothing waits for it on the host.
+
+``signed_distance`` is ``closest`` with the sign of the angle-weighted pseudo-normal of the closest face, edge or vertex (include/tirt.h, "Signed
+distance"): ``dist = -sqrt(dist2)`` inside a closed, consistently oriented mesh or an analytic sphere, ``+sqrt(dist2)`` outside and on the surface,
+``inf`` where nothing is found.  The first signed call after the geometry changed builds the table of pseudo-normals on the device, on the same stream
+(no host sync); ``mesh_report()`` builds it at once, waits, and says whether the meshes are closed -- on an open mesh the sign is "which side of the sheet".
 """
 import collections
 import os
@@ -16,6 +24,7 @@ import os
 from . import _native
 
 PointHits = collections.namedtuple("PointHits", ["dist2", "prim", "point", "uv"])
+SignedHits = collections.namedtuple("SignedHits", ["dist", "prim", "point", "uv"])
 
 
 def _torch():
@@ -107,6 +116,32 @@ class PointQuery:
                                                out_d2=d2.data_ptr(), out_prim=prim.data_ptr(), out_point=point.data_ptr() if attributes else 0,
                                                out_uv=uv.data_ptr() if attributes else 0, stream=stream)
         return PointHits(d2, prim, point, uv)
+
+    def signed_distance(self, points, max_distance=None, attributes=False):
+        """The signed distance to the nearest surface point of every query, bit for bit Context.signed_distance's: dist (inf where nothing is found; negative
+        inside), prim (-1) and, with attributes=True, the point and its (u, v) -- those three are closest()'s.  Asynchronous on the current stream."""
+        torch = self.torch
+        dev, n, stride = self._check_points(points, "signed_distance")
+        dptr, dstride, dall = self._check_bound(max_distance, dev, n, "signed_distance")
+        sd = torch.empty(n, dtype=torch.float32, device=dev)
+        prim = torch.empty(n, dtype=torch.int32, device=dev)
+        point = torch.empty((n, 3), dtype=torch.float32, device=dev) if attributes else None
+        uv = torch.empty((n, 2), dtype=torch.float32, device=dev) if attributes else None
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self.scene.ctx.query_signed_distance(points.data_ptr(), n, stride, sd.data_ptr(), self.stack_size, self.flags, dmax=dptr, dmax_stride=dstride,
+                                                 dmax_all=dall, out_prim=prim.data_ptr(), out_point=point.data_ptr() if attributes else 0,
+                                                 out_uv=uv.data_ptr() if attributes else 0, stream=stream)
+        return SignedHits(sd, prim, point, uv)
+
+    def inside(self, points):
+        """[N] bool: signed_distance(points).dist < 0"""
+        return self.signed_distance(points).dist < 0
+
+    def mesh_report(self):
+        """Builds the pseudo-normal table now and waits for it: the counts of triangle edges that are boundary, non-manifold and flipped, of invalid
+        (zero-area or non-finite) triangles and of primitives, and closed = the first four are zero (the sign means inside / outside everywhere)"""
+        return self.scene.ctx.signed_distance_prepare()
 
     def closest_counts(self, points, max_distance=None):
         """closest() with the per-query N_box / N_leaf counts ([N, 2] int32) of a COUNT_NODES walk: (PointHits, counts)"""

@@ -46,6 +46,9 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# the counts of tirt_signed_distance_prepare, in its order
+SD_REPORT = ("boundary_edges", "nonmanifold_edges", "flipped_edges", "invalid_triangles", "primitives")
+
 TRAVERSE_ORDERED = 0
 TRAVERSE_EXHAUSTIVE = 1
 COUNT_NODES = 2
@@ -176,6 +179,12 @@ SIGNATURES = {
                                            _vp, C.c_int64, _vp, _vp]),
     "tirt_closest_point": (C.c_int, [_vp, _f32p, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "tirt_kat_closest_point": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, _f32p]),
+    "tirt_query_signed_distance": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64,
+                                             _vp, C.c_int64, _vp, _vp, _vp]),
+    "tirt_signed_distance": (C.c_int, [_vp, _f32p, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tirt_signed_distance_prepare": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "tirt_signed_distance_table_download": (C.c_int, [_vp, _f32p]),
+    "tirt_kat_signed_distance": (C.c_int, [_vp, _f32p, C.c_int, _f32p]),
     "tirt_comm_init": (C.c_int, [C.POINTER(_vp), C.c_int]),
     "tirt_film_reduce": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int]),
     "tirt_comm_destroy": (C.c_int, [C.POINTER(_vp), C.c_int]),
@@ -887,6 +896,55 @@ class Context:
         rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 7 if is_sphere else 12)
         out = np.zeros((rows.shape[0], 6), np.float32)
         check(lib().tirt_kat_closest_point(self.handle, rows.reshape(-1), rows.shape[0], 1 if is_sphere else 0, out.reshape(-1)))
+        return out
+
+    def query_signed_distance(self, points, n, point_stride, out_sd, stack_size=64, flags=0, dmax=0, dmax_stride=1, dmax_all=float("inf"), out_d2=0,
+                              out_prim=0, out_point=0, point_out_stride=3, out_uv=0, uv_stride=2, counts=0, stream=0):
+        """tirt_query_signed_distance on device memory (include/tirt.h, "Signed distance"): query_closest_point with out_sd; the first call after the
+        geometry changed builds the pseudo-normal table on the context's stream.  ti_raytrace_amd.PointQuery is the torch front end."""
+        check(lib().tirt_query_signed_distance(self.handle, _vp(int(points) or None), int(n), int(point_stride), _vp(int(dmax) or None), int(dmax_stride),
+                                               float(dmax_all), int(stack_size), int(flags), _vp(int(out_d2) or None), _vp(int(out_prim) or None),
+                                               _vp(int(out_point) or None), int(point_out_stride), _vp(int(out_uv) or None), int(uv_stride),
+                                               _vp(int(counts) or None), _vp(int(stream) or None), _vp(int(out_sd) or None)))
+
+    def signed_distance(self, points, max_distance=None, stack_size=64, flags=0, attributes=True):
+        """tirt_signed_distance, the host route: as closest_point, with the signed distance first ->
+        (dist (n,), dist2 (n,), prim (n,), point (n, 3) or None, uv (n, 2) or None, counts (n, 2) or None [COUNT_NODES])"""
+        points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = points.shape[0]
+        dmax = None
+        if max_distance is not None:
+            dmax = np.ascontiguousarray(np.broadcast_to(np.asarray(max_distance, np.float32), (n,)))
+        sd = np.zeros(n, np.float32)
+        d2 = np.zeros(n, np.float32)
+        prim = np.zeros(n, np.int32)
+        point = np.zeros((n, 3), np.float32) if attributes else None
+        uv = np.zeros((n, 2), np.float32) if attributes else None
+        counts = np.zeros((n, 2), np.int32) if (flags & COUNT_NODES) else None
+        check(lib().tirt_signed_distance(self.handle, points.reshape(-1), n, _ptr(dmax), int(stack_size), int(flags), _ptr(d2), _ptr(prim),
+                                         _ptr(point), _ptr(uv), _ptr(counts), _ptr(sd)))
+        return sd, d2, prim, point, uv, counts
+
+    def signed_distance_prepare(self):
+        """tirt_signed_distance_prepare: builds the table now and waits -> the five counts as a dict, and `closed` (the first four are zero)"""
+        out = (C.c_int64 * 5)()
+        check(lib().tirt_signed_distance_prepare(self.handle, out))
+        r = dict(zip(SD_REPORT, (int(x) for x in out)))
+        r["closed"] = not any(r[k] for k in SD_REPORT[:4])
+        return r
+
+    def signed_distance_table(self):
+        """tirt_signed_distance_table_download: (n, 7, 4) float32 -- rows interior, A, B, C, AB, AC, BC; [:, 0, 3] viewed as int32 holds the edge classes"""
+        n = self.signed_distance_prepare()["primitives"]
+        out = np.zeros((n, 7, 4), np.float32)
+        check(lib().tirt_signed_distance_table_download(self.handle, out.reshape(-1)))
+        return out
+
+    def kat_signed_distance(self, rows):
+        """include/tirt.h, tirt_kat_signed_distance: rows (n, 33) (p, a, b, c, N[7][3]) -> (n, 2): sd, the feature's row index"""
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 33)
+        out = np.zeros((rows.shape[0], 2), np.float32)
+        check(lib().tirt_kat_signed_distance(self.handle, rows.reshape(-1), rows.shape[0], out.reshape(-1)))
         return out
 
     def bvh_info(self):

@@ -3,6 +3,9 @@
 //
 //   k_cp_scan   one query per lane against all n primitive records in primitive-id order (TIRT_TRAVERSE_EXHAUSTIVE): the yardstick on the device
 //   k_cp_walk   one query per lane, best-first over the quantised 4-wide nodes `cnode` (BvhView): the hot path
+// Both are templates on <COUNT, SIGNED>.  SIGNED (tirt_query_signed_distance / tirt_signed_distance, include/tirt.h "Signed distance") adds an epilogue and
+// nothing else: sd_store classifies the answer's (u, v), gathers ONE row of the pseudo-normal table that tirt_signed_distance.hip keeps (a sphere: its
+// record again) and stores the signed distance.  The SIGNED = false instantiations hold no trace of it (DESIGN.md has their digests and registers).
 //
 // Both call cp_triangle / cp_sphere / cp_accept (tirt_closest_point.h) and nothing else decides an answer, and the answer is the minimum of a total
 // order on (D2, prim): the walk returns the scan's bits if and only if it never skips a primitive that would have been accepted.
@@ -52,16 +55,7 @@
 
 namespace tirt {
 
-constexpr int CP_BLOCK = 64;                 // one wave per block
-#ifndef CP_LDS_DEPTH_N
-#define CP_LDS_DEPTH_N 16
-#endif
-constexpr int CP_LDS_DEPTH = CP_LDS_DEPTH_N;  // stack entries per lane in LDS: 16 x 8 B x 64 lanes = 8 KiB per block (24: the same rate, 32 / 48: 15 % / 36 % slower, profiles/closest_point_rate.txt)
 constexpr int CP_WAVES_PER_CU = 20;          // persistent blocks per CU at most: what 8 KiB of LDS each admits (62 VGPRs would admit 32)
-constexpr size_t CP_SPILL_BYTES_MAX = (size_t)256 << 20;      // the grid shrinks until the stacks' global tails fit this
-constexpr int CP_SENT = (int)0x80000000;     // "nothing to do": never a node index nor a leaf code (k_trace's TR_SENT)
-constexpr float CP_MARGIN_CELLS = 0.5f, CP_MARGIN_PER_RHO = 0.5f;
-TD float cp_margin_cells(float rho_p, float rho_0) { return CP_MARGIN_CELLS + CP_MARGIN_PER_RHO * (rho_p + rho_0); }
 
 struct CpArgs {
     BvhView bvh;
@@ -73,6 +67,8 @@ struct CpArgs {
     uint2 *spill;                                       // [stack_size - CP_LDS_DEPTH][gridDim.x * CP_BLOCK], or nullptr when stack_size <= CP_LDS_DEPTH
     float *out_d2; int32_t *out_prim; float *out_point; int64_t point_out_stride; float *out_uv; int64_t uv_stride; int2 *counts;
     DevCounters *ctr;
+    // signed distance (the SIGNED instantiations alone read these; at the end, so that the others' argument offsets stay what they were)
+    const float4 *sd_tab; const int *sd_state; float *out_sd;      // [n_prim][SD_ROWS]; sd_state[0] != 0: the table's build dropped a stack entry
 };
 
 TD void cp_load_query(const CpArgs &a, int q, v3 &p, float &lim2)
@@ -105,7 +101,27 @@ TD void cp_test_record(const BvhView &b, int slot, bool is_tri, const v3 p, floa
     if (cp_accept(r.d2, prim, lim2, best2, best_prim)) { best2 = r.d2; best_prim = prim; bp = r; }
 }
 
-template <bool COUNT>
+// the SIGNED epilogue: the sign of the answer from the winner's table row (a sphere: from its record, read again); nothing found: +inf.  A table whose
+// build ran out of stack is no table: every sd is NaN (and stack_overflow has been counted: tirt_stats says TIRT_ERR_STACK)
+TD void sd_store(const CpArgs &a, int q, const v3 p, int best_prim, const CpPoint &bp)
+{
+    float sd = __int_as_float(0x7f800000);
+    if (best_prim >= 0) {
+        if (a.primitive[(size_t)best_prim * PRI_VEC] == PRIMITIVE_TRI) {
+            const float4 *rows = a.sd_tab + (size_t)best_prim * SD_ROWS;
+            int f;
+            sd = sd_sign(p, bp, [rows](int k) { const float4 r = rows[k]; return V(r.x, r.y, r.z); }, f);
+        } else {
+            const float4 *tp = a.bvh.tri + (size_t)a.prim_slot[best_prim] * TRI_STRIDE;
+            const float4 ta = tp[0], tb = tp[1];
+            sd = sd_sign_sphere(p, bp.d2, V(ta.x, ta.y, ta.z), tb.x);
+        }
+    }
+    if (a.sd_state[0] != 0) sd = __int_as_float(0x7fc00000);
+    a.out_sd[q] = sd;
+}
+
+template <bool COUNT, bool SIGNED>
 __global__ __launch_bounds__(CP_BLOCK) void k_cp_scan(CpArgs a)
 {
     const int q = blockIdx.x * CP_BLOCK + threadIdx.x;
@@ -117,13 +133,13 @@ __global__ __launch_bounds__(CP_BLOCK) void k_cp_scan(CpArgs a)
     for (int i = 0; i < a.n_prim; i++)
         cp_test_record(a.bvh, a.prim_slot[i], a.primitive[(size_t)i * PRI_VEC] == PRIMITIVE_TRI, p, lim2, best2, best_prim, bp);
     cp_store(a, q, best2, best_prim, bp, 0u, (unsigned)a.n_prim, COUNT);
+    if constexpr (SIGNED) sd_store(a, q, p, best_prim, bp);
 }
 
-template <bool COUNT>
+template <bool COUNT, bool SIGNED>
 __global__ __launch_bounds__(CP_BLOCK) void k_cp_walk(CpArgs a)
 {
     __shared__ uint2 stk[CP_LDS_DEPTH * CP_BLOCK];      // [entry][lane]
-    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
     const BvhView &b = a.bvh;
     const int lane = threadIdx.x;
     const size_t gthreads = (size_t)gridDim.x * CP_BLOCK, gtid = (size_t)blockIdx.x * CP_BLOCK + lane;
@@ -176,10 +192,7 @@ __global__ __launch_bounds__(CP_BLOCK) void k_cp_walk(CpArgs a)
                 if (COUNT) nbox += 4;
                 constexpr float MISS = 3.0e38f;
                 float l0, l1, l2, l3;
-#define CP_AXIS(W, k, pk)                                                                           \
-                ({  const h2v h__ = __builtin_bit_cast(h2v, (unsigned)(W));                         \
-                    const float mn__ = b.grid_min[k] + (float)h__.x * b.cell[k], mx__ = b.grid_min[k] + (float)h__.y * b.cell[k]; \
-                    maxf(maxf(mn__ - (pk), (pk) - mx__) - m, 0.0f); })
+#define CP_AXIS(W, k, pk) CP_AXIS_GAP(b, m, W, k, pk)
                 // kept: a child that is there and can still win (never culled on equality).  The flag travels with the child through the sort, so
                 // a kept child whose lb2 overflowed to +inf (a query ~1e19 away, cut = +inf) sorts behind the dropped ones and is still pushed
 #define CP_BOX(X, Y, Z, code_, lb_, keep_)                                                          \
@@ -221,6 +234,7 @@ __global__ __launch_bounds__(CP_BLOCK) void k_cp_walk(CpArgs a)
             }
         }
         if (live) cp_store(a, q, best2, best_prim, bp, nbox, nleaf, COUNT);
+        if constexpr (SIGNED) { if (live) sd_store(a, q, p, best_prim, bp); }
         if (overflow) n_over++;
     }
     n_over = wave_sum(n_over);
@@ -240,7 +254,7 @@ static int cp_common_checks(tirt_ctx *c, const char *fn, int64_t n, int stack_si
 // `n` queries in chunks of `chunk` on the context's stream; every pointer is device memory (or null)
 static int cp_chunks(tirt_ctx *c, const float *points, int64_t n, int64_t point_stride, const float *dmax, int64_t dmax_stride, float dmax_all,
                      int stack_size, int flags, int chunk, float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride,
-                     float *out_uv, int64_t uv_stride, int2 *counts)
+                     float *out_uv, int64_t uv_stride, int2 *counts, float *out_sd = nullptr)      // out_sd: the SIGNED kernels (the table stands: sd_table_ensure)
 {
     if (ensure_counters(c)) return TIRT_ERR_HIP;
     const bool scan = (flags & TIRT_TRAVERSE_EXHAUSTIVE) != 0, cnt = (flags & TIRT_COUNT_NODES) != 0;
@@ -250,6 +264,8 @@ static int cp_chunks(tirt_ctx *c, const float *points, int64_t n, int64_t point_
     a.point_stride = point_stride; a.dmax_stride = dmax_stride; a.dmax_all = dmax_all;
     a.stack_size = stack_size; a.point_out_stride = point_out_stride; a.uv_stride = uv_stride;
     a.ctr = c->dev_counters.as<DevCounters>();
+    const bool sgn = out_sd != nullptr;
+    if (sgn) { a.sd_tab = c->sd_tab.as<float4>(); a.sd_state = c->sd_state.as<int>(); }
     // the walk's grid: a lane for every query of a chunk, at most CP_WAVES_PER_CU blocks per CU, fewer while the stacks' global tails would not fit
     int grid_cap = c->cu_count * CP_WAVES_PER_CU;
     const size_t tail = stack_size > CP_LDS_DEPTH ? (size_t)(stack_size - CP_LDS_DEPTH) * sizeof(uint2) : 0;      // bytes per thread
@@ -270,82 +286,94 @@ static int cp_chunks(tirt_ctx *c, const float *points, int64_t n, int64_t point_
         a.out_d2 = out_d2 ? out_d2 + base : nullptr; a.out_prim = out_prim ? out_prim + base : nullptr;
         a.out_point = out_point ? out_point + base * point_out_stride : nullptr; a.out_uv = out_uv ? out_uv + base * uv_stride : nullptr;
         a.counts = counts ? counts + base : nullptr;
+        a.out_sd = sgn ? out_sd + base : nullptr;
         const int blocks = (m + CP_BLOCK - 1) / CP_BLOCK;
-        if (scan) {
-            if (cnt) hipLaunchKernelGGL(k_cp_scan<true>, dim3(blocks), dim3(CP_BLOCK), 0, c->stream, a);
-            else hipLaunchKernelGGL(k_cp_scan<false>, dim3(blocks), dim3(CP_BLOCK), 0, c->stream, a);
-        } else {
-            const int g = blocks < grid_max ? blocks : grid_max;
-            if (cnt) hipLaunchKernelGGL(k_cp_walk<true>, dim3(g), dim3(CP_BLOCK), 0, c->stream, a);
-            else hipLaunchKernelGGL(k_cp_walk<false>, dim3(g), dim3(CP_BLOCK), 0, c->stream, a);
-        }
+#define CP_LAUNCH(K, G)                                                                             \
+        do {                                                                                        \
+            if (sgn) { if (cnt) hipLaunchKernelGGL((K<true, true>), dim3(G), dim3(CP_BLOCK), 0, c->stream, a);      \
+                       else hipLaunchKernelGGL((K<false, true>), dim3(G), dim3(CP_BLOCK), 0, c->stream, a); }       \
+            else { if (cnt) hipLaunchKernelGGL((K<true, false>), dim3(G), dim3(CP_BLOCK), 0, c->stream, a);         \
+                   else hipLaunchKernelGGL((K<false, false>), dim3(G), dim3(CP_BLOCK), 0, c->stream, a); }          \
+        } while (0)
+        if (scan) CP_LAUNCH(k_cp_scan, blocks);
+        else { const int g = blocks < grid_max ? blocks : grid_max; CP_LAUNCH(k_cp_walk, g); }
+#undef CP_LAUNCH
     }
     return TIRT_OK;
 }
 
-static int query_closest_point(tirt_ctx *c, const float *points, int64_t n, int64_t point_stride, const float *dmax, int64_t dmax_stride, float dmax_all,
-                               int stack_size, int flags, float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride,
-                               float *out_uv, int64_t uv_stride, int32_t *counts, void *stream)
+// tirt_query_closest_point, and with `sgn` tirt_query_signed_distance (the same checks, out_sd beside the other outputs, the table made first)
+static int query_closest_point(tirt_ctx *c, const char *fn, bool sgn, const float *points, int64_t n, int64_t point_stride, const float *dmax, int64_t dmax_stride,
+                               float dmax_all, int stack_size, int flags, float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride,
+                               float *out_uv, int64_t uv_stride, int32_t *counts, float *out_sd, void *stream)
 {
-    const char *fn = "tirt_query_closest_point";
+    const std::string f = std::string(fn) + ": ";
     if (int rc = cp_common_checks(c, fn, n, stack_size, flags)) return rc;
-    TIRT_REQUIRE(point_stride >= 3, "tirt_query_closest_point: point_stride < 3 (floats per point)");
-    TIRT_REQUIRE(!out_point || point_out_stride >= 3, "tirt_query_closest_point: point_out_stride < 3 (floats per closest point)");
-    TIRT_REQUIRE(!out_uv || uv_stride >= 2, "tirt_query_closest_point: uv_stride < 2");
-    TIRT_REQUIRE(!dmax || dmax_stride >= 1, "tirt_query_closest_point: dmax_stride < 1");
-    TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, "tirt_query_closest_point: counts must be 8-byte aligned");
+    TIRT_REQUIRE(point_stride >= 3, f + "point_stride < 3 (floats per point)");
+    TIRT_REQUIRE(!out_point || point_out_stride >= 3, f + "point_out_stride < 3 (floats per closest point)");
+    TIRT_REQUIRE(!out_uv || uv_stride >= 2, f + "uv_stride < 2");
+    TIRT_REQUIRE(!dmax || dmax_stride >= 1, f + "dmax_stride < 1");
+    TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, f + "counts must be 8-byte aligned");
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
         (void)hipGetLastError();
-        set_error(std::string(fn) + ": the caller's stream is not a stream of this process's HIP runtime");
+        set_error(f + "the caller's stream is not a stream of this process's HIP runtime");
         return TIRT_ERR_ARG;
     }
-    TIRT_REQUIRE(cs == hipStreamCaptureStatusNone, std::string(fn) + ": the caller's stream is capturing a graph (queries cannot be captured)");
+    TIRT_REQUIRE(cs == hipStreamCaptureStatusNone, f + "the caller's stream is capturing a graph (queries cannot be captured)");
     if (n == 0) return TIRT_OK;
-    TIRT_REQUIRE(points, "tirt_query_closest_point: null points");
-    if (int rc = require_device_ptr(c, points, "tirt_query_closest_point: points")) return rc;
-    if (dmax) if (int rc = require_device_ptr(c, dmax, "tirt_query_closest_point: dmax")) return rc;
-    if (out_d2) if (int rc = require_device_ptr(c, out_d2, "tirt_query_closest_point: out_d2")) return rc;
-    if (out_prim) if (int rc = require_device_ptr(c, out_prim, "tirt_query_closest_point: out_prim")) return rc;
-    if (out_point) if (int rc = require_device_ptr(c, out_point, "tirt_query_closest_point: out_point")) return rc;
-    if (out_uv) if (int rc = require_device_ptr(c, out_uv, "tirt_query_closest_point: out_uv")) return rc;
+    TIRT_REQUIRE(points, f + "null points");
+    TIRT_REQUIRE(!sgn || out_sd, f + "null out_sd");
+    if (int rc = require_device_ptr(c, points, (f + "points").c_str())) return rc;
+    if (dmax) if (int rc = require_device_ptr(c, dmax, (f + "dmax").c_str())) return rc;
+    if (out_d2) if (int rc = require_device_ptr(c, out_d2, (f + "out_d2").c_str())) return rc;
+    if (out_prim) if (int rc = require_device_ptr(c, out_prim, (f + "out_prim").c_str())) return rc;
+    if (out_point) if (int rc = require_device_ptr(c, out_point, (f + "out_point").c_str())) return rc;
+    if (out_uv) if (int rc = require_device_ptr(c, out_uv, (f + "out_uv").c_str())) return rc;
+    if (sgn) if (int rc = require_device_ptr(c, out_sd, (f + "out_sd").c_str())) return rc;
     const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
-    if (want_counts) if (int rc = require_device_ptr(c, counts, "tirt_query_closest_point: counts")) return rc;
+    if (want_counts) if (int rc = require_device_ptr(c, counts, (f + "counts").c_str())) return rc;
     const int chunk = (int)(n < (int64_t)c->query_chunk ? n : (int64_t)c->query_chunk);
     if (int rc = query_begin(c, stream)) return rc;
+    if (sgn) if (int rc = sd_table_ensure(c, stack_size)) return rc;      // (on the context's stream, after the caller's work: no host sync)
     if (int rc = cp_chunks(c, points, n, point_stride, dmax, dmax_stride, dmax_all, stack_size, flags, chunk, out_d2, out_prim, out_point,
-                           point_out_stride, out_uv, uv_stride, want_counts ? (int2 *)counts : nullptr)) return rc;
+                           point_out_stride, out_uv, uv_stride, want_counts ? (int2 *)counts : nullptr, sgn ? out_sd : nullptr)) return rc;
     return query_end(c, stream);
 }
 
-// host arrays staged in the context's query scratch (query_mem: 52 bytes per query), one chunk of all of them, back with a sync
-static int closest_point_host(tirt_ctx *c, const float *points, int n, const float *dmax, int stack_size, int flags, float *out_d2, int32_t *out_prim,
-                              float *out_point, float *out_uv, int32_t *counts)
+// host arrays staged in the context's query scratch (query_mem: 52 bytes per query, 56 with out_sd), one chunk of all of them, back with a sync.
+// `sgn`: tirt_signed_distance -- the table is made first and, the stream being waited for anyway, its build's verdict read: TIRT_ERR_STACK, no answers
+static int closest_point_host(tirt_ctx *c, const char *fn, bool sgn, const float *points, int n, const float *dmax, int stack_size, int flags, float *out_d2,
+                              int32_t *out_prim, float *out_point, float *out_uv, int32_t *counts, float *out_sd)
 {
-    if (int rc = cp_common_checks(c, "tirt_closest_point", n, stack_size, flags)) return rc;
+    if (int rc = cp_common_checks(c, fn, n, stack_size, flags)) return rc;
     if (n == 0) return TIRT_OK;
-    TIRT_REQUIRE(points, "tirt_closest_point: null points");
-    const size_t N = (size_t)n, bytes = N * 52;
+    TIRT_REQUIRE(points, std::string(fn) + ": null points");
+    TIRT_REQUIRE(!sgn || out_sd, std::string(fn) + ": null out_sd");
+    const size_t N = (size_t)n, bytes = N * (sgn ? 56 : 52);
     hipStream_t st = c->stream;
     if (bytes > c->query_mem.bytes) {
         TIRT_HIP(hipStreamSynchronize(st));
         if (c->query_mem.ensure(bytes)) return TIRT_ERR_HIP;
     }
-    // counts [n][2] first (8-byte aligned), then points [n][3], dmax [n], d2 [n], prim [n], point [n][3], uv [n][2]
+    // counts [n][2] first (8-byte aligned), then points [n][3], dmax [n], d2 [n], prim [n], point [n][3], uv [n][2], sd [n]
     int2 *d_counts = c->query_mem.as<int2>();
     float *d_points = (float *)(d_counts + N), *d_dmax = d_points + 3 * N, *d_d2 = d_dmax + N;
     int32_t *d_prim = (int32_t *)(d_d2 + N);
-    float *d_point = (float *)(d_prim + N), *d_uv = d_point + 3 * N;
+    float *d_point = (float *)(d_prim + N), *d_uv = d_point + 3 * N, *d_sd = d_uv + 2 * N;
     const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
     TIRT_HIP(hipMemcpyAsync(d_points, points, sizeof(float) * 3 * N, hipMemcpyHostToDevice, st));
     if (dmax) TIRT_HIP(hipMemcpyAsync(d_dmax, dmax, sizeof(float) * N, hipMemcpyHostToDevice, st));
+    if (sgn) if (int rc = sd_table_ensure(c, stack_size)) return rc;
     if (int rc = cp_chunks(c, d_points, n, 3, dmax ? d_dmax : nullptr, 1, __builtin_inff(), stack_size, flags, n, d_d2, d_prim, d_point, 3, d_uv, 2,
-                           want_counts ? d_counts : nullptr)) return rc;
+                           want_counts ? d_counts : nullptr, sgn ? d_sd : nullptr)) return rc;
+    if (sgn) if (int rc = sd_table_verdict(c, fn)) return rc;      // (waits for the stream)
     if (out_d2) TIRT_HIP(hipMemcpyAsync(out_d2, d_d2, sizeof(float) * N, hipMemcpyDeviceToHost, st));
     if (out_prim) TIRT_HIP(hipMemcpyAsync(out_prim, d_prim, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
     if (out_point) TIRT_HIP(hipMemcpyAsync(out_point, d_point, sizeof(float) * 3 * N, hipMemcpyDeviceToHost, st));
     if (out_uv) TIRT_HIP(hipMemcpyAsync(out_uv, d_uv, sizeof(float) * 2 * N, hipMemcpyDeviceToHost, st));
     if (want_counts) TIRT_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int2) * N, hipMemcpyDeviceToHost, st));
+    if (sgn) TIRT_HIP(hipMemcpyAsync(out_sd, d_sd, sizeof(float) * N, hipMemcpyDeviceToHost, st));
     TIRT_HIP(hipStreamSynchronize(st));
     TIRT_HIP(hipGetLastError());
     return TIRT_OK;
@@ -364,6 +392,20 @@ __global__ void k_kat_closest_point(const float *in, int n, int is_sphere, float
     o[0] = a.d2; o[1] = a.q.x; o[2] = a.q.y; o[3] = a.q.z; o[4] = a.u; o[5] = a.v;
 }
 
+// rows of (p3, a3, b3, c3, N[7][3]) -> sd, feature: cp_triangle, then sd_sign on the row's own pseudo-normals
+__global__ void k_kat_signed_distance(const float *in, int n, float *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *r = in + (size_t)i * 33;
+    const v3 p = V(r[0], r[1], r[2]);
+    const CpPoint a = cp_triangle(p, V(r[3], r[4], r[5]), V(r[6], r[7], r[8]), V(r[9], r[10], r[11]));
+    const float *N = r + 12;
+    int f;
+    const float sd = sd_sign(p, a, [N](int k) { return V(N[3 * k], N[3 * k + 1], N[3 * k + 2]); }, f);
+    out[(size_t)i * 2] = sd; out[(size_t)i * 2 + 1] = (float)f;
+}
+
 }  // namespace tirt
 
 using namespace tirt;
@@ -375,15 +417,41 @@ int tirt_query_closest_point(tirt_ctx *c, const float *points, int64_t n, int64_
                              float *out_uv, int64_t uv_stride, int32_t *counts, void *stream)
 {
     CTX(c);
-    return query_closest_point(c, points, n, point_stride, dmax, dmax_stride, dmax_all, stack_size, flags, out_d2, out_prim, out_point, point_out_stride,
-                               out_uv, uv_stride, counts, stream);
+    return query_closest_point(c, "tirt_query_closest_point", false, points, n, point_stride, dmax, dmax_stride, dmax_all, stack_size, flags, out_d2, out_prim,
+                               out_point, point_out_stride, out_uv, uv_stride, counts, nullptr, stream);
+}
+
+int tirt_query_signed_distance(tirt_ctx *c, const float *points, int64_t n, int64_t point_stride, const float *dmax, int64_t dmax_stride, float dmax_all,
+                               int stack_size, int flags, float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride,
+                               float *out_uv, int64_t uv_stride, int32_t *counts, void *stream, float *out_sd)
+{
+    CTX(c);
+    return query_closest_point(c, "tirt_query_signed_distance", true, points, n, point_stride, dmax, dmax_stride, dmax_all, stack_size, flags, out_d2, out_prim,
+                               out_point, point_out_stride, out_uv, uv_stride, counts, out_sd, stream);
+}
+
+int tirt_signed_distance(tirt_ctx *c, const float *points, int n, const float *dmax, int stack_size, int flags, float *out_d2, int32_t *out_prim,
+                         float *out_point, float *out_uv, int32_t *counts, float *out_sd)
+{
+    CTX(c);
+    return closest_point_host(c, "tirt_signed_distance", true, points, n, dmax, stack_size, flags, out_d2, out_prim, out_point, out_uv, counts, out_sd);
+}
+
+int tirt_kat_signed_distance(tirt_ctx *c, const float *in, int n, float *out)
+{
+    TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_signed_distance: null pointer or negative n");
+    CTX(c);
+    if (n == 0) return TIRT_OK;
+    return kat_round_trip(c, "tirt_kat_signed_distance", {{in, kat_row_bytes(n, 33)}}, out, kat_row_bytes(n, 2), [&](const void *const *din, void *dout) {
+        hipLaunchKernelGGL(k_kat_signed_distance, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float *)din[0], n, (float *)dout);
+    });
 }
 
 int tirt_closest_point(tirt_ctx *c, const float *points, int n, const float *dmax, int stack_size, int flags, float *out_d2, int32_t *out_prim,
                        float *out_point, float *out_uv, int32_t *counts)
 {
     CTX(c);
-    return closest_point_host(c, points, n, dmax, stack_size, flags, out_d2, out_prim, out_point, out_uv, counts);
+    return closest_point_host(c, "tirt_closest_point", false, points, n, dmax, stack_size, flags, out_d2, out_prim, out_point, out_uv, counts, nullptr);
 }
 
 int tirt_kat_closest_point(tirt_ctx *c, const float *in, int n, int is_sphere, float *out)

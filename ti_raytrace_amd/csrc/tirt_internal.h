@@ -450,6 +450,10 @@ struct tirt_ctx {
     // context's stream after and before the caller's (made on first use)
     tirt::DevBuf query_mem; size_t query_chunk = (size_t)1 << 21;
     hipEvent_t query_ev_in = nullptr, query_ev_out = nullptr;
+    // signed distance (tirt_signed_distance.hip): sd_tab = float4[n][7] pseudo-normals per primitive id, sd_state = the build's verdict and counts (SdState);
+    // sd_tab_valid: the table is the one of the present vertices (dropped by tirt_scene_upload, tirt_vertex_update[_device], tirt_lbvh_build; made again by
+    // the first signed query); sd_tab_stack = the stack_size it was built with; sd_tab_checked: the host has read the verdict (nothing was dropped)
+    tirt::DevBuf sd_tab, sd_state; bool sd_tab_valid = false, sd_tab_checked = false; int sd_tab_stack = 0;
     tirt::DevBuf dyn_mem;                         // geometry updates (tirt_dynamic.hip): validation flag, scene box and its block partials, the staged rows of a host update
 
     // RCCL communicator of tirt_comm_init (single-process multi-GPU film reduce; opaque ncclComm_t)
@@ -534,6 +538,10 @@ int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_strid
 int require_device_ptr(tirt_ctx *c, const void *p, const char *what);
 int query_begin(tirt_ctx *c, void *stream);
 int query_end(tirt_ctx *c, void *stream);
+// tirt_signed_distance.hip: the pseudo-normal table behind the signed queries.  sd_table_ensure queues its build on c->stream where it does not stand (no host
+// sync); sd_table_verdict waits for the stream and reads what the build said: TIRT_ERR_STACK (and no table) if it dropped a stack entry
+int sd_table_ensure(tirt_ctx *c, int stack_size);
+int sd_table_verdict(tirt_ctx *c, const char *fn);
 int denoise_film(tirt_ctx *c, const tirt_denoise_t *prm, bool var);      // tirt_denoise.hip; var: the variance-guided mode
 int denoise_device(tirt_ctx *c, bool var, const float *hdr, const float *aov, const float *mom, float *out, int W, int H, const tirt_denoise_t *prm, void *stream);
 int denoise_into_film_buffer(tirt_ctx *c, const std::string &fn, const float *hdr, const float *aov, const float *mom, const tirt_denoise_t *prm);
