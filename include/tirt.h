@@ -823,7 +823,7 @@ int tirt_query_occluded(tirt_ctx *ctx, const float *rays, int64_t nr, int64_t ra
  *   D2 <= lim2 the one with the smallest D2; at equal D2 bits the smallest primitive id.  A NaN D2 is never accepted, and neither is D2 = +inf: "nothing"
  *   is prim = -1, d2 = +inf, point and uv 0 -- so a NaN or infinite coordinate of p finds nothing.  This is the minimum of a total order on (D2, prim):
  *   it does not depend on the order of the visits, and the culled walk returns the bits of a scan over all primitives (the culling argument is in the
- *   head of csrc/tirt_closest_point.hip).  Alpha cut-outs are ignored: a transparent texel is still surface.
+ *   head of csrc/tirt_point_walk.h).  Alpha cut-outs are ignored: a transparent texel is still surface.
  * tirt_query_closest_point: device memory on the caller's stream with the plumbing of tirt_query_closest -- asynchronous, ordered after and before
  *   `stream` by two events, no host sync, chunks of option "query_chunk_rays" (one launch each; it reads and writes the caller's arrays in place and
  *   needs 0 bytes of scratch per query).  Row i of the points starts at points + i * point_stride floats; dmax[i * dmax_stride] per query, or dmax_all

@@ -426,6 +426,34 @@ def test_long_chain_and_stack_overflow(gpu_ctx_ok, tree):
     assert ctx.stats()["stack_overflow"] == 0
 
 
+@pytest.mark.parametrize("tree", [1, 0])
+def test_stack_sizes_around_the_lds_part(gpu_ctx_ok, tree):
+    """the same chain and queries with stacks that end just below, at and just beyond the 16 entries a lane has in LDS (at 16 there is no tail and the
+    spill pointer is null, at 17 the tail is one entry per thread): a query can only differ from the scan if it dropped an entry, a query that fits a
+    stack fits every larger one, and a lane does fill all of LDS (dropped entries are counted, nothing else happens to them)"""
+    ex = long_chain_scene(16, 16)
+    ex.scene.ctx.set_option("traversal_tree", tree)
+    ex.build_scene()
+    ctx = ex.scene.ctx
+    pts = query_points(E.scene_geometry(ex.scene), 2048, seed=29)
+    scan = device_answer(ex, pts, SCAN)
+    sizes = (15, 16, 17, 18, 24, 2048)
+    over, miss = [], []
+    for s in sizes:
+        ctx.stats_reset()
+        d2, prim, _, _ = device_answer(ex, pts, 0, stack_size=s)
+        try:
+            over.append(ctx.stats()["stack_overflow"])
+        except _native.TirtStackOverflow as err:
+            over.append(err.stats["stack_overflow"])
+        miss.append(int(((d2.view(np.uint32) != scan[0].view(np.uint32)) | (prim != scan[1])).sum()))
+    print("tree %d: stack sizes %s: queries that dropped an entry %s, queries that differ from the scan %s" % (tree, sizes, over, miss))
+    assert all(m <= o for m, o in zip(miss, over)), (sizes, over, miss)
+    assert all(a >= b for a, b in zip(over, over[1:])), (sizes, over)
+    assert over[-1] == 0 and miss[-1] == 0
+    assert over[1] > 0, "no lane filled the 16 entries in LDS: the sizes around them test nothing"
+
+
 # ---- 7. moving geometry ------------------------------------------------------------------------------------------------------------------------------
 def test_after_update_vertices(gpu_ctx_ok):
     tris = sphere_obj_triangles()

@@ -211,6 +211,28 @@ def test_deep_tree_uses_the_stacks_tail(gpu_ctx_ok, tree):
     assert ctx.stats()["stack_overflow"] == 0
 
 
+@pytest.mark.parametrize("tree", [1, 0])
+def test_deep_tree_at_the_end_of_the_stacks_lds_part(gpu_ctx_ok, tree):
+    """the same scene with the build's stack ending where its LDS part ends (16: no tail, the spill pointer is null) and one entry later (17: a tail of
+    one entry per thread): refused as the 4-entry stack is, and the table made afterwards is the restatement's"""
+    from common import long_chain_scene
+    ex = long_chain_scene(16, 16)
+    ex.scene.ctx.set_option("traversal_tree", tree)
+    ex.build_scene()
+    ctx = ex.scene.ctx
+    geom = E.scene_geometry(ex.scene)
+    pts = S.uniform_queries(geom, 512)
+    for s in (16, 17):
+        with pytest.raises(_native.TirtError, match=r"error -4:.*ran out of traversal stack \(stack_size %d\)" % s):
+            ctx.signed_distance(pts, stack_size=s)
+        try:
+            ctx.stats()
+        except _native.TirtStackOverflow:
+            pass
+    tab = ctx.signed_distance_table()
+    assert np.array_equal(tab.view(np.uint32), SE.table(geom, ex.scene.primitive_count).view(np.uint32))
+
+
 # ---- bounds, layouts, sizes ---------------------------------------------------------------------------------------------------------------------
 def test_bounds_layouts_and_sizes(gpu_ctx_ok, tmp_dir):
     c = full("union", tmp_dir)

@@ -3,9 +3,9 @@
 // replaces the answer.  One text for the scan (k_cp_scan), the walk (k_cp_walk) and the known-answer entry (k_kat_closest_point), tirt_closest_point.hip:
 // what the three return can only differ in WHICH primitives they look at.  fp32 throughout, every operation and its order as written (the library is
 // compiled with -ffp-contract=off); tests/closest_point_expected.py restates it in numpy.
-// Below them: what a point's walk over `cnode` shares between k_cp_walk and k_sd_build (the margin, the decode of a child's planes, the stack's shape), and
-// the pieces of the signed distance (include/tirt.h "Signed distance"; tests/signed_distance_expected.py): the feature rule, sd_sign, and the per-triangle
-// terms of the pseudo-normal table.
+// Below them: the pieces of the signed distance (include/tirt.h "Signed distance"; tests/signed_distance_expected.py): the feature rule, sd_sign, and the per-triangle
+// terms of the pseudo-normal table.  (What a point's WALK over `cnode` is made of -- the margin, the decode of a child's planes, the lane stack and its
+// sizing -- is tirt_point_walk.h.)
 #pragma once
 #include "tirt_device.h"
 
@@ -55,23 +55,6 @@ TD float cp_limit2(const float dmax) { return dmax >= 0.0f ? dmax * dmax : -1.0f
 // result does not depend on the order in which the candidates come.
 TD bool cp_accept(const float d2, const int prim, const float lim2, const float best2, const int best_prim)
 { return (d2 <= lim2) & ((d2 < best2) | ((d2 == best2) & (prim < best_prim))); }
-
-// ---- what the walk of a point over `cnode` shares between k_cp_walk and the table build of tirt_signed_distance.hip ----
-constexpr int CP_BLOCK = 64;                 // one wave per block
-#ifndef CP_LDS_DEPTH_N
-#define CP_LDS_DEPTH_N 16
-#endif
-constexpr int CP_LDS_DEPTH = CP_LDS_DEPTH_N;  // stack entries per lane in LDS: 16 x 8 B x 64 lanes = 8 KiB per block (24: the same rate, 32 / 48: 15 % / 36 % slower, profiles/closest_point_rate.txt)
-constexpr size_t CP_SPILL_BYTES_MAX = (size_t)256 << 20;      // the grid shrinks until the stacks' global tails fit this
-constexpr int CP_SENT = (int)0x80000000;     // "nothing to do": never a node index nor a leaf code (k_trace's TR_SENT)
-constexpr float CP_MARGIN_CELLS = 0.5f, CP_MARGIN_PER_RHO = 0.5f;
-TD float cp_margin_cells(float rho_p, float rho_0) { return CP_MARGIN_CELLS + CP_MARGIN_PER_RHO * (rho_p + rho_0); }
-typedef _Float16 cp_h2v __attribute__((ext_vector_type(2)));
-// the distance of coordinate pk to the decoded planes of axis k of one child (dword W of its node), less the margin m_, never negative: 0 = inside the grown box
-#define CP_AXIS_GAP(b_, m_, W, k, pk)                                                               \
-                ({  const cp_h2v h__ = __builtin_bit_cast(cp_h2v, (unsigned)(W));                   \
-                    const float mn__ = (b_).grid_min[k] + (float)h__.x * (b_).cell[k], mx__ = (b_).grid_min[k] + (float)h__.y * (b_).cell[k]; \
-                    maxf(maxf(mn__ - (pk), (pk) - mx__) - (m_), 0.0f); })
 
 // ---- signed distance (include/tirt.h, "Signed distance") ----
 // the feature of a closest point from its (u, v), as the row of the primitive's table entry: 0 interior, 1 A, 2 B, 3 C, 4 AB, 5 AC, 6 BC

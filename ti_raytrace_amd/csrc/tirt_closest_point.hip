@@ -12,50 +12,28 @@
 //
 // THE WALK.  A wave is a block (no barrier anywhere); lane l holds query base + l and the blocks stride over the chunk.  A node visit decodes the four
 // children's planes (grid_min + h * cell, h the fp16 halves of the record), forms lb2 = sum over the axes of max(mn - p - m, p - mx - m, 0)^2 with the
-// margin m below, drops empty slots and children with lb2 > cut (cut = min(best D2 so far, lim2)), sorts the rest (five compare-exchanges, as k_trace),
+// margin m of PointMargin (tirt_point_walk.h), drops empty slots and children with lb2 > cut (cut = min(best D2 so far, lim2)), sorts the rest (five compare-exchanges, as k_trace),
 // descends into the nearest and pushes the others far to near WITH their lb2; a popped entry is tested against the cut of that moment again (the best
 // distance of a nearest-neighbour walk shrinks fast: most entries are dead when they surface).  Leaves gather the three quads of the record; the
 // sphere branch (a square root and a division) sits behind a wave ballot, as in trace_leaf_step.  Node steps and leaf steps alternate, each for the
-// lanes that are at one.  Stack entries are 8 bytes (child code, lb2); the first CP_LDS_DEPTH of a lane live in LDS ([entry][lane]), the rest of its
-// stack_size in the context's spill buffer ([entry][global thread]) -- DESIGN.md "Closest point" has the sizes and why 16.  An entry beyond stack_size
+// lanes that are at one.  The stack is PointStack (tirt_point_walk.h) with entries of 8 bytes (child code, lb2): the first CP_LDS_DEPTH of a lane live in LDS
+// ([entry][lane]), the rest of its stack_size in the context's spill buffer ([entry][global thread]) -- DESIGN.md "Closest point" has the sizes and why 16.  An entry beyond stack_size
 // is dropped and the query counted in DevCounters::stack_overflow (tirt_stats: TIRT_ERR_STACK), as a ray's.
 // The walk starts at root_qcode (a leaf code in a one-primitive scene).  Every analytic sphere is below it: its slot carries its padded box
 // (shapes_boxed) or the whole grid, and both contain the sphere, as every ancestor's box does -- the chain nodes at far_qcode exist for rays, whose
 // sphere test can answer from outside the padded box; a closest point lies ON the sphere.  Spot and laser leaves are reached and skipped.
 // A query with a NaN or infinite coordinate finds nothing by the definition (every D2 is NaN or +inf): it does not walk.
 //
-// WHY THE CULL IS CONSERVATIVE.  A subtree is skipped on lb2 > cut only, never on equality, so it suffices that lb2 <= D2 holds, as computed fp32
-// numbers, for every primitive t below the node.  Write eps = 2^-24, E = the largest extent of the padded root box, C = E / 60000 = the largest cell,
-// M = the largest coordinate magnitude among p and the scene, d = the distance from p to t.
-//  (1) The computed D2.  cp_triangle's Q is a vertex, or a + ab u with u in [0, 1] (AB, AC, BC: the region tests make numerator and denominator
-//      non-negative with numerator <= denominator, and a correctly rounded quotient keeps that), or (a + ab u) + ac v with u = vb den, v = vc den.
-//      On an edge the exact a + ab u lies on the segment, hence in the leaf's exact box, and the evaluated one differs from it by the roundings of
-//      b - a, the product and the sum: <= 2 eps M per coordinate.  In the interior u, v, 1 - u - v carry the error of va, vb, vc (differences of
-//      products of dot products whose terms reach |ab| |ap|): a relative error of order eps (|p - a| / |ab|) in (u, v), i.e. a shift of Q IN THE
-//      TRIANGLE'S PLANE of order eps (d + |ab|), a few eps M again.  So Q is within k eps M of the box with k "a few"; p - Q adds eps M / 2 per
-//      coordinate and the dot product 3 eps relative.  sqrt(D2) >= (d_box - sqrt(3) (k + 1) eps M) (1 - 2 eps), d_box = the exact distance from p to
-//      the exact box.  The sphere: |len - r| is off by <= 3 eps max(len, r) <= 3 eps (M + d) from a distance to a surface inside its box.
-//      [A needle whose area is so small against its edges that va + vb + vc is rounding noise can put the interior's Q further out than that; such a
-//      triangle has no trustworthy interior answer in the scan either.  The margin below is sized for k <= 100, not for "a few".]
-//  (2) The computed lb2.  A decoded plane is off by eps E / 4 (the product) + eps M / 2 (the sum), the differences mn - p, p - mx by eps M each at
-//      most, the squares and sums by 3 eps relative: sqrt(lb2) <= (|e| + 3 sqrt(3) eps M) (1 + 2 eps), e the exact per-axis distances to the
-//      quantised box moved outward by m.
-//  (3) The slack.  A quantised plane is >= 0.9 of ITS axis' cell outside the exact box (tirt_internal.h: rounded outward by at least one cell); that
-//      cell can be tiny on a flat scene's thin axis, so it is not relied on beyond the rounding of the planes themselves.  The margin m is the SAME
-//      length on all axes, m = mc * C.  With x the exact per-axis distances to the exact box (|x| = d_box) and e_a <= max(x_a - m, 0):
-//      |x|^2 = |e|^2 + 2 e.(x - e) + |x - e|^2 >= (|e| + m)^2 whenever e != 0, because x_a - e_a = m on every axis with e_a > 0.  So |e| <= d_box - m.
-//  Together: lb2 <= D2 if m >= sqrt(3) (k + 4) eps M + 4 eps d.  With rho_p = max_a |p_a - grid_min_a| / E and rho_0 = max_a |grid_min_a| / E,
-//  M <= (rho_0 + max(rho_p, 1/2)) E and d <= sqrt(3) (rho_p + 1/2) E; eps E = 0.00358 C.  mc = 0.5 + 0.5 (rho_p + rho_0) (cp_margin_cells) gives
-//  m >= 0.5 C (rho_p + rho_0 + 1) >= 140 eps M and leaves >= 100 eps M for k after the 4 sqrt(3) eps M and 4 eps d terms (<= 14 + 14 eps M-equivalents).
-//  Unlike trace_margin_cells it grows with the SCENE's distance from the origin too (rho_0): a mesh 10^4 extents from the origin has vertices that are
-//  36 cells apart in fp32.  Half a cell is 8e-6 of the extent: it costs no visit worth counting near the scene; a query many extents away
-//  gets a margin that swallows the boxes and its walk degenerates towards the scan, which is acceptable (no cut-off).
+// WHY THE CULL IS CONSERVATIVE: the head of tirt_point_walk.h, beside the margin it is about (PointMargin, which k_sd_build shares, as it does the stack).
 #include "tirt_internal.h"
 #include "tirt_closest_point.h"
+#include "tirt_point_walk.h"
 
 namespace tirt {
 
 constexpr int CP_WAVES_PER_CU = 20;          // persistent blocks per CU at most: what 8 KiB of LDS each admits (62 VGPRs would admit 32)
+
+typedef unsigned CpEntry __attribute__((ext_vector_type(2)));      // a stack entry: (child code, bits of lb2)
 
 struct CpArgs {
     BvhView bvh;
@@ -64,7 +42,7 @@ struct CpArgs {
     const float *dmax; int64_t dmax_stride; float dmax_all;
     int n;                                              // queries of this chunk
     int stack_size;
-    uint2 *spill;                                       // [stack_size - CP_LDS_DEPTH][gridDim.x * CP_BLOCK], or nullptr when stack_size <= CP_LDS_DEPTH
+    CpEntry *spill;                                     // the stacks' tails (point_walk_launch_shape), or nullptr when stack_size <= CP_LDS_DEPTH
     float *out_d2; int32_t *out_prim; float *out_point; int64_t point_out_stride; float *out_uv; int64_t uv_stride; int2 *counts;
     DevCounters *ctr;
     // signed distance (the SIGNED instantiations alone read these; at the end, so that the others' argument offsets stay what they were)
@@ -139,13 +117,10 @@ __global__ __launch_bounds__(CP_BLOCK) void k_cp_scan(CpArgs a)
 template <bool COUNT, bool SIGNED>
 __global__ __launch_bounds__(CP_BLOCK) void k_cp_walk(CpArgs a)
 {
-    __shared__ uint2 stk[CP_LDS_DEPTH * CP_BLOCK];      // [entry][lane]
+    __shared__ CpEntry stk[CP_LDS_DEPTH * CP_BLOCK];    // [entry][lane]
     const BvhView &b = a.bvh;
     const int lane = threadIdx.x;
-    const size_t gthreads = (size_t)gridDim.x * CP_BLOCK, gtid = (size_t)blockIdx.x * CP_BLOCK + lane;
-    const float cell_max = maxf(maxf(b.cell[0], b.cell[1]), b.cell[2]);
-    const float inv_ext = 1.0f / (cell_max * (2.0f * TR_GRID_HALF));
-    const float rho_0 = maxf(maxf(absf(b.grid_min[0]), absf(b.grid_min[1])), absf(b.grid_min[2])) * inv_ext;
+    const PointMargin pm(b);
     unsigned long long n_over = 0;
 
     for (int base = blockIdx.x * CP_BLOCK; base < a.n; base += gridDim.x * CP_BLOCK) {      // wave-uniform
@@ -156,57 +131,36 @@ __global__ __launch_bounds__(CP_BLOCK) void k_cp_walk(CpArgs a)
         float best2 = __int_as_float(0x7f800000); int best_prim = -1;
         CpPoint bp; bp.d2 = best2; bp.q = V(0.0f, 0.0f, 0.0f); bp.u = 0.0f; bp.v = 0.0f;
         const bool finite = absf(p.x) < best2 && absf(p.y) < best2 && absf(p.z) < best2;      // false for NaN and +-inf
-        const float rho_p = maxf(maxf(absf(p.x - b.grid_min[0]), absf(p.y - b.grid_min[1])), absf(p.z - b.grid_min[2])) * inv_ext;
-        const float m = cp_margin_cells(rho_p, rho_0) * cell_max;
+        const float m = pm.margin(b, p);
         float cut = lim2;                       // min(best2, lim2): best2 starts at +inf
         int cur = (live && finite && lim2 >= 0.0f) ? b.root_qcode : CP_SENT;
-        int sp = 0;                             // entries on this lane's stack
-        unsigned nbox = 0, nleaf = 0; bool overflow = false;
-
-#define CP_PUSH(code_, lb2_)                                                                        \
-        do {                                                                                        \
-            if (sp < a.stack_size) {                                                                \
-                const uint2 e__ = make_uint2((unsigned)(code_), __float_as_uint(lb2_));             \
-                if (sp < CP_LDS_DEPTH) stk[sp * CP_BLOCK + lane] = e__;                             \
-                else a.spill[(size_t)(sp - CP_LDS_DEPTH) * gthreads + gtid] = e__;                  \
-                sp++;                                                                               \
-            } else overflow = true;               /* out of room: the entry is lost (counted) */    \
-        } while (0)
-        // the next entry that can still win; most are dead by the time they surface
-#define CP_POP()                                                                                    \
-        do {                                                                                        \
-            cur = CP_SENT;                                                                          \
-            while (sp > 0) {                                                                        \
-                sp--;                                                                               \
-                const uint2 e__ = sp < CP_LDS_DEPTH ? stk[sp * CP_BLOCK + lane] : a.spill[(size_t)(sp - CP_LDS_DEPTH) * gthreads + gtid]; \
-                if (!(__uint_as_float(e__.y) > cut)) { cur = (int)e__.x; break; }                   \
-            }                                                                                       \
-        } while (0)
+        PointStack<CpEntry> st(stk, a.spill, a.stack_size, lane);
+        unsigned nbox = 0, nleaf = 0;
+        // the next entry that can still win, or CP_SENT; most are dead by the time they surface
+        auto pop_live = [&]() {
+            while (!st.empty()) { const CpEntry e = st.pop(); if (!(__uint_as_float(e.y) > cut)) return (int)e.x; }
+            return CP_SENT;
+        };
 
         while (__builtin_amdgcn_ballot_w64(cur != CP_SENT) != 0ull) {
             // ---- node step: the lanes that are at an inner node
             if (cur >= 0) {
                 const uint4 *w = b.cnode + (size_t)cur * 4;
                 const uint4 q0 = w[0], q1 = w[1], q2 = w[2], q3 = w[3];
-                int c0 = (int)q3.x, c1 = (int)q3.y, c2 = (int)q3.z, c3 = (int)q3.w;
                 if (COUNT) nbox += 4;
                 constexpr float MISS = 3.0e38f;
-                float l0, l1, l2, l3;
-#define CP_AXIS(W, k, pk) CP_AXIS_GAP(b, m, W, k, pk)
+                int c0, c1, c2, c3; float l0, l1, l2, l3; bool k0, k1, k2, k3;
                 // kept: a child that is there and can still win (never culled on equality).  The flag travels with the child through the sort, so
                 // a kept child whose lb2 overflowed to +inf (a query ~1e19 away, cut = +inf) sorts behind the dropped ones and is still pushed
-#define CP_BOX(X, Y, Z, code_, lb_, keep_)                                                          \
+#define CP_BOX(i, X, Y, Z, code_)                                                                   \
                 do {                                                                                \
-                    const float ex__ = CP_AXIS(X, 0, p.x), ey__ = CP_AXIS(Y, 1, p.y), ez__ = CP_AXIS(Z, 2, p.z); \
+                    const float ex__ = CP_AXIS_GAP(b, m, X, 0, p.x), ey__ = CP_AXIS_GAP(b, m, Y, 1, p.y), ez__ = CP_AXIS_GAP(b, m, Z, 2, p.z); \
                     const float s__ = (ex__ * ex__ + ey__ * ey__) + ez__ * ez__;                    \
-                    keep_ = ((code_) != TR_EMPTY) && !(s__ > cut);                                  \
-                    lb_ = keep_ ? s__ : MISS;                                                       \
+                    c##i = (int)(code_);                                                            \
+                    k##i = (c##i != TR_EMPTY) && !(s__ > cut);                                      \
+                    l##i = k##i ? s__ : MISS;                                                       \
                 } while (0)
-                bool k0, k1, k2, k3;
-                CP_BOX(q0.x, q0.y, q0.z, c0, l0, k0);
-                CP_BOX(q0.w, q1.x, q1.y, c1, l1, k1);
-                CP_BOX(q1.z, q1.w, q2.x, c2, l2, k2);
-                CP_BOX(q2.y, q2.z, q2.w, c3, l3, k3);
+                CP_EACH_CHILD(CP_BOX);
 #define CP_CE(la, ca, ka, lb, cb, kb)                                                               \
                 do {                                                                                \
                     const bool s__ = (lb) < (la);                                                   \
@@ -216,10 +170,10 @@ __global__ __launch_bounds__(CP_BLOCK) void k_cp_walk(CpArgs a)
                     la = lo__; lb = hi__; ca = clo__; cb = chi__; ka = klo__; kb = khi__;           \
                 } while (0)
                 CP_CE(l0, c0, k0, l1, c1, k1); CP_CE(l2, c2, k2, l3, c3, k3); CP_CE(l0, c0, k0, l2, c2, k2); CP_CE(l1, c1, k1, l3, c3, k3); CP_CE(l1, c1, k1, l2, c2, k2);
-                if (k3) CP_PUSH(c3, l3);
-                if (k2) CP_PUSH(c2, l2);
-                if (k1) CP_PUSH(c1, l1);
-                if (k0) cur = c0; else CP_POP();
+                if (k3) st.push(CpEntry{(unsigned)c3, __float_as_uint(l3)});
+                if (k2) st.push(CpEntry{(unsigned)c2, __float_as_uint(l2)});
+                if (k1) st.push(CpEntry{(unsigned)c1, __float_as_uint(l1)});
+                cur = k0 ? c0 : pop_live();
             }
             // ---- leaf step: the lanes that are at a leaf
             const bool at_leaf = cur < 0 && cur != CP_SENT;
@@ -227,28 +181,18 @@ __global__ __launch_bounds__(CP_BLOCK) void k_cp_walk(CpArgs a)
                 if (at_leaf) {
                     const int code = ~cur;
                     if (COUNT) nleaf += 1;
-                    cp_test_record(b, code & 0x3fffffff, ((code >> 30) & 1) == 0, p, lim2, best2, best_prim, bp);
+                    cp_test_record(b, leaf_slot(code), leaf_is_tri(code), p, lim2, best2, best_prim, bp);
                     cut = __builtin_fminf(best2, lim2);
-                    CP_POP();
+                    cur = pop_live();
                 }
             }
         }
         if (live) cp_store(a, q, best2, best_prim, bp, nbox, nleaf, COUNT);
         if constexpr (SIGNED) { if (live) sd_store(a, q, p, best_prim, bp); }
-        if (overflow) n_over++;
+        if (st.overflow) n_over++;
     }
     n_over = wave_sum(n_over);
     if (lane == 0 && n_over && a.ctr) atomicAdd(&a.ctr->stack_overflow, n_over);
-}
-
-// the checks of query_common_checks (tirt_query.hip), worded for points
-static int cp_common_checks(tirt_ctx *c, const char *fn, int64_t n, int stack_size, int flags)
-{
-    TIRT_REQUIRE(c->built, std::string(fn) + ": LBVH not built");
-    TIRT_REQUIRE(n >= 0, std::string(fn) + ": n < 0");
-    TIRT_REQUIRE(stack_size >= 1 && stack_size <= 4096, std::string(fn) + ": stack_size 1..4096");
-    TIRT_REQUIRE((flags & ~(TIRT_TRAVERSE_EXHAUSTIVE | TIRT_COUNT_NODES)) == 0, std::string(fn) + ": unknown flags");
-    return TIRT_OK;
 }
 
 // `n` queries in chunks of `chunk` on the context's stream; every pointer is device memory (or null)
@@ -266,19 +210,9 @@ static int cp_chunks(tirt_ctx *c, const float *points, int64_t n, int64_t point_
     a.ctr = c->dev_counters.as<DevCounters>();
     const bool sgn = out_sd != nullptr;
     if (sgn) { a.sd_tab = c->sd_tab.as<float4>(); a.sd_state = c->sd_state.as<int>(); }
-    // the walk's grid: a lane for every query of a chunk, at most CP_WAVES_PER_CU blocks per CU, fewer while the stacks' global tails would not fit
-    int grid_cap = c->cu_count * CP_WAVES_PER_CU;
-    const size_t tail = stack_size > CP_LDS_DEPTH ? (size_t)(stack_size - CP_LDS_DEPTH) * sizeof(uint2) : 0;      // bytes per thread
-    if (tail) { const size_t fit = CP_SPILL_BYTES_MAX / (tail * CP_BLOCK); if ((size_t)grid_cap > fit) grid_cap = (int)(fit > 0 ? fit : 1); }
-    int grid_max = (int)(((int64_t)(n < chunk ? n : chunk) + CP_BLOCK - 1) / CP_BLOCK); if (grid_max > grid_cap) grid_max = grid_cap;
-    if (!scan && tail) {
-        const size_t want = tail * CP_BLOCK * (size_t)grid_max;
-        if (want > c->spill.bytes) {            // growing frees the old buffer, which queued work may still use
-            TIRT_HIP(hipStreamSynchronize(c->stream));
-            if (c->spill.ensure(want)) return TIRT_ERR_HIP;
-        }
-        a.spill = c->spill.as<uint2>();
-    }
+    // the walk's grid: a lane for every query of a chunk, as far as the stacks allow (the scan has no stack)
+    int grid_max = 0;
+    if (!scan) if (int rc = point_walk_launch_shape(c, stack_size, CP_WAVES_PER_CU, ((int64_t)(n < chunk ? n : chunk) + CP_BLOCK - 1) / CP_BLOCK, grid_max, a.spill)) return rc;
     for (int64_t base = 0; base < n; base += chunk) {
         const int m = (int)(n - base < chunk ? n - base : chunk);
         a.n = m;
@@ -308,19 +242,13 @@ static int query_closest_point(tirt_ctx *c, const char *fn, bool sgn, const floa
                                float *out_uv, int64_t uv_stride, int32_t *counts, float *out_sd, void *stream)
 {
     const std::string f = std::string(fn) + ": ";
-    if (int rc = cp_common_checks(c, fn, n, stack_size, flags)) return rc;
+    if (int rc = query_common_checks(c, fn, "n", n, stack_size, flags)) return rc;
     TIRT_REQUIRE(point_stride >= 3, f + "point_stride < 3 (floats per point)");
     TIRT_REQUIRE(!out_point || point_out_stride >= 3, f + "point_out_stride < 3 (floats per closest point)");
     TIRT_REQUIRE(!out_uv || uv_stride >= 2, f + "uv_stride < 2");
     TIRT_REQUIRE(!dmax || dmax_stride >= 1, f + "dmax_stride < 1");
     TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, f + "counts must be 8-byte aligned");
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error(f + "the caller's stream is not a stream of this process's HIP runtime");
-        return TIRT_ERR_ARG;
-    }
-    TIRT_REQUIRE(cs == hipStreamCaptureStatusNone, f + "the caller's stream is capturing a graph (queries cannot be captured)");
+    if (int rc = require_caller_stream(c, fn, stream, "queries")) return rc;
     if (n == 0) return TIRT_OK;
     TIRT_REQUIRE(points, f + "null points");
     TIRT_REQUIRE(!sgn || out_sd, f + "null out_sd");
@@ -346,7 +274,7 @@ static int query_closest_point(tirt_ctx *c, const char *fn, bool sgn, const floa
 static int closest_point_host(tirt_ctx *c, const char *fn, bool sgn, const float *points, int n, const float *dmax, int stack_size, int flags, float *out_d2,
                               int32_t *out_prim, float *out_point, float *out_uv, int32_t *counts, float *out_sd)
 {
-    if (int rc = cp_common_checks(c, fn, n, stack_size, flags)) return rc;
+    if (int rc = query_common_checks(c, fn, "n", n, stack_size, flags)) return rc;
     if (n == 0) return TIRT_OK;
     TIRT_REQUIRE(points, std::string(fn) + ": null points");
     TIRT_REQUIRE(!sgn || out_sd, std::string(fn) + ": null out_sd");

@@ -231,13 +231,7 @@ int denoise_device(tirt_ctx *c, bool var, const float *hdr, const float *aov, co
     const std::string fn = var ? "tirt_denoise_var_device" : "tirt_denoise_device";
     TIRT_REQUIRE(W >= 1 && H >= 1 && (long long)W * H < (1ll << 30), fn + ": bad size");
     if (int rc = denoise_check_params(fn, prm, var ? DNV_DEFAULTS : DN_DEFAULTS)) return rc;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error(fn + ": the caller's stream is not a stream of this process's HIP runtime");
-        return TIRT_ERR_ARG;
-    }
-    TIRT_REQUIRE(cs == hipStreamCaptureStatusNone, fn + ": the caller's stream is capturing a graph (the filter cannot be captured)");
+    if (int rc = require_caller_stream(c, fn, stream, "the filter")) return rc;
     const struct { const char *name; const float *p; size_t words; } in[3] = {{"hdr", hdr, 3}, {"aov", aov, TIRT_AOV_WORDS}, {"mom", mom, TIRT_MOM_WORDS}};
     const int nin = var ? 3 : 2;
     const size_t NP = (size_t)W * H;

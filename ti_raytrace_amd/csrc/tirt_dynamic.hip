@@ -243,13 +243,7 @@ int tirt_vertex_update_device(tirt_ctx *c, int64_t first, int64_t count, const f
     TIRT_REQUIRE(c, "null context");
     TIRT_HIP(hipSetDevice(c->device));
     if (int rc = dyn_common_checks(c, fn, first, count, pos, pos_stride, nrm, nrm_stride)) return rc;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("tirt_vertex_update_device: the caller's stream is not a stream of this process's HIP runtime");
-        return TIRT_ERR_ARG;
-    }
-    TIRT_REQUIRE(cs == hipStreamCaptureStatusNone, "tirt_vertex_update_device: the caller's stream is capturing a graph (a geometry update cannot be captured)");
+    if (int rc = require_caller_stream(c, fn, stream, "a geometry update")) return rc;
     if (count == 0) return TIRT_OK;
     const char *why = " is not device memory of this context's device (a host pointer -- both pointers host: tirt_vertex_update --, another device's "
                       "memory, or memory of a second HIP runtime in the process)";

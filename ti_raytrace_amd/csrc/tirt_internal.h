@@ -64,6 +64,9 @@ struct DevBuf {
 #endif
 constexpr int TRI_STRIDE = TRI_STRIDE_N;                 // float4 per primitive record
 constexpr int TR_EMPTY = (int)0x80000001;
+// a leaf's child code, inverted (lc = ~code): the record slot, and whether the record is a triangle's (bit 30 clear) or a shape's
+__host__ __device__ inline int leaf_slot(int lc) { return lc & 0x3fffffff; }
+__host__ __device__ inline bool leaf_is_tri(int lc) { return ((lc >> 30) & 1) == 0; }
 #ifndef TR_TOP_LEVELS_N
 #define TR_TOP_LEVELS_N 5
 #endif
@@ -154,12 +157,13 @@ template <bool VERIFY, bool CUTOUT = false, class CS = NoCutSource>
 TD bool trace_leaf_step(const BvhView &b, const RayCtx &r, const bool par, const int code, float &hit_t, float &hit_u, float &hit_v, int &hit_prim, int &hit_leaf)
 {
     static_assert(!CUTOUT || !std::is_same<CS, NoCutSource>::value, "trace_leaf_step<VERIFY, true> needs a source of the cut-out pointers (NoCutSource hands out none)");
+    // (leaf_slot(code), written out here and at cut_uv below: through the helper the CUTOUT twins of k_trace compile to two to four instructions more)
     const float4 *tp = b.tri + (size_t)(code & 0x3fffffff) * TRI_STRIDE;          // records in the traversal tree's leaf order
     // (the records themselves must NOT be loaded non-temporally: -25 %, profiles/r05m -- their residency in L2 is what the kernel lives on)
     const float4 ta = tp[0], tb = tp[1], tc = tp[2];
     int prim = __float_as_int(tc.w);                                              // the primitive id rides in the last word
     const v3 o = V(r.ox, r.oy, r.oz), d = V(r.dx, r.dy, r.dz);
-    const bool is_tri = ((code >> 30) & 1) == 0;
+    const bool is_tri = leaf_is_tri(code);
     const v3 pa = V(ta.x, ta.y, ta.z), pb = V(tb.x, tb.y, tb.z), pc = V(tc.x, tc.y, tc.z);
     float t, u, v;
     bool sph = false;
@@ -534,8 +538,11 @@ int query_closest(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride
                   float *out_hit, int64_t hit_stride, int32_t *counts, void *stream);      // tirt_query.hip
 int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, const float *tmax, int64_t tmax_stride, float tmax_all,
                    int stack_size, int flags, uint8_t *out_occluded, void *stream);
-// what the entry points that take caller-owned device memory share (tirt_query.hip): the pointer check, and the two events that order the context's stream after and before the caller's
+// what the entry points that take caller-owned device memory share (tirt_query.hip): the pointer check, the check of the caller's stream ("... (`what` cannot be
+// captured)"), the first checks of every query, and the two events that order the context's stream after and before the caller's
 int require_device_ptr(tirt_ctx *c, const void *p, const char *what);
+int require_caller_stream(tirt_ctx *c, const std::string &fn, void *stream, const char *what);
+int query_common_checks(tirt_ctx *c, const char *fn, const char *count, int64_t n, int stack_size, int flags);
 int query_begin(tirt_ctx *c, void *stream);
 int query_end(tirt_ctx *c, void *stream);
 // tirt_signed_distance.hip: the pseudo-normal table behind the signed queries.  sd_table_ensure queues its build on c->stream where it does not stand (no host

@@ -146,8 +146,8 @@ __global__ __launch_bounds__(64) void k_pvb_beam(BvhView b, CameraView cam, Tile
                 // distance), and the least projection of its corners on the axis instead of its box's (no point of it is nearer)
                 float nr = nearp;
                 const int lc = ~code;
-                if (((lc >> 30) & 1) == 0) {
-                    const float4 *tp = b.tri + (size_t)(lc & 0x3fffffff) * TRI_STRIDE;
+                if (leaf_is_tri(lc)) {
+                    const float4 *tp = b.tri + (size_t)leaf_slot(lc) * TRI_STRIDE;
                     const float4 ta = tp[0], tb = tp[1], tc = tp[2];
                     const v3 w0 = V(ta.x, ta.y, ta.z), w1 = V(tb.x, tb.y, tb.z), w2 = V(tc.x, tc.y, tc.z);
                     const v3 g0 = V((w0.x - eye.x) / cell.x, (w0.y - eye.y) / cell.y, (w0.z - eye.z) / cell.z);

@@ -81,21 +81,33 @@ int require_device_ptr(tirt_ctx *c, const void *p, const char *what)
     return TIRT_ERR_ARG;
 }
 
-static int query_common_checks(tirt_ctx *c, const char *fn, int64_t nr, int64_t ray_stride, int stack_size, int flags, void *stream)
+// The caller's stream must be one of this process's HIP runtime and not capturing a graph (`what` cannot be captured): refused before anything is queued.
+int require_caller_stream(tirt_ctx *c, const std::string &fn, void *stream, const char *what)
 {
-    TIRT_REQUIRE(c->built, std::string(fn) + ": LBVH not built");
-    TIRT_REQUIRE(nr >= 0, std::string(fn) + ": nr < 0");
-    TIRT_REQUIRE(ray_stride >= 6, std::string(fn) + ": ray_stride < 6 (floats per ray: origin, direction)");
-    TIRT_REQUIRE(stack_size >= 1 && stack_size <= 4096, std::string(fn) + ": stack_size 1..4096");
-    TIRT_REQUIRE((flags & ~(TIRT_TRAVERSE_EXHAUSTIVE | TIRT_COUNT_NODES)) == 0, std::string(fn) + ": unknown flags");
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
         (void)hipGetLastError();
-        set_error(std::string(fn) + ": the caller's stream is not a stream of this process's HIP runtime");
+        set_error(fn + ": the caller's stream is not a stream of this process's HIP runtime");
         return TIRT_ERR_ARG;
     }
-    TIRT_REQUIRE(cs == hipStreamCaptureStatusNone, std::string(fn) + ": the caller's stream is capturing a graph (queries cannot be captured)");
+    TIRT_REQUIRE(cs == hipStreamCaptureStatusNone, fn + ": the caller's stream is capturing a graph (" + what + " cannot be captured)");
     return TIRT_OK;
+}
+
+// what every query entry checks first, on rays (`count` = "nr") and on points ("n") alike
+int query_common_checks(tirt_ctx *c, const char *fn, const char *count, int64_t n, int stack_size, int flags)
+{
+    TIRT_REQUIRE(c->built, std::string(fn) + ": LBVH not built");
+    TIRT_REQUIRE(n >= 0, std::string(fn) + ": " + count + " < 0");
+    TIRT_REQUIRE(stack_size >= 1 && stack_size <= 4096, std::string(fn) + ": stack_size 1..4096");
+    TIRT_REQUIRE((flags & ~(TIRT_TRAVERSE_EXHAUSTIVE | TIRT_COUNT_NODES)) == 0, std::string(fn) + ": unknown flags");
+    return TIRT_OK;
+}
+static int ray_query_checks(tirt_ctx *c, const char *fn, int64_t nr, int64_t ray_stride, int stack_size, int flags, void *stream)
+{
+    if (int rc = query_common_checks(c, fn, "nr", nr, stack_size, flags)) return rc;
+    TIRT_REQUIRE(ray_stride >= 6, std::string(fn) + ": ray_stride < 6 (floats per ray: origin, direction)");
+    return require_caller_stream(c, fn, stream, "queries");
 }
 
 // Scratch of one chunk of `chunk` rays (ray records, then hit records).  Growing the buffer waits for the work queued on the context's
@@ -157,7 +169,7 @@ int query_closest(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride
                   float *out_hit, int64_t hit_stride, int32_t *counts, void *stream)
 {
     const char *fn = "tirt_query_closest";
-    if (int rc = query_common_checks(c, fn, nr, ray_stride, stack_size, flags, stream)) return rc;
+    if (int rc = ray_query_checks(c, fn, nr, ray_stride, stack_size, flags, stream)) return rc;
     TIRT_REQUIRE(!out_hit || hit_stride >= 13, "tirt_query_closest: hit_stride < 13 (floats per hit record)");
     TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, "tirt_query_closest: counts must be 8-byte aligned");
     if (nr == 0) return TIRT_OK;
@@ -211,7 +223,7 @@ int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_strid
                    int stack_size, int flags, uint8_t *out_occluded, void *stream)
 {
     const char *fn = "tirt_query_occluded";
-    if (int rc = query_common_checks(c, fn, nr, ray_stride, stack_size, flags, stream)) return rc;
+    if (int rc = ray_query_checks(c, fn, nr, ray_stride, stack_size, flags, stream)) return rc;
     TIRT_REQUIRE(!tmax || tmax_stride >= 1, "tirt_query_occluded: tmax_stride < 1");
     if (nr == 0) return TIRT_OK;
     TIRT_REQUIRE(rays && out_occluded, "tirt_query_occluded: null rays / out_occluded");

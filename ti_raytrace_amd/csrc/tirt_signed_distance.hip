@@ -5,7 +5,7 @@
 //
 // The scene has no connectivity: its vertex rows are a triangle soup.  k_sd_build finds it on the device, without welding anything: one lane per triangle
 // CORNER walks the quantised 4-wide nodes `cnode` from root_qcode and descends into every child whose decoded box, grown by k_cp_walk's margin
-// (cp_margin_cells: the head of tirt_closest_point.hip has why it covers the decode's rounding), contains the corner's position v.  A triangle with a
+// (PointMargin: the head of tirt_point_walk.h has why it covers the decode's rounding), contains the corner's position v.  A triangle with a
 // corner AT v has v in its exact box, which the quantised boxes of its leaf slot and of every ancestor contain: every such triangle is reached, once
 // (a primitive has one leaf; the chain nodes at far_qcode hold analytic spheres only and are not entered).  At a triangle leaf t' that is valid
 // (0 < |g|^2 < inf) and has a corner == v (three fp32 ==), the lane adds I(alpha' n') to the vertex sum, and, if the corner before or after that one
@@ -14,12 +14,13 @@
 // The lane then writes its two rows; the class bits go into row 0's last word with an atomic OR (the table is zeroed first, which is also what the
 // rows of spheres, spots and lasers are).  tests/signed_distance_expected.py restates all of it in numpy with brute-force matching.
 //
-// The stack is k_cp_walk's with 4-byte entries (a child code; nothing is culled, so there is no lb2): CP_LDS_DEPTH per lane in LDS, the rest of
-// stack_size in the context's spill buffer.  An entry that does not fit is a triangle the sums may miss: the lane raises SdState::overflow and counts in
+// The stack is k_cp_walk's (PointStack, tirt_point_walk.h) with 4-byte entries (a child code; nothing is culled, so there is no lb2): CP_LDS_DEPTH per lane
+// in LDS, the rest of stack_size in the context's spill buffer.  An entry that does not fit is a triangle the sums may miss: the lane raises SdState::overflow and counts in
 // DevCounters::stack_overflow.  The SIGNED kernels answer NaN from such a table, tirt_stats reports TIRT_ERR_STACK, and every entry that waits for the
 // stream anyway (tirt_signed_distance, _prepare, _table_download) reads the verdict and returns TIRT_ERR_STACK itself (sd_table_verdict).
 #include "tirt_internal.h"
 #include "tirt_closest_point.h"
+#include "tirt_point_walk.h"
 
 namespace tirt {
 
@@ -32,7 +33,7 @@ struct SdArgs {
     BvhView bvh;
     const int *primitive, *prim_slot; int n_prim;
     int stack_size;
-    int *spill;                              // [stack_size - CP_LDS_DEPTH][gridDim.x * CP_BLOCK], or nullptr when stack_size <= CP_LDS_DEPTH
+    int *spill;                              // the stacks' tails (point_walk_launch_shape), or nullptr when stack_size <= CP_LDS_DEPTH
     float4 *tab; SdState *state; DevCounters *ctr;
 };
 
@@ -43,10 +44,7 @@ __global__ __launch_bounds__(CP_BLOCK) void k_sd_build(SdArgs a)
     __shared__ int stk[CP_LDS_DEPTH * CP_BLOCK];      // [entry][lane]
     const BvhView &b = a.bvh;
     const int lane = threadIdx.x;
-    const size_t gthreads = (size_t)gridDim.x * CP_BLOCK, gtid = (size_t)blockIdx.x * CP_BLOCK + lane;
-    const float cell_max = maxf(maxf(b.cell[0], b.cell[1]), b.cell[2]);
-    const float inv_ext = 1.0f / (cell_max * (2.0f * TR_GRID_HALF));
-    const float rho_0 = maxf(maxf(absf(b.grid_min[0]), absf(b.grid_min[1])), absf(b.grid_min[2])) * inv_ext;
+    const PointMargin pm(b);
     const int total = 3 * a.n_prim;
     unsigned long long n_over = 0, n_boundary = 0, n_nonmanifold = 0, n_flipped = 0, n_invalid = 0;
 
@@ -63,32 +61,17 @@ __global__ __launch_bounds__(CP_BLOCK) void k_sd_build(SdArgs a)
             v1 = k == 0 ? pb : (k == 1 ? pc : pa);
             own_valid = sd_triangle_normal(pa, pb, pc, own_n);
         }
-        const float rho_p = maxf(maxf(absf(v.x - b.grid_min[0]), absf(v.y - b.grid_min[1])), absf(v.z - b.grid_min[2])) * inv_ext;
-        const float m = cp_margin_cells(rho_p, rho_0) * cell_max;
+        const float m = pm.margin(b, v);
         long long sx = 0, sy = 0, sz = 0, ex = 0, ey = 0, ez = 0;
         int others = 0, same_way = 0;
         int cur = is_tri ? b.root_qcode : CP_SENT;
-        int sp = 0; bool overflow = false;
-
-#define SD_PUSH(code_)                                                                              \
-        do {                                                                                        \
-            if (sp < a.stack_size) {                                                                \
-                if (sp < CP_LDS_DEPTH) stk[sp * CP_BLOCK + lane] = (code_);                         \
-                else a.spill[(size_t)(sp - CP_LDS_DEPTH) * gthreads + gtid] = (code_);              \
-                sp++;                                                                               \
-            } else overflow = true;               /* out of room: the entry is lost, and the table with it */ \
-        } while (0)
-#define SD_POP()                                                                                    \
-        do {                                                                                        \
-            cur = CP_SENT;                                                                          \
-            if (sp > 0) { sp--; cur = sp < CP_LDS_DEPTH ? stk[sp * CP_BLOCK + lane] : a.spill[(size_t)(sp - CP_LDS_DEPTH) * gthreads + gtid]; } \
-        } while (0)
+        PointStack<int> st(stk, a.spill, a.stack_size, lane);
         // a child that is there and whose grown box holds v: the first becomes the next node, the others wait on the stack
-#define SD_CHILD(X, Y, Z, code_)                                                                    \
+#define SD_CHILD(i, X, Y, Z, code_)                                                                 \
         do {                                                                                        \
             const float gx__ = CP_AXIS_GAP(b, m, X, 0, v.x), gy__ = CP_AXIS_GAP(b, m, Y, 1, v.y), gz__ = CP_AXIS_GAP(b, m, Z, 2, v.z); \
-            if (((code_) != TR_EMPTY) & (gx__ == 0.0f) & (gy__ == 0.0f) & (gz__ == 0.0f)) {         \
-                if (nxt == CP_SENT) nxt = (code_); else SD_PUSH(code_);                             \
+            if (((int)(code_) != TR_EMPTY) & (gx__ == 0.0f) & (gy__ == 0.0f) & (gz__ == 0.0f)) {    \
+                if (nxt == CP_SENT) nxt = (int)(code_); else st.push((int)(code_));                 \
             }                                                                                       \
         } while (0)
 
@@ -97,16 +80,13 @@ __global__ __launch_bounds__(CP_BLOCK) void k_sd_build(SdArgs a)
                 const uint4 *w = b.cnode + (size_t)cur * 4;
                 const uint4 q0 = w[0], q1 = w[1], q2 = w[2], q3 = w[3];
                 int nxt = CP_SENT;
-                SD_CHILD(q0.x, q0.y, q0.z, (int)q3.x);
-                SD_CHILD(q0.w, q1.x, q1.y, (int)q3.y);
-                SD_CHILD(q1.z, q1.w, q2.x, (int)q3.z);
-                SD_CHILD(q2.y, q2.z, q2.w, (int)q3.w);
+                CP_EACH_CHILD(SD_CHILD);
                 cur = nxt;
-                if (cur == CP_SENT) SD_POP();
+                if (cur == CP_SENT && !st.empty()) cur = st.pop();
             } else {
                 const int code = ~cur;
-                if (((code >> 30) & 1) == 0) {
-                    const float4 *tp = b.tri + (size_t)(code & 0x3fffffff) * TRI_STRIDE;
+                if (leaf_is_tri(code)) {
+                    const float4 *tp = b.tri + (size_t)leaf_slot(code) * TRI_STRIDE;
                     const float4 ta = tp[0], tb = tp[1], tc = tp[2];
                     const int other = __float_as_int(tc.w);
                     const v3 pa = V(ta.x, ta.y, ta.z), pb = V(tb.x, tb.y, tb.z), pc = V(tc.x, tc.y, tc.z);
@@ -126,12 +106,10 @@ __global__ __launch_bounds__(CP_BLOCK) void k_sd_build(SdArgs a)
                         }
                     }
                 }
-                SD_POP();
+                cur = st.empty() ? CP_SENT : st.pop();
             }
         }
 #undef SD_CHILD
-#undef SD_POP
-#undef SD_PUSH
 
         if (is_tri) {
             float4 *rows = a.tab + (size_t)prim * SD_ROWS;
@@ -147,7 +125,7 @@ __global__ __launch_bounds__(CP_BLOCK) void k_sd_build(SdArgs a)
             if (bits) atomicOr((int *)rows + 3, bits);
             n_boundary += cls == 1; n_nonmanifold += cls == 2; n_flipped += cls == 3;
         }
-        if (overflow) { a.state->overflow = 1; n_over++; }
+        if (st.overflow) { a.state->overflow = 1; n_over++; }      // (the entry is lost, and the table with it)
     }
     n_over = wave_sum(n_over); n_boundary = wave_sum(n_boundary); n_nonmanifold = wave_sum(n_nonmanifold);
     n_flipped = wave_sum(n_flipped); n_invalid = wave_sum(n_invalid);
@@ -175,19 +153,8 @@ static int sd_table_build(tirt_ctx *c, int stack_size)
     a.primitive = c->primitive.as<int>(); a.prim_slot = c->prim_slot.as<int>(); a.n_prim = c->n;
     a.stack_size = stack_size;
     a.tab = c->sd_tab.as<float4>(); a.state = c->sd_state.as<SdState>(); a.ctr = c->dev_counters.as<DevCounters>();
-    int grid = c->cu_count * SD_WAVES_PER_CU;
-    const size_t tail = stack_size > CP_LDS_DEPTH ? (size_t)(stack_size - CP_LDS_DEPTH) * sizeof(int) : 0;      // bytes per thread
-    if (tail) { const size_t fit = CP_SPILL_BYTES_MAX / (tail * CP_BLOCK); if ((size_t)grid > fit) grid = (int)(fit > 0 ? fit : 1); }
-    const int blocks = (int)(((int64_t)3 * c->n + CP_BLOCK - 1) / CP_BLOCK);
-    if (grid > blocks) grid = blocks;
-    if (tail) {
-        const size_t want = tail * CP_BLOCK * (size_t)grid;
-        if (want > c->spill.bytes) {
-            TIRT_HIP(hipStreamSynchronize(c->stream));
-            if (c->spill.ensure(want)) return TIRT_ERR_HIP;
-        }
-        a.spill = c->spill.as<int>();
-    }
+    int grid;
+    if (int rc = point_walk_launch_shape(c, stack_size, SD_WAVES_PER_CU, ((int64_t)3 * c->n + CP_BLOCK - 1) / CP_BLOCK, grid, a.spill)) return rc;
     TIRT_HIP(hipMemsetAsync(c->sd_tab.p, 0, tab_bytes, c->stream));
     TIRT_HIP(hipMemsetAsync(c->sd_state.p, 0, sizeof(SdState), c->stream));
     hipLaunchKernelGGL(k_sd_build, dim3(grid), dim3(CP_BLOCK), 0, c->stream, a);

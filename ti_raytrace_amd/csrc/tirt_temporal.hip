@@ -220,13 +220,7 @@ int temporal_device(tirt_ctx *c, const float *hdr_c, const float *aov_c, const f
     TIRT_REQUIRE(W >= 1 && H >= 1 && (long long)W * H < (1ll << 30), fn + ": bad size");
     if (int rc = temporal_check_params(fn, prm)) return rc;
     TIRT_REQUIRE(cur && prev, fn + ": null camera");
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error(fn + ": the caller's stream is not a stream of this process's HIP runtime");
-        return TIRT_ERR_ARG;
-    }
-    TIRT_REQUIRE(cs == hipStreamCaptureStatusNone, fn + ": the caller's stream is capturing a graph (the accumulation cannot be captured)");
+    if (int rc = require_caller_stream(c, fn, stream, "the accumulation")) return rc;
     const size_t NP = (size_t)W * H;
     const int NA = motion ? 9 : 8;                         // the outputs are a[6] and a[7]
     const struct { const char *name; const void *p; size_t words; bool out; } a[9] = {
