@@ -84,7 +84,7 @@ int tirt_sync(tirt_ctx *ctx);
  *          "shade_grid" -- kernel tuning
  *          "shade_specialize" (0/1, default 1) -- k_shade / k_shade_spec are compiled for a few scene feature sets (tirt_shade_features); 1 launches the
  *            narrowest instantiation that covers the scene, 0 the generic kernel for every scene.  Same films bit for bit either way
- *          "query_chunk_rays" (256 .. 2^27, default 2^21) -- rays per chunk of tirt_query_closest / tirt_query_occluded (48 B of scratch each)
+ *          "query_chunk_rays" (256 .. 2^27, default 2^21) -- rays per chunk of tirt_query_closest / tirt_query_occluded (48 B of scratch each; tirt_query_hits divides it by k)
  *          "bdpt_bounded" (0/1, default 1) -- BDPT connection rays are cut off at their target distance (same
  *            visibility answers as the full closest-hit query; 0 = reference-style full query, for cross-checks)
  *          "merge_paths" -- consecutive tirt_pt_rgb_render calls over contiguous frames are merged
@@ -800,6 +800,42 @@ int tirt_query_closest(tirt_ctx *ctx, const float *rays, int64_t nr, int64_t ray
 int tirt_query_occluded(tirt_ctx *ctx, const float *rays, int64_t nr, int64_t ray_stride,
                         const float *tmax, int64_t tmax_stride, float tmax_all,
                         int stack_size, int flags, uint8_t *out_occluded, void *stream);
+
+/* First K hits (no reference counterpart as an entry point; csrc/tirt_multi_hit.hip / .h): the first k surfaces a ray meets, in order, and the count of all
+ * of them -- what a caller otherwise gets from k tirt_query_closest calls, each from the previous hit pushed along the ray by an epsilon (which skips or
+ * repeats surfaces closer together than the epsilon and loses one of two coincident triangles).  Everything is fp32, in the order written.
+ * Bound.  Ray i has a bound tmax (+inf when none is given) and B = min(1e6, tmax) (1e6 = INF_VALUE, the reference's "no hit").  A tmax that is <= 0 or NaN
+ *   finds nothing.
+ * The hit set H(i) holds every primitive p that meets all three conditions:
+ *   1. the reference's exhaustive traversal (Scene.py:702-744) reaches p's leaf: `slabs` passes on every proper ancestor of the leaf in the reference's LBVH;
+ *   2. the reference's primitive test gives 0 < t < B: Moller-Trumbore on E1 = v1 - v0, E2 = v2 - v0, or the analytic sphere's near root (Scene.py:529-638);
+ *   3. on a scene with cut-outs ("Alpha cut-outs"), the triangle is untagged or tex_alpha at the hit's uv is >= 0.5.
+ *   A ray with a NaN component has H = {}.  H is a set: it does not depend on the order of the visits.
+ * Order.  t ascending; at equal t bits the LARGER compact leaf index comes first -- the equal-distance rule of the closest hit, so the first element of H is
+ *   tirt_query_closest's hit, bit for bit, whenever tmax does not exclude it.
+ * Outputs, for k in 0 .. TIRT_HITS_MAX, each optional: out_t[i * k + j] and out_prim[i * k + j] for j < k are the j-th element of H(i), and 1e6 and -1 where
+ *   H has fewer; out_hit + (i * k + j) * hit_stride = the 13 floats of tirt_trace_closest for that hit (a miss as tirt_query_closest writes it);
+ *   out_count[i] = |H(i)| as int32, which may exceed k.  k == 0 with out_count is the count alone.  With out_count the walk has to meet every element of H and
+ *   culls by the bound only; without it, it also culls by the k-th nearest hit so far.
+ * tirt_query_hits: device memory on the caller's stream with tirt_query_closest's plumbing, flags and refusals; tmax[i * tmax_stride] per ray, or tmax_all for
+ *   every ray when tmax is NULL.  Rays go through in chunks of max(256, query_chunk_rays / max(k, 1)) (40 + 16 k bytes of scratch per ray); counts[nr*2] =
+ *   N_box, N_leaf per ray (8-byte aligned; only with TIRT_COUNT_NODES).  TIRT_TRAVERSE_EXHAUSTIVE walks the reference's two-child tree by the reference's rule
+ *   (no distance cull): the yardstick, same bits.  stack_size 1..4096 entries of 4 bytes per ray (the first 16 in LDS, the rest in the context's spill buffer);
+ *   an entry that does not fit is dropped and the ray counted in stack_overflow (tirt_stats: TIRT_ERR_STACK).  The rays count in rays_closest.
+ *   Refused with TIRT_ERR_ARG before anything is queued, beside tirt_query_closest's refusals: k outside 0 .. TIRT_HITS_MAX, k == 0 without out_count,
+ *   hit_stride < 13 with out_hit, tmax_stride < 1 with tmax.  nr == 0 queues nothing.
+ * tirt_trace_hits: host arrays (rays[nr*6], tmax[nr] or NULL = +inf, out_t[nr*k], out_prim[nr*k], out_hit[nr*k*13], out_count[nr], counts[nr*2]), staged and
+ *   synchronous, as tirt_trace_closest is to tirt_query_closest.
+ * tirt_kat_hit_list: host only, no context: the n candidates cand[4 i ..] = (t, u, v, bits leaf), leaf >= 0, in the order given through the list code the
+ *   kernel runs (csrc/tirt_multi_hit.h) with this k and bound.  out_list[4 j ..] = entry j; out_info = {entries held, candidates with 0 < t < B,
+ *   bits of the threshold distance, the threshold's leaf (-1: the list has room)}. */
+#define TIRT_HITS_MAX 64
+int tirt_query_hits(tirt_ctx *ctx, const float *rays, int64_t nr, int64_t ray_stride,
+                    const float *tmax, int64_t tmax_stride, float tmax_all, int k, int stack_size, int flags,
+                    float *out_t, int32_t *out_prim, float *out_hit, int64_t hit_stride, int32_t *out_count, int32_t *counts, void *stream);
+int tirt_trace_hits(tirt_ctx *ctx, const float *rays, int nr, const float *tmax, int k, int stack_size, int flags,
+                    float *out_t, int32_t *out_prim, float *out_hit, int32_t *out_count, int32_t *counts);
+int tirt_kat_hit_list(const float *cand, int n, int k, float bound, float *out_list, int32_t *out_info);
 
 /* Closest point (no reference counterpart; csrc/tirt_closest_point.h / .hip): the nearest surface point of the scene to a query point p.
  * Everything is fp32, every operation in the order written, no contraction; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.

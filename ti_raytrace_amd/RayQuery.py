@@ -4,6 +4,8 @@
     q = RayQuery(scene, stack_size=64, flags=0)           # scene after setup_data_gpu() (Example.build_scene)
     h = q.closest(rays, attributes=False)                 # RayHits(t [N] f32, prim [N] i32, record [N, 13] f32 or None)
     occ = q.occluded(rays, tmax=None)                     # [N] torch.bool: a hit with t < tmax (None = inf, a float, or an [N] f32 tensor)
+    m = q.hits(rays, k, tmax=None, attributes=False, count=False)   # RayMultiHits(t [N, k], prim [N, k], record [N, k, 13] or None, count [N] i32 or None)
+    c = q.count(rays, tmax=None)                          # [N] int32: all hits with t < tmax
 
 ``rays`` is a float32 tensor ``[N, C >= 6]`` on the scene context's device with ``stride(1) == 1`` and any row stride (origin, direction
 in the first six columns: an ``[N, 8]`` tensor's ``[:, :6]`` view works).  The outputs come from ``torch.empty`` on that device and the
@@ -11,11 +13,13 @@ work is queued on ``torch.cuda.current_stream(device)``: nothing waits for it on
 ``tirt_query_closest`` / ``tirt_query_occluded``).  ``record`` is tirt_trace_closest's: t, pos3, gnormal3, normal3, tex3.
 """
 import collections
+import operator
 import os
 
 from . import _native
 
 RayHits = collections.namedtuple("RayHits", ["t", "prim", "record"])
+RayMultiHits = collections.namedtuple("RayMultiHits", ["t", "prim", "record", "count"])
 
 
 def _torch():
@@ -69,6 +73,29 @@ class RayQuery:
             raise ValueError("RayQuery.%s: the last dimension of rays must have stride 1, got %d" % (what, rays.stride(1)))
         return dev, n, (rays.stride(0) if n > 1 else max(rays.shape[1], 6))
 
+    def _check_tmax(self, tmax, dev, n, what):
+        """tmax: None (= inf), a float for every ray, or an [N] float32 tensor on the rays' device (any positive stride) -> (address or 0, stride, value for all)"""
+        torch = self.torch
+        tptr, tstride, tall = 0, 1, float("inf")
+        if tmax is None:
+            pass
+        elif isinstance(tmax, torch.Tensor):
+            if tmax.dtype != torch.float32:
+                raise TypeError("RayQuery.%s: tmax must be float32, got %s" % (what, tmax.dtype))
+            if tmax.device != dev:
+                raise ValueError("RayQuery.%s: tmax is on %s, the rays on %s" % (what, tmax.device, dev))
+            if tmax.dim() != 1 or tmax.shape[0] != n:
+                raise ValueError("RayQuery.%s: tmax must be [N] = [%d], got shape %s" % (what, n, tuple(tmax.shape)))
+            if n > 1 and tmax.stride(0) < 1:
+                raise ValueError("RayQuery.%s: tmax must have a positive stride, got %d" % (what, tmax.stride(0)))
+            if n:
+                tptr, tstride = tmax.data_ptr(), (tmax.stride(0) if n > 1 else 1)
+        elif isinstance(tmax, (int, float)):
+            tall = float(tmax)
+        else:
+            raise TypeError("RayQuery.%s: tmax must be None, a float or a float32 tensor, got %s" % (what, type(tmax).__name__))
+        return tptr, tstride, tall
+
     def closest(self, rays, attributes=False):
         """Closest hit of every ray, bit for bit Context.trace_closest's: t (1e6 on a miss), prim (-1 on a miss) and, with
         attributes=True, the 13-float record.  Asynchronous on the current stream."""
@@ -102,27 +129,47 @@ class RayQuery:
         hit), a float for every ray, or an [N] float32 tensor on the same device (any stride).  tmax <= 0 or NaN gives False."""
         torch = self.torch
         dev, n, stride = self._check_rays(rays, "occluded")
-        tptr, tstride, tall = 0, 1, float("inf")
-        if tmax is None:
-            pass
-        elif isinstance(tmax, torch.Tensor):
-            if tmax.dtype != torch.float32:
-                raise TypeError("RayQuery.occluded: tmax must be float32, got %s" % tmax.dtype)
-            if tmax.device != dev:
-                raise ValueError("RayQuery.occluded: tmax is on %s, the rays on %s" % (tmax.device, dev))
-            if tmax.dim() != 1 or tmax.shape[0] != n:
-                raise ValueError("RayQuery.occluded: tmax must be [N] = [%d], got shape %s" % (n, tuple(tmax.shape)))
-            if n > 1 and tmax.stride(0) < 1:
-                raise ValueError("RayQuery.occluded: tmax must have a positive stride, got %d" % tmax.stride(0))
-            if n:
-                tptr, tstride = tmax.data_ptr(), (tmax.stride(0) if n > 1 else 1)
-        elif isinstance(tmax, (int, float)):
-            tall = float(tmax)
-        else:
-            raise TypeError("RayQuery.occluded: tmax must be None, a float or a float32 tensor, got %s" % type(tmax).__name__)
+        tptr, tstride, tall = self._check_tmax(tmax, dev, n, "occluded")
         out = torch.empty(n, dtype=torch.uint8, device=dev)
         if n:
             stream = torch.cuda.current_stream(dev).cuda_stream
             self.scene.ctx.query_occluded(rays.data_ptr(), n, stride, out.data_ptr(), tmax=tptr, tmax_stride=tstride, tmax_all=tall,
                                           stack_size=self.stack_size, flags=self.flags, stream=stream)
         return out.view(torch.bool)
+
+    def hits(self, rays, k, tmax=None, attributes=False, count=False):
+        """The first k hits along every ray, in order (include/tirt.h, "First K hits"): RayMultiHits(t [N, k] f32, prim [N, k] i32, record [N, k, 13] f32 or
+        None, count [N] i32 or None).  Entry 0 is closest()'s hit, bit for bit; entries beyond a ray's hits are 1e6 and -1.  tmax as for occluded(): only
+        hits with t < tmax.  count=True also returns the number of ALL hits below tmax (it may exceed k; the walk then culls by tmax alone).
+        Asynchronous on the current stream."""
+        torch = self.torch
+        dev, n, stride = self._check_rays(rays, "hits")
+        try:
+            k = None if isinstance(k, bool) else operator.index(k)      # (an int of any kind: numpy's too)
+        except TypeError:
+            k = None
+        if k is None or not 1 <= k <= _native.HITS_MAX:
+            raise ValueError("RayQuery.hits: k must be an int in 1..%d (count() returns the count alone)" % _native.HITS_MAX)
+        tptr, tstride, tall = self._check_tmax(tmax, dev, n, "hits")
+        t = torch.empty((n, k), dtype=torch.float32, device=dev)
+        prim = torch.empty((n, k), dtype=torch.int32, device=dev)
+        rec = torch.empty((n, k, 13), dtype=torch.float32, device=dev) if attributes else None
+        cnt = torch.empty(n, dtype=torch.int32, device=dev) if count else None
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self.scene.ctx.query_hits(rays.data_ptr(), n, stride, k, self.stack_size, self.flags, tmax=tptr, tmax_stride=tstride, tmax_all=tall,
+                                      out_t=t.data_ptr(), out_prim=prim.data_ptr(), out_hit=rec.data_ptr() if rec is not None else 0, hit_stride=13,
+                                      out_count=cnt.data_ptr() if cnt is not None else 0, stream=stream)
+        return RayMultiHits(t, prim, rec, cnt)
+
+    def count(self, rays, tmax=None):
+        """[N] int32: the number of hits along every ray with t < tmax (crossing parity, thickness, transmittance).  Asynchronous on the current stream."""
+        torch = self.torch
+        dev, n, stride = self._check_rays(rays, "count")
+        tptr, tstride, tall = self._check_tmax(tmax, dev, n, "count")
+        cnt = torch.empty(n, dtype=torch.int32, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self.scene.ctx.query_hits(rays.data_ptr(), n, stride, 0, self.stack_size, self.flags, tmax=tptr, tmax_stride=tstride, tmax_all=tall,
+                                      out_count=cnt.data_ptr(), stream=stream)
+        return cnt

@@ -17,8 +17,8 @@ if _os.environ.get("TIRT_NO_ENV_TUNING", "0") in ("", "0"):
     _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 from . import SceneData, UtilsFunc, Texture, Camera, LBvh, Scene, PT_RGB, BDPT_RGB, Debug, Example  # noqa: F401
-from .RayQuery import RayQuery, RayHits  # noqa: F401  (torch is imported when a RayQuery is made)
+from .RayQuery import RayQuery, RayHits, RayMultiHits  # noqa: F401  (torch is imported when a RayQuery is made)
 from .PointQuery import PointQuery, PointHits, SignedHits  # noqa: F401  (torch is imported when a PointQuery is made)
 from .Denoise import denoise, denoise_var, temporal_accumulate  # noqa: F401  (torch is imported when they are called)
 
-__all__ = ["SceneData", "UtilsFunc", "Texture", "Camera", "LBvh", "Scene", "PT_RGB", "BDPT_RGB", "Debug", "Example", "RayQuery", "RayHits", "PointQuery", "PointHits", "SignedHits", "denoise", "denoise_var", "temporal_accumulate"]
+__all__ = ["SceneData", "UtilsFunc", "Texture", "Camera", "LBvh", "Scene", "PT_RGB", "BDPT_RGB", "Debug", "Example", "RayQuery", "RayHits", "RayMultiHits", "PointQuery", "PointHits", "SignedHits", "denoise", "denoise_var", "temporal_accumulate"]

@@ -100,6 +100,7 @@ KAT_ENV_SAMPLE_IN, KAT_ENV_SAMPLE_OUT = 2, 10                       # words per 
 KAT_ENV_PDF_IN, KAT_ENV_PDF_OUT = 3, 5                              # words per row of tirt_kat_env_pdf
 KAT_ALPHA_IN, KAT_ALPHA_OUT = 3, 2                                  # words per row of tirt_kat_texture_alpha
 KAT_MAPS_IN, KAT_MAPS_OUT = 3, 8                                    # words per row of tirt_kat_material_maps
+HITS_MAX = 64                                                       # TIRT_HITS_MAX: the largest k of tirt_query_hits
 KAT_STEP_IN, KAT_STEP_OUT = 23, 28                                  # words per row of tirt_kat_shade_step
 
 # context options that select code rather than tune it: name -> (default, meaning).  (The tuning options are listed in include/tirt.h.)
@@ -175,6 +176,9 @@ SIGNATURES = {
     "tirt_trace_shadow": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _vp]),
     "tirt_query_closest": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
     "tirt_query_occluded": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int, _vp, _vp]),
+    "tirt_query_hits": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp]),
+    "tirt_trace_hits": (C.c_int, [_vp, _f32p, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "tirt_kat_hit_list": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_float, _vp, _i32p]),
     "tirt_query_closest_point": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64,
                                            _vp, C.c_int64, _vp, _vp]),
     "tirt_closest_point": (C.c_int, [_vp, _f32p, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -865,6 +869,29 @@ class Context:
         check(lib().tirt_query_occluded(self.handle, _vp(int(rays) or None), int(nr), int(ray_stride), _vp(int(tmax) or None), int(tmax_stride),
                                         float(tmax_all), int(stack_size), int(flags), _vp(int(out_occluded) or None), _vp(int(stream) or None)))
 
+    def query_hits(self, rays, nr, ray_stride, k, stack_size=64, flags=0, tmax=0, tmax_stride=1, tmax_all=float("inf"), out_t=0, out_prim=0, out_hit=0,
+                   hit_stride=13, out_count=0, counts=0, stream=0):
+        """tirt_query_hits on device memory (include/tirt.h, "First K hits"): every buffer is an integer device address (0 = none), tmax = 0 means
+        tmax_all for every ray.  Asynchronous; ti_raytrace_amd.RayQuery.hits / .count are the torch front end."""
+        check(lib().tirt_query_hits(self.handle, _vp(int(rays) or None), int(nr), int(ray_stride), _vp(int(tmax) or None), int(tmax_stride), float(tmax_all),
+                                    int(k), int(stack_size), int(flags), _vp(int(out_t) or None), _vp(int(out_prim) or None), _vp(int(out_hit) or None),
+                                    int(hit_stride), _vp(int(out_count) or None), _vp(int(counts) or None), _vp(int(stream) or None)))
+
+    def trace_hits(self, rays, k, tmax=None, stack_size=64, flags=0, attributes=False, count=True):
+        """tirt_trace_hits, the host route: rays (n, 6) float32, tmax None (= inf), a float or (n,) float32 ->
+        (t (n, k), prim (n, k), record (n, k, 13) or None, count (n,) or None, counts (n, 2) or None [COUNT_NODES])"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n, k = rays.shape[0], int(k)
+        bound = None if tmax is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (n,)))
+        t = np.zeros((n, max(k, 0)), np.float32)
+        prim = np.zeros((n, max(k, 0)), np.int32)
+        rec = np.zeros((n, max(k, 0), 13), np.float32) if attributes else None
+        cnt = np.zeros(n, np.int32) if count else None
+        counts = np.zeros((n, 2), np.int32) if (flags & COUNT_NODES) else None
+        check(lib().tirt_trace_hits(self.handle, rays.reshape(-1), n, _ptr(bound), k, int(stack_size), int(flags), _ptr(t), _ptr(prim), _ptr(rec),
+                                    _ptr(cnt), _ptr(counts)))
+        return t, prim, rec, cnt, counts
+
     def query_closest_point(self, points, n, point_stride, stack_size=64, flags=0, dmax=0, dmax_stride=1, dmax_all=float("inf"), out_d2=0, out_prim=0,
                             out_point=0, point_out_stride=3, out_uv=0, uv_stride=2, counts=0, stream=0):
         """tirt_query_closest_point on device memory: every buffer is an integer device address (0 = none), dmax = 0 means dmax_all for every
@@ -1050,6 +1077,16 @@ def shade_instantiation(word, specialize=True, spectral=False):
     out = C.c_uint32(0)
     check(lib().tirt_shade_instantiation(int(word), int(specialize), int(spectral), C.byref(out)))
     return int(out.value)
+
+
+def kat_hit_list(cand, k, bound=float("inf")):
+    """include/tirt.h, tirt_kat_hit_list (host only, no context): cand (n, 4) words (t, u, v as float32 bits, leaf as int32), in the order given, through the
+    list code of csrc/tirt_multi_hit.h -> (list (held, 4) words, candidates with 0 < t < B, (threshold t, threshold leaf))"""
+    cand = np.ascontiguousarray(cand).view(np.float32).reshape(-1, 4)
+    out = np.zeros((max(int(k), 0), 4), np.float32)
+    info = np.zeros(4, np.int32)
+    check(lib().tirt_kat_hit_list(cand.reshape(-1), cand.shape[0], int(k), float(bound), _ptr(out), info))
+    return out[:info[0]].copy(), int(info[1]), (float(info[2:3].view(np.float32)[0]), int(info[3]))
 
 
 def shade_features_host(material, primitive, shape, light, light_count, env=None, env_power=0.0):

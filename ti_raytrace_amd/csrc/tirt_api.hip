@@ -2,6 +2,7 @@
 // tone map, Scene.process_normal / total_area kernels, stats.  (The known-answer entries tirt_kat_*: tirt_kat.hip.)
 #include "tirt_internal.h"
 #include "tirt_spectral.h"
+#include "tirt_multi_hit.h"
 #include <stddef.h>
 #include <algorithm>
 #include <mutex>
@@ -1332,6 +1333,52 @@ int tirt_query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_
 {
     CTX(c);
     return query_occluded(c, rays, nr, ray_stride, tmax, tmax_stride, tmax_all, stack_size, flags, out_occluded, stream);
+}
+
+// (the checks of k need no context: they come first)
+#define HITS_K_CHECKS(fn)                                                                                     \
+    TIRT_REQUIRE(k >= 0 && k <= TIRT_HITS_MAX, fn ": k outside 0..TIRT_HITS_MAX (64)");                       \
+    TIRT_REQUIRE(k > 0 || out_count, fn ": k == 0 without out_count (nothing to return)")
+int tirt_query_hits(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, const float *tmax, int64_t tmax_stride, float tmax_all, int k,
+                    int stack_size, int flags, float *out_t, int32_t *out_prim, float *out_hit, int64_t hit_stride, int32_t *out_count, int32_t *counts,
+                    void *stream)
+{
+    HITS_K_CHECKS("tirt_query_hits");
+    CTX(c);
+    return query_hits(c, rays, nr, ray_stride, tmax, tmax_stride, tmax_all, k, stack_size, flags, out_t, out_prim, out_hit, hit_stride, out_count, counts, stream);
+}
+
+int tirt_trace_hits(tirt_ctx *c, const float *rays, int nr, const float *tmax, int k, int stack_size, int flags, float *out_t, int32_t *out_prim,
+                    float *out_hit, int32_t *out_count, int32_t *counts)
+{
+    HITS_K_CHECKS("tirt_trace_hits");
+    CTX(c);
+    return trace_hits_host(c, rays, nr, tmax, k, stack_size, flags, out_t, out_prim, out_hit, out_count, counts);
+}
+#undef HITS_K_CHECKS
+
+// host only, no context: candidates (t, u, v, bits leaf) in the order given through MhList (tirt_multi_hit.h), the text k_multi_hit runs
+int tirt_kat_hit_list(const float *cand, int n, int k, float bound, float *out_list, int32_t *out_info)
+{
+    TIRT_REQUIRE(cand && out_info && n >= 0, "tirt_kat_hit_list: null pointer or negative n");
+    TIRT_REQUIRE(k >= 0 && k <= TIRT_HITS_MAX && (k == 0 || out_list), "tirt_kat_hit_list: k outside 0..TIRT_HITS_MAX (64), or no out_list");
+    struct HostList {
+        float *p;
+        MhEntry get(int e) const { MhEntry r; r.t = p[4 * e]; r.u = p[4 * e + 1]; r.v = p[4 * e + 2]; memcpy(&r.leaf, p + 4 * e + 3, 4); return r; }
+        void set(int e, const MhEntry c) { p[4 * e] = c.t; p[4 * e + 1] = c.u; p[4 * e + 2] = c.v; memcpy(p + 4 * e + 3, &c.leaf, 4); }
+    } list = {out_list};
+    const float B = bound < INF_VALUE ? bound : INF_VALUE;
+    MhList L(k, B);
+    int accepted = 0;
+    for (int i = 0; i < n; i++) {
+        MhEntry c; c.t = cand[4 * i]; c.u = cand[4 * i + 1]; c.v = cand[4 * i + 2]; memcpy(&c.leaf, cand + 4 * i + 3, 4);
+        TIRT_REQUIRE(c.leaf >= 0, "tirt_kat_hit_list: a candidate's leaf index is negative");
+        if (!(bound > 0.0f)) continue;                                     // tmax <= 0 or NaN finds nothing
+        if ((c.t > 0.0f) & hit_before(c.t, c.leaf, B, -1)) accepted++;      // membership of H: trace_leaf_step against (B, -1)
+        if (L.wants(c.t, c.leaf)) L.insert(list, c);
+    }
+    out_info[0] = L.n; out_info[1] = accepted; memcpy(&out_info[2], &L.thr_t, 4); out_info[3] = L.thr_leaf;
+    return TIRT_OK;
 }
 
 int tirt_bvh_info(tirt_ctx *c, uint64_t out[4])

@@ -538,6 +538,16 @@ int query_closest(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride
                   float *out_hit, int64_t hit_stride, int32_t *counts, void *stream);      // tirt_query.hip
 int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, const float *tmax, int64_t tmax_stride, float tmax_all,
                    int stack_size, int flags, uint8_t *out_occluded, void *stream);
+// the first k hits of every ray and the count of all (include/tirt.h "First K hits"): the plumbing is tirt_query.hip's, the walk tirt_multi_hit.hip's
+int query_hits(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, const float *tmax, int64_t tmax_stride, float tmax_all, int k, int stack_size,
+               int flags, float *out_t, int32_t *out_prim, float *out_hit, int64_t hit_stride, int32_t *out_count, int32_t *counts, void *stream);
+int trace_hits_host(tirt_ctx *c, const float *rays, int nr, const float *tmax, int k, int stack_size, int flags, float *out_t, int32_t *out_prim,
+                    float *out_hit, int32_t *out_count, int32_t *counts);
+struct MultiHitShape { int grid = 0; void *spill = nullptr; };      // blocks of a launch at most, and the tails of their stacks (multi_hit_shape)
+int multi_hit_shape(tirt_ctx *c, int stack_size, int64_t chunk_rays, MultiHitShape &shape);
+int multi_hit_chunk(tirt_ctx *c, const MultiHitShape &shape, const float4 *rec, float4 *list, int2 *meta, size_t stride, int64_t base, int n, int k,
+                    int stack_size, int flags, bool count_all, int2 *counts, float *out_t, int32_t *out_prim, float *out_hit, int64_t hit_stride,
+                    int32_t *out_count);
 // what the entry points that take caller-owned device memory share (tirt_query.hip): the pointer check, the check of the caller's stream ("... (`what` cannot be
 // captured)"), the first checks of every query, and the two events that order the context's stream after and before the caller's
 int require_device_ptr(tirt_ctx *c, const void *p, const char *what);

@@ -1,5 +1,6 @@
 // tirt_query.hip -- closest-hit and occlusion queries on rays that live in device memory (tirt_query_closest / tirt_query_occluded), and
-// the host route (tirt_trace_closest / tirt_trace_shadow) through the same closest-hit path.
+// the host route (tirt_trace_closest / tirt_trace_shadow) through the same closest-hit path.  At the end of the file: the same plumbing around the
+// first-K-hits walk of tirt_multi_hit.hip (tirt_query_hits / tirt_trace_hits).
 //
 // No reference counterpart as an entry point: the traversal is Scene.closet_hit / closet_hit_shadow (Scene.py:702-744, 671-699), run by
 // the existing k_trace instantiations.  What is new is the plumbing around it, in chunks of option "query_chunk_rays" rays, all on the
@@ -246,6 +247,106 @@ int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_strid
         hipLaunchKernelGGL(k_query_resolve_occluded, g, dim3(B), 0, c->stream, (const float4 *)rec, (const float4 *)hit, base, n, out_occluded);
     }
     return query_end(c, stream);
+}
+
+// ---- the first k hits and the count of all (include/tirt.h "First K hits"; the walk is tirt_multi_hit.hip's) ----
+// Rays per chunk: max(256, query_chunk_rays / max(k, 1)), so that the scratch -- 32 B of ray record, 16 B x k of list and 8 B of (entries, count) per ray --
+// stays of the order the other queries' is.
+static int hits_chunk_of(const tirt_ctx *c, int64_t nr, int k)
+{
+    int64_t chunk = (int64_t)c->query_chunk / (k > 0 ? k : 1);
+    if (chunk < 256) chunk = 256;
+    return (int)(nr < chunk ? nr : chunk);
+}
+struct HitsScratch { float4 *rec, *list; int2 *meta; MultiHitShape shape; };
+// (growing a buffer waits for the work queued on the context's stream, which may still read the old one)
+static int hits_prepare(tirt_ctx *c, int chunk, int k, int stack_size, HitsScratch &s)
+{
+    const size_t bytes = (size_t)chunk * (40 + 16 * (size_t)k);
+    if (bytes > c->query_mem.bytes) {
+        TIRT_HIP(hipStreamSynchronize(c->stream));
+        if (c->query_mem.ensure(bytes)) return TIRT_ERR_HIP;
+    }
+    s.rec = c->query_mem.as<float4>();
+    s.list = s.rec + 2 * (size_t)chunk;
+    s.meta = (int2 *)(s.list + (size_t)k * chunk);
+    if (ensure_counters(c)) return TIRT_ERR_HIP;
+    return multi_hit_shape(c, stack_size, chunk, s.shape);
+}
+// pack, walk, resolve: `nr` rays in chunks of `chunk` on the context's stream; every pointer is device memory (or null)
+static int hits_chunks(tirt_ctx *c, const HitsScratch &s, const float *rays, int64_t nr, int64_t ray_stride, const float *tmax, int64_t tmax_stride,
+                       float tmax_all, int k, int stack_size, int flags, int chunk, float *out_t, int32_t *out_prim, float *out_hit, int64_t hit_stride,
+                       int32_t *out_count, int2 *counts)
+{
+    const int B = 256;
+    for (int64_t base = 0; base < nr; base += chunk) {
+        const int n = (int)(nr - base < chunk ? nr - base : chunk);
+        hipLaunchKernelGGL(k_query_pack, dim3((unsigned)((n + B - 1) / B)), dim3(B), 0, c->stream, rays, base, n, ray_stride, 1, tmax, tmax_stride, tmax_all, s.rec);
+        if (int rc = multi_hit_chunk(c, s.shape, s.rec, s.list, s.meta, (size_t)chunk, base, n, k, stack_size, flags, out_count != nullptr,
+                                     counts ? counts + base : nullptr, out_t, out_prim, out_hit, hit_stride, out_count)) return rc;
+    }
+    return TIRT_OK;
+}
+
+int query_hits(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, const float *tmax, int64_t tmax_stride, float tmax_all, int k, int stack_size,
+               int flags, float *out_t, int32_t *out_prim, float *out_hit, int64_t hit_stride, int32_t *out_count, int32_t *counts, void *stream)
+{
+    const char *fn = "tirt_query_hits";
+    if (int rc = ray_query_checks(c, fn, nr, ray_stride, stack_size, flags, stream)) return rc;
+    TIRT_REQUIRE(!out_hit || hit_stride >= 13, "tirt_query_hits: hit_stride < 13 (floats per hit record)");
+    TIRT_REQUIRE(!tmax || tmax_stride >= 1, "tirt_query_hits: tmax_stride < 1");
+    TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, "tirt_query_hits: counts must be 8-byte aligned");
+    if (nr == 0) return TIRT_OK;
+    TIRT_REQUIRE(rays, "tirt_query_hits: null rays");
+    if (int rc = require_device_ptr(c, rays, "tirt_query_hits: rays")) return rc;
+    if (tmax) if (int rc = require_device_ptr(c, tmax, "tirt_query_hits: tmax")) return rc;
+    if (out_t) if (int rc = require_device_ptr(c, out_t, "tirt_query_hits: out_t")) return rc;
+    if (out_prim) if (int rc = require_device_ptr(c, out_prim, "tirt_query_hits: out_prim")) return rc;
+    if (out_hit) if (int rc = require_device_ptr(c, out_hit, "tirt_query_hits: out_hit")) return rc;
+    if (out_count) if (int rc = require_device_ptr(c, out_count, "tirt_query_hits: out_count")) return rc;
+    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
+    if (want_counts) if (int rc = require_device_ptr(c, counts, "tirt_query_hits: counts")) return rc;
+    const int chunk = hits_chunk_of(c, nr, k);
+    HitsScratch s;
+    if (int rc = hits_prepare(c, chunk, k, stack_size, s)) return rc;
+    if (int rc = query_begin(c, stream)) return rc;
+    if (int rc = hits_chunks(c, s, rays, nr, ray_stride, tmax, tmax_stride, tmax_all, k, stack_size, flags, chunk, out_t, out_prim, out_hit, hit_stride,
+                             out_count, want_counts ? (int2 *)counts : nullptr)) return rc;
+    return query_end(c, stream);
+}
+
+// tirt_trace_hits: host arrays staged in device memory (counts [nr][2] first: 8-byte aligned; rays [nr][6], tmax [nr], t [nr][k], prim [nr][k],
+// records [nr][k][13], count [nr]), through the chunks above, back to the host with a sync
+int trace_hits_host(tirt_ctx *c, const float *rays, int nr, const float *tmax, int k, int stack_size, int flags, float *out_t, int32_t *out_prim,
+                    float *out_hit, int32_t *out_count, int32_t *counts)
+{
+    if (int rc = query_common_checks(c, "tirt_trace_hits", "nr", nr, stack_size, flags)) return rc;
+    if (nr == 0) return TIRT_OK;
+    TIRT_REQUIRE(rays, "tirt_trace_hits: null rays");
+    const size_t N = (size_t)nr, K = (size_t)k;
+    const int chunk = hits_chunk_of(c, nr, k);
+    HitsScratch s;
+    if (int rc = hits_prepare(c, chunk, k, stack_size, s)) return rc;
+    hipStream_t st = c->stream;
+    if (c->trace_stage.ensure(sizeof(float) * N * (10 + 15 * K))) return TIRT_ERR_HIP;      // (used by the host routes alone, and each of their calls ends with a sync)
+    int2 *d_counts = c->trace_stage.as<int2>();
+    float *d_rays = (float *)(d_counts + N), *d_tmax = d_rays + 6 * N, *d_t = d_tmax + N;
+    int32_t *d_prim = (int32_t *)(d_t + K * N);
+    float *d_hit = (float *)(d_prim + K * N);
+    int32_t *d_count = (int32_t *)(d_hit + 13 * K * N);
+    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
+    TIRT_HIP(hipMemcpyAsync(d_rays, rays, sizeof(float) * 6 * N, hipMemcpyHostToDevice, st));
+    if (tmax) TIRT_HIP(hipMemcpyAsync(d_tmax, tmax, sizeof(float) * N, hipMemcpyHostToDevice, st));
+    if (int rc = hits_chunks(c, s, d_rays, nr, 6, tmax ? d_tmax : nullptr, 1, __builtin_inff(), k, stack_size, flags, chunk, out_t ? d_t : nullptr,
+                             out_prim ? d_prim : nullptr, out_hit ? d_hit : nullptr, 13, out_count ? d_count : nullptr, want_counts ? d_counts : nullptr)) return rc;
+    if (out_t && k) TIRT_HIP(hipMemcpyAsync(out_t, d_t, sizeof(float) * K * N, hipMemcpyDeviceToHost, st));
+    if (out_prim && k) TIRT_HIP(hipMemcpyAsync(out_prim, d_prim, sizeof(int32_t) * K * N, hipMemcpyDeviceToHost, st));
+    if (out_hit && k) TIRT_HIP(hipMemcpyAsync(out_hit, d_hit, sizeof(float) * 13 * K * N, hipMemcpyDeviceToHost, st));
+    if (out_count) TIRT_HIP(hipMemcpyAsync(out_count, d_count, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+    if (want_counts) TIRT_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int2) * N, hipMemcpyDeviceToHost, st));
+    TIRT_HIP(hipStreamSynchronize(st));
+    TIRT_HIP(hipGetLastError());
+    return TIRT_OK;
 }
 
 }  // namespace tirt

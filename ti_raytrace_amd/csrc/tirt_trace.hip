@@ -19,6 +19,7 @@
 // first and keeps the first-found candidate on `t < hit_t`): the candidate with the larger
 // compact-node index wins.
 #include "tirt_trace.h"
+#include "tirt_trace_box.h"
 
 namespace tirt {
 
@@ -36,7 +37,6 @@ namespace tirt {
 // (a one-ray-per-lane loop measured 15 % VALU lane utilisation on this workload).  Inner-node
 // steps and triangle tests run in separate loops so that lanes doing the same thing run together.
 typedef float f2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) int lds_int;
 constexpr int TR_PAGE = 8;                    // stack entries moved per page-out / page-in
 constexpr int TR_SENT = (int)0x80000000;      // "stack empty": never a node index nor a leaf code
@@ -296,24 +296,13 @@ __global__ __launch_bounds__(TR_BLOCK, TR_MIN_WAVES) void k_trace(typename trace
                     // from the grid therefore does not cull by distance either (no hit-distance cull, no target-distance bound):
                     // it visits every leaf whose boxes it passes, as the reference does, and so finds the same candidates.
                     if (rho__ > TR_FAR_RHO) cull_far = -3.0e38f;
-#define TR_GRID_AXIS(rel, dd, idd, k, gA, gBn, gBf, grot)                                            \
-                    do {                                                                             \
-                        if (absf(dd) < 0.000001f) {      /* the reference's parallel case: origin inside the slab or no hit */ \
-                            const float og__ = -(rel) * (k == 0 ? c_ic0 : (k == 1 ? c_ic1 : c_ic2));                               \
-                            gA = 1.0e30f; gBn = (-og__ - (mc__ + 1.0f)) * 1.0e30f; gBf = (-og__ + (mc__ + 1.0f)) * 1.0e30f; grot = 0; \
-                        } else {                                                                     \
-                            gA = (k == 0 ? c_ce0 : (k == 1 ? c_ce1 : c_ce2)) * (idd);                                                  \
-                            const float gB__ = (rel) * (idd);                                        \
-                            const float m__ = mc__ * absf(gA);                                       \
-                            gBn = gB__ - m__; gBf = gB__ + m__; grot = gA < 0.0f ? 16 : 0;           \
-                        }                                                                            \
-                    } while (0)
+                    // (TR_GRID_AXIS, and TR_CBOX of the node step: tirt_trace_box.h, one text for this kernel and k_multi_hit)
                     TR_GRID_AXIS(relx__, d.x, r.idx, 0, gAx, gBnx, gBfx, grotx);
                     TR_GRID_AXIS(rely__, d.y, r.idy, 1, gAy, gBny, gBfy, groty);
                     TR_GRID_AXIS(relz__, d.z, r.idz, 2, gAz, gBnz, gBfz, grotz);
                 }
-                if (BOUNDED && t_bound > 0.0f && cull_far > 0.0f) { cull_far = t_bound * 1.01f; settle = t_bound * 0.99f; }
-                lim = __builtin_fminf(__builtin_fminf(hit_t * 1.0001f, __builtin_fabsf(cull_far)), INF_VALUE);      // (v_min: a canonical value, so the node loop does not re-canonicalise it every step)
+                if (BOUNDED && t_bound > 0.0f && cull_far > 0.0f) { cull_far = t_bound * TR_BOUND_SLACK; settle = t_bound * 0.99f; }
+                lim = __builtin_fminf(__builtin_fminf(hit_t * TR_CULL_SLACK, __builtin_fabsf(cull_far)), INF_VALUE);      // (v_min: a canonical value, so the node loop does not re-canonicalise it every step)
                 // (a far-origin ray cannot trust the padded boxes of the analytic spheres: it starts at a chain node that holds the root and
                 // those spheres with whole-grid boxes, BvhView::far_qcode, and so tests them whatever their boxes say -- as the reference does)
                 cur = (MODE == TIRT_TRAVERSE_EXHAUSTIVE) ? c_root : (cull_far < 0.0f ? c_farq : c_rootq);
@@ -430,22 +419,6 @@ __global__ __launch_bounds__(TR_BLOCK, TR_MIN_WAVES) void k_trace(typename trace
                     float d0, d1, d2, d3;                // entry distance of a hit box, MISS otherwise
                     // near/far crossing of each axis: one rotate, two v_fma_mix_f32 (fp16 plane x f32 + f32); then
                     // box hit and entry not beyond the cull distance: tn <= min(tf, lim)
-#define TR_CBOX(X, Y, Z, dist)                                                                       \
-                    do {                                                                             \
-                        const unsigned ux__ = __builtin_amdgcn_alignbit((X), (X), grotx);            \
-                        const unsigned uy__ = __builtin_amdgcn_alignbit((Y), (Y), groty);            \
-                        const unsigned uz__ = __builtin_amdgcn_alignbit((Z), (Z), grotz);            \
-                        const h2v hx__ = __builtin_bit_cast(h2v, ux__), hy__ = __builtin_bit_cast(h2v, uy__), hz__ = __builtin_bit_cast(h2v, uz__); \
-                        const float nx__ = __builtin_fmaf((float)hx__.x, gAx, gBnx), fx__ = __builtin_fmaf((float)hx__.y, gAx, gBfx); \
-                        const float ny__ = __builtin_fmaf((float)hy__.x, gAy, gBny), fy__ = __builtin_fmaf((float)hy__.y, gAy, gBfy); \
-                        const float nz__ = __builtin_fmaf((float)hz__.x, gAz, gBnz), fz__ = __builtin_fmaf((float)hz__.y, gAz, gBfz); \
-                        const float tn__ = __builtin_fmaxf(__builtin_fmaxf(nx__, ny__), __builtin_fmaxf(nz__, 0.0f)); \
-                        /* the far distance in the INTEGER domain (v_min_i32 / v_min3_i32: no canonicalisation of `lim` per step):   \
-                           exact for non-negative floats, and a negative operand (box behind the ray) gives a negative result */      \
-                        const int tfi__ = min(min(__float_as_int(fx__), __float_as_int(fy__)), min(__float_as_int(fz__), lim_i));     \
-                        const float tf__ = __int_as_float(tfi__);                                    \
-                        dist = (tn__ <= tf__) ? tn__ : MISS;                                         \
-                    } while (0)
                     TR_CBOX(q0.x, q0.y, q0.z, d0);
                     TR_CBOX(q0.w, q1.x, q1.y, d1);
                     TR_CBOX(q1.z, q1.w, q2.x, d2);
@@ -494,7 +467,7 @@ __global__ __launch_bounds__(TR_BLOCK, TR_MIN_WAVES) void k_trace(typename trace
             else accepted = trace_leaf_step<MODE != TIRT_TRAVERSE_EXHAUSTIVE>(b, r, par, code, hit_t, hit_u, hit_v, hit_prim, hit_leaf);
             if (from_pend) pend = 0; else TR_POP(cur);
             if (accepted) {
-                lim = __builtin_fminf(__builtin_fminf(cull_far < 0.0f ? INF_VALUE : hit_t * 1.0001f, __builtin_fabsf(cull_far)), INF_VALUE);      // (v_min: a canonical value, so the node loop does not re-canonicalise it every step)
+                lim = __builtin_fminf(__builtin_fminf(cull_far < 0.0f ? INF_VALUE : hit_t * TR_CULL_SLACK, __builtin_fabsf(cull_far)), INF_VALUE);      // (v_min: a canonical value, so the node loop does not re-canonicalise it every step)
                 if (BOUNDED && hit_prim != expect && hit_t < settle) { cur = TR_SENT; paged = 0; pend = 0; }      // answer settled: "occluded"
             }
         }
