@@ -116,6 +116,12 @@ int tirt_sync(tirt_ctx *ctx);
  *            (default 16): batches of fewer frames keep the ordinary launch (making the lists costs 1.2 ms at 1024^2).  "primary_beams_rebuild" (any value):
  *            the lists are forgotten and made again by the next batch that uses them (bench.py times a build inside its clock).  When the memory for the
  *            lists is not to be had the render goes on without them (tirt_primary_beam_stats out[7]).
+ *          "primary_fused" -- (default 1) a PT_RGB batch that uses the lists computes a camera ray's direction, walks its pixel's list and performs the path's first
+ *            shading step in ONE kernel (k_pvb_cand_shade, csrc/tirt_render.hip): the direction and the hit record stay in registers instead of going through
+ *            device memory between three kernels.  The rays the lists leave over are traced as before and shaded by a second, short launch.  Same film, same
+ *            counters, bit for bit; with "time_kernels" both launches count as shading time.  0 = the separate launches (k_generate, k_pvb_cand, k_trace,
+ *            k_pvb_scatter, k_shade).  Batches with feature buffers enabled (tirt_aov_enable reads the camera rays' hit records), of a pixel set, of PT_Spec
+ *            or under "primary_beams_diag" take the separate launches whatever the value.
  *          "bdpt_batch_items" -- (frame, pixel) items per BDPT wavefront batch (default 16 Mi, ~2.2 KB of HBM each: 38 GB; 5 Mi = 12 GB runs config 5 at 2 900 Mrays/s), shared by the batches in flight on render lanes 0 and 1 ("bdpt_lanes", 1..4, default 2: three or four measured no faster)
  *            (config 5, round 3: 4 Mi 2 890, 8 Mi 2 900, 16 Mi 2 995, 32 Mi 2 980 Mrays/s; 256 frames: 8 Mi 2 912, 16 Mi 2 923, 32 Mi 3 032)
  *            A call never sizes its batches beyond what hipMemGetInfo reports free (less 2 GB): next to other users of the device it renders in smaller batches.

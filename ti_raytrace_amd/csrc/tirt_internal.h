@@ -440,6 +440,7 @@ struct tirt_ctx {
     struct PvbSet { tirt::DevBuf count, cand, bound; hipEvent_t busy = nullptr; } pvb_set[2];
     int pvb_cur = 0;                              // the set pvb_key describes
     int pvb_diag = 0;                             // option "primary_beams_diag": k_pvb_cand counts its leaf steps (one atomic per wave: slow) -- tirt_primary_beam_stats out[8..11]
+    int primary_fused = 1;                        // option "primary_fused": PT_RGB's camera ray, list walk and first shading step in one kernel (k_pvb_cand_shade, tirt_render.hip); 0 = the five launches
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pvb_ev;      // HIP events around every list build since the last tirt_stats_reset (read by tirt_primary_beam_stats)
     unsigned long long pvb_builds = 0, pvb_build_ns = 0, pvb_skipped = 0;      // list builds since the reset, their device time, builds given up for lack of memory
     tirt::DevBuf pvb_stat, pvb_tmp;               // (pvb_tmp: the probe scratch where the runtime has no stream-ordered allocation)

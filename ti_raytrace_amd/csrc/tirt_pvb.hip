@@ -20,6 +20,7 @@
 //                     the other rays (no hit within bound: they slipped past what the probes saw) are appended to a list,
 //     k_trace         over that list (directions compacted into the idle `out` arrays of the batch, hits into the idle shadow
 //                     arrays), k_pvb_scatter puts its hit records where bounce 0 expects them.
+//   A PT_RGB batch does k_pvb_cand's walk (pvb_walk_list, tirt_pvb.h) inside its first shading kernel instead: k_pvb_cand_shade, tirt_render.hip.
 //
 // Why the hit records are the ones k_trace writes, bit for bit.  k_trace's answer for a ray is the minimum (distance, then larger
 // leaf index) over the VERIFIED primitive hits of all leaves it reaches, and it reaches every leaf whose enlarged boxes (its own
@@ -29,18 +30,15 @@
 // the list lies within bound it is therefore k_trace's; if not, k_trace is asked.  A list made with bound = infinity (some probe
 // left the scene) and not cut short is complete: a miss on it is a miss.  Rays that fail `slabs` on the root's exact box miss, as in
 // k_trace (KIND_CLOSEST).  A camera further than TR_FAR_RHO extents from the scene (k_trace stops culling by distance there) gets no lists.
-#include "tirt_trace.h"
+#include "tirt_pvb.h"
 #include <cstring>
 
 namespace tirt {
 
-constexpr int PVB_CMAX = 24;                        // leaves on a pixel's list (12: 3 % of the headline's pixels without a list, -1.3 %; 48: no gain -- profiles/r05an_*)
 constexpr int PVB_STACK = 96;                       // node stack of a beam walk (4-wide tree: three entries per level at most)
 constexpr float PVB_WIDEN = 0.55f;                  // the pyramid's corners in pixels from the centre (the jitter is [-0.5, 0.5))
 constexpr float PVB_REACH = 1.5f;                   // a pixel's list reaches this far beyond the farthest probe hit (1.0001: 1.4 % of the camera rays find nothing on their list, 1.25: 0.10 %, 1.5: 0.08 %; profiles/r05an_*)
 constexpr int PVB_BLOCK = 1024;                      // threads of a k_pvb_cand block
-
-struct PvbView { const int *count; const int2 *cand; const float *bound; };     // [P], [PVB_CMAX][P] (leaf code, bits of the nearest distance any ray of the pixel can reach the leaf's box at), [P]; count < 0: no list
 
 __global__ void k_pvb_probes(CameraView cam, TileMap tm, int P, float4 *rays)
 {
@@ -218,35 +216,10 @@ __global__ __launch_bounds__(PVB_BLOCK) void k_pvb_cand(BvhView b, PvbView pv, c
     if (tm.F > 0) { const int ch = __builtin_amdgcn_readfirstlane(s >> 6); k = ((ch / tm.F) << 6) | (s & 63); }
     else if (live) { int f; slot_to_frame_pixel(tm, P, s, f, k); }
     const v3 d = live ? V(__builtin_nontemporal_load(&dx[s]), __builtin_nontemporal_load(&dy[s]), __builtin_nontemporal_load(&dz[s])) : V(0.0f, 0.0f, 1.0f);
-    const RayCtx r = make_ray(eye, d);
-    const bool par = ray_has_parallel_axis(r);
-    int n = live ? pv.count[k] : 0;
-    const float bound = live ? pv.bound[k] : 0.0f;
-    bool resolved = live && n >= 0;
-    // k_trace's first step for a camera ray: the root's exact box -- when the root is an inner node: in a one-primitive scene the root IS the leaf, k_trace
-    // goes straight to the primitive test and a hit that fails the leaf's box has no ancestor to be refused by -- and a NaN ray misses
-    bool dead = false;
-    if (live) {
-        float tn;
-        if (b.root_qcode >= 0 && !slabs(r, b.root_min[0], b.root_min[1], b.root_min[2], b.root_max[0], b.root_max[1], b.root_max[2], tn)) dead = true;
-        if (!((d.x == d.x) & (d.y == d.y) & (d.z == d.z))) dead = true;
-    }
-    if (dead) { n = 0; resolved = true; }
-    if (!resolved) n = 0;
-    float hit_t = INF_VALUE, hit_u = 0.0f, hit_v = 0.0f; int hit_prim = -1, hit_leaf = -1;
+    // the walk of the list, the root-box and NaN shortcuts and the `bound` rule: pvb_walk_list (tirt_pvb.h), shared with k_pvb_cand_shade
+    float hit_t, hit_u, hit_v; int hit_prim;
     int steps = 0, trips = 0;          // (diagnostics, option "primary_beams_diag")
-    for (int c = 0; c < PVB_CMAX; c++) {
-        // (the lists are sorted by the distance at which a ray of the pixel can reach the leaf's box at the earliest: beyond the hit so far, nothing on the rest of the list can win or tie)
-        int2 en = make_int2(0, 0x7f800000);
-        if (c < n) en = pv.cand[(size_t)c * P + k];
-        const bool go = c < n && __int_as_float(en.y) <= hit_t;
-        if (!go) n = 0;
-        if (__ballot(go) == 0ull) break;
-        trips++; if (go) steps++;
-        if (go) (void)trace_leaf_step<true>(b, r, par, ~en.x, hit_t, hit_u, hit_v, hit_prim, hit_leaf);      // k_trace's leaf step itself (tirt_internal.h)
-    }
-    // within bound: k_trace's answer (a list made without a bound is complete: whatever it says holds)
-    if (resolved && !dead && !(hit_t <= bound) && bound < INF_VALUE) resolved = false;
+    const bool resolved = pvb_walk_list(b, pv, P, k, live, eye, d, hit_t, hit_u, hit_v, hit_prim, steps, trips);
     if (resolved) {
         typedef float f4n __attribute__((ext_vector_type(4)));
         f4n hv = {hit_t, hit_u, hit_v, __int_as_float(hit_prim)};

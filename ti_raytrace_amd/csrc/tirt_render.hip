@@ -20,9 +20,12 @@
 // come in the reference's order: a lane's launches are on one stream, and within a launch a path has one writer.  A path that goes on moves 11 words from one
 // PathSoA to the other (ray, throughput, brdf_pdf, and the slot word with perfect_spec in its bit 31); the rr / rg / rb / flags arrays are PT_Spec's.
 //
+// A PT_RGB batch whose camera rays go through the pixels' candidate lists (tirt_pvb.hip) does k_generate, the list pass and k_shade of bounce 0 in one kernel,
+// k_pvb_cand_shade below (option "primary_fused"): the direction and the first hit record never reach HBM.
+//
 // k_trace and its launchers (the walk, its two visiting rules, the tie rule) are in tirt_trace.hip; this file holds the shading kernels, the tables of
 // their instantiations and the scheduler that submits a batch's launches (pt_render), in that order.
-#include "tirt_trace.h"
+#include "tirt_pvb.h"
 #include "tirt_spectral.h"
 
 namespace tirt {
@@ -259,15 +262,11 @@ TD void shade_path(const SceneView &sc, const TileMap &tm, int P, uint32_t frame
 // ---------------------------------------------------------------------------------------------
 // Wavefront PT_RGB
 // ---------------------------------------------------------------------------------------------
+// The camera ray of path s of a batch: its pixel, the frame's sub-pixel jitter, the direction through it (Camera.py:122-142).  k_generate stores it; the fused
+// first step (k_pvb_cand_shade) keeps it in registers.
 template <bool LIST>
-__global__ void k_generate(PathSoA ps, CameraView cam, TileMap tm, int P, int S, uint32_t frame_begin, uint32_t seed,
-                           DevCounters *ctr)
+TD v3 camera_path_direction(const CameraView &cam, const TileMap &tm, int P, int s, uint32_t frame_begin, uint32_t seed)
 {
-    // Camera rays.  Only the direction is stored: the origin is the eye for every path and the rest of the
-    // bounce-0 state is constant (throughput 1, radiance 0, pdf 1, specular flag set, path id = index), which
-    // k_trace / k_shade of bounce 0 know without reading 48 bytes per path back from HBM.
-    int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= S) return;
     int f, k; slot_to_frame_pixel(tm, P, s, f, k);
     int p = mapped_pixel<LIST>(tm, k);
     int i = p / tm.H, j = p - i * tm.H;
@@ -277,7 +276,19 @@ __global__ void k_generate(PathSoA ps, CameraView cam, TileMap tm, int P, int S,
         jx = tm_rand(seed, (uint32_t)p, frame, TM_DIM_JX) - 0.5f;
         jy = tm_rand(seed, (uint32_t)p, frame, TM_DIM_JY) - 0.5f;
     }
-    v3 d = camera_ray_direction(cam, i, j, jx, jy);
+    return camera_ray_direction(cam, i, j, jx, jy);
+}
+
+template <bool LIST>
+__global__ void k_generate(PathSoA ps, CameraView cam, TileMap tm, int P, int S, uint32_t frame_begin, uint32_t seed,
+                           DevCounters *ctr)
+{
+    // Camera rays.  Only the direction is stored: the origin is the eye for every path and the rest of the
+    // bounce-0 state is constant (throughput 1, radiance 0, pdf 1, specular flag set, path id = index), which
+    // k_trace / k_shade of bounce 0 know without reading 48 bytes per path back from HBM.
+    int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    v3 d = camera_path_direction<LIST>(cam, tm, P, s, frame_begin, seed);
     __builtin_nontemporal_store(d.x, &ps.dx[s]); __builtin_nontemporal_store(d.y, &ps.dy[s]); __builtin_nontemporal_store(d.z, &ps.dz[s]);      // (a stream: k_trace reads it once)
     if (s == 0) atomicAdd(&ctr->paths, (unsigned long long)S);
 }
@@ -308,6 +319,12 @@ __global__ void k_generate(PathSoA ps, CameraView cam, TileMap tm, int P, int S,
 #endif
 #ifndef SH_MIN_WAVES_HDR         // the generic kernel's twin for an RGBE8 environment (SF_ENV_HDR): see DESIGN.md, "HDR environment"
 #define SH_MIN_WAVES_HDR 5       // as its 8-bit sibling: no scratch at 5 (96 VGPRs) since the radiance is no longer live across shade_path (it had 12 bytes, and sat at 4)
+#endif
+#ifndef SH_MIN_WAVES_FUSED_NARROW      // k_pvb_cand_shade<.., true> of the two narrow kernels: 85 VGPRs at 5 waves, 80 and still no scratch at 6 -- and the list walk
+#define SH_MIN_WAVES_FUSED_NARROW 6    // in it waits on memory, which a sixth wave covers: +0.6 % on the headline against 5, every pair (profiles/primary_fused_ab.txt)
+#endif
+#ifndef SH_MIN_WAVES_FUSED_WIDE  // k_pvb_cand_shade<.., true> of the generic kernels that sit at 5 waves (SF_ALL, + SF_TEXTURE, + SF_ENV_HDR): the leftover rays' direction is live
+#define SH_MIN_WAVES_FUSED_WIDE 4      // across shade_path; at 5 (96 VGPRs) they have 20-24 bytes of scratch where k_shade has none, at 4 none (profiles/primary_fused.txt)
 #endif
 // The 78 array pointers of the path state are the first kernel argument and are never read from it directly: each of the three places
 // that needs some of them (a path's state in, the survivor's state out, the shadow ray out) reads those from the kernel-argument segment in
@@ -435,6 +452,145 @@ __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_shade(ShadeArgs paths_i
     if ((threadIdx.x & 63) == 0 && n_shaded) atomicAdd(&s_shaded, n_shaded);
     __syncthreads();
     if (threadIdx.x == 0 && s_shaded) atomicAdd(&ctr->shaded, s_shaded);
+}
+
+// The first step of a camera path in ONE kernel (option "primary_fused"): what k_generate, k_pvb_cand and k_shade of bounce 0 do one after the other, without the
+// direction (12 B written, 24 B read per path) and the hit record (16 B written, 16 B read) going through HBM in between.  k_shade's shape -- blocks, persistent
+// rounds, SH_COLD, one packed atomic per block and round -- around the same three device functions: camera_path_direction, pvb_walk_list (tirt_pvb.h), shade_path.
+//   WALK:   path q of the batch: its direction, its pixel's list; a ray the list resolves is shaded on the spot (k_shade's `first` state: origin = eye, throughput 1,
+//           pdf 1, perfect_spec set, slot == q) and stores its first radiance; a ray it does not resolve is appended to the leftover list -- its slot in in.ox, its
+//           direction in in.dx / dy / dz: the arrays k_generate would have filled -- with a second atomic of the block between the same two barriers (as k_pvb_cand).
+//   !WALK:  after k_trace has written the leftovers' hit records to ps.hit[0 .. n): entry q of that list, shaded with the same state and the slot from the list,
+//           its survivors and shadow rays appended behind the others through the same counter of bounce 0.  Nothing is scattered.
+// The device counters are the three kernels': paths, rays_closest and stat[3], stat[4] (WALK), shaded (both).
+template <unsigned FEAT, int MIN_WAVES, bool WALK>
+__global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_pvb_cand_shade(ShadeArgs paths_in_kernarg_segment, SceneView sc, BvhView bv, PvbView pv, CameraView cam, TileMap tm, int P,
+                                                            uint32_t frame_begin, uint32_t seed, int last_bounce,
+                                                            const int *count_ptr, int count_fixed, unsigned long long *append_ctr, int *fb_count,
+                                                            DevCounters *ctr, unsigned long long *stat)
+{
+    __shared__ unsigned s_wcnt[2][SH_BLOCK / 64], s_fcnt[2][SH_BLOCK / 64];
+    __shared__ unsigned long long s_base[2];
+    __shared__ int s_fbase[2];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const int count = count_ptr ? *count_ptr : count_fixed;
+    const int total = gridDim.x * blockDim.x;
+    const int rounds = (count + total - 1) / total;
+    const v3 eye = V(cam.eye[0], cam.eye[1], cam.eye[2]);
+    unsigned long long n_shaded = 0;
+    for (int it = 0; it < rounds; it++) {
+        const int q = it * total + blockIdx.x * blockDim.x + threadIdx.x;
+        const bool live = q < count;
+        bool shade = false, left = false, want_next = false, want_shadow = false;
+        int slot = 0;
+        v3 direction = V(0.0f, 0.0f, 1.0f);
+        float4 hrec = make_float4(INF_VALUE, 0.0f, 0.0f, __int_as_float(-1));
+        if constexpr (WALK) {
+            // the ray's local pixel, as k_pvb_cand finds it (pixel-block-major numbering: the 64-path chunk is the wave's, its division by F scalar)
+            int k = 0;
+            if (tm.F > 0) { const int ch = __builtin_amdgcn_readfirstlane(q >> 6); k = ((ch / tm.F) << 6) | (q & 63); }
+            else if (live) { int f; slot_to_frame_pixel(tm, P, q, f, k); }
+            slot = q;
+            if (live) direction = camera_path_direction<false>(cam, tm, P, q, frame_begin, seed);
+            float hit_t, hit_u, hit_v; int hit_prim, steps = 0, trips = 0;
+            shade = pvb_walk_list(bv, pv, P, k, live, eye, direction, hit_t, hit_u, hit_v, hit_prim, steps, trips);
+            hrec = make_float4(hit_t, hit_u, hit_v, __int_as_float(hit_prim));
+            left = live && !shade;
+        } else if (live) {
+            SH_COLD(ca);
+            const int *const c_slot = (const int *)ca->in.ox; const float4 *const c_hit = ca->ps.hit;
+            const float *const c_dx = ca->in.dx, *const c_dy = ca->in.dy, *const c_dz = ca->in.dz;
+            asm volatile("" :: "s"(c_slot), "s"(c_hit), "s"(c_dx), "s"(c_dy), "s"(c_dz));
+            slot = SH_LD(c_slot[q]);
+            direction = V(SH_LD(c_dx[q]), SH_LD(c_dy[q]), SH_LD(c_dz[q]));
+            typedef float f4nt__ __attribute__((ext_vector_type(4)));
+            const f4nt__ hnt__ = __builtin_nontemporal_load((const f4nt__ *)&c_hit[q]);
+            hrec = make_float4(hnt__.x, hnt__.y, hnt__.z, hnt__.w);
+            shade = true;
+        }
+        v3 radiance = V(0.0f, 0.0f, 0.0f), next_o = radiance, next_d = radiance, next_thr = radiance;
+        v3 sh_o = radiance, sh_d = radiance, sh_c = radiance;
+        float next_pdf = 0.0f, sh_dist = 0.0f; int next_spec = 0, sh_expect = -2;
+        if (shade) {
+            ShadeStep ss;
+            shade_path<FEAT, false>(sc, tm, P, frame_begin, seed, 0, last_bounce, slot, eye, direction, hrec, V(1.0f, 1.0f, 1.0f), 1.0f, 1, ss);
+            want_next = ss.want_next; want_shadow = ss.want_shadow; if (ss.shaded) n_shaded++;
+            next_o = ss.next_o; next_d = ss.next_d; next_thr = ss.next_thr; next_pdf = ss.next_pdf; next_spec = ss.next_spec;
+            sh_o = ss.sh_o; sh_d = ss.sh_d; sh_c = ss.sh_c; sh_expect = ss.sh_expect; sh_dist = ss.sh_dist;
+            if (ss.adds) radiance = radiance + ss.add;       // 0 + term: the add stays, 0 + (-0) is +0 (k_shade at bounce 0)
+        }
+        // dense compaction, as in k_shade; the leftover rays of the block take their places in their list between the same barriers
+        const int par = it & 1;
+        const unsigned long long nmask = __ballot(want_next), smask = __ballot(want_shadow), fmask = WALK ? __ballot(left) : 0ull;
+        if (lane == 0) { s_wcnt[par][wid] = (unsigned)__popcll(nmask) | ((unsigned)__popcll(smask) << 16); if (WALK) s_fcnt[par][wid] = (unsigned)__popcll(fmask); }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned tn = 0, tsd = 0, tf = 0;
+#pragma unroll
+            for (int w = 0; w < SH_BLOCK / 64; w++) { tn += s_wcnt[par][w] & 0xffffu; tsd += s_wcnt[par][w] >> 16; if (WALK) tf += s_fcnt[par][w]; }
+            s_base[par] = (tn | tsd) ? atomicAdd(append_ctr, (unsigned long long)tn | ((unsigned long long)tsd << 32)) : 0ull;
+            if (WALK) {
+                s_fbase[par] = tf ? atomicAdd(fb_count, (int)tf) : 0;
+                if (stat && tf) atomicAdd(&stat[3], (unsigned long long)tf);
+            }
+        }
+        __syncthreads();
+        unsigned pn = 0, psd = 0, pf = 0;
+#pragma unroll
+        for (int w = 0; w < SH_BLOCK / 64; w++) if (w < wid) { pn += s_wcnt[par][w] & 0xffffu; psd += s_wcnt[par][w] >> 16; if (WALK) pf += s_fcnt[par][w]; }
+        const unsigned long long bb = s_base[par];
+        const int qn = (int)(unsigned)(bb & 0xffffffffull) + (int)pn + __popcll(nmask & lt_mask);
+        const int qs = (int)(unsigned)(bb >> 32) + (int)psd + __popcll(smask & lt_mask);
+        if (WALK && left) {
+            SH_COLD(ca);
+            int *const l_slot = (int *)ca->in.ox; float *const l_dx = ca->in.dx, *const l_dy = ca->in.dy, *const l_dz = ca->in.dz;
+            asm volatile("" :: "s"(l_slot), "s"(l_dx), "s"(l_dy), "s"(l_dz));
+            const int at = s_fbase[par] + (int)pf + __popcll(fmask & lt_mask);
+            l_slot[at] = slot; l_dx[at] = direction.x; l_dy[at] = direction.y; l_dz[at] = direction.z;
+        }
+        if (want_next) {
+            SH_COLD(ca);
+            float *const o_ox = ca->out.ox, *const o_oy = ca->out.oy, *const o_oz = ca->out.oz, *const o_dx = ca->out.dx, *const o_dy = ca->out.dy, *const o_dz = ca->out.dz;
+            float *const o_tr = ca->out.tr, *const o_tg = ca->out.tg, *const o_tb = ca->out.tb;
+            float *const o_pdf = ca->out.brdf_pdf; int *const o_slot = ca->out.slot;
+            asm volatile("" :: "s"(o_ox), "s"(o_oy), "s"(o_oz), "s"(o_dx), "s"(o_dy), "s"(o_dz), "s"(o_tr), "s"(o_tg), "s"(o_tb), "s"(o_pdf), "s"(o_slot));
+            SH_ST(o_ox[qn], next_o.x); SH_ST(o_oy[qn], next_o.y); SH_ST(o_oz[qn], next_o.z);
+            SH_ST(o_dx[qn], next_d.x); SH_ST(o_dy[qn], next_d.y); SH_ST(o_dz[qn], next_d.z);
+            SH_ST(o_tr[qn], next_thr.x); SH_ST(o_tg[qn], next_thr.y); SH_ST(o_tb[qn], next_thr.z);
+            SH_ST(o_pdf[qn], next_pdf); SH_ST(o_slot[qn], (int)((uint32_t)slot | ((uint32_t)next_spec << 31)));
+        }
+        // the path's first radiance (k_shade at bounce 0; WALK: slot == q, coalesced).  A leftover ray stores none yet: its !WALK pass does
+        if (shade) {
+            SH_COLD(ca);
+            float *const f_r = ca->ps.fr, *const f_g = ca->ps.fg, *const f_b = ca->ps.fb;
+            asm volatile("" :: "s"(f_r), "s"(f_g), "s"(f_b));
+            SH_ST(f_r[slot], radiance.x); SH_ST(f_g[slot], radiance.y); SH_ST(f_b[slot], radiance.z);
+        }
+        if (want_shadow) {
+            SH_COLD(ca);
+            float *const s_ox = ca->ps.sox, *const s_oy = ca->ps.soy, *const s_oz = ca->ps.soz, *const s_dx = ca->ps.sdx, *const s_dy = ca->ps.sdy, *const s_dz = ca->ps.sdz;
+            float *const s_cr = ca->ps.scr, *const s_cg = ca->ps.scg, *const s_cb = ca->ps.scb, *const s_dist = ca->ps.sdist;
+            int *const s_prim = ca->ps.sprim, *const s_dst = ca->ps.sdst;
+            asm volatile("" :: "s"(s_ox), "s"(s_oy), "s"(s_oz), "s"(s_dx), "s"(s_dy), "s"(s_dz), "s"(s_cr), "s"(s_cg), "s"(s_cb), "s"(s_dist), "s"(s_prim), "s"(s_dst));
+            SH_ST(s_ox[qs], sh_o.x); SH_ST(s_oy[qs], sh_o.y); SH_ST(s_oz[qs], sh_o.z);
+            SH_ST(s_dx[qs], sh_d.x); SH_ST(s_dy[qs], sh_d.y); SH_ST(s_dz[qs], sh_d.z);
+            SH_ST(s_cr[qs], sh_c.x); SH_ST(s_cg[qs], sh_c.y); SH_ST(s_cb[qs], sh_c.z);
+            SH_ST(s_prim[qs], sh_expect); SH_ST(s_dist[qs], sh_dist);
+            SH_ST(s_dst[qs], ~slot);
+        }
+    }
+    __shared__ unsigned long long s_shaded;
+    if (threadIdx.x == 0) s_shaded = 0ull;
+    __syncthreads();
+    n_shaded = wave_sum(n_shaded);
+    if ((threadIdx.x & 63) == 0 && n_shaded) atomicAdd(&s_shaded, n_shaded);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_shaded) atomicAdd(&ctr->shaded, s_shaded);
+    if (WALK && blockIdx.x == 0 && threadIdx.x == 0) {          // what k_generate and k_pvb_cand count
+        atomicAdd(&ctr->paths, (unsigned long long)count); atomicAdd(&ctr->rays_closest, (unsigned long long)count);
+        if (stat) atomicAdd(&stat[4], (unsigned long long)count);
+    }
 }
 
 // integrator/PT_RGB.py:134-136, frames applied in order
@@ -702,22 +858,25 @@ __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_kat_shade_step(SceneVie
 typedef void (*shade_fn_t)(ShadeArgs, SceneView, TileMap, int, uint32_t, uint32_t, int, int, const int *, int, unsigned long long *, DevCounters *, v3);
 typedef void (*shade_spec_fn_t)(ShadeArgs, SceneView, SpecView, TileMap, int, uint32_t, uint32_t, int, int, const int *, int, unsigned long long *, DevCounters *, v3);
 typedef void (*kat_step_fn_t)(SceneView, const float *, int, float *, int, int);
-struct ShadeInst { unsigned feat; shade_fn_t fn, fn_list; kat_step_fn_t kat; };      // fn_list: the same kernel for the batches of a pixel set (LIST); kat: tirt_kat_shade_step's
+typedef void (*fused_fn_t)(ShadeArgs, SceneView, BvhView, PvbView, CameraView, TileMap, int, uint32_t, uint32_t, int, const int *, int, unsigned long long *, int *, DevCounters *, unsigned long long *);
+// fn_list: the same kernel for the batches of a pixel set (LIST); kat: tirt_kat_shade_step's; fused, fused_rest: the first step of a camera path in one kernel
+// (k_pvb_cand_shade with WALK) and its pass over the rays the lists left to k_trace (without)
+struct ShadeInst { unsigned feat; shade_fn_t fn, fn_list; kat_step_fn_t kat; fused_fn_t fused, fused_rest; };
 struct ShadeSpecInst { unsigned feat; shade_spec_fn_t fn; };
-template <unsigned F, int MW>
-constexpr ShadeInst shade_inst() { return {F, k_shade<F, MW>, k_shade<F, MW, true>, k_kat_shade_step<F, MW>}; }
+template <unsigned F, int MW, int MW_WALK = MW>      // MW_WALK: the bound of the fused kernel that walks the lists, where it differs (SH_MIN_WAVES_FUSED_WIDE)
+constexpr ShadeInst shade_inst() { return {F, k_shade<F, MW>, k_shade<F, MW, true>, k_kat_shade_step<F, MW>, k_pvb_cand_shade<F, MW_WALK, true>, k_pvb_cand_shade<F, MW, false>}; }
 // (Built and left out: SF_GLASS | SF_ENV | SF_LIGHT_SPHERE for Teapot and the gallery spheres -- 3 509 VALU against the generic 3 872, but 12 bytes of scratch at
 // the 96-VGPR limit where the generic kernel has none; those scenes stay on the generic kernel.)
 constexpr unsigned SF_I_MAPS = SF_ALL | SF_TEXTURE | SF_TEXTURE_PARAM;               // every texture slot of a material row
 constexpr unsigned SF_E = SF_ENV_SAMPLE, SF_H = SF_ENV_HDR, SF_P = SF_LIGHT_POWER;
 static const ShadeInst SHADE_RGB[] = {
-    shade_inst<SF_LIGHT_SPHERE, SH_MIN_WAVES_NARROW>(),      // Disney, sphere lights, black environment: the synthetic headline scene
-    shade_inst<SF_LIGHT_TRI, SH_MIN_WAVES_NARROW>(),         // Disney, mesh lights, black environment: Cornell box, Veach
-    shade_inst<SF_ALL, SH_MIN_WAVES>(),
-    shade_inst<SF_ALL | SF_TEXTURE, SH_MIN_WAVES>(),         // textured scenes: the generic kernel + the albedo lookup
+    shade_inst<SF_LIGHT_SPHERE, SH_MIN_WAVES_NARROW, SH_MIN_WAVES_FUSED_NARROW>(),      // Disney, sphere lights, black environment: the synthetic headline scene
+    shade_inst<SF_LIGHT_TRI, SH_MIN_WAVES_NARROW, SH_MIN_WAVES_FUSED_NARROW>(),         // Disney, mesh lights, black environment: Cornell box, Veach
+    shade_inst<SF_ALL, SH_MIN_WAVES, SH_MIN_WAVES_FUSED_WIDE>(),
+    shade_inst<SF_ALL | SF_TEXTURE, SH_MIN_WAVES, SH_MIN_WAVES_FUSED_WIDE>(),         // textured scenes: the generic kernel + the albedo lookup
     shade_inst<SF_I_MAPS, SH_MIN_WAVES_MAPS>(),              // + roughness, metallic and normal maps
     shade_inst<SF_ALL | SF_E, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_MAPS | SF_E, SH_MIN_WAVES_ENV>(),
-    shade_inst<SF_ALL | SF_H, SH_MIN_WAVES_HDR>(), shade_inst<SF_I_MAPS | SF_H, SH_MIN_WAVES_MAPS>(),
+    shade_inst<SF_ALL | SF_H, SH_MIN_WAVES_HDR, SH_MIN_WAVES_FUSED_WIDE>(), shade_inst<SF_I_MAPS | SF_H, SH_MIN_WAVES_MAPS>(),
     shade_inst<SF_ALL | SF_E | SF_H, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_MAPS | SF_E | SF_H, SH_MIN_WAVES_ENV>(),
     shade_inst<SF_ALL | SF_P, SH_MIN_WAVES_POWER>(), shade_inst<SF_I_MAPS | SF_P, SH_MIN_WAVES_MAPS>(),
     shade_inst<SF_ALL | SF_E | SF_P, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_MAPS | SF_E | SF_P, SH_MIN_WAVES_ENV>(),
@@ -943,8 +1102,12 @@ static int submit_batch(tirt_ctx *c, const RenderCall &r, Lane &L, uint32_t f0, 
     TIRT_HIP(hipEventRecord(r0, st));
     KernelTimers t = {c->time_kernels != 0, st, {}, {}, {}};
 
+    // the first step of the camera paths in one kernel (k_pvb_cand_shade, option "primary_fused") wherever nothing but bounce 0 itself reads the directions and
+    // the hit records of the camera rays: the feature buffers do (aov_launch), PT_Spec and a pixel set have no fused kernel, the diagnostics are k_pvb_cand's
+    const bool fused = use_beams && c->primary_fused && !spec && !r.list && !c->aov.p && !c->pvb_diag;
+
     TIRT_HIP(hipMemsetAsync(L.counters_mem.p, 0, lane_counter_bytes(max_depth), st));
-    hipLaunchKernelGGL(r.list ? k_generate<true> : k_generate<false>, dim3((S + B - 1) / B), dim3(B), 0, st, L.ps.st[0], c->cam, tm, P, S, f0, seed, ctr);
+    if (!fused) hipLaunchKernelGGL(r.list ? k_generate<true> : k_generate<false>, dim3((S + B - 1) / B), dim3(B), 0, st, L.ps.st[0], c->cam, tm, P, S, f0, seed, ctr);
     // a batch that will run next to the previous one (still in flight on another lane) uses fewer persistent
     // blocks, so that both traversal kernels find LDS on the CUs; a batch submitted to an idle GPU takes them all
     bool busy = false;
@@ -979,28 +1142,45 @@ static int submit_batch(tirt_ctx *c, const RenderCall &r, Lane &L, uint32_t f0, 
         const bool beams = b == 0 && use_beams;
         int *const fb_count = (int *)append_ctr(0) + 4;          // (zeroed with the batch's counters; words 0, 1 of the line: the appends of bounce 0)
         float4 *const fb_hit = (float4 *)L.ps.sox;               // sox, soy, soz, sdx: four consecutive arrays of the lane's pitch
-        if (beams) {
+        // Fused: the kernel's own survivors and shadow rays go where those leftovers went, so they are listed in the `in` arrays (slots in in.ox), which nobody
+        // has filled, their hit records in hit[0 .. n), which nothing reads before bounce 1 writes it; the second pass shades them from there
+        const bool fuse = beams && fused;
+        auto launch_fused = [&](fused_fn_t fn, const int *count_ptr) {
+            const tirt_ctx::PvbSet &ps = c->pvb_set[c->pvb_cur];
+            t.begin(t.shade);
+            hipLaunchKernelGGL(fn, dim3(grid_shade), dim3(SH_BLOCK), 0, st, ShadeArgs{L.ps, in, out}, r.sv, r.bv, PvbView{ps.count.as<int>(), ps.cand.as<int2>(), ps.bound.as<float>()},
+                               c->cam, tm, P, f0, seed, (max_depth == 1) ? 1 : 0, count_ptr, S, append_ctr(0), fb_count, ctr, c->pvb_stat.as<unsigned long long>());
+            t.end(t.shade);
+            c->launches_shade++;
+        };
+        if (fuse) {
+            launch_fused(rgb_inst->fused, nullptr);
+            a.count_ptr = fb_count; a.no_ray_count = 1;          // (a.dx .. a.hit: the `in` arrays and hit already)
+        } else if (beams) {
             pvb_launch_cand(c, st, r.bv, in.dx, in.dy, in.dz, tm, P, S, L.ps.hit, fb_count, (int *)out.ox, out.dx, out.dy, out.dz, ctr);
             a.dx = out.dx; a.dy = out.dy; a.dz = out.dz; a.count_ptr = fb_count; a.hit = fb_hit; a.no_ray_count = 1;
         }
         t.begin(t.closest);                                      // (the traversal timers and counters see k_trace's launch, not the list pass)
         if (int rc = launch_trace(c, st, b == 0 ? KIND_CLOSEST : KIND_MIXED, a, flags, grid_full)) return rc;
         t.end(t.closest);
-        if (beams) pvb_launch_scatter(st, fb_count, (const int *)out.ox, fb_hit, L.ps.hit);
+        if (beams && !fuse) pvb_launch_scatter(st, fb_count, (const int *)out.ox, fb_hit, L.ps.hit);
         c->launches_trace_closest++;
         if (b == 0 && c->aov.p) { if (int rc = aov_launch(c, L, tm, P, F, f0)) return rc; }      // the camera rays' hits are complete: the feature buffers read them
 
-        t.begin(t.shade);
-        if (spec)
-            hipLaunchKernelGGL(shade_spec_fn, dim3(grid_shade), dim3(SH_BLOCK), 0, st, ShadeArgs{L.ps, in, out}, r.sv, *spec, tm, P, f0, seed, b,
-                               (b == max_depth - 1) ? 1 : 0, (b == 0) ? (const int *)nullptr : cnt_path(b), S,
-                               append_ctr(b), ctr, eye_v);
-        else
-        hipLaunchKernelGGL(shade_fn, dim3(grid_shade), dim3(SH_BLOCK), 0, st, ShadeArgs{L.ps, in, out}, r.sv, tm, P, f0, seed, b,
-                           (b == max_depth - 1) ? 1 : 0, (b == 0) ? (const int *)nullptr : cnt_path(b), S,
-                           append_ctr(b), ctr, eye_v);
-        t.end(t.shade);
-        c->launches_shade++;
+        if (fuse) launch_fused(rgb_inst->fused_rest, fb_count);      // the rays k_trace was asked about: their first shading step
+        else {
+            t.begin(t.shade);
+            if (spec)
+                hipLaunchKernelGGL(shade_spec_fn, dim3(grid_shade), dim3(SH_BLOCK), 0, st, ShadeArgs{L.ps, in, out}, r.sv, *spec, tm, P, f0, seed, b,
+                                   (b == max_depth - 1) ? 1 : 0, (b == 0) ? (const int *)nullptr : cnt_path(b), S,
+                                   append_ctr(b), ctr, eye_v);
+            else
+                hipLaunchKernelGGL(shade_fn, dim3(grid_shade), dim3(SH_BLOCK), 0, st, ShadeArgs{L.ps, in, out}, r.sv, tm, P, f0, seed, b,
+                                   (b == max_depth - 1) ? 1 : 0, (b == 0) ? (const int *)nullptr : cnt_path(b), S,
+                                   append_ctr(b), ctr, eye_v);
+            t.end(t.shade);
+            c->launches_shade++;
+        }
 
         if (b == max_depth - 1) {          // the last bounce's shadow rays have no closest-hit launch to ride on
             TraceArgs sa = base;
