@@ -23,6 +23,10 @@
 // A PT_RGB batch whose camera rays go through the pixels' candidate lists (tirt_pvb.hip) does k_generate, the list pass and k_shade of bounce 0 in one kernel,
 // k_pvb_cand_shade below (option "primary_fused"): the direction and the first hit record never reach HBM.
 //
+// The three persistent shading kernels -- k_shade, k_pvb_cand_shade, PT_Spec's k_shade_spec -- differ in their shading body and in what a path carries.  What
+// surrounds the body is one text for all three ("the path queues", below): the loop head (shade_loop), the hit-record load, the dense compaction with its one
+// packed atomic per block and round (queue_slots; the fused kernel's leftover list is an option of it), the store blocks and the `shaded` statistic.
+//
 // k_trace and its launchers (the walk, its two visiting rules, the tie rule) are in tirt_trace.hip; this file holds the shading kernels, the tables of
 // their instantiations and the scheduler that submits a batch's launches (pt_render), in that order.
 #include "tirt_pvb.h"
@@ -293,11 +297,8 @@ __global__ void k_generate(PathSoA ps, CameraView cam, TileMap tm, int P, int S,
     if (s == 0) atomicAdd(&ctr->paths, (unsigned long long)S);
 }
 
-// Block size of k_shade.  The survivors / shadow rays of a block are appended with ONE 64-bit atomic per
-// block and round (low word: next-bounce paths, high word: shadow rays): same-address device atomics
-// retire at ~11 ns each on MI355X, so one atomic per wave and queue (2 x 524k per 33.5 M paths)
-// bounded the kernel at ~6 ms; per 256-thread block it is 131k.  (512-thread blocks halve that again but
-// measured 4 % slower end to end: a 4-wave block needs 112 VGPRs per SIMD and fits next to the resident
+// Block size of the shading kernels: the unit that appends to the path queues with one atomic (queue_slots, below).  (512-thread blocks
+// halve the atomics again but measured 4 % slower end to end: a 4-wave block needs 112 VGPRs per SIMD and fits next to the resident
 // k_trace waves of another lane's batch, an 8-wave block does not.)
 #ifndef SH_BLOCK
 #define SH_BLOCK 256
@@ -335,6 +336,146 @@ typedef const __attribute__((address_space(4))) ShadeArgs *cold_shade_t;
 #define SH_COLD(ca) cold_shade_t ca = (cold_shade_t)__builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(ca))
 #define SH_LD(x) __builtin_nontemporal_load(&(x))
 #define SH_ST(x, v) __builtin_nontemporal_store((v), &(x))
+
+// ---- the path queues: what the three persistent shading kernels (k_shade, k_pvb_cand_shade, k_shade_spec) do around their shading body, written once ----
+// The head of the persistent loop: block b takes paths [it * total + b * SH_BLOCK, + SH_BLOCK) in round `it`; the path count comes from the counter the previous
+// bounce appended to, or is the batch's (bounce 0).  The kernel passes its own blockDim.x and gridDim.x: read in a device function, blockDim.x comes out as
+// the select between the full and the partial work-group's size (a 16-bit global load), which the compiler drops only where it sees the kernel's attributes.
+struct ShadeLoop {
+    int lane, wid, count, first, total, rounds;      // first: the thread's path in round 0
+    unsigned long long lt_mask;                      // the lanes of the wave below this one
+    TD int path(int it) const { return it * total + first; }
+};
+TD ShadeLoop shade_loop(const int *count_ptr, int count_fixed, unsigned block_dim, unsigned grid_dim)
+{
+    ShadeLoop lp;
+    lp.lane = threadIdx.x & 63; lp.wid = threadIdx.x >> 6;
+    lp.lt_mask = (lp.lane == 0) ? 0ull : (~0ull >> (64 - lp.lane));
+    lp.count = count_ptr ? *count_ptr : count_fixed;
+    lp.total = grid_dim * block_dim;
+    lp.rounds = (lp.count + lp.total - 1) / lp.total;
+    lp.first = blockIdx.x * block_dim + threadIdx.x;
+    return lp;
+}
+// k_trace's 16-byte hit record of path q: a stream, read once
+TD float4 load_hit_record(const float4 *hit, int q)
+{
+    typedef float f4nt__ __attribute__((ext_vector_type(4)));
+    const f4nt__ h = __builtin_nontemporal_load((const f4nt__ *)&hit[q]);
+    return make_float4(h.x, h.y, h.z, h.w);
+}
+// Dense compaction of a round: the block's survivors go to consecutive indices of the other PathSoA (`next`), its shadow rays to a dense list of their own
+// (`shadow`); with LEFT the rays the fused kernel leaves to k_trace take their places in a third list (`left`; its counter fb_count, its statistic stat[3])
+// between the same two barriers.  Two ballots, the wave's counts packed 16|16 into s_wcnt, and ONE 64-bit atomic per block and round (low word: next-bounce
+// paths, high word: shadow rays; none for a block that appends nothing): same-address device atomics retire at ~11 ns each on MI355X, so one atomic per wave
+// and queue (2 x 524k per 33.5 M paths) bounded the kernel at ~6 ms; per 256-thread block it is 131k (SH_BLOCK, above).  The LDS words are the calling kernel's
+// and double-buffered by the round's parity: a wave may enter round it + 1 while another still reads the bases of round it.
+struct QueueSlots { int next, shadow, left; };
+template <bool LEFT = false>
+TD QueueSlots queue_slots(const ShadeLoop &lp, int it, bool want_next, bool want_shadow, unsigned (&s_wcnt)[2][SH_BLOCK / 64], unsigned long long (&s_base)[2],
+                          unsigned long long *append_ctr, bool left = false, unsigned (*s_fcnt)[SH_BLOCK / 64] = nullptr, int *s_fbase = nullptr,
+                          int *fb_count = nullptr, unsigned long long *stat = nullptr)
+{
+    const int par = it & 1;
+    const unsigned long long nmask = __ballot(want_next), smask = __ballot(want_shadow), fmask = LEFT ? __ballot(left) : 0ull;
+    if (lp.lane == 0) { s_wcnt[par][lp.wid] = (unsigned)__popcll(nmask) | ((unsigned)__popcll(smask) << 16); if (LEFT) s_fcnt[par][lp.wid] = (unsigned)__popcll(fmask); }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned tn = 0, tsd = 0, tf = 0;
+#pragma unroll
+        for (int w = 0; w < SH_BLOCK / 64; w++) { tn += s_wcnt[par][w] & 0xffffu; tsd += s_wcnt[par][w] >> 16; if (LEFT) tf += s_fcnt[par][w]; }
+        s_base[par] = (tn | tsd) ? atomicAdd(append_ctr, (unsigned long long)tn | ((unsigned long long)tsd << 32)) : 0ull;
+        if (LEFT) {
+            s_fbase[par] = tf ? atomicAdd(fb_count, (int)tf) : 0;
+            if (stat && tf) atomicAdd(&stat[3], (unsigned long long)tf);
+        }
+    }
+    __syncthreads();
+    unsigned pn = 0, psd = 0, pf = 0;
+#pragma unroll
+    for (int w = 0; w < SH_BLOCK / 64; w++) if (w < lp.wid) { pn += s_wcnt[par][w] & 0xffffu; psd += s_wcnt[par][w] >> 16; if (LEFT) pf += s_fcnt[par][w]; }
+    const unsigned long long bb = s_base[par];
+    QueueSlots at;
+    at.next = (int)(unsigned)(bb & 0xffffffffull) + (int)pn + __popcll(nmask & lp.lt_mask);
+    at.shadow = (int)(unsigned)(bb >> 32) + (int)psd + __popcll(smask & lp.lt_mask);
+    at.left = LEFT ? s_fbase[par] + (int)pf + __popcll(fmask & lp.lt_mask) : 0;
+    return at;
+}
+// PT_RGB: a survivor's 11 words into the other PathSoA (the slot word carries perfect_spec in bit 31), a shadow ray's 12 into its list, a camera path's first
+// radiance into fr / fg / fb[slot] (slot == q but for the fused kernel's leftovers: coalesced).  Each reads its array pointers from the kernel-argument segment in
+// one batch of scalar loads (SH_COLD, above); the empty asm keeps the batch together.
+TD void store_survivor(int at, int slot, const ShadeStep &s)
+{
+    SH_COLD(ca);
+    float *const o_ox = ca->out.ox, *const o_oy = ca->out.oy, *const o_oz = ca->out.oz, *const o_dx = ca->out.dx, *const o_dy = ca->out.dy, *const o_dz = ca->out.dz;
+    float *const o_tr = ca->out.tr, *const o_tg = ca->out.tg, *const o_tb = ca->out.tb;
+    float *const o_pdf = ca->out.brdf_pdf; int *const o_slot = ca->out.slot;
+    asm volatile("" :: "s"(o_ox), "s"(o_oy), "s"(o_oz), "s"(o_dx), "s"(o_dy), "s"(o_dz), "s"(o_tr), "s"(o_tg), "s"(o_tb), "s"(o_pdf), "s"(o_slot));
+    SH_ST(o_ox[at], s.next_o.x); SH_ST(o_oy[at], s.next_o.y); SH_ST(o_oz[at], s.next_o.z);
+    SH_ST(o_dx[at], s.next_d.x); SH_ST(o_dy[at], s.next_d.y); SH_ST(o_dz[at], s.next_d.z);
+    SH_ST(o_tr[at], s.next_thr.x); SH_ST(o_tg[at], s.next_thr.y); SH_ST(o_tb[at], s.next_thr.z);
+    SH_ST(o_pdf[at], s.next_pdf); SH_ST(o_slot[at], (int)((uint32_t)slot | ((uint32_t)s.next_spec << 31)));
+}
+TD void store_shadow_ray(int at, int slot, const ShadeStep &s)
+{
+    SH_COLD(ca);
+    float *const s_ox = ca->ps.sox, *const s_oy = ca->ps.soy, *const s_oz = ca->ps.soz, *const s_dx = ca->ps.sdx, *const s_dy = ca->ps.sdy, *const s_dz = ca->ps.sdz;
+    float *const s_cr = ca->ps.scr, *const s_cg = ca->ps.scg, *const s_cb = ca->ps.scb, *const s_dist = ca->ps.sdist;
+    int *const s_prim = ca->ps.sprim, *const s_dst = ca->ps.sdst;
+    asm volatile("" :: "s"(s_ox), "s"(s_oy), "s"(s_oz), "s"(s_dx), "s"(s_dy), "s"(s_dz), "s"(s_cr), "s"(s_cg), "s"(s_cb), "s"(s_dist), "s"(s_prim), "s"(s_dst));
+    SH_ST(s_ox[at], s.sh_o.x); SH_ST(s_oy[at], s.sh_o.y); SH_ST(s_oz[at], s.sh_o.z);
+    SH_ST(s_dx[at], s.sh_d.x); SH_ST(s_dy[at], s.sh_d.y); SH_ST(s_dz[at], s.sh_d.z);
+    SH_ST(s_cr[at], s.sh_c.x); SH_ST(s_cg[at], s.sh_c.y); SH_ST(s_cb[at], s.sh_c.z);
+    SH_ST(s_prim[at], s.sh_expect); SH_ST(s_dist[at], s.sh_dist);
+    SH_ST(s_dst[at], ~slot);               // always the per-path accumulator (k_trace's dst < 0 case), whether the path goes on or not
+}
+TD void store_first_radiance(int slot, const v3 radiance)
+{
+    SH_COLD(ca);
+    float *const f_r = ca->ps.fr, *const f_g = ca->ps.fg, *const f_b = ca->ps.fb;
+    asm volatile("" :: "s"(f_r), "s"(f_g), "s"(f_b));
+    SH_ST(f_r[slot], radiance.x); SH_ST(f_g[slot], radiance.y); SH_ST(f_b[slot], radiance.z);
+}
+// PT_Spec: a survivor carries four-channel throughput and radiance (15 words; tw in brdf_pdf's array, rw in flags'), a shadow ray a four-channel contribution
+// and, as destination, its path's place in the other PathSoA if the path goes on (k_trace's dst >= 0 case) or ~slot; plain stores
+TD void store_survivor_spec(int at, int slot, const v3 next_o, const v3 next_d, const f4s &next_thr, const f4s &radiance)
+{
+    SH_COLD(ca);
+    float *const o_ox = ca->out.ox, *const o_oy = ca->out.oy, *const o_oz = ca->out.oz, *const o_dx = ca->out.dx, *const o_dy = ca->out.dy, *const o_dz = ca->out.dz;
+    float *const o_tr = ca->out.tr, *const o_tg = ca->out.tg, *const o_tb = ca->out.tb, *const o_rr = ca->out.rr, *const o_rg = ca->out.rg, *const o_rb = ca->out.rb;
+    float *const o_tw = ca->out.brdf_pdf, *const o_rw = (float *)ca->out.flags; int *const o_slot = ca->out.slot;
+    asm volatile("" :: "s"(o_ox), "s"(o_oy), "s"(o_oz), "s"(o_dx), "s"(o_dy), "s"(o_dz), "s"(o_tr), "s"(o_tg), "s"(o_tb), "s"(o_rr), "s"(o_rg), "s"(o_rb),
+                 "s"(o_tw), "s"(o_rw), "s"(o_slot));
+    o_ox[at] = next_o.x; o_oy[at] = next_o.y; o_oz[at] = next_o.z;
+    o_dx[at] = next_d.x; o_dy[at] = next_d.y; o_dz[at] = next_d.z;
+    o_tr[at] = next_thr.v[0]; o_tg[at] = next_thr.v[1]; o_tb[at] = next_thr.v[2]; o_tw[at] = next_thr.v[3];
+    o_rr[at] = radiance.v[0]; o_rg[at] = radiance.v[1]; o_rb[at] = radiance.v[2]; o_rw[at] = radiance.v[3];
+    o_slot[at] = slot;
+}
+TD void store_shadow_ray_spec(int at, int dst, const v3 sh_o, const v3 sh_d, const f4s &sh_c, int sh_expect, float sh_dist)
+{
+    SH_COLD(ca);
+    float *const s_ox = ca->ps.sox, *const s_oy = ca->ps.soy, *const s_oz = ca->ps.soz, *const s_dx = ca->ps.sdx, *const s_dy = ca->ps.sdy, *const s_dz = ca->ps.sdz;
+    float *const s_cr = ca->ps.scr, *const s_cg = ca->ps.scg, *const s_cb = ca->ps.scb, *const s_cw = ca->ps.scw, *const s_dist = ca->ps.sdist;
+    int *const s_prim = ca->ps.sprim, *const s_dst = ca->ps.sdst;
+    asm volatile("" :: "s"(s_ox), "s"(s_oy), "s"(s_oz), "s"(s_dx), "s"(s_dy), "s"(s_dz), "s"(s_cr), "s"(s_cg), "s"(s_cb), "s"(s_cw), "s"(s_dist), "s"(s_prim), "s"(s_dst));
+    s_ox[at] = sh_o.x; s_oy[at] = sh_o.y; s_oz[at] = sh_o.z;
+    s_dx[at] = sh_d.x; s_dy[at] = sh_d.y; s_dz[at] = sh_d.z;
+    s_cr[at] = sh_c.v[0]; s_cg[at] = sh_c.v[1]; s_cb[at] = sh_c.v[2]; s_cw[at] = sh_c.v[3];
+    s_prim[at] = sh_expect; s_dist[at] = sh_dist;
+    s_dst[at] = dst;
+}
+// The `shaded` statistic: wave sum, LDS atomic, one global atomic per block -- not per wave, for the reason given at queue_slots
+TD void count_shaded(unsigned long long n_shaded, unsigned long long &s_shaded, DevCounters *ctr)
+{
+    if (threadIdx.x == 0) s_shaded = 0ull;
+    __syncthreads();
+    n_shaded = wave_sum(n_shaded);
+    if ((threadIdx.x & 63) == 0 && n_shaded) atomicAdd(&s_shaded, n_shaded);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_shaded) atomicAdd(&ctr->shaded, s_shaded);
+}
+
 template <unsigned FEAT, int MIN_WAVES, bool LIST = false>
 __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_shade(ShadeArgs paths_in_kernarg_segment, SceneView sc, TileMap tm, int P,
                                                    uint32_t frame_begin, uint32_t seed, int bounce, int last_bounce,
@@ -343,20 +484,15 @@ __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_shade(ShadeArgs paths_i
 {
     __shared__ unsigned s_wcnt[2][SH_BLOCK / 64];
     __shared__ unsigned long long s_base[2];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    const int count = count_ptr ? *count_ptr : count_fixed;
-    const int total = gridDim.x * blockDim.x;
-    const int rounds = (count + total - 1) / total;
+    const ShadeLoop lp = shade_loop(count_ptr, count_fixed, blockDim.x, gridDim.x);
     unsigned long long n_shaded = 0;
-    for (int it = 0; it < rounds; it++) {
-        const int q = it * total + blockIdx.x * blockDim.x + threadIdx.x;
-        bool live = q < count, want_next = false, want_shadow = false, adds = false;
+    for (int it = 0; it < lp.rounds; it++) {
+        const int q = lp.path(it);
+        bool live = q < lp.count, adds = false;
         int slot = 0;
         // `radiance`: at bounce 0 the path's radiance after this step (0 + the step's term), at a later bounce the term alone -- the radiance so far is fr / fg / fb[slot]
-        v3 radiance = V(0.0f, 0.0f, 0.0f), next_o = radiance, next_d = radiance, next_thr = radiance;
-        v3 sh_o = radiance, sh_d = radiance, sh_c = radiance;
-        float next_pdf = 0.0f, sh_dist = 0.0f; int next_spec = 0, sh_expect = -2;
+        v3 radiance = V(0.0f, 0.0f, 0.0f);
+        ShadeStep ss;
         const bool first = bounce == 0;              // camera rays: constant state, see k_generate
         if (live) {
             SH_COLD(ca);
@@ -370,17 +506,12 @@ __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_shade(ShadeArgs paths_i
             slot = (int)(slot_word & 0x7fffffffu);
             const v3 origin = first ? eye : V(SH_LD(c_ox[q]), SH_LD(c_oy[q]), SH_LD(c_oz[q]));
             const v3 direction = V(SH_LD(c_dx[q]), SH_LD(c_dy[q]), SH_LD(c_dz[q]));
-            typedef float f4nt__ __attribute__((ext_vector_type(4)));
-            const f4nt__ hnt__ = __builtin_nontemporal_load((const f4nt__ *)&c_hit[q]);
-            const float4 hrec = make_float4(hnt__.x, hnt__.y, hnt__.z, hnt__.w);
+            const float4 hrec = load_hit_record(c_hit, q);
             v3 throughout = first ? V(1.0f, 1.0f, 1.0f) : V(SH_LD(c_tr[q]), SH_LD(c_tg[q]), SH_LD(c_tb[q]));
             float brdf_pdf = first ? 1.0f : SH_LD(c_pdf[q]);
             int perfect_spec = (int)(slot_word >> 31);
-            ShadeStep ss;
             shade_path<FEAT, LIST>(sc, tm, P, frame_begin, seed, bounce, last_bounce, slot, origin, direction, hrec, throughout, brdf_pdf, perfect_spec, ss);
-            want_next = ss.want_next; want_shadow = ss.want_shadow; if (ss.shaded) n_shaded++;
-            next_o = ss.next_o; next_d = ss.next_d; next_thr = ss.next_thr; next_pdf = ss.next_pdf; next_spec = ss.next_spec;
-            sh_o = ss.sh_o; sh_d = ss.sh_d; sh_c = ss.sh_c; sh_expect = ss.sh_expect; sh_dist = ss.sh_dist;
+            if (ss.shaded) n_shaded++;
             if (first) {
                 if (ss.adds) radiance = radiance + ss.add;       // 0 + term: the add stays, 0 + (-0) is +0
             } else {
@@ -392,74 +523,33 @@ __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_shade(ShadeArgs paths_i
                 adds = ss.adds && !nothing;
             }
         }
-        // dense compaction: survivors go to consecutive indices of the other PathSoA, shadow rays get their
-        // own dense list with the path whose radiance (fr / fg / fb[slot]) their contribution must be added to
-        const int par = it & 1;
-        const unsigned long long nmask = __ballot(want_next), smask = __ballot(want_shadow);
-        if (lane == 0) s_wcnt[par][wid] = (unsigned)__popcll(nmask) | ((unsigned)__popcll(smask) << 16);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned tn = 0, tsd = 0;
-#pragma unroll
-            for (int w = 0; w < SH_BLOCK / 64; w++) { tn += s_wcnt[par][w] & 0xffffu; tsd += s_wcnt[par][w] >> 16; }
-            s_base[par] = (tn | tsd) ? atomicAdd(append_ctr, (unsigned long long)tn | ((unsigned long long)tsd << 32)) : 0ull;
-        }
-        __syncthreads();
-        unsigned pn = 0, psd = 0;
-#pragma unroll
-        for (int w = 0; w < SH_BLOCK / 64; w++) if (w < wid) { pn += s_wcnt[par][w] & 0xffffu; psd += s_wcnt[par][w] >> 16; }
-        const unsigned long long bb = s_base[par];
-        const int qn = (int)(unsigned)(bb & 0xffffffffull) + (int)pn + __popcll(nmask & lt_mask);
-        const int qs = (int)(unsigned)(bb >> 32) + (int)psd + __popcll(smask & lt_mask);
-        if (want_next) {
-            SH_COLD(ca);
-            float *const o_ox = ca->out.ox, *const o_oy = ca->out.oy, *const o_oz = ca->out.oz, *const o_dx = ca->out.dx, *const o_dy = ca->out.dy, *const o_dz = ca->out.dz;
-            float *const o_tr = ca->out.tr, *const o_tg = ca->out.tg, *const o_tb = ca->out.tb;
-            float *const o_pdf = ca->out.brdf_pdf; int *const o_slot = ca->out.slot;
-            asm volatile("" :: "s"(o_ox), "s"(o_oy), "s"(o_oz), "s"(o_dx), "s"(o_dy), "s"(o_dz), "s"(o_tr), "s"(o_tg), "s"(o_tb), "s"(o_pdf), "s"(o_slot));
-            SH_ST(o_ox[qn], next_o.x); SH_ST(o_oy[qn], next_o.y); SH_ST(o_oz[qn], next_o.z);
-            SH_ST(o_dx[qn], next_d.x); SH_ST(o_dy[qn], next_d.y); SH_ST(o_dz[qn], next_d.z);
-            SH_ST(o_tr[qn], next_thr.x); SH_ST(o_tg[qn], next_thr.y); SH_ST(o_tb[qn], next_thr.z);
-            SH_ST(o_pdf[qn], next_pdf); SH_ST(o_slot[qn], (int)((uint32_t)slot | ((uint32_t)next_spec << 31)));
-        }
-        // the path's radiance lives in fr / fg / fb[slot] from bounce 0 on (k_trace's shadow write-back adds into it there: sdst below): every camera path stores
-        // its first value (slot == q: coalesced), a later bounce adds its term, if it has one, where the path's slot is; a path that ends has nothing left to store
+        // survivors go to consecutive indices of the other PathSoA, shadow rays get their own dense list with the path whose radiance (fr / fg / fb[slot]) their
+        // contribution must be added to
+        const QueueSlots at = queue_slots(lp, it, ss.want_next, ss.want_shadow, s_wcnt, s_base, append_ctr);
+        if (ss.want_next) store_survivor(at.next, slot, ss);
+        // the path's radiance lives in fr / fg / fb[slot] from bounce 0 on (k_trace's shadow write-back adds into it there: store_shadow_ray's ~slot): every camera
+        // path stores its first value, a later bounce adds its term, if it has one, where the path's slot is; a path that ends has nothing left to store
         if (first ? live : adds) {
-            SH_COLD(ca);
-            float *const f_r = ca->ps.fr, *const f_g = ca->ps.fg, *const f_b = ca->ps.fb;
-            asm volatile("" :: "s"(f_r), "s"(f_g), "s"(f_b));
-            if (first) { SH_ST(f_r[slot], radiance.x); SH_ST(f_g[slot], radiance.y); SH_ST(f_b[slot], radiance.z); }
-            else { f_r[slot] = f_r[slot] + radiance.x; f_g[slot] = f_g[slot] + radiance.y; f_b[slot] = f_b[slot] + radiance.z; }
+            if (first) store_first_radiance(slot, radiance);
+            else {
+                SH_COLD(ca);
+                float *const f_r = ca->ps.fr, *const f_g = ca->ps.fg, *const f_b = ca->ps.fb;
+                asm volatile("" :: "s"(f_r), "s"(f_g), "s"(f_b));
+                f_r[slot] = f_r[slot] + radiance.x; f_g[slot] = f_g[slot] + radiance.y; f_b[slot] = f_b[slot] + radiance.z;
+            }
         }
-        if (want_shadow) {
-            SH_COLD(ca);
-            float *const s_ox = ca->ps.sox, *const s_oy = ca->ps.soy, *const s_oz = ca->ps.soz, *const s_dx = ca->ps.sdx, *const s_dy = ca->ps.sdy, *const s_dz = ca->ps.sdz;
-            float *const s_cr = ca->ps.scr, *const s_cg = ca->ps.scg, *const s_cb = ca->ps.scb, *const s_dist = ca->ps.sdist;
-            int *const s_prim = ca->ps.sprim, *const s_dst = ca->ps.sdst;
-            asm volatile("" :: "s"(s_ox), "s"(s_oy), "s"(s_oz), "s"(s_dx), "s"(s_dy), "s"(s_dz), "s"(s_cr), "s"(s_cg), "s"(s_cb), "s"(s_dist), "s"(s_prim), "s"(s_dst));
-            SH_ST(s_ox[qs], sh_o.x); SH_ST(s_oy[qs], sh_o.y); SH_ST(s_oz[qs], sh_o.z);
-            SH_ST(s_dx[qs], sh_d.x); SH_ST(s_dy[qs], sh_d.y); SH_ST(s_dz[qs], sh_d.z);
-            SH_ST(s_cr[qs], sh_c.x); SH_ST(s_cg[qs], sh_c.y); SH_ST(s_cb[qs], sh_c.z);
-            SH_ST(s_prim[qs], sh_expect); SH_ST(s_dist[qs], sh_dist);
-            SH_ST(s_dst[qs], ~slot);           // always the per-path accumulator (k_trace's dst < 0 case), whether the path goes on or not
-        }
+        if (ss.want_shadow) store_shadow_ray(at.shadow, slot, ss);
     }
-    // statistics: one global atomic per block (through LDS), not per wave -- same-address atomics retire at ~11 ns
     __shared__ unsigned long long s_shaded;
-    if (threadIdx.x == 0) s_shaded = 0ull;
-    __syncthreads();
-    n_shaded = wave_sum(n_shaded);
-    if ((threadIdx.x & 63) == 0 && n_shaded) atomicAdd(&s_shaded, n_shaded);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_shaded) atomicAdd(&ctr->shaded, s_shaded);
+    count_shaded(n_shaded, s_shaded, ctr);
 }
 
 // The first step of a camera path in ONE kernel (option "primary_fused"): what k_generate, k_pvb_cand and k_shade of bounce 0 do one after the other, without the
-// direction (12 B written, 24 B read per path) and the hit record (16 B written, 16 B read) going through HBM in between.  k_shade's shape -- blocks, persistent
-// rounds, SH_COLD, one packed atomic per block and round -- around the same three device functions: camera_path_direction, pvb_walk_list (tirt_pvb.h), shade_path.
+// direction (12 B written, 24 B read per path) and the hit record (16 B written, 16 B read) going through HBM in between.  k_shade's loop, literally -- shade_loop,
+// queue_slots, store_survivor / store_first_radiance / store_shadow_ray, count_shaded -- around camera_path_direction, pvb_walk_list (tirt_pvb.h) and shade_path.
 //   WALK:   path q of the batch: its direction, its pixel's list; a ray the list resolves is shaded on the spot (k_shade's `first` state: origin = eye, throughput 1,
 //           pdf 1, perfect_spec set, slot == q) and stores its first radiance; a ray it does not resolve is appended to the leftover list -- its slot in in.ox, its
-//           direction in in.dx / dy / dz: the arrays k_generate would have filled -- with a second atomic of the block between the same two barriers (as k_pvb_cand).
+//           direction in in.dx / dy / dz: the arrays k_generate would have filled -- with a second atomic of the block between queue_slots' two barriers (its LEFT option).
 //   !WALK:  after k_trace has written the leftovers' hit records to ps.hit[0 .. n): entry q of that list, shaded with the same state and the slot from the list,
 //           its survivors and shadow rays appended behind the others through the same counter of bounce 0.  Nothing is scattered.
 // The device counters are the three kernels': paths, rays_closest and stat[3], stat[4] (WALK), shaded (both).
@@ -472,17 +562,13 @@ __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_pvb_cand_shade(ShadeArg
     __shared__ unsigned s_wcnt[2][SH_BLOCK / 64], s_fcnt[2][SH_BLOCK / 64];
     __shared__ unsigned long long s_base[2];
     __shared__ int s_fbase[2];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    const int count = count_ptr ? *count_ptr : count_fixed;
-    const int total = gridDim.x * blockDim.x;
-    const int rounds = (count + total - 1) / total;
+    const ShadeLoop lp = shade_loop(count_ptr, count_fixed, blockDim.x, gridDim.x);
     const v3 eye = V(cam.eye[0], cam.eye[1], cam.eye[2]);
     unsigned long long n_shaded = 0;
-    for (int it = 0; it < rounds; it++) {
-        const int q = it * total + blockIdx.x * blockDim.x + threadIdx.x;
-        const bool live = q < count;
-        bool shade = false, left = false, want_next = false, want_shadow = false;
+    for (int it = 0; it < lp.rounds; it++) {
+        const int q = lp.path(it);
+        const bool live = q < lp.count;
+        bool shade = false, left = false;
         int slot = 0;
         v3 direction = V(0.0f, 0.0f, 1.0f);
         float4 hrec = make_float4(INF_VALUE, 0.0f, 0.0f, __int_as_float(-1));
@@ -504,92 +590,34 @@ __global__ __launch_bounds__(SH_BLOCK, MIN_WAVES) void k_pvb_cand_shade(ShadeArg
             asm volatile("" :: "s"(c_slot), "s"(c_hit), "s"(c_dx), "s"(c_dy), "s"(c_dz));
             slot = SH_LD(c_slot[q]);
             direction = V(SH_LD(c_dx[q]), SH_LD(c_dy[q]), SH_LD(c_dz[q]));
-            typedef float f4nt__ __attribute__((ext_vector_type(4)));
-            const f4nt__ hnt__ = __builtin_nontemporal_load((const f4nt__ *)&c_hit[q]);
-            hrec = make_float4(hnt__.x, hnt__.y, hnt__.z, hnt__.w);
+            hrec = load_hit_record(c_hit, q);
             shade = true;
         }
-        v3 radiance = V(0.0f, 0.0f, 0.0f), next_o = radiance, next_d = radiance, next_thr = radiance;
-        v3 sh_o = radiance, sh_d = radiance, sh_c = radiance;
-        float next_pdf = 0.0f, sh_dist = 0.0f; int next_spec = 0, sh_expect = -2;
+        v3 radiance = V(0.0f, 0.0f, 0.0f);
+        ShadeStep ss;
         if (shade) {
-            ShadeStep ss;
             shade_path<FEAT, false>(sc, tm, P, frame_begin, seed, 0, last_bounce, slot, eye, direction, hrec, V(1.0f, 1.0f, 1.0f), 1.0f, 1, ss);
-            want_next = ss.want_next; want_shadow = ss.want_shadow; if (ss.shaded) n_shaded++;
-            next_o = ss.next_o; next_d = ss.next_d; next_thr = ss.next_thr; next_pdf = ss.next_pdf; next_spec = ss.next_spec;
-            sh_o = ss.sh_o; sh_d = ss.sh_d; sh_c = ss.sh_c; sh_expect = ss.sh_expect; sh_dist = ss.sh_dist;
+            if (ss.shaded) n_shaded++;
             if (ss.adds) radiance = radiance + ss.add;       // 0 + term: the add stays, 0 + (-0) is +0 (k_shade at bounce 0)
         }
-        // dense compaction, as in k_shade; the leftover rays of the block take their places in their list between the same barriers
-        const int par = it & 1;
-        const unsigned long long nmask = __ballot(want_next), smask = __ballot(want_shadow), fmask = WALK ? __ballot(left) : 0ull;
-        if (lane == 0) { s_wcnt[par][wid] = (unsigned)__popcll(nmask) | ((unsigned)__popcll(smask) << 16); if (WALK) s_fcnt[par][wid] = (unsigned)__popcll(fmask); }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned tn = 0, tsd = 0, tf = 0;
-#pragma unroll
-            for (int w = 0; w < SH_BLOCK / 64; w++) { tn += s_wcnt[par][w] & 0xffffu; tsd += s_wcnt[par][w] >> 16; if (WALK) tf += s_fcnt[par][w]; }
-            s_base[par] = (tn | tsd) ? atomicAdd(append_ctr, (unsigned long long)tn | ((unsigned long long)tsd << 32)) : 0ull;
-            if (WALK) {
-                s_fbase[par] = tf ? atomicAdd(fb_count, (int)tf) : 0;
-                if (stat && tf) atomicAdd(&stat[3], (unsigned long long)tf);
-            }
-        }
-        __syncthreads();
-        unsigned pn = 0, psd = 0, pf = 0;
-#pragma unroll
-        for (int w = 0; w < SH_BLOCK / 64; w++) if (w < wid) { pn += s_wcnt[par][w] & 0xffffu; psd += s_wcnt[par][w] >> 16; if (WALK) pf += s_fcnt[par][w]; }
-        const unsigned long long bb = s_base[par];
-        const int qn = (int)(unsigned)(bb & 0xffffffffull) + (int)pn + __popcll(nmask & lt_mask);
-        const int qs = (int)(unsigned)(bb >> 32) + (int)psd + __popcll(smask & lt_mask);
+        // the leftover rays of the block take their places in their list between the barriers of the other two
+        const QueueSlots at = queue_slots<WALK>(lp, it, ss.want_next, ss.want_shadow, s_wcnt, s_base, append_ctr, left, s_fcnt, s_fbase, fb_count, stat);
         if (WALK && left) {
             SH_COLD(ca);
             int *const l_slot = (int *)ca->in.ox; float *const l_dx = ca->in.dx, *const l_dy = ca->in.dy, *const l_dz = ca->in.dz;
             asm volatile("" :: "s"(l_slot), "s"(l_dx), "s"(l_dy), "s"(l_dz));
-            const int at = s_fbase[par] + (int)pf + __popcll(fmask & lt_mask);
-            l_slot[at] = slot; l_dx[at] = direction.x; l_dy[at] = direction.y; l_dz[at] = direction.z;
+            l_slot[at.left] = slot; l_dx[at.left] = direction.x; l_dy[at.left] = direction.y; l_dz[at.left] = direction.z;
         }
-        if (want_next) {
-            SH_COLD(ca);
-            float *const o_ox = ca->out.ox, *const o_oy = ca->out.oy, *const o_oz = ca->out.oz, *const o_dx = ca->out.dx, *const o_dy = ca->out.dy, *const o_dz = ca->out.dz;
-            float *const o_tr = ca->out.tr, *const o_tg = ca->out.tg, *const o_tb = ca->out.tb;
-            float *const o_pdf = ca->out.brdf_pdf; int *const o_slot = ca->out.slot;
-            asm volatile("" :: "s"(o_ox), "s"(o_oy), "s"(o_oz), "s"(o_dx), "s"(o_dy), "s"(o_dz), "s"(o_tr), "s"(o_tg), "s"(o_tb), "s"(o_pdf), "s"(o_slot));
-            SH_ST(o_ox[qn], next_o.x); SH_ST(o_oy[qn], next_o.y); SH_ST(o_oz[qn], next_o.z);
-            SH_ST(o_dx[qn], next_d.x); SH_ST(o_dy[qn], next_d.y); SH_ST(o_dz[qn], next_d.z);
-            SH_ST(o_tr[qn], next_thr.x); SH_ST(o_tg[qn], next_thr.y); SH_ST(o_tb[qn], next_thr.z);
-            SH_ST(o_pdf[qn], next_pdf); SH_ST(o_slot[qn], (int)((uint32_t)slot | ((uint32_t)next_spec << 31)));
-        }
+        if (ss.want_next) store_survivor(at.next, slot, ss);
         // the path's first radiance (k_shade at bounce 0; WALK: slot == q, coalesced).  A leftover ray stores none yet: its !WALK pass does
-        if (shade) {
-            SH_COLD(ca);
-            float *const f_r = ca->ps.fr, *const f_g = ca->ps.fg, *const f_b = ca->ps.fb;
-            asm volatile("" :: "s"(f_r), "s"(f_g), "s"(f_b));
-            SH_ST(f_r[slot], radiance.x); SH_ST(f_g[slot], radiance.y); SH_ST(f_b[slot], radiance.z);
-        }
-        if (want_shadow) {
-            SH_COLD(ca);
-            float *const s_ox = ca->ps.sox, *const s_oy = ca->ps.soy, *const s_oz = ca->ps.soz, *const s_dx = ca->ps.sdx, *const s_dy = ca->ps.sdy, *const s_dz = ca->ps.sdz;
-            float *const s_cr = ca->ps.scr, *const s_cg = ca->ps.scg, *const s_cb = ca->ps.scb, *const s_dist = ca->ps.sdist;
-            int *const s_prim = ca->ps.sprim, *const s_dst = ca->ps.sdst;
-            asm volatile("" :: "s"(s_ox), "s"(s_oy), "s"(s_oz), "s"(s_dx), "s"(s_dy), "s"(s_dz), "s"(s_cr), "s"(s_cg), "s"(s_cb), "s"(s_dist), "s"(s_prim), "s"(s_dst));
-            SH_ST(s_ox[qs], sh_o.x); SH_ST(s_oy[qs], sh_o.y); SH_ST(s_oz[qs], sh_o.z);
-            SH_ST(s_dx[qs], sh_d.x); SH_ST(s_dy[qs], sh_d.y); SH_ST(s_dz[qs], sh_d.z);
-            SH_ST(s_cr[qs], sh_c.x); SH_ST(s_cg[qs], sh_c.y); SH_ST(s_cb[qs], sh_c.z);
-            SH_ST(s_prim[qs], sh_expect); SH_ST(s_dist[qs], sh_dist);
-            SH_ST(s_dst[qs], ~slot);
-        }
+        if (shade) store_first_radiance(slot, radiance);
+        if (ss.want_shadow) store_shadow_ray(at.shadow, slot, ss);
     }
     __shared__ unsigned long long s_shaded;
-    if (threadIdx.x == 0) s_shaded = 0ull;
-    __syncthreads();
-    n_shaded = wave_sum(n_shaded);
-    if ((threadIdx.x & 63) == 0 && n_shaded) atomicAdd(&s_shaded, n_shaded);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_shaded) atomicAdd(&ctr->shaded, s_shaded);
+    count_shaded(n_shaded, s_shaded, ctr);
     if (WALK && blockIdx.x == 0 && threadIdx.x == 0) {          // what k_generate and k_pvb_cand count
-        atomicAdd(&ctr->paths, (unsigned long long)count); atomicAdd(&ctr->rays_closest, (unsigned long long)count);
-        if (stat) atomicAdd(&stat[4], (unsigned long long)count);
+        atomicAdd(&ctr->paths, (unsigned long long)lp.count); atomicAdd(&ctr->rays_closest, (unsigned long long)lp.count);
+        if (stat) atomicAdd(&stat[4], (unsigned long long)lp.count);
     }
 }
 
@@ -629,15 +657,11 @@ __global__ __launch_bounds__(SH_BLOCK, 4) void k_shade_spec(ShadeArgs paths_in_k
 {
     __shared__ unsigned s_wcnt[2][SH_BLOCK / 64];
     __shared__ unsigned long long s_base[2];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    const int count = count_ptr ? *count_ptr : count_fixed;
-    const int total = gridDim.x * blockDim.x;
-    const int rounds = (count + total - 1) / total;
+    const ShadeLoop lp = shade_loop(count_ptr, count_fixed, blockDim.x, gridDim.x);
     unsigned long long n_shaded = 0;
-    for (int it = 0; it < rounds; it++) {
-        const int q = it * total + blockIdx.x * blockDim.x + threadIdx.x;
-        bool live = q < count, want_next = false, want_shadow = false;
+    for (int it = 0; it < lp.rounds; it++) {
+        const int q = lp.path(it);
+        bool live = q < lp.count, want_next = false, want_shadow = false;
         int slot = 0;
         f4s radiance = f4_set(0.0f), next_thr = radiance, sh_c = radiance;
         v3 next_o = V(0.0f, 0.0f, 0.0f), next_d = next_o, sh_o = next_o, sh_d = next_o;
@@ -659,9 +683,7 @@ __global__ __launch_bounds__(SH_BLOCK, 4) void k_shade_spec(ShadeArgs paths_in_k
             const float Lambda = HERO_LAMBDA_MIN + HERO_LAMBDA_STEP * tm_rand(seed, pixel, frame, TM_DIM_SPEC_LAMBDA);     // PT_Spec.py:191
             const v3 origin = first ? eye : V(c_ox[q], c_oy[q], c_oz[q]);
             const v3 direction = V(c_dx[q], c_dy[q], c_dz[q]);
-            typedef float f4nt__ __attribute__((ext_vector_type(4)));
-            const f4nt__ hnt__ = __builtin_nontemporal_load((const f4nt__ *)&c_hit[q]);
-            const float4 hrec = make_float4(hnt__.x, hnt__.y, hnt__.z, hnt__.w);
+            const float4 hrec = load_hit_record(c_hit, q);
             const float t = hrec.x;
             f4s throughout = f4_set(1.0f);
             if (!first) {
@@ -748,61 +770,19 @@ __global__ __launch_bounds__(SH_BLOCK, 4) void k_shade_spec(ShadeArgs paths_in_k
                 radiance = radiance + ((throughout * ibl) * light_rad);
             }
         }
-        const int par = it & 1;
-        const unsigned long long nmask = __ballot(want_next), smask = __ballot(want_shadow);
-        if (lane == 0) s_wcnt[par][wid] = (unsigned)__popcll(nmask) | ((unsigned)__popcll(smask) << 16);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned tn = 0, tsd = 0;
-#pragma unroll
-            for (int w = 0; w < SH_BLOCK / 64; w++) { tn += s_wcnt[par][w] & 0xffffu; tsd += s_wcnt[par][w] >> 16; }
-            s_base[par] = (tn | tsd) ? atomicAdd(append_ctr, (unsigned long long)tn | ((unsigned long long)tsd << 32)) : 0ull;
-        }
-        __syncthreads();
-        unsigned pn = 0, psd = 0;
-#pragma unroll
-        for (int w = 0; w < SH_BLOCK / 64; w++) if (w < wid) { pn += s_wcnt[par][w] & 0xffffu; psd += s_wcnt[par][w] >> 16; }
-        const unsigned long long bb = s_base[par];
-        const int qn = (int)(unsigned)(bb & 0xffffffffull) + (int)pn + __popcll(nmask & lt_mask);
-        const int qs = (int)(unsigned)(bb >> 32) + (int)psd + __popcll(smask & lt_mask);
-        if (want_next) {
-            SH_COLD(ca);
-            float *const o_ox = ca->out.ox, *const o_oy = ca->out.oy, *const o_oz = ca->out.oz, *const o_dx = ca->out.dx, *const o_dy = ca->out.dy, *const o_dz = ca->out.dz;
-            float *const o_tr = ca->out.tr, *const o_tg = ca->out.tg, *const o_tb = ca->out.tb, *const o_rr = ca->out.rr, *const o_rg = ca->out.rg, *const o_rb = ca->out.rb;
-            float *const o_tw = ca->out.brdf_pdf, *const o_rw = (float *)ca->out.flags; int *const o_slot = ca->out.slot;
-            asm volatile("" :: "s"(o_ox), "s"(o_oy), "s"(o_oz), "s"(o_dx), "s"(o_dy), "s"(o_dz), "s"(o_tr), "s"(o_tg), "s"(o_tb), "s"(o_rr), "s"(o_rg), "s"(o_rb),
-                         "s"(o_tw), "s"(o_rw), "s"(o_slot));
-            o_ox[qn] = next_o.x; o_oy[qn] = next_o.y; o_oz[qn] = next_o.z;
-            o_dx[qn] = next_d.x; o_dy[qn] = next_d.y; o_dz[qn] = next_d.z;
-            o_tr[qn] = next_thr.v[0]; o_tg[qn] = next_thr.v[1]; o_tb[qn] = next_thr.v[2]; o_tw[qn] = next_thr.v[3];
-            o_rr[qn] = radiance.v[0]; o_rg[qn] = radiance.v[1]; o_rb[qn] = radiance.v[2]; o_rw[qn] = radiance.v[3];
-            o_slot[qn] = slot;
-        } else if (live) {
+        const QueueSlots at = queue_slots(lp, it, want_next, want_shadow, s_wcnt, s_base, append_ctr);
+        // a path that goes on carries its radiance along; one that ends stores it where k_film_spec reads it
+        if (want_next) store_survivor_spec(at.next, slot, next_o, next_d, next_thr, radiance);
+        else if (live) {
             SH_COLD(ca);
             float *const f_r = ca->ps.fr, *const f_g = ca->ps.fg, *const f_b = ca->ps.fb, *const f_w = ca->ps.fw;
             asm volatile("" :: "s"(f_r), "s"(f_g), "s"(f_b), "s"(f_w));
             f_r[slot] = radiance.v[0]; f_g[slot] = radiance.v[1]; f_b[slot] = radiance.v[2]; f_w[slot] = radiance.v[3];
         }
-        if (want_shadow) {
-            SH_COLD(ca);
-            float *const s_ox = ca->ps.sox, *const s_oy = ca->ps.soy, *const s_oz = ca->ps.soz, *const s_dx = ca->ps.sdx, *const s_dy = ca->ps.sdy, *const s_dz = ca->ps.sdz;
-            float *const s_cr = ca->ps.scr, *const s_cg = ca->ps.scg, *const s_cb = ca->ps.scb, *const s_cw = ca->ps.scw, *const s_dist = ca->ps.sdist;
-            int *const s_prim = ca->ps.sprim, *const s_dst = ca->ps.sdst;
-            asm volatile("" :: "s"(s_ox), "s"(s_oy), "s"(s_oz), "s"(s_dx), "s"(s_dy), "s"(s_dz), "s"(s_cr), "s"(s_cg), "s"(s_cb), "s"(s_cw), "s"(s_dist), "s"(s_prim), "s"(s_dst));
-            s_ox[qs] = sh_o.x; s_oy[qs] = sh_o.y; s_oz[qs] = sh_o.z;
-            s_dx[qs] = sh_d.x; s_dy[qs] = sh_d.y; s_dz[qs] = sh_d.z;
-            s_cr[qs] = sh_c.v[0]; s_cg[qs] = sh_c.v[1]; s_cb[qs] = sh_c.v[2]; s_cw[qs] = sh_c.v[3];
-            s_prim[qs] = sh_expect; s_dist[qs] = sh_dist;
-            s_dst[qs] = want_next ? qn : ~slot;
-        }
+        if (want_shadow) store_shadow_ray_spec(at.shadow, want_next ? at.next : ~slot, sh_o, sh_d, sh_c, sh_expect, sh_dist);
     }
     __shared__ unsigned long long s_shaded;
-    if (threadIdx.x == 0) s_shaded = 0ull;
-    __syncthreads();
-    n_shaded = wave_sum(n_shaded);
-    if ((threadIdx.x & 63) == 0 && n_shaded) atomicAdd(&s_shaded, n_shaded);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_shaded) atomicAdd(&ctr->shaded, s_shaded);
+    count_shaded(n_shaded, s_shaded, ctr);
 }
 
 // integrator/PT_Spec.py:141-158 (AddSplat) + :273-274, frames applied in order
