@@ -888,6 +888,44 @@ int tirt_closest_point(tirt_ctx *ctx, const float *points, int n, const float *d
                        float *out_d2, int32_t *out_prim, float *out_point, float *out_uv, int32_t *counts);
 int tirt_kat_closest_point(tirt_ctx *ctx, const float *in, int n, int is_sphere, float *out);
 
+/* K nearest primitives (no reference counterpart; csrc/tirt_nearest.hip / .h): the k primitives of the scene nearest to a query point p, in order, and the
+ * count of all primitives within the bound -- what a caller otherwise gets from repeated bounded closest-point queries or a KD-tree on the host.
+ * Terms.  D2(p, i), Q(p, i), u(p, i), v(p, i) of primitive i, lim2 = dmax * dmax formed once (dmax < 0 or NaN: lim2 = -1; +inf: no bound) and "a NaN or +inf
+ *   D2 is never accepted" are those of "Closest point", unchanged: fp32, every operation in the order written there.
+ * The set.  N(p) = { i : D2(p, i) <= lim2 and D2(p, i) < +inf }.  A comparison with a NaN is false, so a primitive with a NaN D2 is no element; spot and
+ *   laser shapes have no surface and take no part.  N is a set: it does not depend on the order of the visits.  A query with a NaN or infinite coordinate
+ *   has N = {} (every D2 is NaN or +inf), and so does a negative or NaN bound (no D2 is <= -1).  Alpha cut-outs are ignored, as for the closest point.
+ * Order.  D2 ascending; at equal D2 bits the smaller primitive id comes first.  That is a total order on the elements of N (ids are distinct), and its
+ *   element 0 is tirt_query_closest_point's answer, bit for bit.
+ * Outputs, for k in 0 .. TIRT_NEAREST_MAX, each optional: out_d2[i * k + j] and out_prim[i * k + j] for j < k are D2 and the id of element j of N(p_i),
+ *   and +inf and -1 where N has fewer; out_point + (i * k + j) * point_out_stride = Q and out_uv + (i * k + j) * uv_stride = (u, v) of that element, 0 in
+ *   the padding; out_count[i] = |N(p_i)| as int32, which may exceed k.  k == 0 with out_count is the count alone.
+ * Culling and out_count.  With out_count the walk has to meet every element of N and culls by lim2 only; without it, it also culls by the k-th smallest D2
+ *   so far.  A count without a bound (dmax = +inf) is allowed and degenerates to testing every primitive of the scene for every query.
+ * tirt_query_nearest: device memory on the caller's stream with tirt_query_closest_point's plumbing, flags, stack and refusals: row i of the points at
+ *   points + i * point_stride floats; dmax[i * dmax_stride] per query, or dmax_all for every query when dmax is NULL; counts[n*2] = N_box (four per node
+ *   visit), N_leaf (primitive tests) per query (8-byte aligned; only with TIRT_COUNT_NODES).  Queries go through in chunks of max(256, query_chunk_rays /
+ *   max(k, 1)), two launches each (the walk, then the pass that writes the caller's layout), with 8 + 8 k bytes of scratch per query: the list of (D2, prim)
+ *   and (entries held, |N|).  TIRT_TRAVERSE_EXHAUSTIVE = all primitive records in id order through the same list code (the yardstick: same bits, N_box 0,
+ *   N_leaf = primitives).  stack_size 1..4096 entries of 8 bytes per query (the first 16 in LDS, the rest in the context's spill buffer); an entry that
+ *   does not fit is dropped and the query counted in stack_overflow (tirt_stats: TIRT_ERR_STACK).  The queries are not rays: no ray counter moves.
+ *   Refused with TIRT_ERR_ARG before anything is queued, beside tirt_query_closest_point's refusals: k outside 0 .. TIRT_NEAREST_MAX, k == 0 without
+ *   out_count, k > 0 with no output at all.  n == 0 queues nothing.
+ * tirt_nearest: host arrays (points[n*3], dmax[n] or NULL = +inf, out_d2[n*k], out_prim[n*k], out_point[n*k*3], out_uv[n*k*2], out_count[n], counts[n*2]),
+ *   staged (28 + 28 k bytes per query) and synchronous, as tirt_closest_point is to tirt_query_closest_point.
+ * tirt_kat_nearest_list: host only, no context: the n candidates (d2[i], prim[i]), prim >= 0 and distinct, in the order given through the list code the
+ *   kernels run (csrc/tirt_nearest.h) with this k and lim2 (lim2 itself, not a distance: -1 finds nothing).  out_d2[j], out_prim[j] = element j, padded to
+ *   k with (+inf, -1); out_info = {entries held, |N|, bits of the threshold's D2, the threshold's id (-1: the list has room)}. */
+#define TIRT_NEAREST_MAX 64
+int tirt_query_nearest(tirt_ctx *ctx, const float *points, int64_t n, int64_t point_stride,
+                       const float *dmax, int64_t dmax_stride, float dmax_all, int k, int stack_size, int flags,
+                       float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride,
+                       float *out_uv, int64_t uv_stride, int32_t *out_count, int32_t *counts, void *stream);
+int tirt_nearest(tirt_ctx *ctx, const float *points, int n, const float *dmax, int k, int stack_size, int flags,
+                 float *out_d2, int32_t *out_prim, float *out_point, float *out_uv, int32_t *out_count, int32_t *counts);
+int tirt_kat_nearest_list(const float *d2, const int32_t *prim, int n, int k, float lim2,
+                          float *out_d2, int32_t *out_prim, int32_t *out_info);
+
 /* Signed distance (no reference counterpart; csrc/tirt_signed_distance.hip, sd_sign in csrc/tirt_closest_point.h): the distance of "Closest point" with the
  * sign of the angle-weighted pseudo-normal of the closest FEATURE -- face, edge or vertex (Baerentzen & Aanaes, "Signed distance computation using the
  * angle weighted pseudonormal", 2005).  The face normal of the winning triangle alone is wrong at sharp and concave vertices and edges, where several

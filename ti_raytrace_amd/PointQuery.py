@@ -5,6 +5,8 @@
     h = q.closest(points, max_distance=None, attributes=False)      # PointHits(dist2 [N] f32, prim [N] i32, point [N, 3] or None, uv [N, 2] or None)
     s = q.signed_distance(points, max_distance=None, attributes=False)      # SignedHits(dist [N] f32, prim, point, uv): dist < 0 inside
     m = q.inside(points)                                  # [N] bool
+    nn = q.nearest(points, k, max_distance=None, attributes=False, count=False)      # PointNearest(dist2 [N, k], prim [N, k], point, uv, count [N] or None)
+    c = q.count_within(points, max_distance)              # [N] int32: the primitives within max_distance of each point
     r = q.mesh_report()                                   # {"boundary_edges", "nonmanifold_edges", "flipped_edges", "invalid_triangles", "primitives", "closed"}
 
 ``points`` is a float32 tensor ``[N, C >= 3]`` on the scene context's device with ``stride(1) == 1`` and any row stride (an ``[N, 8]``
@@ -13,18 +15,25 @@ device (any positive stride); a negative or NaN bound finds nothing.  Nothing fo
 ``uv`` is the hit record's convention (``point = a + u (b - a) + v (c - a)``).  The outputs come from ``torch.empty`` and the work is
 queued on ``torch.cuda.current_stream(device)``: nothing waits for it on the host.
 
+``nearest`` returns the ``k`` (0 .. 64) nearest primitives of every query in order -- ``dist2`` ascending, at equal bits the smaller primitive id first;
+column 0 is ``closest``'s answer bit for bit -- padded with ``(inf, -1, 0, 0)`` where fewer than ``k`` lie within the bound, and with ``count=True`` the number
+of ALL primitives within the bound, which may exceed ``k`` (include/tirt.h, "K nearest primitives").  With the count the walk cannot cull by the k-th distance:
+give a bound with it.  ``count_within`` is the count alone.
+
 ``signed_distance`` is ``closest`` with the sign of the angle-weighted pseudo-normal of the closest face, edge or vertex (include/tirt.h, "Signed
 distance"): ``dist = -sqrt(dist2)`` inside a closed, consistently oriented mesh or an analytic sphere, ``+sqrt(dist2)`` outside and on the surface,
 ``inf`` where nothing is found.  The first signed call after the geometry changed builds the table of pseudo-normals on the device, on the same stream
 (no host sync); ``mesh_report()`` builds it at once, waits, and says whether the meshes are closed -- on an open mesh the sign is "which side of the sheet".
 """
 import collections
+import operator
 import os
 
 from . import _native
 
 PointHits = collections.namedtuple("PointHits", ["dist2", "prim", "point", "uv"])
 SignedHits = collections.namedtuple("SignedHits", ["dist", "prim", "point", "uv"])
+PointNearest = collections.namedtuple("PointNearest", ["dist2", "prim", "point", "uv", "count"])
 
 
 def _torch():
@@ -133,6 +142,40 @@ class PointQuery:
                                                  dmax_all=dall, out_prim=prim.data_ptr(), out_point=point.data_ptr() if attributes else 0,
                                                  out_uv=uv.data_ptr() if attributes else 0, stream=stream)
         return SignedHits(sd, prim, point, uv)
+
+    def nearest(self, points, k, max_distance=None, attributes=False, count=False):
+        """The k nearest primitives of every query in the order of include/tirt.h, "K nearest primitives": dist2 [N, k] (inf where fewer are within the
+        bound), prim [N, k] (-1), with attributes=True the points [N, k, 3] and their (u, v) [N, k, 2], with count=True the number of all primitives
+        within the bound [N] int32.  Asynchronous on the current stream."""
+        torch = self.torch
+        try:
+            k = operator.index(k)
+        except TypeError:
+            raise TypeError("PointQuery.nearest: k must be an int, got %s" % type(k).__name__) from None
+        if not 0 <= k <= _native.NEAREST_MAX:
+            raise ValueError("PointQuery.nearest: k must be 0..%d, got %d" % (_native.NEAREST_MAX, k))
+        if k == 0 and not count:
+            raise ValueError("PointQuery.nearest: k == 0 without count=True returns nothing")
+        dev, n, stride = self._check_points(points, "nearest")
+        dptr, dstride, dall = self._check_bound(max_distance, dev, n, "nearest")
+        d2 = torch.empty((n, k), dtype=torch.float32, device=dev)
+        prim = torch.empty((n, k), dtype=torch.int32, device=dev)
+        point = torch.empty((n, k, 3), dtype=torch.float32, device=dev) if attributes else None
+        uv = torch.empty((n, k, 2), dtype=torch.float32, device=dev) if attributes else None
+        cnt = torch.empty(n, dtype=torch.int32, device=dev) if count else None
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self.scene.ctx.query_nearest(points.data_ptr(), n, stride, k, self.stack_size, self.flags, dmax=dptr, dmax_stride=dstride, dmax_all=dall,
+                                         out_d2=d2.data_ptr() if k else 0, out_prim=prim.data_ptr() if k else 0,
+                                         out_point=point.data_ptr() if attributes and k else 0, out_uv=uv.data_ptr() if attributes and k else 0,
+                                         out_count=cnt.data_ptr() if count else 0, stream=stream)
+        return PointNearest(d2, prim, point, uv, cnt)
+
+    def count_within(self, points, max_distance):
+        """[N] int32: how many primitives lie within max_distance (a float or an [N] float32 tensor; required) of every query -- nearest(k=0, count=True)"""
+        if max_distance is None:
+            raise TypeError("PointQuery.count_within: max_distance is required (without a bound every primitive counts)")
+        return self.nearest(points, 0, max_distance, count=True).count
 
     def inside(self, points):
         """[N] bool: signed_distance(points).dist < 0"""

@@ -101,6 +101,7 @@ KAT_ENV_PDF_IN, KAT_ENV_PDF_OUT = 3, 5                              # words per 
 KAT_ALPHA_IN, KAT_ALPHA_OUT = 3, 2                                  # words per row of tirt_kat_texture_alpha
 KAT_MAPS_IN, KAT_MAPS_OUT = 3, 8                                    # words per row of tirt_kat_material_maps
 HITS_MAX = 64                                                       # TIRT_HITS_MAX: the largest k of tirt_query_hits
+NEAREST_MAX = 64                                                    # TIRT_NEAREST_MAX: the largest k of tirt_query_nearest
 KAT_STEP_IN, KAT_STEP_OUT = 23, 28                                  # words per row of tirt_kat_shade_step
 
 # context options that select code rather than tune it: name -> (default, meaning).  (The tuning options are listed in include/tirt.h.)
@@ -183,6 +184,10 @@ SIGNATURES = {
                                            _vp, C.c_int64, _vp, _vp]),
     "tirt_closest_point": (C.c_int, [_vp, _f32p, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "tirt_kat_closest_point": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, _f32p]),
+    "tirt_query_nearest": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64,
+                                     _vp, C.c_int64, _vp, _vp, _vp]),
+    "tirt_nearest": (C.c_int, [_vp, _f32p, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tirt_kat_nearest_list": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_float, _vp, _vp, _i32p]),
     "tirt_query_signed_distance": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64,
                                              _vp, C.c_int64, _vp, _vp, _vp]),
     "tirt_signed_distance": (C.c_int, [_vp, _f32p, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -918,6 +923,33 @@ class Context:
                                        _ptr(point), _ptr(uv), _ptr(counts)))
         return d2, prim, point, uv, counts
 
+    def query_nearest(self, points, n, point_stride, k, stack_size=64, flags=0, dmax=0, dmax_stride=1, dmax_all=float("inf"), out_d2=0, out_prim=0,
+                      out_point=0, point_out_stride=3, out_uv=0, uv_stride=2, out_count=0, counts=0, stream=0):
+        """tirt_query_nearest on device memory (include/tirt.h, "K nearest primitives"): every buffer is an integer device address (0 = none), dmax = 0
+        means dmax_all for every query.  Asynchronous; ti_raytrace_amd.PointQuery.nearest / .count_within are the torch front end."""
+        check(lib().tirt_query_nearest(self.handle, _vp(int(points) or None), int(n), int(point_stride), _vp(int(dmax) or None), int(dmax_stride),
+                                       float(dmax_all), int(k), int(stack_size), int(flags), _vp(int(out_d2) or None), _vp(int(out_prim) or None),
+                                       _vp(int(out_point) or None), int(point_out_stride), _vp(int(out_uv) or None), int(uv_stride),
+                                       _vp(int(out_count) or None), _vp(int(counts) or None), _vp(int(stream) or None)))
+
+    def nearest(self, points, k, max_distance=None, stack_size=64, flags=0, attributes=True, count=True):
+        """tirt_nearest, the host route: points (n, 3) float32, max_distance None (= inf), a float or (n,) float32 ->
+        (dist2 (n, k), prim (n, k), point (n, k, 3) or None, uv (n, k, 2) or None, count (n,) or None, counts (n, 2) or None [COUNT_NODES])"""
+        points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n, k = points.shape[0], int(k)
+        dmax = None
+        if max_distance is not None:
+            dmax = np.ascontiguousarray(np.broadcast_to(np.asarray(max_distance, np.float32), (n,)))
+        d2 = np.zeros((n, max(k, 0)), np.float32)
+        prim = np.zeros((n, max(k, 0)), np.int32)
+        point = np.zeros((n, max(k, 0), 3), np.float32) if attributes else None
+        uv = np.zeros((n, max(k, 0), 2), np.float32) if attributes else None
+        cnt = np.zeros(n, np.int32) if count else None
+        counts = np.zeros((n, 2), np.int32) if (flags & COUNT_NODES) else None
+        check(lib().tirt_nearest(self.handle, points.reshape(-1), n, _ptr(dmax), k, int(stack_size), int(flags), _ptr(d2), _ptr(prim), _ptr(point),
+                                 _ptr(uv), _ptr(cnt), _ptr(counts)))
+        return d2, prim, point, uv, cnt, counts
+
     def kat_closest_point(self, rows, is_sphere=False):
         """include/tirt.h, tirt_kat_closest_point: rows (n, 12) (p, a, b, c) or, is_sphere, (n, 7) (p, c, r) -> (n, 6): d2, q3, u, v"""
         rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 7 if is_sphere else 12)
@@ -1087,6 +1119,20 @@ def kat_hit_list(cand, k, bound=float("inf")):
     info = np.zeros(4, np.int32)
     check(lib().tirt_kat_hit_list(cand.reshape(-1), cand.shape[0], int(k), float(bound), _ptr(out), info))
     return out[:info[0]].copy(), int(info[1]), (float(info[2:3].view(np.float32)[0]), int(info[3]))
+
+
+def kat_nearest_list(d2, prim, k, lim2=float("inf")):
+    """include/tirt.h, tirt_kat_nearest_list (host only, no context): candidates (d2 (n,) float32, prim (n,) int32), in the order given, through the list code
+    of csrc/tirt_nearest.h -> (d2 (k,), prim (k,) padded with (inf, -1), entries held, |N|, (threshold d2, threshold prim))"""
+    d2 = np.ascontiguousarray(d2, np.float32).reshape(-1)
+    prim = np.ascontiguousarray(prim, np.int32).reshape(-1)
+    assert d2.shape == prim.shape
+    out_d2 = np.zeros(max(int(k), 0), np.float32)
+    out_prim = np.zeros(max(int(k), 0), np.int32)
+    info = np.zeros(4, np.int32)
+    check(lib().tirt_kat_nearest_list(_ptr(d2) if d2.size else None, _ptr(prim) if prim.size else None, d2.shape[0], int(k), float(lim2),
+                                      _ptr(out_d2) if out_d2.size else None, _ptr(out_prim) if out_prim.size else None, info))
+    return out_d2, out_prim, int(info[0]), int(info[1]), (float(info[2:3].view(np.float32)[0]), int(info[3]))
 
 
 def shade_features_host(material, primitive, shape, light, light_count, env=None, env_power=0.0):

@@ -52,8 +52,8 @@ TD float cp_limit2(const float dmax) { return dmax >= 0.0f ? dmax * dmax : -1.0f
 
 // Does the candidate (d2, prim) replace the answer (best2, best_prim)?  The answer starts as (+inf, -1), "nothing": a NaN d2 fails every comparison, and
 // d2 = +inf is neither below +inf nor, at equal bits, of a smaller id than -1 -- so neither is ever accepted.  A total order on (d2, prim): the
-// result does not depend on the order in which the candidates come.
-TD bool cp_accept(const float d2, const int prim, const float lim2, const float best2, const int best_prim)
+// result does not depend on the order in which the candidates come.  (__host__ too: tirt_kat_nearest_list runs the neighbour list, tirt_nearest.h, on the host)
+__host__ TD bool cp_accept(const float d2, const int prim, const float lim2, const float best2, const int best_prim)
 { return (d2 <= lim2) & ((d2 < best2) | ((d2 == best2) & (prim < best_prim))); }
 
 // ---- signed distance (include/tirt.h, "Signed distance") ----

@@ -1,0 +1,392 @@
+// tirt_nearest.hip -- the k nearest primitives of a query point, in order, and the count of all within the bound (tirt_query_nearest / tirt_nearest /
+// tirt_kat_nearest_list, include/tirt.h "K nearest primitives").  No reference counterpart: the reference only answers questions that start from a ray.
+//
+//   k_nn_walk<COUNT, COUNT_ALL>   one query per lane, best-first over the quantised 4-wide nodes `cnode` (BvhView): the hot path
+//   k_nn_scan<COUNT>              one query per lane against all n primitive records in primitive-id order (TIRT_TRAVERSE_EXHAUSTIVE): the yardstick
+//   k_nn_resolve                  the lists in the caller's [N, k] layout with the padding, the counts, and Q, u, v formed again from the records
+//
+// Nothing but cp_triangle / cp_sphere (tirt_closest_point.h) decides a primitive's D2, and nothing but NnList (tirt_nearest.h) whether and where it goes in
+// the list.  N is a set and the list the first k of a total order on (D2, prim): neither depends on the order of the visits, so the walk returns the
+// scan's bits if and only if it never skips a primitive that would have been accepted.
+//
+// THE WALK is k_cp_walk's (tirt_closest_point.hip), text for text where it can be: a wave is a block (no barrier anywhere), lane l holds query base + l and
+// the blocks stride over the chunk; a node visit decodes the four children's planes, forms lb2 with the margin of PointMargin (CP_AXIS_GAP, CP_EACH_CHILD,
+// tirt_point_walk.h), drops empty slots and children with lb2 > cut, sorts the rest (five compare-exchanges), descends into the nearest and pushes the
+// others far to near WITH their lb2 into PointStack<CpEntry>; a popped entry is tested against the cut of that moment again.  What differs is the cut:
+//     cut = lim2                                   while the list has room (its threshold is "nothing", D2 = +inf)
+//     cut = min(lim2, D2 of the worst entry)       once the list holds k
+//     cut = lim2                                   always under COUNT_ALL (the caller wants |N|: every element of N has to be met)
+// WHY THE CULL IS CONSERVATIVE: the head of tirt_point_walk.h, unchanged.  A subtree is skipped on lb2 > cut only, never on equality, and lb2 <= D2 holds
+// for every primitive below a node: a skipped subtree holds only primitives with D2 > cut.  Such a primitive is no element of N (cut <= lim2), or sorts
+// behind the worst entry of a full list whatever its id (cut = that entry's D2, and the threshold only ever moves forward).  A primitive whose D2 EQUALS
+// the threshold's is below no skipped node; it joins if its id is smaller (cp_accept).
+// The walk starts at root_qcode, as k_cp_walk does (every analytic sphere is below it), and never enters the chain nodes at far_qcode: a leaf is met at
+// most once, so no primitive appears twice in a list or in the count.  Spot and laser leaves are reached and skipped (a NaN D2).  A query with a NaN or
+// infinite coordinate, or a negative or NaN bound, has N = {}: it does not walk.
+// THE LIST lives in the context's chunk scratch as [entry][query] (8 bytes per entry: a wave's access to entry e is contiguous) with its threshold in
+// registers; per query the scratch holds 8 k bytes of list and 8 bytes of (entries held, |N|).  Chunks are max(256, query_chunk_rays / max(k, 1)) queries.
+// The stack is k_cp_walk's: 8-byte entries (child code, lb2), the first CP_LDS_DEPTH of a lane in LDS, the rest of stack_size in the context's spill
+// buffer (point_walk_launch_shape); an entry beyond stack_size is dropped and the query counted in DevCounters::stack_overflow (tirt_stats: TIRT_ERR_STACK).
+#include <string.h>
+#include "tirt_internal.h"
+#include "tirt_closest_point.h"
+#include "tirt_point_walk.h"
+#include "tirt_nearest.h"
+
+namespace tirt {
+
+constexpr int NN_WAVES_PER_CU = 20;          // persistent blocks per CU at most: what 8 KiB of LDS each admits (k_cp_walk's)
+
+typedef unsigned CpEntry __attribute__((ext_vector_type(2)));      // a stack entry: (child code, bits of lb2) -- k_cp_walk's
+
+struct NnArgs {
+    BvhView bvh;
+    const int *primitive, *prim_slot; int n_prim;      // kind and record slot of primitive i (the scan and the resolve)
+    const float *points; int64_t point_stride;          // this chunk's first row
+    const float *dmax; int64_t dmax_stride; float dmax_all;
+    int n, k;                                           // queries of this chunk; entries of a list at most
+    int stack_size;
+    CpEntry *spill;                                     // the stacks' tails (point_walk_launch_shape), or nullptr when stack_size <= CP_LDS_DEPTH
+    uint2 *list; int2 *meta;                            // [k][stride] entries (bits D2, prim); per query (entries held, |N|)
+    size_t stride;                                      // queries of a full chunk: the distance between two entries of one query
+    int2 *counts;                                       // TIRT_COUNT_NODES: N_box, N_leaf per query of the chunk (or nullptr)
+    DevCounters *ctr;
+};
+
+// one query's list in the chunk scratch: entry e of query i at list[e * stride + i], so a wave's access to entry e is one run of 512 bytes
+struct NnStore {
+    uint2 *p; size_t stride;
+    TD NnEntry get(int e) const { const uint2 v = p[(size_t)e * stride]; NnEntry r; r.d2 = __uint_as_float(v.x); r.prim = (int)v.y; return r; }
+    TD void set(int e, const NnEntry c) const { p[(size_t)e * stride] = make_uint2(__float_as_uint(c.d2), (unsigned)c.prim); }
+};
+
+TD void nn_load_query(const NnArgs &a, int q, v3 &p, float &lim2)
+{
+    const float *r = a.points + (int64_t)q * a.point_stride;
+    p = V(r[0], r[1], r[2]);
+    lim2 = cp_limit2(a.dmax ? a.dmax[(int64_t)q * a.dmax_stride] : a.dmax_all);
+}
+
+// D2, Q, u, v of the record in `slot` and its primitive id: the kind comes from the caller (the leaf code's shape bit, or the primitive table).
+// cp_test_record's text (tirt_closest_point.hip) up to the acceptance, which is the list's here.
+TD CpPoint nn_record(const BvhView &b, int slot, bool is_tri, const v3 p, int &prim)
+{
+    const float4 *tp = b.tri + (size_t)slot * TRI_STRIDE;
+    const float4 ta = tp[0], tb = tp[1], tc = tp[2];
+    prim = __float_as_int(tc.w);
+    const v3 pa = V(ta.x, ta.y, ta.z);
+    CpPoint r; r.d2 = __int_as_float(0x7fc00000); r.q = V(0.0f, 0.0f, 0.0f); r.u = 0.0f; r.v = 0.0f;      // spot / laser: no surface, a NaN D2 is never accepted
+    if (is_tri) r = cp_triangle(p, pa, V(tb.x, tb.y, tb.z), V(tc.x, tc.y, tc.z));
+    const bool sph = !is_tri && (int)tb.y == SHAPE_SPHERE;
+    if (__builtin_amdgcn_ballot_w64(sph) != 0ull) { if (sph) r = cp_sphere(p, pa, tb.x); }
+    return r;
+}
+
+// a candidate against the set and the list: counts it if it is an element of N, inserts it if it sorts before the threshold
+TD void nn_offer(NnList &L, const NnStore &store, float d2, int prim, float lim2, int &count)
+{
+    if (NnList::member(d2, prim, lim2)) count++;
+    if (L.wants(d2, prim, lim2)) { NnEntry e; e.d2 = d2; e.prim = prim; L.insert(store, e); }
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(CP_BLOCK) void k_nn_scan(NnArgs a)
+{
+    const int q = blockIdx.x * CP_BLOCK + threadIdx.x;
+    if (q >= a.n) return;
+    v3 p; float lim2;
+    nn_load_query(a, q, p, lim2);
+    NnList L(a.k);
+    const NnStore store = {a.list + q, a.stride};
+    int count = 0;
+    for (int i = 0; i < a.n_prim; i++) {
+        int prim;
+        const CpPoint r = nn_record(a.bvh, a.prim_slot[i], a.primitive[(size_t)i * PRI_VEC] == PRIMITIVE_TRI, p, prim);
+        nn_offer(L, store, r.d2, prim, lim2, count);
+    }
+    a.meta[q] = make_int2(L.n, count);
+    if (COUNT && a.counts) a.counts[q] = make_int2(0, a.n_prim);
+}
+
+template <bool COUNT, bool COUNT_ALL>
+__global__ __launch_bounds__(CP_BLOCK) void k_nn_walk(NnArgs a)
+{
+    __shared__ CpEntry stk[CP_LDS_DEPTH * CP_BLOCK];    // [entry][lane]
+    const BvhView &b = a.bvh;
+    const int lane = threadIdx.x;
+    const PointMargin pm(b);
+    unsigned long long n_over = 0;
+
+    for (int base = blockIdx.x * CP_BLOCK; base < a.n; base += gridDim.x * CP_BLOCK) {      // wave-uniform
+        const int q = base + lane;
+        const bool live = q < a.n;
+        v3 p = V(0.0f, 0.0f, 0.0f); float lim2 = -1.0f;
+        if (live) nn_load_query(a, q, p, lim2);
+        NnList L(a.k);
+        const NnStore store = {a.list + q, a.stride};
+        int count = 0;
+        const float inf = __int_as_float(0x7f800000);
+        const bool finite = absf(p.x) < inf && absf(p.y) < inf && absf(p.z) < inf;      // false for NaN and +-inf
+        const float m = pm.margin(b, p);
+        float cut = lim2;                       // min(thr_d2, lim2): the threshold starts at +inf
+        int cur = (live && finite && lim2 >= 0.0f) ? b.root_qcode : CP_SENT;
+        PointStack<CpEntry> st(stk, a.spill, a.stack_size, lane);
+        unsigned nbox = 0, nleaf = 0;
+        // the next entry that can still hold an acceptable primitive, or CP_SENT
+        auto pop_live = [&]() {
+            while (!st.empty()) { const CpEntry e = st.pop(); if (!(__uint_as_float(e.y) > cut)) return (int)e.x; }
+            return CP_SENT;
+        };
+
+        while (__builtin_amdgcn_ballot_w64(cur != CP_SENT) != 0ull) {
+            // ---- node step: the lanes that are at an inner node
+            if (cur >= 0) {
+                const uint4 *w = b.cnode + (size_t)cur * 4;
+                const uint4 q0 = w[0], q1 = w[1], q2 = w[2], q3 = w[3];
+                if (COUNT) nbox += 4;
+                constexpr float MISS = 3.0e38f;
+                int c0, c1, c2, c3; float l0, l1, l2, l3; bool k0, k1, k2, k3;
+                // kept: a child that is there and can still hold an acceptable primitive (never culled on equality).  The flag travels with the child
+                // through the sort, so a kept child whose lb2 overflowed to +inf (a query ~1e19 away, cut = +inf) sorts behind the dropped ones and is still pushed
+#define NN_BOX(i, X, Y, Z, code_)                                                                   \
+                do {                                                                                \
+                    const float ex__ = CP_AXIS_GAP(b, m, X, 0, p.x), ey__ = CP_AXIS_GAP(b, m, Y, 1, p.y), ez__ = CP_AXIS_GAP(b, m, Z, 2, p.z); \
+                    const float s__ = (ex__ * ex__ + ey__ * ey__) + ez__ * ez__;                    \
+                    c##i = (int)(code_);                                                            \
+                    k##i = (c##i != TR_EMPTY) && !(s__ > cut);                                      \
+                    l##i = k##i ? s__ : MISS;                                                       \
+                } while (0)
+                CP_EACH_CHILD(NN_BOX);
+#define NN_CE(la, ca, ka, lb, cb, kb)                                                               \
+                do {                                                                                \
+                    const bool s__ = (lb) < (la);                                                   \
+                    const float lo__ = s__ ? (lb) : (la), hi__ = s__ ? (la) : (lb);                 \
+                    const int clo__ = s__ ? (cb) : (ca), chi__ = s__ ? (ca) : (cb);                 \
+                    const bool klo__ = s__ ? (kb) : (ka), khi__ = s__ ? (ka) : (kb);                \
+                    la = lo__; lb = hi__; ca = clo__; cb = chi__; ka = klo__; kb = khi__;           \
+                } while (0)
+                NN_CE(l0, c0, k0, l1, c1, k1); NN_CE(l2, c2, k2, l3, c3, k3); NN_CE(l0, c0, k0, l2, c2, k2); NN_CE(l1, c1, k1, l3, c3, k3); NN_CE(l1, c1, k1, l2, c2, k2);
+                if (k3) st.push(CpEntry{(unsigned)c3, __float_as_uint(l3)});
+                if (k2) st.push(CpEntry{(unsigned)c2, __float_as_uint(l2)});
+                if (k1) st.push(CpEntry{(unsigned)c1, __float_as_uint(l1)});
+                cur = k0 ? c0 : pop_live();
+            }
+            // ---- leaf step: the lanes that are at a leaf
+            const bool at_leaf = cur < 0 && cur != CP_SENT;
+            if (__builtin_amdgcn_ballot_w64(at_leaf) != 0ull) {
+                if (at_leaf) {
+                    const int code = ~cur;
+                    if (COUNT) nleaf += 1;
+                    int prim;
+                    const CpPoint r = nn_record(b, leaf_slot(code), leaf_is_tri(code), p, prim);
+                    nn_offer(L, store, r.d2, prim, lim2, count);
+                    if (!COUNT_ALL) cut = __builtin_fminf(L.thr_d2, lim2);
+                    cur = pop_live();
+                }
+            }
+        }
+        if (live) {
+            a.meta[q] = make_int2(L.n, count);
+            if (COUNT && a.counts) a.counts[q] = make_int2((int)nbox, (int)nleaf);
+        }
+        if (st.overflow) n_over++;
+    }
+    n_over = wave_sum(n_over);
+    if (lane == 0 && n_over && a.ctr) atomicAdd(&a.ctr->stack_overflow, n_over);
+}
+
+// thread (i, j): entry j of query i of the chunk into the caller's arrays (at query `base` + i); j == 0 also writes the count.  Q, u, v: cp_triangle /
+// cp_sphere on the query and the primitive's record once more -- the function and the operands the walk had, hence its bits.  Padding: (+inf, -1, 0, 0).
+__global__ void k_nn_resolve(NnArgs a, int64_t base, float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride, float *out_uv,
+                             int64_t uv_stride, int32_t *out_count)
+{
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int kk = a.k > 0 ? a.k : 1;
+    if (id >= (int64_t)a.n * kk) return;
+    const int i = (int)(id % a.n), j = (int)(id / a.n);
+    const int64_t g = base + i;
+    const int2 m = a.meta[i];
+    if (j == 0 && out_count) out_count[g] = m.y;
+    if (j >= a.k) return;
+    float d2 = __int_as_float(0x7f800000); int prim = -1;
+    CpPoint r; r.d2 = d2; r.q = V(0.0f, 0.0f, 0.0f); r.u = 0.0f; r.v = 0.0f;
+    if (j < m.x) {
+        const uint2 e = a.list[(size_t)j * a.stride + i];
+        d2 = __uint_as_float(e.x); prim = (int)e.y;
+        if (out_point || out_uv) {
+            const float *row = a.points + (int64_t)i * a.point_stride;
+            const v3 p = V(row[0], row[1], row[2]);
+            const float4 *tp = a.bvh.tri + (size_t)a.prim_slot[prim] * TRI_STRIDE;
+            const float4 ta = tp[0], tb = tp[1], tc = tp[2];
+            const v3 pa = V(ta.x, ta.y, ta.z);
+            if (a.primitive[(size_t)prim * PRI_VEC] == PRIMITIVE_TRI) r = cp_triangle(p, pa, V(tb.x, tb.y, tb.z), V(tc.x, tc.y, tc.z));
+            else r = cp_sphere(p, pa, tb.x);      // (an entry of a list has a surface: a shape in it is a sphere)
+        }
+    }
+    const int64_t at = g * a.k + j;
+    if (out_d2) out_d2[at] = d2;
+    if (out_prim) out_prim[at] = prim;
+    if (out_point) { float *o = out_point + at * point_out_stride; o[0] = r.q.x; o[1] = r.q.y; o[2] = r.q.z; }
+    if (out_uv) { float *o = out_uv + at * uv_stride; o[0] = r.u; o[1] = r.v; }
+}
+
+// Queries per chunk: max(256, query_chunk_rays / max(k, 1)), as tirt_query_hits, so that the scratch -- 8 B x k of list and 8 B of (entries, |N|) per
+// query -- stays of the order the other queries' is.
+static int nn_chunk_of(const tirt_ctx *c, int64_t n, int k)
+{
+    int64_t chunk = (int64_t)c->query_chunk / (k > 0 ? k : 1);
+    if (chunk < 256) chunk = 256;
+    return (int)(n < chunk ? n : chunk);
+}
+
+// `n` queries in chunks of `chunk` on the context's stream: walk (or scan), then resolve; every pointer is device memory (or null)
+static int nn_chunks(tirt_ctx *c, const float *points, int64_t n, int64_t point_stride, const float *dmax, int64_t dmax_stride, float dmax_all, int k,
+                     int stack_size, int flags, int chunk, float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride, float *out_uv,
+                     int64_t uv_stride, int32_t *out_count, int2 *counts)
+{
+    if (ensure_counters(c)) return TIRT_ERR_HIP;
+    // the scratch of one chunk: (entries, |N|) per query first (8-byte aligned), then the lists.  Growing the buffer waits for the work queued on the
+    // context's stream, which may still read the old one
+    const size_t bytes = (size_t)chunk * (8 + 8 * (size_t)k);
+    if (bytes > c->query_mem.bytes) {
+        TIRT_HIP(hipStreamSynchronize(c->stream));
+        if (c->query_mem.ensure(bytes)) return TIRT_ERR_HIP;
+    }
+    const bool scan = (flags & TIRT_TRAVERSE_EXHAUSTIVE) != 0, cnt = (flags & TIRT_COUNT_NODES) != 0, count_all = out_count != nullptr;
+    NnArgs a = {};
+    a.bvh = bvh_view(c);
+    a.primitive = c->primitive.as<int>(); a.prim_slot = c->prim_slot.as<int>(); a.n_prim = c->n;
+    a.point_stride = point_stride; a.dmax_stride = dmax_stride; a.dmax_all = dmax_all;
+    a.k = k; a.stack_size = stack_size;
+    a.meta = c->query_mem.as<int2>(); a.list = (uint2 *)(a.meta + chunk); a.stride = (size_t)chunk;
+    a.ctr = c->dev_counters.as<DevCounters>();
+    // the walk's grid: a lane for every query of a chunk, as far as the stacks allow (the scan has no stack)
+    int grid_max = 0;
+    if (!scan) if (int rc = point_walk_launch_shape(c, stack_size, NN_WAVES_PER_CU, ((int64_t)chunk + CP_BLOCK - 1) / CP_BLOCK, grid_max, a.spill)) return rc;
+    for (int64_t base = 0; base < n; base += chunk) {
+        const int m = (int)(n - base < chunk ? n - base : chunk);
+        a.n = m;
+        a.points = points + base * point_stride; a.dmax = dmax ? dmax + base * dmax_stride : nullptr;
+        a.counts = counts ? counts + base : nullptr;
+        const int blocks = (m + CP_BLOCK - 1) / CP_BLOCK;
+        if (scan) {
+            if (cnt) hipLaunchKernelGGL((k_nn_scan<true>), dim3(blocks), dim3(CP_BLOCK), 0, c->stream, a);
+            else hipLaunchKernelGGL((k_nn_scan<false>), dim3(blocks), dim3(CP_BLOCK), 0, c->stream, a);
+        } else {
+            const int g = blocks < grid_max ? blocks : grid_max;
+            if (count_all) { if (cnt) hipLaunchKernelGGL((k_nn_walk<true, true>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a);
+                             else hipLaunchKernelGGL((k_nn_walk<false, true>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a); }
+            else { if (cnt) hipLaunchKernelGGL((k_nn_walk<true, false>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a);
+                   else hipLaunchKernelGGL((k_nn_walk<false, false>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a); }
+        }
+        const int64_t threads = (int64_t)m * (k > 0 ? k : 1);
+        hipLaunchKernelGGL(k_nn_resolve, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, c->stream, a, base, out_d2, out_prim, out_point,
+                           point_out_stride, out_uv, uv_stride, out_count);
+    }
+    return TIRT_OK;
+}
+
+// (the checks of k and of the outputs need no context: they come first)
+#define NN_K_CHECKS(fn)                                                                                                         \
+    TIRT_REQUIRE(k >= 0 && k <= TIRT_NEAREST_MAX, fn ": k outside 0..TIRT_NEAREST_MAX (64)");                                   \
+    TIRT_REQUIRE(k > 0 || out_count, fn ": k == 0 without out_count (nothing to return)");                                      \
+    TIRT_REQUIRE(k == 0 || out_d2 || out_prim || out_point || out_uv || out_count, fn ": no output at all (nothing to return)")
+
+}  // namespace tirt
+
+using namespace tirt;
+
+extern "C" {
+
+int tirt_query_nearest(tirt_ctx *c, const float *points, int64_t n, int64_t point_stride, const float *dmax, int64_t dmax_stride, float dmax_all, int k,
+                       int stack_size, int flags, float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride, float *out_uv,
+                       int64_t uv_stride, int32_t *out_count, int32_t *counts, void *stream)
+{
+    const char *fn = "tirt_query_nearest";
+    const std::string f = std::string(fn) + ": ";
+    NN_K_CHECKS("tirt_query_nearest");
+    CTX(c);
+    if (int rc = query_common_checks(c, fn, "n", n, stack_size, flags)) return rc;
+    TIRT_REQUIRE(point_stride >= 3, f + "point_stride < 3 (floats per point)");
+    TIRT_REQUIRE(!out_point || point_out_stride >= 3, f + "point_out_stride < 3 (floats per closest point)");
+    TIRT_REQUIRE(!out_uv || uv_stride >= 2, f + "uv_stride < 2");
+    TIRT_REQUIRE(!dmax || dmax_stride >= 1, f + "dmax_stride < 1");
+    TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, f + "counts must be 8-byte aligned");
+    if (int rc = require_caller_stream(c, fn, stream, "queries")) return rc;
+    if (n == 0) return TIRT_OK;
+    TIRT_REQUIRE(points, f + "null points");
+    if (int rc = require_device_ptr(c, points, (f + "points").c_str())) return rc;
+    if (dmax) if (int rc = require_device_ptr(c, dmax, (f + "dmax").c_str())) return rc;
+    if (out_d2) if (int rc = require_device_ptr(c, out_d2, (f + "out_d2").c_str())) return rc;
+    if (out_prim) if (int rc = require_device_ptr(c, out_prim, (f + "out_prim").c_str())) return rc;
+    if (out_point) if (int rc = require_device_ptr(c, out_point, (f + "out_point").c_str())) return rc;
+    if (out_uv) if (int rc = require_device_ptr(c, out_uv, (f + "out_uv").c_str())) return rc;
+    if (out_count) if (int rc = require_device_ptr(c, out_count, (f + "out_count").c_str())) return rc;
+    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
+    if (want_counts) if (int rc = require_device_ptr(c, counts, (f + "counts").c_str())) return rc;
+    if (int rc = query_begin(c, stream)) return rc;
+    if (int rc = nn_chunks(c, points, n, point_stride, dmax, dmax_stride, dmax_all, k, stack_size, flags, nn_chunk_of(c, n, k), out_d2, out_prim, out_point,
+                           point_out_stride, out_uv, uv_stride, out_count, want_counts ? (int2 *)counts : nullptr)) return rc;
+    return query_end(c, stream);
+}
+
+// host arrays staged in the context's staging buffer (counts [n][2] first: 8-byte aligned; points [n][3], dmax [n], count [n], d2 [n][k], prim [n][k],
+// point [n][k][3], uv [n][k][2]: 28 + 28 k bytes per query), through the chunks above, back to the host with a sync
+int tirt_nearest(tirt_ctx *c, const float *points, int n, const float *dmax, int k, int stack_size, int flags, float *out_d2, int32_t *out_prim,
+                 float *out_point, float *out_uv, int32_t *out_count, int32_t *counts)
+{
+    const char *fn = "tirt_nearest";
+    NN_K_CHECKS("tirt_nearest");
+    CTX(c);
+    if (int rc = query_common_checks(c, fn, "n", n, stack_size, flags)) return rc;
+    if (n == 0) return TIRT_OK;
+    TIRT_REQUIRE(points, std::string(fn) + ": null points");
+    const size_t N = (size_t)n, K = (size_t)k;
+    hipStream_t st = c->stream;
+    if (c->trace_stage.ensure(N * (28 + 28 * K))) return TIRT_ERR_HIP;      // (used by the host routes alone, and each of their calls ends with a sync)
+    int2 *d_counts = c->trace_stage.as<int2>();
+    float *d_points = (float *)(d_counts + N), *d_dmax = d_points + 3 * N;
+    int32_t *d_count = (int32_t *)(d_dmax + N);
+    float *d_d2 = (float *)(d_count + N);
+    int32_t *d_prim = (int32_t *)(d_d2 + K * N);
+    float *d_point = (float *)(d_prim + K * N), *d_uv = d_point + 3 * K * N;
+    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
+    TIRT_HIP(hipMemcpyAsync(d_points, points, sizeof(float) * 3 * N, hipMemcpyHostToDevice, st));
+    if (dmax) TIRT_HIP(hipMemcpyAsync(d_dmax, dmax, sizeof(float) * N, hipMemcpyHostToDevice, st));
+    if (int rc = nn_chunks(c, d_points, n, 3, dmax ? d_dmax : nullptr, 1, __builtin_inff(), k, stack_size, flags, nn_chunk_of(c, n, k), out_d2 ? d_d2 : nullptr,
+                           out_prim ? d_prim : nullptr, out_point ? d_point : nullptr, 3, out_uv ? d_uv : nullptr, 2, out_count ? d_count : nullptr,
+                           want_counts ? d_counts : nullptr)) return rc;
+    if (out_d2 && k) TIRT_HIP(hipMemcpyAsync(out_d2, d_d2, sizeof(float) * K * N, hipMemcpyDeviceToHost, st));
+    if (out_prim && k) TIRT_HIP(hipMemcpyAsync(out_prim, d_prim, sizeof(int32_t) * K * N, hipMemcpyDeviceToHost, st));
+    if (out_point && k) TIRT_HIP(hipMemcpyAsync(out_point, d_point, sizeof(float) * 3 * K * N, hipMemcpyDeviceToHost, st));
+    if (out_uv && k) TIRT_HIP(hipMemcpyAsync(out_uv, d_uv, sizeof(float) * 2 * K * N, hipMemcpyDeviceToHost, st));
+    if (out_count) TIRT_HIP(hipMemcpyAsync(out_count, d_count, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+    if (want_counts) TIRT_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int2) * N, hipMemcpyDeviceToHost, st));
+    TIRT_HIP(hipStreamSynchronize(st));
+    TIRT_HIP(hipGetLastError());
+    return TIRT_OK;
+}
+
+// host only, no context: candidates (d2[i], prim[i]) in the order given through NnList (tirt_nearest.h), the text k_nn_walk and k_nn_scan run
+int tirt_kat_nearest_list(const float *d2, const int32_t *prim, int n, int k, float lim2, float *out_d2, int32_t *out_prim, int32_t *out_info)
+{
+    TIRT_REQUIRE(out_info && n >= 0 && (n == 0 || (d2 && prim)), "tirt_kat_nearest_list: null pointer or negative n");
+    TIRT_REQUIRE(k >= 0 && k <= TIRT_NEAREST_MAX && (k == 0 || (out_d2 && out_prim)), "tirt_kat_nearest_list: k outside 0..TIRT_NEAREST_MAX (64), or no out_d2 / out_prim");
+    struct HostList {
+        float *d2; int32_t *prim;
+        NnEntry get(int e) const { NnEntry r; r.d2 = d2[e]; r.prim = prim[e]; return r; }
+        void set(int e, const NnEntry c) const { d2[e] = c.d2; prim[e] = c.prim; }
+    } list = {out_d2, out_prim};
+    NnList L(k);
+    int members = 0;
+    for (int i = 0; i < n; i++) {
+        TIRT_REQUIRE(prim[i] >= 0, "tirt_kat_nearest_list: a candidate's primitive id is negative");
+        if (NnList::member(d2[i], prim[i], lim2)) members++;
+        if (L.wants(d2[i], prim[i], lim2)) { NnEntry e; e.d2 = d2[i]; e.prim = prim[i]; L.insert(list, e); }
+    }
+    for (int j = L.n; j < k; j++) { out_d2[j] = __builtin_inff(); out_prim[j] = -1; }      // the padding of the definition
+    out_info[0] = L.n; out_info[1] = members; memcpy(&out_info[2], &L.thr_d2, 4); out_info[3] = L.thr_prim;
+    return TIRT_OK;
+}
+
+}  // extern "C"
