@@ -2015,7 +2015,11 @@ typedef struct { v3 pos, normal, snormal, beta, wo; float fpdf, rpdf; int32_t ty
 typedef struct { bvert eye[BD_EYE_MAX], light[BD_LIGHT_MAX], sample, ltemp, etemp, lminustemp, eminustemp; } bpixel;
 
 typedef struct { float view[16]; } orc_view;
-typedef struct { int W, H; bpixel *px; float view[16]; } orc_bdpt;
+/* One addition into `radiance` (bdpt_render_common), for the tests that bound the film per pixel (tests/bdpt_bound_expected.py): the frame, the pixel p
+ * whose sub-paths made it, the pixel q it was added to, the strategy (e, l) and the three values added (SPEC: after AddSplat's conversion).  Eight 32-bit
+ * words; tests/oracle_api.py has the same layout as a numpy dtype. */
+typedef struct { int32_t frame, p, q, e, l; float r[3]; } orc_bd_record;
+typedef struct { int W, H; bpixel *px; float view[16]; orc_bd_record *rec; long rec_cap, rec_n; int rec_on; } orc_bdpt;
 
 orc_bdpt *orc_bdpt_create(int W, int H, const float *view16)
 {
@@ -2026,6 +2030,11 @@ orc_bdpt *orc_bdpt_create(int W, int H, const float *view16)
     return b;
 }
 void orc_bdpt_destroy(orc_bdpt *b) { if (b) { free(b->px); free(b); } }
+/* The contribution recorder, off by default: from now on every addition a render of this state makes into `radiance` is also written to buf[0 .. cap), in
+ * the order of the additions (buf == NULL or cap == 0: only counted).  The count restarts here; orc_bdpt_record_count says how many records the renders since
+ * then NEEDED, which may be more than cap (the rest was dropped).  The recorder only listens: film and stats are the same bits with it on or off. */
+void orc_bdpt_record(orc_bdpt *b, orc_bd_record *buf, long cap) { b->rec = buf; b->rec_cap = (buf && cap > 0) ? cap : 0; b->rec_n = 0; b->rec_on = cap >= 0; }      /* cap < 0: off again */
+long orc_bdpt_record_count(const orc_bdpt *b) { return b->rec_n; }
 
 static float cosine_hemisphere_pdf(float c) { return fmax_(0.01f, c / M_PIf); }      /* UtilsFunc.py:348-350 */
 static float remap0(float f) { return f == 0.0f ? 1.0f : f; }                        /* BDPT_RGB.py:89-93 */
@@ -2616,7 +2625,17 @@ static int bdpt_render_common(const orc_scene *s, const orc_spec *spec, orc_bdpt
                         }
                     }
                     long q = (e == 1) ? ((nu >= 0) ? (long)nu * H + nv : -1) : p;
-                    if (q >= 0) { radiance[3 * q] += r.x; radiance[3 * q + 1] += r.y; radiance[3 * q + 2] += r.z; }
+                    if (q >= 0) {
+                        if (B->rec_on) {                  /* the recorder (orc_bdpt_record) */
+                            if (B->rec_n < B->rec_cap) {
+                                orc_bd_record *rc = &B->rec[B->rec_n];
+                                rc->frame = (int32_t)frame; rc->p = (int32_t)p; rc->q = (int32_t)q; rc->e = e; rc->l = l;
+                                rc->r[0] = r.x; rc->r[1] = r.y; rc->r[2] = r.z;
+                            }
+                            B->rec_n++;
+                        }
+                        radiance[3 * q] += r.x; radiance[3 * q + 1] += r.y; radiance[3 * q + 2] += r.z;
+                    }
                 }
             }
             if (dbg_dump && f == frame_count - 1) {

@@ -34,6 +34,11 @@ SB = {name: 1 << k for k, name in enumerate((
     "emit_mis", "emit_spec", "glass_reflect", "glass_refract", "extinct", "nee", "nee_nopdf", "nee_reject", "lobe_diffuse", "lobe_specular", "end_pdf",
     "miss_finite", "miss_nonfinite", "light_tri", "light_sphere", "light_spot", "light_laser"))}
 
+# orc_bd_record (oracle.c): one addition into BDPT's radiance planes -- frame, source pixel p, target pixel q, strategy (e, l), the three values added
+BD_RECORD = np.dtype([("frame", np.int32), ("p", np.int32), ("q", np.int32), ("e", np.int32), ("l", np.int32), ("r", np.float32, (3,))])
+assert BD_RECORD.itemsize == 32
+BD_PAIRS_MAX = 7 * 7            # e in 1 .. BD_EYE_MAX, l in 0 .. BD_LIGHT_MAX: more than the depth limit lets through
+
 _libs = {}
 
 
@@ -92,6 +97,9 @@ def load(libm=False, native=False):
         L.orc_bdpt_render.argtypes = [_vp, _vp, C.c_uint32, C.c_int, C.c_uint32, C.c_int, _f32p, _f32p, C.POINTER(OrcStats)]
         L.orc_bdpt_spec_render.restype = C.c_int
         L.orc_bdpt_spec_render.argtypes = [_vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, C.c_int, _f32p, _f32p, C.POINTER(OrcStats)]
+        L.orc_bdpt_record.argtypes = [_vp, _vp, C.c_long]
+        L.orc_bdpt_record_count.restype = C.c_long
+        L.orc_bdpt_record_count.argtypes = [_vp]
         L.orc_tone_map.argtypes = [C.c_float, _f32p, _f32p, C.c_long]
         L.orc_total_area.restype = C.c_float
         L.orc_total_area.argtypes = [_vp]
@@ -230,28 +238,39 @@ class OracleScene:
                                  nthreads, C.byref(st))
         return hdr, st.as_dict()
 
-    def bdpt_render(self, cam, W, H, frame_begin, frame_count, seed=1, stack_size=64, hdr=None, state=None):
-        """BDPT_RGB.render x frame_count.  Returns (hdr, stats, state); pass `state` back to continue
-        with the persistent per-pixel vertex arrays of the previous frames."""
+    def _bdpt(self, call, cam, W, H, frame_count, hdr, state, record):
         if hdr is None:
             hdr = np.zeros((W, H, 3), np.float32)
         if state is None:
             state = self.L.orc_bdpt_create(W, H, np.ascontiguousarray(cam.view_np[0].reshape(-1), np.float32))
         rad = np.zeros((W, H, 3), np.float32)
         st = OrcStats()
-        self.L.orc_bdpt_render(self.h, state, frame_begin, frame_count, seed, stack_size, rad.reshape(-1), hdr.reshape(-1), C.byref(st))
-        return hdr, st.as_dict(), state
+        if not record:
+            call(state, rad.reshape(-1), hdr.reshape(-1), C.byref(st))
+            return hdr, st.as_dict(), state
+        # every (e, l) pair of a pixel sample adds at most once: (depth + 2) * (depth + 1) pairs at the most, with room to spare
+        cap = max(W * H * frame_count, 1) * BD_PAIRS_MAX
+        rec = np.zeros(cap, BD_RECORD)
+        self.L.orc_bdpt_record(state, rec.ctypes.data_as(_vp), cap)
+        try:
+            call(state, rad.reshape(-1), hdr.reshape(-1), C.byref(st))
+            need = self.L.orc_bdpt_record_count(state)
+        finally:
+            self.L.orc_bdpt_record(state, None, -1)
+        assert 0 <= need <= cap, (need, cap)
+        return hdr, st.as_dict(), state, rec[:need].copy()
 
-    def bdpt_spec_render(self, cam, W, H, frame_begin, frame_count, seed=1, stack_size=64, hdr=None, state=None):
+    def bdpt_render(self, cam, W, H, frame_begin, frame_count, seed=1, stack_size=64, hdr=None, state=None, record=False):
+        """BDPT_RGB.render x frame_count.  Returns (hdr, stats, state); pass `state` back to continue
+        with the persistent per-pixel vertex arrays of the previous frames.  record=True: (hdr, stats, state, records), the
+        additions into the radiance planes in the oracle's order (BD_RECORD; oracle.c, orc_bd_record)."""
+        return self._bdpt(lambda state, rad, hdr_, st: self.L.orc_bdpt_render(self.h, state, frame_begin, frame_count, seed, stack_size, rad, hdr_, st),
+                          cam, W, H, frame_count, hdr, state, record)
+
+    def bdpt_spec_render(self, cam, W, H, frame_begin, frame_count, seed=1, stack_size=64, hdr=None, state=None, record=False):
         """BDPT_SPEC.render x frame_count (set_spectral first).  Same conventions as bdpt_render."""
-        if hdr is None:
-            hdr = np.zeros((W, H, 3), np.float32)
-        if state is None:
-            state = self.L.orc_bdpt_create(W, H, np.ascontiguousarray(cam.view_np[0].reshape(-1), np.float32))
-        rad = np.zeros((W, H, 3), np.float32)
-        st = OrcStats()
-        self.L.orc_bdpt_spec_render(self.h, self.spec, state, frame_begin, frame_count, seed, stack_size, rad.reshape(-1), hdr.reshape(-1), C.byref(st))
-        return hdr, st.as_dict(), state
+        return self._bdpt(lambda state, rad, hdr_, st: self.L.orc_bdpt_spec_render(self.h, self.spec, state, frame_begin, frame_count, seed, stack_size, rad, hdr_, st),
+                          cam, W, H, frame_count, hdr, state, record)
 
     def set_spectral(self, t):
         """t: PT_Spec.PathTrace.tables() -- the same arrays the device gets"""
