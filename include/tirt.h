@@ -926,6 +926,69 @@ int tirt_nearest(tirt_ctx *ctx, const float *points, int n, const float *dmax, i
 int tirt_kat_nearest_list(const float *d2, const int32_t *prim, int n, int k, float lim2,
                           float *out_d2, int32_t *out_prim, int32_t *out_info);
 
+/* Triangle distance (no reference counterpart; csrc/tirt_triangle_query.hip / .h): the closest points between a query TRIANGLE T = (p0, p1, p2) and the
+ * scene's triangles, and with a bound of 0 the contact test.  The distance between two triangles is attained vertex-to-face or edge-to-edge, and two
+ * triangles that cross have an edge of one through the other: a query of T's vertices through "Closest point" sees the first case only.
+ * Everything is fp32, every operation in the order written, no contraction; dot, cross and cp_triangle (= the triangle of "Closest point": D2, Q) as above.
+ *   clamp(x) = x < 0 ? 0 : (x > 1 ? 1 : x)  (a NaN passes through).
+ *   seg_seg(p1, q1, p2, q2) -> s, t, d2, P, Q  (Ericson 5.1.9 with exact zero tests in place of an epsilon):
+ *     d1 = q1 - p1, d2v = q2 - p2, r = p1 - p2, A = dot(d1, d1), E = dot(d2v, d2v), F = dot(d2v, r);
+ *     A <= 0 and E <= 0:  s = 0, t = 0
+ *     else A <= 0:        s = 0, t = clamp(F / E)
+ *     else C = dot(d1, r);
+ *       E <= 0:           t = 0, s = clamp((-C) / A)
+ *       else              B = dot(d1, d2v), den = A*E - B*B, s = den > 0 ? clamp((B*F - C*E) / den) : 0, t = (B*s + F) / E;
+ *                         if t < 0: t = 0, s = clamp((-C) / A); else if t > 1: t = 1, s = clamp((B - C) / A)
+ *     P = p1 + d1 * s, Q = p2 + d2v * t, d2 = dot(P - Q, P - Q).
+ *   seg_tri(x0, x1, a, b, c) -> hit, u, v, t, X  (Moeller-Trumbore on the segment x0 -> x1):
+ *     d = x1 - x0, E1 = b - a, E2 = c - a, h = cross(d, E2), det = dot(E1, h).  Unless det < 0 or det > 0: no hit, u = v = t = 0.  Otherwise
+ *     inv = 1 / det, s = x0 - a, u = dot(s, h) * inv, q = cross(s, E1), v = dot(d, q) * inv, t = dot(E2, q) * inv,
+ *     X = (a + E1 * u) + E2 * v, w = (x0 + d * t) - X, m2 = max(max(max(max(dot(x0, x0), dot(x1, x1)), dot(a, a)), dot(b, b)), dot(c, c)) with
+ *     max(x, y) = x > y ? x : y;  hit iff u >= 0 and v >= 0 and u + v <= 1 and t >= 0 and t <= 1 and dot(w, w) <= m2 * 2^-38.
+ *     The last condition confirms the hit by its two points: where the segment runs in the triangle's plane (an edge of a wall against a coplanar
+ *     triangle) det is rounding noise and u, v, t fall in range by accident for triangles that are far apart; the segment's point and the triangle's
+ *     point then disagree.  2^-19 of the largest vertex norm is about 55 roundings of a coordinate: a grazing crossing whose points disagree by more
+ *     is no piercing by this arithmetic, and the other candidates give it its (tiny) distance.
+ * The pair (T, scene triangle i = (a, b, c)) has 21 candidates (d2, P on T, Q on the scene triangle); the index is the `code`:
+ *    0..2      vertex p_j against the scene triangle: r = cp_triangle(p_j, a, b, c); P = p_j, Q = r.Q, d2 = r.D2
+ *    3..5      scene vertex s_j (a, b, c) against T: r = cp_triangle(s_j, p0, p1, p2); Q = s_j, P = r.Q, d2 = r.D2
+ *    6+3e+f    edge e of T (p0p1, p1p2, p2p0) against edge f of the scene triangle (ab, bc, ca): seg_seg(edge e, edge f): its P, Q, d2
+ *    15..17    edge e of T pierces the scene triangle: seg_tri(edge e, a, b, c); a candidate iff hit; d2 = 0, P = Q = X
+ *    18..20    edge f of the scene triangle pierces T: seg_tri(edge f, p0, p1, p2); a candidate iff hit; d2 = 0, P = Q = X (formed on T)
+ *   The pair's answer starts as (d2 = +inf, code = -1, P = Q = 0); going through the codes in order, a candidate replaces it iff its d2 < the answer's d2:
+ *   the smallest d2, at equal bits the first in code order; a NaN d2 is never a candidate (and neither is +inf).  No d2 is -0, so once a d2 of 0 stands
+ *   nothing replaces it and an implementation may skip the later candidates.  A degenerate T or scene triangle yields whatever these expressions yield.
+ * The answer for T with bound dmax: lim2 = dmax * dmax formed once (dmax < 0 or NaN: -1; +inf: no bound) and the rule across primitives are those of
+ *   "Closest point", unchanged, on D2(T, i) = the pair's d2: among the scene triangles with D2 <= lim2 the smallest D2, at equal bits the smallest
+ *   primitive id; NaN and +inf are never accepted.  "Nothing" is prim = -1, d2 = +inf, code = -1, P = Q = 0.  A T with a NaN or infinite coordinate finds
+ *   nothing, whatever its finite corners would yield (its lim2 is -1, as for a negative bound; it does not walk).  The minimum of a total order on (D2, prim): the culled walk returns the bits of the scan over all primitives (the
+ *   culling argument is in the head of csrc/tirt_triangle_query.h).  dmax = 0 is the contact test: prim >= 0 iff some scene triangle touches or crosses T
+ *   by this arithmetic.  Analytic spheres, spot and laser shapes take no part: they are reached and skipped.  Alpha cut-outs are ignored, as for the
+ *   closest point.
+ * tirt_query_mesh_distance: device memory on the caller's stream with tirt_query_closest_point's plumbing, flags (TIRT_TRAVERSE_EXHAUSTIVE = the scan over
+ *   all primitive records in id order, the yardstick; TIRT_COUNT_NODES), stack (1..4096 entries of 8 bytes, the first 16 in LDS; a dropped entry is counted
+ *   in stack_overflow), refusals and n == 0 behaviour: asynchronous, no host sync, one launch per chunk of "query_chunk_rays", 0 bytes of scratch per query.
+ *   Row i of the triangles is 9 floats (p0, p1, p2) at tris + i * tri_stride floats (tri_stride >= 9); dmax[i * dmax_stride] per query, or dmax_all for
+ *   every query when dmax is NULL.  Each output may be NULL: out_d2[n], out_prim[n], out_code[n], out_points + i * points_stride = P then Q (6 floats,
+ *   points_stride >= 6), counts[n*2] = N_box, N_leaf per query (8-byte aligned; only with TIRT_COUNT_NODES).  The walk never culls on equality: with
+ *   the answer at D2 = 0 every leaf whose box meets T's box is still tested, since a smaller id may tie -- a deep penetration costs that.
+ *   Refused with TIRT_ERR_ARG before anything is queued: a pointer that is not device memory of ctx's device, tri_stride < 9, points_stride < 6 with
+ *   out_points, dmax_stride < 1 with dmax, counts not 8-byte aligned, other flags, a stack_size outside 1..4096, an LBVH that is not built, a capturing stream.
+ * tirt_mesh_distance: host arrays (tris[n*9], dmax[n] or NULL = +inf, out_points[n*6], counts[n*2]), staged in the context's query scratch (84 bytes per
+ *   query) and synchronous, as tirt_closest_point is to tirt_query_closest_point.
+ * tirt_kat_tri_tri: explicit operands through the same device functions, one row per thread: what = 0: rows of 18 floats (p0, p1, p2, a, b, c) to 8 floats
+ *   (d2, P3, Q3, (float) code); what = 1: seg_seg rows of 12 floats (p1, q1, p2, q2) to (s, t, d2); what = 2: seg_tri rows of 15 floats (x0, x1, a, b, c)
+ *   to (hit as 0 / 1, u, v, t).
+ * tirt_kat_tri_tri_host: host only, no context: the same rows through the same text compiled for the host. */
+int tirt_query_mesh_distance(tirt_ctx *ctx, const float *tris, int64_t n, int64_t tri_stride,
+                             const float *dmax, int64_t dmax_stride, float dmax_all, int stack_size, int flags,
+                             float *out_d2, int32_t *out_prim, int32_t *out_code, float *out_points, int64_t points_stride,
+                             int32_t *counts, void *stream);
+int tirt_mesh_distance(tirt_ctx *ctx, const float *tris, int n, const float *dmax, int stack_size, int flags,
+                       float *out_d2, int32_t *out_prim, int32_t *out_code, float *out_points, int32_t *counts);
+int tirt_kat_tri_tri(tirt_ctx *ctx, const float *in, int n, int what, float *out);
+int tirt_kat_tri_tri_host(const float *in, int n, int what, float *out);
+
 /* Signed distance (no reference counterpart; csrc/tirt_signed_distance.hip, sd_sign in csrc/tirt_closest_point.h): the distance of "Closest point" with the
  * sign of the angle-weighted pseudo-normal of the closest FEATURE -- face, edge or vertex (Baerentzen & Aanaes, "Signed distance computation using the
  * angle weighted pseudonormal", 2005).  The face normal of the winning triangle alone is wrong at sharp and concave vertices and edges, where several

@@ -188,6 +188,11 @@ SIGNATURES = {
                                      _vp, C.c_int64, _vp, _vp, _vp]),
     "tirt_nearest": (C.c_int, [_vp, _f32p, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tirt_kat_nearest_list": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_float, _vp, _vp, _i32p]),
+    "tirt_query_mesh_distance": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int64,
+                                           _vp, _vp]),
+    "tirt_mesh_distance": (C.c_int, [_vp, _f32p, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "tirt_kat_tri_tri": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, _f32p]),
+    "tirt_kat_tri_tri_host": (C.c_int, [_f32p, C.c_int, C.c_int, _f32p]),
     "tirt_query_signed_distance": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64,
                                              _vp, C.c_int64, _vp, _vp, _vp]),
     "tirt_signed_distance": (C.c_int, [_vp, _f32p, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -950,6 +955,41 @@ class Context:
                                  _ptr(uv), _ptr(cnt), _ptr(counts)))
         return d2, prim, point, uv, cnt, counts
 
+    def query_mesh_distance(self, tris, n, tri_stride, stack_size=64, flags=0, dmax=0, dmax_stride=1, dmax_all=float("inf"), out_d2=0, out_prim=0,
+                            out_code=0, out_points=0, points_stride=6, counts=0, stream=0):
+        """tirt_query_mesh_distance on device memory (include/tirt.h, "Triangle distance"): every buffer is an integer device address (0 = none), dmax = 0
+        means dmax_all for every query.  Asynchronous; ti_raytrace_amd.TriangleQuery is the torch front end."""
+        check(lib().tirt_query_mesh_distance(self.handle, _vp(int(tris) or None), int(n), int(tri_stride), _vp(int(dmax) or None), int(dmax_stride),
+                                             float(dmax_all), int(stack_size), int(flags), _vp(int(out_d2) or None), _vp(int(out_prim) or None),
+                                             _vp(int(out_code) or None), _vp(int(out_points) or None), int(points_stride),
+                                             _vp(int(counts) or None), _vp(int(stream) or None)))
+
+    def mesh_distance(self, tris, max_distance=None, stack_size=64, flags=0, points=True):
+        """tirt_mesh_distance, the host route: tris (n, 3, 3) float32, max_distance None (= inf), a float or (n,) float32 ->
+        (dist2 (n,), prim (n,), code (n,), points (n, 2, 3) [P on the query triangle, Q on the scene] or None, counts (n, 2) or None [COUNT_NODES])"""
+        tris = np.ascontiguousarray(tris, np.float32).reshape(-1, 9)
+        n = tris.shape[0]
+        dmax = None
+        if max_distance is not None:
+            dmax = np.ascontiguousarray(np.broadcast_to(np.asarray(max_distance, np.float32), (n,)))
+        d2 = np.zeros(n, np.float32)
+        prim = np.zeros(n, np.int32)
+        code = np.zeros(n, np.int32)
+        pq = np.zeros((n, 2, 3), np.float32) if points else None
+        counts = np.zeros((n, 2), np.int32) if (flags & COUNT_NODES) else None
+        check(lib().tirt_mesh_distance(self.handle, tris.reshape(-1), n, _ptr(dmax), int(stack_size), int(flags), _ptr(d2), _ptr(prim), _ptr(code),
+                                       _ptr(pq), _ptr(counts)))
+        return d2, prim, code, pq, counts
+
+    def kat_tri_tri(self, rows, what=0):
+        """include/tirt.h, tirt_kat_tri_tri: what = 0: rows (n, 18) (T, a, b, c) -> (n, 8) d2, P3, Q3, code; 1: (n, 12) two segments -> (n, 3) s, t, d2;
+        2: (n, 15) segment and triangle -> (n, 4) hit, u, v, t"""
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, KAT_TRI_TRI_ROWS[what][0])
+        out = np.zeros((rows.shape[0], KAT_TRI_TRI_ROWS[what][1]), np.float32)
+        if rows.shape[0]:
+            check(lib().tirt_kat_tri_tri(self.handle, rows.reshape(-1), rows.shape[0], int(what), out.reshape(-1)))
+        return out
+
     def kat_closest_point(self, rows, is_sphere=False):
         """include/tirt.h, tirt_kat_closest_point: rows (n, 12) (p, a, b, c) or, is_sphere, (n, 7) (p, c, r) -> (n, 6): d2, q3, u, v"""
         rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 7 if is_sphere else 12)
@@ -1119,6 +1159,18 @@ def kat_hit_list(cand, k, bound=float("inf")):
     info = np.zeros(4, np.int32)
     check(lib().tirt_kat_hit_list(cand.reshape(-1), cand.shape[0], int(k), float(bound), _ptr(out), info))
     return out[:info[0]].copy(), int(info[1]), (float(info[2:3].view(np.float32)[0]), int(info[3]))
+
+
+KAT_TRI_TRI_ROWS = {0: (18, 8), 1: (12, 3), 2: (15, 4)}             # tirt_kat_tri_tri[_host]: floats per input and output row of each `what`
+
+
+def kat_tri_tri_host(rows, what=0):
+    """include/tirt.h, tirt_kat_tri_tri_host (host only, no context): Context.kat_tri_tri's rows through the same text compiled for the host"""
+    rows = np.ascontiguousarray(rows, np.float32).reshape(-1, KAT_TRI_TRI_ROWS[what][0])
+    out = np.zeros((rows.shape[0], KAT_TRI_TRI_ROWS[what][1]), np.float32)
+    if rows.shape[0]:
+        check(lib().tirt_kat_tri_tri_host(rows.reshape(-1), rows.shape[0], int(what), out.reshape(-1)))
+    return out
 
 
 def kat_nearest_list(d2, prim, k, lim2=float("inf")):

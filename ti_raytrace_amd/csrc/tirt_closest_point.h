@@ -14,7 +14,7 @@ namespace tirt {
 struct CpPoint { float d2; v3 q; float u, v; };
 
 // (u, v) in the hit record's convention: Q = a + u (b - a) + v (c - a).  A vertex region returns the vertex itself, not a + ab * 1.
-TD CpPoint cp_triangle(const v3 p, const v3 a, const v3 b, const v3 c)
+__host__ TD CpPoint cp_triangle(const v3 p, const v3 a, const v3 b, const v3 c)
 {
     const v3 ab = b - a, ac = c - a, ap = p - a;
     const float d1 = dot(ab, ap), d2 = dot(ac, ap);

@@ -23,15 +23,15 @@ constexpr float PI_UF = (float)3.1415956;           // UtilsFunc.py:37 (sic, qui
 constexpr float PI_SCENE = (float)3.1415926;        // Scene.py:319,343; integrator/PT_RGB.py:129-130
 
 struct v3 { float x, y, z; };
-TD v3 V(float x, float y, float z) { v3 r; r.x = x; r.y = y; r.z = z; return r; }
-TD v3 operator+(v3 a, v3 b) { return V(a.x + b.x, a.y + b.y, a.z + b.z); }
-TD v3 operator-(v3 a, v3 b) { return V(a.x - b.x, a.y - b.y, a.z - b.z); }
-TD v3 operator*(v3 a, v3 b) { return V(a.x * b.x, a.y * b.y, a.z * b.z); }
-TD v3 operator*(v3 a, float s) { return V(a.x * s, a.y * s, a.z * s); }
-TD v3 operator/(v3 a, float s) { return V(a.x / s, a.y / s, a.z / s); }
-TD v3 operator-(v3 a) { return V(-a.x, -a.y, -a.z); }
-TD float dot(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-TD v3 cross(v3 a, v3 b) { return V(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+__host__ TD v3 V(float x, float y, float z) { v3 r; r.x = x; r.y = y; r.z = z; return r; }
+__host__ TD v3 operator+(v3 a, v3 b) { return V(a.x + b.x, a.y + b.y, a.z + b.z); }
+__host__ TD v3 operator-(v3 a, v3 b) { return V(a.x - b.x, a.y - b.y, a.z - b.z); }
+__host__ TD v3 operator*(v3 a, v3 b) { return V(a.x * b.x, a.y * b.y, a.z * b.z); }
+__host__ TD v3 operator*(v3 a, float s) { return V(a.x * s, a.y * s, a.z * s); }
+__host__ TD v3 operator/(v3 a, float s) { return V(a.x / s, a.y / s, a.z / s); }
+__host__ TD v3 operator-(v3 a) { return V(-a.x, -a.y, -a.z); }
+__host__ TD float dot(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__host__ TD v3 cross(v3 a, v3 b) { return V(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
 TD float norm(v3 a) { return tm_sqrt(dot(a, a)); }
 // taichi Vector.normalized(): invlen = 1 / norm; invlen * self
 TD v3 normalized(v3 a) { float inv = 1.0f / norm(a); return a * inv; }

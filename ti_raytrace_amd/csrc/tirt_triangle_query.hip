@@ -1,0 +1,326 @@
+// tirt_triangle_query.hip -- the closest points between a query TRIANGLE and the scene's triangles (tirt_query_mesh_distance / tirt_mesh_distance /
+// tirt_kat_tri_tri / tirt_kat_tri_tri_host, include/tirt.h "Triangle distance").  No reference counterpart: the reference only answers questions that
+// start from a ray.
+//
+//   k_tq_scan   one query triangle per lane against all n primitive records in primitive-id order (TIRT_TRAVERSE_EXHAUSTIVE): the yardstick on the device
+//   k_tq_walk   one query triangle per lane, best-first over the quantised 4-wide nodes `cnode` (BvhView): the hot path
+// Both are templates on <COUNT>.  Both call tq_pair (tirt_triangle_query.h) and cp_accept (tirt_closest_point.h) and nothing else decides an answer, and
+// the answer is the minimum of a total order on (D2, prim): the walk returns the scan's bits if and only if it never skips a primitive that would have
+// been accepted.
+//
+// THE WALK is k_cp_walk's (tirt_closest_point.hip), with a box where that has a point: a wave is a block (no barrier anywhere), lane l holds query
+// base + l and the blocks stride over the chunk.  A node visit decodes the four children's planes, forms lb2 = the sum over the axes of
+// max(max(mn - hi, lo - mx) - m, 0)^2 with [lo, hi] the exact box of the query triangle and m the largest of PointMargin's margins of its three vertices,
+// drops empty slots and children with lb2 > cut (cut = min(best D2 so far, lim2)), sorts the rest (five compare-exchanges), descends into the nearest
+// and pushes the others far to near WITH their lb2; a popped entry is tested against the cut of that moment again.  Node steps and leaf steps alternate
+// behind wave ballots, each for the lanes that are at one.  The stack is PointStack<CpEntry> (tirt_point_walk.h): 16 entries of a lane in LDS, the rest
+// of its stack_size in the context's spill buffer; an entry beyond stack_size is dropped and the query counted in DevCounters::stack_overflow.
+// Culling is on lb2 > cut alone, never on equality: with the answer at D2 = 0 every subtree whose grown box meets the query's box (lb2 == 0) is still
+// visited, because a primitive of a smaller id may tie at 0.  A deep penetration costs that many leaf tests.
+// Analytic spheres, spot and laser leaves are reached and skipped (a NaN D2 is never accepted).  A query with a NaN or infinite coordinate finds nothing
+// by the definition (tq_load_query gives it the lim2 of a negative bound): it does not walk, and the scan accepts nothing for it.
+// THE LEAF STEP is the register-heavy, divergent part: 21 candidates.  tq_pair keeps each of its five groups in a rolled loop over vertices or edges
+// (the operands picked by selects, not by indexed arrays: nothing goes to scratch), so the live state across a candidate is the query (9), the record
+// (9), the pair's answer (8) and the walk's own registers; the groups after a d2 of +0 are skipped.
+//
+// WHY THE CULL IS CONSERVATIVE: the head of tirt_triangle_query.h, which extends the head of tirt_point_walk.h.
+#include "tirt_internal.h"
+#include "tirt_triangle_query.h"
+#include "tirt_point_walk.h"
+
+namespace tirt {
+
+constexpr int TQ_WAVES_PER_CU = 20;          // persistent blocks per CU at most: what 8 KiB of LDS each admits (k_cp_walk's figure; the 102 VGPRs admit 16 at a time)
+
+typedef unsigned CpEntry __attribute__((ext_vector_type(2)));      // a stack entry: (child code, bits of lb2), as k_cp_walk's
+
+struct TqArgs {
+    BvhView bvh;
+    const int *primitive, *prim_slot; int n_prim;      // the scan: kind and record slot of primitive i
+    const float *tris; int64_t tri_stride;              // this chunk's first row: p0, p1, p2
+    const float *dmax; int64_t dmax_stride; float dmax_all;
+    int n;                                              // queries of this chunk
+    int stack_size;
+    CpEntry *spill;                                     // the stacks' tails (point_walk_launch_shape), or nullptr when stack_size <= CP_LDS_DEPTH
+    float *out_d2; int32_t *out_prim, *out_code; float *out_points; int64_t points_stride; int2 *counts;
+    DevCounters *ctr;
+};
+
+struct TqQuery { v3 p0, p1, p2; float lim2; };
+struct TqBest { float d2; int prim, code; v3 P, Q; };
+
+// the distance between the interval [lo_, hi_] and the decoded planes of axis k of one child (dword W of its node), less the margin m_, never negative:
+// 0 = the query's box meets the grown box on this axis
+#define TQ_AXIS_GAP(b_, m_, W, k, lo_, hi_)                                                         \
+                ({  const cp_h2v h__ = __builtin_bit_cast(cp_h2v, (unsigned)(W));                   \
+                    const float mn__ = (b_).grid_min[k] + (float)h__.x * (b_).cell[k], mx__ = (b_).grid_min[k] + (float)h__.y * (b_).cell[k]; \
+                    maxf(maxf(mn__ - (hi_), (lo_) - mx__) - (m_), 0.0f); })
+
+TD bool tq_finite3(const v3 p, const float inf) { return absf(p.x) < inf && absf(p.y) < inf && absf(p.z) < inf; }      // false for NaN and +-inf
+
+// a query with a NaN or infinite coordinate finds nothing by the definition, in the scan as in the walk: its lim2 is that of a negative bound
+TD TqQuery tq_load_query(const TqArgs &a, int q)
+{
+    const float *r = a.tris + (int64_t)q * a.tri_stride;
+    TqQuery t;
+    t.p0 = V(r[0], r[1], r[2]); t.p1 = V(r[3], r[4], r[5]); t.p2 = V(r[6], r[7], r[8]);
+    t.lim2 = cp_limit2(a.dmax ? a.dmax[(int64_t)q * a.dmax_stride] : a.dmax_all);
+    const float inf = __int_as_float(0x7f800000);
+    if (!(tq_finite3(t.p0, inf) && tq_finite3(t.p1, inf) && tq_finite3(t.p2, inf))) t.lim2 = -1.0f;
+    return t;
+}
+
+TD TqBest tq_nothing()
+{
+    TqBest o;
+    o.d2 = __int_as_float(0x7f800000); o.prim = -1; o.code = -1; o.P = V(0.0f, 0.0f, 0.0f); o.Q = o.P;
+    return o;
+}
+
+TD void tq_store(const TqArgs &a, int q, const TqBest &o, unsigned nbox, unsigned nleaf, bool count)
+{
+    if (a.out_d2) a.out_d2[q] = o.d2;
+    if (a.out_prim) a.out_prim[q] = o.prim;
+    if (a.out_code) a.out_code[q] = o.code;
+    if (a.out_points) { float *w = a.out_points + (int64_t)q * a.points_stride; w[0] = o.P.x; w[1] = o.P.y; w[2] = o.P.z; w[3] = o.Q.x; w[4] = o.Q.y; w[5] = o.Q.z; }
+    if (count && a.counts) a.counts[q] = make_int2((int)nbox, (int)nleaf);
+}
+
+// one record against the query: a triangle through tq_pair; anything else has no part (its D2 would be NaN: never accepted)
+TD void tq_test_record(const BvhView &b, int slot, bool is_tri, const TqQuery &t, TqBest &o)
+{
+    if (is_tri) {
+        const float4 *tp = b.tri + (size_t)slot * TRI_STRIDE;
+        const float4 ta = tp[0], tb = tp[1], tc = tp[2];
+        const int prim = __float_as_int(tc.w);
+        const TqPair r = tq_pair(t.p0, t.p1, t.p2, V(ta.x, ta.y, ta.z), V(tb.x, tb.y, tb.z), V(tc.x, tc.y, tc.z));
+        if (cp_accept(r.d2, prim, t.lim2, o.d2, o.prim)) { o.d2 = r.d2; o.prim = prim; o.code = r.code; o.P = r.P; o.Q = r.Q; }
+    }
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(CP_BLOCK) void k_tq_scan(TqArgs a)
+{
+    const int q = blockIdx.x * CP_BLOCK + threadIdx.x;
+    if (q >= a.n) return;
+    const TqQuery t = tq_load_query(a, q);
+    TqBest o = tq_nothing();
+    for (int i = 0; i < a.n_prim; i++)
+        tq_test_record(a.bvh, a.prim_slot[i], a.primitive[(size_t)i * PRI_VEC] == PRIMITIVE_TRI, t, o);
+    tq_store(a, q, o, 0u, (unsigned)a.n_prim, COUNT);
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(CP_BLOCK) void k_tq_walk(TqArgs a)
+{
+    __shared__ CpEntry stk[CP_LDS_DEPTH * CP_BLOCK];    // [entry][lane]
+    const BvhView &b = a.bvh;
+    const int lane = threadIdx.x;
+    const PointMargin pm(b);
+    unsigned long long n_over = 0;
+
+    for (int base = blockIdx.x * CP_BLOCK; base < a.n; base += gridDim.x * CP_BLOCK) {      // wave-uniform
+        const int q = base + lane;
+        const bool live = q < a.n;
+        TqQuery t; t.p0 = V(0.0f, 0.0f, 0.0f); t.p1 = t.p0; t.p2 = t.p0; t.lim2 = -1.0f;
+        if (live) t = tq_load_query(a, q);
+        TqBest o = tq_nothing();
+        const v3 lo = V(minf(minf(t.p0.x, t.p1.x), t.p2.x), minf(minf(t.p0.y, t.p1.y), t.p2.y), minf(minf(t.p0.z, t.p1.z), t.p2.z));
+        const v3 hi = V(maxf(maxf(t.p0.x, t.p1.x), t.p2.x), maxf(maxf(t.p0.y, t.p1.y), t.p2.y), maxf(maxf(t.p0.z, t.p1.z), t.p2.z));
+        const float m = maxf(maxf(pm.margin(b, t.p0), pm.margin(b, t.p1)), pm.margin(b, t.p2));      // rho_p over all three vertices
+        float cut = t.lim2;                     // min(best D2, lim2): the best starts at +inf
+        int cur = (live && t.lim2 >= 0.0f) ? b.root_qcode : CP_SENT;      // (a negative or NaN bound, a query that is not finite: no walk)
+        PointStack<CpEntry> st(stk, a.spill, a.stack_size, lane);
+        unsigned nbox = 0, nleaf = 0;
+        // the next entry that can still win, or CP_SENT
+        auto pop_live = [&]() {
+            while (!st.empty()) { const CpEntry e = st.pop(); if (!(__uint_as_float(e.y) > cut)) return (int)e.x; }
+            return CP_SENT;
+        };
+
+        while (__builtin_amdgcn_ballot_w64(cur != CP_SENT) != 0ull) {
+            // ---- node step: the lanes that are at an inner node
+            if (cur >= 0) {
+                const uint4 *w = b.cnode + (size_t)cur * 4;
+                const uint4 q0 = w[0], q1 = w[1], q2 = w[2], q3 = w[3];
+                if (COUNT) nbox += 4;
+                constexpr float MISS = 3.0e38f;
+                int c0, c1, c2, c3; float l0, l1, l2, l3; bool k0, k1, k2, k3;
+                // kept: a child that is there and can still win (never culled on equality); the flag travels with the child through the sort
+#define TQ_BOX(i, X, Y, Z, code_)                                                                   \
+                do {                                                                                \
+                    const float ex__ = TQ_AXIS_GAP(b, m, X, 0, lo.x, hi.x), ey__ = TQ_AXIS_GAP(b, m, Y, 1, lo.y, hi.y), ez__ = TQ_AXIS_GAP(b, m, Z, 2, lo.z, hi.z); \
+                    const float s__ = (ex__ * ex__ + ey__ * ey__) + ez__ * ez__;                    \
+                    c##i = (int)(code_);                                                            \
+                    k##i = (c##i != TR_EMPTY) && !(s__ > cut);                                      \
+                    l##i = k##i ? s__ : MISS;                                                       \
+                } while (0)
+                CP_EACH_CHILD(TQ_BOX);
+#define TQ_CE(la, ca, ka, lb, cb, kb)                                                               \
+                do {                                                                                \
+                    const bool s__ = (lb) < (la);                                                   \
+                    const float lo__ = s__ ? (lb) : (la), hi__ = s__ ? (la) : (lb);                 \
+                    const int clo__ = s__ ? (cb) : (ca), chi__ = s__ ? (ca) : (cb);                 \
+                    const bool klo__ = s__ ? (kb) : (ka), khi__ = s__ ? (ka) : (kb);                \
+                    la = lo__; lb = hi__; ca = clo__; cb = chi__; ka = klo__; kb = khi__;           \
+                } while (0)
+                TQ_CE(l0, c0, k0, l1, c1, k1); TQ_CE(l2, c2, k2, l3, c3, k3); TQ_CE(l0, c0, k0, l2, c2, k2); TQ_CE(l1, c1, k1, l3, c3, k3); TQ_CE(l1, c1, k1, l2, c2, k2);
+                if (k3) st.push(CpEntry{(unsigned)c3, __float_as_uint(l3)});
+                if (k2) st.push(CpEntry{(unsigned)c2, __float_as_uint(l2)});
+                if (k1) st.push(CpEntry{(unsigned)c1, __float_as_uint(l1)});
+                cur = k0 ? c0 : pop_live();
+            }
+            // ---- leaf step: the lanes that are at a leaf
+            const bool at_leaf = cur < 0 && cur != CP_SENT;
+            if (__builtin_amdgcn_ballot_w64(at_leaf) != 0ull) {
+                if (at_leaf) {
+                    const int code = ~cur;
+                    if (COUNT) nleaf += 1;
+                    tq_test_record(b, leaf_slot(code), leaf_is_tri(code), t, o);
+                    cut = __builtin_fminf(o.d2, t.lim2);
+                    cur = pop_live();
+                }
+            }
+        }
+        if (live) tq_store(a, q, o, nbox, nleaf, COUNT);
+        if (st.overflow) n_over++;
+    }
+    n_over = wave_sum(n_over);
+    if (lane == 0 && n_over && a.ctr) atomicAdd(&a.ctr->stack_overflow, n_over);
+}
+
+// `n` queries in chunks of `chunk` on the context's stream; every pointer is device memory (or null)
+static int tq_chunks(tirt_ctx *c, const float *tris, int64_t n, int64_t tri_stride, const float *dmax, int64_t dmax_stride, float dmax_all,
+                     int stack_size, int flags, int chunk, float *out_d2, int32_t *out_prim, int32_t *out_code, float *out_points, int64_t points_stride,
+                     int2 *counts)
+{
+    if (ensure_counters(c)) return TIRT_ERR_HIP;
+    const bool scan = (flags & TIRT_TRAVERSE_EXHAUSTIVE) != 0, cnt = (flags & TIRT_COUNT_NODES) != 0;
+    TqArgs a = {};
+    a.bvh = bvh_view(c);
+    a.primitive = c->primitive.as<int>(); a.prim_slot = c->prim_slot.as<int>(); a.n_prim = c->n;
+    a.tri_stride = tri_stride; a.dmax_stride = dmax_stride; a.dmax_all = dmax_all;
+    a.stack_size = stack_size; a.points_stride = points_stride;
+    a.ctr = c->dev_counters.as<DevCounters>();
+    // the walk's grid: a lane for every query of a chunk, as far as the stacks allow (the scan has no stack)
+    int grid_max = 0;
+    if (!scan) if (int rc = point_walk_launch_shape(c, stack_size, TQ_WAVES_PER_CU, ((int64_t)(n < chunk ? n : chunk) + CP_BLOCK - 1) / CP_BLOCK, grid_max, a.spill)) return rc;
+    for (int64_t base = 0; base < n; base += chunk) {
+        const int m = (int)(n - base < chunk ? n - base : chunk);
+        a.n = m;
+        a.tris = tris + base * tri_stride; a.dmax = dmax ? dmax + base * dmax_stride : nullptr;
+        a.out_d2 = out_d2 ? out_d2 + base : nullptr; a.out_prim = out_prim ? out_prim + base : nullptr; a.out_code = out_code ? out_code + base : nullptr;
+        a.out_points = out_points ? out_points + base * points_stride : nullptr;
+        a.counts = counts ? counts + base : nullptr;
+        const int blocks = (m + CP_BLOCK - 1) / CP_BLOCK;
+        const int g = blocks < grid_max ? blocks : grid_max;
+        if (scan) { if (cnt) hipLaunchKernelGGL((k_tq_scan<true>), dim3(blocks), dim3(CP_BLOCK), 0, c->stream, a);
+                    else hipLaunchKernelGGL((k_tq_scan<false>), dim3(blocks), dim3(CP_BLOCK), 0, c->stream, a); }
+        else { if (cnt) hipLaunchKernelGGL((k_tq_walk<true>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a);
+               else hipLaunchKernelGGL((k_tq_walk<false>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a); }
+    }
+    return TIRT_OK;
+}
+
+// one row per thread through tq_kat_row (tirt_triangle_query.h): the text tirt_kat_tri_tri_host runs on the host
+__global__ void k_kat_tri_tri(const float *in, int n, int what, int in_stride, int out_stride, float *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    tq_kat_row(in + (size_t)i * in_stride, what, out + (size_t)i * out_stride);
+}
+
+}  // namespace tirt
+
+using namespace tirt;
+
+extern "C" {
+
+int tirt_query_mesh_distance(tirt_ctx *c, const float *tris, int64_t n, int64_t tri_stride, const float *dmax, int64_t dmax_stride, float dmax_all,
+                             int stack_size, int flags, float *out_d2, int32_t *out_prim, int32_t *out_code, float *out_points, int64_t points_stride,
+                             int32_t *counts, void *stream)
+{
+    const char *fn = "tirt_query_mesh_distance";
+    const std::string f = std::string(fn) + ": ";
+    CTX(c);
+    if (int rc = query_common_checks(c, fn, "n", n, stack_size, flags)) return rc;
+    TIRT_REQUIRE(tri_stride >= 9, f + "tri_stride < 9 (floats per triangle)");
+    TIRT_REQUIRE(!out_points || points_stride >= 6, f + "points_stride < 6 (floats per pair of closest points)");
+    TIRT_REQUIRE(!dmax || dmax_stride >= 1, f + "dmax_stride < 1");
+    TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, f + "counts must be 8-byte aligned");
+    if (int rc = require_caller_stream(c, fn, stream, "queries")) return rc;
+    if (n == 0) return TIRT_OK;
+    TIRT_REQUIRE(tris, f + "null tris");
+    if (int rc = require_device_ptr(c, tris, (f + "tris").c_str())) return rc;
+    if (dmax) if (int rc = require_device_ptr(c, dmax, (f + "dmax").c_str())) return rc;
+    if (out_d2) if (int rc = require_device_ptr(c, out_d2, (f + "out_d2").c_str())) return rc;
+    if (out_prim) if (int rc = require_device_ptr(c, out_prim, (f + "out_prim").c_str())) return rc;
+    if (out_code) if (int rc = require_device_ptr(c, out_code, (f + "out_code").c_str())) return rc;
+    if (out_points) if (int rc = require_device_ptr(c, out_points, (f + "out_points").c_str())) return rc;
+    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
+    if (want_counts) if (int rc = require_device_ptr(c, counts, (f + "counts").c_str())) return rc;
+    const int chunk = (int)(n < (int64_t)c->query_chunk ? n : (int64_t)c->query_chunk);
+    if (int rc = query_begin(c, stream)) return rc;
+    if (int rc = tq_chunks(c, tris, n, tri_stride, dmax, dmax_stride, dmax_all, stack_size, flags, chunk, out_d2, out_prim, out_code, out_points,
+                           points_stride, want_counts ? (int2 *)counts : nullptr)) return rc;
+    return query_end(c, stream);
+}
+
+// host arrays staged in the context's query scratch (query_mem: 84 bytes per query), one chunk of all of them, back with a sync
+int tirt_mesh_distance(tirt_ctx *c, const float *tris, int n, const float *dmax, int stack_size, int flags, float *out_d2, int32_t *out_prim,
+                       int32_t *out_code, float *out_points, int32_t *counts)
+{
+    const char *fn = "tirt_mesh_distance";
+    CTX(c);
+    if (int rc = query_common_checks(c, fn, "n", n, stack_size, flags)) return rc;
+    if (n == 0) return TIRT_OK;
+    TIRT_REQUIRE(tris, std::string(fn) + ": null tris");
+    const size_t N = (size_t)n, bytes = N * 84;
+    hipStream_t st = c->stream;
+    if (bytes > c->query_mem.bytes) {
+        TIRT_HIP(hipStreamSynchronize(st));
+        if (c->query_mem.ensure(bytes)) return TIRT_ERR_HIP;
+    }
+    // counts [n][2] first (8-byte aligned), then tris [n][9], dmax [n], d2 [n], prim [n], code [n], points [n][6]
+    int2 *d_counts = c->query_mem.as<int2>();
+    float *d_tris = (float *)(d_counts + N), *d_dmax = d_tris + 9 * N, *d_d2 = d_dmax + N;
+    int32_t *d_prim = (int32_t *)(d_d2 + N), *d_code = d_prim + N;
+    float *d_points = (float *)(d_code + N);
+    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
+    TIRT_HIP(hipMemcpyAsync(d_tris, tris, sizeof(float) * 9 * N, hipMemcpyHostToDevice, st));
+    if (dmax) TIRT_HIP(hipMemcpyAsync(d_dmax, dmax, sizeof(float) * N, hipMemcpyHostToDevice, st));
+    if (int rc = tq_chunks(c, d_tris, n, 9, dmax ? d_dmax : nullptr, 1, __builtin_inff(), stack_size, flags, n, d_d2, d_prim, d_code, d_points, 6,
+                           want_counts ? d_counts : nullptr)) return rc;
+    if (out_d2) TIRT_HIP(hipMemcpyAsync(out_d2, d_d2, sizeof(float) * N, hipMemcpyDeviceToHost, st));
+    if (out_prim) TIRT_HIP(hipMemcpyAsync(out_prim, d_prim, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+    if (out_code) TIRT_HIP(hipMemcpyAsync(out_code, d_code, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+    if (out_points) TIRT_HIP(hipMemcpyAsync(out_points, d_points, sizeof(float) * 6 * N, hipMemcpyDeviceToHost, st));
+    if (want_counts) TIRT_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int2) * N, hipMemcpyDeviceToHost, st));
+    TIRT_HIP(hipStreamSynchronize(st));
+    TIRT_HIP(hipGetLastError());
+    return TIRT_OK;
+}
+
+int tirt_kat_tri_tri(tirt_ctx *c, const float *in, int n, int what, float *out)
+{
+    TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_tri_tri: null pointer or negative n");
+    TIRT_REQUIRE(what >= 0 && what <= 2, "tirt_kat_tri_tri: what is 0 (pair), 1 (segment-segment) or 2 (segment-triangle)");
+    CTX(c);
+    if (n == 0) return TIRT_OK;
+    const int is = TQ_KAT_IN[what], os = TQ_KAT_OUT[what];
+    return kat_round_trip(c, "tirt_kat_tri_tri", {{in, kat_row_bytes(n, is)}}, out, kat_row_bytes(n, os), [&](const void *const *din, void *dout) {
+        hipLaunchKernelGGL(k_kat_tri_tri, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float *)din[0], n, what, is, os, (float *)dout);
+    });
+}
+
+// host only, no context: the same rows through the same text (tq_kat_row), compiled for the host
+int tirt_kat_tri_tri_host(const float *in, int n, int what, float *out)
+{
+    TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_tri_tri_host: null pointer or negative n");
+    TIRT_REQUIRE(what >= 0 && what <= 2, "tirt_kat_tri_tri_host: what is 0 (pair), 1 (segment-segment) or 2 (segment-triangle)");
+    const int is = TQ_KAT_IN[what], os = TQ_KAT_OUT[what];
+    for (int i = 0; i < n; i++) tq_kat_row(in + (size_t)i * is, what, out + (size_t)i * os);
+    return TIRT_OK;
+}
+
+}  // extern "C"
