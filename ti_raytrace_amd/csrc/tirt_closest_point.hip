@@ -10,30 +10,19 @@
 // Both call cp_triangle / cp_sphere / cp_accept (tirt_closest_point.h) and nothing else decides an answer, and the answer is the minimum of a total
 // order on (D2, prim): the walk returns the scan's bits if and only if it never skips a primitive that would have been accepted.
 //
-// THE WALK.  A wave is a block (no barrier anywhere); lane l holds query base + l and the blocks stride over the chunk.  A node visit decodes the four
-// children's planes (grid_min + h * cell, h the fp16 halves of the record), forms lb2 = sum over the axes of max(mn - p - m, p - mx - m, 0)^2 with the
-// margin m of PointMargin (tirt_point_walk.h), drops empty slots and children with lb2 > cut (cut = min(best D2 so far, lim2)), sorts the rest (five compare-exchanges, as k_trace),
-// descends into the nearest and pushes the others far to near WITH their lb2; a popped entry is tested against the cut of that moment again (the best
-// distance of a nearest-neighbour walk shrinks fast: most entries are dead when they surface).  Leaves gather the three quads of the record; the
-// sphere branch (a square root and a division) sits behind a wave ballot, as in trace_leaf_step.  Node steps and leaf steps alternate, each for the
-// lanes that are at one.  The stack is PointStack (tirt_point_walk.h) with entries of 8 bytes (child code, lb2): the first CP_LDS_DEPTH of a lane live in LDS
-// ([entry][lane]), the rest of its stack_size in the context's spill buffer ([entry][global thread]) -- DESIGN.md "Closest point" has the sizes and why 16.  An entry beyond stack_size
+// THE WALK is point_walk (tirt_point_walk.h, which has why its cull is conservative) with lo == hi == the query point and the margin of PointMargin; lane l
+// of a block holds query base + l and the blocks stride over the chunk.  THE CUT is min(best D2 so far, lim2): the leaf tests the record through
+// cp_test_record and returns it.  The stack is PointStack<CpEntry>; DESIGN.md "Closest point" has the sizes and why 16.  An entry beyond stack_size
 // is dropped and the query counted in DevCounters::stack_overflow (tirt_stats: TIRT_ERR_STACK), as a ray's.
 // The walk starts at root_qcode (a leaf code in a one-primitive scene).  Every analytic sphere is below it: its slot carries its padded box
 // (shapes_boxed) or the whole grid, and both contain the sphere, as every ancestor's box does -- the chain nodes at far_qcode exist for rays, whose
 // sphere test can answer from outside the padded box; a closest point lies ON the sphere.  Spot and laser leaves are reached and skipped.
 // A query with a NaN or infinite coordinate finds nothing by the definition (every D2 is NaN or +inf): it does not walk.
-//
-// WHY THE CULL IS CONSERVATIVE: the head of tirt_point_walk.h, beside the margin it is about (PointMargin, which k_sd_build shares, as it does the stack).
 #include "tirt_internal.h"
 #include "tirt_closest_point.h"
 #include "tirt_point_walk.h"
 
 namespace tirt {
-
-constexpr int CP_WAVES_PER_CU = 20;          // persistent blocks per CU at most: what 8 KiB of LDS each admits (62 VGPRs would admit 32)
-
-typedef unsigned CpEntry __attribute__((ext_vector_type(2)));      // a stack entry: (child code, bits of lb2)
 
 struct CpArgs {
     BvhView bvh;
@@ -49,13 +38,6 @@ struct CpArgs {
     const float4 *sd_tab; const int *sd_state; float *out_sd;      // [n_prim][SD_ROWS]; sd_state[0] != 0: the table's build dropped a stack entry
 };
 
-TD void cp_load_query(const CpArgs &a, int q, v3 &p, float &lim2)
-{
-    const float *r = a.points + (int64_t)q * a.point_stride;
-    p = V(r[0], r[1], r[2]);
-    lim2 = cp_limit2(a.dmax ? a.dmax[(int64_t)q * a.dmax_stride] : a.dmax_all);
-}
-
 TD void cp_store(const CpArgs &a, int q, float best2, int best_prim, const CpPoint &bp, unsigned nbox, unsigned nleaf, bool count)
 {
     if (a.out_d2) a.out_d2[q] = best2;
@@ -68,14 +50,8 @@ TD void cp_store(const CpArgs &a, int q, float best2, int best_prim, const CpPoi
 // one record against the query: the kind comes from the caller (the leaf code's shape bit, or the primitive table)
 TD void cp_test_record(const BvhView &b, int slot, bool is_tri, const v3 p, float lim2, float &best2, int &best_prim, CpPoint &bp)
 {
-    const float4 *tp = b.tri + (size_t)slot * TRI_STRIDE;
-    const float4 ta = tp[0], tb = tp[1], tc = tp[2];
-    const int prim = __float_as_int(tc.w);
-    const v3 pa = V(ta.x, ta.y, ta.z);
-    CpPoint r; r.d2 = __int_as_float(0x7fc00000); r.q = V(0.0f, 0.0f, 0.0f); r.u = 0.0f; r.v = 0.0f;      // spot / laser: no surface, a NaN D2 is never accepted
-    if (is_tri) r = cp_triangle(p, pa, V(tb.x, tb.y, tb.z), V(tc.x, tc.y, tc.z));
-    const bool sph = !is_tri && (int)tb.y == SHAPE_SPHERE;
-    if (__builtin_amdgcn_ballot_w64(sph) != 0ull) { if (sph) r = cp_sphere(p, pa, tb.x); }
+    int prim;
+    const CpPoint r = cp_record(b, slot, is_tri, p, prim);
     if (cp_accept(r.d2, prim, lim2, best2, best_prim)) { best2 = r.d2; best_prim = prim; bp = r; }
 }
 
@@ -130,69 +106,21 @@ __global__ __launch_bounds__(CP_BLOCK) void k_cp_walk(CpArgs a)
         if (live) cp_load_query(a, q, p, lim2);
         float best2 = __int_as_float(0x7f800000); int best_prim = -1;
         CpPoint bp; bp.d2 = best2; bp.q = V(0.0f, 0.0f, 0.0f); bp.u = 0.0f; bp.v = 0.0f;
-        const bool finite = absf(p.x) < best2 && absf(p.y) < best2 && absf(p.z) < best2;      // false for NaN and +-inf
+        const float inf = __int_as_float(0x7f800000);
+        const bool finite = CP_FINITE3(p, inf);
         const float m = pm.margin(b, p);
-        float cut = lim2;                       // min(best2, lim2): best2 starts at +inf
-        int cur = (live && finite && lim2 >= 0.0f) ? b.root_qcode : CP_SENT;
+        const int start = (live && finite && lim2 >= 0.0f) ? b.root_qcode : CP_SENT;
         PointStack<CpEntry> st(stk, a.spill, a.stack_size, lane);
         unsigned nbox = 0, nleaf = 0;
-        // the next entry that can still win, or CP_SENT; most are dead by the time they surface
-        auto pop_live = [&]() {
-            while (!st.empty()) { const CpEntry e = st.pop(); if (!(__uint_as_float(e.y) > cut)) return (int)e.x; }
-            return CP_SENT;
-        };
-
-        while (__builtin_amdgcn_ballot_w64(cur != CP_SENT) != 0ull) {
-            // ---- node step: the lanes that are at an inner node
-            if (cur >= 0) {
-                const uint4 *w = b.cnode + (size_t)cur * 4;
-                const uint4 q0 = w[0], q1 = w[1], q2 = w[2], q3 = w[3];
-                if (COUNT) nbox += 4;
-                constexpr float MISS = 3.0e38f;
-                int c0, c1, c2, c3; float l0, l1, l2, l3; bool k0, k1, k2, k3;
-                // kept: a child that is there and can still win (never culled on equality).  The flag travels with the child through the sort, so
-                // a kept child whose lb2 overflowed to +inf (a query ~1e19 away, cut = +inf) sorts behind the dropped ones and is still pushed
-#define CP_BOX(i, X, Y, Z, code_)                                                                   \
-                do {                                                                                \
-                    const float ex__ = CP_AXIS_GAP(b, m, X, 0, p.x), ey__ = CP_AXIS_GAP(b, m, Y, 1, p.y), ez__ = CP_AXIS_GAP(b, m, Z, 2, p.z); \
-                    const float s__ = (ex__ * ex__ + ey__ * ey__) + ez__ * ez__;                    \
-                    c##i = (int)(code_);                                                            \
-                    k##i = (c##i != TR_EMPTY) && !(s__ > cut);                                      \
-                    l##i = k##i ? s__ : MISS;                                                       \
-                } while (0)
-                CP_EACH_CHILD(CP_BOX);
-#define CP_CE(la, ca, ka, lb, cb, kb)                                                               \
-                do {                                                                                \
-                    const bool s__ = (lb) < (la);                                                   \
-                    const float lo__ = s__ ? (lb) : (la), hi__ = s__ ? (la) : (lb);                 \
-                    const int clo__ = s__ ? (cb) : (ca), chi__ = s__ ? (ca) : (cb);                 \
-                    const bool klo__ = s__ ? (kb) : (ka), khi__ = s__ ? (ka) : (kb);                \
-                    la = lo__; lb = hi__; ca = clo__; cb = chi__; ka = klo__; kb = khi__;           \
-                } while (0)
-                CP_CE(l0, c0, k0, l1, c1, k1); CP_CE(l2, c2, k2, l3, c3, k3); CP_CE(l0, c0, k0, l2, c2, k2); CP_CE(l1, c1, k1, l3, c3, k3); CP_CE(l1, c1, k1, l2, c2, k2);
-                if (k3) st.push(CpEntry{(unsigned)c3, __float_as_uint(l3)});
-                if (k2) st.push(CpEntry{(unsigned)c2, __float_as_uint(l2)});
-                if (k1) st.push(CpEntry{(unsigned)c1, __float_as_uint(l1)});
-                cur = k0 ? c0 : pop_live();
-            }
-            // ---- leaf step: the lanes that are at a leaf
-            const bool at_leaf = cur < 0 && cur != CP_SENT;
-            if (__builtin_amdgcn_ballot_w64(at_leaf) != 0ull) {
-                if (at_leaf) {
-                    const int code = ~cur;
-                    if (COUNT) nleaf += 1;
-                    cp_test_record(b, leaf_slot(code), leaf_is_tri(code), p, lim2, best2, best_prim, bp);
-                    cut = __builtin_fminf(best2, lim2);
-                    cur = pop_live();
-                }
-            }
-        }
+        point_walk<COUNT>(b, st, m, p, p, start, lim2, nbox, nleaf, [&](int code) {      // (the first cut is lim2: best2 starts at +inf)
+            cp_test_record(b, leaf_slot(code), leaf_is_tri(code), p, lim2, best2, best_prim, bp);
+            return __builtin_fminf(best2, lim2);
+        });
         if (live) cp_store(a, q, best2, best_prim, bp, nbox, nleaf, COUNT);
         if constexpr (SIGNED) { if (live) sd_store(a, q, p, best_prim, bp); }
         if (st.overflow) n_over++;
     }
-    n_over = wave_sum(n_over);
-    if (lane == 0 && n_over && a.ctr) atomicAdd(&a.ctr->stack_overflow, n_over);
+    point_walk_count_overflow(n_over, lane, a.ctr);
 }
 
 // `n` queries in chunks of `chunk` on the context's stream; every pointer is device memory (or null)
@@ -252,15 +180,9 @@ static int query_closest_point(tirt_ctx *c, const char *fn, bool sgn, const floa
     if (n == 0) return TIRT_OK;
     TIRT_REQUIRE(points, f + "null points");
     TIRT_REQUIRE(!sgn || out_sd, f + "null out_sd");
-    if (int rc = require_device_ptr(c, points, (f + "points").c_str())) return rc;
-    if (dmax) if (int rc = require_device_ptr(c, dmax, (f + "dmax").c_str())) return rc;
-    if (out_d2) if (int rc = require_device_ptr(c, out_d2, (f + "out_d2").c_str())) return rc;
-    if (out_prim) if (int rc = require_device_ptr(c, out_prim, (f + "out_prim").c_str())) return rc;
-    if (out_point) if (int rc = require_device_ptr(c, out_point, (f + "out_point").c_str())) return rc;
-    if (out_uv) if (int rc = require_device_ptr(c, out_uv, (f + "out_uv").c_str())) return rc;
-    if (sgn) if (int rc = require_device_ptr(c, out_sd, (f + "out_sd").c_str())) return rc;
     const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
-    if (want_counts) if (int rc = require_device_ptr(c, counts, (f + "counts").c_str())) return rc;
+    if (int rc = require_device_ptrs(c, f, {{points, "points"}, {dmax, "dmax"}, {out_d2, "out_d2"}, {out_prim, "out_prim"}, {out_point, "out_point"}, {out_uv, "out_uv"},
+                                            {sgn ? out_sd : nullptr, "out_sd"}, {want_counts ? counts : nullptr, "counts"}})) return rc;
     const int chunk = (int)(n < (int64_t)c->query_chunk ? n : (int64_t)c->query_chunk);
     if (int rc = query_begin(c, stream)) return rc;
     if (sgn) if (int rc = sd_table_ensure(c, stack_size)) return rc;      // (on the context's stream, after the caller's work: no host sync)

@@ -552,6 +552,13 @@ int multi_hit_chunk(tirt_ctx *c, const MultiHitShape &shape, const float4 *rec, 
 // what the entry points that take caller-owned device memory share (tirt_query.hip): the pointer check, the check of the caller's stream ("... (`what` cannot be
 // captured)"), the first checks of every query, and the two events that order the context's stream after and before the caller's
 int require_device_ptr(tirt_ctx *c, const void *p, const char *what);
+// ... of a call's arrays in the order given, as "`prefix``name`": a null pointer is an array the caller left out and is skipped; the first refusal is returned
+struct NamedPtr { const void *p; const char *name; };
+inline int require_device_ptrs(tirt_ctx *c, const std::string &prefix, std::initializer_list<NamedPtr> ptrs)
+{
+    for (const NamedPtr &e : ptrs) if (e.p) if (int rc = require_device_ptr(c, e.p, (prefix + e.name).c_str())) return rc;
+    return TIRT_OK;
+}
 int require_caller_stream(tirt_ctx *c, const std::string &fn, void *stream, const char *what);
 int query_common_checks(tirt_ctx *c, const char *fn, const char *count, int64_t n, int stack_size, int flags);
 int query_begin(tirt_ctx *c, void *stream);

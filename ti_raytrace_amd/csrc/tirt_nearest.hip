@@ -9,24 +9,20 @@
 // the list.  N is a set and the list the first k of a total order on (D2, prim): neither depends on the order of the visits, so the walk returns the
 // scan's bits if and only if it never skips a primitive that would have been accepted.
 //
-// THE WALK is k_cp_walk's (tirt_closest_point.hip), text for text where it can be: a wave is a block (no barrier anywhere), lane l holds query base + l and
-// the blocks stride over the chunk; a node visit decodes the four children's planes, forms lb2 with the margin of PointMargin (CP_AXIS_GAP, CP_EACH_CHILD,
-// tirt_point_walk.h), drops empty slots and children with lb2 > cut, sorts the rest (five compare-exchanges), descends into the nearest and pushes the
-// others far to near WITH their lb2 into PointStack<CpEntry>; a popped entry is tested against the cut of that moment again.  What differs is the cut:
+// THE WALK is point_walk (tirt_point_walk.h), as k_cp_walk's: lo == hi == the query point, the margin of PointMargin, PointStack<CpEntry>.  THE CUT is the list's:
 //     cut = lim2                                   while the list has room (its threshold is "nothing", D2 = +inf)
 //     cut = min(lim2, D2 of the worst entry)       once the list holds k
 //     cut = lim2                                   always under COUNT_ALL (the caller wants |N|: every element of N has to be met)
-// WHY THE CULL IS CONSERVATIVE: the head of tirt_point_walk.h, unchanged.  A subtree is skipped on lb2 > cut only, never on equality, and lb2 <= D2 holds
-// for every primitive below a node: a skipped subtree holds only primitives with D2 > cut.  Such a primitive is no element of N (cut <= lim2), or sorts
-// behind the worst entry of a full list whatever its id (cut = that entry's D2, and the threshold only ever moves forward).  A primitive whose D2 EQUALS
-// the threshold's is below no skipped node; it joins if its id is smaller (cp_accept).
+// The leaf offers the record to the set and the list (nn_offer) and returns that.  The argument of tirt_point_walk.h holds with it: a skipped subtree holds
+// only primitives with D2 > cut, and such a primitive is no element of N (cut <= lim2), or sorts behind the worst entry of a full list whatever its id
+// (cut = that entry's D2, and the threshold only ever moves forward).  A primitive whose D2 EQUALS the threshold's is below no skipped node; it joins if
+// its id is smaller (cp_accept).
 // The walk starts at root_qcode, as k_cp_walk does (every analytic sphere is below it), and never enters the chain nodes at far_qcode: a leaf is met at
 // most once, so no primitive appears twice in a list or in the count.  Spot and laser leaves are reached and skipped (a NaN D2).  A query with a NaN or
 // infinite coordinate, or a negative or NaN bound, has N = {}: it does not walk.
 // THE LIST lives in the context's chunk scratch as [entry][query] (8 bytes per entry: a wave's access to entry e is contiguous) with its threshold in
 // registers; per query the scratch holds 8 k bytes of list and 8 bytes of (entries held, |N|).  Chunks are max(256, query_chunk_rays / max(k, 1)) queries.
-// The stack is k_cp_walk's: 8-byte entries (child code, lb2), the first CP_LDS_DEPTH of a lane in LDS, the rest of stack_size in the context's spill
-// buffer (point_walk_launch_shape); an entry beyond stack_size is dropped and the query counted in DevCounters::stack_overflow (tirt_stats: TIRT_ERR_STACK).
+// An entry beyond stack_size is dropped and the query counted in DevCounters::stack_overflow (tirt_stats: TIRT_ERR_STACK).
 #include <string.h>
 #include "tirt_internal.h"
 #include "tirt_closest_point.h"
@@ -34,10 +30,6 @@
 #include "tirt_nearest.h"
 
 namespace tirt {
-
-constexpr int NN_WAVES_PER_CU = 20;          // persistent blocks per CU at most: what 8 KiB of LDS each admits (k_cp_walk's)
-
-typedef unsigned CpEntry __attribute__((ext_vector_type(2)));      // a stack entry: (child code, bits of lb2) -- k_cp_walk's
 
 struct NnArgs {
     BvhView bvh;
@@ -60,28 +52,6 @@ struct NnStore {
     TD void set(int e, const NnEntry c) const { p[(size_t)e * stride] = make_uint2(__float_as_uint(c.d2), (unsigned)c.prim); }
 };
 
-TD void nn_load_query(const NnArgs &a, int q, v3 &p, float &lim2)
-{
-    const float *r = a.points + (int64_t)q * a.point_stride;
-    p = V(r[0], r[1], r[2]);
-    lim2 = cp_limit2(a.dmax ? a.dmax[(int64_t)q * a.dmax_stride] : a.dmax_all);
-}
-
-// D2, Q, u, v of the record in `slot` and its primitive id: the kind comes from the caller (the leaf code's shape bit, or the primitive table).
-// cp_test_record's text (tirt_closest_point.hip) up to the acceptance, which is the list's here.
-TD CpPoint nn_record(const BvhView &b, int slot, bool is_tri, const v3 p, int &prim)
-{
-    const float4 *tp = b.tri + (size_t)slot * TRI_STRIDE;
-    const float4 ta = tp[0], tb = tp[1], tc = tp[2];
-    prim = __float_as_int(tc.w);
-    const v3 pa = V(ta.x, ta.y, ta.z);
-    CpPoint r; r.d2 = __int_as_float(0x7fc00000); r.q = V(0.0f, 0.0f, 0.0f); r.u = 0.0f; r.v = 0.0f;      // spot / laser: no surface, a NaN D2 is never accepted
-    if (is_tri) r = cp_triangle(p, pa, V(tb.x, tb.y, tb.z), V(tc.x, tc.y, tc.z));
-    const bool sph = !is_tri && (int)tb.y == SHAPE_SPHERE;
-    if (__builtin_amdgcn_ballot_w64(sph) != 0ull) { if (sph) r = cp_sphere(p, pa, tb.x); }
-    return r;
-}
-
 // a candidate against the set and the list: counts it if it is an element of N, inserts it if it sorts before the threshold
 TD void nn_offer(NnList &L, const NnStore &store, float d2, int prim, float lim2, int &count)
 {
@@ -95,13 +65,13 @@ __global__ __launch_bounds__(CP_BLOCK) void k_nn_scan(NnArgs a)
     const int q = blockIdx.x * CP_BLOCK + threadIdx.x;
     if (q >= a.n) return;
     v3 p; float lim2;
-    nn_load_query(a, q, p, lim2);
+    cp_load_query(a, q, p, lim2);
     NnList L(a.k);
     const NnStore store = {a.list + q, a.stride};
     int count = 0;
     for (int i = 0; i < a.n_prim; i++) {
         int prim;
-        const CpPoint r = nn_record(a.bvh, a.prim_slot[i], a.primitive[(size_t)i * PRI_VEC] == PRIMITIVE_TRI, p, prim);
+        const CpPoint r = cp_record(a.bvh, a.prim_slot[i], a.primitive[(size_t)i * PRI_VEC] == PRIMITIVE_TRI, p, prim);
         nn_offer(L, store, r.d2, prim, lim2, count);
     }
     a.meta[q] = make_int2(L.n, count);
@@ -121,78 +91,29 @@ __global__ __launch_bounds__(CP_BLOCK) void k_nn_walk(NnArgs a)
         const int q = base + lane;
         const bool live = q < a.n;
         v3 p = V(0.0f, 0.0f, 0.0f); float lim2 = -1.0f;
-        if (live) nn_load_query(a, q, p, lim2);
+        if (live) cp_load_query(a, q, p, lim2);
         NnList L(a.k);
         const NnStore store = {a.list + q, a.stride};
         int count = 0;
         const float inf = __int_as_float(0x7f800000);
-        const bool finite = absf(p.x) < inf && absf(p.y) < inf && absf(p.z) < inf;      // false for NaN and +-inf
+        const bool finite = CP_FINITE3(p, inf);
         const float m = pm.margin(b, p);
-        float cut = lim2;                       // min(thr_d2, lim2): the threshold starts at +inf
-        int cur = (live && finite && lim2 >= 0.0f) ? b.root_qcode : CP_SENT;
+        const int start = (live && finite && lim2 >= 0.0f) ? b.root_qcode : CP_SENT;
         PointStack<CpEntry> st(stk, a.spill, a.stack_size, lane);
         unsigned nbox = 0, nleaf = 0;
-        // the next entry that can still hold an acceptable primitive, or CP_SENT
-        auto pop_live = [&]() {
-            while (!st.empty()) { const CpEntry e = st.pop(); if (!(__uint_as_float(e.y) > cut)) return (int)e.x; }
-            return CP_SENT;
-        };
-
-        while (__builtin_amdgcn_ballot_w64(cur != CP_SENT) != 0ull) {
-            // ---- node step: the lanes that are at an inner node
-            if (cur >= 0) {
-                const uint4 *w = b.cnode + (size_t)cur * 4;
-                const uint4 q0 = w[0], q1 = w[1], q2 = w[2], q3 = w[3];
-                if (COUNT) nbox += 4;
-                constexpr float MISS = 3.0e38f;
-                int c0, c1, c2, c3; float l0, l1, l2, l3; bool k0, k1, k2, k3;
-                // kept: a child that is there and can still hold an acceptable primitive (never culled on equality).  The flag travels with the child
-                // through the sort, so a kept child whose lb2 overflowed to +inf (a query ~1e19 away, cut = +inf) sorts behind the dropped ones and is still pushed
-#define NN_BOX(i, X, Y, Z, code_)                                                                   \
-                do {                                                                                \
-                    const float ex__ = CP_AXIS_GAP(b, m, X, 0, p.x), ey__ = CP_AXIS_GAP(b, m, Y, 1, p.y), ez__ = CP_AXIS_GAP(b, m, Z, 2, p.z); \
-                    const float s__ = (ex__ * ex__ + ey__ * ey__) + ez__ * ez__;                    \
-                    c##i = (int)(code_);                                                            \
-                    k##i = (c##i != TR_EMPTY) && !(s__ > cut);                                      \
-                    l##i = k##i ? s__ : MISS;                                                       \
-                } while (0)
-                CP_EACH_CHILD(NN_BOX);
-#define NN_CE(la, ca, ka, lb, cb, kb)                                                               \
-                do {                                                                                \
-                    const bool s__ = (lb) < (la);                                                   \
-                    const float lo__ = s__ ? (lb) : (la), hi__ = s__ ? (la) : (lb);                 \
-                    const int clo__ = s__ ? (cb) : (ca), chi__ = s__ ? (ca) : (cb);                 \
-                    const bool klo__ = s__ ? (kb) : (ka), khi__ = s__ ? (ka) : (kb);                \
-                    la = lo__; lb = hi__; ca = clo__; cb = chi__; ka = klo__; kb = khi__;           \
-                } while (0)
-                NN_CE(l0, c0, k0, l1, c1, k1); NN_CE(l2, c2, k2, l3, c3, k3); NN_CE(l0, c0, k0, l2, c2, k2); NN_CE(l1, c1, k1, l3, c3, k3); NN_CE(l1, c1, k1, l2, c2, k2);
-                if (k3) st.push(CpEntry{(unsigned)c3, __float_as_uint(l3)});
-                if (k2) st.push(CpEntry{(unsigned)c2, __float_as_uint(l2)});
-                if (k1) st.push(CpEntry{(unsigned)c1, __float_as_uint(l1)});
-                cur = k0 ? c0 : pop_live();
-            }
-            // ---- leaf step: the lanes that are at a leaf
-            const bool at_leaf = cur < 0 && cur != CP_SENT;
-            if (__builtin_amdgcn_ballot_w64(at_leaf) != 0ull) {
-                if (at_leaf) {
-                    const int code = ~cur;
-                    if (COUNT) nleaf += 1;
-                    int prim;
-                    const CpPoint r = nn_record(b, leaf_slot(code), leaf_is_tri(code), p, prim);
-                    nn_offer(L, store, r.d2, prim, lim2, count);
-                    if (!COUNT_ALL) cut = __builtin_fminf(L.thr_d2, lim2);
-                    cur = pop_live();
-                }
-            }
-        }
+        point_walk<COUNT>(b, st, m, p, p, start, lim2, nbox, nleaf, [&](int code) {      // (the first cut is lim2: the threshold starts at +inf)
+            int prim;
+            const CpPoint r = cp_record(b, leaf_slot(code), leaf_is_tri(code), p, prim);
+            nn_offer(L, store, r.d2, prim, lim2, count);
+            return COUNT_ALL ? lim2 : __builtin_fminf(L.thr_d2, lim2);
+        });
         if (live) {
             a.meta[q] = make_int2(L.n, count);
             if (COUNT && a.counts) a.counts[q] = make_int2((int)nbox, (int)nleaf);
         }
         if (st.overflow) n_over++;
     }
-    n_over = wave_sum(n_over);
-    if (lane == 0 && n_over && a.ctr) atomicAdd(&a.ctr->stack_overflow, n_over);
+    point_walk_count_overflow(n_over, lane, a.ctr);
 }
 
 // thread (i, j): entry j of query i of the chunk into the caller's arrays (at query `base` + i); j == 0 also writes the count.  Q, u, v: cp_triangle /
@@ -216,11 +137,8 @@ __global__ void k_nn_resolve(NnArgs a, int64_t base, float *out_d2, int32_t *out
         if (out_point || out_uv) {
             const float *row = a.points + (int64_t)i * a.point_stride;
             const v3 p = V(row[0], row[1], row[2]);
-            const float4 *tp = a.bvh.tri + (size_t)a.prim_slot[prim] * TRI_STRIDE;
-            const float4 ta = tp[0], tb = tp[1], tc = tp[2];
-            const v3 pa = V(ta.x, ta.y, ta.z);
-            if (a.primitive[(size_t)prim * PRI_VEC] == PRIMITIVE_TRI) r = cp_triangle(p, pa, V(tb.x, tb.y, tb.z), V(tc.x, tc.y, tc.z));
-            else r = cp_sphere(p, pa, tb.x);      // (an entry of a list has a surface: a shape in it is a sphere)
+            int id;      // (prim again; an entry of a list has a surface: a shape in it is a sphere)
+            r = cp_record(a.bvh, a.prim_slot[prim], a.primitive[(size_t)prim * PRI_VEC] == PRIMITIVE_TRI, p, id);
         }
     }
     const int64_t at = g * a.k + j;
@@ -262,7 +180,7 @@ static int nn_chunks(tirt_ctx *c, const float *points, int64_t n, int64_t point_
     a.ctr = c->dev_counters.as<DevCounters>();
     // the walk's grid: a lane for every query of a chunk, as far as the stacks allow (the scan has no stack)
     int grid_max = 0;
-    if (!scan) if (int rc = point_walk_launch_shape(c, stack_size, NN_WAVES_PER_CU, ((int64_t)chunk + CP_BLOCK - 1) / CP_BLOCK, grid_max, a.spill)) return rc;
+    if (!scan) if (int rc = point_walk_launch_shape(c, stack_size, CP_WAVES_PER_CU, ((int64_t)chunk + CP_BLOCK - 1) / CP_BLOCK, grid_max, a.spill)) return rc;
     for (int64_t base = 0; base < n; base += chunk) {
         const int m = (int)(n - base < chunk ? n - base : chunk);
         a.n = m;
@@ -315,15 +233,9 @@ int tirt_query_nearest(tirt_ctx *c, const float *points, int64_t n, int64_t poin
     if (int rc = require_caller_stream(c, fn, stream, "queries")) return rc;
     if (n == 0) return TIRT_OK;
     TIRT_REQUIRE(points, f + "null points");
-    if (int rc = require_device_ptr(c, points, (f + "points").c_str())) return rc;
-    if (dmax) if (int rc = require_device_ptr(c, dmax, (f + "dmax").c_str())) return rc;
-    if (out_d2) if (int rc = require_device_ptr(c, out_d2, (f + "out_d2").c_str())) return rc;
-    if (out_prim) if (int rc = require_device_ptr(c, out_prim, (f + "out_prim").c_str())) return rc;
-    if (out_point) if (int rc = require_device_ptr(c, out_point, (f + "out_point").c_str())) return rc;
-    if (out_uv) if (int rc = require_device_ptr(c, out_uv, (f + "out_uv").c_str())) return rc;
-    if (out_count) if (int rc = require_device_ptr(c, out_count, (f + "out_count").c_str())) return rc;
     const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
-    if (want_counts) if (int rc = require_device_ptr(c, counts, (f + "counts").c_str())) return rc;
+    if (int rc = require_device_ptrs(c, f, {{points, "points"}, {dmax, "dmax"}, {out_d2, "out_d2"}, {out_prim, "out_prim"}, {out_point, "out_point"}, {out_uv, "out_uv"},
+                                            {out_count, "out_count"}, {want_counts ? counts : nullptr, "counts"}})) return rc;
     if (int rc = query_begin(c, stream)) return rc;
     if (int rc = nn_chunks(c, points, n, point_stride, dmax, dmax_stride, dmax_all, k, stack_size, flags, nn_chunk_of(c, n, k), out_d2, out_prim, out_point,
                            point_out_stride, out_uv, uv_stride, out_count, want_counts ? (int2 *)counts : nullptr)) return rc;

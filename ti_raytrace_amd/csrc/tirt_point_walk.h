@@ -1,11 +1,19 @@
-// tirt_point_walk.h -- what a walk of a POINT over the quantised 4-wide nodes `cnode` (BvhView) is made of, once, for k_cp_walk (tirt_closest_point.hip)
-// and k_sd_build (tirt_signed_distance.hip): the margin by which a child's decoded box is grown and the distance of a coordinate to it (PointMargin,
-// CP_AXIS_GAP), the stack of one lane (PointStack), and on the host the grid whose stacks fit (point_walk_grid, point_walk_launch_shape).
-// A wave is a block (CP_BLOCK lanes, no barrier anywhere): a lane holds one point and the blocks stride over the work.
+// tirt_point_walk.h -- the walk of a POINT, or of a small box, over the quantised 4-wide nodes `cnode` (BvhView), once.  Its users:
+//   k_cp_walk   (tirt_closest_point.hip)    point_walk with lo == hi == the query point; the cut is min(best D2, lim2)
+//   k_nn_walk   (tirt_nearest.hip)          point_walk with lo == hi == the query point; the cut is the list's threshold (lim2 alone under COUNT_ALL)
+//   k_tq_walk   (tirt_triangle_query.hip)   point_walk with [lo, hi] the query triangle's box; the cut is min(best D2, lim2)
+//   k_sd_build  (tirt_signed_distance.hip)  its own loop (it descends where the gap is 0, culls nothing and sorts nothing) over the same margin, gap and stack
+//   k_multi_hit (tirt_multi_hit.hip)        PointStack<int> and the grid sizing alone (a ray's walk)
+// Here: the margin by which a child's decoded box is grown and the distance of an interval to it (PointMargin, CP_BOX_GAP; CP_AXIS_GAP for a point), the
+// stack of one lane (PointStack), THE WALK (point_walk) with the end of its kernels (point_walk_count_overflow), what its kernels and their scans read
+// (cp_load_query, cp_finite3, cp_record), and on the host the grid whose stacks fit (point_walk_grid, point_walk_launch_shape).
+// A wave is a block (CP_BLOCK lanes, no barrier anywhere): a lane holds one query and the blocks stride over the work.
 //
-// WHY THE CULL IS CONSERVATIVE.  k_cp_walk skips a subtree on lb2 > cut only, never on equality, so it suffices that lb2 <= D2 holds, as computed fp32
+// WHY THE CULL IS CONSERVATIVE.  point_walk skips a subtree on lb2 > cut only, never on equality -- at a node (`kept`) and at a pop (pop_live) -- and the
+// cut a leaf returns only ever shrinks and is never below the D2 of a primitive that could still be accepted (each kernel's head says why for its cut).
+// So it suffices that lb2 <= D2 holds, as computed fp32
 // numbers, for every primitive t below the node.  (k_sd_build descends where lb2 == 0 and needs the same for D2 = 0: a triangle with a corner AT the
-// point.)  Write eps = 2^-24, E = the largest extent of the padded root box, C = E / 60000 = the largest cell,
+// point.  k_tq_walk's box in place of p: the head of tirt_triangle_query.h.)  Write eps = 2^-24, E = the largest extent of the padded root box, C = E / 60000 = the largest cell,
 // M = the largest coordinate magnitude among p and the scene, d = the distance from p to t.
 //  (1) The computed D2.  cp_triangle's Q is a vertex, or a + ab u with u in [0, 1] (AB, AC, BC: the region tests make numerator and denominator
 //      non-negative with numerator <= denominator, and a correctly rounded quotient keeps that), or (a + ab u) + ac v with u = vb den, v = vc den.
@@ -32,6 +40,7 @@
 //  gets a margin that swallows the boxes and its walk degenerates towards the scan, which is acceptable (no cut-off).
 #pragma once
 #include "tirt_internal.h"
+#include "tirt_closest_point.h"
 
 namespace tirt {
 
@@ -58,11 +67,13 @@ struct PointMargin {
     }
 };
 typedef _Float16 cp_h2v __attribute__((ext_vector_type(2)));
-// the distance of coordinate pk to the decoded planes of axis k of one child (dword W of its node), less the margin m_, never negative: 0 = inside the grown box
-#define CP_AXIS_GAP(b_, m_, W, k, pk)                                                               \
+// the distance between the interval [lo_, hi_] and the decoded planes of axis k of one child (dword W of its node), less the margin m_, never negative:
+// 0 = the interval meets the grown box on this axis.  THE gap expression: a point is the interval lo_ == hi_ == pk (CP_AXIS_GAP, k_sd_build's)
+#define CP_BOX_GAP(b_, m_, W, k, lo_, hi_)                                                          \
                 ({  const cp_h2v h__ = __builtin_bit_cast(cp_h2v, (unsigned)(W));                   \
                     const float mn__ = (b_).grid_min[k] + (float)h__.x * (b_).cell[k], mx__ = (b_).grid_min[k] + (float)h__.y * (b_).cell[k]; \
-                    maxf(maxf(mn__ - (pk), (pk) - mx__) - (m_), 0.0f); })
+                    maxf(maxf(mn__ - (hi_), (lo_) - mx__) - (m_), 0.0f); })
+#define CP_AXIS_GAP(b_, m_, W, k, pk) CP_BOX_GAP(b_, m_, W, k, pk, pk)
 // the four children of a node record q0 .. q3 (tirt_internal.h: dword 3c + a = the planes of child c on axis a, dwords 12 .. 15 = the codes): F(c, X, Y, Z, code) each
 #define CP_EACH_CHILD(F) F(0, q0.x, q0.y, q0.z, q3.x); F(1, q0.w, q1.x, q1.y, q3.y); F(2, q1.z, q1.w, q2.x, q3.z); F(3, q2.y, q2.z, q2.w, q3.w)
 
@@ -89,6 +100,104 @@ struct PointStack {
     }
     TD E pop() { sp--; return sp < CP_LDS_DEPTH ? lds[sp * CP_BLOCK + lane] : spill[(size_t)(sp - CP_LDS_DEPTH) * gthreads + gtid]; }      // (not of an empty stack)
 };
+
+// ---- THE WALK of k_cp_walk, k_nn_walk and k_tq_walk: best-first over `cnode` for the lane's query, whose exact box is [lo, hi] (a point: lo == hi) and
+// whose margin is m.  Node steps and leaf steps alternate behind wave ballots, each for the lanes that are at one (a wave is a block: no barrier).
+// A node visit decodes the four children's planes, forms lb2 = the sum over the axes of CP_BOX_GAP^2, drops empty slots and children with lb2 > cut,
+// sorts the rest (five compare-exchanges, as k_trace), descends into the nearest and pushes the others far to near WITH their lb2; a popped entry is
+// tested against the cut of that moment again (the cut shrinks fast: most entries are dead when they surface).  `leaf(code)` tests the record of a
+// leaf code and returns the cut that holds after it; the cut never grows.  `cur` is the start: root_qcode, or CP_SENT for a lane that does not walk.
+typedef unsigned CpEntry __attribute__((ext_vector_type(2)));      // a stack entry: (child code, bits of lb2)
+constexpr int CP_WAVES_PER_CU = 20;          // persistent blocks per CU at most, for all three: what 8 KiB of LDS each admits (k_cp_walk / k_nn_walk: their 59 .. 66 VGPRs would admit 32; k_tq_walk: its 102 .. 105 VGPRs run 16 at a time, the rest wait their turn)
+
+template <bool COUNT, class Leaf>
+TD void point_walk(const BvhView &b, PointStack<CpEntry> &st, const float m, const v3 lo, const v3 hi, int cur, float cut, unsigned &nbox, unsigned &nleaf, Leaf leaf)
+{
+    // the next entry that can still win, or CP_SENT
+    auto pop_live = [&]() {
+        while (!st.empty()) { const CpEntry e = st.pop(); if (!(__uint_as_float(e.y) > cut)) return (int)e.x; }
+        return CP_SENT;
+    };
+    while (__builtin_amdgcn_ballot_w64(cur != CP_SENT) != 0ull) {
+        // ---- node step: the lanes that are at an inner node
+        if (cur >= 0) {
+            const uint4 *w = b.cnode + (size_t)cur * 4;
+            const uint4 q0 = w[0], q1 = w[1], q2 = w[2], q3 = w[3];
+            if (COUNT) nbox += 4;
+            constexpr float MISS = 3.0e38f;
+            int c0, c1, c2, c3; float l0, l1, l2, l3; bool k0, k1, k2, k3;
+            // kept: a child that is there and can still win (never culled on equality).  The flag travels with the child through the sort, so
+            // a kept child whose lb2 overflowed to +inf (a query ~1e19 away, cut = +inf) sorts behind the dropped ones and is still pushed
+#define WALK_BOX(i, X, Y, Z, code_)                                                                   \
+            do {                                                                                    \
+                const float ex__ = CP_BOX_GAP(b, m, X, 0, lo.x, hi.x), ey__ = CP_BOX_GAP(b, m, Y, 1, lo.y, hi.y), ez__ = CP_BOX_GAP(b, m, Z, 2, lo.z, hi.z); \
+                const float s__ = (ex__ * ex__ + ey__ * ey__) + ez__ * ez__;                        \
+                c##i = (int)(code_);                                                                \
+                k##i = (c##i != TR_EMPTY) && !(s__ > cut);                                          \
+                l##i = k##i ? s__ : MISS;                                                           \
+            } while (0)
+            CP_EACH_CHILD(WALK_BOX);
+#undef WALK_BOX
+#define WALK_CE(la, ca, ka, lb, cb, kb)                                                               \
+            do {                                                                                    \
+                const bool s__ = (lb) < (la);                                                       \
+                const float lo__ = s__ ? (lb) : (la), hi__ = s__ ? (la) : (lb);                     \
+                const int clo__ = s__ ? (cb) : (ca), chi__ = s__ ? (ca) : (cb);                     \
+                const bool klo__ = s__ ? (kb) : (ka), khi__ = s__ ? (ka) : (kb);                    \
+                la = lo__; lb = hi__; ca = clo__; cb = chi__; ka = klo__; kb = khi__;               \
+            } while (0)
+            WALK_CE(l0, c0, k0, l1, c1, k1); WALK_CE(l2, c2, k2, l3, c3, k3); WALK_CE(l0, c0, k0, l2, c2, k2); WALK_CE(l1, c1, k1, l3, c3, k3); WALK_CE(l1, c1, k1, l2, c2, k2);
+#undef WALK_CE
+            if (k3) st.push(CpEntry{(unsigned)c3, __float_as_uint(l3)});
+            if (k2) st.push(CpEntry{(unsigned)c2, __float_as_uint(l2)});
+            if (k1) st.push(CpEntry{(unsigned)c1, __float_as_uint(l1)});
+            cur = k0 ? c0 : pop_live();
+        }
+        // ---- leaf step: the lanes that are at a leaf
+        const bool at_leaf = cur < 0 && cur != CP_SENT;
+        if (__builtin_amdgcn_ballot_w64(at_leaf) != 0ull) {
+            if (at_leaf) {
+                if (COUNT) nleaf += 1;
+                cut = leaf(~cur);
+                cur = pop_live();
+            }
+        }
+    }
+}
+
+// the end of a walk kernel: the queries of this wave that lost a stack entry, in one atomic (tirt_stats: TIRT_ERR_STACK)
+TD void point_walk_count_overflow(unsigned long long n_over, int lane, DevCounters *ctr)
+{
+    n_over = wave_sum(n_over);
+    if (lane == 0 && n_over && ctr) atomicAdd(&ctr->stack_overflow, n_over);
+}
+
+// ---- what the walks and their scans read: the query (CpArgs, NnArgs: the same fields), the test of its coordinates, and a primitive's record
+template <class Args>
+TD void cp_load_query(const Args &a, int q, v3 &p, float &lim2)
+{
+    const float *r = a.points + (int64_t)q * a.point_stride;
+    p = V(r[0], r[1], r[2]);
+    lim2 = cp_limit2(a.dmax ? a.dmax[(int64_t)q * a.dmax_stride] : a.dmax_all);
+}
+// false for NaN and +-inf: such a query finds nothing by the definition (every D2 is NaN or +inf) and does not walk.  One text in two forms, each where the
+// compiler keeps what it made of the copies this replaces (profiles/shared_walk_isa.txt): in place in k_cp_walk / k_nn_walk, a call in tq_load_query
+#define CP_FINITE3(p_, inf_) (absf((p_).x) < (inf_) && absf((p_).y) < (inf_) && absf((p_).z) < (inf_))
+TD bool cp_finite3(const v3 p) { const float inf = __int_as_float(0x7f800000); return CP_FINITE3(p, inf); }
+// D2, Q, u, v of the record in `slot` against p, and its primitive id: the kind comes from the caller (the leaf code's shape bit, or the primitive table).
+// The sphere branch (a square root and a division) sits behind a wave ballot, as in trace_leaf_step
+TD CpPoint cp_record(const BvhView &b, int slot, bool is_tri, const v3 p, int &prim)
+{
+    const float4 *tp = b.tri + (size_t)slot * TRI_STRIDE;
+    const float4 ta = tp[0], tb = tp[1], tc = tp[2];
+    prim = __float_as_int(tc.w);
+    const v3 pa = V(ta.x, ta.y, ta.z);
+    CpPoint r; r.d2 = __int_as_float(0x7fc00000); r.q = V(0.0f, 0.0f, 0.0f); r.u = 0.0f; r.v = 0.0f;      // spot / laser: no surface, a NaN D2 is never accepted
+    if (is_tri) r = cp_triangle(p, pa, V(tb.x, tb.y, tb.z), V(tc.x, tc.y, tc.z));
+    const bool sph = !is_tri && (int)tb.y == SHAPE_SPHERE;
+    if (__builtin_amdgcn_ballot_w64(sph) != 0ull) { if (sph) r = cp_sphere(p, pa, tb.x); }
+    return r;
+}
 
 // ---- the host's side of the same stack: how many blocks, and the tails they need.  THE invariant between this and PointStack: `spill` holds
 // (stack_size - CP_LDS_DEPTH) * grid * CP_BLOCK entries, and the kernel is launched with at most `grid` blocks of CP_BLOCK threads.

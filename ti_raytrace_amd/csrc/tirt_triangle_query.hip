@@ -8,13 +8,10 @@
 // the answer is the minimum of a total order on (D2, prim): the walk returns the scan's bits if and only if it never skips a primitive that would have
 // been accepted.
 //
-// THE WALK is k_cp_walk's (tirt_closest_point.hip), with a box where that has a point: a wave is a block (no barrier anywhere), lane l holds query
-// base + l and the blocks stride over the chunk.  A node visit decodes the four children's planes, forms lb2 = the sum over the axes of
-// max(max(mn - hi, lo - mx) - m, 0)^2 with [lo, hi] the exact box of the query triangle and m the largest of PointMargin's margins of its three vertices,
-// drops empty slots and children with lb2 > cut (cut = min(best D2 so far, lim2)), sorts the rest (five compare-exchanges), descends into the nearest
-// and pushes the others far to near WITH their lb2; a popped entry is tested against the cut of that moment again.  Node steps and leaf steps alternate
-// behind wave ballots, each for the lanes that are at one.  The stack is PointStack<CpEntry> (tirt_point_walk.h): 16 entries of a lane in LDS, the rest
-// of its stack_size in the context's spill buffer; an entry beyond stack_size is dropped and the query counted in DevCounters::stack_overflow.
+// THE WALK is point_walk (tirt_point_walk.h), with a box where k_cp_walk has a point: [lo, hi] is the exact box of the query triangle and m the largest of
+// PointMargin's margins of its three vertices; lane l of a block holds query base + l and the blocks stride over the chunk.  THE CUT is min(best D2 so
+// far, lim2): the leaf tests the record through tq_test_record and returns it.  The stack is PointStack<CpEntry>; an entry beyond stack_size is dropped and
+// the query counted in DevCounters::stack_overflow.
 // Culling is on lb2 > cut alone, never on equality: with the answer at D2 = 0 every subtree whose grown box meets the query's box (lb2 == 0) is still
 // visited, because a primitive of a smaller id may tie at 0.  A deep penetration costs that many leaf tests.
 // Analytic spheres, spot and laser leaves are reached and skipped (a NaN D2 is never accepted).  A query with a NaN or infinite coordinate finds nothing
@@ -29,10 +26,6 @@
 #include "tirt_point_walk.h"
 
 namespace tirt {
-
-constexpr int TQ_WAVES_PER_CU = 20;          // persistent blocks per CU at most: what 8 KiB of LDS each admits (k_cp_walk's figure; the 102 VGPRs admit 16 at a time)
-
-typedef unsigned CpEntry __attribute__((ext_vector_type(2)));      // a stack entry: (child code, bits of lb2), as k_cp_walk's
 
 struct TqArgs {
     BvhView bvh;
@@ -49,15 +42,6 @@ struct TqArgs {
 struct TqQuery { v3 p0, p1, p2; float lim2; };
 struct TqBest { float d2; int prim, code; v3 P, Q; };
 
-// the distance between the interval [lo_, hi_] and the decoded planes of axis k of one child (dword W of its node), less the margin m_, never negative:
-// 0 = the query's box meets the grown box on this axis
-#define TQ_AXIS_GAP(b_, m_, W, k, lo_, hi_)                                                         \
-                ({  const cp_h2v h__ = __builtin_bit_cast(cp_h2v, (unsigned)(W));                   \
-                    const float mn__ = (b_).grid_min[k] + (float)h__.x * (b_).cell[k], mx__ = (b_).grid_min[k] + (float)h__.y * (b_).cell[k]; \
-                    maxf(maxf(mn__ - (hi_), (lo_) - mx__) - (m_), 0.0f); })
-
-TD bool tq_finite3(const v3 p, const float inf) { return absf(p.x) < inf && absf(p.y) < inf && absf(p.z) < inf; }      // false for NaN and +-inf
-
 // a query with a NaN or infinite coordinate finds nothing by the definition, in the scan as in the walk: its lim2 is that of a negative bound
 TD TqQuery tq_load_query(const TqArgs &a, int q)
 {
@@ -65,8 +49,7 @@ TD TqQuery tq_load_query(const TqArgs &a, int q)
     TqQuery t;
     t.p0 = V(r[0], r[1], r[2]); t.p1 = V(r[3], r[4], r[5]); t.p2 = V(r[6], r[7], r[8]);
     t.lim2 = cp_limit2(a.dmax ? a.dmax[(int64_t)q * a.dmax_stride] : a.dmax_all);
-    const float inf = __int_as_float(0x7f800000);
-    if (!(tq_finite3(t.p0, inf) && tq_finite3(t.p1, inf) && tq_finite3(t.p2, inf))) t.lim2 = -1.0f;
+    if (!(cp_finite3(t.p0) && cp_finite3(t.p1) && cp_finite3(t.p2))) t.lim2 = -1.0f;
     return t;
 }
 
@@ -128,65 +111,17 @@ __global__ __launch_bounds__(CP_BLOCK) void k_tq_walk(TqArgs a)
         const v3 lo = V(minf(minf(t.p0.x, t.p1.x), t.p2.x), minf(minf(t.p0.y, t.p1.y), t.p2.y), minf(minf(t.p0.z, t.p1.z), t.p2.z));
         const v3 hi = V(maxf(maxf(t.p0.x, t.p1.x), t.p2.x), maxf(maxf(t.p0.y, t.p1.y), t.p2.y), maxf(maxf(t.p0.z, t.p1.z), t.p2.z));
         const float m = maxf(maxf(pm.margin(b, t.p0), pm.margin(b, t.p1)), pm.margin(b, t.p2));      // rho_p over all three vertices
-        float cut = t.lim2;                     // min(best D2, lim2): the best starts at +inf
-        int cur = (live && t.lim2 >= 0.0f) ? b.root_qcode : CP_SENT;      // (a negative or NaN bound, a query that is not finite: no walk)
+        const int start = (live && t.lim2 >= 0.0f) ? b.root_qcode : CP_SENT;      // (a negative or NaN bound, a query that is not finite: no walk)
         PointStack<CpEntry> st(stk, a.spill, a.stack_size, lane);
         unsigned nbox = 0, nleaf = 0;
-        // the next entry that can still win, or CP_SENT
-        auto pop_live = [&]() {
-            while (!st.empty()) { const CpEntry e = st.pop(); if (!(__uint_as_float(e.y) > cut)) return (int)e.x; }
-            return CP_SENT;
-        };
-
-        while (__builtin_amdgcn_ballot_w64(cur != CP_SENT) != 0ull) {
-            // ---- node step: the lanes that are at an inner node
-            if (cur >= 0) {
-                const uint4 *w = b.cnode + (size_t)cur * 4;
-                const uint4 q0 = w[0], q1 = w[1], q2 = w[2], q3 = w[3];
-                if (COUNT) nbox += 4;
-                constexpr float MISS = 3.0e38f;
-                int c0, c1, c2, c3; float l0, l1, l2, l3; bool k0, k1, k2, k3;
-                // kept: a child that is there and can still win (never culled on equality); the flag travels with the child through the sort
-#define TQ_BOX(i, X, Y, Z, code_)                                                                   \
-                do {                                                                                \
-                    const float ex__ = TQ_AXIS_GAP(b, m, X, 0, lo.x, hi.x), ey__ = TQ_AXIS_GAP(b, m, Y, 1, lo.y, hi.y), ez__ = TQ_AXIS_GAP(b, m, Z, 2, lo.z, hi.z); \
-                    const float s__ = (ex__ * ex__ + ey__ * ey__) + ez__ * ez__;                    \
-                    c##i = (int)(code_);                                                            \
-                    k##i = (c##i != TR_EMPTY) && !(s__ > cut);                                      \
-                    l##i = k##i ? s__ : MISS;                                                       \
-                } while (0)
-                CP_EACH_CHILD(TQ_BOX);
-#define TQ_CE(la, ca, ka, lb, cb, kb)                                                               \
-                do {                                                                                \
-                    const bool s__ = (lb) < (la);                                                   \
-                    const float lo__ = s__ ? (lb) : (la), hi__ = s__ ? (la) : (lb);                 \
-                    const int clo__ = s__ ? (cb) : (ca), chi__ = s__ ? (ca) : (cb);                 \
-                    const bool klo__ = s__ ? (kb) : (ka), khi__ = s__ ? (ka) : (kb);                \
-                    la = lo__; lb = hi__; ca = clo__; cb = chi__; ka = klo__; kb = khi__;           \
-                } while (0)
-                TQ_CE(l0, c0, k0, l1, c1, k1); TQ_CE(l2, c2, k2, l3, c3, k3); TQ_CE(l0, c0, k0, l2, c2, k2); TQ_CE(l1, c1, k1, l3, c3, k3); TQ_CE(l1, c1, k1, l2, c2, k2);
-                if (k3) st.push(CpEntry{(unsigned)c3, __float_as_uint(l3)});
-                if (k2) st.push(CpEntry{(unsigned)c2, __float_as_uint(l2)});
-                if (k1) st.push(CpEntry{(unsigned)c1, __float_as_uint(l1)});
-                cur = k0 ? c0 : pop_live();
-            }
-            // ---- leaf step: the lanes that are at a leaf
-            const bool at_leaf = cur < 0 && cur != CP_SENT;
-            if (__builtin_amdgcn_ballot_w64(at_leaf) != 0ull) {
-                if (at_leaf) {
-                    const int code = ~cur;
-                    if (COUNT) nleaf += 1;
-                    tq_test_record(b, leaf_slot(code), leaf_is_tri(code), t, o);
-                    cut = __builtin_fminf(o.d2, t.lim2);
-                    cur = pop_live();
-                }
-            }
-        }
+        point_walk<COUNT>(b, st, m, lo, hi, start, t.lim2, nbox, nleaf, [&](int code) {      // (the first cut is lim2: the best starts at +inf)
+            tq_test_record(b, leaf_slot(code), leaf_is_tri(code), t, o);
+            return __builtin_fminf(o.d2, t.lim2);
+        });
         if (live) tq_store(a, q, o, nbox, nleaf, COUNT);
         if (st.overflow) n_over++;
     }
-    n_over = wave_sum(n_over);
-    if (lane == 0 && n_over && a.ctr) atomicAdd(&a.ctr->stack_overflow, n_over);
+    point_walk_count_overflow(n_over, lane, a.ctr);
 }
 
 // `n` queries in chunks of `chunk` on the context's stream; every pointer is device memory (or null)
@@ -204,7 +139,7 @@ static int tq_chunks(tirt_ctx *c, const float *tris, int64_t n, int64_t tri_stri
     a.ctr = c->dev_counters.as<DevCounters>();
     // the walk's grid: a lane for every query of a chunk, as far as the stacks allow (the scan has no stack)
     int grid_max = 0;
-    if (!scan) if (int rc = point_walk_launch_shape(c, stack_size, TQ_WAVES_PER_CU, ((int64_t)(n < chunk ? n : chunk) + CP_BLOCK - 1) / CP_BLOCK, grid_max, a.spill)) return rc;
+    if (!scan) if (int rc = point_walk_launch_shape(c, stack_size, CP_WAVES_PER_CU, ((int64_t)(n < chunk ? n : chunk) + CP_BLOCK - 1) / CP_BLOCK, grid_max, a.spill)) return rc;
     for (int64_t base = 0; base < n; base += chunk) {
         const int m = (int)(n - base < chunk ? n - base : chunk);
         a.n = m;
@@ -251,14 +186,9 @@ int tirt_query_mesh_distance(tirt_ctx *c, const float *tris, int64_t n, int64_t 
     if (int rc = require_caller_stream(c, fn, stream, "queries")) return rc;
     if (n == 0) return TIRT_OK;
     TIRT_REQUIRE(tris, f + "null tris");
-    if (int rc = require_device_ptr(c, tris, (f + "tris").c_str())) return rc;
-    if (dmax) if (int rc = require_device_ptr(c, dmax, (f + "dmax").c_str())) return rc;
-    if (out_d2) if (int rc = require_device_ptr(c, out_d2, (f + "out_d2").c_str())) return rc;
-    if (out_prim) if (int rc = require_device_ptr(c, out_prim, (f + "out_prim").c_str())) return rc;
-    if (out_code) if (int rc = require_device_ptr(c, out_code, (f + "out_code").c_str())) return rc;
-    if (out_points) if (int rc = require_device_ptr(c, out_points, (f + "out_points").c_str())) return rc;
     const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
-    if (want_counts) if (int rc = require_device_ptr(c, counts, (f + "counts").c_str())) return rc;
+    if (int rc = require_device_ptrs(c, f, {{tris, "tris"}, {dmax, "dmax"}, {out_d2, "out_d2"}, {out_prim, "out_prim"}, {out_code, "out_code"}, {out_points, "out_points"},
+                                            {want_counts ? counts : nullptr, "counts"}})) return rc;
     const int chunk = (int)(n < (int64_t)c->query_chunk ? n : (int64_t)c->query_chunk);
     if (int rc = query_begin(c, stream)) return rc;
     if (int rc = tq_chunks(c, tris, n, tri_stride, dmax, dmax_stride, dmax_all, stack_size, flags, chunk, out_d2, out_prim, out_code, out_points,
