@@ -1070,6 +1070,29 @@ int tirt_trace_timeline(tirt_ctx *ctx, uint64_t *out, int max_waves, int *n_wave
  * out[9] = rays that took more than one, out[10] = lane slots of the waves' trips (64 x the leaf steps of each wave's slowest ray), out[11] = rays that took more
  * than two.  Waits for pending work.  (No reference counterpart: bench / tests.) */
 int tirt_primary_beam_stats(tirt_ctx *ctx, uint64_t out[12]);
+/* The candidate lists themselves, for the tests that hold them to their definition (the header of csrc/tirt_pvb.hip; tests/beam_lists_expected.py).  Diagnostic,
+ * no reference counterpart.
+ * tirt_primary_beam_lists_download makes the lists of the current (build, camera, film) exactly as a batch that uses them would (pvb_prepare: nothing happens when
+ *   they stand already), waits for the stream and copies out the set batches read, in LOCAL pixel order (the order of the context's tiles):
+ *     count[P]               leaves on the pixel's list, -1: the pixel has no list (its camera rays are k_trace's)
+ *     cand[PVB_CMAX][P][2]   entry a of pixel k at (a * P + k) * 2: the leaf's child code as the 4-wide nodes hold it (tirt_wide_tree_download) and the bits of
+ *                            `nr`, the least distance at which a ray of the pixel can reach the leaf; entries a >= count[k] are not defined
+ *     bound[P]               up to this distance the list is complete; 1e6 (the distance of a miss) for a list made without a bound
+ *   count, cand and bound are given together or all NULL; with NULL arrays only info is filled: info[0] = P (the context's local pixels), info[1] = PVB_CMAX,
+ *   info[2] = 1 if the context has lists that batches would use and at least one pixel has one, else 0 -- option "primary_beams" off, a scene with cut-outs, an empty
+ *   film and no list memory all give 0 and count[k] = -1 for every k (cand and bound are then not written); a camera further than 8 extents from the scene gives 0
+ *   with the arrays of the lists it was refused --, info[3] = pixels that have a list.  If the call has to make the lists it COUNTS AS A LIST BUILD in
+ *   tirt_primary_beam_stats (out[5], out[6]), and it resets the counters out[0..4] as every build does.  Waits for pending work.
+ *   TIRT_ERR_ARG, and nothing is changed or written: null ctx or info, only some of the three arrays, no scene / LBVH not built, camera not set, film not created.
+ * tirt_kat_primary_list_walk: known-answer entry for the walk of one camera ray over its pixel's list.  Row r: the ray of local pixel local_pixel[r] with jitter
+ *   (jx[r], jy[r]) is formed as a batch forms it (camera_ray_direction) and handed to pvb_walk_list -- the function the list pass and PT_RGB's fused first step call
+ *   -- on the context's current lists (made first if they do not stand, as above).  One launch of 64-thread blocks, row r on lane r % 64 of block r / 64, so the
+ *   caller's order decides which rays share a wave; the padding lanes of the last block make the call as the padding threads of a batch do.
+ *   out, 9 words per row: direction (3), resolved (1.0f: the hit is k_trace's; 0.0f: the ray would be handed to k_trace), t, u, v, the primitive as its bits (-1: none),
+ *   and the ray's leaf steps as a float.  A row that is not resolved still reports the best hit of the entries it walked.
+ *   TIRT_ERR_ARG as above, and: out_stride < 9, a local pixel outside [0, P), a context without lists (info[2] = 0 for any reason but the far camera). */
+int tirt_primary_beam_lists_download(tirt_ctx *ctx, int32_t *count, int32_t *cand, float *bound, int32_t info[4]);
+int tirt_kat_primary_list_walk(tirt_ctx *ctx, int n, const int32_t *local_pixel, const float *jx, const float *jy, float *out, int out_stride);
 
 /* Fills *out.  Returns TIRT_ERR_STACK (with *out filled in) when stack_overflow > 0: rays dropped subtrees, what was
  * rendered since the last tirt_stats_reset is wrong -- the reference prints "overflow, need larger stack" (Scene.py:741). */

@@ -30,10 +30,12 @@ def _sub(arrs, idx):
     return [a[idx] for a in arrs]
 
 
-def hit_sets(vertex_np, primitive_np, material_np, shape_np, compact, rays, tmax=None, textures=(), flags=()):
-    """-> dict: t, u, v [n, P] float32 and prim, leaf [n, P] in H's order, padded with 1e6 / 0 / -1; count [n] = |H|.  tmax: None, a scalar or [n]"""
+def hit_sets(vertex_np, primitive_np, material_np, shape_np, compact, rays, tmax=None, textures=(), flags=(), prims=None):
+    """-> dict: t, u, v [n, P] float32 and prim, leaf [n, P] in H's order, padded with 1e6 / 0 / -1; count [n] = |H|.  tmax: None, a scalar or [n].
+    prims: only these primitives are asked (P = their number; the caller has shown that no ray can hit another one); `prim` still holds scene indices"""
     rays = np.ascontiguousarray(rays, f).reshape(-1, 6)
-    n, P = rays.shape[0], primitive_np.shape[0]
+    sel = np.arange(primitive_np.shape[0]) if prims is None else np.asarray(prims, np.int64)
+    n, P = rays.shape[0], sel.shape[0]
     o = [rays[:, k].copy() for k in range(3)]; d = [rays[:, 3 + k].copy() for k in range(3)]
     tm = np.full(n, np.inf, f) if tmax is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, f), (n,)))
     with np.errstate(invalid="ignore"):
@@ -42,7 +44,7 @@ def hit_sets(vertex_np, primitive_np, material_np, shape_np, compact, rays, tmax
     leaf = ce.leaf_indices(compact)
     par = parents(compact)
     T = np.full((n, P), np.inf, f); U = np.zeros((n, P), f); Vv = np.zeros((n, P), f)
-    for p in range(P):
+    for q, p in enumerate(sel.tolist()):
         kind, idx, mat = (int(x) for x in primitive_np[p])
         if kind == SCD.PRIMITIVE_TRI:
             V = vertex_np[idx:idx + 3]
@@ -69,15 +71,15 @@ def hit_sets(vertex_np, primitive_np, material_np, shape_np, compact, rays, tmax
             tu = ((Tx[0, 0] * a + Tx[1, 0] * u).astype(f) + Tx[2, 0] * v).astype(f)
             tv = ((Tx[0, 1] * a + Tx[1, 1] * u).astype(f) + Tx[2, 1] * v).astype(f)
             cand &= ce.tex_alpha(textures[tex][0], textures[tex][1], tu, tv) >= ce.CUTOFF
-        T[:, p] = np.where(cand, t, f(np.inf)); U[:, p] = u; Vv[:, p] = v
-    negleaf = np.broadcast_to(-leaf[None, :], (n, P))
+        T[:, q] = np.where(cand, t, f(np.inf)); U[:, q] = u; Vv[:, q] = v
+    negleaf = np.broadcast_to(-leaf[sel][None, :], (n, P))
     order = np.lexsort((negleaf, T), axis=1)                      # t ascending, then the larger leaf first
     rows = np.arange(n)[:, None]
     Ts = T[rows, order]
     inH = np.isfinite(Ts)
     return {"t": np.where(inH, Ts, INF_VALUE).astype(f), "u": np.where(inH, U[rows, order], f(0.0)).astype(f),
-            "v": np.where(inH, Vv[rows, order], f(0.0)).astype(f), "prim": np.where(inH, order, -1).astype(np.int32),
-            "leaf": np.where(inH, leaf[order], -1).astype(np.int64), "count": inH.sum(axis=1).astype(np.int32)}
+            "v": np.where(inH, Vv[rows, order], f(0.0)).astype(f), "prim": np.where(inH, sel[order], -1).astype(np.int32),
+            "leaf": np.where(inH, leaf[sel][order], -1).astype(np.int64), "count": inH.sum(axis=1).astype(np.int32)}
 
 
 def first_k(h, k):

@@ -102,7 +102,8 @@ KAT_ALPHA_IN, KAT_ALPHA_OUT = 3, 2                                  # words per 
 KAT_MAPS_IN, KAT_MAPS_OUT = 3, 8                                    # words per row of tirt_kat_material_maps
 HITS_MAX = 64                                                       # TIRT_HITS_MAX: the largest k of tirt_query_hits
 NEAREST_MAX = 64                                                    # TIRT_NEAREST_MAX: the largest k of tirt_query_nearest
-KAT_STEP_IN, KAT_STEP_OUT = 23, 28                                  # words per row of tirt_kat_shade_step
+KAT_LIST_WALK_OUT = 9                                               # words per output row of tirt_kat_primary_list_walk
+KAT_STEP_IN, KAT_STEP_OUT = 23, 28                                 # words per row of tirt_kat_shade_step
 
 # context options that select code rather than tune it: name -> (default, meaning).  (The tuning options are listed in include/tirt.h.)
 OPTIONS = {
@@ -206,6 +207,8 @@ SIGNATURES = {
     "tirt_micro_gather_rate": (C.c_int, [_vp, C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
     "tirt_trace_timeline": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]),
     "tirt_primary_beam_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "tirt_primary_beam_lists_download": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "tirt_kat_primary_list_walk": (C.c_int, [_vp, C.c_int, _i32p, _f32p, _f32p, _f32p, C.c_int]),
     "tirt_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "tirt_stats_reset": (C.c_int, [_vp]),
     "tirt_kat_math": (C.c_int, [_vp, C.c_int, _f32p, _f32p, _f32p, C.c_int]),
@@ -1065,6 +1068,36 @@ class Context:
         return {"pixels_with_list": int(out[0]), "leaves_listed": int(out[1]), "pixels_all_probes_hit": int(out[2]), "rays_to_k_trace": int(out[3]), "rays": int(out[4]),
                 "list_builds": int(out[5]), "list_build_ms": out[6] * 1.0e-6, "list_builds_skipped": int(out[7]),
                 "diag_leaf_steps": int(out[8]), "diag_rays_more_than_one_step": int(out[9]), "diag_lane_slots": int(out[10]), "diag_rays_more_than_two_steps": int(out[11])}
+
+    def primary_beam_lists_info(self):
+        """tirt.h, tirt_primary_beam_lists_download with NULL arrays: {"P", "cmax", "lists" (bool), "pixels_with_list"}"""
+        info = np.zeros(4, np.int32)
+        check(lib().tirt_primary_beam_lists_download(self.handle, None, None, None, _ptr(info)))
+        return {"P": int(info[0]), "cmax": int(info[1]), "lists": bool(info[2]), "pixels_with_list": int(info[3])}
+
+    def primary_beam_lists_download(self):
+        """The camera rays' candidate lists of the current (build, camera, film), made first if they do not stand (tirt.h, tirt_primary_beam_lists_download): the
+        info above and, in local pixel order, count int32 [P], code int32 [cmax, P] (the leaves' child codes), nr float32 [cmax, P], bound float32 [P]."""
+        out = self.primary_beam_lists_info()
+        P, cmax = out["P"], out["cmax"]
+        count = np.zeros(P, np.int32); cand = np.zeros((cmax, P, 2), np.int32); bound = np.zeros(P, np.float32)
+        info = np.zeros(4, np.int32)
+        check(lib().tirt_primary_beam_lists_download(self.handle, _ptr(count), _ptr(cand), _ptr(bound), _ptr(info)))
+        out.update(lists=bool(info[2]), pixels_with_list=int(info[3]), count=count, code=np.ascontiguousarray(cand[:, :, 0]),
+                   nr=np.ascontiguousarray(cand[:, :, 1]).view(np.float32), bound=bound)
+        return out
+
+    def kat_primary_list_walk(self, local_pixel, jx, jy, out_stride=KAT_LIST_WALK_OUT):
+        """tirt.h, tirt_kat_primary_list_walk: rows (local pixel, jx, jy) -> (n, out_stride) float32: d3, resolved, t, u, v, prim (bits), steps.  Row r runs on lane
+        r % 64 of wave r // 64."""
+        local_pixel = np.ascontiguousarray(local_pixel, np.int32).reshape(-1)
+        jx = np.ascontiguousarray(jx, np.float32).reshape(-1); jy = np.ascontiguousarray(jy, np.float32).reshape(-1)
+        n = local_pixel.shape[0]
+        if jx.shape[0] != n or jy.shape[0] != n:
+            raise ValueError("kat_primary_list_walk: local_pixel, jx and jy have one entry per row")
+        out = np.zeros((n, out_stride), np.float32)
+        check(lib().tirt_kat_primary_list_walk(self.handle, n, local_pixel, jx, jy, out.reshape(-1), int(out_stride)))
+        return out
 
     def micro_gather_rate(self, working_set_bytes, iters=2000):
         v = C.c_double(0.0)

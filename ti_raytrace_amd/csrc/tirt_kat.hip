@@ -3,6 +3,7 @@
 // tirt_kat_env_*, tirt_kat_shade_step and tirt_kat_spec live beside the code they evaluate (tirt_envsample.hip, tirt_render.hip, tirt_spectral.hip).
 #include "tirt_internal.h"
 #include "tirt_spectral.h"
+#include "tirt_pvb.h"
 
 namespace tirt {
 
@@ -196,11 +197,53 @@ __global__ void k_kat_material_maps(SceneView sc, const float *in, int in_stride
     o[0] = uv.x; o[1] = uv.y; o[2] = rough; o[3] = metal; o[4] = Np.x; o[5] = Np.y; o[6] = Np.z; o[7] = 0.0f;
 }
 
+// ---- one camera ray against its pixel's candidate list (tirt_kat_primary_list_walk): pvb_walk_list itself -- the function k_pvb_cand and k_pvb_cand_shade call --
+// on the context's lists.  Blocks of one wave, row r on lane r & 63 of wave r >> 6: the caller's order decides which rays share a wave and its ballots.  The
+// padding lanes of the last wave make the call with live = false, as the padding threads of a batch do.
+__global__ __launch_bounds__(64) void k_kat_pvb_walk(BvhView b, PvbView pv, CameraView cam, TileMap tm, int P, const int *local_pixel, const float *jx, const float *jy,
+                                                     float *out, int out_stride, int n)
+{
+    const int r = blockIdx.x * 64 + threadIdx.x;
+    const bool live = r < n;
+    const int k = live ? local_pixel[r] : 0;
+    const int p = local_to_pixel(tm, k), i = p / tm.H, j = p - i * tm.H;
+    const v3 d = live ? camera_ray_direction(cam, i, j, jx[r], jy[r]) : V(0.0f, 0.0f, 1.0f);
+    const v3 eye = V(cam.eye[0], cam.eye[1], cam.eye[2]);
+    float hit_t, hit_u, hit_v; int hit_prim;
+    int steps = 0, trips = 0;
+    const bool resolved = pvb_walk_list(b, pv, P, k, live, eye, d, hit_t, hit_u, hit_v, hit_prim, steps, trips);
+    if (!live) return;
+    float *o = out + (size_t)r * out_stride;
+    o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = resolved ? 1.0f : 0.0f;
+    o[4] = hit_t; o[5] = hit_u; o[6] = hit_v; o[7] = __int_as_float(hit_prim); o[8] = (float)steps;
+}
+
 }  // namespace tirt
 
 using namespace tirt;
 
 extern "C" {
+
+int tirt_kat_primary_list_walk(tirt_ctx *c, int n, const int32_t *local_pixel, const float *jx, const float *jy, float *out, int out_stride)
+{
+    const char *fn = "tirt_kat_primary_list_walk";
+    TIRT_REQUIRE(local_pixel && jx && jy && out && n >= 0, std::string(fn) + ": null pointer or negative n");
+    TIRT_REQUIRE(out_stride >= 9, std::string(fn) + ": stride too small (9 words out)");
+    CTX(c);
+    bool have = false;
+    if (int rc = pvb_lists_for_tests(c, fn, have)) return rc;
+    TIRT_REQUIRE(have, std::string(fn) + ": the context has no candidate lists (option \"primary_beams\" off, a scene with cut-outs, an empty film or no list memory)");
+    const int P = (int)c->npix_local;
+    for (int i = 0; i < n; i++)
+        TIRT_REQUIRE(local_pixel[i] >= 0 && local_pixel[i] < P, std::string(fn) + ": row " + std::to_string(i) + ": local pixel outside [0, P)");
+    if (n == 0) return TIRT_OK;
+    const TileMap tm = {c->tile_rank, c->tile_count, c->tile_size, c->H, c->tile_blocked, 0};
+    return kat_round_trip(c, fn, {{local_pixel, kat_row_bytes(n, 1)}, {jx, kat_row_bytes(n, 1)}, {jy, kat_row_bytes(n, 1)}}, out, kat_row_bytes(n, out_stride),
+                          [&](const void *const *din, void *dout) {
+        hipLaunchKernelGGL(k_kat_pvb_walk, dim3((n + 63) / 64), dim3(64), 0, c->stream, bvh_view(c), pvb_current_view(c), c->cam, tm, P, (const int *)din[0],
+                           (const float *)din[1], (const float *)din[2], (float *)dout, out_stride, n);
+    });
+}
 
 int tirt_kat_env_sample(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n)
 {

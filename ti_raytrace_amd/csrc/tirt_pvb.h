@@ -9,6 +9,10 @@ constexpr int PVB_CMAX = 24;                        // leaves on a pixel's list 
 
 struct PvbView { const int *count; const int2 *cand; const float *bound; };     // [P], [PVB_CMAX][P] (leaf code, bits of the nearest distance any ray of the pixel can reach the leaf's box at), [P]; count < 0: no list
 
+// tirt_pvb.hip, for the test entries tirt_primary_beam_lists_download and tirt_kat_primary_list_walk (tirt_kat.hip): the current lists, made as a batch makes them
+int pvb_lists_for_tests(tirt_ctx *c, const char *fn, bool &have);
+PvbView pvb_current_view(const tirt_ctx *c);
+
 // One camera ray (from `eye` along `d`, local pixel k of P) against its pixel's list: the hit (hit_t .. hit_prim) and whether it is k_trace's answer (see the
 // header of tirt_pvb.hip); a ray that is not `resolved` is k_trace's.  Every lane of the wave calls it (the loop leaves on a ballot); a lane that is not `live`
 // comes back unresolved.  `steps`, `trips`: leaf steps of this ray and loop trips of its wave (diagnostics, option "primary_beams_diag").

@@ -346,3 +346,52 @@ void pvb_launch_scatter(hipStream_t st, const int *fb_count, const int *fb_slot,
 }
 
 }  // namespace tirt
+
+using namespace tirt;
+
+// What the two test entries below share: the lists of the current (build, camera, film), made -- if they do not stand -- exactly as a batch makes them (pvb_prepare),
+// under the conditions pt_render puts before that call.  `have`: the context holds lists that batches would read (every pixel of a camera further than TR_FAR_RHO
+// extents away has count -1 in them).  The refusals come first and change nothing.
+int tirt::pvb_lists_for_tests(tirt_ctx *c, const char *fn, bool &have)
+{
+    have = false;
+    TIRT_REQUIRE(c->n >= 1 && c->built, std::string(fn) + ": no scene, or its LBVH is not built");
+    TIRT_REQUIRE(c->cam_set, std::string(fn) + ": camera not set");
+    TIRT_REQUIRE(c->hdr.p && c->npix_local >= 0, std::string(fn) + ": film not created");
+    if (sync_all(c)) return TIRT_ERR_HIP;
+    if (ensure_counters(c)) return TIRT_ERR_HIP;
+    if (int rc = ensure_cutout_records(c)) return rc;
+    if (c->npix_local == 0 || !c->primary_beams || c->has_cutout) return TIRT_OK;
+    if (int rc = pvb_prepare(c)) return rc;
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    have = c->pvb_valid;
+    return TIRT_OK;
+}
+PvbView tirt::pvb_current_view(const tirt_ctx *c)
+{
+    const tirt_ctx::PvbSet &ps = c->pvb_set[c->pvb_cur];
+    return PvbView{ps.count.as<int>(), ps.cand.as<int2>(), ps.bound.as<float>()};
+}
+
+extern "C" int tirt_primary_beam_lists_download(tirt_ctx *c, int32_t *count, int32_t *cand, float *bound, int32_t info[4])
+{
+    const char *fn = "tirt_primary_beam_lists_download";
+    TIRT_REQUIRE(info, std::string(fn) + ": null info");
+    TIRT_REQUIRE((count && cand && bound) || (!count && !cand && !bound), std::string(fn) + ": count, cand and bound are given together or not at all");
+    CTX(c);
+    bool have = false;
+    if (int rc = pvb_lists_for_tests(c, fn, have)) return rc;
+    const size_t P = (size_t)c->npix_local;
+    unsigned long long with_list = 0;
+    if (have) TIRT_HIP(hipMemcpy(&with_list, c->pvb_stat.p, sizeof(with_list), hipMemcpyDeviceToHost));      // (k_pvb_beam's own count of the pixels it gave a list)
+    if (count && have) {
+        const PvbView pv = pvb_current_view(c);
+        TIRT_HIP(hipMemcpy(count, pv.count, sizeof(int) * P, hipMemcpyDeviceToHost));
+        TIRT_HIP(hipMemcpy(cand, pv.cand, sizeof(int2) * (size_t)PVB_CMAX * P, hipMemcpyDeviceToHost));
+        TIRT_HIP(hipMemcpy(bound, pv.bound, sizeof(float) * P, hipMemcpyDeviceToHost));
+    } else if (count) {
+        for (size_t k = 0; k < P; k++) count[k] = -1;
+    }
+    info[0] = (int32_t)P; info[1] = PVB_CMAX; info[2] = (have && with_list > 0) ? 1 : 0; info[3] = (int32_t)with_list;
+    return TIRT_OK;
+}
