@@ -989,6 +989,73 @@ int tirt_mesh_distance(tirt_ctx *ctx, const float *tris, int n, const float *dma
 int tirt_kat_tri_tri(tirt_ctx *ctx, const float *in, int n, int what, float *out);
 int tirt_kat_tri_tri_host(const float *in, int n, int what, float *out);
 
+/* Point pairs (no reference counterpart; csrc/tirt_pairs.hip / .h): EVERY primitive within a distance of a query point -- the fixed-radius neighbour list
+ * -- as the rows of a CSR layout.  "K nearest primitives" answers the first k <= 64 and how many; this says which, however many.
+ * Terms.  D2(p, i), Q, u, v, lim2 = dmax * dmax formed once (dmax < 0 or NaN: -1; +inf: no bound) are those of "Closest point", unchanged.
+ * The row of p is the set N(p) of "K nearest primitives", unchanged: { i : D2(p, i) <= lim2 and D2(p, i) < +inf }.  A NaN D2 is never a member.  A query
+ *   with a NaN or infinite coordinate, or a negative or NaN bound, has the empty row.  Analytic spheres take part; spot and laser shapes have no surface and
+ *   do not; alpha cut-outs are ignored.
+ * Order inside a row.  D2 ascending; at equal D2 bits the smaller primitive id first: the total order of "K nearest primitives".  So element 0 of a row that
+ *   is not empty is tirt_query_closest_point's answer bit for bit, the first min(k, length) elements are tirt_query_nearest's list bit for bit, and the row
+ *   does not depend on the order of the visits (which follows the tree build's atomics and differs from one build to the next).
+ * Layout.  row_start[n + 1] is int64: the exclusive prefix sums of the rows' lengths, row_start[n] the total.  Element j of row i is at row_start[i] + j
+ *   of out_d2 and out_prim; out_point + (row_start[i] + j) * point_out_stride = Q and out_uv + (row_start[i] + j) * uv_stride = (u, v) of that pair, formed
+ *   again from the record by the device function the walk ran: the bits tirt_query_closest_point gives for that pair.
+ * mode.  TIRT_PAIRS_COUNT writes row_start and nothing else: the sizing call (capacity and the out arrays are not looked at).  TIRT_PAIRS_FILL reads a
+ *   row_start that a COUNT call on the same queries, bounds and geometry produced, and writes the rows.  TIRT_PAIRS_BOTH counts, scans and fills in one call.
+ * capacity (FILL, BOTH): the number of pairs the out arrays hold.  A row is written iff it fits entirely: 0 <= row_start[i] <= row_start[i + 1] <= capacity.
+ *   A row that does not fit is neither walked a second time nor written, not even in part (a part's content would depend on the order of the walk); nothing
+ *   at or behind the end of the last row that fits is touched.  row_start is complete whatever the capacity: row_start[n] > capacity says the result was cut.
+ * flags.  TIRT_TRAVERSE_EXHAUSTIVE = every primitive record in id order through the same membership, store and order code (the yardstick: same bits, N_box 0,
+ *   N_leaf = primitives); TIRT_COUNT_NODES as elsewhere (counts[n*2], from the counting walk, or the filling walk of a FILL call); TIRT_PAIRS_UNORDERED skips
+ *   the order pass: the order inside a row is then unspecified (the walk's), the set is the same.
+ * tirt_query_point_pairs: device memory on the caller's stream with tirt_query_closest_point's plumbing, stack and refusals, no host wait.  Per chunk of
+ *   "query_chunk_rays" one launch of the counting walk (the row's length into row_start[i + 1]); three launches turn the lengths into row_start in place
+ *   (block sums, one block over the block sums, add -- no kernel waits for another block; 8 bytes of scratch per 1024 queries); one launch per chunk of the
+ *   filling walk (the same walk, the same cut: member number j of row i to row_start[i] + j, guarded by j < the row's length, so that a stack overflow never
+ *   writes outside its row); one launch orders the rows in place, one wave per row (rows of up to 1024 pairs in LDS; longer rows by the same sorting network
+ *   on the caller's arrays in global memory, which is correct for any length and not tuned); one launch forms the points.  A query whose walk dropped a stack
+ *   entry is counted in stack_overflow once per walk.
+ *   Refused with TIRT_ERR_ARG before anything is queued, beside tirt_query_closest_point's refusals: an unknown mode, a null row_start or one that is not
+ *   8-byte aligned, and in FILL and BOTH: neither out_prim nor out_d2, a negative capacity, only one of out_d2 and out_prim without TIRT_PAIRS_UNORDERED
+ *   (they are the key of the order), out_point or out_uv without out_prim.  (With capacity == 0 no row that has a pair fits: the out arrays are not looked
+ *   at and may be NULL.)  n == 0 writes row_start[0] = 0 (COUNT, BOTH) and nothing else.
+ * tirt_point_pairs: host arrays (points[n*3], dmax[n] or NULL = +inf, row_start[n + 1], out arrays of `capacity` pairs), staged and synchronous, as
+ *   tirt_nearest is to tirt_query_nearest.  Only the rows that fit are copied back.
+ * tirt_kat_pairs_host: host only, no context: n_rows rows of members (d2, prim) -- row i is the next row_len[i] entries, D2 >= 0 and finite, prim >= 0 and
+ *   distinct inside a row -- in the order given, through the scan, the capacity rule and the sorting network the kernels run (csrc/tirt_pairs.h):
+ *   row_start[n_rows + 1], and the rows that fit, ordered, at their offsets of out_d2 / out_prim; nothing else of those is written. */
+#define TIRT_PAIRS_COUNT 0
+#define TIRT_PAIRS_FILL 1
+#define TIRT_PAIRS_BOTH 2
+#define TIRT_PAIRS_UNORDERED 4      /* a flag beside TIRT_TRAVERSE_EXHAUSTIVE and TIRT_COUNT_NODES, of the pair lists alone */
+int tirt_query_point_pairs(tirt_ctx *ctx, const float *points, int64_t n, int64_t point_stride,
+                           const float *dmax, int64_t dmax_stride, float dmax_all, int mode, int64_t capacity, int stack_size, int flags,
+                           int64_t *row_start, float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride,
+                           float *out_uv, int64_t uv_stride, int32_t *counts, void *stream);
+int tirt_point_pairs(tirt_ctx *ctx, const float *points, int n, const float *dmax, int mode, int64_t capacity, int stack_size, int flags,
+                     int64_t *row_start, float *out_d2, int32_t *out_prim, float *out_point, float *out_uv, int32_t *counts);
+int tirt_kat_pairs_host(const float *d2, const int32_t *prim, const int32_t *row_len, int n_rows, int64_t capacity,
+                        int64_t *row_start, float *out_d2, int32_t *out_prim);
+
+/* Triangle pairs (no reference counterpart; csrc/tirt_pairs.hip / .h): every scene triangle within a distance of a query TRIANGLE T -- with a bound of 0
+ * the contact pair list of a mesh against the scene -- as the rows of the same CSR layout.
+ * The row of T is the same set on D2(T, i) = the d2 of the pair's answer of "Triangle distance" over the scene's triangles, with that section's rules:
+ *   { i : D2(T, i) <= lim2 and D2(T, i) < +inf }.  A T with a NaN or infinite coordinate has the empty row, and so has a negative or NaN bound.  Analytic
+ *   spheres, spot and laser shapes are skipped; alpha cut-outs are ignored.  dmax = 0 gives every scene triangle that touches or crosses T by that arithmetic:
+ *   the row is not empty exactly where the contact test of "Triangle distance" says prim >= 0.
+ * Order, layout, mode, capacity, flags, launches and refusals are those of "Point pairs" (tri_stride >= 9 and points_stride >= 6 in the place of the point
+ *   strides); element 0 of a row is tirt_query_mesh_distance's answer bit for bit.  out_code[row_start[i] + j] is the `code` of that pair's answer -- it
+ *   travels with its pair through the order pass -- and out_points + (row_start[i] + j) * points_stride = P on T then Q on the scene triangle (6 floats),
+ *   formed again by the pair's arithmetic after the order.
+ * tirt_mesh_pairs: host arrays (tris[n*9], dmax[n] or NULL = +inf, out_points[capacity*6]), staged and synchronous. */
+int tirt_query_mesh_pairs(tirt_ctx *ctx, const float *tris, int64_t n, int64_t tri_stride,
+                          const float *dmax, int64_t dmax_stride, float dmax_all, int mode, int64_t capacity, int stack_size, int flags,
+                          int64_t *row_start, float *out_d2, int32_t *out_prim, int32_t *out_code, float *out_points, int64_t points_stride,
+                          int32_t *counts, void *stream);
+int tirt_mesh_pairs(tirt_ctx *ctx, const float *tris, int n, const float *dmax, int mode, int64_t capacity, int stack_size, int flags,
+                    int64_t *row_start, float *out_d2, int32_t *out_prim, int32_t *out_code, float *out_points, int32_t *counts);
+
 /* Signed distance (no reference counterpart; csrc/tirt_signed_distance.hip, sd_sign in csrc/tirt_closest_point.h): the distance of "Closest point" with the
  * sign of the angle-weighted pseudo-normal of the closest FEATURE -- face, edge or vertex (Baerentzen & Aanaes, "Signed distance computation using the
  * angle weighted pseudonormal", 2005).  The face normal of the winning triangle alone is wrong at sharp and concave vertices and edges, where several

@@ -7,6 +7,7 @@
     m = q.inside(points)                                  # [N] bool
     nn = q.nearest(points, k, max_distance=None, attributes=False, count=False)      # PointNearest(dist2 [N, k], prim [N, k], point, uv, count [N] or None)
     c = q.count_within(points, max_distance)              # [N] int32: the primitives within max_distance of each point
+    w = q.within(points, max_distance, attributes=False, capacity=None, ordered=True)      # PointPairs(row_start [N + 1] i64, prim, dist2, point, uv): CSR rows; w.query() = the query index per pair
     r = q.mesh_report()                                   # {"boundary_edges", "nonmanifold_edges", "flipped_edges", "invalid_triangles", "primitives", "closed"}
 
 ``points`` is a float32 tensor ``[N, C >= 3]`` on the scene context's device with ``stride(1) == 1`` and any row stride (an ``[N, 8]``
@@ -34,6 +35,71 @@ from . import _native
 PointHits = collections.namedtuple("PointHits", ["dist2", "prim", "point", "uv"])
 SignedHits = collections.namedtuple("SignedHits", ["dist", "prim", "point", "uv"])
 PointNearest = collections.namedtuple("PointNearest", ["dist2", "prim", "point", "uv", "count"])
+
+
+class _Pairs:
+    """what the two CSR results share: query() expands row_start to the query index of every pair"""
+    __slots__ = ()
+
+    def query(self):
+        """[total] int64: the index of the query each pair belongs to (pairs of rows that were cut by a capacity are not among them)"""
+        import torch
+        lengths = self.row_start[1:] - self.row_start[:-1]
+        fits = self.row_start[1:] <= self.prim.shape[0]
+        return torch.repeat_interleave(torch.arange(lengths.shape[0], device=lengths.device), lengths * fits)
+
+
+class PointPairs(_Pairs, collections.namedtuple("PointPairs", ["row_start", "prim", "dist2", "point", "uv"])):
+    __slots__ = ()
+
+
+def _pairs_front(q, what, tri, queries, max_distance, attributes, capacity, ordered, count_only=False):
+    """PointQuery.within / TriangleQuery.pairs / .count_within: the checks of the sibling calls, then COUNT, the one host wait and FILL (capacity None),
+    or BOTH.  -> (row_start, prim, d2, code, attributes) as tensors"""
+    torch = q.torch
+    if tri:
+        dev, n, stride, queries = q._check_triangles(queries, what)
+    else:
+        dev, n, stride = q._check_points(queries, what)
+    dptr, dstride, dall = q._check_bound(max_distance, dev, n, what)
+    if capacity is not None:
+        capacity = operator.index(capacity)
+        if capacity < 0:
+            raise ValueError("%s.%s: capacity must be >= 0, got %d" % (type(q).__name__, what, capacity))
+    flags = q.flags | (0 if ordered else _native.PAIRS_UNORDERED)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    row_start = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    run = q.scene.ctx.query_mesh_pairs if tri else q.scene.ctx.query_point_pairs
+
+    def call(mode, cap, **out):
+        run(queries.data_ptr() if n else 0, n, stride, mode, row_start.data_ptr(), capacity=cap, stack_size=q.stack_size, flags=flags, dmax=dptr,
+            dmax_stride=dstride, dmax_all=dall, stream=stream, **out)
+    mode = _native.PAIRS_BOTH
+    if capacity is None or count_only:
+        call(_native.PAIRS_COUNT, 0)
+        if count_only:
+            return row_start
+        capacity, mode = int(row_start[-1].item()), _native.PAIRS_FILL      # the one host wait of this path
+    prim = torch.empty(capacity, dtype=torch.int32, device=dev)
+    d2 = torch.empty(capacity, dtype=torch.float32, device=dev)
+    code = torch.empty(capacity, dtype=torch.int32, device=dev) if tri else None
+    out = dict(out_d2=d2.data_ptr(), out_prim=prim.data_ptr())
+    a0 = a1 = None
+    if tri:
+        out["out_code"] = code.data_ptr()
+        if attributes:
+            a0 = torch.empty((capacity, 2, 3), dtype=torch.float32, device=dev)
+            out["out_points"] = a0.data_ptr()
+    elif attributes:
+        a0 = torch.empty((capacity, 3), dtype=torch.float32, device=dev)
+        a1 = torch.empty((capacity, 2), dtype=torch.float32, device=dev)
+        out["out_point"], out["out_uv"] = a0.data_ptr(), a1.data_ptr()
+    if n or mode == _native.PAIRS_BOTH:
+        call(mode, capacity, **out)
+    if tri:
+        from .TriangleQuery import TrianglePairs
+        return TrianglePairs(row_start, prim, d2, code, a0[:, 0] if attributes else None, a0[:, 1] if attributes else None)
+    return PointPairs(row_start, prim, d2, a0, a1)
 
 
 def _torch():
@@ -176,6 +242,16 @@ class PointQuery:
         if max_distance is None:
             raise TypeError("PointQuery.count_within: max_distance is required (without a bound every primitive counts)")
         return self.nearest(points, 0, max_distance, count=True).count
+
+    def within(self, points, max_distance, attributes=False, capacity=None, ordered=True):
+        """EVERY primitive within max_distance (a float or an [N] float32 tensor; None = no bound: every primitive of the scene for every query) of every
+        query, as CSR rows (include/tirt.h, "Point pairs"): PointPairs(row_start [N + 1] int64, prim [total] i32, dist2 [total] f32, point [total, 3], uv
+        [total, 2] or None).  Row i is the slice row_start[i] : row_start[i + 1]; inside a row dist2 ascends and ties go to the smaller primitive id, so
+        its element 0 is closest()'s answer and its first k elements are nearest(k)'s; ordered=False skips that pass (the order is then unspecified).
+        capacity=None sizes the result exactly: a counting call, ONE HOST WAIT to read the total (row_start[-1].item()), then the filling call.
+        capacity=c runs both in one call with no host wait, into arrays of c pairs: only the rows that fit entirely (row_start[i + 1] <= c) are
+        written, row_start is complete, and row_start[-1] > c says the result was cut (what lies behind the last row that fits is uninitialised)."""
+        return _pairs_front(self, "within", False, points, max_distance, attributes, capacity, ordered)
 
     def inside(self, points):
         """[N] bool: signed_distance(points).dist < 0"""

@@ -5,6 +5,8 @@ counterpart; include/tirt.h, "Triangle distance": the definition, bit for bit; c
     h = q.closest(triangles, max_distance=None, points=False)      # TriangleClosest(d2 [n] f32, prim [n] i32, code [n] i32, point_query, point_scene [n, 3] or None)
     m = q.collides(triangles)                             # [n] bool: closest(triangles, max_distance=0.0).prim >= 0
     h, counts = q.closest_counts(triangles, max_distance=None)      # counts [n, 2] int32: N_box, N_leaf of a COUNT_NODES walk
+    p = q.pairs(triangles, max_distance=0.0, points=False, capacity=None, ordered=True)      # TrianglePairs(row_start [n + 1] i64, prim, d2, code, point_query, point_scene): CSR rows; p.query() = the query index per pair
+    c = q.count_within(triangles, max_distance)           # [n] int32: the scene triangles within max_distance of each query triangle
 
 ``triangles`` is a float32 tensor ``[n, 3, 3]`` (triangle, vertex, xyz) on the scene context's device whose last two dimensions are contiguous (strides
 ``(s, 3, 1)`` with any ``s >= 9``: a slice of a wider buffer is handed over without a copy; any other layout is copied once), or a pair
@@ -20,9 +22,13 @@ go to the smallest primitive id, so the walk cannot stop at the first contact).
 import collections
 
 from . import _native
-from .PointQuery import PointQuery
+from .PointQuery import PointQuery, _Pairs, _pairs_front
 
 TriangleClosest = collections.namedtuple("TriangleClosest", ["d2", "prim", "code", "point_query", "point_scene"])
+
+
+class TrianglePairs(_Pairs, collections.namedtuple("TrianglePairs", ["row_start", "prim", "d2", "code", "point_query", "point_scene"])):
+    __slots__ = ()
 
 
 class TriangleQuery:
@@ -99,6 +105,24 @@ class TriangleQuery:
     def collides(self, triangles):
         """[n] bool: the query triangle touches or crosses some scene triangle by the definition's arithmetic -- closest(triangles, max_distance=0.0).prim >= 0"""
         return self.closest(triangles, max_distance=0.0).prim >= 0
+
+    def pairs(self, triangles, max_distance=0.0, points=False, capacity=None, ordered=True):
+        """EVERY scene triangle within max_distance of every query triangle -- with the default 0.0 the contact pair list: all that touch or cross it --
+        as CSR rows (include/tirt.h, "Triangle pairs"): TrianglePairs(row_start [n + 1] int64, prim [total] i32, d2 [total] f32, code [total] i32,
+        point_query, point_scene [total, 3] or None).  Row i is the slice row_start[i] : row_start[i + 1]; inside a row d2 ascends and ties go to the
+        smaller primitive id, so its element 0 is closest()'s answer and a row is non-empty at 0.0 exactly where collides() is true; ordered=False skips
+        that pass.  capacity=None sizes the result exactly: a counting call, ONE HOST WAIT to read the total, then the filling call.  capacity=c runs
+        both in one call with no host wait: only the rows that fit entirely (row_start[i + 1] <= c) are written, row_start is complete, and
+        row_start[-1] > c says the result was cut."""
+        return _pairs_front(self, "pairs", True, triangles, max_distance, points, capacity, ordered)
+
+    def count_within(self, triangles, max_distance):
+        """[n] int32: how many scene triangles lie within max_distance (a float or an [n] float32 tensor; required) of every query triangle: the lengths
+        of pairs()'s rows, from the counting call alone.  Asynchronous on the current stream."""
+        if max_distance is None:
+            raise TypeError("TriangleQuery.count_within: max_distance is required (without a bound every triangle counts)")
+        row_start = _pairs_front(self, "count_within", True, triangles, max_distance, False, None, True, count_only=True)
+        return (row_start[1:] - row_start[:-1]).to(self.torch.int32)
 
     def closest_counts(self, triangles, max_distance=None):
         """closest() with the per-query N_box / N_leaf counts ([n, 2] int32) of a COUNT_NODES walk: (TriangleClosest, counts)"""

@@ -52,6 +52,8 @@ SD_REPORT = ("boundary_edges", "nonmanifold_edges", "flipped_edges", "invalid_tr
 TRAVERSE_ORDERED = 0
 TRAVERSE_EXHAUSTIVE = 1
 COUNT_NODES = 2
+PAIRS_COUNT, PAIRS_FILL, PAIRS_BOTH = 0, 1, 2                       # TIRT_PAIRS_*: the modes of tirt_query_point_pairs / tirt_query_mesh_pairs
+PAIRS_UNORDERED = 4                                                 # TIRT_PAIRS_UNORDERED: their flag beside the two above
 
 # tirt_debug_render modes (include/tirt.h): the views of integrator/Debug.py:62-65
 DEBUG_ALBEDO = 0
@@ -194,6 +196,13 @@ SIGNATURES = {
     "tirt_mesh_distance": (C.c_int, [_vp, _f32p, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "tirt_kat_tri_tri": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, _f32p]),
     "tirt_kat_tri_tri_host": (C.c_int, [_f32p, C.c_int, C.c_int, _f32p]),
+    "tirt_query_point_pairs": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
+                                         C.c_int64, _vp, C.c_int64, _vp, _vp]),
+    "tirt_point_pairs": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tirt_kat_pairs_host": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp]),
+    "tirt_query_mesh_pairs": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
+                                        _vp, C.c_int64, _vp, _vp]),
+    "tirt_mesh_pairs": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tirt_query_signed_distance": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64,
                                              _vp, C.c_int64, _vp, _vp, _vp]),
     "tirt_signed_distance": (C.c_int, [_vp, _f32p, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -984,6 +993,68 @@ class Context:
                                        _ptr(pq), _ptr(counts)))
         return d2, prim, code, pq, counts
 
+    def query_point_pairs(self, points, n, point_stride, mode, row_start, capacity=0, stack_size=64, flags=0, dmax=0, dmax_stride=1, dmax_all=float("inf"),
+                          out_d2=0, out_prim=0, out_point=0, point_out_stride=3, out_uv=0, uv_stride=2, counts=0, stream=0):
+        """tirt_query_point_pairs on device memory (include/tirt.h, "Point pairs"): every buffer is an integer device address (0 = none), dmax = 0 means
+        dmax_all for every query; mode is PAIRS_COUNT, PAIRS_FILL or PAIRS_BOTH.  Asynchronous; ti_raytrace_amd.PointQuery.within is the torch front end."""
+        check(lib().tirt_query_point_pairs(self.handle, _vp(int(points) or None), int(n), int(point_stride), _vp(int(dmax) or None), int(dmax_stride),
+                                           float(dmax_all), int(mode), int(capacity), int(stack_size), int(flags), _vp(int(row_start) or None),
+                                           _vp(int(out_d2) or None), _vp(int(out_prim) or None), _vp(int(out_point) or None), int(point_out_stride),
+                                           _vp(int(out_uv) or None), int(uv_stride), _vp(int(counts) or None), _vp(int(stream) or None)))
+
+    def query_mesh_pairs(self, tris, n, tri_stride, mode, row_start, capacity=0, stack_size=64, flags=0, dmax=0, dmax_stride=1, dmax_all=float("inf"),
+                         out_d2=0, out_prim=0, out_code=0, out_points=0, points_stride=6, counts=0, stream=0):
+        """tirt_query_mesh_pairs on device memory (include/tirt.h, "Triangle pairs"), as query_point_pairs.  ti_raytrace_amd.TriangleQuery.pairs is the
+        torch front end."""
+        check(lib().tirt_query_mesh_pairs(self.handle, _vp(int(tris) or None), int(n), int(tri_stride), _vp(int(dmax) or None), int(dmax_stride),
+                                          float(dmax_all), int(mode), int(capacity), int(stack_size), int(flags), _vp(int(row_start) or None),
+                                          _vp(int(out_d2) or None), _vp(int(out_prim) or None), _vp(int(out_code) or None), _vp(int(out_points) or None),
+                                          int(points_stride), _vp(int(counts) or None), _vp(int(stream) or None)))
+
+    def _pairs_host(self, tri, query, max_distance, capacity, stack_size, flags, attributes):
+        """the host routes of the pair lists: capacity None = a COUNT call, exact arrays, a FILL call; else one BOTH call into arrays of `capacity` pairs
+        (pre-filled: -1 / NaN where no row was written)"""
+        width = 9 if tri else 3
+        query = np.ascontiguousarray(query, np.float32).reshape(-1, width)
+        n = query.shape[0]
+        dmax = None
+        if max_distance is not None:
+            dmax = np.ascontiguousarray(np.broadcast_to(np.asarray(max_distance, np.float32), (n,)))
+        row_start = np.zeros(n + 1, np.int64)
+        counts = np.zeros((n, 2), np.int32) if (flags & COUNT_NODES) else None
+
+        def call(mode, cap, d2, prim, code, a0, a1):
+            if tri:
+                check(lib().tirt_mesh_pairs(self.handle, _ptr(query), n, _ptr(dmax), mode, cap, int(stack_size), int(flags), _ptr(row_start), _ptr(d2),
+                                            _ptr(prim), _ptr(code), _ptr(a0), _ptr(counts)))
+            else:
+                check(lib().tirt_point_pairs(self.handle, _ptr(query), n, _ptr(dmax), mode, cap, int(stack_size), int(flags), _ptr(row_start), _ptr(d2),
+                                             _ptr(prim), _ptr(a0), _ptr(a1), _ptr(counts)))
+        mode = PAIRS_BOTH
+        if capacity is None:
+            call(PAIRS_COUNT, 0, None, None, None, None, None)
+            capacity, mode = int(row_start[-1]), PAIRS_FILL
+        capacity = int(capacity)
+        d2 = np.full(capacity, np.nan, np.float32)
+        prim = np.full(capacity, -1, np.int32)
+        code = np.full(capacity, -1, np.int32) if tri else None
+        a0 = np.zeros((capacity, 2, 3) if tri else (capacity, 3), np.float32) if attributes else None
+        a1 = np.zeros((capacity, 2), np.float32) if attributes and not tri else None
+        call(mode, capacity, d2, prim, code, a0, a1)
+        return row_start, d2, prim, code, a0, a1, counts
+
+    def point_pairs(self, points, max_distance=None, capacity=None, stack_size=64, flags=0, attributes=True):
+        """tirt_point_pairs, the host route: points (n, 3) float32, max_distance None (= inf), a float or (n,) float32 ->
+        (row_start (n + 1,) int64, prim, dist2, point (., 3) or None, uv (., 2) or None, counts (n, 2) or None [COUNT_NODES])"""
+        row_start, d2, prim, _, point, uv, counts = self._pairs_host(False, points, max_distance, capacity, stack_size, flags, attributes)
+        return row_start, prim, d2, point, uv, counts
+
+    def mesh_pairs(self, tris, max_distance=None, capacity=None, stack_size=64, flags=0, points=True):
+        """tirt_mesh_pairs, the host route: tris (n, 3, 3) float32 -> (row_start (n + 1,) int64, prim, dist2, code, points (., 2, 3) [P on the query
+        triangle, Q on the scene] or None, counts (n, 2) or None [COUNT_NODES])"""
+        row_start, d2, prim, code, pq, _, counts = self._pairs_host(True, tris, max_distance, capacity, stack_size, flags, points)
+        return row_start, prim, d2, code, pq, counts
+
     def kat_tri_tri(self, rows, what=0):
         """include/tirt.h, tirt_kat_tri_tri: what = 0: rows (n, 18) (T, a, b, c) -> (n, 8) d2, P3, Q3, code; 1: (n, 12) two segments -> (n, 3) s, t, d2;
         2: (n, 15) segment and triangle -> (n, 4) hit, u, v, t"""
@@ -1218,6 +1289,24 @@ def kat_nearest_list(d2, prim, k, lim2=float("inf")):
     check(lib().tirt_kat_nearest_list(_ptr(d2) if d2.size else None, _ptr(prim) if prim.size else None, d2.shape[0], int(k), float(lim2),
                                       _ptr(out_d2) if out_d2.size else None, _ptr(out_prim) if out_prim.size else None, info))
     return out_d2, out_prim, int(info[0]), int(info[1]), (float(info[2:3].view(np.float32)[0]), int(info[3]))
+
+
+def kat_pairs_host(d2, prim, row_len, capacity=None, fill=(np.nan, -1)):
+    """include/tirt.h, tirt_kat_pairs_host (host only, no context): rows of members (d2, prim) -- row i is the next row_len[i] entries -- in the order
+    given, through the scan, the capacity rule and the sorting network of csrc/tirt_pairs.h -> (row_start (rows + 1,) int64, d2 (capacity,), prim
+    (capacity,)): the rows that fit in order, `fill` elsewhere.  capacity None = the total"""
+    d2 = np.ascontiguousarray(d2, np.float32).reshape(-1)
+    prim = np.ascontiguousarray(prim, np.int32).reshape(-1)
+    row_len = np.ascontiguousarray(row_len, np.int32).reshape(-1)
+    assert d2.shape == prim.shape and int(row_len.sum()) == d2.shape[0]
+    capacity = d2.shape[0] if capacity is None else int(capacity)
+    row_start = np.zeros(row_len.shape[0] + 1, np.int64)
+    out_d2 = np.full(max(capacity, 0), fill[0], np.float32)
+    out_prim = np.full(max(capacity, 0), fill[1], np.int32)
+    check(lib().tirt_kat_pairs_host(_ptr(d2) if d2.size else None, _ptr(prim) if prim.size else None, _ptr(row_len) if row_len.size else None,
+                                    row_len.shape[0], capacity, _ptr(row_start), _ptr(out_d2) if out_d2.size else None,
+                                    _ptr(out_prim) if out_prim.size else None))
+    return row_start, out_d2, out_prim
 
 
 def shade_features_host(material, primitive, shape, light, light_count, env=None, env_power=0.0):
