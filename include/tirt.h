@@ -116,6 +116,10 @@ int tirt_sync(tirt_ctx *ctx);
  *            (default 16): batches of fewer frames keep the ordinary launch (making the lists costs 1.2 ms at 1024^2).  "primary_beams_rebuild" (any value):
  *            the lists are forgotten and made again by the next batch that uses them (bench.py times a build inside its clock).  When the memory for the
  *            lists is not to be had the render goes on without them (tirt_primary_beam_stats out[7]).
+ *          "primary_beams_edges" -- (0/1, default 1) a triangle goes on a pixel's list only if, besides the four faces of the pixel's pyramid, none of the
+ *            triangle's own three edge planes through the eye separates it from the pyramid (pvb_beam_triangle_off, csrc/tirt_pvb.h): a triangle whose screen
+ *            rectangle covers the pixel while the triangle does not is dropped.  Shorter lists, the same hit records, films and counters bit for bit.  Setting it
+ *            makes the next batch that uses lists build them again, as a camera change does; 0 = the lists of the four faces alone.
  *          "primary_fused" -- (default 1) a PT_RGB batch that uses the lists computes a camera ray's direction, walks its pixel's list and performs the path's first
  *            shading step in ONE kernel (k_pvb_cand_shade, csrc/tirt_render.hip): the direction and the hit record stay in registers instead of going through
  *            device memory between three kernels.  The rays the lists leave over are traced as before and shaded by a second, short launch.  Same film, same
@@ -1157,7 +1161,13 @@ int tirt_primary_beam_stats(tirt_ctx *ctx, uint64_t out[12]);
  *   caller's order decides which rays share a wave; the padding lanes of the last block make the call as the padding threads of a batch do.
  *   out, 9 words per row: direction (3), resolved (1.0f: the hit is k_trace's; 0.0f: the ray would be handed to k_trace), t, u, v, the primitive as its bits (-1: none),
  *   and the ray's leaf steps as a float.  A row that is not resolved still reports the best hit of the entries it walked.
- *   TIRT_ERR_ARG as above, and: out_stride < 9, a local pixel outside [0, P), a context without lists (info[2] = 0 for any reason but the far camera). */
+ *   TIRT_ERR_ARG as above, and: out_stride < 9, a local pixel outside [0, P), a context without lists (info[2] = 0 for any reason but the far camera).
+ * tirt_kat_beam_triangle_host: host only, no context: the triangle-against-pyramid test of the list build (pvb_beam_triangle_off, csrc/tirt_pvb.h, the text k_pvb_beam
+ *   calls, compiled for the host).  Row r of `in`, 31 floats: the eye (3), the cell sizes of the tree's grid (3), the four corner directions of the pixel's pyramid
+ *   in the order (-, -), (+, -), (+, +), (-, +) of the film's two axes (12), the rounding bounds eps of its four face planes (4), the triangle's corners (9), all
+ *   in world units; the entry forms the grid units and the face normals as k_pvb_beam does.  out[r] = 1: off, the leaf would not be listed; 0: listed.
+ *   edges = 0: the four faces alone; 1: and the triangle's edge planes.  TIRT_ERR_ARG: a null pointer, n < 0, edges not 0 or 1. */
+int tirt_kat_beam_triangle_host(const float *in, int n, int edges, int32_t *out);
 int tirt_primary_beam_lists_download(tirt_ctx *ctx, int32_t *count, int32_t *cand, float *bound, int32_t info[4]);
 int tirt_kat_primary_list_walk(tirt_ctx *ctx, int n, const int32_t *local_pixel, const float *jx, const float *jy, float *out, int out_stride);
 

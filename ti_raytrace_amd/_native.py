@@ -196,6 +196,7 @@ SIGNATURES = {
     "tirt_mesh_distance": (C.c_int, [_vp, _f32p, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "tirt_kat_tri_tri": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, _f32p]),
     "tirt_kat_tri_tri_host": (C.c_int, [_f32p, C.c_int, C.c_int, _f32p]),
+    "tirt_kat_beam_triangle_host": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p]),
     "tirt_query_point_pairs": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
                                          C.c_int64, _vp, C.c_int64, _vp, _vp]),
     "tirt_point_pairs": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1274,6 +1275,16 @@ def kat_tri_tri_host(rows, what=0):
     out = np.zeros((rows.shape[0], KAT_TRI_TRI_ROWS[what][1]), np.float32)
     if rows.shape[0]:
         check(lib().tirt_kat_tri_tri_host(rows.reshape(-1), rows.shape[0], int(what), out.reshape(-1)))
+    return out
+
+
+def kat_beam_triangle_host(rows, edges=1):
+    """include/tirt.h, tirt_kat_beam_triangle_host (host only, no context): rows (n, 31) = eye, cell, the pyramid's four corner directions, eps, the
+    triangle's corners -> (n,) int32, 1 = off (the list build would not list the leaf); edges = 0: the four faces alone"""
+    rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 31)
+    out = np.zeros(rows.shape[0], np.int32)
+    if rows.shape[0]:
+        check(lib().tirt_kat_beam_triangle_host(rows.reshape(-1), rows.shape[0], int(edges), out))
     return out
 
 

@@ -513,6 +513,7 @@ int tirt_set_option(tirt_ctx *c, const char *name, double value)
     // "primary_beams_rebuild": forget the camera rays' candidate lists -- the next batch that uses lists makes them again (bench.py: a list build inside its clock)
     if (!strcmp(name, "primary_beams_rebuild")) { if (flush_pending(c)) return TIRT_ERR_HIP; c->pvb_valid = false; return TIRT_OK; }
     if (!strcmp(name, "primary_beams_diag")) { if (flush_pending(c)) return TIRT_ERR_HIP; c->pvb_diag = value != 0.0; return TIRT_OK; }
+    if (!strcmp(name, "primary_beams_edges")) { TIRT_REQUIRE(value == 0.0 || value == 1.0, "primary_beams_edges: 0 or 1"); if (flush_pending(c)) return TIRT_ERR_HIP; c->pvb_edges = (int)value; return TIRT_OK; }      // (part of the lists' key: pvb_prepare makes them again)
     if (!strcmp(name, "primary_fused")) { TIRT_REQUIRE(value == 0.0 || value == 1.0, "primary_fused: 0 or 1"); if (flush_pending(c)) return TIRT_ERR_HIP; c->primary_fused = (int)value; return TIRT_OK; }
     if (!strcmp(name, "primary_beams_min_frames")) { TIRT_REQUIRE(value >= 1.0 && value <= 1.0e6, "primary_beams_min_frames out of range"); if (flush_pending(c)) return TIRT_ERR_HIP; c->primary_beams_min_frames = (int)value; return TIRT_OK; }
     if (!strcmp(name, "bdpt_lanes")) { TIRT_REQUIRE(value >= 1.0 && value <= 4.0, "bdpt_lanes: 1..4"); if (sync_all(c)) return TIRT_ERR_HIP; c->bdpt_lanes = (int)value; return TIRT_OK; }

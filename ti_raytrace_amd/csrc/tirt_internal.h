@@ -432,13 +432,14 @@ struct tirt_ctx {
     int bdpt_bounded = 1;                          // option "bdpt_bounded": connection rays stop at their target distance
 
     // primary visibility through pixel beams (tirt_pvb.hip): per local pixel the leaves its camera rays can hit first, made once per (build, camera, film)
-    struct PvbKey { tirt::CameraView cam; unsigned long long build; int W, H, tile_rank, tile_count, tile_size, tile_blocked, P; } pvb_key;
+    struct PvbKey { tirt::CameraView cam; unsigned long long build; int W, H, tile_rank, tile_count, tile_size, tile_blocked, P, edges; } pvb_key;
     bool pvb_valid = false; int primary_beams = 1, primary_beams_min_frames = 16;      // options "primary_beams" (0 = off) and "primary_beams_min_frames" (batches of fewer frames trace their camera rays the ordinary way)
     unsigned long long build_serial = 0;          // counts lbvh_build calls
     // two sets of lists: a rebuild (camera move) writes the set the batches in flight are NOT reading, so it waits only for the batches of the camera before last
     // (one set made every camera move wait for all earlier batches to drain); `busy` = film_done of the last batch that read the set
     struct PvbSet { tirt::DevBuf count, cand, bound; hipEvent_t busy = nullptr; } pvb_set[2];
     int pvb_cur = 0;                              // the set pvb_key describes
+    int pvb_edges = 1;                            // option "primary_beams_edges": k_pvb_beam also drops a triangle that one of its own edge planes through the eye separates from the pixel's pyramid (pvb_beam_triangle_off, tirt_pvb.h); part of pvb_key
     int pvb_diag = 0;                             // option "primary_beams_diag": k_pvb_cand counts its leaf steps (one atomic per wave: slow) -- tirt_primary_beam_stats out[8..11]
     int primary_fused = 1;                        // option "primary_fused": PT_RGB's camera ray, list walk and first shading step in one kernel (k_pvb_cand_shade, tirt_render.hip); 0 = the five launches
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pvb_ev;      // HIP events around every list build since the last tirt_stats_reset (read by tirt_primary_beam_stats)

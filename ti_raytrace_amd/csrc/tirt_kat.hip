@@ -245,6 +245,30 @@ int tirt_kat_primary_list_walk(tirt_ctx *c, int n, const int32_t *local_pixel, c
     });
 }
 
+// host only, no context: pvb_beam_triangle_off (tirt_pvb.h) -- the text k_pvb_beam calls -- compiled for the host, on operands formed as k_pvb_beam forms them.
+// Row of 31 floats: eye (3), cell (3), the pyramid's four corner directions in k_pvb_beam's order (12), eps (4), the triangle's corners (9).  The face normals
+// are turned inward by the sum of the four directions (k_pvb_beam uses the pixel's centre direction: the same side for any pyramid that is not flat).
+int tirt_kat_beam_triangle_host(const float *in, int n, int edges, int32_t *out)
+{
+    TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_beam_triangle_host: null pointer or negative n");
+    TIRT_REQUIRE(edges == 0 || edges == 1, "tirt_kat_beam_triangle_host: edges is 0 (the four faces) or 1 (and the triangle's edge planes)");
+    for (int i = 0; i < n; i++) {
+        const float *a = in + (size_t)i * 31;
+        const v3 eye = V(a[0], a[1], a[2]), cell = V(a[3], a[4], a[5]);
+        v3 dg[4], nrm[4], g[3];
+        for (int q = 0; q < 4; q++) dg[q] = V(a[6 + 3 * q] / cell.x, a[7 + 3 * q] / cell.y, a[8 + 3 * q] / cell.z);
+        const v3 dcg = (dg[0] + dg[1]) + (dg[2] + dg[3]);
+        for (int q = 0; q < 4; q++) {
+            v3 nn = cross(dg[q], dg[(q + 1) & 3]);
+            if (dot(nn, dcg) < 0.0f) nn = -nn;
+            nrm[q] = nn;
+        }
+        for (int j = 0; j < 3; j++) { const float *w = a + 22 + 3 * j; g[j] = V((w[0] - eye.x) / cell.x, (w[1] - eye.y) / cell.y, (w[2] - eye.z) / cell.z); }
+        out[i] = pvb_beam_triangle_off(nrm, a + 18, dg, g[0], g[1], g[2], edges != 0) ? 1 : 0;
+    }
+    return TIRT_OK;
+}
+
 int tirt_kat_env_sample(tirt_ctx *c, const float *in, int in_stride, float *out, int out_stride, int n)
 {
     TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_env_sample: null pointer or negative n");

@@ -10,7 +10,8 @@
 //     k_pvb_beam      bound(pixel) = the farthest of their hit distances x 1.5 (PVB_REACH); the pyramid of the pixel (its corner
 //                     directions moved outward by a twentieth of a pixel) is walked down the quantised 4-wide tree and every LEAF
 //                     whose box -- enlarged by k_trace's own margin -- it meets nearer than bound, and whose triangle does not lie
-//                     wholly outside one of its faces, goes on the pixel's list, nearest first.  A list holds PVB_CMAX leaves: when
+//                     wholly outside one of its faces or wholly beyond one of the triangle's own edge planes through the eye
+//                     (pvb_beam_triangle_off, tirt_pvb.h; option "primary_beams_edges"), goes on the pixel's list, nearest first.  A list holds PVB_CMAX leaves: when
 //                     one more turns up the farthest goes and the pixel's bound comes in to just below it (the list stays complete
 //                     up to its bound);
 //   per batch, instead of the bounce-0 launch of k_trace:
@@ -61,7 +62,7 @@ TD float h2f(unsigned h) { return (float)__builtin_bit_cast(_Float16, (unsigned 
 // children too -- the boxes nest --, and a leaf too many on a list would only cost its test).  The first version gave every pixel its own walk and its own stack in scratch
 // memory: 5.2 ms for a 1024^2 film against this one's ~1 (`profiles/r05ar_*`).
 __global__ __launch_bounds__(64) void k_pvb_beam(BvhView b, CameraView cam, TileMap tm, int P, const float4 *probe_hits, int *count, int2 *cand, float *bound_out,
-                                                 unsigned long long *stat)
+                                                 unsigned long long *stat, int edges)
 {
     __shared__ int s_stack[PVB_STACK];
     __shared__ int2 s_list[PVB_CMAX * 64];                 // [entry][lane]
@@ -107,7 +108,20 @@ __global__ __launch_bounds__(64) void k_pvb_beam(BvhView b, CameraView cam, Tile
         int sp = 0;                                         // (wave-uniform: every push below is decided by a ballot)
         const int root = b.root_qcode;
         // a one-primitive scene: the root IS the leaf
-        if (root < 0) { if (root != (int)0x80000000 && root != TR_EMPTY && open) { s_list[lane] = make_int2(root, 0); n = 1; } }
+        if (root < 0) {
+            if (root != (int)0x80000000 && root != TR_EMPTY && open) {
+                // (with `edges` a lone triangle is held against the pyramid like any other; without, it is listed untested as it always was)
+                bool off = false;
+                if (edges && leaf_is_tri(~root)) {
+                    const float4 *tp = b.tri + (size_t)leaf_slot(~root) * TRI_STRIDE;
+                    const float4 ta = tp[0], tb = tp[1], tc = tp[2];
+                    off = pvb_beam_triangle_off(nrm, eps, dg, V((ta.x - eye.x) / cell.x, (ta.y - eye.y) / cell.y, (ta.z - eye.z) / cell.z),
+                                                V((tb.x - eye.x) / cell.x, (tb.y - eye.y) / cell.y, (tb.z - eye.z) / cell.z),
+                                                V((tc.x - eye.x) / cell.x, (tc.y - eye.y) / cell.y, (tc.z - eye.z) / cell.z), true);
+                }
+                if (!off) { s_list[lane] = make_int2(root, 0); n = 1; }
+            }
+        }
         else { s_stack[0] = root; sp = 1; }
         while (sp > 0) {
             if (__ballot(open) == 0ull) break;
@@ -151,12 +165,7 @@ __global__ __launch_bounds__(64) void k_pvb_beam(BvhView b, CameraView cam, Tile
                     const v3 g0 = V((w0.x - eye.x) / cell.x, (w0.y - eye.y) / cell.y, (w0.z - eye.z) / cell.z);
                     const v3 g1 = V((w1.x - eye.x) / cell.x, (w1.y - eye.y) / cell.y, (w1.z - eye.z) / cell.z);
                     const v3 g2 = V((w2.x - eye.x) / cell.x, (w2.y - eye.y) / cell.y, (w2.z - eye.z) / cell.z);
-                    bool off = false;
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const float e = eps[q] + 0.05f * (absf(nrm[q].x) + absf(nrm[q].y) + absf(nrm[q].z));      // (+ a twentieth of a cell)
-                        off = off || (dot(nrm[q], g0) < -e && dot(nrm[q], g1) < -e && dot(nrm[q], g2) < -e);
-                    }
+                    const bool off = pvb_beam_triangle_off(nrm, eps, dg, g0, g1, g2, edges != 0);      // (tirt_pvb.h: the four faces and, with `edges`, the triangle's own edge planes)
                     const float pr = __builtin_fminf(__builtin_fminf(dot(w0 - eye, dc), dot(w1 - eye, dc)), dot(w2 - eye, dc));
                     nr = maxf(nr, pr - 1.0e-4f * absf(pr) - 1.0e-6f);
                     pass = pass && !off && !(nr > bound);
@@ -272,7 +281,7 @@ int pvb_prepare(tirt_ctx *c)
     tirt_ctx::PvbKey key;
     memset(&key, 0, sizeof(key));
     key.cam = c->cam; key.build = c->build_serial; key.W = c->W; key.H = c->H; key.tile_rank = c->tile_rank; key.tile_count = c->tile_count;
-    key.tile_size = c->tile_size; key.tile_blocked = c->tile_blocked; key.P = P;
+    key.tile_size = c->tile_size; key.tile_blocked = c->tile_blocked; key.P = P; key.edges = c->pvb_edges;
     if (c->pvb_valid && !memcmp(&key, &c->pvb_key, sizeof(key))) return TIRT_OK;
     c->pvb_valid = false;
     if (P <= 0) return TIRT_OK;
@@ -312,7 +321,7 @@ int pvb_prepare(tirt_ctx *c)
     TraceJob job; job.stack_size = c->bdpt_stack; job.ray4 = rays; job.count = 5 * P; job.hit = hits; job.count_rays = false; job.grid_cap = c->tr_grid_alone;
     if (int rc = trace_rays(c, job)) { if (tmp_async) (void)hipFreeAsync(tmp, st); if (e0) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); } return rc; }
     hipLaunchKernelGGL(k_pvb_beam, dim3((P + 63) / 64), dim3(64), 0, st, bvh_view(c), c->cam, tm, P, hits, ps.count.as<int>(), ps.cand.as<int2>(),
-                       ps.bound.as<float>(), c->pvb_stat.as<unsigned long long>());
+                       ps.bound.as<float>(), c->pvb_stat.as<unsigned long long>(), c->pvb_edges);
     if (e0) { (void)hipEventRecord(e1, st); c->pvb_ev.push_back({e0, e1}); }
     if (c->pvb_ev.size() > 64) {           // a caller that moves the camera for hours and never asks for statistics: the oldest pair is long finished
         auto pr = c->pvb_ev.front(); c->pvb_ev.erase(c->pvb_ev.begin());
