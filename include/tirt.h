@@ -1060,6 +1060,79 @@ int tirt_query_mesh_pairs(tirt_ctx *ctx, const float *tris, int64_t n, int64_t t
 int tirt_mesh_pairs(tirt_ctx *ctx, const float *tris, int n, const float *dmax, int mode, int64_t capacity, int stack_size, int flags,
                     int64_t *row_start, float *out_d2, int32_t *out_prim, int32_t *out_code, float *out_points, int32_t *counts);
 
+/* Sphere sweep (no reference counterpart; csrc/tirt_sweep.hip / .h): the first contact of a sphere of radius r whose centre moves along c(t) = o + t d
+ * with the scene -- continuous collision for a particle, a link sphere, a thick beam.  A ray on the centre line has no radius and passes between two
+ * triangles the sphere would hit; stepping "Closest point" along the path tunnels through whatever is thinner than the step.
+ * Everything is fp32, every operation in the order written, no contraction; dot, cross, cp_triangle (D2, Q, u, v of a triangle) and cp_sphere (of an
+ * analytic sphere) are those of "Closest point", unchanged.  A comparison with a NaN is false.
+ * Terms.  A query is (o, d, r, B): d is NOT normalised (d = p1 - p0 with B = 1: t is the time of impact within a step), B = tmax, +inf = no bound.
+ *   c(t) = o + d * t.  Formed once per query, the way lim2 is: r2 = r * r, tol = r * 2^-16 + m, rh = r + tol, rhi2 = rh * rh, nn = dot(d, d).
+ *   m is the query's length: with the scene's grid (cell[3], grid_min[3]; C = max(max(cell[0], cell[1]), cell[2]), iE = 1 / (C * 60000),
+ *   rho_0 = max(max(|grid_min[0]|, |grid_min[1]|), |grid_min[2]|) * iE): rho_o = max(max(|o.x - grid_min[0]|, |o.y - grid_min[1]|), |o.z - grid_min[2]|) * iE,
+ *   rho_q = rho_o + r * iE, m = (0.5 + 0.5 * (rho_q + rho_0)) * C -- the margin of the point walks for o with r / E added: half a cell near the scene,
+ *   8e-6 of the extent, and a fixed share of |o| and of r beyond it.  Alpha cut-outs are ignored, as every distance query ignores them; spot and laser
+ *   shapes have no surface.
+ *   root(a, b, c, ok, sg): disc = b*b - a*c; where ok and a > 0 and disc >= 0: (-b + sg * sqrt(disc)) / a; else +inf.
+ * Contact time of a triangle (a, b, c), T: first c0 = cp_triangle(o, a, b, c); code 0 (overlap at the start): c0.D2 <= r2 gives T = 0 with c0's Q, u, v.
+ *   Otherwise, with ab = b - a, ac = c - a, bc = c - b, ca = a - c, ma = o - a, mb = o - b, mc = o - c, the candidates t1 .. t7 (+inf = none):
+ *   code 1, face: n = cross(ab, ac), n2 = dot(n, n), s = dot(n, ma), nd = dot(n, d), sg = s < 0 ? -1 : 1, h = s * sg, v = nd * sg.  Where n2 > 0 (a zero-area
+ *     triangle has no face candidate) and v < 0 (approaching): rl = r * sqrt(n2); where h >= rl (the centre starts at least r from the plane):
+ *     t = (h - rl) / (-v), p = c(t), and t1 = t iff dot(cross(ab, p - a), n) >= 0 and dot(cross(bc, p - b), n) >= 0 and dot(cross(ca, p - c), n) >= 0
+ *     (the touched point's foot lies in the triangle).
+ *   codes 2, 3, 4, the edges (P, e) = (a, ab), (b, bc), (c, ca) with m = o - P (Ericson 5.3.7, the infinite cylinder about the edge's line):
+ *     me = dot(m, e), de = dot(d, e), ee = dot(e, e), A = ee * nn - de * de, k = dot(m, m) - r2, C = ee * k - me * me, Bq = ee * dot(m, d) - de * me,
+ *     t = root(A, Bq, C, true, -1), ax = me + t * de; the candidate is t iff t >= 0 and ax >= 0 and ax <= ee.  A ray parallel to the edge and an edge of
+ *     length 0 have A = 0 and no candidate: the corners' spheres cover the ends.
+ *   codes 5, 6, 7, the corners P = a, b, c with m = o - P: t = root(nn, dot(m, d), dot(m, m) - r2, true, -1); the candidate is t iff t >= 0.
+ *   A candidate whose root is exactly 0 becomes 2^-126, the smallest positive normal number: T = 0 is kept for code 0, overlap by cp_triangle's own
+ *   arithmetic -- exactly where tirt_query_nearest counts a primitive within r of o -- and a start that arithmetic puts an ulp outside r (a sphere resting
+ *   on a floor) has its contact ahead by less than any step: never dropped, never 0.  A candidate outside 0 <= t <= B is none.  Verification: a candidate counts only if cp_triangle(c(t), a, b, c).D2 <= rhi2 -- k_trace's rule, "every
+ *   accepted hit is re-checked": a root that is cancellation noise far from the triangle is rejected, the contact carries its own certificate (the centre
+ *   is within r + tol of the primitive by the library's own distance function) and the verifying call's Q, u, v are the contact's attributes.  T is the
+ *   smallest candidate that verifies, at equal bits the first in code order (candidates are verified smallest first; a failed one is struck out); none: T = +inf,
+ *   code -1.  The candidates are the boundary pieces of the triangle's Minkowski sum with the ball: each lies inside the sum and the true first contact
+ *   on one of them, so in exact arithmetic the smallest candidate in range is the first contact (Ericson 5.5.6's one-shot test is not exact and not used).
+ *   d = 0: nn = 0, no candidate has a root or an approach; only code 0 can answer.
+ * Analytic sphere (centre Cs, radius R), on cp_sphere's distance to the SURFACE: code 0: cp_sphere(o, Cs, R).D2 <= r2 gives T = 0.  Otherwise m = o - Cs,
+ *   mm = dot(m, m), Ro = R + r, Ri = R - r, co = mm - Ro * Ro, ci = mm - Ri * Ri; outside = co > 0, inside = Ri > 0 and ci < 0;
+ *   t = root(nn, dot(m, d), outside ? co : ci, outside or inside, outside ? -1 : +1): code 8 is the smaller root of radius R + r entered from outside,
+ *   code 9 the larger root of radius R - r left from inside; a root of exactly 0 becomes 2^-126, as above.  It counts iff 0 <= t <= B, t < +inf and cp_sphere(c(t), Cs, R).D2 <= rhi2.
+ * The answer: among the primitives with T <= B the smallest T, at equal bits the smallest primitive id -- "Closest point"'s rule on (T, prim): the minimum
+ *   of a total order, independent of the order of the visits.  Nothing qualifies: t = +inf, prim = -1, code = -1, point, uv and normal 0 (the distance
+ *   family's miss, not the ray family's 1e6).  A query with a NaN or infinite coordinate of o or d, with r < 0, NaN or infinite, or with B < 0 or NaN gets
+ *   the miss without a look at any primitive.  r = 0 is allowed: the centre line against the surface BY THESE FORMULAS -- not tirt_query_closest's
+ *   bits, which follow the reference's Moeller-Trumbore test.
+ * Attributes: point = Q and (u, v) of the verifying call (code 0: of c0), in the hit record's convention; normal = w * (1 / sqrt(dot(w, w))) with
+ *   w = c(T) - Q, and (0, 0, 0) where dot(w, w) is not positive.
+ * blocked: 1 iff some primitive has T <= B.  That does not depend on the visiting order; asked for alone, the walk stops at the first accepted contact.
+ * tirt_query_sweep: device memory on the caller's stream with tirt_query_closest_point's plumbing -- asynchronous, no host sync, one launch per chunk of
+ *   "query_chunk_rays", 0 bytes of scratch per query.  Row i of the rays is (o3, d3) at rays + i * ray_stride floats (ray_stride >= 6);
+ *   radius[i * radius_stride] per query, or radius_all for every query when radius is NULL; tmax likewise.  Each output may be NULL: out_t[n], out_prim[n],
+ *   out_code[n], out_point + i * point_stride, out_uv + i * uv_stride, out_normal + i * normal_stride, out_blocked[n] (bytes), counts[n*2] = N_box, N_leaf
+ *   per query (8-byte aligned; only with TIRT_COUNT_NODES).  flags: TIRT_TRAVERSE_EXHAUSTIVE = the scan over all primitive records in id order (the yardstick:
+ *   same bits), TIRT_COUNT_NODES.  The walk grows every box of the 4-wide nodes by (r + tol) + m, enters it by slabs and never culls on equality (the
+ *   argument is in the head of csrc/tirt_sweep.hip); with the answer at T = 0 every leaf whose grown box holds o is still tested, since a smaller id may
+ *   tie.  stack_size 1..4096 entries of 8 bytes per query (the first 16 in LDS, the rest in the context's spill buffer); an entry that does not fit is
+ *   dropped and the query counted in stack_overflow (tirt_stats: TIRT_ERR_STACK).  The queries are not rays: no ray counter moves.
+ *   Refused with TIRT_ERR_ARG before anything is queued: a pointer that is not device memory of ctx's device, ray_stride < 6, radius_stride < 1 with
+ *   radius, tmax_stride < 1 with tmax, point_stride < 3 with out_point, uv_stride < 2 with out_uv, normal_stride < 3 with out_normal, counts not 8-byte
+ *   aligned, other flags, a stack_size outside 1..4096, an LBVH that is not built, a capturing stream.  n == 0 queues nothing.
+ * tirt_sweep: host arrays (rays[n*6], radius[n] or NULL = radius_all, tmax[n] or NULL = +inf, out_point[n*3], out_uv[n*2], out_normal[n*3], out_blocked[n]),
+ *   staged in the context's query scratch (88 bytes per query) and synchronous.
+ * tirt_kat_sweep: explicit operands through the same device functions, one row per thread: rows of 18 floats (o3, d3, r, m, B, a3, b3, c3) or, with
+ *   is_sphere, 13 floats (o3, d3, r, m, B, Cs3, R) -- m is given, not formed -- to rows of 8 floats (T, (float) code, Q3, u, v, the verifying call's D2);
+ *   a miss is (+inf, -1, 0, 0, 0, 0, 0, 0).
+ * tirt_kat_sweep_host: host only, no context: the same rows through the same text compiled for the host. */
+int tirt_query_sweep(tirt_ctx *ctx, const float *rays, int64_t n, int64_t ray_stride, const float *radius, int64_t radius_stride, float radius_all,
+                     const float *tmax, int64_t tmax_stride, float tmax_all, int stack_size, int flags,
+                     float *out_t, int32_t *out_prim, int32_t *out_code, float *out_point, int64_t point_stride, float *out_uv, int64_t uv_stride,
+                     float *out_normal, int64_t normal_stride, uint8_t *out_blocked, int32_t *counts, void *stream);
+int tirt_sweep(tirt_ctx *ctx, const float *rays, int n, const float *radius, float radius_all, const float *tmax, int stack_size, int flags,
+               float *out_t, int32_t *out_prim, int32_t *out_code, float *out_point, float *out_uv, float *out_normal, uint8_t *out_blocked,
+               int32_t *counts);
+int tirt_kat_sweep(tirt_ctx *ctx, const float *in, int n, int is_sphere, float *out);
+int tirt_kat_sweep_host(const float *in, int n, int is_sphere, float *out);
+
 /* Signed distance (no reference counterpart; csrc/tirt_signed_distance.hip, sd_sign in csrc/tirt_closest_point.h): the distance of "Closest point" with the
  * sign of the angle-weighted pseudo-normal of the closest FEATURE -- face, edge or vertex (Baerentzen & Aanaes, "Signed distance computation using the
  * angle weighted pseudonormal", 2005).  The face normal of the winning triangle alone is wrong at sharp and concave vertices and edges, where several

@@ -197,6 +197,11 @@ SIGNATURES = {
     "tirt_kat_tri_tri": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, _f32p]),
     "tirt_kat_tri_tri_host": (C.c_int, [_f32p, C.c_int, C.c_int, _f32p]),
     "tirt_kat_beam_triangle_host": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p]),
+    "tirt_query_sweep": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, _vp, C.c_int64, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp,
+                                   _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp]),
+    "tirt_sweep": (C.c_int, [_vp, _f32p, C.c_int, _vp, C.c_float, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tirt_kat_sweep": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, _f32p]),
+    "tirt_kat_sweep_host": (C.c_int, [_f32p, C.c_int, C.c_int, _f32p]),
     "tirt_query_point_pairs": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
                                          C.c_int64, _vp, C.c_int64, _vp, _vp]),
     "tirt_point_pairs": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1072,6 +1077,46 @@ class Context:
         check(lib().tirt_kat_closest_point(self.handle, rows.reshape(-1), rows.shape[0], 1 if is_sphere else 0, out.reshape(-1)))
         return out
 
+    def query_sweep(self, rays, n, ray_stride, stack_size=64, flags=0, radius=0, radius_stride=1, radius_all=0.0, tmax=0, tmax_stride=1,
+                    tmax_all=float("inf"), out_t=0, out_prim=0, out_code=0, out_point=0, point_stride=3, out_uv=0, uv_stride=2, out_normal=0,
+                    normal_stride=3, out_blocked=0, counts=0, stream=0):
+        """tirt_query_sweep on device memory (include/tirt.h, "Sphere sweep"): every buffer is an integer device address (0 = none), radius = 0 means
+        radius_all and tmax = 0 means tmax_all for every query.  Asynchronous; ti_raytrace_amd.SweepQuery is the torch front end."""
+        check(lib().tirt_query_sweep(self.handle, _vp(int(rays) or None), int(n), int(ray_stride), _vp(int(radius) or None), int(radius_stride),
+                                     float(radius_all), _vp(int(tmax) or None), int(tmax_stride), float(tmax_all), int(stack_size), int(flags),
+                                     _vp(int(out_t) or None), _vp(int(out_prim) or None), _vp(int(out_code) or None), _vp(int(out_point) or None),
+                                     int(point_stride), _vp(int(out_uv) or None), int(uv_stride), _vp(int(out_normal) or None), int(normal_stride),
+                                     _vp(int(out_blocked) or None), _vp(int(counts) or None), _vp(int(stream) or None)))
+
+    def sweep(self, rays, radius, tmax=None, stack_size=64, flags=0, attributes=True, blocked_only=False):
+        """tirt_sweep, the host route: rays (n, 6) float32, radius a float or (n,) float32, tmax None (= inf), a float or (n,) float32 ->
+        a dict of t (n,), prim (n,), code (n,), point (n, 3), uv (n, 2), normal (n, 3) [attributes], blocked (n,) bool, counts (n, 2) [COUNT_NODES];
+        blocked_only: `blocked` (and counts) alone, through the walk that stops at the first contact"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n = rays.shape[0]
+        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (n,)))
+        bound = None if tmax is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (n,)))
+        out = {"blocked": np.zeros(n, np.uint8)}
+        if not blocked_only:
+            out.update(t=np.zeros(n, np.float32), prim=np.zeros(n, np.int32), code=np.zeros(n, np.int32))
+            if attributes:
+                out.update(point=np.zeros((n, 3), np.float32), uv=np.zeros((n, 2), np.float32), normal=np.zeros((n, 3), np.float32))
+        if flags & COUNT_NODES:
+            out["counts"] = np.zeros((n, 2), np.int32)
+        check(lib().tirt_sweep(self.handle, rays.reshape(-1), n, _ptr(rad), 0.0, _ptr(bound), int(stack_size), int(flags), _ptr(out.get("t")),
+                               _ptr(out.get("prim")), _ptr(out.get("code")), _ptr(out.get("point")), _ptr(out.get("uv")), _ptr(out.get("normal")),
+                               _ptr(out["blocked"]), _ptr(out.get("counts"))))
+        out["blocked"] = out["blocked"].view(np.bool_)
+        return out
+
+    def kat_sweep(self, rows, is_sphere=False):
+        """include/tirt.h, tirt_kat_sweep: rows (n, 18) (o, d, r, m, B, a, b, c) or, is_sphere, (n, 13) (o, d, r, m, B, C, R) -> (n, 8): T, code, Q3, u, v, D2"""
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, KAT_SWEEP_ROWS[bool(is_sphere)])
+        out = np.zeros((rows.shape[0], 8), np.float32)
+        if rows.shape[0]:
+            check(lib().tirt_kat_sweep(self.handle, rows.reshape(-1), rows.shape[0], 1 if is_sphere else 0, out.reshape(-1)))
+        return out
+
     def query_signed_distance(self, points, n, point_stride, out_sd, stack_size=64, flags=0, dmax=0, dmax_stride=1, dmax_all=float("inf"), out_d2=0,
                               out_prim=0, out_point=0, point_out_stride=3, out_uv=0, uv_stride=2, counts=0, stream=0):
         """tirt_query_signed_distance on device memory (include/tirt.h, "Signed distance"): query_closest_point with out_sd; the first call after the
@@ -1275,6 +1320,18 @@ def kat_tri_tri_host(rows, what=0):
     out = np.zeros((rows.shape[0], KAT_TRI_TRI_ROWS[what][1]), np.float32)
     if rows.shape[0]:
         check(lib().tirt_kat_tri_tri_host(rows.reshape(-1), rows.shape[0], int(what), out.reshape(-1)))
+    return out
+
+
+KAT_SWEEP_ROWS = {False: 18, True: 13}                              # tirt_kat_sweep[_host]: floats per input row of a triangle / an analytic sphere
+
+
+def kat_sweep_host(rows, is_sphere=False):
+    """include/tirt.h, tirt_kat_sweep_host (host only, no context): Context.kat_sweep's rows through the same text compiled for the host"""
+    rows = np.ascontiguousarray(rows, np.float32).reshape(-1, KAT_SWEEP_ROWS[bool(is_sphere)])
+    out = np.zeros((rows.shape[0], 8), np.float32)
+    if rows.shape[0]:
+        check(lib().tirt_kat_sweep_host(rows.reshape(-1), rows.shape[0], 1 if is_sphere else 0, out.reshape(-1)))
     return out
 
 

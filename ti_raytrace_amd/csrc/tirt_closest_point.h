@@ -37,7 +37,7 @@ __host__ TD CpPoint cp_triangle(const v3 p, const v3 a, const v3 b, const v3 c)
     return r;
 }
 
-TD CpPoint cp_sphere(const v3 p, const v3 c, const float rad)
+__host__ TD CpPoint cp_sphere(const v3 p, const v3 c, const float rad)      // (__host__ too: tirt_kat_sweep_host verifies a contact through it)
 {
     const v3 pc = p - c;
     const float len = tm_sqrt(dot(pc, pc)), d = absf(len - rad);

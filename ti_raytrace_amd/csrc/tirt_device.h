@@ -35,7 +35,7 @@ __host__ TD v3 cross(v3 a, v3 b) { return V(a.y * b.z - a.z * b.y, a.z * b.x - a
 TD float norm(v3 a) { return tm_sqrt(dot(a, a)); }
 // taichi Vector.normalized(): invlen = 1 / norm; invlen * self
 TD v3 normalized(v3 a) { float inv = 1.0f / norm(a); return a * inv; }
-TD float absf(float x) { return x < 0.0f ? -x : x; }
+__host__ TD float absf(float x) { return x < 0.0f ? -x : x; }
 TD float minf(float a, float b) { return a < b ? a : b; }
 TD float maxf(float a, float b) { return a > b ? a : b; }
 TD float clampf(float x, float lo, float hi) { return minf(hi, maxf(lo, x)); }
