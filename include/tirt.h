@@ -880,8 +880,8 @@ int tirt_kat_hit_list(const float *cand, int n, int k, float bound, float *out_l
  *   query counted in stack_overflow (tirt_stats: TIRT_ERR_STACK), as a ray's.  The queries are not rays: no ray counter moves.
  *   Refused with TIRT_ERR_ARG before anything is queued: a pointer that is not device memory of ctx's device, point_stride < 3, point_out_stride < 3
  *   with out_point, uv_stride < 2 with out_uv, dmax_stride < 1 with dmax, other flags, an LBVH that is not built, a capturing stream.  n == 0 queues nothing.
- * tirt_closest_point: host arrays (points[n*3], dmax[n] or NULL = +inf, out_point[n*3], out_uv[n*2]), staged in the context's query scratch (52 bytes
- *   per query) and synchronous, as tirt_trace_closest is to tirt_query_closest.
+ * tirt_closest_point: host arrays (points[n*3], dmax[n] or NULL = +inf, out_point[n*3], out_uv[n*2]), staged in the context's staging buffer (the
+ *   columns that are there, each aligned to its element) and synchronous, as tirt_trace_closest is to tirt_query_closest.
  * tirt_kat_closest_point: D2, Q, u, v of explicit operands through the same device function, one row per thread: rows of 12 floats (p3, a3, b3, c3) or,
  *   with is_sphere, 7 floats (p3, c3, r), to rows of 6 floats (d2, q3, u, v). */
 int tirt_query_closest_point(tirt_ctx *ctx, const float *points, int64_t n, int64_t point_stride,
@@ -916,7 +916,7 @@ int tirt_kat_closest_point(tirt_ctx *ctx, const float *in, int n, int is_sphere,
  *   Refused with TIRT_ERR_ARG before anything is queued, beside tirt_query_closest_point's refusals: k outside 0 .. TIRT_NEAREST_MAX, k == 0 without
  *   out_count, k > 0 with no output at all.  n == 0 queues nothing.
  * tirt_nearest: host arrays (points[n*3], dmax[n] or NULL = +inf, out_d2[n*k], out_prim[n*k], out_point[n*k*3], out_uv[n*k*2], out_count[n], counts[n*2]),
- *   staged (28 + 28 k bytes per query) and synchronous, as tirt_closest_point is to tirt_query_closest_point.
+ *   staged in the context's staging buffer and synchronous, as tirt_closest_point is to tirt_query_closest_point.
  * tirt_kat_nearest_list: host only, no context: the n candidates (d2[i], prim[i]), prim >= 0 and distinct, in the order given through the list code the
  *   kernels run (csrc/tirt_nearest.h) with this k and lim2 (lim2 itself, not a distance: -1 finds nothing).  out_d2[j], out_prim[j] = element j, padded to
  *   k with (+inf, -1); out_info = {entries held, |N|, bits of the threshold's D2, the threshold's id (-1: the list has room)}. */
@@ -978,8 +978,8 @@ int tirt_kat_nearest_list(const float *d2, const int32_t *prim, int n, int k, fl
  *   the answer at D2 = 0 every leaf whose box meets T's box is still tested, since a smaller id may tie -- a deep penetration costs that.
  *   Refused with TIRT_ERR_ARG before anything is queued: a pointer that is not device memory of ctx's device, tri_stride < 9, points_stride < 6 with
  *   out_points, dmax_stride < 1 with dmax, counts not 8-byte aligned, other flags, a stack_size outside 1..4096, an LBVH that is not built, a capturing stream.
- * tirt_mesh_distance: host arrays (tris[n*9], dmax[n] or NULL = +inf, out_points[n*6], counts[n*2]), staged in the context's query scratch (84 bytes per
- *   query) and synchronous, as tirt_closest_point is to tirt_query_closest_point.
+ * tirt_mesh_distance: host arrays (tris[n*9], dmax[n] or NULL = +inf, out_points[n*6], counts[n*2]), staged in the context's staging buffer and
+ *   synchronous, as tirt_closest_point is to tirt_query_closest_point.
  * tirt_kat_tri_tri: explicit operands through the same device functions, one row per thread: what = 0: rows of 18 floats (p0, p1, p2, a, b, c) to 8 floats
  *   (d2, P3, Q3, (float) code); what = 1: seg_seg rows of 12 floats (p1, q1, p2, q2) to (s, t, d2); what = 2: seg_tri rows of 15 floats (x0, x1, a, b, c)
  *   to (hit as 0 / 1, u, v, t).
@@ -1118,7 +1118,7 @@ int tirt_mesh_pairs(tirt_ctx *ctx, const float *tris, int n, const float *dmax, 
  *   radius, tmax_stride < 1 with tmax, point_stride < 3 with out_point, uv_stride < 2 with out_uv, normal_stride < 3 with out_normal, counts not 8-byte
  *   aligned, other flags, a stack_size outside 1..4096, an LBVH that is not built, a capturing stream.  n == 0 queues nothing.
  * tirt_sweep: host arrays (rays[n*6], radius[n] or NULL = radius_all, tmax[n] or NULL = +inf, out_point[n*3], out_uv[n*2], out_normal[n*3], out_blocked[n]),
- *   staged in the context's query scratch (88 bytes per query) and synchronous.
+ *   staged in the context's staging buffer and synchronous.
  * tirt_kat_sweep: explicit operands through the same device functions, one row per thread: rows of 18 floats (o3, d3, r, m, B, a3, b3, c3) or, with
  *   is_sphere, 13 floats (o3, d3, r, m, B, Cs3, R) -- m is given, not formed -- to rows of 8 floats (T, (float) code, Q3, u, v, the verifying call's D2);
  *   a miss is (+inf, -1, 0, 0, 0, 0, 0, 0).

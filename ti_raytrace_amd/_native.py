@@ -426,6 +426,11 @@ def _ptr(arr):
     return None if arr is None else arr.ctypes.data_as(C.c_void_p)
 
 
+def _bound(value, n):
+    """a per-query bound of the host routes (max_distance, tmax, radius): None stays None, a float or (n,) array becomes contiguous (n,) float32"""
+    return None if value is None else np.ascontiguousarray(np.broadcast_to(np.asarray(value, np.float32), (n,)))
+
+
 def _kat_rows(symbol, handle, head, rows, out_stride, words=False, in_stride=None):
     """One known-answer entry over a table of rows: symbol(handle, *head, rows, in_stride, out, out_stride, n) -> the zero-initialised (n, out_stride) float32.
     words: the rows are 32-bit words taken as their bits (integers ride in them); otherwise they are converted to float32."""
@@ -910,7 +915,7 @@ class Context:
         (t (n, k), prim (n, k), record (n, k, 13) or None, count (n,) or None, counts (n, 2) or None [COUNT_NODES])"""
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n, k = rays.shape[0], int(k)
-        bound = None if tmax is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (n,)))
+        bound = _bound(tmax, n)
         t = np.zeros((n, max(k, 0)), np.float32)
         prim = np.zeros((n, max(k, 0)), np.int32)
         rec = np.zeros((n, max(k, 0), 13), np.float32) if attributes else None
@@ -934,9 +939,7 @@ class Context:
         (dist2 (n,), prim (n,), point (n, 3) or None, uv (n, 2) or None, counts (n, 2) or None [COUNT_NODES])"""
         points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
         n = points.shape[0]
-        dmax = None
-        if max_distance is not None:
-            dmax = np.ascontiguousarray(np.broadcast_to(np.asarray(max_distance, np.float32), (n,)))
+        dmax = _bound(max_distance, n)
         d2 = np.zeros(n, np.float32)
         prim = np.zeros(n, np.int32)
         point = np.zeros((n, 3), np.float32) if attributes else None
@@ -960,9 +963,7 @@ class Context:
         (dist2 (n, k), prim (n, k), point (n, k, 3) or None, uv (n, k, 2) or None, count (n,) or None, counts (n, 2) or None [COUNT_NODES])"""
         points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
         n, k = points.shape[0], int(k)
-        dmax = None
-        if max_distance is not None:
-            dmax = np.ascontiguousarray(np.broadcast_to(np.asarray(max_distance, np.float32), (n,)))
+        dmax = _bound(max_distance, n)
         d2 = np.zeros((n, max(k, 0)), np.float32)
         prim = np.zeros((n, max(k, 0)), np.int32)
         point = np.zeros((n, max(k, 0), 3), np.float32) if attributes else None
@@ -987,9 +988,7 @@ class Context:
         (dist2 (n,), prim (n,), code (n,), points (n, 2, 3) [P on the query triangle, Q on the scene] or None, counts (n, 2) or None [COUNT_NODES])"""
         tris = np.ascontiguousarray(tris, np.float32).reshape(-1, 9)
         n = tris.shape[0]
-        dmax = None
-        if max_distance is not None:
-            dmax = np.ascontiguousarray(np.broadcast_to(np.asarray(max_distance, np.float32), (n,)))
+        dmax = _bound(max_distance, n)
         d2 = np.zeros(n, np.float32)
         prim = np.zeros(n, np.int32)
         code = np.zeros(n, np.int32)
@@ -1023,9 +1022,7 @@ class Context:
         width = 9 if tri else 3
         query = np.ascontiguousarray(query, np.float32).reshape(-1, width)
         n = query.shape[0]
-        dmax = None
-        if max_distance is not None:
-            dmax = np.ascontiguousarray(np.broadcast_to(np.asarray(max_distance, np.float32), (n,)))
+        dmax = _bound(max_distance, n)
         row_start = np.zeros(n + 1, np.int64)
         counts = np.zeros((n, 2), np.int32) if (flags & COUNT_NODES) else None
 
@@ -1094,8 +1091,8 @@ class Context:
         blocked_only: `blocked` (and counts) alone, through the walk that stops at the first contact"""
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = rays.shape[0]
-        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (n,)))
-        bound = None if tmax is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (n,)))
+        rad = _bound(radius, n)
+        bound = _bound(tmax, n)
         out = {"blocked": np.zeros(n, np.uint8)}
         if not blocked_only:
             out.update(t=np.zeros(n, np.float32), prim=np.zeros(n, np.int32), code=np.zeros(n, np.int32))
@@ -1131,9 +1128,7 @@ class Context:
         (dist (n,), dist2 (n,), prim (n,), point (n, 3) or None, uv (n, 2) or None, counts (n, 2) or None [COUNT_NODES])"""
         points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
         n = points.shape[0]
-        dmax = None
-        if max_distance is not None:
-            dmax = np.ascontiguousarray(np.broadcast_to(np.asarray(max_distance, np.float32), (n,)))
+        dmax = _bound(max_distance, n)
         sd = np.zeros(n, np.float32)
         d2 = np.zeros(n, np.float32)
         prim = np.zeros(n, np.int32)

@@ -21,6 +21,7 @@
 #include "tirt_internal.h"
 #include "tirt_closest_point.h"
 #include "tirt_point_walk.h"
+#include "tirt_query_stage.h"
 
 namespace tirt {
 
@@ -128,40 +129,24 @@ static int cp_chunks(tirt_ctx *c, const float *points, int64_t n, int64_t point_
                      int stack_size, int flags, int chunk, float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride,
                      float *out_uv, int64_t uv_stride, int2 *counts, float *out_sd = nullptr)      // out_sd: the SIGNED kernels (the table stands: sd_table_ensure)
 {
-    if (ensure_counters(c)) return TIRT_ERR_HIP;
-    const bool scan = (flags & TIRT_TRAVERSE_EXHAUSTIVE) != 0, cnt = (flags & TIRT_COUNT_NODES) != 0;
+    const bool scan = (flags & TIRT_TRAVERSE_EXHAUSTIVE) != 0, cnt = (flags & TIRT_COUNT_NODES) != 0, sgn = out_sd != nullptr;
     CpArgs a = {};
-    a.bvh = bvh_view(c);
-    a.primitive = c->primitive.as<int>(); a.prim_slot = c->prim_slot.as<int>(); a.n_prim = c->n;
     a.point_stride = point_stride; a.dmax_stride = dmax_stride; a.dmax_all = dmax_all;
-    a.stack_size = stack_size; a.point_out_stride = point_out_stride; a.uv_stride = uv_stride;
-    a.ctr = c->dev_counters.as<DevCounters>();
-    const bool sgn = out_sd != nullptr;
+    a.point_out_stride = point_out_stride; a.uv_stride = uv_stride;
     if (sgn) { a.sd_tab = c->sd_tab.as<float4>(); a.sd_state = c->sd_state.as<int>(); }
-    // the walk's grid: a lane for every query of a chunk, as far as the stacks allow (the scan has no stack)
-    int grid_max = 0;
-    if (!scan) if (int rc = point_walk_launch_shape(c, stack_size, CP_WAVES_PER_CU, ((int64_t)(n < chunk ? n : chunk) + CP_BLOCK - 1) / CP_BLOCK, grid_max, a.spill)) return rc;
-    for (int64_t base = 0; base < n; base += chunk) {
-        const int m = (int)(n - base < chunk ? n - base : chunk);
+    return point_walk_chunks(c, a, n, chunk, scan, stack_size, [&](int64_t base, int m, int, int grid) {
         a.n = m;
         a.points = points + base * point_stride; a.dmax = dmax ? dmax + base * dmax_stride : nullptr;
         a.out_d2 = out_d2 ? out_d2 + base : nullptr; a.out_prim = out_prim ? out_prim + base : nullptr;
         a.out_point = out_point ? out_point + base * point_out_stride : nullptr; a.out_uv = out_uv ? out_uv + base * uv_stride : nullptr;
         a.counts = counts ? counts + base : nullptr;
         a.out_sd = sgn ? out_sd + base : nullptr;
-        const int blocks = (m + CP_BLOCK - 1) / CP_BLOCK;
-#define CP_LAUNCH(K, G)                                                                             \
-        do {                                                                                        \
-            if (sgn) { if (cnt) hipLaunchKernelGGL((K<true, true>), dim3(G), dim3(CP_BLOCK), 0, c->stream, a);      \
-                       else hipLaunchKernelGGL((K<false, true>), dim3(G), dim3(CP_BLOCK), 0, c->stream, a); }       \
-            else { if (cnt) hipLaunchKernelGGL((K<true, false>), dim3(G), dim3(CP_BLOCK), 0, c->stream, a);         \
-                   else hipLaunchKernelGGL((K<false, false>), dim3(G), dim3(CP_BLOCK), 0, c->stream, a); }          \
-        } while (0)
-        if (scan) CP_LAUNCH(k_cp_scan, blocks);
-        else { const int g = blocks < grid_max ? blocks : grid_max; CP_LAUNCH(k_cp_walk, g); }
-#undef CP_LAUNCH
-    }
-    return TIRT_OK;
+        with_bool(cnt, [&](auto C) { with_bool(sgn, [&](auto S) {
+            constexpr bool COUNT = decltype(C)::value, SIGNED = decltype(S)::value;
+            if (scan) hipLaunchKernelGGL((k_cp_scan<COUNT, SIGNED>), dim3(grid), dim3(CP_BLOCK), 0, c->stream, a);
+            else hipLaunchKernelGGL((k_cp_walk<COUNT, SIGNED>), dim3(grid), dim3(CP_BLOCK), 0, c->stream, a);
+        }); });
+    });
 }
 
 // tirt_query_closest_point, and with `sgn` tirt_query_signed_distance (the same checks, out_sd beside the other outputs, the table made first)
@@ -170,28 +155,23 @@ static int query_closest_point(tirt_ctx *c, const char *fn, bool sgn, const floa
                                float *out_uv, int64_t uv_stride, int32_t *counts, float *out_sd, void *stream)
 {
     const std::string f = std::string(fn) + ": ";
-    if (int rc = query_common_checks(c, fn, "n", n, stack_size, flags)) return rc;
-    TIRT_REQUIRE(point_stride >= 3, f + "point_stride < 3 (floats per point)");
-    TIRT_REQUIRE(!out_point || point_out_stride >= 3, f + "point_out_stride < 3 (floats per closest point)");
-    TIRT_REQUIRE(!out_uv || uv_stride >= 2, f + "uv_stride < 2");
-    TIRT_REQUIRE(!dmax || dmax_stride >= 1, f + "dmax_stride < 1");
-    TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, f + "counts must be 8-byte aligned");
-    if (int rc = require_caller_stream(c, fn, stream, "queries")) return rc;
+    if (int rc = point_query_checks(c, fn, n, stack_size, flags, {{true, point_stride, 3, "point_stride < 3 (floats per point)"},
+                                    {out_point != nullptr, point_out_stride, 3, "point_out_stride < 3 (floats per closest point)"},
+                                    {out_uv != nullptr, uv_stride, 2, "uv_stride < 2"}, {dmax != nullptr, dmax_stride, 1, "dmax_stride < 1"}}, counts, stream)) return rc;
     if (n == 0) return TIRT_OK;
     TIRT_REQUIRE(points, f + "null points");
     TIRT_REQUIRE(!sgn || out_sd, f + "null out_sd");
-    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
+    const QueryPlan pl = query_plan(c, n, flags, counts);
     if (int rc = require_device_ptrs(c, f, {{points, "points"}, {dmax, "dmax"}, {out_d2, "out_d2"}, {out_prim, "out_prim"}, {out_point, "out_point"}, {out_uv, "out_uv"},
-                                            {sgn ? out_sd : nullptr, "out_sd"}, {want_counts ? counts : nullptr, "counts"}})) return rc;
-    const int chunk = (int)(n < (int64_t)c->query_chunk ? n : (int64_t)c->query_chunk);
+                                            {sgn ? out_sd : nullptr, "out_sd"}, {pl.counts, "counts"}})) return rc;
     if (int rc = query_begin(c, stream)) return rc;
     if (sgn) if (int rc = sd_table_ensure(c, stack_size)) return rc;      // (on the context's stream, after the caller's work: no host sync)
-    if (int rc = cp_chunks(c, points, n, point_stride, dmax, dmax_stride, dmax_all, stack_size, flags, chunk, out_d2, out_prim, out_point,
-                           point_out_stride, out_uv, uv_stride, want_counts ? (int2 *)counts : nullptr, sgn ? out_sd : nullptr)) return rc;
+    if (int rc = cp_chunks(c, points, n, point_stride, dmax, dmax_stride, dmax_all, stack_size, flags, pl.chunk, out_d2, out_prim, out_point,
+                           point_out_stride, out_uv, uv_stride, pl.counts, sgn ? out_sd : nullptr)) return rc;
     return query_end(c, stream);
 }
 
-// host arrays staged in the context's query scratch (query_mem: 52 bytes per query, 56 with out_sd), one chunk of all of them, back with a sync.
+// host arrays staged in device memory (QueryStage), one chunk of all of them, back with a sync.  The walk is handed every output, asked for or not.
 // `sgn`: tirt_signed_distance -- the table is made first and, the stream being waited for anyway, its build's verdict read: TIRT_ERR_STACK, no answers
 static int closest_point_host(tirt_ctx *c, const char *fn, bool sgn, const float *points, int n, const float *dmax, int stack_size, int flags, float *out_d2,
                               int32_t *out_prim, float *out_point, float *out_uv, int32_t *counts, float *out_sd)
@@ -200,33 +180,22 @@ static int closest_point_host(tirt_ctx *c, const char *fn, bool sgn, const float
     if (n == 0) return TIRT_OK;
     TIRT_REQUIRE(points, std::string(fn) + ": null points");
     TIRT_REQUIRE(!sgn || out_sd, std::string(fn) + ": null out_sd");
-    const size_t N = (size_t)n, bytes = N * (sgn ? 56 : 52);
-    hipStream_t st = c->stream;
-    if (bytes > c->query_mem.bytes) {
-        TIRT_HIP(hipStreamSynchronize(st));
-        if (c->query_mem.ensure(bytes)) return TIRT_ERR_HIP;
-    }
-    // counts [n][2] first (8-byte aligned), then points [n][3], dmax [n], d2 [n], prim [n], point [n][3], uv [n][2], sd [n]
-    int2 *d_counts = c->query_mem.as<int2>();
-    float *d_points = (float *)(d_counts + N), *d_dmax = d_points + 3 * N, *d_d2 = d_dmax + N;
-    int32_t *d_prim = (int32_t *)(d_d2 + N);
-    float *d_point = (float *)(d_prim + N), *d_uv = d_point + 3 * N, *d_sd = d_uv + 2 * N;
-    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
-    TIRT_HIP(hipMemcpyAsync(d_points, points, sizeof(float) * 3 * N, hipMemcpyHostToDevice, st));
-    if (dmax) TIRT_HIP(hipMemcpyAsync(d_dmax, dmax, sizeof(float) * N, hipMemcpyHostToDevice, st));
+    const size_t N = (size_t)n;
+    QueryStage s(c);
+    const auto k_points = s.in(points, 3 * N);
+    const auto k_dmax = s.in(dmax, N);
+    const auto k_d2 = s.out(out_d2, N);
+    const auto k_prim = s.out(out_prim, N);
+    const auto k_point = s.out(out_point, 3 * N);
+    const auto k_uv = s.out(out_uv, 2 * N);
+    const auto k_counts = s.out_counts(counts, flags, N);
+    const auto k_sd = s.out(out_sd, N, sgn);
+    if (int rc = s.begin()) return rc;
     if (sgn) if (int rc = sd_table_ensure(c, stack_size)) return rc;
-    if (int rc = cp_chunks(c, d_points, n, 3, dmax ? d_dmax : nullptr, 1, __builtin_inff(), stack_size, flags, n, d_d2, d_prim, d_point, 3, d_uv, 2,
-                           want_counts ? d_counts : nullptr, sgn ? d_sd : nullptr)) return rc;
+    if (int rc = cp_chunks(c, s.ptr(k_points), n, 3, s.ptr(k_dmax), 1, __builtin_inff(), stack_size, flags, n, s.ptr(k_d2), s.ptr(k_prim), s.ptr(k_point), 3,
+                           s.ptr(k_uv), 2, s.ptr(k_counts), s.ptr(k_sd))) return rc;
     if (sgn) if (int rc = sd_table_verdict(c, fn)) return rc;      // (waits for the stream)
-    if (out_d2) TIRT_HIP(hipMemcpyAsync(out_d2, d_d2, sizeof(float) * N, hipMemcpyDeviceToHost, st));
-    if (out_prim) TIRT_HIP(hipMemcpyAsync(out_prim, d_prim, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-    if (out_point) TIRT_HIP(hipMemcpyAsync(out_point, d_point, sizeof(float) * 3 * N, hipMemcpyDeviceToHost, st));
-    if (out_uv) TIRT_HIP(hipMemcpyAsync(out_uv, d_uv, sizeof(float) * 2 * N, hipMemcpyDeviceToHost, st));
-    if (want_counts) TIRT_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int2) * N, hipMemcpyDeviceToHost, st));
-    if (sgn) TIRT_HIP(hipMemcpyAsync(out_sd, d_sd, sizeof(float) * N, hipMemcpyDeviceToHost, st));
-    TIRT_HIP(hipStreamSynchronize(st));
-    TIRT_HIP(hipGetLastError());
-    return TIRT_OK;
+    return s.finish();
 }
 
 // rows of (p3, a3, b3, c3) or (p3, c3, r) -> d2, q3, u, v

@@ -450,10 +450,10 @@ struct tirt_ctx {
     tirt::DevBuf spec_dev;                      // the SpecView again, in device memory (BDPT_SPEC)
     tirt::DevBuf spec_mem; bool spec_set = false; void *spec_view = nullptr;      // spec_view: a heap tirt::SpecView (tirt_spectral.h) with device pointers
 
-    tirt::DevBuf trace_stage;                     // tirt_trace_closest / tirt_trace_shadow (tirt_query.hip): the host rays and the results on their way back
+    tirt::DevBuf trace_stage;                     // the host entries of all queries (QueryStage, tirt_query_stage.h): the host arrays and the results on their way back
     tirt::DevBuf debug_mem;                       // Debug integrator (tirt_debug.hip): hit records + camera directions of the local pixels
-    // ray queries on device memory (tirt_query.hip): one chunk's ray + hit records, option "query_chunk_rays", the two events that order the
-    // context's stream after and before the caller's (made on first use)
+    // queries (tirt_query.hip): the kernels' scratch of one chunk (query_scratch: ray + hit records, lists, block sums), option "query_chunk_rays", the
+    // two events that order the context's stream after and before the caller's (made on first use)
     tirt::DevBuf query_mem; size_t query_chunk = (size_t)1 << 21;
     hipEvent_t query_ev_in = nullptr, query_ev_out = nullptr;
     // signed distance (tirt_signed_distance.hip): sd_tab = float4[n][7] pseudo-normals per primitive id, sd_state = the build's verdict and counts (SdState);
@@ -562,6 +562,17 @@ inline int require_device_ptrs(tirt_ctx *c, const std::string &prefix, std::init
 }
 int require_caller_stream(tirt_ctx *c, const std::string &fn, void *stream, const char *what);
 int query_common_checks(tirt_ctx *c, const char *fn, const char *count, int64_t n, int stack_size, int flags);
+// the checks the point-walk device entries open with, in this order: query_common_checks, the strides of the arrays that are there in the order listed
+// ("`fn`: `text`"), the 8-byte alignment of `counts`, the caller's stream
+struct StrideCheck { bool present; int64_t stride, minimum; const char *text; };
+int point_query_checks(tirt_ctx *c, const char *fn, int64_t n, int stack_size, int flags, std::initializer_list<StrideCheck> strides, const int32_t *counts, void *stream);
+// ... and what they go on with: N_box / N_leaf are written iff the caller gave `counts` and asked for TIRT_COUNT_NODES; a chunk is min(n, option "query_chunk_rays")
+struct QueryPlan { int2 *counts; int chunk; };
+inline QueryPlan query_plan(const tirt_ctx *c, int64_t n, int flags, int32_t *counts)
+{
+    return QueryPlan{counts && (flags & TIRT_COUNT_NODES) ? (int2 *)counts : nullptr, (int)(n < (int64_t)c->query_chunk ? n : (int64_t)c->query_chunk)};
+}
+int query_scratch(tirt_ctx *c, size_t bytes);      // query_mem, the kernels' scratch, of at least `bytes`: growing it waits for the context's stream first
 int query_begin(tirt_ctx *c, void *stream);
 int query_end(tirt_ctx *c, void *stream);
 // tirt_signed_distance.hip: the pseudo-normal table behind the signed queries.  sd_table_ensure queues its build on c->stream where it does not stand (no host

@@ -27,6 +27,7 @@
 #include "tirt_internal.h"
 #include "tirt_closest_point.h"
 #include "tirt_point_walk.h"
+#include "tirt_query_stage.h"
 #include "tirt_nearest.h"
 
 namespace tirt {
@@ -162,46 +163,26 @@ static int nn_chunks(tirt_ctx *c, const float *points, int64_t n, int64_t point_
                      int stack_size, int flags, int chunk, float *out_d2, int32_t *out_prim, float *out_point, int64_t point_out_stride, float *out_uv,
                      int64_t uv_stride, int32_t *out_count, int2 *counts)
 {
-    if (ensure_counters(c)) return TIRT_ERR_HIP;
-    // the scratch of one chunk: (entries, |N|) per query first (8-byte aligned), then the lists.  Growing the buffer waits for the work queued on the
-    // context's stream, which may still read the old one
-    const size_t bytes = (size_t)chunk * (8 + 8 * (size_t)k);
-    if (bytes > c->query_mem.bytes) {
-        TIRT_HIP(hipStreamSynchronize(c->stream));
-        if (c->query_mem.ensure(bytes)) return TIRT_ERR_HIP;
-    }
+    // the scratch of one chunk: (entries, |N|) per query first (8-byte aligned), then the lists
+    if (int rc = query_scratch(c, (size_t)chunk * (8 + 8 * (size_t)k))) return rc;
     const bool scan = (flags & TIRT_TRAVERSE_EXHAUSTIVE) != 0, cnt = (flags & TIRT_COUNT_NODES) != 0, count_all = out_count != nullptr;
     NnArgs a = {};
-    a.bvh = bvh_view(c);
-    a.primitive = c->primitive.as<int>(); a.prim_slot = c->prim_slot.as<int>(); a.n_prim = c->n;
     a.point_stride = point_stride; a.dmax_stride = dmax_stride; a.dmax_all = dmax_all;
-    a.k = k; a.stack_size = stack_size;
+    a.k = k;
     a.meta = c->query_mem.as<int2>(); a.list = (uint2 *)(a.meta + chunk); a.stride = (size_t)chunk;
-    a.ctr = c->dev_counters.as<DevCounters>();
-    // the walk's grid: a lane for every query of a chunk, as far as the stacks allow (the scan has no stack)
-    int grid_max = 0;
-    if (!scan) if (int rc = point_walk_launch_shape(c, stack_size, CP_WAVES_PER_CU, ((int64_t)chunk + CP_BLOCK - 1) / CP_BLOCK, grid_max, a.spill)) return rc;
-    for (int64_t base = 0; base < n; base += chunk) {
-        const int m = (int)(n - base < chunk ? n - base : chunk);
+    return point_walk_chunks(c, a, n, chunk, scan, stack_size, [&](int64_t base, int m, int, int grid) {
         a.n = m;
         a.points = points + base * point_stride; a.dmax = dmax ? dmax + base * dmax_stride : nullptr;
         a.counts = counts ? counts + base : nullptr;
-        const int blocks = (m + CP_BLOCK - 1) / CP_BLOCK;
-        if (scan) {
-            if (cnt) hipLaunchKernelGGL((k_nn_scan<true>), dim3(blocks), dim3(CP_BLOCK), 0, c->stream, a);
-            else hipLaunchKernelGGL((k_nn_scan<false>), dim3(blocks), dim3(CP_BLOCK), 0, c->stream, a);
-        } else {
-            const int g = blocks < grid_max ? blocks : grid_max;
-            if (count_all) { if (cnt) hipLaunchKernelGGL((k_nn_walk<true, true>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a);
-                             else hipLaunchKernelGGL((k_nn_walk<false, true>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a); }
-            else { if (cnt) hipLaunchKernelGGL((k_nn_walk<true, false>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a);
-                   else hipLaunchKernelGGL((k_nn_walk<false, false>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a); }
-        }
+        with_bool(cnt, [&](auto C) {
+            constexpr bool COUNT = decltype(C)::value;
+            if (scan) hipLaunchKernelGGL((k_nn_scan<COUNT>), dim3(grid), dim3(CP_BLOCK), 0, c->stream, a);
+            else with_bool(count_all, [&](auto A) { hipLaunchKernelGGL((k_nn_walk<COUNT, decltype(A)::value>), dim3(grid), dim3(CP_BLOCK), 0, c->stream, a); });
+        });
         const int64_t threads = (int64_t)m * (k > 0 ? k : 1);
         hipLaunchKernelGGL(k_nn_resolve, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, c->stream, a, base, out_d2, out_prim, out_point,
                            point_out_stride, out_uv, uv_stride, out_count);
-    }
-    return TIRT_OK;
+    });
 }
 
 // (the checks of k and of the outputs need no context: they come first)
@@ -224,26 +205,22 @@ int tirt_query_nearest(tirt_ctx *c, const float *points, int64_t n, int64_t poin
     const std::string f = std::string(fn) + ": ";
     NN_K_CHECKS("tirt_query_nearest");
     CTX(c);
-    if (int rc = query_common_checks(c, fn, "n", n, stack_size, flags)) return rc;
-    TIRT_REQUIRE(point_stride >= 3, f + "point_stride < 3 (floats per point)");
-    TIRT_REQUIRE(!out_point || point_out_stride >= 3, f + "point_out_stride < 3 (floats per closest point)");
-    TIRT_REQUIRE(!out_uv || uv_stride >= 2, f + "uv_stride < 2");
-    TIRT_REQUIRE(!dmax || dmax_stride >= 1, f + "dmax_stride < 1");
-    TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, f + "counts must be 8-byte aligned");
-    if (int rc = require_caller_stream(c, fn, stream, "queries")) return rc;
+    if (int rc = point_query_checks(c, fn, n, stack_size, flags, {{true, point_stride, 3, "point_stride < 3 (floats per point)"},
+                                    {out_point != nullptr, point_out_stride, 3, "point_out_stride < 3 (floats per closest point)"},
+                                    {out_uv != nullptr, uv_stride, 2, "uv_stride < 2"}, {dmax != nullptr, dmax_stride, 1, "dmax_stride < 1"}}, counts, stream)) return rc;
     if (n == 0) return TIRT_OK;
     TIRT_REQUIRE(points, f + "null points");
-    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
+    int2 *const want_counts = query_plan(c, n, flags, counts).counts;
     if (int rc = require_device_ptrs(c, f, {{points, "points"}, {dmax, "dmax"}, {out_d2, "out_d2"}, {out_prim, "out_prim"}, {out_point, "out_point"}, {out_uv, "out_uv"},
-                                            {out_count, "out_count"}, {want_counts ? counts : nullptr, "counts"}})) return rc;
+                                            {out_count, "out_count"}, {want_counts, "counts"}})) return rc;
     if (int rc = query_begin(c, stream)) return rc;
     if (int rc = nn_chunks(c, points, n, point_stride, dmax, dmax_stride, dmax_all, k, stack_size, flags, nn_chunk_of(c, n, k), out_d2, out_prim, out_point,
-                           point_out_stride, out_uv, uv_stride, out_count, want_counts ? (int2 *)counts : nullptr)) return rc;
+                           point_out_stride, out_uv, uv_stride, out_count, want_counts)) return rc;
     return query_end(c, stream);
 }
 
-// host arrays staged in the context's staging buffer (counts [n][2] first: 8-byte aligned; points [n][3], dmax [n], count [n], d2 [n][k], prim [n][k],
-// point [n][k][3], uv [n][k][2]: 28 + 28 k bytes per query), through the chunks above, back to the host with a sync
+// host arrays staged in device memory (QueryStage), through the chunks above, back to the host with a sync.  The walk is handed the outputs the caller
+// asked for, and no others
 int tirt_nearest(tirt_ctx *c, const float *points, int n, const float *dmax, int k, int stack_size, int flags, float *out_d2, int32_t *out_prim,
                  float *out_point, float *out_uv, int32_t *out_count, int32_t *counts)
 {
@@ -254,29 +231,19 @@ int tirt_nearest(tirt_ctx *c, const float *points, int n, const float *dmax, int
     if (n == 0) return TIRT_OK;
     TIRT_REQUIRE(points, std::string(fn) + ": null points");
     const size_t N = (size_t)n, K = (size_t)k;
-    hipStream_t st = c->stream;
-    if (c->trace_stage.ensure(N * (28 + 28 * K))) return TIRT_ERR_HIP;      // (used by the host routes alone, and each of their calls ends with a sync)
-    int2 *d_counts = c->trace_stage.as<int2>();
-    float *d_points = (float *)(d_counts + N), *d_dmax = d_points + 3 * N;
-    int32_t *d_count = (int32_t *)(d_dmax + N);
-    float *d_d2 = (float *)(d_count + N);
-    int32_t *d_prim = (int32_t *)(d_d2 + K * N);
-    float *d_point = (float *)(d_prim + K * N), *d_uv = d_point + 3 * K * N;
-    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
-    TIRT_HIP(hipMemcpyAsync(d_points, points, sizeof(float) * 3 * N, hipMemcpyHostToDevice, st));
-    if (dmax) TIRT_HIP(hipMemcpyAsync(d_dmax, dmax, sizeof(float) * N, hipMemcpyHostToDevice, st));
-    if (int rc = nn_chunks(c, d_points, n, 3, dmax ? d_dmax : nullptr, 1, __builtin_inff(), k, stack_size, flags, nn_chunk_of(c, n, k), out_d2 ? d_d2 : nullptr,
-                           out_prim ? d_prim : nullptr, out_point ? d_point : nullptr, 3, out_uv ? d_uv : nullptr, 2, out_count ? d_count : nullptr,
-                           want_counts ? d_counts : nullptr)) return rc;
-    if (out_d2 && k) TIRT_HIP(hipMemcpyAsync(out_d2, d_d2, sizeof(float) * K * N, hipMemcpyDeviceToHost, st));
-    if (out_prim && k) TIRT_HIP(hipMemcpyAsync(out_prim, d_prim, sizeof(int32_t) * K * N, hipMemcpyDeviceToHost, st));
-    if (out_point && k) TIRT_HIP(hipMemcpyAsync(out_point, d_point, sizeof(float) * 3 * K * N, hipMemcpyDeviceToHost, st));
-    if (out_uv && k) TIRT_HIP(hipMemcpyAsync(out_uv, d_uv, sizeof(float) * 2 * K * N, hipMemcpyDeviceToHost, st));
-    if (out_count) TIRT_HIP(hipMemcpyAsync(out_count, d_count, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-    if (want_counts) TIRT_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int2) * N, hipMemcpyDeviceToHost, st));
-    TIRT_HIP(hipStreamSynchronize(st));
-    TIRT_HIP(hipGetLastError());
-    return TIRT_OK;
+    QueryStage s(c);
+    const auto k_points = s.in(points, 3 * N);
+    const auto k_dmax = s.in(dmax, N);
+    const auto k_count = s.out(out_count, N, out_count != nullptr);
+    const auto k_d2 = s.out(out_d2, K * N, out_d2 != nullptr);
+    const auto k_prim = s.out(out_prim, K * N, out_prim != nullptr);
+    const auto k_point = s.out(out_point, 3 * K * N, out_point != nullptr);
+    const auto k_uv = s.out(out_uv, 2 * K * N, out_uv != nullptr);
+    const auto k_counts = s.out_counts(counts, flags, N);
+    if (int rc = s.begin()) return rc;
+    if (int rc = nn_chunks(c, s.ptr(k_points), n, 3, s.ptr(k_dmax), 1, __builtin_inff(), k, stack_size, flags, nn_chunk_of(c, n, k), s.ptr(k_d2), s.ptr(k_prim),
+                           s.ptr(k_point), 3, s.ptr(k_uv), 2, s.ptr(k_count), s.ptr(k_counts))) return rc;
+    return s.finish();
 }
 
 // host only, no context: candidates (d2[i], prim[i]) in the order given through NnList (tirt_nearest.h), the text k_nn_walk and k_nn_scan run

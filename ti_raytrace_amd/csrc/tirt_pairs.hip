@@ -30,6 +30,7 @@
 #include "tirt_closest_point.h"
 #include "tirt_triangle_query.h"
 #include "tirt_point_walk.h"
+#include "tirt_query_stage.h"
 #include "tirt_nearest.h"
 #include "tirt_pairs.h"
 
@@ -401,62 +402,42 @@ static int pairs_arg_checks(const std::string &f, const PairsCall &p)
 // the launches of a call on the context's stream; every pointer is device memory (or null)
 static int pairs_run(tirt_ctx *c, const PairsCall &p)
 {
-    if (ensure_counters(c)) return TIRT_ERR_HIP;
     const bool scan = (p.flags & TIRT_TRAVERSE_EXHAUSTIVE) != 0, cnt = (p.flags & TIRT_COUNT_NODES) != 0, ordered = (p.flags & TIRT_PAIRS_UNORDERED) == 0;
     const bool count = p.mode != TIRT_PAIRS_FILL, fill = p.mode != TIRT_PAIRS_COUNT && p.capacity > 0;      // (no row that has a pair fits arrays of 0 pairs)
     const int64_t n = p.n;
-    const int chunk = (int)(n < (int64_t)c->query_chunk ? n : (int64_t)c->query_chunk);
-    // the scan's block sums: the only scratch (8 bytes per PAIRS_SCAN_BLOCK queries).  Growing the buffer waits for the work queued on the context's stream
+    // the scan's block sums: the only scratch (8 bytes per PAIRS_SCAN_BLOCK queries)
     const int64_t nb = pairs_scan_blocks(n);
-    if (count && (size_t)nb * 8 > c->query_mem.bytes) {
-        TIRT_HIP(hipStreamSynchronize(c->stream));
-        if (c->query_mem.ensure((size_t)nb * 8)) return TIRT_ERR_HIP;
-    }
+    if (count) if (int rc = query_scratch(c, (size_t)nb * 8)) return rc;
     PairArgs a = {};
-    a.bvh = bvh_view(c);
-    a.primitive = c->primitive.as<int>(); a.prim_slot = c->prim_slot.as<int>(); a.n_prim = c->n;
     a.query_stride = p.query_stride; a.dmax_stride = p.dmax_stride; a.dmax_all = p.dmax_all;
-    a.stack_size = p.stack_size;
     a.capacity = p.capacity;
     a.out_d2 = p.out_d2; a.out_prim = p.out_prim; a.out_code = p.out_code;
-    a.ctr = c->dev_counters.as<DevCounters>();
-    int grid_max = 0;
-    if (!scan) if (int rc = point_walk_launch_shape(c, p.stack_size, CP_WAVES_PER_CU, ((int64_t)chunk + CP_BLOCK - 1) / CP_BLOCK, grid_max, a.spill)) return rc;
     // one walk (or scan) per chunk; FILL = false leaves the lengths, FILL = true writes the rows.  N_box / N_leaf come from the counting walk, or from the
     // filling walk of a FILL call
-#define PAIRS_LAUNCH(KW, KS, FILL_, CNT_)                                                                                             \
-    do {                                                                                                                            \
-        if (scan) hipLaunchKernelGGL((KS<FILL_>), dim3(blocks), dim3(CP_BLOCK), 0, c->stream, a);                                   \
-        else hipLaunchKernelGGL((KW<CNT_, FILL_>), dim3(blocks < grid_max ? blocks : grid_max), dim3(CP_BLOCK), 0, c->stream, a);   \
-    } while (0)
     auto walks = [&](bool filling, bool with_counts) {
-        for (int64_t base = 0; base < n; base += chunk) {
-            const int m = (int)(n - base < chunk ? n - base : chunk);
+        return point_walk_chunks(c, a, n, query_plan(c, n, p.flags, nullptr).chunk, scan, p.stack_size, [&](int64_t base, int m, int, int grid) {
             a.n = m;
             a.query = p.query + base * p.query_stride; a.dmax = p.dmax ? p.dmax + base * p.dmax_stride : nullptr;
             a.row_start = p.row_start + base;
             a.counts = with_counts && p.counts ? p.counts + base : nullptr;
-            const int blocks = (m + CP_BLOCK - 1) / CP_BLOCK;
-            const bool cn = cnt && with_counts;
-            if (p.tri) {
-                if (filling) { if (cn) PAIRS_LAUNCH(k_tqp_walk, k_tqp_scan, true, true); else PAIRS_LAUNCH(k_tqp_walk, k_tqp_scan, true, false); }
-                else { if (cn) PAIRS_LAUNCH(k_tqp_walk, k_tqp_scan, false, true); else PAIRS_LAUNCH(k_tqp_walk, k_tqp_scan, false, false); }
-            } else {
-                if (filling) { if (cn) PAIRS_LAUNCH(k_pp_walk, k_pp_scan, true, true); else PAIRS_LAUNCH(k_pp_walk, k_pp_scan, true, false); }
-                else { if (cn) PAIRS_LAUNCH(k_pp_walk, k_pp_scan, false, true); else PAIRS_LAUNCH(k_pp_walk, k_pp_scan, false, false); }
-            }
-        }
+            with_bool(filling, [&](auto F) { with_bool(cnt && with_counts, [&](auto C) {
+                constexpr bool FILL = decltype(F)::value, COUNT = decltype(C)::value;
+                if (scan) { if (p.tri) hipLaunchKernelGGL((k_tqp_scan<FILL>), dim3(grid), dim3(CP_BLOCK), 0, c->stream, a);
+                            else hipLaunchKernelGGL((k_pp_scan<FILL>), dim3(grid), dim3(CP_BLOCK), 0, c->stream, a); }
+                else { if (p.tri) hipLaunchKernelGGL((k_tqp_walk<COUNT, FILL>), dim3(grid), dim3(CP_BLOCK), 0, c->stream, a);
+                       else hipLaunchKernelGGL((k_pp_walk<COUNT, FILL>), dim3(grid), dim3(CP_BLOCK), 0, c->stream, a); }
+            }); });
+        });
     };
-#undef PAIRS_LAUNCH
     if (count) {
-        walks(false, true);
+        if (int rc = walks(false, true)) return rc;
         int64_t *sums = c->query_mem.as<int64_t>();
         hipLaunchKernelGGL(k_pairs_block_sum, dim3((unsigned)nb), dim3(PAIRS_SCAN_BLOCK), 0, c->stream, (const int64_t *)(p.row_start + 1), n, sums);
         hipLaunchKernelGGL(k_pairs_scan_sums, dim3(1), dim3(PAIRS_SCAN_BLOCK), 0, c->stream, sums, nb);
         hipLaunchKernelGGL(k_pairs_scan_add, dim3((unsigned)nb), dim3(PAIRS_SCAN_BLOCK), 0, c->stream, p.row_start, n, (const int64_t *)sums);
     }
     if (fill) {
-        walks(true, !count);
+        if (int rc = walks(true, !count)) return rc;
         // a wave per row, as many as keep the device busy
         const int64_t rows_grid = (int64_t)c->cu_count * 32;
         const unsigned g = (unsigned)(n < rows_grid ? n : rows_grid);
@@ -479,17 +460,11 @@ static int pairs_query(tirt_ctx *c, const char *fn, PairsCall p, int32_t *counts
     const std::string f = std::string(fn) + ": ";
     if (int rc = pairs_arg_checks(f, p)) return rc;
     CTX(c);
-    if (int rc = query_common_checks(c, fn, "n", p.n, p.stack_size, p.flags & ~TIRT_PAIRS_UNORDERED)) return rc;
-    const int64_t qmin = p.tri ? 9 : 3;
-    TIRT_REQUIRE(p.query_stride >= qmin, f + (p.tri ? "tri_stride < 9 (floats per triangle)" : "point_stride < 3 (floats per point)"));
-    if (p.tri) TIRT_REQUIRE(!p.attr0 || p.attr0_stride >= 6, f + "points_stride < 6 (floats per pair of closest points)");
-    else {
-        TIRT_REQUIRE(!p.attr0 || p.attr0_stride >= 3, f + "point_out_stride < 3 (floats per closest point)");
-        TIRT_REQUIRE(!p.attr1 || p.attr1_stride >= 2, f + "uv_stride < 2");
-    }
-    TIRT_REQUIRE(!p.dmax || p.dmax_stride >= 1, f + "dmax_stride < 1");
-    TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, f + "counts must be 8-byte aligned");
-    if (int rc = require_caller_stream(c, fn, stream, "queries")) return rc;
+    const StrideCheck q_stride = p.tri ? StrideCheck{true, p.query_stride, 9, "tri_stride < 9 (floats per triangle)"} : StrideCheck{true, p.query_stride, 3, "point_stride < 3 (floats per point)"};
+    const StrideCheck a0_stride = p.tri ? StrideCheck{p.attr0 != nullptr, p.attr0_stride, 6, "points_stride < 6 (floats per pair of closest points)"}
+                                        : StrideCheck{p.attr0 != nullptr, p.attr0_stride, 3, "point_out_stride < 3 (floats per closest point)"};
+    if (int rc = point_query_checks(c, fn, p.n, p.stack_size, p.flags & ~TIRT_PAIRS_UNORDERED, {q_stride, a0_stride, {!p.tri && p.attr1, p.attr1_stride, 2, "uv_stride < 2"},
+                                    {p.dmax != nullptr, p.dmax_stride, 1, "dmax_stride < 1"}}, counts, stream)) return rc;
     const bool fill = p.mode != TIRT_PAIRS_COUNT && p.capacity > 0;
     if (!fill) { p.out_d2 = nullptr; p.out_prim = nullptr; p.out_code = nullptr; p.attr0 = nullptr; p.attr1 = nullptr; }      // COUNT writes row_start and nothing else
     if (int rc = require_device_ptrs(c, f, {{p.row_start, "row_start"}})) return rc;
@@ -500,8 +475,7 @@ static int pairs_query(tirt_ctx *c, const char *fn, PairsCall p, int32_t *counts
         return query_end(c, stream);
     }
     TIRT_REQUIRE(p.query, f + (p.tri ? "null tris" : "null points"));
-    const bool want_counts = counts && (p.flags & TIRT_COUNT_NODES);
-    p.counts = want_counts ? (int2 *)counts : nullptr;
+    p.counts = query_plan(c, p.n, p.flags, counts).counts;
     if (int rc = require_device_ptrs(c, f, {{p.query, p.tri ? "tris" : "points"}, {p.dmax, "dmax"}, {p.out_d2, "out_d2"}, {p.out_prim, "out_prim"}, {p.out_code, "out_code"},
                                             {p.attr0, p.tri ? "out_points" : "out_point"}, {p.attr1, "out_uv"}, {p.counts, "counts"}})) return rc;
     if (int rc = query_begin(c, stream)) return rc;
@@ -509,9 +483,8 @@ static int pairs_query(tirt_ctx *c, const char *fn, PairsCall p, int32_t *counts
     return query_end(c, stream);
 }
 
-// the host entry of both kinds: host arrays staged in the context's staging buffer -- counts [n][2] and row_start [n + 1] first (8-byte aligned), the
-// queries, dmax [n], then per pair of the capacity d2, prim, code and the attributes --, through pairs_run, back to the host with a sync.  Only the rows
-// that were written come back: what lies behind them in the caller's arrays stays as it was
+// the host entry of both kinds: host arrays staged in device memory (QueryStage; the per-pair columns hold `capacity` pairs), through pairs_run, back to
+// the host with a sync.  Only the rows that were written come back: what lies behind them in the caller's arrays stays as it was
 static int pairs_host(tirt_ctx *c, const char *fn, PairsCall p, int32_t *counts)
 {
     const std::string f = std::string(fn) + ": ";
@@ -521,45 +494,38 @@ static int pairs_host(tirt_ctx *c, const char *fn, PairsCall p, int32_t *counts)
     const bool fill = p.mode != TIRT_PAIRS_COUNT && p.capacity > 0;
     if (p.n == 0) { if (p.mode != TIRT_PAIRS_FILL) p.row_start[0] = 0; return TIRT_OK; }
     TIRT_REQUIRE(p.query, f + (p.tri ? "null tris" : "null points"));
-    const size_t N = (size_t)p.n, QW = p.tri ? 9 : 3, CAP = fill ? (size_t)p.capacity : 0;
-    const size_t attr_w = p.tri ? 6 : 5;      // floats of attributes per pair: P, Q or Q, u, v
-    hipStream_t st = c->stream;
-    if (c->trace_stage.ensure(N * (8 + 8 + 4 * QW + 4) + 8 + CAP * (12 + 4 * attr_w))) return TIRT_ERR_HIP;      // (used by the host routes alone, and each of their calls ends with a sync)
-    int2 *d_counts = c->trace_stage.as<int2>();
-    int64_t *d_row = (int64_t *)(d_counts + N);
-    float *d_query = (float *)(d_row + N + 1), *d_dmax = d_query + QW * N, *d_d2 = d_dmax + N;
-    int32_t *d_prim = (int32_t *)(d_d2 + CAP), *d_code = d_prim + CAP;
-    float *d_a0 = (float *)(d_code + CAP), *d_a1 = d_a0 + (p.tri ? 6 : 3) * CAP;
-    const bool want_counts = counts && (p.flags & TIRT_COUNT_NODES);
-    int64_t *h_row = p.row_start; float *h_d2 = p.out_d2; int32_t *h_prim = p.out_prim, *h_code = p.out_code; float *h_a0 = p.attr0, *h_a1 = p.attr1;
-    TIRT_HIP(hipMemcpyAsync(d_query, p.query, sizeof(float) * QW * N, hipMemcpyHostToDevice, st));
-    if (p.dmax) TIRT_HIP(hipMemcpyAsync(d_dmax, p.dmax, sizeof(float) * N, hipMemcpyHostToDevice, st));
-    if (p.mode == TIRT_PAIRS_FILL) TIRT_HIP(hipMemcpyAsync(d_row, h_row, sizeof(int64_t) * (N + 1), hipMemcpyHostToDevice, st));
-    p.query = d_query; p.query_stride = (int64_t)QW; p.dmax = p.dmax ? d_dmax : nullptr; p.dmax_stride = 1; p.dmax_all = __builtin_inff();
-    p.row_start = d_row;
+    const size_t N = (size_t)p.n, QW = p.tri ? 9 : 3, CAP = fill ? (size_t)p.capacity : 0, A0 = p.tri ? 6 : 3;      // A0: floats of attr0 per pair (P, Q or Q)
+    const int64_t *h_row = p.row_start;
+    QueryStage s(c);
+    const auto k_row = p.mode == TIRT_PAIRS_FILL ? s.in(p.row_start, N + 1) : s.out(p.row_start, N + 1);
+    const auto k_query = s.in(p.query, QW * N);
+    const auto k_dmax = s.in(p.dmax, N);
     // (the key of the order needs d2 and prim on the device whichever of them the caller wants back)
-    p.out_d2 = fill ? d_d2 : nullptr; p.out_prim = fill ? d_prim : nullptr; p.out_code = fill && p.tri && h_code ? d_code : nullptr;
-    p.attr0 = fill && h_a0 ? d_a0 : nullptr; p.attr0_stride = p.tri ? 6 : 3;
-    p.attr1 = fill && h_a1 ? d_a1 : nullptr; p.attr1_stride = 2;
-    p.counts = want_counts ? d_counts : nullptr;
+    const auto k_d2 = s.out(p.out_d2, CAP, fill);
+    const auto k_prim = s.out(p.out_prim, CAP, fill);
+    const auto k_code = s.out(p.out_code, CAP, fill && p.tri && p.out_code);
+    const auto k_a0 = s.out(p.attr0, A0 * CAP, fill && p.attr0);
+    const auto k_a1 = s.out(p.attr1, 2 * CAP, fill && p.attr1);
+    const auto k_counts = s.out_counts(counts, p.flags, N);
+    if (int rc = s.begin()) return rc;
+    p.query = s.ptr(k_query); p.query_stride = (int64_t)QW; p.dmax = s.ptr(k_dmax); p.dmax_stride = 1; p.dmax_all = __builtin_inff();
+    p.row_start = s.ptr(k_row);
+    p.out_d2 = s.ptr(k_d2); p.out_prim = s.ptr(k_prim); p.out_code = s.ptr(k_code);
+    p.attr0 = s.ptr(k_a0); p.attr0_stride = (int64_t)A0;
+    p.attr1 = s.ptr(k_a1); p.attr1_stride = 2;
+    p.counts = s.ptr(k_counts);
     if (int rc = pairs_run(c, p)) return rc;
-    if (p.mode != TIRT_PAIRS_FILL) TIRT_HIP(hipMemcpyAsync(h_row, d_row, sizeof(int64_t) * (N + 1), hipMemcpyDeviceToHost, st));
-    if (want_counts) TIRT_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int2) * N, hipMemcpyDeviceToHost, st));
-    TIRT_HIP(hipStreamSynchronize(st));
-    if (fill) {
-        size_t written = 0;      // the rows that fit are a prefix of the rows
-        for (size_t i = 0; i < N && pairs_row_fits(h_row[i], h_row[i + 1], p.capacity); i++) written = (size_t)h_row[i + 1];
-        if (written) {
-            if (h_d2) TIRT_HIP(hipMemcpyAsync(h_d2, d_d2, sizeof(float) * written, hipMemcpyDeviceToHost, st));
-            if (h_prim) TIRT_HIP(hipMemcpyAsync(h_prim, d_prim, sizeof(int32_t) * written, hipMemcpyDeviceToHost, st));
-            if (p.out_code) TIRT_HIP(hipMemcpyAsync(h_code, d_code, sizeof(int32_t) * written, hipMemcpyDeviceToHost, st));
-            if (p.attr0) TIRT_HIP(hipMemcpyAsync(h_a0, d_a0, sizeof(float) * (p.tri ? 6 : 3) * written, hipMemcpyDeviceToHost, st));
-            if (p.attr1) TIRT_HIP(hipMemcpyAsync(h_a1, d_a1, sizeof(float) * 2 * written, hipMemcpyDeviceToHost, st));
-            TIRT_HIP(hipStreamSynchronize(st));
-        }
-    }
-    TIRT_HIP(hipGetLastError());
-    return TIRT_OK;
+    if (int rc = s.fetch(k_row)) return rc;
+    if (int rc = s.fetch(k_counts)) return rc;
+    if (int rc = s.sync()) return rc;
+    size_t written = 0;      // the rows that fit are a prefix of the rows
+    for (size_t i = 0; fill && i < N && pairs_row_fits(h_row[i], h_row[i + 1], p.capacity); i++) written = (size_t)h_row[i + 1];
+    if (int rc = s.fetch(k_d2, written)) return rc;
+    if (int rc = s.fetch(k_prim, written)) return rc;
+    if (int rc = s.fetch(k_code, written)) return rc;
+    if (int rc = s.fetch(k_a0, A0 * written)) return rc;
+    if (int rc = s.fetch(k_a1, 2 * written)) return rc;
+    return s.finish();
 }
 
 }  // namespace tirt

@@ -6,7 +6,8 @@
 //   k_multi_hit (tirt_multi_hit.hip)        PointStack<int> and the grid sizing alone (a ray's walk)
 // Here: the margin by which a child's decoded box is grown and the distance of an interval to it (PointMargin, CP_BOX_GAP; CP_AXIS_GAP for a point), the
 // stack of one lane (PointStack), THE WALK (point_walk) with the end of its kernels (point_walk_count_overflow), what its kernels and their scans read
-// (cp_load_query, cp_finite3, cp_record), and on the host the grid whose stacks fit (point_walk_grid, point_walk_launch_shape).
+// (cp_load_query, cp_finite3, cp_record), and on the host the grid whose stacks fit (point_walk_grid, point_walk_launch_shape) and the launches of a call in
+// chunks (point_walk_chunks, with point_walk_args and with_bool).
 // A wave is a block (CP_BLOCK lanes, no barrier anywhere): a lane holds one query and the blocks stride over the work.
 //
 // WHY THE CULL IS CONSERVATIVE.  point_walk skips a subtree on lb2 > cut only, never on equality -- at a node (`kept`) and at a pop (pop_live) -- and the
@@ -222,6 +223,35 @@ inline int point_walk_launch_shape(tirt_ctx *c, int stack_size, int waves_per_cu
         if (c->spill.ensure(want)) return TIRT_ERR_HIP;
     }
     if (tail) spill = c->spill.as<E>();
+    return TIRT_OK;
+}
+
+// ---- the launches of a call, shared by cp_chunks, nn_chunks, tq_chunks, sw_chunks and pairs_run
+// the fields every walk's Args has (CpArgs, NnArgs, TqArgs, SwArgs, PairArgs: the same names); after ensure_counters
+template <class Args>
+inline void point_walk_args(tirt_ctx *c, int stack_size, Args &a)
+{
+    a.bvh = bvh_view(c);
+    a.primitive = c->primitive.as<int>(); a.prim_slot = c->prim_slot.as<int>(); a.n_prim = c->n;
+    a.stack_size = stack_size;
+    a.ctr = c->dev_counters.as<DevCounters>();
+}
+// a runtime bool as a template argument: f(std::true_type()) or f(std::false_type())
+template <class F> inline void with_bool(bool b, F f) { if (b) f(std::true_type()); else f(std::false_type()); }
+// `n` queries in chunks of `chunk`: the counters, the shared fields of `a`, the walk's grid -- a lane for every query of a chunk, as far as the stacks allow
+// (the scan has no stack: a block per CP_BLOCK queries) -- and f(base, m, blocks, grid) per chunk of m queries in `blocks` blocks, to launch on `grid` of them
+template <class Args, class F>
+inline int point_walk_chunks(tirt_ctx *c, Args &a, int64_t n, int chunk, bool scan, int stack_size, F f)
+{
+    if (ensure_counters(c)) return TIRT_ERR_HIP;
+    point_walk_args(c, stack_size, a);
+    int grid_max = 0;
+    if (!scan) if (int rc = point_walk_launch_shape(c, stack_size, CP_WAVES_PER_CU, ((int64_t)(n < chunk ? n : chunk) + CP_BLOCK - 1) / CP_BLOCK, grid_max, a.spill)) return rc;
+    for (int64_t base = 0; base < n; base += chunk) {
+        const int m = (int)(n - base < chunk ? n - base : chunk);
+        const int blocks = (m + CP_BLOCK - 1) / CP_BLOCK;
+        f(base, m, blocks, scan || blocks < grid_max ? blocks : grid_max);
+    }
     return TIRT_OK;
 }
 

@@ -17,6 +17,7 @@
 // tmax (or a miss) otherwise.  Rays from far away (no culling), the exhaustive walk and tmax <= 0 / NaN (no bound) end with the full closest
 // hit.  A miss leaves t = INF_VALUE (1e6, the reference's value), which is why the test is not a bare t < tmax.
 #include "tirt_trace.h"
+#include "tirt_query_stage.h"
 
 namespace tirt {
 
@@ -104,6 +105,13 @@ int query_common_checks(tirt_ctx *c, const char *fn, const char *count, int64_t 
     TIRT_REQUIRE((flags & ~(TIRT_TRAVERSE_EXHAUSTIVE | TIRT_COUNT_NODES)) == 0, std::string(fn) + ": unknown flags");
     return TIRT_OK;
 }
+int point_query_checks(tirt_ctx *c, const char *fn, int64_t n, int stack_size, int flags, std::initializer_list<StrideCheck> strides, const int32_t *counts, void *stream)
+{
+    if (int rc = query_common_checks(c, fn, "n", n, stack_size, flags)) return rc;
+    for (const StrideCheck &s : strides) TIRT_REQUIRE(!s.present || s.stride >= s.minimum, std::string(fn) + ": " + s.text);
+    TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, std::string(fn) + ": counts must be 8-byte aligned");
+    return require_caller_stream(c, fn, stream, "queries");
+}
 static int ray_query_checks(tirt_ctx *c, const char *fn, int64_t nr, int64_t ray_stride, int stack_size, int flags, void *stream)
 {
     if (int rc = query_common_checks(c, fn, "nr", nr, stack_size, flags)) return rc;
@@ -111,21 +119,26 @@ static int ray_query_checks(tirt_ctx *c, const char *fn, int64_t nr, int64_t ray
     return require_caller_stream(c, fn, stream, "queries");
 }
 
-// Scratch of one chunk of `chunk` rays (ray records, then hit records).  Growing the buffer waits for the work queued on the context's
-// stream, which may still read the old one.
-static int query_prepare(tirt_ctx *c, int chunk, float4 *&rec, float4 *&hit)
+// The kernels' scratch (query_mem) of at least `bytes`.  Growing the buffer waits for the work queued on the context's stream, which may still
+// read the old one.
+int query_scratch(tirt_ctx *c, size_t bytes)
 {
-    const size_t bytes = (size_t)chunk * 48;
     if (bytes > c->query_mem.bytes) {
         TIRT_HIP(hipStreamSynchronize(c->stream));
         if (c->query_mem.ensure(bytes)) return TIRT_ERR_HIP;
     }
+    return TIRT_OK;
+}
+
+// Scratch of one chunk of `chunk` rays (ray records, then hit records).
+static int query_prepare(tirt_ctx *c, int chunk, float4 *&rec, float4 *&hit)
+{
+    if (int rc = query_scratch(c, (size_t)chunk * 48)) return rc;
     rec = c->query_mem.as<float4>();
     hit = rec + 2 * (size_t)chunk;
     if (ensure_counters(c)) return TIRT_ERR_HIP;
     return TIRT_OK;
 }
-static int query_chunk_of(const tirt_ctx *c, int64_t nr) { return (int)(nr < (int64_t)c->query_chunk ? nr : (int64_t)c->query_chunk); }
 
 // the two ordering events are made on first use
 int query_begin(tirt_ctx *c, void *stream)
@@ -175,25 +188,18 @@ int query_closest(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride
     TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, "tirt_query_closest: counts must be 8-byte aligned");
     if (nr == 0) return TIRT_OK;
     TIRT_REQUIRE(rays, "tirt_query_closest: null rays");
-    if (int rc = require_device_ptr(c, rays, "tirt_query_closest: rays")) return rc;
-    if (out_t) if (int rc = require_device_ptr(c, out_t, "tirt_query_closest: out_t")) return rc;
-    if (out_prim) if (int rc = require_device_ptr(c, out_prim, "tirt_query_closest: out_prim")) return rc;
-    if (out_hit) if (int rc = require_device_ptr(c, out_hit, "tirt_query_closest: out_hit")) return rc;
-    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
-    if (want_counts) if (int rc = require_device_ptr(c, counts, "tirt_query_closest: counts")) return rc;
-    const int chunk = query_chunk_of(c, nr);
+    const QueryPlan pl = query_plan(c, nr, flags, counts);
+    if (int rc = require_device_ptrs(c, "tirt_query_closest: ", {{rays, "rays"}, {out_t, "out_t"}, {out_prim, "out_prim"}, {out_hit, "out_hit"}, {pl.counts, "counts"}})) return rc;
     float4 *rec, *hit;
-    if (int rc = query_prepare(c, chunk, rec, hit)) return rc;
+    if (int rc = query_prepare(c, pl.chunk, rec, hit)) return rc;
     if (int rc = query_begin(c, stream)) return rc;
     TraceJob job; job.stack_size = stack_size; job.flags = flags; job.grid_cap = c->tr_grid_alone;
-    if (int rc = closest_chunks(c, rays, nr, ray_stride, chunk, rec, hit, job, true, out_t, out_prim, out_hit, hit_stride,
-                                want_counts ? (int2 *)counts : nullptr)) return rc;
+    if (int rc = closest_chunks(c, rays, nr, ray_stride, pl.chunk, rec, hit, job, true, out_t, out_prim, out_hit, hit_stride, pl.counts)) return rc;
     return query_end(c, stream);
 }
 
 // tirt_trace_closest / tirt_trace_shadow: host rays (6 floats each) staged in device memory, one chunk of all of them through the
 // closest-hit path above with the grid of a busy GPU (trace_grid), shadow: t, else the 13-float record, back to the host with a sync.
-// (The staging buffer is used here alone, and each call ends with a sync of the stream that used it.)
 int trace_host(tirt_ctx *c, const float *rays, int nr, int stack_size, int flags, bool shadow, float *out_f, int32_t *out_prim, int32_t *counts)
 {
     TIRT_REQUIRE(c->built, "trace: LBVH not built");
@@ -201,23 +207,18 @@ int trace_host(tirt_ctx *c, const float *rays, int nr, int stack_size, int flags
     if (nr == 0) return TIRT_OK;
     float4 *rec, *hit;
     if (int rc = query_prepare(c, nr, rec, hit)) return rc;
-    // staging: rays [nr][6], t or records [nr][13], prim [nr], counts [nr][2]
-    if (c->trace_stage.ensure(sizeof(float) * 22 * (size_t)nr)) return TIRT_ERR_HIP;
-    float *d_rays = c->trace_stage.as<float>(), *d_out = d_rays + 6 * (size_t)nr;
-    int32_t *d_prim = (int32_t *)(d_out + 13 * (size_t)nr);
-    int2 *d_counts = (int2 *)(d_prim + nr);
-    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
-    hipStream_t st = c->stream;
-    TIRT_HIP(hipMemcpyAsync(d_rays, rays, sizeof(float) * 6 * (size_t)nr, hipMemcpyHostToDevice, st));
+    const size_t N = (size_t)nr;
+    QueryStage s(c);
+    const auto k_rays = s.in(rays, 6 * N);
+    const auto k_out = s.out(out_f, (shadow ? 1 : 13) * N);      // t, or the records
+    const auto k_prim = s.out(out_prim, N);
+    const auto k_counts = s.out_counts(counts, flags, N);
+    if (int rc = s.begin()) return rc;
+    float *d_out = s.ptr(k_out);
     TraceJob job; job.stack_size = stack_size; job.flags = flags; job.grid_cap = c->tr_grid;
-    if (int rc = closest_chunks(c, d_rays, nr, 6, nr, rec, hit, job, false, shadow ? d_out : nullptr, d_prim, shadow ? nullptr : d_out, 13,
-                                want_counts ? d_counts : nullptr)) return rc;
-    TIRT_HIP(hipMemcpyAsync(out_f, d_out, sizeof(float) * (shadow ? 1 : 13) * (size_t)nr, hipMemcpyDeviceToHost, st));
-    TIRT_HIP(hipMemcpyAsync(out_prim, d_prim, sizeof(int32_t) * (size_t)nr, hipMemcpyDeviceToHost, st));
-    if (want_counts) TIRT_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int2) * (size_t)nr, hipMemcpyDeviceToHost, st));
-    TIRT_HIP(hipStreamSynchronize(st));
-    TIRT_HIP(hipGetLastError());
-    return TIRT_OK;
+    if (int rc = closest_chunks(c, s.ptr(k_rays), nr, 6, nr, rec, hit, job, false, shadow ? d_out : nullptr, s.ptr(k_prim), shadow ? nullptr : d_out, 13,
+                                s.ptr(k_counts))) return rc;
+    return s.finish();
 }
 
 int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, const float *tmax, int64_t tmax_stride, float tmax_all,
@@ -228,10 +229,8 @@ int query_occluded(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_strid
     TIRT_REQUIRE(!tmax || tmax_stride >= 1, "tirt_query_occluded: tmax_stride < 1");
     if (nr == 0) return TIRT_OK;
     TIRT_REQUIRE(rays && out_occluded, "tirt_query_occluded: null rays / out_occluded");
-    if (int rc = require_device_ptr(c, rays, "tirt_query_occluded: rays")) return rc;
-    if (tmax) if (int rc = require_device_ptr(c, tmax, "tirt_query_occluded: tmax")) return rc;
-    if (int rc = require_device_ptr(c, out_occluded, "tirt_query_occluded: out_occluded")) return rc;
-    const int chunk = query_chunk_of(c, nr);
+    if (int rc = require_device_ptrs(c, "tirt_query_occluded: ", {{rays, "rays"}, {tmax, "tmax"}, {out_occluded, "out_occluded"}})) return rc;
+    const int chunk = query_plan(c, nr, flags, nullptr).chunk;
     float4 *rec, *hit;
     if (int rc = query_prepare(c, chunk, rec, hit)) return rc;
     if (int rc = query_begin(c, stream)) return rc;
@@ -259,14 +258,9 @@ static int hits_chunk_of(const tirt_ctx *c, int64_t nr, int k)
     return (int)(nr < chunk ? nr : chunk);
 }
 struct HitsScratch { float4 *rec, *list; int2 *meta; MultiHitShape shape; };
-// (growing a buffer waits for the work queued on the context's stream, which may still read the old one)
 static int hits_prepare(tirt_ctx *c, int chunk, int k, int stack_size, HitsScratch &s)
 {
-    const size_t bytes = (size_t)chunk * (40 + 16 * (size_t)k);
-    if (bytes > c->query_mem.bytes) {
-        TIRT_HIP(hipStreamSynchronize(c->stream));
-        if (c->query_mem.ensure(bytes)) return TIRT_ERR_HIP;
-    }
+    if (int rc = query_scratch(c, (size_t)chunk * (40 + 16 * (size_t)k))) return rc;
     s.rec = c->query_mem.as<float4>();
     s.list = s.rec + 2 * (size_t)chunk;
     s.meta = (int2 *)(s.list + (size_t)k * chunk);
@@ -298,25 +292,19 @@ int query_hits(tirt_ctx *c, const float *rays, int64_t nr, int64_t ray_stride, c
     TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, "tirt_query_hits: counts must be 8-byte aligned");
     if (nr == 0) return TIRT_OK;
     TIRT_REQUIRE(rays, "tirt_query_hits: null rays");
-    if (int rc = require_device_ptr(c, rays, "tirt_query_hits: rays")) return rc;
-    if (tmax) if (int rc = require_device_ptr(c, tmax, "tirt_query_hits: tmax")) return rc;
-    if (out_t) if (int rc = require_device_ptr(c, out_t, "tirt_query_hits: out_t")) return rc;
-    if (out_prim) if (int rc = require_device_ptr(c, out_prim, "tirt_query_hits: out_prim")) return rc;
-    if (out_hit) if (int rc = require_device_ptr(c, out_hit, "tirt_query_hits: out_hit")) return rc;
-    if (out_count) if (int rc = require_device_ptr(c, out_count, "tirt_query_hits: out_count")) return rc;
-    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
-    if (want_counts) if (int rc = require_device_ptr(c, counts, "tirt_query_hits: counts")) return rc;
+    int2 *const want_counts = query_plan(c, nr, flags, counts).counts;
+    if (int rc = require_device_ptrs(c, "tirt_query_hits: ", {{rays, "rays"}, {tmax, "tmax"}, {out_t, "out_t"}, {out_prim, "out_prim"}, {out_hit, "out_hit"},
+                                                             {out_count, "out_count"}, {want_counts, "counts"}})) return rc;
     const int chunk = hits_chunk_of(c, nr, k);
     HitsScratch s;
     if (int rc = hits_prepare(c, chunk, k, stack_size, s)) return rc;
     if (int rc = query_begin(c, stream)) return rc;
     if (int rc = hits_chunks(c, s, rays, nr, ray_stride, tmax, tmax_stride, tmax_all, k, stack_size, flags, chunk, out_t, out_prim, out_hit, hit_stride,
-                             out_count, want_counts ? (int2 *)counts : nullptr)) return rc;
+                             out_count, want_counts)) return rc;
     return query_end(c, stream);
 }
 
-// tirt_trace_hits: host arrays staged in device memory (counts [nr][2] first: 8-byte aligned; rays [nr][6], tmax [nr], t [nr][k], prim [nr][k],
-// records [nr][k][13], count [nr]), through the chunks above, back to the host with a sync
+// tirt_trace_hits: host arrays staged in device memory (QueryStage), through the chunks above, back to the host with a sync
 int trace_hits_host(tirt_ctx *c, const float *rays, int nr, const float *tmax, int k, int stack_size, int flags, float *out_t, int32_t *out_prim,
                     float *out_hit, int32_t *out_count, int32_t *counts)
 {
@@ -327,26 +315,18 @@ int trace_hits_host(tirt_ctx *c, const float *rays, int nr, const float *tmax, i
     const int chunk = hits_chunk_of(c, nr, k);
     HitsScratch s;
     if (int rc = hits_prepare(c, chunk, k, stack_size, s)) return rc;
-    hipStream_t st = c->stream;
-    if (c->trace_stage.ensure(sizeof(float) * N * (10 + 15 * K))) return TIRT_ERR_HIP;      // (used by the host routes alone, and each of their calls ends with a sync)
-    int2 *d_counts = c->trace_stage.as<int2>();
-    float *d_rays = (float *)(d_counts + N), *d_tmax = d_rays + 6 * N, *d_t = d_tmax + N;
-    int32_t *d_prim = (int32_t *)(d_t + K * N);
-    float *d_hit = (float *)(d_prim + K * N);
-    int32_t *d_count = (int32_t *)(d_hit + 13 * K * N);
-    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
-    TIRT_HIP(hipMemcpyAsync(d_rays, rays, sizeof(float) * 6 * N, hipMemcpyHostToDevice, st));
-    if (tmax) TIRT_HIP(hipMemcpyAsync(d_tmax, tmax, sizeof(float) * N, hipMemcpyHostToDevice, st));
-    if (int rc = hits_chunks(c, s, d_rays, nr, 6, tmax ? d_tmax : nullptr, 1, __builtin_inff(), k, stack_size, flags, chunk, out_t ? d_t : nullptr,
-                             out_prim ? d_prim : nullptr, out_hit ? d_hit : nullptr, 13, out_count ? d_count : nullptr, want_counts ? d_counts : nullptr)) return rc;
-    if (out_t && k) TIRT_HIP(hipMemcpyAsync(out_t, d_t, sizeof(float) * K * N, hipMemcpyDeviceToHost, st));
-    if (out_prim && k) TIRT_HIP(hipMemcpyAsync(out_prim, d_prim, sizeof(int32_t) * K * N, hipMemcpyDeviceToHost, st));
-    if (out_hit && k) TIRT_HIP(hipMemcpyAsync(out_hit, d_hit, sizeof(float) * 13 * K * N, hipMemcpyDeviceToHost, st));
-    if (out_count) TIRT_HIP(hipMemcpyAsync(out_count, d_count, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-    if (want_counts) TIRT_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int2) * N, hipMemcpyDeviceToHost, st));
-    TIRT_HIP(hipStreamSynchronize(st));
-    TIRT_HIP(hipGetLastError());
-    return TIRT_OK;
+    QueryStage q(c);      // (the walk is handed the outputs the caller asked for, and no others)
+    const auto k_rays = q.in(rays, 6 * N);
+    const auto k_tmax = q.in(tmax, N);
+    const auto k_t = q.out(out_t, K * N, out_t != nullptr);
+    const auto k_prim = q.out(out_prim, K * N, out_prim != nullptr);
+    const auto k_hit = q.out(out_hit, 13 * K * N, out_hit != nullptr);
+    const auto k_count = q.out(out_count, N, out_count != nullptr);
+    const auto k_counts = q.out_counts(counts, flags, N);
+    if (int rc = q.begin()) return rc;
+    if (int rc = hits_chunks(c, s, q.ptr(k_rays), nr, 6, q.ptr(k_tmax), 1, __builtin_inff(), k, stack_size, flags, chunk, q.ptr(k_t), q.ptr(k_prim), q.ptr(k_hit), 13,
+                             q.ptr(k_count), q.ptr(k_counts))) return rc;
+    return q.finish();
 }
 
 }  // namespace tirt

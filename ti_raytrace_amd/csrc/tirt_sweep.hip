@@ -39,6 +39,7 @@
 #include "tirt_internal.h"
 #include "tirt_sweep.h"
 #include "tirt_point_walk.h"
+#include "tirt_query_stage.h"
 
 namespace tirt {
 
@@ -233,20 +234,12 @@ struct SwCall {      // what the two entry points hand to sw_chunks: every point
 // `n` queries in chunks of `chunk` on the context's stream
 static int sw_chunks(tirt_ctx *c, const SwCall &p, int chunk)
 {
-    if (ensure_counters(c)) return TIRT_ERR_HIP;
     const bool scan = (p.flags & TIRT_TRAVERSE_EXHAUSTIVE) != 0, cnt = (p.flags & TIRT_COUNT_NODES) != 0;
     const bool any = p.out_blocked && !p.out_t && !p.out_prim && !p.out_code && !p.out_point && !p.out_uv && !p.out_normal;
     SwArgs a = {};
-    a.bvh = bvh_view(c);
-    a.primitive = c->primitive.as<int>(); a.prim_slot = c->prim_slot.as<int>(); a.n_prim = c->n;
     a.ray_stride = p.ray_stride; a.radius_stride = p.radius_stride; a.radius_all = p.radius_all; a.tmax_stride = p.tmax_stride; a.tmax_all = p.tmax_all;
-    a.stack_size = p.stack_size; a.point_stride = p.point_stride; a.uv_stride = p.uv_stride; a.normal_stride = p.normal_stride;
-    a.ctr = c->dev_counters.as<DevCounters>();
-    // the walk's grid: a lane for every query of a chunk, as far as the stacks allow (the scan has no stack)
-    int grid_max = 0;
-    if (!scan) if (int rc = point_walk_launch_shape(c, p.stack_size, CP_WAVES_PER_CU, ((int64_t)(p.n < chunk ? p.n : chunk) + CP_BLOCK - 1) / CP_BLOCK, grid_max, a.spill)) return rc;
-    for (int64_t base = 0; base < p.n; base += chunk) {
-        const int m = (int)(p.n - base < chunk ? p.n - base : chunk);
+    a.point_stride = p.point_stride; a.uv_stride = p.uv_stride; a.normal_stride = p.normal_stride;
+    return point_walk_chunks(c, a, p.n, chunk, scan, p.stack_size, [&](int64_t base, int m, int, int grid) {
         a.n = m;
         a.rays = p.rays + base * p.ray_stride;
         a.radius = p.radius ? p.radius + base * p.radius_stride : nullptr; a.tmax = p.tmax ? p.tmax + base * p.tmax_stride : nullptr;
@@ -254,19 +247,12 @@ static int sw_chunks(tirt_ctx *c, const SwCall &p, int chunk)
         a.out_point = p.out_point ? p.out_point + base * p.point_stride : nullptr; a.out_uv = p.out_uv ? p.out_uv + base * p.uv_stride : nullptr;
         a.out_normal = p.out_normal ? p.out_normal + base * p.normal_stride : nullptr; a.out_blocked = p.out_blocked ? p.out_blocked + base : nullptr;
         a.counts = p.counts ? p.counts + base : nullptr;
-        const int blocks = (m + CP_BLOCK - 1) / CP_BLOCK;
-        if (scan) {
-            if (cnt) hipLaunchKernelGGL((k_sw_scan<true>), dim3(blocks), dim3(CP_BLOCK), 0, c->stream, a);
-            else hipLaunchKernelGGL((k_sw_scan<false>), dim3(blocks), dim3(CP_BLOCK), 0, c->stream, a);
-        } else {
-            const int g = blocks < grid_max ? blocks : grid_max;
-            if (any) { if (cnt) hipLaunchKernelGGL((k_sw_walk<true, true>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a);
-                       else hipLaunchKernelGGL((k_sw_walk<false, true>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a); }
-            else { if (cnt) hipLaunchKernelGGL((k_sw_walk<true, false>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a);
-                   else hipLaunchKernelGGL((k_sw_walk<false, false>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a); }
-        }
-    }
-    return TIRT_OK;
+        with_bool(cnt, [&](auto C) {
+            constexpr bool COUNT = decltype(C)::value;
+            if (scan) hipLaunchKernelGGL((k_sw_scan<COUNT>), dim3(grid), dim3(CP_BLOCK), 0, c->stream, a);
+            else with_bool(any, [&](auto A) { hipLaunchKernelGGL((k_sw_walk<COUNT, decltype(A)::value>), dim3(grid), dim3(CP_BLOCK), 0, c->stream, a); });
+        });
+    });
 }
 
 // one row per thread through sw_kat_row (tirt_sweep.h): the text tirt_kat_sweep_host runs on the host
@@ -291,30 +277,25 @@ int tirt_query_sweep(tirt_ctx *c, const float *rays, int64_t n, int64_t ray_stri
     const char *fn = "tirt_query_sweep";
     const std::string f = std::string(fn) + ": ";
     CTX(c);
-    if (int rc = query_common_checks(c, fn, "n", n, stack_size, flags)) return rc;
-    TIRT_REQUIRE(ray_stride >= 6, f + "ray_stride < 6 (floats per ray)");
-    TIRT_REQUIRE(!radius || radius_stride >= 1, f + "radius_stride < 1");
-    TIRT_REQUIRE(!tmax || tmax_stride >= 1, f + "tmax_stride < 1");
-    TIRT_REQUIRE(!out_point || point_stride >= 3, f + "point_stride < 3 (floats per contact point)");
-    TIRT_REQUIRE(!out_uv || uv_stride >= 2, f + "uv_stride < 2");
-    TIRT_REQUIRE(!out_normal || normal_stride >= 3, f + "normal_stride < 3 (floats per normal)");
-    TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, f + "counts must be 8-byte aligned");
-    if (int rc = require_caller_stream(c, fn, stream, "queries")) return rc;
+    if (int rc = point_query_checks(c, fn, n, stack_size, flags, {{true, ray_stride, 6, "ray_stride < 6 (floats per ray)"},
+                                    {radius != nullptr, radius_stride, 1, "radius_stride < 1"}, {tmax != nullptr, tmax_stride, 1, "tmax_stride < 1"},
+                                    {out_point != nullptr, point_stride, 3, "point_stride < 3 (floats per contact point)"}, {out_uv != nullptr, uv_stride, 2, "uv_stride < 2"},
+                                    {out_normal != nullptr, normal_stride, 3, "normal_stride < 3 (floats per normal)"}}, counts, stream)) return rc;
     if (n == 0) return TIRT_OK;
     TIRT_REQUIRE(rays, f + "null rays");
-    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
+    const QueryPlan pl = query_plan(c, n, flags, counts);
     if (int rc = require_device_ptrs(c, f, {{rays, "rays"}, {radius, "radius"}, {tmax, "tmax"}, {out_t, "out_t"}, {out_prim, "out_prim"}, {out_code, "out_code"},
                                             {out_point, "out_point"}, {out_uv, "out_uv"}, {out_normal, "out_normal"}, {out_blocked, "out_blocked"},
-                                            {want_counts ? counts : nullptr, "counts"}})) return rc;
-    const int chunk = (int)(n < (int64_t)c->query_chunk ? n : (int64_t)c->query_chunk);
+                                            {pl.counts, "counts"}})) return rc;
     if (int rc = query_begin(c, stream)) return rc;
     const SwCall p = {rays, n, ray_stride, radius, radius_stride, radius_all, tmax, tmax_stride, tmax_all, stack_size, flags, out_t, out_prim, out_code,
-                      out_point, point_stride, out_uv, uv_stride, out_normal, normal_stride, out_blocked, want_counts ? (int2 *)counts : nullptr};
-    if (int rc = sw_chunks(c, p, chunk)) return rc;
+                      out_point, point_stride, out_uv, uv_stride, out_normal, normal_stride, out_blocked, pl.counts};
+    if (int rc = sw_chunks(c, p, pl.chunk)) return rc;
     return query_end(c, stream);
 }
 
-// host arrays staged in the context's query scratch (query_mem: 88 bytes per query), one chunk of all of them, back with a sync
+// host arrays staged in device memory (QueryStage), one chunk of all of them, back with a sync.  The walk is handed every output, asked for or not -- but
+// `blocked` alone, if the caller asked for nothing else: the ANY walk
 int tirt_sweep(tirt_ctx *c, const float *rays, int n, const float *radius, float radius_all, const float *tmax, int stack_size, int flags, float *out_t,
                int32_t *out_prim, int32_t *out_code, float *out_point, float *out_uv, float *out_normal, uint8_t *out_blocked, int32_t *counts)
 {
@@ -323,38 +304,25 @@ int tirt_sweep(tirt_ctx *c, const float *rays, int n, const float *radius, float
     if (int rc = query_common_checks(c, fn, "n", n, stack_size, flags)) return rc;
     if (n == 0) return TIRT_OK;
     TIRT_REQUIRE(rays, std::string(fn) + ": null rays");
-    const size_t N = (size_t)n, bytes = N * 88;
-    hipStream_t st = c->stream;
-    if (bytes > c->query_mem.bytes) {
-        TIRT_HIP(hipStreamSynchronize(st));
-        if (c->query_mem.ensure(bytes)) return TIRT_ERR_HIP;
-    }
-    // counts [n][2] first (8-byte aligned), then rays [n][6], radius [n], tmax [n], t [n], prim [n], code [n], point [n][3], uv [n][2], normal [n][3], blocked [n] bytes
-    int2 *d_counts = c->query_mem.as<int2>();
-    float *d_rays = (float *)(d_counts + N), *d_radius = d_rays + 6 * N, *d_tmax = d_radius + N, *d_t = d_tmax + N;
-    int32_t *d_prim = (int32_t *)(d_t + N), *d_code = d_prim + N;
-    float *d_point = (float *)(d_code + N), *d_uv = d_point + 3 * N, *d_normal = d_uv + 2 * N;
-    uint8_t *d_blocked = (uint8_t *)(d_normal + 3 * N);
-    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
+    const size_t N = (size_t)n;
     const bool only_blocked = out_blocked && !out_t && !out_prim && !out_code && !out_point && !out_uv && !out_normal;
-    TIRT_HIP(hipMemcpyAsync(d_rays, rays, sizeof(float) * 6 * N, hipMemcpyHostToDevice, st));
-    if (radius) TIRT_HIP(hipMemcpyAsync(d_radius, radius, sizeof(float) * N, hipMemcpyHostToDevice, st));
-    if (tmax) TIRT_HIP(hipMemcpyAsync(d_tmax, tmax, sizeof(float) * N, hipMemcpyHostToDevice, st));
-    SwCall p = {d_rays, n, 6, radius ? d_radius : nullptr, 1, radius_all, tmax ? d_tmax : nullptr, 1, __builtin_inff(), stack_size, flags, d_t, d_prim, d_code,
-                d_point, 3, d_uv, 2, d_normal, 3, out_blocked ? d_blocked : nullptr, want_counts ? d_counts : nullptr};
-    if (only_blocked) { p.out_t = nullptr; p.out_prim = nullptr; p.out_code = nullptr; p.out_point = nullptr; p.out_uv = nullptr; p.out_normal = nullptr; }      // (the ANY walk)
+    QueryStage s(c);
+    const auto k_rays = s.in(rays, 6 * N);
+    const auto k_radius = s.in(radius, N);
+    const auto k_tmax = s.in(tmax, N);
+    const auto k_t = s.out(out_t, N, !only_blocked);
+    const auto k_prim = s.out(out_prim, N, !only_blocked);
+    const auto k_code = s.out(out_code, N, !only_blocked);
+    const auto k_point = s.out(out_point, 3 * N, !only_blocked);
+    const auto k_uv = s.out(out_uv, 2 * N, !only_blocked);
+    const auto k_normal = s.out(out_normal, 3 * N, !only_blocked);
+    const auto k_blocked = s.out(out_blocked, N, out_blocked != nullptr);
+    const auto k_counts = s.out_counts(counts, flags, N);
+    if (int rc = s.begin()) return rc;
+    const SwCall p = {s.ptr(k_rays), n, 6, s.ptr(k_radius), 1, radius_all, s.ptr(k_tmax), 1, __builtin_inff(), stack_size, flags, s.ptr(k_t), s.ptr(k_prim),
+                      s.ptr(k_code), s.ptr(k_point), 3, s.ptr(k_uv), 2, s.ptr(k_normal), 3, s.ptr(k_blocked), s.ptr(k_counts)};
     if (int rc = sw_chunks(c, p, n)) return rc;
-    if (out_t) TIRT_HIP(hipMemcpyAsync(out_t, d_t, sizeof(float) * N, hipMemcpyDeviceToHost, st));
-    if (out_prim) TIRT_HIP(hipMemcpyAsync(out_prim, d_prim, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-    if (out_code) TIRT_HIP(hipMemcpyAsync(out_code, d_code, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-    if (out_point) TIRT_HIP(hipMemcpyAsync(out_point, d_point, sizeof(float) * 3 * N, hipMemcpyDeviceToHost, st));
-    if (out_uv) TIRT_HIP(hipMemcpyAsync(out_uv, d_uv, sizeof(float) * 2 * N, hipMemcpyDeviceToHost, st));
-    if (out_normal) TIRT_HIP(hipMemcpyAsync(out_normal, d_normal, sizeof(float) * 3 * N, hipMemcpyDeviceToHost, st));
-    if (out_blocked) TIRT_HIP(hipMemcpyAsync(out_blocked, d_blocked, N, hipMemcpyDeviceToHost, st));
-    if (want_counts) TIRT_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int2) * N, hipMemcpyDeviceToHost, st));
-    TIRT_HIP(hipStreamSynchronize(st));
-    TIRT_HIP(hipGetLastError());
-    return TIRT_OK;
+    return s.finish();
 }
 
 int tirt_kat_sweep(tirt_ctx *c, const float *in, int n, int is_sphere, float *out)

@@ -24,6 +24,7 @@
 #include "tirt_internal.h"
 #include "tirt_triangle_query.h"
 #include "tirt_point_walk.h"
+#include "tirt_query_stage.h"
 
 namespace tirt {
 
@@ -129,32 +130,22 @@ static int tq_chunks(tirt_ctx *c, const float *tris, int64_t n, int64_t tri_stri
                      int stack_size, int flags, int chunk, float *out_d2, int32_t *out_prim, int32_t *out_code, float *out_points, int64_t points_stride,
                      int2 *counts)
 {
-    if (ensure_counters(c)) return TIRT_ERR_HIP;
     const bool scan = (flags & TIRT_TRAVERSE_EXHAUSTIVE) != 0, cnt = (flags & TIRT_COUNT_NODES) != 0;
     TqArgs a = {};
-    a.bvh = bvh_view(c);
-    a.primitive = c->primitive.as<int>(); a.prim_slot = c->prim_slot.as<int>(); a.n_prim = c->n;
     a.tri_stride = tri_stride; a.dmax_stride = dmax_stride; a.dmax_all = dmax_all;
-    a.stack_size = stack_size; a.points_stride = points_stride;
-    a.ctr = c->dev_counters.as<DevCounters>();
-    // the walk's grid: a lane for every query of a chunk, as far as the stacks allow (the scan has no stack)
-    int grid_max = 0;
-    if (!scan) if (int rc = point_walk_launch_shape(c, stack_size, CP_WAVES_PER_CU, ((int64_t)(n < chunk ? n : chunk) + CP_BLOCK - 1) / CP_BLOCK, grid_max, a.spill)) return rc;
-    for (int64_t base = 0; base < n; base += chunk) {
-        const int m = (int)(n - base < chunk ? n - base : chunk);
+    a.points_stride = points_stride;
+    return point_walk_chunks(c, a, n, chunk, scan, stack_size, [&](int64_t base, int m, int, int grid) {
         a.n = m;
         a.tris = tris + base * tri_stride; a.dmax = dmax ? dmax + base * dmax_stride : nullptr;
         a.out_d2 = out_d2 ? out_d2 + base : nullptr; a.out_prim = out_prim ? out_prim + base : nullptr; a.out_code = out_code ? out_code + base : nullptr;
         a.out_points = out_points ? out_points + base * points_stride : nullptr;
         a.counts = counts ? counts + base : nullptr;
-        const int blocks = (m + CP_BLOCK - 1) / CP_BLOCK;
-        const int g = blocks < grid_max ? blocks : grid_max;
-        if (scan) { if (cnt) hipLaunchKernelGGL((k_tq_scan<true>), dim3(blocks), dim3(CP_BLOCK), 0, c->stream, a);
-                    else hipLaunchKernelGGL((k_tq_scan<false>), dim3(blocks), dim3(CP_BLOCK), 0, c->stream, a); }
-        else { if (cnt) hipLaunchKernelGGL((k_tq_walk<true>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a);
-               else hipLaunchKernelGGL((k_tq_walk<false>), dim3(g), dim3(CP_BLOCK), 0, c->stream, a); }
-    }
-    return TIRT_OK;
+        with_bool(cnt, [&](auto C) {
+            constexpr bool COUNT = decltype(C)::value;
+            if (scan) hipLaunchKernelGGL((k_tq_scan<COUNT>), dim3(grid), dim3(CP_BLOCK), 0, c->stream, a);
+            else hipLaunchKernelGGL((k_tq_walk<COUNT>), dim3(grid), dim3(CP_BLOCK), 0, c->stream, a);
+        });
+    });
 }
 
 // one row per thread through tq_kat_row (tirt_triangle_query.h): the text tirt_kat_tri_tri_host runs on the host
@@ -178,25 +169,21 @@ int tirt_query_mesh_distance(tirt_ctx *c, const float *tris, int64_t n, int64_t 
     const char *fn = "tirt_query_mesh_distance";
     const std::string f = std::string(fn) + ": ";
     CTX(c);
-    if (int rc = query_common_checks(c, fn, "n", n, stack_size, flags)) return rc;
-    TIRT_REQUIRE(tri_stride >= 9, f + "tri_stride < 9 (floats per triangle)");
-    TIRT_REQUIRE(!out_points || points_stride >= 6, f + "points_stride < 6 (floats per pair of closest points)");
-    TIRT_REQUIRE(!dmax || dmax_stride >= 1, f + "dmax_stride < 1");
-    TIRT_REQUIRE(!counts || ((uintptr_t)counts & 7) == 0, f + "counts must be 8-byte aligned");
-    if (int rc = require_caller_stream(c, fn, stream, "queries")) return rc;
+    if (int rc = point_query_checks(c, fn, n, stack_size, flags, {{true, tri_stride, 9, "tri_stride < 9 (floats per triangle)"},
+                                    {out_points != nullptr, points_stride, 6, "points_stride < 6 (floats per pair of closest points)"},
+                                    {dmax != nullptr, dmax_stride, 1, "dmax_stride < 1"}}, counts, stream)) return rc;
     if (n == 0) return TIRT_OK;
     TIRT_REQUIRE(tris, f + "null tris");
-    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
+    const QueryPlan pl = query_plan(c, n, flags, counts);
     if (int rc = require_device_ptrs(c, f, {{tris, "tris"}, {dmax, "dmax"}, {out_d2, "out_d2"}, {out_prim, "out_prim"}, {out_code, "out_code"}, {out_points, "out_points"},
-                                            {want_counts ? counts : nullptr, "counts"}})) return rc;
-    const int chunk = (int)(n < (int64_t)c->query_chunk ? n : (int64_t)c->query_chunk);
+                                            {pl.counts, "counts"}})) return rc;
     if (int rc = query_begin(c, stream)) return rc;
-    if (int rc = tq_chunks(c, tris, n, tri_stride, dmax, dmax_stride, dmax_all, stack_size, flags, chunk, out_d2, out_prim, out_code, out_points,
-                           points_stride, want_counts ? (int2 *)counts : nullptr)) return rc;
+    if (int rc = tq_chunks(c, tris, n, tri_stride, dmax, dmax_stride, dmax_all, stack_size, flags, pl.chunk, out_d2, out_prim, out_code, out_points,
+                           points_stride, pl.counts)) return rc;
     return query_end(c, stream);
 }
 
-// host arrays staged in the context's query scratch (query_mem: 84 bytes per query), one chunk of all of them, back with a sync
+// host arrays staged in device memory (QueryStage), one chunk of all of them, back with a sync.  The walk is handed every output, asked for or not
 int tirt_mesh_distance(tirt_ctx *c, const float *tris, int n, const float *dmax, int stack_size, int flags, float *out_d2, int32_t *out_prim,
                        int32_t *out_code, float *out_points, int32_t *counts)
 {
@@ -205,30 +192,19 @@ int tirt_mesh_distance(tirt_ctx *c, const float *tris, int n, const float *dmax,
     if (int rc = query_common_checks(c, fn, "n", n, stack_size, flags)) return rc;
     if (n == 0) return TIRT_OK;
     TIRT_REQUIRE(tris, std::string(fn) + ": null tris");
-    const size_t N = (size_t)n, bytes = N * 84;
-    hipStream_t st = c->stream;
-    if (bytes > c->query_mem.bytes) {
-        TIRT_HIP(hipStreamSynchronize(st));
-        if (c->query_mem.ensure(bytes)) return TIRT_ERR_HIP;
-    }
-    // counts [n][2] first (8-byte aligned), then tris [n][9], dmax [n], d2 [n], prim [n], code [n], points [n][6]
-    int2 *d_counts = c->query_mem.as<int2>();
-    float *d_tris = (float *)(d_counts + N), *d_dmax = d_tris + 9 * N, *d_d2 = d_dmax + N;
-    int32_t *d_prim = (int32_t *)(d_d2 + N), *d_code = d_prim + N;
-    float *d_points = (float *)(d_code + N);
-    const bool want_counts = counts && (flags & TIRT_COUNT_NODES);
-    TIRT_HIP(hipMemcpyAsync(d_tris, tris, sizeof(float) * 9 * N, hipMemcpyHostToDevice, st));
-    if (dmax) TIRT_HIP(hipMemcpyAsync(d_dmax, dmax, sizeof(float) * N, hipMemcpyHostToDevice, st));
-    if (int rc = tq_chunks(c, d_tris, n, 9, dmax ? d_dmax : nullptr, 1, __builtin_inff(), stack_size, flags, n, d_d2, d_prim, d_code, d_points, 6,
-                           want_counts ? d_counts : nullptr)) return rc;
-    if (out_d2) TIRT_HIP(hipMemcpyAsync(out_d2, d_d2, sizeof(float) * N, hipMemcpyDeviceToHost, st));
-    if (out_prim) TIRT_HIP(hipMemcpyAsync(out_prim, d_prim, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-    if (out_code) TIRT_HIP(hipMemcpyAsync(out_code, d_code, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-    if (out_points) TIRT_HIP(hipMemcpyAsync(out_points, d_points, sizeof(float) * 6 * N, hipMemcpyDeviceToHost, st));
-    if (want_counts) TIRT_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int2) * N, hipMemcpyDeviceToHost, st));
-    TIRT_HIP(hipStreamSynchronize(st));
-    TIRT_HIP(hipGetLastError());
-    return TIRT_OK;
+    const size_t N = (size_t)n;
+    QueryStage s(c);
+    const auto k_tris = s.in(tris, 9 * N);
+    const auto k_dmax = s.in(dmax, N);
+    const auto k_d2 = s.out(out_d2, N);
+    const auto k_prim = s.out(out_prim, N);
+    const auto k_code = s.out(out_code, N);
+    const auto k_points = s.out(out_points, 6 * N);
+    const auto k_counts = s.out_counts(counts, flags, N);
+    if (int rc = s.begin()) return rc;
+    if (int rc = tq_chunks(c, s.ptr(k_tris), n, 9, s.ptr(k_dmax), 1, __builtin_inff(), stack_size, flags, n, s.ptr(k_d2), s.ptr(k_prim), s.ptr(k_code),
+                           s.ptr(k_points), 6, s.ptr(k_counts))) return rc;
+    return s.finish();
 }
 
 int tirt_kat_tri_tri(tirt_ctx *c, const float *in, int n, int what, float *out)
