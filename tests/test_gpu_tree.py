@@ -1,7 +1,8 @@
 """The traversal tree (ti_raytrace_amd/csrc/tirt_sah.hip): the binned-SAH binary tree the ordered traversal walks instead of
 the reference's LBVH (accel/LBvh.py:229-467).  It may be any hierarchy over the same primitives -- every candidate hit is
 verified against the reference tree (Scene.py:702-744) -- but it has to BE one: every primitive in exactly one leaf, every
-box the union of its children's, pre-order layout.  And the option must not change a single bit of any result."""
+box the union of its children's, pre-order layout.  And the option must not change a single bit of any result.
+WHICH tree it has to be -- every node split as the header of tirt_sah.hip defines -- is test_gpu_sah_tree.py's."""
 import numpy as np
 import pytest
 
@@ -139,8 +140,8 @@ def test_cost_optimal_collapse_changes_no_bit(gpu_ctx_ok, experiments_lib):
 
 @pytest.mark.parametrize("kind", ["exponential", "identical", "two_clusters"])
 def test_traversal_tree_on_hostile_distributions(gpu_ctx_ok, kind):
-    """Inputs a binned SAH build handles badly: centroids spaced exponentially (every split peels off a few primitives: the tree
-    is as deep as the 64 levels after which ranges are halved), 3000 identical triangles (no plane separates anything: halving
+    """Inputs a binned SAH build handles badly: centroids spaced exponentially (lopsided splits; 18 levels, not the 64 after
+    which ranges are halved: docs/HISTORY.md; test_gpu_sah_tree.py has the set that gets there), 3000 identical triangles (no plane separates anything: halving
     from the root), two far-apart clusters of very different size.  The tree must still be a tree and the hits the oracle's."""
     r = np.random.RandomState(7)
     tris = hostile_triangles(kind, r)

@@ -17,6 +17,10 @@
 // and centroid bounds, (B) 32 bins per axis by centroid (integer-keyed min / max / count atomics in LDS), (C) the cheapest
 // of the 3 x 31 candidate planes by area(L) * n_L + area(R) * n_R, (D) a stable partition of the range into the other
 // index buffer.  All centroids in one bin on every axis (duplicates), or a tree deeper than 64 levels: the range is halved.
+// Ties of (C) go to the lowest axis * 32 + plane; nodes of at most SAH_MINI primitives price the cut behind each primitive
+// instead (k_sah_subtree), ties to the lowest axis * 16 + position in the range.  tests/sah_tree_expected.py restates all of it
+// in numpy and tests/test_gpu_sah_tree.py holds every node of the downloaded tree to it, so a change of ANY decision here
+// (or of the order in a range) shows there, not in a film.
 // Sizes of node, so that the top of the tree is as parallel as its bottom:
 //   subtree (<= SAH_SUB primitives)   the WHOLE subtree is finished by one wave in one launch at the end (k_sah_subtree): its nodes of more
 //                                     than SAH_MINI primitives with the binned sweep below, smaller ones 16 lanes per node, everything in
