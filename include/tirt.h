@@ -1309,6 +1309,20 @@ int tirt_kat_shade_tables(tirt_ctx *ctx, int which, const float *in, float *out,
  * cover the context's feature word, feat 255 or 511 on a context without uploaded textures, a hit row (t < 1e6) whose prim is outside [0, n_prims), a pixel outside [0, 2^31 - 1). */
 int tirt_kat_shade_step(tirt_ctx *ctx, uint32_t feat, const float *in, int in_stride, float *out, int out_stride, int n);
 
+/* One shading step of PT_Spec (integrator/PT_Spec.py:207-274 between a closest hit and the next: the emitter hit, glass with its wavelength pick / Disney, the NEE
+ * set-up with its four-channel contribution, the next ray, the analytic sky for a miss) by the body of one instantiation of k_shade_spec, on the context's own
+ * tables and the spectral tables of tirt_spectral_upload -- for tests/test_gpu_shade_spec_step.py against the CPU oracle's orc_kat_shade_spec_step.  One launch,
+ * row i on thread i.  The hero wavelength is the row's: 360 + 100 * rand(seed, pixel, frame).
+ * feat: 32 (sphere lights), 4 (mesh lights) or 127 (generic): the three words tirt_shade_instantiation returns for a spectral render.
+ * in, 23 words per row (integers as their bit patterns): words 0..14 as tirt_kat_shade_step's -- seed, pixel, frame, bounce, last_bounce; origin3, direction3; t, u,
+ *   v, prim (t >= 1e6: a miss, prim unused) --, then throughout4 (15..18) and radiance4 (19..22).  NaN and infinity in the ray, the barycentrics and the state are data.
+ * out, 29 words per row: radiance4 (0..3), shaded, want_next, next_o3 (6..8), next_d3 (9..11), next_thr4 (12..15), want_shadow (16), sh_o3, sh_d3, sh_c4 (23..26),
+ *   sh_expect (27), sh_dist (28) -- what k_shade_spec writes to the path state and the shadow-ray queue; a field the step does not set is 0, sh_expect -2.  sh_c counts
+ *   if the shadow ray finds sh_expect first.
+ * TIRT_ERR_ARG before anything is launched: in_stride < 23, out_stride < 29, a feat that is not one of the three (both also with a NULL ctx), no scene, no spectral
+ * tables, a feat that does not cover the context's feature word, a hit row (t < 1e6) whose prim is outside [0, n_prims), a pixel outside [0, 2^31 - 1). */
+int tirt_kat_shade_spec_step(tirt_ctx *ctx, uint32_t feat, const float *in, int in_stride, float *out, int out_stride, int n);
+
 /* ---- native Wavefront OBJ/MTL ingest (host only; no device, no context) -----------------------------
  * Replaces the reference's use of the third-party PyWavefront 1.3.3 package in Scene.add_obj
  * (Scene.py:66-127: `pywavefront.Wavefront(filename)`, `scene.materials[name].vertices / vertex_format /

@@ -1453,6 +1453,145 @@ static v3 glass_sample_lambda(v3 dir, v3 N, float Lambda, float probability, flo
     return next_dir;
 }
 
+/* One path at one bounce: integrator/PT_Spec.py:207-274 between the closest hit and the next one, as a function of the hit record (t, u, v, prim;
+ * t >= INF_VALUE: a miss) and the path's state -- four-channel throughput and radiance; PT_Spec carries no brdf_pdf and no perfect_spec from one bounce
+ * to the next (:214).  The hero wavelength is the path's: 360 + 100 * rand(seed, pixel, frame, TM_DIM_SPEC_LAMBDA).  The fields are what the device's
+ * k_shade_spec writes to its path state and its shadow-ray queue; a field the taken branch does not write keeps its default (0, sh_expect -2).  The NEE
+ * contribution sh_c is NOT added here: it counts if the shadow ray (sh_o, sh_d) finds primitive sh_expect first (-2: no primitive) -- pt_spec_pixel makes
+ * that test.  (The reference makes it before it evaluates the BSDF, :243-244; the sum is the same.)  `branch`: one SSB_* bit per arm taken (diagnostic). */
+enum {
+    SSB_EMIT_FRONT = 1 << 0, SSB_EMIT_BACK = 1 << 1, SSB_GLASS_REFLECT = 1 << 2, SSB_GLASS_REFRACT = 1 << 3,
+    SSB_NEE = 1 << 4, SSB_NEE_NOPDF = 1 << 5, SSB_NEE_REJECT = 1 << 6,
+    SSB_LIGHT_TRI = 1 << 7, SSB_LIGHT_SPHERE = 1 << 8, SSB_LIGHT_SPOT = 1 << 9, SSB_LIGHT_LASER = 1 << 10,
+    SSB_END_PDF = 1 << 11, SSB_END_THR = 1 << 12,              /* the continuation test of :256 failed on its pdf / on max(throughput 0..2); both may be set */
+    SSB_MISS_FINITE = 1 << 13, SSB_MISS_NONFINITE = 1 << 14, SSB_MISS_BELOW = 1 << 15      /* BELOW: a finite direction whose theta was clamped to pi/2 */
+};
+typedef struct {
+    v4s radiance; int shaded;
+    int want_next; v3 next_o, next_d; v4s next_thr;
+    int want_shadow; v3 sh_o, sh_d; v4s sh_c; int sh_expect; float sh_dist;
+    uint32_t branch;
+} shade_spec_step;
+
+static shade_spec_step pt_spec_step(const orc_scene *s, const orc_spec *sp, uint32_t seed, uint32_t pixel, uint32_t frame, int bounce, int last_bounce,
+                                    v3 origin, v3 direction, float t, float u, float v, int prim, v4s throughout, v4s radiance)
+{
+    shade_spec_step r;
+    r.shaded = r.want_next = r.want_shadow = 0; r.sh_dist = 0.0f; r.sh_expect = -2; r.branch = 0u;
+    r.next_o = r.next_d = r.sh_o = r.sh_d = V(0, 0, 0);
+    for (int k = 0; k < HERO_N; k++) r.next_thr.v[k] = r.sh_c.v[k] = 0.0f;
+    const uint32_t dim0 = TM_DIM_BOUNCE0 + TM_DIMS_PER_BOUNCE * (uint32_t)bounce;
+    const float Lambda = HERO_LAMBDA_MIN + HERO_LAMBDA_STEP * tm_rand(seed, pixel, frame, TM_DIM_SPEC_LAMBDA);      /* :191 */
+    const v4s light_rad = hero_sample(&sp->spd[0], Lambda);          /* the same for every vertex of the path (:212) */
+    float light_pdf = 1.0f, brdf_pdf = 1.0f, f_or_b = 1.0f, brdf = 1.0f;
+    if (t < INF_VALUE) {
+        hit_t h; h.t = t; h.prim = prim; h.u = u; h.v = v;
+        prim_attributes(s, origin, direction, prim, t, u, v, &h.pos, &h.gnor, &h.nor, &h.tex);
+        v3 normal = h.nor;
+        v3 fnormal = vscale(h.nor, signf(vdot(vneg(direction), h.gnor)));
+        int mat_id = s->primitive[(size_t)h.prim * PRI_VEC + 2];
+        const float *m = s->material + (size_t)mat_id * MAT_VEC;
+        v3 mat_color = V(m[2], m[3], m[4]);
+        int mat_type = (int)m[0];
+        /* :213 -- the "tint" is the colour of the material that was HIT, also where the NEE sample below uses it */
+        const v4s light_tint = emission_to_rad(sp, mat_color, Lambda);
+        if (mat_type == MAT_LIGHT) {
+            const float fCosTheta = vdot(direction, normal);
+            if (fCosTheta < 0.0f) {
+                const float area = get_prim_area(s, h.prim);
+                light_pdf = (h.t * h.t) / (area * fCosTheta);
+                (void)light_pdf;       /* perfect_spec is reset to 1 at the top of every iteration (:214): the MIS branch is dead */
+                radiance = v4_add(radiance, v4_mul(v4_mul(throughout, light_rad), light_tint));
+                r.branch |= SSB_EMIT_FRONT;
+            } else r.branch |= SSB_EMIT_BACK;
+        } else {
+            v3 next_dir;
+            r.shaded = 1;
+            const v4s reflect_spec = get_spec_power(s, sp, mat_id, Lambda);
+            if (mat_type == MAT_GLASS) {
+                int index = (int)(tm_rand(seed, pixel, frame, dim0 + TM_SLOT_HERO) * (float)HERO_N);     /* HeroSample.py:33-35 */
+                const float rnd_lambda = Lambda + (float)index * HERO_LAMBDA_STEP;
+                next_dir = glass_sample_lambda(direction, normal, rnd_lambda, tm_rand(seed, pixel, frame, dim0 + TM_SLOT_GLASS), &f_or_b);
+                brdf = 1.0f; brdf_pdf = 1.0f;
+                r.branch |= f_or_b < 0.0f ? SSB_GLASS_REFRACT : SSB_GLASS_REFLECT;
+            } else {
+                if (s->light_count > 0) {
+                int lidx = (int)(tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LIGHT) * (float)s->light_count);
+                if (lidx >= s->light_count) lidx = s->light_count - 1;
+                int light_prim = s->light[lidx];
+                float ra = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LA);
+                float rb = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LB);
+                v3 light_pos, light_normal;
+                get_prim_random_point_normal(s, light_prim, ra, rb, &light_pos, &light_normal);
+                {
+                    const int32_t *lp = s->primitive + (size_t)light_prim * PRI_VEC;
+                    const int lst = lp[0] == PRIMITIVE_TRI ? -1 : (int)s->shape[(size_t)lp[1] * SHA_VEC];
+                    r.branch |= lst == -1 ? SSB_LIGHT_TRI : lst == SHAPE_SPHERE ? SSB_LIGHT_SPHERE : lst == SHAPE_SPOT ? SSB_LIGHT_SPOT : lst == SHAPE_LASER ? SSB_LIGHT_LASER : 0u;
+                }
+                float light_area = get_prim_area(s, light_prim);
+                float light_choice_pdf = 1.0f / ((float)s->light_count * light_area);
+                light_normal = vnormalized(light_normal);
+                v3 light_dir = vsub(h.pos, light_pos);
+                float light_dist = vnorm(light_dir);
+                light_dir = vdivs(light_dir, light_dist);
+                (void)light_shape_visible(s, light_prim, light_dir, light_normal, light_dist, &light_choice_pdf);   /* only its pdf reaches :245 */
+                float NdotL_surface = vdot(fnormal, light_dir);
+                float NdotL_light = vdot(light_normal, light_dir);
+                if ((NdotL_surface < 0.0f) & (NdotL_light > 0.0f)) {
+                    float e_pdf;
+                    const float e_brdf = disney_evaluate_pdf(s, fnormal, vneg(direction), vneg(light_dir), mat_id, &e_pdf);
+                    light_pdf = light_dist * light_dist * light_choice_pdf / NdotL_light;
+                    v4s c; for (int k = 0; k < HERO_N; k++) c.v[k] = 0.0f;
+                    int expect = -2;                        /* never equals a primitive id */
+                    if (e_pdf > 0.0f) {
+                        const float w = power_heuristic(light_pdf, e_pdf) / fmax_(0.0001f, light_pdf);
+                        c = v4_scale(light_rad, w);
+                        c = v4_mul(c, light_tint);
+                        c = v4_mul(c, throughout);
+                        c = v4_mul(c, reflect_spec);
+                        c = v4_scale(c, e_brdf);
+                        c = v4_scale(c, fabs_(NdotL_surface));
+                        expect = h.prim;
+                        r.branch |= SSB_NEE;
+                    } else r.branch |= SSB_NEE_NOPDF;
+                    r.want_shadow = 1; r.sh_o = light_pos; r.sh_d = light_dir; r.sh_c = c; r.sh_expect = expect; r.sh_dist = light_dist;
+                } else r.branch |= SSB_NEE_REJECT;
+                }   /* light_count > 0 */
+                float rnd[3] = { tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LOBE),
+                                 tm_rand(seed, pixel, frame, dim0 + TM_SLOT_R1),
+                                 tm_rand(seed, pixel, frame, dim0 + TM_SLOT_R2) };
+                next_dir = disney_sample(s, direction, fnormal, mat_id, rnd);
+                f_or_b = 1.0f;
+                brdf = disney_evaluate_pdf(s, fnormal, next_dir, vneg(direction), mat_id, &brdf_pdf);      /* (N, V = next_dir, L = -direction): :251 */
+                brdf *= fabs_(vdot(normal, next_dir));
+            }
+            const v3 next_origin = offset_ray(h.pos, vscale(fnormal, signf(f_or_b)));
+            const int thr_ok = fmax_(throughout.v[2], fmax_(throughout.v[0], throughout.v[1])) > 0.0f;      /* channels 0..2 of four (:256) */
+            if (!(brdf_pdf > 0.0f)) r.branch |= SSB_END_PDF;
+            if (!thr_ok) r.branch |= SSB_END_THR;
+            if ((brdf_pdf > 0.0f) & thr_ok) {
+                throughout = v4_mul(throughout, v4_divs(v4_scale(reflect_spec, brdf), brdf_pdf));
+                r.want_next = !last_bounce;          /* depth reaches max_depth after the last bounce: the loop ends */
+                r.next_o = next_origin; r.next_d = next_dir; r.next_thr = throughout;
+            }
+        }
+    } else {
+        /* :267-274: the analytic sky */
+        const float dis = m_sqrt(direction.x * direction.x + direction.z * direction.z);
+        const float beta = m_atan2(direction.y, dis);
+        const float gamma = m_acos(vdot(direction, V(sp->sun_dir[0], sp->sun_dir[1], sp->sun_dir[2])));
+        const float theta = clampf(0.5f * PI_SCENE - beta, 0.0f, 0.5f * PI_SCENE);
+        v4s ibl;
+        for (int k = 0; k < HERO_N; k++) ibl.v[k] = sky_radiance(sp, theta, gamma, Lambda + (float)k * HERO_LAMBDA_STEP);
+        radiance = v4_add(radiance, v4_mul(v4_mul(throughout, ibl), light_rad));
+        const int finite = (direction.x - direction.x == 0.0f) & (direction.y - direction.y == 0.0f) & (direction.z - direction.z == 0.0f);
+        r.branch |= finite ? SSB_MISS_FINITE : SSB_MISS_NONFINITE;
+        if (finite && 0.5f * PI_SCENE - beta > 0.5f * PI_SCENE) r.branch |= SSB_MISS_BELOW;
+    }
+    r.radiance = radiance;
+    return r;
+}
+
 /* integrator/PT_Spec.py:181-279: one pixel-sample; returns the four hero radiances and the hero wavelength */
 static v4s pt_spec_pixel(const orc_scene *s, const orc_spec *sp, int i, int j, int H, uint32_t frame, uint32_t seed,
                          int max_depth, int32_t *stack, int stack_size, orc_stats *st, float *Lambda_out)
@@ -1475,106 +1614,26 @@ static v4s pt_spec_pixel(const orc_scene *s, const orc_spec *sp, int i, int j, i
         float wz = ((M[8] * x + M[9] * y) + M[10] * z) + M[11] * w;
         next_dir = vnormalized(V(wx, wy, wz));
     }
-    const float Lambda = HERO_LAMBDA_MIN + HERO_LAMBDA_STEP * tm_rand(seed, pixel, frame, TM_DIM_SPEC_LAMBDA);
-    *Lambda_out = Lambda;
+    *Lambda_out = HERO_LAMBDA_MIN + HERO_LAMBDA_STEP * tm_rand(seed, pixel, frame, TM_DIM_SPEC_LAMBDA);
     int depth = 0;
-    float light_pdf = 1.0f, brdf_pdf = 1.0f, f_or_b = 1.0f, brdf = 1.0f;
     v4s throughout, radiance;
     for (int k = 0; k < HERO_N; k++) { throughout.v[k] = 1.0f; radiance.v[k] = 0.0f; }
-    const v4s light_rad = hero_sample(&sp->spd[0], Lambda);          /* the same for every vertex of the path (:212) */
     if (st) st->paths++;
     while (depth < max_depth) {
         v3 origin = next_origin, direction = next_dir;
-        uint32_t dim0 = TM_DIM_BOUNCE0 + TM_DIMS_PER_BOUNCE * (uint32_t)depth;
         hit_t h = closet_hit(s, origin, direction, stack, stack_size, st);
-        if (h.t < INF_VALUE) {
-            v3 normal = h.nor;
-            v3 fnormal = vscale(h.nor, signf(vdot(vneg(direction), h.gnor)));
-            int mat_id = s->primitive[(size_t)h.prim * PRI_VEC + 2];
-            const float *m = s->material + (size_t)mat_id * MAT_VEC;
-            v3 mat_color = V(m[2], m[3], m[4]);
-            int mat_type = (int)m[0];
-            /* :213 -- the "tint" is the colour of the material that was HIT, also where the NEE sample below uses it */
-            const v4s light_tint = emission_to_rad(sp, mat_color, Lambda);
-            if (mat_type == MAT_LIGHT) {
-                const float fCosTheta = vdot(direction, normal);
-                if (fCosTheta < 0.0f) {
-                    const float area = get_prim_area(s, h.prim);
-                    light_pdf = (h.t * h.t) / (area * fCosTheta);
-                    (void)light_pdf;       /* perfect_spec is reset to 1 at the top of every iteration (:214): the MIS branch is dead */
-                    radiance = v4_add(radiance, v4_mul(v4_mul(throughout, light_rad), light_tint));
-                }
-                break;
-            } else {
-                if (st) st->shaded++;
-                const v4s reflect_spec = get_spec_power(s, sp, mat_id, Lambda);
-                if (mat_type == MAT_GLASS) {
-                    int index = (int)(tm_rand(seed, pixel, frame, dim0 + TM_SLOT_HERO) * (float)HERO_N);     /* HeroSample.py:33-35 */
-                    const float rnd_lambda = Lambda + (float)index * HERO_LAMBDA_STEP;
-                    next_dir = glass_sample_lambda(direction, normal, rnd_lambda, tm_rand(seed, pixel, frame, dim0 + TM_SLOT_GLASS), &f_or_b);
-                    brdf = 1.0f; brdf_pdf = 1.0f;
-                } else {
-                    if (s->light_count > 0) {
-                    int lidx = (int)(tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LIGHT) * (float)s->light_count);
-                    if (lidx >= s->light_count) lidx = s->light_count - 1;
-                    int light_prim = s->light[lidx];
-                    float ra = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LA);
-                    float rb = tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LB);
-                    v3 light_pos, light_normal;
-                    get_prim_random_point_normal(s, light_prim, ra, rb, &light_pos, &light_normal);
-                    float light_area = get_prim_area(s, light_prim);
-                    float light_choice_pdf = 1.0f / ((float)s->light_count * light_area);
-                    light_normal = vnormalized(light_normal);
-                    v3 light_dir = vsub(h.pos, light_pos);
-                    float light_dist = vnorm(light_dir);
-                    light_dir = vdivs(light_dir, light_dist);
-                    (void)light_shape_visible(s, light_prim, light_dir, light_normal, light_dist, &light_choice_pdf);   /* only its pdf reaches :245 */
-                    float NdotL_surface = vdot(fnormal, light_dir);
-                    float NdotL_light = vdot(light_normal, light_dir);
-                    if ((NdotL_surface < 0.0f) & (NdotL_light > 0.0f)) {
-                        int shadow_prim;
-                        (void)closet_hit_shadow(s, light_pos, light_dir, stack, stack_size, &shadow_prim, st);
-                        if (shadow_prim == h.prim) {
-                            brdf = disney_evaluate_pdf(s, fnormal, vneg(direction), vneg(light_dir), mat_id, &brdf_pdf);
-                            light_pdf = light_dist * light_dist * light_choice_pdf / NdotL_light;
-                            if (brdf_pdf > 0.0f) {
-                                const float w = power_heuristic(light_pdf, brdf_pdf) / fmax_(0.0001f, light_pdf);
-                                v4s c = v4_scale(light_rad, w);
-                                c = v4_mul(c, light_tint);
-                                c = v4_mul(c, throughout);
-                                c = v4_mul(c, reflect_spec);
-                                c = v4_scale(c, brdf);
-                                c = v4_scale(c, fabs_(NdotL_surface));
-                                radiance = v4_add(radiance, c);
-                            }
-                        }
-                    }
-                    }
-                    float rnd[3] = { tm_rand(seed, pixel, frame, dim0 + TM_SLOT_LOBE),
-                                     tm_rand(seed, pixel, frame, dim0 + TM_SLOT_R1),
-                                     tm_rand(seed, pixel, frame, dim0 + TM_SLOT_R2) };
-                    next_dir = disney_sample(s, direction, fnormal, mat_id, rnd);
-                    f_or_b = 1.0f;
-                    brdf = disney_evaluate_pdf(s, fnormal, next_dir, vneg(direction), mat_id, &brdf_pdf);      /* (N, V = next_dir, L = -direction): :251 */
-                    brdf *= fabs_(vdot(normal, next_dir));
-                }
-                next_origin = offset_ray(h.pos, vscale(fnormal, signf(f_or_b)));
-                if ((brdf_pdf > 0.0f) & (fmax_(throughout.v[2], fmax_(throughout.v[0], throughout.v[1])) > 0.0f)) {
-                    throughout = v4_mul(throughout, v4_divs(v4_scale(reflect_spec, brdf), brdf_pdf));
-                    depth += 1;
-                } else break;
-            }
-        } else {
-            /* :267-274: the analytic sky */
-            const float dis = m_sqrt(direction.x * direction.x + direction.z * direction.z);
-            const float beta = m_atan2(direction.y, dis);
-            const float gamma = m_acos(vdot(direction, V(sp->sun_dir[0], sp->sun_dir[1], sp->sun_dir[2])));
-            const float theta = clampf(0.5f * PI_SCENE - beta, 0.0f, 0.5f * PI_SCENE);
-            v4s ibl;
-            for (int k = 0; k < HERO_N; k++) ibl.v[k] = sky_radiance(sp, theta, gamma, Lambda + (float)k * HERO_LAMBDA_STEP);
-            radiance = v4_add(radiance, v4_mul(v4_mul(throughout, ibl), light_rad));
-            break;
+        const shade_spec_step r = pt_spec_step(s, sp, seed, pixel, frame, depth, depth == max_depth - 1, origin, direction, h.t, h.u, h.v, h.prim,
+                                               throughout, radiance);
+        radiance = r.radiance;
+        if (st && r.shaded) st->shaded++;
+        if (r.want_shadow) {                                                        /* PT_Spec.py:243-248 */
+            int shadow_prim;
+            (void)closet_hit_shadow(s, r.sh_o, r.sh_d, stack, stack_size, &shadow_prim, st);
+            if (shadow_prim == r.sh_expect) radiance = v4_add(radiance, r.sh_c);
         }
+        if (!r.want_next) break;
+        next_origin = r.next_o; next_dir = r.next_d; throughout = r.next_thr;
+        depth += 1;
     }
     return radiance;
 }
@@ -2699,6 +2758,33 @@ int orc_kat_shade_step(const orc_scene *s, const float *in, int in_stride, float
         o[11] = r.next_thr.x; o[12] = r.next_thr.y; o[13] = r.next_thr.z; o[14] = r.next_pdf; oi[15] = r.next_spec; oi[16] = r.want_shadow;
         o[17] = r.sh_o.x; o[18] = r.sh_o.y; o[19] = r.sh_o.z; o[20] = r.sh_d.x; o[21] = r.sh_d.y; o[22] = r.sh_d.z;
         o[23] = r.sh_c.x; o[24] = r.sh_c.y; o[25] = r.sh_c.z; oi[26] = r.sh_expect; o[27] = r.sh_dist; oi[28] = (int32_t)r.branch;
+    }
+    return 0;
+}
+/* pt_spec_step row by row, beside the RGB rows above.  in: [n*in_stride] 32-bit words -- seed, pixel, frame, bounce, last_bounce (integers), origin3,
+ * direction3, t, u, v, prim (integer): the RGB row's words 0..14; then throughout4 (15..18) and radiance4 (19..22): 23 words; out: [n*out_stride] --
+ * radiance4 (0..3), shaded, want_next, next_o3 (6..8), next_d3 (9..11), next_thr4 (12..15), want_shadow (16), sh_o3, sh_d3, sh_c4 (23..26), sh_expect,
+ * sh_dist (the 29 words of the device's tirt_kat_shade_spec_step), then the branch word (SSB_*): 30 words.  A row with t < INF_VALUE must name a
+ * primitive of the scene. */
+int orc_kat_shade_spec_step(const orc_scene *s, const orc_spec *sp, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    if (!s || !sp || !in || !out || in_stride < 23 || out_stride < 30 || n < 0) return -1;
+    for (int i = 0; i < n; i++) {
+        const float *a = in + (size_t)i * in_stride; const uint32_t *w = (const uint32_t *)a;
+        if (a[11] < INF_VALUE && ((int32_t)w[14] < 0 || (int32_t)w[14] >= s->n)) return -2;
+    }
+    for (int i = 0; i < n; i++) {
+        const float *a = in + (size_t)i * in_stride; const uint32_t *w = (const uint32_t *)a;
+        float *o = out + (size_t)i * out_stride; int32_t *oi = (int32_t *)o;
+        v4s thr, rad; for (int k = 0; k < HERO_N; k++) { thr.v[k] = a[15 + k]; rad.v[k] = a[19 + k]; }
+        const shade_spec_step r = pt_spec_step(s, sp, w[0], w[1], w[2], (int)w[3], (int)w[4] != 0, V(a[5], a[6], a[7]), V(a[8], a[9], a[10]), a[11], a[12], a[13], (int)w[14],
+                                               thr, rad);
+        for (int k = 0; k < HERO_N; k++) { o[k] = r.radiance.v[k]; o[12 + k] = r.next_thr.v[k]; o[23 + k] = r.sh_c.v[k]; }
+        oi[4] = r.shaded; oi[5] = r.want_next;
+        o[6] = r.next_o.x; o[7] = r.next_o.y; o[8] = r.next_o.z; o[9] = r.next_d.x; o[10] = r.next_d.y; o[11] = r.next_d.z;
+        oi[16] = r.want_shadow;
+        o[17] = r.sh_o.x; o[18] = r.sh_o.y; o[19] = r.sh_o.z; o[20] = r.sh_d.x; o[21] = r.sh_d.y; o[22] = r.sh_d.z;
+        oi[27] = r.sh_expect; o[28] = r.sh_dist; oi[29] = (int32_t)r.branch;
     }
     return 0;
 }

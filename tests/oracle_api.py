@@ -34,6 +34,12 @@ SB = {name: 1 << k for k, name in enumerate((
     "emit_mis", "emit_spec", "glass_reflect", "glass_refract", "extinct", "nee", "nee_nopdf", "nee_reject", "lobe_diffuse", "lobe_specular", "end_pdf",
     "miss_finite", "miss_nonfinite", "light_tri", "light_sphere", "light_spot", "light_laser"))}
 
+# orc_kat_shade_spec_step: words per output row (the device's 29 + the branch word) and the bits of its branch word (oracle.c, SSB_*)
+SHADE_SPEC_STEP_OUT = 30
+SSB = {name: 1 << k for k, name in enumerate((
+    "emit_front", "emit_back", "glass_reflect", "glass_refract", "nee", "nee_nopdf", "nee_reject", "light_tri", "light_sphere", "light_spot", "light_laser",
+    "end_pdf", "end_thr", "miss_finite", "miss_nonfinite", "miss_below"))}
+
 # orc_bd_record (oracle.c): one addition into BDPT's radiance planes -- frame, source pixel p, target pixel q, strategy (e, l), the three values added
 BD_RECORD = np.dtype([("frame", np.int32), ("p", np.int32), ("q", np.int32), ("e", np.int32), ("l", np.int32), ("r", np.float32, (3,))])
 assert BD_RECORD.itemsize == 32
@@ -86,6 +92,8 @@ def load(libm=False, native=False):
         L.orc_shadow_hit_batch.argtypes = [_vp, _f32p, C.c_int, C.c_int, _f32p, _i32p, _vp]
         L.orc_kat_shade_step.restype = C.c_int
         L.orc_kat_shade_step.argtypes = [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]
+        L.orc_kat_shade_spec_step.restype = C.c_int
+        L.orc_kat_shade_spec_step.argtypes = [_vp, _vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int]
         L.orc_pt_rgb_render.restype = C.c_int
         L.orc_pt_rgb_render.argtypes = [_vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int,
                                         _f32p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -212,6 +220,17 @@ class OracleScene:
         rc = self.L.orc_kat_shade_step(self.h, rows.reshape(-1), stride, out.reshape(-1), SHADE_STEP_OUT, n)
         if rc != 0:
             raise ValueError("orc_kat_shade_step: %s" % {-1: "bad arguments", -2: "a hit row names no primitive of the scene"}.get(rc, rc))
+        return out
+
+    def kat_shade_spec_step(self, rows):
+        """orc_kat_shade_spec_step (set_spectral first): rows (n, 23) of 32-bit words (layout in oracle.c / include/tirt.h) -> (n, 30) float32 view,
+        word 29 = the branch word"""
+        rows = np.ascontiguousarray(rows).view(np.float32)
+        n, stride = rows.shape
+        out = np.zeros((n, SHADE_SPEC_STEP_OUT), np.float32)
+        rc = self.L.orc_kat_shade_spec_step(self.h, self.spec, rows.reshape(-1), stride, out.reshape(-1), SHADE_SPEC_STEP_OUT, n)
+        if rc != 0:
+            raise ValueError("orc_kat_shade_spec_step: %s" % {-1: "bad arguments", -2: "a hit row names no primitive of the scene"}.get(rc, rc))
         return out
 
     def shadow_hit(self, rays, stack_size=64, counts=False):

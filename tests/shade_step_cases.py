@@ -191,7 +191,8 @@ def unit(v):
     return v / np.linalg.norm(v, axis=-1, keepdims=True)
 
 
-def real_hit_rows(ex, orc, rng, n_random=16000, n_bundle=8000, n_second=12000):
+def random_and_bundled_rays(ex, rng, n_random=16000, n_bundle=8000):
+    """rays[n, 6] float32: random rays from inside and outside the scene box, then camera-like coherent bundles"""
     sc = ex.scene
     lo, hi = sc.minboundarynp[0].astype(np.float64), sc.maxboundarynp[0].astype(np.float64)
     mid, ext = 0.5 * (lo + hi), 0.5 * (hi - lo)
@@ -210,7 +211,11 @@ def real_hit_rows(ex, orc, rng, n_random=16000, n_bundle=8000, n_second=12000):
         g = (np.arange(20) - 9.5) / 20.0 * rng.uniform(0.2, 0.8)
         dd = unit(fwd[None, None, :] + g[:, None, None] * side[None, None, :] + g[None, :, None] * up[None, None, :]).reshape(-1, 3)
         rays.append(np.concatenate([np.broadcast_to(eye, dd.shape), dd], axis=1).astype(f32))
-    first = rows_from_rays(orc, np.concatenate(rays, axis=0), rng)
+    return np.concatenate(rays, axis=0)
+
+
+def real_hit_rows(ex, orc, rng, n_random=16000, n_bundle=8000, n_second=12000):
+    first = rows_from_rays(orc, random_and_bundled_rays(ex, rng, n_random, n_bundle), rng)
     # second-bounce rays: the continuation the oracle's step gives the first hits with an ordinary state (they start at offset_ray points)
     plain = first.copy()
     pf = plain.view(np.float32)

@@ -106,6 +106,7 @@ HITS_MAX = 64                                                       # TIRT_HITS_
 NEAREST_MAX = 64                                                    # TIRT_NEAREST_MAX: the largest k of tirt_query_nearest
 KAT_LIST_WALK_OUT = 9                                               # words per output row of tirt_kat_primary_list_walk
 KAT_STEP_IN, KAT_STEP_OUT = 23, 28                                 # words per row of tirt_kat_shade_step
+KAT_SPEC_STEP_IN, KAT_SPEC_STEP_OUT = 23, 29                       # words per row of tirt_kat_shade_spec_step
 
 # context options that select code rather than tune it: name -> (default, meaning).  (The tuning options are listed in include/tirt.h.)
 OPTIONS = {
@@ -232,6 +233,7 @@ SIGNATURES = {
     "tirt_shade_table_download": (C.c_int, [_vp, C.c_int, _f32p, C.c_uint64]),
     "tirt_kat_shade_tables": (C.c_int, [_vp, C.c_int, _vp, _f32p, C.c_int]),
     "tirt_kat_shade_step": (C.c_int, [_vp, C.c_uint32, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
+    "tirt_kat_shade_spec_step": (C.c_int, [_vp, C.c_uint32, _f32p, C.c_int, _f32p, C.c_int, C.c_int]),
     "tirt_obj_load": (C.c_int, [C.c_char_p, C.POINTER(_vp)]),
     "tirt_obj_free": (None, [_vp]),
     "tirt_obj_material_count": (C.c_int, [_vp]),
@@ -1257,6 +1259,10 @@ class Context:
         """include/tirt.h, tirt_kat_shade_step: rows (n, >= 23) of 32-bit words (float32 view; integers as bit patterns) -> (n, out_stride) float32."""
         return kat_shade_step(self.handle, feat, rows, out_stride)
 
+    def kat_shade_spec_step(self, feat, rows, out_stride=KAT_SPEC_STEP_OUT):
+        """include/tirt.h, tirt_kat_shade_spec_step: rows (n, >= 23) of 32-bit words (float32 view; integers as bit patterns) -> (n, out_stride) float32."""
+        return kat_shade_spec_step(self.handle, feat, rows, out_stride)
+
     def kat_spec(self, which, inp, out_stride):
         return _kat_rows("tirt_kat_spec", self.handle, (int(which),), inp, out_stride)
 
@@ -1264,6 +1270,11 @@ class Context:
 def kat_shade_step(handle, feat, rows, out_stride=KAT_STEP_OUT, in_stride=None):
     """tirt_kat_shade_step on a raw context handle (None: only the refusals that need no context can be reached)."""
     return _kat_rows("tirt_kat_shade_step", handle, (int(feat),), rows, out_stride, words=True, in_stride=in_stride)
+
+
+def kat_shade_spec_step(handle, feat, rows, out_stride=KAT_SPEC_STEP_OUT, in_stride=None):
+    """tirt_kat_shade_spec_step on a raw context handle (None: only the refusals that need no context can be reached)."""
+    return _kat_rows("tirt_kat_shade_spec_step", handle, (int(feat),), rows, out_stride, words=True, in_stride=in_stride)
 
 
 def texture_upload(handle, textures):

@@ -633,6 +633,8 @@ int flush_pending(tirt_ctx *c);
 bool kat_shade_step_has_inst(unsigned feat);      // tirt_render.hip: is `feat` the word of an instantiation of k_shade
 bool shade_instantiation(unsigned word, int specialize, bool spectral, unsigned *feat);      // tirt_render.hip: the word of the instantiation a render launches; false: none
 int kat_shade_step(tirt_ctx *c, unsigned feat, const float *in, int in_stride, float *out, int out_stride, int n);
+bool kat_shade_spec_step_has_inst(unsigned feat);      // tirt_render.hip: is `feat` the word of an instantiation of k_shade_spec
+int kat_shade_spec_step(tirt_ctx *c, unsigned feat, const float *in, int in_stride, float *out, int out_stride, int n);
 
 // The device round trip of a known-answer entry (tirt_kat_*, tirt_spec_table_build), after the entry's own checks: device copies of the inputs (on c->stream;
 // an input of 0 bytes gets none, its pointer is null), a zeroed output, `launch(device inputs in order, device output)` -- one hipLaunchKernelGGL on c->stream --,

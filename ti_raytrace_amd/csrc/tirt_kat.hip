@@ -1,6 +1,6 @@
 // tirt_kat.hip -- the known-answer entry points of include/tirt.h (tirt_kat_*): device functions evaluated row by row, one thread per row, for the tests
 // that hold them to the oracle bit for bit.  Every entry checks its own arguments and then makes one kat_round_trip (tirt_internal.h).  The kernels of
-// tirt_kat_env_*, tirt_kat_shade_step and tirt_kat_spec live beside the code they evaluate (tirt_envsample.hip, tirt_render.hip, tirt_spectral.hip).
+// tirt_kat_env_*, tirt_kat_shade_step, tirt_kat_shade_spec_step and tirt_kat_spec live beside the code they evaluate (tirt_envsample.hip, tirt_render.hip, tirt_spectral.hip).
 #include "tirt_internal.h"
 #include "tirt_spectral.h"
 #include "tirt_pvb.h"
@@ -373,6 +373,16 @@ int tirt_kat_shade_step(tirt_ctx *c, uint32_t feat, const float *in, int in_stri
     TIRT_REQUIRE(kat_shade_step_has_inst(feat), "tirt_kat_shade_step: feat is not an instantiation of k_shade (the words tirt_shade_instantiation returns: include/tirt.h, tirt_kat_shade_step)");
     CTX(c);
     return kat_shade_step(c, feat, in, in_stride, out, out_stride, n);
+}
+
+int tirt_kat_shade_spec_step(tirt_ctx *c, uint32_t feat, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    // what needs no context first (and no device: these refusals hold for a null context too)
+    TIRT_REQUIRE(in && out && n >= 0, "tirt_kat_shade_spec_step: null pointer or negative n");
+    TIRT_REQUIRE(in_stride >= 23 && out_stride >= 29, "tirt_kat_shade_spec_step: stride too small (23 words in, 29 out)");
+    TIRT_REQUIRE(kat_shade_spec_step_has_inst(feat), "tirt_kat_shade_spec_step: feat is not an instantiation of k_shade_spec (32, 4 or 127: include/tirt.h, tirt_kat_shade_spec_step)");
+    CTX(c);
+    return kat_shade_spec_step(c, feat, in, in_stride, out, out_stride, n);
 }
 
 int tirt_kat_shade_tables(tirt_ctx *c, int which, const float *in, float *out, int n)

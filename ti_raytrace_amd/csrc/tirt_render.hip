@@ -649,9 +649,17 @@ __global__ void k_film(PathState ps, TileMap tm, int P, int F, uint32_t frame_be
 // the hero wavelength is not stored: Lambda = 360 + 100 * rand(pixel, frame, TM_DIM_SPEC_LAMBDA) is recomputed where it is needed.
 // Reference behaviours kept: the NEE sample is tinted with the colour of the surface that was HIT (`light_tint` of :213), not with
 // the light's emission; Disney.evaluate_pdf for the continuation is called with (N, V = next_dir, L = -direction) (:251).
-template <unsigned FEAT>
+//
+// KAT: the known-answer instantiation behind tirt_kat_shade_spec_step (include/tirt.h) -- this kernel's shading body, the same text, on row q of a table in place of
+// path q of a queue.  What differs is compiled under `if constexpr (KAT)` and nowhere else: the path's state and its (seed, pixel, frame, bounce, last_bounce) come
+// from the row's 23 words, and the step's answers go to the 29 words of the output row instead of the queues (no compaction, no atomics, no statistic).  Its
+// arguments: paths.in.ox = the input rows, paths.out.ox = the output rows, count_fixed = the number of rows, P = the input stride, tm.H = the output stride,
+// count_ptr = nullptr; the others are unused.  The render's instantiations (KAT == false) hold no trace of it: their instruction text is the kernel's before
+// the parameter was added (tools/isa_stats.py; docs/HISTORY.md).
+[[maybe_unused]] constexpr int KAT_SPEC_STEP_IN = 23, KAT_SPEC_STEP_OUT = 29;
+template <unsigned FEAT, bool KAT = false>
 __global__ __launch_bounds__(SH_BLOCK, 4) void k_shade_spec(ShadeArgs paths_in_kernarg_segment, SceneView sc, SpecView sp, TileMap tm, int P,
-                                                   uint32_t frame_begin, uint32_t seed, int bounce, int last_bounce,
+                                                   uint32_t frame_begin, uint32_t seed_of_batch, int bounce_of_launch, int last_bounce_of_launch,
                                                    const int *count_ptr, int count_fixed, unsigned long long *append_ctr,
                                                    DevCounters *ctr, v3 eye)
 {
@@ -666,8 +674,14 @@ __global__ __launch_bounds__(SH_BLOCK, 4) void k_shade_spec(ShadeArgs paths_in_k
         f4s radiance = f4_set(0.0f), next_thr = radiance, sh_c = radiance;
         v3 next_o = V(0.0f, 0.0f, 0.0f), next_d = next_o, sh_o = next_o, sh_d = next_o;
         float sh_dist = 0.0f; int sh_expect = -2;
+        [[maybe_unused]] const unsigned long long n_shaded_before = n_shaded;
         if (live) {
-            const bool first = bounce == 0;
+            // a row's words (KAT); integers travel as their bit patterns
+            [[maybe_unused]] const float *const row = KAT ? paths_in_kernarg_segment.in.ox + (size_t)q * (size_t)P : nullptr;
+            const uint32_t seed = KAT ? (uint32_t)__float_as_int(row[0]) : seed_of_batch;
+            const int bounce = KAT ? __float_as_int(row[3]) : bounce_of_launch;
+            const int last_bounce = KAT ? (int)(__float_as_int(row[4]) != 0) : last_bounce_of_launch;
+            const bool first = KAT ? false : bounce == 0;
             SH_COLD(ca);          // (the path-state pointers: read here, in one batch of scalar loads -- see k_shade)
             const int *const c_slot = ca->in.slot; const float4 *const c_hit = ca->ps.hit;
             const float *const c_ox = ca->in.ox, *const c_oy = ca->in.oy, *const c_oz = ca->in.oz, *const c_dx = ca->in.dx, *const c_dy = ca->in.dy, *const c_dz = ca->in.dz;
@@ -675,21 +689,31 @@ __global__ __launch_bounds__(SH_BLOCK, 4) void k_shade_spec(ShadeArgs paths_in_k
             const float *const c_tw = ca->in.brdf_pdf, *const c_rw = (const float *)ca->in.flags;
             asm volatile("" :: "s"(c_slot), "s"(c_hit), "s"(c_ox), "s"(c_oy), "s"(c_oz), "s"(c_dx), "s"(c_dy), "s"(c_dz), "s"(c_tr), "s"(c_tg), "s"(c_tb),
                          "s"(c_rr), "s"(c_rg), "s"(c_rb), "s"(c_tw), "s"(c_rw));
-            slot = first ? q : c_slot[q];
-            int f, k; slot_to_frame_pixel(tm, P, slot, f, k);
-            const uint32_t pixel = (uint32_t)local_to_pixel(tm, k);
-            const uint32_t frame = frame_begin + (uint32_t)f;
+            uint32_t pixel, frame;
+            if constexpr (KAT) { pixel = (uint32_t)__float_as_int(row[1]); frame = (uint32_t)__float_as_int(row[2]); }
+            else {
+                slot = first ? q : c_slot[q];
+                int f, k; slot_to_frame_pixel(tm, P, slot, f, k);
+                pixel = (uint32_t)local_to_pixel(tm, k);
+                frame = frame_begin + (uint32_t)f;
+            }
             const uint32_t dim0 = TM_DIM_BOUNCE0 + TM_DIMS_PER_BOUNCE * (uint32_t)bounce;
             const float Lambda = HERO_LAMBDA_MIN + HERO_LAMBDA_STEP * tm_rand(seed, pixel, frame, TM_DIM_SPEC_LAMBDA);     // PT_Spec.py:191
-            const v3 origin = first ? eye : V(c_ox[q], c_oy[q], c_oz[q]);
-            const v3 direction = V(c_dx[q], c_dy[q], c_dz[q]);
-            const float4 hrec = load_hit_record(c_hit, q);
-            const float t = hrec.x;
+            v3 origin, direction; float4 hrec;
             f4s throughout = f4_set(1.0f);
-            if (!first) {
-                throughout.v[0] = c_tr[q]; throughout.v[1] = c_tg[q]; throughout.v[2] = c_tb[q]; throughout.v[3] = c_tw[q];
-                radiance.v[0] = c_rr[q]; radiance.v[1] = c_rg[q]; radiance.v[2] = c_rb[q]; radiance.v[3] = c_rw[q];
+            if constexpr (KAT) {
+                origin = V(row[5], row[6], row[7]); direction = V(row[8], row[9], row[10]); hrec = make_float4(row[11], row[12], row[13], row[14]);
+                for (int w = 0; w < HERO_N; w++) { throughout.v[w] = row[15 + w]; radiance.v[w] = row[19 + w]; }
+            } else {
+                origin = first ? eye : V(c_ox[q], c_oy[q], c_oz[q]);
+                direction = V(c_dx[q], c_dy[q], c_dz[q]);
+                hrec = load_hit_record(c_hit, q);
+                if (!first) {
+                    throughout.v[0] = c_tr[q]; throughout.v[1] = c_tg[q]; throughout.v[2] = c_tb[q]; throughout.v[3] = c_tw[q];
+                    radiance.v[0] = c_rr[q]; radiance.v[1] = c_rg[q]; radiance.v[2] = c_rb[q]; radiance.v[3] = c_rw[q];
+                }
             }
+            const float t = hrec.x;
             const f4s light_rad = hero_sample(sp.spd[0], Lambda);                                   // :212
             if (t < INF_VALUE) {
                 const int prim_id = __float_as_int(hrec.w);
@@ -770,6 +794,18 @@ __global__ __launch_bounds__(SH_BLOCK, 4) void k_shade_spec(ShadeArgs paths_in_k
                 radiance = radiance + ((throughout * ibl) * light_rad);
             }
         }
+        if constexpr (KAT) {          // the row's answers: what the stores below would write, and whether the row was counted as shaded
+            if (live) {
+                float *const o = paths_in_kernarg_segment.out.ox + (size_t)q * (size_t)tm.H;
+                for (int w = 0; w < HERO_N; w++) { o[w] = radiance.v[w]; o[12 + w] = next_thr.v[w]; o[23 + w] = sh_c.v[w]; }
+                o[4] = __int_as_float(n_shaded != n_shaded_before ? 1 : 0); o[5] = __int_as_float(want_next ? 1 : 0);
+                o[6] = next_o.x; o[7] = next_o.y; o[8] = next_o.z; o[9] = next_d.x; o[10] = next_d.y; o[11] = next_d.z;
+                o[16] = __int_as_float(want_shadow ? 1 : 0);
+                o[17] = sh_o.x; o[18] = sh_o.y; o[19] = sh_o.z; o[20] = sh_d.x; o[21] = sh_d.y; o[22] = sh_d.z;
+                o[27] = __int_as_float(sh_expect); o[28] = sh_dist;
+            }
+            continue;
+        }
         const QueueSlots at = queue_slots(lp, it, want_next, want_shadow, s_wcnt, s_base, append_ctr);
         // a path that goes on carries its radiance along; one that ends stores it where k_film_spec reads it
         if (want_next) store_survivor_spec(at.next, slot, next_o, next_d, next_thr, radiance);
@@ -781,6 +817,7 @@ __global__ __launch_bounds__(SH_BLOCK, 4) void k_shade_spec(ShadeArgs paths_in_k
         }
         if (want_shadow) store_shadow_ray_spec(at.shadow, want_next ? at.next : ~slot, sh_o, sh_d, sh_c, sh_expect, sh_dist);
     }
+    if constexpr (KAT) return;
     __shared__ unsigned long long s_shaded;
     count_shaded(n_shaded, s_shaded, ctr);
 }
@@ -842,7 +879,7 @@ typedef void (*fused_fn_t)(ShadeArgs, SceneView, BvhView, PvbView, CameraView, T
 // fn_list: the same kernel for the batches of a pixel set (LIST); kat: tirt_kat_shade_step's; fused, fused_rest: the first step of a camera path in one kernel
 // (k_pvb_cand_shade with WALK) and its pass over the rays the lists left to k_trace (without)
 struct ShadeInst { unsigned feat; shade_fn_t fn, fn_list; kat_step_fn_t kat; fused_fn_t fused, fused_rest; };
-struct ShadeSpecInst { unsigned feat; shade_spec_fn_t fn; };
+struct ShadeSpecInst { unsigned feat; shade_spec_fn_t fn, kat; };      // kat: tirt_kat_shade_spec_step's (k_shade_spec<feat, true>)
 template <unsigned F, int MW, int MW_WALK = MW>      // MW_WALK: the bound of the fused kernel that walks the lists, where it differs (SH_MIN_WAVES_FUSED_WIDE)
 constexpr ShadeInst shade_inst() { return {F, k_shade<F, MW>, k_shade<F, MW, true>, k_kat_shade_step<F, MW>, k_pvb_cand_shade<F, MW_WALK, true>, k_pvb_cand_shade<F, MW, false>}; }
 // (Built and left out: SF_GLASS | SF_ENV | SF_LIGHT_SPHERE for Teapot and the gallery spheres -- 3 509 VALU against the generic 3 872, but 12 bytes of scratch at
@@ -863,7 +900,8 @@ static const ShadeInst SHADE_RGB[] = {
     shade_inst<SF_ALL | SF_H | SF_P, SH_MIN_WAVES_POWER>(), shade_inst<SF_I_MAPS | SF_H | SF_P, SH_MIN_WAVES_MAPS>(),
     shade_inst<SF_ALL | SF_E | SF_H | SF_P, SH_MIN_WAVES_ENV>(), shade_inst<SF_I_MAPS | SF_E | SF_H | SF_P, SH_MIN_WAVES_ENV>()};
 static const ShadeSpecInst SHADE_SPEC_INST[] = {
-    {SF_LIGHT_SPHERE, k_shade_spec<SF_LIGHT_SPHERE>}, {SF_LIGHT_TRI, k_shade_spec<SF_LIGHT_TRI>}, {SF_ALL, k_shade_spec<SF_ALL>}};
+    {SF_LIGHT_SPHERE, k_shade_spec<SF_LIGHT_SPHERE>, k_shade_spec<SF_LIGHT_SPHERE, true>}, {SF_LIGHT_TRI, k_shade_spec<SF_LIGHT_TRI>, k_shade_spec<SF_LIGHT_TRI, true>},
+    {SF_ALL, k_shade_spec<SF_ALL>, k_shade_spec<SF_ALL, true>}};
 // The rule: the first entry, in table order, that carries exactly the word's derived bits and covers its other bits (SF_CUTOUT aside: no instantiation depends on it);
 // with specialize == 0 only the entries that carry all of SF_ALL.  Null where the table has none: no word that a context can hold
 template <class T, size_t N>
@@ -912,6 +950,40 @@ int kat_shade_step(tirt_ctx *c, unsigned feat, const float *in, int in_stride, f
     if (ensure_shade_records(c)) return TIRT_ERR_HIP;
     return kat_round_trip(c, "tirt_kat_shade_step", {{in, kat_row_bytes(n, in_stride)}}, out, kat_row_bytes(n, out_stride), [&](const void *const *din, void *dout) {
         hipLaunchKernelGGL(fn, dim3((n + SH_BLOCK - 1) / SH_BLOCK), dim3(SH_BLOCK), 0, c->stream, scene_view(c), (const float *)din[0], in_stride, (float *)dout, out_stride, n);
+    });
+}
+
+// ---- the entry behind tirt_kat_shade_spec_step: the known-answer twin of the instantiation of k_shade_spec whose word is exactly `feat` ----
+static shade_spec_fn_t kat_spec_step_inst(unsigned feat)
+{
+    for (const ShadeSpecInst &e : SHADE_SPEC_INST) if (e.feat == feat) return e.kat;
+    return nullptr;
+}
+bool kat_shade_spec_step_has_inst(unsigned feat) { return kat_spec_step_inst(feat) != nullptr; }
+// the arguments that need no context were checked by the caller (tirt_kat.hip); here: what depends on the scene and the tables, then the launch
+int kat_shade_spec_step(tirt_ctx *c, unsigned feat, const float *in, int in_stride, float *out, int out_stride, int n)
+{
+    TIRT_REQUIRE(c->n >= 1, "tirt_kat_shade_spec_step: no scene");
+    TIRT_REQUIRE(c->spec_set && c->spec_view, "tirt_kat_shade_spec_step: no spectral tables (tirt_spectral_upload first)");
+    // the word pt_render picks k_shade_spec's instantiation by: the context's stored word, without the derived bits PT_Spec never sees
+    TIRT_REQUIRE((c->shade_features & ~SF_CUTOUT & ~feat) == 0u, "tirt_kat_shade_spec_step: feat does not cover the scene's feature word (tirt_shade_features)");
+    const shade_spec_fn_t fn = kat_spec_step_inst(feat);
+    TIRT_REQUIRE(fn, "tirt_kat_shade_spec_step: feat is not an instantiation of k_shade_spec");
+    for (int i = 0; i < n; i++) {
+        const float *a = in + (size_t)i * in_stride;
+        const int32_t *w = (const int32_t *)a; const int32_t prim = w[14], pixel = w[1];
+        TIRT_REQUIRE(!(a[11] < INF_VALUE) || (prim >= 0 && prim < c->n), "tirt_kat_shade_spec_step: row " + std::to_string(i) + ": prim outside [0, n_prims) of a hit (t < INF)");
+        TIRT_REQUIRE(pixel >= 0 && pixel < 0x7fffffff, "tirt_kat_shade_spec_step: row " + std::to_string(i) + ": pixel outside [0, 2^31 - 1)");
+    }
+    if (n == 0) return TIRT_OK;
+    if (sync_all(c)) return TIRT_ERR_HIP;
+    if (ensure_shade_records(c)) return TIRT_ERR_HIP;
+    return kat_round_trip(c, "tirt_kat_shade_spec_step", {{in, kat_row_bytes(n, in_stride)}}, out, kat_row_bytes(n, out_stride), [&](const void *const *din, void *dout) {
+        // the arguments of k_shade_spec<feat, true>: rows in and out where a render has its path arrays, the strides in P and tm.H, n as the fixed count
+        ShadeArgs rows{}; rows.in.ox = (float *)const_cast<void *>(din[0]); rows.out.ox = (float *)dout;
+        TileMap tm{}; tm.H = out_stride;
+        hipLaunchKernelGGL(fn, dim3((n + SH_BLOCK - 1) / SH_BLOCK), dim3(SH_BLOCK), 0, c->stream, rows, scene_view(c), *(const SpecView *)c->spec_view, tm, in_stride,
+                           0u, 0u, 0, 0, (const int *)nullptr, n, (unsigned long long *)nullptr, (DevCounters *)nullptr, V(0.0f, 0.0f, 0.0f));
     });
 }
 
