@@ -482,6 +482,26 @@ int tirt_bdpt_rgb_render(tirt_ctx *ctx, uint32_t frame_begin, int frame_count, u
  * (reflectances and emitters through the RGB -> spectrum table, dispersive glass, AddSplat through the CIE observer).  Needs
  * tirt_spectral_upload.  The example that uses it: example/prism_rainbow.py (a laser through a prism). */
 int tirt_bdpt_spec_render(tirt_ctx *ctx, uint32_t frame_begin, int frame_count, uint32_t seed);
+/* ---- BDPT under test: the contributions and the sub-path vertices themselves (tests/test_gpu_bdpt_records.py) -----------------------------
+ * A film shows BDPT's contributions only as sums formed by float atomics in no fixed order; these two show the numbers added and what they were made from.
+ * tirt_bdpt_record_enable: capacity >= 0 turns the contribution record on with room for `capacity` records and restarts its count; capacity < 0 turns it off
+ *   and frees it.  While on, tirt_bdpt_rgb_render / tirt_bdpt_spec_render write one record per contribution they EVALUATE with a target on the film: every
+ *   connection whose ray met the primitive it was aimed at (k_bd_resolve's list) and every eye sub-path that ended on an emitter (k_bd_emitted), zero or
+ *   not; an e == 1 connection that projects off the film has no target and no record.  A record is eight 32-bit words: frame, source pixel p (whose
+ *   sub-paths made it), target pixel q (where it is added), e, l as int32, then the three values added as float32 (SPEC: after the sensor conversion) --
+ *   before k_bd_resolve's pairwise pre-sum.  The order of the records is not defined.  Records beyond the capacity are dropped and still counted.
+ *   The film is made as always (same atomics); the kernels launched are instantiations that differ from the usual ones by the store alone, and with
+ *   the record off the usual ones are launched.  Waits for pending work.
+ * tirt_bdpt_record_download: the first min(capacity, kept) records into `records`, and into *needed how many the renders since the enable needed
+ *   (which may exceed either capacity).  TIRT_ERR_ARG when the record is off.
+ * tirt_bdpt_vertices_download: what the kernels of the last BDPT call left in device memory, provided it ran as ONE batch: *items = its items (frames x
+ *   owned pixels); with capacity >= *items also item_rows[4 * it] = frame, pixel, eye_depth | tail << 16 (tail: slot eye[eye_depth] holds a surface vertex of
+ *   this item whose sampling ended the path), light_depth, and vertices[it][13][80 bytes]: eye slots 0..6, light slots 0..5, each (pos, prim) (snormal, mat)
+ *   (normal, fpdf) (beta, rpdf) (wo, int16 type, int16 delta).  capacity <= 0 asks for *items alone.  Slots the item did not write hold what was there
+ *   (option "bdpt_state_fill").  Launches nothing in a render.  TIRT_ERR_ARG when no BDPT call has rendered into this film or the last one used more than one batch. */
+int tirt_bdpt_record_enable(tirt_ctx *ctx, long capacity);
+int tirt_bdpt_record_download(tirt_ctx *ctx, void *records, long capacity, long *needed);
+int tirt_bdpt_vertices_download(tirt_ctx *ctx, int32_t *item_rows, void *vertices, long capacity, long *items);
 
 /* ---- spectral path: integrator/PT_Spec.py (hero-wavelength path tracer) -----------------------------
  * tirt_spec_table_build: spectrum/JakobSpecTable.py:1-439 on the device -- the RGB -> sigmoid-spectrum coefficient table that

@@ -2071,14 +2071,33 @@ void orc_process_normal(orc_scene *s, const int32_t *vertex_index)
 static const float EPS_UF = 0.00001f;      /* UtilsFunc.py:36 */
 
 typedef struct { v3 pos, normal, snormal, beta, wo; float fpdf, rpdf; int32_t type, prim, mat, delta; } bvert;   /* BDPT_Vertex.py:10-21 */
-typedef struct { bvert eye[BD_EYE_MAX], light[BD_LIGHT_MAX], sample, ltemp, etemp, lminustemp, eminustemp; } bpixel;
+/* wmask[slot] (eye 0..6, light 7..12): the fields of that vertex which the CURRENT frame has stored -- the frame's clearing of beta / type / fpdf / rpdf and every
+ * store of bd_eye_path / bd_light_path, set where the store stands.  The reference keeps one set of arrays per pixel and never clears the rest, so a slot's delta,
+ * prim, mat or normals may be an earlier frame's; the mask tells the two apart (orc_bdpt_vertex_export).  Nothing reads it but the export. */
+#define BVF_POS 1u
+#define BVF_PRIM 2u
+#define BVF_SNORMAL 4u
+#define BVF_MAT 8u
+#define BVF_NORMAL 16u
+#define BVF_FPDF 32u
+#define BVF_BETA 64u
+#define BVF_RPDF 128u
+#define BVF_WO 256u
+#define BVF_TYPE 512u
+#define BVF_DELTA 1024u
+#define BVF_CLEARED (BVF_BETA | BVF_TYPE | BVF_FPDF | BVF_RPDF)
+typedef struct { bvert eye[BD_EYE_MAX], light[BD_LIGHT_MAX], sample, ltemp, etemp, lminustemp, eminustemp; uint32_t wmask[BD_EYE_MAX + BD_LIGHT_MAX]; } bpixel;
 
 typedef struct { float view[16]; } orc_view;
 /* One addition into `radiance` (bdpt_render_common), for the tests that bound the film per pixel (tests/bdpt_bound_expected.py): the frame, the pixel p
  * whose sub-paths made it, the pixel q it was added to, the strategy (e, l) and the three values added (SPEC: after AddSplat's conversion).  Eight 32-bit
  * words; tests/oracle_api.py has the same layout as a numpy dtype. */
 typedef struct { int32_t frame, p, q, e, l; float r[3]; } orc_bd_record;
-typedef struct { int W, H; bpixel *px; float view[16]; orc_bd_record *rec; long rec_cap, rec_n; int rec_on; } orc_bdpt;
+/* One pixel sample's sub-paths as they stand when its connections begin (after bd_eye_path and bd_light_path of the frame): the depths, whether slot
+ * eye[eye_depth] holds a surface vertex stored in this frame whose sampling ended the path (`tail`), the write masks and the 13 vertices (eye 0..6, light 0..5).
+ * tests/oracle_api.py has the same layout as a numpy dtype. */
+typedef struct { int32_t frame, pixel, eye_depth, tail, light_depth; uint32_t mask[BD_EYE_MAX + BD_LIGHT_MAX]; bvert v[BD_EYE_MAX + BD_LIGHT_MAX]; } orc_bd_vertices;
+typedef struct { int W, H; bpixel *px; float view[16]; orc_bd_record *rec; long rec_cap, rec_n; int rec_on; orc_bd_vertices *vex; long vex_cap, vex_n; int vex_on; } orc_bdpt;
 
 orc_bdpt *orc_bdpt_create(int W, int H, const float *view16)
 {
@@ -2094,6 +2113,9 @@ void orc_bdpt_destroy(orc_bdpt *b) { if (b) { free(b->px); free(b); } }
  * then NEEDED, which may be more than cap (the rest was dropped).  The recorder only listens: film and stats are the same bits with it on or off. */
 void orc_bdpt_record(orc_bdpt *b, orc_bd_record *buf, long cap) { b->rec = buf; b->rec_cap = (buf && cap > 0) ? cap : 0; b->rec_n = 0; b->rec_on = cap >= 0; }      /* cap < 0: off again */
 long orc_bdpt_record_count(const orc_bdpt *b) { return b->rec_n; }
+/* The vertex export, off by default, with the recorder's conventions: one orc_bd_vertices per pixel sample, in the order the samples are rendered; cap < 0: off. */
+void orc_bdpt_vertex_export(orc_bdpt *b, orc_bd_vertices *buf, long cap) { b->vex = buf; b->vex_cap = (buf && cap > 0) ? cap : 0; b->vex_n = 0; b->vex_on = cap >= 0; }
+long orc_bdpt_vertex_export_count(const orc_bdpt *b) { return b->vex_n; }
 
 static float cosine_hemisphere_pdf(float c) { return fmax_(0.01f, c / M_PIf); }      /* UtilsFunc.py:348-350 */
 static float remap0(float f) { return f == 0.0f ? 1.0f : f; }                        /* BDPT_RGB.py:89-93 */
@@ -2215,6 +2237,8 @@ static int bd_eye_path(const orc_scene *s, const bd_spec *spc, bpixel *P, int i,
     if (frame != 0) { jx = tm_rand(seed, pixel, frame, TM_DIM_JX) - 0.5f; jy = tm_rand(seed, pixel, frame, TM_DIM_JY) - 0.5f; }
     v3 dir = camera_dir(s, i, j, jx, jy);
     eye[0].pos = origin; eye[0].normal = dir; eye[0].beta = V(1, 1, 1); eye[0].fpdf = 1.0f; eye[0].type = VERTEX_LENS;
+    uint32_t *wm = P->wmask;
+    wm[0] |= BVF_POS | BVF_NORMAL | BVF_BETA | BVF_FPDF | BVF_TYPE;
     int pre_depth = 0, depth = 1;
     float pdfFwd = 1.0f, pdfRev = 0.0f;
     v3 beta = V(1, 1, 1);
@@ -2234,6 +2258,7 @@ static int bd_eye_path(const orc_scene *s, const bd_spec *spc, bpixel *P, int i,
             bvert *e = &eye[depth];
             e->pos = pos; e->normal = normal; e->snormal = fnormal; e->wo = dir; e->rpdf = 0.0f; e->prim = h.prim; e->mat = mat_id;
             e->fpdf = pdfFwd * fabs_(vdot(to, eye[pre_depth].normal)) * inv_dist2;
+            wm[depth] |= BVF_POS | BVF_NORMAL | BVF_SNORMAL | BVF_WO | BVF_RPDF | BVF_PRIM | BVF_MAT | BVF_FPDF | BVF_BETA | BVF_TYPE;      /* (beta and type: one of the two branches below) */
             if (mat_type == MAT_LIGHT) {
                 if (spc) e->beta = vmul(beta, bd_reflect(s, spc, mat_id));          /* SPEC: beta * reflect_power, no cosine (BDPT_SPEC.py:228) */
                 else e->beta = vscale(vmul(beta, mat_color), fabs_(vdot(normal, dir)));
@@ -2247,6 +2272,7 @@ static int bd_eye_path(const orc_scene *s, const bd_spec *spc, bpixel *P, int i,
             v3 reflect_color = bd_reflect(s, spc, mat_id);
             bsample bs = bd_sample(s, spc, dir, normal, fnormal, mat_id, mat_type, seed, pixel, frame,
                                    BD_DIM_EYE + 8u * (uint32_t)depth, &e->delta);
+            wm[depth] |= BVF_DELTA;
             pdfFwd = bs.pdfFwd;
             if (pdfFwd > 0.0f) {
                 if (mat_type == MAT_GLASS) {
@@ -2257,6 +2283,7 @@ static int bd_eye_path(const orc_scene *s, const bd_spec *spc, bpixel *P, int i,
                     pdfRev = disney_pdf(s, fnormal, bs.next_dir, vneg(dir), mat_id);
                 }
                 eye[pre_depth].rpdf = pdfRev * fabs_(vdot(to, e->normal)) * inv_dist2;
+                wm[pre_depth] |= BVF_RPDF;
                 if (!spc && bs.f_or_b < 0.0f) {            /* (SPEC has no extinction roulette) */
                     float R = m_exp(-h.t / m[6]);
                     if (tm_rand(seed, pixel, frame, BD_DIM_EYE + 8u * (uint32_t)depth + TM_SLOT_EXT) >= R) break;
@@ -2329,6 +2356,8 @@ static int bd_light_path(const orc_scene *s, const bd_spec *spc, bpixel *P, int 
     else light[0].beta = vdivs(emission, light_pdf);
     light[0].pos = lpos; light[0].normal = lnor;
     light[0].fpdf = light_pdf; light[0].rpdf = 0.0f; light[0].wo = ldir; light[0].type = VERTEX_LIGHT;
+    uint32_t *wm = P->wmask + BD_EYE_MAX;
+    wm[0] |= BVF_BETA | BVF_POS | BVF_NORMAL | BVF_FPDF | BVF_RPDF | BVF_WO | BVF_TYPE;
     int pre_depth = 0, depth = 1;
     float pdfFwd = dir_pdf, pdfRev = 0.0f;
     v3 beta = spc ? light[0].beta                                               /* SPEC: beta = power[0], no cosine (BDPT_SPEC.py:294) */
@@ -2352,9 +2381,11 @@ static int bd_light_path(const orc_scene *s, const bd_spec *spc, bpixel *P, int 
             float inv_dist2 = 1.0f / (dist * dist);
             to = vdivs(to, dist);
             L->fpdf *= fabs_(vdot(to, light[pre_depth].normal)) * inv_dist2;
+            wm[depth] |= BVF_POS | BVF_NORMAL | BVF_SNORMAL | BVF_BETA | BVF_WO | BVF_FPDF | BVF_RPDF | BVF_TYPE | BVF_PRIM | BVF_MAT;
             v3 reflect_color = bd_reflect(s, spc, mat_id);
             bsample bs = bd_sample(s, spc, dir, normal, fnormal, mat_id, mat_type, seed, pixel, frame,
                                    BD_DIM_LIGHT + 8u * (uint32_t)depth, &L->delta);
+            wm[depth] |= BVF_DELTA;
             pdfFwd = bs.pdfFwd;
             if (pdfFwd > 0.0f) {
                 if (mat_type == MAT_GLASS) {
@@ -2365,6 +2396,7 @@ static int bd_light_path(const orc_scene *s, const bd_spec *spc, bpixel *P, int 
                     pdfRev = disney_pdf(s, fnormal, bs.next_dir, vneg(dir), mat_id);
                 }
                 light[pre_depth].rpdf = pdfRev * fabs_(vdot(to, L->normal)) * inv_dist2;
+                wm[pre_depth] |= BVF_RPDF;
                 if (!spc && bs.f_or_b < 0.0f) {
                     float R = m_exp(-h.t / m[6]);
                     if (tm_rand(seed, pixel, frame, BD_DIM_LIGHT + 8u * (uint32_t)depth + TM_SLOT_EXT) >= R) break;
@@ -2644,6 +2676,7 @@ static int bdpt_render_common(const orc_scene *s, const orc_spec *spec, orc_bdpt
             bpixel *P = &B->px[p];
             for (int e = 0; e < BD_EYE_MAX; e++) { P->eye[e].beta = V(0, 0, 0); P->eye[e].type = VERTEX_NONE; P->eye[e].fpdf = 0.0f; P->eye[e].rpdf = 0.0f; }
             for (int l = 0; l < BD_LIGHT_MAX; l++) { P->light[l].beta = V(0, 0, 0); P->light[l].type = VERTEX_NONE; P->light[l].fpdf = 0.0f; P->light[l].rpdf = 0.0f; }
+            for (int k = 0; k < BD_EYE_MAX + BD_LIGHT_MAX; k++) P->wmask[k] = BVF_CLEARED;
         }
         for (long p = 0; p < (long)W * H; p++) {
             int i = (int)(p / H), j = (int)(p % H);
@@ -2656,6 +2689,16 @@ static int bdpt_render_common(const orc_scene *s, const orc_spec *spec, orc_bdpt
             int eye_depth = bd_eye_path(s, spc, P, i, j, H, frame, seed, stack, stack_size, &st);
             int light_depth = bd_light_path(s, spc, P, i, j, H, frame, seed, stack, stack_size, &st);
             const uint64_t shadow_before = st.rays_shadow;
+            if (B->vex_on) {                          /* the vertex export (orc_bdpt_vertex_export): before any connection touches the arrays */
+                if (B->vex_n < B->vex_cap) {
+                    orc_bd_vertices *x = &B->vex[B->vex_n];
+                    x->frame = (int32_t)frame; x->pixel = (int32_t)p; x->eye_depth = eye_depth; x->light_depth = light_depth;
+                    x->tail = (eye_depth < BD_EYE_MAX && (P->wmask[eye_depth] & BVF_POS)) ? 1 : 0;
+                    memcpy(x->mask, P->wmask, sizeof(x->mask));
+                    memcpy(x->v, P->eye, sizeof(bvert) * BD_EYE_MAX); memcpy(x->v + BD_EYE_MAX, P->light, sizeof(bvert) * BD_LIGHT_MAX);
+                }
+                B->vex_n++;
+            }
             for (int e = 1; e <= eye_depth; e++) {
                 for (int l = 0; l <= light_depth; l++) {
                     int depth = l + e - 2;

@@ -43,6 +43,15 @@ SSB = {name: 1 << k for k, name in enumerate((
 # orc_bd_record (oracle.c): one addition into BDPT's radiance planes -- frame, source pixel p, target pixel q, strategy (e, l), the three values added
 BD_RECORD = np.dtype([("frame", np.int32), ("p", np.int32), ("q", np.int32), ("e", np.int32), ("l", np.int32), ("r", np.float32, (3,))])
 assert BD_RECORD.itemsize == 32
+# orc_bd_vertices (oracle.c): one pixel sample's sub-paths as its connections find them -- depths, tail, per slot the mask of the fields stored in this frame
+# (BVF: bit per field) and the 13 vertices (eye slots 0..6, light slots 7..12) in the oracle's own field order
+BD_ORC_VERTEX = np.dtype([("pos", np.float32, (3,)), ("normal", np.float32, (3,)), ("snormal", np.float32, (3,)), ("beta", np.float32, (3,)), ("wo", np.float32, (3,)),
+                          ("fpdf", np.float32), ("rpdf", np.float32), ("type", np.int32), ("prim", np.int32), ("mat", np.int32), ("delta", np.int32)])
+BD_SLOTS = 13
+BD_VERTICES = np.dtype([("frame", np.int32), ("pixel", np.int32), ("eye_depth", np.int32), ("tail", np.int32), ("light_depth", np.int32),
+                        ("mask", np.uint32, (BD_SLOTS,)), ("v", BD_ORC_VERTEX, (BD_SLOTS,))])
+BVF = {name: 1 << k for k, name in enumerate(("pos", "prim", "snormal", "mat", "normal", "fpdf", "beta", "rpdf", "wo", "type", "delta"))}
+assert BD_ORC_VERTEX.itemsize == 84 and BD_VERTICES.itemsize == 4 * (5 + BD_SLOTS) + 84 * BD_SLOTS
 BD_PAIRS_MAX = 7 * 7            # e in 1 .. BD_EYE_MAX, l in 0 .. BD_LIGHT_MAX: more than the depth limit lets through
 
 _libs = {}
@@ -108,6 +117,9 @@ def load(libm=False, native=False):
         L.orc_bdpt_record.argtypes = [_vp, _vp, C.c_long]
         L.orc_bdpt_record_count.restype = C.c_long
         L.orc_bdpt_record_count.argtypes = [_vp]
+        L.orc_bdpt_vertex_export.argtypes = [_vp, _vp, C.c_long]
+        L.orc_bdpt_vertex_export_count.restype = C.c_long
+        L.orc_bdpt_vertex_export_count.argtypes = [_vp]
         L.orc_tone_map.argtypes = [C.c_float, _f32p, _f32p, C.c_long]
         L.orc_total_area.restype = C.c_float
         L.orc_total_area.argtypes = [_vp]
@@ -257,11 +269,21 @@ class OracleScene:
                                  nthreads, C.byref(st))
         return hdr, st.as_dict()
 
-    def _bdpt(self, call, cam, W, H, frame_count, hdr, state, record):
+    def _bdpt(self, call, cam, W, H, frame_count, hdr, state, record, vertices=False):
         if hdr is None:
             hdr = np.zeros((W, H, 3), np.float32)
         if state is None:
             state = self.L.orc_bdpt_create(W, H, np.ascontiguousarray(cam.view_np[0].reshape(-1), np.float32))
+        if vertices:            # one orc_bd_vertices per pixel sample; the result gains them as its last element
+            vex = np.zeros(max(W * H * frame_count, 1), BD_VERTICES)
+            self.L.orc_bdpt_vertex_export(state, vex.ctypes.data_as(_vp), len(vex))
+            try:
+                out = self._bdpt(call, cam, W, H, frame_count, hdr, state, record)
+                need = self.L.orc_bdpt_vertex_export_count(state)
+            finally:
+                self.L.orc_bdpt_vertex_export(state, None, -1)
+            assert need == W * H * frame_count, (need, W * H * frame_count)
+            return out + (vex,)
         rad = np.zeros((W, H, 3), np.float32)
         st = OrcStats()
         if not record:
@@ -279,17 +301,18 @@ class OracleScene:
         assert 0 <= need <= cap, (need, cap)
         return hdr, st.as_dict(), state, rec[:need].copy()
 
-    def bdpt_render(self, cam, W, H, frame_begin, frame_count, seed=1, stack_size=64, hdr=None, state=None, record=False):
+    def bdpt_render(self, cam, W, H, frame_begin, frame_count, seed=1, stack_size=64, hdr=None, state=None, record=False, vertices=False):
         """BDPT_RGB.render x frame_count.  Returns (hdr, stats, state); pass `state` back to continue
         with the persistent per-pixel vertex arrays of the previous frames.  record=True: (hdr, stats, state, records), the
-        additions into the radiance planes in the oracle's order (BD_RECORD; oracle.c, orc_bd_record)."""
+        additions into the radiance planes in the oracle's order (BD_RECORD; oracle.c, orc_bd_record).  vertices=True appends the sub-path vertices of every pixel
+        sample (BD_VERTICES; oracle.c, orc_bd_vertices) to whichever tuple that is."""
         return self._bdpt(lambda state, rad, hdr_, st: self.L.orc_bdpt_render(self.h, state, frame_begin, frame_count, seed, stack_size, rad, hdr_, st),
-                          cam, W, H, frame_count, hdr, state, record)
+                          cam, W, H, frame_count, hdr, state, record, vertices)
 
-    def bdpt_spec_render(self, cam, W, H, frame_begin, frame_count, seed=1, stack_size=64, hdr=None, state=None, record=False):
+    def bdpt_spec_render(self, cam, W, H, frame_begin, frame_count, seed=1, stack_size=64, hdr=None, state=None, record=False, vertices=False):
         """BDPT_SPEC.render x frame_count (set_spectral first).  Same conventions as bdpt_render."""
         return self._bdpt(lambda state, rad, hdr_, st: self.L.orc_bdpt_spec_render(self.h, self.spec, state, frame_begin, frame_count, seed, stack_size, rad, hdr_, st),
-                          cam, W, H, frame_count, hdr, state, record)
+                          cam, W, H, frame_count, hdr, state, record, vertices)
 
     def set_spectral(self, t):
         """t: PT_Spec.PathTrace.tables() -- the same arrays the device gets"""

@@ -36,12 +36,46 @@ CASES = [
     Case("duplicates_32x32", "duplicates", 32, 32, 3, 0.3, False, 2),
     Case("prism_16x12", "prism", 16, 12, 3, 0.8, True),
     Case("spec_spot_laser_16x12", "spec_spot_laser", 16, 12, 3, 0.8, True),
+    # The green wall of the box emits (and is on the light list): from 0.4 diagonals most eye sub-paths of every length end on an emitter, which is what the l == 0
+    # strategies (k_bd_emitted) need -- the cases above give (6, 0) two contributions and (7, 0) ten.  tests/bdpt_records_expected.py counts what these add.
+    Case("emitter_wall_24x20", "emitter_wall", 24, 20, 20, 0.4, False),
+    Case("spec_emitter_wall_24x20", "spec_emitter_wall", 24, 20, 20, 0.4, True),
+    # a sphere emitter inside the box: the l == 1 connections that end on one (the cases above reach a sphere 37 times in RGB)
+    Case("sphere_light_16x12", "sphere_light", 16, 12, 4, 0.8, False),
+    Case("spec_sphere_light_16x12", "spec_sphere_light", 16, 12, 4, 0.8, True),
 ]
 CASE_IDS = [c.name for c in CASES]
 BY_NAME = {c.name: c for c in CASES}
 TEETH = ("cornell_24x20", "veach_24x20")
 SPARSE = ("duplicates_32x32",)
 ONE_TARGET = ("cornell_far_7x7",)
+
+
+def emitter_wall(ex, emission=(1.5, 4.0, 1.5)):
+    """the box's green wall becomes an emitter AFTER add_obj has read it as a surface: the material's row, and its triangles onto the light list where add_obj would have
+    put them (in primitive order)"""
+    from ti_raytrace_amd import SceneData as SCD
+    sc = ex.scene
+    (index,) = [k for k, m in enumerate(sc.material_cpu) if m.type == SCD.MAT_DISNEY and tuple(np.round(m.color[:3], 3)) == (0.0, 1.0, 0.0)]
+    sc.material_cpu[index].type = SCD.MAT_LIGHT
+    sc.material_cpu[index].setColor(list(emission))
+    for first, ntri, mat, _ in sc._prim_mat:
+        if mat == index:
+            sc.light_cpu.extend(range(first, first + ntri)); sc.light_count += ntri
+    sc.light_cpu.sort()
+    assert sc.light_count == len(sc.light_cpu) == len(set(sc.light_cpu)) and sc.light_count > 2
+
+
+@functools.lru_cache(maxsize=None)
+def _spec_table(res, xyz, d65):
+    return oa.spec_table_build(res, np.frombuffer(xyz, np.float32), np.frombuffer(d65, np.float32))
+
+
+def spec_table(res, xyz, d65):
+    """the Rgb2Spec table from the oracle, built once for all the spectral cases of a session (it depends on the observer and the illuminant alone)"""
+    xyz, d65 = np.ascontiguousarray(xyz, np.float32), np.ascontiguousarray(d65, np.float32)
+    scale, coeff = _spec_table(int(res), xyz.tobytes(), d65.tobytes())
+    return scale.copy(), coeff.copy()
 
 
 def build(case, device_id=None):
@@ -61,12 +95,20 @@ def build(case, device_id=None):
     elif case.kind == "spec_spot_laser":
         ex = spot_laser_scene(W, H, device_id=device_id)
         ex.integrator = BDPT_SPEC.BDPT(W, H, ex.cam, ex.scene, 64)
+    elif case.kind in ("emitter_wall", "spec_emitter_wall", "sphere_light", "spec_sphere_light"):
+        from ti_raytrace_amd import scenes
+        ex = scenes.cornell_box(W, H, 4, device_id=device_id)
+        if case.kind.endswith("sphere_light"):
+            ex.add_sphere_light(pos=(278.0, 300.0, -280.0), radius=60.0, emission=30.0)
+        else:
+            emitter_wall(ex)
+        ex.integrator = (BDPT_SPEC if case.spec else BDPT_RGB).BDPT(W, H, ex.cam, ex.scene, 64)
     else:
         raise ValueError(case.kind)
     if device_id is None:
         ex.scene.setup_data_cpu(); ex.integrator.setup_data_cpu()
         if case.spec:
-            ex.integrator.setup_tables(lambda res, xyz, d65: oa.spec_table_build(res, xyz, d65))
+            ex.integrator.setup_tables(spec_table)
     else:
         ex.build_scene()
         ex.scene.total_area()
@@ -133,6 +175,10 @@ def test_the_recorder_changes_no_bit_and_the_record_is_complete_and_ordered(name
     assert same_bits(plain, film) and pst == st, "the film or the stats change with the recorder on"
     again, ast, _ = oracle_render(o, ex, case, record=False)          # (and a state that once recorded goes back to not recording: _bdpt turns it off)
     assert same_bits(again, film) and ast == st
+    vfilm, vst, _, vrec, vex = oracle_render(o, ex, case, vertices=True)          # the vertex export (and the write masks it reads) only listens too
+    assert same_bits(vfilm, film) and vst == st and vrec.tobytes() == rec.tobytes() and len(vex) == W * H * frames, "the film, the stats or the records change with the vertex export on"
+    vfilm, vst, _, vex2 = oracle_render(o, ex, case, record=False, vertices=True)
+    assert same_bits(vfilm, film) and vst == st and vex2.tobytes() == vex.tobytes()
     assert rec.dtype == oa.BD_RECORD and len(rec) > 0
     assert (np.diff(rec["frame"]) >= 0).all() and rec["frame"].min() == 0 and rec["frame"].max() == frames - 1
     for f in range(frames):

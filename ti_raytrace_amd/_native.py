@@ -107,6 +107,13 @@ NEAREST_MAX = 64                                                    # TIRT_NEARE
 KAT_LIST_WALK_OUT = 9                                               # words per output row of tirt_kat_primary_list_walk
 KAT_STEP_IN, KAT_STEP_OUT = 23, 28                                 # words per row of tirt_kat_shade_step
 KAT_SPEC_STEP_IN, KAT_SPEC_STEP_OUT = 23, 29                       # words per row of tirt_kat_shade_spec_step
+# tirt_bdpt_record_download: one contribution of BDPT -- frame, source pixel p, target pixel q, strategy (e, l), the three values added
+BD_RECORD = np.dtype([("frame", np.int32), ("p", np.int32), ("q", np.int32), ("e", np.int32), ("l", np.int32), ("r", np.float32, (3,))])
+# tirt_bdpt_vertices_download: one sub-path vertex (csrc/tirt_bdpt.hip, bvert: five 16-byte quads) and what it returns per item
+BD_VERTEX = np.dtype([("pos", np.float32, (3,)), ("prim", np.int32), ("snormal", np.float32, (3,)), ("mat", np.int32), ("normal", np.float32, (3,)), ("fpdf", np.float32),
+                      ("beta", np.float32, (3,)), ("rpdf", np.float32), ("wo", np.float32, (3,)), ("type", np.int16), ("delta", np.int16)])
+BD_ITEM_ROW = np.dtype([("frame", np.int32), ("pixel", np.int32), ("eye_depth", np.int32), ("tail", np.int32), ("light_depth", np.int32)])
+assert BD_RECORD.itemsize == 32 and BD_VERTEX.itemsize == 80
 
 # context options that select code rather than tune it: name -> (default, meaning).  (The tuning options are listed in include/tirt.h.)
 OPTIONS = {
@@ -169,6 +176,9 @@ SIGNATURES = {
     "tirt_pt_rgb_render": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int]),
     "tirt_bdpt_rgb_render": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_uint32]),
     "tirt_bdpt_spec_render": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_uint32]),
+    "tirt_bdpt_record_enable": (C.c_int, [_vp, C.c_long]),
+    "tirt_bdpt_record_download": (C.c_int, [_vp, _vp, C.c_long, C.POINTER(C.c_long)]),
+    "tirt_bdpt_vertices_download": (C.c_int, [_vp, C.POINTER(C.c_int32), _vp, C.c_long, C.POINTER(C.c_long)]),
     "tirt_debug_render": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int]),
     "tirt_tone_map": (C.c_int, [_vp, C.c_float]),
     "tirt_film_download": (C.c_int, [_vp, _vp, _vp]),
@@ -450,6 +460,7 @@ class Context:
         self._h = C.c_void_p()
         check(lib().tirt_create(int(device_id), C.byref(self._h)))
         self.device_id = int(device_id)
+        self._bdpt_record_cap = -1                 # what bdpt_record_enable asked for (bdpt_record_download returns no more than the device kept)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -671,6 +682,39 @@ class Context:
 
     def bdpt_spec_render(self, frame_begin, frame_count, seed):
         check(lib().tirt_bdpt_spec_render(self.handle, int(frame_begin), int(frame_count), int(seed)))
+
+    def bdpt_record_enable(self, capacity):
+        """capacity >= 0: the BDPT renders from now on also write their contributions (BD_RECORD) and the count restarts; < 0: off"""
+        check(lib().tirt_bdpt_record_enable(self.handle, int(capacity)))
+        self._bdpt_record_cap = int(capacity)
+
+    def bdpt_record_download(self, capacity=None, out=None):
+        """(records, needed): what the BDPT renders since bdpt_record_enable wrote, in no defined order, and how many records they needed -- more than
+        len(records) when the enabled capacity (or `capacity` / `out` here) was too small.  capacity None: as many as were needed (or as `out` holds)."""
+        need = C.c_long(0)
+        if out is None:
+            if capacity is None:
+                check(lib().tirt_bdpt_record_download(self.handle, None, 0, C.byref(need)))
+                capacity = need.value
+            out = np.zeros(int(capacity), BD_RECORD)
+        else:
+            assert out.dtype == BD_RECORD and out.flags["C_CONTIGUOUS"]
+            capacity = len(out) if capacity is None else min(int(capacity), len(out))
+        check(lib().tirt_bdpt_record_download(self.handle, out.ctypes.data_as(_vp), int(capacity), C.byref(need)))
+        return out[:max(0, min(int(capacity), need.value, self._bdpt_record_cap))], need.value          # (what was kept: not more than the enabled capacity)
+
+    def bdpt_vertices_download(self):
+        """(rows, vertices) of the last BDPT call, which must have run as one batch: rows[n] (frame, pixel, eye_depth, tail, light_depth) and
+        vertices[n, 13] of BD_VERTEX (eye slots 0..6, light slots 7..12) as the kernels left them"""
+        n = C.c_long(0)
+        check(lib().tirt_bdpt_vertices_download(self.handle, None, None, 0, C.byref(n)))
+        raw = np.zeros((n.value, 4), np.int32)
+        verts = np.zeros((n.value, 13), BD_VERTEX)
+        check(lib().tirt_bdpt_vertices_download(self.handle, raw.ctypes.data_as(C.POINTER(C.c_int32)), verts.ctypes.data_as(_vp), n.value, C.byref(n)))
+        rows = np.zeros(n.value, BD_ITEM_ROW)
+        rows["frame"], rows["pixel"], rows["light_depth"] = raw[:, 0], raw[:, 1], raw[:, 3]
+        rows["eye_depth"], rows["tail"] = raw[:, 2] & 0xffff, raw[:, 2] >> 16
+        return rows, verts
 
     def pt_spec_render(self, frame_begin, frame_count, seed, max_depth=10, stack_size=64, flags=0):
         check(lib().tirt_pt_spec_render(self.handle, int(frame_begin), int(frame_count), int(seed),

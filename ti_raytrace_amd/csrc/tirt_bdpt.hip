@@ -25,6 +25,7 @@
 // frame order, over a small persistent per-pixel memory of the seven delta fields (`bdpt_px`) -- every surface vertex's store
 // counts, including the one of a vertex whose sampling ended the path and which the returned depth therefore leaves out.  Everything else
 // (sample/temp vertices of mis_weight, geometry of slots beyond the current depth) is written before it is read.
+// (Held on the device since: tests/test_gpu_bdpt_records.py compares every vertex field the reference stores in a frame, `delta` on every live slot, and every contribution with the oracle's, bit for bit.)
 // Other reference behaviours kept on purpose (see oracle/oracle.c for the same list): material INDEX compared with
 // MAT_DISNEY in mis_weight; restores to index -1 skipped.  Light-tracing contributions are added to other pixels with
 // float atomics, so a frame is reproducible only up to the order of those additions (the parity test uses the north
@@ -363,6 +364,12 @@ TD void bd_sample_light(const BdCtx &c, uint32_t pixel, uint32_t frame, uint32_t
     lpos_o = lpos; lnor_o = lnor; ldir_o = ldir; emission_o = emission; lp_o = lp; choice_pdf_o = choice_pdf; dir_pdf_o = dir_pdf;
 }
 
+// Where the shadow ray of an l == 1 connection, aimed at a point on emitter `prim` from `dist` away, may be cut off (option "bdpt_bounded").  A triangle is met AT
+// the point.  A sphere is met on its near side first, and Scene.sample_li / sample_light choose points all over it: with the point on the far side, geometry INSIDE
+// the sphere lies behind the ray's closest hit and before the point, and a bounded query would settle on it as an occluder where the reference's closest hit is the
+// sphere (tests/test_gpu_bdpt_records.py, spec_sphere_light_16x12: the box's tall block reaches into the sphere).  Shapes get the full query.
+TD float bd_emitter_bound(const BdCtx &c, int prim, float dist) { return (c.bounded && c.sc.primitive[(size_t)prim * PRI_VEC] == PRIMITIVE_TRI) ? dist : -1.0f; }
+
 // BDPT_RGB.py:481-592
 template <bool SPEC>
 TD v3 bd_connect_path(const BdCtx &c, const bpixel &P, const bvert &EV, bvert &sample, int i, int j, int e, int l, uint32_t frame, int &nu, int &nv, Tracer &T)
@@ -409,7 +416,7 @@ TD v3 bd_connect_path(const BdCtx &c, const bpixel &P, const bvert &EV, bvert &s
                             light_choice_pdf, light_dir_pdf);
             const v3 wi = normalized(surface - light_pos);
             const float NdotLl = dot(wi, light_normal), NdotLe = dot(wi, EV.snormal);
-            const SimpleHit sh = bd_trace(T, surface, -wi, light_prim, c.bounded ? norm(surface - light_pos) : -1.0f);
+            const SimpleHit sh = bd_trace(T, surface, -wi, light_prim, bd_emitter_bound(c, light_prim, norm(surface - light_pos)));
             if ((sh.prim == light_prim) & (sh.t > EPS_UF)) {
                 const float light_pdf = light_choice_pdf;
                 float pdf;
@@ -441,7 +448,7 @@ TD v3 bd_connect_path(const BdCtx &c, const bpixel &P, const bvert &EV, bvert &s
             light_emission = light_emission * light_shape_visible(s, light_prim, wi, light_normal, light_dist, light_choice_pdf);   // spot / laser (Scene.py:491-516)
             const float NdotLl = dot(wi, light_normal);
             const float NdotLe = dot(wi, EV.snormal);
-            const SimpleHit sh = bd_trace(T, surface, -wi, light_prim, c.bounded ? light_dist : -1.0f);
+            const SimpleHit sh = bd_trace(T, surface, -wi, light_prim, bd_emitter_bound(c, light_prim, light_dist));
             if ((sh.prim == light_prim) & (sh.t > EPS_UF)) {
                 const float light_pdf = light_choice_pdf;
                 float pdf;
@@ -783,6 +790,20 @@ TD void bd_splat(const BdCtx &c, float *rad, int e, int nu, int nv, int p, uint3
     bd_splat_add(rad, q, r);
 }
 
+// The contribution record (tirt_bdpt_record_enable; include/tirt.h): the REC instantiations of k_bd_emitted and k_bd_resolve append one 32-byte record -- frame, source
+// pixel p, target pixel q, e, l, the three values -- per contribution they evaluate with a target on the film, zero or not, in whatever order the lanes get there.  `need`
+// counts every one of them; those beyond `cap` are dropped.  REC is a parameter PACK, empty or <BdRec>: the kernels without it take the arguments they always took and hold
+// no trace of it (one text, `if constexpr` around the store, as k_shade_spec<FEAT, KAT>) -- a bool and a trailing argument would have moved their hidden arguments.
+struct BdRec { float4 *rec; unsigned long long *need; unsigned long long cap; };
+TD void bd_record(const BdRec &R, uint32_t frame, int p, long q, int e, int l, v3 r)
+{
+    const unsigned long long k = atomicAdd(R.need, 1ull);
+    if (k < R.cap) {
+        R.rec[2 * k] = make_float4(__int_as_float((int)frame), __int_as_float(p), __int_as_float((int)q), __int_as_float(e));
+        R.rec[2 * k + 1] = make_float4(__int_as_float(l), r.x, r.y, r.z);
+    }
+}
+
 constexpr int BD_OWNER_BITS = 26;                  // a queued connection's owner word: item | pair slot << 26 (49 slots; a batch holds < 2^26 items)
 
 // BDPT_RGB.py:615-637, the double loop over (e, l), per item: the geometry of every connection.  A pair that needs a visibility ray
@@ -861,8 +882,8 @@ __global__ __launch_bounds__(BD_CONNECT_BLOCK) void k_bd_connect(BdCtx c, BdItem
 
 // The l == 0 pairs (BDPT_RGB.py:489-491): an eye vertex that lies on an emitter contributes its beta, MIS-weighted.  A sub-path ends on
 // the emitter it meets (:152-158), so per item only e = eye_depth can be one; the light sub-path's depth does not matter (l = 0 <= any).
-template <bool SPEC>
-__global__ void k_bd_emitted(BdCtx c, BdItems items, BdSteps steps, TileMap tm, int P, int N, uint32_t frame_begin, float *radiance, long frame_stride)
+template <bool SPEC, class... REC>
+__global__ void k_bd_emitted(BdCtx c, BdItems items, BdSteps steps, TileMap tm, int P, int N, uint32_t frame_begin, float *radiance, long frame_stride, REC... rec)
 {
     const int it = blockIdx.x * blockDim.x + threadIdx.x;
     if (it >= N) return;
@@ -879,6 +900,11 @@ __global__ void k_bd_emitted(BdCtx c, BdItems items, BdSteps steps, TileMap tm, 
     int nu = 0, nv = 0;
     const bvert EV = B.eye[e - 1];
     const v3 r = bd_connect_path<SPEC>(c, B, EV, sample, i, j, e, 0, frame, nu, nv, T);
+    if constexpr (sizeof...(REC) > 0) {
+        v3 rr = r;
+        const long q = bd_splat_target<SPEC>(c, e, nu, nv, p, frame, rr);
+        if (q >= 0) bd_record(rec..., frame, p, q, e, 0, rr);
+    }
     bd_splat<SPEC>(c, radiance + (size_t)f * (size_t)frame_stride, e, nu, nv, p, frame, r);
 }
 
@@ -903,9 +929,9 @@ static_assert(BD_RESOLVE_ITEMS == 128, "k_bd_resolve's list entries hold the ite
 #else
 #define BD_RESOLVE_BOUNDS __launch_bounds__(BD_RESOLVE_ITEMS, BD_RESOLVE_WAVES)
 #endif      // (said so, the compiler schedules the kernel within 128 VGPRs a little better: config 5 + 2 %, three A/B pairs)
-template <bool SPEC>
+template <bool SPEC, class... REC>
 __global__ BD_RESOLVE_BOUNDS void k_bd_resolve(BdCtx c, BdItems items, TileMap tm, int P, int N, uint32_t frame_begin, const int *ibase, const int *icount,
-                             const unsigned long long *qmask, const float4 *shits, const float4 *stage, float *radiance, long frame_stride)
+                             const unsigned long long *qmask, const float4 *shits, const float4 *stage, float *radiance, long frame_stride, REC... rec)
 {
     // the unoccluded connections, item by item: item of the group | pair slot << 7 | queue place from the base of the item's wave on << 13 (< 64 x 20).  One word each: at
     // eight bytes the list alone (20 KB) held a CU to seven blocks
@@ -976,6 +1002,7 @@ __global__ BD_RESOLVE_BOUNDS void k_bd_resolve(BdCtx c, BdItems items, TileMap t
             r = bd_connect_path<SPEC>(c, B, EV, sample, i, j, e, l, frame, nu, nv, T);
             const long q = bd_splat_target<SPEC>(c, e, nu, nv, p, frame, r);
             if (q >= 0) key = (long long)f * (long long)(frame_stride / 3) + q;
+            if constexpr (sizeof...(REC) > 0) { if (q >= 0) bd_record(rec..., frame, p, q, e, l, r); }            // what bd_splat_target left, before the pre-sum below
           }
           // The e >= 2 connections of an item all add to the item's own pixel and sit in neighbouring lanes: one atomic per run of equal targets instead of one per
           // connection (a third of the atomics; the kernel is 19 % faster without any).  A run's sum is formed pairwise, so the film differs from per-connection
@@ -1104,6 +1131,10 @@ int bdpt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t see
     DevCounters *ctr = c->dev_counters.as<DevCounters>();
     TileMap tm = {c->tile_rank, c->tile_count, c->tile_size, c->H, c->tile_blocked, 0};
     const int B = 128;
+    const bool rec_on = c->bd_rec_cap >= 0 && c->bd_rec.p;
+    BdRec rec = {nullptr, nullptr, 0ull};
+    if (rec_on) { rec.need = c->bd_rec.as<unsigned long long>(); rec.rec = (float4 *)((char *)c->bd_rec.p + 32); rec.cap = (unsigned long long)c->bd_rec_cap; }
+    c->bd_last.batches = 0;
     // everything queued on the main stream so far precedes the lanes' work
     if (NL > 1) { TIRT_HIP(hipEventRecord(c->ev_main, c->stream)); for (int l = 0; l < NL; l++) TIRT_HIP(hipStreamWaitEvent(c->lanes[l].stream, c->ev_main, 0)); }
     hipEvent_t last_delta = nullptr, last_film = nullptr;
@@ -1165,14 +1196,15 @@ int bdpt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t see
         hipLaunchKernelGGL(k_bd_compact, dim3((N + B - 1) / B), dim3(B), 0, st, N, ibase, icount, qlist, scount, &ctr->rays_shadow);
         tj.query = true; tj.ray4 = stage; tj.ray_index = qlist; tj.count = (int)(SCAP < (size_t)N * BD_RAY_PAIRS ? SCAP : (size_t)N * BD_RAY_PAIRS); tj.count_ptr = scount; tj.hit = shits;
         if (int rc = trace_rays(c, tj)) return rc;
-        if (spectral) hipLaunchKernelGGL(k_bd_emitted<true>, dim3((N + B - 1) / B), dim3(B), 0, st, bc, items, state, tm, P, N, frame0, bl.rad.as<float>(), 3 * NP);
-        else hipLaunchKernelGGL(k_bd_emitted<false>, dim3((N + B - 1) / B), dim3(B), 0, st, bc, items, state, tm, P, N, frame0, bl.rad.as<float>(), 3 * NP);
         {
+            if (rec_on) hipLaunchKernelGGL((spectral ? k_bd_emitted<true, BdRec> : k_bd_emitted<false, BdRec>), dim3((N + B - 1) / B), dim3(B), 0, st, bc, items, state, tm, P, N, frame0, bl.rad.as<float>(), 3 * NP, rec);
+            else hipLaunchKernelGGL(spectral ? k_bd_emitted<true> : k_bd_emitted<false>, dim3((N + B - 1) / B), dim3(B), 0, st, bc, items, state, tm, P, N, frame0, bl.rad.as<float>(), 3 * NP);
             size_t rg = ((size_t)N + BD_RESOLVE_ITEMS - 1) / BD_RESOLVE_ITEMS;            // grid-stride over groups of BD_RESOLVE_ITEMS items
             if (rg > 8192) rg = 8192;
-            if (spectral) hipLaunchKernelGGL(k_bd_resolve<true>, dim3((unsigned)rg), dim3(BD_RESOLVE_ITEMS), 0, st, bc, items, tm, P, N, frame0, ibase, icount, qmask, shits, stage, bl.rad.as<float>(), 3 * NP);
-            else hipLaunchKernelGGL(k_bd_resolve<false>, dim3((unsigned)rg), dim3(BD_RESOLVE_ITEMS), 0, st, bc, items, tm, P, N, frame0, ibase, icount, qmask, shits, stage, bl.rad.as<float>(), 3 * NP);
+            if (rec_on) hipLaunchKernelGGL((spectral ? k_bd_resolve<true, BdRec> : k_bd_resolve<false, BdRec>), dim3((unsigned)rg), dim3(BD_RESOLVE_ITEMS), 0, st, bc, items, tm, P, N, frame0, ibase, icount, qmask, shits, stage, bl.rad.as<float>(), 3 * NP, rec);
+            else hipLaunchKernelGGL(spectral ? k_bd_resolve<true> : k_bd_resolve<false>, dim3((unsigned)rg), dim3(BD_RESOLVE_ITEMS), 0, st, bc, items, tm, P, N, frame0, ibase, icount, qmask, shits, stage, bl.rad.as<float>(), 3 * NP);
         }
+        c->bd_last.N = N; c->bd_last.P = P; c->bd_last.frame0 = frame0; c->bd_last.tm = tm;
         if (last_film) TIRT_HIP(hipStreamWaitEvent(st, last_film, 0));        // the running mean applies the frames in order
         for (int f = 0; f < F; f++) {
             const float coff = 1.0f / ((float)(int)(frame0 + (uint32_t)f) + 1.0f);
@@ -1187,7 +1219,84 @@ int bdpt_render(tirt_ctx *c, uint32_t frame_begin, int frame_count, uint32_t see
         TIRT_HIP(hipStreamWaitEvent(c->stream, c->bd[l].delta_done, 0));
     }
     TIRT_HIP(hipGetLastError());
+    c->bd_last.batches = batch;
     return TIRT_OK;
 }
 
+// (frame, pixel) of every item of a batch, by the kernels' own numbering: tirt_bdpt_vertices_download's, never part of a render
+__global__ void k_bd_item_ids(TileMap tm, int P, int N, uint32_t frame_begin, int *out)
+{
+    const int it = blockIdx.x * blockDim.x + threadIdx.x;
+    if (it >= N) return;
+    int f, k; slot_to_frame_pixel(tm, P, it, f, k);
+    out[2 * it] = (int)(frame_begin + (uint32_t)f); out[2 * it + 1] = local_to_pixel(tm, k);
+}
+
 }  // namespace tirt
+
+using namespace tirt;
+
+extern "C" {
+
+int tirt_bdpt_record_enable(tirt_ctx *c, long capacity)
+{
+    TIRT_REQUIRE(c, "tirt_bdpt_record_enable: null context");
+    TIRT_REQUIRE(capacity < ((long)1 << 40), "tirt_bdpt_record_enable: capacity out of range");
+    if (sync_all(c)) return TIRT_ERR_HIP;
+    if (capacity < 0) { c->bd_rec_cap = -1; c->bd_rec.release(); return TIRT_OK; }
+    c->bd_rec_cap = -1;
+    if (c->bd_rec.ensure(32 + sizeof(float4) * 2 * (size_t)capacity)) return TIRT_ERR_HIP;
+    TIRT_HIP(hipMemsetAsync(c->bd_rec.p, 0, 32, c->stream));
+    TIRT_HIP(hipStreamSynchronize(c->stream));
+    c->bd_rec_cap = capacity;
+    return TIRT_OK;
+}
+
+int tirt_bdpt_record_download(tirt_ctx *c, void *records, long capacity, long *needed)
+{
+    TIRT_REQUIRE(c && needed, "tirt_bdpt_record_download: null pointer");
+    TIRT_REQUIRE(c->bd_rec_cap >= 0 && c->bd_rec.p, "tirt_bdpt_record_download: the record is not enabled (tirt_bdpt_record_enable)");
+    TIRT_REQUIRE(capacity >= 0 && (records || capacity == 0), "tirt_bdpt_record_download: bad capacity or null buffer");
+    if (sync_all(c)) return TIRT_ERR_HIP;
+    unsigned long long need = 0;
+    TIRT_HIP(hipMemcpy(&need, c->bd_rec.p, sizeof(need), hipMemcpyDeviceToHost));
+    long n = need < (unsigned long long)c->bd_rec_cap ? (long)need : c->bd_rec_cap;          // what the kernels kept
+    if (n > capacity) n = capacity;
+    if (n > 0) TIRT_HIP(hipMemcpy(records, (const char *)c->bd_rec.p + 32, sizeof(float4) * 2 * (size_t)n, hipMemcpyDeviceToHost));
+    *needed = (long)need;
+    return TIRT_OK;
+}
+
+int tirt_bdpt_vertices_download(tirt_ctx *c, int32_t *item_rows, void *vertices, long capacity, long *items_out)
+{
+    TIRT_REQUIRE(c && items_out, "tirt_bdpt_vertices_download: null pointer");
+    if (sync_all(c)) return TIRT_ERR_HIP;
+    TIRT_REQUIRE(c->bd_last.batches >= 1 && c->bdpt_px.p && c->bd[0].items.p, "tirt_bdpt_vertices_download: no BDPT call has rendered into this film");
+    TIRT_REQUIRE(c->bd_last.batches == 1, "tirt_bdpt_vertices_download: the last BDPT call ran as more than one batch (render fewer frames per call or raise bdpt_batch_items)");
+    const size_t N = (size_t)c->bd_last.N;
+    *items_out = (long)N;
+    if (capacity <= 0) return TIRT_OK;               // asked for the number of items alone
+    TIRT_REQUIRE((size_t)capacity >= N && item_rows && vertices, "tirt_bdpt_vertices_download: buffers smaller than the batch");
+    TIRT_REQUIRE(c->bd[0].items.bytes >= BD_ITEM_BYTES * N && c->bd[0].state.bytes >= BD_STEP_BYTES * N, "tirt_bdpt_vertices_download: batch state released");
+    std::vector<float4> q(N * (size_t)(BD_SLOTS * BD_QUADS));
+    std::vector<int> ed(N), ld(N), ids(2 * N);
+    const BdSteps S = bd_steps(c->bd[0].state.p, N);
+    TIRT_HIP(hipMemcpy(q.data(), c->bd[0].items.p, BD_ITEM_BYTES * N, hipMemcpyDeviceToHost));
+    TIRT_HIP(hipMemcpy(ed.data(), S.ed, sizeof(int) * N, hipMemcpyDeviceToHost));
+    TIRT_HIP(hipMemcpy(ld.data(), S.ld, sizeof(int) * N, hipMemcpyDeviceToHost));
+    DevBuf tmp;
+    if (tmp.ensure(sizeof(int) * 2 * N)) return TIRT_ERR_HIP;
+    hipLaunchKernelGGL(k_bd_item_ids, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, c->stream, c->bd_last.tm, c->bd_last.P, (int)N, c->bd_last.frame0, tmp.as<int>());
+    hipError_t e = hipMemcpyAsync(ids.data(), tmp.p, sizeof(int) * 2 * N, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    tmp.release();
+    TIRT_HIP(e);
+    float4 *out = (float4 *)vertices;
+    for (size_t it = 0; it < N; it++) {
+        item_rows[4 * it] = ids[2 * it]; item_rows[4 * it + 1] = ids[2 * it + 1]; item_rows[4 * it + 2] = ed[it]; item_rows[4 * it + 3] = ld[it];
+        for (size_t sk = 0; sk < (size_t)(BD_SLOTS * BD_QUADS); sk++) out[it * (size_t)(BD_SLOTS * BD_QUADS) + sk] = q[sk * N + it];          // BdItems: quad k of slot s of item `it` at (s * 5 + k) * stride + it
+    }
+    return TIRT_OK;
+}
+
+}  // extern "C"

@@ -430,6 +430,10 @@ struct tirt_ctx {
     size_t bdpt_mem_budget = 0;                    // option "bdpt_mem_budget" (bytes, 0 = off): upper bound on what a BDPT call may take for its batch state, as if the device had only that much free (tests)
     int bdpt_stack = 64;                           // option "bdpt_stack_size": traversal stack entries of BDPT's rays (BDPT.__init__'s stack_size; LDS part + paged spill)
     int bdpt_bounded = 1;                          // option "bdpt_bounded": connection rays stop at their target distance
+    // tirt_bdpt_record_enable: 32 bytes of header (the count that was needed, 64 bits) + bd_rec_cap records of 32 bytes; bd_rec_cap < 0: off, the kernels launched are the ones without the store
+    tirt::DevBuf bd_rec; long bd_rec_cap = -1;
+    // what the last BDPT call left in bd[0] (tirt_bdpt_vertices_download): how many batches it ran as, and the last batch's items, local pixels, first frame and item numbering
+    struct { int batches = 0, N = 0, P = 0; uint32_t frame0 = 0; tirt::TileMap tm = {}; } bd_last;
 
     // primary visibility through pixel beams (tirt_pvb.hip): per local pixel the leaves its camera rays can hit first, made once per (build, camera, film)
     struct PvbKey { tirt::CameraView cam; unsigned long long build; int W, H, tile_rank, tile_count, tile_size, tile_blocked, P, edges; } pvb_key;
