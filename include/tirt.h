@@ -1199,6 +1199,63 @@ int tirt_signed_distance_prepare(tirt_ctx *ctx, int64_t report[5]);
 int tirt_signed_distance_table_download(tirt_ctx *ctx, float *out);
 int tirt_kat_signed_distance(tirt_ctx *ctx, const float *in, int n, float *out);
 
+/* Winding number (no reference counterpart; csrc/tirt_winding.hip, the terms in csrc/tirt_winding.h): the generalized winding number of Jacobson et al.
+ * 2013, w(q) = (1 / 4 pi) sum_t Omega_t(q), evaluated with the far-field expansion of Barill et al. 2018 ("Fast winding numbers for soups and clouds",
+ * orders 0 and 1) over the quantised 4-wide nodes.  0 or 1 for a closed mesh, smooth near holes, additive over overlapping shells; w > 0.5 is the inside
+ * test that survives open, flipped and self-intersecting meshes, where the pseudo-normal sign of "Signed distance" flips behind every hole.
+ * All fp32 unless stated, every operation in the order written, no contraction, dot and cross as above; tm_sqrt / tm_atan2 are csrc/tirt_math.h's.
+ * Triangle term, for a query q and a triangle (A, B, C) that is VALID as above (g = cross(B - A, C - A), 0 < dot(g, g) < +inf): a = A - q, b = B - q,
+ *   c = C - q; la = tm_sqrt(dot(a, a)), lb, lc alike; num = dot(a, cross(b, c));
+ *   den = (((la * lb) * lc + dot(a, b) * lc) + dot(a, c) * lb) + dot(b, c) * la;   Omega = 2.0f * tm_atan2(num, den)   (Van Oosterom & Strackee 1983).
+ *   An invalid triangle: Omega = 0.  Positive where the normal g points away from q.  A query on the triangle's plane is not special-cased: num is 0 where
+ *   the arithmetic makes it so (an axis-aligned face), den > 0 outside the triangle and < 0 inside it, tm_atan2(+-0, den < 0) = +pi (tirt_math.h does not
+ *   distinguish signed zeros): 0 outside, +2 pi -- half a turn -- inside, on either orientation.  q at a corner: tm_atan2(0, 0) = 0.
+ * Analytic sphere with centre Cs and radius R: pc = q - Cs, len = tm_sqrt(dot(pc, pc)); Omega = len < R ? 12.566370614359172f : 0.  Spots and lasers: 0.
+ * Quantisation: I(x) = (int64) rintf(x * 1073741824.0f) if |x * 1073741824.0f| < 2^62, else 0 (a NaN or overflowed term counts as nothing; an exact term
+ *   is at most 2 pi (1 + 2^-22), so 2^24 primitives sum to less than 2^24 * 2^33 = 2^57 < 2^63).  The terms of a query are added in 64-bit integers: the
+ *   sum S does not depend on the order of the visits, nor on how the build's atomics numbered the nodes.
+ * The answer: w = ((float) S * 9.313225746154785e-10f) * 0.07957747154594767f (round to nearest: 2^-30, then 1 / 4 pi).  A query with a NaN or infinite
+ *   coordinate answers NaN and adds nothing.  Alpha cut-outs are ignored as above.
+ * The moment table: one row of 16 floats per (4-wide node, child slot) whose code names an inner node (index 4 * node + slot; all other rows are zero), over
+ *   the valid triangles beneath that child.  ext = max_k(cell[k]) * 60000.0f = m 2^e with 0.5 <= m < 1 (e = the exponent field of ext - 126);
+ *   s2 = 2^(37 - 2 e), s3 = 2^(37 - 3 e).  A position relative to grid_min is below 2^(e - 1) in magnitude and |g| / 2 below 1.5 * 2^(2 e), so every scaled
+ *   term below is under 1.5 * 2^37 and 2^24 of them under 2^62.  Per triangle: h = 0.5f * g per component; ar = 0.5f * tm_sqrt(dot(g, g));
+ *   cen = (((A - grid_min) + (B - grid_min)) + (C - grid_min)) * 0.3333333432674408f per component; J(x, s) = (int64) rint((double) x * s) in float64 (0 if the
+ *   product is NaN or reaches 2^62).  The sixteen 64-bit sums: J(h.x, s2), J(h.y, s2), J(h.z, s2); J(ar, s2); J(ar * cen.k, s3), k = x, y, z;
+ *   J(cen.i * h.j, s3), row-major in (i, j).  Integer sums over a set: the table is a function of the tree's structure alone.
+ *   The row, in float64 with + - * / only and one rounding to fp32 per word: area = (double) S3 / s2 (as a product with 2^(2 e - 37)), N_j = S_j / s2,
+ *   M_ij = S_(7 + 3 i + j) / s3; if S3 > 0: p_k = (S_(4 + k) / s3) / area and p~_k = (float)(p_k + (double) grid_min[k]), else p_k = 0 and
+ *   p~_k = 0.5f * (mn_k + mx_k) of the slot's decoded box (mn_k = grid_min[k] + (float) h_lo * cell[k], mx_k alike from the slot's two fp16 planes: the decode
+ *   of the closest-point walk); C_ij = (float)(M_ij - p_i * N_j).  r2 in fp32: f_k = max(|p~_k - mn_k|, |mx_k - p~_k|), r2 = (f_x * f_x + f_y * f_y) + f_z * f_z:
+ *   the squared distance from p~ to the farthest corner of the decoded box.  Row words: p~ (3), r2, N (3), C (9, row-major).
+ * The walk starts at the root (a one-primitive scene: at its leaf).  Per child slot of a node: empty -- skipped; a leaf -- its primitive's term, always;
+ *   an inner child with row (p~, r2, N, C): d = p~ - q per component, d2 = dot(d, d); iff d2 > (beta * beta) * r2 as computed numbers it is APPROXIMATED:
+ *   s = tm_sqrt(d2), d3 = d2 * s, t0 = dot(N, d) / d3, tr = (C00 + C11) + C22, cd_i = dot(row i of C, d), t1 = tr / d3 - (3.0f * dot(d, cd)) / (d2 * d3),
+ *   and I(t0) + I(t1) is added; else it is descended.  beta >= 1, or +inf (the comparison is then never true: the exact sum); anything else is
+ *   TIRT_ERR_ARG.  An analytic sphere beneath an approximated child adds nothing, rightly: q is outside the ball about p~ that holds the child's box.
+ *   Nothing is sorted or culled.  Stack: 4-byte entries, the first 16 in LDS; an entry beyond stack_size loses a subtree: that query answers NaN and
+ *   counts in stack_overflow (tirt_stats: TIRT_ERR_STACK).  TIRT_TRAVERSE_EXHAUSTIVE: every primitive in id order, no table use (beta is checked, not used).
+ *   TIRT_COUNT_NODES: counts[2 q] = child slots examined (4 per node visited), counts[2 q + 1] = leaves evaluated (the scan: 0 and n).
+ * The table is context state, built ON THE DEVICE by the first winding call after tirt_scene_upload, tirt_vertex_update[_device] or tirt_lbvh_build dropped
+ *   it: bottom-up, one launch per level of the 4-wide tree, then one launch for the rows; on the context's stream, inside the query's own ordering, no
+ *   host sync (allocating it, on first use or for a larger scene, waits for the context's stream as growing any scratch buffer does).
+ * tirt_query_winding_number: points (row q at points + q * point_stride, point_stride >= 3) and out_w[n] in device memory, optional counts[2 n] (8-byte
+ *   aligned), the caller's stream; chunks, flags and refusals as tirt_query_closest_point.  n == 0 queues nothing.
+ * tirt_winding_number: host arrays (points[n * 3], out_w[n], counts or NULL), staged and synchronous.
+ * tirt_winding_prepare: builds the table now unless it stands, and waits.
+ * tirt_winding_table_download: the same, then table[wide_nodes * 64] floats and sums[wide_nodes * 16] (the sums of everything beneath each NODE) where not
+ *   NULL, and info[0] = wide_nodes, info[1] = e.
+ * tirt_kat_winding: rows of 12 floats (q3, A3, B3, C3) or, with is_sphere, 7 (q3, Cs3, R) through the same device functions to rows of four 32-bit words:
+ *   the bits of Omega, the bits of the w of that term alone, I(Omega) low word, high word.
+ * tirt_kat_winding_host: host only, no context: the same rows through the same text compiled for the host. */
+int tirt_query_winding_number(tirt_ctx *ctx, const float *points, int64_t n, int64_t point_stride, float beta, int stack_size, int flags,
+                              float *out_w, int32_t *counts, void *stream);
+int tirt_winding_number(tirt_ctx *ctx, const float *points, int n, float beta, int stack_size, int flags, float *out_w, int32_t *counts);
+int tirt_winding_prepare(tirt_ctx *ctx);
+int tirt_winding_table_download(tirt_ctx *ctx, float *table, int64_t *sums, int32_t info[2]);
+int tirt_kat_winding(tirt_ctx *ctx, const float *in, int n, int is_sphere, uint32_t *out);
+int tirt_kat_winding_host(const float *in, int n, int is_sphere, uint32_t *out);
+
 /* Multi-GPU without a Python framework in the loop (the reference has nothing here): ONE host thread drives
  * ndev contexts, one per device of the node, each created with tirt_film_create(..., tile_rank = i, tile_count = ndev, ...).
  * tirt_comm_init builds one RCCL communicator over them (librccl is loaded on first use); tirt_film_reduce sums the films

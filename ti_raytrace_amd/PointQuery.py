@@ -4,7 +4,8 @@
     q = PointQuery(scene, stack_size=64, flags=0)         # scene after setup_data_gpu() (Example.build_scene)
     h = q.closest(points, max_distance=None, attributes=False)      # PointHits(dist2 [N] f32, prim [N] i32, point [N, 3] or None, uv [N, 2] or None)
     s = q.signed_distance(points, max_distance=None, attributes=False)      # SignedHits(dist [N] f32, prim, point, uv): dist < 0 inside
-    m = q.inside(points)                                  # [N] bool
+    m = q.inside(points, method="pseudonormal")           # [N] bool; method="winding": winding_number(points) > 0.5
+    wn = q.winding_number(points, beta=2.0)               # [N] f32: the generalized winding number (1 inside, 0 outside, in between near holes)
     nn = q.nearest(points, k, max_distance=None, attributes=False, count=False)      # PointNearest(dist2 [N, k], prim [N, k], point, uv, count [N] or None)
     c = q.count_within(points, max_distance)              # [N] int32: the primitives within max_distance of each point
     w = q.within(points, max_distance, attributes=False, capacity=None, ordered=True)      # PointPairs(row_start [N + 1] i64, prim, dist2, point, uv): CSR rows; w.query() = the query index per pair
@@ -25,6 +26,12 @@ give a bound with it.  ``count_within`` is the count alone.
 distance"): ``dist = -sqrt(dist2)`` inside a closed, consistently oriented mesh or an analytic sphere, ``+sqrt(dist2)`` outside and on the surface,
 ``inf`` where nothing is found.  The first signed call after the geometry changed builds the table of pseudo-normals on the device, on the same stream
 (no host sync); ``mesh_report()`` builds it at once, waits, and says whether the meshes are closed -- on an open mesh the sign is "which side of the sheet".
+
+``winding_number`` is the generalized winding number (include/tirt.h, "Winding number"): the sum of the signed solid angles of all triangles over 4 pi --
+1 inside a closed mesh, 0 outside, fractional near a hole, 2 inside two overlapping shells -- with far clusters of triangles replaced by two terms from
+their moments where the cluster is more than ``beta`` of its radii away (``beta >= 1``; ``float("inf")``: the exact sum).  ``w > 0.5`` is the inside test
+for meshes that ``mesh_report()`` calls open: ``inside(points, method="winding")``.  The first winding call after the geometry changed builds the moment
+table on the device, on the same stream (no host sync).
 """
 import collections
 import operator
@@ -253,9 +260,40 @@ class PointQuery:
         written, row_start is complete, and row_start[-1] > c says the result was cut (what lies behind the last row that fits is uninitialised)."""
         return _pairs_front(self, "within", False, points, max_distance, attributes, capacity, ordered)
 
-    def inside(self, points):
-        """[N] bool: signed_distance(points).dist < 0"""
-        return self.signed_distance(points).dist < 0
+    def inside(self, points, method="pseudonormal"):
+        """[N] bool: signed_distance(points).dist < 0, or with method="winding": winding_number(points) > 0.5 (open, flipped or intersecting meshes)"""
+        if method == "pseudonormal":
+            return self.signed_distance(points).dist < 0
+        if method == "winding":
+            return self.winding_number(points) > 0.5
+        raise ValueError('PointQuery.inside: method is "pseudonormal" or "winding", got %r' % (method,))
+
+    def _winding(self, points, beta, what, count):
+        torch = self.torch
+        try:
+            beta = float(beta)
+        except (TypeError, ValueError):
+            raise TypeError("PointQuery.%s: beta must be a float, got %s" % (what, type(beta).__name__)) from None
+        if not beta >= 1.0:
+            raise ValueError("PointQuery.%s: beta must be >= 1 or inf, got %r" % (what, beta))
+        dev, n, stride = self._check_points(points, what)
+        w = torch.empty(n, dtype=torch.float32, device=dev)
+        counts = torch.empty((n, 2), dtype=torch.int32, device=dev) if count else None
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            self.scene.ctx.query_winding_number(points.data_ptr(), n, stride, w.data_ptr(), beta=beta, stack_size=self.stack_size,
+                                                flags=self.flags | (_native.COUNT_NODES if count else 0), counts=counts.data_ptr() if count else 0,
+                                                stream=stream)
+        return w, counts
+
+    def winding_number(self, points, beta=2.0):
+        """[N] float32: the generalized winding number of every query, bit for bit Context.winding_number's (NaN for a query with a NaN or infinite
+        coordinate, or one that ran out of traversal stack).  Asynchronous on the current stream."""
+        return self._winding(points, beta, "winding_number", False)[0]
+
+    def winding_counts(self, points, beta=2.0):
+        """winding_number() with the per-query counts ([N, 2] int32: child slots examined, leaves evaluated) of a COUNT_NODES walk: (w, counts)"""
+        return self._winding(points, beta, "winding_counts", True)
 
     def mesh_report(self):
         """Builds the pseudo-normal table now and waits for it: the counts of triangle edges that are boundary, non-manifold and flipped, of invalid

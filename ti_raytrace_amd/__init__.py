@@ -2,7 +2,7 @@
 
 Modules keep the reference's names: ``SceneData``, ``Scene``, ``Camera``, ``LBvh``,
 ``PT_RGB``, ``Debug``, ``UtilsFunc``, ``Texture``, ``Example`` (+ ``scenes`` with the example set-ups, ``RayQuery``: closest-hit / occlusion
-queries on rays in PyTorch device tensors, ``PointQuery``: the nearest surface point, the signed distance, the k nearest primitives and all primitives within a radius of points in such tensors, ``TriangleQuery``: the closest points, the contact test and the contact pair list between triangles in such tensors and the scene, ``SweepQuery``: the first contact of a moving sphere with the scene for sweeps in such tensors, and ``denoise`` / ``denoise_var``: the a-trous denoiser of ``PathTrace.denoise()`` / ``denoise_var()`` on PyTorch device tensors).
+queries on rays in PyTorch device tensors, ``PointQuery``: the nearest surface point, the signed distance, the winding number, the k nearest primitives and all primitives within a radius of points in such tensors, ``TriangleQuery``: the closest points, the contact test and the contact pair list between triangles in such tensors and the scene, ``SweepQuery``: the first contact of a moving sphere with the scene for sweeps in such tensors, and ``denoise`` / ``denoise_var``: the a-trous denoiser of ``PathTrace.denoise()`` / ``denoise_var()`` on PyTorch device tensors).
 The compute path is ``csrc/libtirt.so`` (hand-written HIP for gfx950) behind the C-ABI of
 ``include/tirt.h``; see DESIGN.md / INTEGRATION.md.
 """

@@ -226,6 +226,12 @@ SIGNATURES = {
     "tirt_signed_distance_prepare": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "tirt_signed_distance_table_download": (C.c_int, [_vp, _f32p]),
     "tirt_kat_signed_distance": (C.c_int, [_vp, _f32p, C.c_int, _f32p]),
+    "tirt_query_winding_number": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "tirt_winding_number": (C.c_int, [_vp, _f32p, C.c_int, C.c_float, C.c_int, C.c_int, _vp, _vp]),
+    "tirt_winding_prepare": (C.c_int, [_vp]),
+    "tirt_winding_table_download": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "tirt_kat_winding": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, _vp]),
+    "tirt_kat_winding_host": (C.c_int, [_f32p, C.c_int, C.c_int, _vp]),
     "tirt_comm_init": (C.c_int, [C.POINTER(_vp), C.c_int]),
     "tirt_film_reduce": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int]),
     "tirt_comm_destroy": (C.c_int, [C.POINTER(_vp), C.c_int]),
@@ -1207,6 +1213,42 @@ class Context:
         check(lib().tirt_kat_signed_distance(self.handle, rows.reshape(-1), rows.shape[0], out.reshape(-1)))
         return out
 
+    def query_winding_number(self, points, n, point_stride, out_w, beta=2.0, stack_size=64, flags=0, counts=0, stream=0):
+        """tirt_query_winding_number on device memory (include/tirt.h, "Winding number"); the first call after the geometry changed builds the moment
+        table on the context's stream.  ti_raytrace_amd.PointQuery is the torch front end."""
+        check(lib().tirt_query_winding_number(self.handle, _vp(int(points) or None), int(n), int(point_stride), float(beta), int(stack_size), int(flags),
+                                              _vp(int(out_w) or None), _vp(int(counts) or None), _vp(int(stream) or None)))
+
+    def winding_number(self, points, beta=2.0, stack_size=64, flags=0):
+        """tirt_winding_number, the host route: points (n, 3) -> w (n,) float32, or (w, counts (n, 2) int32) with COUNT_NODES"""
+        points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = points.shape[0]
+        w = np.zeros(n, np.float32)
+        counts = np.zeros((n, 2), np.int32) if (flags & COUNT_NODES) else None
+        check(lib().tirt_winding_number(self.handle, points.reshape(-1), n, float(beta), int(stack_size), int(flags), _ptr(w), _ptr(counts)))
+        return (w, counts) if counts is not None else w
+
+    def winding_prepare(self):
+        """tirt_winding_prepare: builds the moment table now (unless it stands) and waits"""
+        check(lib().tirt_winding_prepare(self.handle))
+
+    def winding_table(self):
+        """tirt_winding_table_download -> (table (wide_nodes, 4, 16) float32: per node and child slot p~ 3, r2, N 3, C 9; sums (wide_nodes, 16) int64: the
+        integer moments of everything beneath each node; e: the exponent of the scales)"""
+        info = np.zeros(2, np.int32)
+        check(lib().tirt_winding_table_download(self.handle, None, None, _ptr(info)))
+        table = np.zeros((int(info[0]), 4, 16), np.float32); sums = np.zeros((int(info[0]), 16), np.int64)
+        check(lib().tirt_winding_table_download(self.handle, _ptr(table), _ptr(sums), _ptr(info)))
+        return table, sums, int(info[1])
+
+    def kat_winding(self, rows, is_sphere=False):
+        """include/tirt.h, tirt_kat_winding: rows (n, 12) (q, A, B, C) or (n, 7) (q, centre, r) -> (omega (n,) float32, w (n,) float32, I (n,) int64)"""
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, KAT_WINDING_ROWS[bool(is_sphere)])
+        out = np.zeros((rows.shape[0], 4), np.uint32)
+        if rows.shape[0]:
+            check(lib().tirt_kat_winding(self.handle, rows.reshape(-1), rows.shape[0], 1 if is_sphere else 0, _ptr(out)))
+        return _kat_winding_out(out)
+
     def bvh_info(self):
         out = (C.c_uint64 * 4)()
         check(lib().tirt_bvh_info(self.handle, out))
@@ -1371,6 +1413,22 @@ def kat_tri_tri_host(rows, what=0):
     if rows.shape[0]:
         check(lib().tirt_kat_tri_tri_host(rows.reshape(-1), rows.shape[0], int(what), out.reshape(-1)))
     return out
+
+
+KAT_WINDING_ROWS = {False: 12, True: 7}                             # tirt_kat_winding[_host]: floats per input row of a triangle / an analytic sphere
+
+
+def _kat_winding_out(out):
+    return out[:, 0].copy().view(np.float32), out[:, 1].copy().view(np.float32), np.ascontiguousarray(out[:, 2:4]).view(np.int64).reshape(-1)
+
+
+def kat_winding_host(rows, is_sphere=False):
+    """include/tirt.h, tirt_kat_winding_host (host only, no context): Context.kat_winding's rows through the same text compiled for the host"""
+    rows = np.ascontiguousarray(rows, np.float32).reshape(-1, KAT_WINDING_ROWS[bool(is_sphere)])
+    out = np.zeros((rows.shape[0], 4), np.uint32)
+    if rows.shape[0]:
+        check(lib().tirt_kat_winding_host(rows.reshape(-1), rows.shape[0], 1 if is_sphere else 0, _ptr(out)))
+    return _kat_winding_out(out)
 
 
 KAT_SWEEP_ROWS = {False: 18, True: 13}                              # tirt_kat_sweep[_host]: floats per input row of a triangle / an analytic sphere

@@ -431,7 +431,7 @@ void tirt_destroy(tirt_ctx *c)
     DevBuf *bufs[] = {&c->vertex, &c->primitive, &c->material, &c->shape, &c->light, &c->env, &c->tex, &c->cut_uv, &c->cut_flags, &c->mat_lrgb, &c->shade_rec, &c->light_rec, &c->morton_unsorted, &c->keys_a,
                       &c->keys_b, &c->vals_a, &c->vals_b, &c->hist, &c->morton_sorted, &c->bvh_node, &c->compact, &c->parent,
                       &c->flag, &c->subtree, &c->build_status, &c->leaf_compact, &c->wnode, &c->tri, &c->prim_slot, &c->cnode, &c->cparent, &c->csize, &c->wide_queue, &c->wide_levels, &c->sah_compact, &c->sah_csize, &c->sah_parent, &c->wide_dp, &c->sah_box, &c->sah_idx, &c->sah_tasks, &c->sah_counts, &c->hdr, &c->rgb, &c->aov, &c->mom, &c->mom_cnt, &c->pixset, &c->pixset_tmp, &c->tp_mem, &c->mv_rec, &c->mv_snap, &c->dn_mem, &c->dn_out,
-                      &c->counters_mem, &c->spill, &c->trace_stage, &c->debug_mem, &c->query_mem, &c->sd_tab, &c->sd_state, &c->dyn_mem, &c->dev_counters, &c->bdpt_px, &c->bd_rec, &c->timeline, &c->pvb_set[0].count, &c->pvb_set[0].cand, &c->pvb_set[0].bound, &c->pvb_set[1].count, &c->pvb_set[1].cand, &c->pvb_set[1].bound, &c->pvb_stat, &c->pvb_tmp};
+                      &c->counters_mem, &c->spill, &c->trace_stage, &c->debug_mem, &c->query_mem, &c->sd_tab, &c->sd_state, &c->wn_tab, &c->wn_sums, &c->dyn_mem, &c->dev_counters, &c->bdpt_px, &c->bd_rec, &c->timeline, &c->pvb_set[0].count, &c->pvb_set[0].cand, &c->pvb_set[0].bound, &c->pvb_set[1].count, &c->pvb_set[1].cand, &c->pvb_set[1].bound, &c->pvb_stat, &c->pvb_tmp};
     for (DevBuf *b : bufs) b->release();
     for (auto &bl : c->bd) {
         DevBuf *bb[] = {&bl.items, &bl.state, &bl.rays, &bl.hits, &bl.qidx, &bl.ctr, &bl.rad};
@@ -568,7 +568,7 @@ int tirt_scene_upload(tirt_ctx *c, const float *vertex, int nv, const int32_t *p
         }
     }
     hipStream_t st = c->stream;
-    c->built = false; c->sd_tab_valid = false;
+    c->built = false; c->sd_tab_valid = false; c->wn_tab_valid = false;
     c->tp_valid = false; c->mv_moved = false;  // another world: the temporal history (tirt_temporal.hip) and its snapshot of the vertex rows describe the old one
     if (upload(c->vertex, vertex, sizeof(float) * 9 * (size_t)nv, st)) return TIRT_ERR_HIP;
     if (upload(c->primitive, primitive, sizeof(int) * 3 * (size_t)n, st)) return TIRT_ERR_HIP;

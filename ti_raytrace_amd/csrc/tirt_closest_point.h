@@ -96,7 +96,8 @@ TD float sd_corner_angle(const v3 e1, const v3 e2)
     const v3 x = cross(e1, e2);
     return tm_atan2(tm_sqrt(dot(x, x)), dot(e1, e2));
 }
-TD long long sd_quant(const float x) { return (long long)__builtin_rintf(x * 1073741824.0f); }
+__host__ TD long long sd_quant(const float x) {      // (__host__ too: tirt_kat_winding_host quantises a term through it)
+ return (long long)__builtin_rintf(x * 1073741824.0f); }
 constexpr int SD_ROWS = 7;                   // float4 per primitive id: interior, A, B, C, AB, AC, BC
 
 }  // namespace tirt

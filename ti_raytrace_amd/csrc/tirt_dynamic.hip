@@ -192,7 +192,7 @@ static int dyn_apply(tirt_ctx *c, const char *fn, int64_t first, int64_t count, 
     float hb[6];
     TIRT_HIP(hipMemcpyAsync(hb, box, sizeof(hb), hipMemcpyDeviceToHost, st));
     // from here on the old build describes geometry that is gone, whatever the copy and the sync below return
-    c->built = false; c->built_sah = 0; c->shade_rec_valid = false; c->light_rec_valid = false; c->pvb_valid = false; c->sd_tab_valid = false;
+    c->built = false; c->built_sah = 0; c->shade_rec_valid = false; c->light_rec_valid = false; c->pvb_valid = false; c->sd_tab_valid = false; c->wn_tab_valid = false;
     refresh_shade_features(c);                 // (with the tables it selects kernels for; moving vertices changes no bit of it)
     TIRT_HIP(hipStreamSynchronize(st));
     TIRT_HIP(hipGetLastError());

@@ -464,6 +464,11 @@ struct tirt_ctx {
     // sd_tab_valid: the table is the one of the present vertices (dropped by tirt_scene_upload, tirt_vertex_update[_device], tirt_lbvh_build; made again by
     // the first signed query); sd_tab_stack = the stack_size it was built with; sd_tab_checked: the host has read the verdict (nothing was dropped)
     tirt::DevBuf sd_tab, sd_state; bool sd_tab_valid = false, sd_tab_checked = false; int sd_tab_stack = 0;
+    // winding number (tirt_winding.hip): wn_tab = float4[wide_nodes * 4][4], the moment row of every (node, child slot) that names an inner node; wn_sums = the
+    // int64[wide_nodes][16] sums they were made from; wn_tab_valid: the table is the one of the present tree (dropped where sd_tab_valid is; made again by the
+    // first winding call).  wide_level_off[L] = the first node of level L of the 4-wide tree, one entry more than there are levels (build_wide)
+    tirt::DevBuf wn_tab, wn_sums; bool wn_tab_valid = false;
+    std::vector<int> wide_level_off;
     tirt::DevBuf dyn_mem;                         // geometry updates (tirt_dynamic.hip): validation flag, scene box and its block partials, the staged rows of a host update
 
     // RCCL communicator of tirt_comm_init (single-process multi-GPU film reduce; opaque ncclComm_t)
@@ -583,6 +588,7 @@ int query_end(tirt_ctx *c, void *stream);
 // sync); sd_table_verdict waits for the stream and reads what the build said: TIRT_ERR_STACK (and no table) if it dropped a stack entry
 int sd_table_ensure(tirt_ctx *c, int stack_size);
 int sd_table_verdict(tirt_ctx *c, const char *fn);
+int wn_table_ensure(tirt_ctx *c);      // tirt_winding.hip: queues the build of the moment table on c->stream where it does not stand (no host sync)
 int denoise_film(tirt_ctx *c, const tirt_denoise_t *prm, bool var);      // tirt_denoise.hip; var: the variance-guided mode
 int denoise_device(tirt_ctx *c, bool var, const float *hdr, const float *aov, const float *mom, float *out, int W, int H, const tirt_denoise_t *prm, void *stream);
 int denoise_into_film_buffer(tirt_ctx *c, const std::string &fn, const float *hdr, const float *aov, const float *mom, const tirt_denoise_t *prm);

@@ -622,7 +622,7 @@ static int build_wide(tirt_ctx *c, const float *compact, const int *csize, const
         TIRT_HIP(hipEventRecord(c->ev1, st));
         TIRT_HIP(hipMemcpyAsync(host_lv, c->wide_levels.p, sizeof(host_lv), hipMemcpyDeviceToHost, st));
         TIRT_HIP(hipStreamSynchronize(st));
-        if (host_lv[(WIDE_LEVELS_MAX + 2) + level] == 0) { c->wide_nodes = host_lv[level]; break; }       // the next level is empty: done
+        if (host_lv[(WIDE_LEVELS_MAX + 2) + level] == 0) { c->wide_nodes = host_lv[level]; c->wide_level_off.assign(host_lv, host_lv + level + 1); break; }       // the next level is empty: done
         TIRT_REQUIRE(level < WIDE_LEVELS_MAX, "tirt_lbvh_build: the 4-wide tree is deeper than 2048 levels");
     }
     return TIRT_OK;
@@ -656,7 +656,7 @@ int lbvh_build(tirt_ctx *c)
     TIRT_REQUIRE(c->n >= 1, "tirt_lbvh_build: no primitives uploaded");
     const int n = c->n, N = 2 * n - 1;
     hipStream_t st = c->stream, st0 = st;
-    c->built = false; c->built_sah = 0; c->sd_tab_valid = false;      // (the signed-distance table is walked out of the tree's leaves: made again with it)
+    c->built = false; c->built_sah = 0; c->sd_tab_valid = false; c->wn_tab_valid = false;      // (the signed-distance table is walked out of the tree's leaves: made again with it)
     if (c->morton_unsorted.ensure(sizeof(int2) * (size_t)n)) return TIRT_ERR_HIP;
     if (c->morton_sorted.ensure(sizeof(int2) * (size_t)n)) return TIRT_ERR_HIP;
     if (c->keys_a.ensure(sizeof(int) * (size_t)n) || c->keys_b.ensure(sizeof(int) * (size_t)n) ||
@@ -722,7 +722,7 @@ int lbvh_build(tirt_ctx *c)
         gm.g0[k] = c->grid_min[k]; gm.inv_cell[k] = 1.0f / cell; c->grid_inv_cell[k] = gm.inv_cell[k];
     }
     // surface-area collapse of the binary tree into 4-wide nodes, one launch per level of the wide tree (k_wide_level)
-    c->wide_nodes = 0;
+    c->wide_nodes = 0; c->wide_level_off.clear();
     const float *tree = c->compact.as<float>(); const int *tree_size = c->csize.as<int>(), *tree_parent = c->cparent.as<int>();
     // analytic spheres get their own padded box in the traversal tree when there are few of them (far-origin rays enter through chain nodes that
     // hold them with whole-grid boxes: BvhView::far_qcode); otherwise, and on the reference's LBVH, their 4-wide slots span the whole grid as before
